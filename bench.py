@@ -17,6 +17,13 @@ started plainly with --gpus N > 1 it launches that same command itself, before a
 rank i mod N (query.h:1471-1476 has no cross-query state).  No data-path collective for `query`; `topk` ends every
 step with one all-gather of fixed-size [ceil(Q/N), k] (int32 id, f64 score) lists.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, config, and what the timed steps' own counters give: phases, roofline on the GPU schedule's counts,
+walk_bound).  --full adds everything else: the CPU
+baselines, the accuracy check against exact PPR, the push roofline on FIFO counts, the --balanced and dangling variants and,
+in the default configuration, brief runs of BASELINE configs 3-5.  --dump-outputs DIR writes what the last timed step
+computed as .npy files (dump_outputs).
+
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
 """
 import argparse
@@ -69,9 +76,16 @@ def parse(argv=None):
     ap.add_argument("--plumbing-only", action="store_true",
                     help="test hook (tests/test_dist_cpu.py): launcher, sharding, barrier / max-over-ranks timing and the top-k "
                          "gather with gloo on CPU and a stand-in step; no GPU, no engine")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, accuracy, FIFO-count roofline, variants and (default configuration) configs 3-5; "
+                         "without it the --no-* options above are all on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64, < 64 MB)")
     args = ap.parse_args(argv)
     if not args.queries:
         args.queries = DEFAULT_QUERIES.get(args.graph, 1000)
+    if not args.full:  # a plain run measures the headline only
+        args.no_cpu = args.no_accuracy = args.no_variants = args.no_configs = True
     return args
 
 
@@ -307,6 +321,52 @@ def scale_fifo_counts(fifo_pops, fifo_relax, k, stats, tm, q_timed):
             f"counts (FIFO / GPU: pops {rp:.3f}, relaxations {re:.3f})")
 
 
+DUMP_SEED = 20261016
+DUMP_PPR_BYTES = 48 << 20  # the PPR sample's share of the 64 MB the dump may take (stats and top-k lists are the rest)
+
+
+def dump_outputs(args, eng, np, mine, last, topk_out, rank, world):
+    """--dump-outputs DIR: what the last timed step computed, as float64 .npy files, so that two builds can be compared
+    output for output on the same seeded inputs.  With N > 1 ranks, rank r writes DIR/rank<r>/ (its own shard).
+
+    query: the per-query stats the step returned (stats_<field>.npy, one entry per source of the step, in step order),
+    and the PPR estimates of a fixed sample of the step's sources (ppr.npy [rows, cols], ppr_sources.npy; ppr_nodes.npy
+    names the columns when the graph is too large to keep whole rows).  The timed step leaves the PPR vectors in HBM
+    (want_ppr=False), so they are computed again here, one source per call: the RNG contract keys every walk by its
+    source id (include/fora_hip.h), so a source's result does not depend on the batch it runs in -- the stats of each
+    repeat are checked against the step's.
+    top-k: the gathered [Q, k] ids and scores (rank 0) and the rounds of this rank's queries."""
+    out_dir = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+    if args.topk:
+        if rank == 0:
+            save("topk_ids", topk_out["ids"])
+            save("topk_scores", topk_out["sc"])
+        save("topk_rounds", topk_out["rounds"])
+        return
+    fields = [f for f in last.dtype.names if f != "reserved_"]
+    for f in fields:
+        save("stats_" + f, last[f])  # u64 counters above 2^53 (rsum_fix) round; rsum carries the same value
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    rows = np.sort(rng.choice(len(mine), size=min(8, len(mine)), replace=False))
+    cols = None
+    budget = DUMP_PPR_BYTES // world
+    if len(rows) * eng.n * 8 > budget:
+        cols = np.sort(rng.choice(eng.n, size=budget // (8 * len(rows)), replace=False))
+        save("ppr_nodes", cols)
+    ppr = []
+    for i in rows:
+        p, st = eng.query(mine[i:i + 1], with_idx=args.with_idx, want_ppr=True)
+        assert all(st[0][f] == last[i][f] for f in fields), f"source {mine[i]}: stats of the repeat differ from the timed step's"
+        ppr.append(p[0] if cols is None else p[0, cols])
+    save("ppr", np.stack(ppr) if ppr else np.zeros((0, eng.n)))
+    save("ppr_sources", mine[rows])
+
+
 def run_workload(args, ctx, light=False):
     """One workload: graph, engine, warm-up, timed steps, the result object (rank 0; None on the others).
     light: an extra configuration inside the default run -- no CPU legs, no accuracy pass, no variants."""
@@ -377,6 +437,8 @@ def run_workload(args, ctx, light=False):
     dt_local = time.perf_counter() - t0
     dt = max_over_ranks(dt_local, world if use_dist else 1, dev)
     tm = eng.timing()
+    if args.dump_outputs and not light:
+        dump_outputs(args, eng, np, mine, last, topk_out, rank, world)
     shard = f"sources i mod {world}"
     qdesc = (f"query_size={args.queries}/GPU" if args.scaling == "weak" else f"query_size={args.queries} in total ({shard})")
     # evidence of the N > 1 run in the line itself: what torch.distributed saw, and the spread over the ranks
@@ -504,7 +566,7 @@ def run_workload(args, ctx, light=False):
             p_fifo, e_fifo, counts_from = scale_fifo_counts(pp, pr, pn, last, tm, q_timed)
             if world > 1:
                 out["cpu_baseline"] = None
-                out["cpu_baseline_note"] = "the CPU port is timed at N = 1 only (default `python bench.py`)"
+                out["cpu_baseline_note"] = "the CPU port is timed at N = 1 only (`python bench.py --full`)"
         else:
             fr = fifo_ratio_file(args.graph)
             if fr:

@@ -18,7 +18,8 @@ def _run(cmd):
 
 
 def test_bench_contract_small_graph():
-    d = _run([sys.executable, "bench.py", "--graph", "small", "--queries", "64", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"])
+    d = _run([sys.executable, "bench.py", "--graph", "small", "--queries", "64", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2",
+              "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -36,12 +37,36 @@ def test_bench_contract_small_graph():
 def test_bench_topk_and_torchrun_rank():
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
               "--master-port", "29633", "bench.py", "--gpus", "1", "--graph", "small", "--queries", "32", "--topk", "50", "--with-idx",
-              "--steps", "1", "--warmup", "1", "--scaling", "strong"])
+              "--steps", "1", "--warmup", "1", "--scaling", "strong", "--full"])
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["config"]["k"] == 50 and d["value"] > 0
     assert d["config"]["gather_bytes_per_step"] == 32 * 50 * 12
     # the top-k line carries a roofline of its pushes on FIFO top-k push counts (oracle: orc_topk_push_counts with the GPU run's rounds)
     r = d["roofline"]
     assert r is not None and r["bound"] == "hbm" and 0 < r["frac"] < 1 and "FIFO top-k pushes" in r["algorithmic_counts"]
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes what the
+    last timed step computed, the same from run to run."""
+    import numpy as np
+    args = ["bench.py", "--graph", "small", "--queries", "64", "--steps", "3", "--warmup", "1"]
+    d = _run([sys.executable, *args, "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["value"] > 0 and abs(d["ms_per_step"] - 1e3 * 64 / d["value"]) < 1e-6 * d["ms_per_step"]
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "accuracy", "variants", "configs"):
+        assert k not in d, k
+    _run([sys.executable, *args, "--dump-outputs", str(tmp_path / "b")])
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    out = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n, a in out.items():
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    assert out["stats_n_walks.npy"].shape == (64,) and (out["stats_ppr_sum_fix.npy"] == 2.0 ** 62).all()
+    assert out["ppr.npy"].shape == (8, 32_000) and np.allclose(out["ppr.npy"].sum(axis=1), 1.0, rtol=0, atol=1e-12)
+    t = tmp_path / "topk"
+    _run([sys.executable, "bench.py", "--graph", "small", "--queries", "16", "--topk", "20", "--with-idx", "--steps", "1", "--warmup", "1",
+          "--dump-outputs", str(t)])
+    ids, sc = np.load(t / "topk_ids.npy"), np.load(t / "topk_scores.npy")
+    assert ids.shape == sc.shape == (16, 20) and (np.diff(sc, axis=1) <= 0).all() and np.load(t / "topk_rounds.npy").shape == (16,)
 
 
 def test_bench_line_names_the_walk_bound_and_its_sources():

@@ -2,14 +2,15 @@
 # GPU box: whole GPU test suite, smoke, the default bench line, ws profiles (kernel stats + PMC traffic)
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$R"; mkdir -p gpurun_out
+O="${BENCH_OUT:-bench_out}"; mkdir -p "$O"; export O  # where the bench line goes
 T0=$(date +%s)
 timeout 1500 python3 -m pytest tests -x -q -m gpu > gpurun_out/re_tests.log 2>&1; echo "tests rc=$? in $(( $(date +%s) - T0 )) s"; tail -3 gpurun_out/re_tests.log
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 T0=$(date +%s)
-timeout 900 python3 bench.py > gpurun_out/re_bench_default.json 2> gpurun_out/re_bench_default.err; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"
+timeout 900 python3 bench.py --full > "$O/re_bench_default.json" 2> "$O/re_bench_default.err"; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"
 python3 - <<'PY'
-import json
-d = json.loads(open("gpurun_out/re_bench_default.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.environ["O"] + "/re_bench_default.json").read().strip().splitlines()[-1])
 print("headline %.0f q/s, ms/step %.1f, roofline %.3f traffic %s" % (d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["traffic"]))
 print({k: round(v / d["steps"], 1) for k, v in d["phases"].items() if k.endswith("_ms")})
 print("dangling", {k: v for k, v in d["variants"]["dangling_rmat"].items() if k.startswith("value")})
