@@ -17,6 +17,7 @@ SYMBOLS = [
     "fora_hip_get_index", "fora_hip_set_index", "fora_hip_clear_index", "fora_hip_query_batch",
     "fora_hip_query_batch_fix", "fora_hip_topk_batch", "fora_hip_topk_bound_batch", "fora_hip_power_iteration_batch", "fora_hip_push_batch", "fora_hip_walk_counts",
     "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
+    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch",
 ]
 
 
@@ -254,6 +255,36 @@ class Engine:
             self._ctx, _p(src), C.c_int(nq), C.c_int(max_iter), _p(ppr) if want_ppr else None,
             _p(fix) if want_fix else None, C.c_int(k), _p(ids) if k else None, _p(sc) if k else None))
         return ppr, fix, ids, sc
+
+    # ---- baselines (--algo montecarlo / fwdpush)
+    def montecarlo(self, sources, epsilon=0.5, k=0, want_ppr=False, want_fix=True):
+        """Monte-Carlo SSPPR (montecarlo_query, query.h:16-43): (ppr f64 [nq,n] or None, ppr raw u64 or None,
+        ids [nq,k] or None, scores or None, stats)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        ppr = np.zeros((nq, self.n), dtype=np.float64) if want_ppr else None
+        fix = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
+        ids = np.zeros((nq, k), dtype=np.int32) if k else None
+        sc = np.zeros((nq, k), dtype=np.float64) if k else None
+        self._chk(self._lib.fora_hip_montecarlo_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), _p(ppr), _p(fix),
+                                                      C.c_int(k), _p(ids), _p(sc), st))
+        return ppr, fix, ids, sc, self._stats(st, nq)
+
+    def fwdpush(self, sources, epsilon=0.5, rmax_scale=1.0, k=0, want_ppr=False, want_fix=True):
+        """FwdPush (forward_local_update_linear at fwdpush_setting's rmax, ppr = reserve): (ppr f64 or None, reserve raw
+        or None, residue raw or None, ids or None, scores or None, stats)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        ppr = np.zeros((nq, self.n), dtype=np.float64) if want_ppr else None
+        rsv = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
+        res = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
+        ids = np.zeros((nq, k), dtype=np.int32) if k else None
+        sc = np.zeros((nq, k), dtype=np.float64) if k else None
+        self._chk(self._lib.fora_hip_fwdpush_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), C.c_double(rmax_scale),
+                                                   _p(ppr), _p(rsv), _p(res), C.c_int(k), _p(ids), _p(sc), st))
+        return ppr, rsv, res, ids, sc, self._stats(st, nq)
 
     # ---- stage hooks
     def walk_counts(self, residue, rsum):

@@ -1347,8 +1347,11 @@ int sync_twin(fora_ctx *c) {
     return FORA_OK;
 }
 
+// topk > 0: also the top-k of each slot's ppr slab (k_topk_select: score descending, ties id ascending, padded with (0, 0.0))
+// into ids / scores (either may be null); the caller has checked 1 <= topk <= min(SEL_MAXK, n).
 int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int flags, double *ppr_d,
-                 uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats) {
+                 uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats, int topk = 0, int32_t *ids = nullptr,
+                 double *scores = nullptr) {
     if (!c) return FORA_E_ARG;
     if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
     if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first");
@@ -1375,15 +1378,26 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
         if (ppr_d) { double *row = ppr_d + (uint64_t)i * n; memset(row, 0, n * 8); row[s] = 1.0; }
         if (ppr_fix) { uint64_t *row = ppr_fix + (uint64_t)i * n; memset(row, 0, n * 8); row[s] = FIX_ONE; }
         if (residue_fix) memset(residue_fix + (uint64_t)i * n, 0, n * 8);
+        if (topk > 0) { // one non-zero entry, then the padding
+            if (ids) { int32_t *row = ids + (uint64_t)i * topk; memset(row, 0, (size_t)topk * 4); row[0] = s; }
+            if (scores) { double *row = scores + (uint64_t)i * topk; memset(row, 0, (size_t)topk * 8); row[0] = 1.0; }
+        }
     }
+    const bool want_topk = topk > 0 && (ids || scores);
     const int nl = (int)live_src.size();
     if (nl == 0) return FORA_OK;
     c->bk_div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
     int rc = ensure_workspace(c, nl, c->omega);
     if (rc) return rc;
-    // second lane when there is more than one batch to run
+    if (want_topk && c->topk_cap < c->B * topk) {
+        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
+        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * topk * 4));
+        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * topk * 8));
+        c->topk_cap = c->B * topk;
+    }
+    // second lane when there is more than one batch to run (not with top-k outputs: their buffers live on the first lane)
     fora_ctx *lanes[2] = {c, c};
-    if (nl > c->B && c->opt_.pipeline == 1) { // opt-in: measured no gain on ws (kernels time-slice)
+    if (nl > c->B && c->opt_.pipeline == 1 && !want_topk) { // opt-in: measured no gain on ws (kernels time-slice)
         rc = sync_twin(c);
         if (rc) return rc;
         rc = ensure_workspace(c->twin, c->B, c->omega);
@@ -1400,6 +1414,21 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
             st_tmp.resize((size_t)p.nb);
             fill_stats(p.lane, p.nb, st_tmp.data());
             for (int i = 0; i < p.nb; i++) stats[live_at[(size_t)p.b0 + i]] = st_tmp[(size_t)i];
+        }
+        if (want_topk) { // (p.lane == c here)
+            const Dev ds = make_dev(c, p.nb, false);
+            int r2 = launch_select(c, ds, p.nb, topk, c->d_topk_ids, c->d_topk_sc, 0);
+            if (r2) return r2;
+            std::vector<int32_t> hid((size_t)p.nb * topk);
+            std::vector<double> hsc((size_t)p.nb * topk);
+            HIPCHK(c, hipMemcpyAsync(hid.data(), c->d_topk_ids, hid.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(hsc.data(), c->d_topk_sc, hsc.size() * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // (the ctx stream does not synchronise with the null stream)
+            for (int i = 0; i < p.nb; i++) {
+                const uint64_t at = (uint64_t)live_at[(size_t)p.b0 + i] * topk;
+                if (ids) memcpy(ids + at, hid.data() + (size_t)i * topk, (size_t)topk * 4);
+                if (scores) memcpy(scores + at, hsc.data() + (size_t)i * topk, (size_t)topk * 8);
+            }
         }
         // slots i .. j - 1 of the batch whose places in the caller's arrays are consecutive too: one copy
         for (int i = 0; i < p.nb && (ppr_d || ppr_fix || residue_fix);) {
@@ -2523,6 +2552,143 @@ static int power_iteration_batch_impl(fora_ctx *c, const int32_t *sources, int n
         }
     }
     return FORA_OK;
+}
+
+// ---- baselines of the reference's experiments: --algo montecarlo (query.h:1482-1493) and --algo fwdpush (:1495-1511)
+static int check_baseline_args(fora_ctx *c, const int32_t *sources, int nq, double epsilon, int k) {
+    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha, seed)");
+    if (nq < 0 || (nq && !sources)) return fail(c, FORA_E_ARG, "bad sources");
+    if (!(epsilon > 0)) return fail(c, FORA_E_ARG, "epsilon must be > 0");
+    if (k < 0 || k > SEL_MAXK || k > c->n) return fail(c, FORA_E_ARG, "bad k");
+    for (int i = 0; i < nq; i++)
+        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+    return FORA_OK;
+}
+
+// FwdPush: the push of the FORA path at fwdpush_setting's rmax (algo.h:485-496), ppr = the reserve
+// (compute_ppr_with_reserve, query.h:243-253).  The ctx's own rmax (and --balanced) are put back when the call returns.
+struct PushRmaxScope {
+    fora_ctx *c;
+    double rmax;
+    bool balanced;
+    PushRmaxScope(fora_ctx *ctx, double r) : c(ctx), rmax(ctx->rmax), balanced(ctx->balanced) { c->rmax = r; c->balanced = false; }
+    ~PushRmaxScope() { c->rmax = rmax; c->balanced = balanced; }
+};
+static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
+                              uint64_t *reserve_fix_out, uint64_t *residue_fix_out, int k, int32_t *ids, double *scores,
+                              fora_query_stats *stats) {
+    if (!c) return FORA_E_ARG;
+    if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
+    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    const double delta = 1.0 / c->n;
+    const double rmax = rmax_scale * delta * epsilon * c->n / c->m_attr; // config.rmax_scale*config.delta*config.epsilon*n/m
+    if (!(rmax > 0) || !std::isfinite(rmax)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
+    PushRmaxScope scope(c, rmax);
+    return query_common(c, sources, nq, 0, RUN_PUSH_ONLY, ppr_out, reserve_fix_out, residue_fix_out, stats, k, ids, scores);
+}
+
+// Monte-Carlo: W walks per source (k_walk_mc), W = the integers i >= 0 with i < omega, omega = montecarlo_setting
+// (algo.h:477-483).  A launch runs at most MC_LAUNCH_WALKS walks over all slots of the batch.
+constexpr uint64_t MC_LAUNCH_WALKS = 1ull << 28;
+static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out,
+                                 uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
+    if (!c) return FORA_E_ARG;
+    if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
+    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
+    const double omega = 3 * log(2 / pfail) / epsilon / epsilon / delta; // fwd_rw_count, algo.h:478
+    if (!(omega < 0x1p48)) return fail(c, FORA_E_ARG, "epsilon too small: more than 2^48 walks per source");
+    const uint64_t W = (uint64_t)std::ceil(omega); // for (unsigned long i = 0; i < config.omega; i++)
+    if (W == 0) return fail(c, FORA_E_ARG, "no walks");
+    const uint64_t wbase = FIX_ONE / W, wrem = FIX_ONE % W;
+    const bool want_topk = k > 0 && (ids || scores);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->bk_div = 1;
+    int rc = ensure_workspace(c, nq, c->omega); // (the FORA plan: only the ppr slabs and the per-slot words are used here)
+    if (rc) return rc;
+    const uint64_t n = (uint64_t)c->n;
+    if (want_topk && c->topk_cap < c->B * k) {
+        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
+        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
+        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
+        c->topk_cap = c->B * k;
+    }
+    const int per = even_batch(nq, c->B);
+    for (int b0 = 0; b0 < nq; b0 += per) {
+        const int nb = std::min(per, nq - b0);
+        const int hb = ev_begin(c, 5);
+        rc = reset_batch_state(c, nb, sources + b0);
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
+        const Dev d = make_dev(c, nb, false);
+        // walk numbers per launch and per workgroup: about eight workgroups per CU, 4 Ki .. 64 Ki walks each
+        const uint64_t span = std::max<uint64_t>(1, MC_LAUNCH_WALKS / (uint64_t)nb);
+        for (uint64_t j0 = 0; j0 < W; j0 += span) {
+            const uint64_t j1 = std::min(W, j0 + span);
+            const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
+            const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
+            const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
+            const int h = ev_begin(c, 3);
+            hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, wbase, wrem, j0, j1, per_wg);
+            ev_end(c, h);
+        }
+        {
+            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
+            const int h = ev_begin(c, 4);
+            hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d);
+            ev_end(c, h);
+        }
+        if (want_topk) {
+            const int h = ev_begin(c, 4);
+            rc = launch_select(c, d, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
+            if (rc) return rc;
+            ev_end(c, h);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        ev_end(c, hb);
+        rc = check_dev_err(c);
+        if (rc) return rc;
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("montecarlo: ") + hipGetErrorString(e));
+        ev_collect(c);
+        c->timing.walks += W * (uint64_t)nb;
+        c->timing.walk_steps += *c->h_steps_pin;
+        if (stats)
+            for (int i = 0; i < nb; i++) {
+                fora_query_stats &o = stats[b0 + i];
+                memset(&o, 0, sizeof(o));
+                o.n_walks = W;
+                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
+                o.dangling_source = c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]] ? 1 : 0;
+            }
+        if (want_topk) {
+            if (ids) HIPCHK(c, hipMemcpy(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost));
+            if (scores) HIPCHK(c, hipMemcpy(scores + (size_t)b0 * k, c->d_topk_sc, (size_t)nb * k * 8, hipMemcpyDeviceToHost));
+        }
+        const uint64_t bytes = (uint64_t)nb * n * 8;
+        if (ppr_fix_out) HIPCHK(c, hipMemcpy(ppr_fix_out + (uint64_t)b0 * n, c->d_ppr, bytes, hipMemcpyDeviceToHost));
+        if (ppr_out) {
+            double *dst = ppr_out + (uint64_t)b0 * n;
+            HIPCHK(c, hipMemcpy(dst, c->d_ppr, bytes, hipMemcpyDeviceToHost));
+            uint64_t *raw = (uint64_t *)dst;
+            for (uint64_t i = 0; i < (uint64_t)nb * n; i++) dst[i] = std::ldexp((double)raw[i], -62);
+        }
+    }
+    return FORA_OK;
+}
+
+int fora_hip_montecarlo_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out, uint64_t *ppr_fix_out,
+                              int k, int32_t *ids, double *scores, fora_query_stats *stats) {
+    return montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats); // (no buckets, no push: nothing to retry)
+}
+
+int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
+                           uint64_t *reserve_fix_out, uint64_t *residue_fix_out, int k, int32_t *ids, double *scores,
+                           fora_query_stats *stats) {
+    return with_bucket_retry(c, [&] {
+        return fwdpush_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, reserve_fix_out, residue_fix_out, k, ids, scores, stats);
+    });
 }
 
 int fora_hip_reset_timing(fora_ctx *c) {

@@ -9,6 +9,7 @@
 //                                        index build), k_accum<true>
 //   index build     build.h:325-354   -> k_index_alloc + k_walk_online<WALK_TO_INDEX>
 //   top-k           query.h:972-1045, algo.h:578-610 -> k_topk_frontier, k_count_above, k_topk_select
+//   Monte-Carlo     query.h:16-43     -> k_walk_mc (the --algo montecarlo baseline)
 // Many source queries ("slots") run concurrently; slot q owns dense slabs residue[q*n .. (q+1)*n) and
 // ppr[q*n ..) of 2^-62 fixed-point u64 in HBM.  Every cross-thread accumulation is an integer add (LDS
 // ds_add_u64 inside a workgroup that owns the target range, integer atomics otherwise), so results do not
@@ -3121,6 +3122,120 @@ __global__ void __launch_bounds__(BLOCK) k_walks_raw(Dev d, uint32_t stream, uin
     if (i >= count) return;
     uint32_t steps = 0;
     dests[i] = walk_one(d, (uint32_t)starts[i], js[i], stream, round, nzh, steps);
+}
+
+// ---- Monte-Carlo SSPPR (montecarlo_query, query.h:16-43; random_walk, algo.h:124-142).  grid = (X, nq): workgroup x of
+// slot q runs walk numbers [j0 + x * per_wg, min(j1, j0 + (x + 1) * per_wg)) from the slot's source s, each wave a
+// contiguous quarter of them, idle lanes taking the next walk numbers every second iteration (as in k_walk_online).  Walk j
+// is walk j of the Philox contract with start = stream = s, round 0, zero-hop walks allowed, and carries
+// wbase + (j < wrem) units to its endpoint (wbase = floor(2^62 / W), wrem = 2^62 mod W: the slab sums to FIX_ONE).
+// Endpoints crowd around the source (at least alpha of the walks end ON it), so one global atomic per walk would hit a
+// few hot words: the source's weight is summed in a register per lane, every other endpoint in an LDS open-addressing
+// table of u64 sums, flushed with one global add per occupied entry; an endpoint that finds no entry within MC_PROBES
+// slots is added to HBM at once.  Integer adds: any combining order gives the same bits.
+constexpr int MC_TAB_BITS = 11;
+constexpr uint32_t MC_TAB = 1u << MC_TAB_BITS; // 2048 entries, 24 KiB of LDS per workgroup
+constexpr int MC_PROBES = 8;
+constexpr uint32_t MC_EMPTY = 0xFFFFFFFFu;
+__device__ __forceinline__ bool mc_tab_add(uint32_t *keys, unsigned long long *vals, uint32_t v, uint64_t w) {
+    uint32_t h = (v * 0x9E3779B1u) >> (32 - MC_TAB_BITS);
+    for (int p = 0; p < MC_PROBES; p++) {
+        uint32_t k = keys[h];
+        if (k == MC_EMPTY) {
+            k = atomicCAS(&keys[h], MC_EMPTY, v);
+            if (k == MC_EMPTY) k = v;
+        }
+        if (k == v) {
+            atomicAdd(&vals[h], (unsigned long long)w);
+            return true;
+        }
+        h = (h + 1) & (MC_TAB - 1);
+    }
+    return false;
+}
+__global__ void __launch_bounds__(BLOCK) k_walk_mc(Dev d, uint64_t wbase, uint64_t wrem, uint64_t j0, uint64_t j1, uint64_t per_wg) {
+    __shared__ uint32_t s_key[MC_TAB];
+    __shared__ unsigned long long s_val[MC_TAB];
+    __shared__ unsigned long long s_src[BLOCK / 64];
+    __shared__ uint32_t s_steps[BLOCK / 64];
+    const int q = blockIdx.y;
+    const uint64_t lo = j0 + (uint64_t)blockIdx.x * per_wg;
+    if (lo >= j1) return;
+    const uint64_t hi = min(j1, lo + per_wg);
+    const uint32_t s = (uint32_t)d.src[q];
+    const uint64_t slab = (uint64_t)q * d.n;
+    int64_t beg0; uint64_t deg0;
+    if (d.rp32) { // the walks stay inside the compact copy's working set (walk_move)
+        const U32Pair rp = *(const U32Pair *)(d.rp32 + s);
+        beg0 = rp.a;
+        deg0 = rp.b - rp.a;
+    } else node_row(d, s, beg0, deg0);
+    if (deg0 == 0) { // algo.h:127-129: every walk ends on s -- the range's weight in closed form
+        if (threadIdx.x == 0) {
+            const uint64_t extra = wrem > lo ? min(hi, wrem) - lo : 0;
+            atomicAdd((unsigned long long *)&d.ppr[slab + s], (unsigned long long)((hi - lo) * wbase + extra));
+        }
+        return;
+    }
+    for (uint32_t i = threadIdx.x; i < MC_TAB; i += BLOCK) { s_key[i] = MC_EMPTY; s_val[i] = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const uint64_t span = hi - lo;
+    uint64_t wptr = lo + ((span * (uint64_t)wid) >> 2); // next unassigned walk number of this wave (span < 2^62 / 4)
+    const uint64_t wend = lo + ((span * (uint64_t)(wid + 1)) >> 2);
+    bool active = false;
+    uint32_t cur = s, t = 0, steps = 0;
+    uint64_t wj = 0, src_acc = 0;
+    uint32_t rw[4] = {0, 0, 0, 0};
+    for (uint32_t it = 0;; it++) {
+        if ((it & 1u) == 0) {
+            const unsigned long long idle = __ballot(!active);
+            const uint64_t avail = wend - wptr;
+            if (!avail && idle == ~0ull) break;
+            if (avail && idle) {
+                const uint32_t rank = __popcll(idle & ((1ull << lane) - 1));
+                if (!active && rank < avail) {
+                    wj = wptr + rank;
+                    cur = s;
+                    t = 0;
+                    active = true;
+                }
+                const uint32_t want = (uint32_t)__popcll(idle);
+                wptr += want < avail ? want : avail;
+            }
+            if (active)
+                philox4x32_10(s, (uint32_t)wj, (uint32_t)((wj >> 32) & 0xFFFFu) | (((t >> 1) & 0xFFu) << 24),
+                              s ^ ((t >> 9) * 0x9E3779B9u), d.seed_lo, d.seed_hi, rw); // round 0, stream = s
+        }
+        if (active) {
+            const uint32_t ws = (it & 1u) ? rw[2] : rw[0], wm = (it & 1u) ? rw[3] : rw[1];
+            if (ws < d.alpha32) { // algo.h:131-133: the walk ends on cur
+                active = false;
+                const uint64_t w = wbase + (wj < wrem ? 1u : 0u);
+                if (cur == s) src_acc += w;
+                else if (!mc_tab_add(s_key, s_val, cur, w)) atomicAdd((unsigned long long *)&d.ppr[slab + cur], (unsigned long long)w);
+            } else {
+                if (t) cur = walk_move(d, cur, s, wm);                                                 // algo.h:134-140
+                else if (d.rp32) cur = colp_at(d, (uint64_t)beg0 + (((uint64_t)wm * deg0) >> 32));
+                else cur = (uint32_t)d.col[beg0 + (int64_t)(((uint64_t)wm * deg0) >> 32)];
+                t++;
+                steps++;
+            }
+        }
+    }
+    const uint64_t ssum = wave_sum(src_acc), wsteps = wave_sum((uint64_t)steps);
+    if (lane == 0) { s_src[wid] = ssum; s_steps[wid] = (uint32_t)wsteps; } // < 2^32 steps per wave
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < MC_TAB; i += BLOCK) {
+        const uint32_t v = s_key[i];
+        if (v != MC_EMPTY) atomicAdd((unsigned long long *)&d.ppr[slab + v], s_val[i]);
+    }
+    if (threadIdx.x == 0) {
+        unsigned long long a = 0, b = 0;
+        for (int w = 0; w < BLOCK / 64; w++) { a += s_src[w]; b += s_steps[w]; }
+        if (a) atomicAdd((unsigned long long *)&d.ppr[slab + s], a);
+        if (b) atomicAdd(d.tot_steps, b);
+    }
 }
 
 } // namespace fora

@@ -26,9 +26,11 @@ static const char *const BATCH_TOPK = "batch-topk";         // config.h:39
 static const char *const CHECK_GRAPH = "check-graph"; // not in the reference: loader self-check
 static const char *const CHECK_INDEX = "check-index"; // not in the reference: index file self-check (no GPU needed)
 static const char *const FORA = "fora";
+static const char *const FWDPUSH = "fwdpush"; // config.h:43
+static const char *const MC = "montecarlo";   // config.h:44
 
 // timer slots: config.h:47-57
-enum { FORA_QUERY = 3, FWD_LU = 5, RONDOM_WALK = 6, SORT_MAP = 8 };
+enum { MC_QUERY = 1, FORA_QUERY = 3, FWD_LU = 5, RONDOM_WALK = 6, SORT_MAP = 8 };
 
 struct Config { // config.h:86-160
     std::string graph_alias = "nethept"; // fora.cpp:63

@@ -49,6 +49,8 @@ static const char *HELP =
     "\n"
     "algo: \n"
     "  fora\n"
+    "  montecarlo\n"
+    "  fwdpush\n"
     "options: \n"
     "  --prefix <prefix>\n"
     "  --epsilon <epsilon>\n"
@@ -73,11 +75,12 @@ static const char *HELP =
 // display_time_usage (algo.h:368-402) + set_result (algo.h:404-440)
 static void finish(const Graph &graph, int used_counter, unsigned query_size, double n_walks, double n_hit) {
     const double tot = timers.get(used_counter);
+    const bool fora = config.algo == FORA;
     cout << "Total cost (s): " << tot << endl;
-    cout << timers.get(RONDOM_WALK) * 100.0 / tot << "%" << " for random walk cost" << endl;
-    cout << timers.get(FWD_LU) * 100.0 / tot << "%" << " for forward push cost" << endl;
-    split_line();
-    if (config.with_rw_idx) cout << "Average rand-walk idx hit ratio: " << n_hit * 100.0 / n_walks << "%" << endl;
+    if (config.algo != FWDPUSH) cout << timers.get(RONDOM_WALK) * 100.0 / tot << "%" << " for random walk cost" << endl;
+    if (config.algo != MC) cout << timers.get(FWD_LU) * 100.0 / tot << "%" << " for forward push cost" << endl;
+    if (fora) split_line();
+    if (config.with_rw_idx && fora) cout << "Average rand-walk idx hit ratio: " << n_hit * 100.0 / n_walks << "%" << endl;
     if (config.action == TOPK) { // algo.h:394-398; the reference asserts when no source had ground truth
         if (result.real_topk_source_count > 0) {
             cout << "Average top-K Precision: " << result.topk_precision / result.real_topk_source_count << endl;
@@ -92,11 +95,13 @@ static void finish(const Graph &graph, int used_counter, unsigned query_size, do
     result.total_mem_usage = proc_memory_mb();
     result.total_time_usage = tot;
     result.num_randwalk = n_walks;
-    if (config.with_rw_idx) { result.num_rw_idx_use = n_hit; result.hit_idx_ratio = n_hit / n_walks; }
+    if (config.with_rw_idx && fora) { result.num_rw_idx_use = n_hit; result.hit_idx_ratio = n_hit / n_walks; }
     result.randwalk_time = timers.get(RONDOM_WALK);
     result.randwalk_time_ratio = timers.get(RONDOM_WALK) * 100 / tot;
-    result.propagation_time = timers.get(FWD_LU);
-    result.propagation_time_ratio = timers.get(FWD_LU) * 100 / tot;
+    if (fora) { // set_result, algo.h:423-427: the propagation fields are FORA's (and BiPPR's) only
+        result.propagation_time = timers.get(FWD_LU);
+        result.propagation_time_ratio = timers.get(FWD_LU) * 100 / tot;
+    }
     if (config.action == TOPK) result.topk_sort_time = timers.get(SORT_MAP);
 }
 
@@ -259,7 +264,11 @@ static void add_shard_timers(const std::vector<Shard> &shards, int total_slot) {
     if (config.action == TOPK) timers.add(SORT_MAP, other);
 }
 
+static int do_query_baseline(Graph &graph);
+static int do_topk_baseline(Graph &graph);
+
 static int do_query(Graph &graph) { // query(), query.h:1415-1515 FORA branch
+    if (config.algo != FORA) return do_query_baseline(graph);
     info("config.algo", config.algo);
     std::vector<int32_t> queries;
     if (!graph.load_ss_query(queries)) { cerr << graph.error << endl; exit(0); } // algo.h:513-516
@@ -334,6 +343,7 @@ static int run_topk_pass(const Graph &graph, const std::vector<int32_t> &queries
 }
 
 static int do_topk(Graph &graph) { // topk(), query.h:1309-1413 FORA branch
+    if (config.algo != FORA) return do_topk_baseline(graph);
     std::vector<int32_t> queries;
     if (!graph.load_ss_query(queries)) { cerr << graph.error << endl; exit(0); }
     info("queries.size()", queries.size());
@@ -382,6 +392,7 @@ static int do_topk(Graph &graph) { // topk(), query.h:1309-1413 FORA branch
 }
 
 static int do_batch_topk(Graph &graph) { // batch_topk(), query.h:1517-1640, FORA branch (:1612-1636): the algorithm runs again per k
+    if (config.algo != FORA) return do_topk_baseline(graph);
     std::vector<int32_t> queries;
     if (!graph.load_ss_query(queries)) { cerr << graph.error << endl; exit(0); }
     info("queries.size()", queries.size());
@@ -433,6 +444,177 @@ static int do_batch_topk(Graph &graph) { // batch_topk(), query.h:1517-1640, FOR
     cout << endl << "Recall:" << endl;
     for (unsigned k : ks) cout << (pred[k].count ? pred[k].recall / pred[k].count : 0.0) << "\t";
     cout << endl;
+    return 0;
+}
+
+// ---- baselines: --algo montecarlo / fwdpush.  montecarlo_setting / fwdpush_setting (algo.h:477-496) for the log lines and
+// the result JSON; the engine computes the same values from the same operands.
+static void baseline_setting(const Graph &graph) {
+    if (config.algo == MC) config.omega = 3 * log(2 / config.pfail) / config.epsilon / config.epsilon / config.delta;
+    else config.rmax = config.rmax_scale * config.delta * config.epsilon * graph.n / graph.m;
+    info("config.delta", config.delta); // display_setting, algo.h:341-346
+    info("config.pfail", config.pfail);
+    info("config.rmax", config.rmax);
+    info("config.omega", config.omega);
+}
+
+// the baseline for the sources of the query list (sources i mod G over the GPUs); k > 0: top-k lists in query order
+static int run_baseline(const Graph &graph, const std::vector<int32_t> &queries, unsigned query_size, unsigned k,
+                        std::vector<int32_t> &ids, std::vector<double> &scores, std::vector<fora_query_stats> &st,
+                        std::vector<Shard> &shards) {
+    ids.assign((size_t)query_size * k, 0);
+    scores.assign((size_t)query_size * k, 0.0);
+    st.assign(query_size, fora_query_stats{});
+    return run_sharded(graph, queries, query_size, nullptr, shards, [&](fora_ctx *ctx, Shard &s) {
+        const size_t nl = s.sources.size();
+        std::vector<int32_t> lid(nl * k);
+        std::vector<double> lsc(nl * k);
+        std::vector<fora_query_stats> lst(nl);
+        const int rc = config.algo == MC
+                           ? fora_hip_montecarlo_batch(ctx, s.sources.data(), (int)nl, config.epsilon, nullptr, nullptr, (int)k,
+                                                       k ? lid.data() : nullptr, k ? lsc.data() : nullptr, lst.data())
+                           : fora_hip_fwdpush_batch(ctx, s.sources.data(), (int)nl, config.epsilon, config.rmax_scale, nullptr, nullptr,
+                                                    nullptr, (int)k, k ? lid.data() : nullptr, k ? lsc.data() : nullptr, lst.data());
+        if (rc) return 1;
+        for (size_t i = 0; i < nl; i++) {
+            std::copy(lid.begin() + (long)(i * k), lid.begin() + (long)((i + 1) * k), ids.begin() + (long)(s.pos[i] * k));
+            std::copy(lsc.begin() + (long)(i * k), lsc.begin() + (long)((i + 1) * k), scores.begin() + (long)(s.pos[i] * k));
+            st[s.pos[i]] = lst[i];
+        }
+        return 0;
+    });
+}
+
+// timer slots of the baselines: the whole run in `total_slot`; the walk kernels in RONDOM_WALK (montecarlo_query, query.h:22)
+// or the push kernels in FWD_LU (get_topk, query.h:1162)
+static void add_baseline_timers(const std::vector<Shard> &shards, int total_slot) {
+    double wall = 0, push = 0, walk = 0;
+    for (auto &s : shards) {
+        wall = std::max(wall, s.seconds);
+        push = std::max(push, (s.tm.push_pop_ms + s.tm.push_expand_ms + s.tm.push_accum_ms + s.tm.push_tail_ms + s.tm.push_team_ms) * 1e-3);
+        walk = std::max(walk, s.tm.walk_ms * 1e-3);
+    }
+    timers.add(total_slot, wall);
+    if (config.algo == MC) timers.add(RONDOM_WALK, walk);
+    else if (total_slot != FWD_LU) timers.add(FWD_LU, push);
+}
+
+static int do_query_baseline(Graph &graph) { // query(), query.h:1482-1511
+    info("config.algo", config.algo);
+    std::vector<int32_t> queries;
+    if (!graph.load_ss_query(queries)) { cerr << graph.error << endl; exit(0); }
+    unsigned query_size = std::min<unsigned>((unsigned)queries.size(), config.query_size);
+    info("query_size", query_size);
+    if (!(config.rmax_scale >= 0)) { cerr << "rmax_scale must be >= 0" << endl; return 1; }
+    baseline_setting(graph);
+    const int used_counter = config.algo == MC ? MC_QUERY : FWD_LU;
+    std::vector<int32_t> ids;
+    std::vector<double> scores;
+    std::vector<fora_query_stats> st;
+    std::vector<Shard> shards;
+    if (run_baseline(graph, queries, query_size, 0, ids, scores, st, shards)) return 1;
+    double n_walks = 0;
+    for (unsigned i = 0; i < query_size; i++) {
+        cout << i + 1 << ". source node:" << queries[i] << endl; // query.h:1490, :1505
+        n_walks += (double)st[i].n_walks;                         // num_total_rw += config.omega, query.h:23
+    }
+    split_line();
+    add_baseline_timers(shards, used_counter);
+    finish(graph, used_counter, query_size, n_walks, 0);
+    return 0;
+}
+
+// compute_precision_for_dif_k, algo.h:628-674: precision / recall of the first k' entries of the one top-k list, k' in ks
+struct PredK { double precision = 0, recall = 0; int count = 0; };
+static void compute_precision_for_dif_k(int32_t v, const int32_t *ids, const double *scores, const std::vector<unsigned> &ks,
+                                        std::map<unsigned, PredK> &pred) {
+    auto it = exact_topk_pprs.find(v);
+    if (exact_topk_pprs.empty() || it == exact_topk_pprs.end()) return;
+    for (unsigned k : ks) {
+        std::unordered_set<int32_t> topk_set, exact_set;
+        for (unsigned j = 0; j < k && j < config.k; j++)
+            if (scores[j] > 0) topk_set.insert(ids[j]);
+        double hits = 0;
+        const size_t size_e = std::min<size_t>(k, it->second.size());
+        for (size_t i = 0; i < size_e; i++) {
+            const auto &p = it->second[i];
+            if (p.second > 0) {
+                exact_set.insert(p.first);
+                if (topk_set.count(p.first)) hits++;
+            }
+        }
+        if (exact_set.empty()) continue; // (the reference divides by zero here)
+        double precision = 0;
+        for (int32_t id : topk_set)
+            if (exact_set.count(id)) precision++;
+        pred[k].precision += precision / (double)exact_set.size();
+        pred[k].recall += hits / (double)exact_set.size();
+        pred[k].count++;
+    }
+}
+
+// topk() / batch_topk() for the baselines (query.h:1325-1339, 1585-1611): ONE run at config.k, then precision and recall
+// of its first k' entries for every k' of ks (a single-source algorithm does not depend on k)
+static int do_topk_baseline(Graph &graph) {
+    const bool batch = config.action == BATCH_TOPK;
+    std::vector<int32_t> queries;
+    if (!graph.load_ss_query(queries)) { cerr << graph.error << endl; exit(0); }
+    info("queries.size()", queries.size());
+    unsigned query_size = std::min<unsigned>((unsigned)queries.size(), config.query_size);
+    if (!(config.k < (unsigned)graph.n - 1) || !(config.k > 1)) { cerr << "k out of range" << endl; return 1; } // :1317-1318
+    if (config.k > 1024) { cerr << "k > 1024 not supported" << endl; return 1; }
+    if (!(config.rmax_scale >= 0)) { cerr << "rmax_scale must be >= 0" << endl; return 1; }
+    info("config.k", config.k);
+    split_line();
+    load_exact_topk(); // query.h:1323, :1529
+    std::vector<unsigned> ks; // query.h:1328-1335, :1585-1591
+    const unsigned step = config.k / 5;
+    if (step > 0) for (unsigned i = 1; i < 5; i++) ks.push_back(i * step);
+    ks.push_back(config.k);
+    baseline_setting(graph);
+    const unsigned k = config.k;
+    std::vector<int32_t> ids;
+    std::vector<double> scores;
+    std::vector<fora_query_stats> st;
+    std::vector<Shard> shards;
+    if (run_baseline(graph, queries, query_size, k, ids, scores, st, shards)) return 1;
+    std::map<unsigned, PredK> pred;
+    double n_walks = 0;
+    FILE *fo = nullptr;
+    string out;
+    if (!batch) {
+        if (config.exe_result_dir.empty() || config.exe_result_dir.back() != '/') config.exe_result_dir += "/";
+        make_dirs(config.exe_result_dir);
+        out = config.exe_result_dir + config.graph_alias + ".topk.k-" + std::to_string(k) + ".txt";
+        fo = fopen(out.c_str(), "w");
+    }
+    for (unsigned i = 0; i < query_size; i++) {
+        cout << i + 1 << ". source node:" << queries[i] << endl;
+        n_walks += (double)st[i].n_walks;
+        const int32_t *qi = &ids[(size_t)i * k];
+        const double *qs = &scores[(size_t)i * k];
+        compute_precision_for_dif_k(queries[i], qi, qs, ks, pred); // get_topk, query.h:1176-1178
+        compute_precision(queries[i], qi, qs, k);                  // :1180
+        if (fo) {
+            fprintf(fo, "%d", queries[i]);
+            for (unsigned j = 0; j < k; j++) fprintf(fo, " %d:%.17g", qi[j], qs[j]);
+            fprintf(fo, "\n");
+        }
+        split_line();
+    }
+    if (fo) fclose(fo);
+    if (!batch) cout << "average iter times:" << 0 << endl; // query.h:1403 (num_iter_topk: FORA's rounds only)
+    add_baseline_timers(shards, 0);
+    finish(graph, 0, query_size, n_walks, 0);
+    split_line(); // display_precision_for_dif_k, algo.h:676-692
+    cout << config.algo << endl;
+    for (unsigned kk : ks) cout << kk << "\t";
+    cout << endl << "Precision:" << endl;
+    for (unsigned kk : ks) cout << (pred[kk].count ? pred[kk].precision / pred[kk].count : 0.0) << "\t";
+    cout << endl << "Recall:" << endl;
+    for (unsigned kk : ks) cout << (pred[kk].count ? pred[kk].recall / pred[kk].count : 0.0) << "\t";
+    cout << endl;
+    if (fo) cout << "top-k lists written to " << out << endl;
     return 0;
 }
 
@@ -570,9 +752,10 @@ int main(int argc, char *argv[]) {
         cerr << "sub command not regoznized" << endl; // fora.cpp:278-281
         return 1;
     }
-    if ((act == QUERY || act == TOPK || act == BATCH_TOPK) && config.algo != FORA) { // fora.cpp:169-175, :226-231
+    if ((act == QUERY || act == TOPK || act == BATCH_TOPK) && config.algo != FORA && config.algo != MC &&
+        config.algo != FWDPUSH) { // fora.cpp:169-175, :226-231 (bippr / hubppr are not part of this build)
         info("Wrong algo param: ", config.algo);
-        cerr << "only --algo fora is part of this build" << endl;
+        cerr << "only --algo fora, montecarlo or fwdpush is part of this build" << endl;
         return 1;
     }
     if ((act == QUERY || act == TOPK || act == BUILD || act == BATCH_TOPK) && !(config.epsilon > 0)) { cerr << "--epsilon must be > 0" << endl; return 1; }

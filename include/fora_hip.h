@@ -30,6 +30,12 @@
  * one call per two steps, counter = (start node, walk# lo32, walk# bits 32..47 | round << 16 | (step/2 & 255) << 24,
  * stream ^ (step >> 9) * 0x9E3779B9), stream = the query's source id (FORA_STREAM_INDEX for index walks).
  * Version 1 (round 1) lacked the (step >> 9) term; walks of up to 512 steps are identical in both.
+ * Monte-Carlo walks (fora_hip_montecarlo_batch): source s runs W walks, W = the number of integers i >= 0 with
+ * (double)i < omega_mc (the reference's `for (unsigned long i = 0; i < config.omega; i++)`, query.h:24); walk j < W is
+ * the walk above with start = s, stream = s, round = 0, walk# j, zero-hop walks allowed (random_walk, algo.h:124-142),
+ * i.e. it ends where orc_walk(g, seed, s, 0, s, j) and fora_hip_walks(stream s, round 0, no_zero_hop 0, start s, j) end.
+ * It carries floor(2^62 / W) + (j < 2^62 mod W) units to its endpoint, so sum(ppr) == FORA_FIX_ONE exactly; the
+ * reference's cnt / omega differs from that by a factor omega / W, between 1 - 1/omega and 1.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -195,6 +201,25 @@ int fora_hip_topk_bound_batch(fora_ctx *ctx, const int32_t *sources, int nq, int
 int fora_hip_power_iteration_batch(fora_ctx *ctx, const int32_t *sources, int nq, int max_iter,
                                    double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids,
                                    double *scores);
+
+/* ---- baselines of the reference's experiments (query.h:1482-1511; get_topk :1139-1166; batch_topk :1553-1611).
+ * Both use the ctx's alpha and seed and leave its FORA parameters (fora_hip_get_params) untouched.  Any output pointer may
+ * be NULL; ppr_out / *_fix_out: nq*n, ids / scores: nq*k (k == 0: no top-k; else 1 <= k <= min(1024, n), score
+ * descending, ties id ascending, padded with (0, 0.0), as fora_hip_topk_batch).  Bad nq / sources, k or epsilon <= 0:
+ * FORA_E_ARG. */
+/* --algo montecarlo: montecarlo_query (query.h:16-43), omega = montecarlo_setting (algo.h:477-483)
+ * 3*log(2/pfail)/epsilon/epsilon/delta with pfail = delta = 1/n; walks as in the RNG contract above.  Stats: n_walks = W,
+ * ppr_sum_fix, dangling_source.  Timing: walk_ms. */
+int fora_hip_montecarlo_batch(fora_ctx *ctx, const int32_t *sources, int nq, double epsilon,
+                              double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores,
+                              fora_query_stats *stats);
+/* --algo fwdpush: forward_local_update_linear (algo.h:954-1018) at rmax = fwdpush_setting (algo.h:485-496)
+ * rmax_scale*delta*epsilon*n/m (delta = 1/n, m = m_attr of fora_hip_set_graph), the same push as fora_hip_push_batch;
+ * ppr = the reserve (compute_ppr_with_reserve, query.h:243-253), the residue is dropped: sum(ppr) = 1 - rsum.  Stats:
+ * pops, relax, rsum, rmax_used, levels.  Timing: the push fields. */
+int fora_hip_fwdpush_batch(fora_ctx *ctx, const int32_t *sources, int nq, double epsilon, double rmax_scale,
+                           double *ppr_out, uint64_t *reserve_fix_out, uint64_t *residue_fix_out,
+                           int k, int32_t *ids, double *scores, fora_query_stats *stats);
 
 /* ---- stage hooks (same device code as the paths above, exposed for parity tests) */
 /* forward push only (forward_local_update_linear, algo.h:954-1018) */
