@@ -17,8 +17,9 @@ SYMBOLS = [
     "fora_hip_get_index", "fora_hip_set_index", "fora_hip_clear_index", "fora_hip_query_batch",
     "fora_hip_query_batch_fix", "fora_hip_topk_batch", "fora_hip_topk_bound_batch", "fora_hip_power_iteration_batch", "fora_hip_push_batch", "fora_hip_walk_counts",
     "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
-    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch",
+    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bwdpush_batch",
 ]
+BWD_FIX_ONE = 1 << 60
 
 
 class ForaError(RuntimeError):
@@ -48,6 +49,15 @@ class Timing(C.Structure):
                 ("relax", C.c_uint64), ("walks", C.c_uint64), ("walk_steps", C.c_uint64),
                 ("levels", C.c_uint64), ("idx_hits", C.c_uint64), ("push_tail_ms", C.c_double), ("push_tail_launches", C.c_uint64),
                 ("push_team_ms", C.c_double), ("push_team_launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BwdStats(C.Structure):
+    _fields_ = [("targets", C.c_uint64), ("pops", C.c_uint64), ("relax", C.c_uint64), ("entries", C.c_uint64),
+                ("global_targets", C.c_uint64), ("levels", C.c_int32), ("chunks", C.c_int32), ("bwd_ms", C.c_double),
+                ("walk_ms", C.c_double), ("combine_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -286,7 +296,34 @@ class Engine:
                                                    _p(ppr), _p(rsv), _p(res), C.c_int(k), _p(ids), _p(sc), st))
         return ppr, rsv, res, ids, sc, self._stats(st, nq)
 
+    def bippr(self, sources, epsilon=0.5, rmax_scale=1.0, k=0, want_ppr=False, want_fix=True):
+        """BiPPR (bippr_query / bippr_query_topk, query.h:71-193): (ppr f64 [nq,n] or None, ppr raw u64 at 2^60 or None,
+        ids [nq,k] or None, scores or None, stats, backward-push counters as a dict)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        bwd = BwdStats()
+        ppr = np.zeros((nq, self.n), dtype=np.float64) if want_ppr else None
+        fix = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
+        ids = np.zeros((nq, k), dtype=np.int32) if k else None
+        sc = np.zeros((nq, k), dtype=np.float64) if k else None
+        self._chk(self._lib.fora_hip_bippr_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), C.c_double(rmax_scale),
+                                                 _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), st, C.byref(bwd)))
+        return ppr, fix, ids, sc, self._stats(st, nq), bwd.as_dict()
+
     # ---- stage hooks
+    def bwdpush(self, targets, rmax):
+        """Backward push (reverse_local_update_linear, algo.h:703-751) to each target: (reserve u64 [nt,n] at 2^60,
+        residue u64 [nt,n] at 2^60, counters as a dict)."""
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        nt = tg.size
+        rsv = np.zeros((nt, self.n), dtype=np.uint64)
+        res = np.zeros((nt, self.n), dtype=np.uint64)
+        bwd = BwdStats()
+        self._chk(self._lib.fora_hip_bwdpush_batch(self._ctx, _p(tg), C.c_int(nt), C.c_double(rmax), _p(rsv), _p(res),
+                                                   C.byref(bwd)))
+        return rsv, res, bwd.as_dict()
+
     def walk_counts(self, residue, rsum):
         residue = np.ascontiguousarray(residue, dtype=np.float64)
         out = np.zeros(self.n, dtype=np.uint64)

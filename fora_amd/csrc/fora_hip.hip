@@ -5,6 +5,7 @@
 // there is no CPU fallback: without a HIP device every entry point fails.
 #include "fora_kernels.h"
 #include "fora_team.h"
+#include "fora_bwd.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -24,7 +25,7 @@ namespace {
 
 struct EvPair {
     hipEvent_t a, b;
-    int kind; // 0 pop, 1 expand, 2 walk_alloc, 3 walk, 4 other, 5 batch, 6 accum, 7 walk accum, 8 round sweep, 9 tail, 10 team push
+    int kind; // 0 pop, 1 expand, 2 walk_alloc, 3 walk, 4 other, 5 batch, 6 accum, 7 walk accum, 8 round sweep, 9 tail, 10 team push, 11 backward push, 12 bippr combine
 };
 
 } // namespace
@@ -79,6 +80,8 @@ struct Tunables {
     int64_t pipeline = 0;        // 1: second lane (stream + workspace) when a call has more than one batch
     int64_t profile = 1;         // 0: no HIP event pairs around the launches
     int64_t grid = 2048;         // workgroups of the direct-path kernels
+    int64_t bwd_lds_cap = BWD_CAP_DEFAULT; // backward push: entries per target's LDS table (at most BWD_CAP_MAX); a target with more goes to the global tier; 0: every target does
+    int64_t bwd_chunk = 0;       // backward push: targets per chunk (0: as many as the entry budget from free HBM holds)
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
     {"direct", &Tunables::direct, true}, {"force_wide", &Tunables::force_wide, true}, {"pass_bins", &Tunables::pass_bins, true},
@@ -87,6 +90,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"wx", &Tunables::wx, false}, {"tail", &Tunables::tail, false}, {"tail_always", &Tunables::tail_always, false},
     {"select_compact", &Tunables::select_compact, false}, {"pipeline", &Tunables::pipeline, false}, {"team", &Tunables::team, true}, {"team_size", &Tunables::team_size, true}, {"team_tail", &Tunables::team_tail, false}, {"team_xcd", &Tunables::team_xcd, false}, {"team_max", &Tunables::team_max, true}, {"team_hubs", &Tunables::team_hubs, true}, {"team_log", &Tunables::team_log, false}, {"topk_bk_div", &Tunables::topk_bk_div, true}, {"quads", &Tunables::quads, false}, {"team_timeout_ms", &Tunables::team_timeout_ms, false}, {"team_abort_level", &Tunables::team_abort_level, false}, {"acc_group", &Tunables::acc_group, false}, {"slot_major", &Tunables::slot_major, false}, {"team_coop", &Tunables::team_coop, false}, {"tail_hubs", &Tunables::tail_hubs, false}, {"rounds", &Tunables::rounds, false}, {"defer", &Tunables::defer, true}, {"defer_min", &Tunables::defer_min, false}, {"round_div", &Tunables::round_div, false},
     {"profile", &Tunables::profile, false}, {"grid", &Tunables::grid, false},
+    {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -251,6 +255,24 @@ struct fora_ctx {
     size_t ev_used = 0;
     fora_timing timing{};
     int grid_blocks = 2048;
+
+    // backward push (fora_bwd.h): reverse CSR (built on first use, freed with the graph) and its own buffers, apart from
+    // the FORA workspace; grow-only
+    int64_t *d_rin_ptr = nullptr;
+    int32_t *d_rin = nullptr;
+    int32_t *d_bt = nullptr;         // targets of the call
+    uint32_t *d_bcnt = nullptr, *d_bspill = nullptr, *d_blist = nullptr;
+    uint8_t *d_bflag = nullptr;
+    uint64_t *d_boff = nullptr;
+    uint64_t bt_cap = 0;
+    uint32_t *d_enode = nullptr;     // entries of a chunk
+    uint64_t *d_ep = nullptr, *d_er = nullptr;
+    uint64_t e_cap = 0;
+    uint64_t *d_gr = nullptr, *d_gp = nullptr, *d_gfy = nullptr; // global tier: [g_wgs][n] each, kept zero
+    uint32_t *d_gtag = nullptr, *d_glist = nullptr, *d_gfn = nullptr;
+    uint32_t g_wgs = 0;
+    unsigned long long *d_bstat = nullptr;
+    double bwd_ms = 0, combine_ms = 0; // event times of the call in progress (EvPair kinds 11, 12)
 };
 
 namespace {
@@ -280,6 +302,8 @@ void free_graph(fora_ctx *c) {
     dfree(c->d_colt); dfree(c->d_team_rowq); dfree(c->d_team_off); dfree(c->d_team_n2l); dfree(c->d_team_l2n); dfree(c->d_team_deg16); dfree(c->d_team_rowl); dfree(c->d_team_hubtgt); c->team_H = 0; c->team_T = 0; c->team_R = 0; c->team_cap = 0; c->team_checked = false;
     dfree(c->d_dg_perm); dfree(c->d_dg_inv); dfree(c->d_dg_colp); dfree(c->d_dg_rec); dfree(c->d_dg_T); dfree(c->d_dg_invb);
     c->dg = WalkDG{};
+    dfree(c->d_rin_ptr); dfree(c->d_rin);
+    dfree(c->d_gr); dfree(c->d_gp); dfree(c->d_gfy); dfree(c->d_gtag); dfree(c->d_glist); dfree(c->d_gfn); c->g_wgs = 0; // (sized by n)
     c->split_pbins = 0;
     c->n = 0; c->nnz = 0;
 }
@@ -782,6 +806,8 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case 7: c->timing.walk_accum_ms += ms; break;
         case 9: c->timing.push_tail_ms += ms; c->timing.push_tail_launches++; break;
         case 10: c->timing.push_team_ms += ms; c->timing.push_team_launches++; break;
+        case 11: c->bwd_ms += ms; break;     // backward push: reported through fora_bwd_stats only (fora_timing keeps its layout)
+        case 12: c->combine_ms += ms; break;
         case 8: c->timing.push_accum_ms += ms; break; // k_round_sweep: part of the level's accumulate time, not a launch of its own in the counts
         }
     }
@@ -1600,6 +1626,8 @@ void fora_hip_destroy(fora_ctx *c) {
     free_workspace(c);
     free_index(c);
     free_graph(c);
+    dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
+    dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er); dfree(c->d_bstat);
     dfree(c->d_stamps);
     for (auto &p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2591,6 +2619,20 @@ static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, doubl
 // Monte-Carlo: W walks per source (k_walk_mc), W = the integers i >= 0 with i < omega, omega = montecarlo_setting
 // (algo.h:477-483).  A launch runs at most MC_LAUNCH_WALKS walks over all slots of the batch.
 constexpr uint64_t MC_LAUNCH_WALKS = 1ull << 28;
+// walks j < W of every slot of the batch (k_walk_mc) into the slots' ppr slabs, walk j carrying wbase + (j < wrem) units
+static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, uint64_t W, uint64_t wbase, uint64_t wrem) {
+    // walk numbers per launch and per workgroup: about eight workgroups per CU, 4 Ki .. 64 Ki walks each
+    const uint64_t span = std::max<uint64_t>(1, MC_LAUNCH_WALKS / (uint64_t)nb);
+    for (uint64_t j0 = 0; j0 < W; j0 += span) {
+        const uint64_t j1 = std::min(W, j0 + span);
+        const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
+        const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
+        const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
+        const int h = ev_begin(c, 3);
+        hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, wbase, wrem, j0, j1, per_wg);
+        ev_end(c, h);
+    }
+}
 static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out,
                                  uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
     if (!c) return FORA_E_ARG;
@@ -2621,17 +2663,7 @@ static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, do
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
         const Dev d = make_dev(c, nb, false);
-        // walk numbers per launch and per workgroup: about eight workgroups per CU, 4 Ki .. 64 Ki walks each
-        const uint64_t span = std::max<uint64_t>(1, MC_LAUNCH_WALKS / (uint64_t)nb);
-        for (uint64_t j0 = 0; j0 < W; j0 += span) {
-            const uint64_t j1 = std::min(W, j0 + span);
-            const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
-            const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
-            const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
-            const int h = ev_begin(c, 3);
-            hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, wbase, wrem, j0, j1, per_wg);
-            ev_end(c, h);
-        }
+        launch_mc_walks(c, d, nb, W, wbase, wrem);
         {
             const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
             const int h = ev_begin(c, 4);
@@ -2689,6 +2721,407 @@ int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double e
     return with_bucket_retry(c, [&] {
         return fwdpush_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, reserve_fix_out, residue_fix_out, k, ids, scores, stats);
     });
+}
+
+// ---- backward push (reverse_local_update_linear, algo.h:703-751) and --algo bippr (bippr_query, query.h:71-124; bippr_query_topk
+// :126-193).  The pushes run in two passes over the call's targets: a count pass (entries per target, counters, the targets
+// that overflow the LDS tier) and, chunk by chunk, a write pass that runs the same pushes again and writes their entries
+// target-major.  Chunks follow from the counts, so no chunk boundary depends on anything but the entry budget.
+struct DevTmp { // device buffer freed on every return path
+    void *p = nullptr;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+};
+static int ensure_reverse_csr(fora_ctx *c) {
+    if (c->d_rin_ptr) return FORA_OK;
+    const uint64_t n = (uint64_t)c->n, nnz = (uint64_t)c->nnz;
+    DevTmp indeg, cursor;
+    HIPCHK(c, hipMalloc(&indeg.p, n * 4));
+    HIPCHK(c, hipMemsetAsync(indeg.p, 0, n * 4, c->stream));
+    if (nnz) hipLaunchKernelGGL(k_rev_count, dim3((unsigned)std::min<uint64_t>((nnz + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream,
+                                (const int32_t *)c->d_col, nnz, (uint32_t *)indeg.p);
+    std::vector<uint32_t> h_in(n);
+    HIPCHK(c, hipMemcpyAsync(h_in.data(), indeg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int64_t> rp(n + 1);
+    rp[0] = 0;
+    for (uint64_t v = 0; v < n; v++) rp[v + 1] = rp[v] + h_in[v];
+    HIPCHK(c, hipMalloc(&c->d_rin_ptr, (n + 1) * 8));
+    HIPCHK(c, hipMalloc(&c->d_rin, std::max<uint64_t>(1, nnz) * 4));
+    HIPCHK(c, hipMalloc(&cursor.p, std::max<uint64_t>(1, n) * 8));
+    HIPCHK(c, hipMemcpyAsync(c->d_rin_ptr, rp.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cursor.p, rp.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rev_fill, dim3((unsigned)std::min<uint64_t>((n * 64 + BLOCK - 1) / BLOCK, 16384)), dim3(BLOCK), 0, c->stream,
+                       (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col, c->n, (unsigned long long *)cursor.p, c->d_rin);
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors and the cursor go out of scope)
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("reverse CSR: ") + hipGetErrorString(e));
+    return FORA_OK;
+}
+
+static int ensure_bwd_targets(fora_ctx *c, uint64_t nt) {
+    if (!c->d_bstat) HIPCHK(c, hipMalloc(&c->d_bstat, BS_WORDS * 8));
+    if (c->bt_cap >= nt && c->d_bt) return FORA_OK;
+    dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
+    c->bt_cap = 0;
+    const uint64_t m = std::max<uint64_t>(1, nt);
+    HIPCHK(c, hipMalloc(&c->d_bt, m * 4));
+    HIPCHK(c, hipMalloc(&c->d_bcnt, m * 4));
+    HIPCHK(c, hipMalloc(&c->d_bspill, m * 4));
+    HIPCHK(c, hipMalloc(&c->d_blist, m * 4));
+    HIPCHK(c, hipMalloc(&c->d_bflag, m));
+    HIPCHK(c, hipMalloc(&c->d_boff, (m + 1) * 8));
+    c->bt_cap = m;
+    return FORA_OK;
+}
+
+// global tier: dense slabs for up to 64 targets in flight, 36 bytes per node each, at most a quarter of the free HBM
+static int ensure_global_tier(fora_ctx *c) {
+    if (c->d_gr) return FORA_OK;
+    const uint64_t n = (uint64_t)c->n;
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>({64, (uint64_t)c->prop.multiProcessorCount, (uint64_t)(fr / 4) / (36 * n)}));
+    HIPCHK(c, hipMalloc(&c->d_gr, g * n * 8));
+    HIPCHK(c, hipMalloc(&c->d_gp, g * n * 8));
+    HIPCHK(c, hipMalloc(&c->d_gfy, g * n * 8));
+    HIPCHK(c, hipMalloc(&c->d_gtag, g * n * 4));
+    HIPCHK(c, hipMalloc(&c->d_glist, g * n * 4));
+    HIPCHK(c, hipMalloc(&c->d_gfn, g * n * 4));
+    // (on the ctx stream: it does not synchronise with the null stream, and the first global-tier kernel must see zeros)
+    HIPCHK(c, hipMemsetAsync(c->d_gr, 0, g * n * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_gp, 0, g * n * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_gtag, 0, g * n * 4, c->stream));
+    c->g_wgs = (uint32_t)g;
+    return FORA_OK;
+}
+
+struct BwdRun {
+    uint64_t thr = 0, afix = 0;
+    uint32_t cap = 0;
+    std::vector<uint32_t> cnt;   // entries per target
+    std::vector<uint32_t> spill; // targets of the global tier, ascending
+    std::vector<uint64_t> off;   // first entry of target i over the whole call (nt + 1)
+    std::vector<std::pair<uint32_t, uint32_t>> chunks; // [t0, t1)
+    uint64_t stat[BS_WORDS] = {};
+};
+
+static BwdDev make_bwd(fora_ctx *c, const BwdRun &r) {
+    BwdDev b{};
+    b.rin_ptr = c->d_rin_ptr; b.rin = c->d_rin; b.deg = c->d_deg;
+    b.targets = c->d_bt; b.cap = r.cap; b.thr = r.thr; b.afix = r.afix;
+    b.cnt = c->d_bcnt; b.spilled = c->d_bflag; b.spill = c->d_bspill; b.stat = c->d_bstat;
+    b.off = c->d_boff; b.e_node = c->d_enode; b.e_p = c->d_ep; b.e_r = c->d_er;
+    b.g_r = c->d_gr; b.g_p = c->d_gp; b.g_fy = c->d_gfy; b.g_tag = c->d_gtag; b.g_list = c->d_glist; b.g_fn = c->d_gfn;
+    b.n = (uint32_t)c->n;
+    b.err = (uint32_t *)(c->d_bstat + BS_WORDS - 1);
+    return b;
+}
+
+static unsigned bwd_grid(const fora_ctx *c, uint64_t items, uint64_t per_cu) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(items, (uint64_t)c->prop.multiProcessorCount * per_cu));
+}
+
+static int bwd_check_err(fora_ctx *c, const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return FORA_OK;
+}
+
+// count pass over the nt targets already in d_bt; then the chunks
+static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
+    r.thr = (uint64_t)std::floor(std::ldexp(rmax, 60));
+    r.afix = (uint64_t)std::ldexp(c->alpha, 62); // (as the forward push: make_dev's afix)
+    r.cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.bwd_lds_cap, 0), BWD_CAP_MAX);
+    HIPCHK(c, hipMemsetAsync(c->d_bstat, 0, BS_WORDS * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_bflag, 0, nt, c->stream));
+    const int h = ev_begin(c, 11);
+    if (r.cap > 0) {
+        BwdDev b = make_bwd(c, r);
+        b.nlist = nt;
+        hipLaunchKernelGGL((k_bwd_push<false, false>), dim3(bwd_grid(c, nt, 8)), dim3(BLOCK), 0, c->stream, b);
+    }
+    HIPCHK(c, hipMemcpyAsync(r.stat, c->d_bstat, BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (r.cap > 0) {
+        r.spill.resize(r.stat[BS_SPILL]);
+        if (!r.spill.empty()) {
+            HIPCHK(c, hipMemcpy(r.spill.data(), c->d_bspill, r.spill.size() * 4, hipMemcpyDeviceToHost));
+            std::sort(r.spill.begin(), r.spill.end());
+        }
+    } else {
+        r.spill.resize(nt);
+        for (uint32_t i = 0; i < nt; i++) r.spill[i] = i;
+    }
+    if (!r.spill.empty()) {
+        if (int rc = ensure_global_tier(c)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_blist, r.spill.data(), r.spill.size() * 4, hipMemcpyHostToDevice, c->stream));
+        BwdDev b = make_bwd(c, r);
+        b.list = c->d_blist;
+        b.nlist = (uint32_t)r.spill.size();
+        hipLaunchKernelGGL((k_bwd_push<true, false>), dim3(std::min<uint32_t>(c->g_wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
+    }
+    ev_end(c, h);
+    r.cnt.resize(nt);
+    HIPCHK(c, hipMemcpyAsync(r.cnt.data(), c->d_bcnt, (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.stat, c->d_bstat, BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int rc = bwd_check_err(c, "backward push")) return rc;
+    if (r.stat[BS_WORDS - 1] & 0xFFFFFFFFull) return fail(c, FORA_E_OVERFLOW, "backward push: level cap reached");
+    r.off.assign((size_t)nt + 1, 0);
+    for (uint32_t i = 0; i < nt; i++) r.off[i + 1] = r.off[i] + r.cnt[i];
+    // chunks: at most bwd_chunk targets, at most the entries a fifth of the free HBM holds (20 bytes each)
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t have = c->e_cap;
+    const uint64_t budget = std::max<uint64_t>({have, (uint64_t)(fr / 5) / 20, (uint64_t)BWD_CAP_MAX});
+    const uint64_t per = c->opt_.bwd_chunk > 0 ? (uint64_t)c->opt_.bwd_chunk : ~0ull;
+    r.chunks.clear();
+    for (uint32_t t0 = 0; t0 < nt;) {
+        uint32_t t1 = t0 + 1; // (one target always fits: a global-tier target has at most n entries, see the budget check below)
+        while (t1 < nt && t1 - t0 < per && r.off[t1 + 1] - r.off[t0] <= budget) t1++;
+        r.chunks.push_back({t0, t1});
+        t0 = t1;
+    }
+    return FORA_OK;
+}
+
+// write pass of chunk k: entries of its targets into d_enode / d_ep / d_er, offsets d_boff (chunk-relative)
+static int bwd_write(fora_ctx *c, const BwdRun &r, size_t k) {
+    const uint32_t t0 = r.chunks[k].first, t1 = r.chunks[k].second, len = t1 - t0;
+    const uint64_t ne = r.off[t1] - r.off[t0];
+    if (c->e_cap < ne) {
+        dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er);
+        c->e_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_enode, ne * 4));
+        HIPCHK(c, hipMalloc(&c->d_ep, ne * 8));
+        HIPCHK(c, hipMalloc(&c->d_er, ne * 8));
+        c->e_cap = ne;
+    }
+    std::vector<uint64_t> off((size_t)len + 1);
+    for (uint32_t i = 0; i <= len; i++) off[i] = r.off[t0 + i] - r.off[t0];
+    std::vector<uint32_t> gl;
+    for (auto it = std::lower_bound(r.spill.begin(), r.spill.end(), t0); it != r.spill.end() && *it < t1; ++it) gl.push_back(*it - t0);
+    HIPCHK(c, hipMemcpyAsync(c->d_boff, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (!gl.empty()) HIPCHK(c, hipMemcpyAsync(c->d_blist, gl.data(), gl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int h = ev_begin(c, 11);
+    BwdDev b = make_bwd(c, r);
+    b.targets = c->d_bt + t0;
+    b.spilled = c->d_bflag + t0;
+    if (r.cap > 0 && gl.size() < len) {
+        b.nlist = len;
+        hipLaunchKernelGGL((k_bwd_push<false, true>), dim3(bwd_grid(c, len, 8)), dim3(BLOCK), 0, c->stream, b);
+    }
+    if (!gl.empty()) {
+        b.list = c->d_blist;
+        b.nlist = (uint32_t)gl.size();
+        hipLaunchKernelGGL((k_bwd_push<true, true>), dim3(std::min<uint32_t>(c->g_wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
+    }
+    ev_end(c, h);
+    uint64_t st[BS_WORDS];
+    HIPCHK(c, hipMemcpyAsync(st, c->d_bstat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (off / gl are host vectors of this frame)
+    if (int rc = bwd_check_err(c, "backward push (write)")) return rc;
+    if (st[BS_WORDS - 1] & 0xFFFFFFFFull) {
+        const uint64_t i = st[BS_BAD] ? st[BS_BAD] - 1 + t0 : 0;
+        char buf[200];
+        snprintf(buf, sizeof(buf), "backward push: write pass disagrees with its count pass (target index %llu, %u entries counted, %s tier)",
+                 (unsigned long long)i, st[BS_BAD] ? r.cnt[i] : 0u, std::binary_search(r.spill.begin(), r.spill.end(), (uint32_t)i) ? "global" : "LDS");
+        return fail(c, FORA_E_OVERFLOW, buf);
+    }
+    return FORA_OK;
+}
+
+static int check_bwd_rmax(fora_ctx *c, double rmax) {
+    if (!(rmax > 0) || !std::isfinite(rmax)) return fail(c, FORA_E_ARG, "rmax must be > 0");
+    // every residue stays below max(1, rmax / alpha) and every estimate below 1 + that: u64 at 2^60 holds less than 16
+    if (!(1.0 + std::max(1.0, rmax / c->alpha) < 16.0)) return fail(c, FORA_E_ARG, "rmax / alpha too large for the 2^60 fixed point");
+    return FORA_OK;
+}
+
+static void fill_bwd_stats(fora_ctx *c, const BwdRun &r, uint64_t nt, fora_bwd_stats *bwd, double walk_ms) {
+    if (!bwd) return;
+    memset(bwd, 0, sizeof(*bwd));
+    bwd->targets = nt;
+    bwd->pops = r.stat[BS_POPS];
+    bwd->relax = r.stat[BS_RELAX];
+    bwd->entries = r.stat[BS_ENTRIES];
+    bwd->global_targets = r.spill.size();
+    bwd->levels = (int32_t)r.stat[BS_LEVELS];
+    bwd->chunks = (int32_t)r.chunks.size();
+    bwd->bwd_ms = c->bwd_ms;
+    bwd->walk_ms = walk_ms;
+    bwd->combine_ms = c->combine_ms;
+}
+
+static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
+                              uint64_t *residue_fix_out, fora_bwd_stats *bwd) {
+    if (!c) return FORA_E_ARG;
+    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha)");
+    if (nt < 0 || (nt && !targets)) return fail(c, FORA_E_ARG, "bad targets");
+    for (int i = 0; i < nt; i++)
+        if (targets[i] < 0 || targets[i] >= c->n) return fail(c, FORA_E_ARG, "target id out of range");
+    if (int rc = check_bwd_rmax(c, rmax)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->bwd_ms = c->combine_ms = 0;
+    BwdRun r;
+    if (nt == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
+    if (int rc = ensure_reverse_csr(c)) return rc;
+    if (int rc = ensure_bwd_targets(c, (uint64_t)nt)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bt, targets, (size_t)nt * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = bwd_count(c, (uint32_t)nt, rmax, r)) return rc;
+    const uint64_t n = (uint64_t)c->n;
+    if (reserve_fix_out) memset(reserve_fix_out, 0, (size_t)nt * n * 8);
+    if (residue_fix_out) memset(residue_fix_out, 0, (size_t)nt * n * 8);
+    for (size_t k = 0; k < r.chunks.size() && (reserve_fix_out || residue_fix_out); k++) {
+        if (int rc = bwd_write(c, r, k)) return rc;
+        const uint32_t t0 = r.chunks[k].first, t1 = r.chunks[k].second;
+        const uint64_t ne = r.off[t1] - r.off[t0];
+        std::vector<uint32_t> nd(ne);
+        std::vector<uint64_t> p(ne), q(ne);
+        HIPCHK(c, hipMemcpy(nd.data(), c->d_enode, ne * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(p.data(), c->d_ep, ne * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(q.data(), c->d_er, ne * 8, hipMemcpyDeviceToHost));
+        for (uint32_t i = t0; i < t1; i++)
+            for (uint64_t e = r.off[i] - r.off[t0]; e < r.off[i + 1] - r.off[t0]; e++) {
+                if (reserve_fix_out) reserve_fix_out[(uint64_t)i * n + nd[e]] = p[e];
+                if (residue_fix_out) residue_fix_out[(uint64_t)i * n + nd[e]] = q[e];
+            }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ev_collect(c);
+    fill_bwd_stats(c, r, (uint64_t)nt, bwd, 0);
+    return FORA_OK;
+}
+
+static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
+                            uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
+    if (!c) return FORA_E_ARG;
+    if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
+    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    if (!(rmax_scale > 0) || !std::isfinite(rmax_scale)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
+    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
+    double rmax = epsilon * sqrt(c->m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, algo.h:442-447
+    rmax *= rmax_scale;
+    const double omega = rmax * 3 * log(2.0 / pfail) / delta / epsilon / epsilon;
+    if (int rc = check_bwd_rmax(c, rmax)) return rc;
+    if (!(omega < 0x1p48)) return fail(c, FORA_E_ARG, "epsilon too small: more than 2^48 walks per source");
+    const uint64_t W = (uint64_t)std::ceil(omega); // for (unsigned long i = 0; i < config.omega; i++)
+    if (W == 0) return fail(c, FORA_E_ARG, "no walks");
+    const uint64_t wbase = FIX_ONE / W, wrem = FIX_ONE % W;
+    const bool want_topk = k > 0 && (ids || scores);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->bwd_ms = c->combine_ms = 0;
+    const double walk_ms0 = c->timing.walk_ms;
+    BwdRun r;
+    if (nq == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
+    c->bk_div = 1;
+    int rc = ensure_workspace(c, nq, c->omega); // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
+    if (rc) return rc;
+    const uint64_t n = (uint64_t)c->n;
+    if (want_topk && c->topk_cap < c->B * k) {
+        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
+        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
+        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
+        c->topk_cap = c->B * k;
+    }
+    // every node is a target (query.h:91: for i < graph.n)
+    if ((rc = ensure_reverse_csr(c))) return rc;
+    if ((rc = ensure_bwd_targets(c, n))) return rc;
+    {
+        std::vector<int32_t> iota(n);
+        for (uint64_t v = 0; v < n; v++) iota[v] = (int32_t)v;
+        HIPCHK(c, hipMemcpyAsync(c->d_bt, iota.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = bwd_count(c, (uint32_t)n, rmax, r))) return rc; // (synchronises)
+    }
+    const bool one_chunk = r.chunks.size() == 1;
+    if (one_chunk && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
+    const int per = even_batch(nq, c->B);
+    for (int b0 = 0; b0 < nq; b0 += per) {
+        const int nb = std::min(per, nq - b0);
+        const int hb = ev_begin(c, 5);
+        rc = reset_batch_state(c, nb, sources + b0);
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
+        const Dev d = make_dev(c, nb, false);
+        launch_mc_walks(c, d, nb, W, wbase, wrem); // walk slabs c_b at 2^-62 in d_ppr
+        const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
+        int h = ev_begin(c, 12);
+        hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+                           (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
+        ev_end(c, h);
+        for (size_t ck = 0; ck < r.chunks.size(); ck++) {
+            if (!one_chunk && (rc = bwd_write(c, r, ck))) return rc;
+            const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
+            h = ev_begin(c, 12);
+            hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
+                               (const uint64_t *)c->d_residue, (uint32_t)nb, (const int32_t *)c->d_src, (const uint64_t *)c->d_boff,
+                               (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->d_ppr);
+            ev_end(c, h);
+        }
+        h = ev_begin(c, 12);
+        hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+                           n, (uint64_t)nb); // -> slot-major estimates at 2^-60 in the residue slabs
+        ev_end(c, h);
+        Dev dr = d;
+        dr.ppr = c->d_residue;
+        {
+            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
+            h = ev_begin(c, 4);
+            hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dr);
+            ev_end(c, h);
+        }
+        if (want_topk) {
+            h = ev_begin(c, 4);
+            rc = launch_select(c, dr, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
+            if (rc) return rc;
+            ev_end(c, h);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        ev_end(c, hb);
+        rc = check_dev_err(c);
+        if (rc) return rc;
+        if ((rc = bwd_check_err(c, "bippr"))) return rc;
+        ev_collect(c);
+        c->timing.walks += W * (uint64_t)nb;
+        c->timing.walk_steps += *c->h_steps_pin;
+        if (stats)
+            for (int i = 0; i < nb; i++) {
+                fora_query_stats &o = stats[b0 + i];
+                memset(&o, 0, sizeof(o));
+                o.n_walks = W;
+                o.rmax_used = rmax;
+                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
+                o.dangling_source = c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]] ? 1 : 0;
+            }
+        if (want_topk) { // k_topk_select scales by 2^-62; the estimates are at 2^-60
+            std::vector<double> sc((size_t)nb * k);
+            if (ids) HIPCHK(c, hipMemcpy(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(sc.data(), c->d_topk_sc, sc.size() * 8, hipMemcpyDeviceToHost));
+            if (scores) for (size_t i = 0; i < sc.size(); i++) scores[(size_t)b0 * k + i] = sc[i] * 4;
+        }
+        const uint64_t bytes = (uint64_t)nb * n * 8;
+        if (ppr_fix_out) HIPCHK(c, hipMemcpy(ppr_fix_out + (uint64_t)b0 * n, c->d_residue, bytes, hipMemcpyDeviceToHost));
+        if (ppr_out) {
+            double *dst = ppr_out + (uint64_t)b0 * n;
+            HIPCHK(c, hipMemcpy(dst, c->d_residue, bytes, hipMemcpyDeviceToHost));
+            uint64_t *raw = (uint64_t *)dst;
+            for (uint64_t i = 0; i < (uint64_t)nb * n; i++) dst[i] = std::ldexp((double)raw[i], -60);
+        }
+    }
+    fill_bwd_stats(c, r, n, bwd, c->timing.walk_ms - walk_ms0);
+    return FORA_OK;
+}
+
+int fora_hip_bwdpush_batch(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
+                           uint64_t *residue_fix_out, fora_bwd_stats *bwd) {
+    return bwdpush_batch_impl(c, targets, nt, rmax, reserve_fix_out, residue_fix_out, bwd);
+}
+
+int fora_hip_bippr_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
+                         uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
+    return bippr_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, ppr_fix_out, k, ids, scores, stats, bwd);
 }
 
 int fora_hip_reset_timing(fora_ctx *c) {

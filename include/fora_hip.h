@@ -36,6 +36,29 @@
  * i.e. it ends where orc_walk(g, seed, s, 0, s, j) and fora_hip_walks(stream s, round 0, no_zero_hop 0, start s, j) end.
  * It carries floor(2^62 / W) + (j < 2^62 mod W) units to its endpoint, so sum(ppr) == FORA_FIX_ONE exactly; the
  * reference's cnt / omega differs from that by a factor omega / W, between 1 - 1/omega and 1.
+ * BACKWARD PUSH (fora_hip_bwdpush_batch; reverse_local_update_linear, algo.h:703-751) works at its own fixed point,
+ * 1.0 == FORA_BWD_FIX_ONE == 2^60.  Target t starts from r = e_t * 2^60, p = 0; thr = floor(rmax * 2^60), and a node
+ * pops iff r[v] > thr (the reference's `> myeps`, algo.h:743).  The push is level-synchronous: at each level every v
+ * of F = {v : r[v] > thr} pops at the same moment -- x = r[v], r[v] = 0, keep = floor(x * alpha62 / 2^62) with
+ * alpha62 = floor(alpha * 2^62) (the forward push's alpha), p[v] += keep, y = x - keep -- and every in-edge u -> v of the
+ * CSR (duplicates each with its own share, self loops dropped as they are in the CSR) adds floor(y / outdeg(u)) to
+ * r[u]; all increments land after all pops of the level, and the push stops when F is empty.  The reference's FIFO
+ * order is not reproduced (its `break` on `< myeps`, algo.h:725, never fires: a queued residue only grows).
+ * Counters: pops, relaxations (in-edges traversed at every pop) and levels (levels with a non-empty F).
+ * Backward residues are not probability mass: a node under the threshold can collect (1 - alpha) * max r in one level,
+ * so every r stays below max(1, rmax / alpha) and every BiPPR estimate below 1 + max(1, rmax / alpha).  A u64 at 2^60
+ * holds values below 16: an (alpha, rmax) with 1 + max(1, rmax / alpha) >= 16 is FORA_E_ARG.
+ * BIPPR (fora_hip_bippr_batch; bippr_query, query.h:71-124; bippr_query_topk :126-193): bippr_setting (algo.h:442-447)
+ * in the reference's operand order with delta = pfail = 1/n, m = m_attr:
+ * rmax = epsilon*sqrt(m*1.0*delta/3.0/log(2.0/pfail)); rmax *= rmax_scale; omega = rmax*3*log(2.0/pfail)/delta/epsilon/epsilon;
+ * W = ceil(omega), FORA_E_ARG unless 1 <= W < 2^48.  The ctx's alpha and seed are used, its FORA rmax / omega are left
+ * untouched.  c = the walk slab at 2^-62: walks j < W with start = stream = s, round 0, each carrying
+ * floor(2^62 / W) + (j < 2^62 mod W) units (the Monte-Carlo slab of fora_hip_montecarlo_batch, with W walks).  For every
+ * node i (a backward push to target i at rmax, giving p_i, r_i): ppr[i] = p_i[s] + sum_v floor(c[v] * r_i[v] / 2^62), at
+ * 2^60, each term floored on its own from the 128-bit product and the terms added as integers.  With rmax >= 1 nothing
+ * pops and ppr[i] = floor(c[i] / 4) (the reference's else branch, query.h:114-119).  A dangling source keeps the
+ * reference's bias: every walk stops at s and no in-edge reaches s, so ppr = keep(2^60) at s and 0 elsewhere.  Double
+ * outputs are value * 2^-60; sum(ppr) (ppr_sum_fix) is NOT conserved (an estimate, not a distribution).
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -46,6 +69,7 @@ extern "C" {
 
 #define FORA_FIX_ONE (1ULL << 62)
 #define FORA_STREAM_INDEX 0xFFFFFFFFu
+#define FORA_BWD_FIX_ONE (1ULL << 60)
 
 enum {
     FORA_OK = 0,
@@ -103,6 +127,15 @@ typedef struct {
     double push_team_ms;    /* k_push_team launches (graphs of the narrow layout: the whole push above the tail, one launch per batch) */
     uint64_t push_team_launches;
 } fora_timing;
+
+/* Counters of a backward-push sweep (fora_hip_bwdpush_batch, fora_hip_bippr_batch).  Sums over the call's pushes. */
+typedef struct {
+    uint64_t targets, pops, relax;   /* sums over the call's backward pushes */
+    uint64_t entries;                /* non-zero (node, target) reserve + residue entries produced */
+    uint64_t global_targets;         /* targets that overflowed the LDS tier */
+    int32_t levels, chunks;          /* deepest push; target chunks the call used */
+    double bwd_ms, walk_ms, combine_ms;
+} fora_bwd_stats;
 
 /* ---- lifecycle ---------------------------------------------------------- */
 int fora_hip_device_count(void); /* usable HIP devices (0 when there is none) */
@@ -221,10 +254,27 @@ int fora_hip_fwdpush_batch(fora_ctx *ctx, const int32_t *sources, int nq, double
                            double *ppr_out, uint64_t *reserve_fix_out, uint64_t *residue_fix_out,
                            int k, int32_t *ids, double *scores, fora_query_stats *stats);
 
+/* --algo bippr: bippr_query / bippr_query_topk (query.h:71-193), estimate as in the BIPPR contract above; ppr_out /
+ * ppr_fix_out at 2^-60 / 2^60, top-k scores = estimate * 2^-60.  The n backward pushes run once per call (chunk by chunk
+ * when their entries outgrow the budget from free HBM; a call of several batches then runs them once per batch) and
+ * are shared by every source of it.  Stats: n_walks = W, rmax_used, dangling_source, ppr_sum_fix; every other field 0.
+ * Timing: walks, walk_steps, walk_ms; backward push and combine times only in *bwd (NULL: not wanted).  Options
+ * "bwd_lds_cap" (entries per LDS table, 0: every target on the global tier) and "bwd_chunk" (targets per chunk, 0: by
+ * memory) change no bit. */
+int fora_hip_bippr_batch(fora_ctx *ctx, const int32_t *sources, int nq, double epsilon, double rmax_scale,
+                         double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores,
+                         fora_query_stats *stats, fora_bwd_stats *bwd);
+
 /* ---- stage hooks (same device code as the paths above, exposed for parity tests) */
 /* forward push only (forward_local_update_linear, algo.h:954-1018) */
 int fora_hip_push_batch(fora_ctx *ctx, const int32_t *sources, int nq, uint64_t *reserve_fix_out,
                         uint64_t *residue_fix_out, fora_query_stats *stats);
+/* reverse_local_update_linear for nt targets at the given rmax (the BACKWARD PUSH contract above): dense nt*n outputs at
+ * 2^60, either may be NULL; an approximate single-target PPR, pi(s, t) = reserve[s] + sum_v pi(s, v) * residue[v].  Uses
+ * the ctx's alpha, leaves its parameters untouched.  Bad targets, rmax <= 0 or out of the fixed point's range:
+ * FORA_E_ARG. */
+int fora_hip_bwdpush_batch(fora_ctx *ctx, const int32_t *targets, int nt, double rmax,
+                           uint64_t *reserve_fix_out, uint64_t *residue_fix_out, fora_bwd_stats *bwd);
 /* walk allocation in the reference's f64 arithmetic (query.h:270,282 / :349,:364):
  * residue: n doubles (<= 0 entries get 0 walks); returns N and num_s_rw[n]. */
 int fora_hip_walk_counts(fora_ctx *ctx, const double *residue, double rsum, uint64_t *num_s_rw,
