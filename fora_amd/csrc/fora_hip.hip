@@ -77,7 +77,6 @@ struct Tunables {
     int64_t topk_bk_div = 16;    // top-k (--opt driver) on wide graphs: message buckets of 1 / this of a query's capacity (plan_workspace); 1: as large as a query's.
                                  // Twitter-2010-sized, k = 500 --opt --with_idx, 125 sources: 1 -> 245 q/s (8 slots per batch), 8 -> 279 (30), 16 -> 303 (37), 32 -> 304 (41), 64 -> 306 (44); same bits
     int64_t quads = 1;           // wide layouts, one bin pass per level: k_pushq_bin reads quad-padded copies of col / col_hub with 16-byte loads (0: single edges, round 4)
-    int64_t pipeline = 0;        // 1: second lane (stream + workspace) when a call has more than one batch
     int64_t profile = 1;         // 0: no HIP event pairs around the launches
     int64_t grid = 2048;         // workgroups of the direct-path kernels
     int64_t bwd_lds_cap = BWD_CAP_DEFAULT; // backward push: entries per target's LDS table (at most BWD_CAP_MAX); a target with more goes to the global tier; 0: every target does
@@ -88,7 +87,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"no_split", &Tunables::no_split, true}, {"no_compact", &Tunables::no_compact, false}, {"walk_dg", &Tunables::walk_dg, false}, {"dg_hubs", &Tunables::dg_hubs, false}, {"hubs", &Tunables::hubs, true}, {"hubs_wide", &Tunables::hubs_wide, true}, {"hub_min", &Tunables::hub_min, false}, {"bkcap", &Tunables::bkcap, true},
     {"ovcap", &Tunables::ovcap, true}, {"tiny", &Tunables::tiny, false}, {"xb", &Tunables::xb, false}, {"ax", &Tunables::ax, false},
     {"wx", &Tunables::wx, false}, {"tail", &Tunables::tail, false}, {"tail_always", &Tunables::tail_always, false},
-    {"select_compact", &Tunables::select_compact, false}, {"pipeline", &Tunables::pipeline, false}, {"team", &Tunables::team, true}, {"team_size", &Tunables::team_size, true}, {"team_tail", &Tunables::team_tail, false}, {"team_xcd", &Tunables::team_xcd, false}, {"team_max", &Tunables::team_max, true}, {"team_hubs", &Tunables::team_hubs, true}, {"team_log", &Tunables::team_log, false}, {"topk_bk_div", &Tunables::topk_bk_div, true}, {"quads", &Tunables::quads, false}, {"team_timeout_ms", &Tunables::team_timeout_ms, false}, {"team_abort_level", &Tunables::team_abort_level, false}, {"acc_group", &Tunables::acc_group, false}, {"slot_major", &Tunables::slot_major, false}, {"team_coop", &Tunables::team_coop, false}, {"tail_hubs", &Tunables::tail_hubs, false}, {"rounds", &Tunables::rounds, false}, {"defer", &Tunables::defer, true}, {"defer_min", &Tunables::defer_min, false}, {"round_div", &Tunables::round_div, false},
+    {"select_compact", &Tunables::select_compact, false}, {"team", &Tunables::team, true}, {"team_size", &Tunables::team_size, true}, {"team_tail", &Tunables::team_tail, false}, {"team_xcd", &Tunables::team_xcd, false}, {"team_max", &Tunables::team_max, true}, {"team_hubs", &Tunables::team_hubs, true}, {"team_log", &Tunables::team_log, false}, {"topk_bk_div", &Tunables::topk_bk_div, true}, {"quads", &Tunables::quads, false}, {"team_timeout_ms", &Tunables::team_timeout_ms, false}, {"team_abort_level", &Tunables::team_abort_level, false}, {"acc_group", &Tunables::acc_group, false}, {"slot_major", &Tunables::slot_major, false}, {"team_coop", &Tunables::team_coop, false}, {"tail_hubs", &Tunables::tail_hubs, false}, {"rounds", &Tunables::rounds, false}, {"defer", &Tunables::defer, true}, {"defer_min", &Tunables::defer_min, false}, {"round_div", &Tunables::round_div, false},
     {"profile", &Tunables::profile, false}, {"grid", &Tunables::grid, false},
     {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
 };
@@ -232,10 +231,6 @@ struct fora_ctx {
     std::vector<QState> h_qs;
     QState *h_qs_pin = nullptr;              // pinned landing area of the per-slot accumulators
     unsigned long long *h_steps_pin = nullptr;
-    // second lane: own stream + workspace, shares graph / index / params; lets the push of batch
-    // k+1 overlap the (fabric-bound) walks of batch k
-    fora_ctx *twin = nullptr;
-    bool is_twin = false;
     uint32_t bk_scale = 1;        // bucket capacity multiplier, doubled after a bucket overflow (see with_bucket_retry)
     uint32_t bk_scale_topk = 1;   // ... of the calls that plan with a divisor (bk_div > 1: the top-k driver on wide graphs).  Its own word: those calls start at 1 / 16 of a
                                   // query's buckets and overflow far more often; a doubling there must not shrink the batches of later query / power-iteration calls
@@ -247,7 +242,6 @@ struct fora_ctx {
     double c_pop = 2.0e-11, c_edge = 2.4e-11, t_walk = 6.5e-11, t_idx = 2.2e-11, bal_start = 8;
     std::vector<double> h_rmax_used;
     std::vector<int32_t> h_rounds;
-    int pending_nq = 0;                      // batch enqueued on this lane, not yet finished
 
     // timing
     bool profiling = true;
@@ -294,6 +288,10 @@ template <typename T> void dfree(T *&p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+struct DevTmp { // device buffer freed on every return path
+    void *p = nullptr;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+};
 
 void free_graph(fora_ctx *c) {
     dfree(c->d_row_ptr); dfree(c->d_col); dfree(c->d_rowinfo); dfree(c->d_deg); dfree(c->d_rp32); dfree(c->d_colp); dfree(c->d_col_push); dfree(c->d_row_split);
@@ -436,7 +434,6 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
 // pass of k_pushq_bin reads only its own part of each popped row.  Built once per (graph, pass size).
 int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
     const int npass = pbins > 0 ? (nbins + pbins - 1) / pbins : 1;
-    if (c->is_twin) return FORA_OK; // shares the first lane's tables (sync_twin)
     if (npass <= 1 || c->opt_.no_split) { dfree(c->d_col_push); dfree(c->d_row_split); c->split_pbins = 0; return FORA_OK; }
     if (c->d_row_split && c->split_pbins == pbins) return FORA_OK;
     dfree(c->d_col_push); dfree(c->d_row_split);
@@ -477,7 +474,6 @@ static bool want_team(const fora_ctx *c) {
     return on && want_binned(c) && !want_wide(c) && c->nnz > 0 && c->nnz < (1ll << 32); // (rowl / colt / off index edges with 32 bits)
 }
 int ensure_team(fora_ctx *c) {
-    if (c->is_twin) return FORA_OK; // shares the first lane's tables (sync_twin)
     const bool want = want_team(c);
     const uint32_t force = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_size, 0), TEAM_MAX);
     const uint32_t hubs_opt = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_hubs, 0), 4096);
@@ -582,7 +578,7 @@ int team_fits(fora_ctx *c);
 int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
     if (int rt = ensure_team(c)) return rt;
-    if (!c->is_twin && c->opt_.hubs < 0 && !want_wide(c) && c->hub_for_team != (want_team(c) && c->team_T != 0)) {
+    if (c->opt_.hubs < 0 && !want_wide(c) && c->hub_for_team != (want_team(c) && c->team_T != 0)) {
         // the `team` / `team_size` options changed which push this graph takes: the hub copy follows (see build_hub_copy)
         std::vector<int32_t> col((size_t)std::max<int64_t>(1, c->nnz));
         HIPCHK(c, hipMemcpy(col.data(), c->d_col, (size_t)c->nnz * 4, hipMemcpyDeviceToHost));
@@ -614,7 +610,7 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         free_workspace(c);
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
-        uint64_t budget = (uint64_t)(fr * (c->opt_.pipeline == 1 ? 0.4 : 0.75)); // with option pipeline a second lane holds its own workspace
+        uint64_t budget = (uint64_t)(fr * 0.75);
         if (c->team_T) { // the team push's own buffers (allocated below) come out of the same memory
             const uint64_t T = c->team_T, nt = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
             const uint64_t team_bytes = nt * (2 * c->team_cap * 4 + 3 * T * (c->team_R + 64 + c->team_H) * 8 + T * (10ull << 17) + 2 * T * T * 8);
@@ -831,6 +827,93 @@ int check_dev_err(fora_ctx *c) {
     return FORA_OK;
 }
 
+// ---- plumbing shared by the batch entry points
+// first checks of every batch call: graph and params present, `nq` ids behind a non-null pointer
+int check_batch_args(fora_ctx *c, const int32_t *ids, int nq, const char *what = "source") {
+    if (!c) return FORA_E_ARG;
+    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first");
+    if (nq < 0 || (nq && !ids)) return fail(c, FORA_E_ARG, std::string("bad ") + what + "s: negative count or null array");
+    return FORA_OK;
+}
+// ... and the last one, after the call's own arguments: every id in [0, n) (the ids are read only once all else passed)
+int check_id_range(fora_ctx *c, const int32_t *ids, int nq, const char *what = "source") {
+    for (int i = 0; i < nq; i++)
+        if (ids[i] < 0 || ids[i] >= c->n) return fail(c, FORA_E_ARG, std::string(what) + " id out of range");
+    return FORA_OK;
+}
+// k of a top-k output: what k_topk_select takes
+int check_k(fora_ctx *c, int k) {
+    if (k < 1 || k > SEL_MAXK || k > c->n) return fail(c, FORA_E_ARG, "k out of range (1 .. min(1024, n))");
+    return FORA_OK;
+}
+
+bool is_dangling(const fora_ctx *c, int32_t s) { return c->h_row_ptr[(size_t)s + 1] == c->h_row_ptr[(size_t)s]; }
+
+// a device (ids, scores) pair of B * k entries, grown on demand
+int grow_pair(fora_ctx *c, int k, int32_t *&ids, double *&scores, int &cap) {
+    if (cap >= c->B * k) return FORA_OK;
+    dfree(ids); dfree(scores);
+    cap = 0;
+    HIPCHK(c, hipMalloc(&ids, (size_t)c->B * k * 4));
+    HIPCHK(c, hipMalloc(&scores, (size_t)c->B * k * 8));
+    cap = c->B * k;
+    return FORA_OK;
+}
+
+// Slots [slot, slot + cnt) of a device slab into rows [row, row + cnt) of the caller's n-wide arrays (either may be null):
+// raw u64, and f64 at 2^-frac.
+int copy_slab_out(fora_ctx *c, const uint64_t *slab, uint64_t slot, uint64_t row, uint64_t cnt, uint64_t *fix_out, double *f64_out,
+                  int frac) {
+    const uint64_t n = (uint64_t)c->n, at = row * n, from = slot * n, len = cnt * n;
+    if (fix_out) HIPCHK(c, hipMemcpy(fix_out + at, slab + from, len * 8, hipMemcpyDeviceToHost));
+    if (f64_out) {
+        // u64 and f64 have the same size: copy raw, convert in place on the host
+        double *dst = f64_out + at;
+        HIPCHK(c, hipMemcpy(dst, slab + from, len * 8, hipMemcpyDeviceToHost));
+        const uint64_t *raw = (const uint64_t *)dst;
+        for (uint64_t x = 0; x < len; x++) dst[x] = std::ldexp((double)raw[x], -frac);
+    }
+    return FORA_OK;
+}
+
+// The top k of slots [0, nb) (c->d_topk_ids / d_topk_sc) into the caller's ids / scores (either may be null): slot i to row
+// rows[i], or to row row0 + i without rows; the scores times `scale`.
+int copy_topk_out(fora_ctx *c, int nb, int k, int32_t *ids, double *scores, uint64_t row0, const int *rows = nullptr, double scale = 1.0) {
+    std::vector<int32_t> hid(ids ? (size_t)nb * k : 0);
+    std::vector<double> hsc(scores ? (size_t)nb * k : 0);
+    if (ids) HIPCHK(c, hipMemcpyAsync(hid.data(), c->d_topk_ids, hid.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    if (scores) HIPCHK(c, hipMemcpyAsync(hsc.data(), c->d_topk_sc, hsc.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the ctx stream does not synchronise with the null stream)
+    for (int i = 0; i < nb; i++) {
+        const uint64_t at = (rows ? (uint64_t)rows[i] : row0 + (uint64_t)i) * (uint64_t)k;
+        if (ids) memcpy(ids + at, hid.data() + (size_t)i * k, (size_t)k * 4);
+        if (scores) for (int j = 0; j < k; j++) scores[at + j] = hsc[(size_t)i * k + j] * scale;
+    }
+    return FORA_OK;
+}
+
+// End of a batch: close its event pair, read the device error word (waits for the stream), check the launches, collect
+// the event times.
+int close_batch(fora_ctx *c, int hb, const char *what) {
+    ev_end(c, hb);
+    if (int rc = check_dev_err(c)) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    ev_collect(c);
+    return FORA_OK;
+}
+
+// the per-slot counters of a batch (host copy of its QState words) into fora_timing
+void fold_counters(fora_ctx *c, const QState *qs, int nb) {
+    for (int i = 0; i < nb; i++) {
+        c->timing.pops += qs[i].pops;
+        c->timing.relax += qs[i].relax;
+        c->timing.walks += qs[i].n_walks;
+        c->timing.idx_hits += qs[i].n_hit;
+    }
+}
+
 // Level loop of the push for the slots already initialised (level-0 frontier in place).
 // Launches run ahead of the host by SPEC levels: an empty level costs a few near-empty
 // launches, a host round trip per level would cost more.
@@ -1008,9 +1091,9 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
 // Team push of a batch (fora_team.h): ONE launch runs every slot's push down to a small frontier with the residue
 // resident in LDS, k_push_tail finishes the slots.  Nothing here waits for the device.
 static bool use_team(const fora_ctx *c, const Dev &d) {
-    // not while a second lane may have its own full-chip team kernel in flight (option pipeline), not after a time-out
+    // not after a time-out
     return c->team_T && c->d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
-           c->team_fit != 0 && c->team_suspend == 0 && c->opt_.pipeline != 1 && !c->is_twin;
+           c->team_fit != 0 && c->team_suspend == 0;
 }
 // Can every workgroup of a k_push_team launch be resident at once?  (Asked once per workspace; raises the kernel's
 // dynamic LDS limit on the way.)
@@ -1205,9 +1288,6 @@ void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t rou
     }
 }
 
-// one batch of <= B sources: push (+ refinement).  Results stay in the slabs.
-// one batch of <= B sources, part 1: push (host-driven level loop, returns when the push is done)
-// and everything after it enqueued on the lane's stream.  Results stay in the slabs.
 // --balanced push of a batch (query.h:848-884): rounds of the incremental push (algo.h:1020-1093) with rmax halving
 // from 8*config.rmax; a slot keeps going while its estimated walk cost exceeds what its push has cost so far.
 int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
@@ -1222,7 +1302,7 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
     c->h_rmax_used.assign((size_t)nq, c->rmax);
     c->h_rounds.assign((size_t)nq, 1);
     for (int i = 0; i < nq; i++)
-        if (c->h_row_ptr[sources[i] + 1] == c->h_row_ptr[sources[i]]) active[i] = 0; // :864, :882
+        if (is_dangling(c, sources[i])) active[i] = 0; // :864, :882
     for (int i = 0; i < nq; i++) if (active[i]) c->h_rounds[i] = 0;
     double rmax = c->rmax * c->bal_start; // :862
     for (int round = 0;; round++) {
@@ -1260,9 +1340,9 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
     return FORA_OK;
 }
 
-int batch_begin(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int flags) {
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+// One batch of <= B sources: push (+ refinement) and k_ppr_sum, then the batch's close-out; its per-slot accumulators
+// land in h_qs.  Results stay in the slabs.
+int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int flags) {
     const int hb = ev_begin(c, 5);
     int rc = reset_batch_state(c, nq, sources);
     if (rc) return rc;
@@ -1297,80 +1377,31 @@ int batch_begin(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int 
     }
     HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    ev_end(c, hb);
-    c->pending_nq = nq;
-    return FORA_OK;
-}
-
-// part 2: wait for the lane, check device flags, fold timings and counters
-int batch_finish(fora_ctx *c) {
-    const int nq = c->pending_nq;
-    c->pending_nq = 0;
-    int rc = check_dev_err(c);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("batch: ") + hipGetErrorString(e));
-    ev_collect(c);
+    if ((rc = close_batch(c, hb, "batch"))) return rc;
     for (int i = 0; i < nq; i++) c->h_qs[i] = c->h_qs_pin[i];
     c->timing.walk_steps += *c->h_steps_pin;
-    for (int i = 0; i < nq; i++) {
-        c->timing.pops += c->h_qs[i].pops;
-        c->timing.relax += c->h_qs[i].relax;
-        c->timing.walks += c->h_qs[i].n_walks;
-        c->timing.idx_hits += c->h_qs[i].n_hit;
-    }
+    fold_counters(c, c->h_qs.data(), nq);
     return FORA_OK;
 }
 
-void fill_stats(const fora_ctx *c, int nq, fora_query_stats *out) {
-    for (int i = 0; i < nq; i++) {
-        const QState &s = c->h_qs[i];
-        fora_query_stats &o = out[i];
-        o.rsum_fix = FIX_ONE - s.reserved;
-        o.rsum = std::ldexp((double)o.rsum_fix, -62);
-        o.n_rw = s.n_rw; o.n_walks = s.n_walks; o.n_idx_hit = s.n_hit;
-        o.pops = s.pops; o.relax = s.relax; o.ppr_sum_fix = s.ppr_sum;
-        o.levels = (int32_t)s.levels; o.dangling_source = (int32_t)s.dangling_source;
-        o.rmax_used = c->balanced && (size_t)i < c->h_rmax_used.size() ? c->h_rmax_used[i] : c->rmax;
-        o.push_rounds = c->balanced && (size_t)i < c->h_rounds.size() ? c->h_rounds[i] : 1;
-        o.reserved_ = 0;
-    }
+// stats of slot i of the batch just run
+void fill_stats(const fora_ctx *c, int i, fora_query_stats &o) {
+    const QState &s = c->h_qs[i];
+    o.rsum_fix = FIX_ONE - s.reserved;
+    o.rsum = std::ldexp((double)o.rsum_fix, -62);
+    o.n_rw = s.n_rw; o.n_walks = s.n_walks; o.n_idx_hit = s.n_hit;
+    o.pops = s.pops; o.relax = s.relax; o.ppr_sum_fix = s.ppr_sum;
+    o.levels = (int32_t)s.levels; o.dangling_source = (int32_t)s.dangling_source;
+    o.rmax_used = c->balanced && (size_t)i < c->h_rmax_used.size() ? c->h_rmax_used[i] : c->rmax;
+    o.push_rounds = c->balanced && (size_t)i < c->h_rounds.size() ? c->h_rounds[i] : 1;
+    o.reserved_ = 0;
 }
 
-// (re)creates the second lane and mirrors graph / index / params into it (non-owning pointers)
-int sync_twin(fora_ctx *c) {
-    if (!c->twin) {
-        fora_ctx *w = new (std::nothrow) fora_ctx();
-        if (!w) return fail(c, FORA_E_NOMEM, "twin lane");
-        w->is_twin = true;
-        w->device = c->device;
-        w->prop = c->prop;
-        if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) { delete w; return fail(c, FORA_E_HIP, "twin stream"); }
-        w->profiling = c->profiling;
-        w->opt_ = c->opt_;
-        w->grid_blocks = c->grid_blocks;
-        c->twin = w;
-    }
-    fora_ctx *w = c->twin;
-    if (w->n != c->n || w->d_col != c->d_col) free_workspace(w);
-    w->n = c->n; w->m_attr = c->m_attr; w->nnz = c->nnz;
-    w->d_row_ptr = c->d_row_ptr; w->d_col = c->d_col; w->d_rowinfo = c->d_rowinfo; w->d_deg = c->d_deg;
-    w->d_rp32 = c->d_rp32; w->d_colp = c->d_colp; w->colbits = c->colbits;
-    w->dg = c->dg; // arrays owned by c
-    w->d_col_hub = c->d_col_hub; w->d_hub_node = c->d_hub_node; w->d_hub_first = c->d_hub_first; w->hubs = c->hubs; w->hub_shift = c->hub_shift;
-    w->d_col_push = c->d_col_push; w->d_row_split = c->d_row_split; w->split_pbins = c->split_pbins; // shared, owned by c
-    w->d_col4 = c->d_col4; w->d_col_hub4 = c->d_col_hub4; w->d_rowinfo4 = c->d_rowinfo4; w->quads = c->quads;
-    w->d_colt = c->d_colt; w->d_team_rowq = c->d_team_rowq; w->d_team_off = c->d_team_off; w->d_team_n2l = c->d_team_n2l; w->d_team_l2n = c->d_team_l2n; w->d_team_deg16 = c->d_team_deg16; w->d_team_rowl = c->d_team_rowl; w->d_team_hubtgt = c->d_team_hubtgt; w->team_H = c->team_H; w->team_T = c->team_T; w->team_R = c->team_R; w->team_cap = c->team_cap; w->dangling_frac = c->dangling_frac;
-    w->have_params = c->have_params; w->alpha = c->alpha; w->epsilon = c->epsilon; w->rmax_scale = c->rmax_scale;
-    w->rmax = c->rmax; w->omega = c->omega; w->opt = c->opt; w->seed = c->seed;
-    w->d_rw_idx = c->d_rw_idx; w->d_idx_off = c->d_idx_off; w->d_idx_cnt = c->d_idx_cnt;
-    w->idx_len = c->idx_len; w->have_index = c->have_index;
-    w->bk_scale = c->bk_scale; w->bk_scale_topk = c->bk_scale_topk;
-    w->d_stamps = c->d_stamps;
-    w->opt_ = c->opt_;
-    w->balanced = c->balanced; w->bal_start = c->bal_start; w->c_pop = c->c_pop; w->c_edge = c->c_edge; w->t_walk = c->t_walk; w->t_idx = c->t_idx;
-    w->batch_req = c->B; // same slot count as the first lane
-    return FORA_OK;
+// workspace of a call of `slots` queries at the ctx's omega, and the (ids, scores) pair of k entries per slot when k > 0
+int ensure_query_workspace(fora_ctx *c, int slots, int k) {
+    c->bk_div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
+    if (int rc = ensure_workspace(c, slots, c->omega)) return rc;
+    return k > 0 ? grow_pair(c, k, c->d_topk_ids, c->d_topk_sc, c->topk_cap) : FORA_OK;
 }
 
 // topk > 0: also the top-k of each slot's ppr slab (k_topk_select: score descending, ties id ascending, padded with (0, 0.0))
@@ -1378,14 +1409,10 @@ int sync_twin(fora_ctx *c) {
 int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int flags, double *ppr_d,
                  uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats, int topk = 0, int32_t *ids = nullptr,
                  double *scores = nullptr) {
-    if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first");
-    if (nq < 0 || (nq && !sources)) return fail(c, FORA_E_ARG, "bad sources");
+    if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
     HIPCHK(c, hipSetDevice(c->device));
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+    if (int rc = check_id_range(c, sources, nq)) return rc;
     const uint64_t n = (uint64_t)c->n;
     // A dangling source is its own whole answer (algo.h:961-965: reserve[s] = 1, rsum = 0, no push, no walks): it is
     // written here and never takes a slot.  (On the R-MAT variant with 52 % dangling nodes half of a batch's slots were
@@ -1395,7 +1422,7 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     std::vector<int> live_at; // position of live source i in the caller's arrays
     for (int i = 0; i < nq; i++) {
         const int32_t s = sources[i];
-        if (c->h_row_ptr[s + 1] != c->h_row_ptr[s]) { live_src.push_back(s); live_at.push_back(i); continue; }
+        if (!is_dangling(c, s)) { live_src.push_back(s); live_at.push_back(i); continue; }
         if (stats) {
             fora_query_stats &o = stats[i];
             memset(&o, 0, sizeof(o));
@@ -1412,95 +1439,130 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     const bool want_topk = topk > 0 && (ids || scores);
     const int nl = (int)live_src.size();
     if (nl == 0) return FORA_OK;
-    c->bk_div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
-    int rc = ensure_workspace(c, nl, c->omega);
+    int rc = ensure_query_workspace(c, nl, want_topk ? topk : 0);
     if (rc) return rc;
-    if (want_topk && c->topk_cap < c->B * topk) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * topk * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * topk * 8));
-        c->topk_cap = c->B * topk;
-    }
-    // second lane when there is more than one batch to run (not with top-k outputs: their buffers live on the first lane)
-    fora_ctx *lanes[2] = {c, c};
-    if (nl > c->B && c->opt_.pipeline == 1 && !want_topk) { // opt-in: measured no gain on ws (kernels time-slice)
-        rc = sync_twin(c);
-        if (rc) return rc;
-        rc = ensure_workspace(c->twin, c->B, c->omega);
-        if (rc) { c->err = c->twin->err; return rc; }
-        if (c->twin->B >= c->B) lanes[1] = c->twin;
-    }
-    struct Pending { fora_ctx *lane; int b0, nb; };
-    std::vector<Pending> inflight;
-    std::vector<fora_query_stats> st_tmp;
-    auto finish = [&](const Pending &p) -> int {
-        int r = batch_finish(p.lane);
-        if (r) { if (p.lane != c) c->err = p.lane->err; return r; }
-        if (stats) {
-            st_tmp.resize((size_t)p.nb);
-            fill_stats(p.lane, p.nb, st_tmp.data());
-            for (int i = 0; i < p.nb; i++) stats[live_at[(size_t)p.b0 + i]] = st_tmp[(size_t)i];
-        }
-        if (want_topk) { // (p.lane == c here)
-            const Dev ds = make_dev(c, p.nb, false);
-            int r2 = launch_select(c, ds, p.nb, topk, c->d_topk_ids, c->d_topk_sc, 0);
-            if (r2) return r2;
-            std::vector<int32_t> hid((size_t)p.nb * topk);
-            std::vector<double> hsc((size_t)p.nb * topk);
-            HIPCHK(c, hipMemcpyAsync(hid.data(), c->d_topk_ids, hid.size() * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(hsc.data(), c->d_topk_sc, hsc.size() * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream)); // (the ctx stream does not synchronise with the null stream)
-            for (int i = 0; i < p.nb; i++) {
-                const uint64_t at = (uint64_t)live_at[(size_t)p.b0 + i] * topk;
-                if (ids) memcpy(ids + at, hid.data() + (size_t)i * topk, (size_t)topk * 4);
-                if (scores) memcpy(scores + at, hsc.data() + (size_t)i * topk, (size_t)topk * 8);
-            }
+    const int per = even_batch(nl, c->B);
+    for (int b0 = 0; b0 < nl; b0 += per) {
+        const int nb = std::min(per, nl - b0);
+        const int *at = live_at.data() + b0; // places of the batch's slots in the caller's arrays
+        if ((rc = run_query_batch(c, live_src.data() + b0, nb, with_idx != 0, flags))) return rc;
+        if (stats) for (int i = 0; i < nb; i++) fill_stats(c, i, stats[at[i]]);
+        if (want_topk) {
+            if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
+            if ((rc = copy_topk_out(c, nb, topk, ids, scores, 0, at))) return rc;
         }
         // slots i .. j - 1 of the batch whose places in the caller's arrays are consecutive too: one copy
-        for (int i = 0; i < p.nb && (ppr_d || ppr_fix || residue_fix);) {
-            int j = i + 1;
-            while (j < p.nb && live_at[(size_t)p.b0 + j] == live_at[(size_t)p.b0 + j - 1] + 1) j++;
-            const uint64_t at = (uint64_t)live_at[(size_t)p.b0 + i] * n, from = (uint64_t)i * n, cnt = (uint64_t)(j - i) * n;
-            if (ppr_d) {
-                // u64 and f64 have the same size: copy raw, convert in place on the host
-                double *dst = ppr_d + at;
-                HIPCHK(c, hipMemcpy(dst, p.lane->d_ppr + from, cnt * 8, hipMemcpyDeviceToHost));
-                uint64_t *raw = (uint64_t *)dst;
-                for (uint64_t x = 0; x < cnt; x++) {
-                    uint64_t u = raw[x];
-                    dst[x] = std::ldexp((double)u, -62);
-                }
-            }
-            if (ppr_fix) HIPCHK(c, hipMemcpy(ppr_fix + at, p.lane->d_ppr + from, cnt * 8, hipMemcpyDeviceToHost));
-            if (residue_fix) HIPCHK(c, hipMemcpy(residue_fix + at, p.lane->d_residue + from, cnt * 8, hipMemcpyDeviceToHost));
-            i = j;
+        for (int i = 0, j; i < nb && (ppr_d || ppr_fix || residue_fix); i = j) {
+            for (j = i + 1; j < nb && at[j] == at[j - 1] + 1; j++) {}
+            if ((rc = copy_slab_out(c, c->d_ppr, i, at[i], j - i, ppr_fix, ppr_d, 62))) return rc;
+            if ((rc = copy_slab_out(c, c->d_residue, i, at[i], j - i, residue_fix, nullptr, 62))) return rc;
         }
-        return FORA_OK;
-    };
-    int k = 0;
-    const int per = even_batch(nl, c->B);
-    for (int b0 = 0; b0 < nl; b0 += per, k++) {
-        const int nb = std::min(per, nl - b0);
-        fora_ctx *lane = lanes[k & 1];
-        // the lane's previous batch must be drained before its workspace is reused
-        for (size_t i = 0; i < inflight.size();) {
-            if (inflight[i].lane == lane) {
-                rc = finish(inflight[i]);
-                if (rc) return rc;
-                inflight.erase(inflight.begin() + (long)i);
-            } else i++;
-        }
-        rc = batch_begin(lane, live_src.data() + b0, nb, with_idx != 0, flags);
-        if (rc) { if (lane != c) c->err = lane->err; return rc; }
-        inflight.push_back({lane, b0, nb});
-    }
-    for (const Pending &p : inflight) {
-        rc = finish(p);
-        if (rc) return rc;
     }
     return FORA_OK;
 }
 
+// ---- frame of the two top-k drivers (fora_hip_topk_batch, fora_hip_topk_bound_batch): all active slots of a batch are
+// in the same round, so delta / rmax / omega are uniform per round; finished slots drop out.  Each driver keeps its own
+// delta schedule, rmax / omega formulas, bounds kernels and stop rule.
+
+// The index cursors of a new batch all read as zero: a new epoch (the slabs themselves are cleared when they are allocated
+// and when the 24-bit epoch wraps).
+int next_cursor_epoch(fora_ctx *c) {
+    if (c->cursor_epoch == 0 || c->cursor_epoch >= 0xFFFFFFu) {
+        HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, (uint64_t)c->B * (uint64_t)c->n * 8, c->stream));
+        c->cursor_epoch = 0;
+    }
+    c->cursor_epoch++;
+    return FORA_OK;
+}
+
+// slabs of the drivers: ppr2 (the rounds' ppr), index cursors, active marks, per-slot counts; the (ids, scores) pair
+int ensure_topk_slabs(fora_ctx *c, int k) {
+    if (!c->d_ppr2) {
+        const uint64_t slab = (uint64_t)c->B * (uint64_t)c->n;
+        HIPCHK(c, hipMalloc(&c->d_ppr2, slab * 8));
+        HIPCHK(c, hipMalloc(&c->d_cursor, slab * 8));
+        HIPCHK(c, hipMalloc(&c->d_active, (size_t)c->B));
+        HIPCHK(c, hipMalloc(&c->d_above, (size_t)c->B * 8));
+    }
+    return grow_pair(c, k, c->d_topk_ids, c->d_topk_sc, c->topk_cap);
+}
+
+// host side of a batch; the vectors are kept from batch to batch (asynchronous copies read them)
+struct TopkBatch {
+    int hb = -1;                      // the batch's event pair
+    std::vector<uint8_t> active, inactive;
+    std::vector<int32_t> nround;      // rounds each slot has run
+};
+
+// Batch start: state reset, a new cursor epoch, k_init_batch.  A dangling source never runs a round (query.h:1007-1011,
+// :951-955: one round, ppr = e_s), so its slot starts inactive and its ppr2 := reserve here; every other slot's ppr2 is
+// written by its first round's copy (round 5 copied all slots here: one 12-GB slab pass per Twitter-2010-sized batch for nothing).
+int topk_batch_start(fora_ctx *c, TopkBatch &tb, const int32_t *sources, int nb, bool with_idx, uint32_t chunks) {
+    tb.hb = ev_begin(c, 5);
+    if (int rc = reset_batch_state(c, nb, sources)) return rc;
+    if (with_idx) if (int rc = next_cursor_epoch(c)) return rc; // query.h:997-998, :937-938: every cursor of the batch reads as 0
+    hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, make_dev(c, nb, with_idx), 1);
+    tb.active.assign((size_t)nb, 1);
+    tb.inactive.assign((size_t)nb, 0);
+    tb.nround.assign((size_t)nb, 1);
+    bool any_inactive = false;
+    for (int i = 0; i < nb; i++)
+        if (is_dangling(c, sources[i])) { tb.active[i] = 0; tb.inactive[i] = 1; any_inactive = true; }
+    if (any_inactive) {
+        HIPCHK(c, hipMemcpyAsync(c->d_active, tb.inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2, (const uint8_t *)c->d_active);
+    }
+    return FORA_OK;
+}
+
+// One round of the active slots: the per-round resets, the push from every node at or over the round's threshold
+// (algo.h:1020-1093), ppr2 := reserve, then walk allocation (KIND of k_walk_alloc; round_walks: walks per slot, or null) and
+// walks into ppr2 (compute_ppr_with_fwdidx_topk, query.h:521-636; ..._with_bound, :639-750).  dw: the round's Dev over ppr2.
+template <int KIND>
+int topk_round(fora_ctx *c, TopkBatch &tb, int nb, bool with_idx, int round, double rmax, double omega, uint32_t chunks,
+               unsigned long long *round_walks, int nzh, Dev &dw) {
+    for (int i = 0; i < nb; i++) if (tb.active[i]) tb.nround[i] = round;
+    HIPCHK(c, hipMemcpyAsync(c->d_active, tb.active.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_above, 0, (size_t)nb * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
+    if (int rc = reset_binned_counters(c)) return rc;
+    const Dev d = make_dev(c, nb, with_idx, rmax, omega);
+    int h = ev_begin(c, 4);
+    hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->d_active);
+    ev_end(c, h);
+    if (int rc = run_push_levels(c, d, nullptr, 0, true)) return rc;
+    h = ev_begin(c, 4);
+    hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2,
+                       (const uint8_t *)c->d_active);
+    ev_end(c, h);
+    dw = d;
+    dw.ppr = c->d_ppr2;
+    h = ev_begin(c, 2);
+    hipLaunchKernelGGL(k_walk_alloc<KIND>, (dw.wide && (dw.slot_major & 8u)) ? dim3(nb, chunks) : dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, with_idx ? 1 : 0,
+                       (const uint8_t *)c->d_active, c->d_cursor, round_walks, c->cursor_epoch);
+    ev_end(c, h);
+    launch_walks(c, dw, nb, with_idx, (uint32_t)round, nzh);
+    return FORA_OK;
+}
+
+// Batch end: the top k of every slot's ppr2 (topk_ppr, algo.h:592-610; sel_thr: per-slot lower limits of the top k, or
+// null), the close-out, ids / scores / rounds of the slots into rows b0 ..., the counters of all their rounds.
+int topk_batch_end(fora_ctx *c, const TopkBatch &tb, int nb, int k, const double *sel_thr, const char *what, int b0,
+                   int32_t *ids, double *scores, int32_t *rounds) {
+    Dev ds = make_dev(c, nb, false);
+    ds.ppr = c->d_ppr2;
+    const int h = ev_begin(c, 4);
+    if (int rc = launch_select(c, ds, nb, k, c->d_topk_ids, c->d_topk_sc, 0, sel_thr)) return rc;
+    ev_end(c, h);
+    if (int rc = close_batch(c, tb.hb, what)) return rc;
+    if (int rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0)) return rc;
+    HIPCHK(c, hipMemcpy(c->h_qs.data(), c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
+    fold_counters(c, c->h_qs.data(), nb);
+    if (rounds) for (int i = 0; i < nb; i++) rounds[b0 + i] = tb.nround[i];
+    return FORA_OK;
+}
 } // namespace
 
 // Two device conditions are not caller errors and are answered by running the call again from scratch (results never
@@ -1516,23 +1578,12 @@ template <class F> int with_bucket_retry(fora_ctx *c, F call) {
         (void)hipStreamSynchronize(c->stream);
         c->ev_used = 0;
         c->timing = t0;
-        c->pending_nq = 0;
-        if (c->twin) {
-            (void)hipStreamSynchronize(c->twin->stream);
-            c->twin->ev_used = 0;
-            c->twin->pending_nq = 0;
-        }
-    };
-    auto set_scales = [&](uint32_t s, uint32_t st) {
-        c->bk_scale = s; c->bk_scale_topk = st;
-        if (c->twin) { c->twin->bk_scale = s; c->twin->bk_scale_topk = st; }
     };
     auto drop_enlarged_plan = [&]() { // the enlarged plan did not help: do not keep it
         if (c->bk_scale == scale0 && c->bk_scale_topk == scale0t) return;
-        set_scales(scale0, scale0t);
+        c->bk_scale = scale0; c->bk_scale_topk = scale0t;
         (void)hipSetDevice(c->device);
         free_workspace(c);
-        if (c->twin) free_workspace(c->twin);
     };
     for (;;) {
         const fora_timing t0 = c ? c->timing : fora_timing{};
@@ -1550,21 +1601,17 @@ template <class F> int with_bucket_retry(fora_ctx *c, F call) {
             forget_attempt(t0);
             continue;
         }
-        const bool bucket = c->bucket_overflow || (c->twin && c->twin->bucket_overflow);
         // the multiplier of the regime the call planned with (fora_ctx::bk_div is set by the call itself)
-        const bool topk_regime = c->bk_div > 1;
-        const uint32_t cur = topk_regime ? c->bk_scale_topk : c->bk_scale;
-        if (!bucket || cur >= (1u << 16)) {
+        uint32_t &cur = c->bk_div > 1 ? c->bk_scale_topk : c->bk_scale;
+        if (!c->bucket_overflow || cur >= (1u << 16)) {
             drop_enlarged_plan();
             return rc;
         }
-        set_scales(topk_regime ? c->bk_scale : c->bk_scale * 2, topk_regime ? c->bk_scale_topk * 2 : c->bk_scale_topk);
+        cur *= 2;
         c->bucket_retries++;
         c->bucket_overflow = false;
         forget_attempt(t0);
-        if (c->twin) c->twin->bucket_overflow = false;
         free_workspace(c);
-        if (c->twin) free_workspace(c->twin);
     }
 }
 
@@ -1614,15 +1661,6 @@ void fora_hip_destroy(fora_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->twin) {
-        fora_ctx *w = c->twin;
-        if (w->stream) (void)hipStreamSynchronize(w->stream);
-        free_workspace(w);
-        for (auto &p : w->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-        if (w->stream) (void)hipStreamDestroy(w->stream);
-        delete w; // graph / index pointers are owned by c
-        c->twin = nullptr;
-    }
     free_workspace(c);
     free_index(c);
     free_graph(c);
@@ -1857,7 +1895,6 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
         if (col[e] < 0 || col[e] >= n) return fail(c, FORA_E_ARG, "edge target out of range"); // graph.h:155-156
     HIPCHK(c, hipSetDevice(c->device));
     free_workspace(c);
-    if (c->twin) free_workspace(c->twin);
     free_index(c);
     free_graph(c);
     c->bk_scale = 1; c->bk_scale_topk = 1;
@@ -1943,7 +1980,7 @@ int fora_hip_get_params(fora_ctx *c, double *rmax, double *omega) {
 
 int fora_hip_set_batch(fora_ctx *c, int batch) {
     if (!c || batch < 0) return FORA_E_ARG;
-    if (batch != c->batch_req) { (void)hipSetDevice(c->device); free_workspace(c); if (c->twin) free_workspace(c->twin); }
+    if (batch != c->batch_req) { (void)hipSetDevice(c->device); free_workspace(c); }
     c->batch_req = batch;
     return FORA_OK;
 }
@@ -1954,12 +1991,10 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
     if (!strcmp(name, "reset")) { // back to the defaults / environment of fora_hip_create
         (void)hipSetDevice(c->device);
         free_workspace(c);
-        if (c->twin) free_workspace(c->twin);
         c->opt_ = tunables_from_env();
         c->team_suspend = 0; // (a time-out's back-off too)
         c->profiling = c->opt_.profile != 0;
         c->grid_blocks = c->opt_.grid > 0 ? (int)c->opt_.grid : 2048;
-        if (c->twin) { c->twin->opt_ = c->opt_; c->twin->grid_blocks = c->grid_blocks; }
         return FORA_OK;
     }
     if (!TEST_PATHS && schedule_option(name) && value != (strcmp(name, "rounds") ? (strcmp(name, "round_div") ? 0 : 4) : 1))
@@ -1968,9 +2003,9 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
         if (!strcmp(name, o.name)) {
             if (c->opt_.*(o.field) == value) return FORA_OK;
             c->opt_.*(o.field) = value;
-            if (o.layout) { (void)hipSetDevice(c->device); free_workspace(c); if (c->twin) free_workspace(c->twin); }
+            if (o.layout) { (void)hipSetDevice(c->device); free_workspace(c); }
             if (!strcmp(name, "profile")) c->profiling = value != 0;
-            if (!strcmp(name, "grid")) { c->grid_blocks = value > 0 ? (int)value : 2048; if (c->twin) c->twin->grid_blocks = c->grid_blocks; }
+            if (!strcmp(name, "grid")) c->grid_blocks = value > 0 ? (int)value : 2048;
             return FORA_OK;
         }
     return fail(c, FORA_E_ARG, std::string("unknown option ") + name);
@@ -2054,11 +2089,7 @@ int fora_hip_build_index(fora_ctx *c) {
     hipLaunchKernelGGL(k_walk_online<WALK_TO_INDEX>, dim3(walk_grid_x(c, 1), 1), dim3(BLOCK), 0, c->stream, d, 0u,
                        c->opt ? 1 : 0, c->d_rw_idx);
     ev_end(c, h);
-    rc = check_dev_err(c);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("build_index: ") + hipGetErrorString(e));
-    ev_collect(c);
+    if ((rc = close_batch(c, -1, "build_index"))) return rc;
     c->have_index = true;
     return FORA_OK;
 }
@@ -2119,21 +2150,19 @@ int fora_hip_push_batch(fora_ctx *c, const int32_t *sources, int nq, uint64_t *r
 int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64_t *num_s_rw, uint64_t *n_rw) {
     if (!c || !c->n || !c->have_params || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
     HIPCHK(c, hipSetDevice(c->device));
-    double *d_r = nullptr;
-    uint64_t *d_num = nullptr, *d_n = nullptr;
+    DevTmp d_r, d_num, d_n;
     const size_t n = (size_t)c->n;
-    HIPCHK(c, hipMalloc(&d_r, n * 8));
-    HIPCHK(c, hipMalloc(&d_num, n * 8));
-    HIPCHK(c, hipMalloc(&d_n, 8));
-    HIPCHK(c, hipMemcpy(d_r, residue, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc(&d_r.p, n * 8));
+    HIPCHK(c, hipMalloc(&d_num.p, n * 8));
+    HIPCHK(c, hipMalloc(&d_n.p, 8));
+    HIPCHK(c, hipMemcpy(d_r.p, residue, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_walk_counts_f64, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                       c->n, d_r, rsum, c->omega, c->alpha, c->opt, d_num, d_n);
+                       c->n, (const double *)d_r.p, rsum, c->omega, c->alpha, c->opt, (uint64_t *)d_num.p, (uint64_t *)d_n.p);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(num_s_rw, d_num, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(num_s_rw, d_num.p, n * 8, hipMemcpyDeviceToHost));
     uint64_t N = 0;
-    HIPCHK(c, hipMemcpy(&N, d_n, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&N, d_n.p, 8, hipMemcpyDeviceToHost));
     if (n_rw) *n_rw = N;
-    dfree(d_r); dfree(d_num); dfree(d_n);
     return FORA_OK;
 }
 
@@ -2144,64 +2173,52 @@ int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_
     for (int64_t i = 0; i < count; i++)
         if (starts[i] < 0 || starts[i] >= c->n) return fail(c, FORA_E_ARG, "walk start out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    int32_t *d_s = nullptr, *d_d = nullptr;
-    uint64_t *d_j = nullptr;
-    HIPCHK(c, hipMalloc(&d_s, (size_t)count * 4));
-    HIPCHK(c, hipMalloc(&d_d, (size_t)count * 4));
-    HIPCHK(c, hipMalloc(&d_j, (size_t)count * 8));
-    HIPCHK(c, hipMemcpy(d_s, starts, (size_t)count * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_j, js, (size_t)count * 8, hipMemcpyHostToDevice));
+    DevTmp d_s, d_d, d_j;
+    HIPCHK(c, hipMalloc(&d_s.p, (size_t)count * 4));
+    HIPCHK(c, hipMalloc(&d_d.p, (size_t)count * 4));
+    HIPCHK(c, hipMalloc(&d_j.p, (size_t)count * 8));
+    HIPCHK(c, hipMemcpy(d_s.p, starts, (size_t)count * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_j.p, js, (size_t)count * 8, hipMemcpyHostToDevice));
     Dev d{};
     d.n = c->n; d.rowinfo = c->d_rowinfo; d.row_ptr = c->d_row_ptr; d.col = c->d_col;
     d.alpha32 = (uint32_t)(c->alpha * 4294967296.0);
     d.seed_lo = (uint32_t)c->seed; d.seed_hi = (uint32_t)(c->seed >> 32);
     hipLaunchKernelGGL(k_walks_raw, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, d,
-                       stream_id, round, no_zero_hop, d_s, d_j, count, d_d);
+                       stream_id, round, no_zero_hop, (const int32_t *)d_s.p, (const uint64_t *)d_j.p, count, (int32_t *)d_d.p);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dests, d_d, (size_t)count * 4, hipMemcpyDeviceToHost));
-    dfree(d_s); dfree(d_d); dfree(d_j);
+    HIPCHK(c, hipMemcpy(dests, d_d.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return FORA_OK;
 }
 
-// top-k driver: fora_query_topk_new (query.h:972-1045) for a batch of slots.  All active slots
-// are in the same round, so delta / rmax / omega are uniform per round; finished slots drop out.
+// top-k driver: fora_query_topk_new (query.h:972-1045) for a batch of slots (frame: topk_batch_start / topk_round /
+// topk_batch_end).
 static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
                            int with_idx, int32_t *ids, double *scores, int32_t *rounds);
-// The index cursors of a new batch all read as zero: a new epoch (the slabs themselves are cleared when they are allocated
-// and when the 24-bit epoch wraps).
-static int next_cursor_epoch(fora_ctx *c) {
-    if (c->cursor_epoch == 0 || c->cursor_epoch >= 0xFFFFFFu) {
-        HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, (uint64_t)c->B * (uint64_t)c->n * 8, c->stream));
-        c->cursor_epoch = 0;
-    }
-    c->cursor_epoch++;
-    return FORA_OK;
-}
-
 int fora_hip_topk_batch(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
                         int with_idx, int32_t *ids, double *scores, int32_t *rounds) {
     return with_bucket_retry(c, [&] { return topk_batch_impl(c, sources, nq, k, epsilon, rmax_scale, with_idx, ids, scores, rounds); });
 }
-static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
-                           int with_idx, int32_t *ids, double *scores, int32_t *rounds) {
-    if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha, seed)");
-    if (k == 0) k = 500; // query.h:975
-    if (nq < 0 || (nq && (!sources || !ids || !scores))) return fail(c, FORA_E_ARG, "bad arguments");
+// checks of both drivers (but the range of the sources)
+static int check_topk_args(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale, int with_idx,
+                           const int32_t *ids, const double *scores) {
+    if (int rc = check_batch_args(c, sources, nq)) return rc;
+    if (nq && (!ids || !scores)) return fail(c, FORA_E_ARG, "ids / scores missing");
     if (k < 2 || k >= c->n - 1) return fail(c, FORA_E_ARG, "k out of range (query.h:1317-1318)");
-    if (k > SEL_MAXK) return fail(c, FORA_E_ARG, "k > 1024 not supported");
+    if (int rc = check_k(c, k)) return rc;
     if (!(epsilon > 0) || !(rmax_scale >= 0)) return fail(c, FORA_E_ARG, "bad epsilon / rmax_scale");
     if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index");
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+    return FORA_OK;
+}
+static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
+                           int with_idx, int32_t *ids, double *scores, int32_t *rounds) {
+    if (k == 0) k = 500; // query.h:975
+    if (int rc = check_topk_args(c, sources, nq, k, epsilon, rmax_scale, with_idx, ids, scores)) return rc;
+    if (int rc = check_id_range(c, sources, nq)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const double n_d = (double)c->n;
     const double min_delta = 1.0 / c->n;           // query.h:974
     const double init_delta = 1.0 / k / 10;        // query.h:976
     const double pfail = 1.0 / c->n / c->n;        // query.h:977
     const long long m = c->m_attr;
-    (void)n_d;
     if (!(init_delta >= min_delta)) { // k > n/10: the reference's round loop (query.h:1001) never runs, topk_ppr sees an empty ppr
         for (size_t i = 0; i < (size_t)nq * k; i++) { ids[i] = 0; scores[i] = 0.0; }
         if (rounds) for (int i = 0; i < nq; i++) rounds[i] = 0;
@@ -2212,128 +2229,49 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
     c->bk_div = want_wide(c) && c->opt_.bkcap <= 0 ? (uint32_t)std::max<int64_t>(1, c->opt_.topk_bk_div) : 1u;
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
-    const uint64_t n = (uint64_t)c->n;
-    if (!c->d_ppr2) {
-        const uint64_t slab = (uint64_t)c->B * n;
-        HIPCHK(c, hipMalloc(&c->d_ppr2, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_cursor, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_active, (size_t)c->B));
-        HIPCHK(c, hipMalloc(&c->d_above, (size_t)c->B * 8));
-    }
-    if (c->topk_cap < c->B * k) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
-        c->topk_cap = c->B * k;
-    }
+    if ((rc = ensure_topk_slabs(c, k))) return rc;
     const uint32_t chunks = slab_grid_x(c, std::min(nq, c->B));
-    std::vector<uint8_t> active, inactive;
+    TopkBatch tb;
     std::vector<unsigned long long> above;
     const int per = even_batch(nq, c->B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
-        rc = reset_batch_state(c, nb, sources + b0);
-        if (rc) return rc;
-        if (with_idx) { int rce = next_cursor_epoch(c); if (rce) return rce; } // query.h:997-998: every cursor of the batch reads as 0
-        Dev d = make_dev(c, nb, with_idx != 0);
-        hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 1);
-        active.assign((size_t)nb, 1);
-        for (int i = 0; i < nb; i++) // dangling source: query.h:1007-1011, one round, ppr = e_s
-            if (c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]]) active[i] = 0;
-        std::vector<int32_t> nround((size_t)nb, 1);
+        if ((rc = topk_batch_start(c, tb, sources + b0, nb, with_idx != 0, chunks))) return rc;
         std::vector<double> sel_thr((size_t)nb, 0.0); // slots that stop with k entries >= T: the top k are among those
-        // ppr2 := reserve once for the slots that never run a round (dangling sources: ppr = e_s); every other slot's ppr2 is written
-        // by its first round's copy (round 5 copied all slots here: one 12-GB slab pass per Twitter-2010-sized batch for nothing)
-        inactive.assign((size_t)nb, 0);
-        bool any_inactive = false;
-        for (int i = 0; i < nb; i++) { inactive[i] = active[i] ? 0 : 1; any_inactive |= inactive[i] != 0; }
-        if (any_inactive) {
-            HIPCHK(c, hipMemcpyAsync(c->d_active, inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2, (const uint8_t *)c->d_active);
-        }
         double delta = init_delta;
         int round = 0;
         while (delta >= min_delta) { // query.h:1001
-            bool any = false;
-            for (int i = 0; i < nb; i++) any |= active[i] != 0;
-            if (!any) break;
+            if (std::find(tb.active.begin(), tb.active.end(), 1) == tb.active.end()) break;
             round++;
             // fora_topk_setting, algo.h:466-474
             double rmax = epsilon * sqrt(delta / 3 / m / log(2 / pfail));
             rmax *= sqrt(1.0 * m * rmax) * rmax_scale * 3;
             const double omega = (2 + epsilon) * log(2 / pfail) / delta / epsilon / epsilon;
-            for (int i = 0; i < nb; i++) if (active[i]) nround[i] = round;
-            HIPCHK(c, hipMemcpyAsync(c->d_active, active.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_above, 0, (size_t)nb * 8, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
-            rc = reset_binned_counters(c);
-            if (rc) return rc;
-            d = make_dev(c, nb, with_idx != 0, rmax, omega);
-            int h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->d_active);
-            ev_end(c, h);
-            rc = run_push_levels(c, d, nullptr, 0, true); // algo.h:1020-1093
-            if (rc) return rc;
-            // compute_ppr_with_fwdidx_topk, query.h:521-636, into ppr2
-            h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2,
-                               (const uint8_t *)c->d_active);
-            ev_end(c, h);
-            Dev dw = d;
-            dw.ppr = c->d_ppr2;
-            h = ev_begin(c, 2);
-            hipLaunchKernelGGL(k_walk_alloc<ALLOC_TOPK>, (dw.wide && (dw.slot_major & 8u)) ? dim3(nb, chunks) : dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, with_idx ? 1 : 0,
-                               (const uint8_t *)c->d_active, c->d_cursor, (unsigned long long *)nullptr, c->cursor_epoch);
-            ev_end(c, h);
-            launch_walks(c, dw, nb, with_idx != 0, (uint32_t)round, with_idx ? 1 : 0);
+            Dev dw{};
+            if ((rc = topk_round<ALLOC_TOPK>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, nullptr, with_idx ? 1 : 0, dw))) return rc;
             const double T = (1 + epsilon) * delta; // query.h:1030
-            h = ev_begin(c, 4);
+            const int h = ev_begin(c, 4);
             hipLaunchKernelGGL(k_count_above, dim3(std::min<uint32_t>(chunks, 256), nb), dim3(BLOCK), 0, c->stream, dw,
                                (const uint8_t *)c->d_active, T, c->d_above);
             ev_end(c, h);
             above.assign((size_t)nb, 0);
             HIPCHK(c, hipMemcpyAsync(above.data(), c->d_above, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
-            rc = check_dev_err(c);
-            if (rc) return rc;
+            if ((rc = check_dev_err(c))) return rc;
             for (int i = 0; i < nb; i++)
-                if (active[i] && (above[i] >= (unsigned long long)k || delta <= min_delta)) {
-                    active[i] = 0;
+                if (tb.active[i] && (above[i] >= (unsigned long long)k || delta <= min_delta)) {
+                    tb.active[i] = 0;
                     if (above[i] >= (unsigned long long)k) sel_thr[i] = T;
                 }
             if (delta <= min_delta) break;
             delta = std::max(min_delta, delta / 4.0); // query.h:1041
         }
-        // topk_ppr, algo.h:592-610
-        Dev ds = make_dev(c, nb, false);
-        ds.ppr = c->d_ppr2;
-        int h = ev_begin(c, 4);
-        rc = launch_select(c, ds, nb, k, c->d_topk_ids, c->d_topk_sc, 0, sel_thr.data());
-        if (rc) return rc;
-        ev_end(c, h);
-        ev_end(c, hb);
-        HIPCHK(c, hipMemcpyAsync(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * k, c->d_topk_sc, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("topk: ") + hipGetErrorString(e));
-        ev_collect(c);
-        HIPCHK(c, hipMemcpy(c->h_qs.data(), c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
-        for (int i = 0; i < nb; i++) { // counters accumulated over all rounds of the slot
-            c->timing.pops += c->h_qs[i].pops;
-            c->timing.relax += c->h_qs[i].relax;
-            c->timing.walks += c->h_qs[i].n_walks;
-            c->timing.idx_hits += c->h_qs[i].n_hit;
-        }
-        if (rounds) for (int i = 0; i < nb; i++) rounds[b0 + i] = nround[i];
+        if ((rc = topk_batch_end(c, tb, nb, k, sel_thr.data(), "topk", b0, ids, scores, rounds))) return rc;
     }
     return FORA_OK;
 }
 
-// top-k with bounds: fora_query_topk_with_bound (query.h:909-969) for a batch of slots.  As in the --opt driver all
-// active slots share a round (delta halves per round), finished slots drop out.  zero_ppr_upper_bound (query.h:935,
-// :748) only ever feeds itself in the reference and is not kept.
+// top-k with bounds: fora_query_topk_with_bound (query.h:909-969) for a batch of slots, in the frame of the --opt driver
+// (delta halves per round).  zero_ppr_upper_bound (query.h:935, :748) only ever feeds itself in the reference and is not kept.
 static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
                                  double ppr_decay_alpha, int with_idx, int32_t *ids, double *scores, int32_t *rounds);
 int fora_hip_topk_bound_batch(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
@@ -2344,17 +2282,9 @@ int fora_hip_topk_bound_batch(fora_ctx *c, const int32_t *sources, int nq, int k
 }
 static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
                                  double ppr_decay_alpha, int with_idx, int32_t *ids, double *scores, int32_t *rounds) {
-    if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha, seed)");
-    if (nq < 0 || (nq && (!sources || !ids || !scores))) return fail(c, FORA_E_ARG, "bad arguments");
-    if (k < 2 || k >= c->n - 1) return fail(c, FORA_E_ARG, "k out of range (query.h:1317-1318)");
-    if (k > SEL_MAXK) return fail(c, FORA_E_ARG, "k > 1024 not supported");
-    if (!(epsilon > 0) || !(rmax_scale >= 0)) return fail(c, FORA_E_ARG, "bad epsilon / rmax_scale");
+    if (int rc = check_topk_args(c, sources, nq, k, epsilon, rmax_scale, with_idx, ids, scores)) return rc;
     if (!(ppr_decay_alpha > 0 && ppr_decay_alpha < 1)) return fail(c, FORA_E_ARG, "bad ppr_decay_alpha");
-    if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index");
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+    if (int rc = check_id_range(c, sources, nq)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const double min_delta = 1.0 / c->n;                                                                    // query.h:911
     const double init_delta = 1.0 / 4;                                                                      // :912
@@ -2366,15 +2296,9 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     c->bk_div = 1;
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
-    const uint64_t n = (uint64_t)c->n;
-    const uint64_t slab = (uint64_t)c->B * n;
-    if (!c->d_ppr2) {
-        HIPCHK(c, hipMalloc(&c->d_ppr2, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_cursor, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_active, (size_t)c->B));
-        HIPCHK(c, hipMalloc(&c->d_above, (size_t)c->B * 8));
-    }
+    if ((rc = ensure_topk_slabs(c, k))) return rc;
     if (!c->d_upper) {
+        const uint64_t slab = (uint64_t)c->B * (uint64_t)c->n;
         HIPCHK(c, hipMalloc(&c->d_upper, slab * 8));
         HIPCHK(c, hipMalloc(&c->d_lower, slab * 8));
         HIPCHK(c, hipMalloc(&c->d_filter, slab));
@@ -2382,81 +2306,29 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
         HIPCHK(c, hipMalloc(&c->d_fail, (size_t)c->B * 4));
         HIPCHK(c, hipMalloc(&c->d_round_walks, (size_t)c->B * 8));
     }
-    if (c->topk_cap < c->B * k) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
-        c->topk_cap = c->B * k;
-    }
-    if (c->lb_cap < c->B * k) {
-        dfree(c->d_lb_ids); dfree(c->d_lb_sc);
-        HIPCHK(c, hipMalloc(&c->d_lb_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_lb_sc, (size_t)c->B * k * 8));
-        c->lb_cap = c->B * k;
-    }
+    if ((rc = grow_pair(c, k, c->d_lb_ids, c->d_lb_sc, c->lb_cap))) return rc;
     const uint32_t chunks = slab_grid_x(c, std::min(nq, c->B));
-    std::vector<uint8_t> active, inactive;
+    TopkBatch tb;
     std::vector<unsigned long long> above;
     std::vector<uint32_t> failv;
     const int per = even_batch(nq, c->B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
-        rc = reset_batch_state(c, nb, sources + b0);
-        if (rc) return rc;
-        if (with_idx) { int rce = next_cursor_epoch(c); if (rce) return rce; } // query.h:937-938: every cursor of the batch reads as 0
+        if ((rc = topk_batch_start(c, tb, sources + b0, nb, with_idx != 0, chunks))) return rc;
         hipLaunchKernelGGL(k_bounds_reset, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_upper, c->d_lower); // :941-942
-        Dev d = make_dev(c, nb, with_idx != 0);
-        hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 1);
-        active.assign((size_t)nb, 1);
-        for (int i = 0; i < nb; i++) // dangling source: query.h:951-955
-            if (c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]]) active[i] = 0;
-        std::vector<int32_t> nround((size_t)nb, 1);
-        inactive.assign((size_t)nb, 0); // (see fora_hip_topk_batch: only the slots that never run a round need this copy)
-        bool any_inactive = false;
-        for (int i = 0; i < nb; i++) { inactive[i] = active[i] ? 0 : 1; any_inactive |= inactive[i] != 0; }
-        if (any_inactive) {
-            HIPCHK(c, hipMemcpyAsync(c->d_active, inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2, (const uint8_t *)c->d_active);
-        }
         double delta = init_delta;
         int round = 0;
         while (delta >= min_delta) { // query.h:944
-            bool any = false;
-            for (int i = 0; i < nb; i++) any |= active[i] != 0;
-            if (!any) break;
+            if (std::find(tb.active.begin(), tb.active.end(), 1) == tb.active.end()) break;
             round++;
             double rmax = epsilon * sqrt(delta / 3 / m / L); // fora_setting with the round's delta, algo.h:455-463
             rmax *= rmax_scale;
             const double omega = (2 + epsilon) * L / delta / epsilon / epsilon;
-            for (int i = 0; i < nb; i++) if (active[i]) nround[i] = round;
-            HIPCHK(c, hipMemcpyAsync(c->d_active, active.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_above, 0, (size_t)nb * 8, c->stream));
             HIPCHK(c, hipMemsetAsync(c->d_fail, 0, (size_t)nb * 4, c->stream));
             HIPCHK(c, hipMemsetAsync(c->d_round_walks, 0, (size_t)nb * 8, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
-            rc = reset_binned_counters(c);
-            if (rc) return rc;
-            d = make_dev(c, nb, with_idx != 0, rmax, omega);
-            int h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->d_active);
-            ev_end(c, h);
-            rc = run_push_levels(c, d, nullptr, 0, true); // algo.h:1020-1093
-            if (rc) return rc;
-            // compute_ppr_with_fwdidx_topk_with_bound, query.h:639-750, into ppr2
-            h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2,
-                               (const uint8_t *)c->d_active);
-            ev_end(c, h);
-            Dev dw = d;
-            dw.ppr = c->d_ppr2;
-            h = ev_begin(c, 2);
-            hipLaunchKernelGGL(k_walk_alloc<ALLOC_BOUND>, (dw.wide && (dw.slot_major & 8u)) ? dim3(nb, chunks) : dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, with_idx ? 1 : 0,
-                               (const uint8_t *)c->d_active, c->d_cursor, c->d_round_walks, c->cursor_epoch);
-            ev_end(c, h);
-            launch_walks(c, dw, nb, with_idx != 0, (uint32_t)round, 0);
-            h = ev_begin(c, 4);
+            Dev dw{};
+            if ((rc = topk_round<ALLOC_BOUND>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, c->d_round_walks, 0, dw))) return rc;
+            const int h = ev_begin(c, 4);
             if (delta < threshold) // query.h:745-746
                 hipLaunchKernelGGL(k_bounds_update, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, (const uint64_t *)c->d_ppr,
                                    (const uint8_t *)c->d_active, (const unsigned long long *)c->d_round_walks, L,
@@ -2468,8 +2340,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
             if (bounds_on) {
                 Dev dl = dw;
                 dl.ppr = (uint64_t *)c->d_lower; // non-negative f64: bit patterns order like the values
-                rc = launch_select(c, dl, nb, k, c->d_lb_ids, c->d_lb_sc, 1);
-                if (rc) return rc;
+                if ((rc = launch_select(c, dl, nb, k, c->d_lb_ids, c->d_lb_sc, 1))) return rc;
                 hipLaunchKernelGGL(k_bound_ratio, dim3(nb), dim3(SEL_THREADS), 0, c->stream, dw, k, (const int32_t *)c->d_lb_ids,
                                    (const double *)c->d_lb_sc, (const uint8_t *)c->d_active, (const double *)c->d_upper,
                                    1.0 + epsilon, c->d_filter, c->d_fail);
@@ -2482,37 +2353,16 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
             failv.assign((size_t)nb, 0);
             HIPCHK(c, hipMemcpyAsync(above.data(), c->d_above, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(failv.data(), c->d_fail, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
-            rc = check_dev_err(c);
-            if (rc) return rc;
+            if ((rc = check_dev_err(c))) return rc;
             for (int i = 0; i < nb; i++) {
-                if (!active[i]) continue;
+                if (!tb.active[i]) continue;
                 const bool stop = above[i] >= (unsigned long long)k || (bounds_on && failv[i] == 0);
-                if (stop || delta <= min_delta) active[i] = 0; // query.h:962-964
+                if (stop || delta <= min_delta) tb.active[i] = 0; // query.h:962-964
             }
             if (delta <= min_delta) break;
             delta = std::max(min_delta, delta / 2.0); // query.h:966
         }
-        Dev ds = make_dev(c, nb, false);
-        ds.ppr = c->d_ppr2;
-        int h = ev_begin(c, 4);
-        rc = launch_select(c, ds, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
-        if (rc) return rc;
-        ev_end(c, h);
-        ev_end(c, hb);
-        HIPCHK(c, hipMemcpyAsync(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * k, c->d_topk_sc, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("topk (bounds): ") + hipGetErrorString(e));
-        ev_collect(c);
-        HIPCHK(c, hipMemcpy(c->h_qs.data(), c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
-        for (int i = 0; i < nb; i++) {
-            c->timing.pops += c->h_qs[i].pops;
-            c->timing.relax += c->h_qs[i].relax;
-            c->timing.walks += c->h_qs[i].n_walks;
-            c->timing.idx_hits += c->h_qs[i].n_hit;
-        }
-        if (rounds) for (int i = 0; i < nb; i++) rounds[b0 + i] = nround[i];
+        if ((rc = topk_batch_end(c, tb, nb, k, nullptr, "topk (bounds)", b0, ids, scores, rounds))) return rc;
     }
     return FORA_OK;
 }
@@ -2527,71 +2377,41 @@ int fora_hip_power_iteration_batch(fora_ctx *c, const int32_t *sources, int nq, 
 }
 static int power_iteration_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int max_iter, double *ppr_out,
                                       uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores) {
-    if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha)");
-    if (nq < 0 || (nq && !sources) || max_iter < 1 || max_iter >= MAX_LEVELS) return fail(c, FORA_E_ARG, "bad arguments");
+    if (int rc = check_batch_args(c, sources, nq)) return rc;
+    if (max_iter < 1 || max_iter >= MAX_LEVELS) return fail(c, FORA_E_ARG, "max_iter out of range");
     const bool want_topk = ids || scores;
-    if (want_topk && (!ids || !scores || k < 1 || k > SEL_MAXK || k > c->n)) return fail(c, FORA_E_ARG, "bad k / ids / scores");
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
+    if (want_topk && (!ids || !scores)) return fail(c, FORA_E_ARG, "ids and scores go together");
+    if (want_topk) if (int rc = check_k(c, k)) return rc;
+    if (int rc = check_id_range(c, sources, nq)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->bk_div = 1;
-    int rc = ensure_workspace(c, nq, c->omega);
+    int rc = ensure_query_workspace(c, nq, want_topk ? k : 0);
     if (rc) return rc;
-    const uint64_t n = (uint64_t)c->n;
-    if (want_topk && c->topk_cap < c->B * k) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
-        c->topk_cap = c->B * k;
-    }
     const int per = even_batch(nq, c->B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         const int hb = ev_begin(c, 5);
-        rc = reset_batch_state(c, nb, sources + b0);
-        if (rc) return rc;
+        if ((rc = reset_batch_state(c, nb, sources + b0))) return rc;
         Dev d = make_dev(c, nb, false, 0.0, c->omega); // rmax 0 -> threshold of one unit per out-edge
         hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 2);
-        rc = run_push_levels(c, d, nullptr, max_iter);
-        if (rc) return rc;
+        if ((rc = run_push_levels(c, d, nullptr, max_iter))) return rc;
         if (want_topk) {
-            int h = ev_begin(c, 4);
-            rc = launch_select(c, d, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
-            if (rc) return rc;
+            const int h = ev_begin(c, 4);
+            if ((rc = launch_select(c, d, nb, k, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
             ev_end(c, h);
-            HIPCHK(c, hipMemcpyAsync(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * k, c->d_topk_sc, (size_t)nb * k * 8, hipMemcpyDeviceToHost, c->stream));
         }
-        ev_end(c, hb);
-        rc = check_dev_err(c);
-        if (rc) return rc;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("power iteration: ") + hipGetErrorString(e));
-        ev_collect(c);
-        const uint64_t bytes = (uint64_t)nb * n * 8;
-        if (ppr_fix_out) HIPCHK(c, hipMemcpy(ppr_fix_out + (uint64_t)b0 * n, c->d_ppr, bytes, hipMemcpyDeviceToHost));
-        if (ppr_out) {
-            double *dst = ppr_out + (uint64_t)b0 * n;
-            HIPCHK(c, hipMemcpy(dst, c->d_ppr, bytes, hipMemcpyDeviceToHost));
-            uint64_t *raw = (uint64_t *)dst;
-            for (uint64_t i = 0; i < (uint64_t)nb * n; i++) dst[i] = std::ldexp((double)raw[i], -62);
-        }
+        if ((rc = close_batch(c, hb, "power iteration"))) return rc;
+        if (want_topk && (rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0))) return rc;
+        if ((rc = copy_slab_out(c, c->d_ppr, 0, (uint64_t)b0, (uint64_t)nb, ppr_fix_out, ppr_out, 62))) return rc;
     }
     return FORA_OK;
 }
 
 // ---- baselines of the reference's experiments: --algo montecarlo (query.h:1482-1493) and --algo fwdpush (:1495-1511)
 static int check_baseline_args(fora_ctx *c, const int32_t *sources, int nq, double epsilon, int k) {
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha, seed)");
-    if (nq < 0 || (nq && !sources)) return fail(c, FORA_E_ARG, "bad sources");
+    if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (!(epsilon > 0)) return fail(c, FORA_E_ARG, "epsilon must be > 0");
-    if (k < 0 || k > SEL_MAXK || k > c->n) return fail(c, FORA_E_ARG, "bad k");
-    for (int i = 0; i < nq; i++)
-        if (sources[i] < 0 || sources[i] >= c->n) return fail(c, FORA_E_ARG, "source id out of range");
-    return FORA_OK;
+    if (k != 0) if (int rc = check_k(c, k)) return rc; // (0: no top-k)
+    return check_id_range(c, sources, nq);
 }
 
 // FwdPush: the push of the FORA path at fwdpush_setting's rmax (algo.h:485-496), ppr = the reserve
@@ -2606,7 +2426,6 @@ struct PushRmaxScope {
 static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                               uint64_t *reserve_fix_out, uint64_t *residue_fix_out, int k, int32_t *ids, double *scores,
                               fora_query_stats *stats) {
-    if (!c) return FORA_E_ARG;
     if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
     if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
     const double delta = 1.0 / c->n;
@@ -2614,105 +2433,6 @@ static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, doubl
     if (!(rmax > 0) || !std::isfinite(rmax)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
     PushRmaxScope scope(c, rmax);
     return query_common(c, sources, nq, 0, RUN_PUSH_ONLY, ppr_out, reserve_fix_out, residue_fix_out, stats, k, ids, scores);
-}
-
-// Monte-Carlo: W walks per source (k_walk_mc), W = the integers i >= 0 with i < omega, omega = montecarlo_setting
-// (algo.h:477-483).  A launch runs at most MC_LAUNCH_WALKS walks over all slots of the batch.
-constexpr uint64_t MC_LAUNCH_WALKS = 1ull << 28;
-// walks j < W of every slot of the batch (k_walk_mc) into the slots' ppr slabs, walk j carrying wbase + (j < wrem) units
-static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, uint64_t W, uint64_t wbase, uint64_t wrem) {
-    // walk numbers per launch and per workgroup: about eight workgroups per CU, 4 Ki .. 64 Ki walks each
-    const uint64_t span = std::max<uint64_t>(1, MC_LAUNCH_WALKS / (uint64_t)nb);
-    for (uint64_t j0 = 0; j0 < W; j0 += span) {
-        const uint64_t j1 = std::min(W, j0 + span);
-        const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
-        const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
-        const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
-        const int h = ev_begin(c, 3);
-        hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, wbase, wrem, j0, j1, per_wg);
-        ev_end(c, h);
-    }
-}
-static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out,
-                                 uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
-    if (!c) return FORA_E_ARG;
-    if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
-    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
-    const double omega = 3 * log(2 / pfail) / epsilon / epsilon / delta; // fwd_rw_count, algo.h:478
-    if (!(omega < 0x1p48)) return fail(c, FORA_E_ARG, "epsilon too small: more than 2^48 walks per source");
-    const uint64_t W = (uint64_t)std::ceil(omega); // for (unsigned long i = 0; i < config.omega; i++)
-    if (W == 0) return fail(c, FORA_E_ARG, "no walks");
-    const uint64_t wbase = FIX_ONE / W, wrem = FIX_ONE % W;
-    const bool want_topk = k > 0 && (ids || scores);
-    HIPCHK(c, hipSetDevice(c->device));
-    c->bk_div = 1;
-    int rc = ensure_workspace(c, nq, c->omega); // (the FORA plan: only the ppr slabs and the per-slot words are used here)
-    if (rc) return rc;
-    const uint64_t n = (uint64_t)c->n;
-    if (want_topk && c->topk_cap < c->B * k) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
-        c->topk_cap = c->B * k;
-    }
-    const int per = even_batch(nq, c->B);
-    for (int b0 = 0; b0 < nq; b0 += per) {
-        const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
-        rc = reset_batch_state(c, nb, sources + b0);
-        if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
-        const Dev d = make_dev(c, nb, false);
-        launch_mc_walks(c, d, nb, W, wbase, wrem);
-        {
-            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
-            const int h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d);
-            ev_end(c, h);
-        }
-        if (want_topk) {
-            const int h = ev_begin(c, 4);
-            rc = launch_select(c, d, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
-            if (rc) return rc;
-            ev_end(c, h);
-        }
-        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        ev_end(c, hb);
-        rc = check_dev_err(c);
-        if (rc) return rc;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("montecarlo: ") + hipGetErrorString(e));
-        ev_collect(c);
-        c->timing.walks += W * (uint64_t)nb;
-        c->timing.walk_steps += *c->h_steps_pin;
-        if (stats)
-            for (int i = 0; i < nb; i++) {
-                fora_query_stats &o = stats[b0 + i];
-                memset(&o, 0, sizeof(o));
-                o.n_walks = W;
-                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
-                o.dangling_source = c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]] ? 1 : 0;
-            }
-        if (want_topk) {
-            if (ids) HIPCHK(c, hipMemcpy(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost));
-            if (scores) HIPCHK(c, hipMemcpy(scores + (size_t)b0 * k, c->d_topk_sc, (size_t)nb * k * 8, hipMemcpyDeviceToHost));
-        }
-        const uint64_t bytes = (uint64_t)nb * n * 8;
-        if (ppr_fix_out) HIPCHK(c, hipMemcpy(ppr_fix_out + (uint64_t)b0 * n, c->d_ppr, bytes, hipMemcpyDeviceToHost));
-        if (ppr_out) {
-            double *dst = ppr_out + (uint64_t)b0 * n;
-            HIPCHK(c, hipMemcpy(dst, c->d_ppr, bytes, hipMemcpyDeviceToHost));
-            uint64_t *raw = (uint64_t *)dst;
-            for (uint64_t i = 0; i < (uint64_t)nb * n; i++) dst[i] = std::ldexp((double)raw[i], -62);
-        }
-    }
-    return FORA_OK;
-}
-
-int fora_hip_montecarlo_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out, uint64_t *ppr_fix_out,
-                              int k, int32_t *ids, double *scores, fora_query_stats *stats) {
-    return montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats); // (no buckets, no push: nothing to retry)
 }
 
 int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
@@ -2727,10 +2447,6 @@ int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double e
 // :126-193).  The pushes run in two passes over the call's targets: a count pass (entries per target, counters, the targets
 // that overflow the LDS tier) and, chunk by chunk, a write pass that runs the same pushes again and writes their entries
 // target-major.  Chunks follow from the counts, so no chunk boundary depends on anything but the entry budget.
-struct DevTmp { // device buffer freed on every return path
-    void *p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-};
 static int ensure_reverse_csr(fora_ctx *c) {
     if (c->d_rin_ptr) return FORA_OK;
     const uint64_t n = (uint64_t)c->n, nnz = (uint64_t)c->nnz;
@@ -2955,12 +2671,8 @@ static void fill_bwd_stats(fora_ctx *c, const BwdRun &r, uint64_t nt, fora_bwd_s
 
 static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
                               uint64_t *residue_fix_out, fora_bwd_stats *bwd) {
-    if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first (alpha)");
-    if (nt < 0 || (nt && !targets)) return fail(c, FORA_E_ARG, "bad targets");
-    for (int i = 0; i < nt; i++)
-        if (targets[i] < 0 || targets[i] >= c->n) return fail(c, FORA_E_ARG, "target id out of range");
+    if (int rc = check_batch_args(c, targets, nt, "target")) return rc;
+    if (int rc = check_id_range(c, targets, nt, "target")) return rc;
     if (int rc = check_bwd_rmax(c, rmax)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     c->bwd_ms = c->combine_ms = 0;
@@ -2994,9 +2706,129 @@ static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, doubl
     return FORA_OK;
 }
 
+// ---- Monte-Carlo (--algo montecarlo) and BiPPR: one batch loop of walks.  Monte-Carlo: W walks per source (k_walk_mc),
+// omega = montecarlo_setting (algo.h:477-483).  BiPPR: the same walks at bippr_setting's omega, combined with the backward
+// push's entries of every node (bippr_query, query.h:71-124).
+// W = the integers i >= 0 with i < omega (for (unsigned long i = 0; i < config.omega; i++)), walk j carrying wbase + (j < wrem)
+// units of FIX_ONE
+struct WalkCount { uint64_t W = 0, wbase = 0, wrem = 0; };
+static int walk_count(fora_ctx *c, double omega, WalkCount &w) {
+    if (!(omega < 0x1p48)) return fail(c, FORA_E_ARG, "epsilon too small: more than 2^48 walks per source");
+    w.W = (uint64_t)std::ceil(omega);
+    if (w.W == 0) return fail(c, FORA_E_ARG, "no walks");
+    w.wbase = FIX_ONE / w.W;
+    w.wrem = FIX_ONE % w.W;
+    return FORA_OK;
+}
+
+// A launch runs at most MC_LAUNCH_WALKS walks over all slots of the batch.
+constexpr uint64_t MC_LAUNCH_WALKS = 1ull << 28;
+// walks j < W of every slot of the batch (k_walk_mc) into the slots' ppr slabs
+static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, const WalkCount &w) {
+    // walk numbers per launch and per workgroup: about eight workgroups per CU, 4 Ki .. 64 Ki walks each
+    const uint64_t span = std::max<uint64_t>(1, MC_LAUNCH_WALKS / (uint64_t)nb);
+    for (uint64_t j0 = 0; j0 < w.W; j0 += span) {
+        const uint64_t j1 = std::min(w.W, j0 + span);
+        const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
+        const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
+        const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
+        const int h = ev_begin(c, 3);
+        hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, w.wbase, w.wrem, j0, j1, per_wg);
+        ev_end(c, h);
+    }
+}
+
+// BiPPR's step of a batch: the walk slabs c_b (2^-62, slot-major in d_ppr) -> node-major in the residue slabs, combined with
+// the entries of every chunk of targets into d_ppr, -> slot-major estimates at 2^-60 in the residue slabs
+static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
+    const uint64_t n = (uint64_t)c->n;
+    const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
+    int h = ev_begin(c, 12);
+    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+                       (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
+    ev_end(c, h);
+    const bool one_chunk = r.chunks.size() == 1; // (then its entries were written once for every batch)
+    for (size_t ck = 0; ck < r.chunks.size(); ck++) {
+        if (!one_chunk) if (int rc = bwd_write(c, r, ck)) return rc;
+        const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
+        h = ev_begin(c, 12);
+        hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
+                           (const uint64_t *)c->d_residue, (uint32_t)nb, (const int32_t *)c->d_src, (const uint64_t *)c->d_boff,
+                           (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->d_ppr);
+        ev_end(c, h);
+    }
+    h = ev_begin(c, 12);
+    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+                       n, (uint64_t)nb); // -> slot-major estimates at 2^-60 in the residue slabs
+    ev_end(c, h);
+    return FORA_OK;
+}
+
+// The batch loop: walks into the ppr slabs, BiPPR's combine when `bwd` holds the backward push of the call, then k_ppr_sum,
+// top-k, stats and copy-out of the estimates (Monte-Carlo: the ppr slabs at 2^-62; BiPPR: the residue slabs at 2^-60).
+static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkCount &w, const BwdRun *bwd, double rmax_used,
+                        double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
+    const bool want_topk = k > 0 && (ids || scores);
+    uint64_t *const est = bwd ? c->d_residue : c->d_ppr;
+    const int frac = bwd ? 60 : 62;
+    const int per = even_batch(nq, c->B);
+    for (int b0 = 0; b0 < nq; b0 += per) {
+        const int nb = std::min(per, nq - b0);
+        const int hb = ev_begin(c, 5);
+        int rc = reset_batch_state(c, nb, sources + b0);
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
+        const Dev d = make_dev(c, nb, false);
+        launch_mc_walks(c, d, nb, w);
+        if (bwd && (rc = bippr_combine(c, *bwd, nb))) return rc;
+        Dev de = d;
+        de.ppr = est;
+        {
+            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
+            const int h = ev_begin(c, 4);
+            hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, de);
+            ev_end(c, h);
+        }
+        if (want_topk) {
+            const int h = ev_begin(c, 4);
+            if ((rc = launch_select(c, de, nb, k, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
+            ev_end(c, h);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = close_batch(c, hb, bwd ? "bippr" : "montecarlo"))) return rc;
+        c->timing.walks += w.W * (uint64_t)nb;
+        c->timing.walk_steps += *c->h_steps_pin;
+        if (stats)
+            for (int i = 0; i < nb; i++) {
+                fora_query_stats &o = stats[b0 + i];
+                memset(&o, 0, sizeof(o));
+                o.n_walks = w.W;
+                o.rmax_used = rmax_used;
+                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
+                o.dangling_source = is_dangling(c, sources[b0 + i]) ? 1 : 0;
+            }
+        // (k_topk_select scales by 2^-62: BiPPR's scores x 4)
+        if (want_topk && (rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0, nullptr, bwd ? 4.0 : 1.0))) return rc;
+        if ((rc = copy_slab_out(c, est, 0, (uint64_t)b0, (uint64_t)nb, ppr_fix_out, ppr_out, frac))) return rc;
+    }
+    return FORA_OK;
+}
+
+static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out,
+                                 uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
+    if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
+    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
+    WalkCount w;
+    if (int rc = walk_count(c, 3 * log(2 / pfail) / epsilon / epsilon / delta, w)) return rc; // fwd_rw_count, algo.h:478
+    HIPCHK(c, hipSetDevice(c->device));
+    // (the FORA plan: only the ppr slabs and the per-slot words are used here)
+    if (int rc = ensure_query_workspace(c, nq, k > 0 && (ids || scores) ? k : 0)) return rc;
+    return walk_batches(c, sources, nq, w, nullptr, 0, ppr_out, ppr_fix_out, k, ids, scores, stats);
+}
+
 static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                             uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
-    if (!c) return FORA_E_ARG;
     if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
     if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
     if (!(rmax_scale > 0) || !std::isfinite(rmax_scale)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
@@ -3005,26 +2837,17 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
     rmax *= rmax_scale;
     const double omega = rmax * 3 * log(2.0 / pfail) / delta / epsilon / epsilon;
     if (int rc = check_bwd_rmax(c, rmax)) return rc;
-    if (!(omega < 0x1p48)) return fail(c, FORA_E_ARG, "epsilon too small: more than 2^48 walks per source");
-    const uint64_t W = (uint64_t)std::ceil(omega); // for (unsigned long i = 0; i < config.omega; i++)
-    if (W == 0) return fail(c, FORA_E_ARG, "no walks");
-    const uint64_t wbase = FIX_ONE / W, wrem = FIX_ONE % W;
-    const bool want_topk = k > 0 && (ids || scores);
+    WalkCount w;
+    if (int rc = walk_count(c, omega, w)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     c->bwd_ms = c->combine_ms = 0;
     const double walk_ms0 = c->timing.walk_ms;
     BwdRun r;
     if (nq == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
-    c->bk_div = 1;
-    int rc = ensure_workspace(c, nq, c->omega); // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
+    // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
+    int rc = ensure_query_workspace(c, nq, k > 0 && (ids || scores) ? k : 0);
     if (rc) return rc;
     const uint64_t n = (uint64_t)c->n;
-    if (want_topk && c->topk_cap < c->B * k) {
-        dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-        HIPCHK(c, hipMalloc(&c->d_topk_ids, (size_t)c->B * k * 4));
-        HIPCHK(c, hipMalloc(&c->d_topk_sc, (size_t)c->B * k * 8));
-        c->topk_cap = c->B * k;
-    }
     // every node is a target (query.h:91: for i < graph.n)
     if ((rc = ensure_reverse_csr(c))) return rc;
     if ((rc = ensure_bwd_targets(c, n))) return rc;
@@ -3034,84 +2857,15 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
         HIPCHK(c, hipMemcpyAsync(c->d_bt, iota.data(), n * 4, hipMemcpyHostToDevice, c->stream));
         if ((rc = bwd_count(c, (uint32_t)n, rmax, r))) return rc; // (synchronises)
     }
-    const bool one_chunk = r.chunks.size() == 1;
-    if (one_chunk && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
-    const int per = even_batch(nq, c->B);
-    for (int b0 = 0; b0 < nq; b0 += per) {
-        const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
-        rc = reset_batch_state(c, nb, sources + b0);
-        if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
-        const Dev d = make_dev(c, nb, false);
-        launch_mc_walks(c, d, nb, W, wbase, wrem); // walk slabs c_b at 2^-62 in d_ppr
-        const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
-        int h = ev_begin(c, 12);
-        hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
-                           (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
-        ev_end(c, h);
-        for (size_t ck = 0; ck < r.chunks.size(); ck++) {
-            if (!one_chunk && (rc = bwd_write(c, r, ck))) return rc;
-            const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
-            h = ev_begin(c, 12);
-            hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                               (const uint64_t *)c->d_residue, (uint32_t)nb, (const int32_t *)c->d_src, (const uint64_t *)c->d_boff,
-                               (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->d_ppr);
-            ev_end(c, h);
-        }
-        h = ev_begin(c, 12);
-        hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
-                           n, (uint64_t)nb); // -> slot-major estimates at 2^-60 in the residue slabs
-        ev_end(c, h);
-        Dev dr = d;
-        dr.ppr = c->d_residue;
-        {
-            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
-            h = ev_begin(c, 4);
-            hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dr);
-            ev_end(c, h);
-        }
-        if (want_topk) {
-            h = ev_begin(c, 4);
-            rc = launch_select(c, dr, nb, k, c->d_topk_ids, c->d_topk_sc, 0);
-            if (rc) return rc;
-            ev_end(c, h);
-        }
-        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        ev_end(c, hb);
-        rc = check_dev_err(c);
-        if (rc) return rc;
-        if ((rc = bwd_check_err(c, "bippr"))) return rc;
-        ev_collect(c);
-        c->timing.walks += W * (uint64_t)nb;
-        c->timing.walk_steps += *c->h_steps_pin;
-        if (stats)
-            for (int i = 0; i < nb; i++) {
-                fora_query_stats &o = stats[b0 + i];
-                memset(&o, 0, sizeof(o));
-                o.n_walks = W;
-                o.rmax_used = rmax;
-                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
-                o.dangling_source = c->h_row_ptr[sources[b0 + i] + 1] == c->h_row_ptr[sources[b0 + i]] ? 1 : 0;
-            }
-        if (want_topk) { // k_topk_select scales by 2^-62; the estimates are at 2^-60
-            std::vector<double> sc((size_t)nb * k);
-            if (ids) HIPCHK(c, hipMemcpy(ids + (size_t)b0 * k, c->d_topk_ids, (size_t)nb * k * 4, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(sc.data(), c->d_topk_sc, sc.size() * 8, hipMemcpyDeviceToHost));
-            if (scores) for (size_t i = 0; i < sc.size(); i++) scores[(size_t)b0 * k + i] = sc[i] * 4;
-        }
-        const uint64_t bytes = (uint64_t)nb * n * 8;
-        if (ppr_fix_out) HIPCHK(c, hipMemcpy(ppr_fix_out + (uint64_t)b0 * n, c->d_residue, bytes, hipMemcpyDeviceToHost));
-        if (ppr_out) {
-            double *dst = ppr_out + (uint64_t)b0 * n;
-            HIPCHK(c, hipMemcpy(dst, c->d_residue, bytes, hipMemcpyDeviceToHost));
-            uint64_t *raw = (uint64_t *)dst;
-            for (uint64_t i = 0; i < (uint64_t)nb * n; i++) dst[i] = std::ldexp((double)raw[i], -60);
-        }
-    }
+    if (r.chunks.size() == 1 && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
+    if ((rc = walk_batches(c, sources, nq, w, &r, rmax, ppr_out, ppr_fix_out, k, ids, scores, stats))) return rc;
     fill_bwd_stats(c, r, n, bwd, c->timing.walk_ms - walk_ms0);
     return FORA_OK;
+}
+
+int fora_hip_montecarlo_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out, uint64_t *ppr_fix_out,
+                              int k, int32_t *ids, double *scores, fora_query_stats *stats) {
+    return montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats); // (no buckets, no push: nothing to retry)
 }
 
 int fora_hip_bwdpush_batch(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
@@ -3127,7 +2881,6 @@ int fora_hip_bippr_batch(fora_ctx *c, const int32_t *sources, int nq, double eps
 int fora_hip_reset_timing(fora_ctx *c) {
     if (!c) return FORA_E_ARG;
     c->timing = fora_timing{};
-    if (c->twin) c->twin->timing = fora_timing{};
     (void)hipSetDevice(c->device);
     (void)hipMemset(c->d_stamps, 0, 32 * sizeof(unsigned long long));
     return FORA_OK;
@@ -3141,17 +2894,6 @@ int fora_hip_get_stamps(fora_ctx *c, uint64_t *out32) {
 int fora_hip_get_timing(fora_ctx *c, fora_timing *out) {
     if (!c || !out) return FORA_E_ARG;
     *out = c->timing;
-    if (c->twin) {
-        const fora_timing &w = c->twin->timing;
-        out->push_pop_ms += w.push_pop_ms; out->push_expand_ms += w.push_expand_ms; out->push_accum_ms += w.push_accum_ms;
-        out->walk_alloc_ms += w.walk_alloc_ms; out->walk_ms += w.walk_ms; out->walk_accum_ms += w.walk_accum_ms;
-        out->other_ms += w.other_ms; out->batch_ms += w.batch_ms;
-        out->push_pop_launches += w.push_pop_launches; out->push_expand_launches += w.push_expand_launches;
-        out->push_accum_launches += w.push_accum_launches; out->walk_launches += w.walk_launches; out->batches += w.batches;
-        out->pops += w.pops; out->relax += w.relax; out->walks += w.walks; out->walk_steps += w.walk_steps; out->levels += w.levels;
-        out->idx_hits += w.idx_hits;
-        out->push_tail_ms += w.push_tail_ms; out->push_tail_launches += w.push_tail_launches;
-    }
     return FORA_OK;
 }
 

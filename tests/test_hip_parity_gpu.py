@@ -607,19 +607,23 @@ def test_bounded_deferral_bit_exact(engine_test, oracle, small_dangling, k, dmin
         oracle.twin_set_defer_min(0)
 
 
-def test_two_lane_pipeline_same_bits(engine, oracle, small, monkeypatch):
-    """Opt-in second lane (push of batch k+1 overlapping walks of batch k) gives the same bits."""
+def test_batch_size_same_bits_no_pipeline(engine, oracle, small):
+    """Batches of 3 slots give the same ppr and residue bits as the default batch; the second lane (option
+    `pipeline`) is gone."""
+    import fora_amd
     g = small
     _load(engine, g, epsilon=0.5)
     srcs = pick_sources(g, 10, 61)
     engine.set_batch(3)
-    a, ra, _ = engine.query_fix(srcs)
-    engine.set_option("pipeline", 1)
+    try:
+        a, ra, _ = engine.query_fix(srcs)
+    finally:
+        engine.set_batch(0)
     b, rb, st = engine.query_fix(srcs)
-    engine.set_option("pipeline", 0)
-    engine.set_batch(0)
     assert (a == b).all() and (ra == rb).all()
     assert all(s["ppr_sum_fix"] == oracle.FIX_ONE for s in st)
+    with pytest.raises(fora_amd.ForaError):
+        engine.set_option("pipeline", 1)
 
 
 @pytest.mark.parametrize("gname", ["tiny_dangling", "small", "small_dangling"])
