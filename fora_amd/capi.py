@@ -18,6 +18,7 @@ SYMBOLS = [
     "fora_hip_query_batch_fix", "fora_hip_topk_batch", "fora_hip_topk_bound_batch", "fora_hip_power_iteration_batch", "fora_hip_push_batch", "fora_hip_walk_counts",
     "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
     "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bwdpush_batch",
+    "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -61,6 +62,21 @@ class BwdStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SparseStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("max_row", C.c_uint64), ("thr_fix", C.c_uint64), ("batches", C.c_int32),
+                ("reserved_", C.c_int32), ("compact_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def to_torch_csr(row_ptr, ids, vals, n):
+    """The [nq, n] torch.sparse_csr_tensor of a device result of Engine.query_sparse (column ids widened to int64 to
+    match row_ptr)."""
+    import torch
+    return torch.sparse_csr_tensor(row_ptr, ids.to(torch.int64), vals, size=(row_ptr.numel() - 1, int(n)))
 
 
 def lib_path():
@@ -111,6 +127,7 @@ class Engine:
         if rc:
             raise ForaError(rc, "fora_hip_create failed (no gfx950 GPU visible?)")
         self.n = 0
+        self.device = int(device)
 
     def close(self):
         if self._ctx:
@@ -211,6 +228,50 @@ class Engine:
         self._chk(self._lib.fora_hip_query_batch_fix(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)),
                                                      _p(ppr), _p(res), st))
         return ppr, res, self._stats(st, nq)
+
+    def query_sparse(self, sources, with_idx=False, threshold=None, want_fix=False, device=False):
+        """query() with the result kept sparse (fora_hip_query_sparse_batch + fora_hip_sparse_fetch): node v of row i is
+        kept iff its fixed-point word is >= max(1, ceil(threshold * 2^62)); threshold=None: 1 / n.  Returns
+        (row_ptr, ids, vals, stats, sparse_stats), with want_fix (row_ptr, ids, vals, fix, stats, sparse_stats): a CSR over
+        the sources, ids ascending inside a row.  device=False: numpy arrays (int64, int32, float64, uint64).
+        device=True: torch tensors on the context's GPU (fix as int64 bits), written there by the library; torch must have
+        been imported before the library was loaded (one HIP runtime in the process)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        sp = SparseStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
+                                                        _p(row_ptr), st, C.byref(sp)))
+        e = int(sp.entries)
+        if device:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("query_sparse(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
+                                   "HIP runtime: import torch before the first Engine is created")
+            dev = torch.device("cuda", self.device)
+            ids = torch.empty(e, dtype=torch.int32, device=dev)
+            vals = torch.empty(e, dtype=torch.float64, device=dev)
+            fix = torch.empty(e, dtype=torch.int64, device=dev) if want_fix else None
+            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
+            self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()),
+                                                      C.c_void_p(fix.data_ptr()) if want_fix else None, C.c_uint64(e)))
+            row_ptr = torch.from_numpy(row_ptr).to(dev)
+        else:
+            ids = np.zeros(e, dtype=np.int32)
+            vals = np.zeros(e, dtype=np.float64)
+            fix = np.zeros(e, dtype=np.uint64) if want_fix else None
+            self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), C.c_uint64(e)))
+        out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
+        return out + (self._stats(st, nq), sp.as_dict())
+
+    def sparse_fetch(self, ids=None, vals=None, fix=None, cap=0):
+        """fora_hip_sparse_fetch into caller-made numpy arrays (any of them None): the held result, again."""
+        self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), C.c_uint64(int(cap))))
+
+    def sparse_clear(self):
+        self._chk(self._lib.fora_hip_sparse_clear(self._ctx))
 
     def push(self, sources, want=True):
         """want=False: only the per-query stats come back (the slabs stay in HBM)."""

@@ -267,6 +267,19 @@ struct fora_ctx {
     uint32_t g_wgs = 0;
     unsigned long long *d_bstat = nullptr;
     double bwd_ms = 0, combine_ms = 0; // event times of the call in progress (EvPair kinds 11, 12)
+
+    // sparse result of the last fora_hip_query_sparse_batch (free_sparse): its own buffers, apart from the workspace --
+    // free_workspace (set_batch, set_option, a bucket retry) leaves them alone
+    int32_t *d_sp_ids = nullptr;     // [sp_cap] entries of all rows, rows in the caller's order
+    uint64_t *d_sp_fix = nullptr;
+    uint64_t sp_cap = 0, sp_entries = 0;
+    bool sp_valid = false;           // a result is held (it may have no entries)
+    uint32_t *d_sp_counts = nullptr, *d_sp_tot = nullptr; // per workgroup [slots][X] and per slot counts of the batch in progress
+    int64_t *d_sp_base = nullptr;    // first entry of every live row of the call
+    uint32_t *h_sp_tot = nullptr;    // pinned landing area of d_sp_tot
+    uint64_t sp_counts_cap = 0, sp_slots_cap = 0, sp_base_cap = 0;
+    double *d_sp_stage = nullptr;    // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
+    double sp_compact_ms = 0;        // event time of the call in progress (EvPair kind 13)
 };
 
 namespace {
@@ -304,6 +317,13 @@ void free_graph(fora_ctx *c) {
     dfree(c->d_gr); dfree(c->d_gp); dfree(c->d_gfy); dfree(c->d_gtag); dfree(c->d_glist); dfree(c->d_gfn); c->g_wgs = 0; // (sized by n)
     c->split_pbins = 0;
     c->n = 0; c->nnz = 0;
+}
+void free_sparse(fora_ctx *c) {
+    dfree(c->d_sp_ids); dfree(c->d_sp_fix); dfree(c->d_sp_counts); dfree(c->d_sp_tot); dfree(c->d_sp_base); dfree(c->d_sp_stage);
+    if (c->h_sp_tot) (void)hipHostFree(c->h_sp_tot);
+    c->h_sp_tot = nullptr;
+    c->sp_cap = c->sp_entries = c->sp_counts_cap = c->sp_slots_cap = c->sp_base_cap = 0;
+    c->sp_valid = false;
 }
 void free_index(fora_ctx *c) {
     dfree(c->d_rw_idx); dfree(c->d_idx_off); dfree(c->d_idx_cnt);
@@ -804,6 +824,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case 10: c->timing.push_team_ms += ms; c->timing.push_team_launches++; break;
         case 11: c->bwd_ms += ms; break;     // backward push: reported through fora_bwd_stats only (fora_timing keeps its layout)
         case 12: c->combine_ms += ms; break;
+        case 13: c->sp_compact_ms += ms; break; // k_sparse_count / k_sparse_write: reported through fora_sparse_stats only
         case 8: c->timing.push_accum_ms += ms; break; // k_round_sweep: part of the level's accumulate time, not a launch of its own in the counts
         }
     }
@@ -1233,6 +1254,152 @@ static int even_batch(int nq, int B) {
     return (nq + nbatch - 1) / nbatch;
 }
 
+// ---- sparse results (fora_hip_query_sparse_batch): host side of one attempt of a call.  Rows are laid out in the
+// caller's order; a batch's rows are placed when its counts are back -- every row before them is known by then (live
+// rows of earlier batches, one entry per dangling row).
+struct SparseRun {
+    uint64_t thr = 1;
+    uint32_t R = SP_TILE, X = 1;       // ids per workgroup, workgroups per slot
+    std::vector<int64_t> row_ptr;      // nq + 1
+    std::vector<int64_t> dang_at;      // entries of the dangling rows ...
+    std::vector<int32_t> dang_src;     // ... and their sources
+    int next_row = 0, live_done = 0, batches = 0;
+    uint64_t cur = 0, max_row = 0;     // entries placed so far; the longest row
+};
+
+// per-call buffers of the two passes: `slots` slots per batch, `live` live rows in all
+int sparse_prepare(fora_ctx *c, SparseRun &sp, int nq, int slots, int live) {
+    const uint64_t n = (uint64_t)c->n;
+    sp.R = (uint32_t)std::max<uint64_t>(8 * SP_TILE, ((n + 1023) / 1024 + SP_TILE - 1) / SP_TILE * SP_TILE); // at most 1024 workgroups per slot
+    sp.X = (uint32_t)((n + sp.R - 1) / sp.R);
+    sp.row_ptr.assign((size_t)nq + 1, 0);
+    const uint64_t counts = (uint64_t)slots * sp.X;
+    if (counts > c->sp_counts_cap) {
+        dfree(c->d_sp_counts); c->sp_counts_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_sp_counts, counts * 4));
+        c->sp_counts_cap = counts;
+    }
+    if ((uint64_t)slots > c->sp_slots_cap) {
+        dfree(c->d_sp_tot); c->sp_slots_cap = 0;
+        if (c->h_sp_tot) (void)hipHostFree(c->h_sp_tot);
+        c->h_sp_tot = nullptr;
+        HIPCHK(c, hipMalloc(&c->d_sp_tot, (size_t)slots * 4));
+        HIPCHK(c, hipHostMalloc((void **)&c->h_sp_tot, (size_t)slots * 4));
+        c->sp_slots_cap = (uint64_t)slots;
+    }
+    if ((uint64_t)live > c->sp_base_cap) {
+        dfree(c->d_sp_base); c->sp_base_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_sp_base, (size_t)live * 8));
+        c->sp_base_cap = (uint64_t)live;
+    }
+    return FORA_OK;
+}
+
+// room for `need` entries, the first `keep` of them already written; rows_done of rows_all rows are placed (what the
+// rest will take is guessed from them, and asked for again if the guess was short)
+int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done, uint64_t rows_all) {
+    if (need <= c->sp_cap) return FORA_OK;
+    const uint64_t guess = rows_done ? (uint64_t)((double)need / (double)rows_done * (double)rows_all * 1.125) + 1024 : need;
+    int32_t *ids = nullptr;
+    uint64_t *fix = nullptr;
+    uint64_t cap = std::max<uint64_t>({need, guess, 1});
+    for (;; cap = need) { // (a guess that does not fit is no reason to fail)
+        if (hipMalloc(&ids, cap * 4) == hipSuccess && hipMalloc(&fix, cap * 8) == hipSuccess) break;
+        (void)hipGetLastError();
+        dfree(ids); dfree(fix);
+        if (cap == need) {
+            (void)hipStreamSynchronize(c->stream);
+            free_sparse(c);
+            return fail(c, FORA_E_NOMEM, "no device memory for the sparse result");
+        }
+    }
+    keep = std::min(keep, c->sp_cap);
+    if (keep) {
+        HIPCHK(c, hipMemcpyAsync(ids, c->d_sp_ids, keep * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(fix, c->d_sp_fix, keep * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    dfree(c->d_sp_ids); dfree(c->d_sp_fix);
+    c->d_sp_ids = ids; c->d_sp_fix = fix; c->sp_cap = cap;
+    return FORA_OK;
+}
+
+// count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out)
+int sparse_count(fora_ctx *c, const SparseRun &sp, int nb) {
+    HIPCHK(c, hipMemsetAsync(c->d_sp_tot, 0, (size_t)nb * 4, c->stream));
+    const int h = ev_begin(c, 13);
+    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, (uint32_t)c->n, sp.thr, sp.R,
+                       c->d_sp_counts, c->d_sp_tot);
+    ev_end(c, h);
+    HIPCHK(c, hipMemcpyAsync(c->h_sp_tot, c->d_sp_tot, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    return FORA_OK;
+}
+
+// rows of the caller up to (not including) row `upto` that no batch has placed yet: dangling sources, one entry each
+void sparse_skip_dangling(SparseRun &sp, const int32_t *sources, int upto) {
+    for (; sp.next_row < upto; sp.next_row++) {
+        sp.row_ptr[(size_t)sp.next_row] = (int64_t)sp.cur;
+        sp.dang_at.push_back((int64_t)sp.cur);
+        sp.dang_src.push_back(sources[sp.next_row]);
+        sp.cur += 1;
+        sp.max_row = std::max<uint64_t>(sp.max_row, 1);
+    }
+}
+
+// write pass of the batch just closed (slot i: row at[i] of the caller); the slabs hold it until the next batch starts
+// on the same stream
+int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, const int *at, int nb) {
+    std::vector<int64_t> base((size_t)nb);
+    const uint64_t keep = sp.cur; // (dangling rows are written at the end: nothing of them to keep)
+    for (int i = 0; i < nb; i++) {
+        sparse_skip_dangling(sp, sources, at[i]);
+        sp.row_ptr[(size_t)at[i]] = base[(size_t)i] = (int64_t)sp.cur;
+        sp.cur += c->h_sp_tot[i];
+        sp.max_row = std::max<uint64_t>(sp.max_row, c->h_sp_tot[i]);
+        sp.next_row = at[i] + 1;
+    }
+    sp.batches++;
+    if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? keep : 0, (uint64_t)sp.next_row, (uint64_t)nq)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_sp_base + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
+    const int h = ev_begin(c, 13);
+    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, (uint32_t)c->n, sp.thr, sp.R,
+                       (const uint32_t *)c->d_sp_counts, (const int64_t *)(c->d_sp_base + sp.live_done), c->d_sp_ids, c->d_sp_fix, c->sp_cap);
+    ev_end(c, h);
+    sp.live_done += nb;
+    return FORA_OK;
+}
+
+// end of a call whose batches all went through: the dangling rows' entries, the last event times, the result is held
+int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, int64_t *row_ptr, fora_sparse_stats *out) {
+    sparse_skip_dangling(sp, sources, nq);
+    sp.row_ptr[(size_t)nq] = (int64_t)sp.cur;
+    if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? sp.cur : 0, (uint64_t)nq, (uint64_t)nq)) return rc; // (only grows when dangling rows came last)
+    DevTmp at, src;
+    const size_t nd = sp.dang_at.size();
+    if (nd) {
+        HIPCHK(c, hipMalloc(&at.p, nd * 8));
+        HIPCHK(c, hipMalloc(&src.p, nd * 4));
+        HIPCHK(c, hipMemcpyAsync(at.p, sp.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(src.p, sp.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_sparse_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd,
+                           (const int64_t *)at.p, (const int32_t *)src.p, c->d_sp_ids, c->d_sp_fix, c->sp_cap);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse result: ") + hipGetErrorString(e));
+    ev_collect(c);
+    c->sp_entries = sp.cur;
+    c->sp_valid = true;
+    memcpy(row_ptr, sp.row_ptr.data(), ((size_t)nq + 1) * 8);
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->entries = sp.cur; out->max_row = sp.max_row; out->thr_fix = sp.thr; out->batches = sp.batches;
+        out->compact_ms = c->sp_compact_ms;
+    }
+    return FORA_OK;
+}
+
 // refinement launches after k_walk_alloc: indexed walks, online walks, and the accumulate of their results
 void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t round, int nzh) {
     const dim3 wg(walk_grid_x(c, nq), nq);
@@ -1342,7 +1509,7 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
 
 // One batch of <= B sources: push (+ refinement) and k_ppr_sum, then the batch's close-out; its per-slot accumulators
 // land in h_qs.  Results stay in the slabs.
-int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int flags) {
+int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int flags, const SparseRun *sp = nullptr) {
     const int hb = ev_begin(c, 5);
     int rc = reset_batch_state(c, nq, sources);
     if (rc) return rc;
@@ -1375,6 +1542,7 @@ int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, 
         hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, d);
         ev_end(c, h);
     }
+    if (sp) if ((rc = sparse_count(c, *sp, nq))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if ((rc = close_batch(c, hb, "batch"))) return rc;
@@ -1408,7 +1576,7 @@ int ensure_query_workspace(fora_ctx *c, int slots, int k) {
 // into ids / scores (either may be null); the caller has checked 1 <= topk <= min(SEL_MAXK, n).
 int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int flags, double *ppr_d,
                  uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats, int topk = 0, int32_t *ids = nullptr,
-                 double *scores = nullptr) {
+                 double *scores = nullptr, SparseRun *sp = nullptr) {
     if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1438,15 +1606,18 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     }
     const bool want_topk = topk > 0 && (ids || scores);
     const int nl = (int)live_src.size();
+    if (sp) sp->row_ptr.assign((size_t)nq + 1, 0);
     if (nl == 0) return FORA_OK;
     int rc = ensure_query_workspace(c, nl, want_topk ? topk : 0);
     if (rc) return rc;
     const int per = even_batch(nl, c->B);
+    if (sp) if ((rc = sparse_prepare(c, *sp, nq, std::min(per, nl), nl))) return rc;
     for (int b0 = 0; b0 < nl; b0 += per) {
         const int nb = std::min(per, nl - b0);
         const int *at = live_at.data() + b0; // places of the batch's slots in the caller's arrays
-        if ((rc = run_query_batch(c, live_src.data() + b0, nb, with_idx != 0, flags))) return rc;
+        if ((rc = run_query_batch(c, live_src.data() + b0, nb, with_idx != 0, flags, sp))) return rc;
         if (stats) for (int i = 0; i < nb; i++) fill_stats(c, i, stats[at[i]]);
+        if (sp) if ((rc = sparse_place(c, *sp, sources, nq, at, nb))) return rc;
         if (want_topk) {
             if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
             if ((rc = copy_topk_out(c, nb, topk, ids, scores, 0, at))) return rc;
@@ -1664,6 +1835,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_workspace(c);
     free_index(c);
     free_graph(c);
+    free_sparse(c);
     dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
     dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er); dfree(c->d_bstat);
     dfree(c->d_stamps);
@@ -1897,6 +2069,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_workspace(c);
     free_index(c);
     free_graph(c);
+    free_sparse(c); // (rows of another graph)
     c->bk_scale = 1; c->bk_scale_topk = 1;
     std::vector<uint64_t> rowinfo((size_t)n);
     std::vector<uint32_t> deg((size_t)n);
@@ -2140,6 +2313,72 @@ int fora_hip_query_batch(fora_ctx *c, const int32_t *sources, int nq, int with_i
 int fora_hip_query_batch_fix(fora_ctx *c, const int32_t *sources, int nq, int with_idx, uint64_t *ppr_fix_out,
                              uint64_t *residue_fix_out, fora_query_stats *stats) {
     return with_bucket_retry(c, [&] { return query_common(c, sources, nq, with_idx, 0, nullptr, ppr_fix_out, residue_fix_out, stats); });
+}
+
+int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t *row_ptr,
+                                fora_query_stats *stats, fora_sparse_stats *sp_out) {
+    if (!c) return FORA_E_ARG;
+    c->sp_valid = false; // the held result ends here, whatever becomes of this call
+    c->sp_entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    return with_bucket_retry(c, [&] {
+        SparseRun run; // (a retried attempt starts from an empty one)
+        run.thr = thr;
+        c->sp_compact_ms = 0;
+        if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, &run)) return rc;
+        return sparse_finish(c, run, sources, nq, row_ptr, sp_out);
+    });
+}
+
+// is p device memory of the ctx's GPU?  (host memory the runtime has never seen: no attributes, or "unregistered")
+static int sparse_dest(fora_ctx *c, const void *p, bool &on_device) {
+    hipPointerAttribute_t a{};
+    on_device = false;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return FORA_OK; }
+    if (a.type != hipMemoryTypeDevice) return FORA_OK;
+    if (a.device != c->device) return fail(c, FORA_E_ARG, "destination is memory of another GPU");
+    on_device = true;
+    return FORA_OK;
+}
+
+int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp_valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (cap < c->sp_entries) return fail(c, FORA_E_ARG, "cap is smaller than the held result");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t e = c->sp_entries;
+    bool vals_on_device = false;
+    if (vals) if (int rc = sparse_dest(c, vals, vals_on_device)) return rc;
+    if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->d_sp_ids, e * 4, hipMemcpyDefault, c->stream));
+    if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, c->d_sp_fix, e * 8, hipMemcpyDefault, c->stream));
+    if (e && vals) {
+        constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
+        const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
+        if (vals_on_device) {
+            hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_sp_fix, e, vals);
+        } else {
+            if (!c->d_sp_stage) HIPCHK(c, hipMalloc(&c->d_sp_stage, SP_STAGE * 8));
+            for (uint64_t at = 0; at < e; at += SP_STAGE) {
+                const uint64_t len = std::min(SP_STAGE, e - at);
+                hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_sp_fix + at, len, c->d_sp_stage);
+                HIPCHK(c, hipMemcpyAsync(vals + at, c->d_sp_stage, len * 8, hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse fetch: ") + hipGetErrorString(err));
+    return FORA_OK;
+}
+
+int fora_hip_sparse_clear(fora_ctx *c) {
+    if (!c) return FORA_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_sparse(c);
+    return FORA_OK;
 }
 
 int fora_hip_push_batch(fora_ctx *c, const int32_t *sources, int nq, uint64_t *reserve_fix_out,

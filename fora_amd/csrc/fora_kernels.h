@@ -3238,4 +3238,121 @@ __global__ void __launch_bounds__(BLOCK) k_walk_mc(Dev d, uint64_t wbase, uint64
     }
 }
 
+// ------------------------------------------------------------------ sparse results (fora_hip_query_sparse_batch)
+// A slot's entries of at least `thr` units (thr >= 1: zeros never pass), compacted in id order into the call's result.
+// Workgroup x of slot q owns the ids [x * R, (x + 1) * R), R a multiple of SP_TILE; k_sparse_count leaves its count in
+// counts[q * X + x] and adds it to tot[q], k_sparse_write places its entries behind those of the workgroups before it.
+// A lane takes the two words of one 16-byte line.  The slab of slot q starts at word q * n, an odd word when q * n is
+// odd: the lanes' pairs then start one id below the range (pair p of the sweep holds ids lo - odd + 2p, + 1) and the ids
+// outside [lo, hi) are masked.  The kernels read the ppr slab and nothing else of the workspace, whatever the layout.
+constexpr int SP_TILE = 2 * BLOCK; // ids per workgroup and step
+constexpr int SP_UNROLL = 4;       // count pass: loads in flight per lane
+__device__ __forceinline__ void sp_load(const uint64_t *slab, int64_t p, int64_t lo, int64_t hi, uint64_t &a, uint64_t &b) {
+    a = 0; b = 0;
+    if (p >= lo && p + 1 < hi) {
+        const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(slab + p);
+        a = x.x; b = x.y;
+    } else {
+        if (p >= lo && p < hi) a = slab[p];
+        if (p + 1 >= lo && p + 1 < hi) b = slab[p + 1];
+    }
+}
+// lanes below this one whose bit is set in mask (v_mbcnt_lo / _hi)
+__device__ __forceinline__ uint32_t sp_mbcnt(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+// grid = (X, nb)
+__global__ void __launch_bounds__(BLOCK) k_sparse_count(const uint64_t *ppr, uint32_t n, uint64_t thr, uint32_t R, uint32_t *counts,
+                                                        uint32_t *tot) {
+    __shared__ uint32_t s_w[BLOCK / 64];
+    const uint32_t q = blockIdx.y;
+    const uint64_t first = (uint64_t)q * n;
+    const uint64_t *slab = ppr + first;
+    const int64_t lo = (int64_t)blockIdx.x * R, hi = min((int64_t)n, lo + (int64_t)R);
+    uint32_t c = 0;
+    const auto masked = [&](int64_t t) { // a step that reaches over an end of the range
+        uint64_t a, b;
+        sp_load(slab, t + 2 * (int64_t)threadIdx.x, lo, hi, a, b);
+        c += (a >= thr ? 1u : 0u) + (b >= thr ? 1u : 0u);
+    };
+    int64_t t = lo - (int64_t)(first & 1);
+    if (first & 1) { masked(t); t += SP_TILE; }
+    for (; t + (int64_t)SP_TILE * SP_UNROLL <= hi; t += (int64_t)SP_TILE * SP_UNROLL) { // whole steps: SP_UNROLL 16-byte loads in flight
+        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(slab + t) + threadIdx.x;
+        ulonglong2 x[SP_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SP_UNROLL; u++) x[u] = src[u * BLOCK];
+#pragma unroll
+        for (int u = 0; u < SP_UNROLL; u++) c += (x[u].x >= thr ? 1u : 0u) + (x[u].y >= thr ? 1u : 0u);
+    }
+    for (; t < hi; t += SP_TILE) masked(t);
+    c = (uint32_t)wave_sum((uint64_t)c);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; w++) t += s_w[w];
+        counts[(uint64_t)q * gridDim.x + blockIdx.x] = t;
+        if (t) atomicAdd(&tot[q], t);
+    }
+}
+// base[q]: first entry of slot q's row in ids / fix (64-bit: a call can hold more than 2^32 entries).  Per step every
+// wave ranks its 128 ids with two ballots, and the four wave totals cross through LDS once (two sets of words, one
+// barrier per step); a workgroup without entries leaves at once, one with entries as soon as its last one is out.
+// cap: entries ids / fix hold (nothing is written beyond it).
+__global__ void __launch_bounds__(BLOCK) k_sparse_write(const uint64_t *ppr, uint32_t n, uint64_t thr, uint32_t R, const uint32_t *counts,
+                                                        const int64_t *base, int32_t *ids, uint64_t *fix, uint64_t cap) {
+    __shared__ uint32_t s_w[2][BLOCK / 64];
+    __shared__ uint32_t s_before[BLOCK / 64];
+    const uint32_t q = blockIdx.y;
+    const uint32_t *cq = counts + (uint64_t)q * gridDim.x;
+    const uint32_t mine = cq[blockIdx.x];
+    if (!mine) return;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t part = 0;
+    for (uint32_t x = threadIdx.x; x < blockIdx.x; x += BLOCK) part += cq[x];
+    part = (uint32_t)wave_sum((uint64_t)part);
+    if (lane == 0) s_before[w] = part;
+    __syncthreads();
+    uint32_t before = 0;
+#pragma unroll
+    for (int i = 0; i < BLOCK / 64; i++) before += s_before[i];
+    uint64_t out = (uint64_t)base[q] + before;
+    const uint64_t first = (uint64_t)q * n;
+    const uint64_t *slab = ppr + first;
+    const int64_t lo = (int64_t)blockIdx.x * R, hi = min((int64_t)n, lo + (int64_t)R);
+    int64_t p = lo - (int64_t)(first & 1) + 2 * (int64_t)threadIdx.x;
+    uint64_t a, b;
+    sp_load(slab, p, lo, hi, a, b);
+    uint32_t done = 0;
+    for (int64_t t = lo - (int64_t)(first & 1); t < hi && done < mine; t += SP_TILE, p += SP_TILE) { // (t, done: the same in every lane)
+        const int par = (int)((uint64_t)(t - lo + 1) / SP_TILE) & 1;
+        uint64_t na, nb; // the next step's words are under way while this step's ranks cross
+        sp_load(slab, p + SP_TILE, lo, hi, na, nb);
+        const bool fa = a >= thr, fb = b >= thr;
+        const unsigned long long ma = __ballot(fa), mb = __ballot(fb);
+        const uint32_t rank = sp_mbcnt(ma) + sp_mbcnt(mb);
+        if (lane == 0) s_w[par][w] = (uint32_t)(__popcll(ma) + __popcll(mb));
+        __syncthreads();
+        uint32_t off = rank, tile = 0;
+#pragma unroll
+        for (int i = 0; i < BLOCK / 64; i++) { const uint32_t c = s_w[par][i]; if (i < w) off += c; tile += c; }
+        const uint64_t ia = out + off, ib = ia + (fa ? 1u : 0u);
+        if (fa && ia < cap) { ids[ia] = (int32_t)p; fix[ia] = a; }
+        if (fb && ib < cap) { ids[ib] = (int32_t)(p + 1); fix[ib] = b; }
+        out += tile; done += tile;
+        a = na; b = nb;
+    }
+}
+// the one-entry rows of dangling sources: (src[i], 1.0) at entry at[i]
+__global__ void __launch_bounds__(BLOCK) k_sparse_single(uint32_t cnt, const int64_t *at, const int32_t *src, int32_t *ids, uint64_t *fix, uint64_t cap) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < cnt && (uint64_t)at[i] < cap) { ids[at[i]] = src[i]; fix[at[i]] = FIX_ONE; }
+}
+// vals of fora_hip_sparse_fetch: fix * 2^-62
+__global__ void __launch_bounds__(BLOCK) k_sparse_vals(const uint64_t *fix, uint64_t cnt, double *vals) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * BLOCK) vals[i] = fix2d(fix[i]);
+}
+
 } // namespace fora

@@ -59,6 +59,26 @@
  * pops and ppr[i] = floor(c[i] / 4) (the reference's else branch, query.h:114-119).  A dangling source keeps the
  * reference's bias: every walk stops at s and no in-edge reaches s, so ppr = keep(2^60) at s and 0 elsewhere.  Double
  * outputs are value * 2^-60; sum(ppr) (ppr_sum_fix) is NOT conserved (an estimate, not a distribution).
+ * SPARSE RESULTS (fora_hip_query_sparse_batch, fora_hip_sparse_fetch, fora_hip_sparse_clear).  The query is
+ * fora_hip_query_batch's: same push, same walks, same batching, same dangling-source fast path, same fora_query_stats,
+ * same bits in the ppr slabs.  Only what leaves the device differs: a CSR over the call's sources, compacted on the GPU.
+ *   - thr_fix = max(1, ceil(threshold * 2^62)), threshold * 2^62 being the exact ldexp of the double; threshold <= 0
+ *     means 1 (every non-zero entry); threshold > 1 or NaN is FORA_E_ARG.  Node v of row i is kept iff
+ *     ppr_fix[i][v] >= thr_fix: the test is made on the fixed-point word, never on a double.  sum(ppr) == FORA_FIX_ONE,
+ *     so a row has at most floor(2^62 / thr_fix) entries, whatever the graph.
+ *   - row i belongs to sources[i], in the caller's order; duplicate sources give duplicate rows; a dangling source gives
+ *     the single entry (s, FORA_FIX_ONE); inside a row the ids ascend; row_ptr[0] == 0, row_ptr[nq] == entries.
+ *   - fix is the raw word and vals[j] == ldexp((double)fix[j], -62), the value the dense ppr_out holds for that node.
+ *   - the result lives in device memory owned by the ctx, outside the query workspace.  It stays valid until the next
+ *     fora_hip_query_sparse_batch (whatever that call returns), fora_hip_sparse_clear, fora_hip_set_graph or
+ *     fora_hip_destroy; every other entry point (queries, top-k, baselines, set_option, set_batch, a bucket retry of a
+ *     later call) leaves it untouched.  A failed sparse call leaves no result.
+ *   - fora_hip_sparse_fetch may be called any number of times.  Each output pointer may be pageable host memory or device
+ *     memory on the ctx's GPU (a device destination is written by the device, never staged through the host).  The ctx's
+ *     stream is synchronised before the call returns, so another stream may read a device destination at once.
+ *     cap < entries, or no held result: FORA_E_ARG and nothing is written.
+ *   - NULL ctx (answered without touching the GPU), NULL row_ptr, bad nq / sources, with_idx without an index:
+ *     FORA_E_ARG.  No device memory for the result: FORA_E_NOMEM, no result held, the ctx still usable.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -137,6 +157,16 @@ typedef struct {
     double bwd_ms, walk_ms, combine_ms;
 } fora_bwd_stats;
 
+/* What a sparse call kept (fora_hip_query_sparse_batch). */
+typedef struct {
+    uint64_t entries;     /* entries kept over the whole call (== row_ptr[nq]) */
+    uint64_t max_row;     /* longest row */
+    uint64_t thr_fix;     /* the threshold actually applied, in units of 2^-62 */
+    int32_t batches;      /* query batches the call ran */
+    int32_t reserved_;
+    double compact_ms;    /* device time of the compaction kernels, summed over the batches */
+} fora_sparse_stats;
+
 /* ---- lifecycle ---------------------------------------------------------- */
 int fora_hip_device_count(void); /* usable HIP devices (0 when there is none) */
 int fora_hip_create(int device, fora_ctx **out);
@@ -210,6 +240,16 @@ int fora_hip_query_batch(fora_ctx *ctx, const int32_t *sources, int nq, int with
 int fora_hip_query_batch_fix(fora_ctx *ctx, const int32_t *sources, int nq, int with_idx,
                              uint64_t *ppr_fix_out, uint64_t *residue_fix_out,
                              fora_query_stats *stats);
+
+/* ---- SSPPR, result kept sparse (the SPARSE RESULTS contract above; the reference keeps ppr sparse too: an iMap with
+ * an occur list, algo.h).  fora_hip_query_batch with the rows thresholded and compacted on the GPU into a CSR the ctx
+ * holds.  row_ptr: nq + 1 entries, required. */
+int fora_hip_query_sparse_batch(fora_ctx *ctx, const int32_t *sources, int nq, int with_idx,
+                                double threshold, int64_t *row_ptr,
+                                fora_query_stats *stats /*nq or NULL*/, fora_sparse_stats *sp /*or NULL*/);
+/* copies the held result; any of ids / vals / fix may be NULL; cap = entries each non-NULL array can take */
+int fora_hip_sparse_fetch(fora_ctx *ctx, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap);
+int fora_hip_sparse_clear(fora_ctx *ctx);
 
 /* ---- top-k: replaces the topk() loop over get_topk -> fora_query_topk_new +
  * topk_ppr (query.h:1397-1401, 1139-1156, 972-1045; algo.h:592-610), --opt driver.
