@@ -1,6 +1,8 @@
 """BiPPR in Python (test helper): bippr_setting (algo.h:442-447), the fixed-point backward push of include/fora_hip.h
 (twin_bwd_push), reverse_local_update_linear in f64 FIFO order as the reference writes it (fifo_bwd_push,
-algo.h:703-751) and the BiPPR estimate (twin_bippr, bippr_query query.h:71-124)."""
+algo.h:703-751) and the BiPPR estimate (twin_bippr, bippr_query query.h:71-124); what the GPU tests need to know about
+a push beyond its result (support_of, targets_over_cap, slot_of), the graph that puts a residue on the pop threshold and
+the top-k order of a dense row (topk_of).  Everything fixed-point stays in Python ints, where a u64 wrap cannot hide."""
 import math
 from collections import deque
 
@@ -37,8 +39,63 @@ def reverse_csr(g):
     return _REV[key][1], _REV[key][2]
 
 
+_PAIRS = {}
+
+
+def _in_pairs(g):
+    """In-edges as Python lists (the twin's inner loop reads nothing else): pairs[v] = [(u, outdeg(u)) for u -> v]."""
+    key = id(g)
+    if key not in _PAIRS:
+        rin_ptr, rin = reverse_csr(g)
+        ptr, rin, deg = rin_ptr.tolist(), rin.tolist(), np.diff(g.row_ptr).tolist()
+        _PAIRS[key] = (g, [[(u, deg[u]) for u in rin[ptr[v]:ptr[v + 1]]] for v in range(g.n)])
+    return _PAIRS[key][1]
+
+
 def twin_bwd_push_sparse(g, t, rmax, alpha=0.2):
-    """The level-synchronous push at 2^60 in Python ints: (reserve dict, residue dict, pops, relax, levels)."""
+    """The level-synchronous push at 2^60 in Python ints: (reserve dict, residue dict, pops, relax, levels).  A level
+    pops every node over thr; only a node that the level before added to can have risen over it, so those are the ones
+    looked at.  The residue dict has a key for the target and for every node that ever got a non-zero increment."""
+    pairs = _in_pairs(g)
+    thr = math.floor(math.ldexp(rmax, 60))
+    afix = int(math.ldexp(alpha, 62))
+    t = int(t)
+    r = [0] * g.n
+    r[t] = BWD_ONE
+    p = {}
+    support = {t}
+    pops = relax = levels = 0
+    front = [t] if BWD_ONE > thr else []
+    while front:
+        levels += 1
+        pops += len(front)
+        pushes = []
+        for v in front:
+            x = r[v]
+            keep = (x * afix) >> 62
+            r[v] = 0
+            p[v] = p.get(v, 0) + keep
+            pushes.append((pairs[v], x - keep))
+        touched = set()
+        add = touched.add
+        for pr, y in pushes:
+            relax += len(pr)
+            for u, d in pr:
+                inc = y // d
+                if inc:
+                    r[u] += inc
+                    add(u)
+        support |= touched
+        front = [u for u in touched if r[u] > thr]
+    r = {v: r[v] for v in support}
+    assert all(x <= thr for x in r.values())
+    assert all(x <= U64 for x in r.values()) and all(x <= U64 for x in p.values())
+    return p, r, pops, relax, levels
+
+
+def twin_bwd_push_scan(g, t, rmax, alpha=0.2):
+    """The same push written the plain way, as a cross-check of twin_bwd_push_sparse: every level scans every residue
+    for the nodes over thr, on dicts, reading the reverse CSR directly.  Slower by the size of the support per level."""
     rin_ptr, rin = reverse_csr(g)
     deg = np.diff(g.row_ptr)
     thr = math.floor(math.ldexp(rmax, 60))
@@ -65,8 +122,19 @@ def twin_bwd_push_sparse(g, t, rmax, alpha=0.2):
                 inc = y // int(deg[u])
                 if inc:
                     r[u] = r.get(u, 0) + inc
-    assert all(x <= U64 for x in r.values()) and all(x <= U64 for x in p.values())
     return p, r, pops, relax, levels
+
+
+def support_of(r):
+    """The nodes a push touched: the keys of the twin's residue dict (the target, and every node that got a non-zero
+    increment).  Its size is what the LDS tier's table has to hold."""
+    return set(r)
+
+
+def targets_over_cap(supports, cap):
+    """How many of the pushes (support sizes, one per target of a call, duplicates counted) outgrow an LDS table of
+    `cap` entries.  cap 0 sends every target to the global tier, and every support holds its target."""
+    return sum(1 for s in supports if s > cap)
 
 
 def twin_bwd_push(g, t, rmax, alpha=0.2):
@@ -140,3 +208,28 @@ def twin_bippr(g, s, rmax, W, ends, alpha=0.2, pushes=None):
         assert acc <= U64
         out[i] = acc
     return out
+
+
+def threshold_graph():
+    """(n, src, dst, target, neighbour) of the graph that puts a residue exactly on the pop threshold at alpha = 0.5:
+    the target's single in-neighbour has out-degree 2, so the target's pop keeps floor(2^60 * 2^61 / 2^62) = 2^59 and
+    the neighbour receives floor(2^59 / 2) = 2^58 = 0.25 * 2^60 exactly.  The neighbour has an in-neighbour of its own,
+    so whether it popped shows in every counter."""
+    #   3 -> 1,  1 -> 0 (the target),  1 -> 2
+    return 4, np.array([1, 1, 3], dtype=np.int32), np.array([0, 2, 1], dtype=np.int32), 0, 1
+
+
+def slot_of(u, bits=11):
+    """Home slot of node u in the LDS tier's table (fora_bwd.h: (u * 0x9E3779B1) >> (32 - BWD_TAB_BITS), 32-bit)."""
+    return ((np.asarray(u, dtype=np.uint64) * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - bits)
+
+
+def topk_of(fix, k, frac=60):
+    """(ids, scores) of a dense fixed-point row: score descending, ties id ascending, padded with (0, 0.0)."""
+    nz = np.flatnonzero(fix)
+    order = sorted(nz.tolist(), key=lambda v: (-int(fix[v]), v))[:k]
+    ids = np.zeros(k, dtype=np.int32)
+    sc = np.zeros(k, dtype=np.float64)
+    ids[:len(order)] = order
+    sc[:len(order)] = [math.ldexp(int(fix[v]), -frac) for v in order]
+    return ids, sc

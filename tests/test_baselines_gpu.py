@@ -112,6 +112,37 @@ def test_montecarlo_webstanford_size(engine, oracle):
         assert (np.abs(ppr[i] - exact[i])[big] <= 0.5 * exact[i][big]).all()
 
 
+def test_montecarlo_second_walk_launch(engine):
+    """Eight ws-sized sources in one batch: 8 W walks are more than one launch of launch_mc_walks runs (MC_LAUNCH_WALKS =
+    2^28 over all slots of the batch), so every slot's walks j >= 2^28 / 8 come from a second launch (j0 > 0)."""
+    import re
+    from fora_amd import synth
+    src = open(os.path.join(ROOT, "fora_amd", "csrc", "fora_hip.hip")).read()
+    assert re.search(r"MC_LAUNCH_WALKS\s*=\s*1ull\s*<<\s*28\b", src)  # the launch limit the arithmetic below is about
+    n, m, rp, col = synth.preset("webstanford")
+    engine.clear_index()
+    engine.set_graph(n, m, rp, col)
+    engine.set_params(epsilon=0.5, seed=SEED)
+    omega, W = mc_walks(n, 0.5)
+    nb = 8
+    assert nb * W > 1 << 28 and (1 << 28) // nb < W <= 2 * ((1 << 28) // nb)  # two launches
+    srcs = synth.query_set(n, nb, 11)
+    engine.set_batch(nb)
+    try:
+        _, fix, _, _, st = engine.montecarlo(srcs, epsilon=0.5)
+        assert engine.get_batch() >= nb  # all eight sources in one batch
+    finally:
+        engine.set_batch(0)
+    js = np.arange(W, dtype=np.uint64)
+    starts = np.zeros(W, dtype=np.int32)
+    for i, s in enumerate(srcs):
+        s = int(s)
+        assert st[i]["n_walks"] == W and st[i]["ppr_sum_fix"] == FIX_ONE and int(fix[i].sum()) == FIX_ONE
+        starts.fill(s)
+        ends = engine.walks(s, 0, starts, js)
+        assert (fix[i] == mc_from_endpoints(n, ends)).all(), (i, s)
+
+
 @pytest.mark.parametrize("layout", ["team", "bucketed", "wide"])
 @pytest.mark.parametrize("gname", ["tiny_dangling", "small"])
 def test_fwdpush_bit_exact_vs_twin(engine, oracle, request, gname, layout):
