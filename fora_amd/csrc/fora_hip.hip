@@ -107,6 +107,78 @@ static Tunables tunables_from_env() {
     return t;
 }
 
+// Owning device (PINNED: pinned host) buffer of `count` elements, move-only.  The size is written once, at alloc(); the
+// clears take it from the buffer, and a clear or a part beyond it is an error instead of a write out of bounds.
+template <typename T, bool PINNED = false> class DevBuf {
+    T *p = nullptr;
+    size_t count = 0;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), count(o.count) { o.p = nullptr; o.count = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(count, o.count); } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; count = 0; }
+    hipError_t alloc(size_t cnt) { // frees what it held; holds nothing after a failure
+        reset();
+        const hipError_t e = PINNED ? hipHostMalloc((void **)&p, cnt * sizeof(T)) : hipMalloc((void **)&p, cnt * sizeof(T));
+        if (e == hipSuccess) count = cnt; else p = nullptr;
+        return e;
+    }
+    hipError_t ensure(size_t cnt) { return p && count >= cnt ? hipSuccess : alloc(cnt); }
+    hipError_t fill(hipStream_t s, int byte, size_t from, size_t cnt) const { // elements [from, from + cnt)
+        return from + cnt > count ? hipErrorInvalidValue : hipMemsetAsync(p + from, byte, cnt * sizeof(T), s);
+    }
+    hipError_t zero(hipStream_t s) const { return fill(s, 0, 0, count); }
+    hipError_t zero(hipStream_t s, size_t cnt) const { return fill(s, 0, 0, cnt); } // a prefix
+    T *part(size_t i, size_t stride) const { return p ? p + i * stride : nullptr; } // i-th of equal parts (the parity pairs); null when empty
+    T *get() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+};
+template <typename T> using PinBuf = DevBuf<T, true>;
+
+// Everything that lives and dies with one plan of the query slots (ensure_workspace; the lazily allocated members: their
+// first user).  free_workspace assigns a fresh one: the initialisers below are the reset values.
+struct Workspace {
+    int B = 0, B_memcap = 0; // slots; slots that fitted the free memory when the workspace was planned (>= B)
+    DevBuf<uint64_t> d_residue, d_ppr, d_wl[2];
+    DevBuf<unsigned char> d_scratch; // PushSeg list during the push, WalkItem list during the walks
+    DevBuf<unsigned long long> d_counters; // wl_count | seg_count | wit_count | tot_steps
+    DevBuf<QState> d_qs; DevBuf<int32_t> d_src; DevBuf<uint32_t> d_err;
+    // bucketed push (n <= MAX_BINS * BIN_SIZE)
+    DevBuf<uint32_t> d_fl[2], d_fl_count; DevBuf<uint64_t> d_inc_tab[2]; // fl_count: [2][B * CSTRIDE]
+    DevBuf<uint32_t> d_ov_w, d_ov_count, d_ov_bin; DevBuf<uint64_t> d_ov_inc; // bucket overflow list, its size [2][B * CSTRIDE], its entries per bin [2][B][nbins]
+    DevBuf<uint32_t> d_bk_w, d_bk_count; DevBuf<uint64_t> d_bk_inc; // bk_w: empty in the wide layout
+    DevBuf<uint32_t> d_wit_count; // [B * CSTRIDE]
+    DevBuf<uint32_t> d_sw;        // [2][B * CSTRIDE] k_round_sweep: append counters, finished-workgroup tickets
+    DevBuf<uint32_t> d_tile_ctr;  // [2][B * CSTRIDE] wide bin kernels: next tile of a slot (Dev::tile_ctr)
+    DevBuf<uint64_t> d_dbm;       // [2][B][dbm_words] bounded deferral: marks of the deferred nodes (Dev::dbm)
+    DevBuf<uint32_t> d_dflag;     // [2][B][nbins]
+    DevBuf<uint32_t> d_dl;        // [2][B][n] k_push_tail's deferred lists; empty without the `defer` option
+    DevBuf<uint64_t> d_hubsum;    // [B][sub][hubs]; empty: no hub pre-aggregation
+    PinBuf<uint32_t> h_flc;       // pinned ring of per-slot frontier sizes
+    // team push (fora_team.h); d_team_msg empty: no team push with this workspace
+    DevBuf<uint32_t> d_team_msg;
+    DevBuf<uint64_t> d_team_inct, d_team_rsvl; // rsvl: reserve accumulators by local id
+    DevBuf<uint16_t> d_team_rlog_id; DevBuf<uint64_t> d_team_rlog_val; // reserve logs (TeamDev::rlog_id)
+    DevBuf<unsigned long long> d_team_cnt; // the teams' barrier words (TeamDev::cntw)
+    DevBuf<uint32_t> d_team_ctl;           // team_ctl_layout
+    uint32_t team_n = 0;                   // teams of a launch
+    int team_fit = -1;                     // 1: every workgroup of a k_push_team launch fits the device at once (occupancy x CUs >= grid); 0: no team push; -1: not asked yet
+    // allocated by their first user (ensure(): each on its own)
+    DevBuf<uint64_t> d_ppr2, d_cursor; // top-k: per-round ppr, index cursors (rw_counter)
+    uint32_t cursor_epoch = 0;         // batch serial number stamped into the cursor words (k_walk_alloc): 0 = the slabs hold no valid word
+    DevBuf<uint8_t> d_active; DevBuf<unsigned long long> d_above;
+    DevBuf<double> d_sel_thr; // [B] launch_select: per-slot limit of the entries that can be among the top k
+    // top-k with bounds: upper_bounds / lower_bounds (query.h:1350-1353), topk_filter marks, stop flags, walks of the round
+    DevBuf<double> d_upper, d_lower;
+    DevBuf<uint8_t> d_filter; DevBuf<uint32_t> d_fail; DevBuf<unsigned long long> d_round_walks;
+    DevBuf<uint32_t> d_nz_counts; // [B][NZ_X + 1]: per-block non-zero counts, then the slot's total
+    DevBuf<int32_t> d_lb_ids, d_topk_ids; DevBuf<double> d_lb_sc, d_topk_sc; // (ids, scores) pairs of B * k entries
+    PinBuf<unsigned long long> h_pinned; // [MAX_LEVELS + 2] frontier sizes read back
+    PinBuf<QState> h_qs_pin;             // pinned landing area of the per-slot accumulators
+    PinBuf<unsigned long long> h_steps_pin;
+};
+
 struct fora_ctx {
     int device = 0;
     Tunables opt_;
@@ -135,7 +207,6 @@ struct fora_ctx {
     uint32_t *d_hub_node = nullptr, *d_hub_first = nullptr;
     uint32_t hubs = 0;
     int hub_shift = 0;               // bin shift the hub ranges were built for
-    uint64_t *d_hubsum = nullptr;    // workspace: [B][sub][hubs]
     uint32_t *d_dg_perm = nullptr, *d_dg_inv = nullptr, *d_dg_colp = nullptr, *d_dg_rec = nullptr, *d_dg_invb = nullptr;
     uint8_t *d_dg_T = nullptr;
     WalkDG dg{};
@@ -143,26 +214,19 @@ struct fora_ctx {
     uint32_t *d_colt = nullptr, *d_team_off = nullptr, *d_team_n2l = nullptr, *d_team_l2n = nullptr;
     uint32_t *d_team_hubtgt = nullptr;
     uint32_t team_H = 0, team_hubs_opt = 0;
-    uint16_t *d_team_rlog_id = nullptr; uint64_t *d_team_rlog_val = nullptr; uint32_t team_rlog_cap = 0; // reserve logs (TeamDev::rlog_id)
-    uint64_t *d_team_rowl = nullptr, *d_team_rsvl = nullptr; // rows by local id (graph); reserve accumulators by local id (workspace)
+    uint32_t team_rlog_cap = 0;      // entries of a member's reserve log per slot (Workspace::d_team_rlog_id)
+    uint64_t *d_team_rowl = nullptr; // rows by local id
     uint16_t *d_team_deg16 = nullptr;
     uint32_t *d_team_rowq = nullptr; // [n] first quad of every node's row in d_colt
     uint32_t team_T = 0, team_R = 0, team_force = 0; // members per team, local ids per member; the team_size option they were built for
     bool team_checked = false, team_wanted = false;  // ensure_team has looked at this graph with these options
     double dangling_frac = 0;        // share of the nodes without out-edges
     uint64_t team_cap = 0;           // message slots per (team, parity)
-    // ... and its workspace
-    uint32_t *d_team_msg = nullptr;
-    uint64_t *d_team_inct = nullptr;
-    unsigned long long *d_team_cnt = nullptr; // the teams' barrier words (TeamDev::cntw)
-    uint32_t *d_team_ctl = nullptr; // ctl: [0] next slot, [32] abort | sync words | slot sequences
-    uint32_t team_n = 0;             // teams of a launch
     bool team_dirty = false;         // a launch ended with an error flag: its reserve accumulators (TeamDev::rsvl) may not be zero
     bool hub_for_team = false;       // the hub copy was sized for the team path (4096 hubs, k_push_tail its only reader)
     bool team_timeout_seen = false;  // the last device error was ERR_TEAM_TIMEOUT (with_retry runs the call again without the team push)
     int team_suspend = 0;            // calls left that push with the bucketed kernels after a team time-out
     uint64_t team_fallbacks = 0;     // calls re-run that way so far (fora_hip_get_option "team_fallbacks")
-    int team_fit = -1;               // 1: every workgroup of a k_push_team launch fits the device at once (occupancy x CUs >= grid); 0: no team push; -1: not asked yet
     bool team_coop_ok = false;       // launch k_push_team cooperatively (option team_coop, device attribute)
     bool team_coop_failed = false;   // hipLaunchCooperativeKernel refused once: plain launches from then on
 
@@ -178,59 +242,18 @@ struct fora_ctx {
     uint64_t idx_len = 0;
     bool have_index = false;
 
-    // workspace
-    int batch_req = 0, B = 0;
-    int B_memcap = 0; // slots that fitted the free memory when the workspace was planned (>= B)
-    uint64_t *d_residue = nullptr, *d_ppr = nullptr, *d_wl[2] = {nullptr, nullptr};
-    void *d_scratch = nullptr; // PushSeg list during the push, WalkItem list during the walks
-    uint64_t wl_cap = 0, seg_cap = 0, wit_cap = 0;
-    unsigned long long *d_counters = nullptr; // wl_count | seg_count | wit_count | tot_steps
-    QState *d_qs = nullptr;
-    int32_t *d_src = nullptr;
-    uint32_t *d_err = nullptr;
+    // workspace: its buffers (ws) and the plan they were sized for, which outlives them (a re-plan compares with it)
+    Workspace ws;
+    int batch_req = 0;
+    uint64_t wl_cap = 0, seg_cap = 0, wit_cap = 0, segq_cap = 0;
     unsigned long long *d_stamps = nullptr; // diagnostic builds (-DFORA_STAMPS)
     // bucketed push (n <= MAX_BINS * BIN_SIZE)
     bool binned = false;
     int nbins = 0, pbins = 0; // bins of the graph; bins per pass (bucket-array stride)
-    uint32_t *d_fl[2] = {nullptr, nullptr}, *d_fl_count = nullptr; // fl_count: [2][B]
-    uint64_t *d_inc_tab[2] = {nullptr, nullptr};
-    uint32_t *d_ov_w = nullptr, *d_ov_count = nullptr, *d_ov_bin = nullptr; // bucket overflow list, its size, its entries per bin [2][B][nbins]
-    uint64_t *d_ov_inc = nullptr;
-    uint32_t ov_cap = 0;
-    uint32_t *d_bk_w = nullptr, *d_bk_count = nullptr;
-    uint64_t *d_bk_inc = nullptr;
-    uint64_t segq_cap = 0;
+    uint32_t ov_cap = 0, dbm_words = 0;
     uint32_t bk_cap = 0, sub = 0; // capacity of one sub-bucket; sub-buckets per (slot, bin) = producer workgroups per slot
-    uint32_t *d_wit_count = nullptr; // [B * CSTRIDE]
-    uint32_t *d_sw = nullptr;        // [2][B * CSTRIDE] k_round_sweep: append counters, finished-workgroup tickets
-    uint32_t *d_tile_ctr = nullptr;  // [2][B * CSTRIDE] wide bin kernels: next tile of a slot (Dev::tile_ctr)
-    uint64_t *d_dbm = nullptr;       // [2][B][dbm_words] bounded deferral: marks of the deferred nodes (Dev::dbm)
-    uint32_t *d_dflag = nullptr;     // [2][B][nbins]
-    uint32_t *d_dl = nullptr;        // [2][B][n] k_push_tail's deferred lists
-    uint32_t dbm_words = 0;
     uint64_t bin_launches = 0;       // parity picks the counter set
-    uint32_t *h_flc = nullptr; // pinned ring of per-slot frontier sizes
-    uint64_t *d_ppr2 = nullptr, *d_cursor = nullptr; // top-k: per-round ppr, index cursors (rw_counter)
-    uint32_t cursor_epoch = 0;       // batch serial number stamped into the cursor words (k_walk_alloc): 0 = the slabs hold no valid word
-    uint8_t *d_active = nullptr;
-    unsigned long long *d_above = nullptr;
-    double *d_sel_thr = nullptr; // [B] launch_select: per-slot limit of the entries that can be among the top k
-    // top-k with bounds: upper_bounds / lower_bounds (query.h:1350-1353), topk_filter marks, stop flags, walks of the round
-    double *d_upper = nullptr, *d_lower = nullptr;
-    uint8_t *d_filter = nullptr;
-    uint32_t *d_fail = nullptr;
-    unsigned long long *d_round_walks = nullptr;
-    uint32_t *d_nz_counts = nullptr; // [B][NZ_X + 1]: per-block non-zero counts, then the slot's total
-    double *d_lb_sc = nullptr;
-    int32_t *d_lb_ids = nullptr;
-    int lb_cap = 0;
-    int32_t *d_topk_ids = nullptr;
-    double *d_topk_sc = nullptr;
-    int topk_cap = 0;
-    unsigned long long *h_pinned = nullptr; // [MAX_LEVELS + 2] frontier sizes read back
     std::vector<QState> h_qs;
-    QState *h_qs_pin = nullptr;              // pinned landing area of the per-slot accumulators
-    unsigned long long *h_steps_pin = nullptr;
     uint32_t bk_scale = 1;        // bucket capacity multiplier, doubled after a bucket overflow (see with_bucket_retry)
     uint32_t bk_scale_topk = 1;   // ... of the calls that plan with a divisor (bk_div > 1: the top-k driver on wide graphs).  Its own word: those calls start at 1 / 16 of a
                                   // query's buckets and overflow far more often; a doubling there must not shrink the batches of later query / power-iteration calls
@@ -301,10 +324,6 @@ template <typename T> void dfree(T *&p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
-struct DevTmp { // device buffer freed on every return path
-    void *p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-};
 
 void free_graph(fora_ctx *c) {
     dfree(c->d_row_ptr); dfree(c->d_col); dfree(c->d_rowinfo); dfree(c->d_deg); dfree(c->d_rp32); dfree(c->d_colp); dfree(c->d_col_push); dfree(c->d_row_split);
@@ -329,29 +348,7 @@ void free_index(fora_ctx *c) {
     dfree(c->d_rw_idx); dfree(c->d_idx_off); dfree(c->d_idx_cnt);
     c->idx_len = 0; c->have_index = false;
 }
-void free_workspace(fora_ctx *c) {
-    dfree(c->d_residue); dfree(c->d_ppr); dfree(c->d_wl[0]); dfree(c->d_wl[1]); dfree(c->d_scratch);
-    dfree(c->d_counters); dfree(c->d_qs); dfree(c->d_src); dfree(c->d_err);
-    dfree(c->d_ppr2); dfree(c->d_cursor); c->cursor_epoch = 0; dfree(c->d_active); dfree(c->d_above); dfree(c->d_sel_thr); dfree(c->d_topk_ids); dfree(c->d_topk_sc);
-    dfree(c->d_upper); dfree(c->d_lower); dfree(c->d_filter); dfree(c->d_fail); dfree(c->d_round_walks);
-    dfree(c->d_lb_sc); dfree(c->d_lb_ids); c->lb_cap = 0;
-    dfree(c->d_nz_counts);
-    c->topk_cap = 0;
-    dfree(c->d_fl[0]); dfree(c->d_fl[1]); dfree(c->d_fl_count); dfree(c->d_inc_tab[0]); dfree(c->d_inc_tab[1]); dfree(c->d_ov_w); dfree(c->d_ov_inc); dfree(c->d_ov_count); dfree(c->d_ov_bin);
-    dfree(c->d_bk_w); dfree(c->d_bk_inc); dfree(c->d_bk_count); dfree(c->d_wit_count); dfree(c->d_sw); dfree(c->d_tile_ctr);
-    dfree(c->d_dbm); dfree(c->d_dflag); dfree(c->d_dl); dfree(c->d_hubsum);
-    dfree(c->d_team_msg); dfree(c->d_team_inct); dfree(c->d_team_rsvl); dfree(c->d_team_rlog_id); dfree(c->d_team_rlog_val); dfree(c->d_team_cnt); dfree(c->d_team_ctl); c->team_n = 0; c->team_fit = -1;
-    if (c->h_flc) (void)hipHostFree(c->h_flc);
-    c->h_flc = nullptr;
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    c->h_pinned = nullptr;
-    if (c->h_qs_pin) (void)hipHostFree(c->h_qs_pin);
-    c->h_qs_pin = nullptr;
-    if (c->h_steps_pin) (void)hipHostFree(c->h_steps_pin);
-    c->h_steps_pin = nullptr;
-    c->B = 0;
-    c->B_memcap = 0;
-}
+void free_workspace(fora_ctx *c) { c->ws = Workspace{}; } // every buffer freed, every field back at its initialiser
 
 constexpr size_t N_COUNTERS = 2 * (size_t)(MAX_LEVELS + 2) + 2;
 // workgroups per slot of the kernels that sweep a slot's slab (walk allocation, top-k frontier / copy / count): ~32 k
@@ -594,6 +591,18 @@ int ensure_team(fora_ctx *c) {
     return FORA_OK;
 }
 
+// Team push: bytes per team of its workspace buffers with reserve logs of `logcap` entries -- message buffers + increment
+// tables (two parities), rsvl, reserve logs, words
+static uint64_t team_bytes_per_team(const fora_ctx *c, uint64_t logcap) {
+    const uint64_t T = c->team_T;
+    return 2 * c->team_cap * 4 + 3 * T * (c->team_R + 64 + c->team_H) * 8 + T * logcap * 10 + 2 * T * T * 8;
+}
+// Words of Workspace::d_team_ctl: [0] next slot, [32] abort | from `sync`: the sync words | from `slot_seq`: the slot sequences
+struct TeamCtl { size_t sync, slot_seq, total; };
+static TeamCtl team_ctl_layout(uint32_t nteams, int slots) {
+    const size_t sync = 64, slot_seq = sync + (size_t)nteams * 5 * 16 * 2;
+    return {sync, slot_seq, slot_seq + (size_t)nteams * ((size_t)slots + 2)};
+}
 int team_fits(fora_ctx *c);
 int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
@@ -611,17 +620,17 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     // an existing workspace with the same layout is kept if it has enough slots: as many as the call can use, or as
     // many as an automatic plan would get at most (1024)
     auto keepable = [&](int need) {
-        if (c->B <= 0 || c->B < need) return false;
-        const WsPlan pe = plan_workspace(c, omega_hint, c->B);
-        if ((c->team_T != 0) != (c->d_team_msg != nullptr)) return false;
-        return c->binned == pe.binned && c->pbins == pe.pbins && c->seg_cap * sizeof(PushSeg) >= (uint64_t)c->B * pe.scratch &&
+        if (c->ws.B <= 0 || c->ws.B < need) return false;
+        const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B);
+        if ((c->team_T != 0) != bool(c->ws.d_team_msg)) return false;
+        return c->binned == pe.binned && c->pbins == pe.pbins && c->seg_cap * sizeof(PushSeg) >= (uint64_t)c->ws.B * pe.scratch &&
                c->wit_cap >= pe.wits && c->bk_cap == pe.bk_cap && c->sub == pe.sub;
     };
     {
         // slots the call can use: its queries, at most 1024, at most what memory allowed when the workspace was planned
         int need = c->batch_req > 0 ? c->batch_req : std::min(want_slots > 0 ? want_slots : 1024, 1024);
-        if (c->batch_req == 0 && c->B > 0 && c->B_memcap > 0) need = std::min(need, c->B_memcap);
-        if (keepable(need)) { const WsPlan pe = plan_workspace(c, omega_hint, c->B); return ensure_row_split(c, pe.nbins, pe.pbins); }
+        if (c->batch_req == 0 && c->ws.B > 0 && c->ws.B_memcap > 0) need = std::min(need, c->ws.B_memcap);
+        if (keepable(need)) { const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B); return ensure_row_split(c, pe.nbins, pe.pbins); }
     }
     int B = c->batch_req > 0 ? c->batch_req : 0;
     if (B == 0) {
@@ -633,7 +642,7 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         uint64_t budget = (uint64_t)(fr * 0.75);
         if (c->team_T) { // the team push's own buffers (allocated below) come out of the same memory
             const uint64_t T = c->team_T, nt = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
-            const uint64_t team_bytes = nt * (2 * c->team_cap * 4 + 3 * T * (c->team_R + 64 + c->team_H) * 8 + T * (10ull << 17) + 2 * T * T * 8);
+            const uint64_t team_bytes = nt * team_bytes_per_team(c, 1u << 17);
             budget -= std::min<uint64_t>(budget / 2, team_bytes);
         }
         B = (int)std::min<uint64_t>(1024, std::max<uint64_t>(1, budget / p.per_slot)); // ws, 1000 queries: 2845 q/s at 256, 3035 at 512, 3101 at 1000
@@ -645,29 +654,30 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     const uint64_t scratch = (uint64_t)B * p.scratch;
     free_workspace(c);
     const uint64_t slab = (uint64_t)B * n;
-    HIPCHK(c, hipMalloc(&c->d_residue, slab * 8));
-    HIPCHK(c, hipMalloc(&c->d_ppr, slab * 8));
+    const size_t ctr = (size_t)B * CSTRIDE; // one counter line per slot
+    Workspace &w = c->ws;
+    HIPCHK(c, w.d_residue.alloc(slab));
+    HIPCHK(c, w.d_ppr.alloc(slab));
     if (p.binned) {
-        HIPCHK(c, hipMalloc(&c->d_fl[0], slab * 4));
-        HIPCHK(c, hipMalloc(&c->d_fl[1], slab * 4));
-        HIPCHK(c, hipMalloc(&c->d_fl_count, (size_t)B * 2 * 4 * CSTRIDE));
-        HIPCHK(c, hipMalloc(&c->d_inc_tab[0], (uint64_t)B * p.segq_cap * 8));
-        HIPCHK(c, hipMalloc(&c->d_inc_tab[1], (uint64_t)B * p.segq_cap * 8));
+        for (auto &fl : w.d_fl) HIPCHK(c, fl.alloc(slab));
+        HIPCHK(c, w.d_fl_count.alloc(2 * ctr));
+        for (auto &tab : w.d_inc_tab) HIPCHK(c, tab.alloc((uint64_t)B * p.segq_cap));
         c->ov_cap = (uint32_t)std::max<uint64_t>(262144, n / 8); // bucket-overflow list, scales with the graph
         if (c->opt_.ovcap > 0) c->ov_cap = (uint32_t)c->opt_.ovcap; // tests
-        HIPCHK(c, hipMalloc(&c->d_ov_w, (uint64_t)B * c->ov_cap * 4));
-        HIPCHK(c, hipMalloc(&c->d_ov_inc, (uint64_t)B * c->ov_cap * 8));
-        HIPCHK(c, hipMalloc(&c->d_ov_count, 2 * (size_t)B * 4 * CSTRIDE));
-        HIPCHK(c, hipMalloc(&c->d_ov_bin, 2 * (size_t)B * p.nbins * 4));
-        if (!want_wide(c)) HIPCHK(c, hipMalloc(&c->d_bk_w, (uint64_t)B * p.pbins * p.sub * p.bk_cap * 4)); // wide: one 64-bit word per message in bk_inc
-        HIPCHK(c, hipMalloc(&c->d_bk_inc, (uint64_t)B * p.pbins * p.sub * p.bk_cap * 8));
-        HIPCHK(c, hipMalloc(&c->d_bk_count, (size_t)B * p.pbins * p.sub * 4));
-        HIPCHK(c, hipHostMalloc(&c->h_flc, (size_t)FLC_RING * B * 4 * CSTRIDE));
+        HIPCHK(c, w.d_ov_w.alloc((uint64_t)B * c->ov_cap));
+        HIPCHK(c, w.d_ov_inc.alloc((uint64_t)B * c->ov_cap));
+        HIPCHK(c, w.d_ov_count.alloc(2 * ctr));
+        HIPCHK(c, w.d_ov_bin.alloc(2 * (size_t)B * p.nbins));
+        const uint64_t buckets = (uint64_t)B * p.pbins * p.sub;
+        if (!want_wide(c)) HIPCHK(c, w.d_bk_w.alloc(buckets * p.bk_cap)); // wide: one 64-bit word per message in bk_inc
+        HIPCHK(c, w.d_bk_inc.alloc(buckets * p.bk_cap));
+        HIPCHK(c, w.d_bk_count.alloc(buckets));
+        HIPCHK(c, w.h_flc.alloc((size_t)FLC_RING * ctr));
         c->dbm_words = (uint32_t)((uint64_t)p.nbins << (bin_shift(c) - 6));
-        HIPCHK(c, hipMalloc(&c->d_dbm, 2 * (size_t)B * c->dbm_words * 8));
-        HIPCHK(c, hipMalloc(&c->d_dflag, 2 * (size_t)B * p.nbins * 4));
-        if (c->opt_.defer > 0) HIPCHK(c, hipMalloc(&c->d_dl, 2 * slab * 4)); // k_push_tail's deferred lists: only with the option (changing it re-plans the workspace)
-        if (c->hubs && c->hub_shift == bin_shift(c)) HIPCHK(c, hipMalloc(&c->d_hubsum, (size_t)B * p.sub * c->hubs * 8));
+        HIPCHK(c, w.d_dbm.alloc(2 * (size_t)B * c->dbm_words));
+        HIPCHK(c, w.d_dflag.alloc(2 * (size_t)B * p.nbins));
+        if (c->opt_.defer > 0) HIPCHK(c, w.d_dl.alloc(2 * slab)); // k_push_tail's deferred lists: only with the option (changing it re-plans the workspace)
+        if (c->hubs && c->hub_shift == bin_shift(c)) HIPCHK(c, w.d_hubsum.alloc((size_t)B * p.sub * c->hubs));
         if (c->team_T) { // team push: message buffers of every team (two parities), bucket counts, control words
             const uint32_t T = c->team_T;
             uint32_t nteams = std::max<uint32_t>(1, (uint32_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
@@ -676,46 +686,40 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
             HIPCHK(c, hipMemGetInfo(&fr, &tot));
             // pops of one member in one slot (ws-sized graph at eps 0.5: 43 k on average); beyond it: rsvl.  Tight memory: shorter logs
             c->team_rlog_cap = 1u << 17;
-            auto per_team_bytes = [&](uint32_t logcap) { // message buffers + increment tables (two parities), rsvl, reserve logs, words
-                return 2 * c->team_cap * 4 + 3 * (uint64_t)T * (c->team_R + 64 + c->team_H) * 8 + (uint64_t)T * logcap * 10 + 2 * (uint64_t)T * T * 8;
-            };
-            while (c->team_rlog_cap > 1024 && per_team_bytes(c->team_rlog_cap) > fr / 4) c->team_rlog_cap /= 2;
-            const uint64_t per_team = per_team_bytes(c->team_rlog_cap);
-            nteams = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nteams, (uint64_t)(fr / 2) / std::max<uint64_t>(1, per_team)));
-            HIPCHK(c, hipMalloc(&c->d_team_msg, (size_t)nteams * 2 * c->team_cap * 4 + 64 + diag::TEAM_MSG_PROBE_WORDS * 4)); // (probe words: 0 in the product build)
-            HIPCHK(c, hipMalloc(&c->d_team_inct, (size_t)nteams * 2 * T * (c->team_R + 64 + c->team_H) * 8));
-            HIPCHK(c, hipMalloc(&c->d_team_rsvl, (size_t)nteams * T * c->team_R * 8));
-            HIPCHK(c, hipMemset(c->d_team_rsvl, 0, (size_t)nteams * T * c->team_R * 8)); // every slot leaves it zero again
-            HIPCHK(c, hipMalloc(&c->d_team_rlog_id, (size_t)nteams * T * c->team_rlog_cap * 2));
-            HIPCHK(c, hipMalloc(&c->d_team_rlog_val, (size_t)nteams * T * c->team_rlog_cap * 8));
-            HIPCHK(c, hipMalloc(&c->d_team_cnt, (size_t)nteams * 2 * T * T * 8));
-            HIPCHK(c, hipMalloc(&c->d_team_ctl, (64 + (size_t)nteams * 5 * 16 * 2 + (size_t)nteams * ((size_t)B + 2)) * 4));
-            c->team_n = nteams;
+            while (c->team_rlog_cap > 1024 && team_bytes_per_team(c, c->team_rlog_cap) > fr / 4) c->team_rlog_cap /= 2;
+            nteams = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nteams, (uint64_t)(fr / 2) / std::max<uint64_t>(1, team_bytes_per_team(c, c->team_rlog_cap))));
+            const size_t members = (size_t)nteams * T;
+            HIPCHK(c, w.d_team_msg.alloc((size_t)nteams * 2 * c->team_cap + 16 + diag::TEAM_MSG_PROBE_WORDS)); // (probe words: 0 in the product build)
+            HIPCHK(c, w.d_team_inct.alloc(members * 2 * (c->team_R + 64 + c->team_H)));
+            HIPCHK(c, w.d_team_rsvl.alloc(members * c->team_R));
+            HIPCHK(c, w.d_team_rsvl.zero(c->stream)); // every slot leaves it zero again
+            HIPCHK(c, w.d_team_rlog_id.alloc(members * c->team_rlog_cap));
+            HIPCHK(c, w.d_team_rlog_val.alloc(members * c->team_rlog_cap));
+            HIPCHK(c, w.d_team_cnt.alloc(members * 2 * T));
+            HIPCHK(c, w.d_team_ctl.alloc(team_ctl_layout(nteams, B).total));
+            w.team_n = nteams;
             if (int rf = team_fits(c)) return rf;
         }
     } else {
-        HIPCHK(c, hipMalloc(&c->d_wl[0], slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_wl[1], slab * 8));
+        for (auto &wl : w.d_wl) HIPCHK(c, wl.alloc(slab));
     }
-    HIPCHK(c, hipMalloc(&c->d_scratch, scratch));
-    HIPCHK(c, hipMalloc(&c->d_wit_count, (size_t)B * 4 * CSTRIDE));
-    HIPCHK(c, hipMalloc(&c->d_sw, 2 * (size_t)B * 4 * CSTRIDE));
-    HIPCHK(c, hipMemset(c->d_sw, 0, 2 * (size_t)B * 4 * CSTRIDE)); // self-resetting
-    HIPCHK(c, hipMalloc(&c->d_tile_ctr, 2 * (size_t)B * 4 * CSTRIDE));
-    HIPCHK(c, hipMemset(c->d_tile_ctr, 0, 2 * (size_t)B * 4 * CSTRIDE)); // every launch zeroes the set of the next one
-    HIPCHK(c, hipMalloc(&c->d_counters, N_COUNTERS * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc(&c->d_qs, (size_t)B * sizeof(QState)));
-    HIPCHK(c, hipMalloc(&c->d_src, (size_t)B * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc(&c->d_err, sizeof(uint32_t)));
-    HIPCHK(c, hipHostMalloc(&c->h_pinned, (MAX_LEVELS + 2) * sizeof(unsigned long long)));
-    HIPCHK(c, hipHostMalloc(&c->h_qs_pin, (size_t)B * sizeof(QState)));
-    HIPCHK(c, hipHostMalloc(&c->h_steps_pin, sizeof(unsigned long long)));
-    c->B = B;
-    c->B_memcap = memcap;
+    HIPCHK(c, w.d_scratch.alloc(scratch));
+    HIPCHK(c, w.d_wit_count.alloc(ctr));
+    HIPCHK(c, w.d_sw.alloc(2 * ctr));
+    HIPCHK(c, w.d_sw.zero(c->stream)); // self-resetting
+    HIPCHK(c, w.d_tile_ctr.alloc(2 * ctr));
+    HIPCHK(c, w.d_tile_ctr.zero(c->stream)); // every launch zeroes the set of the next one
+    HIPCHK(c, w.d_counters.alloc(N_COUNTERS));
+    HIPCHK(c, w.d_qs.alloc((size_t)B));
+    HIPCHK(c, w.d_src.alloc((size_t)B));
+    HIPCHK(c, w.d_err.alloc(1));
+    HIPCHK(c, w.h_pinned.alloc(MAX_LEVELS + 2));
+    HIPCHK(c, w.h_qs_pin.alloc((size_t)B));
+    HIPCHK(c, w.h_steps_pin.alloc(1));
+    w.B = B; w.B_memcap = memcap;
     c->binned = p.binned; c->nbins = p.nbins; c->pbins = p.pbins; c->bk_cap = p.bk_cap; c->sub = p.sub; c->segq_cap = p.segq_cap;
     if (int rs = ensure_row_split(c, p.nbins, p.pbins)) return rs;
-    c->wl_cap = slab;
-    c->seg_cap = scratch / sizeof(PushSeg);
+    c->wl_cap = slab; c->seg_cap = scratch / sizeof(PushSeg);
     c->wit_cap = p.wits; // per slot
     c->h_qs.resize(B);
     return FORA_OK;
@@ -725,20 +729,21 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     if (rmax < 0) rmax = c->rmax;
     if (omega < 0) omega = c->omega;
     Dev d{};
+    const Workspace &w = c->ws;
+    const size_t B = (size_t)w.B, ctr = B * CSTRIDE;
     d.n = c->n; d.nq = nq;
     d.rowinfo = c->d_rowinfo; d.row_ptr = c->d_row_ptr; d.col = c->d_col; d.deg = c->d_deg;
     d.rp32 = c->d_rp32; d.colp = c->d_colp; d.colbits = c->colbits;
     d.colp32 = (uint64_t)c->nnz * c->colbits < (1ull << 32) ? 1 : 0;
     d.dg = c->dg;
-    d.residue = c->d_residue; d.ppr = c->d_ppr;
-    d.wl[0] = c->d_wl[0]; d.wl[1] = c->d_wl[1]; d.wl_cap = c->wl_cap;
-    d.seg = (PushSeg *)c->d_scratch; d.seg_cap = c->seg_cap;
-    d.wit = (WalkItemP *)c->d_scratch; d.wit_cap = c->wit_cap;
-    d.wl_count = c->d_counters;
-    d.seg_count = c->d_counters + (MAX_LEVELS + 2);
-    d.wit_count = c->d_wit_count;
-    d.tot_steps = c->d_counters + 2 * (size_t)(MAX_LEVELS + 2) + 1;
-    d.qs = c->d_qs; d.src = c->d_src; d.err = c->d_err;
+    d.residue = w.d_residue.get(); d.ppr = w.d_ppr.get(); d.wl_cap = c->wl_cap;
+    d.seg = (PushSeg *)w.d_scratch.get(); d.seg_cap = c->seg_cap;
+    d.wit = (WalkItemP *)w.d_scratch.get(); d.wit_cap = c->wit_cap;
+    d.wl_count = w.d_counters.get();
+    d.seg_count = w.d_counters.get() + (MAX_LEVELS + 2);
+    d.wit_count = w.d_wit_count.get();
+    d.tot_steps = w.d_counters.get() + 2 * (size_t)(MAX_LEVELS + 2) + 1;
+    d.qs = w.d_qs.get(); d.src = w.d_src.get(); d.err = w.d_err.get();
     d.afix = (uint64_t)std::ldexp(c->alpha, 62);
     double t = std::ceil(std::ldexp(rmax, 62));
     d.t1 = t >= 9223372036854775808.0 ? (~0ull >> 1) : (t < 1.0 ? 1 : (uint64_t)t);
@@ -759,15 +764,20 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     d.slot_major = c->opt_.slot_major >= 0 ? (uint32_t)c->opt_.slot_major & 15u
                    : (c->bk_div > 1 ? 0u : (4u | (nq >= 32 ? 1u : 0u)));
     d.tiny_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.tiny, 0), 1023); // 512: ws accum 116 -> 113 ms per 3000 queries against 128; 2048: 119, 8192: 193 (the crossing list of the small-bucket path holds 1024)
-    d.fl[0] = c->d_fl[0]; d.fl[1] = c->d_fl[1];
-    d.fl_count[0] = c->d_fl_count; d.fl_count[1] = c->d_fl_count ? c->d_fl_count + (size_t)c->B * CSTRIDE : nullptr;
-    d.inc_tab[0] = c->d_inc_tab[0]; d.inc_tab[1] = c->d_inc_tab[1]; d.segq_cap = c->segq_cap;
+    for (int par = 0; par < 2; par++) { // the two parity sets of a pair are the halves of one buffer (null while it is empty)
+        d.fl[par] = w.d_fl[par].get(); d.inc_tab[par] = w.d_inc_tab[par].get();
+        d.fl_count[par] = w.d_fl_count.part(par, ctr); d.tile_ctr[par] = w.d_tile_ctr.part(par, ctr);
+        d.ov_count[par] = w.d_ov_count.part(par, ctr); d.ov_bin[par] = w.d_ov_bin.part(par, B * c->nbins);
+        d.dbm[par] = w.d_dbm.part(par, B * c->dbm_words); d.dflag[par] = w.d_dflag.part(par, B * c->nbins);
+        d.dl[par] = w.d_dl.part(par, B * c->n); d.wl[par] = w.d_wl[par].get();
+    }
+    d.sw_count = w.d_sw.part(0, ctr); d.sw_done = w.d_sw.part(1, ctr);
     d.pop_next = 1;
     d.stamps = c->d_stamps;
     d.round_div = 0;
     d.rounds = 1; // the query / push entry points raise it (k_round_sweep); top-k, --balanced and power iteration drive their own rounds
-    if (c->binned && c->d_col_hub && c->d_hubsum && c->hub_shift == bin_shift(c) && c->pbins >= c->nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
-        d.col_hub = c->d_col_hub; d.hub_node = c->d_hub_node; d.hub_first = c->d_hub_first; d.hubsum = c->d_hubsum; d.hubs = c->hubs;
+    if (c->binned && c->d_col_hub && w.d_hubsum && c->hub_shift == bin_shift(c) && c->pbins >= c->nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
+        d.col_hub = c->d_col_hub; d.hub_node = c->d_hub_node; d.hub_first = c->d_hub_first; d.hubsum = w.d_hubsum.get(); d.hubs = c->hubs;
         d.hub_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.hub_min, 1), 0x7FFFFFFF);
         d.tail_hubs = c->opt_.tail_hubs != 0 && (size_t)c->hubs * 8 <= 40960 ? 1u : 0u; // (k_push_tail: 20 KiB of static LDS + the sums within 64 KiB)
     }
@@ -776,17 +786,11 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
         d.col_hub4 = d.col_hub ? c->d_col_hub4 : nullptr;
         if (d.col_hub && !d.col_hub4) d.col4 = nullptr; // (no padded hub copy: edges one by one)
     }
-    d.defer_k = TEST_PATHS && c->binned && c->d_dl ? (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer, 0), 8) : 0; // the direct path keeps plain levels
+    d.defer_k = TEST_PATHS && c->binned && w.d_dl ? (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer, 0), 8) : 0; // the direct path keeps plain levels
     d.defer_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer_min, 0), 0x7FFFFFFF);
-    d.dbm[0] = c->d_dbm; d.dbm[1] = c->d_dbm ? c->d_dbm + (size_t)c->B * c->dbm_words : nullptr; d.dbm_words = c->dbm_words;
-    d.dflag[0] = c->d_dflag; d.dflag[1] = c->d_dflag ? c->d_dflag + (size_t)c->B * c->nbins : nullptr;
-    d.dl[0] = c->d_dl; d.dl[1] = c->d_dl ? c->d_dl + (size_t)c->B * c->n : nullptr;
-    d.sw_count = c->d_sw; d.sw_done = c->d_sw ? c->d_sw + (size_t)c->B * CSTRIDE : nullptr;
-    d.tile_ctr[0] = c->d_tile_ctr; d.tile_ctr[1] = c->d_tile_ctr ? c->d_tile_ctr + (size_t)c->B * CSTRIDE : nullptr;
-    d.ov_w = c->d_ov_w; d.ov_inc = c->d_ov_inc; d.ov_cap = c->ov_cap;
-    d.ov_count[0] = c->d_ov_count; d.ov_count[1] = c->d_ov_count ? c->d_ov_count + (size_t)c->B * CSTRIDE : nullptr;
-    d.ov_bin[0] = c->d_ov_bin; d.ov_bin[1] = c->d_ov_bin ? c->d_ov_bin + (size_t)c->B * c->nbins : nullptr;
-    d.bk_w = c->d_bk_w; d.bk_inc = c->d_bk_inc; d.bk_count = c->d_bk_count; d.bk_cap = c->bk_cap; d.sub = c->sub;
+    d.dbm_words = c->dbm_words; d.segq_cap = c->segq_cap;
+    d.ov_w = w.d_ov_w.get(); d.ov_inc = w.d_ov_inc.get(); d.ov_cap = c->ov_cap;
+    d.bk_w = w.d_bk_w.get(); d.bk_inc = w.d_bk_inc.get(); d.bk_count = w.d_bk_count.get(); d.bk_cap = c->bk_cap; d.sub = c->sub;
     if (with_idx) { d.rw_idx = c->d_rw_idx; d.idx_off = c->d_idx_off; d.idx_cnt = c->d_idx_cnt; }
     return d;
 }
@@ -833,7 +837,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
 
 int check_dev_err(fora_ctx *c) {
     uint32_t e = 0;
-    HIPCHK(c, hipMemcpyAsync(&e, c->d_err, sizeof(e), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&e, c->ws.d_err.get(), sizeof(e), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->bucket_overflow = (e & ERR_BUCKET_OVERFLOW) != 0;
     c->team_timeout_seen = (e & ERR_TEAM_TIMEOUT) != 0;
@@ -872,13 +876,9 @@ int check_k(fora_ctx *c, int k) {
 bool is_dangling(const fora_ctx *c, int32_t s) { return c->h_row_ptr[(size_t)s + 1] == c->h_row_ptr[(size_t)s]; }
 
 // a device (ids, scores) pair of B * k entries, grown on demand
-int grow_pair(fora_ctx *c, int k, int32_t *&ids, double *&scores, int &cap) {
-    if (cap >= c->B * k) return FORA_OK;
-    dfree(ids); dfree(scores);
-    cap = 0;
-    HIPCHK(c, hipMalloc(&ids, (size_t)c->B * k * 4));
-    HIPCHK(c, hipMalloc(&scores, (size_t)c->B * k * 8));
-    cap = c->B * k;
+int grow_pair(fora_ctx *c, int k, DevBuf<int32_t> &ids, DevBuf<double> &scores) {
+    HIPCHK(c, ids.ensure((size_t)c->ws.B * k));
+    HIPCHK(c, scores.ensure((size_t)c->ws.B * k));
     return FORA_OK;
 }
 
@@ -898,13 +898,13 @@ int copy_slab_out(fora_ctx *c, const uint64_t *slab, uint64_t slot, uint64_t row
     return FORA_OK;
 }
 
-// The top k of slots [0, nb) (c->d_topk_ids / d_topk_sc) into the caller's ids / scores (either may be null): slot i to row
+// The top k of slots [0, nb) (Workspace::d_topk_ids / d_topk_sc) into the caller's ids / scores (either may be null): slot i to row
 // rows[i], or to row row0 + i without rows; the scores times `scale`.
 int copy_topk_out(fora_ctx *c, int nb, int k, int32_t *ids, double *scores, uint64_t row0, const int *rows = nullptr, double scale = 1.0) {
     std::vector<int32_t> hid(ids ? (size_t)nb * k : 0);
     std::vector<double> hsc(scores ? (size_t)nb * k : 0);
-    if (ids) HIPCHK(c, hipMemcpyAsync(hid.data(), c->d_topk_ids, hid.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    if (scores) HIPCHK(c, hipMemcpyAsync(hsc.data(), c->d_topk_sc, hsc.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ids) HIPCHK(c, hipMemcpyAsync(hid.data(), c->ws.d_topk_ids.get(), hid.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    if (scores) HIPCHK(c, hipMemcpyAsync(hsc.data(), c->ws.d_topk_sc.get(), hsc.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the ctx stream does not synchronise with the null stream)
     for (int i = 0; i < nb; i++) {
         const uint64_t at = (rows ? (uint64_t)rows[i] : row0 + (uint64_t)i) * (uint64_t)k;
@@ -938,6 +938,16 @@ void fold_counters(fora_ctx *c, const QState *qs, int nb) {
 // Level loop of the push for the slots already initialised (level-0 frontier in place).
 // Launches run ahead of the host by SPEC levels: an empty level costs a few near-empty
 // launches, a host round trip per level would cost more.
+// Frontier size (largest slot) from which k_push_tail takes over; 0: never.  ws, push of 1000 queries (round 2's
+// tail kernel: no agent-scope fences, 4 relaxations in flight per lane): 1024: 86.3 ms, 4096: 85.2, 16384: 82.5,
+// 32768: 81.9, 131072: 163 (one workgroup per slot cannot feed the peak levels)
+// The tail runs one workgroup per slot, so it only pays while the slots alone fill the chip: with the 14 slots of a
+// Twitter-2010-sized batch 32768 -> 2048 takes the tail from 128 ms to 11 ms per 28 queries (15.05 -> 15.81 q/s);
+// LJ-sized, 140 slots: 32768 -> 4096 takes it from 16.8 to 2.2 ms per 280 queries (the bucketed levels it
+// replaces cost less).  Default: 32 x the slot count, between 2048 and 32768.
+static uint32_t tail_max_of(const fora_ctx *c, int nq) {
+    return (uint32_t)(c->opt_.tail < 0 ? std::min<int64_t>(32768, std::max<int64_t>(2048, (int64_t)nq * 32)) : c->opt_.tail);
+}
 static inline size_t tail_lds(const Dev &d) { return d.tail_hubs && d.col_hub ? (size_t)d.hubs * 8 : 0; } // k_push_tail's dynamic LDS
 
 // Wide accumulate: bins per workgroup (Dev::acc_group) and the grid's x size.  One bin per workgroup for query / power-iteration
@@ -955,14 +965,13 @@ static unsigned acc_grid(const fora_ctx *c, Dev &dp, int nq) {
 }
 int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, int level_cap = 0, bool round_start = false) {
     const int nq = d.nq;
+    const uint32_t tail_max = tail_max_of(c, nq);
     if (round_start && c->binned && level_cap <= 0 && d.rounds <= 1 && c->opt_.tail != 0) {
         // A round of the top-k / --balanced drivers starts from every node at or over the round's threshold
         // (k_topk_frontier), often a handful: when no slot's frontier is larger than what k_push_tail takes over at anyway,
         // the whole round runs inside that kernel -- one launch instead of two per level plus the look-ahead levels
         // (Twitter-2010-sized top-k: 391 level launches of mostly empty workgroups per 125 queries).
-        const int64_t tail_auto = std::min<int64_t>(32768, std::max<int64_t>(2048, (int64_t)nq * 32));
-        const uint32_t tail_max = (uint32_t)(c->opt_.tail < 0 ? tail_auto : c->opt_.tail);
-        uint32_t *cnt = c->h_flc;
+        uint32_t *cnt = c->ws.h_flc.get();
         HIPCHK(c, hipMemcpyAsync(cnt, d.fl_count[0], (size_t)nq * 4 * CSTRIDE, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         uint32_t fmax = 0;
@@ -986,15 +995,6 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
     int rc = FORA_OK;
     int L = 0;
     const unsigned xb = c->binned ? c->sub : 1u; // producer workgroups per slot = sub-buckets per bucket (Dev::bk_w); ws at 1000 slots: 4 -> 196 ms, 8 -> 178, 16 -> 163, 32 -> 174
-    // frontier size (largest slot) from which k_push_tail takes over; 0: never.  ws, push of 1000 queries (round 2's
-    // tail kernel: no agent-scope fences, 4 relaxations in flight per lane): 1024: 86.3 ms, 4096: 85.2, 16384: 82.5,
-    // 32768: 81.9, 131072: 163 (one workgroup per slot cannot feed the peak levels)
-    // The tail runs one workgroup per slot, so it only pays while the slots alone fill the chip: with the 14 slots of a
-    // Twitter-2010-sized batch 32768 -> 2048 takes the tail from 128 ms to 11 ms per 28 queries (15.05 -> 15.81 q/s);
-    // LJ-sized, 140 slots: 32768 -> 4096 takes it from 16.8 to 2.2 ms per 280 queries (the bucketed levels it
-    // replaces cost less).  Default: 32 x the slot count, between 2048 and 32768.
-    const int64_t tail_auto = std::min<int64_t>(32768, std::max<int64_t>(2048, (int64_t)nq * 32));
-    const uint32_t tail_max = (uint32_t)(c->opt_.tail < 0 ? tail_auto : c->opt_.tail);
     bool past_peak = c->opt_.tail_always == 1; // tests: do not wait for the frontier to have been large first
     for (;; L++) {
         if (level_cap > 0 && L >= level_cap) break; // power iteration: a fixed number of levels
@@ -1048,7 +1048,7 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
                 ev_end(c, h);
 #endif
             }
-            (void)hipMemcpyAsync(c->h_flc + (size_t)((L + 1) % FLC_RING) * c->B * CSTRIDE, d.fl_count[(L + 1) & 1],
+            (void)hipMemcpyAsync(c->ws.h_flc.get() + (size_t)((L + 1) % FLC_RING) * c->ws.B * CSTRIDE, d.fl_count[(L + 1) & 1],
                                  (size_t)nq * 4 * CSTRIDE, hipMemcpyDeviceToHost, c->stream);
         } else {
             int h = ev_begin(c, 0);
@@ -1057,7 +1057,7 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
             h = ev_begin(c, 1);
             hipLaunchKernelGGL(k_push_expand, dim3(c->grid_blocks), dim3(BLOCK), 0, c->stream, d, L);
             ev_end(c, h);
-            (void)hipMemcpyAsync(&c->h_pinned[L + 1], &d.wl_count[L + 1], sizeof(unsigned long long),
+            (void)hipMemcpyAsync(c->ws.h_pinned.get() + L + 1, &d.wl_count[L + 1], sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost, c->stream);
         }
         c->timing.levels++;
@@ -1069,7 +1069,7 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
             uint32_t fmax = 0;
             if (c->binned) {
                 empty = true;
-                const uint32_t *cnt = c->h_flc + (size_t)((K + 1) % FLC_RING) * c->B * CSTRIDE;
+                const uint32_t *cnt = c->ws.h_flc.get() + (size_t)((K + 1) % FLC_RING) * c->ws.B * CSTRIDE;
                 uint32_t rounds_left = 0; // word 1 of a slot's counter line: threshold rounds still to come (k_round_sweep)
                 for (int i = 0; i < nq; i++) { // word 2: nodes the level deferred (they are part of the work that is left)
                     fmax = std::max(fmax, cnt[(size_t)i * CSTRIDE] + cnt[(size_t)i * CSTRIDE + 2]);
@@ -1078,7 +1078,7 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
                 empty = fmax == 0 && rounds_left == 0;
                 if (rounds_left) fmax = std::max(fmax, tail_max + 1); // k_push_tail knows the final threshold only
             } else {
-                empty = c->h_pinned[K + 1] == 0;
+                empty = c->ws.h_pinned.get()[K + 1] == 0;
             }
             if (fmax > tail_max) past_peak = true; // the first levels are small too, but growing
             if (!empty && c->binned && tail_max > 0 && past_peak && fmax <= tail_max) {
@@ -1113,37 +1113,37 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
 // resident in LDS, k_push_tail finishes the slots.  Nothing here waits for the device.
 static bool use_team(const fora_ctx *c, const Dev &d) {
     // not after a time-out
-    return c->team_T && c->d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
-           c->team_fit != 0 && c->team_suspend == 0;
+    return c->team_T && c->ws.d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
+           c->ws.team_fit != 0 && c->team_suspend == 0;
 }
 // Can every workgroup of a k_push_team launch be resident at once?  (Asked once per workspace; raises the kernel's
 // dynamic LDS limit on the way.)
 int team_fits(fora_ctx *c) {
-    if (c->team_fit >= 0 || !c->team_T || !c->d_team_msg) return FORA_OK;
+    if (c->ws.team_fit >= 0 || !c->team_T || !c->ws.d_team_msg) return FORA_OK;
     const size_t lds = ((size_t)c->team_R + 1 + c->team_H) * 8;
     hipFuncAttributes fa{};
     HIPCHK(c, hipFuncGetAttributes(&fa, (const void *)k_push_team));
     HIPCHK(c, hipFuncSetAttribute((const void *)k_push_team, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(163840 - (int)fa.sharedSizeBytes)));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_push_team, TEAM_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-    const uint32_t grid = c->team_n * c->team_T;
-    c->team_fit = (uint64_t)per_cu * (uint64_t)c->prop.multiProcessorCount >= grid ? 1 : 0;
+    const uint32_t grid = c->ws.team_n * c->team_T;
+    c->ws.team_fit = (uint64_t)per_cu * (uint64_t)c->prop.multiProcessorCount >= grid ? 1 : 0;
     int coop = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) != hipSuccess) { (void)hipGetLastError(); coop = 0; }
     c->team_coop_ok = c->opt_.team_coop == 1 && coop != 0;
     return FORA_OK;
 }
 int run_push_team(fora_ctx *c, const Dev &d) {
-    const uint32_t T = c->team_T, nteams = c->team_n;
+    const uint32_t T = c->team_T, nteams = c->ws.team_n;
     TeamDev a{};
     a.n = d.n; a.nq = d.nq; a.rowinfo = d.rowinfo; a.row_ptr = d.row_ptr; a.deg = d.deg; a.src = d.src;
     a.residue = d.residue; a.ppr = d.ppr; a.fl0 = d.fl[0]; a.fl_count0 = d.fl_count[0]; a.inc_tab0 = d.inc_tab[0];
     a.segq_cap = d.segq_cap; a.qs = d.qs; a.err = d.err; a.afix = d.afix; a.t1 = d.t1;
     a.T = T; a.R = c->team_R; a.nteams = nteams;
-    a.colt = c->d_colt; a.rowq = c->d_team_rowq; a.n2l = c->d_team_n2l; a.l2n = c->d_team_l2n; a.deg16 = c->d_team_deg16; a.rowl = c->d_team_rowl; a.rsvl = c->d_team_rsvl; a.rlog_id = c->d_team_rlog_id; a.rlog_val = c->d_team_rlog_val; a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->team_rlog_cap) : c->team_rlog_cap; a.H = c->team_H; a.hubtgt = c->d_team_hubtgt; a.off = c->d_team_off; a.msg = c->d_team_msg; a.inct = c->d_team_inct; a.cntw = c->d_team_cnt;
-    a.ctl = c->d_team_ctl;
-    a.sync = (unsigned long long *)(c->d_team_ctl + 64);
-    a.slot_seq = c->d_team_ctl + 64 + (size_t)nteams * 5 * 16 * 2;
+    a.colt = c->d_colt; a.rowq = c->d_team_rowq; a.n2l = c->d_team_n2l; a.l2n = c->d_team_l2n; a.deg16 = c->d_team_deg16; a.rowl = c->d_team_rowl; a.rsvl = c->ws.d_team_rsvl.get(); a.rlog_id = c->ws.d_team_rlog_id.get(); a.rlog_val = c->ws.d_team_rlog_val.get(); a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->team_rlog_cap) : c->team_rlog_cap; a.H = c->team_H; a.hubtgt = c->d_team_hubtgt; a.off = c->d_team_off; a.msg = c->ws.d_team_msg.get(); a.inct = c->ws.d_team_inct.get(); a.cntw = c->ws.d_team_cnt.get();
+    const Workspace &w = c->ws;
+    const TeamCtl ctl = team_ctl_layout(nteams, w.B);
+    a.ctl = w.d_team_ctl.get(); a.sync = (unsigned long long *)(a.ctl + ctl.sync); a.slot_seq = a.ctl + ctl.slot_seq;
     // frontier size of a slot at which k_push_tail (one workgroup per slot, global atomics) takes over; 0: never
     const int64_t tail_auto = 4096;
     a.tail_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_tail < 0 ? tail_auto : c->opt_.team_tail, 0), 0x7FFFFFFF);
@@ -1155,10 +1155,10 @@ int run_push_team(fora_ctx *c, const Dev &d) {
     a.abort_level = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_abort_level, 0), 1 << 20);
     a.timeout_ticks = (uint64_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_timeout_ms, 0), 60000) * 100000ull; // (100 MHz wall clock)
     const size_t lds = ((size_t)a.R + 1 + a.H) * 8;
-    if (c->team_dirty) { HIPCHK(c, hipMemsetAsync(c->d_team_rsvl, 0, (size_t)nteams * T * c->team_R * 8, c->stream)); c->team_dirty = false; }
-    HIPCHK(c, hipMemsetAsync(c->d_team_ctl, 0, (64 + (size_t)nteams * 5 * 16 * 2) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_team_cnt, 0, (size_t)nteams * 2 * T * T * 8, c->stream)); // no barrier tag of an earlier launch
-    HIPCHK(c, hipMemsetAsync(a.slot_seq, 0xFF, (size_t)nteams * ((size_t)d.nq + 2) * 4, c->stream));
+    if (c->team_dirty) { HIPCHK(c, w.d_team_rsvl.zero(c->stream)); c->team_dirty = false; }
+    HIPCHK(c, w.d_team_ctl.zero(c->stream, ctl.slot_seq)); // the words before the slot sequences
+    HIPCHK(c, w.d_team_cnt.zero(c->stream)); // no barrier tag of an earlier launch
+    HIPCHK(c, w.d_team_ctl.fill(c->stream, 0xFF, ctl.slot_seq, (size_t)nteams * ((size_t)d.nq + 2)));
     int h = ev_begin(c, 10);
     // The members of a team spin on each other: every workgroup of the launch must be resident at once.  team_fits() has
     // checked that the grid fits the device; a cooperative launch makes the runtime promise it (and keeps cooperative
@@ -1196,49 +1196,50 @@ int launch_select(fora_ctx *c, const Dev &ds, int nb, int k, int32_t *ids, doubl
                            (const uint32_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr);
         return FORA_OK;
     }
-    if (!c->d_nz_counts) HIPCHK(c, hipMalloc(&c->d_nz_counts, (size_t)c->B * (NZ_X + 1) * 4));
+    HIPCHK(c, c->ws.d_nz_counts.ensure((size_t)c->ws.B * (NZ_X + 1)));
     const unsigned X = (unsigned)std::min<uint64_t>(NZ_X, ((uint64_t)c->n + 4095) / 4096);
     const uint32_t R = (uint32_t)(((uint64_t)c->n + X - 1) / X);
-    uint32_t *ccount = c->d_nz_counts + (size_t)c->B * NZ_X;
+    uint32_t *ccount = c->ws.d_nz_counts.get() + (size_t)c->ws.B * NZ_X;
     const double *thr = nullptr; // per-slot lower limit of the entries worth compacting (see k_nz_count)
     if (h_thr && !raw) {
-        if (!c->d_sel_thr) HIPCHK(c, hipMalloc(&c->d_sel_thr, (size_t)c->B * sizeof(double)));
-        HIPCHK(c, hipMemcpyAsync(c->d_sel_thr, h_thr, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, c->ws.d_sel_thr.ensure((size_t)c->ws.B));
+        HIPCHK(c, hipMemcpyAsync(c->ws.d_sel_thr.get(), h_thr, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream)); // h_thr is the caller's pageable buffer
-        thr = c->d_sel_thr;
+        thr = c->ws.d_sel_thr.get();
     }
-    hipLaunchKernelGGL(k_nz_count, dim3(X, nb), dim3(BLOCK), 0, c->stream, ds, R, c->d_nz_counts, thr);
-    hipLaunchKernelGGL(k_nz_write, dim3(X, nb), dim3(BLOCK), 0, c->stream, ds, R, (const uint32_t *)c->d_nz_counts, c->d_fl[0],
-                       c->d_inc_tab[0], ccount, thr);
+    hipLaunchKernelGGL(k_nz_count, dim3(X, nb), dim3(BLOCK), 0, c->stream, ds, R, c->ws.d_nz_counts.get(), thr);
+    hipLaunchKernelGGL(k_nz_write, dim3(X, nb), dim3(BLOCK), 0, c->stream, ds, R, (const uint32_t *)c->ws.d_nz_counts.get(), c->ws.d_fl[0].get(),
+                       c->ws.d_inc_tab[0].get(), ccount, thr);
     hipLaunchKernelGGL(k_topk_select, dim3(nb), dim3(SEL_THREADS), 0, c->stream, ds, k, ids, scores, raw,
-                       (const uint32_t *)c->d_fl[0], (const uint64_t *)c->d_inc_tab[0], (const uint32_t *)ccount);
+                       (const uint32_t *)c->ws.d_fl[0].get(), (const uint64_t *)c->ws.d_inc_tab[0].get(), (const uint32_t *)ccount);
     return FORA_OK;
 }
 
 // per-level bookkeeping of the bucketed push that must start from zero
 int reset_binned_counters(fora_ctx *c) {
     if (!c->binned) return FORA_OK;
-    HIPCHK(c, hipMemsetAsync(c->d_fl_count, 0, (size_t)c->B * 2 * 4 * CSTRIDE, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_bk_count, 0, (size_t)c->B * c->pbins * c->sub * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_ov_count, 0, 2 * (size_t)c->B * 4 * CSTRIDE, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_ov_bin, 0, 2 * (size_t)c->B * c->nbins * 4, c->stream));
+    const Workspace &w = c->ws;
+    HIPCHK(c, w.d_fl_count.zero(c->stream));
+    HIPCHK(c, w.d_bk_count.zero(c->stream));
+    HIPCHK(c, w.d_ov_count.zero(c->stream));
+    HIPCHK(c, w.d_ov_bin.zero(c->stream));
     if (TEST_PATHS) { // bounded deferral's bitmaps and flags (test library only; 385 MB per top-k round at Twitter-2010 size)
-        HIPCHK(c, hipMemsetAsync(c->d_dbm, 0, 2 * (size_t)c->B * c->dbm_words * 8, c->stream)); // (a complete push leaves them clear; an aborted one may not)
-        HIPCHK(c, hipMemsetAsync(c->d_dflag, 0, 2 * (size_t)c->B * c->nbins * 4, c->stream));
+        HIPCHK(c, w.d_dbm.zero(c->stream)); // (a complete push leaves them clear; an aborted one may not)
+        HIPCHK(c, w.d_dflag.zero(c->stream));
     }
-    HIPCHK(c, hipMemsetAsync(c->d_tile_ctr, 0, 2 * (size_t)c->B * 4 * CSTRIDE, c->stream)); // both parity sets, every slot: a launch only re-zeroes the slots it runs
+    HIPCHK(c, w.d_tile_ctr.zero(c->stream)); // both parity sets, every slot: a launch only re-zeroes the slots it runs
     return FORA_OK;
 }
 
 int reset_batch_state(fora_ctx *c, int nq, const int32_t *sources) {
-    const uint64_t bytes = (uint64_t)nq * c->n * 8;
+    const uint64_t slabs = (uint64_t)nq * c->n; // the slabs of the batch's slots only
     int h = ev_begin(c, 4);
-    HIPCHK(c, hipMemsetAsync(c->d_residue, 0, bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_ppr, 0, bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_src, sources, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->ws.d_residue.zero(c->stream, slabs));
+    HIPCHK(c, c->ws.d_ppr.zero(c->stream, slabs));
+    HIPCHK(c, c->ws.d_counters.zero(c->stream));
+    HIPCHK(c, c->ws.d_err.zero(c->stream));
+    HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ws.d_src.get(), sources, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     int rc = reset_binned_counters(c);
     ev_end(c, h);
     return rc;
@@ -1328,7 +1329,7 @@ int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done
 int sparse_count(fora_ctx *c, const SparseRun &sp, int nb) {
     HIPCHK(c, hipMemsetAsync(c->d_sp_tot, 0, (size_t)nb * 4, c->stream));
     const int h = ev_begin(c, 13);
-    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, (uint32_t)c->n, sp.thr, sp.R,
+    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->n, sp.thr, sp.R,
                        c->d_sp_counts, c->d_sp_tot);
     ev_end(c, h);
     HIPCHK(c, hipMemcpyAsync(c->h_sp_tot, c->d_sp_tot, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1363,7 +1364,7 @@ int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, con
     HIPCHK(c, hipMemcpyAsync(c->d_sp_base + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
     const int h = ev_begin(c, 13);
-    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, (uint32_t)c->n, sp.thr, sp.R,
+    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->n, sp.thr, sp.R,
                        (const uint32_t *)c->d_sp_counts, (const int64_t *)(c->d_sp_base + sp.live_done), c->d_sp_ids, c->d_sp_fix, c->sp_cap);
     ev_end(c, h);
     sp.live_done += nb;
@@ -1375,15 +1376,15 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, in
     sparse_skip_dangling(sp, sources, nq);
     sp.row_ptr[(size_t)nq] = (int64_t)sp.cur;
     if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? sp.cur : 0, (uint64_t)nq, (uint64_t)nq)) return rc; // (only grows when dangling rows came last)
-    DevTmp at, src;
+    DevBuf<int64_t> at; DevBuf<int32_t> src; // (freed on every return path)
     const size_t nd = sp.dang_at.size();
     if (nd) {
-        HIPCHK(c, hipMalloc(&at.p, nd * 8));
-        HIPCHK(c, hipMalloc(&src.p, nd * 4));
-        HIPCHK(c, hipMemcpyAsync(at.p, sp.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(src.p, sp.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, at.alloc(nd));
+        HIPCHK(c, src.alloc(nd));
+        HIPCHK(c, hipMemcpyAsync(at.get(), sp.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(src.get(), sp.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_sparse_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd,
-                           (const int64_t *)at.p, (const int32_t *)src.p, c->d_sp_ids, c->d_sp_fix, c->sp_cap);
+                           (const int64_t *)at.get(), (const int32_t *)src.get(), c->d_sp_ids, c->d_sp_fix, c->sp_cap);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const hipError_t e = hipGetLastError();
@@ -1455,11 +1456,12 @@ void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t rou
     }
 }
 
+static hipError_t ensure_active(Workspace &w) { return w.d_active.ensure((size_t)w.B); } // marks of the slots that run a round: --balanced and the top-k drivers
 // --balanced push of a batch (query.h:848-884): rounds of the incremental push (algo.h:1020-1093) with rmax halving
 // from 8*config.rmax; a slot keeps going while its estimated walk cost exceeds what its push has cost so far.
 int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
-    if (!c->d_active) HIPCHK(c, hipMalloc(&c->d_active, (size_t)c->B));
-    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->B));
+    HIPCHK(c, ensure_active(c->ws));
+    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
     Dev d = make_dev(c, nq, with_idx);
     int h = ev_begin(c, 4);
     hipLaunchKernelGGL(k_init_batch, dim3((nq + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 1);
@@ -1484,19 +1486,19 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
         }
         if (!any) break;
         if (round >= 64) return fail(c, FORA_E_OVERFLOW, "--balanced: rmax halved 64 times");
-        HIPCHK(c, hipMemcpyAsync(c->d_active, active.data(), (size_t)nq, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ws.d_active.get(), active.data(), (size_t)nq, hipMemcpyHostToDevice, c->stream));
         if (round) {
-            HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
+            HIPCHK(c, c->ws.d_counters.zero(c->stream));
             int rc = reset_binned_counters(c);
             if (rc) return rc;
         }
         Dev dr = make_dev(c, nq, with_idx, rmax, c->omega);
         h = ev_begin(c, 4);
-        hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, dr, (const uint8_t *)c->d_active);
+        hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, dr, (const uint8_t *)c->ws.d_active.get());
         ev_end(c, h);
         int rc = run_push_levels(c, dr, nullptr, 0, true);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpy(c->h_qs.data(), c->d_qs, (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->h_qs.data(), c->ws.d_qs.get(), (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost));
         for (int i = 0; i < nq; i++) {
             rsum_fix[i] = FIX_ONE - c->h_qs[i].reserved;
             pops[i] = c->h_qs[i].pops;
@@ -1543,11 +1545,11 @@ int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, 
         ev_end(c, h);
     }
     if (sp) if ((rc = sparse_count(c, *sp, nq))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ws.h_qs_pin.get(), c->ws.d_qs.get(), (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if ((rc = close_batch(c, hb, "batch"))) return rc;
-    for (int i = 0; i < nq; i++) c->h_qs[i] = c->h_qs_pin[i];
-    c->timing.walk_steps += *c->h_steps_pin;
+    for (int i = 0; i < nq; i++) c->h_qs[i] = c->ws.h_qs_pin.get()[i];
+    c->timing.walk_steps += *c->ws.h_steps_pin.get();
     fold_counters(c, c->h_qs.data(), nq);
     return FORA_OK;
 }
@@ -1569,7 +1571,7 @@ void fill_stats(const fora_ctx *c, int i, fora_query_stats &o) {
 int ensure_query_workspace(fora_ctx *c, int slots, int k) {
     c->bk_div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
     if (int rc = ensure_workspace(c, slots, c->omega)) return rc;
-    return k > 0 ? grow_pair(c, k, c->d_topk_ids, c->d_topk_sc, c->topk_cap) : FORA_OK;
+    return k > 0 ? grow_pair(c, k, c->ws.d_topk_ids, c->ws.d_topk_sc) : FORA_OK;
 }
 
 // topk > 0: also the top-k of each slot's ppr slab (k_topk_select: score descending, ties id ascending, padded with (0, 0.0))
@@ -1610,7 +1612,7 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     if (nl == 0) return FORA_OK;
     int rc = ensure_query_workspace(c, nl, want_topk ? topk : 0);
     if (rc) return rc;
-    const int per = even_batch(nl, c->B);
+    const int per = even_batch(nl, c->ws.B);
     if (sp) if ((rc = sparse_prepare(c, *sp, nq, std::min(per, nl), nl))) return rc;
     for (int b0 = 0; b0 < nl; b0 += per) {
         const int nb = std::min(per, nl - b0);
@@ -1619,14 +1621,14 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
         if (stats) for (int i = 0; i < nb; i++) fill_stats(c, i, stats[at[i]]);
         if (sp) if ((rc = sparse_place(c, *sp, sources, nq, at, nb))) return rc;
         if (want_topk) {
-            if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
+            if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
             if ((rc = copy_topk_out(c, nb, topk, ids, scores, 0, at))) return rc;
         }
         // slots i .. j - 1 of the batch whose places in the caller's arrays are consecutive too: one copy
         for (int i = 0, j; i < nb && (ppr_d || ppr_fix || residue_fix); i = j) {
             for (j = i + 1; j < nb && at[j] == at[j - 1] + 1; j++) {}
-            if ((rc = copy_slab_out(c, c->d_ppr, i, at[i], j - i, ppr_fix, ppr_d, 62))) return rc;
-            if ((rc = copy_slab_out(c, c->d_residue, i, at[i], j - i, residue_fix, nullptr, 62))) return rc;
+            if ((rc = copy_slab_out(c, c->ws.d_ppr.get(), i, at[i], j - i, ppr_fix, ppr_d, 62))) return rc;
+            if ((rc = copy_slab_out(c, c->ws.d_residue.get(), i, at[i], j - i, residue_fix, nullptr, 62))) return rc;
         }
     }
     return FORA_OK;
@@ -1639,24 +1641,24 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
 // The index cursors of a new batch all read as zero: a new epoch (the slabs themselves are cleared when they are allocated
 // and when the 24-bit epoch wraps).
 int next_cursor_epoch(fora_ctx *c) {
-    if (c->cursor_epoch == 0 || c->cursor_epoch >= 0xFFFFFFu) {
-        HIPCHK(c, hipMemsetAsync(c->d_cursor, 0, (uint64_t)c->B * (uint64_t)c->n * 8, c->stream));
-        c->cursor_epoch = 0;
+    if (c->ws.cursor_epoch == 0 || c->ws.cursor_epoch >= 0xFFFFFFu) {
+        HIPCHK(c, c->ws.d_cursor.zero(c->stream));
+        c->ws.cursor_epoch = 0;
     }
-    c->cursor_epoch++;
+    c->ws.cursor_epoch++;
     return FORA_OK;
 }
 
 // slabs of the drivers: ppr2 (the rounds' ppr), index cursors, active marks, per-slot counts; the (ids, scores) pair
 int ensure_topk_slabs(fora_ctx *c, int k) {
-    if (!c->d_ppr2) {
-        const uint64_t slab = (uint64_t)c->B * (uint64_t)c->n;
-        HIPCHK(c, hipMalloc(&c->d_ppr2, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_cursor, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_active, (size_t)c->B));
-        HIPCHK(c, hipMalloc(&c->d_above, (size_t)c->B * 8));
-    }
-    return grow_pair(c, k, c->d_topk_ids, c->d_topk_sc, c->topk_cap);
+    Workspace &w = c->ws;
+    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->n;
+    HIPCHK(c, w.d_ppr2.ensure(slab));
+    if (!w.d_cursor) w.cursor_epoch = 0; // new slabs hold no valid word: next_cursor_epoch clears them
+    HIPCHK(c, w.d_cursor.ensure(slab));
+    HIPCHK(c, ensure_active(w));
+    HIPCHK(c, w.d_above.ensure((size_t)w.B));
+    return grow_pair(c, k, w.d_topk_ids, w.d_topk_sc);
 }
 
 // host side of a batch; the vectors are kept from batch to batch (asynchronous copies read them)
@@ -1681,8 +1683,8 @@ int topk_batch_start(fora_ctx *c, TopkBatch &tb, const int32_t *sources, int nb,
     for (int i = 0; i < nb; i++)
         if (is_dangling(c, sources[i])) { tb.active[i] = 0; tb.inactive[i] = 1; any_inactive = true; }
     if (any_inactive) {
-        HIPCHK(c, hipMemcpyAsync(c->d_active, tb.inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2, (const uint8_t *)c->d_active);
+        HIPCHK(c, hipMemcpyAsync(c->ws.d_active.get(), tb.inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(), (const uint8_t *)c->ws.d_active.get());
     }
     return FORA_OK;
 }
@@ -1694,25 +1696,25 @@ template <int KIND>
 int topk_round(fora_ctx *c, TopkBatch &tb, int nb, bool with_idx, int round, double rmax, double omega, uint32_t chunks,
                unsigned long long *round_walks, int nzh, Dev &dw) {
     for (int i = 0; i < nb; i++) if (tb.active[i]) tb.nround[i] = round;
-    HIPCHK(c, hipMemcpyAsync(c->d_active, tb.active.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_above, 0, (size_t)nb * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ws.d_active.get(), tb.active.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->ws.d_counters.zero(c->stream));
+    HIPCHK(c, c->ws.d_above.zero(c->stream, (size_t)nb));
+    HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
     if (int rc = reset_binned_counters(c)) return rc;
     const Dev d = make_dev(c, nb, with_idx, rmax, omega);
     int h = ev_begin(c, 4);
-    hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->d_active);
+    hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->ws.d_active.get());
     ev_end(c, h);
     if (int rc = run_push_levels(c, d, nullptr, 0, true)) return rc;
     h = ev_begin(c, 4);
-    hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_ppr, c->d_ppr2,
-                       (const uint8_t *)c->d_active);
+    hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(),
+                       (const uint8_t *)c->ws.d_active.get());
     ev_end(c, h);
     dw = d;
-    dw.ppr = c->d_ppr2;
+    dw.ppr = c->ws.d_ppr2.get();
     h = ev_begin(c, 2);
     hipLaunchKernelGGL(k_walk_alloc<KIND>, (dw.wide && (dw.slot_major & 8u)) ? dim3(nb, chunks) : dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, with_idx ? 1 : 0,
-                       (const uint8_t *)c->d_active, c->d_cursor, round_walks, c->cursor_epoch);
+                       (const uint8_t *)c->ws.d_active.get(), c->ws.d_cursor.get(), round_walks, c->ws.cursor_epoch);
     ev_end(c, h);
     launch_walks(c, dw, nb, with_idx, (uint32_t)round, nzh);
     return FORA_OK;
@@ -1723,13 +1725,13 @@ int topk_round(fora_ctx *c, TopkBatch &tb, int nb, bool with_idx, int round, dou
 int topk_batch_end(fora_ctx *c, const TopkBatch &tb, int nb, int k, const double *sel_thr, const char *what, int b0,
                    int32_t *ids, double *scores, int32_t *rounds) {
     Dev ds = make_dev(c, nb, false);
-    ds.ppr = c->d_ppr2;
+    ds.ppr = c->ws.d_ppr2.get();
     const int h = ev_begin(c, 4);
-    if (int rc = launch_select(c, ds, nb, k, c->d_topk_ids, c->d_topk_sc, 0, sel_thr)) return rc;
+    if (int rc = launch_select(c, ds, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0, sel_thr)) return rc;
     ev_end(c, h);
     if (int rc = close_batch(c, tb.hb, what)) return rc;
     if (int rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0)) return rc;
-    HIPCHK(c, hipMemcpy(c->h_qs.data(), c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->h_qs.data(), c->ws.d_qs.get(), (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
     fold_counters(c, c->h_qs.data(), nb);
     if (rounds) for (int i = 0; i < nb; i++) rounds[b0 + i] = tb.nround[i];
     return FORA_OK;
@@ -2157,7 +2159,7 @@ int fora_hip_set_batch(fora_ctx *c, int batch) {
     c->batch_req = batch;
     return FORA_OK;
 }
-int fora_hip_get_batch(fora_ctx *c) { return c ? c->B : FORA_E_ARG; }
+int fora_hip_get_batch(fora_ctx *c) { return c ? c->ws.B : FORA_E_ARG; }
 
 int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return FORA_E_ARG;
@@ -2251,9 +2253,9 @@ int fora_hip_build_index(fora_ctx *c) {
     int rc = ensure_workspace(c, 1, (double)total);
     if (rc) return rc;
     Dev d = make_dev(c, 1, true);
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, N_COUNTERS * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_wit_count, 0, (size_t)c->B * 4 * CSTRIDE, c->stream));
+    HIPCHK(c, c->ws.d_counters.zero(c->stream));
+    HIPCHK(c, c->ws.d_err.zero(c->stream));
+    HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
     const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 2048);
     int h = ev_begin(c, 4);
     hipLaunchKernelGGL(k_index_alloc, dim3(chunks), dim3(BLOCK), 0, c->stream, d);
@@ -2389,18 +2391,18 @@ int fora_hip_push_batch(fora_ctx *c, const int32_t *sources, int nq, uint64_t *r
 int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64_t *num_s_rw, uint64_t *n_rw) {
     if (!c || !c->n || !c->have_params || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp d_r, d_num, d_n;
+    DevBuf<double> d_r; DevBuf<uint64_t> d_num, d_n;
     const size_t n = (size_t)c->n;
-    HIPCHK(c, hipMalloc(&d_r.p, n * 8));
-    HIPCHK(c, hipMalloc(&d_num.p, n * 8));
-    HIPCHK(c, hipMalloc(&d_n.p, 8));
-    HIPCHK(c, hipMemcpy(d_r.p, residue, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, d_r.alloc(n));
+    HIPCHK(c, d_num.alloc(n));
+    HIPCHK(c, d_n.alloc(1));
+    HIPCHK(c, hipMemcpy(d_r.get(), residue, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_walk_counts_f64, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                       c->n, (const double *)d_r.p, rsum, c->omega, c->alpha, c->opt, (uint64_t *)d_num.p, (uint64_t *)d_n.p);
+                       c->n, (const double *)d_r.get(), rsum, c->omega, c->alpha, c->opt, d_num.get(), d_n.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(num_s_rw, d_num.p, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(num_s_rw, d_num.get(), n * 8, hipMemcpyDeviceToHost));
     uint64_t N = 0;
-    HIPCHK(c, hipMemcpy(&N, d_n.p, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&N, d_n.get(), 8, hipMemcpyDeviceToHost));
     if (n_rw) *n_rw = N;
     return FORA_OK;
 }
@@ -2412,20 +2414,20 @@ int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_
     for (int64_t i = 0; i < count; i++)
         if (starts[i] < 0 || starts[i] >= c->n) return fail(c, FORA_E_ARG, "walk start out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp d_s, d_d, d_j;
-    HIPCHK(c, hipMalloc(&d_s.p, (size_t)count * 4));
-    HIPCHK(c, hipMalloc(&d_d.p, (size_t)count * 4));
-    HIPCHK(c, hipMalloc(&d_j.p, (size_t)count * 8));
-    HIPCHK(c, hipMemcpy(d_s.p, starts, (size_t)count * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_j.p, js, (size_t)count * 8, hipMemcpyHostToDevice));
+    DevBuf<int32_t> d_s, d_d; DevBuf<uint64_t> d_j;
+    HIPCHK(c, d_s.alloc((size_t)count));
+    HIPCHK(c, d_d.alloc((size_t)count));
+    HIPCHK(c, d_j.alloc((size_t)count));
+    HIPCHK(c, hipMemcpy(d_s.get(), starts, (size_t)count * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_j.get(), js, (size_t)count * 8, hipMemcpyHostToDevice));
     Dev d{};
     d.n = c->n; d.rowinfo = c->d_rowinfo; d.row_ptr = c->d_row_ptr; d.col = c->d_col;
     d.alpha32 = (uint32_t)(c->alpha * 4294967296.0);
     d.seed_lo = (uint32_t)c->seed; d.seed_hi = (uint32_t)(c->seed >> 32);
     hipLaunchKernelGGL(k_walks_raw, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, d,
-                       stream_id, round, no_zero_hop, (const int32_t *)d_s.p, (const uint64_t *)d_j.p, count, (int32_t *)d_d.p);
+                       stream_id, round, no_zero_hop, (const int32_t *)d_s.get(), (const uint64_t *)d_j.get(), count, d_d.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(dests, d_d.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dests, d_d.get(), (size_t)count * 4, hipMemcpyDeviceToHost));
     return FORA_OK;
 }
 
@@ -2469,10 +2471,10 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
     if ((rc = ensure_topk_slabs(c, k))) return rc;
-    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->B));
+    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
     TopkBatch tb;
     std::vector<unsigned long long> above;
-    const int per = even_batch(nq, c->B);
+    const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         if ((rc = topk_batch_start(c, tb, sources + b0, nb, with_idx != 0, chunks))) return rc;
@@ -2491,10 +2493,10 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
             const double T = (1 + epsilon) * delta; // query.h:1030
             const int h = ev_begin(c, 4);
             hipLaunchKernelGGL(k_count_above, dim3(std::min<uint32_t>(chunks, 256), nb), dim3(BLOCK), 0, c->stream, dw,
-                               (const uint8_t *)c->d_active, T, c->d_above);
+                               (const uint8_t *)c->ws.d_active.get(), T, c->ws.d_above.get());
             ev_end(c, h);
             above.assign((size_t)nb, 0);
-            HIPCHK(c, hipMemcpyAsync(above.data(), c->d_above, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(above.data(), c->ws.d_above.get(), (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
             if ((rc = check_dev_err(c))) return rc;
             for (int i = 0; i < nb; i++)
                 if (tb.active[i] && (above[i] >= (unsigned long long)k || delta <= min_delta)) {
@@ -2536,25 +2538,23 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
     if ((rc = ensure_topk_slabs(c, k))) return rc;
-    if (!c->d_upper) {
-        const uint64_t slab = (uint64_t)c->B * (uint64_t)c->n;
-        HIPCHK(c, hipMalloc(&c->d_upper, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_lower, slab * 8));
-        HIPCHK(c, hipMalloc(&c->d_filter, slab));
-        HIPCHK(c, hipMemset(c->d_filter, 0, slab));
-        HIPCHK(c, hipMalloc(&c->d_fail, (size_t)c->B * 4));
-        HIPCHK(c, hipMalloc(&c->d_round_walks, (size_t)c->B * 8));
-    }
-    if ((rc = grow_pair(c, k, c->d_lb_ids, c->d_lb_sc, c->lb_cap))) return rc;
-    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->B));
+    Workspace &w = c->ws;
+    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->n;
+    HIPCHK(c, w.d_upper.ensure(slab));
+    HIPCHK(c, w.d_lower.ensure(slab));
+    if (!w.d_filter) { HIPCHK(c, w.d_filter.alloc(slab)); HIPCHK(c, w.d_filter.zero(c->stream)); } // the marks start from zero, once
+    HIPCHK(c, w.d_fail.ensure((size_t)w.B));
+    HIPCHK(c, w.d_round_walks.ensure((size_t)w.B));
+    if ((rc = grow_pair(c, k, w.d_lb_ids, w.d_lb_sc))) return rc;
+    const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
     TopkBatch tb;
     std::vector<unsigned long long> above;
     std::vector<uint32_t> failv;
-    const int per = even_batch(nq, c->B);
+    const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         if ((rc = topk_batch_start(c, tb, sources + b0, nb, with_idx != 0, chunks))) return rc;
-        hipLaunchKernelGGL(k_bounds_reset, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->d_upper, c->d_lower); // :941-942
+        hipLaunchKernelGGL(k_bounds_reset, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_upper.get(), c->ws.d_lower.get()); // :941-942
         double delta = init_delta;
         int round = 0;
         while (delta >= min_delta) { // query.h:944
@@ -2563,35 +2563,35 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
             double rmax = epsilon * sqrt(delta / 3 / m / L); // fora_setting with the round's delta, algo.h:455-463
             rmax *= rmax_scale;
             const double omega = (2 + epsilon) * L / delta / epsilon / epsilon;
-            HIPCHK(c, hipMemsetAsync(c->d_fail, 0, (size_t)nb * 4, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->d_round_walks, 0, (size_t)nb * 8, c->stream));
+            HIPCHK(c, c->ws.d_fail.zero(c->stream, (size_t)nb));
+            HIPCHK(c, c->ws.d_round_walks.zero(c->stream, (size_t)nb));
             Dev dw{};
-            if ((rc = topk_round<ALLOC_BOUND>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, c->d_round_walks, 0, dw))) return rc;
+            if ((rc = topk_round<ALLOC_BOUND>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, c->ws.d_round_walks.get(), 0, dw))) return rc;
             const int h = ev_begin(c, 4);
             if (delta < threshold) // query.h:745-746
-                hipLaunchKernelGGL(k_bounds_update, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, (const uint64_t *)c->d_ppr,
-                                   (const uint8_t *)c->d_active, (const unsigned long long *)c->d_round_walks, L,
-                                   1.0 / c->n, sqrt(1.0 / c->n), c->d_upper, c->d_lower);
+                hipLaunchKernelGGL(k_bounds_update, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, (const uint64_t *)c->ws.d_ppr.get(),
+                                   (const uint8_t *)c->ws.d_active.get(), (const unsigned long long *)c->ws.d_round_walks.get(), L,
+                                   1.0 / c->n, sqrt(1.0 / c->n), c->ws.d_upper.get(), c->ws.d_lower.get());
             // if_stop, algo.h:1096-1166
             hipLaunchKernelGGL(k_count_above, dim3(std::min<uint32_t>(chunks, 256), nb), dim3(BLOCK), 0, c->stream, dw,
-                               (const uint8_t *)c->d_active, 2.0 * delta, c->d_above);
+                               (const uint8_t *)c->ws.d_active.get(), 2.0 * delta, c->ws.d_above.get());
             const bool bounds_on = !(delta >= threshold);
             if (bounds_on) {
                 Dev dl = dw;
-                dl.ppr = (uint64_t *)c->d_lower; // non-negative f64: bit patterns order like the values
-                if ((rc = launch_select(c, dl, nb, k, c->d_lb_ids, c->d_lb_sc, 1))) return rc;
-                hipLaunchKernelGGL(k_bound_ratio, dim3(nb), dim3(SEL_THREADS), 0, c->stream, dw, k, (const int32_t *)c->d_lb_ids,
-                                   (const double *)c->d_lb_sc, (const uint8_t *)c->d_active, (const double *)c->d_upper,
-                                   1.0 + epsilon, c->d_filter, c->d_fail);
-                hipLaunchKernelGGL(k_bound_scan, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, k, (const double *)c->d_lb_sc,
-                                   (const uint8_t *)c->d_active, (const double *)c->d_upper, (const double *)c->d_lower, delta,
-                                   1.0 + epsilon, (1 + epsilon) / (1 - epsilon), c->d_filter, c->d_fail);
+                dl.ppr = (uint64_t *)c->ws.d_lower.get(); // non-negative f64: bit patterns order like the values
+                if ((rc = launch_select(c, dl, nb, k, c->ws.d_lb_ids.get(), c->ws.d_lb_sc.get(), 1))) return rc;
+                hipLaunchKernelGGL(k_bound_ratio, dim3(nb), dim3(SEL_THREADS), 0, c->stream, dw, k, (const int32_t *)c->ws.d_lb_ids.get(),
+                                   (const double *)c->ws.d_lb_sc.get(), (const uint8_t *)c->ws.d_active.get(), (const double *)c->ws.d_upper.get(),
+                                   1.0 + epsilon, c->ws.d_filter.get(), c->ws.d_fail.get());
+                hipLaunchKernelGGL(k_bound_scan, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, k, (const double *)c->ws.d_lb_sc.get(),
+                                   (const uint8_t *)c->ws.d_active.get(), (const double *)c->ws.d_upper.get(), (const double *)c->ws.d_lower.get(), delta,
+                                   1.0 + epsilon, (1 + epsilon) / (1 - epsilon), c->ws.d_filter.get(), c->ws.d_fail.get());
             }
             ev_end(c, h);
             above.assign((size_t)nb, 0);
             failv.assign((size_t)nb, 0);
-            HIPCHK(c, hipMemcpyAsync(above.data(), c->d_above, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(failv.data(), c->d_fail, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(above.data(), c->ws.d_above.get(), (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(failv.data(), c->ws.d_fail.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
             if ((rc = check_dev_err(c))) return rc;
             for (int i = 0; i < nb; i++) {
                 if (!tb.active[i]) continue;
@@ -2625,7 +2625,7 @@ static int power_iteration_batch_impl(fora_ctx *c, const int32_t *sources, int n
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_query_workspace(c, nq, want_topk ? k : 0);
     if (rc) return rc;
-    const int per = even_batch(nq, c->B);
+    const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         const int hb = ev_begin(c, 5);
@@ -2635,12 +2635,12 @@ static int power_iteration_batch_impl(fora_ctx *c, const int32_t *sources, int n
         if ((rc = run_push_levels(c, d, nullptr, max_iter))) return rc;
         if (want_topk) {
             const int h = ev_begin(c, 4);
-            if ((rc = launch_select(c, d, nb, k, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
+            if ((rc = launch_select(c, d, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
             ev_end(c, h);
         }
         if ((rc = close_batch(c, hb, "power iteration"))) return rc;
         if (want_topk && (rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0))) return rc;
-        if ((rc = copy_slab_out(c, c->d_ppr, 0, (uint64_t)b0, (uint64_t)nb, ppr_fix_out, ppr_out, 62))) return rc;
+        if ((rc = copy_slab_out(c, c->ws.d_ppr.get(), 0, (uint64_t)b0, (uint64_t)nb, ppr_fix_out, ppr_out, 62))) return rc;
     }
     return FORA_OK;
 }
@@ -2689,24 +2689,24 @@ int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double e
 static int ensure_reverse_csr(fora_ctx *c) {
     if (c->d_rin_ptr) return FORA_OK;
     const uint64_t n = (uint64_t)c->n, nnz = (uint64_t)c->nnz;
-    DevTmp indeg, cursor;
-    HIPCHK(c, hipMalloc(&indeg.p, n * 4));
-    HIPCHK(c, hipMemsetAsync(indeg.p, 0, n * 4, c->stream));
+    DevBuf<uint32_t> indeg; DevBuf<unsigned long long> cursor;
+    HIPCHK(c, indeg.alloc(n));
+    HIPCHK(c, indeg.zero(c->stream));
     if (nnz) hipLaunchKernelGGL(k_rev_count, dim3((unsigned)std::min<uint64_t>((nnz + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream,
-                                (const int32_t *)c->d_col, nnz, (uint32_t *)indeg.p);
+                                (const int32_t *)c->d_col, nnz, indeg.get());
     std::vector<uint32_t> h_in(n);
-    HIPCHK(c, hipMemcpyAsync(h_in.data(), indeg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_in.data(), indeg.get(), n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<int64_t> rp(n + 1);
     rp[0] = 0;
     for (uint64_t v = 0; v < n; v++) rp[v + 1] = rp[v] + h_in[v];
     HIPCHK(c, hipMalloc(&c->d_rin_ptr, (n + 1) * 8));
     HIPCHK(c, hipMalloc(&c->d_rin, std::max<uint64_t>(1, nnz) * 4));
-    HIPCHK(c, hipMalloc(&cursor.p, std::max<uint64_t>(1, n) * 8));
+    HIPCHK(c, cursor.alloc(std::max<uint64_t>(1, n)));
     HIPCHK(c, hipMemcpyAsync(c->d_rin_ptr, rp.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cursor.p, rp.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cursor.get(), rp.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_rev_fill, dim3((unsigned)std::min<uint64_t>((n * 64 + BLOCK - 1) / BLOCK, 16384)), dim3(BLOCK), 0, c->stream,
-                       (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col, c->n, (unsigned long long *)cursor.p, c->d_rin);
+                       (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col, c->n, cursor.get(), c->d_rin);
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors and the cursor go out of scope)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("reverse CSR: ") + hipGetErrorString(e));
@@ -2983,7 +2983,7 @@ static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
     const uint64_t n = (uint64_t)c->n;
     const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
     int h = ev_begin(c, 12);
-    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(),
                        (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
     ev_end(c, h);
     const bool one_chunk = r.chunks.size() == 1; // (then its entries were written once for every batch)
@@ -2992,12 +2992,12 @@ static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
         const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
         h = ev_begin(c, 12);
         hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                           (const uint64_t *)c->d_residue, (uint32_t)nb, (const int32_t *)c->d_src, (const uint64_t *)c->d_boff,
-                           (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->d_ppr);
+                           (const uint64_t *)c->ws.d_residue.get(), (uint32_t)nb, (const int32_t *)c->ws.d_src.get(), (const uint64_t *)c->d_boff,
+                           (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->ws.d_ppr.get());
         ev_end(c, h);
     }
     h = ev_begin(c, 12);
-    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_ppr, c->d_residue,
+    hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(),
                        n, (uint64_t)nb); // -> slot-major estimates at 2^-60 in the residue slabs
     ev_end(c, h);
     return FORA_OK;
@@ -3008,15 +3008,15 @@ static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
 static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkCount &w, const BwdRun *bwd, double rmax_used,
                         double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
     const bool want_topk = k > 0 && (ids || scores);
-    uint64_t *const est = bwd ? c->d_residue : c->d_ppr;
+    uint64_t *const est = bwd ? c->ws.d_residue.get() : c->ws.d_ppr.get();
     const int frac = bwd ? 60 : 62;
-    const int per = even_batch(nq, c->B);
+    const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         const int hb = ev_begin(c, 5);
         int rc = reset_batch_state(c, nb, sources + b0);
         if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(c->d_qs, 0, (size_t)nb * sizeof(QState), c->stream));
+        HIPCHK(c, c->ws.d_qs.zero(c->stream, (size_t)nb));
         const Dev d = make_dev(c, nb, false);
         launch_mc_walks(c, d, nb, w);
         if (bwd && (rc = bippr_combine(c, *bwd, nb))) return rc;
@@ -3030,21 +3030,21 @@ static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkC
         }
         if (want_topk) {
             const int h = ev_begin(c, 4);
-            if ((rc = launch_select(c, de, nb, k, c->d_topk_ids, c->d_topk_sc, 0))) return rc;
+            if ((rc = launch_select(c, de, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
             ev_end(c, h);
         }
-        HIPCHK(c, hipMemcpyAsync(c->h_qs_pin, c->d_qs, (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_steps_pin, d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ws.h_qs_pin.get(), c->ws.d_qs.get(), (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         if ((rc = close_batch(c, hb, bwd ? "bippr" : "montecarlo"))) return rc;
         c->timing.walks += w.W * (uint64_t)nb;
-        c->timing.walk_steps += *c->h_steps_pin;
+        c->timing.walk_steps += *c->ws.h_steps_pin.get();
         if (stats)
             for (int i = 0; i < nb; i++) {
                 fora_query_stats &o = stats[b0 + i];
                 memset(&o, 0, sizeof(o));
                 o.n_walks = w.W;
                 o.rmax_used = rmax_used;
-                o.ppr_sum_fix = c->h_qs_pin[i].ppr_sum;
+                o.ppr_sum_fix = c->ws.h_qs_pin.get()[i].ppr_sum;
                 o.dangling_source = is_dangling(c, sources[b0 + i]) ? 1 : 0;
             }
         // (k_topk_select scales by 2^-62: BiPPR's scores x 4)
