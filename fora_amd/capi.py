@@ -17,7 +17,7 @@ SYMBOLS = [
     "fora_hip_get_index", "fora_hip_set_index", "fora_hip_clear_index", "fora_hip_query_batch",
     "fora_hip_query_batch_fix", "fora_hip_topk_batch", "fora_hip_topk_bound_batch", "fora_hip_power_iteration_batch", "fora_hip_push_batch", "fora_hip_walk_counts",
     "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
-    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bwdpush_batch",
+    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bippr_targets_batch", "fora_hip_bwdpush_batch",
     "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
 ]
 BWD_FIX_ONE = 1 << 60
@@ -371,6 +371,21 @@ class Engine:
         self._chk(self._lib.fora_hip_bippr_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), C.c_double(rmax_scale),
                                                  _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), st, C.byref(bwd)))
         return ppr, fix, ids, sc, self._stats(st, nq), bwd.as_dict()
+
+    def bippr_targets(self, sources, targets, epsilon=0.5, rmax_scale=1.0, want_est=False, want_fix=True):
+        """BiPPR for chosen (source, target) sets (fora_hip_bippr_targets_batch): pi(s, t) for every source and every listed
+        target, nt backward pushes instead of n.  Returns (est f64 [nq,nt] or None, raw u64 at 2^60 [nq,nt] or None, stats,
+        backward-push counters as a dict); fix[i, j] is the word bippr() gives at [i, targets[j]]."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        nq, nt = src.size, tg.size
+        st = (QueryStats * max(1, nq))()
+        bwd = BwdStats()
+        est = np.zeros((nq, nt), dtype=np.float64) if want_est else None
+        fix = np.zeros((nq, nt), dtype=np.uint64) if want_fix else None
+        self._chk(self._lib.fora_hip_bippr_targets_batch(self._ctx, _p(src), C.c_int(nq), _p(tg), C.c_int(nt), C.c_double(epsilon),
+                                                         C.c_double(rmax_scale), _p(est), _p(fix), st, C.byref(bwd)))
+        return est, fix, self._stats(st, nq), bwd.as_dict()
 
     # ---- stage hooks
     def bwdpush(self, targets, rmax):

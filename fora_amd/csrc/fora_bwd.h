@@ -4,6 +4,7 @@
 //   reverse CSR     (graph.h's gr)      -> k_rev_count, k_rev_fill (counting sort of the CSR's edges by target)
 //   backward push   algo.h:703-751      -> k_bwd_push<false, *> (LDS tier), k_bwd_push<true, *> (global tier)
 //   combine         query.h:91-112      -> k_bippr_combine (+ k_transpose_u64 on either side)
+//   targeted combine (a list of targets) -> k_bippr_combine_targets<by slot / by entry>, k_bippr_targets_finish
 //
 // Fixed point 1.0 = BWD_ONE = 2^60 (include/fora_hip.h, FORA_BWD_FIX_ONE).  A push is level-synchronous: every node
 // whose residue is over thr pops at the same moment (phase A: snapshot, zero, keep floor(x * afix / 2^62)), then the
@@ -292,6 +293,136 @@ __global__ void __launch_bounds__(BLOCK) k_bippr_combine(const uint64_t *cT, uin
         }
         if (act) out[row + bq] = acc;
     }
+}
+
+// ---- targeted BiPPR (fora_hip_bippr_targets_batch): the same estimate for a caller's list of targets.  The work is the
+// chunk's ENTRY array, cut into spans of `span` entries, one wave per span: one target with 10^5 entries spreads over
+// 10^5 / span waves, and a chunk of small targets fills the device just the same.  A wave finds the target of its first
+// entry by a binary search in off, walks on across target boundaries with its sums in registers and adds them to the zeroed
+// slot-major block out[slot][nt_all] once per (target segment, slot) -- never once per entry.  The adds are integer adds,
+// so neither the span, the lane mapping nor the order of the atomics changes a bit.
+
+// index of the target that holds entry e < off[nt]: the largest i with off[i] <= e (a target without entries holds none)
+__device__ __forceinline__ uint32_t bpt_owner(const uint64_t *off, uint32_t nt, uint64_t e) {
+    uint32_t lo = 0, hi = nt; // off[lo] <= e < off[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t x, int k) { // lane k's x, k wave-uniform
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, k);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), k);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// BY_SLOT = true: lane = slot (blockIdx.y picks the group of 64 slots), c = the walk slabs node-major ([n][nb]): an entry
+// reads nb consecutive words.  The wave loads 64 entries at a time, one per lane, and hands them round with v_readlane.
+// BY_SLOT = false: lane = entry, c = the walk slabs as the walks wrote them, slot-major ([nb][n]): every lane gathers its
+// own entry's word, slot after slot, and a wave sum closes each (segment, slot).  This is the shape of a call with few
+// sources (one source keeps 64 lanes busy instead of one) and of a call with few entries (no transpose of the slabs).
+// Chunk-relative off / entries as k_bwd_push<*, true> wrote them; the chunk's targets are columns t0 .. t0 + nt - 1.
+template <bool BY_SLOT>
+__global__ void __launch_bounds__(BLOCK) k_bippr_combine_targets(const uint64_t *c, uint32_t nb, uint64_t n, const int32_t *src,
+                                                                 const uint64_t *off, const uint32_t *e_node, const uint64_t *e_p,
+                                                                 const uint64_t *e_r, uint32_t t0, uint32_t nt, uint32_t span,
+                                                                 uint64_t nt_all, unsigned long long *out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t w = (uint64_t)blockIdx.x * (BLOCK / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t ne = off[nt];
+    uint64_t a = w * span;
+    if (a >= ne) return;
+    const uint64_t b = min(ne, a + span);
+    uint32_t i = bpt_owner(off, nt, a);
+    uint64_t seg_end = min(b, off[i + 1]);
+    if (BY_SLOT) {
+        const uint32_t bq = blockIdx.y * 64 + lane;
+        const bool act = bq < nb;
+        const uint32_t s = act ? (uint32_t)src[bq] : BWD_EMPTY;
+        const uint64_t *cq = c + (act ? bq : 0);
+        unsigned long long *oq = out + (uint64_t)(act ? bq : 0) * nt_all + t0;
+        uint64_t acc = 0;
+        for (uint64_t e0 = a; e0 < b; e0 += 64) {
+            const uint64_t mine = e0 + lane;
+            const bool have = mine < b;
+            const uint32_t v = have ? e_node[mine] : 0;
+            const uint64_t r = have ? e_r[mine] : 0, p = have ? e_p[mine] : 0;
+            const int cnt = (int)min((uint64_t)64, b - e0);
+            for (int k = 0; k < cnt;) {
+                const uint64_t e = e0 + k;
+                if (e == seg_end) { // the next target's segment: hand over this one's sum
+                    if (act && acc) atomicAdd(&oq[i], (unsigned long long)acc);
+                    acc = 0;
+                    do i++; while (off[i + 1] <= e);
+                    seg_end = min(b, off[i + 1]);
+                }
+                if (k + 4 <= cnt && e + 4 <= seg_end) { // four gathers in flight
+                    uint32_t vk[4];
+                    uint64_t rk[4], pk[4], ck[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        vk[u] = (uint32_t)__builtin_amdgcn_readlane((int)v, k + u);
+                        rk[u] = readlane_u64(r, k + u);
+                        pk[u] = readlane_u64(p, k + u);
+                        ck[u] = act && rk[u] ? cq[(uint64_t)vk[u] * nb] : 0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        if (ck[u]) acc += mul_shr62(ck[u], rk[u]);
+                        if (vk[u] == s) acc += pk[u];
+                    }
+                    k += 4;
+                } else {
+                    const uint32_t vk = (uint32_t)__builtin_amdgcn_readlane((int)v, k);
+                    const uint64_t rk = readlane_u64(r, k), pk = readlane_u64(p, k);
+                    if (act) {
+                        if (rk) acc += mul_shr62(cq[(uint64_t)vk * nb], rk);
+                        if (vk == s) acc += pk;
+                    }
+                    k++;
+                }
+            }
+        }
+        if (act && acc) atomicAdd(&oq[i], (unsigned long long)acc);
+    } else {
+        for (;;) {
+            for (uint32_t q = 0; q < nb; q++) {
+                const uint32_t s = (uint32_t)src[q];
+                const uint64_t *cq = c + (uint64_t)q * n;
+                uint64_t acc = 0;
+                for (uint64_t e = a + lane; e < seg_end; e += 64) {
+                    const uint32_t v = e_node[e];
+                    const uint64_t r = e_r[e];
+                    if (r) {
+                        const uint64_t cw = cq[v];
+                        if (cw) acc += mul_shr62(cw, r);
+                    }
+                    if (v == s) acc += e_p[e];
+                }
+                acc = wave_sum(acc);
+                if (lane == 0 && acc) atomicAdd(&out[(uint64_t)q * nt_all + t0 + i], (unsigned long long)acc);
+            }
+            a = seg_end;
+            if (a >= b) break;
+            do i++; while (off[i + 1] <= a);
+            seg_end = min(b, off[i + 1]);
+        }
+    }
+}
+
+// end of a batch of the targeted call: the sum of every slot's nt words (u64, wrapping) and, when wanted, the words as f64
+// at 2^-60
+__global__ void __launch_bounds__(BLOCK) k_bippr_targets_finish(const uint64_t *est, uint64_t nt, double *f64, unsigned long long *row_sum) {
+    const uint64_t row = (uint64_t)blockIdx.y * nt;
+    uint64_t acc = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < nt; j += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t x = est[row + j];
+        acc += x;
+        if (f64) f64[row + j] = (double)x * 0x1p-60; // (exact scaling: == ldexp((double)x, -60))
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&row_sum[blockIdx.y], (unsigned long long)acc);
 }
 
 } // namespace fora

@@ -81,6 +81,8 @@ struct Tunables {
     int64_t grid = 2048;         // workgroups of the direct-path kernels
     int64_t bwd_lds_cap = BWD_CAP_DEFAULT; // backward push: entries per target's LDS table (at most BWD_CAP_MAX); a target with more goes to the global tier; 0: every target does
     int64_t bwd_chunk = 0;       // backward push: targets per chunk (0: as many as the entry budget from free HBM holds)
+    int64_t tgt_lanes = -1;      // targeted BiPPR combine (k_bippr_combine_targets): 0 lane = slot over the transposed walk slabs, 1 lane = entry over the slot-major ones, -1: by the batch's slots and the call's entries (want_by_slot).  Same bits either way
+    int64_t tgt_span = 0;        // ... entries per wave (0: from the chunk's entries, 64 .. 1024).  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
     {"direct", &Tunables::direct, true}, {"force_wide", &Tunables::force_wide, true}, {"pass_bins", &Tunables::pass_bins, true},
@@ -90,6 +92,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"select_compact", &Tunables::select_compact, false}, {"team", &Tunables::team, true}, {"team_size", &Tunables::team_size, true}, {"team_tail", &Tunables::team_tail, false}, {"team_xcd", &Tunables::team_xcd, false}, {"team_max", &Tunables::team_max, true}, {"team_hubs", &Tunables::team_hubs, true}, {"team_log", &Tunables::team_log, false}, {"topk_bk_div", &Tunables::topk_bk_div, true}, {"quads", &Tunables::quads, false}, {"team_timeout_ms", &Tunables::team_timeout_ms, false}, {"team_abort_level", &Tunables::team_abort_level, false}, {"acc_group", &Tunables::acc_group, false}, {"slot_major", &Tunables::slot_major, false}, {"team_coop", &Tunables::team_coop, false}, {"tail_hubs", &Tunables::tail_hubs, false}, {"rounds", &Tunables::rounds, false}, {"defer", &Tunables::defer, true}, {"defer_min", &Tunables::defer_min, false}, {"round_div", &Tunables::round_div, false},
     {"profile", &Tunables::profile, false}, {"grid", &Tunables::grid, false},
     {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
+    {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -290,6 +293,10 @@ struct fora_ctx {
     uint32_t g_wgs = 0;
     unsigned long long *d_bstat = nullptr;
     double bwd_ms = 0, combine_ms = 0; // event times of the call in progress (EvPair kinds 11, 12)
+    // targeted BiPPR (fora_hip_bippr_targets_batch): the estimate block of a batch, slot-major [nb][nt] and then the nb row
+    // sums; its f64 copy.  nt has nothing to do with n, so these are no slabs of the workspace; grow-only
+    DevBuf<uint64_t> d_tgt_est;
+    DevBuf<double> d_tgt_f64;
 
     // sparse result of the last fora_hip_query_sparse_batch (free_sparse): its own buffers, apart from the workspace --
     // free_workspace (set_batch, set_option, a bucket retry) leaves them alone
@@ -1840,6 +1847,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_sparse(c);
     dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
     dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er); dfree(c->d_bstat);
+    c->d_tgt_est.reset(); c->d_tgt_f64.reset();
     dfree(c->d_stamps);
     for (auto &p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3102,6 +3110,140 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
     return FORA_OK;
 }
 
+// ---- targeted BiPPR: the estimate of bippr_batch_impl for a caller's list of targets, nt backward pushes instead of n
+// (the TARGETED BIPPR contract of include/fora_hip.h).
+// Lane mapping of k_bippr_combine_targets for a batch of nb slots and a call of `entries` entries.  Lane = slot reads
+// 8 nb contiguous bytes per entry but needs the slabs transposed first (16 n nb bytes); lane = entry gathers one word per
+// lane from the slot-major slabs, a 64-byte sector for 8 bytes.  So: by entry while fewer than 16 slots would leave three
+// quarters of a wave idle, and while the gathers' 64 nb E bytes stay under the transpose's 16 n nb, E < n / 4.
+static bool want_by_slot(const fora_ctx *c, int nb, uint64_t entries) {
+    if (c->opt_.tgt_lanes >= 0) return c->opt_.tgt_lanes == 0;
+    return nb >= 16 && entries >= (uint64_t)c->n / 4;
+}
+
+// The combine of a batch: the walk slabs of the nb slots (slot-major in d_ppr) with the entries of every chunk into the
+// zeroed block `out` ([nb][nt]).
+static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t nt, unsigned long long *out) {
+    const uint64_t n = (uint64_t)c->n;
+    const bool by_slot = want_by_slot(c, nb, r.off[nt]);
+    int h;
+    if (by_slot) {
+        h = ev_begin(c, 12);
+        hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)(((uint64_t)nb + 31) / 32 * ((n + 31) / 32))), dim3(BLOCK), 0, c->stream,
+                           (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(), (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
+        ev_end(c, h);
+    }
+    const uint64_t *slabs = by_slot ? c->ws.d_residue.get() : c->ws.d_ppr.get();
+    const uint64_t groups = by_slot ? ((uint64_t)nb + 63) / 64 : 1;
+    const bool one_chunk = r.chunks.size() == 1; // (then its entries were written once for every batch)
+    for (size_t ck = 0; ck < r.chunks.size(); ck++) {
+        if (!one_chunk) if (int rc = bwd_write(c, r, ck)) return rc;
+        const uint32_t t0 = r.chunks[ck].first, t1 = r.chunks[ck].second;
+        const uint64_t ne = r.off[t1] - r.off[t0];
+        if (!ne) continue;
+        // entries per wave: about 32 waves per CU over the launch, 64 .. 1024 entries each
+        uint64_t span = c->opt_.tgt_span > 0 ? (uint64_t)c->opt_.tgt_span
+                                             : std::min<uint64_t>(1024, std::max<uint64_t>(64, ne * groups / ((uint64_t)c->prop.multiProcessorCount * 32)));
+        span = std::min<uint64_t>(span, 1u << 30);
+        const uint64_t waves = (ne + span - 1) / span;
+        const dim3 grid((unsigned)((waves + BLOCK / 64 - 1) / (BLOCK / 64)), (unsigned)groups);
+        h = ev_begin(c, 12);
+        if (by_slot)
+            hipLaunchKernelGGL((k_bippr_combine_targets<true>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
+                               (const uint64_t *)c->d_boff, (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0,
+                               t1 - t0, (uint32_t)span, nt, out);
+        else
+            hipLaunchKernelGGL((k_bippr_combine_targets<false>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
+                               (const uint64_t *)c->d_boff, (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0,
+                               t1 - t0, (uint32_t)span, nt, out);
+        ev_end(c, h);
+    }
+    return FORA_OK;
+}
+
+static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq, const int32_t *targets, int nt, double epsilon,
+                                    double rmax_scale, double *est_out, uint64_t *est_fix_out, fora_query_stats *stats,
+                                    fora_bwd_stats *bwd) {
+    if (int rc = check_batch_args(c, sources, nq)) return rc;
+    if (int rc = check_batch_args(c, targets, nt, "target")) return rc;
+    if (!(epsilon > 0)) return fail(c, FORA_E_ARG, "epsilon must be > 0");
+    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    if (!(rmax_scale > 0) || !std::isfinite(rmax_scale)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
+    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
+    double rmax = epsilon * sqrt(c->m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, as bippr_batch_impl
+    rmax *= rmax_scale;
+    const double omega = rmax * 3 * log(2.0 / pfail) / delta / epsilon / epsilon;
+    if (int rc = check_bwd_rmax(c, rmax)) return rc;
+    WalkCount w;
+    if (int rc = walk_count(c, omega, w)) return rc;
+    if (int rc = check_id_range(c, sources, nq)) return rc;
+    if (int rc = check_id_range(c, targets, nt, "target")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->bwd_ms = c->combine_ms = 0;
+    const double walk_ms0 = c->timing.walk_ms;
+    BwdRun r;
+    auto fill_stats = [&](int i, uint64_t sum) {
+        if (!stats) return;
+        fora_query_stats &o = stats[i];
+        memset(&o, 0, sizeof(o));
+        o.n_walks = w.W;
+        o.rmax_used = rmax;
+        o.ppr_sum_fix = sum;
+        o.dangling_source = is_dangling(c, sources[i]) ? 1 : 0;
+    };
+    if (nq == 0 || nt == 0) { // nothing to estimate: no push, no walk
+        for (int i = 0; i < nq; i++) fill_stats(i, 0);
+        fill_bwd_stats(c, r, 0, bwd, 0);
+        return FORA_OK;
+    }
+    // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
+    int rc = ensure_query_workspace(c, nq, 0);
+    if (rc) return rc;
+    const uint64_t T = (uint64_t)nt;
+    const int per = even_batch(nq, c->ws.B);
+    // the estimate block of a batch and its row sums
+    const size_t words = (size_t)per * (T + 1);
+    if (c->d_tgt_est.ensure(words) != hipSuccess || (est_out && c->d_tgt_f64.ensure((size_t)per * T) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(c, FORA_E_NOMEM, "no device memory for the estimate block");
+    }
+    if ((rc = ensure_reverse_csr(c))) return rc;
+    if ((rc = ensure_bwd_targets(c, T))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_bt, targets, T * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = bwd_count(c, (uint32_t)nt, rmax, r))) return rc; // (synchronises)
+    if (r.chunks.size() == 1 && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
+    std::vector<uint64_t> sums((size_t)per);
+    for (int b0 = 0; b0 < nq; b0 += per) {
+        const int nb = std::min(per, nq - b0);
+        const uint64_t cells = (uint64_t)nb * T;
+        const int hb = ev_begin(c, 5);
+        if ((rc = reset_batch_state(c, nb, sources + b0))) return rc;
+        HIPCHK(c, c->d_tgt_est.zero(c->stream, cells + (uint64_t)nb));
+        const Dev d = make_dev(c, nb, false);
+        launch_mc_walks(c, d, nb, w);
+        unsigned long long *const est = (unsigned long long *)c->d_tgt_est.get();
+        if ((rc = bippr_combine_targets(c, r, nb, T, est))) return rc;
+        {
+            const int h = ev_begin(c, 12);
+            hipLaunchKernelGGL(k_bippr_targets_finish, dim3((unsigned)std::min<uint64_t>((T + BLOCK - 1) / BLOCK, 64), (unsigned)nb), dim3(BLOCK), 0,
+                               c->stream, (const uint64_t *)c->d_tgt_est.get(), T, est_out ? c->d_tgt_f64.get() : nullptr, est + cells);
+            ev_end(c, h);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = close_batch(c, hb, "bippr targets"))) return rc;
+        c->timing.walks += w.W * (uint64_t)nb;
+        c->timing.walk_steps += *c->ws.h_steps_pin.get();
+        if (stats) {
+            HIPCHK(c, hipMemcpy(sums.data(), c->d_tgt_est.get() + cells, (size_t)nb * 8, hipMemcpyDeviceToHost));
+            for (int i = 0; i < nb; i++) fill_stats(b0 + i, sums[(size_t)i]);
+        }
+        if (est_fix_out) HIPCHK(c, hipMemcpy(est_fix_out + (uint64_t)b0 * T, c->d_tgt_est.get(), cells * 8, hipMemcpyDeviceToHost));
+        if (est_out) HIPCHK(c, hipMemcpy(est_out + (uint64_t)b0 * T, c->d_tgt_f64.get(), cells * 8, hipMemcpyDeviceToHost));
+    }
+    fill_bwd_stats(c, r, T, bwd, c->timing.walk_ms - walk_ms0);
+    return FORA_OK;
+}
+
 int fora_hip_montecarlo_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out, uint64_t *ppr_fix_out,
                               int k, int32_t *ids, double *scores, fora_query_stats *stats) {
     return montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats); // (no buckets, no push: nothing to retry)
@@ -3115,6 +3257,11 @@ int fora_hip_bwdpush_batch(fora_ctx *c, const int32_t *targets, int nt, double r
 int fora_hip_bippr_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                          uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
     return bippr_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, ppr_fix_out, k, ids, scores, stats, bwd);
+}
+
+int fora_hip_bippr_targets_batch(fora_ctx *c, const int32_t *sources, int nq, const int32_t *targets, int nt, double epsilon,
+                                 double rmax_scale, double *est_out, uint64_t *est_fix_out, fora_query_stats *stats, fora_bwd_stats *bwd) {
+    return bippr_targets_batch_impl(c, sources, nq, targets, nt, epsilon, rmax_scale, est_out, est_fix_out, stats, bwd);
 }
 
 int fora_hip_reset_timing(fora_ctx *c) {

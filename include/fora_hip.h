@@ -59,6 +59,28 @@
  * pops and ppr[i] = floor(c[i] / 4) (the reference's else branch, query.h:114-119).  A dangling source keeps the
  * reference's bias: every walk stops at s and no in-edge reaches s, so ppr = keep(2^60) at s and 0 elsewhere.  Double
  * outputs are value * 2^-60; sum(ppr) (ppr_sum_fix) is NOT conserved (an estimate, not a distribution).
+ * TARGETED BIPPR (fora_hip_bippr_targets_batch): the BIPPR estimate for nq sources and a caller's list of nt targets, with
+ * nt backward pushes per call instead of n.  Parameters, W and their bounds, the walk slab of a source and the use of the
+ * ctx's alpha and seed are those of BIPPR above; the ctx's FORA rmax / omega stay untouched.  est_fix_out[i*nt + j] is, bit
+ * for bit, the word fora_hip_bippr_batch writes to ppr_fix_out[i*n + targets[j]] for the same ctx, epsilon and rmax_scale:
+ * p_t[s] + sum_v floor(c_s[v] * r_t[v] / 2^62) at 2^60 with s = sources[i], t = targets[j]; est_out is that word * 2^-60.
+ * The batch size, the tier ("bwd_lds_cap"), the chunking ("bwd_chunk") and the way the combine splits its work
+ * ("tgt_lanes", "tgt_span") change no bit.  With few targets a small rmax_scale moves work from the walks (W shrinks in
+ * proportion) into the nt pushes.
+ *   - targets come in the caller's order, in any order; duplicate targets give duplicate columns, duplicate sources
+ *     duplicate rows; nt may exceed n.  A target without in-edges, or a dangling one, is an ordinary target.
+ *   - a dangling source gives keep(2^60) = floor(2^60 * alpha62 / 2^62) in the columns whose target is s and 0 elsewhere
+ *     (the bias above); rmax >= 1 gives floor(c_s[t] / 4).
+ *   - stats, per source: n_walks = W, rmax_used, dangling_source, ppr_sum_fix = the sum of that row's nt words (u64,
+ *     wrapping); every other field 0.  *bwd: targets = nt; pops, relax and entries summed over the nt pushes, a target
+ *     listed twice counted twice; global_targets, levels, chunks and the three times as for fora_hip_bippr_batch.
+ *     fora_timing: walks, walk_steps, walk_ms.
+ *   - nq == 0 or nt == 0: FORA_OK, nothing is written to the estimates, the stats of the sources are filled
+ *     (ppr_sum_fix 0), *bwd is all zero: no push and no walk runs.
+ *   - NULL ctx (answered without touching the GPU), NULL sources with nq > 0, NULL targets with nt > 0, an id outside
+ *     [0, n), epsilon <= 0, rmax_scale <= 0 or not finite, an (alpha, rmax) out of the fixed point's range: FORA_E_ARG.
+ *     No device memory for a batch's nb x nt estimate block: FORA_E_NOMEM, the ctx still usable.
+ *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched.
  * SPARSE RESULTS (fora_hip_query_sparse_batch, fora_hip_sparse_fetch, fora_hip_sparse_clear).  The query is
  * fora_hip_query_batch's: same push, same walks, same batching, same dangling-source fast path, same fora_query_stats,
  * same bits in the ppr slabs.  Only what leaves the device differs: a CSR over the call's sources, compacted on the GPU.
@@ -304,6 +326,15 @@ int fora_hip_fwdpush_batch(fora_ctx *ctx, const int32_t *sources, int nq, double
 int fora_hip_bippr_batch(fora_ctx *ctx, const int32_t *sources, int nq, double epsilon, double rmax_scale,
                          double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores,
                          fora_query_stats *stats, fora_bwd_stats *bwd);
+
+/* BiPPR for chosen (source, target) sets, the TARGETED BIPPR contract above: pi(s, t) for every s of `sources` and every t
+ * of `targets`, row-major nq x nt; est_out at 2^-60 / est_fix_out at 2^60, either may be NULL.  The nt backward pushes
+ * run once per call and are shared by every source (chunk by chunk, once per batch, when their entries outgrow the budget
+ * from free HBM).  Options "tgt_lanes" (combine: 0 lane = slot, 1 lane = entry, -1 by the call's shape) and "tgt_span"
+ * (entries per wave, 0: by the chunk's size) change no bit. */
+int fora_hip_bippr_targets_batch(fora_ctx *ctx, const int32_t *sources, int nq, const int32_t *targets, int nt,
+                                 double epsilon, double rmax_scale, double *est_out, uint64_t *est_fix_out,
+                                 fora_query_stats *stats, fora_bwd_stats *bwd);
 
 /* ---- stage hooks (same device code as the paths above, exposed for parity tests) */
 /* forward push only (forward_local_update_linear, algo.h:954-1018) */
