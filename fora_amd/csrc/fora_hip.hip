@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace fora;
@@ -135,6 +136,7 @@ public:
     hipError_t zero(hipStream_t s, size_t cnt) const { return fill(s, 0, 0, cnt); } // a prefix
     T *part(size_t i, size_t stride) const { return p ? p + i * stride : nullptr; } // i-th of equal parts (the parity pairs); null when empty
     T *get() const { return p; }
+    size_t size() const { return count; }
     explicit operator bool() const { return p != nullptr; }
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
@@ -182,6 +184,80 @@ struct Workspace {
     PinBuf<unsigned long long> h_steps_pin;
 };
 
+// The graph and everything derived from it (fora_hip_set_graph; the lazily built parts: their first user).  free_graph
+// assigns a fresh one.  A part that is rebuilt on its own is a struct of its own and is complete or empty: its builder
+// resets it, builds into a local value and moves that in after the last step has succeeded.
+struct RowSplit { // multi-pass graphs: row-sorted copy of col (empty: the rows are sorted as loaded), split offsets [n][npass + 1]
+    DevBuf<int32_t> d_col_push; DevBuf<uint32_t> d_row_split;
+    int pbins = 0;
+};
+struct HubCopy { // hub pre-aggregation (Dev::col_hub)
+    DevBuf<int32_t> d_col_hub; DevBuf<uint32_t> d_hub_node, d_hub_first;
+    uint32_t hubs = 0;
+    int shift = 0;         // bin shift the hub ranges were built for
+    bool for_team = false; // sized for the team path (4096 hubs, k_push_tail its only reader); set without a copy too
+};
+struct QuadCopies { // quad-padded copies for the wide bin kernel (Dev::col4); empty: not built
+    DevBuf<int32_t> d_col4, d_col_hub4; DevBuf<uint64_t> d_rowinfo4;
+    uint64_t quads = 0;
+};
+struct WalkCopy { // degree-grouped walk copy: the arrays dg points into; dg.colp == nullptr: none
+    DevBuf<uint32_t> d_perm, d_inv, d_colp, d_rec, d_invb; DevBuf<uint8_t> d_T;
+    WalkDG dg{};
+};
+struct TeamTables { // team push (fora_team.h): target copy of col, bucket offsets; for graphs of the narrow layout
+    DevBuf<uint32_t> d_colt, d_off, d_n2l, d_l2n, d_hubtgt;
+    DevBuf<uint32_t> d_rowq;  // [n] first quad of every node's row in d_colt
+    DevBuf<uint64_t> d_rowl;  // rows by local id
+    DevBuf<uint16_t> d_deg16;
+    uint32_t H = 0, T = 0, R = 0; // hubs, members per team, local ids per member; T == 0: this graph does not take the team path
+    uint64_t cap = 0;             // message slots per (team, parity)
+    bool checked = false, wanted = false; // ensure_team has looked at this graph with these options ...
+    uint32_t force = 0, hubs_opt = 0;     // ... the team_size / team_hubs options among them
+};
+struct ReverseCsr { DevBuf<int64_t> d_rin_ptr; DevBuf<int32_t> d_rin; }; // backward push (fora_bwd.h), built on first use
+struct GlobalTier { // backward push: [wgs][n] each, kept zero
+    DevBuf<uint64_t> d_gr, d_gp, d_gfy; DevBuf<uint32_t> d_gtag, d_glist, d_gfn;
+    uint32_t wgs = 0;
+};
+struct Graph {
+    int32_t n = 0;
+    int64_t m_attr = 0, nnz = 0;
+    std::vector<int64_t> h_row_ptr;
+    DevBuf<int64_t> d_row_ptr; DevBuf<int32_t> d_col; DevBuf<uint64_t> d_rowinfo; DevBuf<uint32_t> d_deg;
+    DevBuf<uint32_t> d_rp32, d_colp; // compact walk copy
+    uint32_t colbits = 0;
+    double dangling_frac = 0; // share of the nodes without out-edges
+    RowSplit split; HubCopy hub; QuadCopies quad; WalkCopy walk; TeamTables team; ReverseCsr rev; GlobalTier tier;
+};
+// Walk index (build_index / set_index; free_index, set_graph).
+struct Index {
+    DevBuf<int32_t> d_rw_idx; DevBuf<uint64_t> d_idx_off, d_idx_cnt;
+    uint64_t len = 0;
+    bool have = false;
+};
+// Backward push and BiPPR: buffers of their own, apart from the FORA workspace; grow-only, kept across graphs until destroy.
+struct BwdBufs {
+    DevBuf<int32_t> d_bt; // targets of the call
+    DevBuf<uint32_t> d_bcnt, d_bspill, d_blist; DevBuf<uint8_t> d_bflag; DevBuf<uint64_t> d_boff;
+    DevBuf<uint32_t> d_enode; DevBuf<uint64_t> d_ep, d_er; // entries of a chunk
+    DevBuf<unsigned long long> d_bstat;
+    // targeted BiPPR (fora_hip_bippr_targets_batch): the estimate block of a batch, slot-major [nb][nt] and then the nb row
+    // sums; its f64 copy.  nt has nothing to do with n, so these are no slabs of the workspace
+    DevBuf<uint64_t> d_tgt_est; DevBuf<double> d_tgt_f64;
+};
+// Sparse result of the last fora_hip_query_sparse_batch (free_sparse: sparse_clear, set_graph), apart from the workspace --
+// free_workspace (set_batch, set_option, a bucket retry) leaves it alone.
+struct SparseResult {
+    DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_fix; // entries of all rows, rows in the caller's order
+    uint64_t entries = 0;
+    bool valid = false; // a result is held (it may have no entries)
+    DevBuf<uint32_t> d_counts, d_tot; // per workgroup [slots][X] and per slot counts of the batch in progress
+    PinBuf<uint32_t> h_tot;           // pinned landing area of d_tot
+    DevBuf<int64_t> d_base;           // first entry of every live row of the call
+    DevBuf<double> d_stage;           // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
+};
+
 struct fora_ctx {
     int device = 0;
     Tunables opt_;
@@ -189,44 +265,9 @@ struct fora_ctx {
     std::string err;
     hipDeviceProp_t prop{};
 
-    // graph
-    int32_t n = 0;
-    int64_t m_attr = 0, nnz = 0;
-    std::vector<int64_t> h_row_ptr;
-    int64_t *d_row_ptr = nullptr;
-    int32_t *d_col = nullptr;
-    uint64_t *d_rowinfo = nullptr;
-    uint32_t *d_deg = nullptr;
-    uint32_t *d_rp32 = nullptr, *d_colp = nullptr;
-    int32_t *d_col_push = nullptr;  // row-sorted copy of col (multi-pass graphs whose rows are not sorted)
-    uint32_t *d_row_split = nullptr; // [n][npass + 1]
-    int split_pbins = 0;
-    uint32_t colbits = 0;
-    // degree-grouped walk copy (WalkDG): device arrays + the scalars of the struct; dg.colp == nullptr: none
-    int32_t *d_col_hub = nullptr;    // hub pre-aggregation (Dev::col_hub)
-    int32_t *d_col4 = nullptr, *d_col_hub4 = nullptr; // quad-padded copies for the wide bin kernel (Dev::col4); null: not built
-    uint64_t *d_rowinfo4 = nullptr;
-    uint64_t quads = 0;              // quads of the padded copies
-    uint32_t *d_hub_node = nullptr, *d_hub_first = nullptr;
-    uint32_t hubs = 0;
-    int hub_shift = 0;               // bin shift the hub ranges were built for
-    uint32_t *d_dg_perm = nullptr, *d_dg_inv = nullptr, *d_dg_colp = nullptr, *d_dg_rec = nullptr, *d_dg_invb = nullptr;
-    uint8_t *d_dg_T = nullptr;
-    WalkDG dg{};
-    // team push (fora_team.h): target copy of col, bucket offsets; built by set_graph for graphs of the narrow layout
-    uint32_t *d_colt = nullptr, *d_team_off = nullptr, *d_team_n2l = nullptr, *d_team_l2n = nullptr;
-    uint32_t *d_team_hubtgt = nullptr;
-    uint32_t team_H = 0, team_hubs_opt = 0;
+    Graph g;
     uint32_t team_rlog_cap = 0;      // entries of a member's reserve log per slot (Workspace::d_team_rlog_id)
-    uint64_t *d_team_rowl = nullptr; // rows by local id
-    uint16_t *d_team_deg16 = nullptr;
-    uint32_t *d_team_rowq = nullptr; // [n] first quad of every node's row in d_colt
-    uint32_t team_T = 0, team_R = 0, team_force = 0; // members per team, local ids per member; the team_size option they were built for
-    bool team_checked = false, team_wanted = false;  // ensure_team has looked at this graph with these options
-    double dangling_frac = 0;        // share of the nodes without out-edges
-    uint64_t team_cap = 0;           // message slots per (team, parity)
     bool team_dirty = false;         // a launch ended with an error flag: its reserve accumulators (TeamDev::rsvl) may not be zero
-    bool hub_for_team = false;       // the hub copy was sized for the team path (4096 hubs, k_push_tail its only reader)
     bool team_timeout_seen = false;  // the last device error was ERR_TEAM_TIMEOUT (with_retry runs the call again without the team push)
     int team_suspend = 0;            // calls left that push with the bucketed kernels after a team time-out
     uint64_t team_fallbacks = 0;     // calls re-run that way so far (fora_hip_get_option "team_fallbacks")
@@ -239,17 +280,13 @@ struct fora_ctx {
     int opt = 0;
     uint64_t seed = 0;
 
-    // index
-    int32_t *d_rw_idx = nullptr;
-    uint64_t *d_idx_off = nullptr, *d_idx_cnt = nullptr;
-    uint64_t idx_len = 0;
-    bool have_index = false;
+    Index ix;
 
     // workspace: its buffers (ws) and the plan they were sized for, which outlives them (a re-plan compares with it)
     Workspace ws;
     int batch_req = 0;
     uint64_t wl_cap = 0, seg_cap = 0, wit_cap = 0, segq_cap = 0;
-    unsigned long long *d_stamps = nullptr; // diagnostic builds (-DFORA_STAMPS)
+    DevBuf<unsigned long long> d_stamps; // diagnostic builds (-DFORA_STAMPS)
     // bucketed push (n <= MAX_BINS * BIN_SIZE)
     bool binned = false;
     int nbins = 0, pbins = 0; // bins of the graph; bins per pass (bucket-array stride)
@@ -276,40 +313,10 @@ struct fora_ctx {
     fora_timing timing{};
     int grid_blocks = 2048;
 
-    // backward push (fora_bwd.h): reverse CSR (built on first use, freed with the graph) and its own buffers, apart from
-    // the FORA workspace; grow-only
-    int64_t *d_rin_ptr = nullptr;
-    int32_t *d_rin = nullptr;
-    int32_t *d_bt = nullptr;         // targets of the call
-    uint32_t *d_bcnt = nullptr, *d_bspill = nullptr, *d_blist = nullptr;
-    uint8_t *d_bflag = nullptr;
-    uint64_t *d_boff = nullptr;
-    uint64_t bt_cap = 0;
-    uint32_t *d_enode = nullptr;     // entries of a chunk
-    uint64_t *d_ep = nullptr, *d_er = nullptr;
-    uint64_t e_cap = 0;
-    uint64_t *d_gr = nullptr, *d_gp = nullptr, *d_gfy = nullptr; // global tier: [g_wgs][n] each, kept zero
-    uint32_t *d_gtag = nullptr, *d_glist = nullptr, *d_gfn = nullptr;
-    uint32_t g_wgs = 0;
-    unsigned long long *d_bstat = nullptr;
+    BwdBufs bw;
     double bwd_ms = 0, combine_ms = 0; // event times of the call in progress (EvPair kinds 11, 12)
-    // targeted BiPPR (fora_hip_bippr_targets_batch): the estimate block of a batch, slot-major [nb][nt] and then the nb row
-    // sums; its f64 copy.  nt has nothing to do with n, so these are no slabs of the workspace; grow-only
-    DevBuf<uint64_t> d_tgt_est;
-    DevBuf<double> d_tgt_f64;
-
-    // sparse result of the last fora_hip_query_sparse_batch (free_sparse): its own buffers, apart from the workspace --
-    // free_workspace (set_batch, set_option, a bucket retry) leaves them alone
-    int32_t *d_sp_ids = nullptr;     // [sp_cap] entries of all rows, rows in the caller's order
-    uint64_t *d_sp_fix = nullptr;
-    uint64_t sp_cap = 0, sp_entries = 0;
-    bool sp_valid = false;           // a result is held (it may have no entries)
-    uint32_t *d_sp_counts = nullptr, *d_sp_tot = nullptr; // per workgroup [slots][X] and per slot counts of the batch in progress
-    int64_t *d_sp_base = nullptr;    // first entry of every live row of the call
-    uint32_t *h_sp_tot = nullptr;    // pinned landing area of d_sp_tot
-    uint64_t sp_counts_cap = 0, sp_slots_cap = 0, sp_base_cap = 0;
-    double *d_sp_stage = nullptr;    // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
-    double sp_compact_ms = 0;        // event time of the call in progress (EvPair kind 13)
+    SparseResult sp;
+    double sp_compact_ms = 0;          // event time of the call in progress (EvPair kind 13)
 };
 
 namespace {
@@ -327,42 +334,18 @@ int fail(fora_ctx *c, int code, const std::string &msg) {
                         std::string(#call) + ": " + hipGetErrorString(e_));                      \
     } while (0)
 
-template <typename T> void dfree(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-void free_graph(fora_ctx *c) {
-    dfree(c->d_row_ptr); dfree(c->d_col); dfree(c->d_rowinfo); dfree(c->d_deg); dfree(c->d_rp32); dfree(c->d_colp); dfree(c->d_col_push); dfree(c->d_row_split);
-    dfree(c->d_col_hub); dfree(c->d_hub_node); dfree(c->d_hub_first); c->hubs = 0;
-    dfree(c->d_col4); dfree(c->d_col_hub4); dfree(c->d_rowinfo4); c->quads = 0;
-    dfree(c->d_colt); dfree(c->d_team_rowq); dfree(c->d_team_off); dfree(c->d_team_n2l); dfree(c->d_team_l2n); dfree(c->d_team_deg16); dfree(c->d_team_rowl); dfree(c->d_team_hubtgt); c->team_H = 0; c->team_T = 0; c->team_R = 0; c->team_cap = 0; c->team_checked = false;
-    dfree(c->d_dg_perm); dfree(c->d_dg_inv); dfree(c->d_dg_colp); dfree(c->d_dg_rec); dfree(c->d_dg_T); dfree(c->d_dg_invb);
-    c->dg = WalkDG{};
-    dfree(c->d_rin_ptr); dfree(c->d_rin);
-    dfree(c->d_gr); dfree(c->d_gp); dfree(c->d_gfy); dfree(c->d_gtag); dfree(c->d_glist); dfree(c->d_gfn); c->g_wgs = 0; // (sized by n)
-    c->split_pbins = 0;
-    c->n = 0; c->nnz = 0;
-}
-void free_sparse(fora_ctx *c) {
-    dfree(c->d_sp_ids); dfree(c->d_sp_fix); dfree(c->d_sp_counts); dfree(c->d_sp_tot); dfree(c->d_sp_base); dfree(c->d_sp_stage);
-    if (c->h_sp_tot) (void)hipHostFree(c->h_sp_tot);
-    c->h_sp_tot = nullptr;
-    c->sp_cap = c->sp_entries = c->sp_counts_cap = c->sp_slots_cap = c->sp_base_cap = 0;
-    c->sp_valid = false;
-}
-void free_index(fora_ctx *c) {
-    dfree(c->d_rw_idx); dfree(c->d_idx_off); dfree(c->d_idx_cnt);
-    c->idx_len = 0; c->have_index = false;
-}
-void free_workspace(fora_ctx *c) { c->ws = Workspace{}; } // every buffer freed, every field back at its initialiser
+// every buffer of the group freed, every field of it back at its initialiser
+void free_graph(fora_ctx *c) { c->g = Graph{}; }
+void free_sparse(fora_ctx *c) { c->sp = SparseResult{}; }
+void free_index(fora_ctx *c) { c->ix = Index{}; }
+void free_workspace(fora_ctx *c) { c->ws = Workspace{}; }
 
 constexpr size_t N_COUNTERS = 2 * (size_t)(MAX_LEVELS + 2) + 2;
 // workgroups per slot of the kernels that sweep a slot's slab (walk allocation, top-k frontier / copy / count): ~32 k
 // workgroups per launch; one per 256 nodes (up to 1 M tiny workgroups at 1000 slots) cost k_walk_alloc 19 ms instead of
 // 8 per 3000 ws queries
 static uint32_t slab_grid_x(const fora_ctx *c, int nq) {
-    const int64_t nchunk = ((int64_t)c->n + BLOCK - 1) / BLOCK;
+    const int64_t nchunk = ((int64_t)c->g.n + BLOCK - 1) / BLOCK;
     int64_t x = std::min<int64_t>(1024, std::max<int64_t>(16, 32768 / std::max(1, nq)));
     if (c->opt_.ax > 0) x = c->opt_.ax;
     return (uint32_t)std::max<int64_t>(1, std::min<int64_t>(std::min(x, nchunk), 65535)); // (may be a grid's y extent: Dev::slot_major)
@@ -391,11 +374,11 @@ static int want_pass_bins(const fora_ctx *c, int nbins) {
 // narrow layout: <= MAX_BINS bins and the slice index fits the 4-byte push message
 static bool want_wide(const fora_ctx *c) {
     if (c->opt_.force_wide == 1) return true; // tests: exercise the wide layout on small graphs
-    return !((uint64_t)c->n <= (uint64_t)MAX_BINS * BIN_SIZE && (uint64_t)c->n <= (1ull << SEG_BITS));
+    return !((uint64_t)c->g.n <= (uint64_t)MAX_BINS * BIN_SIZE && (uint64_t)c->g.n <= (1ull << SEG_BITS));
 }
 // bits of a node id inside its bin: 8192-node bins in the narrow layout, 16384 in the wide ones
 static int bin_shift(const fora_ctx *c) { return want_wide(c) ? BIN_SHIFT_WIDE : BIN_SHIFT; }
-static uint64_t bins_of(const fora_ctx *c) { const int sh = bin_shift(c); return ((uint64_t)c->n + (1ull << sh) - 1) >> sh; }
+static uint64_t bins_of(const fora_ctx *c) { const int sh = bin_shift(c); return ((uint64_t)c->g.n + (1ull << sh) - 1) >> sh; }
 static uint32_t want_bk_cap(const fora_ctx *c) {
     if (c->opt_.bkcap > 0) return (uint32_t)c->opt_.bkcap;
     return 163840; // walk results: ~omega*rsum/nbins per bucket (ws: ~110 k)
@@ -405,7 +388,7 @@ static uint32_t want_bk_cap_wide(const fora_ctx *c) { // messages per (slot, bin
     // a dense level relaxes about every edge once: nnz / nbins messages per bin on average (Twitter-2010-sized: 289 k),
     // hubs' bins beyond that use the overflow list; 196608 covers the indexed walk results (~omega*rsum/nbins per bucket)
     const uint64_t nbins = bins_of(c);
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(196608, (uint64_t)(1.4 * (double)c->nnz / (double)std::max<uint64_t>(1, nbins))), 1u << 26);
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(196608, (uint64_t)(1.4 * (double)c->g.nnz / (double)std::max<uint64_t>(1, nbins))), 1u << 26);
 }
 
 struct WsPlan { uint64_t segs, wits, scratch, per_slot; int nbins, pbins; uint32_t bk_cap, sub; uint64_t segq_cap; bool binned; };
@@ -422,15 +405,15 @@ static uint32_t want_sub(const fora_ctx *c, int slots) {
 }
 static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
     WsPlan p{};
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     p.binned = want_binned(c);
-    p.segs = n + (uint64_t)c->nnz / PUSH_SEG + 64; // per slot
+    p.segs = n + (uint64_t)c->g.nnz / PUSH_SEG + 64; // per slot
     double walks = omega_hint > 0 ? omega_hint : 0;
     if (walks > 4e12) walks = 4e12;
     p.wits = n + n / WALK_SEG + (uint64_t)(walks / WALK_SEG) + 64;
     if (p.binned) {
         p.nbins = (int)bins_of(c);
-        p.pbins = want_wide(c) ? std::min(p.nbins, want_pass_bins(c, p.nbins)) : std::max(p.nbins, (int)c->dg.nbx); // narrow: the walk results in bucket order may need a bin more
+        p.pbins = want_wide(c) ? std::min(p.nbins, want_pass_bins(c, p.nbins)) : std::max(p.nbins, (int)c->g.walk.dg.nbx); // narrow: the walk results in bucket order may need a bin more
         p.sub = want_sub(c, slots);
         { // capacity of one sub-bucket: the bucket's capacity over its sub-buckets (+25 % for uneven producers); the
           // `bkcap` option (tests) sets it directly
@@ -446,7 +429,7 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
         p.segq_cap = n; // frontier positions
         p.scratch = (p.wits * sizeof(WalkItemP) + 95) / 96 * 96; // whole PushSeg (24 B) and WalkItemP (32 B) entries: `keepable` compares seg_cap * sizeof(PushSeg) with it
         p.per_slot = n * 8 * 2 + n * 4 * 2 + p.segq_cap * 8 * 2 + std::max<uint64_t>(262144, n / 8) * 12 + (uint64_t)p.pbins * p.sub * p.bk_cap * (want_wide(c) ? 8 : 12) + p.scratch +
-                     (c->opt_.defer > 0 ? n * 4 * 2 : 0) + n / 4 + 64 + (uint64_t)p.sub * c->hubs * 8; // + deferred lists and bitmaps, hub sums
+                     (c->opt_.defer > 0 ? n * 4 * 2 : 0) + n / 4 + 64 + (uint64_t)p.sub * c->g.hub.hubs * 8; // + deferred lists and bitmaps, hub sums
     } else {
         p.scratch = (std::max(p.segs * sizeof(PushSeg), p.wits * sizeof(WalkItemP)) + 95) / 96 * 96;
         p.per_slot = n * 8 * 4 + p.scratch;
@@ -458,24 +441,25 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
 // pass of k_pushq_bin reads only its own part of each popped row.  Built once per (graph, pass size).
 int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
     const int npass = pbins > 0 ? (nbins + pbins - 1) / pbins : 1;
-    if (npass <= 1 || c->opt_.no_split) { dfree(c->d_col_push); dfree(c->d_row_split); c->split_pbins = 0; return FORA_OK; }
-    if (c->d_row_split && c->split_pbins == pbins) return FORA_OK;
-    dfree(c->d_col_push); dfree(c->d_row_split);
-    const size_t n = (size_t)c->n, nnz = (size_t)c->nnz;
+    if (npass <= 1 || c->opt_.no_split) { c->g.split = RowSplit{}; return FORA_OK; }
+    if (c->g.split.d_row_split && c->g.split.pbins == pbins) return FORA_OK;
+    c->g.split = RowSplit{};
+    RowSplit rs;
+    const size_t n = (size_t)c->g.n, nnz = (size_t)c->g.nnz;
     std::vector<int32_t> col(std::max<size_t>(1, nnz));
-    if (nnz) HIPCHK(c, hipMemcpy(col.data(), c->d_col, nnz * 4, hipMemcpyDeviceToHost));
+    if (nnz) HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), nnz * 4, hipMemcpyDeviceToHost));
     bool sorted = true;
     for (size_t v = 0; v < n && sorted; v++)
-        for (int64_t e = c->h_row_ptr[v] + 1; e < c->h_row_ptr[v + 1]; e++)
+        for (int64_t e = c->g.h_row_ptr[v] + 1; e < c->g.h_row_ptr[v + 1]; e++)
             if (col[(size_t)e - 1] > col[(size_t)e]) { sorted = false; break; }
     if (!sorted) {
-        for (size_t v = 0; v < n; v++) std::sort(col.begin() + c->h_row_ptr[v], col.begin() + c->h_row_ptr[v + 1]);
-        HIPCHK(c, hipMalloc(&c->d_col_push, std::max<size_t>(1, nnz) * 4));
-        HIPCHK(c, hipMemcpy(c->d_col_push, col.data(), nnz * 4, hipMemcpyHostToDevice));
+        for (size_t v = 0; v < n; v++) std::sort(col.begin() + c->g.h_row_ptr[v], col.begin() + c->g.h_row_ptr[v + 1]);
+        HIPCHK(c, rs.d_col_push.alloc(std::max<size_t>(1, nnz)));
+        HIPCHK(c, hipMemcpy(rs.d_col_push.get(), col.data(), nnz * 4, hipMemcpyHostToDevice));
     }
     std::vector<uint32_t> split(n * (size_t)(npass + 1));
     for (size_t v = 0; v < n; v++) {
-        const int32_t *rb = col.data() + c->h_row_ptr[v], *re = col.data() + c->h_row_ptr[v + 1];
+        const int32_t *rb = col.data() + c->g.h_row_ptr[v], *re = col.data() + c->g.h_row_ptr[v + 1];
         uint32_t *sp = split.data() + v * (size_t)(npass + 1);
         sp[0] = 0;
         for (int p = 1; p < npass; p++) {
@@ -484,9 +468,10 @@ int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
         }
         sp[npass] = (uint32_t)(re - rb);
     }
-    HIPCHK(c, hipMalloc(&c->d_row_split, split.size() * 4));
-    HIPCHK(c, hipMemcpy(c->d_row_split, split.data(), split.size() * 4, hipMemcpyHostToDevice));
-    c->split_pbins = pbins;
+    HIPCHK(c, rs.d_row_split.alloc(split.size()));
+    HIPCHK(c, hipMemcpy(rs.d_row_split.get(), split.data(), split.size() * 4, hipMemcpyHostToDevice));
+    rs.pbins = pbins;
+    c->g.split = std::move(rs);
     return FORA_OK;
 }
 
@@ -495,21 +480,21 @@ int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
 // the `team` / `team_size` options ask for another shape.
 static bool want_team(const fora_ctx *c) {
     const bool on = c->opt_.team != 0; // (round 6: also for graphs with many dangling nodes -- 29.7 against 41.7 ms on the R-MAT ws variant, profiles/r06_dangling_team.txt)
-    return on && want_binned(c) && !want_wide(c) && c->nnz > 0 && c->nnz < (1ll << 32); // (rowl / colt / off index edges with 32 bits)
+    return on && want_binned(c) && !want_wide(c) && c->g.nnz > 0 && c->g.nnz < (1ll << 32); // (rowl / colt / off index edges with 32 bits)
 }
 int ensure_team(fora_ctx *c) {
     const bool want = want_team(c);
     const uint32_t force = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_size, 0), TEAM_MAX);
     const uint32_t hubs_opt = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_hubs, 0), 4096);
-    if (c->team_checked && want == c->team_wanted && (!want || (c->team_force == force && c->team_hubs_opt == hubs_opt))) return FORA_OK;
-    c->team_checked = true; c->team_wanted = want;
-    dfree(c->d_colt); dfree(c->d_team_rowq); dfree(c->d_team_off); dfree(c->d_team_n2l); dfree(c->d_team_l2n); dfree(c->d_team_deg16); dfree(c->d_team_rowl); dfree(c->d_team_hubtgt);
-    c->team_H = 0; c->team_hubs_opt = hubs_opt;
-    c->team_T = 0; c->team_R = 0; c->team_cap = 0; c->team_force = force;
-    if (!want) return FORA_OK;
-    const size_t n = (size_t)c->n, nnz = (size_t)c->nnz;
+    if (c->g.team.checked && want == c->g.team.wanted && (!want || (c->g.team.force == force && c->g.team.hubs_opt == hubs_opt))) return FORA_OK;
+    c->g.team = TeamTables{};
+    TeamTables tb;
+    tb.checked = true; tb.wanted = want; tb.force = force; tb.hubs_opt = hubs_opt;
+    const auto done = [&] { c->g.team = std::move(tb); return FORA_OK; }; // (with T == 0: looked at, not taken -- a complete state too)
+    if (!want) return done();
+    const size_t n = (size_t)c->g.n, nnz = (size_t)c->g.nnz;
     std::vector<int32_t> col(nnz);
-    HIPCHK(c, hipMemcpy(col.data(), c->d_col, nnz * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), nnz * 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> indeg(n, 0);
     for (size_t e = 0; e < nnz; e++) indeg[(size_t)col[e]]++;
     // members per team: the fewest (a power of two) whose LDS holds their share of the nodes that have in-edges
@@ -518,7 +503,7 @@ int ensure_team(fora_ctx *c) {
     std::vector<uint32_t> cntm;
     uint32_t R = 0;
     for (;; T *= 2) {
-        if (T > (uint32_t)TEAM_MAX || T > (uint32_t)std::max(1, c->prop.multiProcessorCount * TEAM_WGS_PER_CU)) return FORA_OK; // too large for the team path
+        if (T > (uint32_t)TEAM_MAX || T > (uint32_t)std::max(1, c->prop.multiProcessorCount * TEAM_WGS_PER_CU)) return done(); // too large for the team path
         cntm.assign(T, 0);
         for (size_t v = 0; v < n; v++) if (indeg[v]) cntm[(v >> 6) % T]++;
         R = (*std::max_element(cntm.begin(), cntm.end()) + 63) / 64 * 64;
@@ -534,13 +519,13 @@ int ensure_team(fora_ctx *c) {
         const uint32_t s = (uint32_t)((v >> 6) % T), l = cntm[s]++;
         n2l[v] = (s << TEAM_LBITS) | l;
         l2n[(size_t)s * R + l] = (uint32_t)v;
-        const int64_t dg = c->h_row_ptr[v + 1] - c->h_row_ptr[v];
+        const int64_t dg = c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v];
         deg16[(size_t)s * R + l] = (uint16_t)std::min<int64_t>(dg, 0xFFFF);
         rowl[(size_t)s * R + l] = (uint64_t)v | ((uint64_t)std::min<int64_t>(dg, 8191) << 19); // n <= 2^19; the row's first quad (<< 32) follows below
     }
     // rows of the team copy are padded to whole quads (four words, 16-byte aligned): a lane reads a quad with one load
     std::vector<uint32_t> rowq(n + 1, 0);
-    for (size_t v = 0; v < n; v++) rowq[v + 1] = rowq[v] + (uint32_t)((c->h_row_ptr[v + 1] - c->h_row_ptr[v] + 3) / 4); // (< 2^32: nnz < 2^32, want_team)
+    for (size_t v = 0; v < n; v++) rowq[v + 1] = rowq[v] + (uint32_t)((c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v] + 3) / 4); // (< 2^32: nnz < 2^32, want_team)
     for (size_t v = 0; v < n; v++)
         if (n2l[v] != TEAM_EMPTY) rowl[(size_t)(n2l[v] >> TEAM_LBITS) * R + (n2l[v] & TEAM_LMASK)] |= (uint64_t)rowq[v] << 32;
     // hubs: the nodes of largest in-degree (ties: lower id); their sums travel as one message per member and level
@@ -560,9 +545,9 @@ int ensure_team(fora_ctx *c) {
     std::vector<uint64_t> pair((size_t)T * T, 0);
     for (size_t v = 0; v < n; v++) {
         const uint32_t s = (uint32_t)((v >> 6) % T);
-        for (int64_t e = c->h_row_ptr[v]; e < c->h_row_ptr[v + 1]; e++) {
+        for (int64_t e = c->g.h_row_ptr[v]; e < c->g.h_row_ptr[v + 1]; e++) {
             const uint32_t t = (uint32_t)col[(size_t)e], w = n2l[t];
-            colt[(size_t)rowq[v] * 4 + (size_t)(e - c->h_row_ptr[v])] = hub_of[t] != TEAM_EMPTY ? (0x80000000u | hub_of[t]) : w;
+            colt[(size_t)rowq[v] * 4 + (size_t)(e - c->g.h_row_ptr[v])] = hub_of[t] != TEAM_EMPTY ? (0x80000000u | hub_of[t]) : w;
             if (hub_of[t] == TEAM_EMPTY) pair[(size_t)s * T + (w >> TEAM_LBITS)]++;
         }
     }
@@ -574,35 +559,35 @@ int ensure_team(fora_ctx *c) {
     for (size_t i = 0; i < (size_t)T * T; i++) {
         off[i] = (uint32_t)at;
         at += (pair[i] + 1 + 15) & ~15ull;
-        if (at >= (1ull << 32) || pair[i] + 1 >= (1ull << 24)) return FORA_OK; // 32-bit slots; a bucket's count is 24 bits of its barrier word: no team push for such a graph
+        if (at >= (1ull << 32) || pair[i] + 1 >= (1ull << 24)) return done(); // 32-bit slots; a bucket's count is 24 bits of its barrier word: no team push for such a graph
     }
     off[(size_t)T * T] = (uint32_t)at;
-    HIPCHK(c, hipMalloc(&c->d_colt, colt.size() * 4 + 16));
-    HIPCHK(c, hipMalloc(&c->d_team_rowq, n * 4));
-    HIPCHK(c, hipMemcpy(c->d_team_rowq, rowq.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc(&c->d_team_off, off.size() * 4));
-    HIPCHK(c, hipMalloc(&c->d_team_n2l, n * 4));
-    HIPCHK(c, hipMalloc(&c->d_team_l2n, l2n.size() * 4));
-    HIPCHK(c, hipMalloc(&c->d_team_deg16, deg16.size() * 2));
-    HIPCHK(c, hipMalloc(&c->d_team_hubtgt, hubtgt.size() * 4));
-    HIPCHK(c, hipMemcpy(c->d_team_hubtgt, hubtgt.data(), hubtgt.size() * 4, hipMemcpyHostToDevice));
-    c->team_H = Hn;
-    HIPCHK(c, hipMalloc(&c->d_team_rowl, rowl.size() * 8));
-    HIPCHK(c, hipMemcpy(c->d_team_rowl, rowl.data(), rowl.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_colt, colt.data(), colt.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_team_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_team_n2l, n2l.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_team_l2n, l2n.data(), l2n.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_team_deg16, deg16.data(), deg16.size() * 2, hipMemcpyHostToDevice));
-    c->team_T = T; c->team_R = R; c->team_cap = at;
-    return FORA_OK;
+    HIPCHK(c, tb.d_colt.alloc(colt.size() + 4));
+    HIPCHK(c, tb.d_rowq.alloc(n));
+    HIPCHK(c, hipMemcpy(tb.d_rowq.get(), rowq.data(), n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, tb.d_off.alloc(off.size()));
+    HIPCHK(c, tb.d_n2l.alloc(n));
+    HIPCHK(c, tb.d_l2n.alloc(l2n.size()));
+    HIPCHK(c, tb.d_deg16.alloc(deg16.size()));
+    HIPCHK(c, tb.d_hubtgt.alloc(hubtgt.size()));
+    HIPCHK(c, hipMemcpy(tb.d_hubtgt.get(), hubtgt.data(), hubtgt.size() * 4, hipMemcpyHostToDevice));
+    tb.H = Hn;
+    HIPCHK(c, tb.d_rowl.alloc(rowl.size()));
+    HIPCHK(c, hipMemcpy(tb.d_rowl.get(), rowl.data(), rowl.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.d_colt.get(), colt.data(), colt.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.d_off.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.d_n2l.get(), n2l.data(), n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.d_l2n.get(), l2n.data(), l2n.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(tb.d_deg16.get(), deg16.data(), deg16.size() * 2, hipMemcpyHostToDevice));
+    tb.T = T; tb.R = R; tb.cap = at;
+    return done();
 }
 
 // Team push: bytes per team of its workspace buffers with reserve logs of `logcap` entries -- message buffers + increment
 // tables (two parities), rsvl, reserve logs, words
 static uint64_t team_bytes_per_team(const fora_ctx *c, uint64_t logcap) {
-    const uint64_t T = c->team_T;
-    return 2 * c->team_cap * 4 + 3 * T * (c->team_R + 64 + c->team_H) * 8 + T * logcap * 10 + 2 * T * T * 8;
+    const uint64_t T = c->g.team.T;
+    return 2 * c->g.team.cap * 4 + 3 * T * (c->g.team.R + 64 + c->g.team.H) * 8 + T * logcap * 10 + 2 * T * T * 8;
 }
 // Words of Workspace::d_team_ctl: [0] next slot, [32] abort | from `sync`: the sync words | from `slot_seq`: the slot sequences
 struct TeamCtl { size_t sync, slot_seq, total; };
@@ -612,24 +597,24 @@ static TeamCtl team_ctl_layout(uint32_t nteams, int slots) {
 }
 int team_fits(fora_ctx *c);
 int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
     if (int rt = ensure_team(c)) return rt;
-    if (c->opt_.hubs < 0 && !want_wide(c) && c->hub_for_team != (want_team(c) && c->team_T != 0)) {
+    if (c->opt_.hubs < 0 && !want_wide(c) && c->g.hub.for_team != (want_team(c) && c->g.team.T != 0)) {
         // the `team` / `team_size` options changed which push this graph takes: the hub copy follows (see build_hub_copy)
-        std::vector<int32_t> col((size_t)std::max<int64_t>(1, c->nnz));
-        HIPCHK(c, hipMemcpy(col.data(), c->d_col, (size_t)c->nnz * 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> col((size_t)std::max<int64_t>(1, c->g.nnz));
+        HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), (size_t)c->g.nnz * 4, hipMemcpyDeviceToHost));
         free_workspace(c);
-        if (int rh = build_hub_copy(c, c->h_row_ptr.data(), col.data())) return rh;
+        if (int rh = build_hub_copy(c, c->g.h_row_ptr.data(), col.data())) return rh;
         if (int rq = build_quad_copies(c)) return rq;
     }
     WsPlan p = plan_workspace(c, omega_hint, 1024); // bytes per slot hardly depend on the slot count (sub-bucket rounding)
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     // an existing workspace with the same layout is kept if it has enough slots: as many as the call can use, or as
     // many as an automatic plan would get at most (1024)
     auto keepable = [&](int need) {
         if (c->ws.B <= 0 || c->ws.B < need) return false;
         const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B);
-        if ((c->team_T != 0) != bool(c->ws.d_team_msg)) return false;
+        if ((c->g.team.T != 0) != bool(c->ws.d_team_msg)) return false;
         return c->binned == pe.binned && c->pbins == pe.pbins && c->seg_cap * sizeof(PushSeg) >= (uint64_t)c->ws.B * pe.scratch &&
                c->wit_cap >= pe.wits && c->bk_cap == pe.bk_cap && c->sub == pe.sub;
     };
@@ -647,8 +632,8 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
         uint64_t budget = (uint64_t)(fr * 0.75);
-        if (c->team_T) { // the team push's own buffers (allocated below) come out of the same memory
-            const uint64_t T = c->team_T, nt = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
+        if (c->g.team.T) { // the team push's own buffers (allocated below) come out of the same memory
+            const uint64_t T = c->g.team.T, nt = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
             const uint64_t team_bytes = nt * team_bytes_per_team(c, 1u << 17);
             budget -= std::min<uint64_t>(budget / 2, team_bytes);
         }
@@ -684,9 +669,9 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         HIPCHK(c, w.d_dbm.alloc(2 * (size_t)B * c->dbm_words));
         HIPCHK(c, w.d_dflag.alloc(2 * (size_t)B * p.nbins));
         if (c->opt_.defer > 0) HIPCHK(c, w.d_dl.alloc(2 * slab)); // k_push_tail's deferred lists: only with the option (changing it re-plans the workspace)
-        if (c->hubs && c->hub_shift == bin_shift(c)) HIPCHK(c, w.d_hubsum.alloc((size_t)B * p.sub * c->hubs));
-        if (c->team_T) { // team push: message buffers of every team (two parities), bucket counts, control words
-            const uint32_t T = c->team_T;
+        if (c->g.hub.hubs && c->g.hub.shift == bin_shift(c)) HIPCHK(c, w.d_hubsum.alloc((size_t)B * p.sub * c->g.hub.hubs));
+        if (c->g.team.T) { // team push: message buffers of every team (two parities), bucket counts, control words
+            const uint32_t T = c->g.team.T;
             uint32_t nteams = std::max<uint32_t>(1, (uint32_t)c->prop.multiProcessorCount * TEAM_WGS_PER_CU / T);
             if (c->opt_.team_max > 0) nteams = std::min<uint32_t>(nteams, (uint32_t)c->opt_.team_max);
             size_t fr = 0, tot = 0;
@@ -696,9 +681,9 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
             while (c->team_rlog_cap > 1024 && team_bytes_per_team(c, c->team_rlog_cap) > fr / 4) c->team_rlog_cap /= 2;
             nteams = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nteams, (uint64_t)(fr / 2) / std::max<uint64_t>(1, team_bytes_per_team(c, c->team_rlog_cap))));
             const size_t members = (size_t)nteams * T;
-            HIPCHK(c, w.d_team_msg.alloc((size_t)nteams * 2 * c->team_cap + 16 + diag::TEAM_MSG_PROBE_WORDS)); // (probe words: 0 in the product build)
-            HIPCHK(c, w.d_team_inct.alloc(members * 2 * (c->team_R + 64 + c->team_H)));
-            HIPCHK(c, w.d_team_rsvl.alloc(members * c->team_R));
+            HIPCHK(c, w.d_team_msg.alloc((size_t)nteams * 2 * c->g.team.cap + 16 + diag::TEAM_MSG_PROBE_WORDS)); // (probe words: 0 in the product build)
+            HIPCHK(c, w.d_team_inct.alloc(members * 2 * (c->g.team.R + 64 + c->g.team.H)));
+            HIPCHK(c, w.d_team_rsvl.alloc(members * c->g.team.R));
             HIPCHK(c, w.d_team_rsvl.zero(c->stream)); // every slot leaves it zero again
             HIPCHK(c, w.d_team_rlog_id.alloc(members * c->team_rlog_cap));
             HIPCHK(c, w.d_team_rlog_val.alloc(members * c->team_rlog_cap));
@@ -738,11 +723,11 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     Dev d{};
     const Workspace &w = c->ws;
     const size_t B = (size_t)w.B, ctr = B * CSTRIDE;
-    d.n = c->n; d.nq = nq;
-    d.rowinfo = c->d_rowinfo; d.row_ptr = c->d_row_ptr; d.col = c->d_col; d.deg = c->d_deg;
-    d.rp32 = c->d_rp32; d.colp = c->d_colp; d.colbits = c->colbits;
-    d.colp32 = (uint64_t)c->nnz * c->colbits < (1ull << 32) ? 1 : 0;
-    d.dg = c->dg;
+    d.n = c->g.n; d.nq = nq;
+    d.rowinfo = c->g.d_rowinfo.get(); d.row_ptr = c->g.d_row_ptr.get(); d.col = c->g.d_col.get(); d.deg = c->g.d_deg.get();
+    d.rp32 = c->g.d_rp32.get(); d.colp = c->g.d_colp.get(); d.colbits = c->g.colbits;
+    d.colp32 = (uint64_t)c->g.nnz * c->g.colbits < (1ull << 32) ? 1 : 0;
+    d.dg = c->g.walk.dg;
     d.residue = w.d_residue.get(); d.ppr = w.d_ppr.get(); d.wl_cap = c->wl_cap;
     d.seg = (PushSeg *)w.d_scratch.get(); d.seg_cap = c->seg_cap;
     d.wit = (WalkItemP *)w.d_scratch.get(); d.wit_cap = c->wit_cap;
@@ -759,8 +744,8 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     d.alpha = c->alpha; d.omega = omega; d.opt = c->opt;
     d.binned = c->binned ? 1 : 0; d.nbins = c->nbins; d.wide = c->binned && want_wide(c) ? 1 : 0;
     d.pbins = c->pbins; d.bin_lo = 0; d.bin_cnt = std::min(c->pbins, c->nbins);
-    d.col_push = c->d_col_push ? c->d_col_push : c->d_col;
-    d.row_split = c->d_row_split;
+    d.col_push = c->g.split.d_col_push.get() ? c->g.split.d_col_push.get() : c->g.d_col.get();
+    d.row_split = c->g.split.d_row_split.get();
     d.npass = c->pbins > 0 ? (c->nbins + c->pbins - 1) / c->pbins : 1;
     d.pass = 0;
     d.acc_group = 1; // (set per launch: acc_grid)
@@ -776,21 +761,21 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
         d.fl_count[par] = w.d_fl_count.part(par, ctr); d.tile_ctr[par] = w.d_tile_ctr.part(par, ctr);
         d.ov_count[par] = w.d_ov_count.part(par, ctr); d.ov_bin[par] = w.d_ov_bin.part(par, B * c->nbins);
         d.dbm[par] = w.d_dbm.part(par, B * c->dbm_words); d.dflag[par] = w.d_dflag.part(par, B * c->nbins);
-        d.dl[par] = w.d_dl.part(par, B * c->n); d.wl[par] = w.d_wl[par].get();
+        d.dl[par] = w.d_dl.part(par, B * c->g.n); d.wl[par] = w.d_wl[par].get();
     }
     d.sw_count = w.d_sw.part(0, ctr); d.sw_done = w.d_sw.part(1, ctr);
     d.pop_next = 1;
-    d.stamps = c->d_stamps;
+    d.stamps = c->d_stamps.get();
     d.round_div = 0;
     d.rounds = 1; // the query / push entry points raise it (k_round_sweep); top-k, --balanced and power iteration drive their own rounds
-    if (c->binned && c->d_col_hub && w.d_hubsum && c->hub_shift == bin_shift(c) && c->pbins >= c->nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
-        d.col_hub = c->d_col_hub; d.hub_node = c->d_hub_node; d.hub_first = c->d_hub_first; d.hubsum = w.d_hubsum.get(); d.hubs = c->hubs;
+    if (c->binned && c->g.hub.d_col_hub && w.d_hubsum && c->g.hub.shift == bin_shift(c) && c->pbins >= c->nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
+        d.col_hub = c->g.hub.d_col_hub.get(); d.hub_node = c->g.hub.d_hub_node.get(); d.hub_first = c->g.hub.d_hub_first.get(); d.hubsum = w.d_hubsum.get(); d.hubs = c->g.hub.hubs;
         d.hub_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.hub_min, 1), 0x7FFFFFFF);
-        d.tail_hubs = c->opt_.tail_hubs != 0 && (size_t)c->hubs * 8 <= 40960 ? 1u : 0u; // (k_push_tail: 20 KiB of static LDS + the sums within 64 KiB)
+        d.tail_hubs = c->opt_.tail_hubs != 0 && (size_t)c->g.hub.hubs * 8 <= 40960 ? 1u : 0u; // (k_push_tail: 20 KiB of static LDS + the sums within 64 KiB)
     }
-    if (d.wide && c->d_col4 && !c->d_row_split && !c->d_col_push && c->opt_.quads != 0) { // one bin pass per level: the bin kernel reads quads
-        d.col4 = c->d_col4; d.rowinfo4 = c->d_rowinfo4;
-        d.col_hub4 = d.col_hub ? c->d_col_hub4 : nullptr;
+    if (d.wide && c->g.quad.d_col4 && !c->g.split.d_row_split && !c->g.split.d_col_push && c->opt_.quads != 0) { // one bin pass per level: the bin kernel reads quads
+        d.col4 = c->g.quad.d_col4.get(); d.rowinfo4 = c->g.quad.d_rowinfo4.get();
+        d.col_hub4 = d.col_hub ? c->g.quad.d_col_hub4.get() : nullptr;
         if (d.col_hub && !d.col_hub4) d.col4 = nullptr; // (no padded hub copy: edges one by one)
     }
     d.defer_k = TEST_PATHS && c->binned && w.d_dl ? (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer, 0), 8) : 0; // the direct path keeps plain levels
@@ -798,7 +783,7 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     d.dbm_words = c->dbm_words; d.segq_cap = c->segq_cap;
     d.ov_w = w.d_ov_w.get(); d.ov_inc = w.d_ov_inc.get(); d.ov_cap = c->ov_cap;
     d.bk_w = w.d_bk_w.get(); d.bk_inc = w.d_bk_inc.get(); d.bk_count = w.d_bk_count.get(); d.bk_cap = c->bk_cap; d.sub = c->sub;
-    if (with_idx) { d.rw_idx = c->d_rw_idx; d.idx_off = c->d_idx_off; d.idx_cnt = c->d_idx_cnt; }
+    if (with_idx) { d.rw_idx = c->ix.d_rw_idx.get(); d.idx_off = c->ix.d_idx_off.get(); d.idx_cnt = c->ix.d_idx_cnt.get(); }
     return d;
 }
 
@@ -863,7 +848,7 @@ int check_dev_err(fora_ctx *c) {
 // first checks of every batch call: graph and params present, `nq` ids behind a non-null pointer
 int check_batch_args(fora_ctx *c, const int32_t *ids, int nq, const char *what = "source") {
     if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
     if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first");
     if (nq < 0 || (nq && !ids)) return fail(c, FORA_E_ARG, std::string("bad ") + what + "s: negative count or null array");
     return FORA_OK;
@@ -871,16 +856,16 @@ int check_batch_args(fora_ctx *c, const int32_t *ids, int nq, const char *what =
 // ... and the last one, after the call's own arguments: every id in [0, n) (the ids are read only once all else passed)
 int check_id_range(fora_ctx *c, const int32_t *ids, int nq, const char *what = "source") {
     for (int i = 0; i < nq; i++)
-        if (ids[i] < 0 || ids[i] >= c->n) return fail(c, FORA_E_ARG, std::string(what) + " id out of range");
+        if (ids[i] < 0 || ids[i] >= c->g.n) return fail(c, FORA_E_ARG, std::string(what) + " id out of range");
     return FORA_OK;
 }
 // k of a top-k output: what k_topk_select takes
 int check_k(fora_ctx *c, int k) {
-    if (k < 1 || k > SEL_MAXK || k > c->n) return fail(c, FORA_E_ARG, "k out of range (1 .. min(1024, n))");
+    if (k < 1 || k > SEL_MAXK || k > c->g.n) return fail(c, FORA_E_ARG, "k out of range (1 .. min(1024, n))");
     return FORA_OK;
 }
 
-bool is_dangling(const fora_ctx *c, int32_t s) { return c->h_row_ptr[(size_t)s + 1] == c->h_row_ptr[(size_t)s]; }
+bool is_dangling(const fora_ctx *c, int32_t s) { return c->g.h_row_ptr[(size_t)s + 1] == c->g.h_row_ptr[(size_t)s]; }
 
 // a device (ids, scores) pair of B * k entries, grown on demand
 int grow_pair(fora_ctx *c, int k, DevBuf<int32_t> &ids, DevBuf<double> &scores) {
@@ -893,7 +878,7 @@ int grow_pair(fora_ctx *c, int k, DevBuf<int32_t> &ids, DevBuf<double> &scores) 
 // raw u64, and f64 at 2^-frac.
 int copy_slab_out(fora_ctx *c, const uint64_t *slab, uint64_t slot, uint64_t row, uint64_t cnt, uint64_t *fix_out, double *f64_out,
                   int frac) {
-    const uint64_t n = (uint64_t)c->n, at = row * n, from = slot * n, len = cnt * n;
+    const uint64_t n = (uint64_t)c->g.n, at = row * n, from = slot * n, len = cnt * n;
     if (fix_out) HIPCHK(c, hipMemcpy(fix_out + at, slab + from, len * 8, hipMemcpyDeviceToHost));
     if (f64_out) {
         // u64 and f64 have the same size: copy raw, convert in place on the host
@@ -1120,20 +1105,20 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
 // resident in LDS, k_push_tail finishes the slots.  Nothing here waits for the device.
 static bool use_team(const fora_ctx *c, const Dev &d) {
     // not after a time-out
-    return c->team_T && c->ws.d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
+    return c->g.team.T && c->ws.d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
            c->ws.team_fit != 0 && c->team_suspend == 0;
 }
 // Can every workgroup of a k_push_team launch be resident at once?  (Asked once per workspace; raises the kernel's
 // dynamic LDS limit on the way.)
 int team_fits(fora_ctx *c) {
-    if (c->ws.team_fit >= 0 || !c->team_T || !c->ws.d_team_msg) return FORA_OK;
-    const size_t lds = ((size_t)c->team_R + 1 + c->team_H) * 8;
+    if (c->ws.team_fit >= 0 || !c->g.team.T || !c->ws.d_team_msg) return FORA_OK;
+    const size_t lds = ((size_t)c->g.team.R + 1 + c->g.team.H) * 8;
     hipFuncAttributes fa{};
     HIPCHK(c, hipFuncGetAttributes(&fa, (const void *)k_push_team));
     HIPCHK(c, hipFuncSetAttribute((const void *)k_push_team, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(163840 - (int)fa.sharedSizeBytes)));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_push_team, TEAM_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-    const uint32_t grid = c->ws.team_n * c->team_T;
+    const uint32_t grid = c->ws.team_n * c->g.team.T;
     c->ws.team_fit = (uint64_t)per_cu * (uint64_t)c->prop.multiProcessorCount >= grid ? 1 : 0;
     int coop = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) != hipSuccess) { (void)hipGetLastError(); coop = 0; }
@@ -1141,13 +1126,13 @@ int team_fits(fora_ctx *c) {
     return FORA_OK;
 }
 int run_push_team(fora_ctx *c, const Dev &d) {
-    const uint32_t T = c->team_T, nteams = c->ws.team_n;
+    const uint32_t T = c->g.team.T, nteams = c->ws.team_n;
     TeamDev a{};
     a.n = d.n; a.nq = d.nq; a.rowinfo = d.rowinfo; a.row_ptr = d.row_ptr; a.deg = d.deg; a.src = d.src;
     a.residue = d.residue; a.ppr = d.ppr; a.fl0 = d.fl[0]; a.fl_count0 = d.fl_count[0]; a.inc_tab0 = d.inc_tab[0];
     a.segq_cap = d.segq_cap; a.qs = d.qs; a.err = d.err; a.afix = d.afix; a.t1 = d.t1;
-    a.T = T; a.R = c->team_R; a.nteams = nteams;
-    a.colt = c->d_colt; a.rowq = c->d_team_rowq; a.n2l = c->d_team_n2l; a.l2n = c->d_team_l2n; a.deg16 = c->d_team_deg16; a.rowl = c->d_team_rowl; a.rsvl = c->ws.d_team_rsvl.get(); a.rlog_id = c->ws.d_team_rlog_id.get(); a.rlog_val = c->ws.d_team_rlog_val.get(); a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->team_rlog_cap) : c->team_rlog_cap; a.H = c->team_H; a.hubtgt = c->d_team_hubtgt; a.off = c->d_team_off; a.msg = c->ws.d_team_msg.get(); a.inct = c->ws.d_team_inct.get(); a.cntw = c->ws.d_team_cnt.get();
+    a.T = T; a.R = c->g.team.R; a.nteams = nteams;
+    a.colt = c->g.team.d_colt.get(); a.rowq = c->g.team.d_rowq.get(); a.n2l = c->g.team.d_n2l.get(); a.l2n = c->g.team.d_l2n.get(); a.deg16 = c->g.team.d_deg16.get(); a.rowl = c->g.team.d_rowl.get(); a.rsvl = c->ws.d_team_rsvl.get(); a.rlog_id = c->ws.d_team_rlog_id.get(); a.rlog_val = c->ws.d_team_rlog_val.get(); a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->team_rlog_cap) : c->team_rlog_cap; a.H = c->g.team.H; a.hubtgt = c->g.team.d_hubtgt.get(); a.off = c->g.team.d_off.get(); a.msg = c->ws.d_team_msg.get(); a.inct = c->ws.d_team_inct.get(); a.cntw = c->ws.d_team_cnt.get();
     const Workspace &w = c->ws;
     const TeamCtl ctl = team_ctl_layout(nteams, w.B);
     a.ctl = w.d_team_ctl.get(); a.sync = (unsigned long long *)(a.ctl + ctl.sync); a.slot_seq = a.ctl + ctl.slot_seq;
@@ -1158,7 +1143,7 @@ int run_push_team(fora_ctx *c, const Dev &d) {
     a.tail_always = c->opt_.tail_always == 1 ? 1u : 0u;
     const uint32_t grid = nteams * T;
     a.xcd = (c->opt_.team_xcd >= 1 && grid % 8 == 0 && (grid / 8) % T == 0) ? (uint32_t)c->opt_.team_xcd : 0u;
-    a.stamps = c->d_stamps;
+    a.stamps = c->d_stamps.get();
     a.abort_level = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_abort_level, 0), 1 << 20);
     a.timeout_ticks = (uint64_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_timeout_ms, 0), 60000) * 100000ull; // (100 MHz wall clock)
     const size_t lds = ((size_t)a.R + 1 + a.H) * 8;
@@ -1196,7 +1181,7 @@ int run_push_team(fora_ctx *c, const Dev &d) {
 // ties keep resolving to the lowest ids) into the push's frontier / increment buffers, which are idle here.
 constexpr unsigned NZ_X = 1024;
 int launch_select(fora_ctx *c, const Dev &ds, int nb, int k, int32_t *ids, double *scores, int raw, const double *h_thr = nullptr) {
-    bool compact = c->binned && c->n >= (1 << 20);
+    bool compact = c->binned && c->g.n >= (1 << 20);
     if (c->opt_.select_compact >= 0) compact = c->binned && c->opt_.select_compact == 1; // tests: force / forbid the compacted form
     if (!compact) {
         hipLaunchKernelGGL(k_topk_select, dim3(nb), dim3(SEL_THREADS), 0, c->stream, ds, k, ids, scores, raw,
@@ -1204,8 +1189,8 @@ int launch_select(fora_ctx *c, const Dev &ds, int nb, int k, int32_t *ids, doubl
         return FORA_OK;
     }
     HIPCHK(c, c->ws.d_nz_counts.ensure((size_t)c->ws.B * (NZ_X + 1)));
-    const unsigned X = (unsigned)std::min<uint64_t>(NZ_X, ((uint64_t)c->n + 4095) / 4096);
-    const uint32_t R = (uint32_t)(((uint64_t)c->n + X - 1) / X);
+    const unsigned X = (unsigned)std::min<uint64_t>(NZ_X, ((uint64_t)c->g.n + 4095) / 4096);
+    const uint32_t R = (uint32_t)(((uint64_t)c->g.n + X - 1) / X);
     uint32_t *ccount = c->ws.d_nz_counts.get() + (size_t)c->ws.B * NZ_X;
     const double *thr = nullptr; // per-slot lower limit of the entries worth compacting (see k_nz_count)
     if (h_thr && !raw) {
@@ -1239,7 +1224,7 @@ int reset_binned_counters(fora_ctx *c) {
 }
 
 int reset_batch_state(fora_ctx *c, int nq, const int32_t *sources) {
-    const uint64_t slabs = (uint64_t)nq * c->n; // the slabs of the batch's slots only
+    const uint64_t slabs = (uint64_t)nq * c->g.n; // the slabs of the batch's slots only
     int h = ev_begin(c, 4);
     HIPCHK(c, c->ws.d_residue.zero(c->stream, slabs));
     HIPCHK(c, c->ws.d_ppr.zero(c->stream, slabs));
@@ -1277,69 +1262,52 @@ struct SparseRun {
 
 // per-call buffers of the two passes: `slots` slots per batch, `live` live rows in all
 int sparse_prepare(fora_ctx *c, SparseRun &sp, int nq, int slots, int live) {
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     sp.R = (uint32_t)std::max<uint64_t>(8 * SP_TILE, ((n + 1023) / 1024 + SP_TILE - 1) / SP_TILE * SP_TILE); // at most 1024 workgroups per slot
     sp.X = (uint32_t)((n + sp.R - 1) / sp.R);
     sp.row_ptr.assign((size_t)nq + 1, 0);
-    const uint64_t counts = (uint64_t)slots * sp.X;
-    if (counts > c->sp_counts_cap) {
-        dfree(c->d_sp_counts); c->sp_counts_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_sp_counts, counts * 4));
-        c->sp_counts_cap = counts;
-    }
-    if ((uint64_t)slots > c->sp_slots_cap) {
-        dfree(c->d_sp_tot); c->sp_slots_cap = 0;
-        if (c->h_sp_tot) (void)hipHostFree(c->h_sp_tot);
-        c->h_sp_tot = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_sp_tot, (size_t)slots * 4));
-        HIPCHK(c, hipHostMalloc((void **)&c->h_sp_tot, (size_t)slots * 4));
-        c->sp_slots_cap = (uint64_t)slots;
-    }
-    if ((uint64_t)live > c->sp_base_cap) {
-        dfree(c->d_sp_base); c->sp_base_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_sp_base, (size_t)live * 8));
-        c->sp_base_cap = (uint64_t)live;
-    }
+    HIPCHK(c, c->sp.d_counts.ensure((size_t)slots * sp.X));
+    HIPCHK(c, c->sp.d_tot.ensure((size_t)slots));
+    HIPCHK(c, c->sp.h_tot.ensure((size_t)slots));
+    HIPCHK(c, c->sp.d_base.ensure((size_t)live));
     return FORA_OK;
 }
 
 // room for `need` entries, the first `keep` of them already written; rows_done of rows_all rows are placed (what the
 // rest will take is guessed from them, and asked for again if the guess was short)
 int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done, uint64_t rows_all) {
-    if (need <= c->sp_cap) return FORA_OK;
+    if (need <= c->sp.d_ids.size()) return FORA_OK;
     const uint64_t guess = rows_done ? (uint64_t)((double)need / (double)rows_done * (double)rows_all * 1.125) + 1024 : need;
-    int32_t *ids = nullptr;
-    uint64_t *fix = nullptr;
+    DevBuf<int32_t> ids; DevBuf<uint64_t> fix;
     uint64_t cap = std::max<uint64_t>({need, guess, 1});
     for (;; cap = need) { // (a guess that does not fit is no reason to fail)
-        if (hipMalloc(&ids, cap * 4) == hipSuccess && hipMalloc(&fix, cap * 8) == hipSuccess) break;
+        if (ids.alloc(cap) == hipSuccess && fix.alloc(cap) == hipSuccess) break;
         (void)hipGetLastError();
-        dfree(ids); dfree(fix);
+        ids.reset(); fix.reset();
         if (cap == need) {
             (void)hipStreamSynchronize(c->stream);
             free_sparse(c);
             return fail(c, FORA_E_NOMEM, "no device memory for the sparse result");
         }
     }
-    keep = std::min(keep, c->sp_cap);
+    keep = std::min<uint64_t>(keep, c->sp.d_ids.size());
     if (keep) {
-        HIPCHK(c, hipMemcpyAsync(ids, c->d_sp_ids, keep * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(fix, c->d_sp_fix, keep * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ids.get(), c->sp.d_ids.get(), keep * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(fix.get(), c->sp.d_fix.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    dfree(c->d_sp_ids); dfree(c->d_sp_fix);
-    c->d_sp_ids = ids; c->d_sp_fix = fix; c->sp_cap = cap;
+    c->sp.d_ids = std::move(ids); c->sp.d_fix = std::move(fix);
     return FORA_OK;
 }
 
 // count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out)
 int sparse_count(fora_ctx *c, const SparseRun &sp, int nb) {
-    HIPCHK(c, hipMemsetAsync(c->d_sp_tot, 0, (size_t)nb * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->sp.d_tot.get(), 0, (size_t)nb * 4, c->stream));
     const int h = ev_begin(c, 13);
-    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->n, sp.thr, sp.R,
-                       c->d_sp_counts, c->d_sp_tot);
+    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
+                       c->sp.d_counts.get(), c->sp.d_tot.get());
     ev_end(c, h);
-    HIPCHK(c, hipMemcpyAsync(c->h_sp_tot, c->d_sp_tot, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sp.h_tot.get(), c->sp.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     return FORA_OK;
 }
 
@@ -1362,17 +1330,17 @@ int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, con
     for (int i = 0; i < nb; i++) {
         sparse_skip_dangling(sp, sources, at[i]);
         sp.row_ptr[(size_t)at[i]] = base[(size_t)i] = (int64_t)sp.cur;
-        sp.cur += c->h_sp_tot[i];
-        sp.max_row = std::max<uint64_t>(sp.max_row, c->h_sp_tot[i]);
+        sp.cur += c->sp.h_tot.get()[i];
+        sp.max_row = std::max<uint64_t>(sp.max_row, c->sp.h_tot.get()[i]);
         sp.next_row = at[i] + 1;
     }
     sp.batches++;
     if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? keep : 0, (uint64_t)sp.next_row, (uint64_t)nq)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_sp_base + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->sp.d_base.get() + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
     const int h = ev_begin(c, 13);
-    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->n, sp.thr, sp.R,
-                       (const uint32_t *)c->d_sp_counts, (const int64_t *)(c->d_sp_base + sp.live_done), c->d_sp_ids, c->d_sp_fix, c->sp_cap);
+    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
+                       (const uint32_t *)c->sp.d_counts.get(), (const int64_t *)(c->sp.d_base.get() + sp.live_done), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
     ev_end(c, h);
     sp.live_done += nb;
     return FORA_OK;
@@ -1391,14 +1359,14 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, in
         HIPCHK(c, hipMemcpyAsync(at.get(), sp.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(src.get(), sp.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_sparse_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd,
-                           (const int64_t *)at.get(), (const int32_t *)src.get(), c->d_sp_ids, c->d_sp_fix, c->sp_cap);
+                           (const int64_t *)at.get(), (const int32_t *)src.get(), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse result: ") + hipGetErrorString(e));
     ev_collect(c);
-    c->sp_entries = sp.cur;
-    c->sp_valid = true;
+    c->sp.entries = sp.cur;
+    c->sp.valid = true;
     memcpy(row_ptr, sp.row_ptr.data(), ((size_t)nq + 1) * 8);
     if (out) {
         memset(out, 0, sizeof(*out));
@@ -1546,7 +1514,7 @@ int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, 
         launch_walks(c, d, nq, with_idx, 0u, c->opt ? 1 : 0);
     }
     {
-        const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
+        const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 64);
         h = ev_begin(c, 4);
         hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, d);
         ev_end(c, h);
@@ -1587,10 +1555,10 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
                  uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats, int topk = 0, int32_t *ids = nullptr,
                  double *scores = nullptr, SparseRun *sp = nullptr) {
     if (int rc = check_batch_args(c, sources, nq)) return rc;
-    if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
+    if (with_idx && !c->ix.have) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = check_id_range(c, sources, nq)) return rc;
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     // A dangling source is its own whole answer (algo.h:961-965: reserve[s] = 1, rsum = 0, no push, no walks): it is
     // written here and never takes a slot.  (On the R-MAT variant with 52 % dangling nodes half of a batch's slots were
     // such sources, and every level launch and the tail kernel carried their empty workgroups: push of 1000 queries
@@ -1659,7 +1627,7 @@ int next_cursor_epoch(fora_ctx *c) {
 // slabs of the drivers: ppr2 (the rounds' ppr), index cursors, active marks, per-slot counts; the (ids, scores) pair
 int ensure_topk_slabs(fora_ctx *c, int k) {
     Workspace &w = c->ws;
-    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->n;
+    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->g.n;
     HIPCHK(c, w.d_ppr2.ensure(slab));
     if (!w.d_cursor) w.cursor_epoch = 0; // new slabs hold no valid word: next_cursor_epoch clears them
     HIPCHK(c, w.d_cursor.ensure(slab));
@@ -1691,7 +1659,7 @@ int topk_batch_start(fora_ctx *c, TopkBatch &tb, const int32_t *sources, int nb,
         if (is_dangling(c, sources[i])) { tb.active[i] = 0; tb.inactive[i] = 1; any_inactive = true; }
     if (any_inactive) {
         HIPCHK(c, hipMemcpyAsync(c->ws.d_active.get(), tb.inactive.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(), (const uint8_t *)c->ws.d_active.get());
+        hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->g.n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(), (const uint8_t *)c->ws.d_active.get());
     }
     return FORA_OK;
 }
@@ -1714,7 +1682,7 @@ int topk_round(fora_ctx *c, TopkBatch &tb, int nb, bool with_idx, int round, dou
     ev_end(c, h);
     if (int rc = run_push_levels(c, d, nullptr, 0, true)) return rc;
     h = ev_begin(c, 4);
-    hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(),
+    hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->g.n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(),
                        (const uint8_t *)c->ws.d_active.get());
     ev_end(c, h);
     dw = d;
@@ -1824,8 +1792,8 @@ int fora_hip_create(int device, fora_ctx **out) {
         delete c;
         return FORA_E_NOGPU;
     }
-    if (hipMalloc(&c->d_stamps, 32 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(c->d_stamps, 0, 32 * sizeof(unsigned long long)) != hipSuccess) {
+    if (c->d_stamps.alloc(32) != hipSuccess || hipMemset(c->d_stamps.get(), 0, 32 * sizeof(unsigned long long)) != hipSuccess) {
+        c->d_stamps.reset();
         (void)hipStreamDestroy(c->stream);
         delete c;
         return FORA_E_NOMEM;
@@ -1845,10 +1813,8 @@ void fora_hip_destroy(fora_ctx *c) {
     free_index(c);
     free_graph(c);
     free_sparse(c);
-    dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
-    dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er); dfree(c->d_bstat);
-    c->d_tgt_est.reset(); c->d_tgt_f64.reset();
-    dfree(c->d_stamps);
+    c->bw = BwdBufs{};
+    c->d_stamps.reset();
     for (auto &p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1869,9 +1835,9 @@ int fora_hip_device_info(fora_ctx *c, char *arch, int arch_len, int *cus, uint64
 // id order so that the hubs of a bin are a contiguous range, and a copy of col that names them by that number.
 static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *col) {
     (void)row_ptr;
-    dfree(c->d_col_hub); dfree(c->d_hub_node); dfree(c->d_hub_first); c->hubs = 0; // (a rebuild: ensure_workspace)
-    const int32_t n = c->n;
-    const int64_t nnz = c->nnz;
+    c->g.hub = HubCopy{}; // (a rebuild: ensure_workspace)
+    const int32_t n = c->g.n;
+    const int64_t nnz = c->g.nnz;
     const int64_t wide_auto = nnz <= (1ll << 28) ? 2048 : 0;
     // the hub sums live in the bin kernel's dynamic LDS next to its static arrays: 48 KB in the narrow and the 512-thread
     // wide kernel, 32 KB in the 1024-thread one (its stage of 12 edges per thread takes 122 of the 160 KB)
@@ -1879,8 +1845,8 @@ static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *co
     const int64_t lds_cap = !want_wide(c) ? 6144 : nbins_all > (uint64_t)MAX_BINS_WIDE ? 4096 : 6144;
     // 4096 only when this graph really takes the team path (ensure_team has built its tables: then the bin kernel never runs
     // and k_push_tail is the copy's only reader); a graph the team path rejects pushes with the bin kernel, which wants 1024
-    const bool for_team = want_team(c) && c->team_T != 0;
-    c->hub_for_team = for_team;
+    const bool for_team = want_team(c) && c->g.team.T != 0;
+    c->g.hub.for_team = for_team; // (no copy, for this path: a complete state too -- also after a failure below: ensure_workspace does not try again, the graph pushes without hub sums until the next set_graph, as before)
     const int64_t narrow_auto = for_team ? 4096 : 1024;
     const int64_t want = std::min<int64_t>(std::max<int64_t>(want_wide(c) ? (c->opt_.hubs_wide < 0 ? wide_auto : c->opt_.hubs_wide) : (c->opt_.hubs < 0 ? narrow_auto : c->opt_.hubs), 0), lds_cap);
     if (want == 0 || nnz == 0 || c->opt_.direct == 1) return FORA_OK;
@@ -1905,32 +1871,35 @@ static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *co
         const uint32_t h = hub_of[(size_t)col[e]];
         ch[(size_t)e] = h == 0xFFFFFFFFu ? col[e] : (int32_t)(0x80000000u | h);
     }
-    HIPCHK(c, hipMalloc(&c->d_col_hub, (size_t)nnz * 4));
-    HIPCHK(c, hipMalloc(&c->d_hub_node, H * 4));
-    HIPCHK(c, hipMalloc(&c->d_hub_first, first.size() * 4));
-    HIPCHK(c, hipMemcpy(c->d_col_hub, ch.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_hub_node, hub_node.data(), H * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_hub_first, first.data(), first.size() * 4, hipMemcpyHostToDevice));
-    c->hubs = (uint32_t)H;
-    c->hub_shift = bin_shift(c);
+    HubCopy hc;
+    HIPCHK(c, hc.d_col_hub.alloc((size_t)nnz));
+    HIPCHK(c, hc.d_hub_node.alloc(H));
+    HIPCHK(c, hc.d_hub_first.alloc(first.size()));
+    HIPCHK(c, hipMemcpy(hc.d_col_hub.get(), ch.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(hc.d_hub_node.get(), hub_node.data(), H * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(hc.d_hub_first.get(), first.data(), first.size() * 4, hipMemcpyHostToDevice));
+    hc.hubs = (uint32_t)H;
+    hc.shift = bin_shift(c);
+    hc.for_team = for_team;
+    c->g.hub = std::move(hc);
     return FORA_OK;
 }
 
 // Quad-padded copies of col (and of the hub copy) for the wide bin kernel (Dev::col4), built on the device from what
 // set_graph has uploaded; only for graphs that run the wide layout in one bin pass per level.
 static int build_quad_copies(fora_ctx *c) {
-    dfree(c->d_col4); dfree(c->d_col_hub4); dfree(c->d_rowinfo4); c->quads = 0;
-    if (!want_binned(c) || !want_wide(c) || c->nnz == 0 || c->opt_.quads == 0) return FORA_OK;
+    c->g.quad = QuadCopies{};
+    if (!want_binned(c) || !want_wide(c) || c->g.nnz == 0 || c->opt_.quads == 0) return FORA_OK;
     const uint64_t nbins_all = bins_of(c);
     if ((int64_t)nbins_all > (int64_t)want_pass_bins(c, (int)nbins_all)) return FORA_OK; // several passes per level: pass-split rows, edge by edge
-    const size_t n = (size_t)c->n;
+    const size_t n = (size_t)c->g.n;
     std::vector<uint64_t> ri4(n);
     uint64_t q = 0;
     // (Round 6, measured and dropped: rows placed so that each touches as few 64-byte lines as its length allows -- a row that would
     // straddle one line more than ceil(quads / 4) started at the next line.  LJ-sized bin kernel 315.4 / 314.8 ms against 320.7 / 314.5
     // back to back, Twitter-2010-sized 593.6 / 592.9 against 594.5 / 585.6: what a quad load costs is not the lines its row touches.)
     for (size_t v = 0; v < n; v++) {
-        const uint64_t dg = (uint64_t)(c->h_row_ptr[v + 1] - c->h_row_ptr[v]);
+        const uint64_t dg = (uint64_t)(c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v]);
         ri4[v] = (q << 24) | std::min<uint64_t>(dg, DEG_SAT);
         q += (dg + 3) / 4;
     }
@@ -1938,32 +1907,35 @@ static int build_quad_copies(fora_ctx *c) {
     // The copies are an optimisation (make_dev falls back to single-edge reads without them): they must never make
     // set_graph fail.  Not built when they would take more than a quarter of the free memory (the slots need it more);
     // an allocation that fails all the same leaves "no quads", not an error.
-    const uint64_t qbytes = std::max<uint64_t>(1, q) * 16, need = n * 8 + qbytes * (c->d_col_hub ? 2 : 1);
+    const uint64_t qbytes = std::max<uint64_t>(1, q) * 16, need = n * 8 + qbytes * (c->g.hub.d_col_hub ? 2 : 1);
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
     if (need > fr / 4) return FORA_OK;
-    auto give_up = [&]() { (void)hipGetLastError(); dfree(c->d_col4); dfree(c->d_col_hub4); dfree(c->d_rowinfo4); c->quads = 0; return FORA_OK; };
-    if (hipMalloc(&c->d_rowinfo4, n * 8) != hipSuccess) return give_up();
-    HIPCHK(c, hipMemcpy(c->d_rowinfo4, ri4.data(), n * 8, hipMemcpyHostToDevice));
-    if (hipMalloc(&c->d_col4, qbytes) != hipSuccess) return give_up();
+    QuadCopies qc;
+    auto give_up = [&]() { (void)hipGetLastError(); return FORA_OK; };
+    if (qc.d_rowinfo4.alloc(n) != hipSuccess) return give_up();
+    HIPCHK(c, hipMemcpy(qc.d_rowinfo4.get(), ri4.data(), n * 8, hipMemcpyHostToDevice));
+    if (qc.d_col4.alloc(qbytes / 4) != hipSuccess) return give_up();
     const unsigned grid = (unsigned)std::min<size_t>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->n, (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col,
-                       (const uint64_t *)c->d_rowinfo4, c->d_col4);
-    if (c->d_col_hub) {
-        if (hipMalloc(&c->d_col_hub4, qbytes) != hipSuccess) return give_up();
-        hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->n, (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col_hub,
-                           (const uint64_t *)c->d_rowinfo4, c->d_col_hub4);
+    hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.d_col.get(),
+                       (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col4.get());
+    if (c->g.hub.d_col_hub) {
+        if (qc.d_col_hub4.alloc(qbytes / 4) != hipSuccess) return give_up();
+        hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.hub.d_col_hub.get(),
+                           (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col_hub4.get());
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->quads = q;
+    qc.quads = q;
+    c->g.quad = std::move(qc);
     return FORA_OK;
 }
 
 // Degree-grouped walk copy (WalkDG, fora_kernels.h) of graphs that run the narrow layout: H hub records + at most 255
 // out-degree classes whose tables fit a workgroup's LDS share.  Graphs that do not qualify keep k_walk_online.
 static int build_walk_dg(fora_ctx *c, const int64_t *row_ptr, const int32_t *col) {
-    const int32_t n = c->n;
-    const int64_t nnz = c->nnz;
+    c->g.walk = WalkCopy{};
+    const int32_t n = c->g.n;
+    const int64_t nnz = c->g.nnz;
     if (c->opt_.walk_dg == 0 || c->opt_.no_compact == 1 || nnz >= (1ll << 31) || nnz == 0) return FORA_OK;
     if (!((uint64_t)n <= (uint64_t)MAX_BINS * BIN_SIZE && (uint64_t)n <= (1ull << SEG_BITS))) return FORA_OK; // narrow layout only
     std::vector<uint32_t> order((size_t)n); // nodes by (out-degree descending, id ascending)
@@ -2035,16 +2007,17 @@ static int build_walk_dg(fora_ctx *c, const int64_t *row_ptr, const int32_t *col
     }
     while (T.size() & 3) T.push_back(0);
     if (T.empty()) T.assign(4, 0);
-    HIPCHK(c, hipMalloc(&c->d_dg_perm, (size_t)n * 4));
-    HIPCHK(c, hipMalloc(&c->d_dg_inv, (size_t)np * 4));
-    HIPCHK(c, hipMalloc(&c->d_dg_colp, words * 4));
-    HIPCHK(c, hipMalloc(&c->d_dg_rec, std::max<size_t>(1, rec.size()) * 4));
-    HIPCHK(c, hipMalloc(&c->d_dg_T, T.size()));
-    HIPCHK(c, hipMemcpy(c->d_dg_perm, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_dg_inv, inv.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_dg_colp, pk.data(), words * 4, hipMemcpyHostToDevice));
-    if (!rec.empty()) HIPCHK(c, hipMemcpy(c->d_dg_rec, rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_dg_T, T.data(), T.size(), hipMemcpyHostToDevice));
+    WalkCopy wc;
+    HIPCHK(c, wc.d_perm.alloc((size_t)n));
+    HIPCHK(c, wc.d_inv.alloc((size_t)np));
+    HIPCHK(c, wc.d_colp.alloc(words));
+    HIPCHK(c, wc.d_rec.alloc(std::max<size_t>(1, rec.size())));
+    HIPCHK(c, wc.d_T.alloc(T.size()));
+    HIPCHK(c, hipMemcpy(wc.d_perm.get(), perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(wc.d_inv.get(), inv.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(wc.d_colp.get(), pk.data(), words * 4, hipMemcpyHostToDevice));
+    if (!rec.empty()) HIPCHK(c, hipMemcpy(wc.d_rec.get(), rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(wc.d_T.get(), T.data(), T.size(), hipMemcpyHostToDevice));
     // bucket order of the ids behind the hubs: 64-id blocks dealt round-robin to nbx bins
     const uint32_t nblk64 = (np - H + 63) / 64;
     const uint32_t nbx = std::max<uint32_t>(2, (nblk64 + 127) / 128); // (2 at least: floor(2^32 / nbx) + 1 must fit 32 bits)
@@ -2054,15 +2027,16 @@ static int build_walk_dg(fora_ctx *c, const int64_t *row_ptr, const int32_t *col
         invb[((size_t)(b64 % nbx) << BIN_SHIFT) | ((b64 / nbx) << 6) | (u & 63u)] = inv[x];
     }
     if (nbx <= (uint32_t)MAX_BINS) {
-        HIPCHK(c, hipMalloc(&c->d_dg_invb, invb.size() * 4));
-        HIPCHK(c, hipMemcpy(c->d_dg_invb, invb.data(), invb.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, wc.d_invb.alloc(invb.size()));
+        HIPCHK(c, hipMemcpy(wc.d_invb.get(), invb.data(), invb.size() * 4, hipMemcpyHostToDevice));
     }
     WalkDG g{};
-    g.invb = c->d_dg_invb; g.nbx = c->d_dg_invb ? nbx : 0; g.nbx_magic = (uint32_t)((1ull << 32) / nbx) + 1;
-    g.perm = c->d_dg_perm; g.inv = c->d_dg_inv; g.colp = c->d_dg_colp; g.rec = c->d_dg_rec; g.T = c->d_dg_T;
+    g.invb = wc.d_invb.get(); g.nbx = wc.d_invb.get() ? nbx : 0; g.nbx_magic = (uint32_t)((1ull << 32) / nbx) + 1;
+    g.perm = wc.d_perm.get(); g.inv = wc.d_inv.get(); g.colp = wc.d_colp.get(); g.rec = wc.d_rec.get(); g.T = wc.d_T.get();
     g.H = H; g.nrec = nrec; g.nblk = (uint32_t)T.size(); g.ts = ts; g.bits = bits; g.zero_first = zero_first;
     g.bits32 = (uint64_t)nnz * bits < (1ull << 32) ? 1 : 0;
-    c->dg = g;
+    wc.dg = g;
+    c->g.walk = std::move(wc);
     return FORA_OK;
 }
 
@@ -2081,62 +2055,64 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_graph(c);
     free_sparse(c); // (rows of another graph)
     c->bk_scale = 1; c->bk_scale_topk = 1;
-    std::vector<uint64_t> rowinfo((size_t)n);
-    std::vector<uint32_t> deg((size_t)n);
-    int64_t n_dangling = 0;
-    for (int32_t v = 0; v < n; v++) {
-        const uint64_t dg = (uint64_t)(row_ptr[v + 1] - row_ptr[v]);
-        n_dangling += dg == 0;
-        if (dg > 0xFFFFFFFFull) return fail(c, FORA_E_ARG, "out-degree over 2^32");
-        deg[v] = (uint32_t)dg;
-        rowinfo[v] = ((uint64_t)row_ptr[v] << 24) | std::min<uint64_t>(dg, DEG_SAT);
-    }
-    HIPCHK(c, hipMalloc(&c->d_row_ptr, ((size_t)n + 1) * 8));
-    HIPCHK(c, hipMalloc(&c->d_col, std::max<size_t>(1, (size_t)nnz) * 4));
-    HIPCHK(c, hipMalloc(&c->d_rowinfo, (size_t)n * 8));
-    HIPCHK(c, hipMalloc(&c->d_deg, (size_t)n * 4));
-    HIPCHK(c, hipMemcpy(c->d_row_ptr, row_ptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz) HIPCHK(c, hipMemcpy(c->d_col, col, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_rowinfo, rowinfo.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_deg, deg.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    if (nnz < (1ll << 31) && c->opt_.no_compact != 1) { // compact walk-step copy
-        uint32_t bits = 1;
-        while ((1ull << bits) < (uint64_t)n) bits++;
-        if (bits > 31) bits = 31;
-        std::vector<uint32_t> rp32((size_t)n + 1);
-        for (int32_t v = 0; v <= n; v++) rp32[v] = (uint32_t)row_ptr[v];
-        const size_t words = (size_t)(((uint64_t)nnz * bits + 31) / 32) + 2;
-        std::vector<uint32_t> pk(words, 0);
-        for (int64_t e = 0; e < nnz; e++) {
-            const uint64_t at = (uint64_t)e * bits;
-            const uint64_t x = (uint64_t)(uint32_t)col[e] << (at & 31);
-            pk[at >> 5] |= (uint32_t)x;
-            pk[(at >> 5) + 1] |= (uint32_t)(x >> 32);
+    const int rc = [&]() -> int {
+        std::vector<uint64_t> rowinfo((size_t)n);
+        std::vector<uint32_t> deg((size_t)n);
+        int64_t n_dangling = 0;
+        for (int32_t v = 0; v < n; v++) {
+            const uint64_t dg = (uint64_t)(row_ptr[v + 1] - row_ptr[v]);
+            n_dangling += dg == 0;
+            if (dg > 0xFFFFFFFFull) return fail(c, FORA_E_ARG, "out-degree over 2^32");
+            deg[v] = (uint32_t)dg;
+            rowinfo[v] = ((uint64_t)row_ptr[v] << 24) | std::min<uint64_t>(dg, DEG_SAT);
         }
-        HIPCHK(c, hipMalloc(&c->d_rp32, rp32.size() * 4));
-        HIPCHK(c, hipMalloc(&c->d_colp, words * 4));
-        HIPCHK(c, hipMemcpy(c->d_rp32, rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_colp, pk.data(), words * 4, hipMemcpyHostToDevice));
-        c->colbits = bits;
-    }
-    c->h_row_ptr.assign(row_ptr, row_ptr + n + 1);
-    c->n = n; c->m_attr = m_attr; c->nnz = nnz;
-    c->dangling_frac = (double)n_dangling / (double)n;
-    if (int rc = build_walk_dg(c, row_ptr, col)) return rc;
-    c->team_checked = false;
-    if (int rc = ensure_team(c)) return rc; // (before the hub copy: its size depends on whether the team path takes this graph)
-    if (int rc = build_hub_copy(c, row_ptr, col)) return rc;
-    if (int rc = build_quad_copies(c)) return rc;
-    return FORA_OK;
+        HIPCHK(c, c->g.d_row_ptr.alloc((size_t)n + 1));
+        HIPCHK(c, c->g.d_col.alloc(std::max<size_t>(1, (size_t)nnz)));
+        HIPCHK(c, c->g.d_rowinfo.alloc((size_t)n));
+        HIPCHK(c, c->g.d_deg.alloc((size_t)n));
+        HIPCHK(c, hipMemcpy(c->g.d_row_ptr.get(), row_ptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        if (nnz) HIPCHK(c, hipMemcpy(c->g.d_col.get(), col, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->g.d_rowinfo.get(), rowinfo.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->g.d_deg.get(), deg.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        if (nnz < (1ll << 31) && c->opt_.no_compact != 1) { // compact walk-step copy
+            uint32_t bits = 1;
+            while ((1ull << bits) < (uint64_t)n) bits++;
+            if (bits > 31) bits = 31;
+            std::vector<uint32_t> rp32((size_t)n + 1);
+            for (int32_t v = 0; v <= n; v++) rp32[v] = (uint32_t)row_ptr[v];
+            const size_t words = (size_t)(((uint64_t)nnz * bits + 31) / 32) + 2;
+            std::vector<uint32_t> pk(words, 0);
+            for (int64_t e = 0; e < nnz; e++) {
+                const uint64_t at = (uint64_t)e * bits;
+                const uint64_t x = (uint64_t)(uint32_t)col[e] << (at & 31);
+                pk[at >> 5] |= (uint32_t)x;
+                pk[(at >> 5) + 1] |= (uint32_t)(x >> 32);
+            }
+            HIPCHK(c, c->g.d_rp32.alloc(rp32.size()));
+            HIPCHK(c, c->g.d_colp.alloc(words));
+            HIPCHK(c, hipMemcpy(c->g.d_rp32.get(), rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(c->g.d_colp.get(), pk.data(), words * 4, hipMemcpyHostToDevice));
+            c->g.colbits = bits;
+        }
+        c->g.h_row_ptr.assign(row_ptr, row_ptr + n + 1);
+        c->g.n = n; c->g.m_attr = m_attr; c->g.nnz = nnz;
+        c->g.dangling_frac = (double)n_dangling / (double)n;
+        if (int rb = build_walk_dg(c, row_ptr, col)) return rb;
+        if (int rb = ensure_team(c)) return rb; // (before the hub copy: its size depends on whether the team path takes this graph)
+        if (int rb = build_hub_copy(c, row_ptr, col)) return rb;
+        return build_quad_copies(c);
+    }();
+    if (rc) free_graph(c); // no half-built graph: the next call answers "set_graph first"
+    return rc;
 }
 
 int fora_hip_set_params(fora_ctx *c, double alpha, double epsilon, double rmax_scale, int opt, uint64_t seed) {
     if (!c) return FORA_E_ARG;
-    if (!c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
     if (!(alpha > 0 && alpha < 1) || !(epsilon > 0) || !(rmax_scale >= 0)) return fail(c, FORA_E_ARG, "bad params");
     // graph.h:177-178 then algo.h:455-463, in the reference's operand order
-    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
-    const long long m = c->m_attr;
+    const double delta = 1.0 / c->g.n, pfail = 1.0 / c->g.n;
+    const long long m = c->g.m_attr;
     double rmax = epsilon * sqrt(delta / 3 / m / log(2 / pfail));
     if (opt) rmax *= rmax_scale / (1 - alpha);
     else rmax *= rmax_scale;
@@ -2204,7 +2180,7 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "bucket_retries")) { *value = (int64_t)c->bucket_retries; return FORA_OK; } // re-runs with doubled message buckets
     if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
     if (!strcmp(name, "team_suspended")) { *value = c->team_suspend; return FORA_OK; }             // calls left that do not try the team push
-    if (!strcmp(name, "team_members")) { *value = c->team_T; return FORA_OK; }                      // 0: this graph / workspace has no team push
+    if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
     if (!strcmp(name, "team_cooperative")) { *value = c->team_coop_ok && !c->team_coop_failed ? 1 : 0; return FORA_OK; }
     for (const auto &o : OPTIONS)
         if (!strcmp(name, o.name)) { *value = c->opt_.*(o.field); return FORA_OK; }
@@ -2226,8 +2202,8 @@ int fora_hip_set_balanced(fora_ctx *c, int on, double start_scale, double c_pop,
 static uint64_t host_index_sizes(const fora_ctx *c, uint64_t *off, uint64_t *cnt) {
     // build.h:325-334
     uint64_t total = 0;
-    for (int32_t v = 0; v < c->n; v++) {
-        const size_t deg = (size_t)(c->h_row_ptr[v + 1] - c->h_row_ptr[v]);
+    for (int32_t v = 0; v < c->g.n; v++) {
+        const size_t deg = (size_t)(c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v]);
         unsigned long num_rw;
         if (c->opt) num_rw = (unsigned long)ceil(deg * c->rmax * (1 - c->alpha) * c->omega);
         else num_rw = (unsigned long)ceil(deg * c->rmax * c->omega);
@@ -2239,71 +2215,76 @@ static uint64_t host_index_sizes(const fora_ctx *c, uint64_t *off, uint64_t *cnt
 }
 
 int fora_hip_index_sizes(fora_ctx *c, uint64_t *total, uint64_t *off, uint64_t *cnt) {
-    if (!c || !c->n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
+    if (!c || !c->g.n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
     const uint64_t t = host_index_sizes(c, off, cnt);
     if (total) *total = t;
     return FORA_OK;
 }
 
 int fora_hip_build_index(fora_ctx *c) {
-    if (!c || !c->n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
+    if (!c || !c->g.n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> off((size_t)c->n), cnt((size_t)c->n);
+    std::vector<uint64_t> off((size_t)c->g.n), cnt((size_t)c->g.n);
     const uint64_t total = host_index_sizes(c, off.data(), cnt.data());
     free_index(c);
-    HIPCHK(c, hipMalloc(&c->d_rw_idx, std::max<uint64_t>(1, total) * 4));
-    HIPCHK(c, hipMalloc(&c->d_idx_off, (size_t)c->n * 8));
-    HIPCHK(c, hipMalloc(&c->d_idx_cnt, (size_t)c->n * 8));
-    HIPCHK(c, hipMemcpy(c->d_idx_off, off.data(), (size_t)c->n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_idx_cnt, cnt.data(), (size_t)c->n * 8, hipMemcpyHostToDevice));
-    c->idx_len = total;
+    Index ix;
+    HIPCHK(c, ix.d_rw_idx.alloc(std::max<uint64_t>(1, total)));
+    HIPCHK(c, ix.d_idx_off.alloc((size_t)c->g.n));
+    HIPCHK(c, ix.d_idx_cnt.alloc((size_t)c->g.n));
+    HIPCHK(c, hipMemcpy(ix.d_idx_off.get(), off.data(), (size_t)c->g.n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ix.d_idx_cnt.get(), cnt.data(), (size_t)c->g.n * 8, hipMemcpyHostToDevice));
+    ix.len = total;
     c->bk_div = 1;
     int rc = ensure_workspace(c, 1, (double)total);
     if (rc) return rc;
-    Dev d = make_dev(c, 1, true);
+    Dev d = make_dev(c, 1, false);
+    d.rw_idx = ix.d_rw_idx.get(); d.idx_off = ix.d_idx_off.get(); d.idx_cnt = ix.d_idx_cnt.get(); // the index being built
     HIPCHK(c, c->ws.d_counters.zero(c->stream));
     HIPCHK(c, c->ws.d_err.zero(c->stream));
     HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
-    const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 2048);
+    const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 2048);
     int h = ev_begin(c, 4);
     hipLaunchKernelGGL(k_index_alloc, dim3(chunks), dim3(BLOCK), 0, c->stream, d);
     ev_end(c, h);
     h = ev_begin(c, 3);
     hipLaunchKernelGGL(k_walk_online<WALK_TO_INDEX>, dim3(walk_grid_x(c, 1), 1), dim3(BLOCK), 0, c->stream, d, 0u,
-                       c->opt ? 1 : 0, c->d_rw_idx);
+                       c->opt ? 1 : 0, ix.d_rw_idx.get());
     ev_end(c, h);
     if ((rc = close_batch(c, -1, "build_index"))) return rc;
-    c->have_index = true;
+    ix.have = true;
+    c->ix = std::move(ix);
     return FORA_OK;
 }
 
 int fora_hip_get_index(fora_ctx *c, int32_t *rw_idx, uint64_t len, uint64_t *off, uint64_t *cnt) {
-    if (!c || !c->have_index) return fail(c, FORA_E_ARG, "no index");
-    if (rw_idx && len < c->idx_len) return fail(c, FORA_E_ARG, "rw_idx buffer too small");
+    if (!c || !c->ix.have) return fail(c, FORA_E_ARG, "no index");
+    if (rw_idx && len < c->ix.len) return fail(c, FORA_E_ARG, "rw_idx buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
-    if (rw_idx && c->idx_len) HIPCHK(c, hipMemcpy(rw_idx, c->d_rw_idx, c->idx_len * 4, hipMemcpyDeviceToHost));
-    if (off) HIPCHK(c, hipMemcpy(off, c->d_idx_off, (size_t)c->n * 8, hipMemcpyDeviceToHost));
-    if (cnt) HIPCHK(c, hipMemcpy(cnt, c->d_idx_cnt, (size_t)c->n * 8, hipMemcpyDeviceToHost));
+    if (rw_idx && c->ix.len) HIPCHK(c, hipMemcpy(rw_idx, c->ix.d_rw_idx.get(), c->ix.len * 4, hipMemcpyDeviceToHost));
+    if (off) HIPCHK(c, hipMemcpy(off, c->ix.d_idx_off.get(), (size_t)c->g.n * 8, hipMemcpyDeviceToHost));
+    if (cnt) HIPCHK(c, hipMemcpy(cnt, c->ix.d_idx_cnt.get(), (size_t)c->g.n * 8, hipMemcpyDeviceToHost));
     return FORA_OK;
 }
 
 int fora_hip_set_index(fora_ctx *c, const int32_t *rw_idx, uint64_t len, const uint64_t *off, const uint64_t *cnt) {
-    if (!c || !c->n) return fail(c, FORA_E_ARG, "set_graph first");
+    if (!c || !c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
     if (!off || !cnt || (len && !rw_idx)) return fail(c, FORA_E_ARG, "bad index");
-    for (int32_t v = 0; v < c->n; v++)
+    for (int32_t v = 0; v < c->g.n; v++)
         if (off[v] + cnt[v] > len) return fail(c, FORA_E_ARG, "index entry range out of bounds");
     for (uint64_t i = 0; i < len; i++)
-        if (rw_idx[i] < 0 || rw_idx[i] >= c->n) return fail(c, FORA_E_ARG, "index endpoint out of range");
+        if (rw_idx[i] < 0 || rw_idx[i] >= c->g.n) return fail(c, FORA_E_ARG, "index endpoint out of range");
     HIPCHK(c, hipSetDevice(c->device));
     free_index(c);
-    HIPCHK(c, hipMalloc(&c->d_rw_idx, std::max<uint64_t>(1, len) * 4));
-    HIPCHK(c, hipMalloc(&c->d_idx_off, (size_t)c->n * 8));
-    HIPCHK(c, hipMalloc(&c->d_idx_cnt, (size_t)c->n * 8));
-    if (len) HIPCHK(c, hipMemcpy(c->d_rw_idx, rw_idx, len * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_idx_off, off, (size_t)c->n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_idx_cnt, cnt, (size_t)c->n * 8, hipMemcpyHostToDevice));
-    c->idx_len = len;
-    c->have_index = true;
+    Index ix;
+    HIPCHK(c, ix.d_rw_idx.alloc(std::max<uint64_t>(1, len)));
+    HIPCHK(c, ix.d_idx_off.alloc((size_t)c->g.n));
+    HIPCHK(c, ix.d_idx_cnt.alloc((size_t)c->g.n));
+    if (len) HIPCHK(c, hipMemcpy(ix.d_rw_idx.get(), rw_idx, len * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ix.d_idx_off.get(), off, (size_t)c->g.n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ix.d_idx_cnt.get(), cnt, (size_t)c->g.n * 8, hipMemcpyHostToDevice));
+    ix.len = len;
+    ix.have = true;
+    c->ix = std::move(ix);
     return FORA_OK;
 }
 
@@ -2328,8 +2309,8 @@ int fora_hip_query_batch_fix(fora_ctx *c, const int32_t *sources, int nq, int wi
 int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t *row_ptr,
                                 fora_query_stats *stats, fora_sparse_stats *sp_out) {
     if (!c) return FORA_E_ARG;
-    c->sp_valid = false; // the held result ends here, whatever becomes of this call
-    c->sp_entries = 0;
+    c->sp.valid = false; // the held result ends here, whatever becomes of this call
+    c->sp.entries = 0;
     if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
     if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
     const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
@@ -2355,25 +2336,25 @@ static int sparse_dest(fora_ctx *c, const void *p, bool &on_device) {
 
 int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap) {
     if (!c) return FORA_E_ARG;
-    if (!c->sp_valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (cap < c->sp_entries) return fail(c, FORA_E_ARG, "cap is smaller than the held result");
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, "cap is smaller than the held result");
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t e = c->sp_entries;
+    const uint64_t e = c->sp.entries;
     bool vals_on_device = false;
     if (vals) if (int rc = sparse_dest(c, vals, vals_on_device)) return rc;
-    if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->d_sp_ids, e * 4, hipMemcpyDefault, c->stream));
-    if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, c->d_sp_fix, e * 8, hipMemcpyDefault, c->stream));
+    if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->sp.d_ids.get(), e * 4, hipMemcpyDefault, c->stream));
+    if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, c->sp.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
     if (e && vals) {
         constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
         const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
         if (vals_on_device) {
-            hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_sp_fix, e, vals);
+            hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->sp.d_fix.get(), e, vals);
         } else {
-            if (!c->d_sp_stage) HIPCHK(c, hipMalloc(&c->d_sp_stage, SP_STAGE * 8));
+            HIPCHK(c, c->sp.d_stage.ensure(SP_STAGE));
             for (uint64_t at = 0; at < e; at += SP_STAGE) {
                 const uint64_t len = std::min(SP_STAGE, e - at);
-                hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->d_sp_fix + at, len, c->d_sp_stage);
-                HIPCHK(c, hipMemcpyAsync(vals + at, c->d_sp_stage, len * 8, hipMemcpyDeviceToHost, c->stream));
+                hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->sp.d_fix.get() + at, len, c->sp.d_stage.get());
+                HIPCHK(c, hipMemcpyAsync(vals + at, c->sp.d_stage.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
             }
         }
     }
@@ -2397,16 +2378,16 @@ int fora_hip_push_batch(fora_ctx *c, const int32_t *sources, int nq, uint64_t *r
 }
 
 int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64_t *num_s_rw, uint64_t *n_rw) {
-    if (!c || !c->n || !c->have_params || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
+    if (!c || !c->g.n || !c->have_params || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<double> d_r; DevBuf<uint64_t> d_num, d_n;
-    const size_t n = (size_t)c->n;
+    const size_t n = (size_t)c->g.n;
     HIPCHK(c, d_r.alloc(n));
     HIPCHK(c, d_num.alloc(n));
     HIPCHK(c, d_n.alloc(1));
     HIPCHK(c, hipMemcpy(d_r.get(), residue, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_walk_counts_f64, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                       c->n, (const double *)d_r.get(), rsum, c->omega, c->alpha, c->opt, d_num.get(), d_n.get());
+                       c->g.n, (const double *)d_r.get(), rsum, c->omega, c->alpha, c->opt, d_num.get(), d_n.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(num_s_rw, d_num.get(), n * 8, hipMemcpyDeviceToHost));
     uint64_t N = 0;
@@ -2417,10 +2398,10 @@ int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64
 
 int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_hop, const int32_t *starts,
                    const uint64_t *js, int64_t count, int32_t *dests) {
-    if (!c || !c->n || !c->have_params || count < 0) return fail(c, FORA_E_ARG, "bad call");
+    if (!c || !c->g.n || !c->have_params || count < 0) return fail(c, FORA_E_ARG, "bad call");
     if (count == 0) return FORA_OK;
     for (int64_t i = 0; i < count; i++)
-        if (starts[i] < 0 || starts[i] >= c->n) return fail(c, FORA_E_ARG, "walk start out of range");
+        if (starts[i] < 0 || starts[i] >= c->g.n) return fail(c, FORA_E_ARG, "walk start out of range");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<int32_t> d_s, d_d; DevBuf<uint64_t> d_j;
     HIPCHK(c, d_s.alloc((size_t)count));
@@ -2429,7 +2410,7 @@ int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_
     HIPCHK(c, hipMemcpy(d_s.get(), starts, (size_t)count * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_j.get(), js, (size_t)count * 8, hipMemcpyHostToDevice));
     Dev d{};
-    d.n = c->n; d.rowinfo = c->d_rowinfo; d.row_ptr = c->d_row_ptr; d.col = c->d_col;
+    d.n = c->g.n; d.rowinfo = c->g.d_rowinfo.get(); d.row_ptr = c->g.d_row_ptr.get(); d.col = c->g.d_col.get();
     d.alpha32 = (uint32_t)(c->alpha * 4294967296.0);
     d.seed_lo = (uint32_t)c->seed; d.seed_hi = (uint32_t)(c->seed >> 32);
     hipLaunchKernelGGL(k_walks_raw, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, d,
@@ -2452,10 +2433,10 @@ static int check_topk_args(fora_ctx *c, const int32_t *sources, int nq, int k, d
                            const int32_t *ids, const double *scores) {
     if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (nq && (!ids || !scores)) return fail(c, FORA_E_ARG, "ids / scores missing");
-    if (k < 2 || k >= c->n - 1) return fail(c, FORA_E_ARG, "k out of range (query.h:1317-1318)");
+    if (k < 2 || k >= c->g.n - 1) return fail(c, FORA_E_ARG, "k out of range (query.h:1317-1318)");
     if (int rc = check_k(c, k)) return rc;
     if (!(epsilon > 0) || !(rmax_scale >= 0)) return fail(c, FORA_E_ARG, "bad epsilon / rmax_scale");
-    if (with_idx && !c->have_index) return fail(c, FORA_E_ARG, "with_idx without an index");
+    if (with_idx && !c->ix.have) return fail(c, FORA_E_ARG, "with_idx without an index");
     return FORA_OK;
 }
 static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, double epsilon, double rmax_scale,
@@ -2464,10 +2445,10 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
     if (int rc = check_topk_args(c, sources, nq, k, epsilon, rmax_scale, with_idx, ids, scores)) return rc;
     if (int rc = check_id_range(c, sources, nq)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const double min_delta = 1.0 / c->n;           // query.h:974
+    const double min_delta = 1.0 / c->g.n;           // query.h:974
     const double init_delta = 1.0 / k / 10;        // query.h:976
-    const double pfail = 1.0 / c->n / c->n;        // query.h:977
-    const long long m = c->m_attr;
+    const double pfail = 1.0 / c->g.n / c->g.n;        // query.h:977
+    const long long m = c->g.m_attr;
     if (!(init_delta >= min_delta)) { // k > n/10: the reference's round loop (query.h:1001) never runs, topk_ppr sees an empty ppr
         for (size_t i = 0; i < (size_t)nq * k; i++) { ids[i] = 0; scores[i] = 0.0; }
         if (rounds) for (int i = 0; i < nq; i++) rounds[i] = 0;
@@ -2535,19 +2516,19 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     if (!(ppr_decay_alpha > 0 && ppr_decay_alpha < 1)) return fail(c, FORA_E_ARG, "bad ppr_decay_alpha");
     if (int rc = check_id_range(c, sources, nq)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    const double min_delta = 1.0 / c->n;                                                                    // query.h:911
+    const double min_delta = 1.0 / c->g.n;                                                                    // query.h:911
     const double init_delta = 1.0 / 4;                                                                      // :912
-    const double threshold = (1.0 - ppr_decay_alpha) / pow(500, ppr_decay_alpha) / pow(c->n, 1 - ppr_decay_alpha); // :913
-    const double pfail = 1.0 / c->n / c->n / log(c->n);                                                     // :915
+    const double threshold = (1.0 - ppr_decay_alpha) / pow(500, ppr_decay_alpha) / pow(c->g.n, 1 - ppr_decay_alpha); // :913
+    const double pfail = 1.0 / c->g.n / c->g.n / log(c->g.n);                                                     // :915
     const double L = log(2 / pfail);
-    const long long m = c->m_attr;
+    const long long m = c->g.m_attr;
     const double omega_max = (2 + epsilon) * L / min_delta / epsilon / epsilon;
     c->bk_div = 1;
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
     if ((rc = ensure_topk_slabs(c, k))) return rc;
     Workspace &w = c->ws;
-    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->n;
+    const uint64_t slab = (uint64_t)w.B * (uint64_t)c->g.n;
     HIPCHK(c, w.d_upper.ensure(slab));
     HIPCHK(c, w.d_lower.ensure(slab));
     if (!w.d_filter) { HIPCHK(c, w.d_filter.alloc(slab)); HIPCHK(c, w.d_filter.zero(c->stream)); } // the marks start from zero, once
@@ -2562,7 +2543,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         if ((rc = topk_batch_start(c, tb, sources + b0, nb, with_idx != 0, chunks))) return rc;
-        hipLaunchKernelGGL(k_bounds_reset, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->n, c->ws.d_upper.get(), c->ws.d_lower.get()); // :941-942
+        hipLaunchKernelGGL(k_bounds_reset, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->g.n, c->ws.d_upper.get(), c->ws.d_lower.get()); // :941-942
         double delta = init_delta;
         int round = 0;
         while (delta >= min_delta) { // query.h:944
@@ -2579,7 +2560,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
             if (delta < threshold) // query.h:745-746
                 hipLaunchKernelGGL(k_bounds_update, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, (const uint64_t *)c->ws.d_ppr.get(),
                                    (const uint8_t *)c->ws.d_active.get(), (const unsigned long long *)c->ws.d_round_walks.get(), L,
-                                   1.0 / c->n, sqrt(1.0 / c->n), c->ws.d_upper.get(), c->ws.d_lower.get());
+                                   1.0 / c->g.n, sqrt(1.0 / c->g.n), c->ws.d_upper.get(), c->ws.d_lower.get());
             // if_stop, algo.h:1096-1166
             hipLaunchKernelGGL(k_count_above, dim3(std::min<uint32_t>(chunks, 256), nb), dim3(BLOCK), 0, c->stream, dw,
                                (const uint8_t *)c->ws.d_active.get(), 2.0 * delta, c->ws.d_above.get());
@@ -2674,9 +2655,9 @@ static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, doubl
                               uint64_t *reserve_fix_out, uint64_t *residue_fix_out, int k, int32_t *ids, double *scores,
                               fora_query_stats *stats) {
     if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
-    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
-    const double delta = 1.0 / c->n;
-    const double rmax = rmax_scale * delta * epsilon * c->n / c->m_attr; // config.rmax_scale*config.delta*config.epsilon*n/m
+    if (c->g.m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    const double delta = 1.0 / c->g.n;
+    const double rmax = rmax_scale * delta * epsilon * c->g.n / c->g.m_attr; // config.rmax_scale*config.delta*config.epsilon*n/m
     if (!(rmax > 0) || !std::isfinite(rmax)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
     PushRmaxScope scope(c, rmax);
     return query_common(c, sources, nq, 0, RUN_PUSH_ONLY, ppr_out, reserve_fix_out, residue_fix_out, stats, k, ids, scores);
@@ -2695,66 +2676,68 @@ int fora_hip_fwdpush_batch(fora_ctx *c, const int32_t *sources, int nq, double e
 // that overflow the LDS tier) and, chunk by chunk, a write pass that runs the same pushes again and writes their entries
 // target-major.  Chunks follow from the counts, so no chunk boundary depends on anything but the entry budget.
 static int ensure_reverse_csr(fora_ctx *c) {
-    if (c->d_rin_ptr) return FORA_OK;
-    const uint64_t n = (uint64_t)c->n, nnz = (uint64_t)c->nnz;
+    if (c->g.rev.d_rin_ptr) return FORA_OK;
+    const uint64_t n = (uint64_t)c->g.n, nnz = (uint64_t)c->g.nnz;
     DevBuf<uint32_t> indeg; DevBuf<unsigned long long> cursor;
     HIPCHK(c, indeg.alloc(n));
     HIPCHK(c, indeg.zero(c->stream));
     if (nnz) hipLaunchKernelGGL(k_rev_count, dim3((unsigned)std::min<uint64_t>((nnz + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream,
-                                (const int32_t *)c->d_col, nnz, indeg.get());
+                                (const int32_t *)c->g.d_col.get(), nnz, indeg.get());
     std::vector<uint32_t> h_in(n);
     HIPCHK(c, hipMemcpyAsync(h_in.data(), indeg.get(), n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<int64_t> rp(n + 1);
     rp[0] = 0;
     for (uint64_t v = 0; v < n; v++) rp[v + 1] = rp[v] + h_in[v];
-    HIPCHK(c, hipMalloc(&c->d_rin_ptr, (n + 1) * 8));
-    HIPCHK(c, hipMalloc(&c->d_rin, std::max<uint64_t>(1, nnz) * 4));
+    ReverseCsr rev;
+    HIPCHK(c, rev.d_rin_ptr.alloc(n + 1));
+    HIPCHK(c, rev.d_rin.alloc(std::max<uint64_t>(1, nnz)));
     HIPCHK(c, cursor.alloc(std::max<uint64_t>(1, n)));
-    HIPCHK(c, hipMemcpyAsync(c->d_rin_ptr, rp.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rev.d_rin_ptr.get(), rp.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(cursor.get(), rp.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_rev_fill, dim3((unsigned)std::min<uint64_t>((n * 64 + BLOCK - 1) / BLOCK, 16384)), dim3(BLOCK), 0, c->stream,
-                       (const int64_t *)c->d_row_ptr, (const int32_t *)c->d_col, c->n, cursor.get(), c->d_rin);
+                       (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.d_col.get(), c->g.n, cursor.get(), rev.d_rin.get());
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors and the cursor go out of scope)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("reverse CSR: ") + hipGetErrorString(e));
+    c->g.rev = std::move(rev);
     return FORA_OK;
 }
 
 static int ensure_bwd_targets(fora_ctx *c, uint64_t nt) {
-    if (!c->d_bstat) HIPCHK(c, hipMalloc(&c->d_bstat, BS_WORDS * 8));
-    if (c->bt_cap >= nt && c->d_bt) return FORA_OK;
-    dfree(c->d_bt); dfree(c->d_bcnt); dfree(c->d_bspill); dfree(c->d_blist); dfree(c->d_bflag); dfree(c->d_boff);
-    c->bt_cap = 0;
+    BwdBufs &b = c->bw;
     const uint64_t m = std::max<uint64_t>(1, nt);
-    HIPCHK(c, hipMalloc(&c->d_bt, m * 4));
-    HIPCHK(c, hipMalloc(&c->d_bcnt, m * 4));
-    HIPCHK(c, hipMalloc(&c->d_bspill, m * 4));
-    HIPCHK(c, hipMalloc(&c->d_blist, m * 4));
-    HIPCHK(c, hipMalloc(&c->d_bflag, m));
-    HIPCHK(c, hipMalloc(&c->d_boff, (m + 1) * 8));
-    c->bt_cap = m;
+    HIPCHK(c, b.d_bstat.ensure(BS_WORDS));
+    if (b.d_boff.size() < m + 1) { b.d_bt.reset(); b.d_bcnt.reset(); b.d_bspill.reset(); b.d_blist.reset(); b.d_bflag.reset(); b.d_boff.reset(); } // a regrow frees the group first: its peak memory
+    HIPCHK(c, b.d_bt.ensure(m));
+    HIPCHK(c, b.d_bcnt.ensure(m));
+    HIPCHK(c, b.d_bspill.ensure(m));
+    HIPCHK(c, b.d_blist.ensure(m));
+    HIPCHK(c, b.d_bflag.ensure(m));
+    HIPCHK(c, b.d_boff.ensure(m + 1));
     return FORA_OK;
 }
 
 // global tier: dense slabs for up to 64 targets in flight, 36 bytes per node each, at most a quarter of the free HBM
 static int ensure_global_tier(fora_ctx *c) {
-    if (c->d_gr) return FORA_OK;
-    const uint64_t n = (uint64_t)c->n;
+    if (c->g.tier.d_gr) return FORA_OK;
+    const uint64_t n = (uint64_t)c->g.n;
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
     const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>({64, (uint64_t)c->prop.multiProcessorCount, (uint64_t)(fr / 4) / (36 * n)}));
-    HIPCHK(c, hipMalloc(&c->d_gr, g * n * 8));
-    HIPCHK(c, hipMalloc(&c->d_gp, g * n * 8));
-    HIPCHK(c, hipMalloc(&c->d_gfy, g * n * 8));
-    HIPCHK(c, hipMalloc(&c->d_gtag, g * n * 4));
-    HIPCHK(c, hipMalloc(&c->d_glist, g * n * 4));
-    HIPCHK(c, hipMalloc(&c->d_gfn, g * n * 4));
+    GlobalTier t;
+    HIPCHK(c, t.d_gr.alloc(g * n));
+    HIPCHK(c, t.d_gp.alloc(g * n));
+    HIPCHK(c, t.d_gfy.alloc(g * n));
+    HIPCHK(c, t.d_gtag.alloc(g * n));
+    HIPCHK(c, t.d_glist.alloc(g * n));
+    HIPCHK(c, t.d_gfn.alloc(g * n));
     // (on the ctx stream: it does not synchronise with the null stream, and the first global-tier kernel must see zeros)
-    HIPCHK(c, hipMemsetAsync(c->d_gr, 0, g * n * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_gp, 0, g * n * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_gtag, 0, g * n * 4, c->stream));
-    c->g_wgs = (uint32_t)g;
+    HIPCHK(c, t.d_gr.zero(c->stream));
+    HIPCHK(c, t.d_gp.zero(c->stream));
+    HIPCHK(c, t.d_gtag.zero(c->stream));
+    t.wgs = (uint32_t)g;
+    c->g.tier = std::move(t);
     return FORA_OK;
 }
 
@@ -2770,13 +2753,13 @@ struct BwdRun {
 
 static BwdDev make_bwd(fora_ctx *c, const BwdRun &r) {
     BwdDev b{};
-    b.rin_ptr = c->d_rin_ptr; b.rin = c->d_rin; b.deg = c->d_deg;
-    b.targets = c->d_bt; b.cap = r.cap; b.thr = r.thr; b.afix = r.afix;
-    b.cnt = c->d_bcnt; b.spilled = c->d_bflag; b.spill = c->d_bspill; b.stat = c->d_bstat;
-    b.off = c->d_boff; b.e_node = c->d_enode; b.e_p = c->d_ep; b.e_r = c->d_er;
-    b.g_r = c->d_gr; b.g_p = c->d_gp; b.g_fy = c->d_gfy; b.g_tag = c->d_gtag; b.g_list = c->d_glist; b.g_fn = c->d_gfn;
-    b.n = (uint32_t)c->n;
-    b.err = (uint32_t *)(c->d_bstat + BS_WORDS - 1);
+    b.rin_ptr = c->g.rev.d_rin_ptr.get(); b.rin = c->g.rev.d_rin.get(); b.deg = c->g.d_deg.get();
+    b.targets = c->bw.d_bt.get(); b.cap = r.cap; b.thr = r.thr; b.afix = r.afix;
+    b.cnt = c->bw.d_bcnt.get(); b.spilled = c->bw.d_bflag.get(); b.spill = c->bw.d_bspill.get(); b.stat = c->bw.d_bstat.get();
+    b.off = c->bw.d_boff.get(); b.e_node = c->bw.d_enode.get(); b.e_p = c->bw.d_ep.get(); b.e_r = c->bw.d_er.get();
+    b.g_r = c->g.tier.d_gr.get(); b.g_p = c->g.tier.d_gp.get(); b.g_fy = c->g.tier.d_gfy.get(); b.g_tag = c->g.tier.d_gtag.get(); b.g_list = c->g.tier.d_glist.get(); b.g_fn = c->g.tier.d_gfn.get();
+    b.n = (uint32_t)c->g.n;
+    b.err = (uint32_t *)(c->bw.d_bstat.get() + BS_WORDS - 1);
     return b;
 }
 
@@ -2795,20 +2778,20 @@ static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
     r.thr = (uint64_t)std::floor(std::ldexp(rmax, 60));
     r.afix = (uint64_t)std::ldexp(c->alpha, 62); // (as the forward push: make_dev's afix)
     r.cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.bwd_lds_cap, 0), BWD_CAP_MAX);
-    HIPCHK(c, hipMemsetAsync(c->d_bstat, 0, BS_WORDS * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_bflag, 0, nt, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->bw.d_bstat.get(), 0, BS_WORDS * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->bw.d_bflag.get(), 0, nt, c->stream));
     const int h = ev_begin(c, 11);
     if (r.cap > 0) {
         BwdDev b = make_bwd(c, r);
         b.nlist = nt;
         hipLaunchKernelGGL((k_bwd_push<false, false>), dim3(bwd_grid(c, nt, 8)), dim3(BLOCK), 0, c->stream, b);
     }
-    HIPCHK(c, hipMemcpyAsync(r.stat, c->d_bstat, BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.stat, c->bw.d_bstat.get(), BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (r.cap > 0) {
         r.spill.resize(r.stat[BS_SPILL]);
         if (!r.spill.empty()) {
-            HIPCHK(c, hipMemcpy(r.spill.data(), c->d_bspill, r.spill.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(r.spill.data(), c->bw.d_bspill.get(), r.spill.size() * 4, hipMemcpyDeviceToHost));
             std::sort(r.spill.begin(), r.spill.end());
         }
     } else {
@@ -2817,16 +2800,16 @@ static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
     }
     if (!r.spill.empty()) {
         if (int rc = ensure_global_tier(c)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_blist, r.spill.data(), r.spill.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->bw.d_blist.get(), r.spill.data(), r.spill.size() * 4, hipMemcpyHostToDevice, c->stream));
         BwdDev b = make_bwd(c, r);
-        b.list = c->d_blist;
+        b.list = c->bw.d_blist.get();
         b.nlist = (uint32_t)r.spill.size();
-        hipLaunchKernelGGL((k_bwd_push<true, false>), dim3(std::min<uint32_t>(c->g_wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
+        hipLaunchKernelGGL((k_bwd_push<true, false>), dim3(std::min<uint32_t>(c->g.tier.wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
     }
     ev_end(c, h);
     r.cnt.resize(nt);
-    HIPCHK(c, hipMemcpyAsync(r.cnt.data(), c->d_bcnt, (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(r.stat, c->d_bstat, BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.cnt.data(), c->bw.d_bcnt.get(), (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.stat, c->bw.d_bstat.get(), BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (int rc = bwd_check_err(c, "backward push")) return rc;
     if (r.stat[BS_WORDS - 1] & 0xFFFFFFFFull) return fail(c, FORA_E_OVERFLOW, "backward push: level cap reached");
@@ -2835,7 +2818,7 @@ static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
     // chunks: at most bwd_chunk targets, at most the entries a fifth of the free HBM holds (20 bytes each)
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const uint64_t have = c->e_cap;
+    const uint64_t have = std::min({c->bw.d_enode.size(), c->bw.d_ep.size(), c->bw.d_er.size()});
     const uint64_t budget = std::max<uint64_t>({have, (uint64_t)(fr / 5) / 20, (uint64_t)BWD_CAP_MAX});
     const uint64_t per = c->opt_.bwd_chunk > 0 ? (uint64_t)c->opt_.bwd_chunk : ~0ull;
     r.chunks.clear();
@@ -2852,36 +2835,32 @@ static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
 static int bwd_write(fora_ctx *c, const BwdRun &r, size_t k) {
     const uint32_t t0 = r.chunks[k].first, t1 = r.chunks[k].second, len = t1 - t0;
     const uint64_t ne = r.off[t1] - r.off[t0];
-    if (c->e_cap < ne) {
-        dfree(c->d_enode); dfree(c->d_ep); dfree(c->d_er);
-        c->e_cap = 0;
-        HIPCHK(c, hipMalloc(&c->d_enode, ne * 4));
-        HIPCHK(c, hipMalloc(&c->d_ep, ne * 8));
-        HIPCHK(c, hipMalloc(&c->d_er, ne * 8));
-        c->e_cap = ne;
-    }
+    if (c->bw.d_er.size() < ne) { c->bw.d_enode.reset(); c->bw.d_ep.reset(); c->bw.d_er.reset(); } // (as ensure_bwd_targets)
+    HIPCHK(c, c->bw.d_enode.ensure(ne));
+    HIPCHK(c, c->bw.d_ep.ensure(ne));
+    HIPCHK(c, c->bw.d_er.ensure(ne));
     std::vector<uint64_t> off((size_t)len + 1);
     for (uint32_t i = 0; i <= len; i++) off[i] = r.off[t0 + i] - r.off[t0];
     std::vector<uint32_t> gl;
     for (auto it = std::lower_bound(r.spill.begin(), r.spill.end(), t0); it != r.spill.end() && *it < t1; ++it) gl.push_back(*it - t0);
-    HIPCHK(c, hipMemcpyAsync(c->d_boff, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
-    if (!gl.empty()) HIPCHK(c, hipMemcpyAsync(c->d_blist, gl.data(), gl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->bw.d_boff.get(), off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (!gl.empty()) HIPCHK(c, hipMemcpyAsync(c->bw.d_blist.get(), gl.data(), gl.size() * 4, hipMemcpyHostToDevice, c->stream));
     const int h = ev_begin(c, 11);
     BwdDev b = make_bwd(c, r);
-    b.targets = c->d_bt + t0;
-    b.spilled = c->d_bflag + t0;
+    b.targets = c->bw.d_bt.get() + t0;
+    b.spilled = c->bw.d_bflag.get() + t0;
     if (r.cap > 0 && gl.size() < len) {
         b.nlist = len;
         hipLaunchKernelGGL((k_bwd_push<false, true>), dim3(bwd_grid(c, len, 8)), dim3(BLOCK), 0, c->stream, b);
     }
     if (!gl.empty()) {
-        b.list = c->d_blist;
+        b.list = c->bw.d_blist.get();
         b.nlist = (uint32_t)gl.size();
-        hipLaunchKernelGGL((k_bwd_push<true, true>), dim3(std::min<uint32_t>(c->g_wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
+        hipLaunchKernelGGL((k_bwd_push<true, true>), dim3(std::min<uint32_t>(c->g.tier.wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
     }
     ev_end(c, h);
     uint64_t st[BS_WORDS];
-    HIPCHK(c, hipMemcpyAsync(st, c->d_bstat, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st, c->bw.d_bstat.get(), sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (off / gl are host vectors of this frame)
     if (int rc = bwd_check_err(c, "backward push (write)")) return rc;
     if (st[BS_WORDS - 1] & 0xFFFFFFFFull) {
@@ -2927,9 +2906,9 @@ static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, doubl
     if (nt == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
     if (int rc = ensure_reverse_csr(c)) return rc;
     if (int rc = ensure_bwd_targets(c, (uint64_t)nt)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_bt, targets, (size_t)nt * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->bw.d_bt.get(), targets, (size_t)nt * 4, hipMemcpyHostToDevice, c->stream));
     if (int rc = bwd_count(c, (uint32_t)nt, rmax, r)) return rc;
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     if (reserve_fix_out) memset(reserve_fix_out, 0, (size_t)nt * n * 8);
     if (residue_fix_out) memset(residue_fix_out, 0, (size_t)nt * n * 8);
     for (size_t k = 0; k < r.chunks.size() && (reserve_fix_out || residue_fix_out); k++) {
@@ -2938,9 +2917,9 @@ static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, doubl
         const uint64_t ne = r.off[t1] - r.off[t0];
         std::vector<uint32_t> nd(ne);
         std::vector<uint64_t> p(ne), q(ne);
-        HIPCHK(c, hipMemcpy(nd.data(), c->d_enode, ne * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(p.data(), c->d_ep, ne * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(q.data(), c->d_er, ne * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(nd.data(), c->bw.d_enode.get(), ne * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(p.data(), c->bw.d_ep.get(), ne * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(q.data(), c->bw.d_er.get(), ne * 8, hipMemcpyDeviceToHost));
         for (uint32_t i = t0; i < t1; i++)
             for (uint64_t e = r.off[i] - r.off[t0]; e < r.off[i + 1] - r.off[t0]; e++) {
                 if (reserve_fix_out) reserve_fix_out[(uint64_t)i * n + nd[e]] = p[e];
@@ -2988,7 +2967,7 @@ static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, const WalkCount &
 // BiPPR's step of a batch: the walk slabs c_b (2^-62, slot-major in d_ppr) -> node-major in the residue slabs, combined with
 // the entries of every chunk of targets into d_ppr, -> slot-major estimates at 2^-60 in the residue slabs
 static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
     int h = ev_begin(c, 12);
     hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(),
@@ -3000,8 +2979,8 @@ static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
         const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
         h = ev_begin(c, 12);
         hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                           (const uint64_t *)c->ws.d_residue.get(), (uint32_t)nb, (const int32_t *)c->ws.d_src.get(), (const uint64_t *)c->d_boff,
-                           (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0, len, c->ws.d_ppr.get());
+                           (const uint64_t *)c->ws.d_residue.get(), (uint32_t)nb, (const int32_t *)c->ws.d_src.get(), (const uint64_t *)c->bw.d_boff.get(),
+                           (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0, len, c->ws.d_ppr.get());
         ev_end(c, h);
     }
     h = ev_begin(c, 12);
@@ -3031,7 +3010,7 @@ static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkC
         Dev de = d;
         de.ppr = est;
         {
-            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->n + BLOCK - 1) / BLOCK, 64);
+            const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 64);
             const int h = ev_begin(c, 4);
             hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, de);
             ev_end(c, h);
@@ -3065,7 +3044,7 @@ static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkC
 static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out,
                                  uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats) {
     if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
-    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
+    const double delta = 1.0 / c->g.n, pfail = 1.0 / c->g.n;
     WalkCount w;
     if (int rc = walk_count(c, 3 * log(2 / pfail) / epsilon / epsilon / delta, w)) return rc; // fwd_rw_count, algo.h:478
     HIPCHK(c, hipSetDevice(c->device));
@@ -3077,10 +3056,10 @@ static int montecarlo_batch_impl(fora_ctx *c, const int32_t *sources, int nq, do
 static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                             uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
     if (int rc = check_baseline_args(c, sources, nq, epsilon, k)) return rc;
-    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    if (c->g.m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
     if (!(rmax_scale > 0) || !std::isfinite(rmax_scale)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
-    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
-    double rmax = epsilon * sqrt(c->m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, algo.h:442-447
+    const double delta = 1.0 / c->g.n, pfail = 1.0 / c->g.n;
+    double rmax = epsilon * sqrt(c->g.m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, algo.h:442-447
     rmax *= rmax_scale;
     const double omega = rmax * 3 * log(2.0 / pfail) / delta / epsilon / epsilon;
     if (int rc = check_bwd_rmax(c, rmax)) return rc;
@@ -3094,14 +3073,14 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
     // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
     int rc = ensure_query_workspace(c, nq, k > 0 && (ids || scores) ? k : 0);
     if (rc) return rc;
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     // every node is a target (query.h:91: for i < graph.n)
     if ((rc = ensure_reverse_csr(c))) return rc;
     if ((rc = ensure_bwd_targets(c, n))) return rc;
     {
         std::vector<int32_t> iota(n);
         for (uint64_t v = 0; v < n; v++) iota[v] = (int32_t)v;
-        HIPCHK(c, hipMemcpyAsync(c->d_bt, iota.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->bw.d_bt.get(), iota.data(), n * 4, hipMemcpyHostToDevice, c->stream));
         if ((rc = bwd_count(c, (uint32_t)n, rmax, r))) return rc; // (synchronises)
     }
     if (r.chunks.size() == 1 && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
@@ -3118,13 +3097,13 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
 // quarters of a wave idle, and while the gathers' 64 nb E bytes stay under the transpose's 16 n nb, E < n / 4.
 static bool want_by_slot(const fora_ctx *c, int nb, uint64_t entries) {
     if (c->opt_.tgt_lanes >= 0) return c->opt_.tgt_lanes == 0;
-    return nb >= 16 && entries >= (uint64_t)c->n / 4;
+    return nb >= 16 && entries >= (uint64_t)c->g.n / 4;
 }
 
 // The combine of a batch: the walk slabs of the nb slots (slot-major in d_ppr) with the entries of every chunk into the
 // zeroed block `out` ([nb][nt]).
 static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t nt, unsigned long long *out) {
-    const uint64_t n = (uint64_t)c->n;
+    const uint64_t n = (uint64_t)c->g.n;
     const bool by_slot = want_by_slot(c, nb, r.off[nt]);
     int h;
     if (by_slot) {
@@ -3150,11 +3129,11 @@ static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t 
         h = ev_begin(c, 12);
         if (by_slot)
             hipLaunchKernelGGL((k_bippr_combine_targets<true>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
-                               (const uint64_t *)c->d_boff, (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0,
+                               (const uint64_t *)c->bw.d_boff.get(), (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0,
                                t1 - t0, (uint32_t)span, nt, out);
         else
             hipLaunchKernelGGL((k_bippr_combine_targets<false>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
-                               (const uint64_t *)c->d_boff, (const uint32_t *)c->d_enode, (const uint64_t *)c->d_ep, (const uint64_t *)c->d_er, t0,
+                               (const uint64_t *)c->bw.d_boff.get(), (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0,
                                t1 - t0, (uint32_t)span, nt, out);
         ev_end(c, h);
     }
@@ -3167,10 +3146,10 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
     if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (int rc = check_batch_args(c, targets, nt, "target")) return rc;
     if (!(epsilon > 0)) return fail(c, FORA_E_ARG, "epsilon must be > 0");
-    if (c->m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
+    if (c->g.m_attr <= 0) return fail(c, FORA_E_ARG, "m of the graph must be > 0");
     if (!(rmax_scale > 0) || !std::isfinite(rmax_scale)) return fail(c, FORA_E_ARG, "rmax_scale must be > 0");
-    const double delta = 1.0 / c->n, pfail = 1.0 / c->n;
-    double rmax = epsilon * sqrt(c->m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, as bippr_batch_impl
+    const double delta = 1.0 / c->g.n, pfail = 1.0 / c->g.n;
+    double rmax = epsilon * sqrt(c->g.m_attr * 1.0 * delta / 3.0 / log(2.0 / pfail)); // bippr_setting, as bippr_batch_impl
     rmax *= rmax_scale;
     const double omega = rmax * 3 * log(2.0 / pfail) / delta / epsilon / epsilon;
     if (int rc = check_bwd_rmax(c, rmax)) return rc;
@@ -3203,13 +3182,13 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
     const int per = even_batch(nq, c->ws.B);
     // the estimate block of a batch and its row sums
     const size_t words = (size_t)per * (T + 1);
-    if (c->d_tgt_est.ensure(words) != hipSuccess || (est_out && c->d_tgt_f64.ensure((size_t)per * T) != hipSuccess)) {
+    if (c->bw.d_tgt_est.ensure(words) != hipSuccess || (est_out && c->bw.d_tgt_f64.ensure((size_t)per * T) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(c, FORA_E_NOMEM, "no device memory for the estimate block");
     }
     if ((rc = ensure_reverse_csr(c))) return rc;
     if ((rc = ensure_bwd_targets(c, T))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_bt, targets, T * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->bw.d_bt.get(), targets, T * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = bwd_count(c, (uint32_t)nt, rmax, r))) return rc; // (synchronises)
     if (r.chunks.size() == 1 && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
     std::vector<uint64_t> sums((size_t)per);
@@ -3218,15 +3197,15 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
         const uint64_t cells = (uint64_t)nb * T;
         const int hb = ev_begin(c, 5);
         if ((rc = reset_batch_state(c, nb, sources + b0))) return rc;
-        HIPCHK(c, c->d_tgt_est.zero(c->stream, cells + (uint64_t)nb));
+        HIPCHK(c, c->bw.d_tgt_est.zero(c->stream, cells + (uint64_t)nb));
         const Dev d = make_dev(c, nb, false);
         launch_mc_walks(c, d, nb, w);
-        unsigned long long *const est = (unsigned long long *)c->d_tgt_est.get();
+        unsigned long long *const est = (unsigned long long *)c->bw.d_tgt_est.get();
         if ((rc = bippr_combine_targets(c, r, nb, T, est))) return rc;
         {
             const int h = ev_begin(c, 12);
             hipLaunchKernelGGL(k_bippr_targets_finish, dim3((unsigned)std::min<uint64_t>((T + BLOCK - 1) / BLOCK, 64), (unsigned)nb), dim3(BLOCK), 0,
-                               c->stream, (const uint64_t *)c->d_tgt_est.get(), T, est_out ? c->d_tgt_f64.get() : nullptr, est + cells);
+                               c->stream, (const uint64_t *)c->bw.d_tgt_est.get(), T, est_out ? c->bw.d_tgt_f64.get() : nullptr, est + cells);
             ev_end(c, h);
         }
         HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -3234,11 +3213,11 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
         c->timing.walks += w.W * (uint64_t)nb;
         c->timing.walk_steps += *c->ws.h_steps_pin.get();
         if (stats) {
-            HIPCHK(c, hipMemcpy(sums.data(), c->d_tgt_est.get() + cells, (size_t)nb * 8, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(sums.data(), c->bw.d_tgt_est.get() + cells, (size_t)nb * 8, hipMemcpyDeviceToHost));
             for (int i = 0; i < nb; i++) fill_stats(b0 + i, sums[(size_t)i]);
         }
-        if (est_fix_out) HIPCHK(c, hipMemcpy(est_fix_out + (uint64_t)b0 * T, c->d_tgt_est.get(), cells * 8, hipMemcpyDeviceToHost));
-        if (est_out) HIPCHK(c, hipMemcpy(est_out + (uint64_t)b0 * T, c->d_tgt_f64.get(), cells * 8, hipMemcpyDeviceToHost));
+        if (est_fix_out) HIPCHK(c, hipMemcpy(est_fix_out + (uint64_t)b0 * T, c->bw.d_tgt_est.get(), cells * 8, hipMemcpyDeviceToHost));
+        if (est_out) HIPCHK(c, hipMemcpy(est_out + (uint64_t)b0 * T, c->bw.d_tgt_f64.get(), cells * 8, hipMemcpyDeviceToHost));
     }
     fill_bwd_stats(c, r, T, bwd, c->timing.walk_ms - walk_ms0);
     return FORA_OK;
@@ -3268,13 +3247,13 @@ int fora_hip_reset_timing(fora_ctx *c) {
     if (!c) return FORA_E_ARG;
     c->timing = fora_timing{};
     (void)hipSetDevice(c->device);
-    (void)hipMemset(c->d_stamps, 0, 32 * sizeof(unsigned long long));
+    (void)hipMemset(c->d_stamps.get(), 0, 32 * sizeof(unsigned long long));
     return FORA_OK;
 }
 int fora_hip_get_stamps(fora_ctx *c, uint64_t *out32) {
     if (!c || !out32) return FORA_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(out32, c->d_stamps, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out32, c->d_stamps.get(), 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return FORA_OK;
 }
 int fora_hip_get_timing(fora_ctx *c, fora_timing *out) {
