@@ -24,10 +24,11 @@ static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *co
 static int build_quad_copies(fora_ctx *c);
 namespace {
 
-struct EvPair {
-    hipEvent_t a, b;
-    int kind; // 0 pop, 1 expand, 2 walk_alloc, 3 walk, 4 other, 5 batch, 6 accum, 7 walk accum, 8 round sweep, 9 tail, 10 team push, 11 backward push, 12 bippr combine
-};
+// What an event pair times, named after the fora_timing field it feeds.  The switch of ev_collect is the one place that says which
+// launches count under which kind.
+enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
+              EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT };
+struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
 
@@ -141,10 +142,28 @@ public:
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
 
+// What a workspace is sized for (plan_workspace): the one copy of these words.  Every reader goes through Workspace::plan.
+struct WsPlan {
+    bool binned = false;                // bucketed push; false: the one-atomic-per-edge path (option `direct`)
+    int nbins = 0, pbins = 0;           // bins of the graph; bins per pass (bucket-array stride)
+    uint32_t sub = 0, bk_cap = 0;       // sub-buckets per (slot, bin) = producer workgroups per slot; capacity of one sub-bucket
+    uint32_t ov_cap = 0, dbm_words = 0; // per slot: entries of the bucket-overflow list, words of the deferral bitmap
+    uint64_t segq_cap = 0, wit_cap = 0; // per slot: frontier positions, walk items
+    uint64_t wl_cap = 0, seg_cap = 0;   // all slots: entries of a slab, PushSeg entries of the scratch
+    uint32_t team_rlog_cap = 0;         // entries of a member's reserve log per slot (Workspace::d_team_rlog_id): follows from the memory that is free when
+                                        // the team buffers are allocated, so ensure_workspace writes it there, not plan_workspace
+    uint64_t segs = 0, scratch = 0, per_slot = 0; // planning intermediates, per slot: PushSeg entries, scratch bytes, bytes in all
+    bool fits(const WsPlan &want) const { // can buffers sized for this plan serve a call that plans `want` for the same slot count?
+        return binned == want.binned && pbins == want.pbins && seg_cap >= want.seg_cap && wit_cap >= want.wit_cap && bk_cap == want.bk_cap && sub == want.sub;
+    }
+};
+
 // Everything that lives and dies with one plan of the query slots (ensure_workspace; the lazily allocated members: their
-// first user).  free_workspace assigns a fresh one: the initialisers below are the reset values.
+// first user), the plan included.  free_workspace assigns a fresh one: the initialisers below are the reset values.  ensure_workspace builds
+// into a local value and moves it in after its last step: the workspace is complete or empty (B == 0, an empty plan), never half-built.
 struct Workspace {
     int B = 0, B_memcap = 0; // slots; slots that fitted the free memory when the workspace was planned (>= B)
+    WsPlan plan;
     DevBuf<uint64_t> d_residue, d_ppr, d_wl[2];
     DevBuf<unsigned char> d_scratch; // PushSeg list during the push, WalkItem list during the walks
     DevBuf<unsigned long long> d_counters; // wl_count | seg_count | wit_count | tot_steps
@@ -258,65 +277,54 @@ struct SparseResult {
     DevBuf<double> d_stage;           // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
 };
 
+// The loose words of the context, grouped by role.
+struct Params { // fora_hip_set_params / _raw
+    bool have = false;
+    double alpha = 0.2, epsilon = 0.5, rmax_scale = 1.0, rmax = 0, omega = 0;
+    int opt = 0; uint64_t seed = 0;
+};
+struct Balanced { // --balanced (query.h:848-884): cost model in seconds (fora_hip_set_balanced), per-slot results of the last batch
+    bool on = false;
+    double c_pop = 2.0e-11, c_edge = 2.4e-11, t_walk = 6.5e-11, t_idx = 2.2e-11, start = 8;
+    std::vector<double> h_rmax_used; std::vector<int32_t> h_rounds;
+};
+struct TeamState { // run state of the team push (fora_team.h)
+    bool dirty = false;        // a launch ended with an error flag: its reserve accumulators (TeamDev::rsvl) may not be zero
+    bool timeout_seen = false; // the last device error was ERR_TEAM_TIMEOUT (with_bucket_retry runs the call again without the team push)
+    int suspend = 0;           // calls left that push with the bucketed kernels after a team time-out
+    uint64_t fallbacks = 0;    // calls re-run that way so far (fora_hip_get_option "team_fallbacks")
+    bool coop_ok = false;      // launch k_push_team cooperatively (option team_coop, device attribute)
+    bool coop_failed = false;  // hipLaunchCooperativeKernel refused once: plain launches from then on
+};
+struct BucketRetry { // see with_bucket_retry
+    uint32_t scale = 1;      // bucket capacity multiplier, doubled after a bucket overflow
+    uint32_t scale_topk = 1; // ... of the calls that plan with a divisor (div > 1: the top-k driver on wide graphs).  Its own word: those calls start at 1 / 16 of a
+                             // query's buckets and overflow far more often; a doubling there must not shrink the batches of later query / power-iteration calls
+    uint32_t div = 1;        // bucket capacity divisor of the call in progress (top-k: TOPK_BK_DIV on wide graphs, plan_workspace).  Not part of
+                             // the plan: a kept workspace may have been planned under another call's divisor
+    bool overflow = false;   // the last device error was ERR_BUCKET_OVERFLOW
+    uint64_t retries = 0;    // calls re-run with doubled buckets so far (fora_hip_get_option "bucket_retries")
+};
+struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what they add up to
+    bool profiling = true;
+    std::vector<EvPair> ev_pool; size_t ev_used = 0;
+    fora_timing total{};
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT)
+};
+
 struct fora_ctx {
     int device = 0;
-    Tunables opt_;
     hipStream_t stream = nullptr;
-    std::string err;
     hipDeviceProp_t prop{};
-
-    Graph g;
-    uint32_t team_rlog_cap = 0;      // entries of a member's reserve log per slot (Workspace::d_team_rlog_id)
-    bool team_dirty = false;         // a launch ended with an error flag: its reserve accumulators (TeamDev::rsvl) may not be zero
-    bool team_timeout_seen = false;  // the last device error was ERR_TEAM_TIMEOUT (with_retry runs the call again without the team push)
-    int team_suspend = 0;            // calls left that push with the bucketed kernels after a team time-out
-    uint64_t team_fallbacks = 0;     // calls re-run that way so far (fora_hip_get_option "team_fallbacks")
-    bool team_coop_ok = false;       // launch k_push_team cooperatively (option team_coop, device attribute)
-    bool team_coop_failed = false;   // hipLaunchCooperativeKernel refused once: plain launches from then on
-
-    // params
-    bool have_params = false;
-    double alpha = 0.2, epsilon = 0.5, rmax_scale = 1.0, rmax = 0, omega = 0;
-    int opt = 0;
-    uint64_t seed = 0;
-
-    Index ix;
-
-    // workspace: its buffers (ws) and the plan they were sized for, which outlives them (a re-plan compares with it)
-    Workspace ws;
-    int batch_req = 0;
-    uint64_t wl_cap = 0, seg_cap = 0, wit_cap = 0, segq_cap = 0;
-    DevBuf<unsigned long long> d_stamps; // diagnostic builds (-DFORA_STAMPS)
-    // bucketed push (n <= MAX_BINS * BIN_SIZE)
-    bool binned = false;
-    int nbins = 0, pbins = 0; // bins of the graph; bins per pass (bucket-array stride)
-    uint32_t ov_cap = 0, dbm_words = 0;
-    uint32_t bk_cap = 0, sub = 0; // capacity of one sub-bucket; sub-buckets per (slot, bin) = producer workgroups per slot
-    uint64_t bin_launches = 0;       // parity picks the counter set
+    std::string err;
+    Tunables opt_;
+    int grid_blocks = 2048; // (option `grid`)
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp;
+    int batch_req = 0;         // the caller's request (fora_hip_set_batch), not part of a plan
+    uint64_t bin_launches = 0; // parity picks the counter set
     std::vector<QState> h_qs;
-    uint32_t bk_scale = 1;        // bucket capacity multiplier, doubled after a bucket overflow (see with_bucket_retry)
-    uint32_t bk_scale_topk = 1;   // ... of the calls that plan with a divisor (bk_div > 1: the top-k driver on wide graphs).  Its own word: those calls start at 1 / 16 of a
-                                  // query's buckets and overflow far more often; a doubling there must not shrink the batches of later query / power-iteration calls
-    uint64_t bucket_retries = 0;  // calls re-run with doubled buckets so far (fora_hip_get_option "bucket_retries")
-    uint32_t bk_div = 1;          // bucket capacity divisor of the call in progress (top-k: TOPK_BK_DIV on wide graphs, plan_workspace)
-    bool bucket_overflow = false; // the last device error was ERR_BUCKET_OVERFLOW
-    // --balanced (query.h:848-884): cost model in seconds
-    bool balanced = false;
-    double c_pop = 2.0e-11, c_edge = 2.4e-11, t_walk = 6.5e-11, t_idx = 2.2e-11, bal_start = 8;
-    std::vector<double> h_rmax_used;
-    std::vector<int32_t> h_rounds;
-
-    // timing
-    bool profiling = true;
-    std::vector<EvPair> ev_pool;
-    size_t ev_used = 0;
-    fora_timing timing{};
-    int grid_blocks = 2048;
-
-    BwdBufs bw;
-    double bwd_ms = 0, combine_ms = 0; // event times of the call in progress (EvPair kinds 11, 12)
-    SparseResult sp;
-    double sp_compact_ms = 0;          // event time of the call in progress (EvPair kind 13)
+    Params par; Balanced bal; TeamState team_run; BucketRetry retry; Timing tm;
+    DevBuf<unsigned long long> d_stamps; // diagnostic builds (-DFORA_STAMPS)
 };
 
 namespace {
@@ -391,7 +399,6 @@ static uint32_t want_bk_cap_wide(const fora_ctx *c) { // messages per (slot, bin
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(196608, (uint64_t)(1.4 * (double)c->g.nnz / (double)std::max<uint64_t>(1, nbins))), 1u << 26);
 }
 
-struct WsPlan { uint64_t segs, wits, scratch, per_slot; int nbins, pbins; uint32_t bk_cap, sub; uint64_t segq_cap; bool binned; };
 // (the wide / narrow choice changes bk_cap, which forces a re-plan of the workspace)
 // sub-buckets per (slot, bin) = producer workgroups per slot (Dev::bk_w): ~16 k producer workgroups per launch
 static uint32_t want_sub(const fora_ctx *c, int slots) {
@@ -403,14 +410,15 @@ static uint32_t want_sub(const fora_ctx *c, int slots) {
     if (want_wide(c)) return slots >= 256 ? 32u : slots >= 32 ? 64u : (uint32_t)MAX_SUB;
     return (uint32_t)std::min(MAX_SUB, std::max(16, 16384 / std::max(1, slots)));
 }
+// the whole plan of a workspace of `slots` slots (but team_rlog_cap, see WsPlan); reads the graph, the options and BucketRetry only
 static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
-    WsPlan p{};
+    WsPlan p;
     const uint64_t n = (uint64_t)c->g.n;
     p.binned = want_binned(c);
-    p.segs = n + (uint64_t)c->g.nnz / PUSH_SEG + 64; // per slot
+    p.segs = n + (uint64_t)c->g.nnz / PUSH_SEG + 64;
     double walks = omega_hint > 0 ? omega_hint : 0;
     if (walks > 4e12) walks = 4e12;
-    p.wits = n + n / WALK_SEG + (uint64_t)(walks / WALK_SEG) + 64;
+    p.wit_cap = n + n / WALK_SEG + (uint64_t)(walks / WALK_SEG) + 64;
     if (p.binned) {
         p.nbins = (int)bins_of(c);
         p.pbins = want_wide(c) ? std::min(p.nbins, want_pass_bins(c, p.nbins)) : std::max(p.nbins, (int)c->g.walk.dg.nbx); // narrow: the walk results in bucket order may need a bin more
@@ -419,21 +427,25 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
           // `bkcap` option (tests) sets it directly
             const uint64_t total = (uint64_t)(want_wide(c) ? want_bk_cap_wide(c) : want_bk_cap(c));
             uint64_t cap = c->opt_.bkcap > 0 ? total : (total + total / 4 + p.sub - 1) / p.sub;
-            // the top-k driver's rounds push from small frontiers (delta starts at 1 / 10k): its buckets start at 1 / bk_div of
+            // the top-k driver's rounds push from small frontiers (delta starts at 1 / 10k): its buckets start at 1 / BucketRetry::div of
             // a query's -- a slot is a fifth of the memory, a batch holds that many more of them, and every per-round launch
             // (k_push_tail: ONE workgroup per slot; the slab sweeps; the walk kernels) works on that many more slots at once.
             // A round that does overflow is run again with doubled buckets like any other (with_bucket_retry)
-            cap = std::min<uint64_t>(std::max<uint64_t>(cap * (c->bk_div > 1 ? c->bk_scale_topk : c->bk_scale) / std::max<uint32_t>(1, c->bk_div), 64), 1u << 28);
+            cap = std::min<uint64_t>(std::max<uint64_t>(cap * (c->retry.div > 1 ? c->retry.scale_topk : c->retry.scale) / std::max<uint32_t>(1, c->retry.div), 64), 1u << 28);
             p.bk_cap = (uint32_t)((cap + 15) & ~15ull);
         }
-        p.segq_cap = n; // frontier positions
-        p.scratch = (p.wits * sizeof(WalkItemP) + 95) / 96 * 96; // whole PushSeg (24 B) and WalkItemP (32 B) entries: `keepable` compares seg_cap * sizeof(PushSeg) with it
+        p.segq_cap = n;
+        p.ov_cap = c->opt_.ovcap > 0 ? (uint32_t)c->opt_.ovcap : (uint32_t)std::max<uint64_t>(262144, n / 8); // scales with the graph; the option: tests
+        p.dbm_words = (uint32_t)((uint64_t)p.nbins << (bin_shift(c) - 6));
+        p.scratch = (p.wit_cap * sizeof(WalkItemP) + 95) / 96 * 96; // whole PushSeg (24 B) and WalkItemP (32 B) entries
         p.per_slot = n * 8 * 2 + n * 4 * 2 + p.segq_cap * 8 * 2 + std::max<uint64_t>(262144, n / 8) * 12 + (uint64_t)p.pbins * p.sub * p.bk_cap * (want_wide(c) ? 8 : 12) + p.scratch +
                      (c->opt_.defer > 0 ? n * 4 * 2 : 0) + n / 4 + 64 + (uint64_t)p.sub * c->g.hub.hubs * 8; // + deferred lists and bitmaps, hub sums
     } else {
-        p.scratch = (std::max(p.segs * sizeof(PushSeg), p.wits * sizeof(WalkItemP)) + 95) / 96 * 96;
+        p.scratch = (std::max(p.segs * sizeof(PushSeg), p.wit_cap * sizeof(WalkItemP)) + 95) / 96 * 96;
         p.per_slot = n * 8 * 4 + p.scratch;
     }
+    p.wl_cap = (uint64_t)slots * n;
+    p.seg_cap = (uint64_t)slots * p.scratch / sizeof(PushSeg);
     return p;
 }
 
@@ -595,7 +607,7 @@ static TeamCtl team_ctl_layout(uint32_t nteams, int slots) {
     const size_t sync = 64, slot_seq = sync + (size_t)nteams * 5 * 16 * 2;
     return {sync, slot_seq, slot_seq + (size_t)nteams * ((size_t)slots + 2)};
 }
-int team_fits(fora_ctx *c);
+int team_fits(fora_ctx *c, Workspace &w);
 int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     if (!c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
     if (int rt = ensure_team(c)) return rt;
@@ -607,22 +619,15 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         if (int rh = build_hub_copy(c, c->g.h_row_ptr.data(), col.data())) return rh;
         if (int rq = build_quad_copies(c)) return rq;
     }
-    WsPlan p = plan_workspace(c, omega_hint, 1024); // bytes per slot hardly depend on the slot count (sub-bucket rounding)
-    const uint64_t n = (uint64_t)c->g.n;
-    // an existing workspace with the same layout is kept if it has enough slots: as many as the call can use, or as
-    // many as an automatic plan would get at most (1024)
-    auto keepable = [&](int need) {
-        if (c->ws.B <= 0 || c->ws.B < need) return false;
-        const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B);
-        if ((c->g.team.T != 0) != bool(c->ws.d_team_msg)) return false;
-        return c->binned == pe.binned && c->pbins == pe.pbins && c->seg_cap * sizeof(PushSeg) >= (uint64_t)c->ws.B * pe.scratch &&
-               c->wit_cap >= pe.wits && c->bk_cap == pe.bk_cap && c->sub == pe.sub;
-    };
     {
-        // slots the call can use: its queries, at most 1024, at most what memory allowed when the workspace was planned
+        // An existing workspace is kept if it has enough slots -- as many as the call can use (its queries, at most 1024, at most what memory allowed when
+        // the workspace was planned) --, team buffers exactly when the graph takes the team path, and a plan that fits the one this call would make for its slots.
         int need = c->batch_req > 0 ? c->batch_req : std::min(want_slots > 0 ? want_slots : 1024, 1024);
         if (c->batch_req == 0 && c->ws.B > 0 && c->ws.B_memcap > 0) need = std::min(need, c->ws.B_memcap);
-        if (keepable(need)) { const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B); return ensure_row_split(c, pe.nbins, pe.pbins); }
+        if (c->ws.B > 0 && c->ws.B >= need && (c->g.team.T != 0) == bool(c->ws.d_team_msg)) {
+            const WsPlan pe = plan_workspace(c, omega_hint, c->ws.B);
+            if (c->ws.plan.fits(pe)) return ensure_row_split(c, pe.nbins, pe.pbins);
+        }
     }
     int B = c->batch_req > 0 ? c->batch_req : 0;
     if (B == 0) {
@@ -637,27 +642,26 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
             const uint64_t team_bytes = nt * team_bytes_per_team(c, 1u << 17);
             budget -= std::min<uint64_t>(budget / 2, team_bytes);
         }
-        B = (int)std::min<uint64_t>(1024, std::max<uint64_t>(1, budget / p.per_slot)); // ws, 1000 queries: 2845 q/s at 256, 3035 at 512, 3101 at 1000
+        const uint64_t per_slot = plan_workspace(c, omega_hint, 1024).per_slot; // bytes per slot hardly depend on the slot count (sub-bucket rounding)
+        B = (int)std::min<uint64_t>(1024, std::max<uint64_t>(1, budget / per_slot)); // ws, 1000 queries: 2845 q/s at 256, 3035 at 512, 3101 at 1000
     }
     B = std::max(1, B);
     const int memcap = B;
     if (want_slots > 0 && c->batch_req == 0) B = std::min(B, std::max(want_slots, 1));
-    p = plan_workspace(c, omega_hint, B);
-    const uint64_t scratch = (uint64_t)B * p.scratch;
     free_workspace(c);
-    const uint64_t slab = (uint64_t)B * n;
+    Workspace w; // moved into c->ws after the last step: a failure on the way leaves no workspace
+    w.plan = plan_workspace(c, omega_hint, B);
+    WsPlan &p = w.plan;
+    const uint64_t slab = p.wl_cap;
     const size_t ctr = (size_t)B * CSTRIDE; // one counter line per slot
-    Workspace &w = c->ws;
     HIPCHK(c, w.d_residue.alloc(slab));
     HIPCHK(c, w.d_ppr.alloc(slab));
     if (p.binned) {
         for (auto &fl : w.d_fl) HIPCHK(c, fl.alloc(slab));
         HIPCHK(c, w.d_fl_count.alloc(2 * ctr));
         for (auto &tab : w.d_inc_tab) HIPCHK(c, tab.alloc((uint64_t)B * p.segq_cap));
-        c->ov_cap = (uint32_t)std::max<uint64_t>(262144, n / 8); // bucket-overflow list, scales with the graph
-        if (c->opt_.ovcap > 0) c->ov_cap = (uint32_t)c->opt_.ovcap; // tests
-        HIPCHK(c, w.d_ov_w.alloc((uint64_t)B * c->ov_cap));
-        HIPCHK(c, w.d_ov_inc.alloc((uint64_t)B * c->ov_cap));
+        HIPCHK(c, w.d_ov_w.alloc((uint64_t)B * p.ov_cap));
+        HIPCHK(c, w.d_ov_inc.alloc((uint64_t)B * p.ov_cap));
         HIPCHK(c, w.d_ov_count.alloc(2 * ctr));
         HIPCHK(c, w.d_ov_bin.alloc(2 * (size_t)B * p.nbins));
         const uint64_t buckets = (uint64_t)B * p.pbins * p.sub;
@@ -665,8 +669,7 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
         HIPCHK(c, w.d_bk_inc.alloc(buckets * p.bk_cap));
         HIPCHK(c, w.d_bk_count.alloc(buckets));
         HIPCHK(c, w.h_flc.alloc((size_t)FLC_RING * ctr));
-        c->dbm_words = (uint32_t)((uint64_t)p.nbins << (bin_shift(c) - 6));
-        HIPCHK(c, w.d_dbm.alloc(2 * (size_t)B * c->dbm_words));
+        HIPCHK(c, w.d_dbm.alloc(2 * (size_t)B * p.dbm_words));
         HIPCHK(c, w.d_dflag.alloc(2 * (size_t)B * p.nbins));
         if (c->opt_.defer > 0) HIPCHK(c, w.d_dl.alloc(2 * slab)); // k_push_tail's deferred lists: only with the option (changing it re-plans the workspace)
         if (c->g.hub.hubs && c->g.hub.shift == bin_shift(c)) HIPCHK(c, w.d_hubsum.alloc((size_t)B * p.sub * c->g.hub.hubs));
@@ -677,25 +680,25 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
             size_t fr = 0, tot = 0;
             HIPCHK(c, hipMemGetInfo(&fr, &tot));
             // pops of one member in one slot (ws-sized graph at eps 0.5: 43 k on average); beyond it: rsvl.  Tight memory: shorter logs
-            c->team_rlog_cap = 1u << 17;
-            while (c->team_rlog_cap > 1024 && team_bytes_per_team(c, c->team_rlog_cap) > fr / 4) c->team_rlog_cap /= 2;
-            nteams = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nteams, (uint64_t)(fr / 2) / std::max<uint64_t>(1, team_bytes_per_team(c, c->team_rlog_cap))));
+            p.team_rlog_cap = 1u << 17;
+            while (p.team_rlog_cap > 1024 && team_bytes_per_team(c, p.team_rlog_cap) > fr / 4) p.team_rlog_cap /= 2;
+            nteams = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nteams, (uint64_t)(fr / 2) / std::max<uint64_t>(1, team_bytes_per_team(c, p.team_rlog_cap))));
             const size_t members = (size_t)nteams * T;
             HIPCHK(c, w.d_team_msg.alloc((size_t)nteams * 2 * c->g.team.cap + 16 + diag::TEAM_MSG_PROBE_WORDS)); // (probe words: 0 in the product build)
             HIPCHK(c, w.d_team_inct.alloc(members * 2 * (c->g.team.R + 64 + c->g.team.H)));
             HIPCHK(c, w.d_team_rsvl.alloc(members * c->g.team.R));
             HIPCHK(c, w.d_team_rsvl.zero(c->stream)); // every slot leaves it zero again
-            HIPCHK(c, w.d_team_rlog_id.alloc(members * c->team_rlog_cap));
-            HIPCHK(c, w.d_team_rlog_val.alloc(members * c->team_rlog_cap));
+            HIPCHK(c, w.d_team_rlog_id.alloc(members * p.team_rlog_cap));
+            HIPCHK(c, w.d_team_rlog_val.alloc(members * p.team_rlog_cap));
             HIPCHK(c, w.d_team_cnt.alloc(members * 2 * T));
             HIPCHK(c, w.d_team_ctl.alloc(team_ctl_layout(nteams, B).total));
             w.team_n = nteams;
-            if (int rf = team_fits(c)) return rf;
+            if (int rf = team_fits(c, w)) return rf;
         }
     } else {
         for (auto &wl : w.d_wl) HIPCHK(c, wl.alloc(slab));
     }
-    HIPCHK(c, w.d_scratch.alloc(scratch));
+    HIPCHK(c, w.d_scratch.alloc((uint64_t)B * p.scratch));
     HIPCHK(c, w.d_wit_count.alloc(ctr));
     HIPCHK(c, w.d_sw.alloc(2 * ctr));
     HIPCHK(c, w.d_sw.zero(c->stream)); // self-resetting
@@ -709,44 +712,43 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     HIPCHK(c, w.h_qs_pin.alloc((size_t)B));
     HIPCHK(c, w.h_steps_pin.alloc(1));
     w.B = B; w.B_memcap = memcap;
-    c->binned = p.binned; c->nbins = p.nbins; c->pbins = p.pbins; c->bk_cap = p.bk_cap; c->sub = p.sub; c->segq_cap = p.segq_cap;
     if (int rs = ensure_row_split(c, p.nbins, p.pbins)) return rs;
-    c->wl_cap = slab; c->seg_cap = scratch / sizeof(PushSeg);
-    c->wit_cap = p.wits; // per slot
+    c->ws = std::move(w);
     c->h_qs.resize(B);
     return FORA_OK;
 }
 
 Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega = -1) {
-    if (rmax < 0) rmax = c->rmax;
-    if (omega < 0) omega = c->omega;
+    if (rmax < 0) rmax = c->par.rmax;
+    if (omega < 0) omega = c->par.omega;
     Dev d{};
     const Workspace &w = c->ws;
+    const WsPlan &p = c->ws.plan;
     const size_t B = (size_t)w.B, ctr = B * CSTRIDE;
     d.n = c->g.n; d.nq = nq;
     d.rowinfo = c->g.d_rowinfo.get(); d.row_ptr = c->g.d_row_ptr.get(); d.col = c->g.d_col.get(); d.deg = c->g.d_deg.get();
     d.rp32 = c->g.d_rp32.get(); d.colp = c->g.d_colp.get(); d.colbits = c->g.colbits;
     d.colp32 = (uint64_t)c->g.nnz * c->g.colbits < (1ull << 32) ? 1 : 0;
     d.dg = c->g.walk.dg;
-    d.residue = w.d_residue.get(); d.ppr = w.d_ppr.get(); d.wl_cap = c->wl_cap;
-    d.seg = (PushSeg *)w.d_scratch.get(); d.seg_cap = c->seg_cap;
-    d.wit = (WalkItemP *)w.d_scratch.get(); d.wit_cap = c->wit_cap;
+    d.residue = w.d_residue.get(); d.ppr = w.d_ppr.get(); d.wl_cap = p.wl_cap;
+    d.seg = (PushSeg *)w.d_scratch.get(); d.seg_cap = p.seg_cap;
+    d.wit = (WalkItemP *)w.d_scratch.get(); d.wit_cap = p.wit_cap;
     d.wl_count = w.d_counters.get();
     d.seg_count = w.d_counters.get() + (MAX_LEVELS + 2);
     d.wit_count = w.d_wit_count.get();
     d.tot_steps = w.d_counters.get() + 2 * (size_t)(MAX_LEVELS + 2) + 1;
     d.qs = w.d_qs.get(); d.src = w.d_src.get(); d.err = w.d_err.get();
-    d.afix = (uint64_t)std::ldexp(c->alpha, 62);
+    d.afix = (uint64_t)std::ldexp(c->par.alpha, 62);
     double t = std::ceil(std::ldexp(rmax, 62));
     d.t1 = t >= 9223372036854775808.0 ? (~0ull >> 1) : (t < 1.0 ? 1 : (uint64_t)t);
-    d.alpha32 = (uint32_t)(c->alpha * 4294967296.0);
-    d.seed_lo = (uint32_t)c->seed; d.seed_hi = (uint32_t)(c->seed >> 32);
-    d.alpha = c->alpha; d.omega = omega; d.opt = c->opt;
-    d.binned = c->binned ? 1 : 0; d.nbins = c->nbins; d.wide = c->binned && want_wide(c) ? 1 : 0;
-    d.pbins = c->pbins; d.bin_lo = 0; d.bin_cnt = std::min(c->pbins, c->nbins);
+    d.alpha32 = (uint32_t)(c->par.alpha * 4294967296.0);
+    d.seed_lo = (uint32_t)c->par.seed; d.seed_hi = (uint32_t)(c->par.seed >> 32);
+    d.alpha = c->par.alpha; d.omega = omega; d.opt = c->par.opt;
+    d.binned = p.binned ? 1 : 0; d.nbins = p.nbins; d.wide = p.binned && want_wide(c) ? 1 : 0;
+    d.pbins = p.pbins; d.bin_lo = 0; d.bin_cnt = std::min(p.pbins, p.nbins);
     d.col_push = c->g.split.d_col_push.get() ? c->g.split.d_col_push.get() : c->g.d_col.get();
     d.row_split = c->g.split.d_row_split.get();
-    d.npass = c->pbins > 0 ? (c->nbins + c->pbins - 1) / c->pbins : 1;
+    d.npass = p.pbins > 0 ? (p.nbins + p.pbins - 1) / p.pbins : 1;
     d.pass = 0;
     d.acc_group = 1; // (set per launch: acc_grid)
     // Dispatch order of the wide kernels (Dev::slot_major), measured per kernel (profiles/r06_slot_major.txt): slot-major pays for the bin kernel
@@ -754,13 +756,13 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     // 620 -> 930 ms) and for the indexed walks of query calls (LJ-sized ~ - 5 %, Twitter-2010-sized - 2 %); it loses for the accumulate, the walk
     // allocation and everything in the top-k drivers.  FETCH_SIZE and TCC hits / misses are the same in both orders: if it is reuse, it is in the memory-side Infinity Cache.
     d.slot_major = c->opt_.slot_major >= 0 ? (uint32_t)c->opt_.slot_major & 15u
-                   : (c->bk_div > 1 ? 0u : (4u | (nq >= 32 ? 1u : 0u)));
+                   : (c->retry.div > 1 ? 0u : (4u | (nq >= 32 ? 1u : 0u)));
     d.tiny_max = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.tiny, 0), 1023); // 512: ws accum 116 -> 113 ms per 3000 queries against 128; 2048: 119, 8192: 193 (the crossing list of the small-bucket path holds 1024)
     for (int par = 0; par < 2; par++) { // the two parity sets of a pair are the halves of one buffer (null while it is empty)
         d.fl[par] = w.d_fl[par].get(); d.inc_tab[par] = w.d_inc_tab[par].get();
         d.fl_count[par] = w.d_fl_count.part(par, ctr); d.tile_ctr[par] = w.d_tile_ctr.part(par, ctr);
-        d.ov_count[par] = w.d_ov_count.part(par, ctr); d.ov_bin[par] = w.d_ov_bin.part(par, B * c->nbins);
-        d.dbm[par] = w.d_dbm.part(par, B * c->dbm_words); d.dflag[par] = w.d_dflag.part(par, B * c->nbins);
+        d.ov_count[par] = w.d_ov_count.part(par, ctr); d.ov_bin[par] = w.d_ov_bin.part(par, B * p.nbins);
+        d.dbm[par] = w.d_dbm.part(par, B * p.dbm_words); d.dflag[par] = w.d_dflag.part(par, B * p.nbins);
         d.dl[par] = w.d_dl.part(par, B * c->g.n); d.wl[par] = w.d_wl[par].get();
     }
     d.sw_count = w.d_sw.part(0, ctr); d.sw_done = w.d_sw.part(1, ctr);
@@ -768,7 +770,7 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     d.stamps = c->d_stamps.get();
     d.round_div = 0;
     d.rounds = 1; // the query / push entry points raise it (k_round_sweep); top-k, --balanced and power iteration drive their own rounds
-    if (c->binned && c->g.hub.d_col_hub && w.d_hubsum && c->g.hub.shift == bin_shift(c) && c->pbins >= c->nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
+    if (p.binned && c->g.hub.d_col_hub && w.d_hubsum && c->g.hub.shift == bin_shift(c) && p.pbins >= p.nbins) { // one pass per level only: the passes of larger graphs read a row-sorted copy
         d.col_hub = c->g.hub.d_col_hub.get(); d.hub_node = c->g.hub.d_hub_node.get(); d.hub_first = c->g.hub.d_hub_first.get(); d.hubsum = w.d_hubsum.get(); d.hubs = c->g.hub.hubs;
         d.hub_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.hub_min, 1), 0x7FFFFFFF);
         d.tail_hubs = c->opt_.tail_hubs != 0 && (size_t)c->g.hub.hubs * 8 <= 40960 ? 1u : 0u; // (k_push_tail: 20 KiB of static LDS + the sums within 64 KiB)
@@ -778,63 +780,83 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
         d.col_hub4 = d.col_hub ? c->g.quad.d_col_hub4.get() : nullptr;
         if (d.col_hub && !d.col_hub4) d.col4 = nullptr; // (no padded hub copy: edges one by one)
     }
-    d.defer_k = TEST_PATHS && c->binned && w.d_dl ? (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer, 0), 8) : 0; // the direct path keeps plain levels
+    d.defer_k = TEST_PATHS && p.binned && w.d_dl ? (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer, 0), 8) : 0; // the direct path keeps plain levels
     d.defer_min = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.defer_min, 0), 0x7FFFFFFF);
-    d.dbm_words = c->dbm_words; d.segq_cap = c->segq_cap;
-    d.ov_w = w.d_ov_w.get(); d.ov_inc = w.d_ov_inc.get(); d.ov_cap = c->ov_cap;
-    d.bk_w = w.d_bk_w.get(); d.bk_inc = w.d_bk_inc.get(); d.bk_count = w.d_bk_count.get(); d.bk_cap = c->bk_cap; d.sub = c->sub;
+    d.dbm_words = p.dbm_words; d.segq_cap = p.segq_cap;
+    d.ov_w = w.d_ov_w.get(); d.ov_inc = w.d_ov_inc.get(); d.ov_cap = p.ov_cap;
+    d.bk_w = w.d_bk_w.get(); d.bk_inc = w.d_bk_inc.get(); d.bk_count = w.d_bk_count.get(); d.bk_cap = p.bk_cap; d.sub = p.sub;
     if (with_idx) { d.rw_idx = c->ix.d_rw_idx.get(); d.idx_off = c->ix.d_idx_off.get(); d.idx_cnt = c->ix.d_idx_cnt.get(); }
     return d;
 }
 
 // ---- event-pair timing of individual launches on the ctx stream
-int ev_begin(fora_ctx *c, int kind) {
-    if (!c->profiling) return -1;
-    if (c->ev_used == c->ev_pool.size()) {
-        EvPair p{};
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return -1;
-        c->ev_pool.push_back(p);
+// One pair of the pool around a span of launches: begun by the constructor (or begin()), ended by end() where stream work follows that must
+// stay outside the span, by the destructor otherwise -- so no return path leaves a pair open.  `profile` option off (or no event to be had): nothing.
+class EvSpan {
+    fora_ctx *c;
+    int h = -1; // the pair in Timing::ev_pool; -1: none open
+public:
+    explicit EvSpan(fora_ctx *ctx) : c(ctx) {} // not begun yet
+    EvSpan(fora_ctx *ctx, EvKind kind) : c(ctx) { begin(kind); }
+    EvSpan(const EvSpan &) = delete; EvSpan &operator=(const EvSpan &) = delete;
+    ~EvSpan() { end(); }
+    void begin(EvKind kind) {
+        end();
+        Timing &t = c->tm;
+        if (!t.profiling) return;
+        if (t.ev_used == t.ev_pool.size()) {
+            EvPair p{};
+            if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return;
+            t.ev_pool.push_back(p);
+        }
+        EvPair &p = t.ev_pool[t.ev_used];
+        p.kind = kind;
+        (void)hipEventRecord(p.a, c->stream);
+        h = (int)t.ev_used++;
     }
-    EvPair &p = c->ev_pool[c->ev_used];
-    p.kind = kind;
-    (void)hipEventRecord(p.a, c->stream);
-    return (int)c->ev_used++;
-}
-void ev_end(fora_ctx *c, int h) {
-    if (h >= 0) (void)hipEventRecord(c->ev_pool[h].b, c->stream);
-}
+    void end() { if (h >= 0) (void)hipEventRecord(c->tm.ev_pool[h].b, c->stream); h = -1; }
+};
 void ev_collect(fora_ctx *c) { // call after the stream is idle
-    for (size_t i = 0; i < c->ev_used; i++) {
+    Timing &t = c->tm;
+    for (size_t i = 0; i < t.ev_used; i++) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].a, c->ev_pool[i].b) != hipSuccess) continue;
-        switch (c->ev_pool[i].kind) {
-        case 0: c->timing.push_pop_ms += ms; c->timing.push_pop_launches++; break;
-        case 1: c->timing.push_expand_ms += ms; c->timing.push_expand_launches++; break;
-        case 2: c->timing.walk_alloc_ms += ms; break;
-        case 3: c->timing.walk_ms += ms; c->timing.walk_launches++; break;
-        case 4: c->timing.other_ms += ms; break;
-        case 5: c->timing.batch_ms += ms; c->timing.batches++; break;
-        case 6: c->timing.push_accum_ms += ms; c->timing.push_accum_launches++; break;
-        case 7: c->timing.walk_accum_ms += ms; break;
-        case 9: c->timing.push_tail_ms += ms; c->timing.push_tail_launches++; break;
-        case 10: c->timing.push_team_ms += ms; c->timing.push_team_launches++; break;
-        case 11: c->bwd_ms += ms; break;     // backward push: reported through fora_bwd_stats only (fora_timing keeps its layout)
-        case 12: c->combine_ms += ms; break;
-        case 13: c->sp_compact_ms += ms; break; // k_sparse_count / k_sparse_write: reported through fora_sparse_stats only
-        case 8: c->timing.push_accum_ms += ms; break; // k_round_sweep: part of the level's accumulate time, not a launch of its own in the counts
+        if (hipEventElapsedTime(&ms, t.ev_pool[i].a, t.ev_pool[i].b) != hipSuccess) continue;
+        fora_timing &f = t.total;
+        switch (t.ev_pool[i].kind) {
+        case EV_PUSH_POP: f.push_pop_ms += ms; f.push_pop_launches++; break;          // k_push_pop (direct path)
+        case EV_PUSH_EXPAND: f.push_expand_ms += ms; f.push_expand_launches++; break; // k_push_expand; the bin kernels k_pushq_bin
+        case EV_WALK_ALLOC: f.walk_alloc_ms += ms; break;                             // k_walk_alloc
+        case EV_WALK: f.walk_ms += ms; f.walk_launches++; break;                      // k_walk_idx (wide: with its accumulate passes), k_walk_dg / k_walk_online, k_walk_mc
+        case EV_OTHER: f.other_ms += ms; break;                                       // resets, k_init_batch, k_topk_frontier, k_copy_slab, k_ppr_sum, k_count_above, bounds, select, k_index_alloc
+        case EV_BATCH: f.batch_ms += ms; f.batches++; break;                          // a whole batch, from its reset to its close-out
+        case EV_PUSH_ACCUM: f.push_accum_ms += ms; f.push_accum_launches++; break;    // k_accum of a push level
+        case EV_WALK_ACCUM: f.walk_accum_ms += ms; break;                             // k_accum of the walk results (narrow layout)
+        case EV_ROUND_SWEEP: f.push_accum_ms += ms; break;                            // k_round_sweep: part of the level's accumulate time, not a launch of its own in the counts
+        case EV_PUSH_TAIL: f.push_tail_ms += ms; f.push_tail_launches++; break;       // k_push_tail
+        case EV_PUSH_TEAM: f.push_team_ms += ms; f.push_team_launches++; break;       // k_push_team
+        case EV_BWD: t.bwd_ms += ms; break;               // k_bwd_push: reported through fora_bwd_stats only (fora_timing keeps its layout)
+        case EV_COMBINE: t.combine_ms += ms; break;       // BiPPR's transposes, combines and finish: fora_bwd_stats only
+        case EV_SP_COMPACT: t.sp_compact_ms += ms; break; // k_sparse_count / k_sparse_write: reported through fora_sparse_stats only
         }
     }
-    c->ev_used = 0;
+    t.ev_used = 0;
 }
+// A call that fails leaves no pair behind (every entry point's last step): the next call's timings hold only its own launches.
+void drop_pairs(fora_ctx *c) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    c->tm.ev_used = 0;
+}
+int drop_pairs_unless_ok(fora_ctx *c, int rc) { if (rc != FORA_OK && c && c->tm.ev_used) drop_pairs(c); return rc; }
 
 int check_dev_err(fora_ctx *c) {
     uint32_t e = 0;
     HIPCHK(c, hipMemcpyAsync(&e, c->ws.d_err.get(), sizeof(e), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->bucket_overflow = (e & ERR_BUCKET_OVERFLOW) != 0;
-    c->team_timeout_seen = (e & ERR_TEAM_TIMEOUT) != 0;
-    if (e) c->team_dirty = true;
+    c->retry.overflow = (e & ERR_BUCKET_OVERFLOW) != 0;
+    c->team_run.timeout_seen = (e & ERR_TEAM_TIMEOUT) != 0;
     if (e) {
+        c->team_run.dirty = true;
         char buf[256];
         snprintf(buf, sizeof(buf), "device work list overflow (flags 0x%x%s)", e,
                  (e & ERR_TEAM_TIMEOUT) ? ": a team of k_push_team waited too long for a member (workgroups not co-resident); the call is run again with the bucketed push"
@@ -849,7 +871,7 @@ int check_dev_err(fora_ctx *c) {
 int check_batch_args(fora_ctx *c, const int32_t *ids, int nq, const char *what = "source") {
     if (!c) return FORA_E_ARG;
     if (!c->g.n) return fail(c, FORA_E_ARG, "set_graph first");
-    if (!c->have_params) return fail(c, FORA_E_ARG, "set_params first");
+    if (!c->par.have) return fail(c, FORA_E_ARG, "set_params first");
     if (nq < 0 || (nq && !ids)) return fail(c, FORA_E_ARG, std::string("bad ") + what + "s: negative count or null array");
     return FORA_OK;
 }
@@ -906,10 +928,10 @@ int copy_topk_out(fora_ctx *c, int nb, int k, int32_t *ids, double *scores, uint
     return FORA_OK;
 }
 
-// End of a batch: close its event pair, read the device error word (waits for the stream), check the launches, collect
-// the event times.
-int close_batch(fora_ctx *c, int hb, const char *what) {
-    ev_end(c, hb);
+// End of a batch: close its event pair (null: none), read the device error word (waits for the stream), check the launches, collect the event
+// times.  The batch pair spans functions and ends here, ahead of the error word's copy: ended by hand; its owner's destructor covers the early returns.
+int close_batch(fora_ctx *c, EvSpan *batch, const char *what) {
+    if (batch) batch->end();
     if (int rc = check_dev_err(c)) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
@@ -920,10 +942,10 @@ int close_batch(fora_ctx *c, int hb, const char *what) {
 // the per-slot counters of a batch (host copy of its QState words) into fora_timing
 void fold_counters(fora_ctx *c, const QState *qs, int nb) {
     for (int i = 0; i < nb; i++) {
-        c->timing.pops += qs[i].pops;
-        c->timing.relax += qs[i].relax;
-        c->timing.walks += qs[i].n_walks;
-        c->timing.idx_hits += qs[i].n_hit;
+        c->tm.total.pops += qs[i].pops;
+        c->tm.total.relax += qs[i].relax;
+        c->tm.total.walks += qs[i].n_walks;
+        c->tm.total.idx_hits += qs[i].n_hit;
     }
 }
 
@@ -950,15 +972,16 @@ static inline size_t tail_lds(const Dev &d) { return d.tail_hubs && d.col_hub ? 
 static unsigned acc_grid(const fora_ctx *c, Dev &dp, int nq) {
     const uint64_t pairs = (uint64_t)dp.bin_cnt * (uint64_t)std::max(1, nq);
     const uint64_t want = (uint64_t)std::max(1, c->prop.multiProcessorCount) * 24; // workgroups that keep the chip busy with one per CU at a time
-    uint32_t g = c->bk_div > 1 ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs / want, 1), 8) : 1u;
+    uint32_t g = c->retry.div > 1 ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pairs / want, 1), 8) : 1u;
     if (c->opt_.acc_group > 0) g = (uint32_t)std::min<int64_t>(c->opt_.acc_group, ACC_GROUP_MAX);
     dp.acc_group = g;
     return (unsigned)((dp.bin_cnt + g - 1) / g);
 }
 int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, int level_cap = 0, bool round_start = false) {
     const int nq = d.nq;
+    const WsPlan &p = c->ws.plan;
     const uint32_t tail_max = tail_max_of(c, nq);
-    if (round_start && c->binned && level_cap <= 0 && d.rounds <= 1 && c->opt_.tail != 0) {
+    if (round_start && p.binned && level_cap <= 0 && d.rounds <= 1 && c->opt_.tail != 0) {
         // A round of the top-k / --balanced drivers starts from every node at or over the round's threshold
         // (k_topk_frontier), often a handful: when no slot's frontier is larger than what k_push_tail takes over at anyway,
         // the whole round runs inside that kernel -- one launch instead of two per level plus the look-ahead levels
@@ -970,10 +993,10 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
         for (int i = 0; i < nq; i++) fmax = std::max(fmax, cnt[(size_t)i * CSTRIDE]);
         if (fmax == 0) { if (levels_run) *levels_run = 0; return FORA_OK; }
         if (fmax <= tail_max) {
-            int h = ev_begin(c, 9);
+            EvSpan ev(c, EV_PUSH_TAIL);
             hipLaunchKernelGGL(k_push_tail, dim3(nq), dim3(TAIL_THREADS), tail_lds(d), c->stream, d, 0, 0);
-            ev_end(c, h);
-            c->timing.levels++;
+            ev.end();
+            c->tm.total.levels++;
             if (levels_run) *levels_run = 1;
             hipError_t e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("push: ") + hipGetErrorString(e));
@@ -986,21 +1009,21 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
     for (auto &e : done) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int rc = FORA_OK;
     int L = 0;
-    const unsigned xb = c->binned ? c->sub : 1u; // producer workgroups per slot = sub-buckets per bucket (Dev::bk_w); ws at 1000 slots: 4 -> 196 ms, 8 -> 178, 16 -> 163, 32 -> 174
+    const unsigned xb = p.binned ? p.sub : 1u; // producer workgroups per slot = sub-buckets per bucket (Dev::bk_w); ws at 1000 slots: 4 -> 196 ms, 8 -> 178, 16 -> 163, 32 -> 174
     bool past_peak = c->opt_.tail_always == 1; // tests: do not wait for the frontier to have been large first
     for (;; L++) {
         if (level_cap > 0 && L >= level_cap) break; // power iteration: a fixed number of levels
         if (L >= MAX_LEVELS) { rc = fail(c, FORA_E_OVERFLOW, "push level cap reached"); break; }
-        if (c->binned) {
-            for (int lo = 0; lo < c->nbins; lo += c->pbins) { // one pass per group of pbins bins (usually one)
+        if (p.binned) {
+            for (int lo = 0; lo < p.nbins; lo += p.pbins) { // one pass per group of pbins bins (usually one)
                 Dev dp = d;
                 if (level_cap > 0 || d.rounds > 1) dp.defer_k = 0; // capped runs (power iteration) and threshold rounds keep plain levels
                 dp.bin_lo = lo;
-                dp.bin_cnt = std::min(c->pbins, c->nbins - lo);
-                dp.pass = lo / c->pbins;
+                dp.bin_cnt = std::min(p.pbins, p.nbins - lo);
+                dp.pass = lo / p.pbins;
                 dp.pop_next = !(level_cap > 0 && L + 1 >= level_cap); // a capped run leaves the last crossing nodes unpopped
                 dp.launch_par = (int32_t)(c->bin_launches++ & 1);
-                int h = ev_begin(c, 1);
+                EvSpan ev(c, EV_PUSH_EXPAND);
                 {
                     const size_t hub_lds = dp.col_hub ? (size_t)dp.hubs * 8 : 0;
                     const bool hub = dp.col_hub != nullptr, split = dp.row_split != nullptr, sched = TEST_PATHS && (dp.rounds > 1 || dp.defer_k > 0);
@@ -1019,7 +1042,7 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
                     else if (hub) FORA_BIN_LAUNCH(NBV, NT, true, false, false); \
                     else if (split) FORA_BIN_LAUNCH(NBV, NT, false, true, false); \
                     else FORA_BIN_LAUNCH(NBV, NT, false, false, false); } while (0)
-                    if (d.wide && c->pbins > MAX_BINS_WIDE) FORA_BIN_PICK(MAX_BINS_HUGE, BIN_THREADS_HUGE);
+                    if (d.wide && p.pbins > MAX_BINS_WIDE) FORA_BIN_PICK(MAX_BINS_HUGE, BIN_THREADS_HUGE);
                     else if (d.wide) FORA_BIN_PICK(MAX_BINS_WIDE, BIN_THREADS_WIDE);
                     else FORA_BIN_PICK(MAX_BINS, BLOCK);
 #undef FORA_BIN_PICK
@@ -1027,39 +1050,35 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
 #undef FORA_BIN_SCHED
 #undef FORA_BIN_LAUNCH
                 }
-                ev_end(c, h);
-                h = ev_begin(c, 6);
+                ev.begin(EV_PUSH_ACCUM);
                 if (d.wide) { const unsigned gx = acc_grid(c, dp, nq); hipLaunchKernelGGL((k_accum<false, true>), (dp.slot_major & 2u) ? dim3(nq, gx) : dim3(gx, nq), dim3(ACC_THREADS_WIDE), 0, c->stream, dp, L); }
                 else hipLaunchKernelGGL((k_accum<false, false>), dim3(dp.bin_cnt, nq), dim3(ACC_THREADS), 0, c->stream, dp, L);
-                ev_end(c, h);
             }
             if (TEST_PATHS && d.rounds > 1) { // threshold rounds: slots whose frontier ran dry move on to the next (halved) threshold
 #if FORA_TEST_PATHS
-                int h = ev_begin(c, 8);
+                EvSpan ev(c, EV_ROUND_SWEEP);
                 hipLaunchKernelGGL(k_round_sweep, dim3(std::min<uint32_t>(slab_grid_x(c, nq), 32u), nq), dim3(BLOCK), 0, c->stream, d, L);
-                ev_end(c, h);
 #endif
             }
             (void)hipMemcpyAsync(c->ws.h_flc.get() + (size_t)((L + 1) % FLC_RING) * c->ws.B * CSTRIDE, d.fl_count[(L + 1) & 1],
                                  (size_t)nq * 4 * CSTRIDE, hipMemcpyDeviceToHost, c->stream);
         } else {
-            int h = ev_begin(c, 0);
+            EvSpan ev(c, EV_PUSH_POP);
             hipLaunchKernelGGL(k_push_pop, dim3(c->grid_blocks), dim3(BLOCK), 0, c->stream, d, L);
-            ev_end(c, h);
-            h = ev_begin(c, 1);
+            ev.begin(EV_PUSH_EXPAND);
             hipLaunchKernelGGL(k_push_expand, dim3(c->grid_blocks), dim3(BLOCK), 0, c->stream, d, L);
-            ev_end(c, h);
+            ev.end();
             (void)hipMemcpyAsync(c->ws.h_pinned.get() + L + 1, &d.wl_count[L + 1], sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost, c->stream);
         }
-        c->timing.levels++;
+        c->tm.total.levels++;
         (void)hipEventRecord(done[L % (SPEC + 1)], c->stream);
         if (L >= SPEC) {
             const int K = L - SPEC;
             if (hipEventSynchronize(done[K % (SPEC + 1)]) != hipSuccess) { rc = fail(c, FORA_E_HIP, "event sync"); break; }
             bool empty;
             uint32_t fmax = 0;
-            if (c->binned) {
+            if (p.binned) {
                 empty = true;
                 const uint32_t *cnt = c->ws.h_flc.get() + (size_t)((K + 1) % FLC_RING) * c->ws.B * CSTRIDE;
                 uint32_t rounds_left = 0; // word 1 of a slot's counter line: threshold rounds still to come (k_round_sweep)
@@ -1073,17 +1092,17 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
                 empty = c->ws.h_pinned.get()[K + 1] == 0;
             }
             if (fmax > tail_max) past_peak = true; // the first levels are small too, but growing
-            if (!empty && c->binned && tail_max > 0 && past_peak && fmax <= tail_max) {
+            if (!empty && p.binned && tail_max > 0 && past_peak && fmax <= tail_max) {
                 // every slot's frontier is small: finish inside one workgroup per slot instead of launching levels
                 const int next = L + 1;
                 const int remaining = level_cap > 0 ? level_cap - next : 0;
                 if (level_cap <= 0 || remaining > 0) {
-                    int h = ev_begin(c, 9);
+                    EvSpan ev(c, EV_PUSH_TAIL);
                     Dev dt = d;
                     if (d.rounds > 1) dt.defer_k = 0;
                     hipLaunchKernelGGL(k_push_tail, dim3(nq), dim3(TAIL_THREADS), tail_lds(dt), c->stream, dt, next, remaining);
-                    ev_end(c, h);
-                    c->timing.levels++;
+                    ev.end();
+                    c->tm.total.levels++;
                 }
                 break;
             }
@@ -1105,24 +1124,23 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
 // resident in LDS, k_push_tail finishes the slots.  Nothing here waits for the device.
 static bool use_team(const fora_ctx *c, const Dev &d) {
     // not after a time-out
-    return c->g.team.T && c->ws.d_team_msg && c->binned && !d.wide && !c->balanced && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
-           c->ws.team_fit != 0 && c->team_suspend == 0;
+    return c->g.team.T && c->ws.d_team_msg && c->ws.plan.binned && !d.wide && !c->bal.on && d.rounds <= 1 && d.defer_k == 0 && want_team(c) &&
+           c->ws.team_fit != 0 && c->team_run.suspend == 0;
 }
-// Can every workgroup of a k_push_team launch be resident at once?  (Asked once per workspace; raises the kernel's
-// dynamic LDS limit on the way.)
-int team_fits(fora_ctx *c) {
-    if (c->ws.team_fit >= 0 || !c->g.team.T || !c->ws.d_team_msg) return FORA_OK;
+// Can every workgroup of a k_push_team launch be resident at once?  (Asked once per workspace, the one being built with its
+// team buffers in place; raises the kernel's dynamic LDS limit on the way.)
+int team_fits(fora_ctx *c, Workspace &w) {
     const size_t lds = ((size_t)c->g.team.R + 1 + c->g.team.H) * 8;
     hipFuncAttributes fa{};
     HIPCHK(c, hipFuncGetAttributes(&fa, (const void *)k_push_team));
     HIPCHK(c, hipFuncSetAttribute((const void *)k_push_team, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(163840 - (int)fa.sharedSizeBytes)));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_push_team, TEAM_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-    const uint32_t grid = c->ws.team_n * c->g.team.T;
-    c->ws.team_fit = (uint64_t)per_cu * (uint64_t)c->prop.multiProcessorCount >= grid ? 1 : 0;
+    const uint32_t grid = w.team_n * c->g.team.T;
+    w.team_fit = (uint64_t)per_cu * (uint64_t)c->prop.multiProcessorCount >= grid ? 1 : 0;
     int coop = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) != hipSuccess) { (void)hipGetLastError(); coop = 0; }
-    c->team_coop_ok = c->opt_.team_coop == 1 && coop != 0;
+    c->team_run.coop_ok = c->opt_.team_coop == 1 && coop != 0;
     return FORA_OK;
 }
 int run_push_team(fora_ctx *c, const Dev &d) {
@@ -1132,7 +1150,7 @@ int run_push_team(fora_ctx *c, const Dev &d) {
     a.residue = d.residue; a.ppr = d.ppr; a.fl0 = d.fl[0]; a.fl_count0 = d.fl_count[0]; a.inc_tab0 = d.inc_tab[0];
     a.segq_cap = d.segq_cap; a.qs = d.qs; a.err = d.err; a.afix = d.afix; a.t1 = d.t1;
     a.T = T; a.R = c->g.team.R; a.nteams = nteams;
-    a.colt = c->g.team.d_colt.get(); a.rowq = c->g.team.d_rowq.get(); a.n2l = c->g.team.d_n2l.get(); a.l2n = c->g.team.d_l2n.get(); a.deg16 = c->g.team.d_deg16.get(); a.rowl = c->g.team.d_rowl.get(); a.rsvl = c->ws.d_team_rsvl.get(); a.rlog_id = c->ws.d_team_rlog_id.get(); a.rlog_val = c->ws.d_team_rlog_val.get(); a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->team_rlog_cap) : c->team_rlog_cap; a.H = c->g.team.H; a.hubtgt = c->g.team.d_hubtgt.get(); a.off = c->g.team.d_off.get(); a.msg = c->ws.d_team_msg.get(); a.inct = c->ws.d_team_inct.get(); a.cntw = c->ws.d_team_cnt.get();
+    a.colt = c->g.team.d_colt.get(); a.rowq = c->g.team.d_rowq.get(); a.n2l = c->g.team.d_n2l.get(); a.l2n = c->g.team.d_l2n.get(); a.deg16 = c->g.team.d_deg16.get(); a.rowl = c->g.team.d_rowl.get(); a.rsvl = c->ws.d_team_rsvl.get(); a.rlog_id = c->ws.d_team_rlog_id.get(); a.rlog_val = c->ws.d_team_rlog_val.get(); a.rlog_cap = c->opt_.team_log == 0 ? 0u : c->opt_.team_log > 0 ? std::min<uint32_t>((uint32_t)c->opt_.team_log, c->ws.plan.team_rlog_cap) : c->ws.plan.team_rlog_cap; a.H = c->g.team.H; a.hubtgt = c->g.team.d_hubtgt.get(); a.off = c->g.team.d_off.get(); a.msg = c->ws.d_team_msg.get(); a.inct = c->ws.d_team_inct.get(); a.cntw = c->ws.d_team_cnt.get();
     const Workspace &w = c->ws;
     const TeamCtl ctl = team_ctl_layout(nteams, w.B);
     a.ctl = w.d_team_ctl.get(); a.sync = (unsigned long long *)(a.ctl + ctl.sync); a.slot_seq = a.ctl + ctl.slot_seq;
@@ -1147,30 +1165,30 @@ int run_push_team(fora_ctx *c, const Dev &d) {
     a.abort_level = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_abort_level, 0), 1 << 20);
     a.timeout_ticks = (uint64_t)std::min<int64_t>(std::max<int64_t>(c->opt_.team_timeout_ms, 0), 60000) * 100000ull; // (100 MHz wall clock)
     const size_t lds = ((size_t)a.R + 1 + a.H) * 8;
-    if (c->team_dirty) { HIPCHK(c, w.d_team_rsvl.zero(c->stream)); c->team_dirty = false; }
+    if (c->team_run.dirty) { HIPCHK(c, w.d_team_rsvl.zero(c->stream)); c->team_run.dirty = false; }
     HIPCHK(c, w.d_team_ctl.zero(c->stream, ctl.slot_seq)); // the words before the slot sequences
     HIPCHK(c, w.d_team_cnt.zero(c->stream)); // no barrier tag of an earlier launch
     HIPCHK(c, w.d_team_ctl.fill(c->stream, 0xFF, ctl.slot_seq, (size_t)nteams * ((size_t)d.nq + 2)));
-    int h = ev_begin(c, 10);
+    EvSpan ev(c, EV_PUSH_TEAM);
     // The members of a team spin on each other: every workgroup of the launch must be resident at once.  team_fits() has
     // checked that the grid fits the device; a cooperative launch makes the runtime promise it (and keeps cooperative
     // kernels of other contexts from interleaving their workgroups with ours).  Whatever still goes wrong ends in
     // ERR_TEAM_TIMEOUT after team_timeout_ms, and with_retry runs the call again through the bucketed kernels.
     bool launched = false;
-    if (c->team_coop_ok && !c->team_coop_failed) {
+    if (c->team_run.coop_ok && !c->team_run.coop_failed) {
         void *args[] = {(void *)&a};
         const hipError_t le = hipLaunchCooperativeKernel((const void *)k_push_team, dim3(grid), dim3(TEAM_THREADS), args, (unsigned)lds, c->stream);
         if (le == hipSuccess) launched = true;
-        else { (void)hipGetLastError(); c->team_coop_failed = true; }
+        else { (void)hipGetLastError(); c->team_run.coop_failed = true; }
     }
     if (!launched) hipLaunchKernelGGL(k_push_team, dim3(grid), dim3(TEAM_THREADS), lds, c->stream, a);
-    ev_end(c, h);
-    c->timing.levels++;
+    ev.end();
+    c->tm.total.levels++;
     if (a.tail_max) {
-        h = ev_begin(c, 9);
+        ev.begin(EV_PUSH_TAIL);
         hipLaunchKernelGGL(k_push_tail, dim3(d.nq), dim3(TAIL_THREADS), tail_lds(d), c->stream, d, 0, 0);
-        ev_end(c, h);
-        c->timing.levels++;
+        ev.end();
+        c->tm.total.levels++;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("team push launch: ") + hipGetErrorString(e));
@@ -1181,8 +1199,8 @@ int run_push_team(fora_ctx *c, const Dev &d) {
 // ties keep resolving to the lowest ids) into the push's frontier / increment buffers, which are idle here.
 constexpr unsigned NZ_X = 1024;
 int launch_select(fora_ctx *c, const Dev &ds, int nb, int k, int32_t *ids, double *scores, int raw, const double *h_thr = nullptr) {
-    bool compact = c->binned && c->g.n >= (1 << 20);
-    if (c->opt_.select_compact >= 0) compact = c->binned && c->opt_.select_compact == 1; // tests: force / forbid the compacted form
+    bool compact = c->ws.plan.binned && c->g.n >= (1 << 20);
+    if (c->opt_.select_compact >= 0) compact = c->ws.plan.binned && c->opt_.select_compact == 1; // tests: force / forbid the compacted form
     if (!compact) {
         hipLaunchKernelGGL(k_topk_select, dim3(nb), dim3(SEL_THREADS), 0, c->stream, ds, k, ids, scores, raw,
                            (const uint32_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr);
@@ -1209,7 +1227,7 @@ int launch_select(fora_ctx *c, const Dev &ds, int nb, int k, int32_t *ids, doubl
 
 // per-level bookkeeping of the bucketed push that must start from zero
 int reset_binned_counters(fora_ctx *c) {
-    if (!c->binned) return FORA_OK;
+    if (!c->ws.plan.binned) return FORA_OK;
     const Workspace &w = c->ws;
     HIPCHK(c, w.d_fl_count.zero(c->stream));
     HIPCHK(c, w.d_bk_count.zero(c->stream));
@@ -1225,16 +1243,14 @@ int reset_binned_counters(fora_ctx *c) {
 
 int reset_batch_state(fora_ctx *c, int nq, const int32_t *sources) {
     const uint64_t slabs = (uint64_t)nq * c->g.n; // the slabs of the batch's slots only
-    int h = ev_begin(c, 4);
+    EvSpan ev(c, EV_OTHER);
     HIPCHK(c, c->ws.d_residue.zero(c->stream, slabs));
     HIPCHK(c, c->ws.d_ppr.zero(c->stream, slabs));
     HIPCHK(c, c->ws.d_counters.zero(c->stream));
     HIPCHK(c, c->ws.d_err.zero(c->stream));
     HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ws.d_src.get(), sources, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    int rc = reset_binned_counters(c);
-    ev_end(c, h);
-    return rc;
+    return reset_binned_counters(c); // (the span ends behind it)
 }
 
 enum { RUN_PUSH_ONLY = 1 };
@@ -1303,10 +1319,10 @@ int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done
 // count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out)
 int sparse_count(fora_ctx *c, const SparseRun &sp, int nb) {
     HIPCHK(c, hipMemsetAsync(c->sp.d_tot.get(), 0, (size_t)nb * 4, c->stream));
-    const int h = ev_begin(c, 13);
+    EvSpan ev(c, EV_SP_COMPACT);
     hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
                        c->sp.d_counts.get(), c->sp.d_tot.get());
-    ev_end(c, h);
+    ev.end();
     HIPCHK(c, hipMemcpyAsync(c->sp.h_tot.get(), c->sp.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     return FORA_OK;
 }
@@ -1338,10 +1354,9 @@ int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, con
     if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? keep : 0, (uint64_t)sp.next_row, (uint64_t)nq)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->sp.d_base.get() + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
-    const int h = ev_begin(c, 13);
+    EvSpan ev(c, EV_SP_COMPACT);
     hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
                        (const uint32_t *)c->sp.d_counts.get(), (const int64_t *)(c->sp.d_base.get() + sp.live_done), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
-    ev_end(c, h);
     sp.live_done += nb;
     return FORA_OK;
 }
@@ -1371,38 +1386,37 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, in
     if (out) {
         memset(out, 0, sizeof(*out));
         out->entries = sp.cur; out->max_row = sp.max_row; out->thr_fix = sp.thr; out->batches = sp.batches;
-        out->compact_ms = c->sp_compact_ms;
+        out->compact_ms = c->tm.sp_compact_ms;
     }
     return FORA_OK;
 }
 
 // refinement launches after k_walk_alloc: indexed walks, online walks, and the accumulate of their results
 void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t round, int nzh) {
+    const WsPlan &p = c->ws.plan;
     const dim3 wg(walk_grid_x(c, nq), nq);
-    const dim3 wgs(c->binned ? c->sub : 1u, nq); // kernels that fill buckets: one workgroup per sub-bucket (Dev::bk_w)
-    int h = ev_begin(c, 3);
+    const dim3 wgs(p.binned ? p.sub : 1u, nq); // kernels that fill buckets: one workgroup per sub-bucket (Dev::bk_w)
+    EvSpan ev(c, EV_WALK);
     if (with_idx) {
-        if (!c->binned) hipLaunchKernelGGL(k_walk_idx<1>, wg, dim3(BLOCK), 0, c->stream, d);
+        if (!p.binned) hipLaunchKernelGGL(k_walk_idx<1>, wg, dim3(BLOCK), 0, c->stream, d);
         else if (!d.wide) hipLaunchKernelGGL(k_walk_idx<MAX_BINS>, wgs, dim3(BLOCK), 0, c->stream, d);
         else
-            for (int lo = 0; lo < c->nbins; lo += c->pbins) { // buckets are reused pass by pass
+            for (int lo = 0; lo < p.nbins; lo += p.pbins) { // buckets are reused pass by pass
                 Dev dp = d;
                 dp.bin_lo = lo;
-                dp.bin_cnt = std::min(c->pbins, c->nbins - lo);
+                dp.bin_cnt = std::min(p.pbins, p.nbins - lo);
                 const dim3 wgi = (dp.slot_major & 4u) ? dim3(wgs.y, wgs.x) : wgs;
-                if (c->pbins > MAX_BINS_WIDE) hipLaunchKernelGGL(k_walk_idx<MAX_BINS_HUGE>, wgi, dim3(BIN_THREADS_HUGE), 0, c->stream, dp);
+                if (p.pbins > MAX_BINS_WIDE) hipLaunchKernelGGL(k_walk_idx<MAX_BINS_HUGE>, wgi, dim3(BIN_THREADS_HUGE), 0, c->stream, dp);
                 else hipLaunchKernelGGL(k_walk_idx<MAX_BINS_WIDE>, wgi, dim3(BIN_THREADS_WIDE), 0, c->stream, dp);
                 { const unsigned gx = acc_grid(c, dp, nq); hipLaunchKernelGGL((k_accum<true, true>), (dp.slot_major & 2u) ? dim3(nq, gx) : dim3(gx, nq), dim3(ACC_THREADS_WIDE), 0, c->stream, dp, 0); }
             }
     }
-    const bool dg = c->binned && !d.wide && d.dg.colp && c->opt_.walk_dg != 0; // narrow layout: one gather per step over the degree-grouped copy
+    const bool dg = p.binned && !d.wide && d.dg.colp && c->opt_.walk_dg != 0; // narrow layout: one gather per step over the degree-grouped copy
     const bool xl = dg && c->opt_.walk_dg != 1 && d.dg.invb;                  // ... and results in bucket order (no gather per walk either)
     if (xl && with_idx) { // the indexed results are in plain ids: reduce them before the buckets are reused in bucket order
-        ev_end(c, h);
-        h = ev_begin(c, 7);
-        hipLaunchKernelGGL((k_accum<true, false>), dim3(c->nbins, nq), dim3(ACC_THREADS), 0, c->stream, d, 0);
-        ev_end(c, h);
-        h = ev_begin(c, 3);
+        ev.begin(EV_WALK_ACCUM);
+        hipLaunchKernelGGL((k_accum<true, false>), dim3(p.nbins, nq), dim3(ACC_THREADS), 0, c->stream, d, 0);
+        ev.begin(EV_WALK);
     }
     Dev dw = d;
     if (xl) { dw.nbins = (int32_t)d.dg.nbx; dw.acc_xl = d.dg.invb; }
@@ -1422,12 +1436,11 @@ void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t rou
         }
 #undef FORA_DG_LAUNCH
     } else
-        hipLaunchKernelGGL(k_walk_online<WALK_TO_PPR>, c->binned && !d.wide ? wgs : wg, dim3(BLOCK), 0, c->stream, d, round, nzh, (int32_t *)nullptr);
-    ev_end(c, h);
-    if (c->binned && !d.wide) { // narrow layout: indexed and online results share the buckets (bucket-order results: see above)
-        h = ev_begin(c, 7);
+        hipLaunchKernelGGL(k_walk_online<WALK_TO_PPR>, p.binned && !d.wide ? wgs : wg, dim3(BLOCK), 0, c->stream, d, round, nzh, (int32_t *)nullptr);
+    ev.end();
+    if (p.binned && !d.wide) { // narrow layout: indexed and online results share the buckets (bucket-order results: see above)
+        ev.begin(EV_WALK_ACCUM);
         hipLaunchKernelGGL((k_accum<true, false>), dim3(dw.nbins, nq), dim3(ACC_THREADS), 0, c->stream, dw, 0);
-        ev_end(c, h);
     }
 }
 
@@ -1438,26 +1451,26 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
     HIPCHK(c, ensure_active(c->ws));
     const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
     Dev d = make_dev(c, nq, with_idx);
-    int h = ev_begin(c, 4);
+    EvSpan ev(c, EV_OTHER);
     hipLaunchKernelGGL(k_init_batch, dim3((nq + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 1);
-    ev_end(c, h);
+    ev.end();
     std::vector<uint8_t> active((size_t)nq, 1);
     std::vector<uint64_t> rsum_fix((size_t)nq, FIX_ONE), pops((size_t)nq, 0), relax((size_t)nq, 0);
-    c->h_rmax_used.assign((size_t)nq, c->rmax);
-    c->h_rounds.assign((size_t)nq, 1);
+    c->bal.h_rmax_used.assign((size_t)nq, c->par.rmax);
+    c->bal.h_rounds.assign((size_t)nq, 1);
     for (int i = 0; i < nq; i++)
         if (is_dangling(c, sources[i])) active[i] = 0; // :864, :882
-    for (int i = 0; i < nq; i++) if (active[i]) c->h_rounds[i] = 0;
-    double rmax = c->rmax * c->bal_start; // :862
+    for (int i = 0; i < nq; i++) if (active[i]) c->bal.h_rounds[i] = 0;
+    double rmax = c->par.rmax * c->bal.start; // :862
     for (int round = 0;; round++) {
         bool any = false;
         for (int i = 0; i < nq; i++) {
             if (!active[i]) continue;
-            const double t = (!with_idx || rmax >= c->rmax) ? c->t_walk : c->t_idx;                       // :825-838
-            const double est = c->omega * std::ldexp((double)rsum_fix[i], -62) * (1 - c->alpha) * t;
-            const double used = (double)pops[i] * c->c_pop + (double)relax[i] * c->c_edge;
+            const double t = (!with_idx || rmax >= c->par.rmax) ? c->bal.t_walk : c->bal.t_idx;                       // :825-838
+            const double est = c->par.omega * std::ldexp((double)rsum_fix[i], -62) * (1 - c->par.alpha) * t;
+            const double used = (double)pops[i] * c->bal.c_pop + (double)relax[i] * c->bal.c_edge;
             if (!(est > used)) active[i] = 0;                                                              // :866
-            else { any = true; c->h_rmax_used[i] = rmax; c->h_rounds[i] = round + 1; }
+            else { any = true; c->bal.h_rmax_used[i] = rmax; c->bal.h_rounds[i] = round + 1; }
         }
         if (!any) break;
         if (round >= 64) return fail(c, FORA_E_OVERFLOW, "--balanced: rmax halved 64 times");
@@ -1467,10 +1480,10 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
             int rc = reset_binned_counters(c);
             if (rc) return rc;
         }
-        Dev dr = make_dev(c, nq, with_idx, rmax, c->omega);
-        h = ev_begin(c, 4);
+        Dev dr = make_dev(c, nq, with_idx, rmax, c->par.omega);
+        ev.begin(EV_OTHER);
         hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, dr, (const uint8_t *)c->ws.d_active.get());
-        ev_end(c, h);
+        ev.end();
         int rc = run_push_levels(c, dr, nullptr, 0, true);
         if (rc) return rc;
         HIPCHK(c, hipMemcpy(c->h_qs.data(), c->ws.d_qs.get(), (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost));
@@ -1487,44 +1500,44 @@ int push_balanced(fora_ctx *c, const int32_t *sources, int nq, bool with_idx) {
 // One batch of <= B sources: push (+ refinement) and k_ppr_sum, then the batch's close-out; its per-slot accumulators
 // land in h_qs.  Results stay in the slabs.
 int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, int flags, const SparseRun *sp = nullptr) {
-    const int hb = ev_begin(c, 5);
+    EvSpan batch(c, EV_BATCH);
     int rc = reset_batch_state(c, nq, sources);
     if (rc) return rc;
     Dev d = make_dev(c, nq, with_idx);
-    int h;
-    if (c->balanced) {
+    EvSpan ev(c);
+    if (c->bal.on) {
         rc = push_balanced(c, sources, nq, with_idx);
     } else {
-        if (TEST_PATHS && c->binned) d.rounds = (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.rounds, 1), 16);
+        if (TEST_PATHS && c->ws.plan.binned) d.rounds = (int32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.rounds, 1), 16);
         d.round_div = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.round_div, 0), 1 << 20);
         const bool team = use_team(c, d);
-        h = ev_begin(c, 4);
+        ev.begin(EV_OTHER);
         hipLaunchKernelGGL(k_init_batch, dim3((nq + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, team ? 3 : 0);
-        ev_end(c, h);
+        ev.end();
         rc = team ? run_push_team(c, d) : run_push_levels(c, d);
         d.rounds = 1;
     }
     if (rc) return rc;
     if (!(flags & RUN_PUSH_ONLY)) {
         const uint32_t chunks = slab_grid_x(c, nq);
-        h = ev_begin(c, 2);
+        ev.begin(EV_WALK_ALLOC);
         hipLaunchKernelGGL(k_walk_alloc<ALLOC_QUERY>, (d.wide && (d.slot_major & 8u)) ? dim3(nq, chunks) : dim3(chunks, nq), dim3(BLOCK), 0, c->stream, d, with_idx ? 1 : 0,
                            (const uint8_t *)nullptr, (uint64_t *)nullptr, (unsigned long long *)nullptr, 0u);
-        ev_end(c, h);
-        launch_walks(c, d, nq, with_idx, 0u, c->opt ? 1 : 0);
+        ev.end();
+        launch_walks(c, d, nq, with_idx, 0u, c->par.opt ? 1 : 0);
     }
     {
         const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 64);
-        h = ev_begin(c, 4);
+        ev.begin(EV_OTHER);
         hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, d);
-        ev_end(c, h);
+        ev.end();
     }
     if (sp) if ((rc = sparse_count(c, *sp, nq))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ws.h_qs_pin.get(), c->ws.d_qs.get(), (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = close_batch(c, hb, "batch"))) return rc;
+    if ((rc = close_batch(c, &batch, "batch"))) return rc;
     for (int i = 0; i < nq; i++) c->h_qs[i] = c->ws.h_qs_pin.get()[i];
-    c->timing.walk_steps += *c->ws.h_steps_pin.get();
+    c->tm.total.walk_steps += *c->ws.h_steps_pin.get();
     fold_counters(c, c->h_qs.data(), nq);
     return FORA_OK;
 }
@@ -1537,15 +1550,15 @@ void fill_stats(const fora_ctx *c, int i, fora_query_stats &o) {
     o.n_rw = s.n_rw; o.n_walks = s.n_walks; o.n_idx_hit = s.n_hit;
     o.pops = s.pops; o.relax = s.relax; o.ppr_sum_fix = s.ppr_sum;
     o.levels = (int32_t)s.levels; o.dangling_source = (int32_t)s.dangling_source;
-    o.rmax_used = c->balanced && (size_t)i < c->h_rmax_used.size() ? c->h_rmax_used[i] : c->rmax;
-    o.push_rounds = c->balanced && (size_t)i < c->h_rounds.size() ? c->h_rounds[i] : 1;
+    o.rmax_used = c->bal.on && (size_t)i < c->bal.h_rmax_used.size() ? c->bal.h_rmax_used[i] : c->par.rmax;
+    o.push_rounds = c->bal.on && (size_t)i < c->bal.h_rounds.size() ? c->bal.h_rounds[i] : 1;
     o.reserved_ = 0;
 }
 
 // workspace of a call of `slots` queries at the ctx's omega, and the (ids, scores) pair of k entries per slot when k > 0
 int ensure_query_workspace(fora_ctx *c, int slots, int k) {
-    c->bk_div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
-    if (int rc = ensure_workspace(c, slots, c->omega)) return rc;
+    c->retry.div = 1; // (queries with smaller buckets, measured: LJ-sized 350 -> 220 q/s -- the indexed walks' results overflow into direct atomics; Twitter-2010-sized: no change)
+    if (int rc = ensure_workspace(c, slots, c->par.omega)) return rc;
     return k > 0 ? grow_pair(c, k, c->ws.d_topk_ids, c->ws.d_topk_sc) : FORA_OK;
 }
 
@@ -1571,7 +1584,7 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
         if (stats) {
             fora_query_stats &o = stats[i];
             memset(&o, 0, sizeof(o));
-            o.ppr_sum_fix = FIX_ONE; o.dangling_source = 1; o.rmax_used = c->rmax; o.push_rounds = 1;
+            o.ppr_sum_fix = FIX_ONE; o.dangling_source = 1; o.rmax_used = c->par.rmax; o.push_rounds = 1;
         }
         if (ppr_d) { double *row = ppr_d + (uint64_t)i * n; memset(row, 0, n * 8); row[s] = 1.0; }
         if (ppr_fix) { uint64_t *row = ppr_fix + (uint64_t)i * n; memset(row, 0, n * 8); row[s] = FIX_ONE; }
@@ -1638,7 +1651,7 @@ int ensure_topk_slabs(fora_ctx *c, int k) {
 
 // host side of a batch; the vectors are kept from batch to batch (asynchronous copies read them)
 struct TopkBatch {
-    int hb = -1;                      // the batch's event pair
+    EvSpan span;                      // the batch's event pair (topk_batch_start .. close_batch)
     std::vector<uint8_t> active, inactive;
     std::vector<int32_t> nround;      // rounds each slot has run
 };
@@ -1647,7 +1660,7 @@ struct TopkBatch {
 // :951-955: one round, ppr = e_s), so its slot starts inactive and its ppr2 := reserve here; every other slot's ppr2 is
 // written by its first round's copy (round 5 copied all slots here: one 12-GB slab pass per Twitter-2010-sized batch for nothing).
 int topk_batch_start(fora_ctx *c, TopkBatch &tb, const int32_t *sources, int nb, bool with_idx, uint32_t chunks) {
-    tb.hb = ev_begin(c, 5);
+    tb.span.begin(EV_BATCH);
     if (int rc = reset_batch_state(c, nb, sources)) return rc;
     if (with_idx) if (int rc = next_cursor_epoch(c)) return rc; // query.h:997-998, :937-938: every cursor of the batch reads as 0
     hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, make_dev(c, nb, with_idx), 1);
@@ -1677,34 +1690,34 @@ int topk_round(fora_ctx *c, TopkBatch &tb, int nb, bool with_idx, int round, dou
     HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
     if (int rc = reset_binned_counters(c)) return rc;
     const Dev d = make_dev(c, nb, with_idx, rmax, omega);
-    int h = ev_begin(c, 4);
+    EvSpan ev(c, EV_OTHER);
     hipLaunchKernelGGL(k_topk_frontier, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, d, (const uint8_t *)c->ws.d_active.get());
-    ev_end(c, h);
+    ev.end();
     if (int rc = run_push_levels(c, d, nullptr, 0, true)) return rc;
-    h = ev_begin(c, 4);
+    ev.begin(EV_OTHER);
     hipLaunchKernelGGL(k_copy_slab, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, c->g.n, c->ws.d_ppr.get(), c->ws.d_ppr2.get(),
                        (const uint8_t *)c->ws.d_active.get());
-    ev_end(c, h);
+    ev.end();
     dw = d;
     dw.ppr = c->ws.d_ppr2.get();
-    h = ev_begin(c, 2);
+    ev.begin(EV_WALK_ALLOC);
     hipLaunchKernelGGL(k_walk_alloc<KIND>, (dw.wide && (dw.slot_major & 8u)) ? dim3(nb, chunks) : dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, with_idx ? 1 : 0,
                        (const uint8_t *)c->ws.d_active.get(), c->ws.d_cursor.get(), round_walks, c->ws.cursor_epoch);
-    ev_end(c, h);
+    ev.end();
     launch_walks(c, dw, nb, with_idx, (uint32_t)round, nzh);
     return FORA_OK;
 }
 
 // Batch end: the top k of every slot's ppr2 (topk_ppr, algo.h:592-610; sel_thr: per-slot lower limits of the top k, or
 // null), the close-out, ids / scores / rounds of the slots into rows b0 ..., the counters of all their rounds.
-int topk_batch_end(fora_ctx *c, const TopkBatch &tb, int nb, int k, const double *sel_thr, const char *what, int b0,
+int topk_batch_end(fora_ctx *c, TopkBatch &tb, int nb, int k, const double *sel_thr, const char *what, int b0,
                    int32_t *ids, double *scores, int32_t *rounds) {
     Dev ds = make_dev(c, nb, false);
     ds.ppr = c->ws.d_ppr2.get();
-    const int h = ev_begin(c, 4);
+    EvSpan ev(c, EV_OTHER);
     if (int rc = launch_select(c, ds, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0, sel_thr)) return rc;
-    ev_end(c, h);
-    if (int rc = close_batch(c, tb.hb, what)) return rc;
+    ev.end();
+    if (int rc = close_batch(c, &tb.span, what)) return rc;
     if (int rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0)) return rc;
     HIPCHK(c, hipMemcpy(c->h_qs.data(), c->ws.d_qs.get(), (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost));
     fold_counters(c, c->h_qs.data(), nb);
@@ -1719,49 +1732,49 @@ int topk_batch_end(fora_ctx *c, const TopkBatch &tb, int nb, int k, const double
 // context's kernels held CUs) -- the next calls push with the bucketed kernels.
 constexpr int TEAM_SUSPEND_CALLS = 8;
 template <class F> int with_bucket_retry(fora_ctx *c, F call) {
-    const uint32_t scale0 = c ? c->bk_scale : 1, scale0t = c ? c->bk_scale_topk : 1;
+    if (!c) return call();
+    BucketRetry &br = c->retry;
+    const uint32_t scale0 = br.scale, scale0t = br.scale_topk;
     bool team_retried = false;
     auto forget_attempt = [&](const fora_timing &t0) { // the failed attempt must leave no trace in the timings: drop its event pairs and counters
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        c->ev_used = 0;
-        c->timing = t0;
+        drop_pairs(c);
+        c->tm.total = t0;
     };
-    auto drop_enlarged_plan = [&]() { // the enlarged plan did not help: do not keep it
-        if (c->bk_scale == scale0 && c->bk_scale_topk == scale0t) return;
-        c->bk_scale = scale0; c->bk_scale_topk = scale0t;
-        (void)hipSetDevice(c->device);
-        free_workspace(c);
+    auto give_up = [&](int rc) { // the enlarged plan did not help: do not keep it; no pair of the failed call stays behind
+        if (br.scale != scale0 || br.scale_topk != scale0t) {
+            br.scale = scale0; br.scale_topk = scale0t;
+            (void)hipSetDevice(c->device);
+            free_workspace(c);
+        }
+        return drop_pairs_unless_ok(c, rc);
     };
     for (;;) {
-        const fora_timing t0 = c ? c->timing : fora_timing{};
+        const fora_timing t0 = c->tm.total;
         const int rc = call();
-        if (c && rc == FORA_OK && c->team_suspend > 0 && !team_retried) c->team_suspend--; // (a retried call has just started the count)
-        if (!c || rc != FORA_E_OVERFLOW) {
-            if (c && rc != FORA_OK) drop_enlarged_plan();
-            return rc;
-        }
-        if (c->team_timeout_seen && !team_retried) {
-            c->team_timeout_seen = false;
-            c->team_suspend = TEAM_SUSPEND_CALLS;
-            c->team_fallbacks++;
+        if (rc == FORA_OK && c->team_run.suspend > 0 && !team_retried) c->team_run.suspend--; // (a retried call has just started the count)
+        if (rc == FORA_OK) return rc;
+        if (rc != FORA_E_OVERFLOW) return give_up(rc);
+        if (c->team_run.timeout_seen && !team_retried) {
+            c->team_run.timeout_seen = false;
+            c->team_run.suspend = TEAM_SUSPEND_CALLS;
+            c->team_run.fallbacks++;
             team_retried = true;
             forget_attempt(t0);
             continue;
         }
-        // the multiplier of the regime the call planned with (fora_ctx::bk_div is set by the call itself)
-        uint32_t &cur = c->bk_div > 1 ? c->bk_scale_topk : c->bk_scale;
-        if (!c->bucket_overflow || cur >= (1u << 16)) {
-            drop_enlarged_plan();
-            return rc;
-        }
+        // the multiplier of the regime the call planned with (BucketRetry::div is set by the call itself)
+        uint32_t &cur = br.div > 1 ? br.scale_topk : br.scale;
+        if (!br.overflow || cur >= (1u << 16)) return give_up(rc);
         cur *= 2;
-        c->bucket_retries++;
-        c->bucket_overflow = false;
+        br.retries++;
+        br.overflow = false;
         forget_attempt(t0);
         free_workspace(c);
     }
 }
+
+// the words of the context that mirror an option
+static void apply_options(fora_ctx *c) { c->tm.profiling = c->opt_.profile != 0; c->grid_blocks = c->opt_.grid > 0 ? (int)c->opt_.grid : 2048; }
 
 // =============================================================================== C ABI
 extern "C" {
@@ -1799,8 +1812,7 @@ int fora_hip_create(int device, fora_ctx **out) {
         return FORA_E_NOMEM;
     }
     c->opt_ = tunables_from_env();
-    c->profiling = c->opt_.profile != 0;
-    if (c->opt_.grid > 0) c->grid_blocks = (int)c->opt_.grid;
+    apply_options(c);
     *out = c;
     return FORA_OK;
 }
@@ -1815,7 +1827,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_sparse(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
-    for (auto &p : c->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
+    for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2054,7 +2066,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_index(c);
     free_graph(c);
     free_sparse(c); // (rows of another graph)
-    c->bk_scale = 1; c->bk_scale_topk = 1;
+    c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
         std::vector<uint64_t> rowinfo((size_t)n);
         std::vector<uint32_t> deg((size_t)n);
@@ -2117,23 +2129,22 @@ int fora_hip_set_params(fora_ctx *c, double alpha, double epsilon, double rmax_s
     if (opt) rmax *= rmax_scale / (1 - alpha);
     else rmax *= rmax_scale;
     const double omega = (2 + epsilon) * log(2 / pfail) / delta / epsilon / epsilon;
-    c->alpha = alpha; c->epsilon = epsilon; c->rmax_scale = rmax_scale; c->opt = opt ? 1 : 0; c->seed = seed;
-    c->rmax = rmax; c->omega = omega; c->have_params = true;
+    c->par = Params{true, alpha, epsilon, rmax_scale, rmax, omega, opt ? 1 : 0, seed};
     return FORA_OK;
 }
 
 int fora_hip_set_params_raw(fora_ctx *c, double alpha, double rmax, double omega, int opt, uint64_t seed) {
     if (!c) return FORA_E_ARG;
     if (!(alpha > 0 && alpha < 1) || !(rmax > 0) || !(omega >= 0)) return fail(c, FORA_E_ARG, "bad params");
-    c->alpha = alpha; c->rmax = rmax; c->omega = omega; c->opt = opt ? 1 : 0; c->seed = seed;
-    c->have_params = true;
+    c->par.alpha = alpha; c->par.rmax = rmax; c->par.omega = omega; c->par.opt = opt ? 1 : 0; c->par.seed = seed;
+    c->par.have = true;
     return FORA_OK;
 }
 
 int fora_hip_get_params(fora_ctx *c, double *rmax, double *omega) {
-    if (!c || !c->have_params) return FORA_E_ARG;
-    if (rmax) *rmax = c->rmax;
-    if (omega) *omega = c->omega;
+    if (!c || !c->par.have) return FORA_E_ARG;
+    if (rmax) *rmax = c->par.rmax;
+    if (omega) *omega = c->par.omega;
     return FORA_OK;
 }
 
@@ -2151,9 +2162,8 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
         (void)hipSetDevice(c->device);
         free_workspace(c);
         c->opt_ = tunables_from_env();
-        c->team_suspend = 0; // (a time-out's back-off too)
-        c->profiling = c->opt_.profile != 0;
-        c->grid_blocks = c->opt_.grid > 0 ? (int)c->opt_.grid : 2048;
+        c->team_run.suspend = 0; // (a time-out's back-off too)
+        apply_options(c);
         return FORA_OK;
     }
     if (!TEST_PATHS && schedule_option(name) && value != (strcmp(name, "rounds") ? (strcmp(name, "round_div") ? 0 : 4) : 1))
@@ -2163,8 +2173,7 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
             if (c->opt_.*(o.field) == value) return FORA_OK;
             c->opt_.*(o.field) = value;
             if (o.layout) { (void)hipSetDevice(c->device); free_workspace(c); }
-            if (!strcmp(name, "profile")) c->profiling = value != 0;
-            if (!strcmp(name, "grid")) c->grid_blocks = value > 0 ? (int)value : 2048;
+            apply_options(c);
             return FORA_OK;
         }
     return fail(c, FORA_E_ARG, std::string("unknown option ") + name);
@@ -2177,11 +2186,11 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "diag_build")) { *value = FORA_DIAG_BUILD; return FORA_OK; }    // 1: a probe / stamp / fake build (fora_diag.h) -- never the shipped library
     if (!c) return FORA_E_ARG;
     // read-only state of the engine beside the knobs
-    if (!strcmp(name, "bucket_retries")) { *value = (int64_t)c->bucket_retries; return FORA_OK; } // re-runs with doubled message buckets
-    if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
-    if (!strcmp(name, "team_suspended")) { *value = c->team_suspend; return FORA_OK; }             // calls left that do not try the team push
+    if (!strcmp(name, "bucket_retries")) { *value = (int64_t)c->retry.retries; return FORA_OK; } // re-runs with doubled message buckets
+    if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_run.fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
+    if (!strcmp(name, "team_suspended")) { *value = c->team_run.suspend; return FORA_OK; }             // calls left that do not try the team push
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
-    if (!strcmp(name, "team_cooperative")) { *value = c->team_coop_ok && !c->team_coop_failed ? 1 : 0; return FORA_OK; }
+    if (!strcmp(name, "team_cooperative")) { *value = c->team_run.coop_ok && !c->team_run.coop_failed ? 1 : 0; return FORA_OK; }
     for (const auto &o : OPTIONS)
         if (!strcmp(name, o.name)) { *value = c->opt_.*(o.field); return FORA_OK; }
     return fail(c, FORA_E_ARG, std::string("unknown option ") + name);
@@ -2189,12 +2198,13 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
 
 int fora_hip_set_balanced(fora_ctx *c, int on, double start_scale, double c_pop, double c_edge, double t_walk, double t_idx) {
     if (!c) return FORA_E_ARG;
-    c->balanced = on != 0;
-    c->bal_start = start_scale > 0 ? start_scale : 8;
-    c->c_pop = c_pop > 0 ? c_pop : 2.0e-11;
-    c->c_edge = c_edge > 0 ? c_edge : 2.4e-11;
-    c->t_walk = t_walk > 0 ? t_walk : 6.5e-11;
-    c->t_idx = t_idx > 0 ? t_idx : 2.2e-11;
+    const Balanced def; // (the defaults: its initialisers)
+    c->bal.on = on != 0;
+    c->bal.start = start_scale > 0 ? start_scale : def.start;
+    c->bal.c_pop = c_pop > 0 ? c_pop : def.c_pop;
+    c->bal.c_edge = c_edge > 0 ? c_edge : def.c_edge;
+    c->bal.t_walk = t_walk > 0 ? t_walk : def.t_walk;
+    c->bal.t_idx = t_idx > 0 ? t_idx : def.t_idx;
     return FORA_OK;
 }
 
@@ -2205,8 +2215,8 @@ static uint64_t host_index_sizes(const fora_ctx *c, uint64_t *off, uint64_t *cnt
     for (int32_t v = 0; v < c->g.n; v++) {
         const size_t deg = (size_t)(c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v]);
         unsigned long num_rw;
-        if (c->opt) num_rw = (unsigned long)ceil(deg * c->rmax * (1 - c->alpha) * c->omega);
-        else num_rw = (unsigned long)ceil(deg * c->rmax * c->omega);
+        if (c->par.opt) num_rw = (unsigned long)ceil(deg * c->par.rmax * (1 - c->par.alpha) * c->par.omega);
+        else num_rw = (unsigned long)ceil(deg * c->par.rmax * c->par.omega);
         if (off) off[v] = total;
         if (cnt) cnt[v] = num_rw;
         total += num_rw;
@@ -2215,14 +2225,14 @@ static uint64_t host_index_sizes(const fora_ctx *c, uint64_t *off, uint64_t *cnt
 }
 
 int fora_hip_index_sizes(fora_ctx *c, uint64_t *total, uint64_t *off, uint64_t *cnt) {
-    if (!c || !c->g.n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
+    if (!c || !c->g.n || !c->par.have) return fail(c, FORA_E_ARG, "set_graph and set_params first");
     const uint64_t t = host_index_sizes(c, off, cnt);
     if (total) *total = t;
     return FORA_OK;
 }
 
 int fora_hip_build_index(fora_ctx *c) {
-    if (!c || !c->g.n || !c->have_params) return fail(c, FORA_E_ARG, "set_graph and set_params first");
+    if (!c || !c->g.n || !c->par.have) return fail(c, FORA_E_ARG, "set_graph and set_params first");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint64_t> off((size_t)c->g.n), cnt((size_t)c->g.n);
     const uint64_t total = host_index_sizes(c, off.data(), cnt.data());
@@ -2234,7 +2244,7 @@ int fora_hip_build_index(fora_ctx *c) {
     HIPCHK(c, hipMemcpy(ix.d_idx_off.get(), off.data(), (size_t)c->g.n * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(ix.d_idx_cnt.get(), cnt.data(), (size_t)c->g.n * 8, hipMemcpyHostToDevice));
     ix.len = total;
-    c->bk_div = 1;
+    c->retry.div = 1;
     int rc = ensure_workspace(c, 1, (double)total);
     if (rc) return rc;
     Dev d = make_dev(c, 1, false);
@@ -2243,14 +2253,13 @@ int fora_hip_build_index(fora_ctx *c) {
     HIPCHK(c, c->ws.d_err.zero(c->stream));
     HIPCHK(c, c->ws.d_wit_count.zero(c->stream));
     const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 2048);
-    int h = ev_begin(c, 4);
+    EvSpan ev(c, EV_OTHER);
     hipLaunchKernelGGL(k_index_alloc, dim3(chunks), dim3(BLOCK), 0, c->stream, d);
-    ev_end(c, h);
-    h = ev_begin(c, 3);
+    ev.begin(EV_WALK);
     hipLaunchKernelGGL(k_walk_online<WALK_TO_INDEX>, dim3(walk_grid_x(c, 1), 1), dim3(BLOCK), 0, c->stream, d, 0u,
-                       c->opt ? 1 : 0, ix.d_rw_idx.get());
-    ev_end(c, h);
-    if ((rc = close_batch(c, -1, "build_index"))) return rc;
+                       c->par.opt ? 1 : 0, ix.d_rw_idx.get());
+    ev.end();
+    if ((rc = close_batch(c, nullptr, "build_index"))) return drop_pairs_unless_ok(c, rc);
     ix.have = true;
     c->ix = std::move(ix);
     return FORA_OK;
@@ -2317,7 +2326,7 @@ int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int
     return with_bucket_retry(c, [&] {
         SparseRun run; // (a retried attempt starts from an empty one)
         run.thr = thr;
-        c->sp_compact_ms = 0;
+        c->tm.sp_compact_ms = 0;
         if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, &run)) return rc;
         return sparse_finish(c, run, sources, nq, row_ptr, sp_out);
     });
@@ -2378,7 +2387,7 @@ int fora_hip_push_batch(fora_ctx *c, const int32_t *sources, int nq, uint64_t *r
 }
 
 int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64_t *num_s_rw, uint64_t *n_rw) {
-    if (!c || !c->g.n || !c->have_params || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
+    if (!c || !c->g.n || !c->par.have || !residue || !num_s_rw) return fail(c, FORA_E_ARG, "bad call");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<double> d_r; DevBuf<uint64_t> d_num, d_n;
     const size_t n = (size_t)c->g.n;
@@ -2387,7 +2396,7 @@ int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64
     HIPCHK(c, d_n.alloc(1));
     HIPCHK(c, hipMemcpy(d_r.get(), residue, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_walk_counts_f64, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
-                       c->g.n, (const double *)d_r.get(), rsum, c->omega, c->alpha, c->opt, d_num.get(), d_n.get());
+                       c->g.n, (const double *)d_r.get(), rsum, c->par.omega, c->par.alpha, c->par.opt, d_num.get(), d_n.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(num_s_rw, d_num.get(), n * 8, hipMemcpyDeviceToHost));
     uint64_t N = 0;
@@ -2398,7 +2407,7 @@ int fora_hip_walk_counts(fora_ctx *c, const double *residue, double rsum, uint64
 
 int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_hop, const int32_t *starts,
                    const uint64_t *js, int64_t count, int32_t *dests) {
-    if (!c || !c->g.n || !c->have_params || count < 0) return fail(c, FORA_E_ARG, "bad call");
+    if (!c || !c->g.n || !c->par.have || count < 0) return fail(c, FORA_E_ARG, "bad call");
     if (count == 0) return FORA_OK;
     for (int64_t i = 0; i < count; i++)
         if (starts[i] < 0 || starts[i] >= c->g.n) return fail(c, FORA_E_ARG, "walk start out of range");
@@ -2411,8 +2420,8 @@ int fora_hip_walks(fora_ctx *c, uint32_t stream_id, uint32_t round, int no_zero_
     HIPCHK(c, hipMemcpy(d_j.get(), js, (size_t)count * 8, hipMemcpyHostToDevice));
     Dev d{};
     d.n = c->g.n; d.rowinfo = c->g.d_rowinfo.get(); d.row_ptr = c->g.d_row_ptr.get(); d.col = c->g.d_col.get();
-    d.alpha32 = (uint32_t)(c->alpha * 4294967296.0);
-    d.seed_lo = (uint32_t)c->seed; d.seed_hi = (uint32_t)(c->seed >> 32);
+    d.alpha32 = (uint32_t)(c->par.alpha * 4294967296.0);
+    d.seed_lo = (uint32_t)c->par.seed; d.seed_hi = (uint32_t)(c->par.seed >> 32);
     hipLaunchKernelGGL(k_walks_raw, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, d,
                        stream_id, round, no_zero_hop, (const int32_t *)d_s.get(), (const uint64_t *)d_j.get(), count, d_d.get());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2456,12 +2465,12 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
     }
     // omega of the last possible round bounds the walk work list
     const double omega_max = (2 + epsilon) * log(2 / pfail) / min_delta / epsilon / epsilon;
-    c->bk_div = want_wide(c) && c->opt_.bkcap <= 0 ? (uint32_t)std::max<int64_t>(1, c->opt_.topk_bk_div) : 1u;
+    c->retry.div = want_wide(c) && c->opt_.bkcap <= 0 ? (uint32_t)std::max<int64_t>(1, c->opt_.topk_bk_div) : 1u;
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
     if ((rc = ensure_topk_slabs(c, k))) return rc;
     const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
-    TopkBatch tb;
+    TopkBatch tb{EvSpan(c)};
     std::vector<unsigned long long> above;
     const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
@@ -2480,10 +2489,10 @@ static int topk_batch_impl(fora_ctx *c, const int32_t *sources, int nq, int k, d
             Dev dw{};
             if ((rc = topk_round<ALLOC_TOPK>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, nullptr, with_idx ? 1 : 0, dw))) return rc;
             const double T = (1 + epsilon) * delta; // query.h:1030
-            const int h = ev_begin(c, 4);
+            EvSpan ev(c, EV_OTHER);
             hipLaunchKernelGGL(k_count_above, dim3(std::min<uint32_t>(chunks, 256), nb), dim3(BLOCK), 0, c->stream, dw,
                                (const uint8_t *)c->ws.d_active.get(), T, c->ws.d_above.get());
-            ev_end(c, h);
+            ev.end();
             above.assign((size_t)nb, 0);
             HIPCHK(c, hipMemcpyAsync(above.data(), c->ws.d_above.get(), (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
             if ((rc = check_dev_err(c))) return rc;
@@ -2523,7 +2532,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     const double L = log(2 / pfail);
     const long long m = c->g.m_attr;
     const double omega_max = (2 + epsilon) * L / min_delta / epsilon / epsilon;
-    c->bk_div = 1;
+    c->retry.div = 1;
     int rc = ensure_workspace(c, nq, omega_max);
     if (rc) return rc;
     if ((rc = ensure_topk_slabs(c, k))) return rc;
@@ -2536,7 +2545,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
     HIPCHK(c, w.d_round_walks.ensure((size_t)w.B));
     if ((rc = grow_pair(c, k, w.d_lb_ids, w.d_lb_sc))) return rc;
     const uint32_t chunks = slab_grid_x(c, std::min(nq, c->ws.B));
-    TopkBatch tb;
+    TopkBatch tb{EvSpan(c)};
     std::vector<unsigned long long> above;
     std::vector<uint32_t> failv;
     const int per = even_batch(nq, c->ws.B);
@@ -2556,7 +2565,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
             HIPCHK(c, c->ws.d_round_walks.zero(c->stream, (size_t)nb));
             Dev dw{};
             if ((rc = topk_round<ALLOC_BOUND>(c, tb, nb, with_idx != 0, round, rmax, omega, chunks, c->ws.d_round_walks.get(), 0, dw))) return rc;
-            const int h = ev_begin(c, 4);
+            EvSpan ev(c, EV_OTHER);
             if (delta < threshold) // query.h:745-746
                 hipLaunchKernelGGL(k_bounds_update, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, dw, (const uint64_t *)c->ws.d_ppr.get(),
                                    (const uint8_t *)c->ws.d_active.get(), (const unsigned long long *)c->ws.d_round_walks.get(), L,
@@ -2576,7 +2585,7 @@ static int topk_bound_batch_impl(fora_ctx *c, const int32_t *sources, int nq, in
                                    (const uint8_t *)c->ws.d_active.get(), (const double *)c->ws.d_upper.get(), (const double *)c->ws.d_lower.get(), delta,
                                    1.0 + epsilon, (1 + epsilon) / (1 - epsilon), c->ws.d_filter.get(), c->ws.d_fail.get());
             }
-            ev_end(c, h);
+            ev.end();
             above.assign((size_t)nb, 0);
             failv.assign((size_t)nb, 0);
             HIPCHK(c, hipMemcpyAsync(above.data(), c->ws.d_above.get(), (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2617,17 +2626,16 @@ static int power_iteration_batch_impl(fora_ctx *c, const int32_t *sources, int n
     const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
+        EvSpan batch(c, EV_BATCH);
         if ((rc = reset_batch_state(c, nb, sources + b0))) return rc;
-        Dev d = make_dev(c, nb, false, 0.0, c->omega); // rmax 0 -> threshold of one unit per out-edge
+        Dev d = make_dev(c, nb, false, 0.0, c->par.omega); // rmax 0 -> threshold of one unit per out-edge
         hipLaunchKernelGGL(k_init_batch, dim3((nb + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, d, 2);
         if ((rc = run_push_levels(c, d, nullptr, max_iter))) return rc;
         if (want_topk) {
-            const int h = ev_begin(c, 4);
+            EvSpan ev(c, EV_OTHER);
             if ((rc = launch_select(c, d, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
-            ev_end(c, h);
         }
-        if ((rc = close_batch(c, hb, "power iteration"))) return rc;
+        if ((rc = close_batch(c, &batch, "power iteration"))) return rc;
         if (want_topk && (rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)b0))) return rc;
         if ((rc = copy_slab_out(c, c->ws.d_ppr.get(), 0, (uint64_t)b0, (uint64_t)nb, ppr_fix_out, ppr_out, 62))) return rc;
     }
@@ -2648,8 +2656,8 @@ struct PushRmaxScope {
     fora_ctx *c;
     double rmax;
     bool balanced;
-    PushRmaxScope(fora_ctx *ctx, double r) : c(ctx), rmax(ctx->rmax), balanced(ctx->balanced) { c->rmax = r; c->balanced = false; }
-    ~PushRmaxScope() { c->rmax = rmax; c->balanced = balanced; }
+    PushRmaxScope(fora_ctx *ctx, double r) : c(ctx), rmax(ctx->par.rmax), balanced(ctx->bal.on) { c->par.rmax = r; c->bal.on = false; }
+    ~PushRmaxScope() { c->par.rmax = rmax; c->bal.on = balanced; }
 };
 static int fwdpush_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                               uint64_t *reserve_fix_out, uint64_t *residue_fix_out, int k, int32_t *ids, double *scores,
@@ -2776,11 +2784,11 @@ static int bwd_check_err(fora_ctx *c, const char *what) {
 // count pass over the nt targets already in d_bt; then the chunks
 static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
     r.thr = (uint64_t)std::floor(std::ldexp(rmax, 60));
-    r.afix = (uint64_t)std::ldexp(c->alpha, 62); // (as the forward push: make_dev's afix)
+    r.afix = (uint64_t)std::ldexp(c->par.alpha, 62); // (as the forward push: make_dev's afix)
     r.cap = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.bwd_lds_cap, 0), BWD_CAP_MAX);
     HIPCHK(c, hipMemsetAsync(c->bw.d_bstat.get(), 0, BS_WORDS * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->bw.d_bflag.get(), 0, nt, c->stream));
-    const int h = ev_begin(c, 11);
+    EvSpan ev(c, EV_BWD);
     if (r.cap > 0) {
         BwdDev b = make_bwd(c, r);
         b.nlist = nt;
@@ -2806,7 +2814,7 @@ static int bwd_count(fora_ctx *c, uint32_t nt, double rmax, BwdRun &r) {
         b.nlist = (uint32_t)r.spill.size();
         hipLaunchKernelGGL((k_bwd_push<true, false>), dim3(std::min<uint32_t>(c->g.tier.wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
     }
-    ev_end(c, h);
+    ev.end();
     r.cnt.resize(nt);
     HIPCHK(c, hipMemcpyAsync(r.cnt.data(), c->bw.d_bcnt.get(), (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(r.stat, c->bw.d_bstat.get(), BS_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2845,7 +2853,7 @@ static int bwd_write(fora_ctx *c, const BwdRun &r, size_t k) {
     for (auto it = std::lower_bound(r.spill.begin(), r.spill.end(), t0); it != r.spill.end() && *it < t1; ++it) gl.push_back(*it - t0);
     HIPCHK(c, hipMemcpyAsync(c->bw.d_boff.get(), off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
     if (!gl.empty()) HIPCHK(c, hipMemcpyAsync(c->bw.d_blist.get(), gl.data(), gl.size() * 4, hipMemcpyHostToDevice, c->stream));
-    const int h = ev_begin(c, 11);
+    EvSpan ev(c, EV_BWD);
     BwdDev b = make_bwd(c, r);
     b.targets = c->bw.d_bt.get() + t0;
     b.spilled = c->bw.d_bflag.get() + t0;
@@ -2858,7 +2866,7 @@ static int bwd_write(fora_ctx *c, const BwdRun &r, size_t k) {
         b.nlist = (uint32_t)gl.size();
         hipLaunchKernelGGL((k_bwd_push<true, true>), dim3(std::min<uint32_t>(c->g.tier.wgs, b.nlist)), dim3(BLOCK), 0, c->stream, b);
     }
-    ev_end(c, h);
+    ev.end();
     uint64_t st[BS_WORDS];
     HIPCHK(c, hipMemcpyAsync(st, c->bw.d_bstat.get(), sizeof(st), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (off / gl are host vectors of this frame)
@@ -2876,7 +2884,7 @@ static int bwd_write(fora_ctx *c, const BwdRun &r, size_t k) {
 static int check_bwd_rmax(fora_ctx *c, double rmax) {
     if (!(rmax > 0) || !std::isfinite(rmax)) return fail(c, FORA_E_ARG, "rmax must be > 0");
     // every residue stays below max(1, rmax / alpha) and every estimate below 1 + that: u64 at 2^60 holds less than 16
-    if (!(1.0 + std::max(1.0, rmax / c->alpha) < 16.0)) return fail(c, FORA_E_ARG, "rmax / alpha too large for the 2^60 fixed point");
+    if (!(1.0 + std::max(1.0, rmax / c->par.alpha) < 16.0)) return fail(c, FORA_E_ARG, "rmax / alpha too large for the 2^60 fixed point");
     return FORA_OK;
 }
 
@@ -2890,9 +2898,9 @@ static void fill_bwd_stats(fora_ctx *c, const BwdRun &r, uint64_t nt, fora_bwd_s
     bwd->global_targets = r.spill.size();
     bwd->levels = (int32_t)r.stat[BS_LEVELS];
     bwd->chunks = (int32_t)r.chunks.size();
-    bwd->bwd_ms = c->bwd_ms;
+    bwd->bwd_ms = c->tm.bwd_ms;
     bwd->walk_ms = walk_ms;
-    bwd->combine_ms = c->combine_ms;
+    bwd->combine_ms = c->tm.combine_ms;
 }
 
 static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
@@ -2901,7 +2909,7 @@ static int bwdpush_batch_impl(fora_ctx *c, const int32_t *targets, int nt, doubl
     if (int rc = check_id_range(c, targets, nt, "target")) return rc;
     if (int rc = check_bwd_rmax(c, rmax)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->bwd_ms = c->combine_ms = 0;
+    c->tm.bwd_ms = c->tm.combine_ms = 0;
     BwdRun r;
     if (nt == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
     if (int rc = ensure_reverse_csr(c)) return rc;
@@ -2958,9 +2966,8 @@ static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, const WalkCount &
         const uint64_t wgs = std::max<uint64_t>(1, (uint64_t)c->prop.multiProcessorCount * 8 / (uint64_t)nb);
         const uint64_t per_wg = std::min<uint64_t>(1 << 16, std::max<uint64_t>(1 << 12, (j1 - j0 + wgs - 1) / wgs));
         const unsigned X = (unsigned)((j1 - j0 + per_wg - 1) / per_wg);
-        const int h = ev_begin(c, 3);
+        EvSpan ev(c, EV_WALK);
         hipLaunchKernelGGL(k_walk_mc, dim3(X, nb), dim3(BLOCK), 0, c->stream, d, w.wbase, w.wrem, j0, j1, per_wg);
-        ev_end(c, h);
     }
 }
 
@@ -2969,24 +2976,23 @@ static void launch_mc_walks(fora_ctx *c, const Dev &d, int nb, const WalkCount &
 static int bippr_combine(fora_ctx *c, const BwdRun &r, int nb) {
     const uint64_t n = (uint64_t)c->g.n;
     const uint64_t tiles = ((uint64_t)nb + 31) / 32 * ((n + 31) / 32);
-    int h = ev_begin(c, 12);
+    EvSpan ev(c, EV_COMBINE);
     hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(),
                        (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
-    ev_end(c, h);
+    ev.end();
     const bool one_chunk = r.chunks.size() == 1; // (then its entries were written once for every batch)
     for (size_t ck = 0; ck < r.chunks.size(); ck++) {
         if (!one_chunk) if (int rc = bwd_write(c, r, ck)) return rc;
         const uint32_t t0 = r.chunks[ck].first, len = r.chunks[ck].second - t0;
-        h = ev_begin(c, 12);
+        ev.begin(EV_COMBINE);
         hipLaunchKernelGGL(k_bippr_combine, dim3((unsigned)(((uint64_t)len * 64 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream,
                            (const uint64_t *)c->ws.d_residue.get(), (uint32_t)nb, (const int32_t *)c->ws.d_src.get(), (const uint64_t *)c->bw.d_boff.get(),
                            (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0, len, c->ws.d_ppr.get());
-        ev_end(c, h);
+        ev.end();
     }
-    h = ev_begin(c, 12);
+    ev.begin(EV_COMBINE);
     hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)tiles), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(),
                        n, (uint64_t)nb); // -> slot-major estimates at 2^-60 in the residue slabs
-    ev_end(c, h);
     return FORA_OK;
 }
 
@@ -3000,7 +3006,7 @@ static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkC
     const int per = even_batch(nq, c->ws.B);
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
-        const int hb = ev_begin(c, 5);
+        EvSpan batch(c, EV_BATCH);
         int rc = reset_batch_state(c, nb, sources + b0);
         if (rc) return rc;
         HIPCHK(c, c->ws.d_qs.zero(c->stream, (size_t)nb));
@@ -3011,20 +3017,18 @@ static int walk_batches(fora_ctx *c, const int32_t *sources, int nq, const WalkC
         de.ppr = est;
         {
             const uint32_t chunks = (uint32_t)std::min<int64_t>(((int64_t)c->g.n + BLOCK - 1) / BLOCK, 64);
-            const int h = ev_begin(c, 4);
+            EvSpan ev(c, EV_OTHER);
             hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nb), dim3(BLOCK), 0, c->stream, de);
-            ev_end(c, h);
         }
         if (want_topk) {
-            const int h = ev_begin(c, 4);
+            EvSpan ev(c, EV_OTHER);
             if ((rc = launch_select(c, de, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
-            ev_end(c, h);
         }
         HIPCHK(c, hipMemcpyAsync(c->ws.h_qs_pin.get(), c->ws.d_qs.get(), (size_t)nb * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = close_batch(c, hb, bwd ? "bippr" : "montecarlo"))) return rc;
-        c->timing.walks += w.W * (uint64_t)nb;
-        c->timing.walk_steps += *c->ws.h_steps_pin.get();
+        if ((rc = close_batch(c, &batch, bwd ? "bippr" : "montecarlo"))) return rc;
+        c->tm.total.walks += w.W * (uint64_t)nb;
+        c->tm.total.walk_steps += *c->ws.h_steps_pin.get();
         if (stats)
             for (int i = 0; i < nb; i++) {
                 fora_query_stats &o = stats[b0 + i];
@@ -3066,8 +3070,8 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
     WalkCount w;
     if (int rc = walk_count(c, omega, w)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->bwd_ms = c->combine_ms = 0;
-    const double walk_ms0 = c->timing.walk_ms;
+    c->tm.bwd_ms = c->tm.combine_ms = 0;
+    const double walk_ms0 = c->tm.total.walk_ms;
     BwdRun r;
     if (nq == 0) { fill_bwd_stats(c, r, 0, bwd, 0); return FORA_OK; }
     // (the FORA plan: the ppr and residue slabs and the per-slot words are used here)
@@ -3085,7 +3089,7 @@ static int bippr_batch_impl(fora_ctx *c, const int32_t *sources, int nq, double 
     }
     if (r.chunks.size() == 1 && (rc = bwd_write(c, r, 0))) return rc; // shared by every batch
     if ((rc = walk_batches(c, sources, nq, w, &r, rmax, ppr_out, ppr_fix_out, k, ids, scores, stats))) return rc;
-    fill_bwd_stats(c, r, n, bwd, c->timing.walk_ms - walk_ms0);
+    fill_bwd_stats(c, r, n, bwd, c->tm.total.walk_ms - walk_ms0);
     return FORA_OK;
 }
 
@@ -3105,12 +3109,10 @@ static bool want_by_slot(const fora_ctx *c, int nb, uint64_t entries) {
 static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t nt, unsigned long long *out) {
     const uint64_t n = (uint64_t)c->g.n;
     const bool by_slot = want_by_slot(c, nb, r.off[nt]);
-    int h;
     if (by_slot) {
-        h = ev_begin(c, 12);
+        EvSpan ev(c, EV_COMBINE);
         hipLaunchKernelGGL(k_transpose_u64, dim3((unsigned)(((uint64_t)nb + 31) / 32 * ((n + 31) / 32))), dim3(BLOCK), 0, c->stream,
                            (const uint64_t *)c->ws.d_ppr.get(), c->ws.d_residue.get(), (uint64_t)nb, n); // -> node-major [n][nb] in the residue slabs
-        ev_end(c, h);
     }
     const uint64_t *slabs = by_slot ? c->ws.d_residue.get() : c->ws.d_ppr.get();
     const uint64_t groups = by_slot ? ((uint64_t)nb + 63) / 64 : 1;
@@ -3126,7 +3128,7 @@ static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t 
         span = std::min<uint64_t>(span, 1u << 30);
         const uint64_t waves = (ne + span - 1) / span;
         const dim3 grid((unsigned)((waves + BLOCK / 64 - 1) / (BLOCK / 64)), (unsigned)groups);
-        h = ev_begin(c, 12);
+        EvSpan ev(c, EV_COMBINE);
         if (by_slot)
             hipLaunchKernelGGL((k_bippr_combine_targets<true>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
                                (const uint64_t *)c->bw.d_boff.get(), (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0,
@@ -3135,7 +3137,6 @@ static int bippr_combine_targets(fora_ctx *c, const BwdRun &r, int nb, uint64_t 
             hipLaunchKernelGGL((k_bippr_combine_targets<false>), grid, dim3(BLOCK), 0, c->stream, slabs, (uint32_t)nb, n, (const int32_t *)c->ws.d_src.get(),
                                (const uint64_t *)c->bw.d_boff.get(), (const uint32_t *)c->bw.d_enode.get(), (const uint64_t *)c->bw.d_ep.get(), (const uint64_t *)c->bw.d_er.get(), t0,
                                t1 - t0, (uint32_t)span, nt, out);
-        ev_end(c, h);
     }
     return FORA_OK;
 }
@@ -3158,8 +3159,8 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
     if (int rc = check_id_range(c, sources, nq)) return rc;
     if (int rc = check_id_range(c, targets, nt, "target")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->bwd_ms = c->combine_ms = 0;
-    const double walk_ms0 = c->timing.walk_ms;
+    c->tm.bwd_ms = c->tm.combine_ms = 0;
+    const double walk_ms0 = c->tm.total.walk_ms;
     BwdRun r;
     auto fill_stats = [&](int i, uint64_t sum) {
         if (!stats) return;
@@ -3195,7 +3196,7 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
     for (int b0 = 0; b0 < nq; b0 += per) {
         const int nb = std::min(per, nq - b0);
         const uint64_t cells = (uint64_t)nb * T;
-        const int hb = ev_begin(c, 5);
+        EvSpan batch(c, EV_BATCH);
         if ((rc = reset_batch_state(c, nb, sources + b0))) return rc;
         HIPCHK(c, c->bw.d_tgt_est.zero(c->stream, cells + (uint64_t)nb));
         const Dev d = make_dev(c, nb, false);
@@ -3203,15 +3204,14 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
         unsigned long long *const est = (unsigned long long *)c->bw.d_tgt_est.get();
         if ((rc = bippr_combine_targets(c, r, nb, T, est))) return rc;
         {
-            const int h = ev_begin(c, 12);
+            EvSpan ev(c, EV_COMBINE);
             hipLaunchKernelGGL(k_bippr_targets_finish, dim3((unsigned)std::min<uint64_t>((T + BLOCK - 1) / BLOCK, 64), (unsigned)nb), dim3(BLOCK), 0,
                                c->stream, (const uint64_t *)c->bw.d_tgt_est.get(), T, est_out ? c->bw.d_tgt_f64.get() : nullptr, est + cells);
-            ev_end(c, h);
         }
         HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = close_batch(c, hb, "bippr targets"))) return rc;
-        c->timing.walks += w.W * (uint64_t)nb;
-        c->timing.walk_steps += *c->ws.h_steps_pin.get();
+        if ((rc = close_batch(c, &batch, "bippr targets"))) return rc;
+        c->tm.total.walks += w.W * (uint64_t)nb;
+        c->tm.total.walk_steps += *c->ws.h_steps_pin.get();
         if (stats) {
             HIPCHK(c, hipMemcpy(sums.data(), c->bw.d_tgt_est.get() + cells, (size_t)nb * 8, hipMemcpyDeviceToHost));
             for (int i = 0; i < nb; i++) fill_stats(b0 + i, sums[(size_t)i]);
@@ -3219,33 +3219,33 @@ static int bippr_targets_batch_impl(fora_ctx *c, const int32_t *sources, int nq,
         if (est_fix_out) HIPCHK(c, hipMemcpy(est_fix_out + (uint64_t)b0 * T, c->bw.d_tgt_est.get(), cells * 8, hipMemcpyDeviceToHost));
         if (est_out) HIPCHK(c, hipMemcpy(est_out + (uint64_t)b0 * T, c->bw.d_tgt_f64.get(), cells * 8, hipMemcpyDeviceToHost));
     }
-    fill_bwd_stats(c, r, T, bwd, c->timing.walk_ms - walk_ms0);
+    fill_bwd_stats(c, r, T, bwd, c->tm.total.walk_ms - walk_ms0);
     return FORA_OK;
 }
 
 int fora_hip_montecarlo_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double *ppr_out, uint64_t *ppr_fix_out,
                               int k, int32_t *ids, double *scores, fora_query_stats *stats) {
-    return montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats); // (no buckets, no push: nothing to retry)
+    return drop_pairs_unless_ok(c, montecarlo_batch_impl(c, sources, nq, epsilon, ppr_out, ppr_fix_out, k, ids, scores, stats)); // (no buckets, no push: nothing to retry)
 }
 
 int fora_hip_bwdpush_batch(fora_ctx *c, const int32_t *targets, int nt, double rmax, uint64_t *reserve_fix_out,
                            uint64_t *residue_fix_out, fora_bwd_stats *bwd) {
-    return bwdpush_batch_impl(c, targets, nt, rmax, reserve_fix_out, residue_fix_out, bwd);
+    return drop_pairs_unless_ok(c, bwdpush_batch_impl(c, targets, nt, rmax, reserve_fix_out, residue_fix_out, bwd));
 }
 
 int fora_hip_bippr_batch(fora_ctx *c, const int32_t *sources, int nq, double epsilon, double rmax_scale, double *ppr_out,
                          uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, fora_query_stats *stats, fora_bwd_stats *bwd) {
-    return bippr_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, ppr_fix_out, k, ids, scores, stats, bwd);
+    return drop_pairs_unless_ok(c, bippr_batch_impl(c, sources, nq, epsilon, rmax_scale, ppr_out, ppr_fix_out, k, ids, scores, stats, bwd));
 }
 
 int fora_hip_bippr_targets_batch(fora_ctx *c, const int32_t *sources, int nq, const int32_t *targets, int nt, double epsilon,
                                  double rmax_scale, double *est_out, uint64_t *est_fix_out, fora_query_stats *stats, fora_bwd_stats *bwd) {
-    return bippr_targets_batch_impl(c, sources, nq, targets, nt, epsilon, rmax_scale, est_out, est_fix_out, stats, bwd);
+    return drop_pairs_unless_ok(c, bippr_targets_batch_impl(c, sources, nq, targets, nt, epsilon, rmax_scale, est_out, est_fix_out, stats, bwd));
 }
 
 int fora_hip_reset_timing(fora_ctx *c) {
     if (!c) return FORA_E_ARG;
-    c->timing = fora_timing{};
+    c->tm.total = fora_timing{};
     (void)hipSetDevice(c->device);
     (void)hipMemset(c->d_stamps.get(), 0, 32 * sizeof(unsigned long long));
     return FORA_OK;
@@ -3258,7 +3258,7 @@ int fora_hip_get_stamps(fora_ctx *c, uint64_t *out32) {
 }
 int fora_hip_get_timing(fora_ctx *c, fora_timing *out) {
     if (!c || !out) return FORA_E_ARG;
-    *out = c->timing;
+    *out = c->tm.total;
     return FORA_OK;
 }
 
