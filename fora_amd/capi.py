@@ -19,6 +19,7 @@ SYMBOLS = [
     "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
     "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bippr_targets_batch", "fora_hip_bwdpush_batch",
     "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
+    "fora_hip_query_seeds_batch",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -67,6 +68,14 @@ class BwdStats(C.Structure):
 class SparseStats(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("max_row", C.c_uint64), ("thr_fix", C.c_uint64), ("batches", C.c_int32),
                 ("reserved_", C.c_int32), ("compact_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+class SeedsStats(C.Structure):
+    _fields_ = [("seeds", C.c_uint64), ("distinct", C.c_uint64), ("queries", C.c_uint64), ("dangling", C.c_uint64),
+                ("batches", C.c_int32), ("reserved_", C.c_int32), ("combine_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
@@ -386,6 +395,39 @@ class Engine:
         self._chk(self._lib.fora_hip_bippr_targets_batch(self._ctx, _p(src), C.c_int(nq), _p(tg), C.c_int(nt), C.c_double(epsilon),
                                                          C.c_double(rmax_scale), _p(est), _p(fix), st, C.byref(bwd)))
         return est, fix, self._stats(st, nq), bwd.as_dict()
+
+    def query_seeds(self, sets, weights=None, with_idx=False, k=0, want_ppr=False, want_fix=True):
+        """PPR restarting on weighted seed sets (fora_hip_query_seeds_batch): one row per set, the rows of the seeds combined
+        on the GPU.  sets: a LIST of int sequences, one per set, or a 2-TUPLE (set_ptr, seeds) in CSR form -- a tuple of two
+        is always read as that pair, so two sets go in a list; weights: the same shape (a list of float sequences, or one
+        flat array beside `seeds`), None: uniform.  Returns a dict: fix (raw u64 at 2^62 [ns,n] or None), ppr
+        (f64 [ns,n] or None), ids / scores ([ns,k] or None), row_sum_fix (u64 [ns]), stats (a dict)."""
+        flat = isinstance(sets, tuple) and len(sets) == 2
+        if flat:
+            set_ptr = np.ascontiguousarray(sets[0], dtype=np.int64)
+            seeds = np.ascontiguousarray(sets[1], dtype=np.int32)
+        else:
+            sets = [np.asarray(x, dtype=np.int32).reshape(-1) for x in sets]
+            set_ptr = np.zeros(len(sets) + 1, dtype=np.int64)
+            np.cumsum(np.array([x.size for x in sets], dtype=np.int64), out=set_ptr[1:])
+            seeds = np.concatenate(sets).astype(np.int32) if sets else np.zeros(0, dtype=np.int32)
+        w = None
+        if weights is not None:
+            w = weights if flat else (np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in weights])
+                                      if len(weights) else np.zeros(0))
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.size != seeds.size:
+                raise ValueError("weights must have the shape of the seeds")
+        ns = set_ptr.size - 1
+        st = SeedsStats()
+        ppr = np.zeros((ns, self.n), dtype=np.float64) if want_ppr else None
+        fix = np.zeros((ns, self.n), dtype=np.uint64) if want_fix else None
+        ids = np.zeros((ns, k), dtype=np.int32) if k > 0 else None
+        sc = np.zeros((ns, k), dtype=np.float64) if k > 0 else None
+        sums = np.zeros(ns, dtype=np.uint64)
+        self._chk(self._lib.fora_hip_query_seeds_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
+                                                       _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), _p(sums), C.byref(st)))
+        return {"fix": fix, "ppr": ppr, "ids": ids, "scores": sc, "row_sum_fix": sums, "stats": st.as_dict()}
 
     # ---- stage hooks
     def bwdpush(self, targets, rmax):

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -27,7 +28,7 @@ namespace {
 // What an event pair times, named after the fora_timing field it feeds.  The switch of ev_collect is the one place that says which
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
-              EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT };
+              EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -85,6 +86,7 @@ struct Tunables {
     int64_t bwd_chunk = 0;       // backward push: targets per chunk (0: as many as the entry budget from free HBM holds)
     int64_t tgt_lanes = -1;      // targeted BiPPR combine (k_bippr_combine_targets): 0 lane = slot over the transposed walk slabs, 1 lane = entry over the slot-major ones, -1: by the batch's slots and the call's entries (want_by_slot).  Same bits either way
     int64_t tgt_span = 0;        // ... entries per wave (0: from the chunk's entries, 64 .. 1024).  Same bits for every value
+    int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
     {"direct", &Tunables::direct, true}, {"force_wide", &Tunables::force_wide, true}, {"pass_bins", &Tunables::pass_bins, true},
@@ -95,6 +97,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"profile", &Tunables::profile, false}, {"grid", &Tunables::grid, false},
     {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
     {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
+    {"seeds_dedup", &Tunables::seeds_dedup, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -265,6 +268,12 @@ struct BwdBufs {
     // sums; its f64 copy.  nt has nothing to do with n, so these are no slabs of the workspace
     DevBuf<uint64_t> d_tgt_est; DevBuf<double> d_tgt_f64;
 };
+// Seed sets (fora_hip_query_seeds_batch): buffers of their own, apart from the workspace; grow-only, kept until set_graph or destroy.
+struct SeedBufs {
+    DevBuf<uint64_t> d_acc;  // the accumulator block of a call, [ns][n] at 2^-62 (n changes with the graph: no slabs of the workspace's plan)
+    DevBuf<uint64_t> d_list; // use list of the batch in progress (SeedBatch::pack); the dangling seeds' triples after the last batch
+    DevBuf<unsigned long long> d_sums; // [ns] row sums
+};
 // Sparse result of the last fora_hip_query_sparse_batch (free_sparse: sparse_clear, set_graph), apart from the workspace --
 // free_workspace (set_batch, set_option, a bucket retry) leaves it alone.
 struct SparseResult {
@@ -309,7 +318,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -319,7 +328,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd;
     int batch_req = 0;         // the caller's request (fora_hip_set_batch), not part of a plan
     uint64_t bin_launches = 0; // parity picks the counter set
     std::vector<QState> h_qs;
@@ -837,6 +846,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_BWD: t.bwd_ms += ms; break;               // k_bwd_push: reported through fora_bwd_stats only (fora_timing keeps its layout)
         case EV_COMBINE: t.combine_ms += ms; break;       // BiPPR's transposes, combines and finish: fora_bwd_stats only
         case EV_SP_COMPACT: t.sp_compact_ms += ms; break; // k_sparse_count / k_sparse_write: reported through fora_sparse_stats only
+        case EV_SEED_COMBINE: t.seed_combine_ms += ms; break; // k_seed_combine: reported through fora_seeds_stats only
         }
     }
     t.ev_used = 0;
@@ -1622,6 +1632,191 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     return FORA_OK;
 }
 
+// ---- seed sets (fora_hip_query_seeds_batch; the SEED SETS contract of include/fora_hip.h).  PPR is linear in the restart
+// vector: every seed a call needs runs once as an ordinary query (run_query_batch), and k_seed_combine folds the batch's ppr
+// slabs into one accumulator row per set before the next batch reuses them.  Nothing of the push or the walks knows of sets.
+struct SeedUse { uint32_t set, slot; uint64_t w; }; // term of a set: the row of `slot` (of the call, then of its batch) times w / 2^62
+// The use list of one batch, sorted by set, as one upload: use_w[U] (u64), then use_slot[U] | seg[T + 1] | set_id[T] (u32).
+struct SeedBatch {
+    std::vector<SeedUse> uses;
+    std::vector<uint64_t> pack;
+    uint32_t U = 0, T = 0;
+    void build() {
+        U = (uint32_t)uses.size();
+        T = 0;
+        for (uint32_t i = 0; i < U; i++) T += i == 0 || uses[i].set != uses[i - 1].set;
+        pack.assign((size_t)U + ((size_t)U + 2 * (size_t)T + 2) / 2, 0);
+        uint32_t *slot = (uint32_t *)(pack.data() + U), *seg = slot + U, *set_id = seg + T + 1;
+        uint32_t t = 0;
+        for (uint32_t i = 0; i < U; i++) {
+            pack[i] = uses[i].w;
+            slot[i] = uses[i].slot;
+            if (i == 0 || uses[i].set != uses[i - 1].set) { seg[t] = i; set_id[t++] = uses[i].set; }
+        }
+        seg[T] = U;
+    }
+};
+
+// the combine of the batch just closed: its slabs hold the rows until the next batch starts on the same stream
+int seed_combine(fora_ctx *c, const SeedBatch &b) {
+    if (!b.U) return FORA_OK;
+    HIPCHK(c, hipMemcpyAsync(c->sd.d_list.get(), b.pack.data(), b.pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+    const uint64_t *use_w = c->sd.d_list.get();
+    const uint32_t *use_slot = (const uint32_t *)(use_w + b.U), *seg = use_slot + b.U, *set_id = seg + b.T + 1;
+    const uint32_t n = (uint32_t)c->g.n;
+    const uint32_t R = (uint32_t)std::max<uint64_t>(2 * SC_TILE, (((uint64_t)n + 1023) / 1024 + SC_TILE - 1) / SC_TILE * SC_TILE); // at most 1024 workgroups per set
+    const unsigned X = (unsigned)(((uint64_t)n + R - 1) / R);
+    EvSpan ev(c, EV_SEED_COMBINE);
+    for (uint32_t y0 = 0; y0 < b.T; y0 += 65535)
+        hipLaunchKernelGGL(k_seed_combine, dim3(X, std::min<uint32_t>(65535, b.T - y0)), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), n, R,
+                           set_id + y0, seg + y0, use_slot, use_w, c->sd.d_acc.get());
+    return FORA_OK;
+}
+
+int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                     double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, uint64_t *row_sum_fix_out,
+                     fora_seeds_stats *st) {
+    if (int rc = check_batch_args(c, nullptr, 0)) return rc;
+    if (ns < 0) return fail(c, FORA_E_ARG, "bad sets: negative count");
+    if (st) memset(st, 0, sizeof(*st));
+    if (ns == 0) return FORA_OK;
+    if (!set_ptr || !seeds) return fail(c, FORA_E_ARG, "bad sets: null set_ptr or seeds");
+    if (set_ptr[0] != 0) return fail(c, FORA_E_ARG, "set_ptr[0] must be 0");
+    for (int g = 0; g < ns; g++)
+        if (set_ptr[g + 1] <= set_ptr[g]) return fail(c, FORA_E_ARG, set_ptr[g + 1] < set_ptr[g] ? "set_ptr decreases" : "empty seed set");
+    const int64_t total = set_ptr[ns];
+    if (total > 0x7FFFFFFF) return fail(c, FORA_E_ARG, "more than 2^31 - 1 seeds in one call");
+    if (with_idx && !c->ix.have) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
+    if (k != 0) if (int rc = check_k(c, k)) return rc; // (0: no top-k)
+    if (int rc = check_id_range(c, seeds, (int)total, "seed")) return rc;
+    // the weights at 2^-62
+    std::vector<uint64_t> wfix((size_t)total);
+    for (int g = 0; g < ns; g++) {
+        const int64_t j0 = set_ptr[g], kg = set_ptr[g + 1] - j0;
+        if (!weights) {
+            const uint64_t base = FIX_ONE / (uint64_t)kg, rem = FIX_ONE % (uint64_t)kg;
+            for (int64_t j = 0; j < kg; j++) wfix[(size_t)(j0 + j)] = base + ((uint64_t)j < rem ? 1 : 0);
+            continue;
+        }
+        double S = 0;
+        for (int64_t j = 0; j < kg; j++) {
+            const double w = weights[j0 + j];
+            if (!std::isfinite(w) || w < 0) return fail(c, FORA_E_ARG, "seed weights must be finite and >= 0");
+            S += w;
+        }
+        if (!(S > 0) || !std::isfinite(S)) return fail(c, FORA_E_ARG, "the weights of a seed set must have a finite sum > 0");
+        for (int64_t j = 0; j < kg; j++) wfix[(size_t)(j0 + j)] = (uint64_t)std::ldexp(weights[j0 + j] / S, 62);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->tm.seed_combine_ms = 0;
+    const uint64_t n = (uint64_t)c->g.n;
+    // Slots: the seeds that run, in order of first appearance.  A dangling seed is its own whole answer (query_common) and
+    // takes none: its term is w at the seed itself.
+    const bool dedup = c->opt_.seeds_dedup != 0;
+    std::unordered_map<int32_t, uint32_t> slot_of; // seed id -> slot (with dedup; without: -> 0, the ids seen)
+    std::vector<int32_t> slot_src;
+    std::vector<SeedUse> uses;                     // the terms of the live seeds, by set
+    std::vector<uint32_t> dang_set; std::vector<int32_t> dang_node; std::vector<uint64_t> dang_w;
+    for (int g = 0; g < ns; g++)
+        for (int64_t j = set_ptr[g]; j < set_ptr[g + 1]; j++) {
+            const int32_t s = seeds[j];
+            const auto seen = slot_of.find(s);
+            if (is_dangling(c, s)) {
+                if (seen == slot_of.end()) slot_of.emplace(s, 0u);
+                dang_set.push_back((uint32_t)g); dang_node.push_back(s); dang_w.push_back(wfix[(size_t)j]);
+                continue;
+            }
+            uint32_t slot;
+            if (dedup && seen != slot_of.end()) slot = seen->second;
+            else {
+                slot = (uint32_t)slot_src.size();
+                slot_src.push_back(s);
+                if (seen == slot_of.end()) slot_of.emplace(s, slot);
+            }
+            uses.push_back(SeedUse{(uint32_t)g, slot, wfix[(size_t)j]});
+        }
+    const int nl = (int)slot_src.size();
+    const bool want_topk = k > 0 && (ids || scores);
+    // The accumulator block, ahead of the workspace: a batch size chosen from the free memory then accounts for it.  No room
+    // beside a workspace that is already there: that one goes, and the call plans a new one in what the block leaves.
+    const uint64_t cells = (uint64_t)ns * n;
+    const char *const no_room = "no device memory for the seed sets' accumulator block (ns x n words): split the call";
+    if (cells > (1ull << 40)) return fail(c, FORA_E_NOMEM, no_room); // (8 TB: more than any device holds, and cells * 8 stays far from 2^64)
+    if (c->sd.d_acc.ensure(cells) != hipSuccess) {
+        (void)hipGetLastError();
+        free_workspace(c);
+        if (c->sd.d_acc.ensure(cells) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, FORA_E_NOMEM, no_room);
+        }
+    }
+    HIPCHK(c, c->sd.d_acc.zero(c->stream, cells));
+    int rc = FORA_OK;
+    int nbatch = 0;
+    if (nl > 0 || want_topk) {
+        if ((rc = ensure_query_workspace(c, std::max(nl, 1), want_topk ? k : 0))) return rc;
+    }
+    if (nl > 0) {
+        const int per = even_batch(nl, c->ws.B);
+        nbatch = (nl + per - 1) / per;
+        std::vector<SeedBatch> batches((size_t)nbatch);
+        for (const SeedUse &u : uses) batches[u.slot / (uint32_t)per].uses.push_back(SeedUse{u.set, u.slot % (uint32_t)per, u.w}); // (in set order)
+        size_t words = 0;
+        for (SeedBatch &b : batches) { b.build(); words = std::max(words, b.pack.size()); }
+        HIPCHK(c, c->sd.d_list.ensure(std::max<size_t>(words, 1)));
+        for (int bi = 0; bi < nbatch; bi++) {
+            const int b0 = bi * per, nb = std::min(per, nl - b0);
+            if ((rc = run_query_batch(c, slot_src.data() + b0, nb, with_idx != 0, 0))) return rc;
+            if ((rc = seed_combine(c, batches[(size_t)bi]))) return rc;
+        }
+    }
+    uint64_t *const acc = c->sd.d_acc.get();
+    const size_t nd = dang_set.size();
+    if (nd) { // w[nd] (u64), then set[nd] | node[nd] (32-bit)
+        std::vector<uint64_t> pack(nd + (2 * nd + 1) / 2, 0);
+        memcpy(pack.data(), dang_w.data(), nd * 8);
+        memcpy(pack.data() + nd, dang_set.data(), nd * 4);
+        memcpy((uint32_t *)(pack.data() + nd) + nd, dang_node.data(), nd * 4);
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the last combine reads the list)
+        HIPCHK(c, c->sd.d_list.ensure(pack.size()));
+        HIPCHK(c, hipMemcpyAsync(c->sd.d_list.get(), pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+        const uint32_t *dset = (const uint32_t *)(c->sd.d_list.get() + nd);
+        hipLaunchKernelGGL(k_seed_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, dset, (const int32_t *)(dset + nd),
+                           (const uint64_t *)c->sd.d_list.get(), (uint32_t)n, acc);
+    }
+    if (row_sum_fix_out) {
+        HIPCHK(c, c->sd.d_sums.ensure((size_t)ns));
+        HIPCHK(c, c->sd.d_sums.zero(c->stream, (size_t)ns));
+        const unsigned chunks = (unsigned)std::min<uint64_t>((n + BLOCK - 1) / BLOCK, 64);
+        hipLaunchKernelGGL(k_seed_row_sum, dim3((unsigned)ns, chunks), dim3(BLOCK), 0, c->stream, (const uint64_t *)acc, (uint32_t)n, c->sd.d_sums.get());
+        HIPCHK(c, hipMemcpyAsync(row_sum_fix_out, c->sd.d_sums.get(), (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (want_topk)
+        for (int r0 = 0; r0 < ns; r0 += c->ws.B) { // the select works on the slots of a workspace: at most B rows at a time
+            const int nb = std::min(c->ws.B, ns - r0);
+            Dev ds = make_dev(c, nb, false);
+            ds.ppr = acc + (uint64_t)r0 * n;
+            if ((rc = launch_select(c, ds, nb, k, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
+            if ((rc = copy_topk_out(c, nb, k, ids, scores, (uint64_t)r0))) return rc;
+        }
+    if (ppr_fix_out) HIPCHK(c, hipMemcpyAsync(ppr_fix_out, acc, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ppr_out) { // in place: the block has no reader left
+        hipLaunchKernelGGL(k_seed_f64, dim3((unsigned)std::min<uint64_t>((cells + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, acc, cells);
+        HIPCHK(c, hipMemcpyAsync(ppr_out, acc, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("seed sets: ") + hipGetErrorString(e));
+    ev_collect(c);
+    if (st) {
+        st->seeds = (uint64_t)total; st->distinct = (uint64_t)slot_of.size(); st->queries = (uint64_t)nl; st->dangling = (uint64_t)nd;
+        st->batches = nbatch; st->combine_ms = c->tm.seed_combine_ms;
+    }
+    return FORA_OK;
+}
+
 // ---- frame of the two top-k drivers (fora_hip_topk_batch, fora_hip_topk_bound_batch): all active slots of a batch are
 // in the same round, so delta / rmax / omega are uniform per round; finished slots drop out.  Each driver keeps its own
 // delta schedule, rmax / omega formulas, bounds kernels and stop rule.
@@ -2066,6 +2261,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_index(c);
     free_graph(c);
     free_sparse(c); // (rows of another graph)
+    c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
         std::vector<uint64_t> rowinfo((size_t)n);
@@ -2329,6 +2525,15 @@ int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int
         c->tm.sp_compact_ms = 0;
         if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, &run)) return rc;
         return sparse_finish(c, run, sources, nq, row_ptr, sp_out);
+    });
+}
+
+// ---- seed sets: weighted multi-seed queries, one row per set (the SEED SETS contract of include/fora_hip.h)
+int fora_hip_query_seeds_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                               double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, uint64_t *row_sum_fix_out,
+                               fora_seeds_stats *st) {
+    return with_bucket_retry(c, [&] {
+        return query_seeds_impl(c, set_ptr, seeds, weights, ns, with_idx, ppr_out, ppr_fix_out, k, ids, scores, row_sum_fix_out, st);
     });
 }
 

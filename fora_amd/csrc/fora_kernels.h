@@ -3355,4 +3355,89 @@ __global__ void __launch_bounds__(BLOCK) k_sparse_vals(const uint64_t *fix, uint
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * BLOCK) vals[i] = fix2d(fix[i]);
 }
 
+// ------------------------------------------------------------------ seed sets (fora_hip_query_seeds_batch)
+// The rows of a batch folded into the call's accumulator block acc[ns][n]: row g += sum over the uses (slot, wfix) of set
+// g in this batch of floor(wfix * ppr[slot][v] / 2^62), every term floored on its own, the terms added as integers.
+// grid = (tiles, sets the batch touches): workgroup (x, y) owns the ids [x * R, (x + 1) * R), R a multiple of SC_TILE, of
+// set set_id[y], whose uses are [seg[y], seg[y + 1]) -- no other workgroup of the launch writes that piece of acc, and the
+// launches of a call follow each other on one stream, so the update is a plain read-add-write.  A lane takes the two words
+// of one 16-byte line; a row (slot * n, set * n) that starts at an odd word is read (written) with 8-byte accesses instead
+// -- the choice is the same for every lane of the launch's workgroup.  SC_UNROLL uses are in flight per lane.
+constexpr int SC_TILE = 2 * BLOCK; // ids per workgroup and step
+constexpr int SC_UNROLL = 4;       // uses in flight per lane
+__device__ __forceinline__ void sc_load(const uint64_t *row, bool aligned, uint32_t v, uint32_t hi, uint64_t &a, uint64_t &b) {
+    a = 0; b = 0;
+    if (aligned && v + 1 < hi) {
+        const ulonglong2 x = *reinterpret_cast<const ulonglong2 *>(row + v);
+        a = x.x; b = x.y;
+    } else {
+        if (v < hi) a = row[v];
+        if (v + 1 < hi) b = row[v + 1];
+    }
+}
+__global__ void __launch_bounds__(BLOCK) k_seed_combine(const uint64_t *ppr, uint32_t n, uint32_t R, const uint32_t *set_id, const uint32_t *seg,
+                                                        const uint32_t *use_slot, const uint64_t *use_w, uint64_t *acc) {
+    const uint32_t u0 = seg[blockIdx.y], u1 = seg[blockIdx.y + 1];
+    const uint64_t first = (uint64_t)set_id[blockIdx.y] * n;
+    uint64_t *out = acc + first;
+    const bool out_al = !(first & 1);
+    const uint32_t lo = blockIdx.x * R, hi = min(n, lo + R);
+    for (uint32_t v = lo + 2 * threadIdx.x; v < hi; v += SC_TILE) { // (v even: lo is a multiple of SC_TILE)
+        uint64_t sa = 0, sb = 0;
+        uint32_t u = u0;
+        for (; u + SC_UNROLL <= u1; u += SC_UNROLL) {
+            uint64_t a[SC_UNROLL], b[SC_UNROLL], w[SC_UNROLL];
+#pragma unroll
+            for (int i = 0; i < SC_UNROLL; i++) {
+                const uint64_t at = (uint64_t)use_slot[u + i] * n;
+                w[i] = use_w[u + i];
+                sc_load(ppr + at, !(at & 1), v, hi, a[i], b[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < SC_UNROLL; i++) { sa += mulshift62(w[i], a[i]); sb += mulshift62(w[i], b[i]); }
+        }
+        for (; u < u1; u++) {
+            const uint64_t at = (uint64_t)use_slot[u] * n, w = use_w[u];
+            uint64_t a, b;
+            sc_load(ppr + at, !(at & 1), v, hi, a, b);
+            sa += mulshift62(w, a); sb += mulshift62(w, b);
+        }
+        uint64_t oa, ob;
+        sc_load(out, out_al, v, hi, oa, ob);
+        oa += sa; ob += sb;
+        if (out_al && v + 1 < hi) {
+            *reinterpret_cast<ulonglong2 *>(out + v) = make_ulonglong2(oa, ob);
+        } else {
+            out[v] = oa; // (v < hi: the loop's condition)
+            if (v + 1 < hi) out[v + 1] = ob;
+        }
+    }
+}
+// the terms of the dangling seeds: acc[set][node] += wfix (a set may list the same dangling seed twice: atomics)
+__global__ void __launch_bounds__(BLOCK) k_seed_single(uint32_t cnt, const uint32_t *set_id, const int32_t *node, const uint64_t *w, uint32_t n,
+                                                       uint64_t *acc) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < cnt) atomicAdd((unsigned long long *)&acc[(uint64_t)set_id[i] * n + (uint32_t)node[i]], (unsigned long long)w[i]);
+}
+// sum of every row of the block; grid = (rows, chunks), row_sum zeroed
+__global__ void __launch_bounds__(BLOCK) k_seed_row_sum(const uint64_t *acc, uint32_t n, unsigned long long *row_sum) {
+    const uint64_t *row = acc + (uint64_t)blockIdx.x * n;
+    uint64_t s = 0;
+    const uint64_t step = (uint64_t)gridDim.y * BLOCK;
+    for (uint64_t v0 = (uint64_t)blockIdx.y * BLOCK + threadIdx.x; v0 < (uint64_t)n; v0 += step * SLAB_UNROLL) {
+        uint64_t x[SLAB_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * step < (uint64_t)n ? row[v0 + u * step] : 0;
+#pragma unroll
+        for (int u = 0; u < SLAB_UNROLL; u++) s += x[u];
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&row_sum[blockIdx.x], (unsigned long long)s);
+}
+// the block as f64 at 2^-62, in place (the last device step of a call that wants ppr_out)
+__global__ void __launch_bounds__(BLOCK) k_seed_f64(uint64_t *acc, uint64_t cnt) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * BLOCK)
+        acc[i] = (uint64_t)__double_as_longlong(fix2d(acc[i]));
+}
+
 } // namespace fora

@@ -101,6 +101,37 @@
  *     cap < entries, or no held result: FORA_E_ARG and nothing is written.
  *   - NULL ctx (answered without touching the GPU), NULL row_ptr, bad nq / sources, with_idx without an index:
  *     FORA_E_ARG.  No device memory for the result: FORA_E_NOMEM, no result held, the ctx still usable.
+ * SEED SETS (fora_hip_query_seeds_batch): PPR that restarts on a weighted SET of nodes, pi(w, .) = sum_j w_j * pi(s_j, .), one
+ * row per set.  Every seed the call needs runs once as an ordinary query of fora_hip_query_batch (same push, same walks, same
+ * batching, same dangling-source fast path); the rows are folded on the GPU, in fixed point, before anything leaves it.
+ *   - set g is seeds[set_ptr[g] .. set_ptr[g+1]), k_g >= 1 seeds in the caller's order.  Duplicate seeds inside a set are
+ *     separate terms, the same seed may appear in many sets, duplicate sets give duplicate rows.
+ *   - weights == NULL (uniform): seed j of a set (0-based) gets wfix_j = floor(2^62 / k_g) + (j < 2^62 mod k_g), so
+ *     sum(wfix) == 2^62 exactly.
+ *   - weights given (set_ptr[ns] of them, beside the seeds): every weight finite and >= 0, the set's sum S > 0 (and finite), S
+ *     added left to right in doubles; wfix_j = (uint64_t)ldexp(w_j / S, 62) -- the ldexp is exact, the cast floors, every
+ *     wfix_j <= 2^62; sum(wfix) <= 2^62 up to the rounding of the k_g divisions and of the adds of S (2^-53 relative each,
+ *     2^9 units: sum(wfix) <= 2^62 + 2^10 k_g; <= 2^62 where S and the quotients are exact).
+ *   - row_g[v] = sum_j floor(wfix_j * x_j[v] / 2^62), x_j being the row fora_hip_query_batch_fix writes for seeds[j] with the same
+ *     ctx state (parameters, seed, with_idx, options, --balanced): each term floored on its own from the 128-bit product, the
+ *     terms added as integers.  The value is at 2^-62; ppr_out is the word * 2^-62.  A dangling seed contributes exactly wfix_j
+ *     at v = s_j (its row is FORA_FIX_ONE at s).  A singleton set with uniform weight gives x unchanged.
+ *   - row_sum_fix_out[g] = sum_v row_g[v] <= sum(wfix) (bounded above: exactly 2^62 for uniform weights): the combine creates
+ *     no mass beyond the weights; the mass lost is at most one unit per non-zero term.
+ *   - no bit depends on the batch size, on which batch a seed lands in, on the option "seeds_dedup" (1, default: a seed id runs
+ *     once per call; 0: every listed seed takes a slot of its own) or on any knob the environment can set: the rows x_j have
+ *     that property and the combine is integer adds.
+ *   - top-k: 1 <= k <= min(1024, n), or k == 0 for none; score descending, ties by ascending id, padded with (0, 0.0), as
+ *     fora_hip_topk_batch; taken from row_g, scores = word * 2^-62.
+ *   - stats: seeds = set_ptr[ns]; distinct = distinct seed ids; queries = single-source queries run; dangling = listed seeds
+ *     without out-edges (they never take a slot); batches; combine_ms.  fora_timing folds the underlying queries exactly as
+ *     fora_hip_query_batch would.
+ *   - ns == 0: FORA_OK, nothing is written, *st is all zero.
+ *   - NULL ctx (answered without touching the GPU), ns < 0, NULL set_ptr or seeds with work to do, set_ptr[0] != 0, a decreasing
+ *     set_ptr, an empty set, a seed id outside [0, n), a bad weight or a zero sum, with_idx without an index, a bad k:
+ *     FORA_E_ARG.  No device memory for the ns x n accumulator block: FORA_E_NOMEM, the ctx still usable; the caller splits
+ *     the call.
+ *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -189,6 +220,17 @@ typedef struct {
     double compact_ms;    /* device time of the compaction kernels, summed over the batches */
 } fora_sparse_stats;
 
+/* What a seed-set call ran (fora_hip_query_seeds_batch). */
+typedef struct {
+    uint64_t seeds;        /* seeds listed over all sets (== set_ptr[ns]) */
+    uint64_t distinct;     /* distinct seed ids of the call */
+    uint64_t queries;      /* single-source queries actually run (slots taken): distinct non-dangling seeds
+                              with dedup on, listed non-dangling seeds with it off */
+    uint64_t dangling;     /* listed seeds without out-edges (never take a slot) */
+    int32_t batches, reserved_;
+    double combine_ms;     /* device time of the combine kernels, summed over the batches */
+} fora_seeds_stats;
+
 /* ---- lifecycle ---------------------------------------------------------- */
 int fora_hip_device_count(void); /* usable HIP devices (0 when there is none) */
 int fora_hip_create(int device, fora_ctx **out);
@@ -272,6 +314,15 @@ int fora_hip_query_sparse_batch(fora_ctx *ctx, const int32_t *sources, int nq, i
 /* copies the held result; any of ids / vals / fix may be NULL; cap = entries each non-NULL array can take */
 int fora_hip_sparse_fetch(fora_ctx *ctx, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap);
 int fora_hip_sparse_clear(fora_ctx *ctx);
+
+/* ---- SSPPR on seed sets (the SEED SETS contract above; the reference personalises on one node only).  ns sets in CSR form:
+ * set_ptr ns + 1 entries, seeds / weights set_ptr[ns] entries (weights NULL: uniform).  Any output may be NULL: ppr_out /
+ * ppr_fix_out ns*n, ids / scores ns*k (k == 0: no top-k), row_sum_fix_out ns. */
+int fora_hip_query_seeds_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, const int32_t *seeds,
+                               const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx,
+                               double *ppr_out /*ns*n or NULL*/, uint64_t *ppr_fix_out /*ns*n or NULL*/,
+                               int k, int32_t *ids, double *scores /*ns*k or NULL*/,
+                               uint64_t *row_sum_fix_out /*ns or NULL*/, fora_seeds_stats *st /*or NULL*/);
 
 /* ---- top-k: replaces the topk() loop over get_topk -> fora_query_topk_new +
  * topk_ppr (query.h:1397-1401, 1139-1156, 972-1045; algo.h:592-610), --opt driver.
