@@ -1015,6 +1015,9 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
             return FORA_OK;
         }
     }
+    // the bin kernel has no instantiation for these: ensure_row_split builds split offsets for several passes only, which the narrow layout
+    // and the hub copy (make_dev) never run
+    if (p.binned && d.row_split && (d.col_hub || !d.wide)) return fail(c, FORA_E_ARG, "push: pass-split rows with a narrow layout or a hub copy");
     hipEvent_t done[SPEC + 1];
     for (auto &e : done) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int rc = FORA_OK;
@@ -1038,26 +1041,21 @@ int run_push_levels(fora_ctx *c, const Dev &d, uint64_t *levels_run = nullptr, i
                     const size_t hub_lds = dp.col_hub ? (size_t)dp.hubs * 8 : 0;
                     const bool hub = dp.col_hub != nullptr, split = dp.row_split != nullptr, sched = TEST_PATHS && (dp.rounds > 1 || dp.defer_k > 0);
                     const dim3 bgrid = (dp.wide && (dp.slot_major & 1u)) ? dim3(nq, xb) : dim3(xb, nq); // (Dev::slot_major: the slot is the fastest-varying index)
-#define FORA_BIN_LAUNCH(NBV, NT, HUBV, SPLITV, SCHEDV) hipLaunchKernelGGL((k_pushq_bin<NBV, HUBV, SPLITV, SCHEDV>), bgrid, dim3(NT), hub_lds, c->stream, dp, L)
-#if FORA_TEST_PATHS
-#define FORA_BIN_SCHED(NBV, NT) FORA_BIN_LAUNCH(NBV, NT, true, true, true)
-#else
-#define FORA_BIN_SCHED(NBV, NT) (void)0
-#endif
-#define FORA_BIN_QUAD(NBV, NT, HUBV) hipLaunchKernelGGL((k_pushq_bin<NBV, HUBV, false, false, true>), bgrid, dim3(NT), hub_lds, c->stream, dp, L)
-#define FORA_BIN_PICK(NBV, NT) do { \
-                    if (!sched && !split && dp.col4 && NBV > MAX_BINS) { if (hub) FORA_BIN_QUAD(NBV, NT, true); else FORA_BIN_QUAD(NBV, NT, false); break; } \
-                    if (sched) FORA_BIN_SCHED(NBV, NT); /* schedule experiments: the everything instantiation (test library only) */ \
-                    else if (hub && split) FORA_BIN_LAUNCH(NBV, NT, true, true, false); \
-                    else if (hub) FORA_BIN_LAUNCH(NBV, NT, true, false, false); \
-                    else if (split) FORA_BIN_LAUNCH(NBV, NT, false, true, false); \
-                    else FORA_BIN_LAUNCH(NBV, NT, false, false, false); } while (0)
-                    if (d.wide && p.pbins > MAX_BINS_WIDE) FORA_BIN_PICK(MAX_BINS_HUGE, BIN_THREADS_HUGE);
-                    else if (d.wide) FORA_BIN_PICK(MAX_BINS_WIDE, BIN_THREADS_WIDE);
-                    else FORA_BIN_PICK(MAX_BINS, BLOCK);
-#undef FORA_BIN_PICK
-#undef FORA_BIN_QUAD
-#undef FORA_BIN_SCHED
+#define FORA_BIN_LAUNCH(HUBV, SPLITV, SCHEDV, QUADV) hipLaunchKernelGGL((k_pushq_bin<NBV, HUBV, SPLITV, SCHEDV, QUADV>), bgrid, dim3(BinThreads<NBV>::value), hub_lds, c->stream, dp, L)
+                    // Only the forms a plan can reach are instantiated (checked above: pass-split rows come with a wide layout and without the hub copy;
+                    // make_dev sets col4 for wide layouts in one pass only).
+                    auto pick = [&](auto nb) {
+                        constexpr int NBV = decltype(nb)::value;
+                        if constexpr (TEST_PATHS) if (sched) { FORA_BIN_LAUNCH(true, true, true, false); return; } // schedule experiments: the everything instantiation (test library only)
+                        if constexpr (NBV > MAX_BINS) {
+                            if (split) { FORA_BIN_LAUNCH(false, true, false, false); return; }
+                            if (dp.col4) { if (hub) FORA_BIN_LAUNCH(true, false, false, true); else FORA_BIN_LAUNCH(false, false, false, true); return; }
+                        }
+                        if (hub) FORA_BIN_LAUNCH(true, false, false, false); else FORA_BIN_LAUNCH(false, false, false, false);
+                    };
+                    if (d.wide && p.pbins > MAX_BINS_WIDE) pick(std::integral_constant<int, MAX_BINS_HUGE>());
+                    else if (d.wide) pick(std::integral_constant<int, MAX_BINS_WIDE>());
+                    else pick(std::integral_constant<int, MAX_BINS>());
 #undef FORA_BIN_LAUNCH
                 }
                 ev.begin(EV_PUSH_ACCUM);

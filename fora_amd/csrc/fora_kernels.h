@@ -489,6 +489,34 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w, u
     return x + (w > 0 ? a0 : 0) + (w > 1 ? a1 : 0) + (w > 2 ? a2 : 0);
 }
 
+// Entry search.  A tile's NT entries (frontier nodes, walk items) hold cnt[i] units each (edges, quads, walks), concatenated:
+// s_pref[0 .. NT] are the exclusive prefix sums in LDS, s_pref[NT] the total.  Unit x < total belongs to the largest entry lo
+// with s_pref[lo] <= x; a binary search lands on the FIRST of a run of equal sums, so entries without units are stepped over.
+// A lane searches once for its first unit and steps for the following ones.
+constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x >> 1); }
+template <int NT>
+__device__ __forceinline__ uint32_t pref_find(const uint32_t *s_pref, uint32_t x) {
+    static_assert((NT & (NT - 1)) == 0, "a power of two entries");
+    uint32_t lo = 0, hi = NT;
+#pragma unroll
+    for (int it = 0; it < ilog2(NT); it++) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_pref[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint32_t pref_step(const uint32_t *s_pref, uint32_t lo, uint32_t x) {
+    while (s_pref[lo + 1] <= x) lo++;
+    return lo;
+}
+
+// Slab sweeps: SLAB_UNROLL guarded loads of p[base + v0 + u * step], all in flight together; 0 where v0 + u * step >= n
+template <typename T>
+__device__ __forceinline__ void slab_load(uint64_t (&x)[SLAB_UNROLL], const uint64_t *p, T base, T v0, T step, T n) {
+#pragma unroll
+    for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * step < n ? p[base + v0 + u * step] : 0;
+}
+
 // wave-aggregated append of `flag`ged 64-bit items to a list (one atomic per wave)
 __device__ __forceinline__ void wave_append(bool flag, uint64_t item, uint64_t *list,
                                             unsigned long long *count, uint64_t cap, uint32_t *err,
@@ -719,12 +747,7 @@ __global__ void __launch_bounds__(BLOCK) k_push_expand(Dev d, int L) {
             bool cross = false;
             uint64_t item = 0;
             if (e < total) {
-                uint32_t lo = 0, hi = BLOCK; // largest lo with s_pref[lo] <= e
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (s_pref[mid] <= e) lo = mid; else hi = mid;
-                }
+                const uint32_t lo = pref_find<BLOCK>(s_pref, e);
                 const uint32_t w = (uint32_t)d.col[s_ebeg[lo] + (e - s_pref[lo])];
                 const uint64_t inc = s_inc[lo];
                 const uint32_t q = s_q[lo];
@@ -739,6 +762,10 @@ __global__ void __launch_bounds__(BLOCK) k_push_expand(Dev d, int L) {
         __syncthreads();
     }
 }
+
+} // namespace fora
+#include "fora_exchange.h" // the sub-bucket exchange of the bin and walk kernels (needs Dev and the block scans above)
+namespace fora {
 
 // ------------------------------------------------------------------ bucketed push
 // Same level semantics as k_push_pop / k_push_expand, reorganised so that no per-edge global
@@ -763,7 +790,7 @@ __global__ void __launch_bounds__(BLOCK) k_push_expand(Dev d, int L) {
 // chunks of BIN_EPT * BLOCK: each lane gathers BIN_EPT consecutive edges (all loads issued before any is waited
 // for), an LDS histogram over the target bins gives every message its rank, the workgroup's LDS fill counters give the
 // chunk its place in the workgroup's own sub-buckets (Dev::bk_w: no global atomic), the messages are staged bin-sorted
-// in LDS and the stage is written out in runs.  No slice list is materialised: a narrow message names the frontier position of its source node
+// in LDS and the stage is written out in runs (these steps: BinExchange, fora_exchange.h; shared with k_walk_idx).  No slice list is materialised: a narrow message names the frontier position of its source node
 // (increment table `inc_tab`), a wide one carries the increment.  Measured and dropped: gathering with
 // consecutive lanes on consecutive edges through an LDS address table, carrying rowinfo in the frontier entry, and
 // loading the entries one or two tiles ahead -- the kernel is bound by its instruction and LDS mix, not by these waits.
@@ -772,6 +799,9 @@ __global__ void __launch_bounds__(BLOCK) k_push_expand(Dev d, int L) {
 template <int NB, bool HUB, bool SPLIT, bool SCHED, bool QUAD = false>
 __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int L) {
     static_assert(!(QUAD && SPLIT), "pass-split rows are read edge by edge");
+    // the forms no plan launches are not instantiated (run_push_levels): the narrow layout runs one pass per level and has no quad copies,
+    // the hub copy needs one pass and pass-split rows several -- only the test library's everything form (SCHED) carries both
+    static_assert(SCHED || ((NB > MAX_BINS || !(SPLIT || QUAD)) && !(HUB && SPLIT)), "a form no workspace plan can launch");
     constexpr int NT = BinThreads<NB>::value; // workgroup size = frontier entries per tile; BIN_EPT * NT edges per chunk
     const bool slot_major = NB > MAX_BINS && (d.slot_major & 1u); // (see Dev::slot_major)
     const int q = slot_major ? blockIdx.x : blockIdx.y;
@@ -805,10 +835,7 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
     __shared__ uint64_t s_inc[NT];
     __shared__ uint32_t s_pref[NT + 1];
     __shared__ uint32_t s_w[NT / 64];
-    // per bin: messages of the chunk, first stage slot of the bin (s_lofs[b + 1] - s_lofs[b] = that count again), and
-    // s_fill: messages this workgroup has put into its sub-bucket of the bin so far
-    __shared__ uint32_t s_cnt[NB], s_lofs[NB + 1];
-    __shared__ uint32_t s_fill[NB];
+    __shared__ uint32_t s_cnt[NB], s_lofs[NB + 1], s_fill[NB]; // (see BinExchange)
     BIN_RANK_PROBE_DECL(NB)
     // stage: ONE word per message and its bin.  narrow: (local target << SEG_BITS) | frontier position;
     // wide: local target (13 bits) | source entry inside the tile (SRC_BITS)
@@ -819,15 +846,10 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
     const uint64_t fbase = (uint64_t)q * d.segq_cap;
     const uint32_t *in = d.fl[par] + slab;
     uint64_t *incs = d.inc_tab[par] + fbase;
-    const uint32_t sub = d.sub; // == gx: this workgroup owns sub-bucket bx of every bin of the slot
-    uint32_t *bkc = d.bk_count + (uint64_t)q * d.pbins * sub + bx;                  // count of bin b: bkc[b * sub]
-    const uint64_t bk0 = ((uint64_t)q * d.pbins * sub + bx) * d.bk_cap;             // sub-bucket of bin b: bk0 + b * sub * bk_cap
-    const uint64_t bstride = (uint64_t)sub * d.bk_cap;
-    const uint32_t bin_lo = (uint32_t)d.bin_lo, bin_cnt = (uint32_t)d.bin_cnt;
-    for (uint32_t i = threadIdx.x; i < (uint32_t)NB; i += NT) {
-        s_cnt[i] = 0;
-        s_fill[i] = i < bin_cnt ? bkc[(uint64_t)i * sub] : 0;
-    }
+    const uint32_t bin_lo = (uint32_t)d.bin_lo;
+    // the exchange (fora_exchange.h).  d.sub == gx: this workgroup owns sub-bucket bx of every bin of the slot
+    const BinExchange<NB, NT, PAD> ex{s_cnt, s_lofs, s_fill, s_w, SubBuckets(d.bk_count, d.pbins, d.sub, d.bk_cap, q, bx), (uint32_t)d.bin_cnt};
+    ex.load_fills();
     uint64_t acc_res = 0, acc_dang = 0, acc_pops = 0, acc_relax = 0;
     STAMP_DECL
     constexpr uint32_t GRAN = WIDE ? FORA_TILE_GRAN_BIN : NT; // see tile_pos
@@ -886,20 +908,12 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
                 constexpr int QEPT = BIN_EPT / 4;
                 static_assert(!QUAD || BIN_EPT % 4 == 0, "whole quads per lane");
                 const uint32_t q0 = cb + threadIdx.x * QEPT;
-                uint32_t lo = 0;
-                if (q0 < total) {
-                    uint32_t hi = NT;
-#pragma unroll
-                    for (int it = 0; it < (NT == 256 ? 8 : NT == 512 ? 9 : 10); it++) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (s_pref[mid] <= q0) lo = mid; else hi = mid;
-                    }
-                }
+                uint32_t lo = q0 < total ? pref_find<NT>(s_pref, q0) : 0;
                 uint32_t sq[QEPT > 0 ? QEPT : 1];
 #pragma unroll
                 for (int j = 0; j < QEPT; j++) { // entries without edges: step over them
                     const uint32_t qq = q0 + j;
-                    if (qq < total) while (s_pref[lo + 1] <= qq) lo++;
+                    if (qq < total) lo = pref_step(s_pref, lo, qq);
                     sq[j] = lo;
                 }
                 uint4 x[QEPT > 0 ? QEPT : 1], xp[QEPT > 0 ? QEPT : 1];
@@ -922,19 +936,11 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
                 }
             } else {
             const uint32_t e0 = cb + threadIdx.x * BIN_EPT; // lane t takes 8 consecutive edges: ONE binary search for the source entry
-            uint32_t lo = 0;
-            if (e0 < total) {
-                uint32_t hi = NT;
-#pragma unroll
-                for (int it = 0; it < (NT == 256 ? 8 : NT == 512 ? 9 : 10); it++) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (s_pref[mid] <= e0) lo = mid; else hi = mid;
-                }
-            }
+            uint32_t lo = e0 < total ? pref_find<NT>(s_pref, e0) : 0;
 #pragma unroll
             for (int k = 0; k < BIN_EPT; k++) { // entries without edges: step over them
                 const uint32_t e = e0 + k;
-                if (e < total) while (s_pref[lo + 1] <= e) lo++;
+                if (e < total) lo = pref_step(s_pref, lo, e);
                 si[k] = lo;
             }
 #pragma unroll
@@ -954,48 +960,21 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
             }
 #pragma unroll
             for (int k = 0; k < BIN_EPT; k++) {
-                if (w[k] != 0xFFFFFFFFu && (w[k] >> BS) - bin_lo >= bin_cnt) w[k] = 0xFFFFFFFFu; // another pass's bins
-                if (w[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&s_cnt[(w[k] >> BS) - bin_lo], 1u); // rank inside (chunk, bin)
+                if (w[k] != 0xFFFFFFFFu && !ex.in_pass((w[k] >> BS) - bin_lo)) w[k] = 0xFFFFFFFFu; // another pass's bins
+                if (w[k] != 0xFFFFFFFFu) rank[k] = ex.rank((w[k] >> BS) - bin_lo);
                 if (w[k] != 0xFFFFFFFFu) BIN_RANK_PROBE((w[k] >> BS) - bin_lo);
             }
             diag::bin_sync_probe();
             __syncthreads();
             STAMP(1);
-            uint32_t staged; // messages of this chunk that belong to the pass's bins
-            { // take sub-bucket space (a counter in LDS, no atomic) and lay the bins out in the LDS stage:
-              // lane t owns bins t*PER .. t*PER+PER-1
-                constexpr int PER = (NB + NT - 1) / NT;
-                uint32_t c[PER], mine = 0;
-#pragma unroll
-                for (int j = 0; j < PER; j++) {
-                    const uint32_t b = threadIdx.x * PER + j;
-                    c[j] = b < (uint32_t)d.bin_cnt && b < (uint32_t)NB ? s_cnt[b] : 0;
-                    mine += c[j];
-                }
-                uint32_t ctot;
-                uint32_t pre2 = block_excl_scan_n<NT>(mine, s_w, ctot);
-                staged = ctot;
-#pragma unroll
-                for (int j = 0; j < PER; j++) {
-                    const uint32_t b = threadIdx.x * PER + j;
-                    if (b < (uint32_t)NB) {
-                        s_lofs[b] = pre2;
-                        pre2 += c[j];
-                        if (c[j]) {
-                            s_fill[b] += (c[j] + (PAD - 1)) & ~(uint32_t)(PAD - 1);
-                            s_cnt[b] = 0;
-                        }
-                    }
-                }
-                if (threadIdx.x == NT - 1) s_lofs[NB] = ctot;
-            }
+            const uint32_t staged = ex.layout(); // messages of this chunk that belong to the pass's bins
             __syncthreads();
             STAMP(2);
 #pragma unroll
             for (int k = 0; k < BIN_EPT; k++) {
                 if (w[k] != 0xFFFFFFFFu) {
                     const uint32_t b = (w[k] >> BS) - bin_lo;
-                    const uint32_t sp = s_lofs[b] + rank[k];
+                    const uint32_t sp = ex.slot(b, rank[k]);
                     const uint32_t own = si[k];
                     const uint32_t sw = WIDE ? (w[k] & (BSZ - 1)) | (own << BS) : ((w[k] & (BSZ - 1)) << SEG_BITS) | tile_pos<GRAN>(own, tile, seg_len);
                     s_msg[sp] = sw;
@@ -1012,9 +991,8 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
                 uint32_t sidx = 0, local;
                 if (WIDE) { sidx = e >> BS; local = e & (BSZ - 1); }
                 else local = e >> SEG_BITS; // narrow: the word names the frontier position
-                const uint32_t crun = s_lofs[b + 1] - s_lofs[b]; // messages of this (chunk, bin) run
-                const uint32_t pos = s_fill[b] - ((crun + (PAD - 1)) & ~(uint32_t)(PAD - 1)) + (m - s_lofs[b]); // s_fill already counts this chunk's (padded) run
-                const uint64_t at = bk0 + (uint64_t)b * bstride + pos;
+                const uint32_t pos = ex.pos(b, m);
+                const uint64_t at = ex.bk.at(b, pos);
                 bool parked = pos >= d.bk_cap; // sub-bucket full
                 if (!parked) {
                     if (WIDE) {
@@ -1038,16 +1016,7 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
                     } else atomicOr(d.err, ERR_BUCKET_OVERFLOW);
                 }
             }
-            if (PAD > 1) { // null words up to the sector boundary (merged with the run's last sector in L2)
-                for (uint32_t b = threadIdx.x; b < bin_cnt; b += NT) {
-                    const uint32_t crun = s_lofs[b + 1] - s_lofs[b];
-                    const uint32_t prun = (crun + (PAD - 1)) & ~(uint32_t)(PAD - 1);
-                    for (uint32_t i = crun; i < prun; i++) {
-                        const uint32_t pos = s_fill[b] - prun + i;
-                        if (pos < d.bk_cap) d.bk_inc[bk0 + (uint64_t)b * bstride + pos] = 0ull;
-                    }
-                }
-            }
+            ex.pad_runs(d.bk_inc, d.bk_cap);
             STAMP(4);
         }
         if (WIDE && threadIdx.x == 0) s_next = next_tile;
@@ -1055,10 +1024,10 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_pushq_bin(Dev d, int 
         tile = WIDE ? s_next : next_tile; // (slot-major: thread 0's next_tile is the static one)
         STAMP(5);
     }
-    for (uint32_t i = threadIdx.x; i < bin_cnt; i += NT) bkc[(uint64_t)i * sub] = s_fill[i];
+    ex.store_fills();
     if (hubmode) { // the workgroup's row of hub sums (every workgroup of the slot writes one, with or without tiles: k_accum reads them all)
         __syncthreads();
-        uint64_t *row = d.hubsum + ((uint64_t)q * sub + bx) * d.hubs;
+        uint64_t *row = d.hubsum + ((uint64_t)q * ex.bk.sub + bx) * d.hubs;
         for (uint32_t i = threadIdx.x; i < d.hubs; i += NT) row[i] = s_hub[i];
     }
     STAMP_FLUSH(0);
@@ -1248,15 +1217,7 @@ __global__ void __launch_bounds__(TAIL_THREADS, FORA_TAIL_WPE) k_push_tail(Dev d
             __syncthreads();
             for (uint32_t cb = 0; cb < total; cb += TAIL_THREADS * TAIL_EPT) {
                 const uint32_t e0 = cb + tid * TAIL_EPT;
-                uint32_t lo = 0;
-                if (e0 < total) {
-                    uint32_t hi = TAIL_THREADS;
-#pragma unroll
-                    for (int it = 0; it < (TAIL_THREADS == 1024 ? 10 : TAIL_THREADS == 512 ? 9 : 8); it++) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (s_pref[mid] <= e0) lo = mid; else hi = mid;
-                    }
-                }
+                uint32_t lo = e0 < total ? pref_find<TAIL_THREADS>(s_pref, e0) : 0;
                 uint32_t w[TAIL_EPT], dg[TAIL_EPT];
                 uint64_t inc[TAIL_EPT], old[TAIL_EPT];
 #pragma unroll
@@ -1264,7 +1225,7 @@ __global__ void __launch_bounds__(TAIL_THREADS, FORA_TAIL_WPE) k_push_tail(Dev d
                     const uint32_t e = e0 + k;
                     w[k] = 0xFFFFFFFFu; inc[k] = 0;
                     if (e < total) {
-                        while (s_pref[lo + 1] <= e) lo++; // nodes without edges
+                        lo = pref_step(s_pref, lo, e); // nodes without edges
                         inc[k] = s_inc[lo];
                         w[k] = (uint32_t)colsrc[s_ebeg[lo] + (e - s_pref[lo])];
                     }
@@ -1409,13 +1370,14 @@ __device__ __forceinline__ void accum_bin(DevRef d, int L, const int lb, const i
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint64_t slab = (uint64_t)q * d.n;
     const uint32_t sub = d.sub;
-    const uint64_t bi = (uint64_t)q * d.pbins + lb;
+    const Bucket bkt(d, q, lb);
+    const uint64_t bk0 = bkt.first(d.bk_cap); // sub-bucket x starts at bk0 + x * bk_cap
     // the bucket's sub-buckets: counts (clamped: the excess is in the overflow list (push) / went by direct atomics (walks))
     if (threadIdx.x < 64) {
         uint32_t t = 0;
         for (uint32_t x = threadIdx.x; x < sub; x += 64) {
-            uint32_t c = d.bk_count[bi * sub + x];
-            if (c) d.bk_count[bi * sub + x] = 0;
+            uint32_t c = d.bk_count[bkt.count(x)];
+            if (c) d.bk_count[bkt.count(x)] = 0;
             if (c > d.bk_cap) c = d.bk_cap;
             s_scnt[x] = c;
             t += c;
@@ -1458,7 +1420,6 @@ __device__ __forceinline__ void accum_bin(DevRef d, int L, const int lb, const i
     uint32_t *fl_next = d.fl[par ^ 1] + slab;
     uint64_t *inc_next = TO_PPR ? nullptr : d.inc_tab[par ^ 1] + (uint64_t)q * d.segq_cap;
     uint32_t *flc_next = &d.fl_count[par ^ 1][q * CSTRIDE];
-    const uint64_t bk0 = bi * sub * d.bk_cap; // sub-bucket x starts at bk0 + x * bk_cap
     const uint32_t node0 = (uint32_t)b << BS;
     const uint64_t *itab = TO_PPR ? nullptr : d.inc_tab[par] + (uint64_t)q * d.segq_cap;
     const uint64_t t1q = TO_PPR ? 0 : thr_unit(d.t1, d.qs[q].tshift); // the slot's threshold unit in its current round
@@ -1758,7 +1719,7 @@ __global__ void __launch_bounds__(WIDE ? ACC_THREADS_WIDE : ACC_THREADS) k_accum
         if (threadIdx.x < (uint32_t)ACC_GROUP_MAX) s_gbusy[threadIdx.x] = 0;
         __syncthreads();
         const uint32_t sub = d.sub;
-        const uint32_t *cnts = d.bk_count + ((uint64_t)q * d.pbins + lb0) * sub;
+        const uint32_t *cnts = d.bk_count + Bucket(d, q, lb0).count(0); // the counts of G consecutive buckets
         for (uint32_t i = threadIdx.x; i < nb * sub; i += AT)
             if (cnts[i]) s_gbusy[i / sub] = 1u; // (benign race: every writer stores 1)
         if (threadIdx.x < nb) { // the other reasons a bin may have work (see accum_bin): overflow entries, hub sums, the dangling mass, deferred nodes
@@ -2069,8 +2030,7 @@ __global__ void __launch_bounds__(BLOCK) k_copy_slab(int32_t n, const uint64_t *
     const uint64_t step = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t v0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; v0 < (uint64_t)n; v0 += step * SLAB_UNROLL) {
         uint64_t x[SLAB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * step < (uint64_t)n ? src[slab + v0 + u * step] : 0;
+        slab_load(x, src, slab, v0, step, (uint64_t)n);
 #pragma unroll
         for (int u = 0; u < SLAB_UNROLL; u++) if (v0 + u * step < (uint64_t)n) dst[slab + v0 + u * step] = x[u];
     }
@@ -2086,8 +2046,7 @@ __global__ void __launch_bounds__(BLOCK) k_count_above(Dev d, const uint8_t *act
     const uint64_t step = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t v0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; v0 < (uint64_t)d.n; v0 += step * SLAB_UNROLL) {
         uint64_t x[SLAB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = (v0 + u * step < (uint64_t)d.n) ? d.ppr[slab + v0 + u * step] : 0;
+        slab_load(x, d.ppr, slab, v0, step, (uint64_t)d.n);
 #pragma unroll
         for (int u = 0; u < SLAB_UNROLL; u++) acc += x[u] && fix2d(x[u]) >= T; // T > 0
     }
@@ -2114,8 +2073,7 @@ __global__ void __launch_bounds__(BLOCK) k_nz_count(Dev d, uint32_t R, uint32_t 
     uint32_t c = 0;
     for (uint32_t v0 = lo + threadIdx.x; v0 < hi; v0 += BLOCK * SLAB_UNROLL) {
         uint64_t x[SLAB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * BLOCK < hi ? p[v0 + u * BLOCK] : 0;
+        slab_load(x, p, 0u, v0, (uint32_t)BLOCK, hi);
 #pragma unroll
         for (int u = 0; u < SLAB_UNROLL; u++) c += x[u] != 0 && (!thr || fix2d(x[u]) >= t);
     }
@@ -2462,8 +2420,8 @@ template <int ST>
 __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) {
     const int lane = threadIdx.x & 63;
     const uint64_t slab = (uint64_t)q * d.n;
-    const uint64_t bk0 = ((uint64_t)q * d.pbins * d.sub + blockIdx.x) * d.bk_cap; // sub-bucket blockIdx.x of bin b: + b * sub * bk_cap
-    const uint64_t bstride = (uint64_t)d.sub * d.bk_cap;
+    // workgroup x fills sub-bucket x of every bin (SubBuckets; only the two words the flush needs: the walk kernels are short of SGPRs)
+    const uint64_t bk0 = SubBuckets::first_of(d.pbins, d.sub, d.bk_cap, q, blockIdx.x), bstride = SubBuckets::stride_of(d.sub, d.bk_cap);
     st.bcnt[lane] = 0;
     st.bcnt[lane + 64] = 0;
     __builtin_amdgcn_wave_barrier();
@@ -2506,12 +2464,8 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
             const uint32_t b = dd >> BIN_SHIFT;
             const uint32_t pos = st.bbase[b] + (m - st.bcnt[b]);
             // non-temporal: the results are read once, by k_accum; kept out of the way of the packed targets the walk steps
-            // gather through L2 (walk kernel 93.8 -> 92.2 ms per 1000 ws queries; -DFORA_STAGE_PLAIN_STORE: plain stores)
-#ifndef FORA_STAGE_PLAIN_STORE
+            // gather through L2 (walk kernel 93.8 -> 92.2 ms per 1000 ws queries against plain stores)
             if (pos < d.bk_cap) __builtin_nontemporal_store(pk, &d.bk_inc[bk0 + (uint64_t)b * bstride + pos]);
-#else
-            if (pos < d.bk_cap) d.bk_inc[bk0 + (uint64_t)b * bstride + pos] = pk;
-#endif
             else atomicAdd((unsigned long long *)&d.ppr[slab + (st.xl ? st.xl[dd] : dd)], (unsigned long long)(pk >> WPACK_SHIFT)); // bucket full
         }
     }
@@ -2545,8 +2499,8 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
 
 // ---- indexed part of the refinement (query.h:290-296, 301-306): walks jj < idx_n of an item
 // are read from rw_idx.  Streaming gather; grid = (X, nq).  With the bucketed layouts the results
-// go through the same block-level chunk binning as the push (LDS histogram, one global atomic per
-// (chunk, bin), bin-sorted LDS stage, run write-out) and are reduced by k_accum<true>.
+// go through the same block-level chunk binning as the push (BinExchange, fora_exchange.h: LDS histogram,
+// space in the workgroup's own sub-buckets, bin-sorted LDS stage, run write-out) and are reduced by k_accum<true>.
 template <int NB>
 __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
     constexpr int NT = BinThreads<NB>::value; // workgroup size = walk items per tile
@@ -2562,8 +2516,7 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
     static_assert(DB + IB + 1 <= 32, "stage word: destination | item | carries-one-more-unit");
     __shared__ uint64_t s_j0[NT], s_pos[NT], s_incr[NT], s_rem[NT];
     __shared__ uint32_t s_pref[NT + 1], s_w[NT / 64];
-    __shared__ uint32_t s_cnt[NB], s_lofs[NB + 1];
-    __shared__ uint32_t s_fill[NB]; // results this workgroup has put into its sub-bucket of every bin (see Dev::bk_w)
+    __shared__ uint32_t s_cnt[NB], s_lofs[NB + 1], s_fill[NB]; // (see BinExchange)
     // stage: ONE word per result (destination | item << DB | extra unit << (DB + IB)) and its bin; the weight comes from the item
     __shared__ uint32_t s_msg[BINNED ? CHUNK : 1];
     __shared__ uint16_t s_bin[BINNED ? CHUNK : 1];
@@ -2574,14 +2527,10 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
     if (!nitems || *d.err) return;
     const WalkItemP *items = d.wit + (uint64_t)q * d.wit_cap;
     const uint64_t slab = (uint64_t)q * d.n;
-    const uint32_t sub = d.sub; // BINNED: == gx, this workgroup owns sub-bucket bx of every bin of the slot
-    uint32_t *bkc = d.bk_count + (uint64_t)q * d.pbins * sub + bx;      // count of bin b: bkc[b * sub]
-    const uint64_t bk0 = ((uint64_t)q * d.pbins * sub + bx) * d.bk_cap; // sub-bucket of bin b: bk0 + b * sub * bk_cap
-    const uint32_t bin_lo = (uint32_t)d.bin_lo, bin_cnt = (uint32_t)d.bin_cnt;
-    if (BINNED) for (uint32_t i = threadIdx.x; i < (uint32_t)NB; i += NT) {
-        s_cnt[i] = 0;
-        s_fill[i] = i < bin_cnt ? bkc[(uint64_t)i * sub] : 0;
-    }
+    const uint32_t bin_lo = (uint32_t)d.bin_lo;
+    // the exchange (fora_exchange.h).  BINNED: d.sub == gx, this workgroup owns sub-bucket bx of every bin of the slot
+    const BinExchange<NB, NT, PAD> ex{s_cnt, s_lofs, s_fill, s_w, SubBuckets(d.bk_count, d.pbins, d.sub, d.bk_cap, q, bx), (uint32_t)d.bin_cnt};
+    if (BINNED) ex.load_fills();
     constexpr uint32_t GRAN = FORA_TILE_GRAN_WALK; // see tile_pos
     const uint32_t ntiles = (nitems + NT - 1) / NT;
     const uint32_t seg_len = ntiles * GRAN;
@@ -2602,19 +2551,11 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
         for (uint32_t cb = 0; cb < total; cb += CHUNK) {
             uint32_t dest[EPT], rank[EPT], li[EPT];
             const uint32_t e0 = cb + threadIdx.x * EPT;
-            uint32_t lo = 0;
-            if (e0 < total) {
-                uint32_t hi = NT;
-#pragma unroll
-                for (int it = 0; it < IB; it++) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (s_pref[mid] <= e0) lo = mid; else hi = mid;
-                }
-            }
+            uint32_t lo = e0 < total ? pref_find<NT>(s_pref, e0) : 0;
 #pragma unroll
             for (int k = 0; k < EPT; k++) { // items can be empty here (idx_n == 0): advance past them
                 const uint32_t e = e0 + k;
-                if (e < total) while (s_pref[lo + 1] <= e) lo++;
+                if (e < total) lo = pref_step(s_pref, lo, e);
                 li[k] = lo;
             }
 #pragma unroll
@@ -2637,43 +2578,17 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
             }
 #pragma unroll
             for (int k = 0; k < EPT; k++) {
-                if (dest[k] != 0xFFFFFFFFu && (dest[k] >> BS) - bin_lo >= bin_cnt) dest[k] = 0xFFFFFFFFu; // another pass
-                if (dest[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&s_cnt[(dest[k] >> BS) - bin_lo], 1u);
+                if (dest[k] != 0xFFFFFFFFu && !ex.in_pass((dest[k] >> BS) - bin_lo)) dest[k] = 0xFFFFFFFFu; // another pass
+                if (dest[k] != 0xFFFFFFFFu) rank[k] = ex.rank((dest[k] >> BS) - bin_lo);
             }
             __syncthreads();
-            uint32_t staged; // results of this chunk that belong to the pass's bins
-            {
-                constexpr int PER = (NB + NT - 1) / NT;
-                uint32_t c[PER], mine = 0;
-#pragma unroll
-                for (int j = 0; j < PER; j++) {
-                    const uint32_t b = threadIdx.x * PER + j;
-                    c[j] = b < (uint32_t)d.bin_cnt && b < (uint32_t)NB ? s_cnt[b] : 0;
-                    mine += c[j];
-                }
-                uint32_t ctot;
-                uint32_t pre2 = block_excl_scan_n<NT>(mine, s_w, ctot);
-                staged = ctot;
-#pragma unroll
-                for (int j = 0; j < PER; j++) {
-                    const uint32_t b = threadIdx.x * PER + j;
-                    if (b < (uint32_t)NB) {
-                        s_lofs[b] = pre2;
-                        pre2 += c[j];
-                        if (c[j]) { // space in the workgroup's own sub-bucket: a counter in LDS, no global atomic
-                            s_fill[b] += (c[j] + (PAD - 1)) & ~(uint32_t)(PAD - 1);
-                            s_cnt[b] = 0;
-                        }
-                    }
-                }
-                if (threadIdx.x == NT - 1) s_lofs[NB] = ctot;
-            }
+            const uint32_t staged = ex.layout(); // results of this chunk that belong to the pass's bins
             __syncthreads();
 #pragma unroll
             for (int k = 0; k < EPT; k++) {
                 if (dest[k] != 0xFFFFFFFFu) {
                     const uint32_t b = (dest[k] >> BS) - bin_lo;
-                    const uint32_t sp = s_lofs[b] + rank[k];
+                    const uint32_t sp = ex.slot(b, rank[k]);
                     s_msg[sp] = (WIDE ? dest[k] & (BSZ - 1) : dest[k]) | (li[k] << DB);
                     s_bin[sp] = (uint16_t)b;
                 }
@@ -2683,27 +2598,17 @@ __global__ void __launch_bounds__(BinThreads<NB>::value) k_walk_idx(Dev d) {
                 const uint32_t e = s_msg[m], b = s_bin[m];
                 const uint32_t dd = e & ((1u << DB) - 1);
                 const uint64_t wgt = s_incr[(e >> DB) & (uint32_t)(NT - 1)] + (e >> (DB + IB));
-                const uint32_t crun = s_lofs[b + 1] - s_lofs[b];
-                const uint32_t pos = s_fill[b] - ((crun + (PAD - 1)) & ~(uint32_t)(PAD - 1)) + (m - s_lofs[b]); // s_fill already counts this chunk's (padded) run
+                const uint32_t pos = ex.pos(b, m);
                 const bool fits = wgt < (WIDE ? WIDE_MAXV : WPACK_MAXW);
-                if (pos < d.bk_cap) d.bk_inc[bk0 + (uint64_t)b * sub * d.bk_cap + pos] = fits ? (uint64_t)dd | (wgt << DB) : 0ull;
+                if (pos < d.bk_cap) d.bk_inc[ex.bk.at(b, pos)] = fits ? (uint64_t)dd | (wgt << DB) : 0ull;
                 if (pos >= d.bk_cap || !fits) // sub-bucket full / weight too large for the packed word: direct atomic, same sum
                     atomicAdd((unsigned long long *)&d.ppr[slab + (WIDE ? ((bin_lo + b) << BS) | dd : dd)], (unsigned long long)wgt);
             }
-            if (PAD > 1) { // null words up to the sector boundary (see k_pushq_bin)
-                for (uint32_t b = threadIdx.x; b < bin_cnt; b += NT) {
-                    const uint32_t crun = s_lofs[b + 1] - s_lofs[b];
-                    const uint32_t prun = (crun + (PAD - 1)) & ~(uint32_t)(PAD - 1);
-                    for (uint32_t i = crun; i < prun; i++) {
-                        const uint32_t pos = s_fill[b] - prun + i;
-                        if (pos < d.bk_cap) d.bk_inc[bk0 + (uint64_t)b * sub * d.bk_cap + pos] = 0ull;
-                    }
-                }
-            }
+            ex.pad_runs(d.bk_inc, d.bk_cap);
         }
         __syncthreads();
     }
-    if (BINNED) for (uint32_t i = threadIdx.x; i < bin_cnt; i += NT) bkc[(uint64_t)i * sub] = s_fill[i];
+    if (BINNED) ex.store_fills();
 }
 
 // ---- online walks (query.h:297-300, 320-323; build.h:344-354).  grid = (X, nq).
@@ -2966,16 +2871,12 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
                 const uint32_t i = tile * WT + lane;
                 uint32_t cnt = 0;
                 if (lane < WT && i < nitems) {
-#ifndef FORA_DG_PLAIN_ITEMS
                     WalkItem w; // read once: keep the items out of the way of the packed targets in L2
                     {
                         const uint64_t *wp = (const uint64_t *)&items[i];
                         const uint64_t x0 = NT_LOAD(wp), x1 = NT_LOAD(wp + 1), x3 = NT_LOAD(wp + 3); // (online walks: no index position)
                         w = wit_unpack(x0, x1, 0, x3);
                     }
-#else
-                    const WalkItem w = wit_load(&items[i]);
-#endif
                     s_j0[lane] = w.j0; s_incr[lane] = w.incr; s_rem[lane] = w.rem;
                     s_v[lane] = w.v;
                     s_vp[lane] = g.perm[w.v];
@@ -3086,8 +2987,7 @@ __global__ void __launch_bounds__(BLOCK) k_ppr_sum(Dev d) {
     const uint64_t step = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t v0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; v0 < (uint64_t)d.n; v0 += step * SLAB_UNROLL) {
         uint64_t x[SLAB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * step < (uint64_t)d.n ? d.ppr[slab + v0 + u * step] : 0;
+        slab_load(x, d.ppr, slab, v0, step, (uint64_t)d.n);
 #pragma unroll
         for (int u = 0; u < SLAB_UNROLL; u++) acc += x[u];
     }
@@ -3426,8 +3326,7 @@ __global__ void __launch_bounds__(BLOCK) k_seed_row_sum(const uint64_t *acc, uin
     const uint64_t step = (uint64_t)gridDim.y * BLOCK;
     for (uint64_t v0 = (uint64_t)blockIdx.y * BLOCK + threadIdx.x; v0 < (uint64_t)n; v0 += step * SLAB_UNROLL) {
         uint64_t x[SLAB_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SLAB_UNROLL; u++) x[u] = v0 + u * step < (uint64_t)n ? row[v0 + u * step] : 0;
+        slab_load(x, row, (uint64_t)0, v0, step, (uint64_t)n);
 #pragma unroll
         for (int u = 0; u < SLAB_UNROLL; u++) s += x[u];
     }

@@ -78,9 +78,10 @@ def test_shipped_library_is_not_a_diagnostic_build():
     assert _build_flag(capi.lib_path(), "test_paths") == 0
     test_lib = os.path.join(ROOT, "fora_amd", "libfora_hip_test.so")
     assert _build_flag(test_lib, "diag_build") == 0 and _build_flag(test_lib, "test_paths") == 1
-    for f in ("fora_kernels.h", "fora_team.h", "fora_hip.hip"):
+    for f in ("fora_kernels.h", "fora_exchange.h", "fora_team.h", "fora_hip.hip"):
         text = open(os.path.join(ROOT, "fora_amd", "csrc", f)).read()
-        for pat in ("FORA_PROBE_", "FORA_DG_FAKE", "ifdef FORA_STAMPS", "defined(FORA_STAMPS"):
+        for pat in ("FORA_PROBE_", "FORA_DG_FAKE", "ifdef FORA_STAMPS", "defined(FORA_STAMPS", "FORA_STAGE_PLAIN_STORE",
+                    "FORA_DG_PLAIN_ITEMS"):
             assert pat not in text, (f, pat)
     # ... and a context-bound option still needs a context
     lib = ctypes.CDLL(capi.lib_path())
