@@ -456,6 +456,10 @@ __device__ __forceinline__ uint32_t wave_incl_scan_max(uint32_t x) {
     x = max(x, dpp0<0x143, 0xC>(x));
     return x;
 }
+// lanes below this one whose bit is set in mask (v_mbcnt_lo / _hi)
+__device__ __forceinline__ uint32_t sp_mbcnt(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total) {
     const uint32_t x = wave_incl_scan_add(v);
     total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
@@ -2416,7 +2420,9 @@ struct WaveStage {
     uint32_t count;  // wave-uniform
     const uint32_t *xl; // not null: destinations are in WalkDG bucket order, original id = xl[dest] (only the direct-atomic fallbacks need it)
 };
-template <int ST>
+// XLD (k_walk_dg<.., XL = true>): an entry's low word holds the endpoint's copy id less H, and its place in WalkDG bucket
+// order is worked out here, where every lane holds an entry, instead of by the whole wave in every iteration of the walk loop.
+template <int ST, bool XLD = false>
 __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) {
     const int lane = threadIdx.x & 63;
     const uint64_t slab = (uint64_t)q * d.n;
@@ -2434,6 +2440,12 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
         wv[k] = NONE;
         if (m < st.count) {
             wv[k] = st.pk[m];
+            if (XLD) {
+                const uint32_t lo = (uint32_t)wv[k], u = lo & ((1u << WPACK_SHIFT) - 1), blk = u >> 6;
+                const uint32_t qd = __umulhi(blk, d.dg.nbx_magic); // blk / nbx
+                const uint32_t dest = ((blk - qd * d.dg.nbx) << BIN_SHIFT) | (qd << 6) | (u & 63u);
+                wv[k] = (wv[k] & 0xFFFFFFFF00000000ull) | ((lo & ~((1u << WPACK_SHIFT) - 1)) | dest);
+            }
             rk[k] = atomicAdd(&st.bcnt[((uint32_t)wv[k] & ((1u << WPACK_SHIFT) - 1)) >> BIN_SHIFT], 1u);
         }
     }
@@ -2472,20 +2484,21 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     __builtin_amdgcn_wave_barrier();
     st.count = 0;
 }
-template <int ST>
+// CHECKW false: the caller has dealt with the weights that do not fit the packed word
+template <int ST, bool XLD = false, bool CHECKW = true>
 __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, bool has, uint32_t dest, uint64_t w) {
-    if (has && w >= WPACK_MAXW) { // does not fit the packed word (tiny walk budgets only)
+    if (CHECKW && has && w >= WPACK_MAXW) { // does not fit the packed word (tiny walk budgets only)
         atomicAdd((unsigned long long *)&d.ppr[(uint64_t)q * d.n + (st.xl ? st.xl[dest] : dest)], (unsigned long long)w);
         has = false;
     }
     const unsigned long long mask = __ballot(has);
     if (!mask) return;
     if (has) {
-        const uint32_t pos = st.count + __popcll(mask & ((1ull << (threadIdx.x & 63)) - 1));
+        const uint32_t pos = st.count + sp_mbcnt(mask);
         st.pk[pos] = (uint64_t)dest | (w << WPACK_SHIFT);
     }
     st.count += (uint32_t)__popcll(mask);
-    if (st.count > ST - 64) stage_flush<ST>(d, q, st);
+    if (st.count > ST - 64) stage_flush<ST, XLD>(d, q, st);
 }
 #define WAVE_STAGE_DECL_N(st, NWAVES, ST)                                                           \
     __shared__ uint64_t st##_pk[NWAVES][ST];                                                        \
@@ -2785,15 +2798,19 @@ __device__ __forceinline__ uint32_t dg_colp_at(const WalkDG &g, uint32_t e) {
 template <bool NZH, bool BITS32, bool XL>
 __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu(FORA_DG_WPE, 8))) k_walk_dg(Dev d, uint32_t round) {
     constexpr int NW = DG_THREADS / 64;
-    extern __shared__ __attribute__((aligned(16))) uint64_t dg_lds64[]; // (16-byte aligned: the records below are read as uint4) // XL: hub accumulators [H] (u64) | first[nrec] | deg[nrec] | base[nrec] | T[nblk] (bytes)
+    extern __shared__ __attribute__((aligned(16))) uint64_t dg_lds64[]; // (16-byte aligned: the records below are read as uint4) // XL: hub accumulators [H] (u64) | records [nrec] (16 bytes each: classes, then hubs) | T[nblk] (bytes)
     // Walk items are staged per WAVE, WT at a time: a walk that has started lives in its lane's registers, so the wave
     // loads its next WT items as soon as the walks of the current ones are handed out -- lanes never wait for the longest
     // walk of a tile to end, and the loop has no workgroup barrier.  (First form: 256 items per workgroup between two
     // barriers, an eighth of their walks per wave: a tile's last walks ran on a few lanes for ~9 iterations per ~35.)
     constexpr int WT = DG_TILE / NW;
     static_assert(WT >= 1 && WT <= 64, "a lane loads one item of its wave's tile");
-    __shared__ uint64_t w_j0[NW][WT], w_incr[NW][WT], w_rem[NW][WT];
-    __shared__ uint32_t w_v[NW][WT], w_vp[NW][WT], w_idxn[NW][WT], w_pref[NW][WT + 1], s_w[NW];
+    // An item of the wave's tile as the hand-out reads it: two 16-byte words from ONE address.  jb = j0 + idx_n - (walks of the
+    // tile before this item), so that walk e of the tile is walk jb + e of its node (online walks follow the indexed ones).
+    struct __attribute__((aligned(16))) TileItem { uint64_t jb, rem, incr; uint32_t v, vp; };
+    static_assert(sizeof(TileItem) == 32, "two uint4");
+    __shared__ TileItem w_item[NW][WT];
+    __shared__ uint32_t w_pref[NW][WT + 1], s_w[NW];
     // A fifth of all walks stop where they started (algo.h:131-133 at the first step): with XL their weights are summed per
     // item in LDS (w_self) and leave as ONE result per item when the wave replaces its tile -- a walk that outlives its tile
     // (its tag names the tile it came from) is emitted on its own as before.
@@ -2802,20 +2819,22 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint32_t nitems = (uint32_t)min((uint64_t)d.wit_count[q * CSTRIDE], d.wit_cap); // (see k_walk_idx)
     if (!nitems || *d.err) return;
     const WalkDG &g = d.dg;
-    const uint32_t H = g.H, ts = g.ts, nblk1 = g.nblk ? g.nblk - 1 : 0;
+    const uint32_t H = g.H, ts = g.ts;
     unsigned long long *s_hub = (unsigned long long *)dg_lds64;
     uint32_t *dg_lds = (uint32_t *)(dg_lds64 + (XL ? ((H + 1) & ~1u) : 0)); // (whole 16-byte words of hub accumulators)
     // a record in LDS: (first copy id, out-degree, first edge, -) as ONE 16-byte word -- a move reads it with one ds_read_b128
     // (rounds 3-4: three arrays, three reads and their addresses per step)
+    // In LDS the class records come first and the hub records behind them, so that the class byte of a block IS the record's index.
     uint4 *s_rec = (uint4 *)dg_lds;                       // [nrec]; 16-byte aligned: dg_lds64 is, H * 8 keeps it
+    const uint32_t ncls = g.nrec - H;
     const uint8_t *s_T = (const uint8_t *)(dg_lds + 4 * g.nrec);
-    for (uint32_t i = threadIdx.x; i < g.nrec; i += DG_THREADS) s_rec[i] = make_uint4(g.rec[i], g.rec[g.nrec + i], g.rec[2 * g.nrec + i], 0u);
+    for (uint32_t i = threadIdx.x; i < g.nrec; i += DG_THREADS) s_rec[i < H ? ncls + i : i - H] = make_uint4(g.rec[i], g.rec[g.nrec + i], g.rec[2 * g.nrec + i], 0u);
     for (uint32_t i = threadIdx.x; i < (g.nblk + 3) / 4; i += DG_THREADS) dg_lds[4 * g.nrec + i] = ((const uint32_t *)g.T)[i];
     if (XL) for (uint32_t i = threadIdx.x; i < H; i += DG_THREADS) s_hub[i] = 0;
     const WalkItemP *items = d.wit + (uint64_t)q * d.wit_cap;
     const uint64_t slab = (uint64_t)q * d.n;
     const uint32_t stream = (uint32_t)d.src[q];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (wave-uniform, and known to be: what hangs on it stays in scalar registers)
     uint32_t steps = 0;
     WAVE_STAGE_DECL_N(st, NW, DG_STAGE)
     if (XL) st.xl = g.invb;
@@ -2824,12 +2843,13 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     __syncthreads();
     // one move (algo.h:134-140) from copy id `cur` with random word wm
     auto move = [&](uint32_t cur, uint32_t startp, uint32_t wm) -> uint32_t {
-        const uint32_t tb = s_T[min((cur - H) >> ts, nblk1)]; // (a hub: cur - H wraps, the index is clamped, the byte unused -- no branch around the read)
-        const uint32_t r = cur < H ? cur : H + tb;
+        uint32_t r = ncls + cur;
+        if (cur >= H) r = s_T[(cur - H) >> ts]; // (a copy id in use behind the hubs: its block is in the table)
         const uint4 rc = s_rec[r];
         const uint32_t dg = rc.y;
         const uint32_t e = rc.z + (cur - rc.x) * dg + __umulhi(wm, dg);
-        const uint32_t nx = dg_colp_at<BITS32>(g, dg ? e : 0u);
+        // out-degree 0: e is the record's first edge, at most the number of edges -- a read inside colp's padding words, unused
+        const uint32_t nx = dg_colp_at<BITS32>(g, e);
         return dg ? nx : startp;
     };
     // !XL: result waiting for its original id (loaded at the end of the previous iteration)
@@ -2837,130 +2857,146 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     uint32_t pend_node = 0;
     uint64_t pend_w = 0;
     unsigned long long *s_self = w_self[XL ? wid : 0];
+    TileItem *s_item = w_item[wid];
+    uint32_t *s_pref = w_pref[wid];
     if (XL && lane < WT) s_self[lane] = 0;
     uint32_t gen = 0, tag = 0; // tiles this wave has loaded; (tile << 6 | item) of this lane's walk
     // the tile's self sums -> results like any other endpoint (hub accumulators / the wave's stage), then zero
     auto flush_self = [&]() {
         if (!XL) return;
         const unsigned long long sv = lane < WT ? s_self[lane] : 0ull;
-        const uint32_t dn = lane < WT ? w_vp[wid][lane] : 0u;
+        const uint32_t dn = lane < WT ? s_item[lane].vp : 0u;
         if (lane < WT && sv) s_self[lane] = 0;
         if (sv && dn < H) atomicAdd(&s_hub[dn], sv); // LDS
-        const uint32_t u = dn - H, blk = u >> 6;
-        const uint32_t qd = __umulhi(blk, g.nbx_magic);
-        const uint32_t dest = ((blk - qd * g.nbx) << BIN_SHIFT) | (qd << 6) | (u & 63u);
-        stage_emit<DG_STAGE>(d, q, st, sv != 0 && dn >= H, dest, (uint64_t)sv);
+        bool has = sv != 0 && dn >= H;
+        if (has && sv >= WPACK_MAXW) { // does not fit the packed word (tiny walk budgets only)
+            atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[dn]], sv);
+            has = false;
+        }
+        stage_emit<DG_STAGE, true, false>(d, q, st, has, dn - H, (uint64_t)sv);
     };
-    uint64_t *s_j0 = w_j0[wid], *s_incr = w_incr[wid], *s_rem = w_rem[wid];
-    uint32_t *s_v = w_v[wid], *s_vp = w_vp[wid], *s_idxn = w_idxn[wid], *s_pref = w_pref[wid];
     const uint32_t ntiles = (nitems + WT - 1) / WT;
     uint32_t tile = blockIdx.x * NW + wid;      // the wave's next tile of WT items
     const uint32_t tstride = gridDim.x * NW;
-    uint32_t wptr = 0, wend = 0;                // walks of the current tile: wptr .. wend - 1 are not handed out yet (wave-uniform)
-    uint32_t cur_item = 0;                      // item holding walk wptr (wave-uniform)
+    // wave-uniform, kept in scalar registers (readfirstlane where a value comes out of LDS or a lane): the loop's tests on
+    // them and the advance of cur_item are scalar instructions
+    uint32_t wptr = 0, wend = 0;                // walks of the current tile: wptr .. wend - 1 are not handed out yet
+    uint32_t cur_item = 0;                      // item holding walk wptr
+    bool big = false;                           // some item of a tile loaded so far has weights that may not fit the packed word (sticky: walks outlive their tile)
+    auto advance = [&]() { // items without (remaining) online walks
+        while (wptr < wend && (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pref[cur_item + 1]) <= wptr) cur_item++;
+    };
     bool active = false;
-    uint32_t cur = 0, start = 0, startp = 0, t = 0;
-    uint64_t wj = 0, wgt = 0;
+    // A walk's Philox counter words live in registers: c0 = start (original id), c1 = low word of the walk's number, c2 = its
+    // high 16 bits | round << 16 | (calls so far & 0xFF) << 24, c3 = stream ^ (calls >> 8) * 0x9E3779B9 -- the same words as
+    // k_walk_online builds from t (t = 2 * calls while the walk runs).  A call adds 1 << 24 to c2; when that wraps, every 512
+    // steps, c3 moves on by one multiple of the constant (a rare branch).
+    uint32_t cur = 0, start = 0, startp = 0, c1 = 0, c2 = 0, c3 = 0;
+    const uint32_t c2_round = (round & 0xFFu) << 16;
+    uint64_t wgt = 0;
     for (;;) {
-        int32_t done = -1; // endpoint (copy id) reached this iteration
+        bool fin = false; // the lane's walk ended in this iteration, at cur
         const unsigned long long idle = __ballot(!active);
         if (idle && wptr == wend) { // lanes are free and the tile is handed out: the next tile that has walks
             while (wptr == wend && tile < ntiles) {
                 if (gen) flush_self();
                 gen++;
                 const uint32_t i = tile * WT + lane;
-                uint32_t cnt = 0;
-                if (lane < WT && i < nitems) {
-                    WalkItem w; // read once: keep the items out of the way of the packed targets in L2
-                    {
-                        const uint64_t *wp = (const uint64_t *)&items[i];
-                        const uint64_t x0 = NT_LOAD(wp), x1 = NT_LOAD(wp + 1), x3 = NT_LOAD(wp + 3); // (online walks: no index position)
-                        w = wit_unpack(x0, x1, 0, x3);
-                    }
-                    s_j0[lane] = w.j0; s_incr[lane] = w.incr; s_rem[lane] = w.rem;
-                    s_v[lane] = w.v;
-                    s_vp[lane] = g.perm[w.v];
-                    s_idxn[lane] = w.idx_n;
-                    cnt = w.cnt - w.idx_n;
+                const bool have = lane < WT && i < nitems;
+                WalkItem w = {};
+                if (have) { // read once: keep the items out of the way of the packed targets in L2
+                    const uint64_t *wp = (const uint64_t *)&items[i];
+                    const uint64_t x0 = NT_LOAD(wp), x1 = NT_LOAD(wp + 1), x3 = NT_LOAD(wp + 3); // (online walks: no index position)
+                    w = wit_unpack(x0, x1, 0, x3);
                 }
+                const uint32_t cnt = have ? w.cnt - w.idx_n : 0u;
                 uint32_t total;
                 const uint32_t pre = wave_excl_scan(cnt, total);
+                if (have) {
+                    TileItem it;
+                    it.jb = w.j0 + w.idx_n - pre; // online walks follow the indexed ones
+                    it.rem = w.rem; it.incr = w.incr;
+                    it.v = w.v; it.vp = g.perm[w.v];
+                    s_item[lane] = it;
+                }
+                if (__ballot(have && w.incr + 1 >= WPACK_MAXW)) big = true;
                 if (lane < WT) s_pref[lane] = pre;
                 if (lane == 0) s_pref[WT] = total;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the wave's own LDS writes, read by its lanes below)
                 __builtin_amdgcn_wave_barrier();
                 wptr = 0; wend = total; cur_item = 0;
                 tile += tstride;
-                while (wptr < wend && (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pref[cur_item + 1]) <= wptr) cur_item++; // items without online walks
+                advance();
             }
         }
         const uint32_t avail = wend - wptr;
         if (!avail && idle == ~0ull) break; // (no tile left either)
         if (avail && idle) {
-            const uint32_t rank = __popcll(idle & ((1ull << lane) - 1));
+            const uint32_t rank = sp_mbcnt(idle);
             if (!active && rank < avail) {
                 const uint32_t e = wptr + rank;
                 uint32_t item = cur_item;
                 while (s_pref[item + 1] <= e) item++;
-                const uint32_t jj = s_idxn[item] + (e - s_pref[item]); // online walks follow the indexed ones
-                wj = s_j0[item] + jj;
-                start = s_v[item];
-                startp = s_vp[item];
-                wgt = s_incr[item] + (wj < s_rem[item] ? 1 : 0); // (!XL: the lane's previous result already waits in pend_w)
+                const uint4 ia = ((const uint4 *)&s_item[item])[0], ib = ((const uint4 *)&s_item[item])[1]; // (jb, rem) | (incr, v, vp)
+                const uint64_t wj = (((uint64_t)ia.y << 32) | ia.x) + e;
+                const uint64_t rem = ((uint64_t)ia.w << 32) | ia.z;
+                wgt = (((uint64_t)ib.y << 32) | ib.x) + (wj < rem ? 1 : 0); // (!XL: the lane's previous result already waits in pend_w)
+                start = ib.z;
+                startp = ib.w;
+                c1 = (uint32_t)wj;
+                c2 = ((uint32_t)(wj >> 32) & 0xFFFFu) | c2_round;
+                c3 = stream;
                 cur = startp;
-                t = 0;
                 tag = (gen << 6) | item;
-                if (startp >= g.zero_first) done = (int32_t)startp; // algo.h:127-129
-                else active = true;
+                fin = startp >= g.zero_first; // algo.h:127-129
+                active = !fin;
             }
             const uint32_t want = (uint32_t)__popcll(idle);
             wptr += want < avail ? want : avail;
-            while (wptr < wend && (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pref[cur_item + 1]) <= wptr) cur_item++;
+            advance();
             __builtin_amdgcn_wave_barrier(); // (every lane has read its item before the tile can be replaced)
         }
         if (active) {
             uint32_t rw[4];
-            philox4x32_10(start, (uint32_t)wj,
-                          (uint32_t)((wj >> 32) & 0xFFFFu) | ((round & 0xFFu) << 16) | (((t >> 1) & 0xFFu) << 24),
-                          stream ^ ((t >> 9) * 0x9E3779B9u), d.seed_lo, d.seed_hi, rw);
-            if (!(NZH && t == 0) && rw[0] < d.alpha32) { // algo.h:131-133
-                done = (int32_t)cur;
-                active = false;
+            philox4x32_10(start, c1, c2, c3, d.seed_lo, d.seed_hi, rw);
+            const uint32_t later = (c2 >> 24) | (c3 ^ stream); // 0: the walk's first call (t == 0)
+            c2 += 1u << 24; // (for the next call: a walk that ends here has no use for it)
+            if (__ballot(c2 < (1u << 24))) { // 256 calls = 512 steps on: the next multiple in c3
+                asm volatile("" ::: "memory"); // (keeps the branch: as a select this would be five instructions in every iteration)
+                if (c2 < (1u << 24)) c3 = stream ^ ((c3 ^ stream) + 0x9E3779B9u);
+            }
+            if (!(NZH && later == 0) && rw[0] < d.alpha32) { // algo.h:131-133
+                fin = true;
             } else {
-                cur = move(diag::dg_from(cur, t), startp, rw[1]); // (diag::dg_from: the identity in the product build)
+                cur = move(diag::dg_from(cur, later), startp, rw[1]); // (diag::dg_from: the identity in the product build)
                 steps++;
                 if (rw[2] < d.alpha32) {
-                    t++;
-                    done = (int32_t)cur;
-                    active = false;
+                    fin = true;
                 } else {
                     cur = move(diag::dg_from(cur, 1u), startp, rw[3]);
-                    t += 2;
                     steps++;
                 }
             }
+            active = !fin;
         }
         if (XL) { // query.h:299,322
-            bool ended = done >= 0;
-            const uint32_t dn = (uint32_t)done;
-            if (ended && dn == startp && (tag >> 6) == gen) { // back where it started, and the item is still in the tile
-                atomicAdd(&s_self[tag & 63u], (unsigned long long)wgt); // LDS
-                ended = false;
-            }
-            if (ended && dn < H) atomicAdd(&s_hub[dn], (unsigned long long)wgt); // LDS
-            const uint32_t u = dn - H, blk = u >> 6;
-            const uint32_t qd = __umulhi(blk, g.nbx_magic);                      // blk / nbx
-            const uint32_t dest = ((blk - qd * g.nbx) << BIN_SHIFT) | (qd << 6) | (u & 63u);
-            stage_emit<DG_STAGE>(d, q, st, ended && dn >= H, dest, wgt);
+            // (plain predicates, no flag changed under a branch: the staged lanes' mask stays a scalar pair)
+            const bool self = fin && cur == startp && tag >= (gen << 6); // back where it started, and the item is still in the tile (a tag's tile is never ahead of gen)
+            if (self) atomicAdd(&s_self[tag & 63u], (unsigned long long)wgt); // LDS
+            const bool away = fin && !self;
+            if (away && cur < H) atomicAdd(&s_hub[cur], (unsigned long long)wgt); // LDS
+            const bool over = big && wgt >= WPACK_MAXW; // does not fit the packed word (tiny walk budgets only)
+            if (away && cur >= H && over) atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[cur]], (unsigned long long)wgt);
+            stage_emit<DG_STAGE, true, false>(d, q, st, away && cur >= H && !over, cur - H, wgt); // (the place in bucket order: stage_flush)
         } else {
             stage_emit<DG_STAGE>(d, q, st, pend, pend_node, pend_w);
-            pend = done >= 0;
-            if (pend) { pend_node = g.inv[done]; pend_w = wgt; }
+            pend = fin;
+            if (pend) { pend_node = g.inv[cur]; pend_w = wgt; }
         }
     }
     if (!XL) stage_emit<DG_STAGE>(d, q, st, pend, pend_node, pend_w);
     if (gen) flush_self();
-    if (st.count) stage_flush<DG_STAGE>(d, q, st);
+    if (st.count) stage_flush<DG_STAGE, XL>(d, q, st);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < (uint32_t)d.nbins; i += DG_THREADS) bkc[(uint64_t)i * d.sub] = st.fill[i];
     if (XL) for (uint32_t i = threadIdx.x; i < H; i += DG_THREADS) { // the hubs' share of this workgroup's walks
@@ -3156,10 +3192,6 @@ __device__ __forceinline__ void sp_load(const uint64_t *slab, int64_t p, int64_t
         if (p >= lo && p < hi) a = slab[p];
         if (p + 1 >= lo && p + 1 < hi) b = slab[p + 1];
     }
-}
-// lanes below this one whose bit is set in mask (v_mbcnt_lo / _hi)
-__device__ __forceinline__ uint32_t sp_mbcnt(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 // grid = (X, nb)
 __global__ void __launch_bounds__(BLOCK) k_sparse_count(const uint64_t *ppr, uint32_t n, uint64_t thr, uint32_t R, uint32_t *counts,
