@@ -1,0 +1,43 @@
+// fora_consts.h -- the plain numbers that both the kernels (fora_kernels.h, fora_team.h) and the host-side table builders
+// (fora_tables.h) read.  No HIP: a plain C++ compiler takes this file.
+#pragma once
+#include <stdint.h>
+
+namespace fora {
+
+constexpr uint32_t DEG_SAT = 0xFFFFFFu; // rowinfo low 24 bits: out-degree, saturating
+// bucketed push (graphs of up to MAX_BINS * BIN_SIZE nodes): increments are binned by target
+// range and reduced in LDS instead of one global atomic per edge
+#ifndef FORA_BIN_SHIFT
+#define FORA_BIN_SHIFT 13
+#endif
+constexpr int BIN_SHIFT = FORA_BIN_SHIFT;      // narrow layout
+constexpr uint32_t BIN_SIZE = 1u << BIN_SHIFT; // 8192 nodes -> 64 KiB of u64 accumulators in LDS
+// Wide layouts: 16384-node bins (128 KiB of accumulators, one 1024-thread accumulate workgroup per CU): half the bins, so
+// twice the messages per (chunk, bin) run, and a Twitter-2010-sized graph (2543 bins) needs ONE bin pass per level instead
+// of two.  Same run: LJ-sized 280 indexed queries 904 -> 833 ms, Twitter-2010-sized 15.96 -> 18.48 q/s.
+#ifndef FORA_BIN_SHIFT_WIDE
+#define FORA_BIN_SHIFT_WIDE 14
+#endif
+constexpr int BIN_SHIFT_WIDE = FORA_BIN_SHIFT_WIDE;
+constexpr uint32_t BIN_SIZE_WIDE = 1u << BIN_SHIFT_WIDE;
+constexpr int MAX_BINS = 128;       // narrow layout: 4-B push messages, staged walk results
+constexpr int MAX_BINS_WIDE = 1024; // wide layout: 8-byte messages (local target | value << 14), up to 1024 bins per pass ...
+constexpr int MAX_BINS_HUGE = 2560; // ... or 2560 for graphs with more bins (Twitter-2010: 2543 bins, one pass)
+constexpr int SEG_BITS = 32 - BIN_SHIFT; // narrow push message = (target & (BIN_SIZE-1)) << SEG_BITS | frontier position
+
+// team push (fora_team.h)
+constexpr int TEAM_MAX = 32;                  // members of a team (5 bits of a target word)
+constexpr int TEAM_LBITS = 15;                // bits of a local id
+#ifndef FORA_TEAM_THREADS
+#define FORA_TEAM_THREADS 1024
+#endif
+#ifndef FORA_TEAM_WGS_PER_CU
+#define FORA_TEAM_WGS_PER_CU (FORA_TEAM_THREADS == 1024 ? 1 : 2)
+#endif
+constexpr int TEAM_WGS_PER_CU = FORA_TEAM_WGS_PER_CU;
+constexpr uint32_t TEAM_R_CAP = TEAM_WGS_PER_CU == 1 ? 15296 : 7680; // local ids per member at most: 8 * (R + 1) + the static LDS of k_push_team <= 160 KiB / workgroups per CU
+constexpr uint32_t TEAM_LMASK = (1u << TEAM_LBITS) - 1u;
+constexpr uint32_t TEAM_EMPTY = 0xFFFFFFFFu;
+
+} // namespace fora

@@ -6,6 +6,7 @@
 #include "fora_kernels.h"
 #include "fora_team.h"
 #include "fora_bwd.h"
+#include "fora_tables.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -20,9 +21,6 @@
 
 using namespace fora;
 
-struct fora_ctx;
-static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *col); // (defined below, beside set_graph)
-static int build_quad_copies(fora_ctx *c);
 namespace {
 
 // What an event pair times, named after the fora_timing field it feeds.  The switch of ev_collect is the one place that says which
@@ -133,6 +131,13 @@ public:
         return e;
     }
     hipError_t ensure(size_t cnt) { return p && count >= cnt ? hipSuccess : alloc(cnt); }
+    hipError_t upload(const T *src, size_t cnt, size_t min_count = 0) { // alloc(cnt, or min_count if that is more) + a blocking copy of cnt elements from the host; holds nothing after a failure
+        hipError_t e = alloc(std::max(cnt, min_count));
+        if (e == hipSuccess && cnt) e = hipMemcpy(p, src, cnt * sizeof(T), hipMemcpyHostToDevice);
+        if (e != hipSuccess) reset();
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &v, size_t min_count = 0) { return upload(v.data(), v.size(), min_count); }
     hipError_t fill(hipStream_t s, int byte, size_t from, size_t cnt) const { // elements [from, from + cnt)
         return from + cnt > count ? hipErrorInvalidValue : hipMemsetAsync(p + from, byte, cnt * sizeof(T), s);
     }
@@ -458,6 +463,16 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
     return p;
 }
 
+// col as uploaded, back on the host (one element at least).  The graph keeps no host copy: 5.9 GB at Twitter-2010 size
+int download_col(fora_ctx *c, std::vector<int32_t> &col) {
+    col.resize((size_t)std::max<int64_t>(1, c->g.nnz));
+    HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), (size_t)c->g.nnz * 4, hipMemcpyDeviceToHost));
+    return FORA_OK;
+}
+
+// The derived forms of the graph.  Each function below decides whether this graph, with these options on this device, gets
+// the form; fora_tables.h computes it; the vectors are uploaded into a local value that is moved in after the last step.
+
 // Multi-pass graphs (more bins than one pass holds): row-sorted copy of col + per-row split offsets, so that every
 // pass of k_pushq_bin reads only its own part of each popped row.  Built once per (graph, pass size).
 int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
@@ -465,32 +480,12 @@ int ensure_row_split(fora_ctx *c, int nbins, int pbins) {
     if (npass <= 1 || c->opt_.no_split) { c->g.split = RowSplit{}; return FORA_OK; }
     if (c->g.split.d_row_split && c->g.split.pbins == pbins) return FORA_OK;
     c->g.split = RowSplit{};
+    std::vector<int32_t> col;
+    if (int rd = download_col(c, col)) return rd;
+    const SplitTables t = make_row_split(c->g.n, c->g.h_row_ptr.data(), std::move(col), npass, pbins, bin_shift(c));
     RowSplit rs;
-    const size_t n = (size_t)c->g.n, nnz = (size_t)c->g.nnz;
-    std::vector<int32_t> col(std::max<size_t>(1, nnz));
-    if (nnz) HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), nnz * 4, hipMemcpyDeviceToHost));
-    bool sorted = true;
-    for (size_t v = 0; v < n && sorted; v++)
-        for (int64_t e = c->g.h_row_ptr[v] + 1; e < c->g.h_row_ptr[v + 1]; e++)
-            if (col[(size_t)e - 1] > col[(size_t)e]) { sorted = false; break; }
-    if (!sorted) {
-        for (size_t v = 0; v < n; v++) std::sort(col.begin() + c->g.h_row_ptr[v], col.begin() + c->g.h_row_ptr[v + 1]);
-        HIPCHK(c, rs.d_col_push.alloc(std::max<size_t>(1, nnz)));
-        HIPCHK(c, hipMemcpy(rs.d_col_push.get(), col.data(), nnz * 4, hipMemcpyHostToDevice));
-    }
-    std::vector<uint32_t> split(n * (size_t)(npass + 1));
-    for (size_t v = 0; v < n; v++) {
-        const int32_t *rb = col.data() + c->g.h_row_ptr[v], *re = col.data() + c->g.h_row_ptr[v + 1];
-        uint32_t *sp = split.data() + v * (size_t)(npass + 1);
-        sp[0] = 0;
-        for (int p = 1; p < npass; p++) {
-            const int64_t first_node = ((int64_t)p * pbins) << bin_shift(c);
-            sp[p] = (uint32_t)(std::lower_bound(rb, re, (int32_t)std::min<int64_t>(first_node, INT32_MAX)) - rb);
-        }
-        sp[npass] = (uint32_t)(re - rb);
-    }
-    HIPCHK(c, rs.d_row_split.alloc(split.size()));
-    HIPCHK(c, hipMemcpy(rs.d_row_split.get(), split.data(), split.size() * 4, hipMemcpyHostToDevice));
+    if (!t.col_sorted.empty()) HIPCHK(c, rs.d_col_push.upload(t.col_sorted));
+    HIPCHK(c, rs.d_row_split.upload(t.split));
     rs.pbins = pbins;
     c->g.split = std::move(rs);
     return FORA_OK;
@@ -513,95 +508,116 @@ int ensure_team(fora_ctx *c) {
     tb.checked = true; tb.wanted = want; tb.force = force; tb.hubs_opt = hubs_opt;
     const auto done = [&] { c->g.team = std::move(tb); return FORA_OK; }; // (with T == 0: looked at, not taken -- a complete state too)
     if (!want) return done();
-    const size_t n = (size_t)c->g.n, nnz = (size_t)c->g.nnz;
-    std::vector<int32_t> col(nnz);
-    HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), nnz * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> indeg(n, 0);
-    for (size_t e = 0; e < nnz; e++) indeg[(size_t)col[e]]++;
-    // members per team: the fewest (a power of two) whose LDS holds their share of the nodes that have in-edges
-    uint32_t T = 1;
-    while (T < force) T *= 2;
-    std::vector<uint32_t> cntm;
-    uint32_t R = 0;
-    for (;; T *= 2) {
-        if (T > (uint32_t)TEAM_MAX || T > (uint32_t)std::max(1, c->prop.multiProcessorCount * TEAM_WGS_PER_CU)) return done(); // too large for the team path
-        cntm.assign(T, 0);
-        for (size_t v = 0; v < n; v++) if (indeg[v]) cntm[(v >> 6) % T]++;
-        R = (*std::max_element(cntm.begin(), cntm.end()) + 63) / 64 * 64;
-        if (R == 0) R = 64;
-        if (R <= TEAM_R_CAP) break;
-    }
-    std::vector<uint32_t> n2l(n, TEAM_EMPTY), l2n((size_t)T * R, TEAM_EMPTY);
-    std::vector<uint16_t> deg16((size_t)T * R, 0);
-    std::vector<uint64_t> rowl((size_t)T * R, 0);
-    std::fill(cntm.begin(), cntm.end(), 0);
-    for (size_t v = 0; v < n; v++) {
-        if (!indeg[v]) continue;
-        const uint32_t s = (uint32_t)((v >> 6) % T), l = cntm[s]++;
-        n2l[v] = (s << TEAM_LBITS) | l;
-        l2n[(size_t)s * R + l] = (uint32_t)v;
-        const int64_t dg = c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v];
-        deg16[(size_t)s * R + l] = (uint16_t)std::min<int64_t>(dg, 0xFFFF);
-        rowl[(size_t)s * R + l] = (uint64_t)v | ((uint64_t)std::min<int64_t>(dg, 8191) << 19); // n <= 2^19; the row's first quad (<< 32) follows below
-    }
-    // rows of the team copy are padded to whole quads (four words, 16-byte aligned): a lane reads a quad with one load
-    std::vector<uint32_t> rowq(n + 1, 0);
-    for (size_t v = 0; v < n; v++) rowq[v + 1] = rowq[v] + (uint32_t)((c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v] + 3) / 4); // (< 2^32: nnz < 2^32, want_team)
-    for (size_t v = 0; v < n; v++)
-        if (n2l[v] != TEAM_EMPTY) rowl[(size_t)(n2l[v] >> TEAM_LBITS) * R + (n2l[v] & TEAM_LMASK)] |= (uint64_t)rowq[v] << 32;
-    // hubs: the nodes of largest in-degree (ties: lower id); their sums travel as one message per member and level
-    // (their LDS sums share the 160 KiB with the residues and ~23 KB of static arrays)
-    const uint64_t lds_left = 163840 / TEAM_WGS_PER_CU - 23 * 1024 - ((uint64_t)R + 1) * 8;
-    const uint32_t Hn = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(hubs_opt, n), lds_left / 8);
-    std::vector<uint32_t> hub_of(n, TEAM_EMPTY), hubtgt(std::max<uint32_t>(1, Hn), 0);
-    std::vector<uint8_t> hub_ok(std::max<uint32_t>(1, Hn), 0);
-    if (Hn) {
-        std::vector<uint32_t> order(n);
-        for (size_t v = 0; v < n; v++) order[v] = (uint32_t)v;
-        std::partial_sort(order.begin(), order.begin() + Hn, order.end(),
-                          [&](uint32_t x, uint32_t y) { return indeg[x] != indeg[y] ? indeg[x] > indeg[y] : x < y; });
-        for (uint32_t h = 0; h < Hn; h++) if (indeg[order[h]]) { hub_of[order[h]] = h; hubtgt[h] = n2l[order[h]]; hub_ok[h] = 1; }
-    }
-    std::vector<uint32_t> colt((size_t)rowq[n] * 4, TEAM_EMPTY);
-    std::vector<uint64_t> pair((size_t)T * T, 0);
-    for (size_t v = 0; v < n; v++) {
-        const uint32_t s = (uint32_t)((v >> 6) % T);
-        for (int64_t e = c->g.h_row_ptr[v]; e < c->g.h_row_ptr[v + 1]; e++) {
-            const uint32_t t = (uint32_t)col[(size_t)e], w = n2l[t];
-            colt[(size_t)rowq[v] * 4 + (size_t)(e - c->g.h_row_ptr[v])] = hub_of[t] != TEAM_EMPTY ? (0x80000000u | hub_of[t]) : w;
-            if (hub_of[t] == TEAM_EMPTY) pair[(size_t)s * T + (w >> TEAM_LBITS)]++;
-        }
-    }
-    for (uint32_t h = 0; h < Hn; h++) // a member sends a hub at most one message per level
-        if (hub_ok[h]) for (uint32_t s = 0; s < T; s++) pair[(size_t)s * T + (hubtgt[h] >> TEAM_LBITS)]++;
-    // bucket (s -> d): one 4-byte message per edge + the dangling mass of the level; whole 64-byte lines
-    std::vector<uint32_t> off((size_t)T * T + 1, 0);
-    uint64_t at = 0;
-    for (size_t i = 0; i < (size_t)T * T; i++) {
-        off[i] = (uint32_t)at;
-        at += (pair[i] + 1 + 15) & ~15ull;
-        if (at >= (1ull << 32) || pair[i] + 1 >= (1ull << 24)) return done(); // 32-bit slots; a bucket's count is 24 bits of its barrier word: no team push for such a graph
-    }
-    off[(size_t)T * T] = (uint32_t)at;
-    HIPCHK(c, tb.d_colt.alloc(colt.size() + 4));
-    HIPCHK(c, tb.d_rowq.alloc(n));
-    HIPCHK(c, hipMemcpy(tb.d_rowq.get(), rowq.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, tb.d_off.alloc(off.size()));
-    HIPCHK(c, tb.d_n2l.alloc(n));
-    HIPCHK(c, tb.d_l2n.alloc(l2n.size()));
-    HIPCHK(c, tb.d_deg16.alloc(deg16.size()));
-    HIPCHK(c, tb.d_hubtgt.alloc(hubtgt.size()));
-    HIPCHK(c, hipMemcpy(tb.d_hubtgt.get(), hubtgt.data(), hubtgt.size() * 4, hipMemcpyHostToDevice));
-    tb.H = Hn;
-    HIPCHK(c, tb.d_rowl.alloc(rowl.size()));
-    HIPCHK(c, hipMemcpy(tb.d_rowl.get(), rowl.data(), rowl.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.d_colt.get(), colt.data(), colt.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.d_off.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.d_n2l.get(), n2l.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.d_l2n.get(), l2n.data(), l2n.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tb.d_deg16.get(), deg16.data(), deg16.size() * 2, hipMemcpyHostToDevice));
-    tb.T = T; tb.R = R; tb.cap = at;
+    std::vector<int32_t> col;
+    if (int rd = download_col(c, col)) return rd;
+    const uint32_t max_members = (uint32_t)std::min(TEAM_MAX, std::max(1, c->prop.multiProcessorCount * TEAM_WGS_PER_CU));
+    const TeamLayout t = make_team_layout(c->g.n, c->g.h_row_ptr.data(), col.data(), force, max_members, hubs_opt);
+    if (!t.T) return done();
+    HIPCHK(c, tb.d_colt.upload(t.colt, t.colt.size() + 4)); // (a lane without a quad of its own loads quad 0: there is one)
+    HIPCHK(c, tb.d_rowq.upload(t.rowq.data(), (size_t)c->g.n));
+    HIPCHK(c, tb.d_off.upload(t.off));
+    HIPCHK(c, tb.d_n2l.upload(t.n2l));
+    HIPCHK(c, tb.d_l2n.upload(t.l2n));
+    HIPCHK(c, tb.d_deg16.upload(t.deg16));
+    HIPCHK(c, tb.d_hubtgt.upload(t.hubtgt));
+    HIPCHK(c, tb.d_rowl.upload(t.rowl));
+    tb.H = t.H; tb.T = t.T; tb.R = t.R; tb.cap = t.cap;
     return done();
+}
+
+// Hub pre-aggregation of the narrow push (Dev::col_hub): the `hubs` nodes of largest in-degree (ties: lower id), numbered in
+// id order so that the hubs of a bin are a contiguous range, and a copy of col that names them by that number.
+int build_hub_copy(fora_ctx *c, const int32_t *col) {
+    c->g.hub = HubCopy{}; // (a rebuild: ensure_workspace)
+    const int64_t nnz = c->g.nnz;
+    const int64_t wide_auto = nnz <= (1ll << 28) ? 2048 : 0;
+    // the hub sums live in the bin kernel's dynamic LDS next to its static arrays: 48 KB in the narrow and the 512-thread
+    // wide kernel, 32 KB in the 1024-thread one (its stage of 12 edges per thread takes 122 of the 160 KB)
+    const uint64_t nbins_all = bins_of(c);
+    const int64_t lds_cap = !want_wide(c) ? 6144 : nbins_all > (uint64_t)MAX_BINS_WIDE ? 4096 : 6144;
+    // 4096 only when this graph really takes the team path (ensure_team has built its tables: then the bin kernel never runs
+    // and k_push_tail is the copy's only reader); a graph the team path rejects pushes with the bin kernel, which wants 1024
+    const bool for_team = want_team(c) && c->g.team.T != 0;
+    c->g.hub.for_team = for_team; // (no copy, for this path: a complete state too -- also after a failure below: ensure_workspace does not try again, the graph pushes without hub sums until the next set_graph, as before)
+    const int64_t narrow_auto = for_team ? 4096 : 1024;
+    const int64_t want = std::min<int64_t>(std::max<int64_t>(want_wide(c) ? (c->opt_.hubs_wide < 0 ? wide_auto : c->opt_.hubs_wide) : (c->opt_.hubs < 0 ? narrow_auto : c->opt_.hubs), 0), lds_cap);
+    if (want == 0 || nnz == 0 || c->opt_.direct == 1) return FORA_OK;
+    if (want_wide(c) && (int64_t)nbins_all > (int64_t)want_pass_bins(c, (int)nbins_all)) return FORA_OK; // several bin passes per level: the passes read the row-sorted copy, hubs are never used (make_dev)
+    const HubTables t = make_hub_tables(c->g.n, col, (size_t)nnz, (size_t)want, bin_shift(c));
+    HubCopy hc;
+    HIPCHK(c, hc.d_col_hub.upload(t.col_hub));
+    HIPCHK(c, hc.d_hub_node.upload(t.hub_node));
+    HIPCHK(c, hc.d_hub_first.upload(t.hub_first));
+    hc.hubs = (uint32_t)t.hub_node.size();
+    hc.shift = bin_shift(c);
+    hc.for_team = for_team;
+    c->g.hub = std::move(hc);
+    return FORA_OK;
+}
+
+// Quad-padded copies of col (and of the hub copy) for the wide bin kernel (Dev::col4), built on the device from what
+// set_graph has uploaded; only for graphs that run the wide layout in one bin pass per level.
+int build_quad_copies(fora_ctx *c) {
+    c->g.quad = QuadCopies{};
+    if (!want_binned(c) || !want_wide(c) || c->g.nnz == 0 || c->opt_.quads == 0) return FORA_OK;
+    const uint64_t nbins_all = bins_of(c);
+    if ((int64_t)nbins_all > (int64_t)want_pass_bins(c, (int)nbins_all)) return FORA_OK; // several passes per level: pass-split rows, edge by edge
+    const size_t n = (size_t)c->g.n;
+    // (Round 6, measured and dropped: rows placed so that each touches as few 64-byte lines as its length allows -- a row that would
+    // straddle one line more than ceil(quads / 4) started at the next line.  LJ-sized bin kernel 315.4 / 314.8 ms against 320.7 / 314.5
+    // back to back, Twitter-2010-sized 593.6 / 592.9 against 594.5 / 585.6: what a quad load costs is not the lines its row touches.)
+    const QuadRows t = make_quad_rows(c->g.n, c->g.h_row_ptr.data());
+    if (t.quads >= (1ull << 40)) return FORA_OK;
+    // The copies are an optimisation (make_dev falls back to single-edge reads without them): they must never make
+    // set_graph fail.  Not built when they would take more than a quarter of the free memory (the slots need it more);
+    // an allocation that fails all the same leaves "no quads", not an error.
+    const uint64_t qbytes = std::max<uint64_t>(1, t.quads) * 16, need = n * 8 + qbytes * (c->g.hub.d_col_hub ? 2 : 1);
+    size_t fr = 0, tot = 0;
+    HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    if (need > fr / 4) return FORA_OK;
+    QuadCopies qc;
+    auto give_up = [&]() { (void)hipGetLastError(); return FORA_OK; };
+    if (qc.d_rowinfo4.upload(t.rowinfo4) != hipSuccess) return give_up();
+    if (qc.d_col4.alloc(qbytes / 4) != hipSuccess) return give_up();
+    const unsigned grid = (unsigned)std::min<size_t>((n + BLOCK - 1) / BLOCK, 1u << 20);
+    hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.d_col.get(),
+                       (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col4.get());
+    if (c->g.hub.d_col_hub) {
+        if (qc.d_col_hub4.alloc(qbytes / 4) != hipSuccess) return give_up();
+        hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.hub.d_col_hub.get(),
+                           (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col_hub4.get());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    qc.quads = t.quads;
+    c->g.quad = std::move(qc);
+    return FORA_OK;
+}
+
+// Degree-grouped walk copy (WalkDG, fora_kernels.h) of graphs that run the narrow layout: H hub records + at most 255
+// out-degree classes whose tables fit a workgroup's LDS share.  Graphs that do not qualify keep k_walk_online.
+int build_walk_dg(fora_ctx *c, const int64_t *row_ptr, const int32_t *col) {
+    c->g.walk = WalkCopy{};
+    const int32_t n = c->g.n;
+    const int64_t nnz = c->g.nnz;
+    if (c->opt_.walk_dg == 0 || c->opt_.no_compact == 1 || nnz >= (1ll << 31) || nnz == 0) return FORA_OK;
+    if (!((uint64_t)n <= (uint64_t)MAX_BINS * BIN_SIZE && (uint64_t)n <= (1ull << SEG_BITS))) return FORA_OK; // narrow layout only
+    const DgTables t = make_walk_dg(n, row_ptr, col, c->opt_.dg_hubs);
+    if (!t.have) return FORA_OK;
+    WalkCopy wc;
+    HIPCHK(c, wc.d_perm.upload(t.perm));
+    HIPCHK(c, wc.d_inv.upload(t.inv));
+    HIPCHK(c, wc.d_colp.upload(t.colp));
+    HIPCHK(c, wc.d_rec.upload(t.rec, 1));
+    HIPCHK(c, wc.d_T.upload(t.T));
+    if (t.nbx) HIPCHK(c, wc.d_invb.upload(t.invb));
+    WalkDG g{};
+    g.invb = wc.d_invb.get(); g.nbx = t.nbx; g.nbx_magic = t.nbx_magic;
+    g.perm = wc.d_perm.get(); g.inv = wc.d_inv.get(); g.colp = wc.d_colp.get(); g.rec = wc.d_rec.get(); g.T = wc.d_T.get();
+    g.H = t.H; g.nrec = t.nrec; g.nblk = (uint32_t)t.T.size(); g.ts = t.ts; g.bits = t.bits; g.zero_first = t.zero_first;
+    g.bits32 = t.bits32;
+    wc.dg = g;
+    c->g.walk = std::move(wc);
+    return FORA_OK;
 }
 
 // Team push: bytes per team of its workspace buffers with reserve logs of `logcap` entries -- message buffers + increment
@@ -622,10 +638,10 @@ int ensure_workspace(fora_ctx *c, int want_slots, double omega_hint) {
     if (int rt = ensure_team(c)) return rt;
     if (c->opt_.hubs < 0 && !want_wide(c) && c->g.hub.for_team != (want_team(c) && c->g.team.T != 0)) {
         // the `team` / `team_size` options changed which push this graph takes: the hub copy follows (see build_hub_copy)
-        std::vector<int32_t> col((size_t)std::max<int64_t>(1, c->g.nnz));
-        HIPCHK(c, hipMemcpy(col.data(), c->g.d_col.get(), (size_t)c->g.nnz * 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> col;
+        if (int rd = download_col(c, col)) return rd;
         free_workspace(c);
-        if (int rh = build_hub_copy(c, c->g.h_row_ptr.data(), col.data())) return rh;
+        if (int rh = build_hub_copy(c, col.data())) return rh;
         if (int rq = build_quad_copies(c)) return rq;
     }
     {
@@ -2036,215 +2052,6 @@ int fora_hip_device_info(fora_ctx *c, char *arch, int arch_len, int *cus, uint64
 }
 
 
-// Hub pre-aggregation of the narrow push (Dev::col_hub): the `hubs` nodes of largest in-degree (ties: lower id), numbered in
-// id order so that the hubs of a bin are a contiguous range, and a copy of col that names them by that number.
-static int build_hub_copy(fora_ctx *c, const int64_t *row_ptr, const int32_t *col) {
-    (void)row_ptr;
-    c->g.hub = HubCopy{}; // (a rebuild: ensure_workspace)
-    const int32_t n = c->g.n;
-    const int64_t nnz = c->g.nnz;
-    const int64_t wide_auto = nnz <= (1ll << 28) ? 2048 : 0;
-    // the hub sums live in the bin kernel's dynamic LDS next to its static arrays: 48 KB in the narrow and the 512-thread
-    // wide kernel, 32 KB in the 1024-thread one (its stage of 12 edges per thread takes 122 of the 160 KB)
-    const uint64_t nbins_all = bins_of(c);
-    const int64_t lds_cap = !want_wide(c) ? 6144 : nbins_all > (uint64_t)MAX_BINS_WIDE ? 4096 : 6144;
-    // 4096 only when this graph really takes the team path (ensure_team has built its tables: then the bin kernel never runs
-    // and k_push_tail is the copy's only reader); a graph the team path rejects pushes with the bin kernel, which wants 1024
-    const bool for_team = want_team(c) && c->g.team.T != 0;
-    c->g.hub.for_team = for_team; // (no copy, for this path: a complete state too -- also after a failure below: ensure_workspace does not try again, the graph pushes without hub sums until the next set_graph, as before)
-    const int64_t narrow_auto = for_team ? 4096 : 1024;
-    const int64_t want = std::min<int64_t>(std::max<int64_t>(want_wide(c) ? (c->opt_.hubs_wide < 0 ? wide_auto : c->opt_.hubs_wide) : (c->opt_.hubs < 0 ? narrow_auto : c->opt_.hubs), 0), lds_cap);
-    if (want == 0 || nnz == 0 || c->opt_.direct == 1) return FORA_OK;
-    if (want_wide(c) && (int64_t)nbins_all > (int64_t)want_pass_bins(c, (int)nbins_all)) return FORA_OK; // several bin passes per level: the passes read the row-sorted copy, hubs are never used (make_dev)
-    std::vector<uint32_t> indeg((size_t)n, 0);
-    for (int64_t e = 0; e < nnz; e++) indeg[(size_t)col[e]]++;
-    std::vector<uint32_t> order((size_t)n);
-    for (int32_t v = 0; v < n; v++) order[(size_t)v] = (uint32_t)v;
-    const size_t H = (size_t)std::min<int64_t>(want, n);
-    std::partial_sort(order.begin(), order.begin() + (long)H, order.end(),
-                      [&](uint32_t a, uint32_t b) { return indeg[a] != indeg[b] ? indeg[a] > indeg[b] : a < b; });
-    std::vector<uint32_t> hub_node(order.begin(), order.begin() + (long)H);
-    std::sort(hub_node.begin(), hub_node.end());
-    std::vector<uint32_t> hub_of((size_t)n, 0xFFFFFFFFu);
-    for (size_t h = 0; h < H; h++) hub_of[hub_node[h]] = (uint32_t)h;
-    const int nbins = (int)bins_of(c);
-    std::vector<uint32_t> first((size_t)nbins + 1, 0);
-    for (size_t h = 0; h < H; h++) first[(hub_node[h] >> bin_shift(c)) + 1]++;
-    for (int b = 0; b < nbins; b++) first[(size_t)b + 1] += first[(size_t)b];
-    std::vector<int32_t> ch((size_t)nnz);
-    for (int64_t e = 0; e < nnz; e++) {
-        const uint32_t h = hub_of[(size_t)col[e]];
-        ch[(size_t)e] = h == 0xFFFFFFFFu ? col[e] : (int32_t)(0x80000000u | h);
-    }
-    HubCopy hc;
-    HIPCHK(c, hc.d_col_hub.alloc((size_t)nnz));
-    HIPCHK(c, hc.d_hub_node.alloc(H));
-    HIPCHK(c, hc.d_hub_first.alloc(first.size()));
-    HIPCHK(c, hipMemcpy(hc.d_col_hub.get(), ch.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(hc.d_hub_node.get(), hub_node.data(), H * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(hc.d_hub_first.get(), first.data(), first.size() * 4, hipMemcpyHostToDevice));
-    hc.hubs = (uint32_t)H;
-    hc.shift = bin_shift(c);
-    hc.for_team = for_team;
-    c->g.hub = std::move(hc);
-    return FORA_OK;
-}
-
-// Quad-padded copies of col (and of the hub copy) for the wide bin kernel (Dev::col4), built on the device from what
-// set_graph has uploaded; only for graphs that run the wide layout in one bin pass per level.
-static int build_quad_copies(fora_ctx *c) {
-    c->g.quad = QuadCopies{};
-    if (!want_binned(c) || !want_wide(c) || c->g.nnz == 0 || c->opt_.quads == 0) return FORA_OK;
-    const uint64_t nbins_all = bins_of(c);
-    if ((int64_t)nbins_all > (int64_t)want_pass_bins(c, (int)nbins_all)) return FORA_OK; // several passes per level: pass-split rows, edge by edge
-    const size_t n = (size_t)c->g.n;
-    std::vector<uint64_t> ri4(n);
-    uint64_t q = 0;
-    // (Round 6, measured and dropped: rows placed so that each touches as few 64-byte lines as its length allows -- a row that would
-    // straddle one line more than ceil(quads / 4) started at the next line.  LJ-sized bin kernel 315.4 / 314.8 ms against 320.7 / 314.5
-    // back to back, Twitter-2010-sized 593.6 / 592.9 against 594.5 / 585.6: what a quad load costs is not the lines its row touches.)
-    for (size_t v = 0; v < n; v++) {
-        const uint64_t dg = (uint64_t)(c->g.h_row_ptr[v + 1] - c->g.h_row_ptr[v]);
-        ri4[v] = (q << 24) | std::min<uint64_t>(dg, DEG_SAT);
-        q += (dg + 3) / 4;
-    }
-    if (q >= (1ull << 40)) return FORA_OK;
-    // The copies are an optimisation (make_dev falls back to single-edge reads without them): they must never make
-    // set_graph fail.  Not built when they would take more than a quarter of the free memory (the slots need it more);
-    // an allocation that fails all the same leaves "no quads", not an error.
-    const uint64_t qbytes = std::max<uint64_t>(1, q) * 16, need = n * 8 + qbytes * (c->g.hub.d_col_hub ? 2 : 1);
-    size_t fr = 0, tot = 0;
-    HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    if (need > fr / 4) return FORA_OK;
-    QuadCopies qc;
-    auto give_up = [&]() { (void)hipGetLastError(); return FORA_OK; };
-    if (qc.d_rowinfo4.alloc(n) != hipSuccess) return give_up();
-    HIPCHK(c, hipMemcpy(qc.d_rowinfo4.get(), ri4.data(), n * 8, hipMemcpyHostToDevice));
-    if (qc.d_col4.alloc(qbytes / 4) != hipSuccess) return give_up();
-    const unsigned grid = (unsigned)std::min<size_t>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.d_col.get(),
-                       (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col4.get());
-    if (c->g.hub.d_col_hub) {
-        if (qc.d_col_hub4.alloc(qbytes / 4) != hipSuccess) return give_up();
-        hipLaunchKernelGGL(k_pad_quads, dim3(grid), dim3(BLOCK), 0, c->stream, c->g.n, (const int64_t *)c->g.d_row_ptr.get(), (const int32_t *)c->g.hub.d_col_hub.get(),
-                           (const uint64_t *)qc.d_rowinfo4.get(), qc.d_col_hub4.get());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    qc.quads = q;
-    c->g.quad = std::move(qc);
-    return FORA_OK;
-}
-
-// Degree-grouped walk copy (WalkDG, fora_kernels.h) of graphs that run the narrow layout: H hub records + at most 255
-// out-degree classes whose tables fit a workgroup's LDS share.  Graphs that do not qualify keep k_walk_online.
-static int build_walk_dg(fora_ctx *c, const int64_t *row_ptr, const int32_t *col) {
-    c->g.walk = WalkCopy{};
-    const int32_t n = c->g.n;
-    const int64_t nnz = c->g.nnz;
-    if (c->opt_.walk_dg == 0 || c->opt_.no_compact == 1 || nnz >= (1ll << 31) || nnz == 0) return FORA_OK;
-    if (!((uint64_t)n <= (uint64_t)MAX_BINS * BIN_SIZE && (uint64_t)n <= (1ull << SEG_BITS))) return FORA_OK; // narrow layout only
-    std::vector<uint32_t> order((size_t)n); // nodes by (out-degree descending, id ascending)
-    for (int32_t v = 0; v < n; v++) order[(size_t)v] = (uint32_t)v;
-    auto degree = [&](uint32_t v) { return (uint32_t)(row_ptr[v + 1] - row_ptr[v]); };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return degree(a) > degree(b); });
-    // smallest hub count that leaves at most 255 distinct degrees behind it
-    uint32_t H = 0, K = 0;
-    for (uint32_t h : {256u, 512u, 1024u, 2048u, 4096u}) {
-        if (c->opt_.dg_hubs > 0 && (int64_t)h < c->opt_.dg_hubs) continue;
-        const uint32_t hh = std::min<uint32_t>(h, (uint32_t)n);
-        uint32_t k = 0;
-        for (size_t i = hh; i < (size_t)n; i++) if (i == hh || degree(order[i]) != degree(order[i - 1])) k++;
-        if (k <= 255) { H = hh; K = k; break; }
-    }
-    if (H == 0 && !(n <= 256)) return FORA_OK;
-    if (n <= 256) { H = (uint32_t)n; K = 0; }
-    uint32_t ts = 6;
-    while ((((uint64_t)n + 256ull * (1ull << ts)) >> ts) > 8192) ts++; // at most 8192 blocks (8 KB of LDS)
-    const uint32_t blk = 1u << ts;
-    const uint32_t nrec = H + K;
-    std::vector<uint32_t> rec((size_t)3 * nrec, 0), perm((size_t)n), inv;
-    uint32_t *first = rec.data(), *rdeg = rec.data() + nrec, *base = rec.data() + 2 * (size_t)nrec;
-    std::vector<uint8_t> T;
-    uint64_t edge = 0;
-    uint32_t id = 0, zero_first = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < H; i++) { // hubs: one record each
-        const uint32_t v = order[i];
-        perm[v] = id; first[i] = id; rdeg[i] = degree(v); base[i] = (uint32_t)edge;
-        if (rdeg[i] == 0 && zero_first == 0xFFFFFFFFu) zero_first = id;
-        edge += rdeg[i]; id++;
-    }
-    uint32_t k = 0;
-    for (size_t i = H; i < (size_t)n;) { // classes, each padded to whole blocks
-        size_t j = i;
-        const uint32_t dg = degree(order[i]);
-        while (j < (size_t)n && degree(order[j]) == dg) j++;
-        const uint32_t r = H + k;
-        first[r] = id; rdeg[r] = dg; base[r] = (uint32_t)edge;
-        if (dg == 0 && zero_first == 0xFFFFFFFFu) zero_first = id;
-        for (size_t t = i; t < j; t++) perm[order[t]] = id + (uint32_t)(t - i);
-        const uint32_t cnt = (uint32_t)(j - i), padded = (cnt + blk - 1) / blk * blk;
-        for (uint32_t b = 0; b < padded / blk; b++) T.push_back((uint8_t)k);
-        edge += (uint64_t)cnt * dg;
-        id += padded;
-        i = j; k++;
-    }
-    const uint32_t np = id; // ids in use (with padding)
-    if (zero_first == 0xFFFFFFFFu) zero_first = np;
-    // every id from zero_first on must be dangling: degrees descend, so the zero class (if any) is the last one
-    uint32_t bits = 1;
-    while ((1ull << bits) < (uint64_t)np) bits++;
-    const size_t lds = (size_t)(H + 1) * 8 + (size_t)4 * nrec * 4 + T.size() + 4;
-    if (lds > 28 * 1024 || bits > 31) return FORA_OK; // static + dynamic LDS of k_walk_dg stay under 64 KB
-    inv.assign((size_t)np, 0);
-    for (int32_t v = 0; v < n; v++) inv[perm[(size_t)v]] = (uint32_t)v;
-    const size_t words = (size_t)(((uint64_t)nnz * bits + 31) / 32) + 2;
-    std::vector<uint32_t> pk(words, 0);
-    uint64_t e = 0;
-    for (uint32_t x = 0; x < np; x++) { // rows in copy-id order, file order inside a row
-        const uint32_t v = inv[x];
-        if (perm[v] != x) continue; // padding id
-        for (int64_t f = row_ptr[v]; f < row_ptr[v + 1]; f++, e++) {
-            const uint64_t at = e * bits;
-            const uint64_t y = (uint64_t)perm[(size_t)col[f]] << (at & 31);
-            pk[at >> 5] |= (uint32_t)y;
-            pk[(at >> 5) + 1] |= (uint32_t)(y >> 32);
-        }
-    }
-    while (T.size() & 3) T.push_back(0);
-    if (T.empty()) T.assign(4, 0);
-    WalkCopy wc;
-    HIPCHK(c, wc.d_perm.alloc((size_t)n));
-    HIPCHK(c, wc.d_inv.alloc((size_t)np));
-    HIPCHK(c, wc.d_colp.alloc(words));
-    HIPCHK(c, wc.d_rec.alloc(std::max<size_t>(1, rec.size())));
-    HIPCHK(c, wc.d_T.alloc(T.size()));
-    HIPCHK(c, hipMemcpy(wc.d_perm.get(), perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(wc.d_inv.get(), inv.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(wc.d_colp.get(), pk.data(), words * 4, hipMemcpyHostToDevice));
-    if (!rec.empty()) HIPCHK(c, hipMemcpy(wc.d_rec.get(), rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(wc.d_T.get(), T.data(), T.size(), hipMemcpyHostToDevice));
-    // bucket order of the ids behind the hubs: 64-id blocks dealt round-robin to nbx bins
-    const uint32_t nblk64 = (np - H + 63) / 64;
-    const uint32_t nbx = std::max<uint32_t>(2, (nblk64 + 127) / 128); // (2 at least: floor(2^32 / nbx) + 1 must fit 32 bits)
-    std::vector<uint32_t> invb((size_t)nbx * BIN_SIZE, 0);
-    for (uint32_t x = H; x < np; x++) {
-        const uint32_t u = x - H, b64 = u >> 6;
-        invb[((size_t)(b64 % nbx) << BIN_SHIFT) | ((b64 / nbx) << 6) | (u & 63u)] = inv[x];
-    }
-    if (nbx <= (uint32_t)MAX_BINS) {
-        HIPCHK(c, wc.d_invb.alloc(invb.size()));
-        HIPCHK(c, hipMemcpy(wc.d_invb.get(), invb.data(), invb.size() * 4, hipMemcpyHostToDevice));
-    }
-    WalkDG g{};
-    g.invb = wc.d_invb.get(); g.nbx = wc.d_invb.get() ? nbx : 0; g.nbx_magic = (uint32_t)((1ull << 32) / nbx) + 1;
-    g.perm = wc.d_perm.get(); g.inv = wc.d_inv.get(); g.colp = wc.d_colp.get(); g.rec = wc.d_rec.get(); g.T = wc.d_T.get();
-    g.H = H; g.nrec = nrec; g.nblk = (uint32_t)T.size(); g.ts = ts; g.bits = bits; g.zero_first = zero_first;
-    g.bits32 = (uint64_t)nnz * bits < (1ull << 32) ? 1 : 0;
-    wc.dg = g;
-    c->g.walk = std::move(wc);
-    return FORA_OK;
-}
-
 int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *row_ptr, const int32_t *col) {
     if (!c) return FORA_E_ARG;
     if (n <= 0 || !row_ptr || row_ptr[0] != 0) return fail(c, FORA_E_ARG, "bad graph");
@@ -2262,50 +2069,24 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
-        std::vector<uint64_t> rowinfo((size_t)n);
-        std::vector<uint32_t> deg((size_t)n);
-        int64_t n_dangling = 0;
-        for (int32_t v = 0; v < n; v++) {
-            const uint64_t dg = (uint64_t)(row_ptr[v + 1] - row_ptr[v]);
-            n_dangling += dg == 0;
-            if (dg > 0xFFFFFFFFull) return fail(c, FORA_E_ARG, "out-degree over 2^32");
-            deg[v] = (uint32_t)dg;
-            rowinfo[v] = ((uint64_t)row_ptr[v] << 24) | std::min<uint64_t>(dg, DEG_SAT);
-        }
-        HIPCHK(c, c->g.d_row_ptr.alloc((size_t)n + 1));
-        HIPCHK(c, c->g.d_col.alloc(std::max<size_t>(1, (size_t)nnz)));
-        HIPCHK(c, c->g.d_rowinfo.alloc((size_t)n));
-        HIPCHK(c, c->g.d_deg.alloc((size_t)n));
-        HIPCHK(c, hipMemcpy(c->g.d_row_ptr.get(), row_ptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-        if (nnz) HIPCHK(c, hipMemcpy(c->g.d_col.get(), col, (size_t)nnz * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->g.d_rowinfo.get(), rowinfo.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->g.d_deg.get(), deg.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        const RowBasics rb = make_row_basics(n, row_ptr);
+        if (!rb.ok) return fail(c, FORA_E_ARG, "out-degree over 2^32");
+        HIPCHK(c, c->g.d_row_ptr.upload(row_ptr, (size_t)n + 1));
+        HIPCHK(c, c->g.d_col.upload(col, (size_t)nnz, 1));
+        HIPCHK(c, c->g.d_rowinfo.upload(rb.rowinfo));
+        HIPCHK(c, c->g.d_deg.upload(rb.deg));
         if (nnz < (1ll << 31) && c->opt_.no_compact != 1) { // compact walk-step copy
-            uint32_t bits = 1;
-            while ((1ull << bits) < (uint64_t)n) bits++;
-            if (bits > 31) bits = 31;
-            std::vector<uint32_t> rp32((size_t)n + 1);
-            for (int32_t v = 0; v <= n; v++) rp32[v] = (uint32_t)row_ptr[v];
-            const size_t words = (size_t)(((uint64_t)nnz * bits + 31) / 32) + 2;
-            std::vector<uint32_t> pk(words, 0);
-            for (int64_t e = 0; e < nnz; e++) {
-                const uint64_t at = (uint64_t)e * bits;
-                const uint64_t x = (uint64_t)(uint32_t)col[e] << (at & 31);
-                pk[at >> 5] |= (uint32_t)x;
-                pk[(at >> 5) + 1] |= (uint32_t)(x >> 32);
-            }
-            HIPCHK(c, c->g.d_rp32.alloc(rp32.size()));
-            HIPCHK(c, c->g.d_colp.alloc(words));
-            HIPCHK(c, hipMemcpy(c->g.d_rp32.get(), rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(c->g.d_colp.get(), pk.data(), words * 4, hipMemcpyHostToDevice));
-            c->g.colbits = bits;
+            const CompactWalk w = make_compact_walk(n, row_ptr, col);
+            HIPCHK(c, c->g.d_rp32.upload(w.rp32));
+            HIPCHK(c, c->g.d_colp.upload(w.colp));
+            c->g.colbits = w.bits;
         }
         c->g.h_row_ptr.assign(row_ptr, row_ptr + n + 1);
         c->g.n = n; c->g.m_attr = m_attr; c->g.nnz = nnz;
-        c->g.dangling_frac = (double)n_dangling / (double)n;
-        if (int rb = build_walk_dg(c, row_ptr, col)) return rb;
-        if (int rb = ensure_team(c)) return rb; // (before the hub copy: its size depends on whether the team path takes this graph)
-        if (int rb = build_hub_copy(c, row_ptr, col)) return rb;
+        c->g.dangling_frac = (double)rb.n_dangling / (double)n;
+        if (int rw = build_walk_dg(c, row_ptr, col)) return rw;
+        if (int rt = ensure_team(c)) return rt; // (before the hub copy: its size depends on whether the team path takes this graph)
+        if (int rh = build_hub_copy(c, col)) return rh;
         return build_quad_copies(c);
     }();
     if (rc) free_graph(c); // no half-built graph: the next call answers "set_graph first"

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "fora_consts.h"
 #include "fora_diag.h"
 
 namespace fora {
@@ -37,26 +38,7 @@ constexpr uint32_t WALK_SEG = 1024; // max walks per walk work item
 #endif
 constexpr bool TEST_PATHS = FORA_TEST_PATHS != 0;
 constexpr uint64_t FIX_ONE = 1ull << 62;
-constexpr uint32_t DEG_SAT = 0xFFFFFFu; // rowinfo low 24 bits: out-degree, saturating
 constexpr int MAX_LEVELS = 1 << 15;
-// bucketed push (graphs of up to MAX_BINS * BIN_SIZE nodes): increments are binned by target
-// range and reduced in LDS instead of one global atomic per edge
-#ifndef FORA_BIN_SHIFT
-#define FORA_BIN_SHIFT 13
-#endif
-constexpr int BIN_SHIFT = FORA_BIN_SHIFT;      // narrow layout
-constexpr uint32_t BIN_SIZE = 1u << BIN_SHIFT; // 8192 nodes -> 64 KiB of u64 accumulators in LDS
-// Wide layouts: 16384-node bins (128 KiB of accumulators, one 1024-thread accumulate workgroup per CU): half the bins, so
-// twice the messages per (chunk, bin) run, and a Twitter-2010-sized graph (2543 bins) needs ONE bin pass per level instead
-// of two.  Same run: LJ-sized 280 indexed queries 904 -> 833 ms, Twitter-2010-sized 15.96 -> 18.48 q/s.
-#ifndef FORA_BIN_SHIFT_WIDE
-#define FORA_BIN_SHIFT_WIDE 14
-#endif
-constexpr int BIN_SHIFT_WIDE = FORA_BIN_SHIFT_WIDE;
-constexpr uint32_t BIN_SIZE_WIDE = 1u << BIN_SHIFT_WIDE;
-constexpr int MAX_BINS = 128;       // narrow layout: 4-B push messages, staged walk results
-constexpr int MAX_BINS_WIDE = 1024; // wide layout: 8-byte messages (local target | value << 14), up to 1024 bins per pass ...
-constexpr int MAX_BINS_HUGE = 2560; // ... or 2560 for graphs with more bins (Twitter-2010: 2543 bins, one pass)
 #ifndef FORA_ACC_THREADS
 #define FORA_ACC_THREADS 512
 #endif
@@ -82,7 +64,6 @@ constexpr int BIN_EPT = 8; // edges per thread per chunk in k_pushq_bin / k_walk
 #ifndef FORA_RUN_PAD_WIDE
 #define FORA_RUN_PAD_WIDE 1
 #endif
-constexpr int SEG_BITS = 32 - BIN_SHIFT; // narrow push message = (target & (BIN_SIZE-1)) << SEG_BITS | frontier position
 // bucket messages are read exactly once: non-temporal loads keep them from displacing the increment table and the
 // slabs in L2 (accumulate kernels -1 %)
 #define NT_LOAD(p) __builtin_nontemporal_load(p)

@@ -38,18 +38,8 @@
 
 namespace fora {
 
-constexpr int TEAM_MAX = 32;                  // members of a team (5 bits of a target word)
-constexpr int TEAM_LBITS = 15;                // bits of a local id
-#ifndef FORA_TEAM_THREADS
-#define FORA_TEAM_THREADS 1024
-#endif
 constexpr int TEAM_THREADS = FORA_TEAM_THREADS; // 1024: one workgroup per CU; 512: two per CU (members of two different teams: one team's waits overlap the other's work)
-#ifndef FORA_TEAM_WGS_PER_CU
-#define FORA_TEAM_WGS_PER_CU (FORA_TEAM_THREADS == 1024 ? 1 : 2)
-#endif
-constexpr int TEAM_WGS_PER_CU = FORA_TEAM_WGS_PER_CU;
 constexpr int TEAM_NW = TEAM_THREADS / 64;
-constexpr uint32_t TEAM_R_CAP = TEAM_WGS_PER_CU == 1 ? 15296 : 7680; // local ids per member at most: 8 * (R + 1) + the static LDS below <= 160 KiB / workgroups per CU
 constexpr int TEAM_NIT = (TEAM_R_CAP + TEAM_THREADS - 1) / TEAM_THREADS; // sweep iterations at most (ids per thread): 15 (30 with 512 threads and one workgroup per CU)
 #ifndef FORA_TEAM_EPT
 #define FORA_TEAM_EPT 4
@@ -65,8 +55,6 @@ constexpr int TEAM_NIT = (TEAM_R_CAP + TEAM_THREADS - 1) / TEAM_THREADS; // swee
 #endif
 constexpr int TEAM_EPT = FORA_TEAM_EPT;       // consecutive edges a lane gathers per chunk
 constexpr int TEAM_CHUNK = 64 * TEAM_EPT;     // edges of a chunk
-constexpr uint32_t TEAM_LMASK = (1u << TEAM_LBITS) - 1u;
-constexpr uint32_t TEAM_EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t ERR_TEAM_TIMEOUT = 16, ERR_TEAM_CAP = 32;
 
 struct TeamDev {
