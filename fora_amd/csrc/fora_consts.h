@@ -26,6 +26,14 @@ constexpr int MAX_BINS_WIDE = 1024; // wide layout: 8-byte messages (local targe
 constexpr int MAX_BINS_HUGE = 2560; // ... or 2560 for graphs with more bins (Twitter-2010: 2543 bins, one pass)
 constexpr int SEG_BITS = 32 - BIN_SHIFT; // narrow push message = (target & (BIN_SIZE-1)) << SEG_BITS | frontier position
 
+// k_walk_dg: the tile of walk items that ticket k of workgroup x names.  A slot's tiles are dealt to its `sub` workgroups
+// of nw waves as a static stride would deal them to the waves (wave w of workgroup x: x * nw + w, + tstride, ... with
+// tstride = sub * nw); a workgroup hands ITS tiles out in ascending order, one ticket per tile, to the wave that asks.
+// Ascending in k, so the first ticket at or past the slot's tile count ends the hand-out.
+constexpr uint32_t dg_ticket_tile(uint32_t x, uint32_t nw, uint32_t tstride, uint32_t k) {
+    return x * nw + k % nw + k / nw * tstride;
+}
+
 // team push (fora_team.h)
 constexpr int TEAM_MAX = 32;                  // members of a team (5 bits of a target word)
 constexpr int TEAM_LBITS = 15;                // bits of a local id

@@ -2746,6 +2746,18 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FORA
 // iteration runs both steps of a Philox call; the endpoint's original id (one gather per WALK) is loaded at the end
 // of the iteration and consumed by the next one's emission, so its latency hides behind the refill and the Philox
 // rounds.  A workgroup is 8 waves sharing one copy of the tables.
+// LDS of a workgroup (NW = 8 waves, DG_STAGE = 256, WT = DG_TILE / NW = 32; XL):
+//   stage words            st_pk     NW * DG_STAGE * 8      16 384
+//   per-wave bin arrays    st_bcnt   NW * MAX_BINS * 4       4 096    (bins' counts, then their first stage slot)
+//                          st_bbase  NW * MAX_BINS * 4       4 096    (bins' first slot in the sub-bucket)
+//   workgroup's fill       st_fill   MAX_BINS * 4              512
+//   tile records           w_item    NW * WT * 32            8 192
+//   tile prefix sums       w_pref    NW * (WT + 1) * 4       1 056
+//   self sums              w_self    NW * WT * 8             2 048    (XL only)
+//   step counts, ticket    s_w, s_ticket                        36 -> 36 432 static with padding
+//   tables (dynamic)       hub sums (H + 1) * 8 | records nrec * 16 | block -> class bytes: 14 232 at the ws-sized bench graph
+//                          (H = 256, 221 classes, 4 550 blocks), at most WALK_DG_LDS_CAP
+//   ~50 KB: three workgroups per CU, 6 waves per SIMD (FORA_DG_WPE).
 #ifndef FORA_DG_THREADS
 #define FORA_DG_THREADS 512
 #endif
@@ -2796,6 +2808,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     // item in LDS (w_self) and leave as ONE result per item when the wave replaces its tile -- a walk that outlives its tile
     // (its tag names the tile it came from) is emitted on its own as before.
     __shared__ unsigned long long w_self[XL ? NW : 1][XL ? WT : 1];
+    __shared__ uint32_t s_ticket; // tiles of this workgroup handed out so far (dg_ticket_tile)
     const int q = blockIdx.y;
     const uint32_t nitems = (uint32_t)min((uint64_t)d.wit_count[q * CSTRIDE], d.wit_cap); // (see k_walk_idx)
     if (!nitems || *d.err) return;
@@ -2821,6 +2834,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     if (XL) st.xl = g.invb;
     uint32_t *bkc = d.bk_count + (uint64_t)q * d.pbins * d.sub + blockIdx.x; // count of bin b: bkc[b * sub]
     for (uint32_t i = threadIdx.x; i < (uint32_t)MAX_BINS; i += DG_THREADS) st.fill[i] = i < (uint32_t)d.nbins ? bkc[(uint64_t)i * d.sub] : 0;
+    if (threadIdx.x == 0) s_ticket = 0;
     __syncthreads();
     // one move (algo.h:134-140) from copy id `cur` with random word wm
     auto move = [&](uint32_t cur, uint32_t startp, uint32_t wm) -> uint32_t {
@@ -2856,9 +2870,17 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
         }
         stage_emit<DG_STAGE, true, false>(d, q, st, has, dn - H, (uint64_t)sv);
     };
+    // The workgroup's tiles are those of its NW waves under a static stride (x * NW + w, + tstride, ...), handed out in that
+    // order to whichever wave runs out of walks first: one returning LDS add per tile.  Tiles differ by up to 30x in walks (a
+    // node with many walks is consecutive items of 1024), and the workgroup holds its LDS until its slowest wave ends.
     const uint32_t ntiles = (nitems + WT - 1) / WT;
-    uint32_t tile = blockIdx.x * NW + wid;      // the wave's next tile of WT items
     const uint32_t tstride = gridDim.x * NW;
+    bool more = true;                           // no ticket has named a tile at or past ntiles yet (tickets ascend: none will after)
+    auto take_tile = [&]() -> uint32_t {
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(&s_ticket, 1u); // LDS
+        return dg_ticket_tile(blockIdx.x, (uint32_t)NW, tstride, (uint32_t)__builtin_amdgcn_readfirstlane((int)k));
+    };
     // wave-uniform, kept in scalar registers (readfirstlane where a value comes out of LDS or a lane): the loop's tests on
     // them and the advance of cur_item are scalar instructions
     uint32_t wptr = 0, wend = 0;                // walks of the current tile: wptr .. wend - 1 are not handed out yet
@@ -2879,7 +2901,9 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
         bool fin = false; // the lane's walk ended in this iteration, at cur
         const unsigned long long idle = __ballot(!active);
         if (idle && wptr == wend) { // lanes are free and the tile is handed out: the next tile that has walks
-            while (wptr == wend && tile < ntiles) {
+            while (wptr == wend && more) {
+                const uint32_t tile = take_tile();
+                if (tile >= ntiles) { more = false; break; }
                 if (gen) flush_self();
                 gen++;
                 const uint32_t i = tile * WT + lane;
@@ -2906,7 +2930,6 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the wave's own LDS writes, read by its lanes below)
                 __builtin_amdgcn_wave_barrier();
                 wptr = 0; wend = total; cur_item = 0;
-                tile += tstride;
                 advance();
             }
         }
