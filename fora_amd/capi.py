@@ -20,6 +20,7 @@ SYMBOLS = [
     "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bippr_targets_batch", "fora_hip_bwdpush_batch",
     "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
     "fora_hip_query_seeds_batch",
+    "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -79,6 +80,25 @@ class SeedsStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+class SweepRow(C.Structure):
+    _fields_ = [("len", C.c_int64), ("best", C.c_int64), ("cut", C.c_uint64), ("vol", C.c_uint64), ("den", C.c_uint64),
+                ("conductance", C.c_double)]
+
+
+_SWEEP_ROW_DTYPE = np.dtype([(name, {C.c_double: np.float64, C.c_uint64: np.uint64, C.c_int64: np.int64}[ct])
+                             for name, ct in SweepRow._fields_], align=True)
+assert _SWEEP_ROW_DTYPE.itemsize == C.sizeof(SweepRow)
+
+
+class SweepStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("max_row", C.c_uint64), ("thr_fix", C.c_uint64), ("edges", C.c_uint64),
+                ("batches", C.c_int32), ("global_rows", C.c_int32), ("compact_ms", C.c_double), ("sort_ms", C.c_double),
+                ("cut_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def to_torch_csr(row_ptr, ids, vals, n):
@@ -281,6 +301,62 @@ class Engine:
 
     def sparse_clear(self):
         self._chk(self._lib.fora_hip_sparse_clear(self._ctx))
+
+    # ---- local clustering (the SWEEP CUT contract of include/fora_hip.h)
+    def sweep(self, sources, with_idx=False, threshold=None, max_size=0, want_profile=False, device=False):
+        """query() followed on the GPU by the sweep over ppr / degree of every row (fora_hip_sweep_batch): the support
+        {v : word >= max(1, ceil(threshold * 2^62))} (threshold=None: 1 / n) in sweep order, the cut and the volume of every
+        prefix of at most max_size nodes (0: all), and the prefix of least conductance.  Returns a dict: row_ptr (int64
+        [nq + 1], prefix sums of the profile lengths), rows (a structured array: len, best, cut, vol, den, conductance),
+        stats, sweep (a dict), and with want_profile ids / cut / vol (int32 / uint64 / uint64; device=True: torch tensors
+        on the context's GPU, the u64 ones as int64 bits).  The best cluster of row i is
+        ids[row_ptr[i] : row_ptr[i] + rows[i]["best"]]."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        rows = (SweepRow * max(1, nq))()
+        sw = SweepStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_sweep_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
+                                                 C.c_int64(int(max_size)), _p(row_ptr), rows, st, C.byref(sw)))
+        out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=nq).copy(),
+               "stats": self._stats(st, nq), "sweep": sw.as_dict()}
+        if want_profile:
+            out["ids"], out["cut"], out["vol"] = self.sweep_fetch(int(row_ptr[-1]), device=device)
+        return out
+
+    def sweep_fetch(self, entries, device=False):
+        """The held profile, again (fora_hip_sweep_fetch): (ids, cut, vol) of `entries` entries each."""
+        e = int(entries)
+        if device:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("sweep_fetch(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
+                                   "HIP runtime: import torch before the first Engine is created")
+            dev = torch.device("cuda", self.device)
+            ids = torch.empty(e, dtype=torch.int32, device=dev)
+            cut = torch.empty(e, dtype=torch.int64, device=dev)
+            vol = torch.empty(e, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
+            self._chk(self._lib.fora_hip_sweep_fetch(self._ctx, C.c_void_p(ids.data_ptr()), C.c_void_p(cut.data_ptr()),
+                                                     C.c_void_p(vol.data_ptr()), C.c_uint64(e)))
+        else:
+            ids = np.zeros(e, dtype=np.int32)
+            cut = np.zeros(e, dtype=np.uint64)
+            vol = np.zeros(e, dtype=np.uint64)
+            self._chk(self._lib.fora_hip_sweep_fetch(self._ctx, _p(ids), _p(cut), _p(vol), C.c_uint64(e)))
+        return ids, cut, vol
+
+    def sweep_clear(self):
+        self._chk(self._lib.fora_hip_sweep_clear(self._ctx))
+
+    def local_cluster(self, sources, with_idx=False, threshold=None, max_size=0):
+        """The cluster of least conductance around every source: one int32 id array per source, in sweep order (empty when
+        no prefix has a denominator: a dangling source)."""
+        r = self.sweep(sources, with_idx=with_idx, threshold=threshold, max_size=max_size, want_profile=True)
+        rp, ids = r["row_ptr"], r["ids"]
+        return [ids[int(rp[i]):int(rp[i]) + int(r["rows"][i]["best"])].copy() for i in range(len(r["rows"]))]
 
     def push(self, sources, want=True):
         """want=False: only the per-query stats come back (the slabs stay in HBM)."""

@@ -6,6 +6,7 @@
 #include "fora_kernels.h"
 #include "fora_team.h"
 #include "fora_bwd.h"
+#include "fora_sweep.h"
 #include "fora_tables.h"
 #include "../../include/fora_hip.h"
 
@@ -26,7 +27,8 @@ namespace {
 // What an event pair times, named after the fora_timing field it feeds.  The switch of ev_collect is the one place that says which
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
-              EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE };
+              EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -84,6 +86,8 @@ struct Tunables {
     int64_t bwd_chunk = 0;       // backward push: targets per chunk (0: as many as the entry budget from free HBM holds)
     int64_t tgt_lanes = -1;      // targeted BiPPR combine (k_bippr_combine_targets): 0 lane = slot over the transposed walk slabs, 1 lane = entry over the slot-major ones, -1: by the batch's slots and the call's entries (want_by_slot).  Same bits either way
     int64_t tgt_span = 0;        // ... entries per wave (0: from the chunk's entries, 64 .. 1024).  Same bits for every value
+    int64_t sweep_lds_cap = SW_TILE_MAX; // sweep cut (fora_hip_sweep_batch): entries of a sort tile, rounded down to a power of two (at most SW_TILE_MAX); a row that fits one is sorted by one workgroup in LDS, a longer one takes the global tier; 0: every row does, every step in global memory.  Same bits for every value
+    int64_t sweep_rows = 0;      // ... rows whose rank maps are live at a time (the rank block holds that many slabs of n words); 0: 256.  Same bits for every value
     int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -96,6 +100,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
     {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
     {"seeds_dedup", &Tunables::seeds_dedup, false},
+    {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -290,6 +295,20 @@ struct SparseResult {
     DevBuf<int64_t> d_base;           // first entry of every live row of the call
     DevBuf<double> d_stage;           // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
 };
+// Sweep profile of the last fora_hip_sweep_batch (free_sweep: sweep_clear, set_graph), apart from the workspace and from the
+// sparse result; the buffers of the call in progress live here too.
+struct SweepResult {
+    DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_cut, d_vol; // profiles of all rows, rows in the caller's order
+    uint64_t entries = 0;
+    bool valid = false; // a result is held (it may have no entries)
+    DevBuf<uint32_t> d_counts, d_tot; PinBuf<uint32_t> h_tot; // count pass of the batch in progress, as SparseResult's
+    DevBuf<int32_t> d_tids; DevBuf<uint64_t> d_tkey;          // padded (id, key) copies of the batch's rows: the sort buffers
+    DevBuf<uint64_t> d_desc;                                  // descriptors of the batch: SweepRowDesc | base | SweepTile | SweepGRow
+    DevBuf<SweepRowOut> d_out; PinBuf<SweepRowOut> h_out;     // per live row of the batch
+    DevBuf<int32_t> d_rank;                                   // [rank_rows][n], -1 between uses
+    uint32_t rank_rows = 0;
+    bool rank_dirty = false; // a call ended between a scatter and its reset
+};
 
 // The loose words of the context, grouped by role.
 struct Params { // fora_hip_set_params / _raw
@@ -323,7 +342,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -333,7 +352,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp;
     int batch_req = 0;         // the caller's request (fora_hip_set_batch), not part of a plan
     uint64_t bin_launches = 0; // parity picks the counter set
     std::vector<QState> h_qs;
@@ -359,6 +378,7 @@ int fail(fora_ctx *c, int code, const std::string &msg) {
 // every buffer of the group freed, every field of it back at its initialiser
 void free_graph(fora_ctx *c) { c->g = Graph{}; }
 void free_sparse(fora_ctx *c) { c->sp = SparseResult{}; }
+void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
 void free_index(fora_ctx *c) { c->ix = Index{}; }
 void free_workspace(fora_ctx *c) { c->ws = Workspace{}; }
 
@@ -863,6 +883,9 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_COMBINE: t.combine_ms += ms; break;       // BiPPR's transposes, combines and finish: fora_bwd_stats only
         case EV_SP_COMPACT: t.sp_compact_ms += ms; break; // k_sparse_count / k_sparse_write: reported through fora_sparse_stats only
         case EV_SEED_COMBINE: t.seed_combine_ms += ms; break; // k_seed_combine: reported through fora_seeds_stats only
+        case EV_SW_COMPACT: t.sw_compact_ms += ms; break;     // the sweep's count / write / key passes: fora_sweep_stats only
+        case EV_SW_SORT: t.sw_sort_ms += ms; break;           // k_sweep_sort_lds / k_sweep_sort_step: fora_sweep_stats only
+        case EV_SW_CUT: t.sw_cut_ms += ms; break;             // scatter, k_sweep_cut, k_sweep_scan, reset: fora_sweep_stats only
         }
     }
     t.ev_used = 0;
@@ -1415,6 +1438,246 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, in
     return FORA_OK;
 }
 
+// ---- sweep cut (fora_hip_sweep_batch; the SWEEP CUT contract of include/fora_hip.h, kernels in fora_sweep.h): host side of
+// one attempt of a call.  The profiles are laid out in the caller's order like the rows of a sparse result; a batch's rows are
+// compacted, sorted and swept once the batch has closed -- its slabs hold the rows until the next batch starts on the stream.
+struct SweepRun {
+    uint64_t thr = 1;
+    int64_t max_size = 0;
+    uint32_t R = SP_TILE, X = 1;          // the compaction's ids per workgroup, workgroups per slot
+    std::vector<int64_t> row_ptr;         // nq + 1: prefix sums of L
+    std::vector<fora_sweep_row> rows;     // nq
+    std::vector<int64_t> dang_at; std::vector<int32_t> dang_src; // entries of the dangling rows and their sources
+    int next_row = 0, batches = 0, global_rows = 0;
+    uint64_t cur = 0, max_row = 0, entries_len = 0, edges = 0; // entries placed so far; the longest support; the supports summed
+};
+
+static fora_sweep_row sweep_row_of(int64_t len, int64_t best, uint64_t cut, uint64_t vol, uint64_t den) {
+    fora_sweep_row r;
+    r.len = len; r.best = best; r.cut = cut; r.vol = vol; r.den = den;
+    r.conductance = best ? (double)cut / (double)den : 1.0;
+    return r;
+}
+static uint32_t sweep_tile(const fora_ctx *c) { // entries of a sort tile; 1: no LDS step at all
+    const int64_t cap = std::min<int64_t>(c->opt_.sweep_lds_cap, SW_TILE_MAX);
+    uint32_t t = 1;
+    while ((int64_t)t * 2 <= cap) t *= 2;
+    return t;
+}
+
+// the rank block of min(live, sweep_rows) slabs, all -1
+int sweep_prepare_rank(fora_ctx *c, int live) {
+    SweepResult &w = c->swp;
+    const uint64_t n = (uint64_t)c->g.n;
+    const uint32_t rows = (uint32_t)std::min<int64_t>(live, c->opt_.sweep_rows > 0 ? c->opt_.sweep_rows : 256);
+    const bool fresh = !w.d_rank || w.d_rank.size() < (uint64_t)rows * n;
+    if (fresh && w.d_rank.alloc((uint64_t)rows * n) != hipSuccess) {
+        (void)hipGetLastError();
+        free_workspace(c); // (no room beside a workspace that is already there: that one goes, as for the seed sets' block)
+        if (w.d_rank.alloc((uint64_t)rows * n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, FORA_E_NOMEM, "no device memory for the sweep's rank block (sweep_rows x n words): lower the option sweep_rows");
+        }
+    }
+    if (fresh || w.rank_dirty) HIPCHK(c, w.d_rank.fill(c->stream, 0xFF, 0, w.d_rank.size()));
+    w.rank_dirty = false;
+    w.rank_rows = rows;
+    return FORA_OK;
+}
+
+// per-call buffers of the passes over a batch of at most `slots` slots
+int sweep_prepare(fora_ctx *c, SweepRun &sw, int slots) {
+    const uint64_t n = (uint64_t)c->g.n;
+    sw.R = (uint32_t)std::max<uint64_t>(8 * SP_TILE, ((n + 1023) / 1024 + SP_TILE - 1) / SP_TILE * SP_TILE); // at most 1024 workgroups per slot
+    sw.X = (uint32_t)((n + sw.R - 1) / sw.R);
+    SweepResult &w = c->swp;
+    HIPCHK(c, w.d_counts.ensure((size_t)slots * sw.X));
+    HIPCHK(c, w.d_tot.ensure((size_t)slots));
+    HIPCHK(c, w.h_tot.ensure((size_t)slots));
+    HIPCHK(c, w.d_out.ensure((size_t)slots));
+    HIPCHK(c, w.h_out.ensure((size_t)slots));
+    return FORA_OK;
+}
+
+// room for `need` profile entries, the first `keep` of them already written (sparse_reserve's scheme)
+int sweep_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done, uint64_t rows_all) {
+    SweepResult &w = c->swp;
+    if (need <= w.d_ids.size()) return FORA_OK;
+    const uint64_t guess = rows_done ? (uint64_t)((double)need / (double)rows_done * (double)rows_all * 1.125) + 1024 : need;
+    DevBuf<int32_t> ids; DevBuf<uint64_t> cut, vol;
+    uint64_t cap = std::max<uint64_t>({need, guess, 1});
+    for (;; cap = need) { // (a guess that does not fit is no reason to fail)
+        if (ids.alloc(cap) == hipSuccess && cut.alloc(cap) == hipSuccess && vol.alloc(cap) == hipSuccess) break;
+        (void)hipGetLastError();
+        ids.reset(); cut.reset(); vol.reset();
+        if (cap == need) {
+            (void)hipStreamSynchronize(c->stream);
+            w.d_ids.reset(); w.d_cut.reset(); w.d_vol.reset();
+            return fail(c, FORA_E_NOMEM, "no device memory for the sweep profiles");
+        }
+    }
+    keep = std::min<uint64_t>(keep, w.d_ids.size());
+    if (keep) {
+        HIPCHK(c, hipMemcpyAsync(ids.get(), w.d_ids.get(), keep * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cut.get(), w.d_cut.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(vol.get(), w.d_vol.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    w.d_ids = std::move(ids); w.d_cut = std::move(cut); w.d_vol = std::move(vol);
+    return FORA_OK;
+}
+
+// rows of the caller up to (not including) row `upto` that no batch has placed yet: dangling sources, one entry each
+void sweep_skip_dangling(SweepRun &sw, const int32_t *sources, int upto) {
+    for (; sw.next_row < upto; sw.next_row++) {
+        sw.row_ptr[(size_t)sw.next_row] = (int64_t)sw.cur;
+        sw.rows[(size_t)sw.next_row] = sweep_row_of(1, 0, 0, 0, 0);
+        sw.dang_at.push_back((int64_t)sw.cur);
+        sw.dang_src.push_back(sources[sw.next_row]);
+        sw.cur += 1; sw.entries_len += 1;
+        sw.max_row = std::max<uint64_t>(sw.max_row, 1);
+    }
+}
+
+// the batch just closed (slot i: row at[i] of the caller): compaction, sort, and chunk by chunk the cut count and the scan
+int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, const int *at, int nb) {
+    SweepResult &w = c->swp;
+    const uint32_t n = (uint32_t)c->g.n;
+    const uint64_t *ppr = c->ws.d_ppr.get();
+    EvSpan ev(c);
+    // count pass
+    HIPCHK(c, hipMemsetAsync(w.d_tot.get(), 0, (size_t)nb * 4, c->stream));
+    ev.begin(EV_SW_COMPACT);
+    hipLaunchKernelGGL(k_sparse_count, dim3(sw.X, nb), dim3(BLOCK), 0, c->stream, ppr, n, sw.thr, sw.R, w.d_counts.get(), w.d_tot.get());
+    ev.end();
+    HIPCHK(c, hipMemcpyAsync(w.h_tot.get(), w.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // layout: padded copies in the sort buffers, profiles in the held arrays
+    const uint32_t T = sweep_tile(c);
+    std::vector<SweepRowDesc> rd((size_t)nb);
+    std::vector<int64_t> tbase((size_t)nb);
+    std::vector<SweepTile> tiles;
+    std::vector<SweepGRow> grows;
+    const uint64_t keep = sw.cur;
+    uint64_t tneed = 0;
+    uint32_t maxP = 0, maxL = 0;
+    for (int i = 0; i < nb; i++) {
+        sweep_skip_dangling(sw, sources, at[i]);
+        const uint32_t len = w.h_tot.get()[i];
+        uint32_t P = len ? 1 : 0;
+        while (P < len) P *= 2; // (len <= n < 2^31)
+        const uint32_t L = sw.max_size > 0 ? (uint32_t)std::min<int64_t>(len, sw.max_size) : len;
+        rd[(size_t)i] = SweepRowDesc{(int64_t)tneed, (int64_t)sw.cur, len, P, L, 0};
+        tbase[(size_t)i] = (int64_t)tneed;
+        if (P > T) { grows.push_back(SweepGRow{(int64_t)tneed, P, 0}); sw.global_rows++; }
+        if (T >= 2) for (uint32_t off = 0; off < P; off += T) tiles.push_back(SweepTile{(int64_t)tneed + off, P, off});
+        sw.row_ptr[(size_t)at[i]] = (int64_t)sw.cur;
+        tneed += P; sw.cur += L; sw.entries_len += len;
+        sw.max_row = std::max<uint64_t>(sw.max_row, len);
+        maxP = std::max(maxP, P); maxL = std::max(maxL, L);
+        sw.next_row = at[i] + 1;
+    }
+    sw.batches++;
+    if (int rc = sweep_reserve(c, sw.cur, keep, (uint64_t)sw.next_row, (uint64_t)nq)) return rc;
+    if (w.d_tids.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess || w.d_tkey.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, FORA_E_NOMEM, "no device memory for the sweep's sort buffers");
+    }
+    const uint64_t tcap = std::min(w.d_tids.size(), w.d_tkey.size()), hcap = w.d_ids.size();
+    // one upload: SweepRowDesc[nb] | base[nb] | SweepTile[] | SweepGRow[]
+    const size_t o_base = (size_t)nb * sizeof(SweepRowDesc) / 8, o_tile = o_base + (size_t)nb, o_grow = o_tile + tiles.size() * sizeof(SweepTile) / 8;
+    std::vector<uint64_t> pack(o_grow + grows.size() * sizeof(SweepGRow) / 8 + 1, 0);
+    memcpy(pack.data(), rd.data(), (size_t)nb * sizeof(SweepRowDesc));
+    memcpy(pack.data() + o_base, tbase.data(), (size_t)nb * 8);
+    if (!tiles.empty()) memcpy(pack.data() + o_tile, tiles.data(), tiles.size() * sizeof(SweepTile));
+    if (!grows.empty()) memcpy(pack.data() + o_grow, grows.data(), grows.size() * sizeof(SweepGRow));
+    HIPCHK(c, w.d_desc.ensure(pack.size()));
+    HIPCHK(c, hipMemcpyAsync(w.d_desc.get(), pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+    const SweepRowDesc *d_rd = (const SweepRowDesc *)w.d_desc.get();
+    const int64_t *d_base = (const int64_t *)(w.d_desc.get() + o_base);
+    const SweepTile *d_tiles = (const SweepTile *)(w.d_desc.get() + o_tile);
+    const SweepGRow *d_grows = (const SweepGRow *)(w.d_desc.get() + o_grow);
+    const auto gx = [](uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + BLOCK - 1) / BLOCK, 128)); };
+    if (maxP) {
+        ev.begin(EV_SW_COMPACT);
+        hipLaunchKernelGGL(k_sparse_write, dim3(sw.X, nb), dim3(BLOCK), 0, c->stream, ppr, n, sw.thr, sw.R, (const uint32_t *)w.d_counts.get(), d_base,
+                           w.d_tids.get(), w.d_tkey.get(), tcap);
+        hipLaunchKernelGGL(k_sweep_keys, dim3(gx(maxP), nb), dim3(BLOCK), 0, c->stream, d_rd, (const uint32_t *)c->g.d_deg.get(), n, w.d_tids.get(), w.d_tkey.get(), tcap);
+        ev.begin(EV_SW_SORT);
+        if (!tiles.empty()) hipLaunchKernelGGL(k_sweep_sort_lds, dim3((unsigned)tiles.size()), dim3(BLOCK), 0, c->stream, w.d_tids.get(), w.d_tkey.get(), tcap, d_tiles, T, 0u);
+        if (!grows.empty())
+            for (uint64_t k = 2 * (uint64_t)T; k <= maxP; k *= 2) {
+                for (uint64_t j = k / 2; j >= T; j /= 2)
+                    hipLaunchKernelGGL(k_sweep_sort_step, dim3(gx(maxP / 2), (unsigned)grows.size()), dim3(BLOCK), 0, c->stream, w.d_tids.get(), w.d_tkey.get(), tcap,
+                                       d_grows, (uint32_t)k, (uint32_t)j);
+                if (T >= 2) hipLaunchKernelGGL(k_sweep_sort_lds, dim3((unsigned)tiles.size()), dim3(BLOCK), 0, c->stream, w.d_tids.get(), w.d_tkey.get(), tcap, d_tiles, T, (uint32_t)k);
+            }
+        ev.end();
+    }
+    // rank maps, cut counts, scans: rank_rows rows at a time
+    ev.begin(EV_SW_CUT);
+    w.rank_dirty = true;
+    for (int r0 = 0; r0 < nb; r0 += (int)w.rank_rows) {
+        const unsigned nr = (unsigned)std::min<int>((int)w.rank_rows, nb - r0);
+        if (maxL) {
+            hipLaunchKernelGGL(k_sweep_scatter<true>, dim3(gx(maxL), nr), dim3(BLOCK), 0, c->stream, d_rd, (uint32_t)r0, w.d_rank.get(), n, (const int32_t *)w.d_tids.get(), tcap,
+                               (const uint32_t *)c->g.d_deg.get(), w.d_ids.get(), w.d_cut.get(), w.d_vol.get(), hcap);
+            hipLaunchKernelGGL(k_sweep_cut, dim3(gx(maxL), nr), dim3(BLOCK), 0, c->stream, d_rd, (uint32_t)r0, (const int32_t *)w.d_rank.get(), n, (const int64_t *)c->g.d_row_ptr.get(),
+                               (const int32_t *)c->g.d_col.get(), (const int32_t *)w.d_ids.get(), (unsigned long long *)w.d_cut.get(), hcap);
+        }
+        hipLaunchKernelGGL(k_sweep_scan, dim3(nr), dim3(BLOCK), 0, c->stream, d_rd, (uint32_t)r0, w.d_cut.get(), w.d_vol.get(), hcap, (uint64_t)c->g.nnz, w.d_out.get());
+        if (maxL)
+            hipLaunchKernelGGL(k_sweep_scatter<false>, dim3(gx(maxL), nr), dim3(BLOCK), 0, c->stream, d_rd, (uint32_t)r0, w.d_rank.get(), n, (const int32_t *)w.d_tids.get(), tcap,
+                               (const uint32_t *)nullptr, (int32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0);
+    }
+    ev.end();
+    HIPCHK(c, hipMemcpyAsync(w.h_out.get(), w.d_out.get(), (size_t)nb * sizeof(SweepRowOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sweep: ") + hipGetErrorString(e));
+    w.rank_dirty = false;
+    for (int i = 0; i < nb; i++) {
+        const SweepRowOut &o = w.h_out.get()[i];
+        sw.rows[(size_t)at[i]] = sweep_row_of(o.len, o.best, o.cut, o.vol, o.den);
+        sw.edges += o.edges;
+    }
+    return FORA_OK;
+}
+
+// end of a call whose batches all went through: the dangling rows' entries, the last event times, the result is held
+int sweep_finish(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, int64_t *row_ptr, fora_sweep_row *rows, fora_sweep_stats *out) {
+    SweepResult &w = c->swp;
+    sweep_skip_dangling(sw, sources, nq);
+    sw.row_ptr[(size_t)nq] = (int64_t)sw.cur;
+    if (int rc = sweep_reserve(c, sw.cur, sw.cur, (uint64_t)nq, (uint64_t)nq)) return rc; // (only grows when dangling rows came last)
+    DevBuf<int64_t> at; DevBuf<int32_t> src; // (freed on every return path)
+    const size_t nd = sw.dang_at.size();
+    if (nd) {
+        HIPCHK(c, at.alloc(nd));
+        HIPCHK(c, src.alloc(nd));
+        HIPCHK(c, hipMemcpyAsync(at.get(), sw.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(src.get(), sw.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_sweep_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, (const int64_t *)at.get(),
+                           (const int32_t *)src.get(), w.d_ids.get(), w.d_cut.get(), w.d_vol.get(), (uint64_t)w.d_ids.size());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sweep result: ") + hipGetErrorString(e));
+    ev_collect(c);
+    w.entries = sw.cur;
+    w.valid = true;
+    memcpy(row_ptr, sw.row_ptr.data(), ((size_t)nq + 1) * 8);
+    if (rows && nq) memcpy(rows, sw.rows.data(), (size_t)nq * sizeof(fora_sweep_row));
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->entries = sw.entries_len; out->max_row = sw.max_row; out->thr_fix = sw.thr; out->edges = sw.edges;
+        out->batches = sw.batches; out->global_rows = sw.global_rows;
+        out->compact_ms = c->tm.sw_compact_ms; out->sort_ms = c->tm.sw_sort_ms; out->cut_ms = c->tm.sw_cut_ms;
+    }
+    return FORA_OK;
+}
+
 // refinement launches after k_walk_alloc: indexed walks, online walks, and the accumulate of their results
 void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t round, int nzh) {
     const WsPlan &p = c->ws.plan;
@@ -1590,7 +1853,7 @@ int ensure_query_workspace(fora_ctx *c, int slots, int k) {
 // into ids / scores (either may be null); the caller has checked 1 <= topk <= min(SEL_MAXK, n).
 int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int flags, double *ppr_d,
                  uint64_t *ppr_fix, uint64_t *residue_fix, fora_query_stats *stats, int topk = 0, int32_t *ids = nullptr,
-                 double *scores = nullptr, SparseRun *sp = nullptr) {
+                 double *scores = nullptr, SparseRun *sp = nullptr, SweepRun *sw = nullptr) {
     if (int rc = check_batch_args(c, sources, nq)) return rc;
     if (with_idx && !c->ix.have) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1621,10 +1884,14 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     const bool want_topk = topk > 0 && (ids || scores);
     const int nl = (int)live_src.size();
     if (sp) sp->row_ptr.assign((size_t)nq + 1, 0);
+    if (sw) sw->row_ptr.assign((size_t)nq + 1, 0);
     if (nl == 0) return FORA_OK;
-    int rc = ensure_query_workspace(c, nl, want_topk ? topk : 0);
+    int rc = FORA_OK;
+    if (sw) if ((rc = sweep_prepare_rank(c, nl))) return rc; // (ahead of the workspace: a batch size chosen from the free memory accounts for the block)
+    rc = ensure_query_workspace(c, nl, want_topk ? topk : 0);
     if (rc) return rc;
     const int per = even_batch(nl, c->ws.B);
+    if (sw) if ((rc = sweep_prepare(c, *sw, std::min(per, nl)))) return rc;
     if (sp) if ((rc = sparse_prepare(c, *sp, nq, std::min(per, nl), nl))) return rc;
     for (int b0 = 0; b0 < nl; b0 += per) {
         const int nb = std::min(per, nl - b0);
@@ -1632,6 +1899,7 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
         if ((rc = run_query_batch(c, live_src.data() + b0, nb, with_idx != 0, flags, sp))) return rc;
         if (stats) for (int i = 0; i < nb; i++) fill_stats(c, i, stats[at[i]]);
         if (sp) if ((rc = sparse_place(c, *sp, sources, nq, at, nb))) return rc;
+        if (sw) if ((rc = sweep_rows_of_batch(c, *sw, sources, nq, at, nb))) return rc;
         if (want_topk) {
             if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
             if ((rc = copy_topk_out(c, nb, topk, ids, scores, 0, at))) return rc;
@@ -2034,6 +2302,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_index(c);
     free_graph(c);
     free_sparse(c);
+    free_sweep(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
     for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2066,6 +2335,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_index(c);
     free_graph(c);
     free_sparse(c); // (rows of another graph)
+    free_sweep(c);
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
@@ -2354,6 +2624,49 @@ int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse fetch: ") + hipGetErrorString(err));
+    return FORA_OK;
+}
+
+// ---- sweep cut: local clustering over the rows of a query (the SWEEP CUT contract of include/fora_hip.h)
+int fora_hip_sweep_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t max_size, int64_t *row_ptr,
+                         fora_sweep_row *rows, fora_query_stats *stats, fora_sweep_stats *sw_out) {
+    if (!c) return FORA_E_ARG;
+    c->swp.valid = false; // the held profile ends here, whatever becomes of this call
+    c->swp.entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    return with_bucket_retry(c, [&] {
+        SweepRun run; // (a retried attempt starts from an empty one)
+        run.thr = thr; run.max_size = max_size;
+        run.rows.assign((size_t)std::max(nq, 0), sweep_row_of(0, 0, 0, 0, 0));
+        c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
+        if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, nullptr, &run)) return rc;
+        return sweep_finish(c, run, sources, nq, row_ptr, rows, sw_out);
+    });
+}
+
+int fora_hip_sweep_fetch(fora_ctx *c, int32_t *ids, uint64_t *cut, uint64_t *vol, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->swp.valid) return fail(c, FORA_E_ARG, "no sweep result is held");
+    if (cap < c->swp.entries) return fail(c, FORA_E_ARG, "cap is smaller than the held result");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t e = c->swp.entries;
+    bool on_device = false;
+    for (const void *p : {(const void *)ids, (const void *)cut, (const void *)vol})
+        if (p) if (int rc = sparse_dest(c, p, on_device)) return rc;
+    if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->swp.d_ids.get(), e * 4, hipMemcpyDefault, c->stream));
+    if (e && cut) HIPCHK(c, hipMemcpyAsync(cut, c->swp.d_cut.get(), e * 8, hipMemcpyDefault, c->stream));
+    if (e && vol) HIPCHK(c, hipMemcpyAsync(vol, c->swp.d_vol.get(), e * 8, hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FORA_OK;
+}
+
+int fora_hip_sweep_clear(fora_ctx *c) {
+    if (!c) return FORA_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_sweep(c);
     return FORA_OK;
 }
 

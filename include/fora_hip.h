@@ -132,6 +132,42 @@
  *     FORA_E_ARG.  No device memory for the ns x n accumulator block: FORA_E_NOMEM, the ctx still usable; the caller splits
  *     the call.
  *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched.
+ * SWEEP CUT (fora_hip_sweep_batch, fora_hip_sweep_fetch, fora_hip_sweep_clear): local clustering by a sweep over ppr / degree
+ * (Andersen-Chung-Lang), computed on the GPU from the rows of a query.  The query is fora_hip_query_batch's: same push, same
+ * walks, same batching, same dangling-source fast path, same fora_query_stats, same bits in the ppr slabs.  Only what is derived
+ * from a row is new.  Row i belongs to sources[i]; everything below is an integer.
+ *   - thr_fix = max(1, ceil(threshold * 2^62)), as for the sparse results: threshold <= 0 means 1, threshold > 1 or NaN is
+ *     FORA_E_ARG.  Support = {v : ppr_fix[i][v] >= thr_fix}; dangling nodes are ordinary members; a dangling source's row is the
+ *     single entry (s, 2^62).
+ *   - key(v) = floor(ppr_fix[v] / max(outdeg(v), 1)), a u64.  The sweep order sorts the support by key descending, ties by
+ *     ascending id; ids inside a row are distinct, so the order is strict and any correct sort gives the same bits.  The key is a
+ *     quotient and not a cross-multiplied compare of ppr_a * deg_b with ppr_b * deg_a: one u64 per node is what a radix or a
+ *     bitonic sort takes, and the floor loses less than one unit of 2^-62 of ppr per unit of degree.
+ *   - len = |support|; L = len if max_size <= 0, else min(len, max_size).  The profile of the row has L entries, order[0..L);
+ *     support nodes past L count as outside.
+ *   - for the prefix S_j = order[0..j], j < L: vol[j] = sum of outdeg(u) over S_j (the real out-degree: a dangling node adds 0);
+ *     cut[j] = number of CSR edges u -> v with u in S_j and v not in S_j (every stored duplicate counts once; the CSR holds no
+ *     self loops); den[j] = min(vol[j], nnz - vol[j]) with nnz = row_ptr[n] of fora_hip_set_graph (not m_attr).  On a symmetric
+ *     CSR cut / den is the usual conductance; on a directed one it is the out-cut over the out-volume.
+ *   - best = the j + 1 that minimises cut[j] / den[j] over the prefixes with den[j] > 0, compared exactly as
+ *     cut_a * den_b < cut_b * den_a on the 128-bit products, ties to the smaller prefix.  No prefix with den > 0 (an empty row, a
+ *     dangling source, a support of dangling nodes only, a support whose every prefix has vol == nnz): best = 0, cut = vol = den = 0, conductance = 1.0.
+ *     Otherwise cut, vol, den are those of the best prefix and conductance = (double)cut / (double)den: each integer converted
+ *     to f64, then one IEEE division.
+ *   - no bit depends on the batch size, on which batch a source lands in, on the push layout, on any knob the environment can
+ *     set, or on the options "sweep_lds_cap" (entries of a sort tile: a row that fits one is sorted by one workgroup in LDS, a
+ *     longer one takes the global tier; 0: every row does) and "sweep_rows" (rows whose rank maps are live at a time).
+ *   - the profile (order, cut, vol per row, rows in the caller's order, row_ptr = prefix sums of L) lives in device memory owned
+ *     by the ctx, outside the query workspace.  It stays valid until the next fora_hip_sweep_batch (whatever that call returns),
+ *     fora_hip_sweep_clear, fora_hip_set_graph or fora_hip_destroy; every other entry point leaves it untouched.  A sweep call
+ *     leaves a held sparse result, the walk index, the options and the FORA parameters untouched.
+ *   - fora_hip_sweep_fetch: any pointer may be NULL; each may be pageable host memory or device memory on the ctx's GPU.
+ *     cap < entries (row_ptr[nq]), or no held result: FORA_E_ARG and nothing is written.  The members of row i's best cluster
+ *     are ids[row_ptr[i] .. row_ptr[i] + rows[i].best).
+ *   - stats: entries = sum of len, max_row = the largest len, thr_fix, edges = out-edges scanned (sum of outdeg over the
+ *     profiles), batches, global_rows = rows sorted on the global tier, and the device times of the three stages.
+ *   - NULL ctx (answered without touching the GPU), NULL row_ptr, bad nq / sources, with_idx without an index: FORA_E_ARG.  No
+ *     device memory: FORA_E_NOMEM, nothing held, the ctx still usable.  nq == 0: FORA_OK, row_ptr[0] = 0, an empty result held.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -231,6 +267,13 @@ typedef struct {
     double combine_ms;     /* device time of the combine kernels, summed over the batches */
 } fora_seeds_stats;
 
+/* One row of a sweep (fora_hip_sweep_batch): the support's size and the best prefix (0: none). */
+typedef struct { int64_t len, best; uint64_t cut, vol, den; double conductance; } fora_sweep_row;
+/* What a sweep call ran. */
+typedef struct { uint64_t entries, max_row, thr_fix, edges; /* out-edges scanned */
+                 int32_t batches, global_rows; /* rows sorted on the global tier */
+                 double compact_ms, sort_ms, cut_ms; } fora_sweep_stats;
+
 /* ---- lifecycle ---------------------------------------------------------- */
 int fora_hip_device_count(void); /* usable HIP devices (0 when there is none) */
 int fora_hip_create(int device, fora_ctx **out);
@@ -314,6 +357,15 @@ int fora_hip_query_sparse_batch(fora_ctx *ctx, const int32_t *sources, int nq, i
 /* copies the held result; any of ids / vals / fix may be NULL; cap = entries each non-NULL array can take */
 int fora_hip_sparse_fetch(fora_ctx *ctx, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap);
 int fora_hip_sparse_clear(fora_ctx *ctx);
+
+/* ---- local clustering (the SWEEP CUT contract above): fora_hip_query_batch, then per row the sweep over ppr / degree and
+ * its best cut, all on the GPU.  The profile stays with the ctx until fetched or replaced. */
+int fora_hip_sweep_batch(fora_ctx *ctx, const int32_t *sources, int nq, int with_idx, double threshold,
+                         int64_t max_size, int64_t *row_ptr /*nq+1, required: prefix sums of L*/,
+                         fora_sweep_row *rows /*nq or NULL*/, fora_query_stats *stats /*nq or NULL*/,
+                         fora_sweep_stats *sw /*or NULL*/);
+int fora_hip_sweep_fetch(fora_ctx *ctx, int32_t *ids /*sweep order*/, uint64_t *cut, uint64_t *vol, uint64_t cap);
+int fora_hip_sweep_clear(fora_ctx *ctx);
 
 /* ---- SSPPR on seed sets (the SEED SETS contract above; the reference personalises on one node only).  ns sets in CSR form:
  * set_ptr ns + 1 entries, seeds / weights set_ptr[ns] entries (weights NULL: uniform).  Any output may be NULL: ppr_out /
