@@ -140,6 +140,7 @@ def load(path=None):
 
 
 TEST_LIB = os.path.join(_HERE, "libfora_hip_test.so")  # -DFORA_TEST_PATHS=1: threshold rounds / bounded deferral compiled in
+TEST_SYMBOLS = ["fora_hip_test_sweep_rows", "fora_hip_test_sweep_scan"]  # the TEST ENTRY POINTS of include/fora_hip.h: TEST_LIB only
 
 
 def _p(a):
@@ -350,6 +351,41 @@ class Engine:
 
     def sweep_clear(self):
         self._chk(self._lib.fora_hip_sweep_clear(self._ctx))
+
+    # ---- the TEST ENTRY POINTS of include/fora_hip.h: Engine(lib=TEST_LIB) only
+    def _test_entry(self, name):
+        if not hasattr(self._lib, name):
+            raise ForaError(-1, f"{name} is in libfora_hip_test.so only: Engine(lib=capi.TEST_LIB)")
+        return getattr(self._lib, name)
+
+    def test_sweep_rows(self, rows_fix, threshold=None, max_size=0, want_profile=True):
+        """sweep() over caller-made rows ([nq, n] fixed-point words) instead of a query's (fora_hip_test_sweep_rows): the
+        same dict, without "stats"."""
+        fix = np.ascontiguousarray(rows_fix, dtype=np.uint64)
+        if fix.ndim != 2 or fix.shape[1] != self.n:
+            raise ValueError("rows_fix must be [nq, n]")
+        nq = fix.shape[0]
+        rows = (SweepRow * max(1, nq))()
+        sw = SweepStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._test_entry("fora_hip_test_sweep_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(thr), C.c_int64(int(max_size)),
+                                                               _p(row_ptr), rows, C.byref(sw)))
+        out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=nq).copy(), "sweep": sw.as_dict()}
+        if want_profile:
+            out["ids"], out["cut"], out["vol"] = self.sweep_fetch(int(row_ptr[-1]))
+        return out
+
+    def test_sweep_scan(self, diff, vol, nnz):
+        """k_sweep_scan on one row (fora_hip_test_sweep_scan): diff (int64 differences of the cuts) and vol (uint64 per
+        position) of one length.  Returns (cut uint64 [L], vol uint64 [L], a dict: len, best, cut, vol, den, edges)."""
+        cut = np.array(diff, dtype=np.int64)
+        v = np.array(vol, dtype=np.uint64)
+        if cut.ndim != 1 or cut.shape != v.shape:
+            raise ValueError("diff and vol must be one-dimensional and of one length")
+        out = np.zeros(6, dtype=np.uint64)
+        self._chk(self._test_entry("fora_hip_test_sweep_scan")(self._ctx, _p(cut), _p(v), C.c_int64(cut.size), C.c_uint64(int(nnz)), _p(out)))
+        return cut.view(np.uint64), v, dict(zip(("len", "best", "cut", "vol", "den", "edges"), (int(x) for x in out)))
 
     def local_cluster(self, sources, with_idx=False, threshold=None, max_size=0):
         """The cluster of least conductance around every source: one int32 id array per source, in sweep order (empty when

@@ -2670,6 +2670,73 @@ int fora_hip_sweep_clear(fora_ctx *c) {
     return FORA_OK;
 }
 
+#if FORA_TEST_PATHS
+// ---- TEST ENTRY POINTS (include/fora_hip.h; libfora_hip_test.so only): chosen inputs in front of the sweep's own host
+// functions and kernels.
+// fora_hip_sweep_batch's frame with the caller's rows in the ppr slabs instead of a query batch's: row i takes slot i - b0 of
+// its batch, no row is skipped (sweep_skip_dangling never reads the sources it is handed).
+int fora_hip_test_sweep_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t max_size, int64_t *row_ptr,
+                             fora_sweep_row *rows, fora_sweep_stats *sw_out) {
+    if (!c) return FORA_E_ARG;
+    c->swp.valid = false;
+    c->swp.entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    return with_bucket_retry(c, [&] {
+        SweepRun run;
+        run.thr = thr; run.max_size = max_size;
+        run.rows.assign((size_t)std::max(nq, 0), sweep_row_of(0, 0, 0, 0, 0));
+        c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
+        if (int rc = check_batch_args(c, reinterpret_cast<const int32_t *>(rows_fix), nq, "row")) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        const uint64_t n = (uint64_t)c->g.n;
+        run.row_ptr.assign((size_t)nq + 1, 0);
+        if (nq) {
+            if (int rc = sweep_prepare_rank(c, nq)) return rc;
+            if (int rc = ensure_query_workspace(c, nq, 0)) return rc;
+            const int per = even_batch(nq, c->ws.B);
+            if (int rc = sweep_prepare(c, run, std::min(per, nq))) return rc;
+            std::vector<int> at((size_t)nq);
+            for (int i = 0; i < nq; i++) at[(size_t)i] = i;
+            for (int b0 = 0; b0 < nq; b0 += per) {
+                const int nb = std::min(per, nq - b0);
+                if ((uint64_t)nb * n > c->ws.d_ppr.size()) return fail(c, FORA_E_HIP, "test_sweep_rows: the batch does not fit the ppr slabs");
+                HIPCHK(c, hipMemcpyAsync(c->ws.d_ppr.get(), rows_fix + (uint64_t)b0 * n, (uint64_t)nb * n * 8, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+                if (int rc = sweep_rows_of_batch(c, run, nullptr, nq, at.data() + b0, nb)) return rc;
+            }
+        }
+        return sweep_finish(c, run, nullptr, nq, row_ptr, rows, sw_out);
+    });
+}
+
+// k_sweep_scan on one row in buffers of this call's own: diff_cut / vol as k_sweep_scatter<true> and k_sweep_cut leave them
+int fora_hip_test_sweep_scan(fora_ctx *c, int64_t *diff_cut, uint64_t *vol, int64_t L, uint64_t nnz, uint64_t *out6) {
+    if (!c) return FORA_E_ARG;
+    if (L < 0 || L > 0x7FFFFFFF || (L && (!diff_cut || !vol)) || !out6) return fail(c, FORA_E_ARG, "test_sweep_scan: bad length or null array");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t len = (size_t)L;
+    DevBuf<uint64_t> d_cut, d_vol, d_desc; DevBuf<SweepRowOut> d_out;
+    const SweepRowDesc rd{0, 0, (uint32_t)L, 0, (uint32_t)L, 0};
+    static_assert(sizeof(SweepRowDesc) % 8 == 0, "uploaded as u64 words");
+    HIPCHK(c, d_cut.upload(reinterpret_cast<const uint64_t *>(diff_cut), len, 1));
+    HIPCHK(c, d_vol.upload(vol, len, 1));
+    HIPCHK(c, d_desc.upload(reinterpret_cast<const uint64_t *>(&rd), sizeof(rd) / 8));
+    HIPCHK(c, d_out.alloc(1));
+    hipLaunchKernelGGL(k_sweep_scan, dim3(1), dim3(BLOCK), 0, c->stream, (const SweepRowDesc *)d_desc.get(), 0u, d_cut.get(), d_vol.get(), (uint64_t)len, nnz, d_out.get());
+    SweepRowOut o;
+    HIPCHK(c, hipMemcpyAsync(&o, d_out.get(), sizeof(o), hipMemcpyDeviceToHost, c->stream));
+    if (len) HIPCHK(c, hipMemcpyAsync(diff_cut, d_cut.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
+    if (len) HIPCHK(c, hipMemcpyAsync(vol, d_vol.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("test_sweep_scan: ") + hipGetErrorString(e));
+    out6[0] = (uint64_t)o.len; out6[1] = (uint64_t)o.best; out6[2] = o.cut; out6[3] = o.vol; out6[4] = o.den; out6[5] = o.edges;
+    return FORA_OK;
+}
+#endif // FORA_TEST_PATHS
+
 int fora_hip_sparse_clear(fora_ctx *c) {
     if (!c) return FORA_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));

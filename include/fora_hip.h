@@ -465,6 +465,21 @@ int fora_hip_get_timing(fora_ctx *ctx, fora_timing *out);
  * fora_hip_reset_timing; [0..15] k_pushq_bin, [16..31] k_accum.  All zero in a product build. */
 int fora_hip_get_stamps(fora_ctx *ctx, uint64_t *out32);
 
+/* ---- TEST ENTRY POINTS: in libfora_hip_test.so (-DFORA_TEST_PATHS=1) only, never in libfora_hip.so, and so not declared
+ * here.  They put chosen inputs in front of the sweep's own host functions and kernels; nothing is computed a second way.
+ *
+ *   int fora_hip_test_sweep_rows(fora_ctx *ctx, const uint64_t *rows_fix (nq * n words), int nq, double threshold,
+ *                                int64_t max_size, int64_t *row_ptr (nq + 1, required), fora_sweep_row *rows (nq or NULL),
+ *                                fora_sweep_stats *sw (or NULL));
+ *     fora_hip_sweep_batch with the caller's rows in place of a query's: the rows are copied into the ppr slabs batch by batch
+ *     (fora_hip_set_batch is honoured) and compacted, sorted and swept as a batch's own rows are.  Every row takes a slot (a
+ *     row is words, not a source: none is "dangling").  Leaves a held profile for fora_hip_sweep_fetch.
+ *
+ *   int fora_hip_test_sweep_scan(fora_ctx *ctx, int64_t *diff_cut (L, in: differences, out: cuts), uint64_t *vol (L, in:
+ *                                per position, out: prefix sums), int64_t L, uint64_t nnz, uint64_t *out6);
+ *     k_sweep_scan on one row of length L under the denominator min(vol, nnz - vol); out6 = len, best, cut, vol, den, edges of
+ *     the row it wrote.  Uses buffers of its own: a held profile is left alone. */
+
 #ifdef __cplusplus
 }
 #endif

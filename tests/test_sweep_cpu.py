@@ -1,6 +1,8 @@
 """The SWEEP CUT contract (include/fora_hip.h) on the CPU: tests/sweep_ref.py, the Python twin the GPU tests compare with,
 against a brute force over set membership; the cases without a best prefix; the tie rule; the recovery of a planted block on
-rows of the oracle's twin; and the C ABI's new symbols and structs."""
+rows of the oracle's twin; the C ABI's new symbols and structs; and the generators of tests/test_sweep_shapes_gpu.py's inputs
+(tie-heavy and hubs-first rows, rings, pairs, inputs of k_sweep_scan), each against the brute force and for the property the
+GPU test relies on.  The two test-only entry points must be in libfora_hip_test.so and nowhere else."""
 import ctypes
 import os
 import re
@@ -30,17 +32,6 @@ def _random_graph(rng, n, dup=True):
     return row_ptr, col
 
 
-def _random_row(rng, n, row_ptr):
-    """a sparse row with equal keys on several ids: words of the form q * max(deg, 1) (+ a remainder below deg)"""
-    deg = np.maximum(np.diff(row_ptr), 1)
-    row = np.zeros(n, dtype=np.uint64)
-    on = rng.random(n) < 0.6
-    q = rng.integers(1, 6, size=n).astype(np.uint64) << np.uint64(40)   # few distinct quotients: ties by id
-    rem = rng.integers(0, 1 << 20, size=n).astype(np.uint64) % deg.astype(np.uint64)
-    row[on] = (q * deg.astype(np.uint64) + rem)[on]
-    return row
-
-
 def _same(a, b):
     for k in ("len", "order", "cut", "vol", "best", "cut_best", "vol_best", "den"):
         assert a[k] == b[k], k
@@ -55,7 +46,7 @@ def test_twin_equals_brute_force(seed):
     deg = np.diff(row_ptr)
     assert (deg == 0).any() and any(col[row_ptr[u]] == col[row_ptr[u] + 1] for u in range(n) if deg[u] >= 2)
     for _ in range(3):
-        row = _random_row(rng, n, row_ptr)
+        row = R.random_row(rng, n, row_ptr)
         full = R.sweep_row(row, row_ptr, col, 1)
         keys = [int(row[v]) // max(int(deg[v]), 1) for v in full["order"]]
         assert keys == sorted(keys, reverse=True) and len(set(keys)) < len(keys)          # equal keys ...
@@ -113,6 +104,123 @@ def test_conductance_ties_go_to_the_smaller_prefix():
     assert r["cut"] == [1, 3] and r["vol"] == [1, 3] and r["best"] == 1 and r["conductance"] == 1.0
 
 
+def test_generators_equal_brute_force():
+    """every row / graph generator of sweep_ref.py the GPU shape tests use, at a size the brute force takes"""
+    rng = np.random.Generator(np.random.PCG64(7200))
+    row_ptr, col = _random_graph(rng, 120)
+    deg = np.diff(row_ptr)
+    # hubs first: degree descending, ties by id, full support
+    row = R.hubs_first_row(row_ptr)
+    full = R.sweep_row(row, row_ptr, col, 1)
+    assert full["order"] == sorted(range(120), key=lambda v: (-int(deg[v]), v))
+    _same(full, R.sweep_brute(row, row_ptr, col, 1))
+    _same(R.sweep_row(row, row_ptr, col, 1, 17), R.sweep_brute(row, row_ptr, col, 1, 17))
+    # the tie-heavy row and its cut-down copies
+    row = R.tie_heavy_row(120, row_ptr, 7201)
+    assert len(set(R.keys_in_order(row, row_ptr, R.sweep_row(row, row_ptr, col, 1)["order"]))) <= 5
+    for length in (1, 40):
+        cutdown = R.row_of_length(row, length)
+        assert int((cutdown > 0).sum()) == length and (cutdown[cutdown > 0] == row[cutdown > 0]).all()
+        _same(R.sweep_row(cutdown, row_ptr, col, 1), R.sweep_brute(cutdown, row_ptr, col, 1))
+    # words at the edges of the key's range
+    row, zero = R.edge_words_row(120, row_ptr, 7202, count=12)
+    r = R.sweep_row(row, row_ptr, col, 1)
+    _same(r, R.sweep_brute(row, row_ptr, col, 1))
+    keys = R.keys_in_order(row, row_ptr, r["order"])
+    assert keys[0] == FIX_ONE and deg[r["order"][0]] == 1
+    assert r["order"][-zero.size:] == zero.tolist() and keys[-zero.size:] == [0] * zero.size and keys[-zero.size - 1] == 1
+    above = {k for k in keys if k & 0xFFFFFFFF == 12345}
+    below = {k for k in keys if k >> 33 == 9}
+    assert len(above) >= 3 and len({k >> 33 for k in above}) == len(above) and len(below) >= 6 and len({k >> 32 for k in below}) == 1
+    # ring, pairs, ring with chords and a hub
+    for n, rp, cl, row in (R.ring_graph(9), R.ring_graph(12), R.pair_graph(5)):
+        r = R.sweep_row(row, rp, cl, 1)
+        assert r["order"] == list(range(n))
+        _same(r, R.sweep_brute(row, rp, cl, 1))
+    n, rp, cl = R.chord_ring_graph(n=90, chords=12, hub_deg=40, seed=7203)
+    d = np.diff(rp)
+    assert d[0] >= 42 and (d >= 2).all() and int(rp[-1]) == cl.size and all(cl[rp[u]:rp[u + 1]].tolist() == sorted(set(cl[rp[u]:rp[u + 1]].tolist())) for u in range(n))
+    assert all((u + 1) % n in cl[rp[u]:rp[u + 1]] and (u - 1) % n in cl[rp[u]:rp[u + 1]] for u in range(n))
+    row = R.hubs_first_row(rp)
+    _same(R.sweep_row(row, rp, cl, 1), R.sweep_brute(row, rp, cl, 1))
+    assert R.minimisers([3, 1, 1, 0], [1, 2, 4, 6], 6) == [1, 2] and R.minimisers([0], [0], 5) == []
+    assert R.tied_boundaries([5, 5, 4, 4, 4, 3], 2) == (1, 2)
+
+
+RING_TIES = {9: (3, 4), 513: (255, 256), 2049: (1023, 1024), 8193: (4095, 4096)}
+
+
+def test_rings_and_pairs_have_tied_minimisers():
+    """what tests/test_sweep_shapes_gpu.py relies on: two adjacent minimising prefixes either side of a lane, a wave, a scan
+    step and position 4096; the twin takes the smaller"""
+    for m, (a, b) in RING_TIES.items():
+        n, rp, cl, row = R.ring_graph(m)
+        r = R.sweep_row(row, rp, cl, 1)
+        assert set(r["cut"][:-1]) == {2} and r["cut"][-1] == 0 and r["vol"] == [2 * (j + 1) for j in range(m)]
+        assert R.minimisers(r["cut"], r["vol"], int(rp[-1])) == [a, b] and r["best"] == a + 1
+    for m, unit in ((9, 4), (513, 64), (2049, 1024), (8193, 4096)):   # a lane's positions, a wave's lanes, a scan step, the tile
+        assert RING_TIES[m][0] // unit + 1 == RING_TIES[m][1] // unit
+    n, rp, cl, row = R.pair_graph(3000)
+    r = R.sweep_row(row, rp, cl, 1)
+    assert R.minimisers(r["cut"], r["vol"], int(rp[-1])) == list(range(1, 5999, 2)) and r["best"] == 2 and r["conductance"] == 0.0
+
+
+def test_long_rows_have_the_ties_and_classes_the_gpu_tests_need(small_dangling):
+    g = small_dangling
+    nnz = int(g.row_ptr[-1])
+    assert (g.deg == 0).any()
+    mins = []
+    for seed in R.TIE_SEEDS:
+        row = R.tie_heavy_row(g.n, g.row_ptr, seed)
+        r = R.sweep_row(row, g.row_ptr, g.col, 1)
+        keys = R.keys_in_order(row, g.row_ptr, r["order"])
+        assert r["len"] > 6 * 4096 and len(set(keys)) == 5
+        tied = [R.tied_boundaries(keys, s) for s in (64, 1024, 4096)]
+        print(seed, r["len"], tied)
+        assert tied[1] == (24, 24) and tied[2] == (6, 6) and tied[0][0] >= tied[0][1] - 1
+        if seed == R.TIE_SEEDS[0]:
+            assert tied[0][0] == tied[0][1] >= 398
+        mins.append(len(R.minimisers(r["cut"], r["vol"], nnz)))
+    assert max(mins) >= 2   # a long row with equal conductances, too
+    row = R.hubs_first_row(g.row_ptr)
+    order = R.sweep_row(row, g.row_ptr, g.col, 1, 256)["order"]
+    d = g.deg[order]
+    assert (int((d >= 256).sum()), int(((d >= 64) & (d < 256)).sum())) == R.HUB_CLASSES
+
+
+@pytest.mark.parametrize("L", R.SCAN_LENGTHS)
+def test_scan_cases_plant_what_they_say(L):
+    rng = np.random.Generator(np.random.PCG64(7300 + L))
+    seen = 0
+    for kind in R.SCAN_KINDS:
+        for p, q in R.SCAN_PLACES.values():
+            if q >= L:
+                continue
+            diff, vol, nnz, winner = R.scan_planted(rng, L, kind, p, q)
+            ref = R.scan_ref(diff, vol, nnz)
+            assert diff.dtype == np.int64 and vol.dtype == np.uint64 and len(diff) == len(vol) == L
+            assert R.minimisers(ref["cut"], ref["vol"], nnz) == ([p, q] if kind == "tie" else [winner]) and ref["best"] == winner + 1
+            a, b = (ref["cut"][p], ref["vol"][p]), (ref["cut"][q], ref["vol"][q])
+            left, right = a[0] * b[1], b[0] * a[1]
+            assert left >> 64 and right >> 64
+            if kind == "tie":
+                assert left == right and a != b
+            elif kind.startswith("high"):
+                assert left >> 64 == right >> 64 and left != right
+            else:
+                assert ((left & (2 ** 64 - 1)) < (right & (2 ** 64 - 1))) != (left < right)
+            seen += 1
+    assert seen == {1: 0, 4: 5, 5: 5, 1024: 15, 1025: 20, 5000: 25}[L]
+    # the background alone: denominators from both sides of nnz / 2, none at the last prefix; and one with slack
+    diff, vol, nnz = R.scan_plain(rng, L)
+    ref = R.scan_ref(diff, vol, nnz)
+    assert ref["edges"] == nnz and (ref["best"] == 0) == (L == 1)
+    assert R.scan_ref(*R.scan_plain(rng, L, 12345))["best"] > 0
+    # no prefix with a denominator
+    ref = R.scan_ref(np.ones(L, np.int64), np.zeros(L, np.uint64), 77)
+    assert (ref["best"], ref["cut_best"], ref["vol_best"], ref["den"], ref["edges"]) == (0, 0, 0, 0, 0) and ref["cut"] == list(range(1, L + 1))
+
+
 def test_planted_block_is_recovered_on_twin_rows(oracle):
     n, row_ptr, col, block = R.planted_graph()
     assert n == 1999 and block.size == 300
@@ -158,3 +266,28 @@ def test_c_abi_declares_exports_and_binds_the_sweep():
     assert lib.fora_hip_sweep_fetch(None, None, None, None, 0) == -1
     lib.fora_hip_sweep_clear.argtypes = [ctypes.c_void_p]
     assert lib.fora_hip_sweep_clear(None) == -1
+
+
+def test_test_entry_points_are_in_the_test_library_only():
+    """the TEST ENTRY POINTS of include/fora_hip.h: exported by libfora_hip_test.so, absent from the product library, from
+    its symbol list and from the header's declarations"""
+    import __graft_entry__
+    __graft_entry__.build()
+    from fora_amd import capi
+    assert capi.TEST_SYMBOLS == ["fora_hip_test_sweep_rows", "fora_hip_test_sweep_scan"]
+    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
+    assert "TEST ENTRY POINTS" in hdr
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    for name in capi.TEST_SYMBOLS:
+        assert hasattr(test, name) and not hasattr(product, name), name
+        assert name not in capi.SYMBOLS and name not in code and name in hdr
+    for name in capi.SYMBOLS:
+        assert hasattr(test, name), name
+    # NULL ctx: answered without touching the GPU
+    test.fora_hip_test_sweep_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int64] + [ctypes.c_void_p] * 3
+    assert test.fora_hip_test_sweep_rows(None, None, 0, 0.0, 0, None, None, None) == -1
+    test.fora_hip_test_sweep_scan.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p]
+    assert test.fora_hip_test_sweep_scan(None, None, None, 0, 0, None) == -1
+    for meth in ("test_sweep_rows", "test_sweep_scan"):
+        assert callable(getattr(capi.Engine, meth))
