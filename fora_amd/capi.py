@@ -21,6 +21,7 @@ SYMBOLS = [
     "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
     "fora_hip_query_seeds_batch",
     "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
+    "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -274,11 +275,17 @@ class Engine:
         thr = 1.0 / self.n if threshold is None else float(threshold)
         self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
                                                         _p(row_ptr), st, C.byref(sp)))
-        e = int(sp.entries)
+        row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(sp.entries), want_fix, device, "query_sparse")
+        out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
+        return out + (self._stats(st, nq), sp.as_dict())
+
+    def _sparse_result(self, row_ptr, e, want_fix, device, who):
+        """The held sparse result of e entries through fora_hip_sparse_fetch: (row_ptr, ids, vals, fix or None) as numpy
+        arrays, or with device as torch tensors on the context's GPU."""
         if device:
             import torch
             if not torch.cuda.is_available():
-                raise RuntimeError("query_sparse(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
+                raise RuntimeError(f"{who}(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
                                    "HIP runtime: import torch before the first Engine is created")
             dev = torch.device("cuda", self.device)
             ids = torch.empty(e, dtype=torch.int32, device=dev)
@@ -293,8 +300,7 @@ class Engine:
             vals = np.zeros(e, dtype=np.float64)
             fix = np.zeros(e, dtype=np.uint64) if want_fix else None
             self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), C.c_uint64(e)))
-        out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
-        return out + (self._stats(st, nq), sp.as_dict())
+        return row_ptr, ids, vals, fix
 
     def sparse_fetch(self, ids=None, vals=None, fix=None, cap=0):
         """fora_hip_sparse_fetch into caller-made numpy arrays (any of them None): the held result, again."""
@@ -508,12 +514,9 @@ class Engine:
                                                          C.c_double(rmax_scale), _p(est), _p(fix), st, C.byref(bwd)))
         return est, fix, self._stats(st, nq), bwd.as_dict()
 
-    def query_seeds(self, sets, weights=None, with_idx=False, k=0, want_ppr=False, want_fix=True):
-        """PPR restarting on weighted seed sets (fora_hip_query_seeds_batch): one row per set, the rows of the seeds combined
-        on the GPU.  sets: a LIST of int sequences, one per set, or a 2-TUPLE (set_ptr, seeds) in CSR form -- a tuple of two
-        is always read as that pair, so two sets go in a list; weights: the same shape (a list of float sequences, or one
-        flat array beside `seeds`), None: uniform.  Returns a dict: fix (raw u64 at 2^62 [ns,n] or None), ppr
-        (f64 [ns,n] or None), ids / scores ([ns,k] or None), row_sum_fix (u64 [ns]), stats (a dict)."""
+    @staticmethod
+    def _seed_sets(sets, weights):
+        """(set_ptr int64, seeds int32, weights float64 or None) of the sets / weights arguments of query_seeds."""
         flat = isinstance(sets, tuple) and len(sets) == 2
         if flat:
             set_ptr = np.ascontiguousarray(sets[0], dtype=np.int64)
@@ -530,6 +533,15 @@ class Engine:
             w = np.ascontiguousarray(w, dtype=np.float64)
             if w.size != seeds.size:
                 raise ValueError("weights must have the shape of the seeds")
+        return set_ptr, seeds, w
+
+    def query_seeds(self, sets, weights=None, with_idx=False, k=0, want_ppr=False, want_fix=True):
+        """PPR restarting on weighted seed sets (fora_hip_query_seeds_batch): one row per set, the rows of the seeds combined
+        on the GPU.  sets: a LIST of int sequences, one per set, or a 2-TUPLE (set_ptr, seeds) in CSR form -- a tuple of two
+        is always read as that pair, so two sets go in a list; weights: the same shape (a list of float sequences, or one
+        flat array beside `seeds`), None: uniform.  Returns a dict: fix (raw u64 at 2^62 [ns,n] or None), ppr
+        (f64 [ns,n] or None), ids / scores ([ns,k] or None), row_sum_fix (u64 [ns]), stats (a dict)."""
+        set_ptr, seeds, w = self._seed_sets(sets, weights)
         ns = set_ptr.size - 1
         st = SeedsStats()
         ppr = np.zeros((ns, self.n), dtype=np.float64) if want_ppr else None
@@ -540,6 +552,52 @@ class Engine:
         self._chk(self._lib.fora_hip_query_seeds_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
                                                        _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), _p(sums), C.byref(st)))
         return {"fix": fix, "ppr": ppr, "ids": ids, "scores": sc, "row_sum_fix": sums, "stats": st.as_dict()}
+
+    def query_seeds_sparse(self, sets, weights=None, with_idx=False, threshold=None, want_fix=False, device=False):
+        """query_seeds() with the rows kept sparse (fora_hip_seeds_sparse_batch + fora_hip_sparse_fetch): node v of set row g
+        is kept iff the row's word -- the sum over the set's seeds -- is >= max(1, ceil(threshold * 2^62)); threshold=None:
+        1 / n.  sets / weights as for query_seeds.  Returns a dict: row_ptr, ids, vals (a CSR over the sets, ids ascending
+        inside a row), fix (the raw words, with want_fix, else None), row_sum_fix (u64 [ns], sums over the WHOLE rows), stats
+        (the seeds stats) and sparse (a dict).  device as for query_sparse: torch tensors written on the context's GPU,
+        usable with to_torch_csr."""
+        set_ptr, seeds, w = self._seed_sets(sets, weights)
+        ns = set_ptr.size - 1
+        st = SeedsStats()
+        sp = SparseStats()
+        row_ptr = np.zeros(ns + 1, dtype=np.int64)
+        sums = np.zeros(ns, dtype=np.uint64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
+                                                        C.c_double(thr), _p(row_ptr), _p(sums), C.byref(st), C.byref(sp)))
+        row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(row_ptr[-1]), want_fix, device, "query_seeds_sparse")
+        return {"row_ptr": row_ptr, "ids": ids, "vals": vals, "fix": fix, "row_sum_fix": sums, "stats": st.as_dict(),
+                "sparse": sp.as_dict()}
+
+    def sweep_seeds(self, sets, weights=None, with_idx=False, threshold=None, max_size=0, want_profile=False, device=False):
+        """Seed-set expansion (fora_hip_seeds_sweep_batch): sweep() over the rows of query_seeds instead of single sources'.
+        sets / weights as for query_seeds, the rest and the returned dict as for sweep, "stats" being the seeds stats."""
+        set_ptr, seeds, w = self._seed_sets(sets, weights)
+        ns = set_ptr.size - 1
+        st = SeedsStats()
+        rows = (SweepRow * max(1, ns))()
+        sw = SweepStats()
+        row_ptr = np.zeros(ns + 1, dtype=np.int64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_seeds_sweep_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
+                                                       C.c_double(thr), C.c_int64(int(max_size)), _p(row_ptr), rows, C.byref(st),
+                                                       C.byref(sw)))
+        out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=ns).copy(),
+               "stats": st.as_dict(), "sweep": sw.as_dict()}
+        if want_profile:
+            out["ids"], out["cut"], out["vol"] = self.sweep_fetch(int(row_ptr[-1]), device=device)
+        return out
+
+    def local_cluster_seeds(self, sets, weights=None, with_idx=False, threshold=None, max_size=0):
+        """The cluster of least conductance around every seed set: one int32 id array per set, in sweep order (empty when no
+        prefix has a denominator: a set of dangling seeds only)."""
+        r = self.sweep_seeds(sets, weights=weights, with_idx=with_idx, threshold=threshold, max_size=max_size, want_profile=True)
+        rp, ids = r["row_ptr"], r["ids"]
+        return [ids[int(rp[i]):int(rp[i]) + int(r["rows"][i]["best"])].copy() for i in range(len(r["rows"]))]
 
     # ---- stage hooks
     def bwdpush(self, targets, rmax):

@@ -89,6 +89,7 @@ struct Tunables {
     int64_t sweep_lds_cap = SW_TILE_MAX; // sweep cut (fora_hip_sweep_batch): entries of a sort tile, rounded down to a power of two (at most SW_TILE_MAX); a row that fits one is sorted by one workgroup in LDS, a longer one takes the global tier; 0: every row does, every step in global memory.  Same bits for every value
     int64_t sweep_rows = 0;      // ... rows whose rank maps are live at a time (the rank block holds that many slabs of n words); 0: 256.  Same bits for every value
     int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
+    int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
     {"direct", &Tunables::direct, true}, {"force_wide", &Tunables::force_wide, true}, {"pass_bins", &Tunables::pass_bins, true},
@@ -99,7 +100,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"profile", &Tunables::profile, false}, {"grid", &Tunables::grid, false},
     {"bwd_lds_cap", &Tunables::bwd_lds_cap, false}, {"bwd_chunk", &Tunables::bwd_chunk, false},
     {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
-    {"seeds_dedup", &Tunables::seeds_dedup, false},
+    {"seeds_dedup", &Tunables::seeds_dedup, false}, {"seeds_rows", &Tunables::seeds_rows, false},
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
@@ -1363,11 +1364,12 @@ int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done
     return FORA_OK;
 }
 
-// count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out)
-int sparse_count(fora_ctx *c, const SparseRun &sp, int nb) {
+// count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out).
+// rows: where the nb rows lie, n words each, 16-byte aligned (null: the workspace's ppr slabs)
+int sparse_count(fora_ctx *c, const SparseRun &sp, int nb, const uint64_t *rows = nullptr) {
     HIPCHK(c, hipMemsetAsync(c->sp.d_tot.get(), 0, (size_t)nb * 4, c->stream));
     EvSpan ev(c, EV_SP_COMPACT);
-    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
+    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
                        c->sp.d_counts.get(), c->sp.d_tot.get());
     ev.end();
     HIPCHK(c, hipMemcpyAsync(c->sp.h_tot.get(), c->sp.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1386,8 +1388,8 @@ void sparse_skip_dangling(SparseRun &sp, const int32_t *sources, int upto) {
 }
 
 // write pass of the batch just closed (slot i: row at[i] of the caller); the slabs hold it until the next batch starts
-// on the same stream
-int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, const int *at, int nb) {
+// on the same stream.  rows: as for sparse_count
+int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, const int *at, int nb, const uint64_t *rows = nullptr) {
     std::vector<int64_t> base((size_t)nb);
     const uint64_t keep = sp.cur; // (dangling rows are written at the end: nothing of them to keep)
     for (int i = 0; i < nb; i++) {
@@ -1402,7 +1404,7 @@ int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, con
     HIPCHK(c, hipMemcpyAsync(c->sp.d_base.get() + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
     EvSpan ev(c, EV_SP_COMPACT);
-    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
+    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
                        (const uint32_t *)c->sp.d_counts.get(), (const int64_t *)(c->sp.d_base.get() + sp.live_done), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
     sp.live_done += nb;
     return FORA_OK;
@@ -1539,11 +1541,12 @@ void sweep_skip_dangling(SweepRun &sw, const int32_t *sources, int upto) {
     }
 }
 
-// the batch just closed (slot i: row at[i] of the caller): compaction, sort, and chunk by chunk the cut count and the scan
-int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, const int *at, int nb) {
+// the batch just closed (slot i: row at[i] of the caller): compaction, sort, and chunk by chunk the cut count and the scan.
+// rows: where the nb rows lie, n words each, 16-byte aligned (null: the workspace's ppr slabs)
+int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, const int *at, int nb, const uint64_t *rows = nullptr) {
     SweepResult &w = c->swp;
     const uint32_t n = (uint32_t)c->g.n;
-    const uint64_t *ppr = c->ws.d_ppr.get();
+    const uint64_t *ppr = rows ? rows : c->ws.d_ppr.get();
     EvSpan ev(c);
     // count pass
     HIPCHK(c, hipMemsetAsync(w.d_tot.get(), 0, (size_t)nb * 4, c->stream));
@@ -1956,9 +1959,15 @@ int seed_combine(fora_ctx *c, const SeedBatch &b) {
     return FORA_OK;
 }
 
-int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
-                     double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, uint64_t *row_sum_fix_out,
-                     fora_seeds_stats *st) {
+// What the three entry points over seed sets share: the arguments checked, the weights at 2^-62, the slots, the accumulator
+// block, the batches with their combines and the dangling seeds' terms.  It leaves the finished block acc[ns][n] (c->sd.d_acc)
+// on the stream -- a set row is complete only here, after the last batch -- and the counts of *st in sc.  ns == 0: FORA_OK and
+// nothing done.  k: of a top-k the caller will take from the workspace's select (0: none); sweep: the sweep's rank block is
+// wanted too (after the accumulator block and ahead of the workspace, so that a batch size chosen from the free memory
+// accounts for both).
+struct SeedCounts { uint64_t seeds = 0, distinct = 0, queries = 0, dangling = 0; int batches = 0; };
+int seeds_accumulate(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                     int k, bool want_topk, bool sweep, fora_seeds_stats *st, SeedCounts &sc) {
     if (int rc = check_batch_args(c, nullptr, 0)) return rc;
     if (ns < 0) return fail(c, FORA_E_ARG, "bad sets: negative count");
     if (st) memset(st, 0, sizeof(*st));
@@ -2019,7 +2028,6 @@ int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
             uses.push_back(SeedUse{(uint32_t)g, slot, wfix[(size_t)j]});
         }
     const int nl = (int)slot_src.size();
-    const bool want_topk = k > 0 && (ids || scores);
     // The accumulator block, ahead of the workspace: a batch size chosen from the free memory then accounts for it.  No room
     // beside a workspace that is already there: that one goes, and the call plans a new one in what the block leaves.
     const uint64_t cells = (uint64_t)ns * n;
@@ -2036,6 +2044,7 @@ int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
     HIPCHK(c, c->sd.d_acc.zero(c->stream, cells));
     int rc = FORA_OK;
     int nbatch = 0;
+    if (sweep) if ((rc = sweep_prepare_rank(c, ns))) return rc;
     if (nl > 0 || want_topk) {
         if ((rc = ensure_query_workspace(c, std::max(nl, 1), want_topk ? k : 0))) return rc;
     }
@@ -2068,13 +2077,38 @@ int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
         hipLaunchKernelGGL(k_seed_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, dset, (const int32_t *)(dset + nd),
                            (const uint64_t *)c->sd.d_list.get(), (uint32_t)n, acc);
     }
-    if (row_sum_fix_out) {
-        HIPCHK(c, c->sd.d_sums.ensure((size_t)ns));
-        HIPCHK(c, c->sd.d_sums.zero(c->stream, (size_t)ns));
-        const unsigned chunks = (unsigned)std::min<uint64_t>((n + BLOCK - 1) / BLOCK, 64);
-        hipLaunchKernelGGL(k_seed_row_sum, dim3((unsigned)ns, chunks), dim3(BLOCK), 0, c->stream, (const uint64_t *)acc, (uint32_t)n, c->sd.d_sums.get());
-        HIPCHK(c, hipMemcpyAsync(row_sum_fix_out, c->sd.d_sums.get(), (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    sc.seeds = (uint64_t)total; sc.distinct = (uint64_t)slot_of.size(); sc.queries = (uint64_t)nl; sc.dangling = (uint64_t)nd; sc.batches = nbatch;
+    return FORA_OK;
+}
+
+// the sums over the whole rows of the finished block, on their way to the caller's array (the stream is not synchronised)
+int seed_row_sums(fora_ctx *c, int ns, uint64_t *row_sum_fix_out) {
+    const uint64_t n = (uint64_t)c->g.n;
+    HIPCHK(c, c->sd.d_sums.ensure((size_t)ns));
+    HIPCHK(c, c->sd.d_sums.zero(c->stream, (size_t)ns));
+    const unsigned chunks = (unsigned)std::min<uint64_t>((n + BLOCK - 1) / BLOCK, 64);
+    hipLaunchKernelGGL(k_seed_row_sum, dim3((unsigned)ns, chunks), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->sd.d_acc.get(), (uint32_t)n, c->sd.d_sums.get());
+    HIPCHK(c, hipMemcpyAsync(row_sum_fix_out, c->sd.d_sums.get(), (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
+    return FORA_OK;
+}
+
+void fill_seeds_stats(const fora_ctx *c, const SeedCounts &sc, fora_seeds_stats *st) { // (after ev_collect)
+    if (!st) return;
+    st->seeds = sc.seeds; st->distinct = sc.distinct; st->queries = sc.queries; st->dangling = sc.dangling;
+    st->batches = sc.batches; st->combine_ms = c->tm.seed_combine_ms;
+}
+
+// fora_hip_query_seeds_batch: the output stage over the finished block
+int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                     double *ppr_out, uint64_t *ppr_fix_out, int k, int32_t *ids, double *scores, uint64_t *row_sum_fix_out,
+                     fora_seeds_stats *st) {
+    const bool want_topk = k > 0 && (ids || scores);
+    SeedCounts sc;
+    int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, k, want_topk, false, st, sc);
+    if (rc || ns == 0) return rc;
+    const uint64_t n = (uint64_t)c->g.n, cells = (uint64_t)ns * n;
+    uint64_t *const acc = c->sd.d_acc.get();
+    if (row_sum_fix_out) if ((rc = seed_row_sums(c, ns, row_sum_fix_out))) return rc;
     if (want_topk)
         for (int r0 = 0; r0 < ns; r0 += c->ws.B) { // the select works on the slots of a workspace: at most B rows at a time
             const int nb = std::min(c->ws.B, ns - r0);
@@ -2092,10 +2126,80 @@ int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("seed sets: ") + hipGetErrorString(e));
     ev_collect(c);
-    if (st) {
-        st->seeds = (uint64_t)total; st->distinct = (uint64_t)slot_of.size(); st->queries = (uint64_t)nl; st->dangling = (uint64_t)nd;
-        st->batches = nbatch; st->combine_ms = c->tm.seed_combine_ms;
+    fill_seeds_stats(c, sc, st);
+    return FORA_OK;
+}
+
+// rows of the finished block that fora_hip_seeds_sparse_batch / fora_hip_seeds_sweep_batch compact (and sort) at a time: the
+// option seeds_rows, at most what a grid's y takes.  k_sparse_count / k_sparse_write choose between 16-byte and 8-byte loads
+// from (q * n) & 1 and take their base for 16-byte aligned; a chunk starts at acc + r0 * n, an odd word when r0 * n is odd.
+// So with an odd n the count is rounded up to even: every chunk then starts at an even row.
+int seeds_chunk(const fora_ctx *c) {
+    int64_t C = std::min<int64_t>(std::max<int64_t>(c->opt_.seeds_rows, 1), 65534);
+    if ((c->g.n & 1) && (C & 1)) C++;
+    return (int)C;
+}
+
+// one attempt of fora_hip_seeds_sparse_batch: the block, then count / place over its rows, every row live and no dangling one
+int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                      uint64_t thr, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
+    SparseRun run; // (a retried attempt starts from an empty one)
+    run.thr = thr;
+    c->tm.sp_compact_ms = 0;
+    if (sp_out) memset(sp_out, 0, sizeof(*sp_out));
+    SeedCounts sc;
+    int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, 0, false, false, st, sc);
+    if (rc) return rc;
+    run.row_ptr.assign((size_t)ns + 1, 0);
+    if (ns == 0) { // an empty result is held; the stats stay zero
+        HIPCHK(c, hipSetDevice(c->device));
+        return sparse_finish(c, run, nullptr, 0, row_ptr, nullptr);
     }
+    const uint64_t n = (uint64_t)c->g.n;
+    const int C = seeds_chunk(c);
+    if ((rc = sparse_prepare(c, run, ns, std::min(C, ns), ns))) return rc;
+    std::vector<int> at((size_t)ns);
+    for (int i = 0; i < ns; i++) at[(size_t)i] = i;
+    for (int r0 = 0; r0 < ns; r0 += C) {
+        const int nb = std::min(C, ns - r0);
+        const uint64_t *rows = c->sd.d_acc.get() + (uint64_t)r0 * n;
+        if ((rc = sparse_count(c, run, nb, rows))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
+        if ((rc = sparse_place(c, run, nullptr, ns, at.data() + r0, nb, rows))) return rc;
+    }
+    if (row_sum_fix_out) if ((rc = seed_row_sums(c, ns, row_sum_fix_out))) return rc;
+    if ((rc = sparse_finish(c, run, nullptr, ns, row_ptr, sp_out))) return rc;
+    fill_seeds_stats(c, sc, st);
+    return FORA_OK;
+}
+
+// one attempt of fora_hip_seeds_sweep_batch: the block, then the sweep's passes over its rows
+int seeds_sweep_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                     uint64_t thr, int64_t max_size, int64_t *row_ptr, fora_sweep_row *rows_out, fora_seeds_stats *st, fora_sweep_stats *sw_out) {
+    SweepRun run; // (a retried attempt starts from an empty one)
+    run.thr = thr; run.max_size = max_size;
+    run.rows.assign((size_t)std::max(ns, 0), sweep_row_of(0, 0, 0, 0, 0));
+    c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
+    if (sw_out) memset(sw_out, 0, sizeof(*sw_out));
+    SeedCounts sc;
+    int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, 0, false, true, st, sc);
+    if (rc) return rc;
+    run.row_ptr.assign((size_t)ns + 1, 0);
+    if (ns == 0) { // an empty result is held; the stats stay zero
+        HIPCHK(c, hipSetDevice(c->device));
+        return sweep_finish(c, run, nullptr, 0, row_ptr, rows_out, nullptr);
+    }
+    const uint64_t n = (uint64_t)c->g.n;
+    const int C = seeds_chunk(c);
+    if ((rc = sweep_prepare(c, run, std::min(C, ns)))) return rc;
+    std::vector<int> at((size_t)ns);
+    for (int i = 0; i < ns; i++) at[(size_t)i] = i;
+    for (int r0 = 0; r0 < ns; r0 += C) {
+        const int nb = std::min(C, ns - r0);
+        if ((rc = sweep_rows_of_batch(c, run, nullptr, ns, at.data() + r0, nb, c->sd.d_acc.get() + (uint64_t)r0 * n))) return rc;
+    }
+    if ((rc = sweep_finish(c, run, nullptr, ns, row_ptr, rows_out, sw_out))) return rc;
+    fill_seeds_stats(c, sc, st);
     return FORA_OK;
 }
 
@@ -2583,6 +2687,35 @@ int fora_hip_query_seeds_batch(fora_ctx *c, const int64_t *set_ptr, const int32_
                                fora_seeds_stats *st) {
     return with_bucket_retry(c, [&] {
         return query_seeds_impl(c, set_ptr, seeds, weights, ns, with_idx, ppr_out, ppr_fix_out, k, ids, scores, row_sum_fix_out, st);
+    });
+}
+
+// ---- seed sets, result kept sparse: the set rows thresholded after the sum, held and fetched like fora_hip_query_sparse_batch's
+int fora_hip_seeds_sparse_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                                double threshold, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
+    if (!c) return FORA_E_ARG;
+    c->sp.valid = false; // the held result ends here, whatever becomes of this call
+    c->sp.entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    return with_bucket_retry(c, [&] {
+        return seeds_sparse_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, row_ptr, row_sum_fix_out, st, sp_out);
+    });
+}
+
+// ---- seed sets, swept: the SWEEP CUT contract over the set rows, held and fetched like fora_hip_sweep_batch's
+int fora_hip_seeds_sweep_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                               double threshold, int64_t max_size, int64_t *row_ptr, fora_sweep_row *rows, fora_seeds_stats *st,
+                               fora_sweep_stats *sw_out) {
+    if (!c) return FORA_E_ARG;
+    c->swp.valid = false; // the held profile ends here, whatever becomes of this call
+    c->swp.entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    return with_bucket_retry(c, [&] {
+        return seeds_sweep_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, max_size, row_ptr, rows, st, sw_out);
     });
 }
 

@@ -92,7 +92,7 @@
  *     the single entry (s, FORA_FIX_ONE); inside a row the ids ascend; row_ptr[0] == 0, row_ptr[nq] == entries.
  *   - fix is the raw word and vals[j] == ldexp((double)fix[j], -62), the value the dense ppr_out holds for that node.
  *   - the result lives in device memory owned by the ctx, outside the query workspace.  It stays valid until the next
- *     fora_hip_query_sparse_batch (whatever that call returns), fora_hip_sparse_clear, fora_hip_set_graph or
+ *     fora_hip_query_sparse_batch or fora_hip_seeds_sparse_batch (whatever that call returns), fora_hip_sparse_clear, fora_hip_set_graph or
  *     fora_hip_destroy; every other entry point (queries, top-k, baselines, set_option, set_batch, a bucket retry of a
  *     later call) leaves it untouched.  A failed sparse call leaves no result.
  *   - fora_hip_sparse_fetch may be called any number of times.  Each output pointer may be pageable host memory or device
@@ -132,6 +132,21 @@
  *     FORA_E_ARG.  No device memory for the ns x n accumulator block: FORA_E_NOMEM, the ctx still usable; the caller splits
  *     the call.
  *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched.
+ * SEED SETS, SPARSE (fora_hip_seeds_sparse_batch): the rows of SEED SETS leave as the CSR of SPARSE RESULTS.  row_g is exactly the
+ * row fora_hip_query_seeds_batch defines (sets, weights, wfix, duplicates, dangling seeds, every word); the threshold and thr_fix
+ * are those of SPARSE RESULTS, applied to row_g -- AFTER the sum: a node whose every term is under thr_fix is kept when their
+ * sum reaches it, which no merge of per-seed thresholded rows can give.
+ *   - row g keeps {v : row_g[v] >= thr_fix}, ids ascending, words unchanged.  The result is the held sparse result of SPARSE
+ *     RESULTS: a call replaces whatever sparse result was held (whatever becomes of the call), fora_hip_sparse_fetch copies it to
+ *     host or device arrays, fora_hip_sparse_clear drops it.  row_sum_fix_out[g] is the sum over the WHOLE row, as in SEED SETS.
+ *   - a uniform singleton set [s] gives the entries of fora_hip_query_sparse_batch for s, word for word (a dangling s: (s, 2^62)).
+ *   - no bit depends on what SEED SETS names, nor on the option "seeds_rows" (rows of the accumulator block compacted at a time,
+ *     default 256, at least 1; with an odd n it is rounded up to even so that every chunk of rows starts 16-byte aligned).
+ *   - stats: *st as in SEED SETS, *sp as in SPARSE RESULTS with batches = chunks of rows compacted.  ns == 0: FORA_OK,
+ *     row_ptr[0] = 0, an empty result held, both stats all zero.
+ *   - errors: those of SEED SETS, plus a NULL row_ptr and a bad threshold (FORA_E_ARG).  No device memory for the accumulator
+ *     block or the result: FORA_E_NOMEM, nothing held, the ctx still usable.
+ *   - a held sweep result, the walk index, the options and the FORA parameters are left untouched; fora_timing as in SEED SETS.
  * SWEEP CUT (fora_hip_sweep_batch, fora_hip_sweep_fetch, fora_hip_sweep_clear): local clustering by a sweep over ppr / degree
  * (Andersen-Chung-Lang), computed on the GPU from the rows of a query.  The query is fora_hip_query_batch's: same push, same
  * walks, same batching, same dangling-source fast path, same fora_query_stats, same bits in the ppr slabs.  Only what is derived
@@ -158,7 +173,7 @@
  *     set, or on the options "sweep_lds_cap" (entries of a sort tile: a row that fits one is sorted by one workgroup in LDS, a
  *     longer one takes the global tier; 0: every row does) and "sweep_rows" (rows whose rank maps are live at a time).
  *   - the profile (order, cut, vol per row, rows in the caller's order, row_ptr = prefix sums of L) lives in device memory owned
- *     by the ctx, outside the query workspace.  It stays valid until the next fora_hip_sweep_batch (whatever that call returns),
+ *     by the ctx, outside the query workspace.  It stays valid until the next fora_hip_sweep_batch or fora_hip_seeds_sweep_batch (whatever that call returns),
  *     fora_hip_sweep_clear, fora_hip_set_graph or fora_hip_destroy; every other entry point leaves it untouched.  A sweep call
  *     leaves a held sparse result, the walk index, the options and the FORA parameters untouched.
  *   - fora_hip_sweep_fetch: any pointer may be NULL; each may be pageable host memory or device memory on the ctx's GPU.
@@ -168,6 +183,22 @@
  *     profiles), batches, global_rows = rows sorted on the global tier, and the device times of the three stages.
  *   - NULL ctx (answered without touching the GPU), NULL row_ptr, bad nq / sources, with_idx without an index: FORA_E_ARG.  No
  *     device memory: FORA_E_NOMEM, nothing held, the ctx still usable.  nq == 0: FORA_OK, row_ptr[0] = 0, an empty result held.
+ * SEED SETS, SWEPT (fora_hip_seeds_sweep_batch): seed-set expansion -- the SWEEP CUT contract applied to the rows of SEED SETS.
+ * row_g is exactly the row fora_hip_query_seeds_batch defines; it is swept as an ordinary row: thr_fix, support, key, order, L,
+ * cut, vol, den, best prefix, ties and conductance are those of SWEEP CUT, with row_g in the place of ppr_fix[i].
+ *   - there is no special case for dangling seeds: they are members of the support like any node.  A set of dangling seeds only
+ *     has those seeds as its support and vol = 0 everywhere, hence best = 0 and conductance = 1.0.
+ *   - the result is the held profile of SWEEP CUT: a call replaces whatever profile was held (whatever becomes of the call),
+ *     fora_hip_sweep_fetch copies it, fora_hip_sweep_clear drops it.
+ *   - a uniform singleton set [s] gives the fora_sweep_row and the profile of fora_hip_sweep_batch for s, word for word (a
+ *     dangling s: len 1, best 0, the profile entry (s, 0, 0)).
+ *   - no bit depends on what SEED SETS and SWEEP CUT name, nor on the option "seeds_rows" (rows of the accumulator block
+ *     compacted and sorted at a time; "sweep_rows" keeps bounding the rank maps inside such a chunk).
+ *   - stats: *st as in SEED SETS, *sw as in SWEEP CUT with batches = chunks of rows.  ns == 0: FORA_OK, row_ptr[0] = 0, an empty
+ *     result held, both stats all zero.
+ *   - errors: those of SEED SETS, plus a NULL row_ptr and a bad threshold (FORA_E_ARG).  No device memory for the accumulator
+ *     block, the rank block or the result: FORA_E_NOMEM, nothing held, the ctx still usable.
+ *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched; fora_timing as in SEED SETS.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -375,6 +406,19 @@ int fora_hip_query_seeds_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, c
                                double *ppr_out /*ns*n or NULL*/, uint64_t *ppr_fix_out /*ns*n or NULL*/,
                                int k, int32_t *ids, double *scores /*ns*k or NULL*/,
                                uint64_t *row_sum_fix_out /*ns or NULL*/, fora_seeds_stats *st /*or NULL*/);
+
+/* ---- seed sets, sparse and swept (the SEED SETS, SPARSE and SEED SETS, SWEPT contracts above): the sets of
+ * fora_hip_query_seeds_batch, their rows thresholded after the sum and held as a sparse result (fora_hip_sparse_fetch /
+ * _clear), or swept and held as a profile (fora_hip_sweep_fetch / _clear).  Nothing dense leaves the device. */
+int fora_hip_seeds_sparse_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, const int32_t *seeds,
+                                const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx, double threshold,
+                                int64_t *row_ptr /*ns+1, required*/, uint64_t *row_sum_fix_out /*ns or NULL*/,
+                                fora_seeds_stats *st /*or NULL*/, fora_sparse_stats *sp /*or NULL*/);
+int fora_hip_seeds_sweep_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, const int32_t *seeds,
+                               const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx, double threshold,
+                               int64_t max_size, int64_t *row_ptr /*ns+1, required: prefix sums of L*/,
+                               fora_sweep_row *rows /*ns or NULL*/, fora_seeds_stats *st /*or NULL*/,
+                               fora_sweep_stats *sw /*or NULL*/);
 
 /* ---- top-k: replaces the topk() loop over get_topk -> fora_query_topk_new +
  * topk_ppr (query.h:1397-1401, 1139-1156, 972-1045; algo.h:592-610), --opt driver.
