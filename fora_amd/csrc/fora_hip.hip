@@ -1682,6 +1682,22 @@ int sweep_finish(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, int6
 }
 
 // refinement launches after k_walk_alloc: indexed walks, online walks, and the accumulate of their results
+// k_walk_dg as the launch selects it: the instantiation, and the bytes of its tables in dynamic LDS (fora_tables.h)
+typedef void (*WalkDgKernel)(Dev, uint32_t);
+static WalkDgKernel walk_dg_kernel(bool nzh, bool bits32, bool xl) {
+    switch ((nzh ? 4 : 0) | (bits32 ? 2 : 0) | (xl ? 1 : 0)) {
+    case 0: return k_walk_dg<false, false, false>;
+    case 1: return k_walk_dg<false, false, true>;
+    case 2: return k_walk_dg<false, true, false>;
+    case 3: return k_walk_dg<false, true, true>;
+    case 4: return k_walk_dg<true, false, false>;
+    case 5: return k_walk_dg<true, false, true>;
+    case 6: return k_walk_dg<true, true, false>;
+    default: return k_walk_dg<true, true, true>;
+    }
+}
+static size_t walk_dg_lds(const WalkDG &g, bool xl) { return walk_dg_lds_bytes(g.H, g.nrec, g.nblk, xl); }
+
 void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t round, int nzh) {
     const WsPlan &p = c->ws.plan;
     const dim3 wg(walk_grid_x(c, nq), nq);
@@ -1711,20 +1727,7 @@ void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t rou
     Dev dw = d;
     if (xl) { dw.nbins = (int32_t)d.dg.nbx; dw.acc_xl = d.dg.invb; }
     if (dg) {
-        const size_t lds = (xl ? (size_t)((d.dg.H + 1) & ~1u) * 8 : 0) + (size_t)4 * d.dg.nrec * 4 + (((size_t)d.dg.nblk + 3) & ~(size_t)3); // hub sums | 16-byte records | block -> class bytes
-#define FORA_DG_LAUNCH(NZH, B32, XLF) hipLaunchKernelGGL((k_walk_dg<NZH, B32, XLF>), wgs, dim3(DG_THREADS), lds, c->stream, dw, round)
-        const int sel = (nzh ? 4 : 0) | (d.dg.bits32 ? 2 : 0) | (xl ? 1 : 0);
-        switch (sel) {
-        case 0: FORA_DG_LAUNCH(false, false, false); break;
-        case 1: FORA_DG_LAUNCH(false, false, true); break;
-        case 2: FORA_DG_LAUNCH(false, true, false); break;
-        case 3: FORA_DG_LAUNCH(false, true, true); break;
-        case 4: FORA_DG_LAUNCH(true, false, false); break;
-        case 5: FORA_DG_LAUNCH(true, false, true); break;
-        case 6: FORA_DG_LAUNCH(true, true, false); break;
-        default: FORA_DG_LAUNCH(true, true, true); break;
-        }
-#undef FORA_DG_LAUNCH
+        hipLaunchKernelGGL(walk_dg_kernel(nzh != 0, d.dg.bits32 != 0, xl), wgs, dim3(DG_THREADS), walk_dg_lds(d.dg, xl), c->stream, dw, round);
     } else
         hipLaunchKernelGGL(k_walk_online<WALK_TO_PPR>, p.binned && !d.wide ? wgs : wg, dim3(BLOCK), 0, c->stream, d, round, nzh, (int32_t *)nullptr);
     ev.end();
@@ -2539,6 +2542,18 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_run.fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
     if (!strcmp(name, "team_suspended")) { *value = c->team_run.suspend; return FORA_OK; }             // calls left that do not try the team push
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
+    if (!strcmp(name, "walk_dg_wgs_per_cu")) { // k_walk_dg's resident workgroups per CU at this graph's tables (0: the graph has no degree-grouped copy)
+        const WalkDG &g = c->g.walk.dg;
+        int wgs = 0;
+        if (g.colp) {
+            const bool xl = c->opt_.walk_dg != 1 && g.invb;
+            (void)hipSetDevice(c->device);
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, (const void *)walk_dg_kernel(false, g.bits32 != 0, xl), DG_THREADS, walk_dg_lds(g, xl)) != hipSuccess)
+                return fail(c, FORA_E_HIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_walk_dg)");
+        }
+        *value = wgs;
+        return FORA_OK;
+    }
     if (!strcmp(name, "team_cooperative")) { *value = c->team_run.coop_ok && !c->team_run.coop_failed ? 1 : 0; return FORA_OK; }
     for (const auto &o : OPTIONS)
         if (!strcmp(name, o.name)) { *value = c->opt_.*(o.field); return FORA_OK; }

@@ -2396,14 +2396,17 @@ constexpr int STAGE = FORA_STAGE; // results per wave.  Round 2 (1000 ws queries
 struct WaveStage {
     uint64_t *pk;    // [STAGE]
     uint32_t *bcnt;  // [MAX_BINS]
-    uint32_t *bbase; // [MAX_BINS]
+    uint32_t *bbase; // [MAX_BINS]; not used by the one-array form (stage_flush<.., ONE = true>)
     uint32_t *fill;  // [MAX_BINS] of the WORKGROUP: messages in its sub-bucket of every bin (see Dev::bk_w)
     uint32_t count;  // wave-uniform
     const uint32_t *xl; // not null: destinations are in WalkDG bucket order, original id = xl[dest] (only the direct-atomic fallbacks need it)
 };
 // XLD (k_walk_dg<.., XL = true>): an entry's low word holds the endpoint's copy id less H, and its place in WalkDG bucket
 // order is worked out here, where every lane holds an entry, instead of by the whole wave in every iteration of the walk loop.
-template <int ST, bool XLD = false>
+// ONE (k_walk_dg): the wave has a single bin array.  bcnt holds the bins' counts, then their first stage slot while the stage
+// is sorted, then (first slot in the sub-bucket) - (first stage slot), so that entry m of the sorted stage goes to bcnt[bin] + m:
+// half the LDS of the two-array form with every word still 32 bits wide -- a sub-bucket may be longer than 65 535.
+template <int ST, bool XLD = false, bool ONE = false>
 __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) {
     const int lane = threadIdx.x & 63;
     const uint64_t slab = (uint64_t)q * d.n;
@@ -2415,6 +2418,7 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     constexpr uint64_t NONE = ~0ull;
     uint32_t rk[ST / 64];
     uint64_t wv[ST / 64];
+    uint32_t dl0 = 0, dl1 = 0; // ONE: (bin's first slot in the sub-bucket) - (its first stage slot), bins lane and lane + 64
 #pragma unroll
     for (int k = 0; k < ST / 64; k++) {
         const uint32_t m = k * 64 + lane;
@@ -2436,8 +2440,13 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
         const uint32_t c0 = lane < d.nbins ? st.bcnt[lane] : 0, c1 = lane + 64 < d.nbins ? st.bcnt[lane + 64] : 0;
         uint32_t t0, t1;
         const uint32_t o0 = wave_excl_scan(c0, t0), o1 = wave_excl_scan(c1, t1);
-        if (c0) st.bbase[lane] = atomicAdd(&st.fill[lane], c0);
-        if (c1) st.bbase[lane + 64] = atomicAdd(&st.fill[lane + 64], c1);
+        if (ONE) {
+            if (c0) dl0 = atomicAdd(&st.fill[lane], c0) - o0;
+            if (c1) dl1 = atomicAdd(&st.fill[lane + 64], c1) - (t0 + o1);
+        } else {
+            if (c0) st.bbase[lane] = atomicAdd(&st.fill[lane], c0);
+            if (c1) st.bbase[lane + 64] = atomicAdd(&st.fill[lane + 64], c1);
+        }
         st.bcnt[lane] = o0;           // from here on: first stage slot of the bin
         st.bcnt[lane + 64] = t0 + o1;
     }
@@ -2448,6 +2457,11 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     for (int k = 0; k < ST / 64; k++)
         if (wv[k] != NONE) st.pk[st.bcnt[((uint32_t)wv[k] & ((1u << WPACK_SHIFT) - 1)) >> BIN_SHIFT] + rk[k]] = wv[k];
     __builtin_amdgcn_wave_barrier();
+    if (ONE) { // (the sort has read the bins' stage slots)
+        st.bcnt[lane] = dl0;
+        st.bcnt[lane + 64] = dl1;
+        __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll
     for (int k = 0; k < ST / 64; k++) {
         const uint32_t m = k * 64 + lane;
@@ -2455,7 +2469,7 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
             const uint64_t pk = st.pk[m];
             const uint32_t dd = (uint32_t)pk & ((1u << WPACK_SHIFT) - 1);
             const uint32_t b = dd >> BIN_SHIFT;
-            const uint32_t pos = st.bbase[b] + (m - st.bcnt[b]);
+            const uint32_t pos = ONE ? st.bcnt[b] + m : st.bbase[b] + (m - st.bcnt[b]);
             // non-temporal: the results are read once, by k_accum; kept out of the way of the packed targets the walk steps
             // gather through L2 (walk kernel 93.8 -> 92.2 ms per 1000 ws queries against plain stores)
             if (pos < d.bk_cap) __builtin_nontemporal_store(pk, &d.bk_inc[bk0 + (uint64_t)b * bstride + pos]);
@@ -2466,7 +2480,7 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     st.count = 0;
 }
 // CHECKW false: the caller has dealt with the weights that do not fit the packed word
-template <int ST, bool XLD = false, bool CHECKW = true>
+template <int ST, bool XLD = false, bool CHECKW = true, bool ONE = false>
 __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, bool has, uint32_t dest, uint64_t w) {
     if (CHECKW && has && w >= WPACK_MAXW) { // does not fit the packed word (tiny walk budgets only)
         atomicAdd((unsigned long long *)&d.ppr[(uint64_t)q * d.n + (st.xl ? st.xl[dest] : dest)], (unsigned long long)w);
@@ -2479,7 +2493,7 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
         st.pk[pos] = (uint64_t)dest | (w << WPACK_SHIFT);
     }
     st.count += (uint32_t)__popcll(mask);
-    if (st.count > ST - 64) stage_flush<ST, XLD>(d, q, st);
+    if (st.count > ST - 64) stage_flush<ST, XLD, ONE>(d, q, st);
 }
 #define WAVE_STAGE_DECL_N(st, NWAVES, ST)                                                           \
     __shared__ uint64_t st##_pk[NWAVES][ST];                                                        \
@@ -2488,6 +2502,15 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
     WaveStage st;                                                                                   \
     st.pk = st##_pk[threadIdx.x >> 6];                                                              \
     st.bcnt = st##_bcnt[threadIdx.x >> 6]; st.bbase = st##_bbase[threadIdx.x >> 6];                 \
+    st.fill = st##_fill; st.count = 0; st.xl = nullptr;
+// the one-array form (stage_flush / stage_emit <.., ONE = true>)
+#define WAVE_STAGE_DECL_ONE(st, NWAVES, ST)                                                         \
+    __shared__ uint64_t st##_pk[NWAVES][ST];                                                        \
+    __shared__ uint32_t st##_bcnt[NWAVES][MAX_BINS];                                                \
+    __shared__ uint32_t st##_fill[MAX_BINS];                                                        \
+    WaveStage st;                                                                                   \
+    st.pk = st##_pk[threadIdx.x >> 6];                                                              \
+    st.bcnt = st##_bcnt[threadIdx.x >> 6]; st.bbase = nullptr;                                      \
     st.fill = st##_fill; st.count = 0; st.xl = nullptr;
 #define WAVE_STAGE_DECL(st) WAVE_STAGE_DECL_N(st, BLOCK / 64, STAGE)
 
@@ -2746,23 +2769,28 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FORA
 // iteration runs both steps of a Philox call; the endpoint's original id (one gather per WALK) is loaded at the end
 // of the iteration and consumed by the next one's emission, so its latency hides behind the refill and the Philox
 // rounds.  A workgroup is 8 waves sharing one copy of the tables.
-// LDS of a workgroup (NW = 8 waves, DG_STAGE = 256, WT = DG_TILE / NW = 32; XL):
-//   stage words            st_pk     NW * DG_STAGE * 8      16 384
-//   per-wave bin arrays    st_bcnt   NW * MAX_BINS * 4       4 096    (bins' counts, then their first stage slot)
-//                          st_bbase  NW * MAX_BINS * 4       4 096    (bins' first slot in the sub-bucket)
+// LDS of a workgroup (NW = 8 waves, DG_STAGE = 384, WT = DG_TILE / NW = 16; XL):
+//   stage words            st_pk     NW * DG_STAGE * 8      24 576
+//   per-wave bin array     st_bcnt   NW * MAX_BINS * 4       4 096    (one array, three uses in a flush: stage_flush<.., ONE>)
 //   workgroup's fill       st_fill   MAX_BINS * 4              512
-//   tile records           w_item    NW * WT * 32            8 192
-//   tile prefix sums       w_pref    NW * (WT + 1) * 4       1 056
-//   self sums              w_self    NW * WT * 8             2 048    (XL only)
-//   step counts, ticket    s_w, s_ticket                        36 -> 36 432 static with padding
+//   tile records           w_item    NW * WT * 32            4 096
+//   tile prefix sums       w_pref    NW * (WT + 1) * 2         272    (16 bits: a tile holds at most WT * WALK_SEG walks)
+//   self sums              w_self    NW * WT * 8             1 024    (XL only)
+//   step counts, ticket    s_w, s_ticket                        36 -> 34 624 static with padding (!XL: 33 600)
 //   tables (dynamic)       hub sums (H + 1) * 8 | records nrec * 16 | block -> class bytes: 14 232 at the ws-sized bench graph
-//                          (H = 256, 221 classes, 4 550 blocks), at most WALK_DG_LDS_CAP
-//   ~50 KB: three workgroups per CU, 6 waves per SIMD (FORA_DG_WPE).
+//                          (H = 256, 221 classes, 4 550 blocks), at most WALK_DG_LDS_CAP (walk_dg_lds_bytes, fora_tables.h)
+//   ~48 KB: three workgroups per CU, 6 waves per SIMD (FORA_DG_WPE).  What the one bin array, the 16-item tiles and the 16-bit
+//   prefix sums freed (10 000 B against two bin arrays, 32-item tiles, 32-bit sums) went into the stage: 256 -> 384 results per
+//   wave, the largest that keeps the static part under 36 KB.  A longer flush stores longer runs per bin (20 % fewer write
+//   requests) and there are fewer of them: walk kernel 82.0 -> 80.1 ms.  The other use of that LDS -- a fourth workgroup per CU at a stage of 256,
+//   40 664 B -- does not come from LDS alone: at this kernel's 106 SGPRs a SIMD holds 7 waves, so the CU still takes three
+//   workgroups; with FORA_DG_WPE = 8 the compiler keeps to 80 SGPRs by spilling 49 of them to lanes, and four do run
+//   (profiles/walk_dg_lds.txt has both).
 #ifndef FORA_DG_THREADS
 #define FORA_DG_THREADS 512
 #endif
 #ifndef FORA_DG_STAGE
-#define FORA_DG_STAGE 256
+#define FORA_DG_STAGE 384
 #endif
 #ifndef FORA_DG_WPE
 #define FORA_DG_WPE 6
@@ -2770,7 +2798,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FORA
 constexpr int DG_THREADS = FORA_DG_THREADS;
 constexpr int DG_STAGE = FORA_DG_STAGE;
 #ifndef FORA_DG_TILE
-#define FORA_DG_TILE 256
+#define FORA_DG_TILE 128
 #endif
 constexpr int DG_TILE = FORA_DG_TILE; // walk items per tile (at most DG_THREADS)
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
@@ -2803,7 +2831,9 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     struct __attribute__((aligned(16))) TileItem { uint64_t jb, rem, incr; uint32_t v, vp; };
     static_assert(sizeof(TileItem) == 32, "two uint4");
     __shared__ TileItem w_item[NW][WT];
-    __shared__ uint32_t w_pref[NW][WT + 1], s_w[NW];
+    static_assert((uint64_t)WT * WALK_SEG <= 0xFFFFu, "a tile's walk count fits the 16-bit prefix sums");
+    __shared__ uint16_t w_pref[NW][WT + 1];
+    __shared__ uint32_t s_w[NW];
     // A fifth of all walks stop where they started (algo.h:131-133 at the first step): with XL their weights are summed per
     // item in LDS (w_self) and leave as ONE result per item when the wave replaces its tile -- a walk that outlives its tile
     // (its tag names the tile it came from) is emitted on its own as before.
@@ -2830,7 +2860,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     const uint32_t stream = (uint32_t)d.src[q];
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (wave-uniform, and known to be: what hangs on it stays in scalar registers)
     uint32_t steps = 0;
-    WAVE_STAGE_DECL_N(st, NW, DG_STAGE)
+    WAVE_STAGE_DECL_ONE(st, NW, DG_STAGE)
     if (XL) st.xl = g.invb;
     uint32_t *bkc = d.bk_count + (uint64_t)q * d.pbins * d.sub + blockIdx.x; // count of bin b: bkc[b * sub]
     for (uint32_t i = threadIdx.x; i < (uint32_t)MAX_BINS; i += DG_THREADS) st.fill[i] = i < (uint32_t)d.nbins ? bkc[(uint64_t)i * d.sub] : 0;
@@ -2853,7 +2883,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     uint64_t pend_w = 0;
     unsigned long long *s_self = w_self[XL ? wid : 0];
     TileItem *s_item = w_item[wid];
-    uint32_t *s_pref = w_pref[wid];
+    uint16_t *s_pref = w_pref[wid];
     if (XL && lane < WT) s_self[lane] = 0;
     uint32_t gen = 0, tag = 0; // tiles this wave has loaded; (tile << 6 | item) of this lane's walk
     // the tile's self sums -> results like any other endpoint (hub accumulators / the wave's stage), then zero
@@ -2868,7 +2898,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
             atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[dn]], sv);
             has = false;
         }
-        stage_emit<DG_STAGE, true, false>(d, q, st, has, dn - H, (uint64_t)sv);
+        stage_emit<DG_STAGE, true, false, true>(d, q, st, has, dn - H, (uint64_t)sv);
     };
     // The workgroup's tiles are those of its NW waves under a static stride (x * NW + w, + tstride, ...), handed out in that
     // order to whichever wave runs out of walks first: one returning LDS add per tile.  Tiles differ by up to 30x in walks (a
@@ -2925,8 +2955,8 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
                     s_item[lane] = it;
                 }
                 if (__ballot(have && w.incr + 1 >= WPACK_MAXW)) big = true;
-                if (lane < WT) s_pref[lane] = pre;
-                if (lane == 0) s_pref[WT] = total;
+                if (lane < WT) s_pref[lane] = (uint16_t)pre;
+                if (lane == 0) s_pref[WT] = (uint16_t)total;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the wave's own LDS writes, read by its lanes below)
                 __builtin_amdgcn_wave_barrier();
                 wptr = 0; wend = total; cur_item = 0;
@@ -2991,16 +3021,16 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
             if (away && cur < H) atomicAdd(&s_hub[cur], (unsigned long long)wgt); // LDS
             const bool over = big && wgt >= WPACK_MAXW; // does not fit the packed word (tiny walk budgets only)
             if (away && cur >= H && over) atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[cur]], (unsigned long long)wgt);
-            stage_emit<DG_STAGE, true, false>(d, q, st, away && cur >= H && !over, cur - H, wgt); // (the place in bucket order: stage_flush)
+            stage_emit<DG_STAGE, true, false, true>(d, q, st, away && cur >= H && !over, cur - H, wgt); // (the place in bucket order: stage_flush)
         } else {
-            stage_emit<DG_STAGE>(d, q, st, pend, pend_node, pend_w);
+            stage_emit<DG_STAGE, false, true, true>(d, q, st, pend, pend_node, pend_w);
             pend = fin;
             if (pend) { pend_node = g.inv[cur]; pend_w = wgt; }
         }
     }
-    if (!XL) stage_emit<DG_STAGE>(d, q, st, pend, pend_node, pend_w);
+    if (!XL) stage_emit<DG_STAGE, false, true, true>(d, q, st, pend, pend_node, pend_w);
     if (gen) flush_self();
-    if (st.count) stage_flush<DG_STAGE, XL>(d, q, st);
+    if (st.count) stage_flush<DG_STAGE, XL, true>(d, q, st);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < (uint32_t)d.nbins; i += DG_THREADS) bkc[(uint64_t)i * d.sub] = st.fill[i];
     if (XL) for (uint32_t i = threadIdx.x; i < H; i += DG_THREADS) { // the hubs' share of this workgroup's walks

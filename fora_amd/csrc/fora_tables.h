@@ -84,6 +84,10 @@ inline CompactWalk make_compact_walk(int32_t n, const int64_t *row_ptr, const in
 // most 255 out-degree classes whose tables fit a workgroup's LDS share
 
 constexpr size_t WALK_DG_LDS_CAP = 28 * 1024; // static + dynamic LDS of k_walk_dg stay under 64 KB
+// k_walk_dg's tables in dynamic LDS as the launch lays them out: hub sums (bucket-order results only) | 16-byte records | block -> class bytes
+inline size_t walk_dg_lds_bytes(uint32_t H, uint32_t nrec, uint32_t nblk, bool xl) {
+    return (xl ? (size_t)((H + 1) & ~1u) * 8 : 0) + (size_t)4 * nrec * 4 + (((size_t)nblk + 3) & ~(size_t)3);
+}
 struct DgTables {
     bool have = false; // false: this graph gets no such copy (no hub count leaves <= 255 classes, tables over the LDS cap, ids over 31 bits)
     uint32_t H = 0, nrec = 0, ts = 0, bits = 0, zero_first = 0, bits32 = 0;
