@@ -34,6 +34,8 @@ constexpr uint32_t dg_ticket_tile(uint32_t x, uint32_t nw, uint32_t tstride, uin
     return x * nw + k % nw + k / nw * tstride;
 }
 
+constexpr int SP_TILE = 512; // k_sparse_count / k_sparse_write: ids per workgroup and step, two per lane (fora_rows.h sizes their grid by it)
+
 // team push (fora_team.h)
 constexpr int TEAM_MAX = 32;                  // members of a team (5 bits of a target word)
 constexpr int TEAM_LBITS = 15;                // bits of a local id

@@ -8,6 +8,7 @@
 #include "fora_bwd.h"
 #include "fora_sweep.h"
 #include "fora_tables.h"
+#include "fora_rows.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -285,24 +286,29 @@ struct SeedBufs {
     DevBuf<uint64_t> d_list; // use list of the batch in progress (SeedBatch::pack); the dangling seeds' triples after the last batch
     DevBuf<unsigned long long> d_sums; // [ns] row sums
 };
+// A result over rows that stays on the device until it is fetched: the sparse rows and the sweep profiles.  Both lay their
+// rows out in the caller's order (RowLayout, fora_rows.h), fill their held arrays batch by batch behind the same count pass
+// (CountBufs, count_rows) and grow them by the same rule (reserve_rows); finish_rows writes the dangling rows' entries and
+// marks the result held; every entry point that makes one first ends the held one (held_rows_begin).  Their own: below.
+struct CountBufs { // count pass of the batch in progress
+    DevBuf<uint32_t> d_counts, d_tot; // per workgroup [slots][X] and per slot
+    PinBuf<uint32_t> h_tot;           // pinned landing area of d_tot
+};
+struct HeldRows {
+    uint64_t entries = 0; bool valid = false; // valid: a result is held (it may have no entries)
+    CountBufs cnt;
+};
 // Sparse result of the last fora_hip_query_sparse_batch (free_sparse: sparse_clear, set_graph), apart from the workspace --
 // free_workspace (set_batch, set_option, a bucket retry) leaves it alone.
-struct SparseResult {
+struct SparseResult : HeldRows {
     DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_fix; // entries of all rows, rows in the caller's order
-    uint64_t entries = 0;
-    bool valid = false; // a result is held (it may have no entries)
-    DevBuf<uint32_t> d_counts, d_tot; // per workgroup [slots][X] and per slot counts of the batch in progress
-    PinBuf<uint32_t> h_tot;           // pinned landing area of d_tot
     DevBuf<int64_t> d_base;           // first entry of every live row of the call
     DevBuf<double> d_stage;           // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
 };
 // Sweep profile of the last fora_hip_sweep_batch (free_sweep: sweep_clear, set_graph), apart from the workspace and from the
 // sparse result; the buffers of the call in progress live here too.
-struct SweepResult {
+struct SweepResult : HeldRows {
     DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_cut, d_vol; // profiles of all rows, rows in the caller's order
-    uint64_t entries = 0;
-    bool valid = false; // a result is held (it may have no entries)
-    DevBuf<uint32_t> d_counts, d_tot; PinBuf<uint32_t> h_tot; // count pass of the batch in progress, as SparseResult's
     DevBuf<int32_t> d_tids; DevBuf<uint64_t> d_tkey;          // padded (id, key) copies of the batch's rows: the sort buffers
     DevBuf<uint64_t> d_desc;                                  // descriptors of the batch: SweepRowDesc | base | SweepTile | SweepGRow
     DevBuf<SweepRowOut> d_out; PinBuf<SweepRowOut> h_out;     // per live row of the batch
@@ -1311,130 +1317,136 @@ static int even_batch(int nq, int B) {
     return (nq + nbatch - 1) / nbatch;
 }
 
-// ---- sparse results (fora_hip_query_sparse_batch): host side of one attempt of a call.  Rows are laid out in the
-// caller's order; a batch's rows are placed when its counts are back -- every row before them is known by then (live
-// rows of earlier batches, one entry per dangling row).
-struct SparseRun {
+// ---- held rows (the comment above CountBufs): what the sparse rows and the sweep profiles share of one attempt of a call
+struct RowsRun {
     uint64_t thr = 1;
-    uint32_t R = SP_TILE, X = 1;       // ids per workgroup, workgroups per slot
-    std::vector<int64_t> row_ptr;      // nq + 1
-    std::vector<int64_t> dang_at;      // entries of the dangling rows ...
-    std::vector<int32_t> dang_src;     // ... and their sources
-    int next_row = 0, live_done = 0, batches = 0;
-    uint64_t cur = 0, max_row = 0;     // entries placed so far; the longest row
+    CompactGeom geo; RowLayout lay; // the compaction's ids per workgroup, workgroups per slot; where the rows lie
 };
 
+// what every entry point that makes a held result starts with: the held one ends here, whatever becomes of this call
+int held_rows_begin(fora_ctx *c, HeldRows &held, const int64_t *row_ptr, double threshold, uint64_t &thr) {
+    held.valid = false; held.entries = 0;
+    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
+    if (!threshold_ok(threshold)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    thr = threshold_word(threshold);
+    return FORA_OK;
+}
+
+// the compaction's geometry, and the count buffers for batches of at most `slots` slots
+int prepare_counts(fora_ctx *c, RowsRun &r, CountBufs &cb, int slots) {
+    r.geo = compact_geom((uint64_t)c->g.n);
+    HIPCHK(c, cb.d_counts.ensure((size_t)slots * r.geo.X));
+    HIPCHK(c, cb.d_tot.ensure((size_t)slots));
+    HIPCHK(c, cb.h_tot.ensure((size_t)slots));
+    return FORA_OK;
+}
+
+// count pass over nb rows; the counts are in cb.h_tot once the stream has been synchronised.
+// rows: where the nb rows lie, n words each, 16-byte aligned (null: the workspace's ppr slabs)
+int count_rows(fora_ctx *c, const RowsRun &r, const uint64_t *rows, int nb, const CountBufs &cb, EvKind kind) {
+    HIPCHK(c, hipMemsetAsync(cb.d_tot.get(), 0, (size_t)nb * 4, c->stream));
+    EvSpan ev(c, kind);
+    hipLaunchKernelGGL(k_sparse_count, dim3(r.geo.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, r.thr, r.geo.R,
+                       cb.d_counts.get(), cb.d_tot.get());
+    ev.end();
+    HIPCHK(c, hipMemcpyAsync(cb.h_tot.get(), cb.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    return FORA_OK;
+}
+
+// room in every held array for the entries placed so far; what the device has written of them is kept (grow_guess: the
+// rows still to come are guessed at).  No room: the held arrays go, and drop_rest (if any) frees what else goes with them.
+template <typename... T>
+int reserve_rows(fora_ctx *c, const RowLayout &lay, const char *no_room, void (*drop_rest)(fora_ctx *), DevBuf<T> &...held) {
+    const uint64_t need = lay.cur;
+    if (need <= std::min({(uint64_t)held.size()...})) return FORA_OK;
+    const uint64_t keep = std::min({lay.written, (uint64_t)held.size()...});
+    return [&](DevBuf<T>... grown) -> int { // the new arrays: moved in at the end, freed on every other way out
+        for (uint64_t cap = grow_guess(need, (uint64_t)lay.next_row, (uint64_t)lay.nq);; cap = need) { // (a guess that does not fit is no reason to fail)
+            if (((grown.alloc(cap) == hipSuccess) && ...)) break;
+            (void)hipGetLastError(); (grown.reset(), ...);
+            if (cap == need) {
+                (void)hipStreamSynchronize(c->stream);
+                (held.reset(), ...);
+                if (drop_rest) drop_rest(c);
+                return fail(c, FORA_E_NOMEM, no_room);
+            }
+        }
+        if (keep) {
+            const auto copy = [&](void *to, const void *from, size_t bytes) { HIPCHK(c, hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, c->stream)); return (int)FORA_OK; };
+            int rc = FORA_OK;
+            ((rc = rc ? rc : copy(grown.get(), held.get(), keep * sizeof(T))), ...);
+            if (rc) return rc;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        ((held = std::move(grown)), ...);
+        return FORA_OK;
+    }(DevBuf<T>()...);
+}
+
+// end of a call whose batches all went through, behind the layout's finish and the kind's reserve: the dangling rows'
+// entries (single(count, entries, sources) launches the kind's kernel for them), the last event times, the result is held
+template <typename Single> int finish_rows(fora_ctx *c, const RowLayout &lay, HeldRows &held, const char *what, int64_t *row_ptr, Single single) {
+    DevBuf<int64_t> at; DevBuf<int32_t> src; // (freed on every return path)
+    const size_t nd = lay.dang_at.size();
+    if (nd) {
+        HIPCHK(c, at.alloc(nd));
+        HIPCHK(c, src.alloc(nd));
+        HIPCHK(c, hipMemcpyAsync(at.get(), lay.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(src.get(), lay.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
+        single((uint32_t)nd, (const int64_t *)at.get(), (const int32_t *)src.get());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    ev_collect(c);
+    held.entries = lay.cur; held.valid = true;
+    memcpy(row_ptr, lay.row_ptr.data(), ((size_t)lay.nq + 1) * 8);
+    return FORA_OK;
+}
+
+// ---- sparse results (fora_hip_query_sparse_batch): what is their own
+struct SparseRun : RowsRun { int live_done = 0; }; // live rows written so far: d_base holds the first entry of each
+
 // per-call buffers of the two passes: `slots` slots per batch, `live` live rows in all
-int sparse_prepare(fora_ctx *c, SparseRun &sp, int nq, int slots, int live) {
-    const uint64_t n = (uint64_t)c->g.n;
-    sp.R = (uint32_t)std::max<uint64_t>(8 * SP_TILE, ((n + 1023) / 1024 + SP_TILE - 1) / SP_TILE * SP_TILE); // at most 1024 workgroups per slot
-    sp.X = (uint32_t)((n + sp.R - 1) / sp.R);
-    sp.row_ptr.assign((size_t)nq + 1, 0);
-    HIPCHK(c, c->sp.d_counts.ensure((size_t)slots * sp.X));
-    HIPCHK(c, c->sp.d_tot.ensure((size_t)slots));
-    HIPCHK(c, c->sp.h_tot.ensure((size_t)slots));
+int sparse_prepare(fora_ctx *c, SparseRun &sp, int slots, int live) {
+    if (int rc = prepare_counts(c, sp, c->sp.cnt, slots)) return rc;
     HIPCHK(c, c->sp.d_base.ensure((size_t)live));
     return FORA_OK;
 }
 
-// room for `need` entries, the first `keep` of them already written; rows_done of rows_all rows are placed (what the
-// rest will take is guessed from them, and asked for again if the guess was short)
-int sparse_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done, uint64_t rows_all) {
-    if (need <= c->sp.d_ids.size()) return FORA_OK;
-    const uint64_t guess = rows_done ? (uint64_t)((double)need / (double)rows_done * (double)rows_all * 1.125) + 1024 : need;
-    DevBuf<int32_t> ids; DevBuf<uint64_t> fix;
-    uint64_t cap = std::max<uint64_t>({need, guess, 1});
-    for (;; cap = need) { // (a guess that does not fit is no reason to fail)
-        if (ids.alloc(cap) == hipSuccess && fix.alloc(cap) == hipSuccess) break;
-        (void)hipGetLastError();
-        ids.reset(); fix.reset();
-        if (cap == need) {
-            (void)hipStreamSynchronize(c->stream);
-            free_sparse(c);
-            return fail(c, FORA_E_NOMEM, "no device memory for the sparse result");
-        }
-    }
-    keep = std::min<uint64_t>(keep, c->sp.d_ids.size());
-    if (keep) {
-        HIPCHK(c, hipMemcpyAsync(ids.get(), c->sp.d_ids.get(), keep * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(fix.get(), c->sp.d_fix.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    c->sp.d_ids = std::move(ids); c->sp.d_fix = std::move(fix);
-    return FORA_OK;
+int sparse_reserve(fora_ctx *c, const RowLayout &lay) { // (no room: the whole result goes)
+    return reserve_rows(c, lay, "no device memory for the sparse result", free_sparse, c->sp.d_ids, c->sp.d_fix);
 }
 
-// count pass over the nb slabs of the batch in progress (inside the batch: its counts come back with the batch's close-out).
-// rows: where the nb rows lie, n words each, 16-byte aligned (null: the workspace's ppr slabs)
-int sparse_count(fora_ctx *c, const SparseRun &sp, int nb, const uint64_t *rows = nullptr) {
-    HIPCHK(c, hipMemsetAsync(c->sp.d_tot.get(), 0, (size_t)nb * 4, c->stream));
-    EvSpan ev(c, EV_SP_COMPACT);
-    hipLaunchKernelGGL(k_sparse_count, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
-                       c->sp.d_counts.get(), c->sp.d_tot.get());
-    ev.end();
-    HIPCHK(c, hipMemcpyAsync(c->sp.h_tot.get(), c->sp.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
-    return FORA_OK;
-}
-
-// rows of the caller up to (not including) row `upto` that no batch has placed yet: dangling sources, one entry each
-void sparse_skip_dangling(SparseRun &sp, const int32_t *sources, int upto) {
-    for (; sp.next_row < upto; sp.next_row++) {
-        sp.row_ptr[(size_t)sp.next_row] = (int64_t)sp.cur;
-        sp.dang_at.push_back((int64_t)sp.cur);
-        sp.dang_src.push_back(sources[sp.next_row]);
-        sp.cur += 1;
-        sp.max_row = std::max<uint64_t>(sp.max_row, 1);
-    }
-}
-
-// write pass of the batch just closed (slot i: row at[i] of the caller); the slabs hold it until the next batch starts
-// on the same stream.  rows: as for sparse_count
-int sparse_place(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, const int *at, int nb, const uint64_t *rows = nullptr) {
+// write pass of the batch just closed (slot i: row at[i] of the caller; at null: row r0 + i); the slabs hold it until the
+// next batch starts on the same stream.  rows: as for count_rows
+int sparse_place(fora_ctx *c, SparseRun &sp, const int *at, int r0, int nb, const uint64_t *rows = nullptr) {
     std::vector<int64_t> base((size_t)nb);
-    const uint64_t keep = sp.cur; // (dangling rows are written at the end: nothing of them to keep)
+    sp.lay.begin_batch();
     for (int i = 0; i < nb; i++) {
-        sparse_skip_dangling(sp, sources, at[i]);
-        sp.row_ptr[(size_t)at[i]] = base[(size_t)i] = (int64_t)sp.cur;
-        sp.cur += c->sp.h_tot.get()[i];
-        sp.max_row = std::max<uint64_t>(sp.max_row, c->sp.h_tot.get()[i]);
-        sp.next_row = at[i] + 1;
+        const uint64_t len = c->sp.cnt.h_tot.get()[i];
+        base[(size_t)i] = sp.lay.place(at ? at[i] : r0 + i, len, len);
     }
-    sp.batches++;
-    if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? keep : 0, (uint64_t)sp.next_row, (uint64_t)nq)) return rc;
+    if (int rc = sparse_reserve(c, sp.lay)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->sp.d_base.get() + sp.live_done, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
     EvSpan ev(c, EV_SP_COMPACT);
-    hipLaunchKernelGGL(k_sparse_write, dim3(sp.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.R,
-                       (const uint32_t *)c->sp.d_counts.get(), (const int64_t *)(c->sp.d_base.get() + sp.live_done), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
+    hipLaunchKernelGGL(k_sparse_write, dim3(sp.geo.X, nb), dim3(BLOCK), 0, c->stream, rows ? rows : (const uint64_t *)c->ws.d_ppr.get(), (uint32_t)c->g.n, sp.thr, sp.geo.R,
+                       (const uint32_t *)c->sp.cnt.d_counts.get(), (const int64_t *)(c->sp.d_base.get() + sp.live_done), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
     sp.live_done += nb;
     return FORA_OK;
 }
 
-// end of a call whose batches all went through: the dangling rows' entries, the last event times, the result is held
-int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, int64_t *row_ptr, fora_sparse_stats *out) {
-    sparse_skip_dangling(sp, sources, nq);
-    sp.row_ptr[(size_t)nq] = (int64_t)sp.cur;
-    if (int rc = sparse_reserve(c, sp.cur, sp.live_done ? sp.cur : 0, (uint64_t)nq, (uint64_t)nq)) return rc; // (only grows when dangling rows came last)
-    DevBuf<int64_t> at; DevBuf<int32_t> src; // (freed on every return path)
-    const size_t nd = sp.dang_at.size();
-    if (nd) {
-        HIPCHK(c, at.alloc(nd));
-        HIPCHK(c, src.alloc(nd));
-        HIPCHK(c, hipMemcpyAsync(at.get(), sp.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(src.get(), sp.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_sparse_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd,
-                           (const int64_t *)at.get(), (const int32_t *)src.get(), c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse result: ") + hipGetErrorString(e));
-    ev_collect(c);
-    c->sp.entries = sp.cur;
-    c->sp.valid = true;
-    memcpy(row_ptr, sp.row_ptr.data(), ((size_t)nq + 1) * 8);
+int sparse_finish(fora_ctx *c, SparseRun &sp, int64_t *row_ptr, fora_sparse_stats *out) {
+    sp.lay.finish();
+    if (int rc = sparse_reserve(c, sp.lay)) return rc; // (only grows when dangling rows came last)
+    if (int rc = finish_rows(c, sp.lay, c->sp, "sparse result", row_ptr, [&](uint32_t nd, const int64_t *at, const int32_t *src) {
+            hipLaunchKernelGGL(k_sparse_single, dim3((nd + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, nd, at, src,
+                               c->sp.d_ids.get(), c->sp.d_fix.get(), (uint64_t)c->sp.d_ids.size());
+        })) return rc;
     if (out) {
         memset(out, 0, sizeof(*out));
-        out->entries = sp.cur; out->max_row = sp.max_row; out->thr_fix = sp.thr; out->batches = sp.batches;
+        out->entries = sp.lay.cur; out->max_row = sp.lay.max_row; out->thr_fix = sp.thr; out->batches = sp.lay.batches;
         out->compact_ms = c->tm.sp_compact_ms;
     }
     return FORA_OK;
@@ -1443,23 +1455,22 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, const int32_t *sources, int nq, in
 // ---- sweep cut (fora_hip_sweep_batch; the SWEEP CUT contract of include/fora_hip.h, kernels in fora_sweep.h): host side of
 // one attempt of a call.  The profiles are laid out in the caller's order like the rows of a sparse result; a batch's rows are
 // compacted, sorted and swept once the batch has closed -- its slabs hold the rows until the next batch starts on the stream.
-struct SweepRun {
-    uint64_t thr = 1;
-    int64_t max_size = 0;
-    uint32_t R = SP_TILE, X = 1;          // the compaction's ids per workgroup, workgroups per slot
-    std::vector<int64_t> row_ptr;         // nq + 1: prefix sums of L
-    std::vector<fora_sweep_row> rows;     // nq
-    std::vector<int64_t> dang_at; std::vector<int32_t> dang_src; // entries of the dangling rows and their sources
-    int next_row = 0, batches = 0, global_rows = 0;
-    uint64_t cur = 0, max_row = 0, entries_len = 0, edges = 0; // entries placed so far; the longest support; the supports summed
-};
-
 static fora_sweep_row sweep_row_of(int64_t len, int64_t best, uint64_t cut, uint64_t vol, uint64_t den) {
     fora_sweep_row r;
     r.len = len; r.best = best; r.cut = cut; r.vol = vol; r.den = den;
     r.conductance = best ? (double)cut / (double)den : 1.0;
     return r;
 }
+struct SweepRun : RowsRun { // (lay.row_ptr: prefix sums of L)
+    int64_t max_size = 0;
+    std::vector<fora_sweep_row> rows; // nq
+    int global_rows = 0; uint64_t edges = 0;
+    SweepRun(uint64_t thr_, int64_t max_size_, int nq) : max_size(max_size_) {
+        thr = thr_;
+        rows.assign((size_t)std::max(nq, 0), sweep_row_of(1, 0, 0, 0, 0)); // a batch writes the row of every source it runs: a row none has written is a dangling source's
+    }
+};
+
 static uint32_t sweep_tile(const fora_ctx *c) { // entries of a sort tile; 1: no LDS step at all
     const int64_t cap = std::min<int64_t>(c->opt_.sweep_lds_cap, SW_TILE_MAX);
     uint32_t t = 1;
@@ -1489,99 +1500,48 @@ int sweep_prepare_rank(fora_ctx *c, int live) {
 
 // per-call buffers of the passes over a batch of at most `slots` slots
 int sweep_prepare(fora_ctx *c, SweepRun &sw, int slots) {
-    const uint64_t n = (uint64_t)c->g.n;
-    sw.R = (uint32_t)std::max<uint64_t>(8 * SP_TILE, ((n + 1023) / 1024 + SP_TILE - 1) / SP_TILE * SP_TILE); // at most 1024 workgroups per slot
-    sw.X = (uint32_t)((n + sw.R - 1) / sw.R);
-    SweepResult &w = c->swp;
-    HIPCHK(c, w.d_counts.ensure((size_t)slots * sw.X));
-    HIPCHK(c, w.d_tot.ensure((size_t)slots));
-    HIPCHK(c, w.h_tot.ensure((size_t)slots));
-    HIPCHK(c, w.d_out.ensure((size_t)slots));
-    HIPCHK(c, w.h_out.ensure((size_t)slots));
+    if (int rc = prepare_counts(c, sw, c->swp.cnt, slots)) return rc;
+    HIPCHK(c, c->swp.d_out.ensure((size_t)slots));
+    HIPCHK(c, c->swp.h_out.ensure((size_t)slots));
     return FORA_OK;
 }
 
-// room for `need` profile entries, the first `keep` of them already written (sparse_reserve's scheme)
-int sweep_reserve(fora_ctx *c, uint64_t need, uint64_t keep, uint64_t rows_done, uint64_t rows_all) {
-    SweepResult &w = c->swp;
-    if (need <= w.d_ids.size()) return FORA_OK;
-    const uint64_t guess = rows_done ? (uint64_t)((double)need / (double)rows_done * (double)rows_all * 1.125) + 1024 : need;
-    DevBuf<int32_t> ids; DevBuf<uint64_t> cut, vol;
-    uint64_t cap = std::max<uint64_t>({need, guess, 1});
-    for (;; cap = need) { // (a guess that does not fit is no reason to fail)
-        if (ids.alloc(cap) == hipSuccess && cut.alloc(cap) == hipSuccess && vol.alloc(cap) == hipSuccess) break;
-        (void)hipGetLastError();
-        ids.reset(); cut.reset(); vol.reset();
-        if (cap == need) {
-            (void)hipStreamSynchronize(c->stream);
-            w.d_ids.reset(); w.d_cut.reset(); w.d_vol.reset();
-            return fail(c, FORA_E_NOMEM, "no device memory for the sweep profiles");
-        }
-    }
-    keep = std::min<uint64_t>(keep, w.d_ids.size());
-    if (keep) {
-        HIPCHK(c, hipMemcpyAsync(ids.get(), w.d_ids.get(), keep * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cut.get(), w.d_cut.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(vol.get(), w.d_vol.get(), keep * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    w.d_ids = std::move(ids); w.d_cut = std::move(cut); w.d_vol = std::move(vol);
-    return FORA_OK;
+int sweep_reserve(fora_ctx *c, const RowLayout &lay) {
+    return reserve_rows(c, lay, "no device memory for the sweep profiles", nullptr, c->swp.d_ids, c->swp.d_cut, c->swp.d_vol);
 }
 
-// rows of the caller up to (not including) row `upto` that no batch has placed yet: dangling sources, one entry each
-void sweep_skip_dangling(SweepRun &sw, const int32_t *sources, int upto) {
-    for (; sw.next_row < upto; sw.next_row++) {
-        sw.row_ptr[(size_t)sw.next_row] = (int64_t)sw.cur;
-        sw.rows[(size_t)sw.next_row] = sweep_row_of(1, 0, 0, 0, 0);
-        sw.dang_at.push_back((int64_t)sw.cur);
-        sw.dang_src.push_back(sources[sw.next_row]);
-        sw.cur += 1; sw.entries_len += 1;
-        sw.max_row = std::max<uint64_t>(sw.max_row, 1);
-    }
-}
-
-// the batch just closed (slot i: row at[i] of the caller): compaction, sort, and chunk by chunk the cut count and the scan.
-// rows: where the nb rows lie, n words each, 16-byte aligned (null: the workspace's ppr slabs)
-int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, const int *at, int nb, const uint64_t *rows = nullptr) {
+// the batch just closed (slot i: row at[i] of the caller; at null: row r0 + i): compaction, sort, and chunk by chunk the cut
+// count and the scan.  rows: as for count_rows
+int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int *at, int r0, int nb, const uint64_t *rows = nullptr) {
     SweepResult &w = c->swp;
     const uint32_t n = (uint32_t)c->g.n;
     const uint64_t *ppr = rows ? rows : c->ws.d_ppr.get();
-    EvSpan ev(c);
-    // count pass
-    HIPCHK(c, hipMemsetAsync(w.d_tot.get(), 0, (size_t)nb * 4, c->stream));
-    ev.begin(EV_SW_COMPACT);
-    hipLaunchKernelGGL(k_sparse_count, dim3(sw.X, nb), dim3(BLOCK), 0, c->stream, ppr, n, sw.thr, sw.R, w.d_counts.get(), w.d_tot.get());
-    ev.end();
-    HIPCHK(c, hipMemcpyAsync(w.h_tot.get(), w.d_tot.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    const auto row_of = [&](int i) { return at ? at[i] : r0 + i; };
+    if (int rc = count_rows(c, sw, rows, nb, w.cnt, EV_SW_COMPACT)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    EvSpan ev(c);
     // layout: padded copies in the sort buffers, profiles in the held arrays
     const uint32_t T = sweep_tile(c);
     std::vector<SweepRowDesc> rd((size_t)nb);
     std::vector<int64_t> tbase((size_t)nb);
     std::vector<SweepTile> tiles;
     std::vector<SweepGRow> grows;
-    const uint64_t keep = sw.cur;
     uint64_t tneed = 0;
     uint32_t maxP = 0, maxL = 0;
+    sw.lay.begin_batch();
     for (int i = 0; i < nb; i++) {
-        sweep_skip_dangling(sw, sources, at[i]);
-        const uint32_t len = w.h_tot.get()[i];
+        const uint32_t len = w.cnt.h_tot.get()[i];
         uint32_t P = len ? 1 : 0;
         while (P < len) P *= 2; // (len <= n < 2^31)
         const uint32_t L = sw.max_size > 0 ? (uint32_t)std::min<int64_t>(len, sw.max_size) : len;
-        rd[(size_t)i] = SweepRowDesc{(int64_t)tneed, (int64_t)sw.cur, len, P, L, 0};
+        rd[(size_t)i] = SweepRowDesc{(int64_t)tneed, sw.lay.place(row_of(i), len, L), len, P, L, 0};
         tbase[(size_t)i] = (int64_t)tneed;
         if (P > T) { grows.push_back(SweepGRow{(int64_t)tneed, P, 0}); sw.global_rows++; }
         if (T >= 2) for (uint32_t off = 0; off < P; off += T) tiles.push_back(SweepTile{(int64_t)tneed + off, P, off});
-        sw.row_ptr[(size_t)at[i]] = (int64_t)sw.cur;
-        tneed += P; sw.cur += L; sw.entries_len += len;
-        sw.max_row = std::max<uint64_t>(sw.max_row, len);
+        tneed += P;
         maxP = std::max(maxP, P); maxL = std::max(maxL, L);
-        sw.next_row = at[i] + 1;
     }
-    sw.batches++;
-    if (int rc = sweep_reserve(c, sw.cur, keep, (uint64_t)sw.next_row, (uint64_t)nq)) return rc;
+    if (int rc = sweep_reserve(c, sw.lay)) return rc;
     if (w.d_tids.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess || w.d_tkey.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, FORA_E_NOMEM, "no device memory for the sweep's sort buffers");
@@ -1604,7 +1564,7 @@ int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int n
     const auto gx = [](uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + BLOCK - 1) / BLOCK, 128)); };
     if (maxP) {
         ev.begin(EV_SW_COMPACT);
-        hipLaunchKernelGGL(k_sparse_write, dim3(sw.X, nb), dim3(BLOCK), 0, c->stream, ppr, n, sw.thr, sw.R, (const uint32_t *)w.d_counts.get(), d_base,
+        hipLaunchKernelGGL(k_sparse_write, dim3(sw.geo.X, nb), dim3(BLOCK), 0, c->stream, ppr, n, sw.thr, sw.geo.R, (const uint32_t *)w.cnt.d_counts.get(), d_base,
                            w.d_tids.get(), w.d_tkey.get(), tcap);
         hipLaunchKernelGGL(k_sweep_keys, dim3(gx(maxP), nb), dim3(BLOCK), 0, c->stream, d_rd, (const uint32_t *)c->g.d_deg.get(), n, w.d_tids.get(), w.d_tkey.get(), tcap);
         ev.begin(EV_SW_SORT);
@@ -1642,40 +1602,25 @@ int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int32_t *sources, int n
     w.rank_dirty = false;
     for (int i = 0; i < nb; i++) {
         const SweepRowOut &o = w.h_out.get()[i];
-        sw.rows[(size_t)at[i]] = sweep_row_of(o.len, o.best, o.cut, o.vol, o.den);
+        sw.rows[(size_t)row_of(i)] = sweep_row_of(o.len, o.best, o.cut, o.vol, o.den);
         sw.edges += o.edges;
     }
     return FORA_OK;
 }
 
-// end of a call whose batches all went through: the dangling rows' entries, the last event times, the result is held
-int sweep_finish(fora_ctx *c, SweepRun &sw, const int32_t *sources, int nq, int64_t *row_ptr, fora_sweep_row *rows, fora_sweep_stats *out) {
+int sweep_finish(fora_ctx *c, SweepRun &sw, int64_t *row_ptr, fora_sweep_row *rows, fora_sweep_stats *out) {
     SweepResult &w = c->swp;
-    sweep_skip_dangling(sw, sources, nq);
-    sw.row_ptr[(size_t)nq] = (int64_t)sw.cur;
-    if (int rc = sweep_reserve(c, sw.cur, sw.cur, (uint64_t)nq, (uint64_t)nq)) return rc; // (only grows when dangling rows came last)
-    DevBuf<int64_t> at; DevBuf<int32_t> src; // (freed on every return path)
-    const size_t nd = sw.dang_at.size();
-    if (nd) {
-        HIPCHK(c, at.alloc(nd));
-        HIPCHK(c, src.alloc(nd));
-        HIPCHK(c, hipMemcpyAsync(at.get(), sw.dang_at.data(), nd * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(src.get(), sw.dang_src.data(), nd * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_sweep_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, (const int64_t *)at.get(),
-                           (const int32_t *)src.get(), w.d_ids.get(), w.d_cut.get(), w.d_vol.get(), (uint64_t)w.d_ids.size());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sweep result: ") + hipGetErrorString(e));
-    ev_collect(c);
-    w.entries = sw.cur;
-    w.valid = true;
-    memcpy(row_ptr, sw.row_ptr.data(), ((size_t)nq + 1) * 8);
-    if (rows && nq) memcpy(rows, sw.rows.data(), (size_t)nq * sizeof(fora_sweep_row));
+    sw.lay.finish();
+    if (int rc = sweep_reserve(c, sw.lay)) return rc; // (only grows when dangling rows came last)
+    if (int rc = finish_rows(c, sw.lay, w, "sweep result", row_ptr, [&](uint32_t nd, const int64_t *at, const int32_t *src) {
+            hipLaunchKernelGGL(k_sweep_single, dim3((nd + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, nd, at, src,
+                               w.d_ids.get(), w.d_cut.get(), w.d_vol.get(), (uint64_t)w.d_ids.size());
+        })) return rc;
+    if (rows && sw.lay.nq) memcpy(rows, sw.rows.data(), (size_t)sw.lay.nq * sizeof(fora_sweep_row));
     if (out) {
         memset(out, 0, sizeof(*out));
-        out->entries = sw.entries_len; out->max_row = sw.max_row; out->thr_fix = sw.thr; out->edges = sw.edges;
-        out->batches = sw.batches; out->global_rows = sw.global_rows;
+        out->entries = sw.lay.support; out->max_row = sw.lay.max_row; out->thr_fix = sw.thr; out->edges = sw.edges;
+        out->batches = sw.lay.batches; out->global_rows = sw.global_rows;
         out->compact_ms = c->tm.sw_compact_ms; out->sort_ms = c->tm.sw_sort_ms; out->cut_ms = c->tm.sw_cut_ms;
     }
     return FORA_OK;
@@ -1825,7 +1770,7 @@ int run_query_batch(fora_ctx *c, const int32_t *sources, int nq, bool with_idx, 
         hipLaunchKernelGGL(k_ppr_sum, dim3(chunks, nq), dim3(BLOCK), 0, c->stream, d);
         ev.end();
     }
-    if (sp) if ((rc = sparse_count(c, *sp, nq))) return rc;
+    if (sp) if ((rc = count_rows(c, *sp, nullptr, nq, c->sp.cnt, EV_SP_COMPACT))) return rc; // (inside the batch: the counts come back with its close-out)
     HIPCHK(c, hipMemcpyAsync(c->ws.h_qs_pin.get(), c->ws.d_qs.get(), (size_t)nq * sizeof(QState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ws.h_steps_pin.get(), d.tot_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if ((rc = close_batch(c, &batch, "batch"))) return rc;
@@ -1889,8 +1834,8 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     }
     const bool want_topk = topk > 0 && (ids || scores);
     const int nl = (int)live_src.size();
-    if (sp) sp->row_ptr.assign((size_t)nq + 1, 0);
-    if (sw) sw->row_ptr.assign((size_t)nq + 1, 0);
+    if (sp) sp->lay.begin(sources, nq);
+    if (sw) sw->lay.begin(sources, nq);
     if (nl == 0) return FORA_OK;
     int rc = FORA_OK;
     if (sw) if ((rc = sweep_prepare_rank(c, nl))) return rc; // (ahead of the workspace: a batch size chosen from the free memory accounts for the block)
@@ -1898,14 +1843,14 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
     if (rc) return rc;
     const int per = even_batch(nl, c->ws.B);
     if (sw) if ((rc = sweep_prepare(c, *sw, std::min(per, nl)))) return rc;
-    if (sp) if ((rc = sparse_prepare(c, *sp, nq, std::min(per, nl), nl))) return rc;
+    if (sp) if ((rc = sparse_prepare(c, *sp, std::min(per, nl), nl))) return rc;
     for (int b0 = 0; b0 < nl; b0 += per) {
         const int nb = std::min(per, nl - b0);
         const int *at = live_at.data() + b0; // places of the batch's slots in the caller's arrays
         if ((rc = run_query_batch(c, live_src.data() + b0, nb, with_idx != 0, flags, sp))) return rc;
         if (stats) for (int i = 0; i < nb; i++) fill_stats(c, i, stats[at[i]]);
-        if (sp) if ((rc = sparse_place(c, *sp, sources, nq, at, nb))) return rc;
-        if (sw) if ((rc = sweep_rows_of_batch(c, *sw, sources, nq, at, nb))) return rc;
+        if (sp) if ((rc = sparse_place(c, *sp, at, 0, nb))) return rc;
+        if (sw) if ((rc = sweep_rows_of_batch(c, *sw, at, 0, nb))) return rc;
         if (want_topk) {
             if ((rc = launch_select(c, make_dev(c, nb, false), nb, topk, c->ws.d_topk_ids.get(), c->ws.d_topk_sc.get(), 0))) return rc;
             if ((rc = copy_topk_out(c, nb, topk, ids, scores, 0, at))) return rc;
@@ -2153,25 +2098,23 @@ int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds,
     SeedCounts sc;
     int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, 0, false, false, st, sc);
     if (rc) return rc;
-    run.row_ptr.assign((size_t)ns + 1, 0);
+    run.lay.begin(nullptr, ns);
     if (ns == 0) { // an empty result is held; the stats stay zero
         HIPCHK(c, hipSetDevice(c->device));
-        return sparse_finish(c, run, nullptr, 0, row_ptr, nullptr);
+        return sparse_finish(c, run, row_ptr, nullptr);
     }
     const uint64_t n = (uint64_t)c->g.n;
     const int C = seeds_chunk(c);
-    if ((rc = sparse_prepare(c, run, ns, std::min(C, ns), ns))) return rc;
-    std::vector<int> at((size_t)ns);
-    for (int i = 0; i < ns; i++) at[(size_t)i] = i;
+    if ((rc = sparse_prepare(c, run, std::min(C, ns), ns))) return rc;
     for (int r0 = 0; r0 < ns; r0 += C) {
         const int nb = std::min(C, ns - r0);
         const uint64_t *rows = c->sd.d_acc.get() + (uint64_t)r0 * n;
-        if ((rc = sparse_count(c, run, nb, rows))) return rc;
+        if ((rc = count_rows(c, run, rows, nb, c->sp.cnt, EV_SP_COMPACT))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
-        if ((rc = sparse_place(c, run, nullptr, ns, at.data() + r0, nb, rows))) return rc;
+        if ((rc = sparse_place(c, run, nullptr, r0, nb, rows))) return rc;
     }
     if (row_sum_fix_out) if ((rc = seed_row_sums(c, ns, row_sum_fix_out))) return rc;
-    if ((rc = sparse_finish(c, run, nullptr, ns, row_ptr, sp_out))) return rc;
+    if ((rc = sparse_finish(c, run, row_ptr, sp_out))) return rc;
     fill_seeds_stats(c, sc, st);
     return FORA_OK;
 }
@@ -2179,29 +2122,25 @@ int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds,
 // one attempt of fora_hip_seeds_sweep_batch: the block, then the sweep's passes over its rows
 int seeds_sweep_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
                      uint64_t thr, int64_t max_size, int64_t *row_ptr, fora_sweep_row *rows_out, fora_seeds_stats *st, fora_sweep_stats *sw_out) {
-    SweepRun run; // (a retried attempt starts from an empty one)
-    run.thr = thr; run.max_size = max_size;
-    run.rows.assign((size_t)std::max(ns, 0), sweep_row_of(0, 0, 0, 0, 0));
+    SweepRun run(thr, max_size, ns); // (a retried attempt starts from an empty one)
     c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
     if (sw_out) memset(sw_out, 0, sizeof(*sw_out));
     SeedCounts sc;
     int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, 0, false, true, st, sc);
     if (rc) return rc;
-    run.row_ptr.assign((size_t)ns + 1, 0);
+    run.lay.begin(nullptr, ns);
     if (ns == 0) { // an empty result is held; the stats stay zero
         HIPCHK(c, hipSetDevice(c->device));
-        return sweep_finish(c, run, nullptr, 0, row_ptr, rows_out, nullptr);
+        return sweep_finish(c, run, row_ptr, rows_out, nullptr);
     }
     const uint64_t n = (uint64_t)c->g.n;
     const int C = seeds_chunk(c);
     if ((rc = sweep_prepare(c, run, std::min(C, ns)))) return rc;
-    std::vector<int> at((size_t)ns);
-    for (int i = 0; i < ns; i++) at[(size_t)i] = i;
     for (int r0 = 0; r0 < ns; r0 += C) {
         const int nb = std::min(C, ns - r0);
-        if ((rc = sweep_rows_of_batch(c, run, nullptr, ns, at.data() + r0, nb, c->sd.d_acc.get() + (uint64_t)r0 * n))) return rc;
+        if ((rc = sweep_rows_of_batch(c, run, nullptr, r0, nb, c->sd.d_acc.get() + (uint64_t)r0 * n))) return rc;
     }
-    if ((rc = sweep_finish(c, run, nullptr, ns, row_ptr, rows_out, sw_out))) return rc;
+    if ((rc = sweep_finish(c, run, row_ptr, rows_out, sw_out))) return rc;
     fill_seeds_stats(c, sc, st);
     return FORA_OK;
 }
@@ -2682,17 +2621,14 @@ int fora_hip_query_batch_fix(fora_ctx *c, const int32_t *sources, int nq, int wi
 int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t *row_ptr,
                                 fora_query_stats *stats, fora_sparse_stats *sp_out) {
     if (!c) return FORA_E_ARG;
-    c->sp.valid = false; // the held result ends here, whatever becomes of this call
-    c->sp.entries = 0;
-    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
-    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
-    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
     return with_bucket_retry(c, [&] {
         SparseRun run; // (a retried attempt starts from an empty one)
         run.thr = thr;
         c->tm.sp_compact_ms = 0;
         if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, &run)) return rc;
-        return sparse_finish(c, run, sources, nq, row_ptr, sp_out);
+        return sparse_finish(c, run, row_ptr, sp_out);
     });
 }
 
@@ -2709,11 +2645,8 @@ int fora_hip_query_seeds_batch(fora_ctx *c, const int64_t *set_ptr, const int32_
 int fora_hip_seeds_sparse_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
                                 double threshold, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
     if (!c) return FORA_E_ARG;
-    c->sp.valid = false; // the held result ends here, whatever becomes of this call
-    c->sp.entries = 0;
-    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
-    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
-    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
     return with_bucket_retry(c, [&] {
         return seeds_sparse_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, row_ptr, row_sum_fix_out, st, sp_out);
     });
@@ -2724,11 +2657,8 @@ int fora_hip_seeds_sweep_batch(fora_ctx *c, const int64_t *set_ptr, const int32_
                                double threshold, int64_t max_size, int64_t *row_ptr, fora_sweep_row *rows, fora_seeds_stats *st,
                                fora_sweep_stats *sw_out) {
     if (!c) return FORA_E_ARG;
-    c->swp.valid = false; // the held profile ends here, whatever becomes of this call
-    c->swp.entries = 0;
-    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
-    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
-    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->swp, row_ptr, threshold, thr)) return rc;
     return with_bucket_retry(c, [&] {
         return seeds_sweep_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, max_size, row_ptr, rows, st, sw_out);
     });
@@ -2779,18 +2709,13 @@ int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix
 int fora_hip_sweep_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t max_size, int64_t *row_ptr,
                          fora_sweep_row *rows, fora_query_stats *stats, fora_sweep_stats *sw_out) {
     if (!c) return FORA_E_ARG;
-    c->swp.valid = false; // the held profile ends here, whatever becomes of this call
-    c->swp.entries = 0;
-    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
-    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
-    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->swp, row_ptr, threshold, thr)) return rc;
     return with_bucket_retry(c, [&] {
-        SweepRun run; // (a retried attempt starts from an empty one)
-        run.thr = thr; run.max_size = max_size;
-        run.rows.assign((size_t)std::max(nq, 0), sweep_row_of(0, 0, 0, 0, 0));
+        SweepRun run(thr, max_size, nq); // (a retried attempt starts from an empty one)
         c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
         if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, nullptr, &run)) return rc;
-        return sweep_finish(c, run, sources, nq, row_ptr, rows, sw_out);
+        return sweep_finish(c, run, row_ptr, rows, sw_out);
     });
 }
 
@@ -2822,40 +2747,33 @@ int fora_hip_sweep_clear(fora_ctx *c) {
 // ---- TEST ENTRY POINTS (include/fora_hip.h; libfora_hip_test.so only): chosen inputs in front of the sweep's own host
 // functions and kernels.
 // fora_hip_sweep_batch's frame with the caller's rows in the ppr slabs instead of a query batch's: row i takes slot i - b0 of
-// its batch, no row is skipped (sweep_skip_dangling never reads the sources it is handed).
+// its batch, no row is skipped (a RowLayout without sources).
 int fora_hip_test_sweep_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t max_size, int64_t *row_ptr,
                              fora_sweep_row *rows, fora_sweep_stats *sw_out) {
     if (!c) return FORA_E_ARG;
-    c->swp.valid = false;
-    c->swp.entries = 0;
-    if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
-    if (!(threshold <= 1.0)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
-    const uint64_t thr = threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->swp, row_ptr, threshold, thr)) return rc;
     return with_bucket_retry(c, [&] {
-        SweepRun run;
-        run.thr = thr; run.max_size = max_size;
-        run.rows.assign((size_t)std::max(nq, 0), sweep_row_of(0, 0, 0, 0, 0));
+        SweepRun run(thr, max_size, nq);
         c->tm.sw_compact_ms = c->tm.sw_sort_ms = c->tm.sw_cut_ms = 0;
         if (int rc = check_batch_args(c, reinterpret_cast<const int32_t *>(rows_fix), nq, "row")) return rc;
         HIPCHK(c, hipSetDevice(c->device));
         const uint64_t n = (uint64_t)c->g.n;
-        run.row_ptr.assign((size_t)nq + 1, 0);
+        run.lay.begin(nullptr, nq);
         if (nq) {
             if (int rc = sweep_prepare_rank(c, nq)) return rc;
             if (int rc = ensure_query_workspace(c, nq, 0)) return rc;
             const int per = even_batch(nq, c->ws.B);
             if (int rc = sweep_prepare(c, run, std::min(per, nq))) return rc;
-            std::vector<int> at((size_t)nq);
-            for (int i = 0; i < nq; i++) at[(size_t)i] = i;
             for (int b0 = 0; b0 < nq; b0 += per) {
                 const int nb = std::min(per, nq - b0);
                 if ((uint64_t)nb * n > c->ws.d_ppr.size()) return fail(c, FORA_E_HIP, "test_sweep_rows: the batch does not fit the ppr slabs");
                 HIPCHK(c, hipMemcpyAsync(c->ws.d_ppr.get(), rows_fix + (uint64_t)b0 * n, (uint64_t)nb * n * 8, hipMemcpyHostToDevice, c->stream));
                 HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
-                if (int rc = sweep_rows_of_batch(c, run, nullptr, nq, at.data() + b0, nb)) return rc;
+                if (int rc = sweep_rows_of_batch(c, run, nullptr, b0, nb)) return rc;
             }
         }
-        return sweep_finish(c, run, nullptr, nq, row_ptr, rows, sw_out);
+        return sweep_finish(c, run, row_ptr, rows, sw_out);
     });
 }
 

@@ -3215,7 +3215,7 @@ __global__ void __launch_bounds__(BLOCK) k_walk_mc(Dev d, uint64_t wbase, uint64
 // A lane takes the two words of one 16-byte line.  The slab of slot q starts at word q * n, an odd word when q * n is
 // odd: the lanes' pairs then start one id below the range (pair p of the sweep holds ids lo - odd + 2p, + 1) and the ids
 // outside [lo, hi) are masked.  The kernels read the ppr slab and nothing else of the workspace, whatever the layout.
-constexpr int SP_TILE = 2 * BLOCK; // ids per workgroup and step
+static_assert(SP_TILE == 2 * BLOCK, "ids per workgroup and step (fora_consts.h)");
 constexpr int SP_UNROLL = 4;       // count pass: loads in flight per lane
 __device__ __forceinline__ void sp_load(const uint64_t *slab, int64_t p, int64_t lo, int64_t hi, uint64_t &a, uint64_t &b) {
     a = 0; b = 0;

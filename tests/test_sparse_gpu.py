@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import pick_sources
+from growth_case import growth_case, growths_with_entries_to_keep
 
 pytestmark = pytest.mark.gpu
 SEED = 0x464F5241
@@ -128,6 +129,22 @@ def test_several_batches_with_a_dangling_row_between_them(engine, tiny_dangling)
         # no source at all
         row_ptr, ids, vals, st, sp = engine.query_sparse(np.zeros(0, dtype=np.int32))
         assert (row_ptr == [0]).all() and ids.size == 0 and vals.size == 0 and sp["entries"] == 0
+    finally:
+        engine.set_batch(0)
+
+
+def test_growth_with_entries_to_keep(engine, small):
+    """the held arrays grow in the middle of a call and the entries written so far move into the new ones"""
+    g, srcs = growth_case(engine, small)
+    engine.set_batch(1)
+    try:
+        want, _, wst = engine.query_fix(srcs)
+        lens = (want != 0).sum(axis=1)
+        print("row lengths", lens.tolist(), "growths with entries to keep", growths_with_entries_to_keep(lens))
+        assert lens[0] == 2 and growths_with_entries_to_keep(lens) >= 2
+        engine.sparse_clear()
+        row_ptr, ids, vals, fix, st, sp = engine.query_sparse(srcs, threshold=0.0, want_fix=True)
+        check_against_dense(want, wst, 1, row_ptr, ids, vals, fix, st, sp, batches=6)
     finally:
         engine.set_batch(0)
 

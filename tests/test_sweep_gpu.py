@@ -12,6 +12,7 @@ import pytest
 
 import sweep_ref as R
 from conftest import pick_sources
+from growth_case import growth_case, growths_with_entries_to_keep
 
 pytestmark = pytest.mark.gpu
 SEED = 0x464F5241
@@ -165,6 +166,24 @@ def test_sweep_equals_twin(engine, request, gname):
         for i, members in enumerate(engine.local_cluster(s)):
             r = _ref(g, want[i], R.thr_fix_of(1.0 / g.n), 0)
             assert members.dtype == np.int32 and members.tolist() == r["order"][:r["best"]] and r["best"] > 0
+
+
+def test_growth_with_entries_to_keep(engine, small):
+    """the held arrays grow in the middle of a call and the profiles written so far move into the new ones (the case of
+    growth_case.py: one row per batch, a row of 2 entries and then five long ones)"""
+    g, srcs = growth_case(engine, small)
+    engine.set_batch(1)
+    try:
+        want, _, wst = engine.query_fix(srcs)
+        lens = (want != 0).sum(axis=1)
+        print("row lengths", lens.tolist(), "growths with entries to keep", growths_with_entries_to_keep(lens))
+        assert lens[0] == 2 and growths_with_entries_to_keep(lens) >= 2
+        engine.sweep_clear()
+        out = engine.sweep(srcs, threshold=0.0, want_profile=True)
+        check(g, want, wst, 0.0, 0, out)
+        assert out["sweep"]["batches"] == 6
+    finally:
+        engine.set_batch(0)
 
 
 def _threshold_for_length(row, length):
