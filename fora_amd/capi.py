@@ -22,6 +22,7 @@ SYMBOLS = [
     "fora_hip_query_seeds_batch",
     "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
     "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
+    "fora_hip_sparse_propagate",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -100,6 +101,19 @@ class SweepStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PropStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("feat_bytes", C.c_uint64),
+                ("chunks", C.c_int32), ("feat_on_device", C.c_int32), ("gather_ms", C.c_double), ("combine_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+PROP_SEG = 256  # FORA_PROP_SEG
+PROP_F32, PROP_BF16 = 0, 1
+PROP_NORMALIZE = 1
 
 
 def to_torch_csr(row_ptr, ids, vals, n):
@@ -309,6 +323,156 @@ class Engine:
     def sparse_clear(self):
         self._chk(self._lib.fora_hip_sparse_clear(self._ctx))
 
+    # ---- feature propagation (the PROPAGATE contract of include/fora_hip.h)
+    @staticmethod
+    def _is_torch(x):
+        return type(x).__module__.split(".")[0] == "torch"
+
+    def _prop_feat(self, feat, bf16):
+        """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate"""
+        if self._is_torch(feat):
+            import torch
+            if not feat.is_cuda or feat.device.index != self.device:
+                raise ValueError("a torch feat must live on the context's GPU")
+            if feat.dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError("a torch feat must be float32 or bfloat16")
+            if feat.dim() != 2 or feat.shape[0] != self.n or (feat.shape[1] > 1 and feat.stride(1) != 1):
+                raise ValueError("feat must be [n, d] with a column stride of one element")
+            ldf = feat.stride(0) if feat.shape[0] > 1 else feat.shape[1]
+            return C.c_void_p(feat.data_ptr()), (PROP_BF16 if feat.dtype == torch.bfloat16 else PROP_F32), int(feat.shape[1]), int(ldf), True, feat
+        a = np.asarray(feat)
+        want = np.uint16 if bf16 else np.float32
+        if a.dtype != want:
+            raise ValueError("a numpy feat must be float32, or uint16 with bf16=True")
+        if a.ndim != 2 or a.shape[0] != self.n:
+            raise ValueError("feat must be [n, d]")
+        it = a.itemsize
+        if (a.shape[1] > 1 and a.strides[1] != it) or (a.shape[0] > 1 and (a.strides[0] % it or a.strides[0] < a.shape[1] * it)):
+            raise ValueError("feat: a column stride other than one element (or rows that overlap) is not supported")
+        ldf = a.strides[0] // it if a.shape[0] > 1 else a.shape[1]
+        return _p(a), (PROP_BF16 if bf16 else PROP_F32), int(a.shape[1]), int(ldf), False, a
+
+    def _prop_out(self, out, nq, d, dtype, on_device, name):
+        """(pointer, ldo, array) of a caller-made output ([nq, d], row stride = ldo) -- it must live where feat lives"""
+        if self._is_torch(out) != on_device:
+            raise ValueError(f"{name}: a torch tensor with a torch feat, a numpy array otherwise")
+        if on_device:
+            ok = out.dim() == 2 and tuple(out.shape) == (nq, d) and (d == 1 or out.stride(1) == 1) and out.is_cuda and out.device.index == self.device
+            ldo = out.stride(0) if nq > 1 else d
+            ptr = C.c_void_p(out.data_ptr())
+            ok = ok and out.dtype == dtype
+        else:
+            ok = out.ndim == 2 and out.shape == (nq, d) and out.dtype == dtype and (d == 1 or out.strides[1] == out.itemsize) and out.strides[0] % out.itemsize == 0
+            ldo = out.strides[0] // out.itemsize if nq > 1 else d
+            ptr = _p(out)
+        if not ok or ldo < d:
+            raise ValueError(f"{name} must be [nq, d] of the output's type with a column stride of one element")
+        return ptr, int(ldo)
+
+    def sparse_propagate(self, row_ptr, feat, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None):
+        """out = (held sparse rows) x feat (fora_hip_sparse_propagate, the PROPAGATE contract of include/fora_hip.h), on the held
+        result of query_sparse / query_seeds_sparse: out[i, c] = sum over the entries of row i of val * feat[id, c] in the
+        contract's fixed order, every bit defined.  row_ptr: as the sparse call returned it.  feat: a numpy float32 array
+        [n, d] (the row stride becomes ldf; a column stride other than one element is rejected), a numpy uint16 array with
+        bf16=True, or a torch tensor on the context's GPU (float32 or bfloat16, any row stride: a column slice of a wider
+        tensor is read in place).  normalize: every row divided by the sum of its kept values.  Returns
+        (out32 or None, out64 or None, stats dict): float32 / float64 [nq, d]; torch tensors on the device with a torch
+        feat, numpy arrays otherwise.  out32 / out64: caller-made outputs to fill instead (their row stride is ldo; columns
+        past d are left alone), both with the same row stride."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq = rp.size - 1
+        fptr, ftype, d, ldf, on_dev, _keep = self._prop_feat(feat, bf16)
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if out32 is None and want32:
+                out32 = torch.empty((nq, d), dtype=torch.float32, device=dev)
+            if out64 is None and want64:
+                out64 = torch.empty((nq, d), dtype=torch.float64, device=dev)
+            t32, t64 = torch.float32, torch.float64
+            torch.cuda.synchronize(dev)  # (feat may have been written, and the allocator may hand out memory, on another stream)
+        else:
+            if out32 is None and want32:
+                out32 = np.zeros((nq, d), dtype=np.float32)
+            if out64 is None and want64:
+                out64 = np.zeros((nq, d), dtype=np.float64)
+            t32, t64 = np.float32, np.float64
+        p32 = p64 = None
+        ldo = d
+        if out32 is not None:
+            p32, ldo = self._prop_out(out32, nq, d, t32, on_dev, "out32")
+        if out64 is not None:
+            p64, ldo64 = self._prop_out(out64, nq, d, t64, on_dev, "out64")
+            if out32 is not None and ldo64 != ldo:
+                raise ValueError("out32 and out64 must have the same row stride in elements")
+            ldo = ldo64
+        ps = PropStats()
+        self._chk(self._lib.fora_hip_sparse_propagate(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
+                                                      C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
+        return out32, out64, ps.as_dict()
+
+    def _propagate_chunks(self, total, chunk, feat, bf16, want32, want64, normalize, run):
+        """the frame of propagate / propagate_seeds: run(i0, i1) leaves the held sparse result of rows [i0, i1) and returns
+        its row_ptr; every chunk's product lands in its rows of one [total, d] output"""
+        _, _, d, _, on_dev, _keep = self._prop_feat(feat, bf16)
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out32 = torch.zeros((total, d), dtype=torch.float32, device=dev) if want32 else None
+            out64 = torch.zeros((total, d), dtype=torch.float64, device=dev) if want64 else None
+        else:
+            out32 = np.zeros((total, d), dtype=np.float32) if want32 else None
+            out64 = np.zeros((total, d), dtype=np.float64) if want64 else None
+        step = total if not chunk or chunk <= 0 else int(chunk)
+        props = []
+        for i0 in range(0, total, max(step, 1)):
+            i1 = min(total, i0 + step)
+            rp = run(i0, i1)
+            _, _, ps = self.sparse_propagate(rp, feat, normalize=normalize, bf16=bf16, want32=False, want64=False,
+                                             out32=None if out32 is None else out32[i0:i1], out64=None if out64 is None else out64[i0:i1])
+            props.append(ps)
+        return out32, out64, props
+
+    def propagate(self, sources, feat, with_idx=False, threshold=None, normalize=False, chunk=None, want32=True, want64=False, bf16=False):
+        """query_sparse then sparse_propagate, per chunk of `chunk` sources (None: all at once), into one [nq, d] output:
+        nothing sparse leaves the device.  REPLACES the held sparse result (the last chunk's rows stay held).  Returns a
+        dict: out32 / out64 (as sparse_propagate), stats (the per-query stats), prop (one stats dict per chunk)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+
+        def run(i0, i1):
+            rp = np.zeros(i1 - i0 + 1, dtype=np.int64)
+            part = (QueryStats * (i1 - i0)).from_buffer(st, i0 * C.sizeof(QueryStats))
+            self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)), C.c_double(thr),
+                                                            _p(rp), part, None))
+            return rp
+        out32, out64, props = self._propagate_chunks(nq, chunk, feat, bf16, want32, want64, normalize, run)
+        return {"out32": out32, "out64": out64, "stats": self._stats(st, nq), "prop": props}
+
+    def propagate_seeds(self, sets, weights, feat, with_idx=False, threshold=None, normalize=False, chunk=None, want32=True, want64=False,
+                        bf16=False):
+        """query_seeds_sparse then sparse_propagate, per chunk of `chunk` sets (None: all at once), into one [ns, d] output.
+        sets / weights as for query_seeds.  REPLACES the held sparse result.  Returns a dict: out32 / out64, prop."""
+        set_ptr, seeds, w = self._seed_sets(sets, weights)
+        ns = set_ptr.size - 1
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+
+        def run(i0, i1):
+            rp = np.zeros(i1 - i0 + 1, dtype=np.int64)
+            lo, hi = int(set_ptr[i0]), int(set_ptr[i1])
+            sp_ = np.ascontiguousarray(set_ptr[i0:i1 + 1] - lo)
+            sd_ = np.ascontiguousarray(seeds[lo:hi])
+            w_ = None if w is None else np.ascontiguousarray(w[lo:hi])
+            self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
+                                                            C.c_double(thr), _p(rp), None, None, None))
+            return rp
+        out32, out64, props = self._propagate_chunks(ns, chunk, feat, bf16, want32, want64, normalize, run)
+        return {"out32": out32, "out64": out64, "prop": props}
+
     # ---- local clustering (the SWEEP CUT contract of include/fora_hip.h)
     def sweep(self, sources, with_idx=False, threshold=None, max_size=0, want_profile=False, device=False):
         """query() followed on the GPU by the sweep over ppr / degree of every row (fora_hip_sweep_batch): the support
@@ -381,6 +545,19 @@ class Engine:
         if want_profile:
             out["ids"], out["cut"], out["vol"] = self.sweep_fetch(int(row_ptr[-1]))
         return out
+
+    def test_sparse_rows(self, rows_fix, threshold=0.0):
+        """query_sparse's compaction over caller-made rows ([nq, n] fixed-point words) instead of a query's
+        (fora_hip_test_sparse_rows): leaves a held sparse result of chosen row lengths.  Returns (row_ptr, sparse stats)."""
+        fix = np.ascontiguousarray(rows_fix, dtype=np.uint64)
+        if fix.ndim != 2 or fix.shape[1] != self.n:
+            raise ValueError("rows_fix must be [nq, n]")
+        nq = fix.shape[0]
+        sp = SparseStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        self._chk(self._test_entry("fora_hip_test_sparse_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(float(threshold)), _p(row_ptr),
+                                                                C.byref(sp)))
+        return row_ptr, sp.as_dict()
 
     def test_sweep_scan(self, diff, vol, nnz):
         """k_sweep_scan on one row (fora_hip_test_sweep_scan): diff (int64 differences of the cuts) and vol (uint64 per

@@ -9,6 +9,7 @@
 #include "fora_sweep.h"
 #include "fora_tables.h"
 #include "fora_rows.h"
+#include "fora_prop.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -29,7 +30,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -90,6 +91,7 @@ struct Tunables {
     int64_t sweep_lds_cap = SW_TILE_MAX; // sweep cut (fora_hip_sweep_batch): entries of a sort tile, rounded down to a power of two (at most SW_TILE_MAX); a row that fits one is sorted by one workgroup in LDS, a longer one takes the global tier; 0: every row does, every step in global memory.  Same bits for every value
     int64_t sweep_rows = 0;      // ... rows whose rank maps are live at a time (the rank block holds that many slabs of n words); 0: 256.  Same bits for every value
     int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
+    int64_t prop_segs = 0;       // PROPAGATE (fora_hip_sparse_propagate): segments whose partial sums are live at a time (a chunk of the call; the partial-sum buffer holds that many rows of d doubles); 0: by free memory, otherwise at least 1.  Same bits for every value
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -103,6 +105,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
     {"seeds_dedup", &Tunables::seeds_dedup, false}, {"seeds_rows", &Tunables::seeds_rows, false},
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
+    {"prop_segs", &Tunables::prop_segs, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -317,6 +320,16 @@ struct SweepResult : HeldRows {
     bool rank_dirty = false; // a call ended between a scatter and its reset
 };
 
+// PROPAGATE (fora_hip_sparse_propagate): buffers of the call in progress, kept between calls and grown when a call needs more
+// (free_prop: set_graph, destroy).  Apart from the sparse result they read.
+struct PropBufs {
+    DevBuf<unsigned char> d_feat;                        // a host `feat`, uploaded on every call
+    DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;   // the call's plan (fora_prop_plan.h)
+    DevBuf<double> d_part; DevBuf<uint64_t> d_segsum;    // partial sums [prop_segs][d] and word sums [prop_segs] of the chunk in progress
+    DevBuf<double> d_carry; DevBuf<uint64_t> d_scarry;   // [2][d] / [2]: the row a chunk cut, one buffer read and one written per chunk
+    DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays
+};
+
 // The loose words of the context, grouped by role.
 struct Params { // fora_hip_set_params / _raw
     bool have = false;
@@ -349,7 +362,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -359,7 +372,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr;
     int batch_req = 0;         // the caller's request (fora_hip_set_batch), not part of a plan
     uint64_t bin_launches = 0; // parity picks the counter set
     std::vector<QState> h_qs;
@@ -386,6 +399,7 @@ int fail(fora_ctx *c, int code, const std::string &msg) {
 void free_graph(fora_ctx *c) { c->g = Graph{}; }
 void free_sparse(fora_ctx *c) { c->sp = SparseResult{}; }
 void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
+void free_prop(fora_ctx *c) { c->pr = PropBufs{}; }
 void free_index(fora_ctx *c) { c->ix = Index{}; }
 void free_workspace(fora_ctx *c) { c->ws = Workspace{}; }
 
@@ -893,6 +907,8 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SW_COMPACT: t.sw_compact_ms += ms; break;     // the sweep's count / write / key passes: fora_sweep_stats only
         case EV_SW_SORT: t.sw_sort_ms += ms; break;           // k_sweep_sort_lds / k_sweep_sort_step: fora_sweep_stats only
         case EV_SW_CUT: t.sw_cut_ms += ms; break;             // scatter, k_sweep_cut, k_sweep_scan, reset: fora_sweep_stats only
+        case EV_PROP_GATHER: t.prop_gather_ms += ms; break;   // k_prop_gather: fora_prop_stats only
+        case EV_PROP_COMBINE: t.prop_combine_ms += ms; break; // k_prop_combine: fora_prop_stats only
         }
     }
     t.ev_used = 0;
@@ -2349,6 +2365,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_graph(c);
     free_sparse(c);
     free_sweep(c);
+    free_prop(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
     for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -2382,6 +2399,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_graph(c);
     free_sparse(c); // (rows of another graph)
     free_sweep(c);
+    free_prop(c); // (the upload of another graph's features)
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
@@ -2705,6 +2723,119 @@ int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix
     return FORA_OK;
 }
 
+// ---- PROPAGATE (the contract of include/fora_hip.h): the held sparse rows times a feature matrix, every bit defined
+static_assert(PROP_SEG == FORA_PROP_SEG, "fora_prop_plan.h and include/fora_hip.h name one segment length");
+extern "C++" { // (templates, and sparse_dest above is in scope here)
+namespace {
+// a grown-or-kept buffer of the call; no room is FORA_E_NOMEM and leaves no sticky HIP error behind
+template <typename T> int prop_ensure(fora_ctx *c, DevBuf<T> &b, size_t cnt, const char *what) {
+    if (b.ensure(std::max<size_t>(cnt, 1)) == hipSuccess) return FORA_OK;
+    (void)hipGetLastError();
+    return fail(c, FORA_E_NOMEM, std::string("no device memory for ") + what);
+}
+template <bool BF16, int V>
+void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
+    const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+    hipLaunchKernelGGL((k_prop_gather<BF16, V>), dim3((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles), dim3(BLOCK), 0, c->stream, segs, nseg,
+                       (const int32_t *)c->sp.d_ids.get(), (const uint64_t *)c->sp.d_fix.get(), feat, ldf, (uint32_t)d, g.G, part, segsum);
+}
+int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, float *out32, double *out64,
+              int64_t ldo, fora_prop_stats *ps) {
+    const bool bf16 = feat_type == FORA_PROP_BF16, normalize = (flags & FORA_PROP_NORMALIZE) != 0;
+    const uint32_t elt = bf16 ? 2 : 4;
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    bool feat_dev = false, o32_dev = false, o64_dev = false;
+    if (feat) if (int rc = sparse_dest(c, feat, feat_dev)) return rc;
+    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
+    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
+    PropBufs &b = c->pr;
+    // ---- the plan: chunks of prop_segs segments; 0: a quarter of the free memory in partial sums at most
+    const uint64_t total = prop_segments(row_ptr, nq);
+    size_t fr = 0, tot = 0;
+    if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, total, (uint64_t)fr, d);
+    const PropPlan plan = prop_plan(row_ptr, nq, per);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (entries && !feat_dev) {
+        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldf + (uint64_t)d) * elt);
+        if (int rc = prop_ensure(c, b.d_feat, bytes, "the feature upload")) return rc;
+        HIPCHK(c, hipMemcpy(b.d_feat.get(), feat, bytes, hipMemcpyHostToDevice));
+        feat = b.d_feat.get();
+    }
+    if (int rc = prop_ensure(c, b.d_segs, plan.segs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, b.d_recs, plan.recs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, b.d_part, (size_t)(per * (uint64_t)d), "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_segsum, (size_t)per, "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_carry, 2 * (size_t)d, "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_scarry, 2, "the partial sums")) return rc;
+    if (out32 && !o32_dev) if (int rc = prop_ensure(c, b.d_out32, (size_t)nq * (size_t)d, "a staged output")) return rc;
+    if (out64 && !o64_dev) if (int rc = prop_ensure(c, b.d_out64, (size_t)nq * (size_t)d, "a staged output")) return rc;
+    if (!plan.segs.empty()) HIPCHK(c, hipMemcpy(b.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b.d_recs.get(), plan.recs.data(), plan.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : b.d_out32.get();
+    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : b.d_out64.get();
+    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
+    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat, ldf, d, elt, bf16 ? widths_bf16 : widths_f32, 3);
+    uint64_t *const segsum = normalize ? b.d_segsum.get() : nullptr;
+    c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const PropChunk &ch = plan.chunks[ci];
+        if (ch.nseg) {
+            EvSpan ev(c, EV_PROP_GATHER);
+            const PropSeg *segs = b.d_segs.get() + ch.seg0;
+            if (!bf16) switch (g.V) {
+                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+            } else switch (g.V) {
+                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+            }
+        }
+        if (ch.nrec) {
+            EvSpan ev(c, EV_PROP_COMBINE);
+            const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
+            const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
+            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, (const PropRowRec *)(b.d_recs.get() + ch.rec0), ch.nrec,
+                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
+                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, o32_dev ? ldo : (int64_t)d, w64, o64_dev ? ldo : (int64_t)d);
+        }
+    }
+    if (out32 && !o32_dev) HIPCHK(c, hipMemcpy2DAsync(out32, (size_t)ldo * 4, w32, (size_t)d * 4, (size_t)d * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (out64 && !o64_dev) HIPCHK(c, hipMemcpy2DAsync(out64, (size_t)ldo * 8, w64, (size_t)d * 8, (size_t)d * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse propagate: ") + hipGetErrorString(err));
+    ev_collect(c);
+    if (ps) {
+        ps->entries = entries; ps->segments = total; ps->max_row = plan.max_row; ps->feat_bytes = entries * (uint64_t)d * elt;
+        ps->chunks = (int32_t)plan.chunks.size(); ps->feat_on_device = feat_dev ? 1 : 0;
+        ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+} // extern "C++"
+
+int fora_hip_sparse_propagate(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags,
+                              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate: negative nq or null row_ptr");
+    if (feat_type != FORA_PROP_F32 && feat_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate: unknown feat_type");
+    if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate: unknown flag");
+    if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate: d outside 1 .. 65536");
+    if (ldf < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate: a leading dimension smaller than d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate: no output");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate: row_ptr is not the held result's");
+    if (c->sp.entries && !feat) return fail(c, FORA_E_ARG, "sparse propagate: null feat");
+    if (ps) memset(ps, 0, sizeof(*ps));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, prop_impl(c, row_ptr, nq, feat, feat_type, d, ldf, flags, out32, out64, ldo, ps));
+}
+
 // ---- sweep cut: local clustering over the rows of a query (the SWEEP CUT contract of include/fora_hip.h)
 int fora_hip_sweep_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t max_size, int64_t *row_ptr,
                          fora_sweep_row *rows, fora_query_stats *stats, fora_sweep_stats *sw_out) {
@@ -2774,6 +2905,38 @@ int fora_hip_test_sweep_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, doub
             }
         }
         return sweep_finish(c, run, row_ptr, rows, sw_out);
+    });
+}
+
+// fora_hip_query_sparse_batch's frame in the same way: the caller's rows in the ppr slabs, counted, placed and held by the
+// library's own compaction -- a held sparse result of exactly chosen row lengths.
+int fora_hip_test_sparse_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t *row_ptr, fora_sparse_stats *sp_out) {
+    if (!c) return FORA_E_ARG;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
+    return with_bucket_retry(c, [&] {
+        SparseRun run;
+        run.thr = thr;
+        c->tm.sp_compact_ms = 0;
+        if (int rc = check_batch_args(c, reinterpret_cast<const int32_t *>(rows_fix), nq, "row")) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        const uint64_t n = (uint64_t)c->g.n;
+        run.lay.begin(nullptr, nq);
+        if (nq) {
+            if (int rc = ensure_query_workspace(c, nq, 0)) return rc;
+            const int per = even_batch(nq, c->ws.B);
+            if (int rc = sparse_prepare(c, run, std::min(per, nq), nq)) return rc;
+            for (int b0 = 0; b0 < nq; b0 += per) {
+                const int nb = std::min(per, nq - b0);
+                if ((uint64_t)nb * n > c->ws.d_ppr.size()) return fail(c, FORA_E_HIP, "test_sparse_rows: the batch does not fit the ppr slabs");
+                HIPCHK(c, hipMemcpyAsync(c->ws.d_ppr.get(), rows_fix + (uint64_t)b0 * n, (uint64_t)nb * n * 8, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+                if (int rc = count_rows(c, run, nullptr, nb, c->sp.cnt, EV_SP_COMPACT)) return rc;
+                HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
+                if (int rc = sparse_place(c, run, nullptr, b0, nb)) return rc;
+            }
+        }
+        return sparse_finish(c, run, row_ptr, sp_out);
     });
 }
 

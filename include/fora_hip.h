@@ -199,6 +199,40 @@
  *   - errors: those of SEED SETS, plus a NULL row_ptr and a bad threshold (FORA_E_ARG).  No device memory for the accumulator
  *     block, the rank block or the result: FORA_E_NOMEM, nothing held, the ctx still usable.
  *   - a held sparse result, the walk index, the options and the FORA parameters are left untouched; fora_timing as in SEED SETS.
+ * PROPAGATE (fora_hip_sparse_propagate): feature propagation Z = PI * H over the held sparse result of SPARSE RESULTS or SEED
+ * SETS, SPARSE -- out[i][c] = sum over the entries e of row i of w_e * H[id_e][c], computed on the GPU.  The order of the
+ * operations is fixed, so every output bit is defined (tests/propagate_ref.py is the twin).
+ *   - row i is the entries [row_ptr[i], row_ptr[i+1]) of the held result, in held order (ids ascending).  row_ptr (nq + 1
+ *     entries, host memory) is the caller's array as the sparse call returned it; it is validated -- row_ptr[0] == 0,
+ *     non-decreasing, row_ptr[nq] == the held entries -- and anything else is FORA_E_ARG.
+ *   - w_e = ldexp((double)fix_e, -62), the double fora_hip_sparse_fetch writes to vals (u64 -> f64 rounds to nearest even).
+ *     h = (double)H[id_e][c]; H is row-major, n rows (the graph's n) of d columns, leading dimension ldf >= d in elements;
+ *     feat_type FORA_PROP_F32: IEEE f32, FORA_PROP_BF16: bf16 widened exactly (bits << 16 as f32).  term_e = w_e * h is one
+ *     IEEE f64 multiply, never fused with the add that follows.
+ *   - segments: a row is cut every FORA_PROP_SEG = 256 entries counted from its first entry.  P_s = the terms of segment s
+ *     added one after the other in entry order, starting from +0.0.  acc = P_0, then acc = acc + P_s for s = 1, 2, ... in
+ *     order.  A row of at most 256 entries is a plain left-to-right sum; an empty row gives +0.0.
+ *   - flag FORA_PROP_NORMALIZE: S = the integer sum of the row's fix words (u64, wrapping; it cannot wrap in practice: at most
+ *     2^62 + 2^10 k for seed sets); acc = acc / ldexp((double)S, -62), one IEEE division, skipped when S == 0.
+ *   - out64[i*ldo + c] = acc; out32[i*ldo + c] = (float)acc, rounded to nearest even.  Either may be NULL, both NULL is
+ *     FORA_E_ARG.  ldo >= d; the columns d .. ldo of an output are not written.
+ *   - feat, out32 and out64 may each be pageable host memory or device memory on the ctx's GPU; a device pointer is read or
+ *     written by the device, never staged through the host; memory of another GPU is FORA_E_ARG.  A device feat needs only
+ *     element alignment: any base offset and any ldf are legal (a column slice of a wider tensor).  A host feat is uploaded
+ *     on every call into a buffer the ctx owns, which only grows and is freed by fora_hip_set_graph and fora_hip_destroy;
+ *     callers that propagate repeatedly pass device memory.  A host output is staged in nq * d elements of device memory.
+ *   - non-finite features follow the IEEE rules; nothing is checked.
+ *   - no bit depends on the batch size, on how the work is split across workgroups and lanes, on whether pointers are host or
+ *     device, or on the option "prop_segs" (segments whose partial sums are live at a time: a call runs in chunks of that many
+ *     segments; 0: by free memory, otherwise at least 1; readable from the environment like the other non-schedule knobs).
+ *   - stats: entries, segments = sum over the rows of ceil(len / 256), max_row, feat_bytes = entries * d * element size,
+ *     chunks = max(1, ceil(segments / prop_segs)), feat_on_device, and the device times of the two kernels.
+ *   - the held sparse result, a held sweep profile, the walk index, the options, the FORA parameters and fora_timing are left
+ *     untouched; the call may be repeated with other features.  The ctx's stream is synchronised before it returns.
+ *   - NULL ctx: answered without touching the GPU.  No held sparse result, nq < 0, NULL row_ptr, a row_ptr that does not match
+ *     the held result, NULL feat with entries to read, d < 1 or d > 65536, ldf < d, ldo < d, an unknown feat_type or flag bit:
+ *     FORA_E_ARG, and nothing is written.  No device memory for the upload, the partial sums or a staged output:
+ *     FORA_E_NOMEM, nothing written, the ctx still usable and the held result intact.  nq == 0: FORA_OK, nothing is written.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -390,6 +424,18 @@ int fora_hip_query_sparse_batch(fora_ctx *ctx, const int32_t *sources, int nq, i
 int fora_hip_sparse_fetch(fora_ctx *ctx, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap);
 int fora_hip_sparse_clear(fora_ctx *ctx);
 
+/* ---- feature propagation over the held sparse result (the PROPAGATE contract above): out = rows * feat, nq x d, in a fixed
+ * order of operations.  feat: n x d elements of feat_type, row-major with pitch ldf; out32 / out64: nq x d with pitch ldo. */
+#define FORA_PROP_SEG 256
+enum { FORA_PROP_F32 = 0, FORA_PROP_BF16 = 1 };
+enum { FORA_PROP_NORMALIZE = 1 };
+typedef struct { uint64_t entries, segments, max_row, feat_bytes; /* entries * d * element size */
+                 int32_t chunks, feat_on_device; double gather_ms, combine_ms; } fora_prop_stats;
+int fora_hip_sparse_propagate(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                              const void *feat, int feat_type, int d, int64_t ldf, int flags,
+                              float *out32 /*or NULL*/, double *out64 /*or NULL*/, int64_t ldo,
+                              fora_prop_stats *ps /*or NULL*/);
+
 /* ---- local clustering (the SWEEP CUT contract above): fora_hip_query_batch, then per row the sweep over ppr / degree and
  * its best cut, all on the GPU.  The profile stays with the ctx until fetched or replaced. */
 int fora_hip_sweep_batch(fora_ctx *ctx, const int32_t *sources, int nq, int with_idx, double threshold,
@@ -523,7 +569,14 @@ int fora_hip_get_stamps(fora_ctx *ctx, uint64_t *out32);
  *   int fora_hip_test_sweep_scan(fora_ctx *ctx, int64_t *diff_cut (L, in: differences, out: cuts), uint64_t *vol (L, in:
  *                                per position, out: prefix sums), int64_t L, uint64_t nnz, uint64_t *out6);
  *     k_sweep_scan on one row of length L under the denominator min(vol, nnz - vol); out6 = len, best, cut, vol, den, edges of
- *     the row it wrote.  Uses buffers of its own: a held profile is left alone. */
+ *     the row it wrote.  Uses buffers of its own: a held profile is left alone.
+ *
+ *   int fora_hip_test_sparse_rows(fora_ctx *ctx, const uint64_t *rows_fix (nq * n words), int nq, double threshold,
+ *                                 int64_t *row_ptr (nq + 1, required), fora_sparse_stats *sp (or NULL));
+ *     fora_hip_query_sparse_batch with the caller's rows in place of a query's: the rows are copied into the ppr slabs batch
+ *     by batch (fora_hip_set_batch is honoured) and counted, placed and held by the library's own compaction.  Every row
+ *     takes a slot.  Leaves a held sparse result of exactly chosen row lengths for fora_hip_sparse_fetch and
+ *     fora_hip_sparse_propagate. */
 
 #ifdef __cplusplus
 }
