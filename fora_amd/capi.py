@@ -22,7 +22,7 @@ SYMBOLS = [
     "fora_hip_query_seeds_batch",
     "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
     "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
-    "fora_hip_sparse_propagate",
+    "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -106,6 +106,15 @@ class SweepStats(C.Structure):
 class PropStats(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("feat_bytes", C.c_uint64),
                 ("chunks", C.c_int32), ("feat_on_device", C.c_int32), ("gather_ms", C.c_double), ("combine_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PropTStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("columns", C.c_uint64), ("segments", C.c_uint64), ("max_col", C.c_uint64), ("feat_bytes", C.c_uint64),
+                ("chunks", C.c_int32), ("feat_on_device", C.c_int32), ("built", C.c_int32), ("short_cols", C.c_int32), ("lds_cols", C.c_int32),
+                ("global_cols", C.c_int32), ("transpose_ms", C.c_double), ("gather_ms", C.c_double), ("combine_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -328,27 +337,30 @@ class Engine:
     def _is_torch(x):
         return type(x).__module__.split(".")[0] == "torch"
 
-    def _prop_feat(self, feat, bf16):
-        """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate"""
+    def _prop_feat(self, feat, bf16, rows=None, name="feat"):
+        """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate ([n, d]), or with
+        rows / name of the grad argument of sparse_propagate_t ([nq, d])"""
+        shape = "[n, d]" if rows is None else "[nq, d]"
+        rows = self.n if rows is None else rows
         if self._is_torch(feat):
             import torch
             if not feat.is_cuda or feat.device.index != self.device:
-                raise ValueError("a torch feat must live on the context's GPU")
+                raise ValueError(f"a torch {name} must live on the context's GPU")
             if feat.dtype not in (torch.float32, torch.bfloat16):
-                raise ValueError("a torch feat must be float32 or bfloat16")
-            if feat.dim() != 2 or feat.shape[0] != self.n or (feat.shape[1] > 1 and feat.stride(1) != 1):
-                raise ValueError("feat must be [n, d] with a column stride of one element")
+                raise ValueError(f"a torch {name} must be float32 or bfloat16")
+            if feat.dim() != 2 or feat.shape[0] != rows or (feat.shape[1] > 1 and feat.stride(1) != 1):
+                raise ValueError(f"{name} must be {shape} with a column stride of one element")
             ldf = feat.stride(0) if feat.shape[0] > 1 else feat.shape[1]
             return C.c_void_p(feat.data_ptr()), (PROP_BF16 if feat.dtype == torch.bfloat16 else PROP_F32), int(feat.shape[1]), int(ldf), True, feat
         a = np.asarray(feat)
         want = np.uint16 if bf16 else np.float32
         if a.dtype != want:
-            raise ValueError("a numpy feat must be float32, or uint16 with bf16=True")
-        if a.ndim != 2 or a.shape[0] != self.n:
-            raise ValueError("feat must be [n, d]")
+            raise ValueError(f"a numpy {name} must be float32, or uint16 with bf16=True")
+        if a.ndim != 2 or a.shape[0] != rows:
+            raise ValueError(f"{name} must be {shape}")
         it = a.itemsize
         if (a.shape[1] > 1 and a.strides[1] != it) or (a.shape[0] > 1 and (a.strides[0] % it or a.strides[0] < a.shape[1] * it)):
-            raise ValueError("feat: a column stride other than one element (or rows that overlap) is not supported")
+            raise ValueError(f"{name}: a column stride other than one element (or rows that overlap) is not supported")
         ldf = a.strides[0] // it if a.shape[0] > 1 else a.shape[1]
         return _p(a), (PROP_BF16 if bf16 else PROP_F32), int(a.shape[1]), int(ldf), False, a
 
@@ -384,34 +396,91 @@ class Engine:
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
         nq = rp.size - 1
         fptr, ftype, d, ldf, on_dev, _keep = self._prop_feat(feat, bf16)
-        if on_dev:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if out32 is None and want32:
-                out32 = torch.empty((nq, d), dtype=torch.float32, device=dev)
-            if out64 is None and want64:
-                out64 = torch.empty((nq, d), dtype=torch.float64, device=dev)
-            t32, t64 = torch.float32, torch.float64
-            torch.cuda.synchronize(dev)  # (feat may have been written, and the allocator may hand out memory, on another stream)
-        else:
-            if out32 is None and want32:
-                out32 = np.zeros((nq, d), dtype=np.float32)
-            if out64 is None and want64:
-                out64 = np.zeros((nq, d), dtype=np.float64)
-            t32, t64 = np.float32, np.float64
-        p32 = p64 = None
-        ldo = d
-        if out32 is not None:
-            p32, ldo = self._prop_out(out32, nq, d, t32, on_dev, "out32")
-        if out64 is not None:
-            p64, ldo64 = self._prop_out(out64, nq, d, t64, on_dev, "out64")
-            if out32 is not None and ldo64 != ldo:
-                raise ValueError("out32 and out64 must have the same row stride in elements")
-            ldo = ldo64
+        out32, out64, p32, p64, ldo = self._prop_outputs(nq, d, on_dev, want32, want64, out32, out64)
         ps = PropStats()
         self._chk(self._lib.fora_hip_sparse_propagate(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
                                                       C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
         return out32, out64, ps.as_dict()
+
+    def _prop_outputs(self, rows, d, on_dev, want32, want64, out32, out64):
+        """the outputs of sparse_propagate / sparse_propagate_t ([rows, d]): made here where the caller brought none, on the
+        device (after a device synchronise) with on_dev.  Returns (out32, out64, pointer32, pointer64, ldo)."""
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if out32 is None and want32:
+                out32 = torch.empty((rows, d), dtype=torch.float32, device=dev)
+            if out64 is None and want64:
+                out64 = torch.empty((rows, d), dtype=torch.float64, device=dev)
+            t32, t64 = torch.float32, torch.float64
+            torch.cuda.synchronize(dev)  # (feat may have been written, and the allocator may hand out memory, on another stream)
+        else:
+            if out32 is None and want32:
+                out32 = np.zeros((rows, d), dtype=np.float32)
+            if out64 is None and want64:
+                out64 = np.zeros((rows, d), dtype=np.float64)
+            t32, t64 = np.float32, np.float64
+        p32 = p64 = None
+        ldo = d
+        if out32 is not None:
+            p32, ldo = self._prop_out(out32, rows, d, t32, on_dev, "out32")
+        if out64 is not None:
+            p64, ldo64 = self._prop_out(out64, rows, d, t64, on_dev, "out64")
+            if out32 is not None and ldo64 != ldo:
+                raise ValueError("out32 and out64 must have the same row stride in elements")
+            ldo = ldo64
+        return out32, out64, p32, p64, ldo
+
+    def sparse_propagate_t(self, row_ptr, grad, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None):
+        """out = (held sparse rows)^T x grad (fora_hip_sparse_propagate_t, the PROPAGATE, TRANSPOSED contract of
+        include/fora_hip.h): out[v, c] = sum over the held entries whose id is v, by ascending row, of val * grad[row, c] --
+        the gradient of a loss with respect to the feat of sparse_propagate when grad is its gradient with respect to the
+        output.  grad: [nq, d], a numpy float32 array (uint16 with bf16=True) or a torch tensor on the context's GPU, with the
+        conventions of sparse_propagate's feat.  normalize: every value divided by the sum of its row's kept values (the
+        adjoint of sparse_propagate(normalize=True)).  Returns (out32 or None, out64 or None, stats dict): [n, d], torch
+        tensors on the device with a torch grad, numpy arrays otherwise.  The first call on a held result builds its
+        transposition (stats["built"] == 1), later calls reuse it."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq = rp.size - 1
+        gptr, gtype, d, ldg, on_dev, _keep = self._prop_feat(grad, bf16, rows=nq, name="grad")
+        out32, out64, p32, p64, ldo = self._prop_outputs(self.n, d, on_dev, want32, want64, out32, out64)
+        ps = PropTStats()
+        self._chk(self._lib.fora_hip_sparse_propagate_t(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
+                                                        C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
+        return out32, out64, ps.as_dict()
+
+    def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
+        """The transposition of the held sparse result (fora_hip_sparse_transpose_fetch): (col_ptr, rows, vals), with want_fix
+        (col_ptr, rows, vals, fix) -- a CSR over the n nodes, column v listing the rows that keep v in ascending order.
+        device=False: numpy arrays (int64, int32, float64, uint64); device=True: torch tensors on the context's GPU (fix as
+        int64 bits), as for query_sparse."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        if device:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("sparse_transpose_fetch(device=True): torch sees no GPU here.  torch and libfora_hip.so must "
+                                   "share one HIP runtime: import torch before the first Engine is created")
+            dev = torch.device("cuda", self.device)
+            col_ptr = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+            rows = torch.empty(e, dtype=torch.int32, device=dev)
+            vals = torch.empty(e, dtype=torch.float64, device=dev)
+            fix = torch.empty(e, dtype=torch.int64, device=dev) if want_fix else None
+            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            col_ptr = np.zeros(self.n + 1, dtype=np.int64)
+            rows = np.zeros(e, dtype=np.int32)
+            vals = np.zeros(e, dtype=np.float64)
+            fix = np.zeros(e, dtype=np.uint64) if want_fix else None
+            ptr = _p
+        self._chk(self._lib.fora_hip_sparse_transpose_fetch(self._ctx, _p(rp), C.c_int(nq), ptr(col_ptr), ptr(rows), ptr(fix), ptr(vals),
+                                                            C.c_uint64(e)))
+        return (col_ptr, rows, vals) + ((fix,) if want_fix else ())
 
     def _propagate_chunks(self, total, chunk, feat, bf16, want32, want64, normalize, run):
         """the frame of propagate / propagate_seeds: run(i0, i1) leaves the held sparse result of rows [i0, i1) and returns

@@ -10,6 +10,7 @@
 #include "fora_tables.h"
 #include "fora_rows.h"
 #include "fora_prop.h"
+#include "fora_propt.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -30,7 +31,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -92,6 +93,7 @@ struct Tunables {
     int64_t sweep_rows = 0;      // ... rows whose rank maps are live at a time (the rank block holds that many slabs of n words); 0: 256.  Same bits for every value
     int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
     int64_t prop_segs = 0;       // PROPAGATE (fora_hip_sparse_propagate): segments whose partial sums are live at a time (a chunk of the call; the partial-sum buffer holds that many rows of d doubles); 0: by free memory, otherwise at least 1.  Same bits for every value
+    int64_t propt_lds_cap = PROPT_LDS_MAX; // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t): keys of a column's run that one workgroup sorts in LDS at most (clamped to 0 .. PROPT_LDS_MAX); a longer run takes the global tier, one of at most 64 keys a wave; 0: every run of two keys or more takes the global tier.  Same bits for every value; a change drops the cached transposition
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -105,7 +107,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"tgt_lanes", &Tunables::tgt_lanes, false}, {"tgt_span", &Tunables::tgt_span, false},
     {"seeds_dedup", &Tunables::seeds_dedup, false}, {"seeds_rows", &Tunables::seeds_rows, false},
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
-    {"prop_segs", &Tunables::prop_segs, false},
+    {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -329,6 +331,19 @@ struct PropBufs {
     DevBuf<double> d_carry; DevBuf<uint64_t> d_scarry;   // [2][d] / [2]: the row a chunk cut, one buffer read and one written per chunk
     DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays
 };
+// PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
+// result, built by the first of the two calls after a result becomes held and kept with it -- it ends wherever the held
+// result ends (sparse_unheld, free_sparse) and when the option "propt_lds_cap" changes.  Complete or empty: the builder fills
+// a local value and moves it in after its last step.
+struct PropTBufs {
+    bool built = false;
+    DevBuf<int32_t> d_rows; DevBuf<uint64_t> d_fix;      // [entries] the row and the held word of every entry, column by column
+    DevBuf<int64_t> d_col_ptr; std::vector<int64_t> h_col_ptr; // [n + 1] and its host copy (the product is planned from it)
+    DevBuf<uint64_t> d_rsum;                             // [nq] S_i, the wrapping sum of row i's words
+    int nq = 0;                                          // rows of the row_ptr it was built from
+    uint64_t columns = 0, max_col = 0;
+    uint32_t short_cols = 0, lds_cols = 0, global_cols = 0;
+};
 
 // The loose words of the context, grouped by role.
 struct Params { // fora_hip_set_params / _raw
@@ -362,7 +377,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -372,8 +387,9 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr;
-    int batch_req = 0;         // the caller's request (fora_hip_set_batch), not part of a plan
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt;
+    uint64_t sparse_gen = 0;   // fora_hip_get_option "sparse_generation": counts the times a sparse result became held or stopped being held
+    int batch_req = 0;        // the caller's request (fora_hip_set_batch), not part of a plan
     uint64_t bin_launches = 0; // parity picks the counter set
     std::vector<QState> h_qs;
     Params par; Balanced bal; TeamState team_run; BucketRetry retry; Timing tm;
@@ -397,7 +413,13 @@ int fail(fora_ctx *c, int code, const std::string &msg) {
 
 // every buffer of the group freed, every field of it back at its initialiser
 void free_graph(fora_ctx *c) { c->g = Graph{}; }
-void free_sparse(fora_ctx *c) { c->sp = SparseResult{}; }
+// the held sparse result stops being held (its arrays stay): the generation moves, the transposition built from it goes
+void sparse_unheld(fora_ctx *c) {
+    if (c->sp.valid) c->sparse_gen++;
+    c->sp.valid = false; c->sp.entries = 0;
+    if (c->pt.built) { (void)hipSetDevice(c->device); c->pt = PropTBufs{}; }
+}
+void free_sparse(fora_ctx *c) { sparse_unheld(c); c->sp = SparseResult{}; }
 void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
 void free_prop(fora_ctx *c) { c->pr = PropBufs{}; }
 void free_index(fora_ctx *c) { c->ix = Index{}; }
@@ -909,6 +931,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SW_CUT: t.sw_cut_ms += ms; break;             // scatter, k_sweep_cut, k_sweep_scan, reset: fora_sweep_stats only
         case EV_PROP_GATHER: t.prop_gather_ms += ms; break;   // k_prop_gather: fora_prop_stats only
         case EV_PROP_COMBINE: t.prop_combine_ms += ms; break; // k_prop_combine: fora_prop_stats only
+        case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
     t.ev_used = 0;
@@ -1341,6 +1364,7 @@ struct RowsRun {
 
 // what every entry point that makes a held result starts with: the held one ends here, whatever becomes of this call
 int held_rows_begin(fora_ctx *c, HeldRows &held, const int64_t *row_ptr, double threshold, uint64_t &thr) {
+    if (&held == static_cast<HeldRows *>(&c->sp)) sparse_unheld(c);
     held.valid = false; held.entries = 0;
     if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
     if (!threshold_ok(threshold)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
@@ -1416,6 +1440,7 @@ template <typename Single> int finish_rows(fora_ctx *c, const RowLayout &lay, He
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     ev_collect(c);
     held.entries = lay.cur; held.valid = true;
+    if (&held == static_cast<HeldRows *>(&c->sp)) c->sparse_gen++;
     memcpy(row_ptr, lay.row_ptr.data(), ((size_t)lay.nq + 1) * 8);
     return FORA_OK;
 }
@@ -2471,6 +2496,7 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
         (void)hipSetDevice(c->device);
         free_workspace(c);
         c->opt_ = tunables_from_env();
+        c->pt = PropTBufs{}; // (built under another "propt_lds_cap", for all we know)
         c->team_run.suspend = 0; // (a time-out's back-off too)
         apply_options(c);
         return FORA_OK;
@@ -2482,6 +2508,7 @@ int fora_hip_set_option(fora_ctx *c, const char *name, int64_t value) {
             if (c->opt_.*(o.field) == value) return FORA_OK;
             c->opt_.*(o.field) = value;
             if (o.layout) { (void)hipSetDevice(c->device); free_workspace(c); }
+            if (o.field == &Tunables::propt_lds_cap) { (void)hipSetDevice(c->device); c->pt = PropTBufs{}; } // the next transposed call builds again, on the new tiers
             apply_options(c);
             return FORA_OK;
         }
@@ -2498,6 +2525,7 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "bucket_retries")) { *value = (int64_t)c->retry.retries; return FORA_OK; } // re-runs with doubled message buckets
     if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_run.fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
     if (!strcmp(name, "team_suspended")) { *value = c->team_run.suspend; return FORA_OK; }             // calls left that do not try the team push
+    if (!strcmp(name, "sparse_generation")) { *value = (int64_t)c->sparse_gen; return FORA_OK; }    // moves whenever a sparse result becomes held or stops being held
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
     if (!strcmp(name, "walk_dg_wgs_per_cu")) { // k_walk_dg's resident workgroups per CU at this graph's tables (0: the graph has no degree-grouped copy)
         const WalkDG &g = c->g.walk.dg;
@@ -2693,6 +2721,24 @@ static int sparse_dest(fora_ctx *c, const void *p, bool &on_device) {
     return FORA_OK;
 }
 
+// e held words (device) as doubles into vals, on the ctx's stream: converted in place for device memory, SP_STAGE at a time
+// through the sparse result's stage buffer for a host array
+static int fetch_vals(fora_ctx *c, const uint64_t *words, uint64_t e, double *vals, bool vals_on_device) {
+    constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
+    const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
+    if (vals_on_device) {
+        hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, words, e, vals);
+        return FORA_OK;
+    }
+    HIPCHK(c, c->sp.d_stage.ensure(SP_STAGE));
+    for (uint64_t at = 0; at < e; at += SP_STAGE) {
+        const uint64_t len = std::min(SP_STAGE, e - at);
+        hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, words + at, len, c->sp.d_stage.get());
+        HIPCHK(c, hipMemcpyAsync(vals + at, c->sp.d_stage.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return FORA_OK;
+}
+
 int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap) {
     if (!c) return FORA_E_ARG;
     if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
@@ -2703,20 +2749,7 @@ int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix
     if (vals) if (int rc = sparse_dest(c, vals, vals_on_device)) return rc;
     if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->sp.d_ids.get(), e * 4, hipMemcpyDefault, c->stream));
     if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, c->sp.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
-    if (e && vals) {
-        constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
-        const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
-        if (vals_on_device) {
-            hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->sp.d_fix.get(), e, vals);
-        } else {
-            HIPCHK(c, c->sp.d_stage.ensure(SP_STAGE));
-            for (uint64_t at = 0; at < e; at += SP_STAGE) {
-                const uint64_t len = std::min(SP_STAGE, e - at);
-                hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->sp.d_fix.get() + at, len, c->sp.d_stage.get());
-                HIPCHK(c, hipMemcpyAsync(vals + at, c->sp.d_stage.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-    }
+    if (e && vals) if (int rc = fetch_vals(c, c->sp.d_fix.get(), e, vals, vals_on_device)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse fetch: ") + hipGetErrorString(err));
@@ -2733,31 +2766,45 @@ template <typename T> int prop_ensure(fora_ctx *c, DevBuf<T> &b, size_t cnt, con
     (void)hipGetLastError();
     return fail(c, FORA_E_NOMEM, std::string("no device memory for ") + what);
 }
+// One side of the product: which output rows are summed over which entries.  Forward: the held rows (ids: nodes, feat: the n
+// feature rows).  Transposed: the columns of the transposition (ids: the rows the entries came from, feat: the nq gradient rows).
+struct PropSide {
+    const int64_t *row_ptr; int rows;        // (host) the output rows' entries
+    uint64_t feat_rows;                      // rows of feat: the extent of a host feat's upload
+    const int32_t *ids; const uint64_t *fix; // (device) the entries
+    const uint64_t *rsum;                    // transposed and normalised: S by id, every weight divided by it in the gather; else null
+    bool divide;                             // forward and normalised: a row's sum divided by its word sum in the combine
+};
+struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
+
 template <bool BF16, int V>
-void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
+void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
     const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
-    hipLaunchKernelGGL((k_prop_gather<BF16, V>), dim3((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles), dim3(BLOCK), 0, c->stream, segs, nseg,
-                       (const int32_t *)c->sp.d_ids.get(), (const uint64_t *)c->sp.d_fix.get(), feat, ldf, (uint32_t)d, g.G, part, segsum);
+    const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
+    if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
+    else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
 }
-int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, float *out32, double *out64,
-              int64_t ldo, fora_prop_stats *ps) {
-    const bool bf16 = feat_type == FORA_PROP_BF16, normalize = (flags & FORA_PROP_NORMALIZE) != 0;
+// the product of one side with feat: plan, buffers, the two kernels chunk by chunk, the staged outputs; the stream is idle and
+// the event times are collected when it returns FORA_OK
+int prop_run(fora_ctx *c, const PropSide &sd, const void *feat, int feat_type, int d, int64_t ldf, float *out32, double *out64, int64_t ldo, PropRunStats &rs) {
+    const bool bf16 = feat_type == FORA_PROP_BF16;
     const uint32_t elt = bf16 ? 2 : 4;
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const int nq = sd.rows;
+    const uint64_t entries = (uint64_t)sd.row_ptr[nq];
     bool feat_dev = false, o32_dev = false, o64_dev = false;
     if (feat) if (int rc = sparse_dest(c, feat, feat_dev)) return rc;
     if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
     if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
     PropBufs &b = c->pr;
     // ---- the plan: chunks of prop_segs segments; 0: a quarter of the free memory in partial sums at most
-    const uint64_t total = prop_segments(row_ptr, nq);
+    const uint64_t total = prop_segments(sd.row_ptr, nq);
     size_t fr = 0, tot = 0;
     if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
     const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, total, (uint64_t)fr, d);
-    const PropPlan plan = prop_plan(row_ptr, nq, per);
+    const PropPlan plan = prop_plan(sd.row_ptr, nq, per);
     // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
     if (entries && !feat_dev) {
-        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldf + (uint64_t)d) * elt);
+        const size_t bytes = (size_t)(((sd.feat_rows - 1) * (uint64_t)ldf + (uint64_t)d) * elt);
         if (int rc = prop_ensure(c, b.d_feat, bytes, "the feature upload")) return rc;
         HIPCHK(c, hipMemcpy(b.d_feat.get(), feat, bytes, hipMemcpyHostToDevice));
         feat = b.d_feat.get();
@@ -2776,7 +2823,7 @@ int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int
     double *const w64 = !out64 ? nullptr : o64_dev ? out64 : b.d_out64.get();
     static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
     const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat, ldf, d, elt, bf16 ? widths_bf16 : widths_f32, 3);
-    uint64_t *const segsum = normalize ? b.d_segsum.get() : nullptr;
+    uint64_t *const segsum = sd.divide ? b.d_segsum.get() : nullptr;
     c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
     for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
         const PropChunk &ch = plan.chunks[ci];
@@ -2784,13 +2831,13 @@ int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int
             EvSpan ev(c, EV_PROP_GATHER);
             const PropSeg *segs = b.d_segs.get() + ch.seg0;
             if (!bf16) switch (g.V) {
-                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
             } else switch (g.V) {
-                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
             }
         }
         if (ch.nrec) {
@@ -2808,10 +2855,121 @@ int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse propagate: ") + hipGetErrorString(err));
     ev_collect(c);
+    rs.segments = total; rs.max_row = plan.max_row; rs.chunks = (int32_t)plan.chunks.size(); rs.feat_on_device = feat_dev ? 1 : 0;
+    return FORA_OK;
+}
+int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, float *out32, double *out64,
+              int64_t ldo, fora_prop_stats *ps) {
+    const PropSide sd{row_ptr, nq, (uint64_t)c->g.n, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0};
+    PropRunStats rs;
+    if (int rc = prop_run(c, sd, feat, feat_type, d, ldf, out32, out64, ldo, rs)) return rc;
     if (ps) {
-        ps->entries = entries; ps->segments = total; ps->max_row = plan.max_row; ps->feat_bytes = entries * (uint64_t)d * elt;
-        ps->chunks = (int32_t)plan.chunks.size(); ps->feat_on_device = feat_dev ? 1 : 0;
+        ps->entries = c->sp.entries; ps->segments = rs.segments; ps->max_row = rs.max_row;
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * (feat_type == FORA_PROP_BF16 ? 2 : 4);
+        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device;
         ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
+    }
+    return FORA_OK;
+}
+
+// ---- PROPAGATE, TRANSPOSED: the transposition of the held result (fora_propt.h, fora_propt_plan.h), built once per held result
+int propt_build(fora_ctx *c, const int64_t *row_ptr, int nq) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    PropTBufs t; // moved into the ctx after the last step; freed on every other way out
+    DevBuf<uint32_t> d_cnt; PinBuf<uint32_t> h_cnt; // counts per node, then the cursors of the place pass; their pinned landing area
+    DevBuf<uint64_t> d_key; DevBuf<int64_t> d_row_ptr; DevBuf<PropTRun> d_runs;
+    // ---- every buffer before the first launch
+    const char *what = "the transposition";
+    if (int rc = prop_ensure(c, t.d_rows, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_fix, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_col_ptr, (size_t)n + 1, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_rsum, (size_t)nq, what)) return rc;
+    if (int rc = prop_ensure(c, d_cnt, (size_t)n, what)) return rc;
+    if (int rc = prop_ensure(c, d_key, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, what)) return rc;
+    if (int rc = prop_ensure(c, d_runs, (size_t)propt_max_runs(n, entries), what)) return rc;
+    if (h_cnt.alloc((size_t)n) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the transposition's counts"); }
+    t.h_col_ptr.assign((size_t)n + 1, 0);
+    t.nq = nq;
+    c->tm.propt_transpose_ms = 0;
+    if (entries) {
+        const uint32_t wgs = (uint32_t)std::min<int>(nq, 65535);
+        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
+        EvSpan ev(c, EV_PROPT_TRANSPOSE);
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
+        HIPCHK(c, t.d_rsum.zero(c->stream, (size_t)nq));
+        hipLaunchKernelGGL(k_propt_count, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(),
+                           (const uint64_t *)c->sp.d_fix.get(), (uint32_t)n, d_cnt.get(), reinterpret_cast<unsigned long long *>(t.d_rsum.get()));
+        HIPCHK(c, hipMemcpyAsync(h_cnt.get(), d_cnt.get(), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
+        if (propt_scan(h_cnt.get(), (int64_t)n, t.h_col_ptr.data()) != entries) return fail(c, FORA_E_HIP, "sparse transpose: the counts do not add up to the held entries");
+        const PropTTiers tiers = propt_tiers(t.h_col_ptr.data(), (int64_t)n, c->opt_.propt_lds_cap);
+        if (tiers.runs.size() > d_runs.size()) return fail(c, FORA_E_HIP, "sparse transpose: more runs than the table holds");
+        t.columns = tiers.columns; t.max_col = tiers.max_col;
+        t.short_cols = tiers.n_short; t.lds_cols = tiers.n_lds; t.global_cols = tiers.n_global;
+        HIPCHK(c, hipMemcpyAsync(t.d_col_ptr.get(), t.h_col_ptr.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (!tiers.runs.empty()) HIPCHK(c, hipMemcpyAsync(d_runs.get(), tiers.runs.data(), tiers.runs.size() * sizeof(PropTRun), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
+        hipLaunchKernelGGL(k_propt_place, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), (uint32_t)n,
+                           (const int64_t *)t.d_col_ptr.get(), d_cnt.get(), d_key.get(), entries);
+        const PropTRun *r_short = d_runs.get(), *r_lds = r_short + tiers.n_short, *r_global = r_lds + tiers.n_lds;
+        if (tiers.n_short) hipLaunchKernelGGL(k_propt_sort_short, dim3((tiers.n_short + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, r_short, tiers.n_short, d_key.get());
+        if (tiers.n_lds) hipLaunchKernelGGL(k_propt_sort_lds, dim3(tiers.n_lds), dim3(BLOCK), 0, c->stream, r_lds, d_key.get());
+        if (tiers.n_global) {
+            const uint32_t P = propt_pow2(tiers.max_global);
+            const unsigned gx = (unsigned)std::min<uint32_t>(std::max<uint32_t>(1, P / 2 / BLOCK), 1024);
+            for (uint32_t r0 = 0; r0 < tiers.n_global; r0 += 65535) { // (a grid's y extent)
+                const dim3 grid(gx, std::min<uint32_t>(65535, tiers.n_global - r0));
+                for (uint32_t k = 2; k <= P; k <<= 1) {
+                    hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, 0u);
+                    for (uint32_t j = k >> 2; j; j >>= 1) hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, j);
+                }
+            }
+        }
+        hipLaunchKernelGGL(k_propt_fill, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const uint64_t *)d_key.get(), entries,
+                           (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const uint64_t *)c->sp.d_fix.get(), t.d_rows.get(), t.d_fix.get());
+        ev.end();
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (h_col_ptr and the tables go out of use)
+    } else {
+        HIPCHK(c, t.d_col_ptr.zero(c->stream, (size_t)n + 1));
+        HIPCHK(c, t.d_rsum.zero(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose: ") + hipGetErrorString(err));
+    ev_collect(c);
+    t.built = true;
+    c->pt = std::move(t);
+    return FORA_OK;
+}
+// the transposition of the held result, built now unless it is there; row_ptr has passed prop_row_ptr_ok
+int propt_ensure(fora_ctx *c, const int64_t *row_ptr, int nq, bool &built_now) {
+    built_now = false;
+    if (c->pt.built && c->pt.nq == nq) return FORA_OK;
+    c->pt = PropTBufs{};
+    if (int rc = propt_build(c, row_ptr, nq)) return rc;
+    built_now = true;
+    return FORA_OK;
+}
+int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, float *out32, double *out64,
+               int64_t ldo, fora_propt_stats *ps) {
+    bool dev = false; // (memory of another GPU is refused before anything is built)
+    if (grad) if (int rc = sparse_dest(c, grad, dev)) return rc;
+    if (out32) if (int rc = sparse_dest(c, out32, dev)) return rc;
+    if (out64) if (int rc = sparse_dest(c, out64, dev)) return rc;
+    bool built_now = false;
+    if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
+    const double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
+    const PropTBufs &t = c->pt;
+    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, (uint64_t)nq, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false};
+    PropRunStats rs;
+    if (int rc = prop_run(c, sd, grad, grad_type, d, ldg, out32, out64, ldo, rs)) return rc;
+    if (ps) {
+        ps->entries = c->sp.entries; ps->columns = t.columns; ps->segments = rs.segments; ps->max_col = t.max_col;
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * (grad_type == FORA_PROP_BF16 ? 2 : 4);
+        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device; ps->built = built_now ? 1 : 0;
+        if (built_now) { ps->short_cols = (int32_t)t.short_cols; ps->lds_cols = (int32_t)t.lds_cols; ps->global_cols = (int32_t)t.global_cols; }
+        ps->transpose_ms = transpose_ms; ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
     }
     return FORA_OK;
 }
@@ -2834,6 +2992,49 @@ int fora_hip_sparse_propagate(fora_ctx *c, const int64_t *row_ptr, int nq, const
     if (nq == 0) return FORA_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, prop_impl(c, row_ptr, nq, feat, feat_type, d, ldf, flags, out32, out64, ldo, ps));
+}
+
+// ---- PROPAGATE, TRANSPOSED (the contract of include/fora_hip.h): out = (held rows)^T * grad, n x d, the same fixed order
+int fora_hip_sparse_propagate_t(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags,
+                                float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate_t: negative nq or null row_ptr");
+    if (grad_type != FORA_PROP_F32 && grad_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown grad_type");
+    if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown flag");
+    if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate_t: d outside 1 .. 65536");
+    if (ldg < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate_t: a leading dimension smaller than d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate_t: no output");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate_t: row_ptr is not the held result's");
+    if (c->sp.entries && !grad) return fail(c, FORA_E_ARG, "sparse propagate_t: null grad");
+    if (ps) memset(ps, 0, sizeof(*ps));
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, propt_impl(c, row_ptr, nq, grad, grad_type, d, ldg, flags, out32, out64, ldo, ps));
+}
+
+int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *col_ptr, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse transpose fetch: row_ptr is not the held result's");
+    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, "cap is smaller than the held result");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool dev = false, vals_on_device = false;
+    if (col_ptr) if (int rc = sparse_dest(c, col_ptr, dev)) return rc;
+    if (rows) if (int rc = sparse_dest(c, rows, dev)) return rc;
+    if (fix) if (int rc = sparse_dest(c, fix, dev)) return rc;
+    if (vals) if (int rc = sparse_dest(c, vals, vals_on_device)) return rc;
+    bool built_now = false;
+    if (int rc = drop_pairs_unless_ok(c, propt_ensure(c, row_ptr, nq, built_now))) return rc;
+    const PropTBufs &t = c->pt;
+    const uint64_t e = c->sp.entries;
+    if (col_ptr) HIPCHK(c, hipMemcpyAsync(col_ptr, t.d_col_ptr.get(), ((size_t)c->g.n + 1) * 8, hipMemcpyDefault, c->stream));
+    if (e && rows) HIPCHK(c, hipMemcpyAsync(rows, t.d_rows.get(), e * 4, hipMemcpyDefault, c->stream));
+    if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, t.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
+    if (e && vals) if (int rc = fetch_vals(c, t.d_fix.get(), e, vals, vals_on_device)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose fetch: ") + hipGetErrorString(err));
+    return FORA_OK;
 }
 
 // ---- sweep cut: local clustering over the rows of a query (the SWEEP CUT contract of include/fora_hip.h)

@@ -2,6 +2,9 @@
 // in fora_prop_plan.h): out[i][c] = sum over the entries e of held row i of w_e * H[id_e][c], every bit defined.
 //   k_prop_gather   one lane group per (segment, column tile): P_s = the segment's terms added in entry order from +0.0,
 //                   in f64 registers, stored to the chunk's partial-sum buffer part[slot][d];
+//   k_prop_gather_t the same body over the transposition of the held result (PROPAGATE, TRANSPOSED; fora_propt.h builds it) when
+//                   every weight is divided by its row's word sum; without that division the transposed product runs
+//                   k_prop_gather itself, rows and columns swapped by the host;
 //   k_prop_combine  one lane per (row record, column): the row's P_s added in segment order, the carry of a row that a
 //                   chunk cut, the normalisation, the stores with the output's pitch.
 // Nothing here is fused: the file is compiled with -ffp-contract=off and the two kernels say so again themselves; there
@@ -65,9 +68,11 @@ __device__ __forceinline__ double prop_widen(const PropRaw<BF16, V> &r, int v) {
 // to PROP_INFLIGHT feature rows are issued before the first of them is widened and added; an entry past the group's
 // count loads nothing.  The adds follow the entry order, so the partial sum does not depend on G, V or the grid.
 // segsum (null: not wanted): the integer sum of the segment's words, by the groups of column tile 0.
-template <bool BF16, int V>
-__global__ void __launch_bounds__(BLOCK) k_prop_gather(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
-                                                       int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum) {
+// TNORM (the transposed product with FORA_PROP_NORMALIZE, k_prop_gather_t): the weight of an entry is its word divided by
+// the word sum of the row it came from, rsum[id] -- one IEEE division per entry, made where the word is converted.
+template <bool BF16, int V, bool TNORM>
+__device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
+                                                 int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum, const uint64_t *rsum) {
 #pragma clang fp contract(off)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t gl = lane & (G - 1u), grp = lane / G;
@@ -89,6 +94,7 @@ __global__ void __launch_bounds__(BLOCK) k_prop_gather(const PropSeg *segs, uint
             id_l = ids[first + base + gl];
             ssum += f;
             w_l = fix2d(f);
+            if constexpr (TNORM) w_l = w_l / fix2d(rsum[id_l]);
         }
         const uint32_t cnt = min(G, len - base);
         for (uint32_t k = 0; k < cnt; k += PROP_INFLIGHT) {
@@ -131,6 +137,18 @@ __global__ void __launch_bounds__(BLOCK) k_prop_gather(const PropSeg *segs, uint
         for (int v = 0; v < V; v++)
             if ((uint32_t)v < ncol) part[(uint64_t)slot * d + c0 + (uint32_t)v] = acc[v];
     }
+}
+template <bool BF16, int V>
+__global__ void __launch_bounds__(BLOCK) k_prop_gather(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
+                                                       int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum) {
+    prop_gather_body<BF16, V, false>(segs, nseg, ids, fix, feat, ldf, d, G, part, segsum, nullptr);
+}
+// the same over the transposition (ids: the rows of a column's entries, feat: the gradient), every weight divided by its row's
+// word sum
+template <bool BF16, int V>
+__global__ void __launch_bounds__(BLOCK) k_prop_gather_t(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
+                                                         int64_t ldf, uint32_t d, uint32_t G, double *part, const uint64_t *rsum) {
+    prop_gather_body<BF16, V, true>(segs, nseg, ids, fix, feat, ldf, d, G, part, nullptr, rsum);
 }
 
 // One lane per (row record, column) of a chunk.  grid = (column blocks, record groups): with d >= BLOCK a workgroup takes

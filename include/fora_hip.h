@@ -233,6 +233,52 @@
  *     the held result, NULL feat with entries to read, d < 1 or d > 65536, ldf < d, ldo < d, an unknown feat_type or flag bit:
  *     FORA_E_ARG, and nothing is written.  No device memory for the upload, the partial sums or a staged output:
  *     FORA_E_NOMEM, nothing written, the ctx still usable and the held result intact.  nq == 0: FORA_OK, nothing is written.
+ * PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): out = PI^T * G over the held sparse
+ * result, n x d -- with G = dL/dZ the gradient of the loss with respect to the H of PROPAGATE.  Every output bit is defined
+ * (tests/propagate_t_ref.py is the twin).
+ *   - the transposition: column v (a node, 0 <= v < n) lists the held entries whose id is v by ascending row index i.  A held
+ *     row lists a node at most once (duplicate sources are separate rows), so the order is strict and any correct construction
+ *     gives the same arrays: col_ptr (n + 1 prefix sums), rows[p] (the row index of entry p), fix[p] (its held word),
+ *     vals[p] = ldexp((double)fix[p], -62).  It is a stable counting sort of the held entries by id, made on the GPU.
+ *   - fora_hip_sparse_transpose_fetch copies these arrays; every pointer may be NULL, and may be pageable host memory or device
+ *     memory of the ctx's GPU.  cap < the held entries, no held result, a row_ptr that is not the held result's: FORA_E_ARG and
+ *     nothing is written.
+ *   - the product: out[v][c] = sum over column v's entries e, in that order, of w'_e * (double)G[row_e][c].  grad is row-major
+ *     nq x d with pitch ldg >= d; grad_type FORA_PROP_F32 or FORA_PROP_BF16 as for feat in PROPAGATE.  Without a flag
+ *     w'_e = ldexp((double)fix_e, -62).  With FORA_PROP_NORMALIZE w'_e = ldexp((double)fix_e, -62) / ldexp((double)S_i, -62), one
+ *     IEEE division, S_i the integer sum of the words of row i = row_e (u64, wrapping, as in PROPAGATE): the adjoint of the
+ *     normalised forward product.  term = w'_e * g is one IEEE f64 multiply, never fused with the add that follows.
+ *   - segments of FORA_PROP_SEG = 256 entries are counted from the column's first entry: P_s summed from +0.0 in entry order,
+ *     acc = P_0, then acc = acc + P_s for s = 1, 2, ... -- the PROPAGATE rule with "row" read as "column".  Nothing is divided
+ *     after the sum.
+ *   - all n output rows are written: a node no row keeps gets +0.0.  out64[v*ldo + c] = acc, out32 = (float)acc rounded to
+ *     nearest even; either may be NULL, the columns d .. ldo of an output row are left alone.  A row of grad whose held row is
+ *     empty is never read by a sum.  Non-finite values follow IEEE; nothing is checked.
+ *   - grad, out32 and out64 may each be host or device memory as in PROPAGATE.  A host grad is uploaded on every call,
+ *     (nq - 1) * ldg + d elements; a host output is staged in n * d elements.
+ *   - no bit depends on the batch size, on host versus device pointers, on the launch shape, on "prop_segs" (which chunks this
+ *     product as it chunks the forward one), on which sort tier a column took, or on the option "propt_lds_cap": a column's run
+ *     of 2 .. 64 entries is sorted by a wave, one of up to "propt_lds_cap" entries (default and at most 4096) by a workgroup in
+ *     LDS, a longer one in device memory; a run longer than the cap goes to device memory whatever its length, so 0 sends
+ *     every run of two entries or more there.
+ *   - lifetime: the transposition, the row sums S_i and a device copy of col_ptr are built by the first of the two calls after
+ *     a sparse result becomes held, kept with it and reused by later calls (built = 0, transpose_ms = 0).  They end with the
+ *     held result -- the next fora_hip_query_sparse_batch or fora_hip_seeds_sparse_batch (whatever that call returns),
+ *     fora_hip_sparse_clear, fora_hip_set_graph, fora_hip_destroy -- and when "propt_lds_cap" is set to another value (or the
+ *     options are reset), which leaves the held result alone.  row_ptr must be the array the sparse call returned, on every call.
+ *   - the held result, a held sweep profile, the walk index, the options, the FORA parameters and fora_timing are left
+ *     untouched by both calls; fora_hip_sparse_propagate gives the same bits before and after a transposition exists.
+ *   - stats: entries, columns = nodes with at least one entry, segments = sum over the columns of ceil(len / 256), max_col,
+ *     feat_bytes = entries * d * element size, chunks, feat_on_device, built, and -- when built -- the columns each tier
+ *     sorted (a column of one entry is sorted by none); transpose_ms spans the build, the host's prefix sum included.
+ *   - errors: the FORA_E_ARG cases of PROPAGATE (no held result, a bad row_ptr, d outside 1 .. 65536, ldg < d, ldo < d, an
+ *     unknown type or flag, both outputs NULL, memory of another GPU) and a NULL grad while the held result has entries:
+ *     nothing is written.  FORA_E_NOMEM: nothing written, no half-built transposition kept, the held result intact and the
+ *     ctx usable.  NULL ctx: answered without touching the GPU.  nq == 0 (an empty held result): FORA_OK, grad may be NULL,
+ *     the outputs are all +0.0.
+ *   - fora_hip_get_option "sparse_generation" (read-only): a counter that increases every time a sparse result becomes held
+ *     or stops being held; a caller that keeps a row_ptr across calls (an autograd function) compares it to know that the
+ *     held rows are still the ones it saw.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -435,6 +481,22 @@ int fora_hip_sparse_propagate(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, in
                               const void *feat, int feat_type, int d, int64_t ldf, int flags,
                               float *out32 /*or NULL*/, double *out64 /*or NULL*/, int64_t ldo,
                               fora_prop_stats *ps /*or NULL*/);
+
+/* ---- the transposed product over the held sparse result (the PROPAGATE, TRANSPOSED contract above): out = rows^T * grad,
+ * n x d, in a fixed order of operations -- the backward pass of fora_hip_sparse_propagate.  grad: nq x d elements of
+ * grad_type, row-major with pitch ldg; out32 / out64: n x d with pitch ldo. */
+typedef struct { uint64_t entries, columns /* nodes with >= 1 entry */, segments, max_col, feat_bytes;
+                 int32_t chunks, feat_on_device, built /* 1: this call built the transposition */,
+                 short_cols, lds_cols, global_cols;   /* columns sorted on each tier by the build (0 when built == 0) */
+                 double transpose_ms, gather_ms, combine_ms; } fora_propt_stats;
+int fora_hip_sparse_propagate_t(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                const void *grad /*nq x d*/, int grad_type, int d, int64_t ldg, int flags,
+                                float *out32 /*n x d or NULL*/, double *out64 /*n x d or NULL*/, int64_t ldo,
+                                fora_propt_stats *ps /*or NULL*/);
+/* copies the transposition of the held result; any of col_ptr / rows / fix / vals may be NULL; cap = entries each of rows /
+ * fix / vals can take, col_ptr takes n + 1 */
+int fora_hip_sparse_transpose_fetch(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                    int64_t *col_ptr /*n+1 or NULL*/, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap);
 
 /* ---- local clustering (the SWEEP CUT contract above): fora_hip_query_batch, then per row the sweep over ppr / degree and
  * its best cut, all on the GPU.  The profile stays with the ctx until fetched or replaced. */
