@@ -1,9 +1,12 @@
 // fora_consts.h -- the plain numbers that both the kernels (fora_kernels.h, fora_team.h) and the host-side table builders
-// (fora_tables.h) read.  No HIP: a plain C++ compiler takes this file.
+// (fora_tables.h) and call planners (fora_rows.h, fora_seeds_plan.h, fora_sweep_plan.h) read.  No HIP: a plain C++ compiler
+// takes this file.
 #pragma once
 #include <stdint.h>
 
 namespace fora {
+
+constexpr uint64_t FIX_ONE = 1ull << 62; // 1.0 of a ppr / residue word, and of a seed's weight
 
 constexpr uint32_t DEG_SAT = 0xFFFFFFu; // rowinfo low 24 bits: out-degree, saturating
 // bucketed push (graphs of up to MAX_BINS * BIN_SIZE nodes): increments are binned by target
@@ -35,6 +38,7 @@ constexpr uint32_t dg_ticket_tile(uint32_t x, uint32_t nw, uint32_t tstride, uin
 }
 
 constexpr int SP_TILE = 512; // k_sparse_count / k_sparse_write: ids per workgroup and step, two per lane (fora_rows.h sizes their grid by it)
+constexpr int SC_TILE = 512; // k_seed_combine: ids per workgroup and step, two per lane (fora_seeds_plan.h sizes its grid by it)
 
 // team push (fora_team.h)
 constexpr int TEAM_MAX = 32;                  // members of a team (5 bits of a target word)

@@ -9,6 +9,7 @@
 #include "fora_sweep.h"
 #include "fora_tables.h"
 #include "fora_rows.h"
+#include "fora_seeds_plan.h"
 #include "fora_prop.h"
 #include "fora_propt.h"
 #include "../../include/fora_hip.h"
@@ -288,7 +289,7 @@ struct BwdBufs {
 // Seed sets (fora_hip_query_seeds_batch): buffers of their own, apart from the workspace; grow-only, kept until set_graph or destroy.
 struct SeedBufs {
     DevBuf<uint64_t> d_acc;  // the accumulator block of a call, [ns][n] at 2^-62 (n changes with the graph: no slabs of the workspace's plan)
-    DevBuf<uint64_t> d_list; // use list of the batch in progress (SeedBatch::pack); the dangling seeds' triples after the last batch
+    DevBuf<uint64_t> d_list; // use list of the batch in progress (SeedBatch::pack, fora_seeds_plan.h); the dangling seeds' triples after the last batch
     DevBuf<unsigned long long> d_sums; // [ns] row sums
 };
 // A result over rows that stays on the device until it is fetched: the sparse rows and the sweep profiles.  Both lay their
@@ -1512,13 +1513,6 @@ struct SweepRun : RowsRun { // (lay.row_ptr: prefix sums of L)
     }
 };
 
-static uint32_t sweep_tile(const fora_ctx *c) { // entries of a sort tile; 1: no LDS step at all
-    const int64_t cap = std::min<int64_t>(c->opt_.sweep_lds_cap, SW_TILE_MAX);
-    uint32_t t = 1;
-    while ((int64_t)t * 2 <= cap) t *= 2;
-    return t;
-}
-
 // the rank block of min(live, sweep_rows) slabs, all -1
 int sweep_prepare_rank(fora_ctx *c, int live) {
     SweepResult &w = c->swp;
@@ -1561,47 +1555,27 @@ int sweep_rows_of_batch(fora_ctx *c, SweepRun &sw, const int *at, int r0, int nb
     if (int rc = count_rows(c, sw, rows, nb, w.cnt, EV_SW_COMPACT)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     EvSpan ev(c);
-    // layout: padded copies in the sort buffers, profiles in the held arrays
-    const uint32_t T = sweep_tile(c);
-    std::vector<SweepRowDesc> rd((size_t)nb);
-    std::vector<int64_t> tbase((size_t)nb);
-    std::vector<SweepTile> tiles;
-    std::vector<SweepGRow> grows;
-    uint64_t tneed = 0;
-    uint32_t maxP = 0, maxL = 0;
-    sw.lay.begin_batch();
-    for (int i = 0; i < nb; i++) {
-        const uint32_t len = w.cnt.h_tot.get()[i];
-        uint32_t P = len ? 1 : 0;
-        while (P < len) P *= 2; // (len <= n < 2^31)
-        const uint32_t L = sw.max_size > 0 ? (uint32_t)std::min<int64_t>(len, sw.max_size) : len;
-        rd[(size_t)i] = SweepRowDesc{(int64_t)tneed, sw.lay.place(row_of(i), len, L), len, P, L, 0};
-        tbase[(size_t)i] = (int64_t)tneed;
-        if (P > T) { grows.push_back(SweepGRow{(int64_t)tneed, P, 0}); sw.global_rows++; }
-        if (T >= 2) for (uint32_t off = 0; off < P; off += T) tiles.push_back(SweepTile{(int64_t)tneed + off, P, off});
-        tneed += P;
-        maxP = std::max(maxP, P); maxL = std::max(maxL, L);
-    }
+    // layout: padded copies in the sort buffers, profiles in the held arrays (fora_sweep_plan.h)
+    const uint32_t T = sweep_tile(c->opt_.sweep_lds_cap);
+    const SweepBatchPlan plan = sweep_batch_plan(w.cnt.h_tot.get(), nb, sw.max_size, T, sw.lay, at, r0);
+    const std::vector<SweepTile> &tiles = plan.tiles;
+    const std::vector<SweepGRow> &grows = plan.grows;
+    const uint32_t maxP = plan.maxP, maxL = plan.maxL;
+    sw.global_rows += (int)grows.size();
     if (int rc = sweep_reserve(c, sw.lay)) return rc;
-    if (w.d_tids.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess || w.d_tkey.ensure(std::max<uint64_t>(tneed, 1)) != hipSuccess) {
+    if (w.d_tids.ensure(std::max<uint64_t>(plan.tneed, 1)) != hipSuccess || w.d_tkey.ensure(std::max<uint64_t>(plan.tneed, 1)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, FORA_E_NOMEM, "no device memory for the sweep's sort buffers");
     }
     const uint64_t tcap = std::min(w.d_tids.size(), w.d_tkey.size()), hcap = w.d_ids.size();
-    // one upload: SweepRowDesc[nb] | base[nb] | SweepTile[] | SweepGRow[]
-    const size_t o_base = (size_t)nb * sizeof(SweepRowDesc) / 8, o_tile = o_base + (size_t)nb, o_grow = o_tile + tiles.size() * sizeof(SweepTile) / 8;
-    std::vector<uint64_t> pack(o_grow + grows.size() * sizeof(SweepGRow) / 8 + 1, 0);
-    memcpy(pack.data(), rd.data(), (size_t)nb * sizeof(SweepRowDesc));
-    memcpy(pack.data() + o_base, tbase.data(), (size_t)nb * 8);
-    if (!tiles.empty()) memcpy(pack.data() + o_tile, tiles.data(), tiles.size() * sizeof(SweepTile));
-    if (!grows.empty()) memcpy(pack.data() + o_grow, grows.data(), grows.size() * sizeof(SweepGRow));
-    HIPCHK(c, w.d_desc.ensure(pack.size()));
-    HIPCHK(c, hipMemcpyAsync(w.d_desc.get(), pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, w.d_desc.ensure(std::max<size_t>(plan.pack.size(), 1)));
+    HIPCHK(c, hipMemcpyAsync(w.d_desc.get(), plan.pack.data(), plan.pack.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
-    const SweepRowDesc *d_rd = (const SweepRowDesc *)w.d_desc.get();
-    const int64_t *d_base = (const int64_t *)(w.d_desc.get() + o_base);
-    const SweepTile *d_tiles = (const SweepTile *)(w.d_desc.get() + o_tile);
-    const SweepGRow *d_grows = (const SweepGRow *)(w.d_desc.get() + o_grow);
+    const SweepDescView<const uint64_t> dv = plan.view<const uint64_t>(w.d_desc.get());
+    const SweepRowDesc *d_rd = dv.rows();
+    const int64_t *d_base = dv.tbase();
+    const SweepTile *d_tiles = dv.tiles();
+    const SweepGRow *d_grows = dv.grows();
     const auto gx = [](uint64_t items) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + BLOCK - 1) / BLOCK, 128)); };
     if (maxP) {
         ev.begin(EV_SW_COMPACT);
@@ -1909,42 +1883,20 @@ int query_common(fora_ctx *c, const int32_t *sources, int nq, int with_idx, int 
 // ---- seed sets (fora_hip_query_seeds_batch; the SEED SETS contract of include/fora_hip.h).  PPR is linear in the restart
 // vector: every seed a call needs runs once as an ordinary query (run_query_batch), and k_seed_combine folds the batch's ppr
 // slabs into one accumulator row per set before the next batch reuses them.  Nothing of the push or the walks knows of sets.
-struct SeedUse { uint32_t set, slot; uint64_t w; }; // term of a set: the row of `slot` (of the call, then of its batch) times w / 2^62
-// The use list of one batch, sorted by set, as one upload: use_w[U] (u64), then use_slot[U] | seg[T + 1] | set_id[T] (u32).
-struct SeedBatch {
-    std::vector<SeedUse> uses;
-    std::vector<uint64_t> pack;
-    uint32_t U = 0, T = 0;
-    void build() {
-        U = (uint32_t)uses.size();
-        T = 0;
-        for (uint32_t i = 0; i < U; i++) T += i == 0 || uses[i].set != uses[i - 1].set;
-        pack.assign((size_t)U + ((size_t)U + 2 * (size_t)T + 2) / 2, 0);
-        uint32_t *slot = (uint32_t *)(pack.data() + U), *seg = slot + U, *set_id = seg + T + 1;
-        uint32_t t = 0;
-        for (uint32_t i = 0; i < U; i++) {
-            pack[i] = uses[i].w;
-            slot[i] = uses[i].slot;
-            if (i == 0 || uses[i].set != uses[i - 1].set) { seg[t] = i; set_id[t++] = uses[i].set; }
-        }
-        seg[T] = U;
-    }
-};
+// The planning of a call -- checks, weights, slots, batches and the words of the uploads -- is fora_seeds_plan.h.
 
 // the combine of the batch just closed: its slabs hold the rows until the next batch starts on the same stream
 int seed_combine(fora_ctx *c, const SeedBatch &b) {
     if (!b.U) return FORA_OK;
     HIPCHK(c, hipMemcpyAsync(c->sd.d_list.get(), b.pack.data(), b.pack.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
-    const uint64_t *use_w = c->sd.d_list.get();
-    const uint32_t *use_slot = (const uint32_t *)(use_w + b.U), *seg = use_slot + b.U, *set_id = seg + b.T + 1;
+    const SeedListView<const uint64_t> l = b.list(c->sd.d_list.get());
     const uint32_t n = (uint32_t)c->g.n;
-    const uint32_t R = (uint32_t)std::max<uint64_t>(2 * SC_TILE, (((uint64_t)n + 1023) / 1024 + SC_TILE - 1) / SC_TILE * SC_TILE); // at most 1024 workgroups per set
-    const unsigned X = (unsigned)(((uint64_t)n + R - 1) / R);
+    const CompactGeom geo = seed_combine_geom(n);
     EvSpan ev(c, EV_SEED_COMBINE);
     for (uint32_t y0 = 0; y0 < b.T; y0 += 65535)
-        hipLaunchKernelGGL(k_seed_combine, dim3(X, std::min<uint32_t>(65535, b.T - y0)), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), n, R,
-                           set_id + y0, seg + y0, use_slot, use_w, c->sd.d_acc.get());
+        hipLaunchKernelGGL(k_seed_combine, dim3(geo.X, std::min<uint32_t>(65535, b.T - y0)), dim3(BLOCK), 0, c->stream, (const uint64_t *)c->ws.d_ppr.get(), n, geo.R,
+                           l.set_id() + y0, l.seg() + y0, l.use_slot(), l.use_w(), c->sd.d_acc.get());
     return FORA_OK;
 }
 
@@ -1958,65 +1910,21 @@ struct SeedCounts { uint64_t seeds = 0, distinct = 0, queries = 0, dangling = 0;
 int seeds_accumulate(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
                      int k, bool want_topk, bool sweep, fora_seeds_stats *st, SeedCounts &sc) {
     if (int rc = check_batch_args(c, nullptr, 0)) return rc;
-    if (ns < 0) return fail(c, FORA_E_ARG, "bad sets: negative count");
-    if (st) memset(st, 0, sizeof(*st));
+    const char *bad = seed_sets_error(set_ptr, seeds, ns);
+    if (st && ns >= 0) memset(st, 0, sizeof(*st)); // (a negative count leaves *st as it was)
+    if (bad) return fail(c, FORA_E_ARG, bad);
     if (ns == 0) return FORA_OK;
-    if (!set_ptr || !seeds) return fail(c, FORA_E_ARG, "bad sets: null set_ptr or seeds");
-    if (set_ptr[0] != 0) return fail(c, FORA_E_ARG, "set_ptr[0] must be 0");
-    for (int g = 0; g < ns; g++)
-        if (set_ptr[g + 1] <= set_ptr[g]) return fail(c, FORA_E_ARG, set_ptr[g + 1] < set_ptr[g] ? "set_ptr decreases" : "empty seed set");
     const int64_t total = set_ptr[ns];
-    if (total > 0x7FFFFFFF) return fail(c, FORA_E_ARG, "more than 2^31 - 1 seeds in one call");
     if (with_idx && !c->ix.have) return fail(c, FORA_E_ARG, "with_idx without an index (build or set one)");
     if (k != 0) if (int rc = check_k(c, k)) return rc; // (0: no top-k)
     if (int rc = check_id_range(c, seeds, (int)total, "seed")) return rc;
-    // the weights at 2^-62
-    std::vector<uint64_t> wfix((size_t)total);
-    for (int g = 0; g < ns; g++) {
-        const int64_t j0 = set_ptr[g], kg = set_ptr[g + 1] - j0;
-        if (!weights) {
-            const uint64_t base = FIX_ONE / (uint64_t)kg, rem = FIX_ONE % (uint64_t)kg;
-            for (int64_t j = 0; j < kg; j++) wfix[(size_t)(j0 + j)] = base + ((uint64_t)j < rem ? 1 : 0);
-            continue;
-        }
-        double S = 0;
-        for (int64_t j = 0; j < kg; j++) {
-            const double w = weights[j0 + j];
-            if (!std::isfinite(w) || w < 0) return fail(c, FORA_E_ARG, "seed weights must be finite and >= 0");
-            S += w;
-        }
-        if (!(S > 0) || !std::isfinite(S)) return fail(c, FORA_E_ARG, "the weights of a seed set must have a finite sum > 0");
-        for (int64_t j = 0; j < kg; j++) wfix[(size_t)(j0 + j)] = (uint64_t)std::ldexp(weights[j0 + j] / S, 62);
-    }
+    std::vector<uint64_t> wfix;
+    if ((bad = seed_weights(set_ptr, weights, ns, wfix))) return fail(c, FORA_E_ARG, bad);
     HIPCHK(c, hipSetDevice(c->device));
     c->tm.seed_combine_ms = 0;
     const uint64_t n = (uint64_t)c->g.n;
-    // Slots: the seeds that run, in order of first appearance.  A dangling seed is its own whole answer (query_common) and
-    // takes none: its term is w at the seed itself.
-    const bool dedup = c->opt_.seeds_dedup != 0;
-    std::unordered_map<int32_t, uint32_t> slot_of; // seed id -> slot (with dedup; without: -> 0, the ids seen)
-    std::vector<int32_t> slot_src;
-    std::vector<SeedUse> uses;                     // the terms of the live seeds, by set
-    std::vector<uint32_t> dang_set; std::vector<int32_t> dang_node; std::vector<uint64_t> dang_w;
-    for (int g = 0; g < ns; g++)
-        for (int64_t j = set_ptr[g]; j < set_ptr[g + 1]; j++) {
-            const int32_t s = seeds[j];
-            const auto seen = slot_of.find(s);
-            if (is_dangling(c, s)) {
-                if (seen == slot_of.end()) slot_of.emplace(s, 0u);
-                dang_set.push_back((uint32_t)g); dang_node.push_back(s); dang_w.push_back(wfix[(size_t)j]);
-                continue;
-            }
-            uint32_t slot;
-            if (dedup && seen != slot_of.end()) slot = seen->second;
-            else {
-                slot = (uint32_t)slot_src.size();
-                slot_src.push_back(s);
-                if (seen == slot_of.end()) slot_of.emplace(s, slot);
-            }
-            uses.push_back(SeedUse{(uint32_t)g, slot, wfix[(size_t)j]});
-        }
-    const int nl = (int)slot_src.size();
+    const SeedSlots slots = seed_slots(set_ptr, seeds, wfix.data(), ns, c->g.h_row_ptr.data(), c->opt_.seeds_dedup != 0);
+    const int nl = (int)slots.slot_src.size();
     // The accumulator block, ahead of the workspace: a batch size chosen from the free memory then accounts for it.  No room
     // beside a workspace that is already there: that one goes, and the call plans a new one in what the block leaves.
     const uint64_t cells = (uint64_t)ns * n;
@@ -2040,33 +1948,28 @@ int seeds_accumulate(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
     if (nl > 0) {
         const int per = even_batch(nl, c->ws.B);
         nbatch = (nl + per - 1) / per;
-        std::vector<SeedBatch> batches((size_t)nbatch);
-        for (const SeedUse &u : uses) batches[u.slot / (uint32_t)per].uses.push_back(SeedUse{u.set, u.slot % (uint32_t)per, u.w}); // (in set order)
+        const std::vector<SeedBatch> batches = seed_batches(slots.uses, nl, per);
         size_t words = 0;
-        for (SeedBatch &b : batches) { b.build(); words = std::max(words, b.pack.size()); }
+        for (const SeedBatch &b : batches) words = std::max(words, b.pack.size());
         HIPCHK(c, c->sd.d_list.ensure(std::max<size_t>(words, 1)));
         for (int bi = 0; bi < nbatch; bi++) {
             const int b0 = bi * per, nb = std::min(per, nl - b0);
-            if ((rc = run_query_batch(c, slot_src.data() + b0, nb, with_idx != 0, 0))) return rc;
+            if ((rc = run_query_batch(c, slots.slot_src.data() + b0, nb, with_idx != 0, 0))) return rc;
             if ((rc = seed_combine(c, batches[(size_t)bi]))) return rc;
         }
     }
-    uint64_t *const acc = c->sd.d_acc.get();
-    const size_t nd = dang_set.size();
-    if (nd) { // w[nd] (u64), then set[nd] | node[nd] (32-bit)
-        std::vector<uint64_t> pack(nd + (2 * nd + 1) / 2, 0);
-        memcpy(pack.data(), dang_w.data(), nd * 8);
-        memcpy(pack.data() + nd, dang_set.data(), nd * 4);
-        memcpy((uint32_t *)(pack.data() + nd) + nd, dang_node.data(), nd * 4);
+    const size_t nd = slots.dang_set.size();
+    if (nd) {
+        const std::vector<uint64_t> pack = seed_dangling_pack(slots);
         HIPCHK(c, hipStreamSynchronize(c->stream)); // (the last combine reads the list)
         HIPCHK(c, c->sd.d_list.ensure(pack.size()));
         HIPCHK(c, hipMemcpyAsync(c->sd.d_list.get(), pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
-        const uint32_t *dset = (const uint32_t *)(c->sd.d_list.get() + nd);
-        hipLaunchKernelGGL(k_seed_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, dset, (const int32_t *)(dset + nd),
-                           (const uint64_t *)c->sd.d_list.get(), (uint32_t)n, acc);
+        const SeedDanglingView<const uint64_t> d{c->sd.d_list.get(), nd};
+        hipLaunchKernelGGL(k_seed_single, dim3((unsigned)((nd + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (uint32_t)nd, d.set(), d.node(), d.w(), (uint32_t)n,
+                           c->sd.d_acc.get());
     }
-    sc.seeds = (uint64_t)total; sc.distinct = (uint64_t)slot_of.size(); sc.queries = (uint64_t)nl; sc.dangling = (uint64_t)nd; sc.batches = nbatch;
+    sc.seeds = (uint64_t)total; sc.distinct = slots.distinct; sc.queries = (uint64_t)nl; sc.dangling = (uint64_t)nd; sc.batches = nbatch;
     return FORA_OK;
 }
 
@@ -2119,15 +2022,8 @@ int query_seeds_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, 
     return FORA_OK;
 }
 
-// rows of the finished block that fora_hip_seeds_sparse_batch / fora_hip_seeds_sweep_batch compact (and sort) at a time: the
-// option seeds_rows, at most what a grid's y takes.  k_sparse_count / k_sparse_write choose between 16-byte and 8-byte loads
-// from (q * n) & 1 and take their base for 16-byte aligned; a chunk starts at acc + r0 * n, an odd word when r0 * n is odd.
-// So with an odd n the count is rounded up to even: every chunk then starts at an even row.
-int seeds_chunk(const fora_ctx *c) {
-    int64_t C = std::min<int64_t>(std::max<int64_t>(c->opt_.seeds_rows, 1), 65534);
-    if ((c->g.n & 1) && (C & 1)) C++;
-    return (int)C;
-}
+// rows of the finished block that fora_hip_seeds_sparse_batch / fora_hip_seeds_sweep_batch compact (and sort) at a time
+int seeds_chunk(const fora_ctx *c) { return fora::seeds_chunk(c->opt_.seeds_rows, (uint64_t)c->g.n); }
 
 // one attempt of fora_hip_seeds_sparse_batch: the block, then count / place over its rows, every row live and no dangling one
 int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,

@@ -37,7 +37,6 @@ constexpr uint32_t WALK_SEG = 1024; // max walks per walk work item
 #define FORA_TEST_PATHS 0
 #endif
 constexpr bool TEST_PATHS = FORA_TEST_PATHS != 0;
-constexpr uint64_t FIX_ONE = 1ull << 62;
 constexpr int MAX_LEVELS = 1 << 15;
 #ifndef FORA_ACC_THREADS
 #define FORA_ACC_THREADS 512
@@ -3329,8 +3328,8 @@ __global__ void __launch_bounds__(BLOCK) k_sparse_vals(const uint64_t *fix, uint
 // launches of a call follow each other on one stream, so the update is a plain read-add-write.  A lane takes the two words
 // of one 16-byte line; a row (slot * n, set * n) that starts at an odd word is read (written) with 8-byte accesses instead
 // -- the choice is the same for every lane of the launch's workgroup.  SC_UNROLL uses are in flight per lane.
-constexpr int SC_TILE = 2 * BLOCK; // ids per workgroup and step
-constexpr int SC_UNROLL = 4;       // uses in flight per lane
+static_assert(SC_TILE == 2 * BLOCK, "ids per workgroup and step (fora_consts.h)");
+constexpr int SC_UNROLL = 4; // uses in flight per lane
 __device__ __forceinline__ void sc_load(const uint64_t *row, bool aligned, uint32_t v, uint32_t hi, uint64_t &a, uint64_t &b) {
     a = 0; b = 0;
     if (aligned && v + 1 < hi) {

@@ -15,10 +15,10 @@ inline bool threshold_ok(double threshold) { return threshold <= 1.0; }
 inline uint64_t threshold_word(double threshold) { return threshold > 0 ? std::max<uint64_t>(1, (uint64_t)std::ceil(std::ldexp(threshold, 62))) : 1; }
 
 // ---- the compaction's grid over a slot of n ids: X workgroups of R ids each, R a multiple of the kernels' tile and at
-// least 8 tiles; at most 1024 workgroups per slot (while n <= 1024 * 2^31: every n there is)
+// least min_tiles tiles; at most 1024 workgroups per slot (while n <= 1024 * 2^31: every n there is)
 struct CompactGeom { uint32_t R = 0, X = 1; };
-inline CompactGeom compact_geom(uint64_t n, uint32_t tile = SP_TILE) {
-    const uint32_t R = (uint32_t)std::max<uint64_t>(8 * (uint64_t)tile, ((n + 1023) / 1024 + tile - 1) / tile * tile);
+inline CompactGeom compact_geom(uint64_t n, uint32_t tile = SP_TILE, uint32_t min_tiles = 8) {
+    const uint32_t R = (uint32_t)std::max<uint64_t>(min_tiles * (uint64_t)tile, ((n + 1023) / 1024 + tile - 1) / tile * tile);
     return CompactGeom{R, (uint32_t)((n + R - 1) / R)};
 }
 

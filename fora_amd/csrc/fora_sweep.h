@@ -1,5 +1,5 @@
 // fora_sweep.h -- local clustering: the sweep cut over a PPR row (Andersen-Chung-Lang), gfx950.  The SWEEP CUT contract of
-// include/fora_hip.h; the host side is sweep_* in fora_hip.hip.
+// include/fora_hip.h; the host side is the batch plan of fora_sweep_plan.h and sweep_* in fora_hip.hip.
 //
 //   compaction   k_sparse_count / k_sparse_write (fora_kernels.h) into the sweep's own buffers, then k_sweep_keys
 //   sort         k_sweep_sort_lds (a tile of a row in LDS: every bitonic step whose stride fits the tile),
@@ -13,24 +13,12 @@
 // the atomics changes nothing.
 #pragma once
 #include "fora_kernels.h"
+#include "fora_sweep_plan.h" // SW_TILE_MAX and the records SweepRowDesc, SweepTile, SweepGRow, SweepRowOut
 
 namespace fora {
 
-// Entries of a sort tile: key (8 bytes) + id (4 bytes) each, 48 KiB of LDS at 4096 -- under the 64 KiB a workgroup gets
-// without asking, and three workgroups per CU inside its 160 KiB.
-constexpr uint32_t SW_TILE_MAX = 4096;
 constexpr int32_t SW_PAD_ID = 0x7FFFFFFF; // sentinel (key 0, this id): after every real entry, n <= 2^31 - 1
 constexpr int SW_SCAN_ITEMS = 4;          // k_sweep_scan: consecutive positions per lane and step
-
-struct SweepRowDesc { // a live row of the batch in progress
-    int64_t tbase;    // first entry of its padded copy in the sort buffers
-    int64_t hbase;    // first entry of its profile in the held arrays
-    uint32_t len, P;  // support size; entries of the padded copy (a power of two >= len, 0 for an empty row)
-    uint32_t L, pad_; // profile length, min(len, max_size)
-};
-struct SweepTile { int64_t base; uint32_t P, off; }; // tile of a row in the sort buffers: its first entry, the row's P, the tile's offset inside the row
-struct SweepGRow { int64_t base; uint32_t P, pad_; }; // a row of the global tier
-struct SweepRowOut { int64_t len, best; uint64_t cut, vol, den, edges; };
 
 // key descending, ties id ascending
 __device__ __forceinline__ bool sw_before(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib) { return ka > kb || (ka == kb && ia < ib); }

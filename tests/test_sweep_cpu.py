@@ -2,10 +2,12 @@
 against a brute force over set membership; the cases without a best prefix; the tie rule; the recovery of a planted block on
 rows of the oracle's twin; the C ABI's new symbols and structs; and the generators of tests/test_sweep_shapes_gpu.py's inputs
 (tie-heavy and hubs-first rows, rings, pairs, inputs of k_sweep_scan), each against the brute force and for the property the
-GPU test relies on.  The two test-only entry points must be in libfora_hip_test.so and nowhere else."""
+GPU test relies on.  The two test-only entry points must be in libfora_hip_test.so and nowhere else.  Last, the host-side plan
+of a sweep batch (fora_amd/csrc/fora_sweep_plan.h) against tests/sweep_plan_check.cpp's brute force, under the sanitizers."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -291,3 +293,49 @@ def test_test_entry_points_are_in_the_test_library_only():
     assert test.fora_hip_test_sweep_scan(None, None, None, 0, 0, None) == -1
     for meth in ("test_sweep_rows", "test_sweep_scan"):
         assert callable(getattr(capi.Engine, meth))
+
+
+# ---- the plan of a sweep batch (fora_amd/csrc/fora_sweep_plan.h): tests/sweep_plan_check.cpp restates it by brute force and
+# runs under the address and undefined-behaviour sanitizers; the sanitized code is that stand-alone program and nothing else
+@pytest.fixture(scope="session")
+def sweep_plan_check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("sweep_plan") / "sweep_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I", os.path.join(ROOT, "fora_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "sweep_plan_check.cpp")], check=True)
+    return exe
+
+
+def _plan_check(exe, *args):
+    r = subprocess.run([exe, *map(str, args)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, (r.stdout.strip().splitlines() or [""])[-1] + "\n" + r.stderr[-2000:]
+    return r.stdout.split()
+
+
+def test_sort_tile_of_the_option(sweep_plan_check):
+    caps = [-1, 0, 1, 2, 3, 63, 64, 100, 4096, 5000]
+    assert [int(x) for x in _plan_check(sweep_plan_check, "tile", *caps)] == [1, 1, 1, 2, 2, 32, 64, 64, 4096, 4096]
+
+
+@pytest.mark.parametrize("T", [1, 2, 64, 4096])
+def test_batch_plan_equals_brute_force(sweep_plan_check, T):
+    """supports around every power of two up to 5 and around the tile, in one batch and split over several; profiles cut at
+    1, at 3, not at all and above every support; rows placed through `at` with dangling rows between, and as r0 + i"""
+    supports = sorted({0, 1, 2, 3, 4, 5, T - 1, T, T + 1, 2 * T, 2 * T + 1})
+    nlive = len(supports)
+    pow2 = lambda x: 0 if x == 0 else 1 << (x - 1).bit_length()
+    with_dangling = ["d9"] + [str(s) for s in supports]
+    for at in (2, 5, nlive + 2):      # first, between two rows of a batch, at a batch's edge for the 3 + rest split, last
+        with_dangling.insert(at, "d9")
+    with_dangling.append("d8")
+    for rows in ("*" + ",".join(map(str, supports)), ",".join(with_dangling)):
+        for batches in ([nlive], [1] * nlive, [3, nlive - 3], [nlive - 2, 1, 1]):
+            for max_size in (0, 1, 3, 2 * T + 7):
+                words = _plan_check(sweep_plan_check, "plan", T, max_size, rows, ",".join(map(str, batches)))
+                assert words[-1] == "ok"
+                f = {k: int(v) for k, v in (w.split("=") for w in words[:-1])}
+                P = [pow2(s) for s in supports]
+                assert f["live"] == nlive and f["maxP"] == max(P) and f["global_rows"] == sum(p > T for p in P)
+                assert f["tiles"] == (0 if T == 1 else sum(-(-p // T) for p in P))
+                assert f["words"] == 5 * nlive + 2 * f["tiles"] + 2 * f["global_rows"]
+                held = sum(min(s, max_size) if max_size > 0 else s for s in supports)
+                assert f["entries"] == held + (0 if rows[0] == "*" else 5)
