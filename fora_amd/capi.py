@@ -23,6 +23,7 @@ SYMBOLS = [
     "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
     "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
     "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
+    "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -74,6 +75,14 @@ class SparseStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+class TopkStats(C.Structure):
+    _fields_ = [("support", C.c_uint64), ("max_support", C.c_uint64), ("k", C.c_uint64), ("cut_rows", C.c_int32),
+                ("lds_rows", C.c_int32), ("global_rows", C.c_int32), ("chunks", C.c_int32), ("select_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class SeedsStats(C.Structure):
@@ -302,6 +311,22 @@ class Engine:
         out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
         return out + (self._stats(st, nq), sp.as_dict())
 
+    def query_sparse_topk(self, sources, k, with_idx=False, threshold=None, want_fix=False, device=False):
+        """query_sparse() with every row cut to its k largest entries on the GPU (fora_hip_query_sparse_topk_batch): word
+        descending, ties by ascending id, the kept entries held in ascending id order.  k >= 1.  Returns what query_sparse
+        returns plus the top-k stats: (row_ptr, ids, vals[, fix], stats, sparse_stats, topk_stats)."""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        nq = src.size
+        st = (QueryStats * max(1, nq))()
+        sp, tk = SparseStats(), TopkStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
+                                                             C.c_int64(int(k)), _p(row_ptr), st, C.byref(sp), C.byref(tk)))
+        row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(sp.entries), want_fix, device, "query_sparse_topk")
+        out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
+        return out + (self._stats(st, nq), sp.as_dict(), tk.as_dict())
+
     def _sparse_result(self, row_ptr, e, want_fix, device, who):
         """The held sparse result of e entries through fora_hip_sparse_fetch: (row_ptr, ids, vals, fix or None) as numpy
         arrays, or with device as torch tensors on the context's GPU."""
@@ -504,10 +529,12 @@ class Engine:
             props.append(ps)
         return out32, out64, props
 
-    def propagate(self, sources, feat, with_idx=False, threshold=None, normalize=False, chunk=None, want32=True, want64=False, bf16=False):
+    def propagate(self, sources, feat, with_idx=False, threshold=None, normalize=False, chunk=None, want32=True, want64=False, bf16=False,
+                  topk=None):
         """query_sparse then sparse_propagate, per chunk of `chunk` sources (None: all at once), into one [nq, d] output:
         nothing sparse leaves the device.  REPLACES the held sparse result (the last chunk's rows stay held).  Returns a
-        dict: out32 / out64 (as sparse_propagate), stats (the per-query stats), prop (one stats dict per chunk)."""
+        dict: out32 / out64 (as sparse_propagate), stats (the per-query stats), prop (one stats dict per chunk).
+        topk=k: the rows are query_sparse_topk's (their k largest entries); None: the full thresholded rows."""
         src = np.ascontiguousarray(sources, dtype=np.int32)
         nq = src.size
         st = (QueryStats * max(1, nq))()
@@ -516,16 +543,21 @@ class Engine:
         def run(i0, i1):
             rp = np.zeros(i1 - i0 + 1, dtype=np.int64)
             part = (QueryStats * (i1 - i0)).from_buffer(st, i0 * C.sizeof(QueryStats))
-            self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)), C.c_double(thr),
-                                                            _p(rp), part, None))
+            if topk is None:
+                self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)), C.c_double(thr),
+                                                                _p(rp), part, None))
+            else:
+                self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)),
+                                                                     C.c_double(thr), C.c_int64(int(topk)), _p(rp), part, None, None))
             return rp
         out32, out64, props = self._propagate_chunks(nq, chunk, feat, bf16, want32, want64, normalize, run)
         return {"out32": out32, "out64": out64, "stats": self._stats(st, nq), "prop": props}
 
     def propagate_seeds(self, sets, weights, feat, with_idx=False, threshold=None, normalize=False, chunk=None, want32=True, want64=False,
-                        bf16=False):
+                        bf16=False, topk=None):
         """query_seeds_sparse then sparse_propagate, per chunk of `chunk` sets (None: all at once), into one [ns, d] output.
-        sets / weights as for query_seeds.  REPLACES the held sparse result.  Returns a dict: out32 / out64, prop."""
+        sets / weights as for query_seeds.  REPLACES the held sparse result.  Returns a dict: out32 / out64, prop.
+        topk=k: the rows are query_seeds_sparse_topk's; None: the full thresholded rows."""
         set_ptr, seeds, w = self._seed_sets(sets, weights)
         ns = set_ptr.size - 1
         thr = 1.0 / self.n if threshold is None else float(threshold)
@@ -536,8 +568,12 @@ class Engine:
             sp_ = np.ascontiguousarray(set_ptr[i0:i1 + 1] - lo)
             sd_ = np.ascontiguousarray(seeds[lo:hi])
             w_ = None if w is None else np.ascontiguousarray(w[lo:hi])
-            self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
-                                                            C.c_double(thr), _p(rp), None, None, None))
+            if topk is None:
+                self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
+                                                                C.c_double(thr), _p(rp), None, None, None))
+            else:
+                self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
+                                                                     C.c_double(thr), C.c_int64(int(topk)), _p(rp), None, None, None, None))
             return rp
         out32, out64, props = self._propagate_chunks(ns, chunk, feat, bf16, want32, want64, normalize, run)
         return {"out32": out32, "out64": out64, "prop": props}
@@ -627,6 +663,19 @@ class Engine:
         self._chk(self._test_entry("fora_hip_test_sparse_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(float(threshold)), _p(row_ptr),
                                                                 C.byref(sp)))
         return row_ptr, sp.as_dict()
+
+    def test_sparse_topk_rows(self, rows_fix, k, threshold=0.0):
+        """test_sparse_rows with the top-k selection behind the compaction (fora_hip_test_sparse_topk_rows): leaves the held
+        top-k result of the caller's rows.  Returns (row_ptr, sparse stats, topk stats)."""
+        fix = np.ascontiguousarray(rows_fix, dtype=np.uint64)
+        if fix.ndim != 2 or fix.shape[1] != self.n:
+            raise ValueError("rows_fix must be [nq, n]")
+        nq = fix.shape[0]
+        sp, tk = SparseStats(), TopkStats()
+        row_ptr = np.zeros(nq + 1, dtype=np.int64)
+        self._chk(self._test_entry("fora_hip_test_sparse_topk_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(float(threshold)),
+                                                                     C.c_int64(int(k)), _p(row_ptr), C.byref(sp), C.byref(tk)))
+        return row_ptr, sp.as_dict(), tk.as_dict()
 
     def test_sweep_scan(self, diff, vol, nnz):
         """k_sweep_scan on one row (fora_hip_test_sweep_scan): diff (int64 differences of the cuts) and vol (uint64 per
@@ -818,6 +867,23 @@ class Engine:
         row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(row_ptr[-1]), want_fix, device, "query_seeds_sparse")
         return {"row_ptr": row_ptr, "ids": ids, "vals": vals, "fix": fix, "row_sum_fix": sums, "stats": st.as_dict(),
                 "sparse": sp.as_dict()}
+
+    def query_seeds_sparse_topk(self, sets, k, weights=None, with_idx=False, threshold=None, want_fix=False, device=False):
+        """query_seeds_sparse() with every set row cut to its k largest entries on the GPU (fora_hip_seeds_sparse_topk_batch;
+        the selection of query_sparse_topk, applied after the sum).  The same dict plus "topk" (the top-k stats)."""
+        set_ptr, seeds, w = self._seed_sets(sets, weights)
+        ns = set_ptr.size - 1
+        st = SeedsStats()
+        sp, tk = SparseStats(), TopkStats()
+        row_ptr = np.zeros(ns + 1, dtype=np.int64)
+        sums = np.zeros(ns, dtype=np.uint64)
+        thr = 1.0 / self.n if threshold is None else float(threshold)
+        self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
+                                                             C.c_double(thr), C.c_int64(int(k)), _p(row_ptr), _p(sums), C.byref(st),
+                                                             C.byref(sp), C.byref(tk)))
+        row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(row_ptr[-1]), want_fix, device, "query_seeds_sparse_topk")
+        return {"row_ptr": row_ptr, "ids": ids, "vals": vals, "fix": fix, "row_sum_fix": sums, "stats": st.as_dict(),
+                "sparse": sp.as_dict(), "topk": tk.as_dict()}
 
     def sweep_seeds(self, sets, weights=None, with_idx=False, threshold=None, max_size=0, want_profile=False, device=False):
         """Seed-set expansion (fora_hip_seeds_sweep_batch): sweep() over the rows of query_seeds instead of single sources'.

@@ -4,6 +4,8 @@
 // workspace of `batch` query slots.  The host side only sequences kernel launches;
 // there is no CPU fallback: without a HIP device every entry point fails.
 #include "fora_kernels.h"
+#include "fora_topk_plan.h"
+#include "fora_sparse_topk.h"
 #include "fora_team.h"
 #include "fora_bwd.h"
 #include "fora_sweep.h"
@@ -32,7 +34,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -95,6 +97,8 @@ struct Tunables {
     int64_t seeds_dedup = 1;     // seed sets (fora_hip_query_seeds_batch): 1 a seed id runs once per call whatever the number of sets that list it; 0 every listed seed takes a slot of its own (tests, tools/seeds_bench.py).  Same bits either way
     int64_t prop_segs = 0;       // PROPAGATE (fora_hip_sparse_propagate): segments whose partial sums are live at a time (a chunk of the call; the partial-sum buffer holds that many rows of d doubles); 0: by free memory, otherwise at least 1.  Same bits for every value
     int64_t propt_lds_cap = PROPT_LDS_MAX; // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t): keys of a column's run that one workgroup sorts in LDS at most (clamped to 0 .. PROPT_LDS_MAX); a longer run takes the global tier, one of at most 64 keys a wave; 0: every run of two keys or more takes the global tier.  Same bits for every value; a change drops the cached transposition
+    int64_t topk_lds_cap = TOPK_LDS_MAX; // SPARSE RESULTS, TOP-K (fora_hip_query_sparse_topk_batch, fora_hip_seeds_sparse_topk_batch): candidates of a cut row that one workgroup stages in LDS at most (clamped to 0 .. TOPK_LDS_MAX, fora_topk_plan.h); a longer row is selected from global memory; 0: every cut row is.  Same bits for every value
+    int64_t topk_cand = 0;       // ... entries of the candidate scratch (the rows of a batch are compacted into it chunk by chunk, consecutive rows, a row never split); 0: by free memory; always at least the longest row.  Same bits for every value
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -109,6 +113,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"seeds_dedup", &Tunables::seeds_dedup, false}, {"seeds_rows", &Tunables::seeds_rows, false},
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
+    {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -310,6 +315,9 @@ struct SparseResult : HeldRows {
     DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_fix; // entries of all rows, rows in the caller's order
     DevBuf<int64_t> d_base;           // first entry of every live row of the call
     DevBuf<double> d_stage;           // fora_hip_sparse_fetch: vals on their way to a host array, SP_STAGE at a time
+    // top-k rows (fora_sparse_topk.h): the candidate scratch, a CSR of (id, word) over the rows of the chunk in progress, and
+    // the chunk's descriptors (the write bases of its rows, then its TopkRow lists)
+    DevBuf<int32_t> d_cand_ids; DevBuf<uint64_t> d_cand_fix; DevBuf<uint64_t> d_tkdesc;
 };
 // Sweep profile of the last fora_hip_sweep_batch (free_sweep: sweep_clear, set_graph), apart from the workspace and from the
 // sparse result; the buffers of the call in progress live here too.
@@ -378,7 +386,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -389,6 +397,7 @@ struct fora_ctx {
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
     Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt;
+    bool topk_lds_ready = false; // k_topk_rows<true> may take the whole of a CU's LDS (topk_lds_limit)
     uint64_t sparse_gen = 0;   // fora_hip_get_option "sparse_generation": counts the times a sparse result became held or stopped being held
     int batch_req = 0;        // the caller's request (fora_hip_set_batch), not part of a plan
     uint64_t bin_launches = 0; // parity picks the counter set
@@ -932,6 +941,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SW_CUT: t.sw_cut_ms += ms; break;             // scatter, k_sweep_cut, k_sweep_scan, reset: fora_sweep_stats only
         case EV_PROP_GATHER: t.prop_gather_ms += ms; break;   // k_prop_gather: fora_prop_stats only
         case EV_PROP_COMBINE: t.prop_combine_ms += ms; break; // k_prop_combine: fora_prop_stats only
+        case EV_TK_SELECT: t.tk_select_ms += ms; break;       // k_topk_rows: fora_topk_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -1364,11 +1374,13 @@ struct RowsRun {
 };
 
 // what every entry point that makes a held result starts with: the held one ends here, whatever becomes of this call
-int held_rows_begin(fora_ctx *c, HeldRows &held, const int64_t *row_ptr, double threshold, uint64_t &thr) {
+// (k: of a top-k call, checked beside the threshold -- a bad one ends the held result like a bad threshold)
+int held_rows_begin(fora_ctx *c, HeldRows &held, const int64_t *row_ptr, double threshold, uint64_t &thr, const int64_t *k = nullptr) {
     if (&held == static_cast<HeldRows *>(&c->sp)) sparse_unheld(c);
     held.valid = false; held.entries = 0;
     if (!row_ptr) return fail(c, FORA_E_ARG, "row_ptr is required");
     if (!threshold_ok(threshold)) return fail(c, FORA_E_ARG, "threshold above 1 or not a number");
+    if (k && !topk_k_ok(*k)) return fail(c, FORA_E_ARG, "k below 1");
     thr = threshold_word(threshold);
     return FORA_OK;
 }
@@ -1447,7 +1459,11 @@ template <typename Single> int finish_rows(fora_ctx *c, const RowLayout &lay, He
 }
 
 // ---- sparse results (fora_hip_query_sparse_batch): what is their own
-struct SparseRun : RowsRun { int live_done = 0; }; // live rows written so far: d_base holds the first entry of each
+struct SparseRun : RowsRun {
+    int live_done = 0;     // live rows written so far: d_base holds the first entry of each
+    int64_t topk = 0;      // > 0: a top-k call, a row holds min(len, topk) entries (topk_place)
+    TopkSums tk;
+};
 
 // per-call buffers of the two passes: `slots` slots per batch, `live` live rows in all
 int sparse_prepare(fora_ctx *c, SparseRun &sp, int slots, int live) {
@@ -1460,9 +1476,97 @@ int sparse_reserve(fora_ctx *c, const RowLayout &lay) { // (no room: the whole r
     return reserve_rows(c, lay, "no device memory for the sparse result", free_sparse, c->sp.d_ids, c->sp.d_fix);
 }
 
+// k_topk_rows<true> stages up to TOPK_LDS_MAX words: its dynamic LDS limit is raised to what a CU has, once per context
+int topk_lds_limit(fora_ctx *c) {
+    if (c->topk_lds_ready) return FORA_OK;
+    hipFuncAttributes fa{};
+    HIPCHK(c, hipFuncGetAttributes(&fa, (const void *)k_topk_rows<true>));
+    HIPCHK(c, hipFuncSetAttribute((const void *)k_topk_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(163840 - (int)fa.sharedSizeBytes)));
+    c->topk_lds_ready = true;
+    return FORA_OK;
+}
+
+// sparse_place of a top-k call (the SPARSE RESULTS, TOP-K contract; planning in fora_topk_plan.h, kernels in
+// fora_sparse_topk.h).  The counts give every row's held length min(len, k) and so its place in the held arrays before
+// anything is written.  The batch is then written in pieces: k_sparse_write compacts a chunk of consecutive rows into the
+// candidate scratch, k_topk_rows copies or selects every row of the chunk into its place, and the next chunk reuses the
+// scratch behind them on the stream.  Every row goes through the scratch, the ones that keep everything too.
+int topk_place(fora_ctx *c, SparseRun &sp, const int *at, int r0, int nb, const uint64_t *rows) {
+    SparseResult &s = c->sp;
+    const uint32_t *len = s.cnt.h_tot.get();
+    const uint64_t n = (uint64_t)c->g.n;
+    const uint32_t lds_cap = topk_lds_cap(c->opt_.topk_lds_cap);
+    std::vector<uint64_t> out((size_t)nb);
+    uint64_t total = 0, longest = 0;
+    sp.lay.begin_batch();
+    for (int i = 0; i < nb; i++) {
+        out[(size_t)i] = (uint64_t)sp.lay.place(at ? at[i] : r0 + i, len[i], topk_held(len[i], sp.topk));
+        sp.tk.add_row(len[i], topk_tier(len[i], sp.topk, lds_cap));
+        total += len[i]; longest = std::max<uint64_t>(longest, len[i]);
+    }
+    if (int rc = sparse_reserve(c, sp.lay)) return rc;
+    if (!total) return FORA_OK;
+    // the scratch
+    uint64_t free_entries = std::min(s.d_cand_ids.size(), s.d_cand_fix.size());
+    if (c->opt_.topk_cand <= 0) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(c, hipMemGetInfo(&fr, &tot));
+        free_entries += (uint64_t)fr / 2 / (sizeof(int32_t) + sizeof(uint64_t)); // half of what is free: the held arrays may still grow
+    }
+    const uint64_t cand_cap = topk_cand_cap(c->opt_.topk_cand, free_entries, total, longest);
+    if (s.d_cand_ids.ensure(cand_cap) != hipSuccess || s.d_cand_fix.ensure(cand_cap) != hipSuccess) {
+        (void)hipGetLastError();
+        s.d_cand_ids.reset(); s.d_cand_fix.reset();
+        return fail(c, FORA_E_NOMEM, "no device memory for the top-k candidates: lower the option topk_cand");
+    }
+    const uint64_t ccap = std::min(s.d_cand_ids.size(), s.d_cand_fix.size()), hcap = std::min(s.d_ids.size(), s.d_fix.size());
+    const TopkBatchPlan plan = topk_chunks(len, nb, cand_cap);
+    const uint64_t *base = rows ? rows : (const uint64_t *)c->ws.d_ppr.get();
+    std::vector<uint64_t> pack;
+    std::vector<TopkRow> staged, plain; // rows selected in LDS; rows copied or selected from global memory
+    for (const TopkChunk &ch : plan.chunks) {
+        sp.tk.chunks++;
+        if (!ch.entries) continue;
+        const int q0 = topk_launch_row(ch.r0, n), nw = ch.r1 - q0;
+        staged.clear(); plain.clear();
+        pack.assign((size_t)nw, ccap); // write bases; a row in front of the chunk writes nothing
+        uint32_t stage = 0;
+        for (int i = ch.r0; i < ch.r1; i++) {
+            pack[(size_t)(i - q0)] = plan.cand[(size_t)i];
+            if (!len[i]) continue;
+            const TopkRow r{plan.cand[(size_t)i], out[(size_t)i], len[i], (uint32_t)topk_held(len[i], sp.topk)};
+            if (topk_tier(len[i], sp.topk, lds_cap) == TOPK_LDS) { staged.push_back(r); stage = std::max(stage, len[i]); }
+            else plain.push_back(r);
+        }
+        const size_t at_staged = pack.size(), at_plain = at_staged + staged.size() * 3;
+        pack.resize(at_plain + plain.size() * 3);
+        if (!staged.empty()) memcpy(pack.data() + at_staged, staged.data(), staged.size() * sizeof(TopkRow));
+        if (!plain.empty()) memcpy(pack.data() + at_plain, plain.data(), plain.size() * sizeof(TopkRow));
+        HIPCHK(c, s.d_tkdesc.ensure(pack.size()));
+        HIPCHK(c, hipMemcpyAsync(s.d_tkdesc.get(), pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (pageable source)
+        if (!staged.empty()) if (int rc = topk_lds_limit(c)) return rc;
+        EvSpan ev(c, EV_SP_COMPACT);
+        hipLaunchKernelGGL(k_sparse_write, dim3(sp.geo.X, (unsigned)nw), dim3(BLOCK), 0, c->stream, base + (uint64_t)q0 * n, (uint32_t)n, sp.thr, sp.geo.R,
+                           (const uint32_t *)s.cnt.d_counts.get() + (size_t)q0 * sp.geo.X, reinterpret_cast<const int64_t *>(s.d_tkdesc.get()),
+                           s.d_cand_ids.get(), s.d_cand_fix.get(), ccap);
+        ev.begin(EV_TK_SELECT);
+        if (!staged.empty())
+            hipLaunchKernelGGL(k_topk_rows<true>, dim3((unsigned)staged.size()), dim3(TOPK_BLOCK), (size_t)stage * 8, c->stream,
+                               reinterpret_cast<const TopkRow *>(s.d_tkdesc.get() + at_staged), (const int32_t *)s.d_cand_ids.get(), (const uint64_t *)s.d_cand_fix.get(), ccap,
+                               s.d_ids.get(), s.d_fix.get(), hcap);
+        if (!plain.empty())
+            hipLaunchKernelGGL(k_topk_rows<false>, dim3((unsigned)plain.size()), dim3(TOPK_BLOCK), 0, c->stream,
+                               reinterpret_cast<const TopkRow *>(s.d_tkdesc.get() + at_plain), (const int32_t *)s.d_cand_ids.get(), (const uint64_t *)s.d_cand_fix.get(), ccap,
+                               s.d_ids.get(), s.d_fix.get(), hcap);
+    }
+    return FORA_OK;
+}
+
 // write pass of the batch just closed (slot i: row at[i] of the caller; at null: row r0 + i); the slabs hold it until the
 // next batch starts on the same stream.  rows: as for count_rows
 int sparse_place(fora_ctx *c, SparseRun &sp, const int *at, int r0, int nb, const uint64_t *rows = nullptr) {
+    if (sp.topk) return topk_place(c, sp, at, r0, nb, rows);
     std::vector<int64_t> base((size_t)nb);
     sp.lay.begin_batch();
     for (int i = 0; i < nb; i++) {
@@ -1479,7 +1583,7 @@ int sparse_place(fora_ctx *c, SparseRun &sp, const int *at, int r0, int nb, cons
     return FORA_OK;
 }
 
-int sparse_finish(fora_ctx *c, SparseRun &sp, int64_t *row_ptr, fora_sparse_stats *out) {
+int sparse_finish(fora_ctx *c, SparseRun &sp, int64_t *row_ptr, fora_sparse_stats *out, fora_topk_stats *tk = nullptr) {
     sp.lay.finish();
     if (int rc = sparse_reserve(c, sp.lay)) return rc; // (only grows when dangling rows came last)
     if (int rc = finish_rows(c, sp.lay, c->sp, "sparse result", row_ptr, [&](uint32_t nd, const int64_t *at, const int32_t *src) {
@@ -1490,6 +1594,13 @@ int sparse_finish(fora_ctx *c, SparseRun &sp, int64_t *row_ptr, fora_sparse_stat
         memset(out, 0, sizeof(*out));
         out->entries = sp.lay.cur; out->max_row = sp.lay.max_row; out->thr_fix = sp.thr; out->batches = sp.lay.batches;
         out->compact_ms = c->tm.sp_compact_ms;
+        if (sp.topk) out->max_row = topk_held(sp.lay.max_row, sp.topk); // the longest HELD row
+    }
+    if (tk) {
+        memset(tk, 0, sizeof(*tk));
+        tk->support = sp.tk.support; tk->max_support = sp.tk.max_support; tk->k = (uint64_t)sp.topk;
+        tk->cut_rows = sp.tk.cut_rows; tk->lds_rows = sp.tk.lds_rows; tk->global_rows = sp.tk.global_rows; tk->chunks = sp.tk.chunks;
+        tk->select_ms = c->tm.tk_select_ms;
     }
     return FORA_OK;
 }
@@ -2027,11 +2138,13 @@ int seeds_chunk(const fora_ctx *c) { return fora::seeds_chunk(c->opt_.seeds_rows
 
 // one attempt of fora_hip_seeds_sparse_batch: the block, then count / place over its rows, every row live and no dangling one
 int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
-                      uint64_t thr, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
+                      uint64_t thr, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out,
+                      int64_t topk = 0, fora_topk_stats *tk_out = nullptr) {
     SparseRun run; // (a retried attempt starts from an empty one)
-    run.thr = thr;
-    c->tm.sp_compact_ms = 0;
+    run.thr = thr; run.topk = topk;
+    c->tm.sp_compact_ms = c->tm.tk_select_ms = 0;
     if (sp_out) memset(sp_out, 0, sizeof(*sp_out));
+    if (tk_out) memset(tk_out, 0, sizeof(*tk_out));
     SeedCounts sc;
     int rc = seeds_accumulate(c, set_ptr, seeds, weights, ns, with_idx, 0, false, false, st, sc);
     if (rc) return rc;
@@ -2051,7 +2164,7 @@ int seeds_sparse_impl(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds,
         if ((rc = sparse_place(c, run, nullptr, r0, nb, rows))) return rc;
     }
     if (row_sum_fix_out) if ((rc = seed_row_sums(c, ns, row_sum_fix_out))) return rc;
-    if ((rc = sparse_finish(c, run, row_ptr, sp_out))) return rc;
+    if ((rc = sparse_finish(c, run, row_ptr, sp_out, tk_out))) return rc;
     fill_seeds_stats(c, sc, st);
     return FORA_OK;
 }
@@ -2560,18 +2673,28 @@ int fora_hip_query_batch_fix(fora_ctx *c, const int32_t *sources, int nq, int wi
     return with_bucket_retry(c, [&] { return query_common(c, sources, nq, with_idx, 0, nullptr, ppr_fix_out, residue_fix_out, stats); });
 }
 
-int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t *row_ptr,
-                                fora_query_stats *stats, fora_sparse_stats *sp_out) {
+// k null: the plain call; otherwise the top-k call with *k
+static int query_sparse_call(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, const int64_t *k, int64_t *row_ptr,
+                             fora_query_stats *stats, fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
     if (!c) return FORA_E_ARG;
     uint64_t thr;
-    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr, k)) return rc;
     return with_bucket_retry(c, [&] {
         SparseRun run; // (a retried attempt starts from an empty one)
-        run.thr = thr;
-        c->tm.sp_compact_ms = 0;
+        run.thr = thr; run.topk = k ? *k : 0;
+        c->tm.sp_compact_ms = c->tm.tk_select_ms = 0;
         if (int rc = query_common(c, sources, nq, with_idx, 0, nullptr, nullptr, nullptr, stats, 0, nullptr, nullptr, &run)) return rc;
-        return sparse_finish(c, run, row_ptr, sp_out);
+        return sparse_finish(c, run, row_ptr, sp_out, tk_out);
     });
+}
+int fora_hip_query_sparse_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t *row_ptr,
+                                fora_query_stats *stats, fora_sparse_stats *sp_out) {
+    return query_sparse_call(c, sources, nq, with_idx, threshold, nullptr, row_ptr, stats, sp_out, nullptr);
+}
+// ---- the k largest entries of every sparse row (the SPARSE RESULTS, TOP-K contract of include/fora_hip.h)
+int fora_hip_query_sparse_topk_batch(fora_ctx *c, const int32_t *sources, int nq, int with_idx, double threshold, int64_t k, int64_t *row_ptr,
+                                     fora_query_stats *stats, fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
+    return query_sparse_call(c, sources, nq, with_idx, threshold, &k, row_ptr, stats, sp_out, tk_out);
 }
 
 // ---- seed sets: weighted multi-seed queries, one row per set (the SEED SETS contract of include/fora_hip.h)
@@ -2584,14 +2707,24 @@ int fora_hip_query_seeds_batch(fora_ctx *c, const int64_t *set_ptr, const int32_
 }
 
 // ---- seed sets, result kept sparse: the set rows thresholded after the sum, held and fetched like fora_hip_query_sparse_batch's
-int fora_hip_seeds_sparse_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
-                                double threshold, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
+static int seeds_sparse_call(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                             double threshold, const int64_t *k, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st,
+                             fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
     if (!c) return FORA_E_ARG;
     uint64_t thr;
-    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr, k)) return rc;
     return with_bucket_retry(c, [&] {
-        return seeds_sparse_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, row_ptr, row_sum_fix_out, st, sp_out);
+        return seeds_sparse_impl(c, set_ptr, seeds, weights, ns, with_idx, thr, row_ptr, row_sum_fix_out, st, sp_out, k ? *k : 0, tk_out);
     });
+}
+int fora_hip_seeds_sparse_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                                double threshold, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st, fora_sparse_stats *sp_out) {
+    return seeds_sparse_call(c, set_ptr, seeds, weights, ns, with_idx, threshold, nullptr, row_ptr, row_sum_fix_out, st, sp_out, nullptr);
+}
+int fora_hip_seeds_sparse_topk_batch(fora_ctx *c, const int64_t *set_ptr, const int32_t *seeds, const double *weights, int ns, int with_idx,
+                                     double threshold, int64_t k, int64_t *row_ptr, uint64_t *row_sum_fix_out, fora_seeds_stats *st,
+                                     fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
+    return seeds_sparse_call(c, set_ptr, seeds, weights, ns, with_idx, threshold, &k, row_ptr, row_sum_fix_out, st, sp_out, tk_out);
 }
 
 // ---- seed sets, swept: the SWEEP CUT contract over the set rows, held and fetched like fora_hip_sweep_batch's
@@ -3007,14 +3140,15 @@ int fora_hip_test_sweep_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, doub
 
 // fora_hip_query_sparse_batch's frame in the same way: the caller's rows in the ppr slabs, counted, placed and held by the
 // library's own compaction -- a held sparse result of exactly chosen row lengths.
-int fora_hip_test_sparse_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t *row_ptr, fora_sparse_stats *sp_out) {
+static int test_sparse_rows_call(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, const int64_t *k, int64_t *row_ptr,
+                                 fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
     if (!c) return FORA_E_ARG;
     uint64_t thr;
-    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr)) return rc;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr, threshold, thr, k)) return rc;
     return with_bucket_retry(c, [&] {
         SparseRun run;
-        run.thr = thr;
-        c->tm.sp_compact_ms = 0;
+        run.thr = thr; run.topk = k ? *k : 0;
+        c->tm.sp_compact_ms = c->tm.tk_select_ms = 0;
         if (int rc = check_batch_args(c, reinterpret_cast<const int32_t *>(rows_fix), nq, "row")) return rc;
         HIPCHK(c, hipSetDevice(c->device));
         const uint64_t n = (uint64_t)c->g.n;
@@ -3033,8 +3167,16 @@ int fora_hip_test_sparse_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, dou
                 if (int rc = sparse_place(c, run, nullptr, b0, nb)) return rc;
             }
         }
-        return sparse_finish(c, run, row_ptr, sp_out);
+        return sparse_finish(c, run, row_ptr, sp_out, tk_out);
     });
+}
+int fora_hip_test_sparse_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t *row_ptr, fora_sparse_stats *sp_out) {
+    return test_sparse_rows_call(c, rows_fix, nq, threshold, nullptr, row_ptr, sp_out, nullptr);
+}
+// ... and with the selection behind the compaction: fora_hip_query_sparse_topk_batch's frame over the caller's rows
+int fora_hip_test_sparse_topk_rows(fora_ctx *c, const uint64_t *rows_fix, int nq, double threshold, int64_t k, int64_t *row_ptr,
+                                   fora_sparse_stats *sp_out, fora_topk_stats *tk_out) {
+    return test_sparse_rows_call(c, rows_fix, nq, threshold, &k, row_ptr, sp_out, tk_out);
 }
 
 // k_sweep_scan on one row in buffers of this call's own: diff_cut / vol as k_sweep_scatter<true> and k_sweep_cut leave them

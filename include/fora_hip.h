@@ -92,8 +92,8 @@
  *     the single entry (s, FORA_FIX_ONE); inside a row the ids ascend; row_ptr[0] == 0, row_ptr[nq] == entries.
  *   - fix is the raw word and vals[j] == ldexp((double)fix[j], -62), the value the dense ppr_out holds for that node.
  *   - the result lives in device memory owned by the ctx, outside the query workspace.  It stays valid until the next
- *     fora_hip_query_sparse_batch or fora_hip_seeds_sparse_batch (whatever that call returns), fora_hip_sparse_clear, fora_hip_set_graph or
- *     fora_hip_destroy; every other entry point (queries, top-k, baselines, set_option, set_batch, a bucket retry of a
+ *     fora_hip_query_sparse_batch or fora_hip_seeds_sparse_batch or one of their top-k forms (whatever that call returns),
+ *     fora_hip_sparse_clear, fora_hip_set_graph or fora_hip_destroy; every other entry point (queries, top-k, baselines, set_option, set_batch, a bucket retry of a
  *     later call) leaves it untouched.  A failed sparse call leaves no result.
  *   - fora_hip_sparse_fetch may be called any number of times.  Each output pointer may be pageable host memory or device
  *     memory on the ctx's GPU (a device destination is written by the device, never staged through the host).  The ctx's
@@ -147,6 +147,34 @@
  *   - errors: those of SEED SETS, plus a NULL row_ptr and a bad threshold (FORA_E_ARG).  No device memory for the accumulator
  *     block or the result: FORA_E_NOMEM, nothing held, the ctx still usable.
  *   - a held sweep result, the walk index, the options and the FORA parameters are left untouched; fora_timing as in SEED SETS.
+ * SPARSE RESULTS, TOP-K (fora_hip_query_sparse_topk_batch, fora_hip_seeds_sparse_topk_batch): the rows of SPARSE RESULTS and of
+ * SEED SETS, SPARSE cut down to their k largest entries on the GPU.  Row i is the row fora_hip_query_sparse_batch defines (for
+ * seed sets: row_g of SEED SETS, SPARSE, thresholded after the sum); its support is {v : word[v] >= thr_fix}, thr_fix from
+ * `threshold` exactly as there, len = |support|.  Everything is an integer.
+ *   - k is an int64_t, k >= 1; any other k is FORA_E_ARG.  k is checked beside the threshold, behind the point where the call
+ *     ends the held sparse result: a bad k, like a bad threshold (or a NULL row_ptr), leaves NO result held -- the one held
+ *     before the call is gone and "sparse_generation" has moved.
+ *   - len <= k: the row is held unchanged.  Otherwise the row keeps the k entries of the support that come first in the strict
+ *     order (word descending, id ascending); ids inside a row are distinct, so any correct selection gives the same arrays.
+ *   - the kept entries are held in ASCENDING ID order, words unchanged: what every consumer of the held result requires, and a
+ *     row still lists a node at most once.
+ *   - a dangling source gives the single entry (s, FORA_FIX_ONE) for every k; a uniform singleton seed set [s] gives the
+ *     single-source top-k row for s, word for word.
+ *   - row_ptr is the prefix sum of min(len, k), one entry per dangling row.
+ *   - the result IS the held sparse result and replaces what was held: fora_hip_sparse_fetch, _clear, _propagate, _propagate_t
+ *     and _transpose_fetch work on it unchanged, "sparse_generation" moves as for the plain calls; a held sweep profile, the
+ *     walk index, the options and the FORA parameters are untouched.
+ *   - no bit depends on the batch size, on the batch a row lands in, on "seeds_rows" or "seeds_dedup", on the tier a row took,
+ *     or on the options "topk_lds_cap" (candidates of a cut row that one workgroup selects in LDS at most; 0: every cut row is
+ *     selected from global memory) and "topk_cand" (entries of the candidate scratch a batch is compacted into chunk by chunk;
+ *     0: by free memory; at least the longest row, a row is never split).  With k >= the longest support row_ptr, ids and fix
+ *     equal those of the plain call word for word.
+ *   - stats: *stats / *st as for the plain calls.  *sp: entries = row_ptr[nq], max_row = the longest HELD row, compact_ms = the
+ *     count and candidate passes.  *tk: support / max_support = sum and max of len over the live rows, k, cut_rows (len > k),
+ *     lds_rows / global_rows (cut rows per tier), chunks (candidate chunks written), select_ms.  row_sum_fix_out stays the sum
+ *     over the WHOLE row, as in SEED SETS.
+ *   - errors: those of the plain calls.  No device memory for the candidates or the result: FORA_E_NOMEM, nothing held, the
+ *     ctx still usable.
  * SWEEP CUT (fora_hip_sweep_batch, fora_hip_sweep_fetch, fora_hip_sweep_clear): local clustering by a sweep over ppr / degree
  * (Andersen-Chung-Lang), computed on the GPU from the rows of a query.  The query is fora_hip_query_batch's: same push, same
  * walks, same batching, same dangling-source fast path, same fora_query_stats, same bits in the ppr slabs.  Only what is derived
@@ -523,6 +551,20 @@ int fora_hip_seeds_sparse_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, 
                                 const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx, double threshold,
                                 int64_t *row_ptr /*ns+1, required*/, uint64_t *row_sum_fix_out /*ns or NULL*/,
                                 fora_seeds_stats *st /*or NULL*/, fora_sparse_stats *sp /*or NULL*/);
+/* ---- top-k sparse rows (the SPARSE RESULTS, TOP-K contract above): the two sparse calls with every row cut to its k largest
+ * entries, held in ascending id order as the held sparse result. */
+typedef struct { uint64_t support, max_support, k;           /* sum and max of len over the live rows */
+                 int32_t cut_rows /* len > k */, lds_rows, global_rows, chunks;
+                 double select_ms; } fora_topk_stats;
+int fora_hip_query_sparse_topk_batch(fora_ctx *ctx, const int32_t *sources, int nq, int with_idx,
+                                     double threshold, int64_t k, int64_t *row_ptr /*nq+1, required*/,
+                                     fora_query_stats *stats /*nq or NULL*/, fora_sparse_stats *sp /*or NULL*/,
+                                     fora_topk_stats *tk /*or NULL*/);
+int fora_hip_seeds_sparse_topk_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, const int32_t *seeds,
+                                     const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx, double threshold,
+                                     int64_t k, int64_t *row_ptr /*ns+1, required*/, uint64_t *row_sum_fix_out /*ns or NULL*/,
+                                     fora_seeds_stats *st /*or NULL*/, fora_sparse_stats *sp /*or NULL*/,
+                                     fora_topk_stats *tk /*or NULL*/);
 int fora_hip_seeds_sweep_batch(fora_ctx *ctx, const int64_t *set_ptr /*ns+1*/, const int32_t *seeds,
                                const double *weights /*set_ptr[ns] or NULL*/, int ns, int with_idx, double threshold,
                                int64_t max_size, int64_t *row_ptr /*ns+1, required: prefix sums of L*/,
@@ -638,7 +680,13 @@ int fora_hip_get_stamps(fora_ctx *ctx, uint64_t *out32);
  *     fora_hip_query_sparse_batch with the caller's rows in place of a query's: the rows are copied into the ppr slabs batch
  *     by batch (fora_hip_set_batch is honoured) and counted, placed and held by the library's own compaction.  Every row
  *     takes a slot.  Leaves a held sparse result of exactly chosen row lengths for fora_hip_sparse_fetch and
- *     fora_hip_sparse_propagate. */
+ *     fora_hip_sparse_propagate.
+ *
+ *   int fora_hip_test_sparse_topk_rows(fora_ctx *ctx, const uint64_t *rows_fix (nq * n words), int nq, double threshold,
+ *                                      int64_t k, int64_t *row_ptr (nq + 1, required), fora_sparse_stats *sp (or NULL),
+ *                                      fora_topk_stats *tk (or NULL));
+ *     fora_hip_test_sparse_rows with the selection of SPARSE RESULTS, TOP-K behind it: the caller's rows are counted, written
+ *     into the candidate scratch chunk by chunk and cut to their k largest entries by the library's own kernels. */
 
 #ifdef __cplusplus
 }
