@@ -24,6 +24,7 @@ SYMBOLS = [
     "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
     "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
     "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
+    "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -129,8 +130,16 @@ class PropTStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SddmmStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("bytes", C.c_uint64),
+                ("a_on_device", C.c_int32), ("b_on_device", C.c_int32), ("sddmm_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROP_SEG = 256  # FORA_PROP_SEG
-PROP_F32, PROP_BF16 = 0, 1
+PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
 PROP_NORMALIZE = 1
 
 
@@ -406,7 +415,33 @@ class Engine:
             raise ValueError(f"{name} must be [nq, d] of the output's type with a column stride of one element")
         return ptr, int(ldo)
 
-    def sparse_propagate(self, row_ptr, feat, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None):
+    def _prop_values(self, values, entries, on_dev):
+        """(pointer, val_type, keep-alive) of the values argument of sparse_propagate / sparse_propagate_t: one float32 or
+        float64 per held entry, a numpy array or a torch tensor on the context's GPU (with torch operands only: the call
+        synchronises the device once, for all of them)"""
+        if self._is_torch(values):
+            import torch
+            if not on_dev:
+                raise ValueError("torch values go with a torch feat / grad")
+            if not values.is_cuda or values.device.index != self.device:
+                raise ValueError("torch values must live on the context's GPU")
+            if values.dtype not in (torch.float32, torch.float64):
+                raise ValueError("values must be float32 or float64")
+            if values.dim() != 1 or values.shape[0] != entries:
+                raise ValueError("values must hold one element per held entry")
+            v = values.detach()
+            if entries > 1 and v.stride(0) != 1:
+                v = v.contiguous()
+            return C.c_void_p(v.data_ptr()), (PROP_F64 if v.dtype == torch.float64 else PROP_F32), v
+        a = np.asarray(values)
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError("values must be float32 or float64")
+        if a.ndim != 1 or a.shape[0] != entries:
+            raise ValueError("values must hold one element per held entry")
+        a = np.ascontiguousarray(a)
+        return _p(a), (PROP_F64 if a.dtype == np.float64 else PROP_F32), a
+
+    def sparse_propagate(self, row_ptr, feat, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None, values=None):
         """out = (held sparse rows) x feat (fora_hip_sparse_propagate, the PROPAGATE contract of include/fora_hip.h), on the held
         result of query_sparse / query_seeds_sparse: out[i, c] = sum over the entries of row i of val * feat[id, c] in the
         contract's fixed order, every bit defined.  row_ptr: as the sparse call returned it.  feat: a numpy float32 array
@@ -415,14 +450,23 @@ class Engine:
         tensor is read in place).  normalize: every row divided by the sum of its kept values.  Returns
         (out32 or None, out64 or None, stats dict): float32 / float64 [nq, d]; torch tensors on the device with a torch
         feat, numpy arrays otherwise.  out32 / out64: caller-made outputs to fill instead (their row stride is ldo; columns
-        past d are left alone), both with the same row stride."""
+        past d are left alone), both with the same row stride.  values (fora_hip_sparse_propagate_vals, PROPAGATE WITH
+        VALUES): one float32 or float64 per held entry, in held order, used as the weights in place of the held values --
+        numpy, or a torch tensor on the GPU beside a torch feat; not together with normalize."""
         if self._is_torch(row_ptr):
             row_ptr = row_ptr.cpu().numpy()
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
         nq = rp.size - 1
         fptr, ftype, d, ldf, on_dev, _keep = self._prop_feat(feat, bf16)
+        if values is not None:
+            vptr, vtype, _vkeep = self._prop_values(values, int(rp[-1]), on_dev)
         out32, out64, p32, p64, ldo = self._prop_outputs(nq, d, on_dev, want32, want64, out32, out64)
         ps = PropStats()
+        if values is not None:
+            self._chk(self._lib.fora_hip_sparse_propagate_vals(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
+                                                               C.c_int(PROP_NORMALIZE if normalize else 0), vptr, C.c_int(vtype), p32, p64,
+                                                               C.c_int64(ldo), C.byref(ps)))
+            return out32, out64, ps.as_dict()
         self._chk(self._lib.fora_hip_sparse_propagate(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
                                                       C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
         return out32, out64, ps.as_dict()
@@ -456,7 +500,7 @@ class Engine:
             ldo = ldo64
         return out32, out64, p32, p64, ldo
 
-    def sparse_propagate_t(self, row_ptr, grad, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None):
+    def sparse_propagate_t(self, row_ptr, grad, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None, values=None):
         """out = (held sparse rows)^T x grad (fora_hip_sparse_propagate_t, the PROPAGATE, TRANSPOSED contract of
         include/fora_hip.h): out[v, c] = sum over the held entries whose id is v, by ascending row, of val * grad[row, c] --
         the gradient of a loss with respect to the feat of sparse_propagate when grad is its gradient with respect to the
@@ -464,17 +508,77 @@ class Engine:
         conventions of sparse_propagate's feat.  normalize: every value divided by the sum of its row's kept values (the
         adjoint of sparse_propagate(normalize=True)).  Returns (out32 or None, out64 or None, stats dict): [n, d], torch
         tensors on the device with a torch grad, numpy arrays otherwise.  The first call on a held result builds its
-        transposition (stats["built"] == 1), later calls reuse it."""
+        transposition (stats["built"] == 1), later calls reuse it.  values (fora_hip_sparse_propagate_t_vals): as for
+        sparse_propagate, one element per held entry in HELD order."""
         if self._is_torch(row_ptr):
             row_ptr = row_ptr.cpu().numpy()
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
         nq = rp.size - 1
         gptr, gtype, d, ldg, on_dev, _keep = self._prop_feat(grad, bf16, rows=nq, name="grad")
+        if values is not None:
+            vptr, vtype, _vkeep = self._prop_values(values, int(rp[-1]), on_dev)
         out32, out64, p32, p64, ldo = self._prop_outputs(self.n, d, on_dev, want32, want64, out32, out64)
         ps = PropTStats()
+        if values is not None:
+            self._chk(self._lib.fora_hip_sparse_propagate_t_vals(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
+                                                                 C.c_int(PROP_NORMALIZE if normalize else 0), vptr, C.c_int(vtype), p32, p64,
+                                                                 C.c_int64(ldo), C.byref(ps)))
+            return out32, out64, ps.as_dict()
         self._chk(self._lib.fora_hip_sparse_propagate_t(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
                                                         C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
         return out32, out64, ps.as_dict()
+
+    def sparse_sddmm(self, row_ptr, a, b, want32=True, want64=False, out32=None, out64=None, a_bf16=False, b_bf16=False):
+        """scores[e] = <a[row of e], b[id of e]> for every held entry e (fora_hip_sparse_sddmm, the SCORES (SDDMM) contract of
+        include/fora_hip.h), in the contract's fixed order, every bit defined.  a: [nq, d], b: [n, d], each a numpy float32
+        array (uint16 with a_bf16 / b_bf16) or a torch tensor on the context's GPU (float32 or bfloat16), with the stride
+        conventions of sparse_propagate's feat; the two may differ in type and in where they live.  Returns
+        (out32 or None, out64 or None, stats dict): float32 / float64 [entries], torch tensors on the device when a or b is
+        a torch tensor, numpy arrays otherwise; out32 / out64: caller-made contiguous outputs of at least `entries`
+        elements to fill instead, each a numpy array or a torch tensor on the GPU."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        aptr, atype, d, lda, a_dev, _ka = self._prop_feat(a, a_bf16, rows=nq, name="a")
+        bptr, btype, db, ldb, b_dev, _kb = self._prop_feat(b, b_bf16, name="b")
+        if db != d:
+            raise ValueError("a and b must have the same number of columns")
+        on_dev = a_dev or b_dev
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda bits: torch.empty(e, dtype=torch.float32 if bits == 32 else torch.float64, device=dev)
+        else:
+            mk = lambda bits: np.zeros(e, dtype=np.float32 if bits == 32 else np.float64)
+        if out32 is None and want32:
+            out32 = mk(32)
+        if out64 is None and want64:
+            out64 = mk(64)
+        ptrs, cap = [], None
+        for o, bits, name in ((out32, 32, "out32"), (out64, 64, "out64")):
+            if o is None:
+                ptrs.append(None)
+                continue
+            if self._is_torch(o):                        # (an output lives where its caller made it, whatever the operands do)
+                import torch
+                dt = torch.float32 if bits == 32 else torch.float64
+                ok = o.dim() == 1 and o.dtype == dt and o.is_cuda and o.device.index == self.device and (o.numel() < 2 or o.stride(0) == 1)
+                ptrs.append(C.c_void_p(o.data_ptr()))
+                cnt = o.numel()
+            else:
+                ok = o.ndim == 1 and o.dtype == (np.float32 if bits == 32 else np.float64) and (o.size < 2 or o.strides[0] == o.itemsize)
+                ptrs.append(_p(o))
+                cnt = o.size
+            if not ok:
+                raise ValueError(f"{name} must be a contiguous one-dimensional array of the output's type")
+            cap = cnt if cap is None else min(cap, cnt)
+        if on_dev:
+            torch.cuda.synchronize(dev)  # (the operands may have been written, and the allocator may hand out memory, on another stream)
+        st = SddmmStats()
+        self._chk(self._lib.fora_hip_sparse_sddmm(self._ctx, _p(rp), C.c_int(nq), aptr, C.c_int(atype), C.c_int64(lda), bptr, C.c_int(btype),
+                                                  C.c_int64(ldb), C.c_int(d), ptrs[0], ptrs[1], C.c_uint64(cap or 0), C.byref(st)))
+        return out32, out64, st.as_dict()
 
     def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
         """The transposition of the held sparse result (fora_hip_sparse_transpose_fetch): (col_ptr, rows, vals), with want_fix

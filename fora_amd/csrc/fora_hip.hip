@@ -14,6 +14,7 @@
 #include "fora_seeds_plan.h"
 #include "fora_prop.h"
 #include "fora_propt.h"
+#include "fora_sddmm.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -34,7 +35,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -338,7 +339,9 @@ struct PropBufs {
     DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;   // the call's plan (fora_prop_plan.h)
     DevBuf<double> d_part; DevBuf<uint64_t> d_segsum;    // partial sums [prop_segs][d] and word sums [prop_segs] of the chunk in progress
     DevBuf<double> d_carry; DevBuf<uint64_t> d_scarry;   // [2][d] / [2]: the row a chunk cut, one buffer read and one written per chunk
-    DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays
+    DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays (SCORES: [entries])
+    DevBuf<unsigned char> d_vals;                        // PROPAGATE WITH VALUES: a host `values`, uploaded on every call
+    DevBuf<unsigned char> d_a;                           // SCORES: a host `a`, uploaded on every call (a host `b` goes to d_feat)
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
 // result, built by the first of the two calls after a result becomes held and kept with it -- it ends wherever the held
@@ -349,6 +352,7 @@ struct PropTBufs {
     DevBuf<int32_t> d_rows; DevBuf<uint64_t> d_fix;      // [entries] the row and the held word of every entry, column by column
     DevBuf<int64_t> d_col_ptr; std::vector<int64_t> h_col_ptr; // [n + 1] and its host copy (the product is planned from it)
     DevBuf<uint64_t> d_rsum;                             // [nq] S_i, the wrapping sum of row i's words
+    DevBuf<int64_t> d_pos; bool has_pos = false;         // [entries] the held place of every transposed entry: made by the first call with values (PROPAGATE WITH VALUES), never by a plain one
     int nq = 0;                                          // rows of the row_ptr it was built from
     uint64_t columns = 0, max_col = 0;
     uint32_t short_cols = 0, lds_cols = 0, global_cols = 0;
@@ -386,7 +390,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -942,6 +946,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_PROP_GATHER: t.prop_gather_ms += ms; break;   // k_prop_gather: fora_prop_stats only
         case EV_PROP_COMBINE: t.prop_combine_ms += ms; break; // k_prop_combine: fora_prop_stats only
         case EV_TK_SELECT: t.tk_select_ms += ms; break;       // k_topk_rows: fora_topk_stats only
+        case EV_SDDMM: t.sddmm_ms += ms; break;               // k_prop_sddmm: fora_sddmm_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -2803,6 +2808,8 @@ struct PropSide {
     const int32_t *ids; const uint64_t *fix; // (device) the entries
     const uint64_t *rsum;                    // transposed and normalised: S by id, every weight divided by it in the gather; else null
     bool divide;                             // forward and normalised: a row's sum divided by its word sum in the combine
+    const void *values = nullptr; bool val64 = false; // PROPAGATE WITH VALUES: the caller's weights (host or device; null: the words), f64 or f32
+    const int64_t *pos = nullptr;            // (device) with values, transposed: the held place of every entry; forward: null
 };
 struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
 
@@ -2810,17 +2817,27 @@ template <bool BF16, int V>
 void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
     const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
     const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
-    if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
+    if (sd.values) {
+        if (sd.pos) {
+            if (sd.val64) hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, true, true>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+            else hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, true, false>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+        } else {
+            if (sd.val64) hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, false, true>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+            else hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, false, false>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+        }
+    } else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
     else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
 }
 // the product of one side with feat: plan, buffers, the two kernels chunk by chunk, the staged outputs; the stream is idle and
 // the event times are collected when it returns FORA_OK
-int prop_run(fora_ctx *c, const PropSide &sd, const void *feat, int feat_type, int d, int64_t ldf, float *out32, double *out64, int64_t ldo, PropRunStats &rs) {
+int prop_run(fora_ctx *c, const PropSide &side, const void *feat, int feat_type, int d, int64_t ldf, float *out32, double *out64, int64_t ldo, PropRunStats &rs) {
     const bool bf16 = feat_type == FORA_PROP_BF16;
     const uint32_t elt = bf16 ? 2 : 4;
+    PropSide sd = side; // (a host `values` is replaced by its upload)
     const int nq = sd.rows;
     const uint64_t entries = (uint64_t)sd.row_ptr[nq];
-    bool feat_dev = false, o32_dev = false, o64_dev = false;
+    bool feat_dev = false, o32_dev = false, o64_dev = false, vals_dev = false;
+    if (sd.values) if (int rc = sparse_dest(c, sd.values, vals_dev)) return rc;
     if (feat) if (int rc = sparse_dest(c, feat, feat_dev)) return rc;
     if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
     if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
@@ -2837,6 +2854,12 @@ int prop_run(fora_ctx *c, const PropSide &sd, const void *feat, int feat_type, i
         if (int rc = prop_ensure(c, b.d_feat, bytes, "the feature upload")) return rc;
         HIPCHK(c, hipMemcpy(b.d_feat.get(), feat, bytes, hipMemcpyHostToDevice));
         feat = b.d_feat.get();
+    }
+    if (entries && sd.values && !vals_dev) {
+        const size_t bytes = (size_t)entries * (sd.val64 ? 8 : 4);
+        if (int rc = prop_ensure(c, b.d_vals, bytes, "the values upload")) return rc;
+        HIPCHK(c, hipMemcpy(b.d_vals.get(), sd.values, bytes, hipMemcpyHostToDevice));
+        sd.values = b.d_vals.get();
     }
     if (int rc = prop_ensure(c, b.d_segs, plan.segs.size(), "the segment table")) return rc;
     if (int rc = prop_ensure(c, b.d_recs, plan.recs.size(), "the segment table")) return rc;
@@ -2887,9 +2910,10 @@ int prop_run(fora_ctx *c, const PropSide &sd, const void *feat, int feat_type, i
     rs.segments = total; rs.max_row = plan.max_row; rs.chunks = (int32_t)plan.chunks.size(); rs.feat_on_device = feat_dev ? 1 : 0;
     return FORA_OK;
 }
-int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, float *out32, double *out64,
-              int64_t ldo, fora_prop_stats *ps) {
-    const PropSide sd{row_ptr, nq, (uint64_t)c->g.n, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0};
+int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, const void *values, int val_type,
+              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+    const PropSide sd{row_ptr, nq, (uint64_t)c->g.n, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0,
+                      values, val_type == FORA_PROP_F64, nullptr};
     PropRunStats rs;
     if (int rc = prop_run(c, sd, feat, feat_type, d, ldf, out32, out64, ldo, rs)) return rc;
     if (ps) {
@@ -2980,19 +3004,45 @@ int propt_ensure(fora_ctx *c, const int64_t *row_ptr, int nq, bool &built_now) {
     built_now = true;
     return FORA_OK;
 }
-int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, float *out32, double *out64,
-               int64_t ldo, fora_propt_stats *ps) {
+// PROPAGATE WITH VALUES: pos of the transposition that is there, made once (k_propt_pos) and kept with it
+int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
+    PropTBufs &t = c->pt;
+    if (t.has_pos) return FORA_OK;
+    const uint64_t entries = c->sp.entries;
+    DevBuf<int64_t> d_pos, d_row_ptr;
+    if (int rc = prop_ensure(c, d_pos, (size_t)entries, "the transposition's places")) return rc;
+    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, "the transposition's places")) return rc;
+    if (entries) {
+        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
+        EvSpan ev(c, EV_PROPT_TRANSPOSE);
+        hipLaunchKernelGGL(k_propt_pos, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const int64_t *)t.d_col_ptr.get(),
+                           (uint32_t)c->g.n, (const int32_t *)t.d_rows.get(), (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), entries, d_pos.get());
+        ev.end();
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (d_row_ptr goes out of use)
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose: ") + hipGetErrorString(err));
+    }
+    t.d_pos = std::move(d_pos);
+    t.has_pos = true;
+    return FORA_OK;
+}
+int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, const void *values, int val_type,
+               float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
     bool dev = false; // (memory of another GPU is refused before anything is built)
     if (grad) if (int rc = sparse_dest(c, grad, dev)) return rc;
+    if (values) if (int rc = sparse_dest(c, values, dev)) return rc;
     if (out32) if (int rc = sparse_dest(c, out32, dev)) return rc;
     if (out64) if (int rc = sparse_dest(c, out64, dev)) return rc;
     bool built_now = false;
     if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
-    const double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
+    double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
+    if (values) if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
     const PropTBufs &t = c->pt;
-    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, (uint64_t)nq, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false};
+    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, (uint64_t)nq, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
+                      values, val_type == FORA_PROP_F64, values ? t.d_pos.get() : nullptr};
     PropRunStats rs;
     if (int rc = prop_run(c, sd, grad, grad_type, d, ldg, out32, out64, ldo, rs)) return rc;
+    if (built_now) transpose_ms = c->tm.propt_transpose_ms; // (with values: the places too)
     if (ps) {
         ps->entries = c->sp.entries; ps->columns = t.columns; ps->segments = rs.segments; ps->max_col = t.max_col;
         ps->feat_bytes = c->sp.entries * (uint64_t)d * (grad_type == FORA_PROP_BF16 ? 2 : 4);
@@ -3005,8 +3055,9 @@ int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, in
 } // namespace
 } // extern "C++"
 
-int fora_hip_sparse_propagate(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags,
-                              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+// the frame of fora_hip_sparse_propagate and fora_hip_sparse_propagate_vals (with_values: values / val_type are the caller's)
+static int prop_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, bool with_values,
+                      const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
     if (!c) return FORA_E_ARG;
     if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
     if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate: negative nq or null row_ptr");
@@ -3017,15 +3068,29 @@ int fora_hip_sparse_propagate(fora_ctx *c, const int64_t *row_ptr, int nq, const
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate: no output");
     if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate: row_ptr is not the held result's");
     if (c->sp.entries && !feat) return fail(c, FORA_E_ARG, "sparse propagate: null feat");
+    if (with_values) {
+        if (flags & FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate: FORA_PROP_NORMALIZE with values");
+        if (val_type != FORA_PROP_F32 && val_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, "sparse propagate: val_type is neither f32 nor f64");
+        if (c->sp.entries && !values) return fail(c, FORA_E_ARG, "sparse propagate: null values");
+    }
     if (ps) memset(ps, 0, sizeof(*ps));
     if (nq == 0) return FORA_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    return drop_pairs_unless_ok(c, prop_impl(c, row_ptr, nq, feat, feat_type, d, ldf, flags, out32, out64, ldo, ps));
+    return drop_pairs_unless_ok(c, prop_impl(c, row_ptr, nq, feat, feat_type, d, ldf, flags, c->sp.entries ? values : nullptr, val_type, out32, out64, ldo, ps));
+}
+int fora_hip_sparse_propagate(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags,
+                              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+    return prop_entry(c, row_ptr, nq, feat, feat_type, d, ldf, flags, false, nullptr, FORA_PROP_F32, out32, out64, ldo, ps);
+}
+// ---- PROPAGATE WITH VALUES (the contract of include/fora_hip.h): the same product, the caller's values as the weights
+int fora_hip_sparse_propagate_vals(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags,
+                                   const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+    return prop_entry(c, row_ptr, nq, feat, feat_type, d, ldf, flags, true, values, val_type, out32, out64, ldo, ps);
 }
 
 // ---- PROPAGATE, TRANSPOSED (the contract of include/fora_hip.h): out = (held rows)^T * grad, n x d, the same fixed order
-int fora_hip_sparse_propagate_t(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags,
-                                float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
+static int propt_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, bool with_values,
+                       const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
     if (!c) return FORA_E_ARG;
     if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
     if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate_t: negative nq or null row_ptr");
@@ -3036,9 +3101,110 @@ int fora_hip_sparse_propagate_t(fora_ctx *c, const int64_t *row_ptr, int nq, con
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate_t: no output");
     if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate_t: row_ptr is not the held result's");
     if (c->sp.entries && !grad) return fail(c, FORA_E_ARG, "sparse propagate_t: null grad");
+    if (with_values) {
+        if (flags & FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate_t: FORA_PROP_NORMALIZE with values");
+        if (val_type != FORA_PROP_F32 && val_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, "sparse propagate_t: val_type is neither f32 nor f64");
+        if (c->sp.entries && !values) return fail(c, FORA_E_ARG, "sparse propagate_t: null values");
+    }
     if (ps) memset(ps, 0, sizeof(*ps));
     HIPCHK(c, hipSetDevice(c->device));
-    return drop_pairs_unless_ok(c, propt_impl(c, row_ptr, nq, grad, grad_type, d, ldg, flags, out32, out64, ldo, ps));
+    return drop_pairs_unless_ok(c, propt_impl(c, row_ptr, nq, grad, grad_type, d, ldg, flags, c->sp.entries ? values : nullptr, val_type, out32, out64, ldo, ps));
+}
+int fora_hip_sparse_propagate_t(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags,
+                                float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
+    return propt_entry(c, row_ptr, nq, grad, grad_type, d, ldg, flags, false, nullptr, FORA_PROP_F32, out32, out64, ldo, ps);
+}
+int fora_hip_sparse_propagate_t_vals(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags,
+                                     const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
+    return propt_entry(c, row_ptr, nq, grad, grad_type, d, ldg, flags, true, values, val_type, out32, out64, ldo, ps);
+}
+
+// ---- SCORES (SDDMM) (the contract of include/fora_hip.h): score_e = <a[row_e], b[id_e]> for every held entry, in a fixed order
+extern "C++" {
+namespace {
+template <bool A_BF16, bool B_BF16>
+void sddmm_launch(fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg, float *o32, double *o64) {
+    const uint64_t units = nseg * SDDMM_UNITS, per_wg = BLOCK / 64;
+    hipLaunchKernelGGL((k_prop_sddmm<A_BF16, B_BF16>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, nseg,
+                       (const int32_t *)c->sp.d_ids.get(), a, lda, b, ldb, (uint32_t)d, lg, o32, o64);
+}
+int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
+               float *out32, double *out64, fora_sddmm_stats *st) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const uint32_t a_elt = a_type == FORA_PROP_BF16 ? 2 : 4, b_elt = b_type == FORA_PROP_BF16 ? 2 : 4;
+    bool a_dev = false, b_dev = false, o32_dev = false, o64_dev = false;
+    if (a) if (int rc = sparse_dest(c, a, a_dev)) return rc;
+    if (b) if (int rc = sparse_dest(c, b, b_dev)) return rc;
+    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
+    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
+    PropBufs &pb = c->pr;
+    const uint64_t total = prop_segments(row_ptr, nq);
+    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: there are no partial sums to hold)
+    // ---- every buffer of the call before the launch: a call that finds no room has written nothing
+    if (entries && !a_dev) {
+        const size_t bytes = (size_t)((((uint64_t)nq - 1) * (uint64_t)lda + (uint64_t)d) * a_elt);
+        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of a")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_a.get(), a, bytes, hipMemcpyHostToDevice));
+        a = pb.d_a.get();
+    }
+    if (entries && !b_dev) {
+        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldb + (uint64_t)d) * b_elt);
+        if (int rc = prop_ensure(c, pb.d_feat, bytes, "the upload of b")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_feat.get(), b, bytes, hipMemcpyHostToDevice));
+        b = pb.d_feat.get();
+    }
+    if (int rc = prop_ensure(c, pb.d_segs, plan.segs.size(), "the segment table")) return rc;
+    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)entries, "a staged output")) return rc;
+    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)entries, "a staged output")) return rc;
+    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
+    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
+    c->tm.sddmm_ms = 0;
+    if (!plan.segs.empty()) {
+        HIPCHK(c, hipMemcpy(pb.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        uint32_t lg = 0;
+        while (lg < 6 && (1u << lg) < (uint32_t)d) lg++; // the smallest group that holds d columns, at most a wave
+        const PropSeg *segs = pb.d_segs.get();
+        const uint64_t nseg = plan.segs.size();
+        EvSpan ev(c, EV_SDDMM);
+        if (a_elt == 4 && b_elt == 4) sddmm_launch<false, false>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
+        else if (a_elt == 4) sddmm_launch<false, true>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
+        else if (b_elt == 4) sddmm_launch<true, false>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
+        else sddmm_launch<true, true>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
+    }
+    if (entries && out32 && !o32_dev) HIPCHK(c, hipMemcpyAsync(out32, w32, (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
+    if (entries && out64 && !o64_dev) HIPCHK(c, hipMemcpyAsync(out64, w64, (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse sddmm: ") + hipGetErrorString(err));
+    ev_collect(c);
+    if (st) {
+        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
+        st->bytes = entries * (uint64_t)d * (a_elt + b_elt);
+        st->a_on_device = a_dev ? 1 : 0; st->b_on_device = b_dev ? 1 : 0;
+        st->sddmm_ms = c->tm.sddmm_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+} // extern "C++"
+
+int fora_hip_sparse_sddmm(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
+                          float *out32, double *out64, uint64_t cap, fora_sddmm_stats *st) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse sddmm: negative nq or null row_ptr");
+    if ((a_type != FORA_PROP_F32 && a_type != FORA_PROP_BF16) || (b_type != FORA_PROP_F32 && b_type != FORA_PROP_BF16))
+        return fail(c, FORA_E_ARG, "sparse sddmm: unknown a_type or b_type");
+    if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse sddmm: d outside 1 .. 65536");
+    if (lda < d || ldb < d) return fail(c, FORA_E_ARG, "sparse sddmm: a leading dimension smaller than d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse sddmm: no output");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse sddmm: row_ptr is not the held result's");
+    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, "sparse sddmm: cap is smaller than the held result");
+    if (c->sp.entries && (!a || !b)) return fail(c, FORA_E_ARG, "sparse sddmm: null a or b");
+    if (st) memset(st, 0, sizeof(*st));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, sddmm_impl(c, row_ptr, nq, a, a_type, lda, b, b_type, ldb, d, out32, out64, st));
 }
 
 int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *col_ptr, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap) {

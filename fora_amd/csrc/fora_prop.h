@@ -5,6 +5,8 @@
 //   k_prop_gather_t the same body over the transposition of the held result (PROPAGATE, TRANSPOSED; fora_propt.h builds it) when
 //                   every weight is divided by its row's word sum; without that division the transposed product runs
 //                   k_prop_gather itself, rows and columns swapped by the host;
+//   k_prop_gather_vals  the same body with the caller's values as the weights (PROPAGATE WITH VALUES), over the held rows or
+//                   over the transposition, where pos[p] (fora_propt.h) says which value entry p takes;
 //   k_prop_combine  one lane per (row record, column): the row's P_s added in segment order, the carry of a row that a
 //                   chunk cut, the normalisation, the stores with the output's pitch.
 // Nothing here is fused: the file is compiled with -ffp-contract=off and the two kernels say so again themselves; there
@@ -70,9 +72,15 @@ __device__ __forceinline__ double prop_widen(const PropRaw<BF16, V> &r, int v) {
 // segsum (null: not wanted): the integer sum of the segment's words, by the groups of column tile 0.
 // TNORM (the transposed product with FORA_PROP_NORMALIZE, k_prop_gather_t): the weight of an entry is its word divided by
 // the word sum of the row it came from, rsum[id] -- one IEEE division per entry, made where the word is converted.
-template <bool BF16, int V, bool TNORM>
+// WSRC (PROPAGATE WITH VALUES): where an entry's weight comes from -- PROP_W_FIX: its held word (the two kernels above, which
+// compile to what they were before the parameter existed); PROP_W_VALUES: the caller's values[e], e the entry's place in the
+// list (the forward product); PROP_W_POS: values[pos[p]], pos the held place of transposed entry p.  VAL64: values are f64,
+// else f32 widened exactly.  With values no word is read and no word sum is made.
+enum : int { PROP_W_FIX = 0, PROP_W_VALUES = 1, PROP_W_POS = 2 };
+template <bool BF16, int V, bool TNORM, int WSRC = PROP_W_FIX, bool VAL64 = false>
 __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
-                                                 int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum, const uint64_t *rsum) {
+                                                 int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum, const uint64_t *rsum,
+                                                 const void *values = nullptr, const int64_t *pos = nullptr) {
 #pragma clang fp contract(off)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t gl = lane & (G - 1u), grp = lane / G;
@@ -90,11 +98,19 @@ __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t n
         int32_t id_l = 0;
         double w_l = 0.0;
         if (base + gl < len) {
-            const uint64_t f = fix[first + base + gl];
-            id_l = ids[first + base + gl];
-            ssum += f;
-            w_l = fix2d(f);
-            if constexpr (TNORM) w_l = w_l / fix2d(rsum[id_l]);
+            if constexpr (WSRC == PROP_W_FIX) {
+                const uint64_t f = fix[first + base + gl];
+                id_l = ids[first + base + gl];
+                ssum += f;
+                w_l = fix2d(f);
+                if constexpr (TNORM) w_l = w_l / fix2d(rsum[id_l]);
+            } else {
+                id_l = ids[first + base + gl];
+                int64_t at = first + base + gl;
+                if constexpr (WSRC == PROP_W_POS) at = pos[at];
+                if constexpr (VAL64) w_l = ((const double *)values)[at];
+                else w_l = (double)((const float *)values)[at];
+            }
         }
         const uint32_t cnt = min(G, len - base);
         for (uint32_t k = 0; k < cnt; k += PROP_INFLIGHT) {
@@ -149,6 +165,13 @@ template <bool BF16, int V>
 __global__ void __launch_bounds__(BLOCK) k_prop_gather_t(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
                                                          int64_t ldf, uint32_t d, uint32_t G, double *part, const uint64_t *rsum) {
     prop_gather_body<BF16, V, true>(segs, nseg, ids, fix, feat, ldf, d, G, part, nullptr, rsum);
+}
+
+// PROPAGATE WITH VALUES: the same body with the caller's values as weights -- forward (pos null) and transposed
+template <bool BF16, int V, bool POS, bool VAL64>
+__global__ void __launch_bounds__(BLOCK) k_prop_gather_vals(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const void *values, const int64_t *pos,
+                                                            const void *feat, int64_t ldf, uint32_t d, uint32_t G, double *part) {
+    prop_gather_body<BF16, V, false, POS ? PROP_W_POS : PROP_W_VALUES, VAL64>(segs, nseg, ids, nullptr, feat, ldf, d, G, part, nullptr, nullptr, values, pos);
 }
 
 // One lane per (row record, column) of a chunk.  grid = (column blocks, record groups): with d >= BLOCK a workgroup takes

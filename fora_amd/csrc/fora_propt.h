@@ -9,7 +9,9 @@
 //   k_propt_sort_short  runs of at most 64 keys: a wave per run, every lane ranks its key against the others by shuffles;
 //   k_propt_sort_lds    runs of at most PROPT_LDS_MAX keys: a workgroup per run, the network of fora_propt_plan.h in LDS;
 //   k_propt_sort_step   longer runs: one step of that network in device memory per launch;
-//   k_propt_fill        rows[p] = key >> 32, fix[p] = the held word the key points at.
+//   k_propt_fill        rows[p] = key >> 32, fix[p] = the held word the key points at;
+//   k_propt_pos         (PROPAGATE WITH VALUES, on the first call with values) pos[p] = the held place of transposed entry p:
+//                       its column v by a search in col_ptr, then v among the ascending ids of row rows[p].
 // Row indices inside a column are distinct, so ascending keys are one order only: the bits are defined from the sort on.
 #pragma once
 #include "fora_kernels.h" // BLOCK
@@ -114,6 +116,34 @@ __global__ void __launch_bounds__(BLOCK) k_propt_fill(const uint64_t *key, uint6
         if (at >= entries) continue;
         rows[p] = (int32_t)i;
         fix[p] = held_fix[at];
+    }
+}
+
+// One lane per transposed entry p.  v = the column that holds p: the last v with col_ptr[v] <= p (empty columns repeat a
+// value, the last of them is the one with entries).  A held row lists its ids in ascending order and each once, so the
+// place of v in row rows[p] is one lower-bound search.  pos[p] is 0, a place that exists, where the tables disagree (they
+// cannot: both come from one held result).
+__global__ void __launch_bounds__(BLOCK) k_propt_pos(const int64_t *col_ptr, uint32_t n, const int32_t *rows, const int64_t *row_ptr, uint32_t nq,
+                                                     const int32_t *ids, uint64_t entries, int64_t *pos) {
+    for (uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; p < entries; p += (uint64_t)gridDim.x * BLOCK) {
+        uint32_t lo = 0, hi = n; // col_ptr[lo] <= p < col_ptr[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if ((uint64_t)col_ptr[mid] <= p) lo = mid; else hi = mid;
+        }
+        const int32_t v = (int32_t)lo;
+        const uint32_t i = (uint32_t)rows[p];
+        int64_t at = 0;
+        if (i < nq) {
+            int64_t a = row_ptr[i], b = row_ptr[i + 1];
+            const int64_t end = b;
+            while (a < b) {
+                const int64_t mid = a + (b - a) / 2;
+                if (ids[mid] < v) a = mid + 1; else b = mid;
+            }
+            if (a < end && (uint64_t)a < entries && ids[a] == v) at = a;
+        }
+        pos[p] = at;
     }
 }
 

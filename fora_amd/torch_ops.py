@@ -1,6 +1,8 @@
 """torch.autograd over the held sparse rows: Z = PI * H forward (Engine.sparse_propagate), dL/dH = PI^T * dL/dZ backward
 (Engine.sparse_propagate_t), both on the rows the engine holds -- the propagation step of an APPNP / PPRGo style model whose
-rows are computed once and whose H = MLP(X) changes at every step.  Import torch before the first Engine is created, so that
+rows are computed once and whose H = MLP(X) changes at every step.  With the caller's values on the held pattern
+(ppr_propagate(values=), ppr_sddmm, row_softmax, ppr_attention) the three operations are each other's gradients, so
+attention over the held neighbourhoods, a learned temperature or a re-weighting stay inside the library.  Import torch before the first Engine is created, so that
 the library and torch share one HIP runtime.  fora_amd/__init__.py does not import this module: the package needs no torch."""
 import torch
 
@@ -27,10 +29,129 @@ class _PprPropagate(torch.autograd.Function):
         return (out32 if ctx.dtype == torch.float32 else out32.to(ctx.dtype)), None, None, None
 
 
-def ppr_propagate(engine, row_ptr, H, normalize=False):
+def _held_guard(ctx_gen, engine, who):
+    if engine.get_option("sparse_generation") != ctx_gen:
+        raise RuntimeError(f"{who}: the engine's held sparse result was replaced or cleared after the forward pass; "
+                           "the backward pass needs the rows the forward pass used")
+
+
+def _dense_operand(X):
+    """a gradient as the library reads it: float32 or bfloat16, [rows, d], column stride one element"""
+    if X.dtype not in (torch.float32, torch.bfloat16):
+        X = X.to(torch.float32)
+    if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1) or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+        X = X.contiguous()
+    return X
+
+
+def _entry_values(g):
+    """a gradient per entry as the values of a product: float32 or float64, contiguous"""
+    if g.dtype not in (torch.float32, torch.float64):
+        g = g.to(torch.float32)
+    return g.contiguous()
+
+
+class _PprPropagateValues(torch.autograd.Function):
+    """Z = P(values) x H: dH = P(values)^T x G (the _t_vals product), dvalues = sddmm(G, H)"""
+
+    @staticmethod
+    def forward(ctx, H, values, engine, row_ptr):
+        out32, _, _ = engine.sparse_propagate(row_ptr, H.detach(), want32=True, want64=False, values=values.detach())
+        ctx.save_for_backward(H, values)
+        ctx.engine, ctx.row_ptr = engine, row_ptr
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        H, values = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "ppr_propagate")
+        G = _dense_operand(G)
+        dH = dv = None
+        if ctx.needs_input_grad[0]:
+            dH, _, _ = engine.sparse_propagate_t(ctx.row_ptr, G, want32=True, want64=False, values=values.detach())
+            dH = dH if H.dtype == torch.float32 else dH.to(H.dtype)
+        if ctx.needs_input_grad[1]:
+            dv, _, _ = engine.sparse_sddmm(ctx.row_ptr, G, H.detach(), want32=True, want64=False)
+            dv = dv if values.dtype == torch.float32 else dv.to(values.dtype)
+        return dH, dv, None, None
+
+
+class _PprSddmm(torch.autograd.Function):
+    """scores = sddmm(A, B): dA = P(g) x B (the _vals product), dB = P(g)^T x A (the _t_vals product)"""
+
+    @staticmethod
+    def forward(ctx, A, B, engine, row_ptr):
+        out32, _, _ = engine.sparse_sddmm(row_ptr, A.detach(), B.detach(), want32=True, want64=False)
+        ctx.save_for_backward(A, B)
+        ctx.engine, ctx.row_ptr = engine, row_ptr
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, g):
+        A, B = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "ppr_sddmm")
+        g = _entry_values(g)
+        dA = dB = None
+        if ctx.needs_input_grad[0]:
+            dA, _, _ = engine.sparse_propagate(ctx.row_ptr, B.detach(), want32=True, want64=False, values=g)
+            dA = dA if A.dtype == torch.float32 else dA.to(A.dtype)
+        if ctx.needs_input_grad[1]:
+            dB, _, _ = engine.sparse_propagate_t(ctx.row_ptr, A.detach(), want32=True, want64=False, values=g)
+            dB = dB if B.dtype == torch.float32 else dB.to(B.dtype)
+        return dA, dB, None, None
+
+
+def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
     """Z = (held sparse rows of `engine`) x H as a differentiable torch operation.  row_ptr: as query_sparse /
     query_seeds_sparse returned it (a numpy array or a tensor).  H: [n, d] float32 or bfloat16 on the engine's GPU, column
     stride one element.  Returns Z [nq, d] float32 on the device; Z.backward(G) leaves H.grad = (held rows)^T x G in H's
     dtype.  The rows must still be held when the backward pass runs: a query_sparse, query_seeds_sparse, sparse_clear or
-    set_graph in between makes it raise."""
-    return _PprPropagate.apply(H, engine, row_ptr, bool(normalize))
+    set_graph in between makes it raise.
+    values: a float32 or float64 tensor of `entries` elements on the device, one per held entry in held order, used as the
+    weights in place of the PPR values (Engine.sparse_propagate(values=)); the result is then differentiable in both H and
+    values -- H.grad by the transposed product with the same values, values.grad = ppr_sddmm(G, H).  Not together with
+    normalize.  values=None is the code path this function always had."""
+    if values is None:
+        return _PprPropagate.apply(H, engine, row_ptr, bool(normalize))
+    if normalize:
+        raise ValueError("ppr_propagate: normalize and values exclude each other (a division is the caller's: see row_softmax)")
+    return _PprPropagateValues.apply(H, values, engine, row_ptr)
+
+
+def ppr_sddmm(engine, row_ptr, A, B):
+    """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
+    the device, differentiable in A ([nq, d]) and B ([n, d]), float32 or bfloat16 tensors on the engine's GPU with a column
+    stride of one element: A.grad = P(g) x B and B.grad = P(g)^T x A, the two products with the scores' gradient g as values.
+    The rows must still be held when the backward pass runs."""
+    return _PprSddmm.apply(A, B, engine, row_ptr)
+
+
+def row_softmax(row_ptr, scores):
+    """softmax of `scores` ([entries]) inside every row of row_ptr ([nq + 1], numpy or a tensor): per row the max is
+    subtracted, then exp, then the division by the row's sum.  Plain torch (scatter operations), differentiable, on the CPU
+    or on a GPU; empty rows are allowed, and nothing here has defined bits."""
+    if not torch.is_tensor(row_ptr):
+        row_ptr = torch.as_tensor(row_ptr)
+    row_ptr = row_ptr.to(device=scores.device, dtype=torch.int64)
+    nq = row_ptr.numel() - 1
+    lens = row_ptr[1:] - row_ptr[:-1]
+    row = torch.repeat_interleave(torch.arange(nq, device=scores.device), lens, output_size=scores.numel())
+    top = torch.full((nq,), float("-inf"), dtype=scores.dtype, device=scores.device)
+    top = top.scatter_reduce(0, row, scores.detach(), reduce="amax", include_self=True)
+    ex = torch.exp(scores - top[row])
+    den = torch.zeros(nq, dtype=scores.dtype, device=scores.device).index_add(0, row, ex)
+    return ex / den[row]
+
+
+def ppr_attention(engine, row_ptr, Q, K, V, scale=None):
+    """Attention of every row over its held neighbourhood: out[i] = sum over the entries e of row i of
+    softmax_row(scale * <Q[i], K[id_e]>)_e * V[id_e] -- ppr_propagate(V, values=row_softmax(ppr_sddmm(Q, K) * scale)).
+    Q: [nq, d], K: [n, d], V: [n, dv]; scale defaults to d ** -0.5.  Differentiable in Q, K and V."""
+    if scale is None:
+        scale = float(Q.shape[1]) ** -0.5
+    scores = ppr_sddmm(engine, row_ptr, Q, K)
+    return ppr_propagate(engine, row_ptr, V, values=row_softmax(row_ptr, scores * scale))

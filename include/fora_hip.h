@@ -307,6 +307,57 @@
  *   - fora_hip_get_option "sparse_generation" (read-only): a counter that increases every time a sparse result becomes held
  *     or stops being held; a caller that keeps a row_ptr across calls (an autograd function) compares it to know that the
  *     held rows are still the ones it saw.
+ * SCORES (SDDMM) (fora_hip_sparse_sddmm): one dot product per held entry -- for entry e, at place e of the held result, in row
+ * i with id v, score_e = <a[i], b[v]> over d columns.  The held rows are the sparsity pattern only: no word is read.  It is
+ * the attention logit of a model over the held neighbourhoods, and the gradient of PROPAGATE WITH VALUES with respect to the
+ * values.  Every output bit is defined (tests/sddmm_ref.py is the twin).
+ *   - row_ptr: validated exactly as in PROPAGATE.  a is row-major nq x d on the row side, pitch lda >= d; b is row-major n x d
+ *     on the node side, pitch ldb >= d.  a_type and b_type are each FORA_PROP_F32 or FORA_PROP_BF16 (widened exactly), chosen
+ *     independently.  d in 1 .. 65536.
+ *   - t_c = (double)a[i][c] * (double)b[v][c], one IEEE f64 multiply; it is exact (two significands of 24 bits, and the
+ *     exponents fit), so only the adds round and their order is the contract:
+ *       q_l, l = 0 .. 63: the t_c with c == l (mod 64), added one after the other in ascending c, starting from +0.0;
+ *       then for o = 32, 16, 8, 4, 2, 1 in this order: q_l = q_l + q_{l+o} for every l < o;
+ *       score_e = q_0.
+ *     No q_l is ever -0.0 (each starts from +0.0), and a q_l with no column is +0.0, so for d <= 32 the first steps of the
+ *     tree add +0.0 and change no bit: a narrower lane group that runs only its own steps gives the same result.  No multiply
+ *     is fused with an add.  Non-finite values follow IEEE; nothing is checked.
+ *   - out64[e] = score_e; out32[e] = (float)score_e, rounded to nearest even.  Either may be NULL, both NULL is FORA_E_ARG.
+ *     cap = the entries each non-NULL output can take; cap < the held entries is FORA_E_ARG and nothing is written.
+ *   - a, b, out32 and out64 may each be pageable host memory or device memory on the ctx's GPU (memory of another GPU is
+ *     FORA_E_ARG).  A device operand needs only element alignment: any base, any pitch, a column slice of a wider tensor.
+ *     A host a is uploaded on every call ((nq - 1) * lda + d elements), a host b likewise ((n - 1) * ldb + d elements); a
+ *     host output is staged in `entries` elements of device memory.  These buffers are the ctx's, shared with PROPAGATE.
+ *   - a row of a whose held row is empty is never read by a product; columns at or past d are never read.
+ *   - no bit depends on the batch size, on "prop_segs", on how the work is split across workgroups and lanes, on alignment,
+ *     or on host versus device pointers.
+ *   - stats: entries, segments and max_row as in PROPAGATE, bytes = entries * d * (a's element size + b's element size),
+ *     a_on_device, b_on_device, and the device time of the kernel.
+ *   - the held result, its transposition, a held sweep profile, the walk index, the options, the FORA parameters and
+ *     fora_timing are left untouched.  The ctx's stream is synchronised before it returns.
+ *   - errors: NULL ctx is answered without touching the GPU.  No held result, nq < 0, NULL row_ptr, a row_ptr that does not
+ *     match, NULL a or b with entries to read, d outside 1 .. 65536, lda < d, ldb < d, an unknown a_type or b_type, both
+ *     outputs NULL, cap too small: FORA_E_ARG, nothing written.  No device memory for an upload or a staged output:
+ *     FORA_E_NOMEM, nothing written, the ctx usable and the held result intact.  nq == 0: FORA_OK, nothing is written.
+ * PROPAGATE WITH VALUES (fora_hip_sparse_propagate_vals, fora_hip_sparse_propagate_t_vals): the products of PROPAGATE and
+ * PROPAGATE, TRANSPOSED with the caller's values in place of the held words -- out = P(values) * H and out = P(values)^T * G,
+ * P(values) the held pattern with values[e] at held entry e.  Each is the other's gradient with respect to the dense operand,
+ * and SCORES (SDDMM) is their gradient with respect to values (tests/propagate_values_ref.py is the twin).
+ *   - values: one element per held entry, in held order; val_type FORA_PROP_F32 (widened exactly) or FORA_PROP_F64 (legal for
+ *     values only).  w_e = (double)values[e].  Host or device memory; a host array is uploaded on every call.  NULL values
+ *     while the held result has entries: FORA_E_ARG.  A val_type other than these two: FORA_E_ARG.
+ *   - everything else is the contract of PROPAGATE and of PROPAGATE, TRANSPOSED word for word with w_e read for the weight:
+ *     term = w_e * h, one f64 multiply never fused; segments of FORA_PROP_SEG = 256 entries of a row (of a column of the
+ *     transposition), P_s from +0.0 in entry order, acc = P_0, acc = acc + P_s; the outputs, the pitches, "prop_segs", the
+ *     sort tiers, the stats, what is left untouched, the errors.  In the transposed product entry p of a column takes
+ *     values[pos[p]], pos[p] the place of that entry in the held result.
+ *   - FORA_PROP_NORMALIZE together with values is FORA_E_ARG: a softmax or a division is the caller's.
+ *   - pos belongs to the transposition: it is made by the first call with values after the transposition exists (or with it,
+ *     when that call builds it: built = 1) and ends with it.  A call with values on a held result whose transposition
+ *     exists reports built = 0 and rebuilds nothing.  The plain calls never make pos, allocate what they always allocated
+ *     and give the bits they always gave, before and after a call with values.
+ *   - with values equal to the f64 vals of fora_hip_sparse_fetch both calls give the bits of the plain calls without
+ *     FORA_PROP_NORMALIZE.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -521,6 +572,29 @@ int fora_hip_sparse_propagate_t(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, 
                                 const void *grad /*nq x d*/, int grad_type, int d, int64_t ldg, int flags,
                                 float *out32 /*n x d or NULL*/, double *out64 /*n x d or NULL*/, int64_t ldo,
                                 fora_propt_stats *ps /*or NULL*/);
+/* ---- the two products with the caller's values as the weights (the PROPAGATE WITH VALUES contract above): values has one
+ * element of val_type (FORA_PROP_F32 or FORA_PROP_F64) per held entry, in held order, in host or device memory. */
+enum { FORA_PROP_F64 = 2 }; /* a val_type only */
+int fora_hip_sparse_propagate_vals(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                   const void *feat, int feat_type, int d, int64_t ldf, int flags /*0*/,
+                                   const void *values /*entries*/, int val_type,
+                                   float *out32 /*or NULL*/, double *out64 /*or NULL*/, int64_t ldo,
+                                   fora_prop_stats *ps /*or NULL*/);
+int fora_hip_sparse_propagate_t_vals(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                     const void *grad /*nq x d*/, int grad_type, int d, int64_t ldg, int flags /*0*/,
+                                     const void *values /*entries*/, int val_type,
+                                     float *out32 /*n x d or NULL*/, double *out64 /*n x d or NULL*/, int64_t ldo,
+                                     fora_propt_stats *ps /*or NULL*/);
+
+/* ---- scores on the held pattern (the SCORES (SDDMM) contract above): out[e] = <a[row of e], b[id of e]> over d columns, in a
+ * fixed order of operations.  a: nq x d elements of a_type with pitch lda; b: n x d elements of b_type with pitch ldb. */
+typedef struct { uint64_t entries, segments, max_row, bytes; /* entries * d * (a's element size + b's) */
+                 int32_t a_on_device, b_on_device; double sddmm_ms; } fora_sddmm_stats;
+int fora_hip_sparse_sddmm(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                          const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
+                          float *out32 /*entries or NULL*/, double *out64 /*entries or NULL*/, uint64_t cap,
+                          fora_sddmm_stats *stats /*or NULL*/);
+
 /* copies the transposition of the held result; any of col_ptr / rows / fix / vals may be NULL; cap = entries each of rows /
  * fix / vals can take, col_ptr takes n + 1 */
 int fora_hip_sparse_transpose_fetch(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
