@@ -25,6 +25,7 @@ SYMBOLS = [
     "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
     "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
     "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
+    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -133,6 +134,15 @@ class PropTStats(C.Structure):
 class SddmmStats(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("bytes", C.c_uint64),
                 ("a_on_device", C.c_int32), ("b_on_device", C.c_int32), ("sddmm_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SoftmaxStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("nan_rows", C.c_uint64),
+                ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("in_on_device", C.c_int32), ("grad_on_device", C.c_int32),
+                ("softmax_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -544,7 +554,15 @@ class Engine:
         bptr, btype, db, ldb, b_dev, _kb = self._prop_feat(b, b_bf16, name="b")
         if db != d:
             raise ValueError("a and b must have the same number of columns")
-        on_dev = a_dev or b_dev
+        out32, out64, p32, p64, cap = self._entry_outputs(e, a_dev or b_dev, want32, want64, out32, out64)
+        st = SddmmStats()
+        self._chk(self._lib.fora_hip_sparse_sddmm(self._ctx, _p(rp), C.c_int(nq), aptr, C.c_int(atype), C.c_int64(lda), bptr, C.c_int(btype),
+                                                  C.c_int64(ldb), C.c_int(d), p32, p64, C.c_uint64(cap), C.byref(st)))
+        return out32, out64, st.as_dict()
+
+    def _entry_outputs(self, e, on_dev, want32, want64, out32, out64):
+        """the per-entry outputs of sparse_sddmm / sparse_softmax ([entries]): made here where the caller brought none, on the
+        device (and after a device synchronise) with on_dev.  Returns (out32, out64, pointer32, pointer64, cap)."""
         if on_dev:
             import torch
             dev = torch.device("cuda", self.device)
@@ -575,9 +593,64 @@ class Engine:
             cap = cnt if cap is None else min(cap, cnt)
         if on_dev:
             torch.cuda.synchronize(dev)  # (the operands may have been written, and the allocator may hand out memory, on another stream)
-        st = SddmmStats()
-        self._chk(self._lib.fora_hip_sparse_sddmm(self._ctx, _p(rp), C.c_int(nq), aptr, C.c_int(atype), C.c_int64(lda), bptr, C.c_int(btype),
-                                                  C.c_int64(ldb), C.c_int(d), ptrs[0], ptrs[1], C.c_uint64(cap or 0), C.byref(st)))
+        return out32, out64, ptrs[0], ptrs[1], cap or 0
+
+    def _entry_operand(self, x, entries, name):
+        """(pointer, element type, on_device, keep-alive) of a per-entry input of sparse_softmax / sparse_softmax_bwd: one
+        float32 or float64 per held entry, a numpy array or a torch tensor on the context's GPU"""
+        if self._is_torch(x):
+            import torch
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError(f"a torch {name} must live on the context's GPU")
+            if x.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"{name} must be float32 or float64")
+            if x.dim() != 1 or x.shape[0] != entries:
+                raise ValueError(f"{name} must hold one element per held entry")
+            v = x.detach()
+            if entries > 1 and v.stride(0) != 1:
+                v = v.contiguous()
+            return C.c_void_p(v.data_ptr()), (PROP_F64 if v.dtype == torch.float64 else PROP_F32), True, v
+        a = np.asarray(x)
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{name} must be float32 or float64")
+        if a.ndim != 1 or a.shape[0] != entries:
+            raise ValueError(f"{name} must hold one element per held entry")
+        a = np.ascontiguousarray(a)
+        return _p(a), (PROP_F64 if a.dtype == np.float64 else PROP_F32), False, a
+
+    def sparse_softmax(self, row_ptr, scores, scale=1.0, want32=True, want64=False, out32=None, out64=None):
+        """y[e] = softmax inside its held row of scores[e] * scale (fora_hip_sparse_softmax, the ROW SOFTMAX contract of
+        include/fora_hip.h): the row's maximum subtracted, the contract's exp_def, the row sum in its fixed order, one
+        division -- every bit defined.  scores: one float32 or float64 per held entry in held order, a numpy array or a torch
+        tensor on the context's GPU.  A row with a NaN, with +inf, or of -inf only becomes NaN (stats["nan_rows"]).  Returns
+        (out32 or None, out64 or None, stats dict): [entries], torch tensors on the device when scores is one, numpy arrays
+        otherwise; out32 / out64: caller-made contiguous outputs of at least `entries` elements, as for sparse_sddmm."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        sptr, stype, on_dev, _keep = self._entry_operand(scores, e, "scores")
+        out32, out64, p32, p64, cap = self._entry_outputs(e, on_dev, want32, want64, out32, out64)
+        st = SoftmaxStats()
+        self._chk(self._lib.fora_hip_sparse_softmax(self._ctx, _p(rp), C.c_int(nq), sptr, C.c_int(stype), C.c_double(float(scale)), p32, p64,
+                                                    C.c_uint64(cap), C.byref(st)))
+        return out32, out64, st.as_dict()
+
+    def sparse_softmax_bwd(self, row_ptr, y, grad, scale=1.0, want32=True, want64=False, out32=None, out64=None):
+        """dx[e] = ((grad[e] - D) * y[e]) * scale with D = the row's sum of y * grad in the contract's order
+        (fora_hip_sparse_softmax_bwd): the gradient of sparse_softmax with respect to scores, y its output and scale its
+        scale.  y and grad: float32 or float64 each, numpy or torch on the GPU; outputs as for sparse_softmax (torch when
+        either input is)."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        yptr, ytype, y_dev, _ky = self._entry_operand(y, e, "y")
+        gptr, gtype, g_dev, _kg = self._entry_operand(grad, e, "grad")
+        out32, out64, p32, p64, cap = self._entry_outputs(e, y_dev or g_dev, want32, want64, out32, out64)
+        st = SoftmaxStats()
+        self._chk(self._lib.fora_hip_sparse_softmax_bwd(self._ctx, _p(rp), C.c_int(nq), yptr, C.c_int(ytype), gptr, C.c_int(gtype), C.c_double(float(scale)),
+                                                        p32, p64, C.c_uint64(cap), C.byref(st)))
         return out32, out64, st.as_dict()
 
     def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
@@ -791,6 +864,14 @@ class Engine:
         out = np.zeros(6, dtype=np.uint64)
         self._chk(self._test_entry("fora_hip_test_sweep_scan")(self._ctx, _p(cut), _p(v), C.c_int64(cut.size), C.c_uint64(int(nnz)), _p(out)))
         return cut.view(np.uint64), v, dict(zip(("len", "best", "cut", "vol", "den", "edges"), (int(x) for x in out)))
+
+    def test_exp(self, t):
+        """exp_def of the ROW SOFTMAX contract on the device (fora_hip_test_exp): t a float64 array of points <= 0 (or -inf).
+        Returns a float64 array of the same shape."""
+        a = np.ascontiguousarray(t, dtype=np.float64)
+        out = np.zeros(a.shape, dtype=np.float64)
+        self._chk(self._test_entry("fora_hip_test_exp")(self._ctx, _p(a), C.c_int64(a.size), _p(out)))
+        return out
 
     def local_cluster(self, sources, with_idx=False, threshold=None, max_size=0):
         """The cluster of least conductance around every source: one int32 id array per source, in sweep order (empty when

@@ -15,6 +15,7 @@
 #include "fora_prop.h"
 #include "fora_propt.h"
 #include "fora_sddmm.h"
+#include "fora_softmax.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -35,7 +36,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -100,6 +101,7 @@ struct Tunables {
     int64_t propt_lds_cap = PROPT_LDS_MAX; // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t): keys of a column's run that one workgroup sorts in LDS at most (clamped to 0 .. PROPT_LDS_MAX); a longer run takes the global tier, one of at most 64 keys a wave; 0: every run of two keys or more takes the global tier.  Same bits for every value; a change drops the cached transposition
     int64_t topk_lds_cap = TOPK_LDS_MAX; // SPARSE RESULTS, TOP-K (fora_hip_query_sparse_topk_batch, fora_hip_seeds_sparse_topk_batch): candidates of a cut row that one workgroup stages in LDS at most (clamped to 0 .. TOPK_LDS_MAX, fora_topk_plan.h); a longer row is selected from global memory; 0: every cut row is.  Same bits for every value
     int64_t topk_cand = 0;       // ... entries of the candidate scratch (the rows of a batch are compacted into it chunk by chunk, consecutive rows, a row never split); 0: by free memory; always at least the longest row.  Same bits for every value
+    int64_t softmax_short = SMAX_SHORT_MAX; // ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): a row of at most this many entries (clamped to 0 .. 256, fora_softmax.h) is one wave's, read once and written once; a longer one goes segment by segment through partial maxima and sums; 0: every row does.  Same bits for every value
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -115,6 +117,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
+    {"softmax_short", &Tunables::softmax_short, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -342,6 +345,7 @@ struct PropBufs {
     DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays (SCORES: [entries])
     DevBuf<unsigned char> d_vals;                        // PROPAGATE WITH VALUES: a host `values`, uploaded on every call
     DevBuf<unsigned char> d_a;                           // SCORES: a host `a`, uploaded on every call (a host `b` goes to d_feat)
+    DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN (a host input goes to d_vals, a host grad to d_a)
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
 // result, built by the first of the two calls after a result becomes held and kept with it -- it ends wherever the held
@@ -390,7 +394,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -947,6 +951,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_PROP_COMBINE: t.prop_combine_ms += ms; break; // k_prop_combine: fora_prop_stats only
         case EV_TK_SELECT: t.tk_select_ms += ms; break;       // k_topk_rows: fora_topk_stats only
         case EV_SDDMM: t.sddmm_ms += ms; break;               // k_prop_sddmm: fora_sddmm_stats only
+        case EV_SOFTMAX: t.softmax_ms += ms; break;           // the k_softmax_* kernels of a call: fora_softmax_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -3207,6 +3212,133 @@ int fora_hip_sparse_sddmm(fora_ctx *c, const int64_t *row_ptr, int nq, const voi
     return drop_pairs_unless_ok(c, sddmm_impl(c, row_ptr, nq, a, a_type, lda, b, b_type, ldb, d, out32, out64, st));
 }
 
+// ---- ROW SOFTMAX (the contract of include/fora_hip.h): softmax inside every held row and its gradient, in a fixed order
+extern "C++" {
+namespace {
+struct SoftmaxWork { const PropSeg *shrt, *lng; uint64_t n_short, n_long; double *seg_max, *part; uint32_t *nan_rows; };
+inline dim3 softmax_grid(uint64_t nseg) { return dim3((unsigned)((nseg + BLOCK / 64 - 1) / (BLOCK / 64))); }
+template <typename TS>
+void softmax_launch(fora_ctx *c, const SoftmaxWork &w, const void *scores, double scale, float *o32, double *o64) {
+    const TS *x = (const TS *)scores;
+    if (w.n_short) hipLaunchKernelGGL((k_softmax_short<TS>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, x, scale, o32, o64, w.nan_rows);
+    if (w.n_long) {
+        hipLaunchKernelGGL((k_softmax_seg_max<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, w.seg_max);
+        hipLaunchKernelGGL((k_softmax_seg_sum<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max, w.part);
+        hipLaunchKernelGGL((k_softmax_div<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max,
+                           (const double *)w.part, o32, o64, w.nan_rows);
+    }
+}
+template <typename TY, typename TG>
+void softmax_bwd_launch(fora_ctx *c, const SoftmaxWork &w, const void *y, const void *g, double scale, float *o32, double *o64) {
+    const TY *yy = (const TY *)y;
+    const TG *gg = (const TG *)g;
+    if (w.n_short) hipLaunchKernelGGL((k_softmax_bwd_short<TY, TG>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, yy, gg, scale, o32, o64);
+    if (w.n_long) {
+        hipLaunchKernelGGL((k_softmax_bwd_seg_sum<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, w.part);
+        hipLaunchKernelGGL((k_softmax_bwd_div<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, scale, (const double *)w.part, o32, o64);
+    }
+}
+// both calls: in = scores (forward) or y (backward), grad = null (forward) or g
+int softmax_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *in, int in_type, const void *grad, int g_type, double scale,
+                 float *out32, double *out64, fora_softmax_stats *st) {
+    const uint64_t entries = c->sp.entries;
+    const bool bwd = grad != nullptr;
+    bool in_dev = false, g_dev = false, o32_dev = false, o64_dev = false;
+    if (in) if (int rc = sparse_dest(c, in, in_dev)) return rc;
+    if (grad) if (int rc = sparse_dest(c, grad, g_dev)) return rc;
+    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
+    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
+    PropBufs &pb = c->pr;
+    const uint64_t total = prop_segments(row_ptr, nq);
+    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: the partials are a few bytes per segment)
+    const SoftmaxLists lists = softmax_lists(plan.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (entries && !in_dev) {
+        const size_t bytes = (size_t)entries * (in_type == FORA_PROP_F64 ? 8 : 4);
+        if (int rc = prop_ensure(c, pb.d_vals, bytes, bwd ? "the upload of y" : "the upload of the scores")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_vals.get(), in, bytes, hipMemcpyHostToDevice));
+        in = pb.d_vals.get();
+    }
+    if (entries && bwd && !g_dev) {
+        const size_t bytes = (size_t)entries * (g_type == FORA_PROP_F64 ? 8 : 4);
+        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of grad")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_a.get(), grad, bytes, hipMemcpyHostToDevice));
+        grad = pb.d_a.get();
+    }
+    if (int rc = prop_ensure(c, pb.d_segs, lists.segs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)lists.n_long, "the segment maxima and sums")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)entries, "a staged output")) return rc;
+    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)entries, "a staged output")) return rc;
+    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
+    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
+    c->tm.softmax_ms = 0;
+    uint32_t nan_rows = 0;
+    if (!lists.segs.empty()) {
+        HIPCHK(c, hipMemcpy(pb.d_segs.get(), lists.segs.data(), lists.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        const SoftmaxWork w{pb.d_segs.get(), pb.d_segs.get() + lists.n_short, lists.n_short, lists.n_long, pb.d_smax.get(), pb.d_smax.get() + lists.n_long, pb.d_smax_nan.get()};
+        const bool in64 = in_type == FORA_PROP_F64, g64 = g_type == FORA_PROP_F64;
+        if (!bwd) HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+        {
+            EvSpan ev(c, EV_SOFTMAX);
+            if (!bwd) {
+                if (in64) softmax_launch<double>(c, w, in, scale, w32, w64);
+                else softmax_launch<float>(c, w, in, scale, w32, w64);
+            } else if (in64) {
+                if (g64) softmax_bwd_launch<double, double>(c, w, in, grad, scale, w32, w64);
+                else softmax_bwd_launch<double, float>(c, w, in, grad, scale, w32, w64);
+            } else {
+                if (g64) softmax_bwd_launch<float, double>(c, w, in, grad, scale, w32, w64);
+                else softmax_bwd_launch<float, float>(c, w, in, grad, scale, w32, w64);
+            }
+        }
+        if (!bwd) HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (entries && out32 && !o32_dev) HIPCHK(c, hipMemcpyAsync(out32, w32, (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
+    if (entries && out64 && !o64_dev) HIPCHK(c, hipMemcpyAsync(out64, w64, (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse softmax: ") + hipGetErrorString(err));
+    ev_collect(c);
+    if (st) {
+        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
+        st->nan_rows = nan_rows; st->short_rows = lists.short_rows; st->long_rows = lists.long_rows;
+        st->in_on_device = in_dev ? 1 : 0; st->grad_on_device = g_dev ? 1 : 0;
+        st->softmax_ms = c->tm.softmax_ms;
+    }
+    return FORA_OK;
+}
+// the frame of the two calls (who: the call's name in messages; grad / g_type: the backward call's)
+int softmax_entry(fora_ctx *c, const char *who, const int64_t *row_ptr, int nq, const void *in, int in_type, bool bwd, const void *grad, int g_type, double scale,
+                  float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
+    if (!c) return FORA_E_ARG;
+    const std::string w = std::string(who) + ": ";
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, w + "negative nq or null row_ptr");
+    if (in_type != FORA_PROP_F32 && in_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
+    if (bwd && g_type != FORA_PROP_F32 && g_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, w + "scale is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, w + "no output");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, w + "row_ptr is not the held result's");
+    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, w + "cap is smaller than the held result");
+    if (c->sp.entries && (!in || (bwd && !grad))) return fail(c, FORA_E_ARG, w + "null input");
+    if (st) memset(st, 0, sizeof(*st));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, softmax_impl(c, row_ptr, nq, c->sp.entries ? in : nullptr, in_type, bwd && c->sp.entries ? grad : nullptr, g_type, scale, out32, out64, st));
+}
+} // namespace
+} // extern "C++"
+
+int fora_hip_sparse_softmax(fora_ctx *c, const int64_t *row_ptr, int nq, const void *scores, int val_type, double scale,
+                            float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
+    return softmax_entry(c, "sparse softmax", row_ptr, nq, scores, val_type, false, nullptr, FORA_PROP_F32, scale, out32, out64, cap, st);
+}
+int fora_hip_sparse_softmax_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, const void *y, int y_type, const void *grad, int g_type, double scale,
+                                float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
+    return softmax_entry(c, "sparse softmax_bwd", row_ptr, nq, y, y_type, true, grad, g_type, scale, out32, out64, cap, st);
+}
+
 int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *col_ptr, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap) {
     if (!c) return FORA_E_ARG;
     if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
@@ -3367,6 +3499,23 @@ int fora_hip_test_sweep_scan(fora_ctx *c, int64_t *diff_cut, uint64_t *vol, int6
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("test_sweep_scan: ") + hipGetErrorString(e));
     out6[0] = (uint64_t)o.len; out6[1] = (uint64_t)o.best; out6[2] = o.cut; out6[3] = o.vol; out6[4] = o.den; out6[5] = o.edges;
+    return FORA_OK;
+}
+
+// exp_def (fora_softmax_exp.h) of n host doubles on the device, in buffers of this call's own: the device's bits apart from any softmax
+int fora_hip_test_exp(fora_ctx *c, const double *t, int64_t n, double *out) {
+    if (!c) return FORA_E_ARG;
+    if (n < 0 || n > 0x7FFFFFFF || (n && (!t || !out))) return fail(c, FORA_E_ARG, "test_exp: bad length or null array");
+    if (!n) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> d_t, d_out;
+    HIPCHK(c, d_t.upload(t, (size_t)n));
+    HIPCHK(c, d_out.alloc((size_t)n));
+    hipLaunchKernelGGL(k_softmax_exp, dim3((unsigned)(((uint64_t)n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const double *)d_t.get(), (uint64_t)n, d_out.get());
+    HIPCHK(c, hipMemcpyAsync(out, d_out.get(), (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, FORA_E_HIP, std::string("test_exp: ") + hipGetErrorString(e));
     return FORA_OK;
 }
 #endif // FORA_TEST_PATHS

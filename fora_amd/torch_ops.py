@@ -1,7 +1,7 @@
 """torch.autograd over the held sparse rows: Z = PI * H forward (Engine.sparse_propagate), dL/dH = PI^T * dL/dZ backward
 (Engine.sparse_propagate_t), both on the rows the engine holds -- the propagation step of an APPNP / PPRGo style model whose
 rows are computed once and whose H = MLP(X) changes at every step.  With the caller's values on the held pattern
-(ppr_propagate(values=), ppr_sddmm, row_softmax, ppr_attention) the three operations are each other's gradients, so
+(ppr_propagate(values=), ppr_sddmm, ppr_row_softmax, row_softmax, ppr_attention) the three operations are each other's gradients, so
 attention over the held neighbourhoods, a learned temperature or a re-weighting stay inside the library.  Import torch before the first Engine is created, so that
 the library and torch share one HIP runtime.  fora_amd/__init__.py does not import this module: the package needs no torch."""
 import torch
@@ -147,11 +147,48 @@ def row_softmax(row_ptr, scores):
     return ex / den[row]
 
 
-def ppr_attention(engine, row_ptr, Q, K, V, scale=None):
+class _PprRowSoftmax(torch.autograd.Function):
+    """y = softmax_row(scores * scale) (Engine.sparse_softmax): dscores = ((g - sum_row(y g)) y) scale (Engine.sparse_softmax_bwd)"""
+
+    @staticmethod
+    def forward(ctx, scores, engine, row_ptr, scale):
+        s = scores.detach()
+        if s.dtype not in (torch.float32, torch.float64):
+            s = s.to(torch.float32)
+        y32, _, _ = engine.sparse_softmax(row_ptr, s, scale=scale, want32=True, want64=False)
+        ctx.save_for_backward(y32)
+        ctx.engine, ctx.row_ptr, ctx.scale, ctx.dtype = engine, row_ptr, scale, scores.dtype
+        ctx.generation = engine.get_option("sparse_generation")
+        return y32
+
+    @staticmethod
+    def backward(ctx, g):
+        (y32,) = ctx.saved_tensors
+        _held_guard(ctx.generation, ctx.engine, "ppr_row_softmax")
+        dx, _, _ = ctx.engine.sparse_softmax_bwd(ctx.row_ptr, y32, _entry_values(g), scale=ctx.scale, want32=True, want64=False)
+        return (dx if ctx.dtype == torch.float32 else dx.to(ctx.dtype)), None, None, None
+
+
+def ppr_row_softmax(engine, row_ptr, scores, scale=1.0):
+    """softmax of scores * scale inside every held row of `engine` (Engine.sparse_softmax, the ROW SOFTMAX contract: a defined
+    exp, a fixed order, every bit defined), float32 [entries] on the device, differentiable in scores (a float32 or float64
+    tensor of one element per held entry on the engine's GPU; the gradient comes back in its dtype).  The backward pass is
+    Engine.sparse_softmax_bwd on the saved float32 output.  scale is a number, not a differentiable operand: a learned
+    temperature multiplies the scores before the call.  The rows must still be held when the backward pass runs."""
+    return _PprRowSoftmax.apply(scores, engine, row_ptr, float(scale))
+
+
+def ppr_attention(engine, row_ptr, Q, K, V, scale=None, softmax="torch"):
     """Attention of every row over its held neighbourhood: out[i] = sum over the entries e of row i of
     softmax_row(scale * <Q[i], K[id_e]>)_e * V[id_e] -- ppr_propagate(V, values=row_softmax(ppr_sddmm(Q, K) * scale)).
-    Q: [nq, d], K: [n, d], V: [n, dv]; scale defaults to d ** -0.5.  Differentiable in Q, K and V."""
+    Q: [nq, d], K: [n, d], V: [n, dv]; scale defaults to d ** -0.5.  Differentiable in Q, K and V.
+    softmax: "torch" (the default) takes the softmax with row_softmax, plain torch; "engine" with ppr_row_softmax, scale
+    folded into the call -- all three steps in the library, forward and backward, every bit defined."""
     if scale is None:
         scale = float(Q.shape[1]) ** -0.5
     scores = ppr_sddmm(engine, row_ptr, Q, K)
+    if softmax == "engine":
+        return ppr_propagate(engine, row_ptr, V, values=ppr_row_softmax(engine, row_ptr, scores, scale))
+    if softmax != "torch":
+        raise ValueError('ppr_attention: softmax is "torch" or "engine"')
     return ppr_propagate(engine, row_ptr, V, values=row_softmax(row_ptr, scores * scale))

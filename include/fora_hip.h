@@ -339,6 +339,49 @@
  *     match, NULL a or b with entries to read, d outside 1 .. 65536, lda < d, ldb < d, an unknown a_type or b_type, both
  *     outputs NULL, cap too small: FORA_E_ARG, nothing written.  No device memory for an upload or a staged output:
  *     FORA_E_NOMEM, nothing written, the ctx usable and the held result intact.  nq == 0: FORA_OK, nothing is written.
+ * ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): softmax of one score per held entry inside every held
+ * row, and its gradient -- between SCORES (SDDMM) and PROPAGATE WITH VALUES the third step of attention over the held
+ * neighbourhoods.  The held rows are the pattern only: no word is read.  Every output bit is defined, the exponential
+ * included (tests/softmax_ref.py is the twin).
+ *   - exp_def(t), for t <= 0 and t = -inf (NaN never reaches it): t < -708.0 or t = -inf gives +0.0, so no result is ever
+ *     subnormal.  Otherwise k = rint(t * LOG2E), one multiply and a rounding to nearest even; r = (t - k * LN2_HI) - k * LN2_LO
+ *     with LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1 (21 trailing zero bits: k * LN2_HI is exact for
+ *     |k| <= 1022) and LN2_LO = 0x1.a39ef35793c76p-33; p = c13, then p = p * r + c_j for j = 12 .. 0, each step one multiply
+ *     and one add, never fused, c_j = 1.0 / (double)(j!) (one IEEE division of two exact doubles; 13! < 2^53); the result is
+ *     p * two_k, one multiply, two_k the double with biased exponent k + 1023 and zero significand (k in [-1021, 0]).
+ *     exp_def(+-0.0) is exactly 1.0.
+ *   - forward: scores has one element per held entry, in held order; val_type FORA_PROP_F32 or FORA_PROP_F64, host or device
+ *     memory as the values of PROPAGATE WITH VALUES.  scale: a finite double, anything else is FORA_E_ARG.
+ *     x_e = (double)scores[e] * scale, one multiply.  m_i = the row's largest x_e.  If an x_e of the row is NaN, or m_i is
+ *     +inf, or m_i is -inf (every entry is -inf), all outputs of the row are the quiet NaN 0x7FF8000000000000 (as f32:
+ *     0x7FC00000).  Otherwise m_i is finite; whether +0.0 or -0.0 wins a tie changes no bit.  p_e = exp_def(x_e - m_i): an
+ *     entry of -inf or one more than 708 below the maximum gives +0.0, the maximum gives exactly 1.0, so S_i >= 1.
+ *   - the row sum S_i: the row is cut every FORA_PROP_SEG = 256 entries counted from its first entry.  In a segment q_l,
+ *     l = 0 .. 63, is the sum of the p at the segment-relative positions j == l (mod 64), added in ascending j starting from
+ *     +0.0; then for o = 32, 16, 8, 4, 2, 1: q_l = q_l + q_{l+o} for every l < o; P_s = q_0.  S = P_0, then S = S + P_s for
+ *     s = 1, 2, ... in order -- the lane order of SCORES (SDDMM) inside the segments of PROPAGATE.
+ *   - y_e = p_e / S_i, one IEEE division; out64[e] = y_e, out32[e] = (float)y_e rounded to nearest even.  An empty row writes
+ *     nothing.  cap, the NULL outputs and host or device pointers as in SCORES (SDDMM).
+ *   - backward: y is the forward output as the caller holds it (y_type f32 or f64), grad is g = dL/dy (g_type f32 or f64,
+ *     chosen independently), scale the forward call's.  t_e = (double)y_e * (double)g_e, one multiply; D_i = the row's sum
+ *     of t_e in exactly the order of S_i; dx_e = ((g_e - D_i) * y_e) * scale -- a subtraction, then two multiplies; outputs
+ *     as in the forward call.  Non-finite values follow IEEE; nothing is checked.  scale is a number, not a differentiable
+ *     operand: a learned temperature multiplies the scores before the call.
+ *   - both calls: row_ptr is validated as in PROPAGATE.  No bit depends on the batch size, on the launch shape, on host
+ *     versus device pointers, on "prop_segs", or on the option "softmax_short": a row of at most that many entries (default
+ *     and at most 256) is read once and written once by one wave; a longer one goes segment by segment through partial
+ *     maxima and sums; 0 sends every row there.  The option is readable from the environment like the other non-schedule
+ *     knobs.
+ *   - stats: entries, segments and max_row as in PROPAGATE; nan_rows = the forward rows written as NaN (0 in the backward
+ *     call); short_rows and long_rows = the non-empty rows per path; in_on_device (scores, or y), grad_on_device; softmax_ms
+ *     = the device time of the call's kernels.
+ *   - the held result, its transposition, a held sweep profile, the walk index, the options, the FORA parameters and
+ *     fora_timing are left untouched.  The ctx's stream is synchronised before it returns.
+ *   - errors: NULL ctx is answered without touching the GPU.  No held result, nq < 0, NULL row_ptr, a row_ptr that does not
+ *     match, a NULL input with entries to read, an element type other than the two, a scale that is not finite, both outputs
+ *     NULL, cap too small, memory of another GPU: FORA_E_ARG, nothing written.  No device memory for an upload, the
+ *     partials or a staged output: FORA_E_NOMEM, nothing written, the ctx usable and the held result intact.  nq == 0:
+ *     FORA_OK, nothing is written.
  * PROPAGATE WITH VALUES (fora_hip_sparse_propagate_vals, fora_hip_sparse_propagate_t_vals): the products of PROPAGATE and
  * PROPAGATE, TRANSPOSED with the caller's values in place of the held words -- out = P(values) * H and out = P(values)^T * G,
  * P(values) the held pattern with values[e] at held entry e.  Each is the other's gradient with respect to the dense operand,
@@ -595,6 +638,20 @@ int fora_hip_sparse_sddmm(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq
                           float *out32 /*entries or NULL*/, double *out64 /*entries or NULL*/, uint64_t cap,
                           fora_sddmm_stats *stats /*or NULL*/);
 
+/* ---- softmax inside every held row and its gradient (the ROW SOFTMAX contract above): one element per held entry in and out,
+ * in held order, every bit defined.  scores / y / grad: FORA_PROP_F32 or FORA_PROP_F64 elements in host or device memory. */
+typedef struct { uint64_t entries, segments, max_row, nan_rows /* forward rows written as NaN */,
+                 short_rows, long_rows;                 /* non-empty rows per path (the option "softmax_short") */
+                 int32_t in_on_device /* scores, or y */, grad_on_device; double softmax_ms; } fora_softmax_stats;
+int fora_hip_sparse_softmax(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                            const void *scores /*entries*/, int val_type, double scale,
+                            float *out32 /*entries or NULL*/, double *out64 /*entries or NULL*/, uint64_t cap,
+                            fora_softmax_stats *stats /*or NULL*/);
+int fora_hip_sparse_softmax_bwd(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                const void *y /*entries*/, int y_type, const void *grad /*entries*/, int g_type, double scale,
+                                float *out32 /*entries or NULL*/, double *out64 /*entries or NULL*/, uint64_t cap,
+                                fora_softmax_stats *stats /*or NULL*/);
+
 /* copies the transposition of the held result; any of col_ptr / rows / fix / vals may be NULL; cap = entries each of rows /
  * fix / vals can take, col_ptr takes n + 1 */
 int fora_hip_sparse_transpose_fetch(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
@@ -760,7 +817,11 @@ int fora_hip_get_stamps(fora_ctx *ctx, uint64_t *out32);
  *                                      int64_t k, int64_t *row_ptr (nq + 1, required), fora_sparse_stats *sp (or NULL),
  *                                      fora_topk_stats *tk (or NULL));
  *     fora_hip_test_sparse_rows with the selection of SPARSE RESULTS, TOP-K behind it: the caller's rows are counted, written
- *     into the candidate scratch chunk by chunk and cut to their k largest entries by the library's own kernels. */
+ *     into the candidate scratch chunk by chunk and cut to their k largest entries by the library's own kernels.
+ *
+ *   int fora_hip_test_exp(fora_ctx *ctx, const double *t (n, host), int64_t n, double *out (n, host));
+ *     exp_def of ROW SOFTMAX on the device, one point per thread, in buffers of its own: the device's bits of the exponential
+ *     apart from any softmax.  Every t is <= 0 or -inf. */
 
 #ifdef __cplusplus
 }
