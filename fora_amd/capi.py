@@ -25,7 +25,7 @@ SYMBOLS = [
     "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
     "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
     "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
-    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd",
+    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -146,6 +146,15 @@ class SoftmaxStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AttnStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("nan_rows", C.c_uint64),
+                ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("q_on_device", C.c_int32), ("k_on_device", C.c_int32),
+                ("v_on_device", C.c_int32), ("pad_", C.c_int32), ("attn_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
 PROP_SEG = 256  # FORA_PROP_SEG
@@ -652,6 +661,46 @@ class Engine:
         self._chk(self._lib.fora_hip_sparse_softmax_bwd(self._ctx, _p(rp), C.c_int(nq), yptr, C.c_int(ytype), gptr, C.c_int(gtype), C.c_double(float(scale)),
                                                         p32, p64, C.c_uint64(cap), C.byref(st)))
         return out32, out64, st.as_dict()
+
+    def sparse_attention(self, row_ptr, Q, K, V, heads=1, scale=None, want32=True, want64=False, want_y32=False, want_y64=False,
+                         out32=None, out64=None, q_bf16=False, k_bf16=False, v_bf16=False):
+        """out = softmax inside every held row of (scale * <Q[row], K[id]>) times V, head by head, in ONE call
+        (fora_hip_sparse_attention, the ATTENTION contract of include/fora_hip.h): bit for bit sparse_sddmm (float64), then
+        sparse_softmax, then sparse_propagate(values=...) on the column slices of the heads.  Q: [nq, heads * d], K:
+        [n, heads * d], V: [n, heads * dv], each a numpy float32 array (uint16 with q_bf16 / k_bf16 / v_bf16) or a torch
+        tensor on the context's GPU (float32 or bfloat16), with the stride conventions of sparse_propagate's feat.  scale:
+        d ** -0.5 when None.  Returns (out32 or None, out64 or None, y32 or None, y64 or None, stats dict): out
+        [nq, heads * dv], y (the probabilities, with want_y32 / want_y64) [heads, entries]; torch tensors on the device when
+        an operand is a torch tensor, numpy arrays otherwise.  out32 / out64: caller-made outputs as for sparse_propagate.
+        A (row, head) with a NaN score, a +inf, or -inf only is written as NaN (stats["nan_rows"])."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        heads = int(heads)
+        qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nq, name="Q")
+        kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, name="K")
+        vptr, vtype, wv, ldv, v_dev, _kv = self._prop_feat(V, v_bf16, name="V")
+        if heads < 1 or wq % heads or wv % heads:
+            raise ValueError("heads must be at least 1 and divide the columns of Q and of V")
+        if wk != wq:
+            raise ValueError("Q and K must have the same number of columns")
+        d, dv = wq // heads, wv // heads
+        on_dev = q_dev or k_dev or v_dev
+        if on_dev and not (q_dev and k_dev and v_dev):
+            raise ValueError("Q, K and V: all torch tensors on the GPU, or all numpy arrays")
+        y32, y64, py32, py64, ycap = self._entry_outputs(heads * e, on_dev, want_y32, want_y64, None, None)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nq, wv, on_dev, want32, want64, out32, out64)
+        st = AttnStats()
+        sc = float(d) ** -0.5 if scale is None else float(scale)
+        self._chk(self._lib.fora_hip_sparse_attention(self._ctx, _p(rp), C.c_int(nq), qptr, C.c_int(qtype), C.c_int64(ldq), kptr, C.c_int(ktype),
+                                                      C.c_int64(ldk), vptr, C.c_int(vtype), C.c_int64(ldv), C.c_int(d), C.c_int(dv), C.c_int(heads),
+                                                      C.c_double(sc), p32, p64, C.c_int64(ldo), py32, py64, C.c_uint64(ycap), C.byref(st)))
+        if y32 is not None:
+            y32 = y32.reshape(heads, e)
+        if y64 is not None:
+            y64 = y64.reshape(heads, e)
+        return out32, out64, y32, y64, st.as_dict()
 
     def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
         """The transposition of the held sparse result (fora_hip_sparse_transpose_fetch): (col_ptr, rows, vals), with want_fix

@@ -16,6 +16,7 @@
 #include "fora_propt.h"
 #include "fora_sddmm.h"
 #include "fora_softmax.h"
+#include "fora_attn.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -36,7 +37,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -102,6 +103,7 @@ struct Tunables {
     int64_t topk_lds_cap = TOPK_LDS_MAX; // SPARSE RESULTS, TOP-K (fora_hip_query_sparse_topk_batch, fora_hip_seeds_sparse_topk_batch): candidates of a cut row that one workgroup stages in LDS at most (clamped to 0 .. TOPK_LDS_MAX, fora_topk_plan.h); a longer row is selected from global memory; 0: every cut row is.  Same bits for every value
     int64_t topk_cand = 0;       // ... entries of the candidate scratch (the rows of a batch are compacted into it chunk by chunk, consecutive rows, a row never split); 0: by free memory; always at least the longest row.  Same bits for every value
     int64_t softmax_short = SMAX_SHORT_MAX; // ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): a row of at most this many entries (clamped to 0 .. 256, fora_softmax.h) is one wave's, read once and written once; a longer one goes segment by segment through partial maxima and sums; 0: every row does.  Same bits for every value
+    int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -117,7 +119,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"sweep_lds_cap", &Tunables::sweep_lds_cap, false}, {"sweep_rows", &Tunables::sweep_rows, false},
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
-    {"softmax_short", &Tunables::softmax_short, false},
+    {"softmax_short", &Tunables::softmax_short, false}, {"attn_short", &Tunables::attn_short, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -345,6 +347,9 @@ struct PropBufs {
     DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays (SCORES: [entries])
     DevBuf<unsigned char> d_vals;                        // PROPAGATE WITH VALUES: a host `values`, uploaded on every call
     DevBuf<unsigned char> d_a;                           // SCORES: a host `a`, uploaded on every call (a host `b` goes to d_feat)
+    DevBuf<unsigned char> d_v;                           // ATTENTION: a host `v`, uploaded on every call (a host `q` goes to d_a, a host `k` to d_feat)
+    DevBuf<double> d_attn_s, d_attn_y;                   // ATTENTION: [entries] the scores and the y of the longer rows, one head at a time
+    DevBuf<float> d_y32; DevBuf<double> d_y64;           // ATTENTION: [heads][entries] y outputs on their way to host arrays
     DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN (a host input goes to d_vals, a host grad to d_a)
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
@@ -394,7 +399,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -952,6 +957,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_TK_SELECT: t.tk_select_ms += ms; break;       // k_topk_rows: fora_topk_stats only
         case EV_SDDMM: t.sddmm_ms += ms; break;               // k_prop_sddmm: fora_sddmm_stats only
         case EV_SOFTMAX: t.softmax_ms += ms; break;           // the k_softmax_* kernels of a call: fora_softmax_stats only
+        case EV_ATTN: t.attn_ms += ms; break;                 // every launch of an ATTENTION call: fora_attn_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -2833,6 +2839,39 @@ void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uin
     } else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
     else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
 }
+// the two kernels chunk by chunk over a plan whose segments and records lie at d_segs and d_recs: the partial sums of one chunk
+// live at a time in the ctx's buffers, which the caller has ensured.  timed: an event pair per launch (PROPAGATE's own stats);
+// a caller with a span of its own around the whole passes false.
+void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, bool bf16, const PropGeom &g,
+                        const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed) {
+    PropBufs &b = c->pr;
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const PropChunk &ch = plan.chunks[ci];
+        if (ch.nseg) {
+            EvSpan ev(c);
+            if (timed) ev.begin(EV_PROP_GATHER);
+            const PropSeg *segs = d_segs + ch.seg0;
+            if (!bf16) switch (g.V) {
+                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+            } else switch (g.V) {
+                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
+            }
+        }
+        if (ch.nrec) {
+            EvSpan ev(c);
+            if (timed) ev.begin(EV_PROP_COMBINE);
+            const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
+            const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
+            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, d_recs + ch.rec0, ch.nrec,
+                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
+                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, ld32, w64, ld64);
+        }
+    }
+}
 // the product of one side with feat: plan, buffers, the two kernels chunk by chunk, the staged outputs; the stream is idle and
 // the event times are collected when it returns FORA_OK
 int prop_run(fora_ctx *c, const PropSide &side, const void *feat, int feat_type, int d, int64_t ldf, float *out32, double *out64, int64_t ldo, PropRunStats &rs) {
@@ -2882,30 +2921,7 @@ int prop_run(fora_ctx *c, const PropSide &side, const void *feat, int feat_type,
     const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat, ldf, d, elt, bf16 ? widths_bf16 : widths_f32, 3);
     uint64_t *const segsum = sd.divide ? b.d_segsum.get() : nullptr;
     c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
-    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
-        const PropChunk &ch = plan.chunks[ci];
-        if (ch.nseg) {
-            EvSpan ev(c, EV_PROP_GATHER);
-            const PropSeg *segs = b.d_segs.get() + ch.seg0;
-            if (!bf16) switch (g.V) {
-                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-            } else switch (g.V) {
-                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-            }
-        }
-        if (ch.nrec) {
-            EvSpan ev(c, EV_PROP_COMBINE);
-            const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
-            const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
-            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, (const PropRowRec *)(b.d_recs.get() + ch.rec0), ch.nrec,
-                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
-                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, o32_dev ? ldo : (int64_t)d, w64, o64_dev ? ldo : (int64_t)d);
-        }
-    }
+    prop_launch_chunks(c, plan, b.d_segs.get(), b.d_recs.get(), sd, bf16, g, feat, ldf, d, segsum, w32, o32_dev ? ldo : (int64_t)d, w64, o64_dev ? ldo : (int64_t)d, true);
     if (out32 && !o32_dev) HIPCHK(c, hipMemcpy2DAsync(out32, (size_t)ldo * 4, w32, (size_t)d * 4, (size_t)d * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     if (out64 && !o64_dev) HIPCHK(c, hipMemcpy2DAsync(out64, (size_t)ldo * 8, w64, (size_t)d * 8, (size_t)d * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3337,6 +3353,195 @@ int fora_hip_sparse_softmax(fora_ctx *c, const int64_t *row_ptr, int nq, const v
 int fora_hip_sparse_softmax_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, const void *y, int y_type, const void *grad, int g_type, double scale,
                                 float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
     return softmax_entry(c, "sparse softmax_bwd", row_ptr, nq, y, y_type, true, grad, g_type, scale, out32, out64, cap, st);
+}
+
+// ---- ATTENTION (the contract of include/fora_hip.h): SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES per head in one call -- the
+// rows of at most "attn_short" entries in the fused kernel (fora_attn.h), the longer ones through the three steps' own kernels
+extern "C++" {
+namespace {
+template <bool QB, bool KB, bool VB, int V>
+void attn_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v, int64_t ldv,
+                 int d, int dv, uint32_t lg, double scale, uint64_t entries, float *o32, int64_t ld32, double *o64, int64_t ld64, float *y32, double *y64, uint32_t *nan_rows) {
+    const uint64_t units = nrow * (uint64_t)heads;
+    hipLaunchKernelGGL((k_attn_short<QB, KB, VB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), q, ldq, k, ldk, v, ldv, (uint32_t)d, (uint32_t)dv, lg, scale, entries, o32, ld32, o64, ld64, y32, y64, nan_rows);
+}
+template <bool QB, bool KB, typename... A>
+void attn_launch_v(bool v_bf16, uint32_t V, A... a) {
+    if (!v_bf16) switch (V) {
+        case 4: attn_launch<QB, KB, false, 4>(a...); break;
+        case 2: attn_launch<QB, KB, false, 2>(a...); break;
+        default: attn_launch<QB, KB, false, 1>(a...); break;
+    } else switch (V) {
+        case 8: attn_launch<QB, KB, true, 8>(a...); break;
+        case 4: attn_launch<QB, KB, true, 4>(a...); break;
+        default: attn_launch<QB, KB, true, 1>(a...); break;
+    }
+}
+inline const void *attn_cols(const void *m, uint64_t col, uint32_t elt) { return (const unsigned char *)m + col * elt; }
+
+int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
+                   const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
+                   float *y32, double *y64, fora_attn_stats *st) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16;
+    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4;
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
+    bool q_dev = false, k_dev = false, v_dev = false, o32_dev = false, o64_dev = false, y32_dev = false, y64_dev = false;
+    if (q) if (int rc = sparse_dest(c, q, q_dev)) return rc;
+    if (k) if (int rc = sparse_dest(c, k, k_dev)) return rc;
+    if (v) if (int rc = sparse_dest(c, v, v_dev)) return rc;
+    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
+    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
+    if (y32) if (int rc = sparse_dest(c, y32, y32_dev)) return rc;
+    if (y64) if (int rc = sparse_dest(c, y64, y64_dev)) return rc;
+    PropBufs &pb = c->pr;
+    // ---- the plan: the short rows' list; the longer rows' segments in chunks of prop_segs (0: a quarter of the free memory in
+    // partial sums at most), split once more for the softmax kernels by softmax_short
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    uint64_t long_segs = 0;
+    for (int i = 0; i < nq; i++) {
+        const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
+        if (len > cap) long_segs += (len + PROP_SEG - 1) / PROP_SEG;
+    }
+    size_t fr = 0, tot = 0;
+    if (long_segs && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, long_segs, (uint64_t)fr, dv);
+    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per);
+    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    const bool lng = !plan.lrows.empty();
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (entries && !q_dev) {
+        const size_t bytes = (size_t)((((uint64_t)nq - 1) * (uint64_t)ldq + wq) * q_elt);
+        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of q")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_a.get(), q, bytes, hipMemcpyHostToDevice));
+        q = pb.d_a.get();
+    }
+    if (entries && !k_dev) {
+        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldk + wq) * k_elt);
+        if (int rc = prop_ensure(c, pb.d_feat, bytes, "the upload of k")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_feat.get(), k, bytes, hipMemcpyHostToDevice));
+        k = pb.d_feat.get();
+    }
+    if (entries && !v_dev) {
+        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldv + wv) * v_elt);
+        if (int rc = prop_ensure(c, pb.d_v, bytes, "the upload of v")) return rc;
+        HIPCHK(c, hipMemcpy(pb.d_v.get(), v, bytes, hipMemcpyHostToDevice));
+        v = pb.d_v.get();
+    }
+    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), at_lrows = at_sm + sm.segs.size(),
+                 nsegs = at_lrows + plan.lrows.size();
+    if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    if (lng) {
+        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)dv), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment maxima and sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the scores of the longer rows")) return rc;
+        if (!y64) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)entries, "the y of the longer rows")) return rc;
+    }
+    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)nq * (size_t)wv, "a staged output")) return rc;
+    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)nq * (size_t)wv, "a staged output")) return rc;
+    if (y32 && !y32_dev) if (int rc = prop_ensure(c, pb.d_y32, (size_t)heads * (size_t)entries, "a staged output")) return rc;
+    if (y64 && !y64_dev) if (int rc = prop_ensure(c, pb.d_y64, (size_t)heads * (size_t)entries, "a staged output")) return rc;
+    PropSeg *const ds = pb.d_segs.get();
+    if (!plan.shrt.empty()) HIPCHK(c, hipMemcpy(ds + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (lng) {
+        HIPCHK(c, hipMemcpy(ds + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(ds + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(ds + at_lrows, plan.lrows.data(), plan.lrows.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    }
+    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
+    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
+    const int64_t ld32 = o32_dev ? ldo : (int64_t)wv, ld64 = o64_dev ? ldo : (int64_t)wv;
+    float *const wy32 = !y32 ? nullptr : y32_dev ? y32 : pb.d_y32.get();
+    double *const wy64 = !y64 ? nullptr : y64_dev ? y64 : pb.d_y64.get();
+    uint32_t lg = 0;
+    while (lg < 6 && (1u << lg) < (uint32_t)d) lg++; // the smallest group that holds d columns, at most a wave
+    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
+    const uint32_t *const widths = v_bf16 ? widths_bf16 : widths_f32;
+    c->tm.attn_ms = 0;
+    uint32_t nan_rows = 0;
+    HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+    {
+        EvSpan ev(c, EV_ATTN);
+        if (!plan.shrt.empty()) {
+            const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)v, ldv, dv, heads, v_elt, widths, 3);
+#define ATTN_ARGS v_bf16, V, c, (const PropSeg *)(ds + at_short), (uint64_t)plan.shrt.size(), heads, q, ldq, k, ldk, v, ldv, d, dv, lg, scale, entries, w32, ld32, w64, ld64, wy32, wy64, pb.d_smax_nan.get()
+            if (!q_bf16 && !k_bf16) attn_launch_v<false, false>(ATTN_ARGS);
+            else if (!q_bf16) attn_launch_v<false, true>(ATTN_ARGS);
+            else if (!k_bf16) attn_launch_v<true, false>(ATTN_ARGS);
+            else attn_launch_v<true, true>(ATTN_ARGS);
+#undef ATTN_ARGS
+        }
+        for (int h = 0; lng && h < heads; h++) { // the longer rows, one head at a time through the two per-entry buffers
+            const void *qh = attn_cols(q, (uint64_t)h * d, q_elt), *kh = attn_cols(k, (uint64_t)h * d, k_elt), *vh = attn_cols(v, (uint64_t)h * dv, v_elt);
+            double *const s64 = pb.d_attn_s.get();
+            double *const yh64 = wy64 ? wy64 + (uint64_t)h * entries : pb.d_attn_y.get();
+            float *const yh32 = wy32 ? wy32 + (uint64_t)h * entries : nullptr;
+            const PropSeg *segs = ds + at_lsegs;
+            const uint64_t nseg = plan.lng.segs.size();
+            if (!q_bf16 && !k_bf16) sddmm_launch<false, false>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            else if (!q_bf16) sddmm_launch<false, true>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            else if (!k_bf16) sddmm_launch<true, false>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            else sddmm_launch<true, true>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            const SoftmaxWork w{ds + at_sm, ds + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, pb.d_smax_nan.get()};
+            softmax_launch<double>(c, w, s64, scale, yh32, yh64);
+            const PropSide sd{row_ptr, nq, n, c->sp.d_ids.get(), nullptr, nullptr, false, yh64, true, nullptr};
+            const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, 3);
+            float *const oh32 = w32 ? w32 + (uint64_t)h * dv : nullptr;
+            double *const oh64 = w64 ? w64 + (uint64_t)h * dv : nullptr;
+            prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, v_bf16, g, vh, ldv, dv, nullptr, oh32, ld32, oh64, ld64, false);
+            const dim3 grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(plan.lrows.size(), 65535));
+            hipLaunchKernelGGL(k_attn_nan_rows, grid, dim3(BLOCK), 0, c->stream, (const PropSeg *)(ds + at_lrows), (uint64_t)plan.lrows.size(), (const double *)yh64,
+                               (uint32_t)dv, oh32, ld32, oh64, ld64);
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
+    if (out32 && !o32_dev) HIPCHK(c, hipMemcpy2DAsync(out32, (size_t)ldo * 4, w32, (size_t)wv * 4, (size_t)wv * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (out64 && !o64_dev) HIPCHK(c, hipMemcpy2DAsync(out64, (size_t)ldo * 8, w64, (size_t)wv * 8, (size_t)wv * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (entries && y32 && !y32_dev) HIPCHK(c, hipMemcpyAsync(y32, wy32, (size_t)heads * (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
+    if (entries && y64 && !y64_dev) HIPCHK(c, hipMemcpyAsync(y64, wy64, (size_t)heads * (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse attention: ") + hipGetErrorString(err));
+    ev_collect(c);
+    if (st) {
+        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
+        st->nan_rows = nan_rows; st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
+        st->q_on_device = q_dev ? 1 : 0; st->k_on_device = k_dev ? 1 : 0; st->v_on_device = v_dev ? 1 : 0;
+        st->attn_ms = c->tm.attn_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+} // extern "C++"
+
+int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
+                              const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
+                              float *y32, double *y64, uint64_t ycap, fora_attn_stats *st) {
+    if (!c) return FORA_E_ARG;
+    const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse attention: negative nq or null row_ptr");
+    if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type)) return fail(c, FORA_E_ARG, "sparse attention: unknown q_type, k_type or v_type");
+    if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: d or dv outside 1 .. 65536");
+    if (heads < 1 || (int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: heads < 1, or heads * d or heads * dv over 65536");
+    if (ldq < (int64_t)heads * d || ldk < (int64_t)heads * d) return fail(c, FORA_E_ARG, "sparse attention: ldq or ldk smaller than heads * d");
+    if (ldv < (int64_t)heads * dv || ldo < (int64_t)heads * dv) return fail(c, FORA_E_ARG, "sparse attention: ldv or ldo smaller than heads * dv");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, "sparse attention: scale is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse attention: no output");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse attention: row_ptr is not the held result's");
+    if ((y32 || y64) && ycap < (uint64_t)heads * c->sp.entries) return fail(c, FORA_E_ARG, "sparse attention: ycap is smaller than heads * the held entries");
+    if (c->sp.entries && (!q || !k || !v)) return fail(c, FORA_E_ARG, "sparse attention: null q, k or v");
+    if (st) memset(st, 0, sizeof(*st));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, attention_impl(c, row_ptr, nq, c->sp.entries ? q : nullptr, q_type, ldq, c->sp.entries ? k : nullptr, k_type, ldk,
+                                                  c->sp.entries ? v : nullptr, v_type, ldv, d, dv, heads, scale, out32, out64, ldo, y32, y64, st));
 }
 
 int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *col_ptr, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap) {

@@ -55,15 +55,18 @@ inline uint64_t prop_chunk_segs(int64_t option, uint64_t segments, uint64_t free
 // prop_segs: segments per chunk, at least 1 (prop_chunk_segs has resolved the option to a number).  row_ptr has passed
 // prop_row_ptr_ok.  A chunk is closed only when a further segment no longer fits, so empty rows never open one of their
 // own: chunks == max(1, ceil(segments / prop_segs)) for nq > 0.
-inline PropPlan prop_plan(const int64_t *row_ptr, int nq, uint64_t prop_segs) {
+// keep(i, len): the rows that take part -- a row it refuses gets no segment and no record, as if the list were made for the
+// others alone (ATTENTION plans its longer rows this way, fora_attn_plan.h); entries and max_row are of the rows kept.
+template <typename Keep>
+inline PropPlan prop_plan_if(const int64_t *row_ptr, int nq, uint64_t prop_segs, Keep keep) {
     PropPlan p;
     prop_segs = std::max<uint64_t>(prop_segs, 1);
     if (nq <= 0) return p;
-    p.entries = (uint64_t)row_ptr[nq];
-    p.segs.reserve((size_t)prop_segments(row_ptr, nq));
     p.chunks.push_back(PropChunk{});
     for (int i = 0; i < nq; i++) {
         const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
+        if (!keep(i, len)) continue;
+        p.entries += len;
         p.max_row = std::max(p.max_row, len);
         if (!len) {
             p.recs.push_back(PropRowRec{i, 0, 0, PROP_FIRST | PROP_LAST});
@@ -88,6 +91,9 @@ inline PropPlan prop_plan(const int64_t *row_ptr, int nq, uint64_t prop_segs) {
         }
     }
     return p;
+}
+inline PropPlan prop_plan(const int64_t *row_ptr, int nq, uint64_t prop_segs) {
+    return prop_plan_if(row_ptr, nq, prop_segs, [](int, uint64_t) { return true; });
 }
 
 // ---- how the gather kernel's lanes map to columns (prop_geom): a lane takes V adjacent columns of one feature row, a

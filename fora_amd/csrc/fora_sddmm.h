@@ -7,7 +7,8 @@
 // the q_l of l >= G are +0.0 and no q_l is ever -0.0, so the steps o >= G of the tree change no bit and the group runs only
 // its own.  The work list is the segment list of fora_prop_plan.h; a wave takes SDDMM_SUB entries of one segment -- one row
 // of A, re-read per column block from the cache -- and every group has the B rows of SDDMM_INFLIGHT entries in flight, whose
-// four trees share their first two exchanges (below).
+// four trees share their first two exchanges (below).  The loop over a wave's entries is sddmm_scores, which the fused
+// attention kernel (fora_attn.h) calls too: what becomes of a finished score is the caller's.
 // Nothing is fused: the file is compiled with -ffp-contract=off and the kernel says so again itself.
 #pragma once
 #include "fora_kernels.h" // BLOCK
@@ -25,25 +26,18 @@ template <bool BF16> __device__ __forceinline__ uint32_t sddmm_load(const void *
     else return __float_as_uint(((const float *)m)[at]);
 }
 
-// grid = ceil(nseg * SDDMM_UNITS / (BLOCK / 64)) workgroups of BLOCK threads; lg = log2(G).  Wave u of the grid owns the
-// entries [sub * SDDMM_SUB, ...) of segment u / SDDMM_UNITS, sub = u % SDDMM_UNITS; group g of its 64 / G groups the entries
-// g, g + 64 / G, ... of those, SDDMM_INFLIGHT of them per round.  Every lane of the wave runs every round (the shuffles of
-// the tree want whole groups); an entry past the count loads nothing and stores nothing.
-template <bool A_BF16, bool B_BF16>
-__global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const void *a, int64_t lda, const void *b,
-                                                      int64_t ldb, uint32_t d, uint32_t lg, float *out32, double *out64) {
+// The scores of `cnt` entries with the ids ids[0 .. cnt) against one row of a (arow: its first element), by one whole wave;
+// lg = log2(G).  Group g of the wave's 64 / G groups takes the entries g, g + 64 / G, ..., SDDMM_INFLIGHT of them per round.
+// Every lane of the wave runs every round (the shuffles of the tree want whole groups); an entry past the count loads nothing
+// and is never handed on.  bcol: the first column of b that counts (a column slice: a head), added to every row's place.
+// sink(k, s): called once per entry k < cnt, on the lane that ends up with its score s -- the one thing in which the callers
+// differ (k_prop_sddmm stores it, k_attn_short of fora_attn.h keeps it in LDS).
+template <bool A_BF16, bool B_BF16, typename Sink>
+__device__ __forceinline__ void sddmm_scores(const int32_t *ids, uint32_t cnt, const void *a, uint64_t arow, const void *b, int64_t ldb, uint64_t bcol,
+                                             uint32_t d, uint32_t lg, uint32_t lane, Sink &&sink) {
 #pragma clang fp contract(off)
-    const uint32_t lane = threadIdx.x & 63u, G = 1u << lg;
+    const uint32_t G = 1u << lg;
     const uint32_t gl = lane & (G - 1u), grp = lane >> lg, ngrp = 64u >> lg;
-    const uint64_t unit = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const uint64_t s = unit / SDDMM_UNITS;
-    const uint32_t lo = (uint32_t)(unit % SDDMM_UNITS) * SDDMM_SUB;
-    if (s >= nseg) return; // (the whole wave)
-    const PropSeg sg = segs[s];
-    if (lo >= sg.len) return;
-    const uint32_t cnt = min(SDDMM_SUB, sg.len - lo);
-    const int64_t e0 = sg.first + lo;
-    const uint64_t arow = (uint64_t)(uint32_t)sg.row * (uint64_t)lda;
     for (uint32_t j0 = 0; j0 < cnt; j0 += ngrp * SDDMM_INFLIGHT) {
         uint64_t brow[SDDMM_INFLIGHT];
         bool valid[SDDMM_INFLIGHT];
@@ -52,7 +46,7 @@ __global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint6
         for (int u = 0; u < SDDMM_INFLIGHT; u++) {
             const uint32_t k = j0 + (uint32_t)u * ngrp + grp;
             valid[u] = k < cnt;
-            brow[u] = valid[u] ? (uint64_t)(uint32_t)ids[e0 + k] * (uint64_t)ldb : 0ull;
+            brow[u] = valid[u] ? (uint64_t)(uint32_t)ids[k] * (uint64_t)ldb + bcol : 0ull;
             q[u] = 0.0;
         }
         for (uint32_t c = gl; c < d; c += 64u) {
@@ -82,10 +76,7 @@ __global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint6
             if ((gl & (o2 - 1u)) == 0) { // the first lane of a quarter: the entry (2 if the second quarter of its half) + (1 if the upper half)
                 const uint32_t u = (up2 ? 2u : 0u) + (up1 ? 1u : 0u);
                 const uint32_t k = j0 + u * ngrp + grp;
-                if (k < cnt) {
-                    if (out64) out64[e0 + k] = s;
-                    if (out32) out32[e0 + k] = (float)s;
-                }
+                if (k < cnt) sink(k, s);
             }
         } else {
             if (G == 2u) {
@@ -96,13 +87,33 @@ __global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint6
 #pragma unroll
                 for (int u = 0; u < SDDMM_INFLIGHT; u++) {
                     if (!valid[u]) continue;
-                    const int64_t e = e0 + j0 + (uint32_t)u * ngrp + grp;
-                    if (out64) out64[e] = q[u];
-                    if (out32) out32[e] = (float)q[u];
+                    sink(j0 + (uint32_t)u * ngrp + grp, q[u]);
                 }
             }
         }
     }
+}
+
+// grid = ceil(nseg * SDDMM_UNITS / (BLOCK / 64)) workgroups of BLOCK threads; lg = log2(G).  Wave u of the grid owns the
+// entries [sub * SDDMM_SUB, ...) of segment u / SDDMM_UNITS, sub = u % SDDMM_UNITS, and scores them with sddmm_scores.
+template <bool A_BF16, bool B_BF16>
+__global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const void *a, int64_t lda, const void *b,
+                                                      int64_t ldb, uint32_t d, uint32_t lg, float *out32, double *out64) {
+#pragma clang fp contract(off)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t unit = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t s = unit / SDDMM_UNITS;
+    const uint32_t lo = (uint32_t)(unit % SDDMM_UNITS) * SDDMM_SUB;
+    if (s >= nseg) return; // (the whole wave)
+    const PropSeg sg = segs[s];
+    if (lo >= sg.len) return;
+    const uint32_t cnt = min(SDDMM_SUB, sg.len - lo);
+    const int64_t e0 = sg.first + lo;
+    const uint64_t arow = (uint64_t)(uint32_t)sg.row * (uint64_t)lda;
+    sddmm_scores<A_BF16, B_BF16>(ids + e0, cnt, a, arow, b, ldb, 0ull, d, lg, lane, [=](uint32_t k, double sc) {
+        if (out64) out64[e0 + k] = sc;
+        if (out32) out32[e0 + k] = (float)sc;
+    });
 }
 
 } // namespace fora

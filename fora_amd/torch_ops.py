@@ -1,7 +1,7 @@
 """torch.autograd over the held sparse rows: Z = PI * H forward (Engine.sparse_propagate), dL/dH = PI^T * dL/dZ backward
 (Engine.sparse_propagate_t), both on the rows the engine holds -- the propagation step of an APPNP / PPRGo style model whose
 rows are computed once and whose H = MLP(X) changes at every step.  With the caller's values on the held pattern
-(ppr_propagate(values=), ppr_sddmm, ppr_row_softmax, row_softmax, ppr_attention) the three operations are each other's gradients, so
+(ppr_propagate(values=), ppr_sddmm, ppr_row_softmax, row_softmax, ppr_attention, ppr_attention_fused) the three operations are each other's gradients, so
 attention over the held neighbourhoods, a learned temperature or a re-weighting stay inside the library.  Import torch before the first Engine is created, so that
 the library and torch share one HIP runtime.  fora_amd/__init__.py does not import this module: the package needs no torch."""
 import torch
@@ -178,17 +178,78 @@ def ppr_row_softmax(engine, row_ptr, scores, scale=1.0):
     return _PprRowSoftmax.apply(scores, engine, row_ptr, float(scale))
 
 
+class _PprAttentionFused(torch.autograd.Function):
+    """out = attention over the held rows in one call (Engine.sparse_attention), y32 saved; the backward pass head by head on
+    column slices with the existing calls: dV = P(y)^T x G, dy = sddmm(G, V), ds = softmax_bwd(y, dy), dQ = P(ds) x K,
+    dK = P(ds)^T x Q"""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, engine, row_ptr, scale, heads):
+        out32, _, y32, _, _ = engine.sparse_attention(row_ptr, Q.detach(), K.detach(), V.detach(), heads=heads, scale=scale,
+                                                      want32=True, want64=False, want_y32=True)
+        ctx.save_for_backward(Q, K, V, y32)
+        ctx.engine, ctx.row_ptr, ctx.scale, ctx.heads = engine, row_ptr, scale, heads
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        Q, K, V, y32 = ctx.saved_tensors
+        engine, row_ptr, heads = ctx.engine, ctx.row_ptr, ctx.heads
+        _held_guard(ctx.generation, engine, "ppr_attention_fused")
+        G = _dense_operand(G)
+        d, dv = Q.shape[1] // heads, V.shape[1] // heads
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        Qd, Kd, Vd = Q.detach(), K.detach(), V.detach()
+        dQ = torch.empty(Q.shape, dtype=torch.float32, device=Q.device) if need_q else None
+        dK = torch.empty(K.shape, dtype=torch.float32, device=K.device) if need_k else None
+        dV = torch.empty(V.shape, dtype=torch.float32, device=V.device) if need_v else None
+        for j in range(heads):
+            qs, vs = slice(j * d, (j + 1) * d), slice(j * dv, (j + 1) * dv)
+            Gj, yj = G[:, vs], y32[j]
+            if need_v:
+                engine.sparse_propagate_t(row_ptr, Gj, want64=False, values=yj, out32=dV[:, vs])
+            if need_q or need_k:
+                dy, _, _ = engine.sparse_sddmm(row_ptr, Gj, Vd[:, vs], want32=True, want64=False)
+                ds, _, _ = engine.sparse_softmax_bwd(row_ptr, yj, dy, scale=ctx.scale, want32=True, want64=False)
+                if need_q:
+                    engine.sparse_propagate(row_ptr, Kd[:, qs], want64=False, values=ds, out32=dQ[:, qs])
+                if need_k:
+                    engine.sparse_propagate_t(row_ptr, Qd[:, qs], want64=False, values=ds, out32=dK[:, qs])
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dQ, Q), cast(dK, K), cast(dV, V), None, None, None, None
+
+
+def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1):
+    """ppr_attention with all three steps in ONE library call (Engine.sparse_attention, the ATTENTION contract): the rows of at
+    most 256 entries are scored, normalised and multiplied by one wave each without anything written in between, and nothing
+    is rounded to float32 between the steps.  Q: [nq, heads * d], K: [n, heads * d], V: [n, heads * dv], float32 or bfloat16
+    on the engine's GPU; head j attends with the columns [j * d, (j + 1) * d) of Q and K and writes the columns
+    [j * dv, (j + 1) * dv) of the result, [nq, heads * dv] float32.  scale defaults to d ** -0.5 and is a number, not a
+    differentiable operand.  Differentiable in Q, K and V: the backward pass runs head by head with the calls ppr_attention
+    (softmax="engine") uses, on the float32 probabilities the forward call saved.  The rows must still be held when it runs."""
+    heads = int(heads)
+    if heads < 1 or Q.shape[1] % heads or V.shape[1] % heads:
+        raise ValueError("ppr_attention_fused: heads must be at least 1 and divide the columns of Q and of V")
+    if scale is None:
+        scale = float(Q.shape[1] // heads) ** -0.5
+    return _PprAttentionFused.apply(Q, K, V, engine, row_ptr, float(scale), heads)
+
+
 def ppr_attention(engine, row_ptr, Q, K, V, scale=None, softmax="torch"):
     """Attention of every row over its held neighbourhood: out[i] = sum over the entries e of row i of
     softmax_row(scale * <Q[i], K[id_e]>)_e * V[id_e] -- ppr_propagate(V, values=row_softmax(ppr_sddmm(Q, K) * scale)).
     Q: [nq, d], K: [n, d], V: [n, dv]; scale defaults to d ** -0.5.  Differentiable in Q, K and V.
     softmax: "torch" (the default) takes the softmax with row_softmax, plain torch; "engine" with ppr_row_softmax, scale
-    folded into the call -- all three steps in the library, forward and backward, every bit defined."""
+    folded into the call -- all three steps in the library, forward and backward, every bit defined; "fused" is
+    ppr_attention_fused with one head -- the forward pass in one library call."""
     if scale is None:
         scale = float(Q.shape[1]) ** -0.5
+    if softmax == "fused":
+        return ppr_attention_fused(engine, row_ptr, Q, K, V, scale=scale, heads=1)
     scores = ppr_sddmm(engine, row_ptr, Q, K)
     if softmax == "engine":
         return ppr_propagate(engine, row_ptr, V, values=ppr_row_softmax(engine, row_ptr, scores, scale))
     if softmax != "torch":
-        raise ValueError('ppr_attention: softmax is "torch" or "engine"')
+        raise ValueError('ppr_attention: softmax is "torch", "engine" or "fused"')
     return ppr_propagate(engine, row_ptr, V, values=row_softmax(row_ptr, scores * scale))

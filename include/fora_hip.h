@@ -382,6 +382,47 @@
  *     NULL, cap too small, memory of another GPU: FORA_E_ARG, nothing written.  No device memory for an upload, the
  *     partials or a staged output: FORA_E_NOMEM, nothing written, the ctx usable and the held result intact.  nq == 0:
  *     FORA_OK, nothing is written.
+ * ATTENTION (fora_hip_sparse_attention): SCORES (SDDMM), ROW SOFTMAX and PROPAGATE WITH VALUES over the held rows in one call,
+ * for `heads` column slices at once -- out = softmax_row(scale * <q, k>) * v on the held pattern.  Every output bit is
+ * defined as the composition of those three contracts (tests/attention_ref.py is the twin).
+ *   - q is row-major nq x heads * d on the row side, pitch ldq; k is n x heads * d and v is n x heads * dv on the node side,
+ *     pitches ldk and ldv; out is nq x heads * dv, pitch ldo.  q_type, k_type and v_type are each FORA_PROP_F32 or
+ *     FORA_PROP_BF16 (widened exactly), chosen independently.  d and dv in 1 .. 65536, heads >= 1 with heads * d and
+ *     heads * dv at most 65536; ldq, ldk >= heads * d; ldv, ldo >= heads * dv; scale a finite double.
+ *   - per head j, with A = q[:, j*d : (j+1)*d], B = k[:, j*d : (j+1)*d] and H = v[:, j*dv : (j+1)*dv]:
+ *       score_e is exactly SCORES (SDDMM) of (A, B): the 64 lane sums and the tree, in f64;
+ *       y_e is exactly ROW SOFTMAX of those f64 scores with `scale`: exp_def, the row sum in the 64-lane order inside
+ *         segments of 256 entries, one division;
+ *       out[i][j*dv + c] is exactly PROPAGATE WITH VALUES of H with the f64 y_e as the values: segments of 256 entries added in
+ *         entry order from +0.0, acc = P_0, acc = acc + P_s.
+ *     Nothing is rounded to f32 between the steps: the call equals fora_hip_sparse_sddmm (out64), fora_hip_sparse_softmax (F64
+ *     in, out64) and fora_hip_sparse_propagate_vals (F64 values) on the column slices, bit for bit, in out64 wherever no NaN
+ *     row is involved.  out32 = (float)out64, rounded to nearest even.  Either may be NULL, both NULL is FORA_E_ARG.
+ *   - y64[j * entries + e] = y_e and y32 = (float)y_e: optional outputs of the probabilities, head by head, which a backward
+ *     pass needs.  Both may be NULL.  ycap = the elements each non-NULL one can take; ycap < heads * entries with a non-NULL
+ *     y output is FORA_E_ARG.
+ *   - a (row, head) whose softmax row is a NaN row by the rule of ROW SOFTMAX (a NaN score, a maximum of +inf, or all -inf)
+ *     is written, not computed: its y entries and its dv outputs are the quiet NaN 0x7FF8000000000000 (as f32: 0x7FC00000),
+ *     and it is counted in nan_rows.  The products define no NaN payload, so on such rows the chained calls agree in
+ *     NaN-ness only.  An empty row writes +0.0 to its heads * dv outputs and nothing to y.
+ *   - q, k, v, out32, out64, y32 and y64 may each be pageable host memory or device memory on the ctx's GPU (memory of another
+ *     GPU is FORA_E_ARG).  A device operand needs only element alignment: any base, any pitch, a column slice of a wider
+ *     tensor.  A host q is uploaded on every call ((nq - 1) * ldq + heads * d elements), a host k and v likewise
+ *     ((n - 1) * pitch + columns elements); host outputs are staged in device memory.  These buffers are the ctx's.
+ *   - no bit depends on the batch size, on "prop_segs", on "softmax_short", on host versus device pointers, on the launch
+ *     shape, or on the option "attn_short": a non-empty row of at most that many entries (default and at most 256) is one
+ *     wave's per head in a fused kernel -- scored, normalised and multiplied without anything leaving the CU; a longer one
+ *     goes through the kernels of the three steps inside the same call, one head at a time; 0 sends every row there.  The
+ *     option is readable from the environment like the other non-schedule knobs.
+ *   - stats: entries, segments and max_row as in PROPAGATE; nan_rows counts (row, head) pairs; short_rows and long_rows = the
+ *     non-empty rows per path; q_on_device, k_on_device, v_on_device; attn_ms = the device time of the call's launches.
+ *   - the held result, its transposition, a held sweep profile, the walk index, the options, the FORA parameters and
+ *     fora_timing are left untouched.  The ctx's stream is synchronised before it returns.
+ *   - errors: NULL ctx is answered without touching the GPU.  The FORA_E_ARG cases of SCORES (SDDMM) (no held result, nq < 0,
+ *     NULL row_ptr, a row_ptr that does not match, a NULL operand with entries to read, an unknown element type, memory of
+ *     another GPU), a scale that is not finite, heads < 1, a width or a pitch out of range, both outs NULL, ycap too small:
+ *     nothing written.  FORA_E_NOMEM: nothing written, the ctx usable and the held result intact.  nq == 0: FORA_OK, nothing
+ *     is written.
  * PROPAGATE WITH VALUES (fora_hip_sparse_propagate_vals, fora_hip_sparse_propagate_t_vals): the products of PROPAGATE and
  * PROPAGATE, TRANSPOSED with the caller's values in place of the held words -- out = P(values) * H and out = P(values)^T * G,
  * P(values) the held pattern with values[e] at held entry e.  Each is the other's gradient with respect to the dense operand,
@@ -651,6 +692,20 @@ int fora_hip_sparse_softmax_bwd(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, 
                                 const void *y /*entries*/, int y_type, const void *grad /*entries*/, int g_type, double scale,
                                 float *out32 /*entries or NULL*/, double *out64 /*entries or NULL*/, uint64_t cap,
                                 fora_softmax_stats *stats /*or NULL*/);
+
+/* ---- attention over the held rows (the ATTENTION contract above): scores, softmax inside every row and the weighted product
+ * in one call, `heads` column slices at once, every bit the composition of the three calls above. */
+typedef struct { uint64_t entries, segments, max_row, nan_rows /* (row, head) pairs written as NaN */,
+                 short_rows, long_rows;                 /* non-empty rows per path (the option "attn_short") */
+                 int32_t q_on_device, k_on_device, v_on_device, pad_; double attn_ms; } fora_attn_stats;
+int fora_hip_sparse_attention(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                              const void *q, int q_type, int64_t ldq /* nq x heads*d */,
+                              const void *k, int k_type, int64_t ldk /* n x heads*d */,
+                              const void *v, int v_type, int64_t ldv /* n x heads*dv */,
+                              int d, int dv, int heads, double scale,
+                              float *out32 /*or NULL*/, double *out64 /*or NULL*/, int64_t ldo /* nq x heads*dv */,
+                              float *y32 /*or NULL*/, double *y64 /*or NULL*/, uint64_t ycap /* heads x entries */,
+                              fora_attn_stats *stats /*or NULL*/);
 
 /* copies the transposition of the held result; any of col_ptr / rows / fix / vals may be NULL; cap = entries each of rows /
  * fix / vals can take, col_ptr takes n + 1 */
