@@ -25,7 +25,7 @@ SYMBOLS = [
     "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
     "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
     "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
-    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention",
+    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention", "fora_hip_sparse_attention_bwd",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -152,6 +152,24 @@ class AttnStats(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("nan_rows", C.c_uint64),
                 ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("q_on_device", C.c_int32), ("k_on_device", C.c_int32),
                 ("v_on_device", C.c_int32), ("pad_", C.c_int32), ("attn_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class AttnGrads(C.Structure):
+    """fora_attn_grads: the outputs of fora_hip_sparse_attention_bwd, each gradient as f32 and / or f64 with one pitch"""
+    _fields_ = [("dq32", C.c_void_p), ("dq64", C.c_void_p), ("lddq", C.c_int64),
+                ("dk32", C.c_void_p), ("dk64", C.c_void_p), ("lddk", C.c_int64),
+                ("dv32", C.c_void_p), ("dv64", C.c_void_p), ("lddv", C.c_int64)]
+
+
+class AttnBwdStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("short_rows", C.c_uint64), ("long_rows", C.c_uint64),
+                ("columns", C.c_uint64), ("max_col", C.c_uint64), ("short_cols", C.c_uint64), ("long_cols", C.c_uint64),
+                ("built", C.c_int32), ("plan_cached", C.c_int32),
+                ("q_on_device", C.c_int32), ("k_on_device", C.c_int32), ("v_on_device", C.c_int32), ("g_on_device", C.c_int32),
+                ("y_on_device", C.c_int32), ("pad_", C.c_int32), ("transpose_ms", C.c_double), ("attn_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
@@ -701,6 +719,57 @@ class Engine:
         if y64 is not None:
             y64 = y64.reshape(heads, e)
         return out32, out64, y32, y64, st.as_dict()
+
+    def sparse_attention_bwd(self, row_ptr, Q, K, V, G, y, heads=1, scale=None, want_dq=True, want_dk=True, want_dv=True, want32=True, want64=False,
+                             q_bf16=False, k_bf16=False, v_bf16=False, g_bf16=False, dq32=None, dq64=None, dk32=None, dk64=None, dv32=None, dv64=None):
+        """The gradients of sparse_attention with respect to Q, K and V for all heads in ONE call
+        (fora_hip_sparse_attention_bwd, the ATTENTION, BACKWARD contract of include/fora_hip.h): bit for bit sparse_sddmm(G, V)
+        (float64), sparse_softmax_bwd(y, .), sparse_propagate(K, values=ds), sparse_propagate_t(Q, values=ds) and
+        sparse_propagate_t(G, values=y) on the column slices of the heads, nothing rounded to float32 in between.  Q, K, V:
+        as for sparse_attention; G: [nq, heads * dv], the gradient of its output (float32, or uint16 with g_bf16, or a torch
+        tensor); y: [heads, entries] float32 or float64, the probabilities the forward call returned.  All operands torch
+        tensors on the context's GPU, or all numpy arrays.  want_dq / want_dk / want_dv: a gradient that is not wanted is
+        not computed.  Returns (dq32, dq64, dk32, dk64, dv32, dv64, stats dict): dq [nq, heads * d], dk [n, heads * d], dv
+        [n, heads * dv], None where not wanted; dq32 .. dv64: caller-made outputs to fill instead, as for sparse_propagate
+        (the two of one gradient with the same row stride; a caller-made output makes its gradient wanted).  The first call on
+        a held result builds its transposition (stats["built"] == 1) and plans the columns; later calls reuse both
+        (stats["plan_cached"] == 1)."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nq, e = rp.size - 1, int(rp[-1])
+        heads = int(heads)
+        qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nq, name="Q")
+        kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, name="K")
+        vptr, vtype, wv, ldv, v_dev, _kv = self._prop_feat(V, v_bf16, name="V")
+        gptr, gtype, wg, ldg, g_dev, _kg = self._prop_feat(G, g_bf16, rows=nq, name="G")
+        if heads < 1 or wq % heads or wv % heads:
+            raise ValueError("heads must be at least 1 and divide the columns of Q and of V")
+        if wk != wq or wg != wv:
+            raise ValueError("Q and K, and V and G, must have the same number of columns")
+        d, dv = wq // heads, wv // heads
+        on_dev = q_dev or k_dev or v_dev or g_dev or self._is_torch(y)
+        if on_dev and not (q_dev and k_dev and v_dev and g_dev and self._is_torch(y)):
+            raise ValueError("Q, K, V, G and y: all torch tensors on the GPU, or all numpy arrays")
+        if tuple(y.shape) != (heads, e):
+            raise ValueError("y must be [heads, entries]")
+        yptr, ytype, _, _ky = self._entry_operand(y.reshape(heads * e), heads * e, "y")
+        gr = AttnGrads()
+        outs = []
+        for name, rows, w, want, o32, o64 in (("dq", nq, wq, want_dq, dq32, dq64), ("dk", self.n, wq, want_dk, dk32, dk64), ("dv", self.n, wv, want_dv, dv32, dv64)):
+            want = want or o32 is not None or o64 is not None
+            o32, o64, p32, p64, ld = self._prop_outputs(rows, w, on_dev, want and want32, want and want64, o32, o64) if want else (None, None, None, None, w)
+            setattr(gr, name + "32", p32.value if p32 is not None else None)
+            setattr(gr, name + "64", p64.value if p64 is not None else None)
+            setattr(gr, "ld" + name, ld)
+            outs += [o32, o64]
+        st = AttnBwdStats()
+        sc = float(d) ** -0.5 if scale is None else float(scale)
+        self._chk(self._lib.fora_hip_sparse_attention_bwd(self._ctx, _p(rp), C.c_int(nq), qptr, C.c_int(qtype), C.c_int64(ldq), kptr, C.c_int(ktype),
+                                                          C.c_int64(ldk), vptr, C.c_int(vtype), C.c_int64(ldv), gptr, C.c_int(gtype), C.c_int64(ldg),
+                                                          yptr, C.c_int(ytype), C.c_uint64(heads * e), C.c_int(d), C.c_int(dv), C.c_int(heads),
+                                                          C.c_double(sc), C.byref(gr), C.byref(st)))
+        return (*outs, st.as_dict())
 
     def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
         """The transposition of the held sparse result (fora_hip_sparse_transpose_fetch): (col_ptr, rows, vals), with want_fix

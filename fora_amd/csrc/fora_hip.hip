@@ -17,6 +17,7 @@
 #include "fora_sddmm.h"
 #include "fora_softmax.h"
 #include "fora_attn.h"
+#include "fora_attn_bwd.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -103,7 +104,7 @@ struct Tunables {
     int64_t topk_lds_cap = TOPK_LDS_MAX; // SPARSE RESULTS, TOP-K (fora_hip_query_sparse_topk_batch, fora_hip_seeds_sparse_topk_batch): candidates of a cut row that one workgroup stages in LDS at most (clamped to 0 .. TOPK_LDS_MAX, fora_topk_plan.h); a longer row is selected from global memory; 0: every cut row is.  Same bits for every value
     int64_t topk_cand = 0;       // ... entries of the candidate scratch (the rows of a batch are compacted into it chunk by chunk, consecutive rows, a row never split); 0: by free memory; always at least the longest row.  Same bits for every value
     int64_t softmax_short = SMAX_SHORT_MAX; // ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): a row of at most this many entries (clamped to 0 .. 256, fora_softmax.h) is one wave's, read once and written once; a longer one goes segment by segment through partial maxima and sums; 0: every row does.  Same bits for every value
-    int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value
+    int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value.  ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd) reads it for rows (k_attn_bwd_short) and columns (k_attn_cols, fora_attn_bwd_plan.h) alike
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -350,6 +351,9 @@ struct PropBufs {
     DevBuf<unsigned char> d_v;                           // ATTENTION: a host `v`, uploaded on every call (a host `q` goes to d_a, a host `k` to d_feat)
     DevBuf<double> d_attn_s, d_attn_y;                   // ATTENTION: [entries] the scores and the y of the longer rows, one head at a time
     DevBuf<float> d_y32; DevBuf<double> d_y64;           // ATTENTION: [heads][entries] y outputs on their way to host arrays
+    DevBuf<unsigned char> d_g;                           // ATTENTION, BACKWARD: a host `g`, uploaded on every call (q, k and v as in ATTENTION, a host `y` goes to d_vals)
+    DevBuf<double> d_attn_ds;                            // ATTENTION, BACKWARD: [heads][entries] ds, written by the row side and read by the column side (dy of the longer rows: d_attn_s)
+    DevBuf<float> d_dk32, d_dv32; DevBuf<double> d_dk64, d_dv64; // ATTENTION, BACKWARD: [n][heads * d] / [n][heads * dv] dk and dv on their way to host arrays (dq goes through d_out32 / d_out64)
     DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN (a host input goes to d_vals, a host grad to d_a)
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
@@ -365,6 +369,14 @@ struct PropTBufs {
     int nq = 0;                                          // rows of the row_ptr it was built from
     uint64_t columns = 0, max_col = 0;
     uint32_t short_cols = 0, lds_cols = 0, global_cols = 0;
+    // ATTENTION, BACKWARD: the split of the columns (fora_attn_bwd_plan.h), planned by the first call under a value of "attn_short"
+    // and a chunk size, its lists resident on the device; it ends with the transposition, being a member of it
+    struct ColPlan {
+        bool valid = false;
+        uint32_t short_cap = 0; uint64_t chunk_segs = 0, long_segs = 0; // the key, and the long columns' segments under that cap
+        AttnColPlan plan;                                               // (host: the chunks of plan.lng sequence the launches)
+        DevBuf<PropSeg> d_short, d_lsegs; DevBuf<PropRowRec> d_lrecs;
+    } cols;
 };
 
 // The loose words of the context, grouped by role.
@@ -3542,6 +3554,294 @@ int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, attention_impl(c, row_ptr, nq, c->sp.entries ? q : nullptr, q_type, ldq, c->sp.entries ? k : nullptr, k_type, ldk,
                                                   c->sp.entries ? v : nullptr, v_type, ldv, d, dv, heads, scale, out32, out64, ldo, y32, y64, st));
+}
+
+// ---- ATTENTION, BACKWARD (the contract of include/fora_hip.h): dq, dk and dv of all heads in one call -- the rows and the columns
+// of at most "attn_short" entries in the fused kernels (fora_attn_bwd.h), the longer ones through the chained calls' own kernels
+extern "C++" {
+namespace {
+template <bool GB, bool VB, bool KB, int V>
+void attn_bwd_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *g, int64_t ldg, const void *v, int64_t ldv, const void *k, int64_t ldk,
+                     int d, int dv, uint32_t lgv, double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const uint64_t units = nrow * (uint64_t)heads;
+    hipLaunchKernelGGL((k_attn_bwd_short<GB, VB, KB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), g, ldg, v, ldv, k, ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, entries, y, y_f64, ds, o32, ld32, o64, ld64);
+}
+template <bool GB, bool VB, typename... A>
+void attn_bwd_launch_k(bool k_bf16, uint32_t V, A... a) {
+    if (!k_bf16) switch (V) {
+        case 4: attn_bwd_launch<GB, VB, false, 4>(a...); break;
+        case 2: attn_bwd_launch<GB, VB, false, 2>(a...); break;
+        default: attn_bwd_launch<GB, VB, false, 1>(a...); break;
+    } else switch (V) {
+        case 8: attn_bwd_launch<GB, VB, true, 8>(a...); break;
+        case 4: attn_bwd_launch<GB, VB, true, 4>(a...); break;
+        default: attn_bwd_launch<GB, VB, true, 1>(a...); break;
+    }
+}
+template <bool BF16, int V>
+void attn_cols_launch(fora_ctx *c, const PropGeom &g, const PropSeg *cols, uint64_t ncol, int heads, const void *values, bool val64, uint64_t entries,
+                      const void *feat, int64_t ldf, int w, float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const uint64_t units = ncol * (uint64_t)heads, per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+    const dim3 grid((unsigned)((units + per_wg - 1) / per_wg), g.tiles);
+    const int32_t *rows = c->pt.d_rows.get();
+    const int64_t *pos = c->pt.d_pos.get();
+    if (val64) hipLaunchKernelGGL((k_attn_cols<BF16, V, true>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+    else hipLaunchKernelGGL((k_attn_cols<BF16, V, false>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+}
+// +0.0 to an n x width output: one clear where the rows lie back to back, a clear per row band otherwise (a pitch wider than
+// the output: what lies between the rows is the caller's)
+template <typename T> hipError_t attn_zero(fora_ctx *c, T *out, int64_t ld, uint64_t rows, uint64_t width) {
+    if (!out || !rows) return hipSuccess;
+    if ((uint64_t)ld == width) return hipMemsetAsync(out, 0, rows * width * sizeof(T), c->stream);
+    return hipMemset2DAsync(out, (size_t)ld * sizeof(T), 0, width * sizeof(T), rows, c->stream);
+}
+// one gradient of the column side: out[v][h * w + c] = the sum over column v's entries p of values[h * entries + pos[p]] *
+// feat[rows[p]][h * w + c].  The outputs zeroed (the empty columns), the short columns of all heads in one launch, the longer
+// ones head by head through PROPAGATE's kernels over the cached plan.
+int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, bool val64, const void *feat, bool bf16, int64_t ldf, int w,
+                  float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const PropTBufs &t = c->pt;
+    const AttnColPlan &cp = t.cols.plan;
+    const uint64_t n = (uint64_t)c->g.n;
+    const uint32_t elt = bf16 ? 2 : 4;
+    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
+    const uint32_t *const widths = bf16 ? widths_bf16 : widths_f32;
+    HIPCHK(c, attn_zero(c, o32, ld32, n, (uint64_t)heads * (uint64_t)w));
+    HIPCHK(c, attn_zero(c, o64, ld64, n, (uint64_t)heads * (uint64_t)w));
+    if (!cp.shrt.empty()) {
+        const PropGeom g = attn_cols_geom(attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, widths, 3), w);
+#define COLS_ARGS c, g, (const PropSeg *)t.cols.d_short.get(), (uint64_t)cp.shrt.size(), heads, values, val64, entries, feat, ldf, w, o32, ld32, o64, ld64
+        if (!bf16) switch (g.V) {
+            case 4: attn_cols_launch<false, 4>(COLS_ARGS); break;
+            case 2: attn_cols_launch<false, 2>(COLS_ARGS); break;
+            default: attn_cols_launch<false, 1>(COLS_ARGS); break;
+        } else switch (g.V) {
+            case 8: attn_cols_launch<true, 8>(COLS_ARGS); break;
+            case 4: attn_cols_launch<true, 4>(COLS_ARGS); break;
+            default: attn_cols_launch<true, 1>(COLS_ARGS); break;
+        }
+#undef COLS_ARGS
+    }
+    for (int h = 0; cp.long_cols && h < heads; h++) {
+        const void *fh = attn_cols(feat, (uint64_t)h * w, elt);
+        const void *vh = (const unsigned char *)values + (uint64_t)h * entries * (val64 ? 8 : 4);
+        const PropSide sd{t.h_col_ptr.data(), (int)n, (uint64_t)t.nq, t.d_rows.get(), nullptr, nullptr, false, vh, val64, t.d_pos.get()};
+        const PropGeom g = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, widths, 3);
+        prop_launch_chunks(c, cp.lng, t.cols.d_lsegs.get(), t.cols.d_lrecs.get(), sd, bf16, g, fh, ldf, w, nullptr, o32 ? o32 + (uint64_t)h * w : nullptr, ld32,
+                           o64 ? o64 + (uint64_t)h * w : nullptr, ld64, false);
+    }
+    return FORA_OK;
+}
+
+int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
+                       const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type,
+                       int d, int dv, int heads, double scale, const fora_attn_grads &gr, fora_attn_bwd_stats *st) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16, g_bf16 = g_type == FORA_PROP_BF16;
+    const bool y_f64 = y_type == FORA_PROP_F64;
+    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4, g_elt = g_bf16 ? 2 : 4, y_elt = y_f64 ? 8 : 4;
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q, k, dq and dk; of v, g and dv
+    const bool want_dq = gr.dq32 || gr.dq64, want_dk = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64;
+    const bool want_rows = want_dq || want_dk, want_cols = want_dk || want_dv; // dy and ds; the transposition
+    bool q_dev = false, k_dev = false, v_dev = false, g_dev = false, y_dev = false;
+    bool dq32_dev = false, dq64_dev = false, dk32_dev = false, dk64_dev = false, dv32_dev = false, dv64_dev = false;
+    if (q) if (int rc = sparse_dest(c, q, q_dev)) return rc;
+    if (k) if (int rc = sparse_dest(c, k, k_dev)) return rc;
+    if (v) if (int rc = sparse_dest(c, v, v_dev)) return rc;
+    if (g) if (int rc = sparse_dest(c, g, g_dev)) return rc;
+    if (y) if (int rc = sparse_dest(c, y, y_dev)) return rc;
+    if (gr.dq32) if (int rc = sparse_dest(c, gr.dq32, dq32_dev)) return rc;
+    if (gr.dq64) if (int rc = sparse_dest(c, gr.dq64, dq64_dev)) return rc;
+    if (gr.dk32) if (int rc = sparse_dest(c, gr.dk32, dk32_dev)) return rc;
+    if (gr.dk64) if (int rc = sparse_dest(c, gr.dk64, dk64_dev)) return rc;
+    if (gr.dv32) if (int rc = sparse_dest(c, gr.dv32, dv32_dev)) return rc;
+    if (gr.dv64) if (int rc = sparse_dest(c, gr.dv64, dv64_dev)) return rc;
+    // ---- the transposition and its places, as the first transposed product with values would build them
+    bool built_now = false;
+    if (want_cols) {
+        if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
+        if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
+    }
+    PropBufs &pb = c->pr;
+    PropTBufs &t = c->pt;
+    // ---- the plans.  Rows: as the forward call's, the longer rows' product d columns wide.  Columns: from the cache when "attn_short"
+    // and the resolved chunk size are the ones it was made under
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    uint64_t long_row_segs = 0, long_col_segs = 0;
+    for (int i = 0; want_rows && i < nq; i++) {
+        const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
+        if (len > cap) long_row_segs += (len + PROP_SEG - 1) / PROP_SEG;
+    }
+    if (want_cols) long_col_segs = t.cols.valid && t.cols.short_cap == cap ? t.cols.long_segs : attn_long_col_segs(t.h_col_ptr.data(), (int64_t)n, cap);
+    size_t fr = 0, tot = 0;
+    if ((long_row_segs || long_col_segs) && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const int wmax = std::max(d, dv);
+    const uint64_t per_rows = prop_chunk_segs(c->opt_.prop_segs, long_row_segs, (uint64_t)fr, d);
+    const uint64_t per_cols = prop_chunk_segs(c->opt_.prop_segs, long_col_segs, (uint64_t)fr, wmax);
+    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per_rows);
+    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    const bool lng_rows = want_rows && !plan.lrows.empty();
+    const bool plan_cached = want_cols && t.cols.valid && t.cols.short_cap == cap && t.cols.chunk_segs == per_cols;
+    if (want_cols && !plan_cached) {
+        PropTBufs::ColPlan nc; // moved into the transposition when complete
+        nc.short_cap = cap; nc.chunk_segs = per_cols; nc.long_segs = long_col_segs;
+        nc.plan = attn_col_plan(t.h_col_ptr.data(), (int64_t)n, cap, per_cols);
+        if (int rc = prop_ensure(c, nc.d_short, nc.plan.shrt.size(), "the column table")) return rc;
+        if (int rc = prop_ensure(c, nc.d_lsegs, nc.plan.lng.segs.size(), "the column table")) return rc;
+        if (int rc = prop_ensure(c, nc.d_lrecs, nc.plan.lng.recs.size(), "the column table")) return rc;
+        if (!nc.plan.shrt.empty()) HIPCHK(c, hipMemcpy(nc.d_short.get(), nc.plan.shrt.data(), nc.plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        if (!nc.plan.lng.segs.empty()) HIPCHK(c, hipMemcpy(nc.d_lsegs.get(), nc.plan.lng.segs.data(), nc.plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        if (!nc.plan.lng.recs.empty()) HIPCHK(c, hipMemcpy(nc.d_lrecs.get(), nc.plan.lng.recs.data(), nc.plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+        nc.valid = true;
+        t.cols = std::move(nc);
+    }
+    const bool lng_cols = want_cols && t.cols.plan.long_cols != 0;
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    const auto upload = [&](const void *&m, bool on_dev, DevBuf<unsigned char> &buf, size_t bytes, const char *what) -> int {
+        if (!entries || on_dev) return FORA_OK;
+        if (int rc = prop_ensure(c, buf, bytes, what)) return rc;
+        HIPCHK(c, hipMemcpy(buf.get(), m, bytes, hipMemcpyHostToDevice));
+        m = buf.get();
+        return FORA_OK;
+    };
+    if (want_dk) if (int rc = upload(q, q_dev, pb.d_a, (size_t)((((uint64_t)nq - 1) * (uint64_t)ldq + wq) * q_elt), "the upload of q")) return rc;
+    if (want_dq) if (int rc = upload(k, k_dev, pb.d_feat, (size_t)(((n - 1) * (uint64_t)ldk + wq) * k_elt), "the upload of k")) return rc;
+    if (want_rows) if (int rc = upload(v, v_dev, pb.d_v, (size_t)(((n - 1) * (uint64_t)ldv + wv) * v_elt), "the upload of v")) return rc;
+    if (int rc = upload(g, g_dev, pb.d_g, (size_t)((((uint64_t)nq - 1) * (uint64_t)ldg + wv) * g_elt), "the upload of g")) return rc;
+    if (int rc = upload(y, y_dev, pb.d_vals, (size_t)heads * (size_t)entries * y_elt, "the upload of y")) return rc;
+    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), nsegs = at_sm + sm.segs.size();
+    if (want_rows) if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
+    if (lng_rows) {
+        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the dy of the longer rows")) return rc;
+    }
+    if (lng_rows || lng_cols) {
+        const uint64_t part = std::max(lng_rows && want_dq ? per_rows * (uint64_t)d : 0, lng_cols ? per_cols * (uint64_t)wmax : 0);
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)part, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)wmax, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    if (want_dk || lng_rows) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)entries, "ds")) return rc;
+    if (gr.dq32 && !dq32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)nq * (size_t)wq, "a staged output")) return rc;
+    if (gr.dq64 && !dq64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)nq * (size_t)wq, "a staged output")) return rc;
+    if (gr.dk32 && !dk32_dev) if (int rc = prop_ensure(c, pb.d_dk32, (size_t)n * (size_t)wq, "a staged output")) return rc;
+    if (gr.dk64 && !dk64_dev) if (int rc = prop_ensure(c, pb.d_dk64, (size_t)n * (size_t)wq, "a staged output")) return rc;
+    if (gr.dv32 && !dv32_dev) if (int rc = prop_ensure(c, pb.d_dv32, (size_t)n * (size_t)wv, "a staged output")) return rc;
+    if (gr.dv64 && !dv64_dev) if (int rc = prop_ensure(c, pb.d_dv64, (size_t)n * (size_t)wv, "a staged output")) return rc;
+    PropSeg *const dsg = pb.d_segs.get();
+    if (want_rows && !plan.shrt.empty()) HIPCHK(c, hipMemcpy(dsg + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (lng_rows) {
+        HIPCHK(c, hipMemcpy(dsg + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dsg + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    }
+    float *const wdq32 = !gr.dq32 ? nullptr : dq32_dev ? gr.dq32 : pb.d_out32.get();
+    double *const wdq64 = !gr.dq64 ? nullptr : dq64_dev ? gr.dq64 : pb.d_out64.get();
+    float *const wdk32 = !gr.dk32 ? nullptr : dk32_dev ? gr.dk32 : pb.d_dk32.get();
+    double *const wdk64 = !gr.dk64 ? nullptr : dk64_dev ? gr.dk64 : pb.d_dk64.get();
+    float *const wdv32 = !gr.dv32 ? nullptr : dv32_dev ? gr.dv32 : pb.d_dv32.get();
+    double *const wdv64 = !gr.dv64 ? nullptr : dv64_dev ? gr.dv64 : pb.d_dv64.get();
+    const int64_t ldq32 = dq32_dev ? gr.lddq : (int64_t)wq, ldq64 = dq64_dev ? gr.lddq : (int64_t)wq;
+    const int64_t ldk32 = dk32_dev ? gr.lddk : (int64_t)wq, ldk64 = dk64_dev ? gr.lddk : (int64_t)wq;
+    const int64_t ldv32 = dv32_dev ? gr.lddv : (int64_t)wv, ldv64 = dv64_dev ? gr.lddv : (int64_t)wv;
+    double *const ds = want_dk || lng_rows ? pb.d_attn_ds.get() : nullptr;
+    uint32_t lgv = 0;
+    while (lgv < 6 && (1u << lgv) < (uint32_t)dv) lgv++; // the smallest group that holds the dv columns of dy, at most a wave
+    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
+    const uint32_t *const widths_k = k_bf16 ? widths_bf16 : widths_f32;
+    c->tm.attn_ms = 0;
+    {
+        EvSpan ev(c, EV_ATTN);
+        if (want_rows && !plan.shrt.empty()) { // dy, ds and dq of the short rows, all heads
+            const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)k, ldk, d, heads, k_elt, widths_k, 3);
+#define BWD_ARGS k_bf16, V, c, (const PropSeg *)(dsg + at_short), (uint64_t)plan.shrt.size(), heads, g, ldg, v, ldv, k, ldk, d, dv, lgv, scale, entries, y, y_f64, want_dk ? ds : (double *)nullptr, wdq32, ldq32, wdq64, ldq64
+            if (!g_bf16 && !v_bf16) attn_bwd_launch_k<false, false>(BWD_ARGS);
+            else if (!g_bf16) attn_bwd_launch_k<false, true>(BWD_ARGS);
+            else if (!v_bf16) attn_bwd_launch_k<true, false>(BWD_ARGS);
+            else attn_bwd_launch_k<true, true>(BWD_ARGS);
+#undef BWD_ARGS
+        }
+        for (int h = 0; lng_rows && h < heads; h++) { // the longer rows, one head at a time: dy, ds into the head's slice, dq
+            const void *gh = attn_cols(g, (uint64_t)h * dv, g_elt), *vh = attn_cols(v, (uint64_t)h * dv, v_elt), *kh = attn_cols(k, (uint64_t)h * d, k_elt);
+            const void *yh = (const unsigned char *)y + (uint64_t)h * entries * y_elt;
+            double *const dy64 = pb.d_attn_s.get(), *const dsh = ds + (uint64_t)h * entries;
+            const PropSeg *segs = dsg + at_lsegs;
+            const uint64_t nseg = plan.lng.segs.size();
+            if (!g_bf16 && !v_bf16) sddmm_launch<false, false>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            else if (!g_bf16) sddmm_launch<false, true>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            else if (!v_bf16) sddmm_launch<true, false>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            else sddmm_launch<true, true>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            const SoftmaxWork w{dsg + at_sm, dsg + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, nullptr};
+            if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, scale, nullptr, dsh);
+            else softmax_bwd_launch<float, double>(c, w, yh, dy64, scale, nullptr, dsh);
+            if (want_dq) {
+                const PropSide sd{row_ptr, nq, n, c->sp.d_ids.get(), nullptr, nullptr, false, dsh, true, nullptr};
+                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, 3);
+                prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, k_bf16, gm, kh, ldk, d, nullptr, wdq32 ? wdq32 + (uint64_t)h * d : nullptr, ldq32,
+                                   wdq64 ? wdq64 + (uint64_t)h * d : nullptr, ldq64, false);
+            }
+        }
+        if (want_dk) if (int rc = attn_bwd_cols(c, heads, entries, ds, true, q, q_bf16, ldq, d, wdk32, ldk32, wdk64, ldk64)) return rc;
+        if (want_dv) if (int rc = attn_bwd_cols(c, heads, entries, y, y_f64, g, g_bf16, ldg, dv, wdv32, ldv32, wdv64, ldv64)) return rc;
+    }
+    if (gr.dq32 && !dq32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dq32, (size_t)gr.lddq * 4, wdq32, (size_t)wq * 4, (size_t)wq * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (gr.dq64 && !dq64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dq64, (size_t)gr.lddq * 8, wdq64, (size_t)wq * 8, (size_t)wq * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (gr.dk32 && !dk32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dk32, (size_t)gr.lddk * 4, wdk32, (size_t)wq * 4, (size_t)wq * 4, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (gr.dk64 && !dk64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dk64, (size_t)gr.lddk * 8, wdk64, (size_t)wq * 8, (size_t)wq * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (gr.dv32 && !dv32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dv32, (size_t)gr.lddv * 4, wdv32, (size_t)wv * 4, (size_t)wv * 4, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (gr.dv64 && !dv64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dv64, (size_t)gr.lddv * 8, wdv64, (size_t)wv * 8, (size_t)wv * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse attention_bwd: ") + hipGetErrorString(err));
+    ev_collect(c);
+    if (st) {
+        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
+        st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
+        if (want_cols) {
+            const AttnColPlan &cp = t.cols.plan;
+            st->columns = cp.columns; st->max_col = cp.max_col; st->short_cols = cp.short_cols; st->long_cols = cp.long_cols;
+        }
+        st->built = built_now ? 1 : 0; st->plan_cached = plan_cached ? 1 : 0;
+        st->q_on_device = q_dev ? 1 : 0; st->k_on_device = k_dev ? 1 : 0; st->v_on_device = v_dev ? 1 : 0; st->g_on_device = g_dev ? 1 : 0;
+        st->y_on_device = y_dev ? 1 : 0;
+        st->transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0; st->attn_ms = c->tm.attn_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+} // extern "C++"
+
+int fora_hip_sparse_attention_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
+                                  const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap,
+                                  int d, int dv, int heads, double scale, const fora_attn_grads *grads, fora_attn_bwd_stats *st) {
+    if (!c) return FORA_E_ARG;
+    const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
+    const char *who = "sparse attention_bwd: ";
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, std::string(who) + "negative nq or null row_ptr");
+    if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type) || !type_ok(g_type)) return fail(c, FORA_E_ARG, std::string(who) + "unknown q_type, k_type, v_type or g_type");
+    if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, std::string(who) + "y_type is neither f32 nor f64");
+    if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, std::string(who) + "d or dv outside 1 .. 65536");
+    if (heads < 1 || (int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, std::string(who) + "heads < 1, or heads * d or heads * dv over 65536");
+    if (ldq < (int64_t)heads * d || ldk < (int64_t)heads * d) return fail(c, FORA_E_ARG, std::string(who) + "ldq or ldk smaller than heads * d");
+    if (ldv < (int64_t)heads * dv || ldg < (int64_t)heads * dv) return fail(c, FORA_E_ARG, std::string(who) + "ldv or ldg smaller than heads * dv");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, std::string(who) + "scale is not finite");
+    if (!grads) return fail(c, FORA_E_ARG, std::string(who) + "no output");
+    const bool want_dq = grads->dq32 || grads->dq64, want_dk = grads->dk32 || grads->dk64, want_dv = grads->dv32 || grads->dv64;
+    if (!want_dq && !want_dk && !want_dv) return fail(c, FORA_E_ARG, std::string(who) + "no output");
+    if ((want_dq && grads->lddq < (int64_t)heads * d) || (want_dk && grads->lddk < (int64_t)heads * d) || (want_dv && grads->lddv < (int64_t)heads * dv))
+        return fail(c, FORA_E_ARG, std::string(who) + "lddq or lddk smaller than heads * d, or lddv smaller than heads * dv");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, std::string(who) + "row_ptr is not the held result's");
+    if (ycap < (uint64_t)heads * c->sp.entries) return fail(c, FORA_E_ARG, std::string(who) + "ycap is smaller than heads * the held entries");
+    if (c->sp.entries && (!q || !k || !v || !g || !y)) return fail(c, FORA_E_ARG, std::string(who) + "null q, k, v, g or y");
+    if (st) memset(st, 0, sizeof(*st));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool e = c->sp.entries != 0;
+    return drop_pairs_unless_ok(c, attention_bwd_impl(c, row_ptr, nq, e ? q : nullptr, q_type, ldq, e ? k : nullptr, k_type, ldk, e ? v : nullptr, v_type, ldv,
+                                                      e ? g : nullptr, g_type, ldg, e ? y : nullptr, y_type, d, dv, heads, scale, *grads, st));
 }
 
 int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *col_ptr, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap) {

@@ -220,20 +220,44 @@ class _PprAttentionFused(torch.autograd.Function):
         return cast(dQ, Q), cast(dK, K), cast(dV, V), None, None, None, None
 
 
-def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1):
+class _PprAttentionFusedBwd(_PprAttentionFused):
+    """the same forward pass; the backward pass is ONE call for all heads (Engine.sparse_attention_bwd) on the saved y32, with
+    nothing rounded to float32 between its steps"""
+
+    @staticmethod
+    def backward(ctx, G):
+        Q, K, V, y32 = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "ppr_attention_fused")
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None, None, None
+        dQ, _, dK, _, dV, _, _ = engine.sparse_attention_bwd(ctx.row_ptr, Q.detach(), K.detach(), V.detach(), _dense_operand(G), y32, heads=ctx.heads,
+                                                             scale=ctx.scale, want_dq=need_q, want_dk=need_k, want_dv=need_v, want32=True, want64=False)
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dQ, Q), cast(dK, K), cast(dV, V), None, None, None, None
+
+
+def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1, backward="calls"):
     """ppr_attention with all three steps in ONE library call (Engine.sparse_attention, the ATTENTION contract): the rows of at
     most 256 entries are scored, normalised and multiplied by one wave each without anything written in between, and nothing
     is rounded to float32 between the steps.  Q: [nq, heads * d], K: [n, heads * d], V: [n, heads * dv], float32 or bfloat16
     on the engine's GPU; head j attends with the columns [j * d, (j + 1) * d) of Q and K and writes the columns
     [j * dv, (j + 1) * dv) of the result, [nq, heads * dv] float32.  scale defaults to d ** -0.5 and is a number, not a
     differentiable operand.  Differentiable in Q, K and V: the backward pass runs head by head with the calls ppr_attention
-    (softmax="engine") uses, on the float32 probabilities the forward call saved.  The rows must still be held when it runs."""
+    (softmax="engine") uses, on the float32 probabilities the forward call saved.  The rows must still be held when it runs.
+    backward: "calls" (the default) is that head-by-head pass; "fused" makes the backward pass one library call for all heads
+    (Engine.sparse_attention_bwd, the ATTENTION, BACKWARD contract) on the same saved probabilities, computing only the
+    gradients autograd asks for and rounding nothing to float32 between its steps."""
     heads = int(heads)
     if heads < 1 or Q.shape[1] % heads or V.shape[1] % heads:
         raise ValueError("ppr_attention_fused: heads must be at least 1 and divide the columns of Q and of V")
+    if backward not in ("calls", "fused"):
+        raise ValueError('ppr_attention_fused: backward is "calls" or "fused"')
     if scale is None:
         scale = float(Q.shape[1] // heads) ** -0.5
-    return _PprAttentionFused.apply(Q, K, V, engine, row_ptr, float(scale), heads)
+    fn = _PprAttentionFused if backward == "calls" else _PprAttentionFusedBwd
+    return fn.apply(Q, K, V, engine, row_ptr, float(scale), heads)
 
 
 def ppr_attention(engine, row_ptr, Q, K, V, scale=None, softmax="torch"):

@@ -423,6 +423,52 @@
  *     another GPU), a scale that is not finite, heads < 1, a width or a pitch out of range, both outs NULL, ycap too small:
  *     nothing written.  FORA_E_NOMEM: nothing written, the ctx usable and the held result intact.  nq == 0: FORA_OK, nothing
  *     is written.
+ * ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd): the gradients of ATTENTION with respect to q, k and v, for all heads in
+ * one call.  Every output bit is defined as a composition of contracts above (tests/attention_bwd_ref.py is the twin).
+ *   - q, k, v, their types and pitches, d, dv, heads and scale are the forward call's.  g = dL/dout is nq x heads * dv,
+ *     FORA_PROP_F32 or FORA_PROP_BF16, pitch ldg >= heads * dv.  y is [heads][entries], FORA_PROP_F32 or FORA_PROP_F64: what
+ *     the forward call wrote to y32 or y64.  ycap = the elements y holds; ycap < heads * entries is FORA_E_ARG.
+ *   - per head j, on the column slices [j*d, (j+1)*d) of q and k and [j*dv, (j+1)*dv) of v and g:
+ *       dy_e is exactly SCORES (SDDMM) of (g slice, v slice), in f64;
+ *       ds_e is exactly ROW SOFTMAX backward of (y_j, dy) with `scale`: the f64 dy as grad, y in the caller's type, in f64;
+ *       dq[i][j*d + c] is exactly PROPAGATE WITH VALUES of the k slice with the f64 ds as the values;
+ *       dk[v][j*d + c] is exactly PROPAGATE WITH VALUES, transposed, of the q slice with the f64 ds as the values;
+ *       dv[v][j*dv + c] is exactly PROPAGATE WITH VALUES, transposed, of the g slice with y_j, in the caller's type, as the
+ *         values.
+ *     Nothing is rounded to f32 between the steps: in every f64 output the call equals fora_hip_sparse_sddmm (out64),
+ *     fora_hip_sparse_softmax_bwd (F64 grad, out64), fora_hip_sparse_propagate_vals (F64 values) and
+ *     fora_hip_sparse_propagate_t_vals (F64 values) chained on the column slices, bit for bit.  The f32 outputs are (float) of
+ *     the f64 outputs, rounded to nearest even.
+ *   - non-finite values follow IEEE as in ROW SOFTMAX backward: nothing is checked and no payload is defined.  Where a NaN
+ *     is involved the chained calls and the twin agree in NaN-ness only.
+ *   - outputs (fora_attn_grads): dq is nq x heads * d, dk is n x heads * d, dv is n x heads * dv; each as f32 and / or f64
+ *     with one pitch per gradient (lddq, lddk >= heads * d; lddv >= heads * dv; the pitch of an absent gradient is not
+ *     read).  A gradient with both pointers NULL is absent and costs nothing: with dq and dk both absent dy and ds are never
+ *     computed.  All three absent is FORA_E_ARG.  An empty row writes +0.0 to its dq; a column with no entry writes +0.0 to
+ *     its dk and dv -- all n columns when the held result has no entries and nq > 0.
+ *   - q, k, v, g, y and the six outputs may each be pageable host memory or device memory on the ctx's GPU (memory of another
+ *     GPU is FORA_E_ARG).  A device operand needs only element alignment: any base, any pitch, a column slice of a wider
+ *     tensor.  Host operands are uploaded on every call and host outputs are staged in device memory, as in ATTENTION.
+ *   - no bit depends on the batch size, on "prop_segs", on "softmax_short", on "propt_lds_cap", on host versus device
+ *     pointers, on the launch shape, on whether the column plan came from the cache, or on the option "attn_short", which
+ *     bounds rows and columns alike: a row of at most that many entries is one wave's per head in k_attn_bwd_short (dy, ds
+ *     and dq without anything but ds leaving the CU), a non-empty column of at most that many entries is one lane group's
+ *     per head in k_attn_cols; the longer rows and the longer columns go through the kernels of the chained calls inside
+ *     the same call, one head at a time; 0 sends everything there.
+ *   - the transposition of the held result and its places (PROPAGATE WITH VALUES) are built when dk or dv is wanted and they
+ *     are missing -- exactly what the first fora_hip_sparse_propagate_t_vals would do; stats.built = 1 then.  The split of
+ *     the columns is planned once per transposition, "attn_short" and chunk size, and kept on the device with it: a second
+ *     call plans and uploads nothing on the column side and reports plan_cached = 1.
+ *   - stats: entries, segments, max_row, short_rows and long_rows as in ATTENTION; columns = the non-empty columns, max_col,
+ *     short_cols and long_cols = the non-empty columns per path (0 when neither dk nor dv is wanted); built, plan_cached; the
+ *     five *_on_device flags; transpose_ms = the device time of building (0 unless built); attn_ms = the device time of the
+ *     call's other launches.
+ *   - the held result, "sparse_generation", a held sweep profile, the walk index, the options, the FORA parameters and
+ *     fora_timing are left untouched.  The ctx's stream is synchronised before it returns.
+ *   - errors: NULL ctx is answered without touching the GPU.  The FORA_E_ARG cases of ATTENTION, and: a NULL g or y with
+ *     entries to read, a y_type other than f32 or f64, a g_type other than f32 or bf16, ycap below heads * entries, a pitch
+ *     below its width, all three gradients absent: nothing written.  FORA_E_NOMEM: nothing written, the ctx usable and the
+ *     held result intact.  nq == 0: FORA_OK, nothing is written.
  * PROPAGATE WITH VALUES (fora_hip_sparse_propagate_vals, fora_hip_sparse_propagate_t_vals): the products of PROPAGATE and
  * PROPAGATE, TRANSPOSED with the caller's values in place of the held words -- out = P(values) * H and out = P(values)^T * G,
  * P(values) the held pattern with values[e] at held entry e.  Each is the other's gradient with respect to the dense operand,
@@ -706,6 +752,25 @@ int fora_hip_sparse_attention(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, in
                               float *out32 /*or NULL*/, double *out64 /*or NULL*/, int64_t ldo /* nq x heads*dv */,
                               float *y32 /*or NULL*/, double *y64 /*or NULL*/, uint64_t ycap /* heads x entries */,
                               fora_attn_stats *stats /*or NULL*/);
+
+/* ---- the gradients of that call (the ATTENTION, BACKWARD contract above): dq, dk and dv for all heads in one call, every bit
+ * the composition of the calls above.  A gradient with both pointers NULL is not computed. */
+typedef struct { float *dq32; double *dq64; int64_t lddq; /* nq x heads*d */
+                 float *dk32; double *dk64; int64_t lddk; /* n x heads*d */
+                 float *dv32; double *dv64; int64_t lddv; /* n x heads*dv */ } fora_attn_grads;
+typedef struct { uint64_t entries, segments, max_row, short_rows, long_rows; /* the rows, as in fora_attn_stats */
+                 uint64_t columns, max_col, short_cols, long_cols;           /* the non-empty columns, and per path */
+                 int32_t built, plan_cached;                                 /* the transposition was built / the column plan was there */
+                 int32_t q_on_device, k_on_device, v_on_device, g_on_device, y_on_device, pad_;
+                 double transpose_ms, attn_ms; } fora_attn_bwd_stats;
+int fora_hip_sparse_attention_bwd(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
+                                  const void *q, int q_type, int64_t ldq /* nq x heads*d */,
+                                  const void *k, int k_type, int64_t ldk /* n x heads*d */,
+                                  const void *v, int v_type, int64_t ldv /* n x heads*dv */,
+                                  const void *g, int g_type, int64_t ldg /* nq x heads*dv */,
+                                  const void *y, int y_type, uint64_t ycap /* heads x entries */,
+                                  int d, int dv, int heads, double scale,
+                                  const fora_attn_grads *grads, fora_attn_bwd_stats *stats /*or NULL*/);
 
 /* copies the transposition of the held result; any of col_ptr / rows / fix / vals may be NULL; cap = entries each of rows /
  * fix / vals can take, col_ptr takes n + 1 */
