@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -341,20 +342,18 @@ struct SweepResult : HeldRows {
 // PROPAGATE (fora_hip_sparse_propagate): buffers of the call in progress, kept between calls and grown when a call needs more
 // (free_prop: set_graph, destroy).  Apart from the sparse result they read.
 struct PropBufs {
-    DevBuf<unsigned char> d_feat;                        // a host `feat`, uploaded on every call
+    // uploads of host operands, made on every call (HeldIn::stage names the buffer an operand goes to): the matrix with n rows
+    // (feat, b, k); the one with nq rows (a, q; ROW SOFTMAX's grad); the per-entry vector (values, scores, y); v; g
+    DevBuf<unsigned char> d_feat, d_a, d_vals, d_v, d_g;
+    // outputs on their way to host arrays (HeldOut::reserve): the nq-row or per-entry output of every call (dq too); y; dk; dv
+    DevBuf<float> d_out32, d_y32, d_dk32, d_dv32; DevBuf<double> d_out64, d_y64, d_dk64, d_dv64;
+    // scratch of the launches
     DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;   // the call's plan (fora_prop_plan.h)
     DevBuf<double> d_part; DevBuf<uint64_t> d_segsum;    // partial sums [prop_segs][d] and word sums [prop_segs] of the chunk in progress
     DevBuf<double> d_carry; DevBuf<uint64_t> d_scarry;   // [2][d] / [2]: the row a chunk cut, one buffer read and one written per chunk
-    DevBuf<float> d_out32; DevBuf<double> d_out64;       // [nq][d]: outputs on their way to host arrays (SCORES: [entries])
-    DevBuf<unsigned char> d_vals;                        // PROPAGATE WITH VALUES: a host `values`, uploaded on every call
-    DevBuf<unsigned char> d_a;                           // SCORES: a host `a`, uploaded on every call (a host `b` goes to d_feat)
-    DevBuf<unsigned char> d_v;                           // ATTENTION: a host `v`, uploaded on every call (a host `q` goes to d_a, a host `k` to d_feat)
-    DevBuf<double> d_attn_s, d_attn_y;                   // ATTENTION: [entries] the scores and the y of the longer rows, one head at a time
-    DevBuf<float> d_y32; DevBuf<double> d_y64;           // ATTENTION: [heads][entries] y outputs on their way to host arrays
-    DevBuf<unsigned char> d_g;                           // ATTENTION, BACKWARD: a host `g`, uploaded on every call (q, k and v as in ATTENTION, a host `y` goes to d_vals)
-    DevBuf<double> d_attn_ds;                            // ATTENTION, BACKWARD: [heads][entries] ds, written by the row side and read by the column side (dy of the longer rows: d_attn_s)
-    DevBuf<float> d_dk32, d_dv32; DevBuf<double> d_dk64, d_dv64; // ATTENTION, BACKWARD: [n][heads * d] / [n][heads * dv] dk and dv on their way to host arrays (dq goes through d_out32 / d_out64)
-    DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN (a host input goes to d_vals, a host grad to d_a)
+    DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN
+    DevBuf<double> d_attn_s, d_attn_y;                   // ATTENTION: [entries] the scores (BACKWARD: dy) and the y of the longer rows, one head at a time
+    DevBuf<double> d_attn_ds;                            // ATTENTION, BACKWARD: [heads][entries] ds, written by the row side and read by the column side
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
 // result, built by the first of the two calls after a result becomes held and kept with it -- it ends wherever the held
@@ -2377,6 +2376,793 @@ template <class F> int with_bucket_retry(fora_ctx *c, F call) {
 // the words of the context that mirror an option
 static void apply_options(fora_ctx *c) { c->tm.profiling = c->opt_.profile != 0; c->grid_blocks = c->opt_.grid > 0 ? (int)c->opt_.grid : 2048; }
 
+// =============================================================================== the host drivers of the calls on the held rows
+namespace {
+// is p device memory of the ctx's GPU?  (host memory the runtime has never seen: no attributes, or "unregistered")
+int sparse_dest(fora_ctx *c, const void *p, bool &on_device) {
+    hipPointerAttribute_t a{};
+    on_device = false;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return FORA_OK; }
+    if (a.type != hipMemoryTypeDevice) return FORA_OK;
+    if (a.device != c->device) return fail(c, FORA_E_ARG, "destination is memory of another GPU");
+    on_device = true;
+    return FORA_OK;
+}
+
+// e held words (device) as doubles into vals, on the ctx's stream: converted in place for device memory, SP_STAGE at a time
+// through the sparse result's stage buffer for a host array
+int fetch_vals(fora_ctx *c, const uint64_t *words, uint64_t e, double *vals, bool vals_on_device) {
+    constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
+    const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
+    if (vals_on_device) {
+        hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, words, e, vals);
+        return FORA_OK;
+    }
+    HIPCHK(c, c->sp.d_stage.ensure(SP_STAGE));
+    for (uint64_t at = 0; at < e; at += SP_STAGE) {
+        const uint64_t len = std::min(SP_STAGE, e - at);
+        hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, words + at, len, c->sp.d_stage.get());
+        HIPCHK(c, hipMemcpyAsync(vals + at, c->sp.d_stage.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return FORA_OK;
+}
+
+// ---- the frame of a call on the held rows: its operands, its outputs, the choice of a kernel, its begin and end
+// a grown-or-kept buffer of the call; no room is FORA_E_NOMEM and leaves no sticky HIP error behind
+template <typename T> int prop_ensure(fora_ctx *c, DevBuf<T> &b, size_t cnt, const char *what) {
+    if (b.ensure(std::max<size_t>(cnt, 1)) == hipSuccess) return FORA_OK;
+    (void)hipGetLastError();
+    return fail(c, FORA_E_NOMEM, std::string("no device memory for ") + what);
+}
+// An operand of the caller's: a strided matrix or a per-entry vector, in host memory or on the ctx's GPU.  resolve() before
+// anything is built, stage() among the call's buffers; ptr() is then what the launches read.  A null operand stays null.
+struct HeldIn {
+    const void *p = nullptr; uint64_t bytes = 0; bool dev = false;
+    static HeldIn matrix(const void *p, uint64_t rows, int64_t ld, uint64_t width, uint32_t elt) { return HeldIn{p, prop_matrix_bytes(rows, (uint64_t)ld, width, elt)}; }
+    static HeldIn vector(const void *p, uint64_t count, uint32_t elt) { return HeldIn{p, prop_vector_bytes(count, elt)}; }
+    int resolve(fora_ctx *c) { return p ? sparse_dest(c, p, dev) : FORA_OK; }
+    // a host operand into buf (`what` names it when there is no room); nothing to do on the device, or without entries
+    int stage(fora_ctx *c, DevBuf<unsigned char> &buf, const char *what) {
+        if (!p || dev || !c->sp.entries) return FORA_OK;
+        if (int rc = prop_ensure(c, buf, (size_t)bytes, what)) return rc;
+        HIPCHK(c, hipMemcpy(buf.get(), p, (size_t)bytes, hipMemcpyHostToDevice));
+        p = buf.get();
+        return FORA_OK;
+    }
+    const void *ptr() const { return p; }
+    int32_t on_device() const { return dev ? 1 : 0; } // (the caller's pointer: the stats)
+};
+// An output of the caller's: rows x width of T at pitch ld; a per-entry vector is vector(): one row without a pitch.  resolve(),
+// then reserve() among the call's buffers; the launches write ptr() at pitch ld() -- the caller's own memory and pitch on the
+// device, a dense staging buffer for a host array, which fetch() copies out after the last launch (with a pitch: row by row,
+// what lies between the rows stays the caller's).  A null output stays null throughout.
+template <typename T> struct HeldOut {
+    T *out = nullptr; int64_t pitch = 0; uint64_t rows = 0, width = 0; bool dev = false; T *work = nullptr;
+    static HeldOut vector(T *out, uint64_t count) { return HeldOut{out, 0, 1, count}; }
+    int resolve(fora_ctx *c) { work = out; return out ? sparse_dest(c, out, dev) : FORA_OK; }
+    int reserve(fora_ctx *c, DevBuf<T> &staging) {
+        if (!out || dev) return FORA_OK;
+        if (int rc = prop_ensure(c, staging, (size_t)(rows * width), "a staged output")) return rc;
+        work = staging.get();
+        return FORA_OK;
+    }
+    T *ptr() const { return work; }
+    T *ptr(uint64_t col) const { return work ? work + col : nullptr; } // (a head's columns)
+    int64_t ld() const { return dev ? pitch : (int64_t)width; }
+    int fetch(fora_ctx *c) const {
+        if (!out || dev || !rows || !width) return FORA_OK;
+        if (!pitch) HIPCHK(c, hipMemcpyAsync(out, work, (size_t)width * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        else HIPCHK(c, hipMemcpy2DAsync(out, (size_t)pitch * sizeof(T), work, (size_t)width * sizeof(T), (size_t)width * sizeof(T), (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+        return FORA_OK;
+    }
+};
+// f(std::bool_constant<bf16>, std::integral_constant<int, V>): the instantiation for an element type and the vector width that
+// prop_geom / attn_vec_width took from prop_widths(bf16)
+template <typename F> void with_vec(bool bf16, uint32_t V, F &&f) {
+    using std::integral_constant;
+    if (!bf16) switch (V) {
+        case 4: f(std::false_type{}, integral_constant<int, 4>{}); break;
+        case 2: f(std::false_type{}, integral_constant<int, 2>{}); break;
+        default: f(std::false_type{}, integral_constant<int, 1>{}); break;
+    } else switch (V) {
+        case 8: f(std::true_type{}, integral_constant<int, 8>{}); break;
+        case 4: f(std::true_type{}, integral_constant<int, 4>{}); break;
+        default: f(std::true_type{}, integral_constant<int, 1>{}); break;
+    }
+}
+// f(std::bool_constant<a>, std::bool_constant<b>)
+template <typename F> void with_bools(bool a, bool b, F &&f) {
+    if (a) { if (b) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (b) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+}
+// the checks every entry point shares, under the call's name `who`; each keeps the checks that are its own
+int held_call_begin(fora_ctx *c, const char *who, const int64_t *row_ptr, int nq) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
+    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, std::string(who) + ": negative nq or null row_ptr");
+    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, std::string(who) + ": row_ptr is not the held result's");
+    return FORA_OK;
+}
+// the end of a call: the stream idle, a failed launch or copy reported under the call's name; collect: the event times read
+int held_call_end(fora_ctx *c, const char *who, bool collect = true) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
+    if (collect) ev_collect(c);
+    return FORA_OK;
+}
+
+// ---- PROPAGATE and PROPAGATE, TRANSPOSED
+// One side of the product: which output rows are summed over which entries.  Forward: the held rows (ids: nodes, feat: the n
+// feature rows).  Transposed: the columns of the transposition (ids: the rows the entries came from, feat: the nq gradient rows).
+struct PropSide {
+    const int64_t *row_ptr; int rows;        // (host) the output rows' entries
+    const int32_t *ids; const uint64_t *fix; // (device) the entries
+    const uint64_t *rsum;                    // transposed and normalised: S by id, every weight divided by it in the gather; else null
+    bool divide;                             // forward and normalised: a row's sum divided by its word sum in the combine
+    const void *values = nullptr; bool val64 = false; // PROPAGATE WITH VALUES: the weights (device; null: the words), f64 or f32
+    const int64_t *pos = nullptr;            // (device) with values, transposed: the held place of every entry; forward: null
+};
+struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
+
+template <bool BF16, int V>
+void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
+    const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+    const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
+    if (sd.values) with_bools(sd.pos != nullptr, sd.val64, [&](auto POS, auto V64) {
+        hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, POS.value, V64.value>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+    });
+    else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
+    else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
+}
+// the two kernels chunk by chunk over a plan whose segments and records lie at d_segs and d_recs: the partial sums of one chunk
+// live at a time in the ctx's buffers, which the caller has ensured.  timed: an event pair per launch (PROPAGATE's own stats);
+// a caller with a span of its own around the whole passes false.
+void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, bool bf16, const PropGeom &g,
+                        const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed) {
+    PropBufs &b = c->pr;
+    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
+        const PropChunk &ch = plan.chunks[ci];
+        if (ch.nseg) {
+            EvSpan ev(c);
+            if (timed) ev.begin(EV_PROP_GATHER);
+            const PropSeg *segs = d_segs + ch.seg0;
+            with_vec(bf16, g.V, [&](auto B, auto V) { prop_launch_gather<B.value, V.value>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); });
+        }
+        if (ch.nrec) {
+            EvSpan ev(c);
+            if (timed) ev.begin(EV_PROP_COMBINE);
+            const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
+            const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
+            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, d_recs + ch.rec0, ch.nrec,
+                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
+                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, ld32, w64, ld64);
+        }
+    }
+}
+// the product of one side with feat: plan, buffers, the two kernels chunk by chunk, the staged outputs; the stream is idle and
+// the event times are collected when it returns FORA_OK
+// every operand and output of a call asked where it lives, before anything is built: memory of another GPU is refused first
+template <typename... O> int held_resolve(fora_ctx *c, O &...o) {
+    int rc = FORA_OK;
+    (void)(((rc = o.resolve(c)) != FORA_OK) || ...);
+    return rc;
+}
+template <typename... O> int held_fetch(fora_ctx *c, const O &...o) { // the staged outputs copied out, after the last launch
+    int rc = FORA_OK;
+    (void)(((rc = o.fetch(c)) != FORA_OK) || ...);
+    return rc;
+}
+// the product of one side with feat (resolved, as values and the outputs are): plan, buffers, the two kernels chunk by chunk, the
+// staged outputs; the stream is idle and the event times are collected when it returns FORA_OK
+int prop_run(fora_ctx *c, const PropSide &side, HeldIn feat, HeldIn values, bool bf16, int d, int64_t ldf, HeldOut<float> o32, HeldOut<double> o64, PropRunStats &rs) {
+    PropSide sd = side;
+    const int nq = sd.rows;
+    PropBufs &b = c->pr;
+    // ---- the plan: chunks of prop_segs segments; 0: a quarter of the free memory in partial sums at most
+    const uint64_t total = prop_segments(sd.row_ptr, nq);
+    size_t fr = 0, tot = 0;
+    if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, total, (uint64_t)fr, d);
+    const PropPlan plan = prop_plan(sd.row_ptr, nq, per);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = feat.stage(c, b.d_feat, "the feature upload")) return rc;
+    if (int rc = values.stage(c, b.d_vals, "the values upload")) return rc;
+    sd.values = values.ptr();
+    if (int rc = prop_ensure(c, b.d_segs, plan.segs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, b.d_recs, plan.recs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, b.d_part, (size_t)(per * (uint64_t)d), "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_segsum, (size_t)per, "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_carry, 2 * (size_t)d, "the partial sums")) return rc;
+    if (int rc = prop_ensure(c, b.d_scarry, 2, "the partial sums")) return rc;
+    if (int rc = o32.reserve(c, b.d_out32)) return rc;
+    if (int rc = o64.reserve(c, b.d_out64)) return rc;
+    if (!plan.segs.empty()) HIPCHK(c, hipMemcpy(b.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b.d_recs.get(), plan.recs.data(), plan.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat.ptr(), ldf, d, bf16 ? 2 : 4, prop_widths(bf16), PROP_NWIDTHS);
+    uint64_t *const segsum = sd.divide ? b.d_segsum.get() : nullptr;
+    c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
+    prop_launch_chunks(c, plan, b.d_segs.get(), b.d_recs.get(), sd, bf16, g, feat.ptr(), ldf, d, segsum, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), true);
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, "sparse propagate")) return rc;
+    rs.segments = total; rs.max_row = plan.max_row; rs.chunks = (int32_t)plan.chunks.size(); rs.feat_on_device = feat.on_device();
+    return FORA_OK;
+}
+// the operands and outputs of the two products: feat of feat_rows rows, values per entry, out of out_rows rows
+struct PropIO { HeldIn feat, values; HeldOut<float> o32; HeldOut<double> o64; };
+PropIO prop_io(fora_ctx *c, const void *feat, bool bf16, uint64_t feat_rows, int64_t ldf, int d, const void *values, int val_type, float *out32, double *out64,
+               uint64_t out_rows, int64_t ldo) {
+    return PropIO{HeldIn::matrix(feat, feat_rows, ldf, (uint64_t)d, bf16 ? 2 : 4), HeldIn::vector(values, c->sp.entries, val_type == FORA_PROP_F64 ? 8 : 4),
+                  HeldOut<float>{out32, ldo, out_rows, (uint64_t)d}, HeldOut<double>{out64, ldo, out_rows, (uint64_t)d}};
+}
+int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, const void *values, int val_type,
+              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
+    const bool bf16 = feat_type == FORA_PROP_BF16;
+    PropIO io = prop_io(c, feat, bf16, (uint64_t)c->g.n, ldf, d, values, val_type, out32, out64, (uint64_t)nq, ldo);
+    if (int rc = held_resolve(c, io.values, io.feat, io.o32, io.o64)) return rc;
+    const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0, values, val_type == FORA_PROP_F64, nullptr};
+    PropRunStats rs;
+    if (int rc = prop_run(c, sd, io.feat, io.values, bf16, d, ldf, io.o32, io.o64, rs)) return rc;
+    if (ps) {
+        ps->entries = c->sp.entries; ps->segments = rs.segments; ps->max_row = rs.max_row;
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * (bf16 ? 2 : 4);
+        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device;
+        ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
+    }
+    return FORA_OK;
+}
+
+// ---- PROPAGATE, TRANSPOSED: the transposition of the held result (fora_propt.h, fora_propt_plan.h), built once per held result
+int propt_build(fora_ctx *c, const int64_t *row_ptr, int nq) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    PropTBufs t; // moved into the ctx after the last step; freed on every other way out
+    DevBuf<uint32_t> d_cnt; PinBuf<uint32_t> h_cnt; // counts per node, then the cursors of the place pass; their pinned landing area
+    DevBuf<uint64_t> d_key; DevBuf<int64_t> d_row_ptr; DevBuf<PropTRun> d_runs;
+    // ---- every buffer before the first launch
+    const char *what = "the transposition";
+    if (int rc = prop_ensure(c, t.d_rows, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_fix, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_col_ptr, (size_t)n + 1, what)) return rc;
+    if (int rc = prop_ensure(c, t.d_rsum, (size_t)nq, what)) return rc;
+    if (int rc = prop_ensure(c, d_cnt, (size_t)n, what)) return rc;
+    if (int rc = prop_ensure(c, d_key, (size_t)entries, what)) return rc;
+    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, what)) return rc;
+    if (int rc = prop_ensure(c, d_runs, (size_t)propt_max_runs(n, entries), what)) return rc;
+    if (h_cnt.alloc((size_t)n) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the transposition's counts"); }
+    t.h_col_ptr.assign((size_t)n + 1, 0);
+    t.nq = nq;
+    c->tm.propt_transpose_ms = 0;
+    if (entries) {
+        const uint32_t wgs = (uint32_t)std::min<int>(nq, 65535);
+        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
+        EvSpan ev(c, EV_PROPT_TRANSPOSE);
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
+        HIPCHK(c, t.d_rsum.zero(c->stream, (size_t)nq));
+        hipLaunchKernelGGL(k_propt_count, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(),
+                           (const uint64_t *)c->sp.d_fix.get(), (uint32_t)n, d_cnt.get(), reinterpret_cast<unsigned long long *>(t.d_rsum.get()));
+        HIPCHK(c, hipMemcpyAsync(h_cnt.get(), d_cnt.get(), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
+        if (propt_scan(h_cnt.get(), (int64_t)n, t.h_col_ptr.data()) != entries) return fail(c, FORA_E_HIP, "sparse transpose: the counts do not add up to the held entries");
+        const PropTTiers tiers = propt_tiers(t.h_col_ptr.data(), (int64_t)n, c->opt_.propt_lds_cap);
+        if (tiers.runs.size() > d_runs.size()) return fail(c, FORA_E_HIP, "sparse transpose: more runs than the table holds");
+        t.columns = tiers.columns; t.max_col = tiers.max_col;
+        t.short_cols = tiers.n_short; t.lds_cols = tiers.n_lds; t.global_cols = tiers.n_global;
+        HIPCHK(c, hipMemcpyAsync(t.d_col_ptr.get(), t.h_col_ptr.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (!tiers.runs.empty()) HIPCHK(c, hipMemcpyAsync(d_runs.get(), tiers.runs.data(), tiers.runs.size() * sizeof(PropTRun), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
+        hipLaunchKernelGGL(k_propt_place, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), (uint32_t)n,
+                           (const int64_t *)t.d_col_ptr.get(), d_cnt.get(), d_key.get(), entries);
+        const PropTRun *r_short = d_runs.get(), *r_lds = r_short + tiers.n_short, *r_global = r_lds + tiers.n_lds;
+        if (tiers.n_short) hipLaunchKernelGGL(k_propt_sort_short, dim3((tiers.n_short + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, r_short, tiers.n_short, d_key.get());
+        if (tiers.n_lds) hipLaunchKernelGGL(k_propt_sort_lds, dim3(tiers.n_lds), dim3(BLOCK), 0, c->stream, r_lds, d_key.get());
+        if (tiers.n_global) {
+            const uint32_t P = propt_pow2(tiers.max_global);
+            const unsigned gx = (unsigned)std::min<uint32_t>(std::max<uint32_t>(1, P / 2 / BLOCK), 1024);
+            for (uint32_t r0 = 0; r0 < tiers.n_global; r0 += 65535) { // (a grid's y extent)
+                const dim3 grid(gx, std::min<uint32_t>(65535, tiers.n_global - r0));
+                for (uint32_t k = 2; k <= P; k <<= 1) {
+                    hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, 0u);
+                    for (uint32_t j = k >> 2; j; j >>= 1) hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, j);
+                }
+            }
+        }
+        hipLaunchKernelGGL(k_propt_fill, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const uint64_t *)d_key.get(), entries,
+                           (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const uint64_t *)c->sp.d_fix.get(), t.d_rows.get(), t.d_fix.get());
+        ev.end();
+    } else {
+        HIPCHK(c, t.d_col_ptr.zero(c->stream, (size_t)n + 1));
+        HIPCHK(c, t.d_rsum.zero(c->stream));
+    }
+    if (int rc = held_call_end(c, "sparse transpose")) return rc; // (idle: h_col_ptr and the tables go out of use)
+    t.built = true;
+    c->pt = std::move(t);
+    return FORA_OK;
+}
+// the transposition of the held result, built now unless it is there; row_ptr has passed prop_row_ptr_ok
+int propt_ensure(fora_ctx *c, const int64_t *row_ptr, int nq, bool &built_now) {
+    built_now = false;
+    if (c->pt.built && c->pt.nq == nq) return FORA_OK;
+    c->pt = PropTBufs{};
+    if (int rc = propt_build(c, row_ptr, nq)) return rc;
+    built_now = true;
+    return FORA_OK;
+}
+// PROPAGATE WITH VALUES: pos of the transposition that is there, made once (k_propt_pos) and kept with it
+int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
+    PropTBufs &t = c->pt;
+    if (t.has_pos) return FORA_OK;
+    const uint64_t entries = c->sp.entries;
+    DevBuf<int64_t> d_pos, d_row_ptr;
+    if (int rc = prop_ensure(c, d_pos, (size_t)entries, "the transposition's places")) return rc;
+    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, "the transposition's places")) return rc;
+    if (entries) {
+        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
+        EvSpan ev(c, EV_PROPT_TRANSPOSE);
+        hipLaunchKernelGGL(k_propt_pos, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const int64_t *)t.d_col_ptr.get(),
+                           (uint32_t)c->g.n, (const int32_t *)t.d_rows.get(), (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), entries, d_pos.get());
+        ev.end();
+        if (int rc = held_call_end(c, "sparse transpose", false)) return rc; // (idle: d_row_ptr goes out of use; the span is collected with the product's)
+    }
+    t.d_pos = std::move(d_pos);
+    t.has_pos = true;
+    return FORA_OK;
+}
+int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, const void *values, int val_type,
+               float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
+    const bool bf16 = grad_type == FORA_PROP_BF16;
+    PropIO io = prop_io(c, grad, bf16, (uint64_t)nq, ldg, d, values, val_type, out32, out64, (uint64_t)c->g.n, ldo);
+    if (int rc = held_resolve(c, io.feat, io.values, io.o32, io.o64)) return rc; // (before the transposition is built)
+    bool built_now = false;
+    if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
+    double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
+    if (values) if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
+    const PropTBufs &t = c->pt;
+    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
+                      values, val_type == FORA_PROP_F64, values ? t.d_pos.get() : nullptr};
+    PropRunStats rs;
+    if (int rc = prop_run(c, sd, io.feat, io.values, bf16, d, ldg, io.o32, io.o64, rs)) return rc;
+    if (built_now) transpose_ms = c->tm.propt_transpose_ms; // (with values: the places too)
+    if (ps) {
+        ps->entries = c->sp.entries; ps->columns = t.columns; ps->segments = rs.segments; ps->max_col = t.max_col;
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * (bf16 ? 2 : 4);
+        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device; ps->built = built_now ? 1 : 0;
+        if (built_now) { ps->short_cols = (int32_t)t.short_cols; ps->lds_cols = (int32_t)t.lds_cols; ps->global_cols = (int32_t)t.global_cols; }
+        ps->transpose_ms = transpose_ms; ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
+    }
+    return FORA_OK;
+}
+
+// ---- SCORES (SDDMM)
+template <bool A_BF16, bool B_BF16>
+void sddmm_launch(fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg, float *o32, double *o64) {
+    const uint64_t units = nseg * SDDMM_UNITS, per_wg = BLOCK / 64;
+    hipLaunchKernelGGL((k_prop_sddmm<A_BF16, B_BF16>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, nseg,
+                       (const int32_t *)c->sp.d_ids.get(), a, lda, b, ldb, (uint32_t)d, lg, o32, o64);
+}
+// sddmm_launch for the element types of a and b
+void sddmm_launch_for(bool a_bf16, bool b_bf16, fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg,
+                      float *o32, double *o64) {
+    with_bools(a_bf16, b_bf16, [&](auto AB, auto BB) { sddmm_launch<AB.value, BB.value>(c, segs, nseg, a, lda, b, ldb, d, lg, o32, o64); });
+}
+int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a_, int a_type, int64_t lda, const void *b_, int b_type, int64_t ldb, int d,
+               float *out32, double *out64, fora_sddmm_stats *st) {
+    const uint64_t entries = c->sp.entries;
+    const bool a_bf16 = a_type == FORA_PROP_BF16, b_bf16 = b_type == FORA_PROP_BF16;
+    const uint32_t a_elt = a_bf16 ? 2 : 4, b_elt = b_bf16 ? 2 : 4;
+    HeldIn a = HeldIn::matrix(a_, (uint64_t)nq, lda, (uint64_t)d, a_elt), b = HeldIn::matrix(b_, (uint64_t)c->g.n, ldb, (uint64_t)d, b_elt);
+    HeldOut<float> o32 = HeldOut<float>::vector(out32, entries);
+    HeldOut<double> o64 = HeldOut<double>::vector(out64, entries);
+    if (int rc = held_resolve(c, a, b, o32, o64)) return rc;
+    PropBufs &pb = c->pr;
+    const uint64_t total = prop_segments(row_ptr, nq);
+    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: there are no partial sums to hold)
+    // ---- every buffer of the call before the launch: a call that finds no room has written nothing
+    if (int rc = a.stage(c, pb.d_a, "the upload of a")) return rc;
+    if (int rc = b.stage(c, pb.d_feat, "the upload of b")) return rc;
+    if (int rc = prop_ensure(c, pb.d_segs, plan.segs.size(), "the segment table")) return rc;
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    c->tm.sddmm_ms = 0;
+    if (!plan.segs.empty()) {
+        HIPCHK(c, hipMemcpy(pb.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        EvSpan ev(c, EV_SDDMM);
+        sddmm_launch_for(a_bf16, b_bf16, c, pb.d_segs.get(), plan.segs.size(), a.ptr(), lda, b.ptr(), ldb, d, prop_group_lg((uint32_t)d), o32.ptr(), o64.ptr());
+    }
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, "sparse sddmm")) return rc;
+    if (st) {
+        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
+        st->bytes = entries * (uint64_t)d * (a_elt + b_elt);
+        st->a_on_device = a.on_device(); st->b_on_device = b.on_device();
+        st->sddmm_ms = c->tm.sddmm_ms;
+    }
+    return FORA_OK;
+}
+
+
+// ---- ROW SOFTMAX
+struct SoftmaxWork { const PropSeg *shrt, *lng; uint64_t n_short, n_long; double *seg_max, *part; uint32_t *nan_rows; };
+inline dim3 softmax_grid(uint64_t nseg) { return dim3((unsigned)((nseg + BLOCK / 64 - 1) / (BLOCK / 64))); }
+template <typename TS>
+void softmax_launch(fora_ctx *c, const SoftmaxWork &w, const void *scores, double scale, float *o32, double *o64) {
+    const TS *x = (const TS *)scores;
+    if (w.n_short) hipLaunchKernelGGL((k_softmax_short<TS>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, x, scale, o32, o64, w.nan_rows);
+    if (w.n_long) {
+        hipLaunchKernelGGL((k_softmax_seg_max<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, w.seg_max);
+        hipLaunchKernelGGL((k_softmax_seg_sum<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max, w.part);
+        hipLaunchKernelGGL((k_softmax_div<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max,
+                           (const double *)w.part, o32, o64, w.nan_rows);
+    }
+}
+template <typename TY, typename TG>
+void softmax_bwd_launch(fora_ctx *c, const SoftmaxWork &w, const void *y, const void *g, double scale, float *o32, double *o64) {
+    const TY *yy = (const TY *)y;
+    const TG *gg = (const TG *)g;
+    if (w.n_short) hipLaunchKernelGGL((k_softmax_bwd_short<TY, TG>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, yy, gg, scale, o32, o64);
+    if (w.n_long) {
+        hipLaunchKernelGGL((k_softmax_bwd_seg_sum<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, w.part);
+        hipLaunchKernelGGL((k_softmax_bwd_div<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, scale, (const double *)w.part, o32, o64);
+    }
+}
+// both calls: in = scores (forward) or y (backward), grad = null (forward) or g
+int softmax_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *in_, int in_type, const void *grad_, int g_type, double scale,
+                 float *out32, double *out64, fora_softmax_stats *st) {
+    const uint64_t entries = c->sp.entries;
+    const bool bwd = grad_ != nullptr, in64 = in_type == FORA_PROP_F64, g64 = g_type == FORA_PROP_F64;
+    HeldIn in = HeldIn::vector(in_, entries, in64 ? 8 : 4), grad = HeldIn::vector(grad_, entries, g64 ? 8 : 4);
+    HeldOut<float> o32 = HeldOut<float>::vector(out32, entries);
+    HeldOut<double> o64 = HeldOut<double>::vector(out64, entries);
+    if (int rc = held_resolve(c, in, grad, o32, o64)) return rc;
+    PropBufs &pb = c->pr;
+    const uint64_t total = prop_segments(row_ptr, nq);
+    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: the partials are a few bytes per segment)
+    const SoftmaxLists lists = softmax_lists(plan.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = in.stage(c, pb.d_vals, bwd ? "the upload of y" : "the upload of the scores")) return rc;
+    if (int rc = grad.stage(c, pb.d_a, "the upload of grad")) return rc;
+    if (int rc = prop_ensure(c, pb.d_segs, lists.segs.size(), "the segment table")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)lists.n_long, "the segment maxima and sums")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    c->tm.softmax_ms = 0;
+    uint32_t nan_rows = 0;
+    if (!lists.segs.empty()) {
+        HIPCHK(c, hipMemcpy(pb.d_segs.get(), lists.segs.data(), lists.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        const SoftmaxWork w{pb.d_segs.get(), pb.d_segs.get() + lists.n_short, lists.n_short, lists.n_long, pb.d_smax.get(), pb.d_smax.get() + lists.n_long, pb.d_smax_nan.get()};
+        if (!bwd) HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+        {
+            EvSpan ev(c, EV_SOFTMAX);
+            if (bwd) with_bools(in64, g64, [&](auto Y64, auto G64) {
+                softmax_bwd_launch<std::conditional_t<Y64.value, double, float>, std::conditional_t<G64.value, double, float>>(c, w, in.ptr(), grad.ptr(), scale, o32.ptr(), o64.ptr());
+            });
+            else if (in64) softmax_launch<double>(c, w, in.ptr(), scale, o32.ptr(), o64.ptr());
+            else softmax_launch<float>(c, w, in.ptr(), scale, o32.ptr(), o64.ptr());
+        }
+        if (!bwd) HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, "sparse softmax")) return rc;
+    if (st) {
+        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
+        st->nan_rows = nan_rows; st->short_rows = lists.short_rows; st->long_rows = lists.long_rows;
+        st->in_on_device = in.on_device(); st->grad_on_device = grad.on_device();
+        st->softmax_ms = c->tm.softmax_ms;
+    }
+    return FORA_OK;
+}
+// the frame of the two calls (who: the call's name in messages; grad / g_type: the backward call's)
+int softmax_entry(fora_ctx *c, const char *who, const int64_t *row_ptr, int nq, const void *in, int in_type, bool bwd, const void *grad, int g_type, double scale,
+                  float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
+    if (int rc = held_call_begin(c, who, row_ptr, nq)) return rc;
+    const std::string w = std::string(who) + ": ";
+    if (in_type != FORA_PROP_F32 && in_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
+    if (bwd && g_type != FORA_PROP_F32 && g_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, w + "scale is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, w + "no output");
+    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, w + "cap is smaller than the held result");
+    if (c->sp.entries && (!in || (bwd && !grad))) return fail(c, FORA_E_ARG, w + "null input");
+    if (st) memset(st, 0, sizeof(*st));
+    if (nq == 0) return FORA_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, softmax_impl(c, row_ptr, nq, c->sp.entries ? in : nullptr, in_type, bwd && c->sp.entries ? grad : nullptr, g_type, scale, out32, out64, st));
+}
+
+// ---- ATTENTION
+template <bool QB, bool KB, bool VB, int V>
+void attn_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v, int64_t ldv,
+                 int d, int dv, uint32_t lg, double scale, uint64_t entries, float *o32, int64_t ld32, double *o64, int64_t ld64, float *y32, double *y64, uint32_t *nan_rows) {
+    const uint64_t units = nrow * (uint64_t)heads;
+    hipLaunchKernelGGL((k_attn_short<QB, KB, VB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), q, ldq, k, ldk, v, ldv, (uint32_t)d, (uint32_t)dv, lg, scale, entries, o32, ld32, o64, ld64, y32, y64, nan_rows);
+}
+inline const void *attn_cols(const void *m, uint64_t col, uint32_t elt) { return (const unsigned char *)m + col * elt; }
+
+int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk,
+                   const void *v_, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
+                   float *y32_, double *y64_, fora_attn_stats *st) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16;
+    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4;
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
+    HeldIn q = HeldIn::matrix(q_, (uint64_t)nq, ldq, wq, q_elt), k = HeldIn::matrix(k_, n, ldk, wq, k_elt), v = HeldIn::matrix(v_, n, ldv, wv, v_elt);
+    HeldOut<float> o32{out32, ldo, (uint64_t)nq, wv}, y32 = HeldOut<float>::vector(y32_, (uint64_t)heads * entries);
+    HeldOut<double> o64{out64, ldo, (uint64_t)nq, wv}, y64 = HeldOut<double>::vector(y64_, (uint64_t)heads * entries);
+    if (int rc = held_resolve(c, q, k, v, o32, o64, y32, y64)) return rc;
+    PropBufs &pb = c->pr;
+    // ---- the plan: the short rows' list; the longer rows' segments in chunks of prop_segs (0: a quarter of the free memory in
+    // partial sums at most), split once more for the softmax kernels by softmax_short
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    const uint64_t long_segs = prop_long_segments(row_ptr, nq, cap);
+    size_t fr = 0, tot = 0;
+    if (long_segs && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, long_segs, (uint64_t)fr, dv);
+    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per);
+    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    const bool lng = !plan.lrows.empty();
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
+    if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
+    if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), at_lrows = at_sm + sm.segs.size(),
+                 nsegs = at_lrows + plan.lrows.size();
+    if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    if (lng) {
+        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)dv), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment maxima and sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the scores of the longer rows")) return rc;
+        if (!y64_) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)entries, "the y of the longer rows")) return rc;
+    }
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = y32.reserve(c, pb.d_y32)) return rc;
+    if (int rc = y64.reserve(c, pb.d_y64)) return rc;
+    PropSeg *const ds = pb.d_segs.get();
+    if (!plan.shrt.empty()) HIPCHK(c, hipMemcpy(ds + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (lng) {
+        HIPCHK(c, hipMemcpy(ds + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(ds + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(ds + at_lrows, plan.lrows.data(), plan.lrows.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    }
+    const uint32_t lg = prop_group_lg((uint32_t)d);
+    const uint32_t *const widths = prop_widths(v_bf16);
+    c->tm.attn_ms = 0;
+    uint32_t nan_rows = 0;
+    HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+    {
+        EvSpan ev(c, EV_ATTN);
+        if (!plan.shrt.empty()) with_bools(q_bf16, k_bf16, [&](auto QB, auto KB) {
+            constexpr bool qb = decltype(QB)::value, kb = decltype(KB)::value;
+            with_vec(v_bf16, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto VB, auto V) {
+                attn_launch<qb, kb, VB.value, V.value>(c, ds + at_short, plan.shrt.size(), heads, q.ptr(), ldq, k.ptr(), ldk, v.ptr(), ldv, d, dv, lg, scale, entries,
+                                                       o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get());
+            });
+        });
+        for (int h = 0; lng && h < heads; h++) { // the longer rows, one head at a time through the two per-entry buffers
+            const void *qh = attn_cols(q.ptr(), (uint64_t)h * d, q_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
+            double *const s64 = pb.d_attn_s.get();
+            double *const yh64 = y64.ptr() ? y64.ptr((uint64_t)h * entries) : pb.d_attn_y.get();
+            float *const yh32 = y32.ptr((uint64_t)h * entries);
+            const PropSeg *segs = ds + at_lsegs;
+            sddmm_launch_for(q_bf16, k_bf16, c, segs, plan.lng.segs.size(), qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            const SoftmaxWork w{ds + at_sm, ds + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, pb.d_smax_nan.get()};
+            softmax_launch<double>(c, w, s64, scale, yh32, yh64);
+            const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), nullptr, nullptr, false, yh64, true, nullptr};
+            const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, PROP_NWIDTHS);
+            float *const oh32 = o32.ptr((uint64_t)h * dv);
+            double *const oh64 = o64.ptr((uint64_t)h * dv);
+            prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, v_bf16, g, vh, ldv, dv, nullptr, oh32, o32.ld(), oh64, o64.ld(), false);
+            const dim3 grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(plan.lrows.size(), 65535));
+            hipLaunchKernelGGL(k_attn_nan_rows, grid, dim3(BLOCK), 0, c->stream, (const PropSeg *)(ds + at_lrows), (uint64_t)plan.lrows.size(), (const double *)yh64,
+                               (uint32_t)dv, oh32, o32.ld(), oh64, o64.ld());
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = held_fetch(c, o32, o64, y32, y64)) return rc;
+    if (int rc = held_call_end(c, "sparse attention")) return rc;
+    if (st) {
+        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
+        st->nan_rows = nan_rows; st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
+        st->q_on_device = q.on_device(); st->k_on_device = k.on_device(); st->v_on_device = v.on_device();
+        st->attn_ms = c->tm.attn_ms;
+    }
+    return FORA_OK;
+}
+
+// ---- ATTENTION, BACKWARD
+template <bool GB, bool VB, bool KB, int V>
+void attn_bwd_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *g, int64_t ldg, const void *v, int64_t ldv, const void *k, int64_t ldk,
+                     int d, int dv, uint32_t lgv, double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const uint64_t units = nrow * (uint64_t)heads;
+    hipLaunchKernelGGL((k_attn_bwd_short<GB, VB, KB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), g, ldg, v, ldv, k, ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, entries, y, y_f64, ds, o32, ld32, o64, ld64);
+}
+template <bool BF16, int V>
+void attn_cols_launch(fora_ctx *c, const PropGeom &g, const PropSeg *cols, uint64_t ncol, int heads, const void *values, bool val64, uint64_t entries,
+                      const void *feat, int64_t ldf, int w, float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const uint64_t units = ncol * (uint64_t)heads, per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+    const dim3 grid((unsigned)((units + per_wg - 1) / per_wg), g.tiles);
+    const int32_t *rows = c->pt.d_rows.get();
+    const int64_t *pos = c->pt.d_pos.get();
+    if (val64) hipLaunchKernelGGL((k_attn_cols<BF16, V, true>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+    else hipLaunchKernelGGL((k_attn_cols<BF16, V, false>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+}
+// +0.0 to an n x width output: one clear where the rows lie back to back, a clear per row band otherwise (a pitch wider than
+// the output: what lies between the rows is the caller's)
+template <typename T> hipError_t attn_zero(fora_ctx *c, T *out, int64_t ld, uint64_t rows, uint64_t width) {
+    if (!out || !rows) return hipSuccess;
+    if ((uint64_t)ld == width) return hipMemsetAsync(out, 0, rows * width * sizeof(T), c->stream);
+    return hipMemset2DAsync(out, (size_t)ld * sizeof(T), 0, width * sizeof(T), rows, c->stream);
+}
+// one gradient of the column side: out[v][h * w + c] = the sum over column v's entries p of values[h * entries + pos[p]] *
+// feat[rows[p]][h * w + c].  The outputs zeroed (the empty columns), the short columns of all heads in one launch, the longer
+// ones head by head through PROPAGATE's kernels over the cached plan.
+int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, bool val64, const void *feat, bool bf16, int64_t ldf, int w,
+                  float *o32, int64_t ld32, double *o64, int64_t ld64) {
+    const PropTBufs &t = c->pt;
+    const AttnColPlan &cp = t.cols.plan;
+    const uint64_t n = (uint64_t)c->g.n;
+    const uint32_t elt = bf16 ? 2 : 4;
+    const uint32_t *const widths = prop_widths(bf16);
+    HIPCHK(c, attn_zero(c, o32, ld32, n, (uint64_t)heads * (uint64_t)w));
+    HIPCHK(c, attn_zero(c, o64, ld64, n, (uint64_t)heads * (uint64_t)w));
+    if (!cp.shrt.empty()) {
+        const PropGeom g = attn_cols_geom(attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, widths, PROP_NWIDTHS), w);
+        with_vec(bf16, g.V, [&](auto B, auto V) {
+            attn_cols_launch<B.value, V.value>(c, g, t.cols.d_short.get(), cp.shrt.size(), heads, values, val64, entries, feat, ldf, w, o32, ld32, o64, ld64);
+        });
+    }
+    for (int h = 0; cp.long_cols && h < heads; h++) {
+        const void *fh = attn_cols(feat, (uint64_t)h * w, elt);
+        const void *vh = (const unsigned char *)values + (uint64_t)h * entries * (val64 ? 8 : 4);
+        const PropSide sd{t.h_col_ptr.data(), (int)n, t.d_rows.get(), nullptr, nullptr, false, vh, val64, t.d_pos.get()};
+        const PropGeom g = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, widths, PROP_NWIDTHS);
+        prop_launch_chunks(c, cp.lng, t.cols.d_lsegs.get(), t.cols.d_lrecs.get(), sd, bf16, g, fh, ldf, w, nullptr, o32 ? o32 + (uint64_t)h * w : nullptr, ld32,
+                           o64 ? o64 + (uint64_t)h * w : nullptr, ld64, false);
+    }
+    return FORA_OK;
+}
+
+int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk,
+                       const void *v_, int v_type, int64_t ldv, const void *g_, int g_type, int64_t ldg, const void *y_, int y_type,
+                       int d, int dv, int heads, double scale, const fora_attn_grads &gr, fora_attn_bwd_stats *st) {
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16, g_bf16 = g_type == FORA_PROP_BF16;
+    const bool y_f64 = y_type == FORA_PROP_F64;
+    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4, g_elt = g_bf16 ? 2 : 4, y_elt = y_f64 ? 8 : 4;
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q, k, dq and dk; of v, g and dv
+    const bool want_dq = gr.dq32 || gr.dq64, want_dk = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64;
+    const bool want_rows = want_dq || want_dk, want_cols = want_dk || want_dv; // dy and ds; the transposition
+    HeldIn q = HeldIn::matrix(q_, (uint64_t)nq, ldq, wq, q_elt), k = HeldIn::matrix(k_, n, ldk, wq, k_elt), v = HeldIn::matrix(v_, n, ldv, wv, v_elt);
+    HeldIn g = HeldIn::matrix(g_, (uint64_t)nq, ldg, wv, g_elt), y = HeldIn::vector(y_, (uint64_t)heads * entries, y_elt);
+    HeldOut<float> dq32{gr.dq32, gr.lddq, (uint64_t)nq, wq}, dk32{gr.dk32, gr.lddk, n, wq}, dv32{gr.dv32, gr.lddv, n, wv};
+    HeldOut<double> dq64{gr.dq64, gr.lddq, (uint64_t)nq, wq}, dk64{gr.dk64, gr.lddk, n, wq}, dv64{gr.dv64, gr.lddv, n, wv};
+    if (int rc = held_resolve(c, q, k, v, g, y, dq32, dq64, dk32, dk64, dv32, dv64)) return rc; // (before the transposition is built)
+    // ---- the transposition and its places, as the first transposed product with values would build them
+    bool built_now = false;
+    if (want_cols) {
+        if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
+        if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
+    }
+    PropBufs &pb = c->pr;
+    PropTBufs &t = c->pt;
+    // ---- the plans.  Rows: as the forward call's, the longer rows' product d columns wide.  Columns: from the cache when "attn_short"
+    // and the resolved chunk size are the ones it was made under
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    const uint64_t long_row_segs = want_rows ? prop_long_segments(row_ptr, nq, cap) : 0;
+    uint64_t long_col_segs = 0;
+    if (want_cols) long_col_segs = t.cols.valid && t.cols.short_cap == cap ? t.cols.long_segs : attn_long_col_segs(t.h_col_ptr.data(), (int64_t)n, cap);
+    size_t fr = 0, tot = 0;
+    if ((long_row_segs || long_col_segs) && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const int wmax = std::max(d, dv);
+    const uint64_t per_rows = prop_chunk_segs(c->opt_.prop_segs, long_row_segs, (uint64_t)fr, d);
+    const uint64_t per_cols = prop_chunk_segs(c->opt_.prop_segs, long_col_segs, (uint64_t)fr, wmax);
+    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per_rows);
+    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
+    const bool lng_rows = want_rows && !plan.lrows.empty();
+    const bool plan_cached = want_cols && t.cols.valid && t.cols.short_cap == cap && t.cols.chunk_segs == per_cols;
+    if (want_cols && !plan_cached) {
+        PropTBufs::ColPlan nc; // moved into the transposition when complete
+        nc.short_cap = cap; nc.chunk_segs = per_cols; nc.long_segs = long_col_segs;
+        nc.plan = attn_col_plan(t.h_col_ptr.data(), (int64_t)n, cap, per_cols);
+        if (int rc = prop_ensure(c, nc.d_short, nc.plan.shrt.size(), "the column table")) return rc;
+        if (int rc = prop_ensure(c, nc.d_lsegs, nc.plan.lng.segs.size(), "the column table")) return rc;
+        if (int rc = prop_ensure(c, nc.d_lrecs, nc.plan.lng.recs.size(), "the column table")) return rc;
+        if (!nc.plan.shrt.empty()) HIPCHK(c, hipMemcpy(nc.d_short.get(), nc.plan.shrt.data(), nc.plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        if (!nc.plan.lng.segs.empty()) HIPCHK(c, hipMemcpy(nc.d_lsegs.get(), nc.plan.lng.segs.data(), nc.plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        if (!nc.plan.lng.recs.empty()) HIPCHK(c, hipMemcpy(nc.d_lrecs.get(), nc.plan.lng.recs.data(), nc.plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+        nc.valid = true;
+        t.cols = std::move(nc);
+    }
+    const bool lng_cols = want_cols && t.cols.plan.long_cols != 0;
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing.  An operand that no
+    // wanted gradient reads is not uploaded
+    if (want_dk) if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
+    if (want_dq) if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
+    if (want_rows) if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    if (int rc = g.stage(c, pb.d_g, "the upload of g")) return rc;
+    if (int rc = y.stage(c, pb.d_vals, "the upload of y")) return rc;
+    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), nsegs = at_sm + sm.segs.size();
+    if (want_rows) if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
+    if (lng_rows) {
+        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the dy of the longer rows")) return rc;
+    }
+    if (lng_rows || lng_cols) {
+        const uint64_t part = std::max(lng_rows && want_dq ? per_rows * (uint64_t)d : 0, lng_cols ? per_cols * (uint64_t)wmax : 0);
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)part, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)wmax, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    if (want_dk || lng_rows) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)entries, "ds")) return rc;
+    if (int rc = dq32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = dq64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = dk32.reserve(c, pb.d_dk32)) return rc;
+    if (int rc = dk64.reserve(c, pb.d_dk64)) return rc;
+    if (int rc = dv32.reserve(c, pb.d_dv32)) return rc;
+    if (int rc = dv64.reserve(c, pb.d_dv64)) return rc;
+    PropSeg *const dsg = pb.d_segs.get();
+    if (want_rows && !plan.shrt.empty()) HIPCHK(c, hipMemcpy(dsg + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (lng_rows) {
+        HIPCHK(c, hipMemcpy(dsg + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(dsg + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    }
+    double *const ds = want_dk || lng_rows ? pb.d_attn_ds.get() : nullptr;
+    const uint32_t lgv = prop_group_lg((uint32_t)dv); // (the dv columns of dy)
+    const uint32_t *const widths_k = prop_widths(k_bf16);
+    c->tm.attn_ms = 0;
+    {
+        EvSpan ev(c, EV_ATTN);
+        if (want_rows && !plan.shrt.empty()) with_bools(g_bf16, v_bf16, [&](auto GB, auto VB) { // dy, ds and dq of the short rows, all heads
+            constexpr bool gb = decltype(GB)::value, vb = decltype(VB)::value;
+            with_vec(k_bf16, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto KB, auto V) {
+                attn_bwd_launch<gb, vb, KB.value, V.value>(c, dsg + at_short, plan.shrt.size(), heads, g.ptr(), ldg, v.ptr(), ldv, k.ptr(), ldk, d, dv, lgv, scale, entries,
+                                                           y.ptr(), y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld());
+            });
+        });
+        for (int h = 0; lng_rows && h < heads; h++) { // the longer rows, one head at a time: dy, ds into the head's slice, dq
+            const void *gh = attn_cols(g.ptr(), (uint64_t)h * dv, g_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt);
+            const void *yh = (const unsigned char *)y.ptr() + (uint64_t)h * entries * y_elt;
+            double *const dy64 = pb.d_attn_s.get(), *const dsh = ds + (uint64_t)h * entries;
+            const PropSeg *segs = dsg + at_lsegs;
+            sddmm_launch_for(g_bf16, v_bf16, c, segs, plan.lng.segs.size(), gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            const SoftmaxWork w{dsg + at_sm, dsg + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, nullptr};
+            if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, scale, nullptr, dsh);
+            else softmax_bwd_launch<float, double>(c, w, yh, dy64, scale, nullptr, dsh);
+            if (want_dq) {
+                const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), nullptr, nullptr, false, dsh, true, nullptr};
+                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, PROP_NWIDTHS);
+                prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, k_bf16, gm, kh, ldk, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
+            }
+        }
+        if (want_dk) if (int rc = attn_bwd_cols(c, heads, entries, ds, true, q.ptr(), q_bf16, ldq, d, dk32.ptr(), dk32.ld(), dk64.ptr(), dk64.ld())) return rc;
+        if (want_dv) if (int rc = attn_bwd_cols(c, heads, entries, y.ptr(), y_f64, g.ptr(), g_bf16, ldg, dv, dv32.ptr(), dv32.ld(), dv64.ptr(), dv64.ld())) return rc;
+    }
+    if (int rc = held_fetch(c, dq32, dq64, dk32, dk64, dv32, dv64)) return rc;
+    if (int rc = held_call_end(c, "sparse attention_bwd")) return rc;
+    if (st) {
+        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
+        st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
+        if (want_cols) {
+            const AttnColPlan &cp = t.cols.plan;
+            st->columns = cp.columns; st->max_col = cp.max_col; st->short_cols = cp.short_cols; st->long_cols = cp.long_cols;
+        }
+        st->built = built_now ? 1 : 0; st->plan_cached = plan_cached ? 1 : 0;
+        st->q_on_device = q.on_device(); st->k_on_device = k.on_device(); st->v_on_device = v.on_device(); st->g_on_device = g.on_device();
+        st->y_on_device = y.on_device();
+        st->transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0; st->attn_ms = c->tm.attn_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+
 // =============================================================================== C ABI
 extern "C" {
 
@@ -2767,35 +3553,6 @@ int fora_hip_seeds_sweep_batch(fora_ctx *c, const int64_t *set_ptr, const int32_
     });
 }
 
-// is p device memory of the ctx's GPU?  (host memory the runtime has never seen: no attributes, or "unregistered")
-static int sparse_dest(fora_ctx *c, const void *p, bool &on_device) {
-    hipPointerAttribute_t a{};
-    on_device = false;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return FORA_OK; }
-    if (a.type != hipMemoryTypeDevice) return FORA_OK;
-    if (a.device != c->device) return fail(c, FORA_E_ARG, "destination is memory of another GPU");
-    on_device = true;
-    return FORA_OK;
-}
-
-// e held words (device) as doubles into vals, on the ctx's stream: converted in place for device memory, SP_STAGE at a time
-// through the sparse result's stage buffer for a host array
-static int fetch_vals(fora_ctx *c, const uint64_t *words, uint64_t e, double *vals, bool vals_on_device) {
-    constexpr uint64_t SP_STAGE = 1ull << 22; // doubles converted on the device per copy to a host array
-    const auto grid = [&](uint64_t cnt) { return dim3((unsigned)std::min<uint64_t>((cnt + BLOCK - 1) / BLOCK, 4096)); };
-    if (vals_on_device) {
-        hipLaunchKernelGGL(k_sparse_vals, grid(e), dim3(BLOCK), 0, c->stream, words, e, vals);
-        return FORA_OK;
-    }
-    HIPCHK(c, c->sp.d_stage.ensure(SP_STAGE));
-    for (uint64_t at = 0; at < e; at += SP_STAGE) {
-        const uint64_t len = std::min(SP_STAGE, e - at);
-        hipLaunchKernelGGL(k_sparse_vals, grid(len), dim3(BLOCK), 0, c->stream, words + at, len, c->sp.d_stage.get());
-        HIPCHK(c, hipMemcpyAsync(vals + at, c->sp.d_stage.get(), len * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    return FORA_OK;
-}
-
 int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix, uint64_t cap) {
     if (!c) return FORA_E_ARG;
     if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
@@ -2807,299 +3564,21 @@ int fora_hip_sparse_fetch(fora_ctx *c, int32_t *ids, double *vals, uint64_t *fix
     if (e && ids) HIPCHK(c, hipMemcpyAsync(ids, c->sp.d_ids.get(), e * 4, hipMemcpyDefault, c->stream));
     if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, c->sp.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
     if (e && vals) if (int rc = fetch_vals(c, c->sp.d_fix.get(), e, vals, vals_on_device)) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse fetch: ") + hipGetErrorString(err));
-    return FORA_OK;
+    return held_call_end(c, "sparse fetch", false);
 }
 
 // ---- PROPAGATE (the contract of include/fora_hip.h): the held sparse rows times a feature matrix, every bit defined
 static_assert(PROP_SEG == FORA_PROP_SEG, "fora_prop_plan.h and include/fora_hip.h name one segment length");
-extern "C++" { // (templates, and sparse_dest above is in scope here)
-namespace {
-// a grown-or-kept buffer of the call; no room is FORA_E_NOMEM and leaves no sticky HIP error behind
-template <typename T> int prop_ensure(fora_ctx *c, DevBuf<T> &b, size_t cnt, const char *what) {
-    if (b.ensure(std::max<size_t>(cnt, 1)) == hipSuccess) return FORA_OK;
-    (void)hipGetLastError();
-    return fail(c, FORA_E_NOMEM, std::string("no device memory for ") + what);
-}
-// One side of the product: which output rows are summed over which entries.  Forward: the held rows (ids: nodes, feat: the n
-// feature rows).  Transposed: the columns of the transposition (ids: the rows the entries came from, feat: the nq gradient rows).
-struct PropSide {
-    const int64_t *row_ptr; int rows;        // (host) the output rows' entries
-    uint64_t feat_rows;                      // rows of feat: the extent of a host feat's upload
-    const int32_t *ids; const uint64_t *fix; // (device) the entries
-    const uint64_t *rsum;                    // transposed and normalised: S by id, every weight divided by it in the gather; else null
-    bool divide;                             // forward and normalised: a row's sum divided by its word sum in the combine
-    const void *values = nullptr; bool val64 = false; // PROPAGATE WITH VALUES: the caller's weights (host or device; null: the words), f64 or f32
-    const int64_t *pos = nullptr;            // (device) with values, transposed: the held place of every entry; forward: null
-};
-struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
-
-template <bool BF16, int V>
-void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
-    const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
-    const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
-    if (sd.values) {
-        if (sd.pos) {
-            if (sd.val64) hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, true, true>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
-            else hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, true, false>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
-        } else {
-            if (sd.val64) hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, false, true>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
-            else hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, false, false>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
-        }
-    } else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
-    else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
-}
-// the two kernels chunk by chunk over a plan whose segments and records lie at d_segs and d_recs: the partial sums of one chunk
-// live at a time in the ctx's buffers, which the caller has ensured.  timed: an event pair per launch (PROPAGATE's own stats);
-// a caller with a span of its own around the whole passes false.
-void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, bool bf16, const PropGeom &g,
-                        const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed) {
-    PropBufs &b = c->pr;
-    for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
-        const PropChunk &ch = plan.chunks[ci];
-        if (ch.nseg) {
-            EvSpan ev(c);
-            if (timed) ev.begin(EV_PROP_GATHER);
-            const PropSeg *segs = d_segs + ch.seg0;
-            if (!bf16) switch (g.V) {
-                case 4: prop_launch_gather<false, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 2: prop_launch_gather<false, 2>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<false, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-            } else switch (g.V) {
-                case 8: prop_launch_gather<true, 8>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                case 4: prop_launch_gather<true, 4>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-                default: prop_launch_gather<true, 1>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); break;
-            }
-        }
-        if (ch.nrec) {
-            EvSpan ev(c);
-            if (timed) ev.begin(EV_PROP_COMBINE);
-            const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
-            const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
-            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, d_recs + ch.rec0, ch.nrec,
-                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
-                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, ld32, w64, ld64);
-        }
-    }
-}
-// the product of one side with feat: plan, buffers, the two kernels chunk by chunk, the staged outputs; the stream is idle and
-// the event times are collected when it returns FORA_OK
-int prop_run(fora_ctx *c, const PropSide &side, const void *feat, int feat_type, int d, int64_t ldf, float *out32, double *out64, int64_t ldo, PropRunStats &rs) {
-    const bool bf16 = feat_type == FORA_PROP_BF16;
-    const uint32_t elt = bf16 ? 2 : 4;
-    PropSide sd = side; // (a host `values` is replaced by its upload)
-    const int nq = sd.rows;
-    const uint64_t entries = (uint64_t)sd.row_ptr[nq];
-    bool feat_dev = false, o32_dev = false, o64_dev = false, vals_dev = false;
-    if (sd.values) if (int rc = sparse_dest(c, sd.values, vals_dev)) return rc;
-    if (feat) if (int rc = sparse_dest(c, feat, feat_dev)) return rc;
-    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
-    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
-    PropBufs &b = c->pr;
-    // ---- the plan: chunks of prop_segs segments; 0: a quarter of the free memory in partial sums at most
-    const uint64_t total = prop_segments(sd.row_ptr, nq);
-    size_t fr = 0, tot = 0;
-    if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, total, (uint64_t)fr, d);
-    const PropPlan plan = prop_plan(sd.row_ptr, nq, per);
-    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
-    if (entries && !feat_dev) {
-        const size_t bytes = (size_t)(((sd.feat_rows - 1) * (uint64_t)ldf + (uint64_t)d) * elt);
-        if (int rc = prop_ensure(c, b.d_feat, bytes, "the feature upload")) return rc;
-        HIPCHK(c, hipMemcpy(b.d_feat.get(), feat, bytes, hipMemcpyHostToDevice));
-        feat = b.d_feat.get();
-    }
-    if (entries && sd.values && !vals_dev) {
-        const size_t bytes = (size_t)entries * (sd.val64 ? 8 : 4);
-        if (int rc = prop_ensure(c, b.d_vals, bytes, "the values upload")) return rc;
-        HIPCHK(c, hipMemcpy(b.d_vals.get(), sd.values, bytes, hipMemcpyHostToDevice));
-        sd.values = b.d_vals.get();
-    }
-    if (int rc = prop_ensure(c, b.d_segs, plan.segs.size(), "the segment table")) return rc;
-    if (int rc = prop_ensure(c, b.d_recs, plan.recs.size(), "the segment table")) return rc;
-    if (int rc = prop_ensure(c, b.d_part, (size_t)(per * (uint64_t)d), "the partial sums")) return rc;
-    if (int rc = prop_ensure(c, b.d_segsum, (size_t)per, "the partial sums")) return rc;
-    if (int rc = prop_ensure(c, b.d_carry, 2 * (size_t)d, "the partial sums")) return rc;
-    if (int rc = prop_ensure(c, b.d_scarry, 2, "the partial sums")) return rc;
-    if (out32 && !o32_dev) if (int rc = prop_ensure(c, b.d_out32, (size_t)nq * (size_t)d, "a staged output")) return rc;
-    if (out64 && !o64_dev) if (int rc = prop_ensure(c, b.d_out64, (size_t)nq * (size_t)d, "a staged output")) return rc;
-    if (!plan.segs.empty()) HIPCHK(c, hipMemcpy(b.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(b.d_recs.get(), plan.recs.data(), plan.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
-    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : b.d_out32.get();
-    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : b.d_out64.get();
-    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
-    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat, ldf, d, elt, bf16 ? widths_bf16 : widths_f32, 3);
-    uint64_t *const segsum = sd.divide ? b.d_segsum.get() : nullptr;
-    c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
-    prop_launch_chunks(c, plan, b.d_segs.get(), b.d_recs.get(), sd, bf16, g, feat, ldf, d, segsum, w32, o32_dev ? ldo : (int64_t)d, w64, o64_dev ? ldo : (int64_t)d, true);
-    if (out32 && !o32_dev) HIPCHK(c, hipMemcpy2DAsync(out32, (size_t)ldo * 4, w32, (size_t)d * 4, (size_t)d * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    if (out64 && !o64_dev) HIPCHK(c, hipMemcpy2DAsync(out64, (size_t)ldo * 8, w64, (size_t)d * 8, (size_t)d * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse propagate: ") + hipGetErrorString(err));
-    ev_collect(c);
-    rs.segments = total; rs.max_row = plan.max_row; rs.chunks = (int32_t)plan.chunks.size(); rs.feat_on_device = feat_dev ? 1 : 0;
-    return FORA_OK;
-}
-int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, const void *values, int val_type,
-              float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
-    const PropSide sd{row_ptr, nq, (uint64_t)c->g.n, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0,
-                      values, val_type == FORA_PROP_F64, nullptr};
-    PropRunStats rs;
-    if (int rc = prop_run(c, sd, feat, feat_type, d, ldf, out32, out64, ldo, rs)) return rc;
-    if (ps) {
-        ps->entries = c->sp.entries; ps->segments = rs.segments; ps->max_row = rs.max_row;
-        ps->feat_bytes = c->sp.entries * (uint64_t)d * (feat_type == FORA_PROP_BF16 ? 2 : 4);
-        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device;
-        ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
-    }
-    return FORA_OK;
-}
-
-// ---- PROPAGATE, TRANSPOSED: the transposition of the held result (fora_propt.h, fora_propt_plan.h), built once per held result
-int propt_build(fora_ctx *c, const int64_t *row_ptr, int nq) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
-    PropTBufs t; // moved into the ctx after the last step; freed on every other way out
-    DevBuf<uint32_t> d_cnt; PinBuf<uint32_t> h_cnt; // counts per node, then the cursors of the place pass; their pinned landing area
-    DevBuf<uint64_t> d_key; DevBuf<int64_t> d_row_ptr; DevBuf<PropTRun> d_runs;
-    // ---- every buffer before the first launch
-    const char *what = "the transposition";
-    if (int rc = prop_ensure(c, t.d_rows, (size_t)entries, what)) return rc;
-    if (int rc = prop_ensure(c, t.d_fix, (size_t)entries, what)) return rc;
-    if (int rc = prop_ensure(c, t.d_col_ptr, (size_t)n + 1, what)) return rc;
-    if (int rc = prop_ensure(c, t.d_rsum, (size_t)nq, what)) return rc;
-    if (int rc = prop_ensure(c, d_cnt, (size_t)n, what)) return rc;
-    if (int rc = prop_ensure(c, d_key, (size_t)entries, what)) return rc;
-    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, what)) return rc;
-    if (int rc = prop_ensure(c, d_runs, (size_t)propt_max_runs(n, entries), what)) return rc;
-    if (h_cnt.alloc((size_t)n) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the transposition's counts"); }
-    t.h_col_ptr.assign((size_t)n + 1, 0);
-    t.nq = nq;
-    c->tm.propt_transpose_ms = 0;
-    if (entries) {
-        const uint32_t wgs = (uint32_t)std::min<int>(nq, 65535);
-        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
-        EvSpan ev(c, EV_PROPT_TRANSPOSE);
-        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
-        HIPCHK(c, t.d_rsum.zero(c->stream, (size_t)nq));
-        hipLaunchKernelGGL(k_propt_count, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(),
-                           (const uint64_t *)c->sp.d_fix.get(), (uint32_t)n, d_cnt.get(), reinterpret_cast<unsigned long long *>(t.d_rsum.get()));
-        HIPCHK(c, hipMemcpyAsync(h_cnt.get(), d_cnt.get(), (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
-        if (propt_scan(h_cnt.get(), (int64_t)n, t.h_col_ptr.data()) != entries) return fail(c, FORA_E_HIP, "sparse transpose: the counts do not add up to the held entries");
-        const PropTTiers tiers = propt_tiers(t.h_col_ptr.data(), (int64_t)n, c->opt_.propt_lds_cap);
-        if (tiers.runs.size() > d_runs.size()) return fail(c, FORA_E_HIP, "sparse transpose: more runs than the table holds");
-        t.columns = tiers.columns; t.max_col = tiers.max_col;
-        t.short_cols = tiers.n_short; t.lds_cols = tiers.n_lds; t.global_cols = tiers.n_global;
-        HIPCHK(c, hipMemcpyAsync(t.d_col_ptr.get(), t.h_col_ptr.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (!tiers.runs.empty()) HIPCHK(c, hipMemcpyAsync(d_runs.get(), tiers.runs.data(), tiers.runs.size() * sizeof(PropTRun), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, d_cnt.zero(c->stream, (size_t)n));
-        hipLaunchKernelGGL(k_propt_place, dim3(wgs), dim3(BLOCK), 0, c->stream, (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), (uint32_t)n,
-                           (const int64_t *)t.d_col_ptr.get(), d_cnt.get(), d_key.get(), entries);
-        const PropTRun *r_short = d_runs.get(), *r_lds = r_short + tiers.n_short, *r_global = r_lds + tiers.n_lds;
-        if (tiers.n_short) hipLaunchKernelGGL(k_propt_sort_short, dim3((tiers.n_short + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, r_short, tiers.n_short, d_key.get());
-        if (tiers.n_lds) hipLaunchKernelGGL(k_propt_sort_lds, dim3(tiers.n_lds), dim3(BLOCK), 0, c->stream, r_lds, d_key.get());
-        if (tiers.n_global) {
-            const uint32_t P = propt_pow2(tiers.max_global);
-            const unsigned gx = (unsigned)std::min<uint32_t>(std::max<uint32_t>(1, P / 2 / BLOCK), 1024);
-            for (uint32_t r0 = 0; r0 < tiers.n_global; r0 += 65535) { // (a grid's y extent)
-                const dim3 grid(gx, std::min<uint32_t>(65535, tiers.n_global - r0));
-                for (uint32_t k = 2; k <= P; k <<= 1) {
-                    hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, 0u);
-                    for (uint32_t j = k >> 2; j; j >>= 1) hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, j);
-                }
-            }
-        }
-        hipLaunchKernelGGL(k_propt_fill, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const uint64_t *)d_key.get(), entries,
-                           (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const uint64_t *)c->sp.d_fix.get(), t.d_rows.get(), t.d_fix.get());
-        ev.end();
-        HIPCHK(c, hipStreamSynchronize(c->stream)); // (h_col_ptr and the tables go out of use)
-    } else {
-        HIPCHK(c, t.d_col_ptr.zero(c->stream, (size_t)n + 1));
-        HIPCHK(c, t.d_rsum.zero(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose: ") + hipGetErrorString(err));
-    ev_collect(c);
-    t.built = true;
-    c->pt = std::move(t);
-    return FORA_OK;
-}
-// the transposition of the held result, built now unless it is there; row_ptr has passed prop_row_ptr_ok
-int propt_ensure(fora_ctx *c, const int64_t *row_ptr, int nq, bool &built_now) {
-    built_now = false;
-    if (c->pt.built && c->pt.nq == nq) return FORA_OK;
-    c->pt = PropTBufs{};
-    if (int rc = propt_build(c, row_ptr, nq)) return rc;
-    built_now = true;
-    return FORA_OK;
-}
-// PROPAGATE WITH VALUES: pos of the transposition that is there, made once (k_propt_pos) and kept with it
-int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
-    PropTBufs &t = c->pt;
-    if (t.has_pos) return FORA_OK;
-    const uint64_t entries = c->sp.entries;
-    DevBuf<int64_t> d_pos, d_row_ptr;
-    if (int rc = prop_ensure(c, d_pos, (size_t)entries, "the transposition's places")) return rc;
-    if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, "the transposition's places")) return rc;
-    if (entries) {
-        HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
-        EvSpan ev(c, EV_PROPT_TRANSPOSE);
-        hipLaunchKernelGGL(k_propt_pos, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const int64_t *)t.d_col_ptr.get(),
-                           (uint32_t)c->g.n, (const int32_t *)t.d_rows.get(), (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), entries, d_pos.get());
-        ev.end();
-        HIPCHK(c, hipStreamSynchronize(c->stream)); // (d_row_ptr goes out of use)
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose: ") + hipGetErrorString(err));
-    }
-    t.d_pos = std::move(d_pos);
-    t.has_pos = true;
-    return FORA_OK;
-}
-int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, const void *values, int val_type,
-               float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
-    bool dev = false; // (memory of another GPU is refused before anything is built)
-    if (grad) if (int rc = sparse_dest(c, grad, dev)) return rc;
-    if (values) if (int rc = sparse_dest(c, values, dev)) return rc;
-    if (out32) if (int rc = sparse_dest(c, out32, dev)) return rc;
-    if (out64) if (int rc = sparse_dest(c, out64, dev)) return rc;
-    bool built_now = false;
-    if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
-    double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
-    if (values) if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
-    const PropTBufs &t = c->pt;
-    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, (uint64_t)nq, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
-                      values, val_type == FORA_PROP_F64, values ? t.d_pos.get() : nullptr};
-    PropRunStats rs;
-    if (int rc = prop_run(c, sd, grad, grad_type, d, ldg, out32, out64, ldo, rs)) return rc;
-    if (built_now) transpose_ms = c->tm.propt_transpose_ms; // (with values: the places too)
-    if (ps) {
-        ps->entries = c->sp.entries; ps->columns = t.columns; ps->segments = rs.segments; ps->max_col = t.max_col;
-        ps->feat_bytes = c->sp.entries * (uint64_t)d * (grad_type == FORA_PROP_BF16 ? 2 : 4);
-        ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device; ps->built = built_now ? 1 : 0;
-        if (built_now) { ps->short_cols = (int32_t)t.short_cols; ps->lds_cols = (int32_t)t.lds_cols; ps->global_cols = (int32_t)t.global_cols; }
-        ps->transpose_ms = transpose_ms; ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
-    }
-    return FORA_OK;
-}
-} // namespace
-} // extern "C++"
 
 // the frame of fora_hip_sparse_propagate and fora_hip_sparse_propagate_vals (with_values: values / val_type are the caller's)
 static int prop_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, bool with_values,
                       const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
-    if (!c) return FORA_E_ARG;
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate: negative nq or null row_ptr");
+    if (int rc = held_call_begin(c, "sparse propagate", row_ptr, nq)) return rc;
     if (feat_type != FORA_PROP_F32 && feat_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate: unknown feat_type");
     if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate: unknown flag");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate: d outside 1 .. 65536");
     if (ldf < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate: a leading dimension smaller than d");
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate: no output");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate: row_ptr is not the held result's");
     if (c->sp.entries && !feat) return fail(c, FORA_E_ARG, "sparse propagate: null feat");
     if (with_values) {
         if (flags & FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate: FORA_PROP_NORMALIZE with values");
@@ -3124,15 +3603,12 @@ int fora_hip_sparse_propagate_vals(fora_ctx *c, const int64_t *row_ptr, int nq, 
 // ---- PROPAGATE, TRANSPOSED (the contract of include/fora_hip.h): out = (held rows)^T * grad, n x d, the same fixed order
 static int propt_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, bool with_values,
                        const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
-    if (!c) return FORA_E_ARG;
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse propagate_t: negative nq or null row_ptr");
+    if (int rc = held_call_begin(c, "sparse propagate_t", row_ptr, nq)) return rc;
     if (grad_type != FORA_PROP_F32 && grad_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown grad_type");
     if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown flag");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate_t: d outside 1 .. 65536");
     if (ldg < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate_t: a leading dimension smaller than d");
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse propagate_t: no output");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse propagate_t: row_ptr is not the held result's");
     if (c->sp.entries && !grad) return fail(c, FORA_E_ARG, "sparse propagate_t: null grad");
     if (with_values) {
         if (flags & FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate_t: FORA_PROP_NORMALIZE with values");
@@ -3153,85 +3629,15 @@ int fora_hip_sparse_propagate_t_vals(fora_ctx *c, const int64_t *row_ptr, int nq
 }
 
 // ---- SCORES (SDDMM) (the contract of include/fora_hip.h): score_e = <a[row_e], b[id_e]> for every held entry, in a fixed order
-extern "C++" {
-namespace {
-template <bool A_BF16, bool B_BF16>
-void sddmm_launch(fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg, float *o32, double *o64) {
-    const uint64_t units = nseg * SDDMM_UNITS, per_wg = BLOCK / 64;
-    hipLaunchKernelGGL((k_prop_sddmm<A_BF16, B_BF16>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, nseg,
-                       (const int32_t *)c->sp.d_ids.get(), a, lda, b, ldb, (uint32_t)d, lg, o32, o64);
-}
-int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
-               float *out32, double *out64, fora_sddmm_stats *st) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
-    const uint32_t a_elt = a_type == FORA_PROP_BF16 ? 2 : 4, b_elt = b_type == FORA_PROP_BF16 ? 2 : 4;
-    bool a_dev = false, b_dev = false, o32_dev = false, o64_dev = false;
-    if (a) if (int rc = sparse_dest(c, a, a_dev)) return rc;
-    if (b) if (int rc = sparse_dest(c, b, b_dev)) return rc;
-    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
-    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
-    PropBufs &pb = c->pr;
-    const uint64_t total = prop_segments(row_ptr, nq);
-    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: there are no partial sums to hold)
-    // ---- every buffer of the call before the launch: a call that finds no room has written nothing
-    if (entries && !a_dev) {
-        const size_t bytes = (size_t)((((uint64_t)nq - 1) * (uint64_t)lda + (uint64_t)d) * a_elt);
-        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of a")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_a.get(), a, bytes, hipMemcpyHostToDevice));
-        a = pb.d_a.get();
-    }
-    if (entries && !b_dev) {
-        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldb + (uint64_t)d) * b_elt);
-        if (int rc = prop_ensure(c, pb.d_feat, bytes, "the upload of b")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_feat.get(), b, bytes, hipMemcpyHostToDevice));
-        b = pb.d_feat.get();
-    }
-    if (int rc = prop_ensure(c, pb.d_segs, plan.segs.size(), "the segment table")) return rc;
-    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)entries, "a staged output")) return rc;
-    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)entries, "a staged output")) return rc;
-    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
-    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
-    c->tm.sddmm_ms = 0;
-    if (!plan.segs.empty()) {
-        HIPCHK(c, hipMemcpy(pb.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        uint32_t lg = 0;
-        while (lg < 6 && (1u << lg) < (uint32_t)d) lg++; // the smallest group that holds d columns, at most a wave
-        const PropSeg *segs = pb.d_segs.get();
-        const uint64_t nseg = plan.segs.size();
-        EvSpan ev(c, EV_SDDMM);
-        if (a_elt == 4 && b_elt == 4) sddmm_launch<false, false>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
-        else if (a_elt == 4) sddmm_launch<false, true>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
-        else if (b_elt == 4) sddmm_launch<true, false>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
-        else sddmm_launch<true, true>(c, segs, nseg, a, lda, b, ldb, d, lg, w32, w64);
-    }
-    if (entries && out32 && !o32_dev) HIPCHK(c, hipMemcpyAsync(out32, w32, (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
-    if (entries && out64 && !o64_dev) HIPCHK(c, hipMemcpyAsync(out64, w64, (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse sddmm: ") + hipGetErrorString(err));
-    ev_collect(c);
-    if (st) {
-        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
-        st->bytes = entries * (uint64_t)d * (a_elt + b_elt);
-        st->a_on_device = a_dev ? 1 : 0; st->b_on_device = b_dev ? 1 : 0;
-        st->sddmm_ms = c->tm.sddmm_ms;
-    }
-    return FORA_OK;
-}
-} // namespace
-} // extern "C++"
 
 int fora_hip_sparse_sddmm(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
                           float *out32, double *out64, uint64_t cap, fora_sddmm_stats *st) {
-    if (!c) return FORA_E_ARG;
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse sddmm: negative nq or null row_ptr");
+    if (int rc = held_call_begin(c, "sparse sddmm", row_ptr, nq)) return rc;
     if ((a_type != FORA_PROP_F32 && a_type != FORA_PROP_BF16) || (b_type != FORA_PROP_F32 && b_type != FORA_PROP_BF16))
         return fail(c, FORA_E_ARG, "sparse sddmm: unknown a_type or b_type");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse sddmm: d outside 1 .. 65536");
     if (lda < d || ldb < d) return fail(c, FORA_E_ARG, "sparse sddmm: a leading dimension smaller than d");
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse sddmm: no output");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse sddmm: row_ptr is not the held result's");
     if (cap < c->sp.entries) return fail(c, FORA_E_ARG, "sparse sddmm: cap is smaller than the held result");
     if (c->sp.entries && (!a || !b)) return fail(c, FORA_E_ARG, "sparse sddmm: null a or b");
     if (st) memset(st, 0, sizeof(*st));
@@ -3241,122 +3647,6 @@ int fora_hip_sparse_sddmm(fora_ctx *c, const int64_t *row_ptr, int nq, const voi
 }
 
 // ---- ROW SOFTMAX (the contract of include/fora_hip.h): softmax inside every held row and its gradient, in a fixed order
-extern "C++" {
-namespace {
-struct SoftmaxWork { const PropSeg *shrt, *lng; uint64_t n_short, n_long; double *seg_max, *part; uint32_t *nan_rows; };
-inline dim3 softmax_grid(uint64_t nseg) { return dim3((unsigned)((nseg + BLOCK / 64 - 1) / (BLOCK / 64))); }
-template <typename TS>
-void softmax_launch(fora_ctx *c, const SoftmaxWork &w, const void *scores, double scale, float *o32, double *o64) {
-    const TS *x = (const TS *)scores;
-    if (w.n_short) hipLaunchKernelGGL((k_softmax_short<TS>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, x, scale, o32, o64, w.nan_rows);
-    if (w.n_long) {
-        hipLaunchKernelGGL((k_softmax_seg_max<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, w.seg_max);
-        hipLaunchKernelGGL((k_softmax_seg_sum<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max, w.part);
-        hipLaunchKernelGGL((k_softmax_div<TS>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, x, scale, (const double *)w.seg_max,
-                           (const double *)w.part, o32, o64, w.nan_rows);
-    }
-}
-template <typename TY, typename TG>
-void softmax_bwd_launch(fora_ctx *c, const SoftmaxWork &w, const void *y, const void *g, double scale, float *o32, double *o64) {
-    const TY *yy = (const TY *)y;
-    const TG *gg = (const TG *)g;
-    if (w.n_short) hipLaunchKernelGGL((k_softmax_bwd_short<TY, TG>), softmax_grid(w.n_short), dim3(BLOCK), 0, c->stream, w.shrt, w.n_short, yy, gg, scale, o32, o64);
-    if (w.n_long) {
-        hipLaunchKernelGGL((k_softmax_bwd_seg_sum<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, w.part);
-        hipLaunchKernelGGL((k_softmax_bwd_div<TY, TG>), softmax_grid(w.n_long), dim3(BLOCK), 0, c->stream, w.lng, w.n_long, yy, gg, scale, (const double *)w.part, o32, o64);
-    }
-}
-// both calls: in = scores (forward) or y (backward), grad = null (forward) or g
-int softmax_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *in, int in_type, const void *grad, int g_type, double scale,
-                 float *out32, double *out64, fora_softmax_stats *st) {
-    const uint64_t entries = c->sp.entries;
-    const bool bwd = grad != nullptr;
-    bool in_dev = false, g_dev = false, o32_dev = false, o64_dev = false;
-    if (in) if (int rc = sparse_dest(c, in, in_dev)) return rc;
-    if (grad) if (int rc = sparse_dest(c, grad, g_dev)) return rc;
-    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
-    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
-    PropBufs &pb = c->pr;
-    const uint64_t total = prop_segments(row_ptr, nq);
-    const PropPlan plan = prop_plan(row_ptr, nq, std::max<uint64_t>(total, 1)); // (one chunk: the partials are a few bytes per segment)
-    const SoftmaxLists lists = softmax_lists(plan.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
-    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
-    if (entries && !in_dev) {
-        const size_t bytes = (size_t)entries * (in_type == FORA_PROP_F64 ? 8 : 4);
-        if (int rc = prop_ensure(c, pb.d_vals, bytes, bwd ? "the upload of y" : "the upload of the scores")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_vals.get(), in, bytes, hipMemcpyHostToDevice));
-        in = pb.d_vals.get();
-    }
-    if (entries && bwd && !g_dev) {
-        const size_t bytes = (size_t)entries * (g_type == FORA_PROP_F64 ? 8 : 4);
-        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of grad")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_a.get(), grad, bytes, hipMemcpyHostToDevice));
-        grad = pb.d_a.get();
-    }
-    if (int rc = prop_ensure(c, pb.d_segs, lists.segs.size(), "the segment table")) return rc;
-    if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)lists.n_long, "the segment maxima and sums")) return rc;
-    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
-    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)entries, "a staged output")) return rc;
-    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)entries, "a staged output")) return rc;
-    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
-    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
-    c->tm.softmax_ms = 0;
-    uint32_t nan_rows = 0;
-    if (!lists.segs.empty()) {
-        HIPCHK(c, hipMemcpy(pb.d_segs.get(), lists.segs.data(), lists.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        const SoftmaxWork w{pb.d_segs.get(), pb.d_segs.get() + lists.n_short, lists.n_short, lists.n_long, pb.d_smax.get(), pb.d_smax.get() + lists.n_long, pb.d_smax_nan.get()};
-        const bool in64 = in_type == FORA_PROP_F64, g64 = g_type == FORA_PROP_F64;
-        if (!bwd) HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
-        {
-            EvSpan ev(c, EV_SOFTMAX);
-            if (!bwd) {
-                if (in64) softmax_launch<double>(c, w, in, scale, w32, w64);
-                else softmax_launch<float>(c, w, in, scale, w32, w64);
-            } else if (in64) {
-                if (g64) softmax_bwd_launch<double, double>(c, w, in, grad, scale, w32, w64);
-                else softmax_bwd_launch<double, float>(c, w, in, grad, scale, w32, w64);
-            } else {
-                if (g64) softmax_bwd_launch<float, double>(c, w, in, grad, scale, w32, w64);
-                else softmax_bwd_launch<float, float>(c, w, in, grad, scale, w32, w64);
-            }
-        }
-        if (!bwd) HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (entries && out32 && !o32_dev) HIPCHK(c, hipMemcpyAsync(out32, w32, (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
-    if (entries && out64 && !o64_dev) HIPCHK(c, hipMemcpyAsync(out64, w64, (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse softmax: ") + hipGetErrorString(err));
-    ev_collect(c);
-    if (st) {
-        st->entries = entries; st->segments = total; st->max_row = plan.max_row;
-        st->nan_rows = nan_rows; st->short_rows = lists.short_rows; st->long_rows = lists.long_rows;
-        st->in_on_device = in_dev ? 1 : 0; st->grad_on_device = g_dev ? 1 : 0;
-        st->softmax_ms = c->tm.softmax_ms;
-    }
-    return FORA_OK;
-}
-// the frame of the two calls (who: the call's name in messages; grad / g_type: the backward call's)
-int softmax_entry(fora_ctx *c, const char *who, const int64_t *row_ptr, int nq, const void *in, int in_type, bool bwd, const void *grad, int g_type, double scale,
-                  float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
-    if (!c) return FORA_E_ARG;
-    const std::string w = std::string(who) + ": ";
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, w + "negative nq or null row_ptr");
-    if (in_type != FORA_PROP_F32 && in_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
-    if (bwd && g_type != FORA_PROP_F32 && g_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, w + "an element type that is neither f32 nor f64");
-    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, w + "scale is not finite");
-    if (!out32 && !out64) return fail(c, FORA_E_ARG, w + "no output");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, w + "row_ptr is not the held result's");
-    if (cap < c->sp.entries) return fail(c, FORA_E_ARG, w + "cap is smaller than the held result");
-    if (c->sp.entries && (!in || (bwd && !grad))) return fail(c, FORA_E_ARG, w + "null input");
-    if (st) memset(st, 0, sizeof(*st));
-    if (nq == 0) return FORA_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return drop_pairs_unless_ok(c, softmax_impl(c, row_ptr, nq, c->sp.entries ? in : nullptr, in_type, bwd && c->sp.entries ? grad : nullptr, g_type, scale, out32, out64, st));
-}
-} // namespace
-} // extern "C++"
 
 int fora_hip_sparse_softmax(fora_ctx *c, const int64_t *row_ptr, int nq, const void *scores, int val_type, double scale,
                             float *out32, double *out64, uint64_t cap, fora_softmax_stats *st) {
@@ -3369,176 +3659,12 @@ int fora_hip_sparse_softmax_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, con
 
 // ---- ATTENTION (the contract of include/fora_hip.h): SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES per head in one call -- the
 // rows of at most "attn_short" entries in the fused kernel (fora_attn.h), the longer ones through the three steps' own kernels
-extern "C++" {
-namespace {
-template <bool QB, bool KB, bool VB, int V>
-void attn_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v, int64_t ldv,
-                 int d, int dv, uint32_t lg, double scale, uint64_t entries, float *o32, int64_t ld32, double *o64, int64_t ld64, float *y32, double *y64, uint32_t *nan_rows) {
-    const uint64_t units = nrow * (uint64_t)heads;
-    hipLaunchKernelGGL((k_attn_short<QB, KB, VB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
-                       (const int32_t *)c->sp.d_ids.get(), q, ldq, k, ldk, v, ldv, (uint32_t)d, (uint32_t)dv, lg, scale, entries, o32, ld32, o64, ld64, y32, y64, nan_rows);
-}
-template <bool QB, bool KB, typename... A>
-void attn_launch_v(bool v_bf16, uint32_t V, A... a) {
-    if (!v_bf16) switch (V) {
-        case 4: attn_launch<QB, KB, false, 4>(a...); break;
-        case 2: attn_launch<QB, KB, false, 2>(a...); break;
-        default: attn_launch<QB, KB, false, 1>(a...); break;
-    } else switch (V) {
-        case 8: attn_launch<QB, KB, true, 8>(a...); break;
-        case 4: attn_launch<QB, KB, true, 4>(a...); break;
-        default: attn_launch<QB, KB, true, 1>(a...); break;
-    }
-}
-inline const void *attn_cols(const void *m, uint64_t col, uint32_t elt) { return (const unsigned char *)m + col * elt; }
-
-int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
-                   const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
-                   float *y32, double *y64, fora_attn_stats *st) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
-    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16;
-    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4;
-    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
-    bool q_dev = false, k_dev = false, v_dev = false, o32_dev = false, o64_dev = false, y32_dev = false, y64_dev = false;
-    if (q) if (int rc = sparse_dest(c, q, q_dev)) return rc;
-    if (k) if (int rc = sparse_dest(c, k, k_dev)) return rc;
-    if (v) if (int rc = sparse_dest(c, v, v_dev)) return rc;
-    if (out32) if (int rc = sparse_dest(c, out32, o32_dev)) return rc;
-    if (out64) if (int rc = sparse_dest(c, out64, o64_dev)) return rc;
-    if (y32) if (int rc = sparse_dest(c, y32, y32_dev)) return rc;
-    if (y64) if (int rc = sparse_dest(c, y64, y64_dev)) return rc;
-    PropBufs &pb = c->pr;
-    // ---- the plan: the short rows' list; the longer rows' segments in chunks of prop_segs (0: a quarter of the free memory in
-    // partial sums at most), split once more for the softmax kernels by softmax_short
-    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
-    uint64_t long_segs = 0;
-    for (int i = 0; i < nq; i++) {
-        const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
-        if (len > cap) long_segs += (len + PROP_SEG - 1) / PROP_SEG;
-    }
-    size_t fr = 0, tot = 0;
-    if (long_segs && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, long_segs, (uint64_t)fr, dv);
-    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per);
-    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
-    const bool lng = !plan.lrows.empty();
-    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
-    if (entries && !q_dev) {
-        const size_t bytes = (size_t)((((uint64_t)nq - 1) * (uint64_t)ldq + wq) * q_elt);
-        if (int rc = prop_ensure(c, pb.d_a, bytes, "the upload of q")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_a.get(), q, bytes, hipMemcpyHostToDevice));
-        q = pb.d_a.get();
-    }
-    if (entries && !k_dev) {
-        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldk + wq) * k_elt);
-        if (int rc = prop_ensure(c, pb.d_feat, bytes, "the upload of k")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_feat.get(), k, bytes, hipMemcpyHostToDevice));
-        k = pb.d_feat.get();
-    }
-    if (entries && !v_dev) {
-        const size_t bytes = (size_t)(((n - 1) * (uint64_t)ldv + wv) * v_elt);
-        if (int rc = prop_ensure(c, pb.d_v, bytes, "the upload of v")) return rc;
-        HIPCHK(c, hipMemcpy(pb.d_v.get(), v, bytes, hipMemcpyHostToDevice));
-        v = pb.d_v.get();
-    }
-    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), at_lrows = at_sm + sm.segs.size(),
-                 nsegs = at_lrows + plan.lrows.size();
-    if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
-    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
-    if (lng) {
-        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
-        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)dv), "the partial sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment maxima and sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the scores of the longer rows")) return rc;
-        if (!y64) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)entries, "the y of the longer rows")) return rc;
-    }
-    if (out32 && !o32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)nq * (size_t)wv, "a staged output")) return rc;
-    if (out64 && !o64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)nq * (size_t)wv, "a staged output")) return rc;
-    if (y32 && !y32_dev) if (int rc = prop_ensure(c, pb.d_y32, (size_t)heads * (size_t)entries, "a staged output")) return rc;
-    if (y64 && !y64_dev) if (int rc = prop_ensure(c, pb.d_y64, (size_t)heads * (size_t)entries, "a staged output")) return rc;
-    PropSeg *const ds = pb.d_segs.get();
-    if (!plan.shrt.empty()) HIPCHK(c, hipMemcpy(ds + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-    if (lng) {
-        HIPCHK(c, hipMemcpy(ds + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(ds + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(ds + at_lrows, plan.lrows.data(), plan.lrows.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
-    }
-    float *const w32 = !out32 ? nullptr : o32_dev ? out32 : pb.d_out32.get();
-    double *const w64 = !out64 ? nullptr : o64_dev ? out64 : pb.d_out64.get();
-    const int64_t ld32 = o32_dev ? ldo : (int64_t)wv, ld64 = o64_dev ? ldo : (int64_t)wv;
-    float *const wy32 = !y32 ? nullptr : y32_dev ? y32 : pb.d_y32.get();
-    double *const wy64 = !y64 ? nullptr : y64_dev ? y64 : pb.d_y64.get();
-    uint32_t lg = 0;
-    while (lg < 6 && (1u << lg) < (uint32_t)d) lg++; // the smallest group that holds d columns, at most a wave
-    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
-    const uint32_t *const widths = v_bf16 ? widths_bf16 : widths_f32;
-    c->tm.attn_ms = 0;
-    uint32_t nan_rows = 0;
-    HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
-    {
-        EvSpan ev(c, EV_ATTN);
-        if (!plan.shrt.empty()) {
-            const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)v, ldv, dv, heads, v_elt, widths, 3);
-#define ATTN_ARGS v_bf16, V, c, (const PropSeg *)(ds + at_short), (uint64_t)plan.shrt.size(), heads, q, ldq, k, ldk, v, ldv, d, dv, lg, scale, entries, w32, ld32, w64, ld64, wy32, wy64, pb.d_smax_nan.get()
-            if (!q_bf16 && !k_bf16) attn_launch_v<false, false>(ATTN_ARGS);
-            else if (!q_bf16) attn_launch_v<false, true>(ATTN_ARGS);
-            else if (!k_bf16) attn_launch_v<true, false>(ATTN_ARGS);
-            else attn_launch_v<true, true>(ATTN_ARGS);
-#undef ATTN_ARGS
-        }
-        for (int h = 0; lng && h < heads; h++) { // the longer rows, one head at a time through the two per-entry buffers
-            const void *qh = attn_cols(q, (uint64_t)h * d, q_elt), *kh = attn_cols(k, (uint64_t)h * d, k_elt), *vh = attn_cols(v, (uint64_t)h * dv, v_elt);
-            double *const s64 = pb.d_attn_s.get();
-            double *const yh64 = wy64 ? wy64 + (uint64_t)h * entries : pb.d_attn_y.get();
-            float *const yh32 = wy32 ? wy32 + (uint64_t)h * entries : nullptr;
-            const PropSeg *segs = ds + at_lsegs;
-            const uint64_t nseg = plan.lng.segs.size();
-            if (!q_bf16 && !k_bf16) sddmm_launch<false, false>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
-            else if (!q_bf16) sddmm_launch<false, true>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
-            else if (!k_bf16) sddmm_launch<true, false>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
-            else sddmm_launch<true, true>(c, segs, nseg, qh, ldq, kh, ldk, d, lg, nullptr, s64);
-            const SoftmaxWork w{ds + at_sm, ds + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, pb.d_smax_nan.get()};
-            softmax_launch<double>(c, w, s64, scale, yh32, yh64);
-            const PropSide sd{row_ptr, nq, n, c->sp.d_ids.get(), nullptr, nullptr, false, yh64, true, nullptr};
-            const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, 3);
-            float *const oh32 = w32 ? w32 + (uint64_t)h * dv : nullptr;
-            double *const oh64 = w64 ? w64 + (uint64_t)h * dv : nullptr;
-            prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, v_bf16, g, vh, ldv, dv, nullptr, oh32, ld32, oh64, ld64, false);
-            const dim3 grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(plan.lrows.size(), 65535));
-            hipLaunchKernelGGL(k_attn_nan_rows, grid, dim3(BLOCK), 0, c->stream, (const PropSeg *)(ds + at_lrows), (uint64_t)plan.lrows.size(), (const double *)yh64,
-                               (uint32_t)dv, oh32, ld32, oh64, ld64);
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(&nan_rows, pb.d_smax_nan.get(), sizeof(nan_rows), hipMemcpyDeviceToHost, c->stream));
-    if (out32 && !o32_dev) HIPCHK(c, hipMemcpy2DAsync(out32, (size_t)ldo * 4, w32, (size_t)wv * 4, (size_t)wv * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    if (out64 && !o64_dev) HIPCHK(c, hipMemcpy2DAsync(out64, (size_t)ldo * 8, w64, (size_t)wv * 8, (size_t)wv * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    if (entries && y32 && !y32_dev) HIPCHK(c, hipMemcpyAsync(y32, wy32, (size_t)heads * (size_t)entries * 4, hipMemcpyDeviceToHost, c->stream));
-    if (entries && y64 && !y64_dev) HIPCHK(c, hipMemcpyAsync(y64, wy64, (size_t)heads * (size_t)entries * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse attention: ") + hipGetErrorString(err));
-    ev_collect(c);
-    if (st) {
-        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
-        st->nan_rows = nan_rows; st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
-        st->q_on_device = q_dev ? 1 : 0; st->k_on_device = k_dev ? 1 : 0; st->v_on_device = v_dev ? 1 : 0;
-        st->attn_ms = c->tm.attn_ms;
-    }
-    return FORA_OK;
-}
-} // namespace
-} // extern "C++"
 
 int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
                               const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
                               float *y32, double *y64, uint64_t ycap, fora_attn_stats *st) {
-    if (!c) return FORA_E_ARG;
+    if (int rc = held_call_begin(c, "sparse attention", row_ptr, nq)) return rc;
     const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, "sparse attention: negative nq or null row_ptr");
     if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type)) return fail(c, FORA_E_ARG, "sparse attention: unknown q_type, k_type or v_type");
     if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: d or dv outside 1 .. 65536");
     if (heads < 1 || (int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: heads < 1, or heads * d or heads * dv over 65536");
@@ -3546,7 +3672,6 @@ int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const
     if (ldv < (int64_t)heads * dv || ldo < (int64_t)heads * dv) return fail(c, FORA_E_ARG, "sparse attention: ldv or ldo smaller than heads * dv");
     if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, "sparse attention: scale is not finite");
     if (!out32 && !out64) return fail(c, FORA_E_ARG, "sparse attention: no output");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, "sparse attention: row_ptr is not the held result's");
     if ((y32 || y64) && ycap < (uint64_t)heads * c->sp.entries) return fail(c, FORA_E_ARG, "sparse attention: ycap is smaller than heads * the held entries");
     if (c->sp.entries && (!q || !k || !v)) return fail(c, FORA_E_ARG, "sparse attention: null q, k or v");
     if (st) memset(st, 0, sizeof(*st));
@@ -3558,269 +3683,13 @@ int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const
 
 // ---- ATTENTION, BACKWARD (the contract of include/fora_hip.h): dq, dk and dv of all heads in one call -- the rows and the columns
 // of at most "attn_short" entries in the fused kernels (fora_attn_bwd.h), the longer ones through the chained calls' own kernels
-extern "C++" {
-namespace {
-template <bool GB, bool VB, bool KB, int V>
-void attn_bwd_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *g, int64_t ldg, const void *v, int64_t ldv, const void *k, int64_t ldk,
-                     int d, int dv, uint32_t lgv, double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *o32, int64_t ld32, double *o64, int64_t ld64) {
-    const uint64_t units = nrow * (uint64_t)heads;
-    hipLaunchKernelGGL((k_attn_bwd_short<GB, VB, KB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
-                       (const int32_t *)c->sp.d_ids.get(), g, ldg, v, ldv, k, ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, entries, y, y_f64, ds, o32, ld32, o64, ld64);
-}
-template <bool GB, bool VB, typename... A>
-void attn_bwd_launch_k(bool k_bf16, uint32_t V, A... a) {
-    if (!k_bf16) switch (V) {
-        case 4: attn_bwd_launch<GB, VB, false, 4>(a...); break;
-        case 2: attn_bwd_launch<GB, VB, false, 2>(a...); break;
-        default: attn_bwd_launch<GB, VB, false, 1>(a...); break;
-    } else switch (V) {
-        case 8: attn_bwd_launch<GB, VB, true, 8>(a...); break;
-        case 4: attn_bwd_launch<GB, VB, true, 4>(a...); break;
-        default: attn_bwd_launch<GB, VB, true, 1>(a...); break;
-    }
-}
-template <bool BF16, int V>
-void attn_cols_launch(fora_ctx *c, const PropGeom &g, const PropSeg *cols, uint64_t ncol, int heads, const void *values, bool val64, uint64_t entries,
-                      const void *feat, int64_t ldf, int w, float *o32, int64_t ld32, double *o64, int64_t ld64) {
-    const uint64_t units = ncol * (uint64_t)heads, per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
-    const dim3 grid((unsigned)((units + per_wg - 1) / per_wg), g.tiles);
-    const int32_t *rows = c->pt.d_rows.get();
-    const int64_t *pos = c->pt.d_pos.get();
-    if (val64) hipLaunchKernelGGL((k_attn_cols<BF16, V, true>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
-    else hipLaunchKernelGGL((k_attn_cols<BF16, V, false>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
-}
-// +0.0 to an n x width output: one clear where the rows lie back to back, a clear per row band otherwise (a pitch wider than
-// the output: what lies between the rows is the caller's)
-template <typename T> hipError_t attn_zero(fora_ctx *c, T *out, int64_t ld, uint64_t rows, uint64_t width) {
-    if (!out || !rows) return hipSuccess;
-    if ((uint64_t)ld == width) return hipMemsetAsync(out, 0, rows * width * sizeof(T), c->stream);
-    return hipMemset2DAsync(out, (size_t)ld * sizeof(T), 0, width * sizeof(T), rows, c->stream);
-}
-// one gradient of the column side: out[v][h * w + c] = the sum over column v's entries p of values[h * entries + pos[p]] *
-// feat[rows[p]][h * w + c].  The outputs zeroed (the empty columns), the short columns of all heads in one launch, the longer
-// ones head by head through PROPAGATE's kernels over the cached plan.
-int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, bool val64, const void *feat, bool bf16, int64_t ldf, int w,
-                  float *o32, int64_t ld32, double *o64, int64_t ld64) {
-    const PropTBufs &t = c->pt;
-    const AttnColPlan &cp = t.cols.plan;
-    const uint64_t n = (uint64_t)c->g.n;
-    const uint32_t elt = bf16 ? 2 : 4;
-    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
-    const uint32_t *const widths = bf16 ? widths_bf16 : widths_f32;
-    HIPCHK(c, attn_zero(c, o32, ld32, n, (uint64_t)heads * (uint64_t)w));
-    HIPCHK(c, attn_zero(c, o64, ld64, n, (uint64_t)heads * (uint64_t)w));
-    if (!cp.shrt.empty()) {
-        const PropGeom g = attn_cols_geom(attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, widths, 3), w);
-#define COLS_ARGS c, g, (const PropSeg *)t.cols.d_short.get(), (uint64_t)cp.shrt.size(), heads, values, val64, entries, feat, ldf, w, o32, ld32, o64, ld64
-        if (!bf16) switch (g.V) {
-            case 4: attn_cols_launch<false, 4>(COLS_ARGS); break;
-            case 2: attn_cols_launch<false, 2>(COLS_ARGS); break;
-            default: attn_cols_launch<false, 1>(COLS_ARGS); break;
-        } else switch (g.V) {
-            case 8: attn_cols_launch<true, 8>(COLS_ARGS); break;
-            case 4: attn_cols_launch<true, 4>(COLS_ARGS); break;
-            default: attn_cols_launch<true, 1>(COLS_ARGS); break;
-        }
-#undef COLS_ARGS
-    }
-    for (int h = 0; cp.long_cols && h < heads; h++) {
-        const void *fh = attn_cols(feat, (uint64_t)h * w, elt);
-        const void *vh = (const unsigned char *)values + (uint64_t)h * entries * (val64 ? 8 : 4);
-        const PropSide sd{t.h_col_ptr.data(), (int)n, (uint64_t)t.nq, t.d_rows.get(), nullptr, nullptr, false, vh, val64, t.d_pos.get()};
-        const PropGeom g = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, widths, 3);
-        prop_launch_chunks(c, cp.lng, t.cols.d_lsegs.get(), t.cols.d_lrecs.get(), sd, bf16, g, fh, ldf, w, nullptr, o32 ? o32 + (uint64_t)h * w : nullptr, ld32,
-                           o64 ? o64 + (uint64_t)h * w : nullptr, ld64, false);
-    }
-    return FORA_OK;
-}
-
-int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
-                       const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type,
-                       int d, int dv, int heads, double scale, const fora_attn_grads &gr, fora_attn_bwd_stats *st) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
-    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16, g_bf16 = g_type == FORA_PROP_BF16;
-    const bool y_f64 = y_type == FORA_PROP_F64;
-    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4, g_elt = g_bf16 ? 2 : 4, y_elt = y_f64 ? 8 : 4;
-    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q, k, dq and dk; of v, g and dv
-    const bool want_dq = gr.dq32 || gr.dq64, want_dk = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64;
-    const bool want_rows = want_dq || want_dk, want_cols = want_dk || want_dv; // dy and ds; the transposition
-    bool q_dev = false, k_dev = false, v_dev = false, g_dev = false, y_dev = false;
-    bool dq32_dev = false, dq64_dev = false, dk32_dev = false, dk64_dev = false, dv32_dev = false, dv64_dev = false;
-    if (q) if (int rc = sparse_dest(c, q, q_dev)) return rc;
-    if (k) if (int rc = sparse_dest(c, k, k_dev)) return rc;
-    if (v) if (int rc = sparse_dest(c, v, v_dev)) return rc;
-    if (g) if (int rc = sparse_dest(c, g, g_dev)) return rc;
-    if (y) if (int rc = sparse_dest(c, y, y_dev)) return rc;
-    if (gr.dq32) if (int rc = sparse_dest(c, gr.dq32, dq32_dev)) return rc;
-    if (gr.dq64) if (int rc = sparse_dest(c, gr.dq64, dq64_dev)) return rc;
-    if (gr.dk32) if (int rc = sparse_dest(c, gr.dk32, dk32_dev)) return rc;
-    if (gr.dk64) if (int rc = sparse_dest(c, gr.dk64, dk64_dev)) return rc;
-    if (gr.dv32) if (int rc = sparse_dest(c, gr.dv32, dv32_dev)) return rc;
-    if (gr.dv64) if (int rc = sparse_dest(c, gr.dv64, dv64_dev)) return rc;
-    // ---- the transposition and its places, as the first transposed product with values would build them
-    bool built_now = false;
-    if (want_cols) {
-        if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
-        if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
-    }
-    PropBufs &pb = c->pr;
-    PropTBufs &t = c->pt;
-    // ---- the plans.  Rows: as the forward call's, the longer rows' product d columns wide.  Columns: from the cache when "attn_short"
-    // and the resolved chunk size are the ones it was made under
-    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
-    uint64_t long_row_segs = 0, long_col_segs = 0;
-    for (int i = 0; want_rows && i < nq; i++) {
-        const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
-        if (len > cap) long_row_segs += (len + PROP_SEG - 1) / PROP_SEG;
-    }
-    if (want_cols) long_col_segs = t.cols.valid && t.cols.short_cap == cap ? t.cols.long_segs : attn_long_col_segs(t.h_col_ptr.data(), (int64_t)n, cap);
-    size_t fr = 0, tot = 0;
-    if ((long_row_segs || long_col_segs) && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const int wmax = std::max(d, dv);
-    const uint64_t per_rows = prop_chunk_segs(c->opt_.prop_segs, long_row_segs, (uint64_t)fr, d);
-    const uint64_t per_cols = prop_chunk_segs(c->opt_.prop_segs, long_col_segs, (uint64_t)fr, wmax);
-    const AttnPlan plan = attn_plan(row_ptr, nq, cap, per_rows);
-    const SoftmaxLists sm = softmax_lists(plan.lng.segs, row_ptr, softmax_short_cap(c->opt_.softmax_short));
-    const bool lng_rows = want_rows && !plan.lrows.empty();
-    const bool plan_cached = want_cols && t.cols.valid && t.cols.short_cap == cap && t.cols.chunk_segs == per_cols;
-    if (want_cols && !plan_cached) {
-        PropTBufs::ColPlan nc; // moved into the transposition when complete
-        nc.short_cap = cap; nc.chunk_segs = per_cols; nc.long_segs = long_col_segs;
-        nc.plan = attn_col_plan(t.h_col_ptr.data(), (int64_t)n, cap, per_cols);
-        if (int rc = prop_ensure(c, nc.d_short, nc.plan.shrt.size(), "the column table")) return rc;
-        if (int rc = prop_ensure(c, nc.d_lsegs, nc.plan.lng.segs.size(), "the column table")) return rc;
-        if (int rc = prop_ensure(c, nc.d_lrecs, nc.plan.lng.recs.size(), "the column table")) return rc;
-        if (!nc.plan.shrt.empty()) HIPCHK(c, hipMemcpy(nc.d_short.get(), nc.plan.shrt.data(), nc.plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        if (!nc.plan.lng.segs.empty()) HIPCHK(c, hipMemcpy(nc.d_lsegs.get(), nc.plan.lng.segs.data(), nc.plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        if (!nc.plan.lng.recs.empty()) HIPCHK(c, hipMemcpy(nc.d_lrecs.get(), nc.plan.lng.recs.data(), nc.plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
-        nc.valid = true;
-        t.cols = std::move(nc);
-    }
-    const bool lng_cols = want_cols && t.cols.plan.long_cols != 0;
-    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
-    const auto upload = [&](const void *&m, bool on_dev, DevBuf<unsigned char> &buf, size_t bytes, const char *what) -> int {
-        if (!entries || on_dev) return FORA_OK;
-        if (int rc = prop_ensure(c, buf, bytes, what)) return rc;
-        HIPCHK(c, hipMemcpy(buf.get(), m, bytes, hipMemcpyHostToDevice));
-        m = buf.get();
-        return FORA_OK;
-    };
-    if (want_dk) if (int rc = upload(q, q_dev, pb.d_a, (size_t)((((uint64_t)nq - 1) * (uint64_t)ldq + wq) * q_elt), "the upload of q")) return rc;
-    if (want_dq) if (int rc = upload(k, k_dev, pb.d_feat, (size_t)(((n - 1) * (uint64_t)ldk + wq) * k_elt), "the upload of k")) return rc;
-    if (want_rows) if (int rc = upload(v, v_dev, pb.d_v, (size_t)(((n - 1) * (uint64_t)ldv + wv) * v_elt), "the upload of v")) return rc;
-    if (int rc = upload(g, g_dev, pb.d_g, (size_t)((((uint64_t)nq - 1) * (uint64_t)ldg + wv) * g_elt), "the upload of g")) return rc;
-    if (int rc = upload(y, y_dev, pb.d_vals, (size_t)heads * (size_t)entries * y_elt, "the upload of y")) return rc;
-    const size_t at_short = 0, at_lsegs = plan.shrt.size(), at_sm = at_lsegs + plan.lng.segs.size(), nsegs = at_sm + sm.segs.size();
-    if (want_rows) if (int rc = prop_ensure(c, pb.d_segs, nsegs, "the segment table")) return rc;
-    if (lng_rows) {
-        if (int rc = prop_ensure(c, pb.d_recs, plan.lng.recs.size(), "the segment table")) return rc;
-        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)sm.n_long, "the segment sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)entries, "the dy of the longer rows")) return rc;
-    }
-    if (lng_rows || lng_cols) {
-        const uint64_t part = std::max(lng_rows && want_dq ? per_rows * (uint64_t)d : 0, lng_cols ? per_cols * (uint64_t)wmax : 0);
-        if (int rc = prop_ensure(c, pb.d_part, (size_t)part, "the partial sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)wmax, "the partial sums")) return rc;
-        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
-    }
-    if (want_dk || lng_rows) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)entries, "ds")) return rc;
-    if (gr.dq32 && !dq32_dev) if (int rc = prop_ensure(c, pb.d_out32, (size_t)nq * (size_t)wq, "a staged output")) return rc;
-    if (gr.dq64 && !dq64_dev) if (int rc = prop_ensure(c, pb.d_out64, (size_t)nq * (size_t)wq, "a staged output")) return rc;
-    if (gr.dk32 && !dk32_dev) if (int rc = prop_ensure(c, pb.d_dk32, (size_t)n * (size_t)wq, "a staged output")) return rc;
-    if (gr.dk64 && !dk64_dev) if (int rc = prop_ensure(c, pb.d_dk64, (size_t)n * (size_t)wq, "a staged output")) return rc;
-    if (gr.dv32 && !dv32_dev) if (int rc = prop_ensure(c, pb.d_dv32, (size_t)n * (size_t)wv, "a staged output")) return rc;
-    if (gr.dv64 && !dv64_dev) if (int rc = prop_ensure(c, pb.d_dv64, (size_t)n * (size_t)wv, "a staged output")) return rc;
-    PropSeg *const dsg = pb.d_segs.get();
-    if (want_rows && !plan.shrt.empty()) HIPCHK(c, hipMemcpy(dsg + at_short, plan.shrt.data(), plan.shrt.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-    if (lng_rows) {
-        HIPCHK(c, hipMemcpy(dsg + at_lsegs, plan.lng.segs.data(), plan.lng.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(dsg + at_sm, sm.segs.data(), sm.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
-    }
-    float *const wdq32 = !gr.dq32 ? nullptr : dq32_dev ? gr.dq32 : pb.d_out32.get();
-    double *const wdq64 = !gr.dq64 ? nullptr : dq64_dev ? gr.dq64 : pb.d_out64.get();
-    float *const wdk32 = !gr.dk32 ? nullptr : dk32_dev ? gr.dk32 : pb.d_dk32.get();
-    double *const wdk64 = !gr.dk64 ? nullptr : dk64_dev ? gr.dk64 : pb.d_dk64.get();
-    float *const wdv32 = !gr.dv32 ? nullptr : dv32_dev ? gr.dv32 : pb.d_dv32.get();
-    double *const wdv64 = !gr.dv64 ? nullptr : dv64_dev ? gr.dv64 : pb.d_dv64.get();
-    const int64_t ldq32 = dq32_dev ? gr.lddq : (int64_t)wq, ldq64 = dq64_dev ? gr.lddq : (int64_t)wq;
-    const int64_t ldk32 = dk32_dev ? gr.lddk : (int64_t)wq, ldk64 = dk64_dev ? gr.lddk : (int64_t)wq;
-    const int64_t ldv32 = dv32_dev ? gr.lddv : (int64_t)wv, ldv64 = dv64_dev ? gr.lddv : (int64_t)wv;
-    double *const ds = want_dk || lng_rows ? pb.d_attn_ds.get() : nullptr;
-    uint32_t lgv = 0;
-    while (lgv < 6 && (1u << lgv) < (uint32_t)dv) lgv++; // the smallest group that holds the dv columns of dy, at most a wave
-    static const uint32_t widths_f32[] = {4, 2, 1}, widths_bf16[] = {8, 4, 1};
-    const uint32_t *const widths_k = k_bf16 ? widths_bf16 : widths_f32;
-    c->tm.attn_ms = 0;
-    {
-        EvSpan ev(c, EV_ATTN);
-        if (want_rows && !plan.shrt.empty()) { // dy, ds and dq of the short rows, all heads
-            const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)k, ldk, d, heads, k_elt, widths_k, 3);
-#define BWD_ARGS k_bf16, V, c, (const PropSeg *)(dsg + at_short), (uint64_t)plan.shrt.size(), heads, g, ldg, v, ldv, k, ldk, d, dv, lgv, scale, entries, y, y_f64, want_dk ? ds : (double *)nullptr, wdq32, ldq32, wdq64, ldq64
-            if (!g_bf16 && !v_bf16) attn_bwd_launch_k<false, false>(BWD_ARGS);
-            else if (!g_bf16) attn_bwd_launch_k<false, true>(BWD_ARGS);
-            else if (!v_bf16) attn_bwd_launch_k<true, false>(BWD_ARGS);
-            else attn_bwd_launch_k<true, true>(BWD_ARGS);
-#undef BWD_ARGS
-        }
-        for (int h = 0; lng_rows && h < heads; h++) { // the longer rows, one head at a time: dy, ds into the head's slice, dq
-            const void *gh = attn_cols(g, (uint64_t)h * dv, g_elt), *vh = attn_cols(v, (uint64_t)h * dv, v_elt), *kh = attn_cols(k, (uint64_t)h * d, k_elt);
-            const void *yh = (const unsigned char *)y + (uint64_t)h * entries * y_elt;
-            double *const dy64 = pb.d_attn_s.get(), *const dsh = ds + (uint64_t)h * entries;
-            const PropSeg *segs = dsg + at_lsegs;
-            const uint64_t nseg = plan.lng.segs.size();
-            if (!g_bf16 && !v_bf16) sddmm_launch<false, false>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
-            else if (!g_bf16) sddmm_launch<false, true>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
-            else if (!v_bf16) sddmm_launch<true, false>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
-            else sddmm_launch<true, true>(c, segs, nseg, gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
-            const SoftmaxWork w{dsg + at_sm, dsg + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, nullptr};
-            if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, scale, nullptr, dsh);
-            else softmax_bwd_launch<float, double>(c, w, yh, dy64, scale, nullptr, dsh);
-            if (want_dq) {
-                const PropSide sd{row_ptr, nq, n, c->sp.d_ids.get(), nullptr, nullptr, false, dsh, true, nullptr};
-                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, 3);
-                prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, k_bf16, gm, kh, ldk, d, nullptr, wdq32 ? wdq32 + (uint64_t)h * d : nullptr, ldq32,
-                                   wdq64 ? wdq64 + (uint64_t)h * d : nullptr, ldq64, false);
-            }
-        }
-        if (want_dk) if (int rc = attn_bwd_cols(c, heads, entries, ds, true, q, q_bf16, ldq, d, wdk32, ldk32, wdk64, ldk64)) return rc;
-        if (want_dv) if (int rc = attn_bwd_cols(c, heads, entries, y, y_f64, g, g_bf16, ldg, dv, wdv32, ldv32, wdv64, ldv64)) return rc;
-    }
-    if (gr.dq32 && !dq32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dq32, (size_t)gr.lddq * 4, wdq32, (size_t)wq * 4, (size_t)wq * 4, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    if (gr.dq64 && !dq64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dq64, (size_t)gr.lddq * 8, wdq64, (size_t)wq * 8, (size_t)wq * 8, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    if (gr.dk32 && !dk32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dk32, (size_t)gr.lddk * 4, wdk32, (size_t)wq * 4, (size_t)wq * 4, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (gr.dk64 && !dk64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dk64, (size_t)gr.lddk * 8, wdk64, (size_t)wq * 8, (size_t)wq * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (gr.dv32 && !dv32_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dv32, (size_t)gr.lddv * 4, wdv32, (size_t)wv * 4, (size_t)wv * 4, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (gr.dv64 && !dv64_dev) HIPCHK(c, hipMemcpy2DAsync(gr.dv64, (size_t)gr.lddv * 8, wdv64, (size_t)wv * 8, (size_t)wv * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse attention_bwd: ") + hipGetErrorString(err));
-    ev_collect(c);
-    if (st) {
-        st->entries = entries; st->segments = plan.segments; st->max_row = plan.max_row;
-        st->short_rows = plan.short_rows; st->long_rows = plan.long_rows;
-        if (want_cols) {
-            const AttnColPlan &cp = t.cols.plan;
-            st->columns = cp.columns; st->max_col = cp.max_col; st->short_cols = cp.short_cols; st->long_cols = cp.long_cols;
-        }
-        st->built = built_now ? 1 : 0; st->plan_cached = plan_cached ? 1 : 0;
-        st->q_on_device = q_dev ? 1 : 0; st->k_on_device = k_dev ? 1 : 0; st->v_on_device = v_dev ? 1 : 0; st->g_on_device = g_dev ? 1 : 0;
-        st->y_on_device = y_dev ? 1 : 0;
-        st->transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0; st->attn_ms = c->tm.attn_ms;
-    }
-    return FORA_OK;
-}
-} // namespace
-} // extern "C++"
 
 int fora_hip_sparse_attention_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk,
                                   const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap,
                                   int d, int dv, int heads, double scale, const fora_attn_grads *grads, fora_attn_bwd_stats *st) {
-    if (!c) return FORA_E_ARG;
+    if (int rc = held_call_begin(c, "sparse attention_bwd", row_ptr, nq)) return rc;
     const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
     const char *who = "sparse attention_bwd: ";
-    if (!c->sp.valid) return fail(c, FORA_E_ARG, "no sparse result is held");
-    if (nq < 0 || !row_ptr) return fail(c, FORA_E_ARG, std::string(who) + "negative nq or null row_ptr");
     if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type) || !type_ok(g_type)) return fail(c, FORA_E_ARG, std::string(who) + "unknown q_type, k_type, v_type or g_type");
     if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, std::string(who) + "y_type is neither f32 nor f64");
     if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, std::string(who) + "d or dv outside 1 .. 65536");
@@ -3833,7 +3702,6 @@ int fora_hip_sparse_attention_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, c
     if (!want_dq && !want_dk && !want_dv) return fail(c, FORA_E_ARG, std::string(who) + "no output");
     if ((want_dq && grads->lddq < (int64_t)heads * d) || (want_dk && grads->lddk < (int64_t)heads * d) || (want_dv && grads->lddv < (int64_t)heads * dv))
         return fail(c, FORA_E_ARG, std::string(who) + "lddq or lddk smaller than heads * d, or lddv smaller than heads * dv");
-    if (!prop_row_ptr_ok(row_ptr, nq, c->sp.entries)) return fail(c, FORA_E_ARG, std::string(who) + "row_ptr is not the held result's");
     if (ycap < (uint64_t)heads * c->sp.entries) return fail(c, FORA_E_ARG, std::string(who) + "ycap is smaller than heads * the held entries");
     if (c->sp.entries && (!q || !k || !v || !g || !y)) return fail(c, FORA_E_ARG, std::string(who) + "null q, k, v, g or y");
     if (st) memset(st, 0, sizeof(*st));
@@ -3863,10 +3731,7 @@ int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq,
     if (e && rows) HIPCHK(c, hipMemcpyAsync(rows, t.d_rows.get(), e * 4, hipMemcpyDefault, c->stream));
     if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, t.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
     if (e && vals) if (int rc = fetch_vals(c, t.d_fix.get(), e, vals, vals_on_device)) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse transpose fetch: ") + hipGetErrorString(err));
-    return FORA_OK;
+    return held_call_end(c, "sparse transpose fetch", false);
 }
 
 // ---- sweep cut: local clustering over the rows of a query (the SWEEP CUT contract of include/fora_hip.h)

@@ -114,5 +114,30 @@ inline PropGeom prop_geom(uint64_t feat_addr, int64_t ldf, int d, uint32_t elt_b
     g.segs_per_wave = 64 / g.G;
     return g;
 }
+// the `widths` of an element type, PROP_NWIDTHS of them: 16 bytes a lane at most
+constexpr int PROP_NWIDTHS = 3;
+inline const uint32_t *prop_widths(bool bf16) {
+    static const uint32_t f32[PROP_NWIDTHS] = {4, 2, 1}, b16[PROP_NWIDTHS] = {8, 4, 1};
+    return bf16 ? b16 : f32;
+}
+// the group exponent: the smallest lg <= 6 with 2^lg >= d -- the lanes that share a d-column dot product, at most a wave
+inline uint32_t prop_group_lg(uint32_t d) {
+    uint32_t lg = 0;
+    while (lg < 6 && (1u << lg) < d) lg++;
+    return lg;
+}
+// the bytes of a caller's operand from its first element to its last: a matrix of `rows` rows of `width` elements at pitch
+// ld >= width (nothing follows the last row), a vector of `count` elements; no rows are no bytes
+inline uint64_t prop_matrix_bytes(uint64_t rows, uint64_t ld, uint64_t width, uint32_t elt_bytes) { return rows ? ((rows - 1) * ld + width) * elt_bytes : 0; }
+inline uint64_t prop_vector_bytes(uint64_t count, uint32_t elt_bytes) { return count * elt_bytes; }
+// the segments of the rows longer than cap: the ones ATTENTION leaves to the three steps' kernels (fora_attn_plan.h)
+inline uint64_t prop_long_segments(const int64_t *row_ptr, int nq, uint32_t cap) {
+    uint64_t s = 0;
+    for (int i = 0; i < nq; i++) {
+        const uint64_t len = (uint64_t)(row_ptr[i + 1] - row_ptr[i]);
+        if (len > cap) s += (len + PROP_SEG - 1) / PROP_SEG;
+    }
+    return s;
+}
 
 } // namespace fora

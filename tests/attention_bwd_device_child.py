@@ -1,6 +1,7 @@
 """Child process of tests/test_attention_bwd_gpu.py::test_device_operands_and_outputs: Engine.sparse_attention_bwd with the
 operands and the outputs in device memory.  torch is imported first, so that the library binds to the HIP runtime torch brought
 along and a tensor's data_ptr() is device memory the library knows.  The process starts fresh and ends here."""
+import ctypes as C
 import os
 import sys
 
@@ -24,6 +25,55 @@ SEED = 0x464F5241
 def bits(x):
     a = x.detach().cpu().contiguous().numpy()
     return a.view({4: np.uint32, 8: np.uint64}[a.itemsize])
+
+
+def ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr() if torch.is_tensor(x) else x.ctypes.data)
+
+
+def raw_attention_bwd(engine, rp, nq, q, k, v, g, y, d, dv, heads, outs, lds):
+    """fora_hip_sparse_attention_bwd itself, every pointer as given (f32 operands, rows back to back, an f64 y); outs: dq32, dq64,
+    dk32, dk64, dv32, dv64; lds: lddq, lddk, lddv; the stats"""
+    gr, st = capi.AttnGrads(), capi.AttnBwdStats()
+    for name, o in zip(("dq32", "dq64", "dk32", "dk64", "dv32", "dv64"), outs):
+        setattr(gr, name, None if o is None else ptr(o).value)
+    gr.lddq, gr.lddk, gr.lddv = lds
+    f32 = C.c_int(capi.PROP_F32)
+    engine._chk(engine._lib.fora_hip_sparse_attention_bwd(engine._ctx, ptr(rp), C.c_int(nq), ptr(q), f32, C.c_int64(heads * d), ptr(k), f32, C.c_int64(heads * d),
+                                                          ptr(v), f32, C.c_int64(heads * dv), ptr(g), f32, C.c_int64(heads * dv), ptr(y), C.c_int(capi.PROP_F64),
+                                                          C.c_uint64(y.shape[0]), C.c_int(d), C.c_int(dv), C.c_int(heads), C.c_double(0.37), C.byref(gr), C.byref(st)))
+    return st.as_dict()
+
+
+def mixed_homes(engine, dev, row_ptr, nq, n, e, rng):
+    """The C ABI takes each pointer on its own (the binding refuses what follows): g and y on the device, q, k and v on the host;
+    dq32 and dv32 host arrays, dk64 and dv64 device tensors, every pitch padded -- the bits of the all-host call, the padding kept"""
+    heads, d, dv, fill = 2, 3, 2, -3.0
+    wq, wv = heads * d, heads * dv
+    lds = (wq + 3, wq + 2, wv + 3)
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    Q, K = ar.scores_operands(rng, nq, n, d, heads)
+    V = rng.standard_normal((n, wv)).astype(np.float32)
+    G = rng.standard_normal((nq, wv)).astype(np.float32)
+    y = np.ascontiguousarray(engine.sparse_attention(row_ptr, Q, K, V, heads=heads, scale=0.37, want32=False, want64=True, want_y64=True)[3].reshape(heads * e))
+    Gd, yd = torch.from_numpy(G).to(dev), torch.from_numpy(y).to(dev)
+    host = lambda rows, ld, dt: np.full((rows, ld), fill, dt)
+    for short in (256, 0):
+        engine.set_option("attn_short", short)
+        hq32, hk64, hv32, hv64 = host(nq, lds[0], np.float32), host(n, lds[1], np.float64), host(n, lds[2], np.float32), host(n, lds[2], np.float64)
+        hst = raw_attention_bwd(engine, rp, nq, Q, K, V, G, y, d, dv, heads, (hq32, None, None, hk64, hv32, hv64), lds)
+        assert all(hst[x + "_on_device"] == 0 for x in "qkvgy") and hst["long_rows"] > 0 and hst["long_cols"] > 0, hst
+        assert (hst["short_rows"] > 0 and hst["short_cols"] > 0) == (short > 0), hst
+        mq32, mv32 = host(nq, lds[0], np.float32), host(n, lds[2], np.float32)
+        mk64 = torch.full((n, lds[1]), fill, dtype=torch.float64, device=dev)
+        mv64 = torch.full((n, lds[2]), fill, dtype=torch.float64, device=dev)
+        st = raw_attention_bwd(engine, rp, nq, Q, K, V, Gd, yd, d, dv, heads, (mq32, None, None, mk64, mv32, mv64), lds)
+        assert st["q_on_device"] == st["k_on_device"] == st["v_on_device"] == 0 and st["g_on_device"] == st["y_on_device"] == 1, st
+        for got, want, w in ((mq32, hq32, wq), (mk64.cpu().numpy(), hk64, wq), (mv32, hv32, wv), (mv64.cpu().numpy(), hv64, wv)):
+            assert (bits(torch.from_numpy(got[:, :w].copy())) == bits(torch.from_numpy(want[:, :w].copy()))).all(), short
+            assert np.isfinite(want[:, :w]).all() and (want[:, :w] != 0).any()
+            assert (got[:, w:] == fill).all() and (want[:, w:] == fill).all(), short
+    engine.set_option("attn_short", 256)
 
 
 def main():
@@ -89,6 +139,7 @@ def main():
                         assert (bits(t64[:, 2:2 + w]) == want[i].view(np.uint64)).all() and (bits(t32[:, 2:2 + w]) == want[i].astype(np.float32).view(np.uint32)).all()
                         assert (t32[:, :2] == -3.0).all() and (t32[:, 2 + w:] == -3.0).all() and (t64[:, :2] == -3.0).all() and (t64[:, 2 + w:] == -3.0).all()
     engine.set_option("attn_short", 256)
+    mixed_homes(engine, dev, row_ptr, nq, n, e, rng)
     # mixed homes are refused by the binding
     try:
         engine.sparse_attention_bwd(row_ptr, Qd, K0, Vd, Gd, yd, heads=heads)

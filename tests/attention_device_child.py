@@ -1,6 +1,7 @@
 """Child process of tests/test_attention_gpu.py::test_device_operands_and_outputs: Engine.sparse_attention with the operands and
 the outputs in device memory.  torch is imported first, so that the library binds to the HIP runtime torch brought along and a
 tensor's data_ptr() is device memory the library knows.  The process starts fresh and ends here."""
+import ctypes as C
 import os
 import sys
 
@@ -24,6 +25,45 @@ SEED = 0x464F5241
 def bits(x):
     a = x.detach().cpu().numpy()
     return a.view({4: np.uint32, 8: np.uint64}[a.itemsize])
+
+
+def ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr() if torch.is_tensor(x) else x.ctypes.data)
+
+
+def raw_attention(engine, rp, nq, q, k, v, d, dv, heads, o32, o64, ldo, y64, ycap):
+    """fora_hip_sparse_attention itself, every pointer as given (f32 operands, rows back to back); the stats"""
+    st = capi.AttnStats()
+    engine._chk(engine._lib.fora_hip_sparse_attention(engine._ctx, ptr(rp), C.c_int(nq), ptr(q), C.c_int(capi.PROP_F32), C.c_int64(heads * d), ptr(k),
+                                                      C.c_int(capi.PROP_F32), C.c_int64(heads * d), ptr(v), C.c_int(capi.PROP_F32), C.c_int64(heads * dv),
+                                                      C.c_int(d), C.c_int(dv), C.c_int(heads), C.c_double(0.37), ptr(o32), ptr(o64), C.c_int64(ldo), None,
+                                                      ptr(y64), C.c_uint64(ycap), C.byref(st)))
+    return st.as_dict()
+
+
+def mixed_homes(engine, dev, row_ptr, nq, n, e, rng):
+    """The C ABI takes each pointer on its own (the binding refuses what follows): q on the host, k and v on the device, out32 a
+    host array and out64 a device tensor of one padded pitch, y64 on the host -- the bits of the all-host call, the padding kept"""
+    heads, d, dv, fill = 2, 3, 2, -3.0
+    w, ldo = heads * dv, heads * dv + 3
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    Q, K = ar.scores_operands(rng, nq, n, d, heads)
+    V = rng.standard_normal((n, w)).astype(np.float32)
+    Kd, Vd = torch.from_numpy(K).to(dev), torch.from_numpy(V).to(dev)
+    for short in (256, 0):
+        engine.set_option("attn_short", short)
+        h32, h64, hy = np.full((nq, ldo), fill, np.float32), np.full((nq, ldo), fill, np.float64), np.zeros(heads * e, np.float64)
+        hst = raw_attention(engine, rp, nq, Q, K, V, d, dv, heads, h32, h64, ldo, hy, heads * e)
+        assert hst["q_on_device"] == hst["k_on_device"] == hst["v_on_device"] == 0 and hst["long_rows"] == (2 if short else nq - 1)
+        m32, m64, my = np.full((nq, ldo), fill, np.float32), torch.full((nq, ldo), fill, dtype=torch.float64, device=dev), np.zeros(heads * e, np.float64)
+        st = raw_attention(engine, rp, nq, Q, Kd, Vd, d, dv, heads, m32, m64, ldo, my, heads * e)
+        assert st["q_on_device"] == 0 and st["k_on_device"] == st["v_on_device"] == 1, st
+        g64 = m64.cpu().numpy()
+        assert (m32[:, :w].view(np.uint32) == h32[:, :w].view(np.uint32)).all() and (g64[:, :w].view(np.uint64) == h64[:, :w].view(np.uint64)).all(), short
+        assert (my.view(np.uint64) == hy.view(np.uint64)).all() and np.isfinite(h64[:, :w]).all() and (hy != 0).any(), short
+        for pad in (m32[:, w:], g64[:, w:], h32[:, w:], h64[:, w:]):
+            assert (pad == fill).all(), short
+    engine.set_option("attn_short", 256)
 
 
 def main():
@@ -76,6 +116,7 @@ def main():
                 assert (bits(t64[:, 2:2 + heads * dv].contiguous()) == want[0].view(np.uint64)).all()
                 assert (bits(t32[:, 2:2 + heads * dv].contiguous()) == want[1].view(np.uint32)).all()
                 assert (t32[:, :2] == -3.0).all() and (t32[:, 2 + heads * dv:] == -3.0).all() and (t64[:, :2] == -3.0).all() and (t64[:, 2 + heads * dv:] == -3.0).all()
+    mixed_homes(engine, dev, row_ptr, nq, n, e, rng)
     # mixed homes are refused by the binding
     try:
         engine.sparse_attention(row_ptr, Qd, K0, Vd, heads=heads)

@@ -4,6 +4,7 @@
 //   prop_plan_check plan <option> <free_bytes> <d> <len,len,...|->   the plan of rows of these lengths; prints its facts
 //   prop_plan_check rowptr                                           prop_row_ptr_ok on good and bad arrays
 //   prop_plan_check geom                                             prop_geom: alignment, widths, lane groups
+//   prop_plan_check helpers                                          widths, group exponent, byte extents, long-row segments
 #include "fora_prop_plan.h"
 
 #include <cstdio>
@@ -110,7 +111,7 @@ static int check_rowptr() {
 }
 
 static int check_geom() {
-    static const uint32_t f32[] = {4, 2, 1}, bf16[] = {8, 4, 1};
+    const uint32_t *const f32 = prop_widths(false), *const bf16 = prop_widths(true);
     int cases = 0;
     for (int d : {1, 2, 3, 4, 16, 63, 64, 65, 128, 130, 256, 257, 4096, 65536})
         for (uint64_t addr : {0ull, 2ull, 4ull, 8ull, 16ull})
@@ -137,10 +138,64 @@ static int check_geom() {
     return 0;
 }
 
+// the pure helpers of the drivers, each against a restatement that shares no code with it
+static int check_helpers() {
+    // the widths: three per element type, descending, ending in 1, 16 bytes a lane at most
+    CHECK(PROP_NWIDTHS == 3);
+    for (int t = 0; t < 2; t++) {
+        const uint32_t *w = prop_widths(t != 0), elt = t ? 2 : 4;
+        CHECK(w[0] * elt == 16 && w[0] > w[1] && w[1] > w[2] && w[2] == 1);
+    }
+    CHECK(prop_widths(false)[1] == 2 && prop_widths(true)[1] == 4);
+    // the group exponent: the smallest lg <= 6 with 2^lg >= d, by trying every lg
+    for (uint32_t d : {1u, 2u, 3u, 4u, 5u, 31u, 32u, 33u, 63u, 64u, 65u, 4096u, 65536u}) {
+        uint32_t want = 6;
+        for (uint32_t lg = 0; lg <= 6; lg++)
+            if ((1ull << lg) >= d) { want = lg; break; }
+        CHECK(prop_group_lg(d) == want);
+    }
+    CHECK(prop_group_lg(1) == 0 && prop_group_lg(2) == 1 && prop_group_lg(63) == 6 && prop_group_lg(64) == 6 && prop_group_lg(65) == 6 && prop_group_lg(65536) == 6);
+    // the byte extents: one past the offset of the last element that is read, by walking the elements
+    for (uint64_t rows : {0ull, 1ull, 2ull, 7ull})
+        for (uint64_t width : {1ull, 3ull, 8ull})
+            for (uint64_t pad : {0ull, 1ull, 5ull})
+                for (uint32_t elt : {2u, 4u, 8u}) {
+                    const uint64_t ld = width + pad;
+                    uint64_t end = 0;
+                    for (uint64_t r = 0; r < rows; r++)
+                        for (uint64_t col = 0; col < width; col++) end = std::max(end, (r * ld + col + 1) * elt);
+                    CHECK(prop_matrix_bytes(rows, ld, width, elt) == end);
+                    CHECK(prop_vector_bytes(rows * width, elt) == rows * width * elt);
+                }
+    CHECK(prop_matrix_bytes(0, 1000, 10, 4) == 0 && prop_matrix_bytes(1, 1000, 10, 4) == 40 && prop_matrix_bytes(2, 1000, 10, 4) == 4040);
+    CHECK(prop_matrix_bytes(2, 10, 10, 2) == 40 && prop_vector_bytes(0, 8) == 0);
+    // the long-row segments: entry by entry, for caps at, one below and one above the rows' lengths
+    const std::vector<int64_t> lens = {0, 1, 5, PROP_SEG - 1, PROP_SEG, PROP_SEG + 1, 2 * PROP_SEG, 2 * PROP_SEG + 1, 600, 0, 3};
+    std::vector<int64_t> row_ptr(lens.size() + 1, 0);
+    for (size_t i = 0; i < lens.size(); i++) row_ptr[i + 1] = row_ptr[i] + lens[i];
+    const int nq = (int)lens.size();
+    std::vector<uint32_t> caps = {0, 0xFFFFFFFFu};
+    for (int64_t L : lens)
+        for (int64_t c = L - 1; c <= L + 1; c++)
+            if (c >= 0) caps.push_back((uint32_t)c);
+    for (uint32_t cap : caps) {
+        uint64_t want = 0;
+        for (int i = 0; i < nq; i++) {
+            if ((uint64_t)lens[(size_t)i] <= cap) continue;
+            for (int64_t e = 0; e < lens[(size_t)i]; e++) want += e % PROP_SEG == 0;
+        }
+        CHECK(prop_long_segments(row_ptr.data(), nq, cap) == want);
+    }
+    CHECK(prop_long_segments(row_ptr.data(), nq, 0) == prop_segments(row_ptr.data(), nq) && prop_long_segments(row_ptr.data(), 0, 0) == 0);
+    printf("caps=%zu ok\n", caps.size());
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 6 && !strcmp(argv[1], "plan")) return check_plan(atoll(argv[2]), strtoull(argv[3], nullptr, 10), atoi(argv[4]), parse_list(argv[5]));
     if (argc >= 2 && !strcmp(argv[1], "rowptr")) return check_rowptr();
     if (argc >= 2 && !strcmp(argv[1], "geom")) return check_geom();
-    fprintf(stderr, "usage: prop_plan_check plan <option> <free_bytes> <d> <lens> | rowptr | geom\n");
+    if (argc >= 2 && !strcmp(argv[1], "helpers")) return check_helpers();
+    fprintf(stderr, "usage: prop_plan_check plan <option> <free_bytes> <d> <lens> | rowptr | geom | helpers\n");
     return 2;
 }

@@ -142,6 +142,12 @@ def test_row_ptr_validation_and_lane_geometry(plan_check):
     assert _run(plan_check, "geom").split()[-1] == "ok"
 
 
+def test_driver_helpers_against_brute_force(plan_check):
+    """the vector widths, the group exponent, the byte extents of the operands and the long-row segment count, each against
+    a restatement at its edges"""
+    assert _run(plan_check, "helpers").split()[-1] == "ok"
+
+
 # ---- (d) the symbol
 def test_symbol_and_null_ctx():
     """the library exports fora_hip_sparse_propagate and answers a NULL ctx with FORA_E_ARG without touching a GPU; the
