@@ -26,6 +26,7 @@ SYMBOLS = [
     "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
     "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
     "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention", "fora_hip_sparse_attention_bwd",
+    "fora_hip_store_put", "fora_hip_store_load", "fora_hip_store_take", "fora_hip_store_info", "fora_hip_store_clear",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -173,6 +174,14 @@ class AttnBwdStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class StoreStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("entries", C.c_uint64), ("max_row", C.c_uint64), ("store_rows", C.c_uint64), ("store_entries", C.c_uint64),
+                ("ids_on_device", C.c_int32), ("fix_on_device", C.c_int32), ("store_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 PROP_SEG = 256  # FORA_PROP_SEG
@@ -402,6 +411,80 @@ class Engine:
 
     def sparse_clear(self):
         self._chk(self._lib.fora_hip_sparse_clear(self._ctx))
+
+    # ---- the row store (the ROW STORE contract of include/fora_hip.h)
+    def store_put(self, row_ptr, append=False):
+        """The held sparse result into the store (fora_hip_store_put), replacing it or, with append, behind its rows.
+        row_ptr: as the sparse call returned it.  Returns the stats dict."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        st = StoreStats()
+        self._chk(self._lib.fora_hip_store_put(self._ctx, _p(rp), C.c_int(rp.size - 1), C.c_int(int(bool(append))), C.byref(st)))
+        return st.as_dict()
+
+    def _store_array(self, x, entries, np_dtype, name):
+        """(pointer, on_device, keep-alive) of the ids / fix argument of store_load: `entries` elements, a numpy array or a
+        one-dimensional torch tensor on the context's GPU (fix as uint64 words, or the same bits as int64)"""
+        if self._is_torch(x):
+            import torch
+            want = (torch.int32,) if np_dtype == np.int32 else (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError(f"a torch {name} must live on the context's GPU")
+            if x.dtype not in want or x.dim() != 1 or x.shape[0] != entries:
+                raise ValueError(f"{name} must hold one {np.dtype(np_dtype).name} per entry")
+            v = x.detach()
+            if entries > 1 and v.stride(0) != 1:
+                v = v.contiguous()
+            return C.c_void_p(v.data_ptr()), True, v
+        a = np.asarray(x)
+        if a.dtype == np.int64 and np_dtype == np.uint64:
+            a = a.view(np.uint64)
+        if a.dtype != np_dtype or a.ndim != 1 or a.shape[0] != entries:
+            raise ValueError(f"{name} must hold one {np.dtype(np_dtype).name} per entry")
+        a = np.ascontiguousarray(a)
+        return _p(a), False, a
+
+    def store_load(self, row_ptr, ids, fix, append=False):
+        """The caller's rows into the store (fora_hip_store_load): row_ptr [nrows + 1] (host), ids (int32) and fix (uint64
+        words; int64 bits are taken as they are) with row_ptr[-1] entries each -- numpy arrays, or torch tensors on the
+        context's GPU, which the device reads in place (a slice of a larger tensor is fine).  Every id is checked on the GPU:
+        inside [0, n) and strictly ascending inside a row.  Returns the stats dict."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        if rp.ndim != 1 or rp.size < 1:
+            raise ValueError("row_ptr must hold nrows + 1 entries")
+        e = max(int(rp[-1]), 0)
+        iptr, i_dev, _ki = self._store_array(ids, e, np.int32, "ids")
+        fptr, f_dev, _kf = self._store_array(fix, e, np.uint64, "fix")
+        if i_dev or f_dev:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))  # (the tensors may have been written on another stream)
+        st = StoreStats()
+        self._chk(self._lib.fora_hip_store_load(self._ctx, _p(rp), C.c_int64(rp.size - 1), iptr, fptr, C.c_int(int(bool(append))), C.byref(st)))
+        return st.as_dict()
+
+    def store_take(self, rows):
+        """Rows `rows` of the store, in that order, become the held sparse result (fora_hip_store_take): one copy on the GPU,
+        no query.  Returns (row_ptr, stats): the row_ptr every call on the held rows takes (sparse_propagate, sparse_attention,
+        torch_ops ...); sparse_fetch copies the rows out."""
+        if self._is_torch(rows):
+            rows = rows.cpu().numpy()
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        row_ptr = np.zeros(r.size + 1, dtype=np.int64)
+        st = StoreStats()
+        self._chk(self._lib.fora_hip_store_take(self._ctx, _p(r), C.c_int(r.size), _p(row_ptr), C.byref(st)))
+        return row_ptr, st.as_dict()
+
+    def store_info(self):
+        """{rows, entries, max_row} of the store (fora_hip_store_info); zeros without one"""
+        rows, entries, max_row = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._lib.fora_hip_store_info(self._ctx, C.byref(rows), C.byref(entries), C.byref(max_row)))
+        return {"rows": rows.value, "entries": entries.value, "max_row": max_row.value}
+
+    def store_clear(self):
+        self._chk(self._lib.fora_hip_store_clear(self._ctx))
 
     # ---- feature propagation (the PROPAGATE contract of include/fora_hip.h)
     @staticmethod

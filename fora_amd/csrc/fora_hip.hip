@@ -18,6 +18,7 @@
 #include "fora_softmax.h"
 #include "fora_attn.h"
 #include "fora_attn_bwd.h"
+#include "fora_store.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -39,7 +40,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -106,6 +107,7 @@ struct Tunables {
     int64_t topk_cand = 0;       // ... entries of the candidate scratch (the rows of a batch are compacted into it chunk by chunk, consecutive rows, a row never split); 0: by free memory; always at least the longest row.  Same bits for every value
     int64_t softmax_short = SMAX_SHORT_MAX; // ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): a row of at most this many entries (clamped to 0 .. 256, fora_softmax.h) is one wave's, read once and written once; a longer one goes segment by segment through partial maxima and sums; 0: every row does.  Same bits for every value
     int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value.  ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd) reads it for rows (k_attn_bwd_short) and columns (k_attn_cols, fora_attn_bwd_plan.h) alike
+    int64_t take_span = STORE_SPAN_DEFAULT; // ROW STORE (fora_hip_store_take; the check of fora_hip_store_load): output entries one workgroup copies, a multiple of 64 and at least 64 (store_span, fora_store_plan.h).  Same bits for every value.  DESIGN.md 5.20 has the runs behind the default
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -122,6 +124,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
     {"softmax_short", &Tunables::softmax_short, false}, {"attn_short", &Tunables::attn_short, false},
+    {"take_span", &Tunables::take_span, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -378,6 +381,19 @@ struct PropTBufs {
     } cols;
 };
 
+// ROW STORE (fora_hip_store_put, _load, _take, _info, _clear): a library of sparse rows 0 .. R - 1 kept on the device, apart from the
+// workspace and from the held sparse result, until fora_hip_store_clear, set_graph or destroy (free_store).  row_ptr lives on the
+// host: a take is planned from it, and the kernels read the plan.  d_ids / d_fix may have room behind `entries`: an append that
+// fits is written there, and is part of the store only once the words below have moved.
+struct RowStore {
+    std::vector<int64_t> h_row_ptr;           // R + 1 (empty: no store, R = 0)
+    DevBuf<int32_t> d_ids; DevBuf<uint64_t> d_fix;
+    uint64_t entries = 0, max_row = 0;
+    int64_t rows() const { return h_row_ptr.empty() ? 0 : (int64_t)h_row_ptr.size() - 1; }
+    // scratch of the call in progress, grow-only: the plan (out_ptr | src | win, fora_store_plan.h); the check's smallest bad entry
+    DevBuf<int64_t> d_plan; DevBuf<unsigned long long> d_bad;
+};
+
 // The loose words of the context, grouped by role.
 struct Params { // fora_hip_set_params / _raw
     bool have = false;
@@ -410,7 +426,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -420,7 +436,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt; RowStore st;
     bool topk_lds_ready = false; // k_topk_rows<true> may take the whole of a CU's LDS (topk_lds_limit)
     uint64_t sparse_gen = 0;   // fora_hip_get_option "sparse_generation": counts the times a sparse result became held or stopped being held
     int batch_req = 0;        // the caller's request (fora_hip_set_batch), not part of a plan
@@ -456,6 +472,7 @@ void sparse_unheld(fora_ctx *c) {
 void free_sparse(fora_ctx *c) { sparse_unheld(c); c->sp = SparseResult{}; }
 void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
 void free_prop(fora_ctx *c) { c->pr = PropBufs{}; }
+void free_store(fora_ctx *c) { c->st = RowStore{}; }
 void free_index(fora_ctx *c) { c->ix = Index{}; }
 void free_workspace(fora_ctx *c) { c->ws = Workspace{}; }
 
@@ -969,6 +986,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SDDMM: t.sddmm_ms += ms; break;               // k_prop_sddmm: fora_sddmm_stats only
         case EV_SOFTMAX: t.softmax_ms += ms; break;           // the k_softmax_* kernels of a call: fora_softmax_stats only
         case EV_ATTN: t.attn_ms += ms; break;                 // every launch of an ATTENTION call: fora_attn_stats only
+        case EV_STORE: t.store_ms += ms; break;               // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -3214,6 +3232,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_sparse(c);
     free_sweep(c);
     free_prop(c);
+    free_store(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
     for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -3248,6 +3267,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_sparse(c); // (rows of another graph)
     free_sweep(c);
     free_prop(c); // (the upload of another graph's features)
+    free_store(c); // (rows over another graph's nodes)
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
@@ -3895,6 +3915,183 @@ int fora_hip_sparse_clear(fora_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_sparse(c);
+    return FORA_OK;
+}
+
+// ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)
+namespace {
+// a plan on the device: out_ptr | src | win in the store's plan buffer
+struct StorePlanDev { const int64_t *out_ptr = nullptr, *src = nullptr, *win = nullptr; };
+int store_upload_plan(fora_ctx *c, const StorePlan &p, StorePlanDev &d) {
+    RowStore &s = c->st;
+    const size_t a = p.out_ptr.size(), b = p.src.size(), w = p.win.size();
+    if (int rc = prop_ensure(c, s.d_plan, a + b + w, "the store's plan")) return rc;
+    int64_t *at = s.d_plan.get();
+    HIPCHK(c, hipMemcpyAsync(at, p.out_ptr.data(), a * 8, hipMemcpyHostToDevice, c->stream));
+    if (b) HIPCHK(c, hipMemcpyAsync(at + a, p.src.data(), b * 8, hipMemcpyHostToDevice, c->stream));
+    if (w) HIPCHK(c, hipMemcpyAsync(at + a + b, p.win.data(), w * 8, hipMemcpyHostToDevice, c->stream));
+    d.out_ptr = at; d.src = at + a; d.win = at + a + b;
+    return FORA_OK;
+}
+inline unsigned store_grid(uint64_t spans) { return (unsigned)std::min<uint64_t>(spans, 1u << 20); } // (the kernels stride over the spans)
+
+// where a put / load writes: behind the store's entries when an append fits there, otherwise into new arrays that start with a
+// copy of the rows that stay -- moved into the store by store_commit, freed on every other way out
+struct StoreDest {
+    DevBuf<int32_t> ids; DevBuf<uint64_t> fix; bool fresh = false;
+    int32_t *p_ids = nullptr; uint64_t *p_fix = nullptr; uint64_t base = 0; // the arrays, and the first entry the call writes
+};
+int store_dest(fora_ctx *c, bool append, uint64_t add, StoreDest &d) {
+    RowStore &s = c->st;
+    d.base = append ? s.entries : 0;
+    const uint64_t total = d.base + add;
+    if (append && total <= std::min<uint64_t>(s.d_ids.size(), s.d_fix.size())) { d.p_ids = s.d_ids.get(); d.p_fix = s.d_fix.get(); return FORA_OK; }
+    d.fresh = true;
+    for (uint64_t cap = d.base ? std::max(total, d.base + d.base / 2) : total;; cap = total) { // (an append grows by half at least; a guess that does not fit is no reason to fail)
+        if (d.ids.alloc((size_t)std::max<uint64_t>(cap, 1)) == hipSuccess && d.fix.alloc((size_t)std::max<uint64_t>(cap, 1)) == hipSuccess) break;
+        (void)hipGetLastError(); d.ids.reset(); d.fix.reset();
+        if (cap == total) return fail(c, FORA_E_NOMEM, "no device memory for the row store");
+    }
+    d.p_ids = d.ids.get(); d.p_fix = d.fix.get();
+    if (d.base) {
+        HIPCHK(c, hipMemcpyAsync(d.p_ids, s.d_ids.get(), d.base * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d.p_fix, s.d_fix.get(), d.base * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return FORA_OK;
+}
+// the last step of a put / load, behind an idle stream: nothing fails from here on
+void store_commit(fora_ctx *c, StoreDest &d, bool append, const int64_t *row_ptr, int64_t nrows, uint64_t max_row) {
+    RowStore &s = c->st;
+    if (!append || s.h_row_ptr.empty()) { s.h_row_ptr.assign(1, 0); s.entries = 0; s.max_row = 0; }
+    if (d.fresh) { s.d_ids = std::move(d.ids); s.d_fix = std::move(d.fix); }
+    for (int64_t i = 1; i <= nrows; i++) s.h_row_ptr.push_back((int64_t)d.base + row_ptr[i]);
+    s.entries = d.base + (uint64_t)row_ptr[nrows];
+    s.max_row = std::max(s.max_row, max_row);
+}
+
+// what put and load share: nrows rows of (row_ptr, ids, fix) become the store, or its rows R ..; ids / fix on the device or the
+// host; check: every entry is validated on the device before anything moves (load; the rows of a held result are valid)
+int store_add(fora_ctx *c, const char *who, const int64_t *row_ptr, int64_t nrows, const int32_t *ids, bool ids_dev, const uint64_t *fix, bool fix_dev, bool check,
+              bool append, fora_store_stats *st) {
+    RowStore &s = c->st;
+    const uint64_t entries = (uint64_t)row_ptr[nrows];
+    uint64_t max_row = 0;
+    for (int64_t i = 0; i < nrows; i++) max_row = std::max(max_row, (uint64_t)(row_ptr[i + 1] - row_ptr[i]));
+    s.h_row_ptr.reserve((append ? s.h_row_ptr.size() : 0) + (size_t)nrows + 1);
+    StorePlan plan; StorePlanDev pd;
+    unsigned long long bad = ~0ull;
+    // ---- every buffer before the first launch
+    StoreDest d;
+    if (check && entries) {
+        plan = store_take_plan(row_ptr, nullptr, nrows, store_span(c->opt_.take_span));
+        if (int rc = prop_ensure(c, s.d_bad, 1, "the store's check")) return rc;
+        if (int rc = store_upload_plan(c, plan, pd)) return rc;
+        HIPCHK(c, hipMemsetAsync(s.d_bad.get(), 0xFF, sizeof(bad), c->stream));
+    }
+    if (int rc = store_dest(c, append, entries, d)) return rc;
+    c->tm.store_ms = 0;
+    if (entries) {
+        EvSpan ev(c, EV_STORE);
+        HIPCHK(c, hipMemcpyAsync(d.p_ids + d.base, ids, entries * 4, ids_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d.p_fix + d.base, fix, entries * 8, fix_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        if (check) hipLaunchKernelGGL(k_store_check, dim3(store_grid(plan.spans)), dim3(BLOCK), 0, c->stream, pd.out_ptr, pd.win, plan.spans, entries, plan.span,
+                                      (const int32_t *)(d.p_ids + d.base), (uint32_t)c->g.n, s.d_bad.get());
+        ev.end();
+        if (check) HIPCHK(c, hipMemcpyAsync(&bad, s.d_bad.get(), sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (int rc = held_call_end(c, who)) return rc; // (idle: the check has finished, the plan and the caller's arrays go out of use)
+    if (bad != ~0ull) {
+        const int64_t row = (int64_t)(std::upper_bound(row_ptr, row_ptr + nrows + 1, (int64_t)bad) - row_ptr) - 1;
+        return fail(c, FORA_E_ARG, std::string(who) + ": entry " + std::to_string(bad) + " (row " + std::to_string(row) + ", place " + std::to_string((int64_t)bad - row_ptr[row]) +
+                                       "): an id outside [0, n), or not above the id before it in its row");
+    }
+    store_commit(c, d, append, row_ptr, nrows, max_row);
+    if (st) {
+        st->rows = (uint64_t)nrows; st->entries = entries; st->max_row = max_row;
+        st->store_rows = (uint64_t)s.rows(); st->store_entries = s.entries;
+        st->ids_on_device = ids_dev ? 1 : 0; st->fix_on_device = fix_dev ? 1 : 0;
+        st->store_ms = c->tm.store_ms;
+    }
+    return FORA_OK;
+}
+
+int store_take_impl(fora_ctx *c, const int64_t *rows, int nb, int64_t *row_ptr_out, fora_store_stats *st) {
+    RowStore &s = c->st;
+    const StorePlan plan = store_take_plan(s.h_row_ptr.data(), rows, nb, store_span(c->opt_.take_span));
+    // ---- every buffer before the launch: no room leaves nothing held and the store as it was
+    const size_t room = (size_t)std::max<uint64_t>(plan.entries, 1);
+    if (c->sp.d_ids.ensure(room) != hipSuccess || c->sp.d_fix.ensure(room) != hipSuccess) {
+        (void)hipGetLastError(); c->sp.d_ids.reset(); c->sp.d_fix.reset();
+        return fail(c, FORA_E_NOMEM, "store take: no device memory for the result");
+    }
+    StorePlanDev pd;
+    c->tm.store_ms = 0;
+    if (plan.entries) {
+        if (int rc = store_upload_plan(c, plan, pd)) return rc;
+        EvSpan ev(c, EV_STORE);
+        hipLaunchKernelGGL(k_store_take, dim3(store_grid(plan.spans)), dim3(BLOCK), 0, c->stream, pd.out_ptr, pd.src, pd.win, plan.spans, plan.entries, plan.span,
+                           (const int32_t *)s.d_ids.get(), (const uint64_t *)s.d_fix.get(), s.entries, c->sp.d_ids.get(), c->sp.d_fix.get(),
+                           (uint64_t)std::min(c->sp.d_ids.size(), c->sp.d_fix.size()));
+    }
+    RowLayout lay; // every row placed by the plan, none dangling: the end of a call that made a held result
+    lay.begin(nullptr, nb);
+    lay.row_ptr = plan.out_ptr; lay.cur = plan.entries; lay.max_row = plan.max_row;
+    if (int rc = finish_rows(c, lay, c->sp, "store take", row_ptr_out, [](uint32_t, const int64_t *, const int32_t *) {})) return rc;
+    if (st) {
+        st->rows = (uint64_t)nb; st->entries = plan.entries; st->max_row = plan.max_row;
+        st->store_rows = (uint64_t)s.rows(); st->store_entries = s.entries;
+        st->store_ms = c->tm.store_ms;
+    }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_store_put(fora_ctx *c, const int64_t *row_ptr, int nq, int append, fora_store_stats *st) {
+    if (int rc = held_call_begin(c, "store put", row_ptr, nq)) return rc;
+    if (st) memset(st, 0, sizeof(*st));
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, store_add(c, "store put", row_ptr, nq, c->sp.d_ids.get(), true, c->sp.d_fix.get(), true, false, append != 0, st));
+}
+
+int fora_hip_store_load(fora_ctx *c, const int64_t *row_ptr, int64_t nrows, const int32_t *ids, const uint64_t *fix, int append, fora_store_stats *st) {
+    if (!c) return FORA_E_ARG;
+    if (!c->g.n) return fail(c, FORA_E_ARG, "store load: set_graph first");
+    if (nrows < 0 || !row_ptr) return fail(c, FORA_E_ARG, "store load: negative nrows or null row_ptr");
+    if (!store_row_ptr_ok(row_ptr, nrows)) return fail(c, FORA_E_ARG, "store load: row_ptr does not start at 0 or decreases");
+    if (row_ptr[nrows] && (!ids || !fix)) return fail(c, FORA_E_ARG, "store load: null ids or fix");
+    if (st) memset(st, 0, sizeof(*st));
+    HIPCHK(c, hipSetDevice(c->device));
+    bool ids_dev = false, fix_dev = false;
+    if (ids) if (int rc = sparse_dest(c, ids, ids_dev)) return rc;
+    if (fix) if (int rc = sparse_dest(c, fix, fix_dev)) return rc;
+    return drop_pairs_unless_ok(c, store_add(c, "store load", row_ptr, nrows, ids, ids_dev, fix, fix_dev, true, append != 0, st));
+}
+
+int fora_hip_store_take(fora_ctx *c, const int64_t *rows, int nb, int64_t *row_ptr_out, fora_store_stats *st) {
+    if (!c) return FORA_E_ARG;
+    uint64_t thr;
+    if (int rc = held_rows_begin(c, c->sp, row_ptr_out, 0.0, thr)) return rc; // (the held result has ended; a null row_ptr_out is refused there)
+    if (st) memset(st, 0, sizeof(*st));
+    if (nb < 0 || (nb > 0 && !rows)) return fail(c, FORA_E_ARG, "store take: negative nb or null rows");
+    const int64_t bad = store_bad_index(rows, nb, c->st.rows());
+    if (bad >= 0) return fail(c, FORA_E_ARG, "store take: rows[" + std::to_string(bad) + "] = " + std::to_string(rows[bad]) + " is outside the store's " + std::to_string(c->st.rows()) + " rows");
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, store_take_impl(c, rows, nb, row_ptr_out, st));
+}
+
+int fora_hip_store_info(fora_ctx *c, int64_t *rows, uint64_t *entries, uint64_t *max_row) {
+    if (!c) return FORA_E_ARG;
+    if (rows) *rows = c->st.rows();
+    if (entries) *entries = c->st.entries;
+    if (max_row) *max_row = c->st.max_row;
+    return FORA_OK;
+}
+
+int fora_hip_store_clear(fora_ctx *c) {
+    if (!c) return FORA_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_store(c);
     return FORA_OK;
 }
 

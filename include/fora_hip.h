@@ -488,6 +488,52 @@
  *     and give the bits they always gave, before and after a call with values.
  *   - with values equal to the f64 vals of fora_hip_sparse_fetch both calls give the bits of the plain calls without
  *     FORA_PROP_NORMALIZE.
+ * ROW STORE (fora_hip_store_put, fora_hip_store_load, fora_hip_store_take, fora_hip_store_info, fora_hip_store_clear): a library
+ * of sparse rows kept on the device, any list of which becomes the held sparse result with one copy on the GPU and no query --
+ * the rows of the training nodes are computed once and every mini-batch takes its own.
+ *   - the store: one per ctx, rows 0 .. R - 1 as (row_ptr, ids, fix), ids and fix in device memory the ctx owns, outside the
+ *     workspace and apart from the held sparse result; row_ptr is kept on the host, where a take is planned.  It lives until
+ *     fora_hip_store_clear, fora_hip_set_graph or fora_hip_destroy; every other entry point leaves it untouched -- the sparse
+ *     calls that replace the held result, fora_hip_sparse_clear, set_option (a reset too), set_batch, a bucket retry.
+ *   - fora_hip_store_put copies the held sparse result into the store, device to device.  row_ptr is validated exactly as in
+ *     PROPAGATE.  append == 0 replaces the store; append != 0 adds the nq rows behind the R rows that are there: row i of the
+ *     call becomes store row R + i (an append to an empty or absent store fills it).  The held result, its transposition,
+ *     "sparse_generation" and everything else stay untouched.  nq == 0 is legal: it adds nothing (and, replacing, leaves an
+ *     empty store).  No held result, or a row_ptr that does not match it: FORA_E_ARG, the store unchanged.
+ *   - fora_hip_store_load does the same with the caller's arrays: rows fetched earlier, or read from disk, come back.  row_ptr
+ *     is a host array of nrows + 1 entries with row_ptr[0] == 0, non-decreasing; row_ptr[nrows] is the number of entries.  ids
+ *     and fix may each be pageable host memory or device memory on the ctx's GPU (memory of another GPU is FORA_E_ARG); a device
+ *     array is read by the device and never staged through the host, at any element alignment (a slice of a larger tensor).
+ *     Every consumer of the held result relies on ids in [0, n) that ascend strictly inside a row, so EVERY entry is checked for
+ *     that on the GPU (k_store_check), and the check has finished before anything moves into the store; the smallest offending
+ *     entry is named by fora_hip_last_error.  Equal or descending ids across a row boundary are legal.  Words may be any u64.
+ *     A bad array or row_ptr, NULL ids or fix while there are entries, nrows < 0, no graph: FORA_E_ARG, the store exactly as it
+ *     was.  nrows == 0 with append == 0 leaves an empty store.
+ *   - both: no device memory is FORA_E_NOMEM, the store unchanged and the ctx usable.  A call that replaces the store, or an
+ *     append that outgrows the room behind the store's entries, builds new arrays and moves them in after its last step; until
+ *     then the old store and the new arrays exist side by side.
+ *   - fora_hip_store_take makes the rows rows[0 .. nb) of the store the held sparse result, in the caller's order; duplicate
+ *     indices give duplicate rows.  Like every call that makes a held result it first ends the one that is held, whatever
+ *     becomes of the call, and "sparse_generation" moves as it does for the query calls; the arguments are checked behind that
+ *     point, as a bad k is in SPARSE RESULTS, TOP-K.  Held row i has the ids and the words of store row rows[i], in that row's
+ *     order, word for word; row_ptr_out (nb + 1) is the prefix sum of the lengths; fora_hip_sparse_fetch gives
+ *     vals[e] == ldexp((double)fix[e], -62) as always.  The store is not changed, and the result is an ordinary held result in
+ *     every respect: fetch, both products, the transposition, SCORES, ROW SOFTMAX, ATTENTION and its backward pass work on it
+ *     unchanged.  nb == 0: FORA_OK, row_ptr_out[0] = 0, an empty result held.  NULL row_ptr_out, nb < 0, NULL rows with nb > 0,
+ *     an index outside [0, R) -- against an empty or absent store too: FORA_E_ARG, nothing held.  No device memory:
+ *     FORA_E_NOMEM, nothing held, the store intact, the ctx usable.  rows is a host array: row_ptr_out has to reach the host
+ *     anyway, every consumer validating the caller's host row_ptr.
+ *   - fora_hip_store_info reports R, the store's entries and its longest row; any pointer may be NULL; an empty or absent store
+ *     reports zeros.  fora_hip_store_clear frees the store.
+ *   - no bit depends on the option "take_span" (the output entries one workgroup of k_store_take copies, and of k_store_check
+ *     checks: a multiple of 64 and at least 64, other values are rounded down to one and clamped to 64 .. 65536; readable from
+ *     the environment like the other non-schedule knobs), on the launch shape, on host versus device pointers, or on whether
+ *     the store was filled by put or by load, at once or by appends.
+ *   - stats (fora_store_stats): rows, entries and max_row of this call; store_rows and store_entries of the store after it (a
+ *     take: unchanged); ids_on_device and fix_on_device (load); store_ms = the device time of the call's kernel and of the copies
+ *     of the call's own rows (the move of the rows that stay, when an append outgrows its room, is not in it).
+ *   - a NULL ctx is answered without touching the GPU (FORA_E_ARG).  A held sweep profile, the walk index, the options, the
+ *     FORA parameters and fora_timing are left untouched by all five; the ctx's stream is idle when they return.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -776,6 +822,20 @@ int fora_hip_sparse_attention_bwd(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/
  * fix / vals can take, col_ptr takes n + 1 */
 int fora_hip_sparse_transpose_fetch(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq,
                                     int64_t *col_ptr /*n+1 or NULL*/, int32_t *rows, uint64_t *fix, double *vals, uint64_t cap);
+
+/* ---- the row store (the ROW STORE contract above): sparse rows kept on the device; put copies the held result in, load the
+ * caller's arrays, take makes a list of the store's rows the held sparse result. */
+typedef struct { uint64_t rows, entries, max_row;      /* of this call */
+                 uint64_t store_rows, store_entries;   /* the store after the call */
+                 int32_t ids_on_device, fix_on_device; /* fora_hip_store_load: where the caller's arrays were */
+                 double store_ms; } fora_store_stats;
+int fora_hip_store_put(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq, int append, fora_store_stats *st /*or NULL*/);
+int fora_hip_store_load(fora_ctx *ctx, const int64_t *row_ptr /*nrows+1, host*/, int64_t nrows,
+                        const int32_t *ids, const uint64_t *fix, int append, fora_store_stats *st /*or NULL*/);
+int fora_hip_store_take(fora_ctx *ctx, const int64_t *rows /*nb, host*/, int nb, int64_t *row_ptr_out /*nb+1, required*/,
+                        fora_store_stats *st /*or NULL*/);
+int fora_hip_store_info(fora_ctx *ctx, int64_t *rows, uint64_t *entries, uint64_t *max_row);
+int fora_hip_store_clear(fora_ctx *ctx);
 
 /* ---- local clustering (the SWEEP CUT contract above): fora_hip_query_batch, then per row the sweep over ppr / degree and
  * its best cut, all on the GPU.  The profile stays with the ctx until fetched or replaced. */
