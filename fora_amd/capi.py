@@ -27,6 +27,7 @@ SYMBOLS = [
     "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
     "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention", "fora_hip_sparse_attention_bwd",
     "fora_hip_store_put", "fora_hip_store_load", "fora_hip_store_take", "fora_hip_store_info", "fora_hip_store_clear",
+    "fora_hip_sparse_compact", "fora_hip_sparse_cols_fetch",
 ]
 BWD_FIX_ONE = 1 << 60
 
@@ -179,6 +180,13 @@ class AttnBwdStats(C.Structure):
 class StoreStats(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("entries", C.c_uint64), ("max_row", C.c_uint64), ("store_rows", C.c_uint64), ("store_entries", C.c_uint64),
                 ("ids_on_device", C.c_int32), ("fix_on_device", C.c_int32), ("store_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ColsStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("cols", C.c_uint64), ("words", C.c_uint64), ("cols_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -486,16 +494,59 @@ class Engine:
     def store_clear(self):
         self._chk(self._lib.fora_hip_store_clear(self._ctx))
 
+    # ---- the held result over its own columns (the COLUMNS contract of include/fora_hip.h)
+    @property
+    def held_cols(self):
+        """The columns of the calls on the held rows (the option "sparse_cols"): the held result's own nc after
+        sparse_compact, the graph's n otherwise."""
+        return self.get_option("sparse_cols")
+
+    def sparse_compact(self, row_ptr, device=False):
+        """The held sparse result re-expressed over its own columns (fora_hip_sparse_compact): every held id becomes its rank
+        in cols, the ascending array of the distinct node ids among the held entries, and from here on every call on the held
+        rows takes operands with len(cols) rows in place of n (X[cols] for an X over the nodes) and returns column-sided
+        outputs of that many rows -- the n_id of a sampled mini-batch.  row_ptr: as the sparse call or store_take returned
+        it.  Returns (cols, stats dict): cols a numpy int32 array, or with device=True a torch int32 tensor on the context's
+        GPU.  Ends with the held result; a second compaction of the same result is refused."""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        nc, st = C.c_int64(0), ColsStats()
+        if device:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("sparse_compact(device=True): torch sees no GPU here.  torch and libfora_hip.so must "
+                                   "share one HIP runtime: import torch before the first Engine is created")
+        self._chk(self._lib.fora_hip_sparse_compact(self._ctx, _p(rp), C.c_int(rp.size - 1), C.byref(nc), C.byref(st)))
+        if device:
+            dev = torch.device("cuda", self.device)
+            cols = torch.empty(nc.value, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
+            ptr = C.c_void_p(cols.data_ptr()) if nc.value else None
+        else:
+            cols = np.zeros(nc.value, dtype=np.int32)
+            ptr = _p(cols) if nc.value else None
+        self._chk(self._lib.fora_hip_sparse_cols_fetch(self._ctx, ptr, C.c_uint64(nc.value)))
+        return cols, st.as_dict()
+
+    def store_take_compact(self, rows, device=False):
+        """store_take, then sparse_compact: rows `rows` of the store become the held result over their own columns.  Returns
+        (row_ptr, cols, stats dict of the compaction)."""
+        row_ptr, _ = self.store_take(rows)
+        cols, st = self.sparse_compact(row_ptr, device=device)
+        return row_ptr, cols, st
+
     # ---- feature propagation (the PROPAGATE contract of include/fora_hip.h)
     @staticmethod
     def _is_torch(x):
         return type(x).__module__.split(".")[0] == "torch"
 
-    def _prop_feat(self, feat, bf16, rows=None, name="feat"):
-        """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate ([n, d]), or with
-        rows / name of the grad argument of sparse_propagate_t ([nq, d])"""
-        shape = "[n, d]" if rows is None else "[nq, d]"
-        rows = self.n if rows is None else rows
+    def _prop_feat(self, feat, bf16, rows=None, name="feat", shape=None):
+        """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate ([n, d]; n: the held
+        columns, held_cols), or with rows / name of the grad argument of sparse_propagate_t ([nq, d]; shape: how the
+        message names another shape)"""
+        shape = shape or ("[n, d] (n: the held columns)" if rows is None else "[nq, d]")
+        rows = self.held_cols if rows is None else rows
         if self._is_torch(feat):
             import torch
             if not feat.is_cuda or feat.device.index != self.device:
@@ -513,7 +564,9 @@ class Engine:
         if a.ndim != 2 or a.shape[0] != rows:
             raise ValueError(f"{name} must be {shape}")
         it = a.itemsize
-        if (a.shape[1] > 1 and a.strides[1] != it) or (a.shape[0] > 1 and (a.strides[0] % it or a.strides[0] < a.shape[1] * it)):
+        if a.shape[0] == 0:                     # (no rows -- a compacted result without columns: nothing is read, and numpy's strides say nothing)
+            a = np.zeros((0, a.shape[1]), dtype=a.dtype)
+        elif (a.shape[1] > 1 and a.strides[1] != it) or (a.shape[0] > 1 and (a.strides[0] % it or a.strides[0] < a.shape[1] * it)):
             raise ValueError(f"{name}: a column stride other than one element (or rows that overlap) is not supported")
         ldf = a.strides[0] // it if a.shape[0] > 1 else a.shape[1]
         return _p(a), (PROP_BF16 if bf16 else PROP_F32), int(a.shape[1]), int(ldf), False, a
@@ -528,7 +581,8 @@ class Engine:
             ptr = C.c_void_p(out.data_ptr())
             ok = ok and out.dtype == dtype
         else:
-            ok = out.ndim == 2 and out.shape == (nq, d) and out.dtype == dtype and (d == 1 or out.strides[1] == out.itemsize) and out.strides[0] % out.itemsize == 0
+            ok = out.ndim == 2 and out.shape == (nq, d) and out.dtype == dtype
+            ok = ok and (nq == 0 or ((d == 1 or out.strides[1] == out.itemsize) and out.strides[0] % out.itemsize == 0))  # (no rows: numpy's strides say nothing)
             ldo = out.strides[0] // out.itemsize if nq > 1 else d
             ptr = _p(out)
         if not ok or ldo < d:
@@ -637,7 +691,7 @@ class Engine:
         gptr, gtype, d, ldg, on_dev, _keep = self._prop_feat(grad, bf16, rows=nq, name="grad")
         if values is not None:
             vptr, vtype, _vkeep = self._prop_values(values, int(rp[-1]), on_dev)
-        out32, out64, p32, p64, ldo = self._prop_outputs(self.n, d, on_dev, want32, want64, out32, out64)
+        out32, out64, p32, p64, ldo = self._prop_outputs(self.held_cols, d, on_dev, want32, want64, out32, out64)
         ps = PropTStats()
         if values is not None:
             self._chk(self._lib.fora_hip_sparse_propagate_t_vals(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
@@ -839,7 +893,8 @@ class Engine:
         yptr, ytype, _, _ky = self._entry_operand(y.reshape(heads * e), heads * e, "y")
         gr = AttnGrads()
         outs = []
-        for name, rows, w, want, o32, o64 in (("dq", nq, wq, want_dq, dq32, dq64), ("dk", self.n, wq, want_dk, dk32, dk64), ("dv", self.n, wv, want_dv, dv32, dv64)):
+        nc = self.held_cols
+        for name, rows, w, want, o32, o64 in (("dq", nq, wq, want_dq, dq32, dq64), ("dk", nc, wq, want_dk, dk32, dk64), ("dv", nc, wv, want_dv, dv32, dv64)):
             want = want or o32 is not None or o64 is not None
             o32, o64, p32, p64, ld = self._prop_outputs(rows, w, on_dev, want and want32, want and want64, o32, o64) if want else (None, None, None, None, w)
             setattr(gr, name + "32", p32.value if p32 is not None else None)
@@ -869,14 +924,14 @@ class Engine:
                 raise RuntimeError("sparse_transpose_fetch(device=True): torch sees no GPU here.  torch and libfora_hip.so must "
                                    "share one HIP runtime: import torch before the first Engine is created")
             dev = torch.device("cuda", self.device)
-            col_ptr = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+            col_ptr = torch.empty(self.held_cols + 1, dtype=torch.int64, device=dev)
             rows = torch.empty(e, dtype=torch.int32, device=dev)
             vals = torch.empty(e, dtype=torch.float64, device=dev)
             fix = torch.empty(e, dtype=torch.int64, device=dev) if want_fix else None
             torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         else:
-            col_ptr = np.zeros(self.n + 1, dtype=np.int64)
+            col_ptr = np.zeros(self.held_cols + 1, dtype=np.int64)
             rows = np.zeros(e, dtype=np.int32)
             vals = np.zeros(e, dtype=np.float64)
             fix = np.zeros(e, dtype=np.uint64) if want_fix else None
@@ -888,7 +943,8 @@ class Engine:
     def _propagate_chunks(self, total, chunk, feat, bf16, want32, want64, normalize, run):
         """the frame of propagate / propagate_seeds: run(i0, i1) leaves the held sparse result of rows [i0, i1) and returns
         its row_ptr; every chunk's product lands in its rows of one [total, d] output"""
-        _, _, d, _, on_dev, _keep = self._prop_feat(feat, bf16)
+        # (over the graph's n nodes, whatever is held now: run() replaces the held result, and a compacted state ends there)
+        _, _, d, _, on_dev, _keep = self._prop_feat(feat, bf16, rows=self.n, shape="[n, d]")
         if on_dev:
             import torch
             dev = torch.device("cuda", self.device)

@@ -19,6 +19,7 @@
 #include "fora_attn.h"
 #include "fora_attn_bwd.h"
 #include "fora_store.h"
+#include "fora_cols.h"
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
@@ -40,7 +41,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -108,6 +109,7 @@ struct Tunables {
     int64_t softmax_short = SMAX_SHORT_MAX; // ROW SOFTMAX (fora_hip_sparse_softmax, fora_hip_sparse_softmax_bwd): a row of at most this many entries (clamped to 0 .. 256, fora_softmax.h) is one wave's, read once and written once; a longer one goes segment by segment through partial maxima and sums; 0: every row does.  Same bits for every value
     int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value.  ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd) reads it for rows (k_attn_bwd_short) and columns (k_attn_cols, fora_attn_bwd_plan.h) alike
     int64_t take_span = STORE_SPAN_DEFAULT; // ROW STORE (fora_hip_store_take; the check of fora_hip_store_load): output entries one workgroup copies, a multiple of 64 and at least 64 (store_span, fora_store_plan.h).  Same bits for every value.  DESIGN.md 5.20 has the runs behind the default
+    int64_t cols_block = COLS_BLOCK_DEFAULT; // COLUMNS (fora_hip_sparse_compact): words of the bitmap one workgroup of k_cols_totals / k_cols_list counts, a power of two from 1 to 4096 (cols_block, fora_cols_plan.h).  Same bits for every value.  DESIGN.md 5.21 has the runs behind the default
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -124,7 +126,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
     {"softmax_short", &Tunables::softmax_short, false}, {"attn_short", &Tunables::attn_short, false},
-    {"take_span", &Tunables::take_span, false},
+    {"take_span", &Tunables::take_span, false}, {"cols_block", &Tunables::cols_block, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -329,6 +331,9 @@ struct SparseResult : HeldRows {
     // top-k rows (fora_sparse_topk.h): the candidate scratch, a CSR of (id, word) over the rows of the chunk in progress, and
     // the chunk's descriptors (the write bases of its rows, then its TopkRow lists)
     DevBuf<int32_t> d_cand_ids; DevBuf<uint64_t> d_cand_fix; DevBuf<uint64_t> d_tkdesc;
+    // COLUMNS (fora_hip_sparse_compact): d_ids hold ranks in the result's own `cols` columns, not node ids.  A flag of its own:
+    // cols == 0 is a legal compacted result.  Ends with the held result (sparse_unheld)
+    bool compacted = false; uint64_t cols = 0;
 };
 // Sweep profile of the last fora_hip_sweep_batch (free_sweep: sweep_clear, set_graph), apart from the workspace and from the
 // sparse result; the buffers of the call in progress live here too.
@@ -394,6 +399,13 @@ struct RowStore {
     DevBuf<int64_t> d_plan; DevBuf<unsigned long long> d_bad;
 };
 
+// COLUMNS (fora_hip_sparse_compact, fora_hip_sparse_cols_fetch): the bitmap over the n nodes, the rank of every word's first set
+// bit, the blocks' totals and offsets, nc, and U itself.  d_cols is U while the held result is compacted (SparseResult::cols
+// entries of it); the rest is scratch of the call in progress.  Grow-only, freed by set_graph and destroy (free_cols).
+struct ColsBufs {
+    DevBuf<unsigned long long> d_bitmap, d_nc; DevBuf<uint32_t> d_wrank, d_btot; DevBuf<int32_t> d_cols;
+};
+
 // The loose words of the context, grouped by role.
 struct Params { // fora_hip_set_params / _raw
     bool have = false;
@@ -426,7 +438,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -436,7 +448,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt; RowStore st;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt; RowStore st; ColsBufs cl;
     bool topk_lds_ready = false; // k_topk_rows<true> may take the whole of a CU's LDS (topk_lds_limit)
     uint64_t sparse_gen = 0;   // fora_hip_get_option "sparse_generation": counts the times a sparse result became held or stopped being held
     int batch_req = 0;        // the caller's request (fora_hip_set_batch), not part of a plan
@@ -467,12 +479,17 @@ void free_graph(fora_ctx *c) { c->g = Graph{}; }
 void sparse_unheld(fora_ctx *c) {
     if (c->sp.valid) c->sparse_gen++;
     c->sp.valid = false; c->sp.entries = 0;
+    c->sp.compacted = false; c->sp.cols = 0;
     if (c->pt.built) { (void)hipSetDevice(c->device); c->pt = PropTBufs{}; }
 }
 void free_sparse(fora_ctx *c) { sparse_unheld(c); c->sp = SparseResult{}; }
 void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
 void free_prop(fora_ctx *c) { c->pr = PropBufs{}; }
 void free_store(fora_ctx *c) { c->st = RowStore{}; }
+void free_cols(fora_ctx *c) { c->cl = ColsBufs{}; }
+// the columns of the held sparse result: the n nodes, or its own nc once fora_hip_sparse_compact has relabelled it.  Every call
+// on the held rows sizes and plans its column side by this
+inline uint64_t held_cols(const fora_ctx *c) { return c->sp.compacted ? c->sp.cols : (uint64_t)c->g.n; }
 void free_index(fora_ctx *c) { c->ix = Index{}; }
 void free_workspace(fora_ctx *c) { c->ws = Workspace{}; }
 
@@ -986,6 +1003,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SDDMM: t.sddmm_ms += ms; break;               // k_prop_sddmm: fora_sddmm_stats only
         case EV_SOFTMAX: t.softmax_ms += ms; break;           // the k_softmax_* kernels of a call: fora_softmax_stats only
         case EV_ATTN: t.attn_ms += ms; break;                 // every launch of an ATTENTION call: fora_attn_stats only
+        case EV_COLS: t.cols_ms += ms; break;                 // the bitmap's clear and the five k_cols_* kernels: fora_cols_stats only
         case EV_STORE: t.store_ms += ms; break;               // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -2616,7 +2634,7 @@ PropIO prop_io(fora_ctx *c, const void *feat, bool bf16, uint64_t feat_rows, int
 int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, const void *values, int val_type,
               float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
     const bool bf16 = feat_type == FORA_PROP_BF16;
-    PropIO io = prop_io(c, feat, bf16, (uint64_t)c->g.n, ldf, d, values, val_type, out32, out64, (uint64_t)nq, ldo);
+    PropIO io = prop_io(c, feat, bf16, held_cols(c), ldf, d, values, val_type, out32, out64, (uint64_t)nq, ldo);
     if (int rc = held_resolve(c, io.values, io.feat, io.o32, io.o64)) return rc;
     const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0, values, val_type == FORA_PROP_F64, nullptr};
     PropRunStats rs;
@@ -2632,7 +2650,7 @@ int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int
 
 // ---- PROPAGATE, TRANSPOSED: the transposition of the held result (fora_propt.h, fora_propt_plan.h), built once per held result
 int propt_build(fora_ctx *c, const int64_t *row_ptr, int nq) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const uint64_t entries = c->sp.entries, n = held_cols(c); // (the columns: the nodes, or the compacted result's own)
     PropTBufs t; // moved into the ctx after the last step; freed on every other way out
     DevBuf<uint32_t> d_cnt; PinBuf<uint32_t> h_cnt; // counts per node, then the cursors of the place pass; their pinned landing area
     DevBuf<uint64_t> d_key; DevBuf<int64_t> d_row_ptr; DevBuf<PropTRun> d_runs;
@@ -2646,7 +2664,7 @@ int propt_build(fora_ctx *c, const int64_t *row_ptr, int nq) {
     if (int rc = prop_ensure(c, d_key, (size_t)entries, what)) return rc;
     if (int rc = prop_ensure(c, d_row_ptr, (size_t)nq + 1, what)) return rc;
     if (int rc = prop_ensure(c, d_runs, (size_t)propt_max_runs(n, entries), what)) return rc;
-    if (h_cnt.alloc((size_t)n) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the transposition's counts"); }
+    if (h_cnt.alloc((size_t)std::max<uint64_t>(n, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the transposition's counts"); }
     t.h_col_ptr.assign((size_t)n + 1, 0);
     t.nq = nq;
     c->tm.propt_transpose_ms = 0;
@@ -2717,7 +2735,7 @@ int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
         HIPCHK(c, hipMemcpy(d_row_ptr.get(), row_ptr, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice));
         EvSpan ev(c, EV_PROPT_TRANSPOSE);
         hipLaunchKernelGGL(k_propt_pos, dim3((unsigned)std::min<uint64_t>((entries + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const int64_t *)t.d_col_ptr.get(),
-                           (uint32_t)c->g.n, (const int32_t *)t.d_rows.get(), (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), entries, d_pos.get());
+                           (uint32_t)held_cols(c), (const int32_t *)t.d_rows.get(), (const int64_t *)d_row_ptr.get(), (uint32_t)nq, (const int32_t *)c->sp.d_ids.get(), entries, d_pos.get());
         ev.end();
         if (int rc = held_call_end(c, "sparse transpose", false)) return rc; // (idle: d_row_ptr goes out of use; the span is collected with the product's)
     }
@@ -2728,14 +2746,14 @@ int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
 int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, const void *values, int val_type,
                float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
     const bool bf16 = grad_type == FORA_PROP_BF16;
-    PropIO io = prop_io(c, grad, bf16, (uint64_t)nq, ldg, d, values, val_type, out32, out64, (uint64_t)c->g.n, ldo);
+    PropIO io = prop_io(c, grad, bf16, (uint64_t)nq, ldg, d, values, val_type, out32, out64, held_cols(c), ldo);
     if (int rc = held_resolve(c, io.feat, io.values, io.o32, io.o64)) return rc; // (before the transposition is built)
     bool built_now = false;
     if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
     double transpose_ms = built_now ? c->tm.propt_transpose_ms : 0.0;
     if (values) if (int rc = propt_ensure_pos(c, row_ptr, nq)) return rc;
     const PropTBufs &t = c->pt;
-    const PropSide sd{t.h_col_ptr.data(), (int)c->g.n, t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
+    const PropSide sd{t.h_col_ptr.data(), (int)held_cols(c), t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
                       values, val_type == FORA_PROP_F64, values ? t.d_pos.get() : nullptr};
     PropRunStats rs;
     if (int rc = prop_run(c, sd, io.feat, io.values, bf16, d, ldg, io.o32, io.o64, rs)) return rc;
@@ -2767,7 +2785,7 @@ int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a_, int 
     const uint64_t entries = c->sp.entries;
     const bool a_bf16 = a_type == FORA_PROP_BF16, b_bf16 = b_type == FORA_PROP_BF16;
     const uint32_t a_elt = a_bf16 ? 2 : 4, b_elt = b_bf16 ? 2 : 4;
-    HeldIn a = HeldIn::matrix(a_, (uint64_t)nq, lda, (uint64_t)d, a_elt), b = HeldIn::matrix(b_, (uint64_t)c->g.n, ldb, (uint64_t)d, b_elt);
+    HeldIn a = HeldIn::matrix(a_, (uint64_t)nq, lda, (uint64_t)d, a_elt), b = HeldIn::matrix(b_, held_cols(c), ldb, (uint64_t)d, b_elt);
     HeldOut<float> o32 = HeldOut<float>::vector(out32, entries);
     HeldOut<double> o64 = HeldOut<double>::vector(out64, entries);
     if (int rc = held_resolve(c, a, b, o32, o64)) return rc;
@@ -2899,7 +2917,7 @@ inline const void *attn_cols(const void *m, uint64_t col, uint32_t elt) { return
 int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk,
                    const void *v_, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
                    float *y32_, double *y64_, fora_attn_stats *st) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const uint64_t entries = c->sp.entries, n = held_cols(c);
     const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16;
     const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4;
     const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
@@ -3024,7 +3042,7 @@ int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, 
                   float *o32, int64_t ld32, double *o64, int64_t ld64) {
     const PropTBufs &t = c->pt;
     const AttnColPlan &cp = t.cols.plan;
-    const uint64_t n = (uint64_t)c->g.n;
+    const uint64_t n = held_cols(c);
     const uint32_t elt = bf16 ? 2 : 4;
     const uint32_t *const widths = prop_widths(bf16);
     HIPCHK(c, attn_zero(c, o32, ld32, n, (uint64_t)heads * (uint64_t)w));
@@ -3049,7 +3067,7 @@ int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, 
 int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk,
                        const void *v_, int v_type, int64_t ldv, const void *g_, int g_type, int64_t ldg, const void *y_, int y_type,
                        int d, int dv, int heads, double scale, const fora_attn_grads &gr, fora_attn_bwd_stats *st) {
-    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const uint64_t entries = c->sp.entries, n = held_cols(c);
     const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16, g_bf16 = g_type == FORA_PROP_BF16;
     const bool y_f64 = y_type == FORA_PROP_F64;
     const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4, g_elt = g_bf16 ? 2 : 4, y_elt = y_f64 ? 8 : 4;
@@ -3233,6 +3251,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_sweep(c);
     free_prop(c);
     free_store(c);
+    free_cols(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
     for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -3268,6 +3287,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_sweep(c);
     free_prop(c); // (the upload of another graph's features)
     free_store(c); // (rows over another graph's nodes)
+    free_cols(c); // (a bitmap over another graph's nodes)
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
@@ -3369,6 +3389,7 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "team_fallbacks")) { *value = (int64_t)c->team_run.fallbacks; return FORA_OK; } // calls re-run with the bucketed push after a team time-out
     if (!strcmp(name, "team_suspended")) { *value = c->team_run.suspend; return FORA_OK; }             // calls left that do not try the team push
     if (!strcmp(name, "sparse_generation")) { *value = (int64_t)c->sparse_gen; return FORA_OK; }    // moves whenever a sparse result becomes held or stops being held
+    if (!strcmp(name, "sparse_cols")) { *value = (int64_t)held_cols(c); return FORA_OK; }           // the columns of the calls on the held rows: n, or nc while a compacted result is held (COLUMNS)
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
     if (!strcmp(name, "walk_dg_wgs_per_cu")) { // k_walk_dg's resident workgroups per CU at this graph's tables (0: the graph has no degree-grouped copy)
         const WalkDG &g = c->g.walk.dg;
@@ -3747,7 +3768,7 @@ int fora_hip_sparse_transpose_fetch(fora_ctx *c, const int64_t *row_ptr, int nq,
     if (int rc = drop_pairs_unless_ok(c, propt_ensure(c, row_ptr, nq, built_now))) return rc;
     const PropTBufs &t = c->pt;
     const uint64_t e = c->sp.entries;
-    if (col_ptr) HIPCHK(c, hipMemcpyAsync(col_ptr, t.d_col_ptr.get(), ((size_t)c->g.n + 1) * 8, hipMemcpyDefault, c->stream));
+    if (col_ptr) HIPCHK(c, hipMemcpyAsync(col_ptr, t.d_col_ptr.get(), ((size_t)held_cols(c) + 1) * 8, hipMemcpyDefault, c->stream));
     if (e && rows) HIPCHK(c, hipMemcpyAsync(rows, t.d_rows.get(), e * 4, hipMemcpyDefault, c->stream));
     if (e && fix) HIPCHK(c, hipMemcpyAsync(fix, t.d_fix.get(), e * 8, hipMemcpyDefault, c->stream));
     if (e && vals) if (int rc = fetch_vals(c, t.d_fix.get(), e, vals, vals_on_device)) return rc;
@@ -3918,6 +3939,78 @@ int fora_hip_sparse_clear(fora_ctx *c) {
     return FORA_OK;
 }
 
+// ---- COLUMNS (the contract of include/fora_hip.h; kernels in fora_cols.h, the arithmetic in fora_cols_plan.h)
+namespace {
+int cols_compact_impl(fora_ctx *c, int64_t *ncols_out, fora_cols_stats *st) {
+    ColsBufs &b = c->cl;
+    const uint64_t entries = c->sp.entries, n = (uint64_t)c->g.n;
+    const uint64_t words = cols_words(n);
+    const uint32_t block = cols_block(c->opt_.cols_block);
+    const uint64_t blocks = cols_blocks(words, block);
+    const uint64_t room = std::min(entries, n); // (no more distinct ids than entries, or than nodes)
+    unsigned long long nc = 0;
+    c->tm.cols_ms = 0;
+    if (entries) {
+        // ---- every buffer before the first launch: a call that finds no room has changed nothing
+        const char *what = "the columns";
+        if (int rc = prop_ensure(c, b.d_bitmap, (size_t)words, what)) return rc;
+        if (int rc = prop_ensure(c, b.d_wrank, (size_t)words, what)) return rc;
+        if (int rc = prop_ensure(c, b.d_btot, 2 * (size_t)blocks, what)) return rc; // totals | offsets
+        if (int rc = prop_ensure(c, b.d_cols, (size_t)room, what)) return rc;
+        if (int rc = prop_ensure(c, b.d_nc, 1, what)) return rc;
+        uint32_t *const tot = b.d_btot.get(), *const off = tot + blocks;
+        const auto grid = [](uint64_t units) { return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(units, 1), 1u << 16)); }; // (the kernels stride over their work)
+        const dim3 flat = grid((entries + BLOCK - 1) / BLOCK);
+        EvSpan ev(c, EV_COLS);
+        HIPCHK(c, hipMemsetAsync(b.d_bitmap.get(), 0, (size_t)words * 8, c->stream));
+        hipLaunchKernelGGL(k_cols_mark, flat, dim3(BLOCK), 0, c->stream, (const int32_t *)c->sp.d_ids.get(), entries, (uint32_t)n, b.d_bitmap.get());
+        hipLaunchKernelGGL(k_cols_totals, grid(blocks), dim3(BLOCK), 0, c->stream, (const unsigned long long *)b.d_bitmap.get(), words, block, blocks, tot);
+        hipLaunchKernelGGL(k_cols_scan, dim3(1), dim3(BLOCK), 0, c->stream, (const uint32_t *)tot, blocks, off, b.d_nc.get());
+        hipLaunchKernelGGL(k_cols_list, grid(blocks), dim3(BLOCK), 0, c->stream, (const unsigned long long *)b.d_bitmap.get(), words, block, blocks, (const uint32_t *)off,
+                           b.d_wrank.get(), b.d_cols.get(), room);
+        hipLaunchKernelGGL(k_cols_relabel, flat, dim3(BLOCK), 0, c->stream, c->sp.d_ids.get(), entries, (uint32_t)n, (const unsigned long long *)b.d_bitmap.get(),
+                           (const uint32_t *)b.d_wrank.get());
+        ev.end();
+        // (a failure behind the first launch: the ids are neither the old nor the new ones for all we know, nothing stays held)
+        if (const hipError_t e = hipMemcpyAsync(&nc, b.d_nc.get(), sizeof(nc), hipMemcpyDeviceToHost, c->stream); e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            sparse_unheld(c);
+            return fail(c, FORA_E_HIP, std::string("sparse compact: ") + hipGetErrorString(e));
+        }
+    }
+    if (int rc = held_call_end(c, "sparse compact")) { sparse_unheld(c); return rc; }
+    if (nc > room) { sparse_unheld(c); return fail(c, FORA_E_HIP, "sparse compact: more columns than the held entries or the nodes"); }
+    // ---- the held result is over its own columns from here on: the ids changed, so the transposition goes and the generation moves
+    c->sp.compacted = true; c->sp.cols = nc;
+    c->pt = PropTBufs{};
+    c->sparse_gen++;
+    *ncols_out = (int64_t)nc;
+    if (st) { st->entries = entries; st->cols = nc; st->words = entries ? words : 0; st->cols_ms = c->tm.cols_ms; }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_sparse_compact(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *ncols_out, fora_cols_stats *st) {
+    if (int rc = held_call_begin(c, "sparse compact", row_ptr, nq)) return rc;
+    if (!ncols_out) return fail(c, FORA_E_ARG, "sparse compact: ncols_out is required");
+    if (c->sp.compacted) return fail(c, FORA_E_ARG, "sparse compact: the held result is compacted already");
+    if (st) memset(st, 0, sizeof(*st));
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, cols_compact_impl(c, ncols_out, st));
+}
+
+int fora_hip_sparse_cols_fetch(fora_ctx *c, int32_t *cols, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid || !c->sp.compacted) return fail(c, FORA_E_ARG, "sparse cols fetch: no compacted sparse result is held");
+    if (cap < c->sp.cols) return fail(c, FORA_E_ARG, "sparse cols fetch: cap is smaller than the held columns");
+    if (c->sp.cols && !cols) return fail(c, FORA_E_ARG, "sparse cols fetch: null cols");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool on_device = false;
+    if (cols) if (int rc = sparse_dest(c, cols, on_device)) return rc;
+    if (c->sp.cols) HIPCHK(c, hipMemcpyAsync(cols, c->cl.d_cols.get(), c->sp.cols * 4, hipMemcpyDefault, c->stream));
+    return held_call_end(c, "sparse cols fetch", false);
+}
+
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)
 namespace {
 // a plan on the device: out_ptr | src | win in the store's plan buffer
@@ -4048,6 +4141,7 @@ int store_take_impl(fora_ctx *c, const int64_t *rows, int nb, int64_t *row_ptr_o
 
 int fora_hip_store_put(fora_ctx *c, const int64_t *row_ptr, int nq, int append, fora_store_stats *st) {
     if (int rc = held_call_begin(c, "store put", row_ptr, nq)) return rc;
+    if (c->sp.compacted) return fail(c, FORA_E_ARG, "store put: the held result is compacted (the store holds node ids)");
     if (st) memset(st, 0, sizeof(*st));
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, store_add(c, "store put", row_ptr, nq, c->sp.d_ids.get(), true, c->sp.d_fix.get(), true, false, append != 0, st));

@@ -3,7 +3,11 @@
 rows are computed once and whose H = MLP(X) changes at every step.  With the caller's values on the held pattern
 (ppr_propagate(values=), ppr_sddmm, ppr_row_softmax, row_softmax, ppr_attention, ppr_attention_fused) the three operations are each other's gradients, so
 attention over the held neighbourhoods, a learned temperature or a re-weighting stay inside the library.  Import torch before the first Engine is created, so that
-the library and torch share one HIP runtime.  fora_amd/__init__.py does not import this module: the package needs no torch."""
+the library and torch share one HIP runtime.  fora_amd/__init__.py does not import this module: the package needs no torch.
+Wherever an operand or a gradient below has n rows, n is the engine's held column count (Engine.held_cols): the nodes of the
+graph, or, after Engine.sparse_compact / store_take_compact, the nc nodes `cols` that the held rows touch -- pass X[cols] and
+autograd carries the gradient back through that index.  A compaction between a forward and its backward pass makes the
+backward pass raise, like any other change of the held rows."""
 import torch
 
 
@@ -107,10 +111,10 @@ class _PprSddmm(torch.autograd.Function):
 
 def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
     """Z = (held sparse rows of `engine`) x H as a differentiable torch operation.  row_ptr: as query_sparse /
-    query_seeds_sparse returned it (a numpy array or a tensor).  H: [n, d] float32 or bfloat16 on the engine's GPU, column
-    stride one element.  Returns Z [nq, d] float32 on the device; Z.backward(G) leaves H.grad = (held rows)^T x G in H's
-    dtype.  The rows must still be held when the backward pass runs: a query_sparse, query_seeds_sparse, sparse_clear or
-    set_graph in between makes it raise.
+    query_seeds_sparse returned it (a numpy array or a tensor).  H: [n, d] (n = engine.held_cols) float32 or bfloat16 on the
+    engine's GPU, column stride one element.  Returns Z [nq, d] float32 on the device; Z.backward(G) leaves H.grad = (held rows)^T x G in H's
+    dtype.  The rows must still be held when the backward pass runs: a query_sparse, query_seeds_sparse, store_take,
+    sparse_compact, sparse_clear or set_graph in between makes it raise.
     values: a float32 or float64 tensor of `entries` elements on the device, one per held entry in held order, used as the
     weights in place of the PPR values (Engine.sparse_propagate(values=)); the result is then differentiable in both H and
     values -- H.grad by the transposed product with the same values, values.grad = ppr_sddmm(G, H).  Not together with
@@ -124,7 +128,7 @@ def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
 
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
-    the device, differentiable in A ([nq, d]) and B ([n, d]), float32 or bfloat16 tensors on the engine's GPU with a column
+    the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32 or bfloat16 tensors on the engine's GPU with a column
     stride of one element: A.grad = P(g) x B and B.grad = P(g)^T x A, the two products with the scores' gradient g as values.
     The rows must still be held when the backward pass runs."""
     return _PprSddmm.apply(A, B, engine, row_ptr)
@@ -241,8 +245,9 @@ class _PprAttentionFusedBwd(_PprAttentionFused):
 def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1, backward="calls"):
     """ppr_attention with all three steps in ONE library call (Engine.sparse_attention, the ATTENTION contract): the rows of at
     most 256 entries are scored, normalised and multiplied by one wave each without anything written in between, and nothing
-    is rounded to float32 between the steps.  Q: [nq, heads * d], K: [n, heads * d], V: [n, heads * dv], float32 or bfloat16
-    on the engine's GPU; head j attends with the columns [j * d, (j + 1) * d) of Q and K and writes the columns
+    is rounded to float32 between the steps.  Q: [nq, heads * d], K: [n, heads * d], V: [n, heads * dv] (n =
+    engine.held_cols: over a compacted result K and V are the rows `cols` of the full matrices), float32 or bfloat16 on the
+    engine's GPU; head j attends with the columns [j * d, (j + 1) * d) of Q and K and writes the columns
     [j * dv, (j + 1) * dv) of the result, [nq, heads * dv] float32.  scale defaults to d ** -0.5 and is a number, not a
     differentiable operand.  Differentiable in Q, K and V: the backward pass runs head by head with the calls ppr_attention
     (softmax="engine") uses, on the float32 probabilities the forward call saved.  The rows must still be held when it runs.
@@ -263,7 +268,7 @@ def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1, backward=
 def ppr_attention(engine, row_ptr, Q, K, V, scale=None, softmax="torch"):
     """Attention of every row over its held neighbourhood: out[i] = sum over the entries e of row i of
     softmax_row(scale * <Q[i], K[id_e]>)_e * V[id_e] -- ppr_propagate(V, values=row_softmax(ppr_sddmm(Q, K) * scale)).
-    Q: [nq, d], K: [n, d], V: [n, dv]; scale defaults to d ** -0.5.  Differentiable in Q, K and V.
+    Q: [nq, d], K: [n, d], V: [n, dv] (n = engine.held_cols); scale defaults to d ** -0.5.  Differentiable in Q, K and V.
     softmax: "torch" (the default) takes the softmax with row_softmax, plain torch; "engine" with ppr_row_softmax, scale
     folded into the call -- all three steps in the library, forward and backward, every bit defined; "fused" is
     ppr_attention_fused with one head -- the forward pass in one library call."""

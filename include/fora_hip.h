@@ -534,6 +534,38 @@
  *     of the call's own rows (the move of the rows that stay, when an append outgrows its room, is not in it).
  *   - a NULL ctx is answered without touching the GPU (FORA_E_ARG).  A held sweep profile, the walk index, the options, the
  *     FORA parameters and fora_timing are left untouched by all five; the ctx's stream is idle when they return.
+ * COLUMNS (fora_hip_sparse_compact, fora_hip_sparse_cols_fetch): the held sparse result re-expressed over its own columns -- the
+ * node set of a mini-batch.  1000 top-64 rows touch at most 64 000 of a graph's n nodes; after a compaction every call on the
+ * held rows has nc columns instead of n, nc the number of distinct ids among the held entries.
+ *   - fora_hip_sparse_compact works on whatever sparse result is held (plain, top-k, seed sets, taken from the store); row_ptr
+ *     is validated exactly as in PROPAGATE.  U is the set of the distinct ids among the held entries in ascending order; it is
+ *     kept on the device.  Every held id is replaced in place by its rank in U, a number in [0, nc) with nc = |U|; the words
+ *     and row_ptr are untouched.  The relabelling is monotone: ids still ascend strictly inside a row, and every contract
+ *     above holds on the compacted result with nc in the place of n.  *ncols_out = nc (required).
+ *   - from then on, and for as long as that result is held, EVERY call on the held rows uses nc where it uses n: feat of
+ *     PROPAGATE, b of SCORES, k and v of ATTENTION have nc rows; the output of PROPAGATE, TRANSPOSED and dk / dv of ATTENTION,
+ *     BACKWARD have nc rows, and nothing wider is read, cleared or written; the transposition has nc columns and
+ *     fora_hip_sparse_transpose_fetch writes nc + 1 entries of col_ptr, none of its columns empty.  With operand rows
+ *     X_loc[j] = X[U[j]] every call gives, bit for bit, what it gives on the uncompacted result with X; the outputs over columns
+ *     are the uncompacted ones' rows U (whose other rows are +0.0).  fora_hip_sparse_fetch returns the local ids.
+ *   - a compaction drops the transposition (it was over n columns) and moves "sparse_generation": the ids changed, and a
+ *     backward pass must not run on rows other than its forward pass saw.  fora_hip_get_option("sparse_cols") reads nc while
+ *     a compacted result is held and n otherwise.
+ *   - the compacted state ends wherever the held result ends: every call that makes a new held result (fora_hip_store_take
+ *     included), fora_hip_sparse_clear, fora_hip_set_graph.  The next result is over the n nodes again.
+ *   - zero held entries: FORA_OK, nc = 0, U empty.  A result that is compacted already, a NULL ncols_out, no held result or a
+ *     row_ptr that is not its own: FORA_E_ARG, nothing changed.  No device memory: FORA_E_NOMEM, nothing changed.  A device
+ *     failure behind the first launch leaves nothing held.
+ *   - fora_hip_sparse_cols_fetch copies U out: nc int32 node ids, ascending, to pageable host memory or to device memory on the
+ *     ctx's GPU (memory of another GPU is FORA_E_ARG).  No compacted result held, or cap < nc: FORA_E_ARG.
+ *   - fora_hip_store_put of a compacted result is FORA_E_ARG, the store unchanged: the store holds node ids.
+ *   - no bit depends on the option "cols_block" (the bitmap words one workgroup counts: a power of two from 1 to 4096, other
+ *     values are clamped and rounded down to one; readable from the environment like the other non-schedule knobs), on the
+ *     launch shape, or on the order in which the device meets the entries: the bitmap is written with OR alone.
+ *   - stats (fora_cols_stats): entries = the held entries; cols = nc; words = the bitmap words scanned, ceil(n / 64) (0 without
+ *     entries); cols_ms = the device time of the bitmap's clear and of the call's kernels.
+ *   - a NULL ctx is answered without touching the GPU (FORA_E_ARG).  The store, a held sweep profile, the walk index, the
+ *     options, the FORA parameters and fora_timing are left untouched; the ctx's stream is idle when both return.
  */
 #ifndef FORA_HIP_H
 #define FORA_HIP_H
@@ -836,6 +868,13 @@ int fora_hip_store_take(fora_ctx *ctx, const int64_t *rows /*nb, host*/, int nb,
                         fora_store_stats *st /*or NULL*/);
 int fora_hip_store_info(fora_ctx *ctx, int64_t *rows, uint64_t *entries, uint64_t *max_row);
 int fora_hip_store_clear(fora_ctx *ctx);
+
+/* ---- the held result over its own columns (the COLUMNS contract above): compact relabels the held ids to ranks in the
+ * ascending set U of the distinct ones, cols_fetch copies U out. */
+typedef struct { uint64_t entries, cols, words; double cols_ms; } fora_cols_stats;
+int fora_hip_sparse_compact(fora_ctx *ctx, const int64_t *row_ptr /*nq+1*/, int nq, int64_t *ncols_out /*required*/,
+                            fora_cols_stats *st /*or NULL*/);
+int fora_hip_sparse_cols_fetch(fora_ctx *ctx, int32_t *cols /*host or device*/, uint64_t cap);
 
 /* ---- local clustering (the SWEEP CUT contract above): fora_hip_query_batch, then per row the sweep over ppr / degree and
  * its best cut, all on the GPU.  The profile stays with the ctx until fetched or replaced. */
