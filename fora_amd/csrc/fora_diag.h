@@ -13,6 +13,7 @@
 //            FORA_PROBE_STORE=off / FORA_PROBE_STORE2=1|2 / FORA_PROBE_GATHER        k_push_team (profiles/r05_team_probes.txt)
 //            FORA_PROBE_BIN_LOAD / _RANK / _STORE / _SYNC / _LDS                     k_pushq_bin  (profiles/r06_wide_probes.txt)
 //            FORA_PROBE_ACC_LOAD / _ATOM / _SWEEP                                    k_accum<false>
+//   counts   FORA_COUNT_STAGED      k_walk_dg: stamps[4] = results the waves' stages sent to the sub-buckets, stamps[5] = flushes, [6] = full ones
 //   fakes    FORA_DG_FAKE_STEP0 / FORA_DG_FAKE_ALL   k_walk_dg with its gathers bent into a 4-KB window: WRONG results, timing floor only
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +22,7 @@
 #if defined(FORA_STAMPS) || defined(FORA_STAMPS_SMALL) || defined(FORA_STAMPS_LEVELS) || defined(FORA_PROBE_STORE) || defined(FORA_PROBE_STORE2) || \
     defined(FORA_PROBE_GATHER) || defined(FORA_PROBE_BIN_LOAD) || defined(FORA_PROBE_BIN_RANK) || defined(FORA_PROBE_BIN_STORE) ||              \
     defined(FORA_PROBE_BIN_SYNC) || defined(FORA_PROBE_BIN_LDS) || defined(FORA_PROBE_ACC_LOAD) || defined(FORA_PROBE_ACC_ATOM) ||               \
-    defined(FORA_PROBE_ACC_SWEEP) || defined(FORA_DG_FAKE_STEP0) || defined(FORA_DG_FAKE_ALL)
+    defined(FORA_PROBE_ACC_SWEEP) || defined(FORA_DG_FAKE_STEP0) || defined(FORA_DG_FAKE_ALL) || defined(FORA_COUNT_STAGED)
 #define FORA_DIAG_BUILD 1
 #else
 #define FORA_DIAG_BUILD 0
@@ -106,6 +107,19 @@ __device__ __forceinline__ uint64_t team_gather_probe(const uint64_t *tb, uint32
 #else
     (void)tb; (void)entry; (void)have;
     return 0;
+#endif
+}
+
+// ---- stage_flush (fora_kernels.h): what a flush of a wave's stage sent; full: by the progress rule of the aligned flush
+__device__ __forceinline__ void flush_sent(unsigned long long *stamps, uint32_t sent, bool full) {
+#ifdef FORA_COUNT_STAGED
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&stamps[4], (unsigned long long)sent);
+        atomicAdd(&stamps[5], 1ull);
+        if (full) atomicAdd(&stamps[6], 1ull);
+    }
+#else
+    (void)stamps; (void)sent; (void)full;
 #endif
 }
 

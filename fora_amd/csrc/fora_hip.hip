@@ -23,6 +23,7 @@
 #include "../../include/fora_hip.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +60,8 @@ struct Tunables {
     int64_t hubs_wide = -1;      // the same for graphs that run the wide layout in one pass per level; -1: 2048 up to 2^28 edges, else 0 (off); read by set_graph.
                                  // LJ-sized push of 280 queries: 0 -> 560.8 ms, 1024 -> 558.7, 2048 -> 550.6, 4096 -> 681.6; Twitter-2010-sized: no gain (the top 2048 of 41.6 M nodes receive few of the edges)
     int64_t hub_min = 4096;      // ... in levels whose frontier holds at least this many nodes of the slot
+    int64_t walk_flush_align = DG_FLUSH_ALIGN; // k_walk_dg: a flush of a wave's result stage stores whole aligned lines of this many results per bin and keeps the rest (stage_flush<.., G>, fora_flush_plan.h): 0 every flush sends all it holds, 8 lines of 64 bytes, 16 of 128.  Same bits for every value.  DESIGN.md 5.3 has the runs behind the default
+    int64_t walk_flush_keep = 0; // ... results a wave's stage may keep at most (0: half the stage); a flush that would keep more sends everything.  Same bits for every value
     int64_t dg_hubs = 0;         // hub records of that copy (0: the fewest that leave <= 255 degree classes); read by set_graph
     int64_t bkcap = 0;           // bucket capacity in messages (0: default per layout)
     int64_t ovcap = 0;           // overflow list capacity (0: scales with the graph)
@@ -114,7 +117,7 @@ struct Tunables {
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
     {"direct", &Tunables::direct, true}, {"force_wide", &Tunables::force_wide, true}, {"pass_bins", &Tunables::pass_bins, true},
-    {"no_split", &Tunables::no_split, true}, {"no_compact", &Tunables::no_compact, false}, {"walk_dg", &Tunables::walk_dg, false}, {"dg_hubs", &Tunables::dg_hubs, false}, {"hubs", &Tunables::hubs, true}, {"hubs_wide", &Tunables::hubs_wide, true}, {"hub_min", &Tunables::hub_min, false}, {"bkcap", &Tunables::bkcap, true},
+    {"no_split", &Tunables::no_split, true}, {"no_compact", &Tunables::no_compact, false}, {"walk_dg", &Tunables::walk_dg, false}, {"walk_flush_align", &Tunables::walk_flush_align, false}, {"walk_flush_keep", &Tunables::walk_flush_keep, false}, {"dg_hubs", &Tunables::dg_hubs, false}, {"hubs", &Tunables::hubs, true}, {"hubs_wide", &Tunables::hubs_wide, true}, {"hub_min", &Tunables::hub_min, false}, {"bkcap", &Tunables::bkcap, true},
     {"ovcap", &Tunables::ovcap, true}, {"tiny", &Tunables::tiny, false}, {"xb", &Tunables::xb, false}, {"ax", &Tunables::ax, false},
     {"wx", &Tunables::wx, false}, {"tail", &Tunables::tail, false}, {"tail_always", &Tunables::tail_always, false},
     {"select_compact", &Tunables::select_compact, false}, {"team", &Tunables::team, true}, {"team_size", &Tunables::team_size, true}, {"team_tail", &Tunables::team_tail, false}, {"team_xcd", &Tunables::team_xcd, false}, {"team_max", &Tunables::team_max, true}, {"team_hubs", &Tunables::team_hubs, true}, {"team_log", &Tunables::team_log, false}, {"topk_bk_div", &Tunables::topk_bk_div, true}, {"quads", &Tunables::quads, false}, {"team_timeout_ms", &Tunables::team_timeout_ms, false}, {"team_abort_level", &Tunables::team_abort_level, false}, {"acc_group", &Tunables::acc_group, false}, {"slot_major", &Tunables::slot_major, false}, {"team_coop", &Tunables::team_coop, false}, {"tail_hubs", &Tunables::tail_hubs, false}, {"rounds", &Tunables::rounds, false}, {"defer", &Tunables::defer, true}, {"defer_min", &Tunables::defer_min, false}, {"round_div", &Tunables::round_div, false},
@@ -577,7 +580,9 @@ static WsPlan plan_workspace(const fora_ctx *c, double omega_hint, int slots) {
             // (k_push_tail: ONE workgroup per slot; the slab sweeps; the walk kernels) works on that many more slots at once.
             // A round that does overflow is run again with doubled buckets like any other (with_bucket_retry)
             cap = std::min<uint64_t>(std::max<uint64_t>(cap * (c->retry.div > 1 ? c->retry.scale_topk : c->retry.scale) / std::max<uint32_t>(1, c->retry.div), 64), 1u << 28);
-            p.bk_cap = (uint32_t)((cap + 15) & ~15ull);
+            // whole 128-byte lines: every sub-bucket then starts on one, which the aligned flush of k_walk_dg counts on
+            p.bk_cap = (uint32_t)((cap + FLUSH_LINE_MAX - 1) & ~(uint64_t)(FLUSH_LINE_MAX - 1));
+            assert(p.bk_cap % FLUSH_LINE_MAX == 0 && FLUSH_LINE_MAX * sizeof(uint64_t) == 128);
         }
         p.segq_cap = n;
         p.ov_cap = c->opt_.ovcap > 0 ? (uint32_t)c->opt_.ovcap : (uint32_t)std::max<uint64_t>(262144, n / 8); // scales with the graph; the option: tests
@@ -941,6 +946,7 @@ Dev make_dev(fora_ctx *c, int nq, bool with_idx, double rmax = -1, double omega 
     d.dbm_words = p.dbm_words; d.segq_cap = p.segq_cap;
     d.ov_w = w.d_ov_w.get(); d.ov_inc = w.d_ov_inc.get(); d.ov_cap = p.ov_cap;
     d.bk_w = w.d_bk_w.get(); d.bk_inc = w.d_bk_inc.get(); d.bk_count = w.d_bk_count.get(); d.bk_cap = p.bk_cap; d.sub = p.sub;
+    d.flush_keep = (uint32_t)std::min<int64_t>(std::max<int64_t>(c->opt_.walk_flush_keep, 0), DG_STAGE);
     if (with_idx) { d.rw_idx = c->ix.d_rw_idx.get(); d.idx_off = c->ix.d_idx_off.get(); d.idx_cnt = c->ix.d_idx_cnt.get(); }
     return d;
 }
@@ -1818,8 +1824,29 @@ int sweep_finish(fora_ctx *c, SweepRun &sw, int64_t *row_ptr, fora_sweep_row *ro
 // refinement launches after k_walk_alloc: indexed walks, online walks, and the accumulate of their results
 // k_walk_dg as the launch selects it: the instantiation, and the bytes of its tables in dynamic LDS (fora_tables.h)
 typedef void (*WalkDgKernel)(Dev, uint32_t);
-static WalkDgKernel walk_dg_kernel(bool nzh, bool bits32, bool xl) {
-    switch ((nzh ? 4 : 0) | (bits32 ? 2 : 0) | (xl ? 1 : 0)) {
+// the option "walk_flush_align" as the kernels know it: results per aligned line of a flush, 0 / 8 / 16
+static int walk_flush_align(const fora_ctx *c) { const int64_t v = c->opt_.walk_flush_align; return v >= 16 ? 16 : v >= 8 ? 8 : 0; }
+template <int G>
+static WalkDgKernel walk_dg_arm(int which) {
+    switch (which) {
+    case 0: return k_flush_arm_walk_dg<G, false, false, false>;
+    case 1: return k_flush_arm_walk_dg<G, false, false, true>;
+    case 2: return k_flush_arm_walk_dg<G, false, true, false>;
+    case 3: return k_flush_arm_walk_dg<G, false, true, true>;
+    case 4: return k_flush_arm_walk_dg<G, true, false, false>;
+    case 5: return k_flush_arm_walk_dg<G, true, false, true>;
+    case 6: return k_flush_arm_walk_dg<G, true, true, false>;
+    default: return k_flush_arm_walk_dg<G, true, true, true>;
+    }
+}
+static WalkDgKernel walk_dg_kernel(bool nzh, bool bits32, bool xl, int align) {
+    const int which = (nzh ? 4 : 0) | (bits32 ? 2 : 0) | (xl ? 1 : 0);
+    if (align != DG_FLUSH_ALIGN) { // the other arms of the flush (every arm has the default's LDS and launch shape)
+        if constexpr (DG_FLUSH_ALIGN != 0) if (align == 0) return walk_dg_arm<0>(which);
+        if constexpr (DG_FLUSH_ALIGN != 8) if (align == 8) return walk_dg_arm<8>(which);
+        if constexpr (DG_FLUSH_ALIGN != 16) if (align == 16) return walk_dg_arm<16>(which);
+    }
+    switch (which) {
     case 0: return k_walk_dg<false, false, false>;
     case 1: return k_walk_dg<false, false, true>;
     case 2: return k_walk_dg<false, true, false>;
@@ -1861,7 +1888,7 @@ void launch_walks(fora_ctx *c, const Dev &d, int nq, bool with_idx, uint32_t rou
     Dev dw = d;
     if (xl) { dw.nbins = (int32_t)d.dg.nbx; dw.acc_xl = d.dg.invb; }
     if (dg) {
-        hipLaunchKernelGGL(walk_dg_kernel(nzh != 0, d.dg.bits32 != 0, xl), wgs, dim3(DG_THREADS), walk_dg_lds(d.dg, xl), c->stream, dw, round);
+        hipLaunchKernelGGL(walk_dg_kernel(nzh != 0, d.dg.bits32 != 0, xl, walk_flush_align(c)), wgs, dim3(DG_THREADS), walk_dg_lds(d.dg, xl), c->stream, dw, round);
     } else
         hipLaunchKernelGGL(k_walk_online<WALK_TO_PPR>, p.binned && !d.wide ? wgs : wg, dim3(BLOCK), 0, c->stream, d, round, nzh, (int32_t *)nullptr);
     ev.end();
@@ -3397,7 +3424,7 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
         if (g.colp) {
             const bool xl = c->opt_.walk_dg != 1 && g.invb;
             (void)hipSetDevice(c->device);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, (const void *)walk_dg_kernel(false, g.bits32 != 0, xl), DG_THREADS, walk_dg_lds(g, xl)) != hipSuccess)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, (const void *)walk_dg_kernel(false, g.bits32 != 0, xl, walk_flush_align(c)), DG_THREADS, walk_dg_lds(g, xl)) != hipSuccess)
                 return fail(c, FORA_E_HIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor(k_walk_dg)");
         }
         *value = wgs;

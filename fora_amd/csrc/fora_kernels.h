@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "fora_consts.h"
 #include "fora_diag.h"
+#include "fora_flush_plan.h"
 
 namespace fora {
 
@@ -314,6 +315,7 @@ struct Dev {
     uint32_t *bk_count;     // [slot][bin][sub]
     uint32_t bk_cap;        // capacity of ONE sub-bucket
     uint32_t sub;           // sub-buckets per bucket (<= MAX_SUB)
+    uint32_t flush_keep;    // k_walk_dg: results an aligned flush may keep in a wave's stage (option "walk_flush_keep"; 0: half the stage; fora_flush_plan.h)
     // messages that found their bucket full (rare; capacity is a tuning knob): per-slot overflow list,
     // folded in by k_accum.  Count is double-buffered by level parity (zeroed one level later).
     uint32_t *ov_w;         // [slot][ov_cap]
@@ -2398,6 +2400,7 @@ struct WaveStage {
     uint32_t *bbase; // [MAX_BINS]; not used by the one-array form (stage_flush<.., ONE = true>)
     uint32_t *fill;  // [MAX_BINS] of the WORKGROUP: messages in its sub-bucket of every bin (see Dev::bk_w)
     uint32_t count;  // wave-uniform
+    uint32_t carried; // stage_flush<.., G > 0>: the first `carried` results were kept by the previous flush (wave-uniform)
     const uint32_t *xl; // not null: destinations are in WalkDG bucket order, original id = xl[dest] (only the direct-atomic fallbacks need it)
 };
 // XLD (k_walk_dg<.., XL = true>): an entry's low word holds the endpoint's copy id less H, and its place in WalkDG bucket
@@ -2405,8 +2408,13 @@ struct WaveStage {
 // ONE (k_walk_dg): the wave has a single bin array.  bcnt holds the bins' counts, then their first stage slot while the stage
 // is sorted, then (first slot in the sub-bucket) - (first stage slot), so that entry m of the sorted stage goes to bcnt[bin] + m:
 // half the LDS of the two-array form with every word still 32 bits wide -- a sub-bucket may be longer than 65 535.
-template <int ST, bool XLD = false, bool ONE = false>
-__device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) {
+// G > 0 (k_walk_dg, with ONE): the flush stores whole aligned lines of G results per bin and keeps the rest of every bin in the
+// stage (fora_flush_plan.h has the rule: head, send, the cap `keep` with its full flush, the slots).  The stage is rebuilt from
+// registers as kept results | sent results, both by bin; `carried` counts the kept ones, which are in bucket order already.
+// all: send everything (the kernel's closing flush).  G = 0: `keep` and `all` are not read, every result leaves.
+template <int ST, bool XLD = false, bool ONE = false, int G = 0>
+__device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st, uint32_t keep = 0, bool all = true) {
+    static_assert(G == 0 || (ONE && (G & (G - 1)) == 0 && ST <= (int)FLUSH_SLOT_MASK), "lines of a power of two of results; a bin's word holds three stage slots");
     const int lane = threadIdx.x & 63;
     const uint64_t slab = (uint64_t)q * d.n;
     // workgroup x fills sub-bucket x of every bin (SubBuckets; only the two words the flush needs: the walk kernels are short of SGPRs)
@@ -2418,13 +2426,15 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     uint32_t rk[ST / 64];
     uint64_t wv[ST / 64];
     uint32_t dl0 = 0, dl1 = 0; // ONE: (bin's first slot in the sub-bucket) - (its first stage slot), bins lane and lane + 64
+    uint32_t kept = 0;         // G: results that stay in the stage, slots 0 .. kept - 1 (wave-uniform)
+    bool full = false;         // G: the progress rule sent everything
 #pragma unroll
     for (int k = 0; k < ST / 64; k++) {
         const uint32_t m = k * 64 + lane;
         wv[k] = NONE;
         if (m < st.count) {
             wv[k] = st.pk[m];
-            if (XLD) {
+            if (XLD && (G == 0 || m >= st.carried)) {
                 const uint32_t lo = (uint32_t)wv[k], u = lo & ((1u << WPACK_SHIFT) - 1), blk = u >> 6;
                 const uint32_t qd = __umulhi(blk, d.dg.nbx_magic); // blk / nbx
                 const uint32_t dest = ((blk - qd * d.dg.nbx) << BIN_SHIFT) | (qd << 6) | (u & 63u);
@@ -2434,7 +2444,30 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
         }
     }
     __builtin_amdgcn_wave_barrier();
-    { // space in the workgroup's sub-buckets: one LDS atomic per (flush, bin) on the workgroup's fill counters; and the
+    if (G) { // what every bin sends and keeps, space in the sub-buckets for what it sends, and the bins' words for the sort
+        const uint32_t c0 = lane < d.nbins ? st.bcnt[lane] : 0, c1 = lane + 64 < d.nbins ? st.bcnt[lane + 64] : 0;
+        uint32_t s0 = c0, s1 = c1;
+        if (!all) { // (the fills are read ahead of the adds below: fora_flush_plan.h)
+            s0 = flush_send(c0, st.fill[lane], (uint32_t)G);
+            s1 = flush_send(c1, st.fill[lane + 64], (uint32_t)G);
+        }
+        // one scan for both: sent results in the low half, kept ones in the high half (each sum is at most ST)
+        uint32_t t0, t1;
+        const uint32_t x0 = wave_excl_scan(s0 | ((c0 - s0) << 16), t0), x1 = wave_excl_scan(s1 | ((c1 - s1) << 16), t1) + t0;
+        kept = (t0 + t1) >> 16;
+        uint32_t sb0 = x0 & 0xFFFFu, kb0 = x0 >> 16, sb1 = x1 & 0xFFFFu, kb1 = x1 >> 16;
+        if (flush_full(kept, keep)) { // progress rule: everything leaves, bin by bin as it stands
+            full = true;
+            s0 = c0; s1 = c1;
+            sb0 += kb0; sb1 += kb1;
+            kb0 = kb1 = 0;
+            kept = 0;
+        }
+        if (s0) dl0 = atomicAdd(&st.fill[lane], s0) - (kept + sb0);
+        if (s1) dl1 = atomicAdd(&st.fill[lane + 64], s1) - (kept + sb1);
+        st.bcnt[lane] = FlushBin::make(s0, kb0, sb0).w;
+        st.bcnt[lane + 64] = FlushBin::make(s1, kb1, sb1).w;
+    } else { // space in the workgroup's sub-buckets: one LDS atomic per (flush, bin) on the workgroup's fill counters; and the
       // bins' offsets inside the wave's stage
         const uint32_t c0 = lane < d.nbins ? st.bcnt[lane] : 0, c1 = lane + 64 < d.nbins ? st.bcnt[lane + 64] : 0;
         uint32_t t0, t1;
@@ -2454,7 +2487,10 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     // bucket slots: one write request per run instead of one per walk
 #pragma unroll
     for (int k = 0; k < ST / 64; k++)
-        if (wv[k] != NONE) st.pk[st.bcnt[((uint32_t)wv[k] & ((1u << WPACK_SHIFT) - 1)) >> BIN_SHIFT] + rk[k]] = wv[k];
+        if (wv[k] != NONE) {
+            const uint32_t bw = st.bcnt[((uint32_t)wv[k] & ((1u << WPACK_SHIFT) - 1)) >> BIN_SHIFT];
+            st.pk[G ? FlushBin{bw}.slot(rk[k], kept) : bw + rk[k]] = wv[k];
+        }
     __builtin_amdgcn_wave_barrier();
     if (ONE) { // (the sort has read the bins' stage slots)
         st.bcnt[lane] = dl0;
@@ -2463,7 +2499,7 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
     }
 #pragma unroll
     for (int k = 0; k < ST / 64; k++) {
-        const uint32_t m = k * 64 + lane;
+        const uint32_t m = kept + k * 64 + lane; // (the sent results lie behind the kept ones)
         if (m < st.count) {
             const uint64_t pk = st.pk[m];
             const uint32_t dd = (uint32_t)pk & ((1u << WPACK_SHIFT) - 1);
@@ -2476,11 +2512,13 @@ __device__ __forceinline__ void stage_flush(const Dev &d, int q, WaveStage &st) 
         }
     }
     __builtin_amdgcn_wave_barrier();
-    st.count = 0;
+    diag::flush_sent(d.stamps, st.count - kept, full); // (nothing in the product build)
+    st.count = kept;
+    if (G) st.carried = kept;
 }
 // CHECKW false: the caller has dealt with the weights that do not fit the packed word
-template <int ST, bool XLD = false, bool CHECKW = true, bool ONE = false>
-__device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, bool has, uint32_t dest, uint64_t w) {
+template <int ST, bool XLD = false, bool CHECKW = true, bool ONE = false, int G = 0>
+__device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, bool has, uint32_t dest, uint64_t w, uint32_t keep = 0) {
     if (CHECKW && has && w >= WPACK_MAXW) { // does not fit the packed word (tiny walk budgets only)
         atomicAdd((unsigned long long *)&d.ppr[(uint64_t)q * d.n + (st.xl ? st.xl[dest] : dest)], (unsigned long long)w);
         has = false;
@@ -2492,7 +2530,7 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
         st.pk[pos] = (uint64_t)dest | (w << WPACK_SHIFT);
     }
     st.count += (uint32_t)__popcll(mask);
-    if (st.count > ST - 64) stage_flush<ST, XLD, ONE>(d, q, st);
+    if (st.count > ST - 64) stage_flush<ST, XLD, ONE, G>(d, q, st, keep, false);
 }
 #define WAVE_STAGE_DECL_N(st, NWAVES, ST)                                                           \
     __shared__ uint64_t st##_pk[NWAVES][ST];                                                        \
@@ -2501,7 +2539,7 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
     WaveStage st;                                                                                   \
     st.pk = st##_pk[threadIdx.x >> 6];                                                              \
     st.bcnt = st##_bcnt[threadIdx.x >> 6]; st.bbase = st##_bbase[threadIdx.x >> 6];                 \
-    st.fill = st##_fill; st.count = 0; st.xl = nullptr;
+    st.fill = st##_fill; st.count = 0; st.carried = 0; st.xl = nullptr;
 // the one-array form (stage_flush / stage_emit <.., ONE = true>)
 #define WAVE_STAGE_DECL_ONE(st, NWAVES, ST)                                                         \
     __shared__ uint64_t st##_pk[NWAVES][ST];                                                        \
@@ -2510,7 +2548,7 @@ __device__ __forceinline__ void stage_emit(const Dev &d, int q, WaveStage &st, b
     WaveStage st;                                                                                   \
     st.pk = st##_pk[threadIdx.x >> 6];                                                              \
     st.bcnt = st##_bcnt[threadIdx.x >> 6]; st.bbase = nullptr;                                      \
-    st.fill = st##_fill; st.count = 0; st.xl = nullptr;
+    st.fill = st##_fill; st.count = 0; st.carried = 0; st.xl = nullptr;
 #define WAVE_STAGE_DECL(st) WAVE_STAGE_DECL_N(st, BLOCK / 64, STAGE)
 
 // ---- indexed part of the refinement (query.h:290-296, 301-306): walks jj < idx_n of an item
@@ -2785,6 +2823,14 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FORA
 //   40 664 B -- does not come from LDS alone: at this kernel's 106 SGPRs a SIMD holds 7 waves, so the CU still takes three
 //   workgroups; with FORA_DG_WPE = 8 the compiler keeps to 80 SGPRs by spilling 49 of them to lanes, and four do run
 //   (profiles/walk_dg_lds.txt has both).
+// The flush (stage_flush<.., ONE, G>, G = DG_FLUSH_ALIGN = 8): per bin it stores whole aligned 64-byte lines of the workgroup's
+//   sub-bucket -- 8 results -- and keeps the bin's last 0 .. 7 in the stage for the next flush, in the stage itself: no LDS added,
+//   63 VGPRs.  The stores are non-temporal, so nothing merged the partial lines at both ends of the ~9-result runs a plain flush
+//   writes: 682 M write requests of 47 bytes per step became 370 M of 64, WRITE_SIZE 32.3 -> 23.8 GB, for 6 % more vector
+//   instructions (a flush is longer, and the carried results bring the next one sooner).  walk kernel 79.7-80.0 -> 78.1-78.4 ms,
+//   ms_per_step 140.1-140.3 -> 138.5-138.8.  Lines of 128 bytes (G = 16) carry ~260 of the 384 slots, pass the cap at most flushes,
+//   which then send everything unaligned, and run at the plain flush's speed; so does a cap of 64.  Options "walk_flush_align" /
+//   "walk_flush_keep" select the arms (k_flush_arm_walk_dg) at run time; profiles/walk_dg_aligned_flush.txt, DESIGN.md 5.3.
 #ifndef FORA_DG_THREADS
 #define FORA_DG_THREADS 512
 #endif
@@ -2815,8 +2861,9 @@ __device__ __forceinline__ uint32_t dg_colp_at(const WalkDG &g, uint32_t e) {
     const uint64_t both = ((uint64_t)cw.b << 32) | cw.a;
     return (uint32_t)(both >> sh) & ((1u << g.bits) - 1u);
 }
-template <bool NZH, bool BITS32, bool XL>
-__global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu(FORA_DG_WPE, 8))) k_walk_dg(Dev d, uint32_t round) {
+// G: results per aligned line of the flush (stage_flush<.., G>; 0: every flush sends all it holds)
+template <bool NZH, bool BITS32, bool XL, int G>
+__device__ __forceinline__ void walk_dg_body(const Dev &d, uint32_t round) {
     constexpr int NW = DG_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) uint64_t dg_lds64[]; // (16-byte aligned: the records below are read as uint4) // XL: hub accumulators [H] (u64) | records [nrec] (16 bytes each: classes, then hubs) | T[nblk] (bytes)
     // Walk items are staged per WAVE, WT at a time: a walk that has started lives in its lane's registers, so the wave
@@ -2861,6 +2908,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
     uint32_t steps = 0;
     WAVE_STAGE_DECL_ONE(st, NW, DG_STAGE)
     if (XL) st.xl = g.invb;
+    const uint32_t keep = flush_keep_cap(DG_STAGE, d.flush_keep); // (read where a flush needs it: a kernel argument)
     uint32_t *bkc = d.bk_count + (uint64_t)q * d.pbins * d.sub + blockIdx.x; // count of bin b: bkc[b * sub]
     for (uint32_t i = threadIdx.x; i < (uint32_t)MAX_BINS; i += DG_THREADS) st.fill[i] = i < (uint32_t)d.nbins ? bkc[(uint64_t)i * d.sub] : 0;
     if (threadIdx.x == 0) s_ticket = 0;
@@ -2897,7 +2945,7 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
             atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[dn]], sv);
             has = false;
         }
-        stage_emit<DG_STAGE, true, false, true>(d, q, st, has, dn - H, (uint64_t)sv);
+        stage_emit<DG_STAGE, true, false, true, G>(d, q, st, has, dn - H, (uint64_t)sv, keep);
     };
     // The workgroup's tiles are those of its NW waves under a static stride (x * NW + w, + tstride, ...), handed out in that
     // order to whichever wave runs out of walks first: one returning LDS add per tile.  Tiles differ by up to 30x in walks (a
@@ -3020,16 +3068,16 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
             if (away && cur < H) atomicAdd(&s_hub[cur], (unsigned long long)wgt); // LDS
             const bool over = big && wgt >= WPACK_MAXW; // does not fit the packed word (tiny walk budgets only)
             if (away && cur >= H && over) atomicAdd((unsigned long long *)&d.ppr[slab + g.inv[cur]], (unsigned long long)wgt);
-            stage_emit<DG_STAGE, true, false, true>(d, q, st, away && cur >= H && !over, cur - H, wgt); // (the place in bucket order: stage_flush)
+            stage_emit<DG_STAGE, true, false, true, G>(d, q, st, away && cur >= H && !over, cur - H, wgt, keep); // (the place in bucket order: stage_flush)
         } else {
-            stage_emit<DG_STAGE, false, true, true>(d, q, st, pend, pend_node, pend_w);
+            stage_emit<DG_STAGE, false, true, true, G>(d, q, st, pend, pend_node, pend_w, keep);
             pend = fin;
             if (pend) { pend_node = g.inv[cur]; pend_w = wgt; }
         }
     }
-    if (!XL) stage_emit<DG_STAGE, false, true, true>(d, q, st, pend, pend_node, pend_w);
+    if (!XL) stage_emit<DG_STAGE, false, true, true, G>(d, q, st, pend, pend_node, pend_w, keep);
     if (gen) flush_self();
-    if (st.count) stage_flush<DG_STAGE, XL, true>(d, q, st);
+    if (st.count) stage_flush<DG_STAGE, XL, true, G>(d, q, st, keep, true); // the closing flush sends everything
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < (uint32_t)d.nbins; i += DG_THREADS) bkc[(uint64_t)i * d.sub] = st.fill[i];
     if (XL) for (uint32_t i = threadIdx.x; i < H; i += DG_THREADS) { // the hubs' share of this workgroup's walks
@@ -3045,6 +3093,21 @@ __global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu
         for (int w = 0; w < NW; w++) bs += s_w[w];
         if (bs) atomicAdd(d.tot_steps, bs);
     }
+}
+
+// The kernel the launch selects by default flushes by FORA_DG_FLUSH_ALIGN; k_flush_arm_walk_dg<G, ..> are the arms of the
+// option "walk_flush_align" (0, 8, 16), the same body.
+#ifndef FORA_DG_FLUSH_ALIGN
+#define FORA_DG_FLUSH_ALIGN 8
+#endif
+constexpr int DG_FLUSH_ALIGN = FORA_DG_FLUSH_ALIGN;
+template <bool NZH, bool BITS32, bool XL>
+__global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu(FORA_DG_WPE, 8))) k_walk_dg(Dev d, uint32_t round) {
+    walk_dg_body<NZH, BITS32, XL, DG_FLUSH_ALIGN>(d, round);
+}
+template <int G, bool NZH, bool BITS32, bool XL>
+__global__ void __launch_bounds__(DG_THREADS) __attribute__((amdgpu_waves_per_eu(FORA_DG_WPE, 8))) k_flush_arm_walk_dg(Dev d, uint32_t round) {
+    walk_dg_body<NZH, BITS32, XL, G>(d, round);
 }
 
 // ------------------------------------------------------------------ epilogue / hooks
