@@ -1,34 +1,19 @@
 """ctypes binding of libfora_hip.so (include/fora_hip.h).  Thin: every method is
-one C-ABI call; errors raise ForaError with fora_hip_last_error()."""
+one C-ABI call; errors raise ForaError with fora_hip_last_error().
+
+The C ABI is stated once here: the struct mirrors, and _ABI, one row per function, which load() binds (restype and
+argtypes) on whatever the library exports -- so a call passes plain Python values and ctypes converts, or refuses,
+each of them.  A new entry point takes three steps: its prototype in include/fora_hip.h, its row in _ABI (a struct of
+its own: a mirror in STRUCTS), one Engine method.  tests/test_capi_cpu.py derives every row and every mirror from the
+header again and fails until they match."""
 import ctypes as C
 import os
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
 FIX_ONE = 1 << 62
 STREAM_INDEX = 0xFFFFFFFF
-
-SYMBOLS = [
-    "fora_hip_create", "fora_hip_destroy", "fora_hip_device_count", "fora_hip_last_error", "fora_hip_device_info",
-    "fora_hip_set_graph", "fora_hip_set_params", "fora_hip_set_params_raw", "fora_hip_get_params",
-    "fora_hip_set_batch", "fora_hip_get_batch", "fora_hip_set_option", "fora_hip_get_option", "fora_hip_set_balanced", "fora_hip_index_sizes", "fora_hip_build_index",
-    "fora_hip_get_index", "fora_hip_set_index", "fora_hip_clear_index", "fora_hip_query_batch",
-    "fora_hip_query_batch_fix", "fora_hip_topk_batch", "fora_hip_topk_bound_batch", "fora_hip_power_iteration_batch", "fora_hip_push_batch", "fora_hip_walk_counts",
-    "fora_hip_walks", "fora_hip_reset_timing", "fora_hip_get_timing", "fora_hip_get_stamps",
-    "fora_hip_montecarlo_batch", "fora_hip_fwdpush_batch", "fora_hip_bippr_batch", "fora_hip_bippr_targets_batch", "fora_hip_bwdpush_batch",
-    "fora_hip_query_sparse_batch", "fora_hip_sparse_fetch", "fora_hip_sparse_clear",
-    "fora_hip_query_seeds_batch",
-    "fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear",
-    "fora_hip_seeds_sparse_batch", "fora_hip_seeds_sweep_batch",
-    "fora_hip_sparse_propagate", "fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch",
-    "fora_hip_query_sparse_topk_batch", "fora_hip_seeds_sparse_topk_batch",
-    "fora_hip_sparse_sddmm", "fora_hip_sparse_propagate_vals", "fora_hip_sparse_propagate_t_vals",
-    "fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd", "fora_hip_sparse_attention", "fora_hip_sparse_attention_bwd",
-    "fora_hip_store_put", "fora_hip_store_load", "fora_hip_store_take", "fora_hip_store_info", "fora_hip_store_clear",
-    "fora_hip_sparse_compact", "fora_hip_sparse_cols_fetch",
-]
 BWD_FIX_ONE = 1 << 60
 
 
@@ -38,158 +23,205 @@ class ForaError(RuntimeError):
         self.code = code
 
 
+# ---- the C ABI: the types of include/fora_hip.h by the names the rows below use.  Every data pointer is "ptr" (c_void_p:
+# host or device memory, or a scalar out-parameter; it takes _p(array), byref(x), a data_ptr() integer and None), a
+# pointer to a fora_* struct is POINTER(its mirror) ("sparse_stats*": an array of the mirror, a byref or None)
+_TYPES = {"void": None, "int": C.c_int, "int32": C.c_int32, "uint32": C.c_uint32, "int64": C.c_int64, "uint64": C.c_uint64,
+          "double": C.c_double, "str": C.c_char_p, "ptr": C.c_void_p, "ctx*": C.c_void_p, "ctx**": C.POINTER(C.c_void_p)}
+
+
+def _fields(spec):
+    """the _fields_ of a mirror from its declaration, "uint64 entries max_row; int32 batches" """
+    return [(name, _TYPES[t]) for t, *names in (part.split() for part in spec.split(";")) for name in names]
+
+
+class _Stats(C.Structure):
+    """a mirror that reads out as a dict; padding (a name that ends in "_": reserved_, pad_) is left out"""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_")}
+
+
+def _np_dtype(mirror):
+    """the structured numpy dtype of an array of a mirror (st[i]["pops"] as on a list of dicts)"""
+    dt = np.dtype([(name, np.dtype(ct)) for name, ct in mirror._fields_], align=True)
+    assert dt.itemsize == C.sizeof(mirror)
+    return dt
+
+
 class QueryStats(C.Structure):
-    _fields_ = [("rsum", C.c_double), ("rsum_fix", C.c_uint64), ("n_rw", C.c_uint64),
-                ("n_walks", C.c_uint64), ("n_idx_hit", C.c_uint64), ("pops", C.c_uint64),
-                ("relax", C.c_uint64), ("ppr_sum_fix", C.c_uint64), ("levels", C.c_int32),
-                ("dangling_source", C.c_int32), ("rmax_used", C.c_double), ("push_rounds", C.c_int32),
-                ("reserved_", C.c_int32)]
+    _fields_ = _fields("double rsum; uint64 rsum_fix n_rw n_walks n_idx_hit pops relax ppr_sum_fix; int32 levels dangling_source;"
+                       "double rmax_used; int32 push_rounds reserved_")
 
 
-_STATS_DTYPE = np.dtype([(name, {C.c_double: np.float64, C.c_uint64: np.uint64, C.c_int32: np.int32}[ct])
-                         for name, ct in QueryStats._fields_], align=True)
-assert _STATS_DTYPE.itemsize == C.sizeof(QueryStats)
+class Timing(_Stats):
+    _fields_ = _fields("double push_pop_ms push_expand_ms push_accum_ms walk_alloc_ms walk_ms walk_accum_ms other_ms batch_ms;"
+                       "uint64 push_pop_launches push_expand_launches push_accum_launches walk_launches batches pops relax walks"
+                       " walk_steps levels idx_hits; double push_tail_ms; uint64 push_tail_launches; double push_team_ms;"
+                       "uint64 push_team_launches")
 
 
-class Timing(C.Structure):
-    _fields_ = [("push_pop_ms", C.c_double), ("push_expand_ms", C.c_double), ("push_accum_ms", C.c_double), ("walk_alloc_ms", C.c_double),
-                ("walk_ms", C.c_double), ("walk_accum_ms", C.c_double), ("other_ms", C.c_double), ("batch_ms", C.c_double),
-                ("push_pop_launches", C.c_uint64), ("push_expand_launches", C.c_uint64), ("push_accum_launches", C.c_uint64),
-                ("walk_launches", C.c_uint64), ("batches", C.c_uint64), ("pops", C.c_uint64),
-                ("relax", C.c_uint64), ("walks", C.c_uint64), ("walk_steps", C.c_uint64),
-                ("levels", C.c_uint64), ("idx_hits", C.c_uint64), ("push_tail_ms", C.c_double), ("push_tail_launches", C.c_uint64),
-                ("push_team_ms", C.c_double), ("push_team_launches", C.c_uint64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class BwdStats(_Stats):
+    _fields_ = _fields("uint64 targets pops relax entries global_targets; int32 levels chunks; double bwd_ms walk_ms combine_ms")
 
 
-class BwdStats(C.Structure):
-    _fields_ = [("targets", C.c_uint64), ("pops", C.c_uint64), ("relax", C.c_uint64), ("entries", C.c_uint64),
-                ("global_targets", C.c_uint64), ("levels", C.c_int32), ("chunks", C.c_int32), ("bwd_ms", C.c_double),
-                ("walk_ms", C.c_double), ("combine_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class SparseStats(_Stats):
+    _fields_ = _fields("uint64 entries max_row thr_fix; int32 batches reserved_; double compact_ms")
 
 
-class SparseStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("max_row", C.c_uint64), ("thr_fix", C.c_uint64), ("batches", C.c_int32),
-                ("reserved_", C.c_int32), ("compact_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+class TopkStats(_Stats):
+    _fields_ = _fields("uint64 support max_support k; int32 cut_rows lds_rows global_rows chunks; double select_ms")
 
 
-class TopkStats(C.Structure):
-    _fields_ = [("support", C.c_uint64), ("max_support", C.c_uint64), ("k", C.c_uint64), ("cut_rows", C.c_int32),
-                ("lds_rows", C.c_int32), ("global_rows", C.c_int32), ("chunks", C.c_int32), ("select_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class SeedsStats(C.Structure):
-    _fields_ = [("seeds", C.c_uint64), ("distinct", C.c_uint64), ("queries", C.c_uint64), ("dangling", C.c_uint64),
-                ("batches", C.c_int32), ("reserved_", C.c_int32), ("combine_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+class SeedsStats(_Stats):
+    _fields_ = _fields("uint64 seeds distinct queries dangling; int32 batches reserved_; double combine_ms")
 
 
 class SweepRow(C.Structure):
-    _fields_ = [("len", C.c_int64), ("best", C.c_int64), ("cut", C.c_uint64), ("vol", C.c_uint64), ("den", C.c_uint64),
-                ("conductance", C.c_double)]
+    _fields_ = _fields("int64 len best; uint64 cut vol den; double conductance")
 
 
-_SWEEP_ROW_DTYPE = np.dtype([(name, {C.c_double: np.float64, C.c_uint64: np.uint64, C.c_int64: np.int64}[ct])
-                             for name, ct in SweepRow._fields_], align=True)
-assert _SWEEP_ROW_DTYPE.itemsize == C.sizeof(SweepRow)
+class SweepStats(_Stats):
+    _fields_ = _fields("uint64 entries max_row thr_fix edges; int32 batches global_rows; double compact_ms sort_ms cut_ms")
 
 
-class SweepStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("max_row", C.c_uint64), ("thr_fix", C.c_uint64), ("edges", C.c_uint64),
-                ("batches", C.c_int32), ("global_rows", C.c_int32), ("compact_ms", C.c_double), ("sort_ms", C.c_double),
-                ("cut_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class PropStats(_Stats):
+    _fields_ = _fields("uint64 entries segments max_row feat_bytes; int32 chunks feat_on_device; double gather_ms combine_ms")
 
 
-class PropStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("feat_bytes", C.c_uint64),
-                ("chunks", C.c_int32), ("feat_on_device", C.c_int32), ("gather_ms", C.c_double), ("combine_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class PropTStats(_Stats):
+    _fields_ = _fields("uint64 entries columns segments max_col feat_bytes;"
+                       "int32 chunks feat_on_device built short_cols lds_cols global_cols; double transpose_ms gather_ms combine_ms")
 
 
-class PropTStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("columns", C.c_uint64), ("segments", C.c_uint64), ("max_col", C.c_uint64), ("feat_bytes", C.c_uint64),
-                ("chunks", C.c_int32), ("feat_on_device", C.c_int32), ("built", C.c_int32), ("short_cols", C.c_int32), ("lds_cols", C.c_int32),
-                ("global_cols", C.c_int32), ("transpose_ms", C.c_double), ("gather_ms", C.c_double), ("combine_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class SddmmStats(_Stats):
+    _fields_ = _fields("uint64 entries segments max_row bytes; int32 a_on_device b_on_device; double sddmm_ms")
 
 
-class SddmmStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("bytes", C.c_uint64),
-                ("a_on_device", C.c_int32), ("b_on_device", C.c_int32), ("sddmm_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class SoftmaxStats(_Stats):
+    _fields_ = _fields("uint64 entries segments max_row nan_rows short_rows long_rows; int32 in_on_device grad_on_device;"
+                       "double softmax_ms")
 
 
-class SoftmaxStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("nan_rows", C.c_uint64),
-                ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("in_on_device", C.c_int32), ("grad_on_device", C.c_int32),
-                ("softmax_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class AttnStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("nan_rows", C.c_uint64),
-                ("short_rows", C.c_uint64), ("long_rows", C.c_uint64), ("q_on_device", C.c_int32), ("k_on_device", C.c_int32),
-                ("v_on_device", C.c_int32), ("pad_", C.c_int32), ("attn_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+class AttnStats(_Stats):
+    _fields_ = _fields("uint64 entries segments max_row nan_rows short_rows long_rows;"
+                       "int32 q_on_device k_on_device v_on_device pad_; double attn_ms")
 
 
 class AttnGrads(C.Structure):
     """fora_attn_grads: the outputs of fora_hip_sparse_attention_bwd, each gradient as f32 and / or f64 with one pitch"""
-    _fields_ = [("dq32", C.c_void_p), ("dq64", C.c_void_p), ("lddq", C.c_int64),
-                ("dk32", C.c_void_p), ("dk64", C.c_void_p), ("lddk", C.c_int64),
-                ("dv32", C.c_void_p), ("dv64", C.c_void_p), ("lddv", C.c_int64)]
+    _fields_ = _fields("ptr dq32 dq64; int64 lddq; ptr dk32 dk64; int64 lddk; ptr dv32 dv64; int64 lddv")
 
 
-class AttnBwdStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("segments", C.c_uint64), ("max_row", C.c_uint64), ("short_rows", C.c_uint64), ("long_rows", C.c_uint64),
-                ("columns", C.c_uint64), ("max_col", C.c_uint64), ("short_cols", C.c_uint64), ("long_cols", C.c_uint64),
-                ("built", C.c_int32), ("plan_cached", C.c_int32),
-                ("q_on_device", C.c_int32), ("k_on_device", C.c_int32), ("v_on_device", C.c_int32), ("g_on_device", C.c_int32),
-                ("y_on_device", C.c_int32), ("pad_", C.c_int32), ("transpose_ms", C.c_double), ("attn_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+class AttnBwdStats(_Stats):
+    _fields_ = _fields("uint64 entries segments max_row short_rows long_rows columns max_col short_cols long_cols;"
+                       "int32 built plan_cached q_on_device k_on_device v_on_device g_on_device y_on_device pad_;"
+                       "double transpose_ms attn_ms")
 
 
-class StoreStats(C.Structure):
-    _fields_ = [("rows", C.c_uint64), ("entries", C.c_uint64), ("max_row", C.c_uint64), ("store_rows", C.c_uint64), ("store_entries", C.c_uint64),
-                ("ids_on_device", C.c_int32), ("fix_on_device", C.c_int32), ("store_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class StoreStats(_Stats):
+    _fields_ = _fields("uint64 rows entries max_row store_rows store_entries; int32 ids_on_device fix_on_device; double store_ms")
 
 
-class ColsStats(C.Structure):
-    _fields_ = [("entries", C.c_uint64), ("cols", C.c_uint64), ("words", C.c_uint64), ("cols_ms", C.c_double)]
+class ColsStats(_Stats):
+    _fields_ = _fields("uint64 entries cols words; double cols_ms")
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+
+_STATS_DTYPE, _SWEEP_ROW_DTYPE = _np_dtype(QueryStats), _np_dtype(SweepRow)
+STRUCTS = {"fora_query_stats": QueryStats, "fora_timing": Timing, "fora_bwd_stats": BwdStats, "fora_sparse_stats": SparseStats,
+           "fora_seeds_stats": SeedsStats, "fora_sweep_row": SweepRow, "fora_sweep_stats": SweepStats, "fora_prop_stats": PropStats,
+           "fora_propt_stats": PropTStats, "fora_sddmm_stats": SddmmStats, "fora_softmax_stats": SoftmaxStats,
+           "fora_attn_stats": AttnStats, "fora_attn_grads": AttnGrads, "fora_attn_bwd_stats": AttnBwdStats,
+           "fora_store_stats": StoreStats, "fora_cols_stats": ColsStats, "fora_topk_stats": TopkStats}
+_TYPES.update({name[len("fora_"):] + "*": C.POINTER(mirror) for name, mirror in STRUCTS.items()})
+
+# one row per function, as the header declares it without the parameter names; "test": one of the TEST ENTRY POINTS of
+# include/fora_hip.h, in libfora_hip_test.so (TEST_LIB) only
+_ABI = """
+int  fora_hip_device_count()
+int  fora_hip_create(int, ctx**)
+void fora_hip_destroy(ctx*)
+str  fora_hip_last_error(ctx*)
+int  fora_hip_device_info(ctx*, str, int, ptr, ptr)
+int  fora_hip_set_graph(ctx*, int32, int64, ptr, ptr)
+int  fora_hip_set_params(ctx*, double, double, double, int, uint64)
+int  fora_hip_set_params_raw(ctx*, double, double, double, int, uint64)
+int  fora_hip_get_params(ctx*, ptr, ptr)
+int  fora_hip_set_balanced(ctx*, int, double, double, double, double, double)
+int  fora_hip_set_batch(ctx*, int)
+int  fora_hip_get_batch(ctx*)
+int  fora_hip_set_option(ctx*, str, int64)
+int  fora_hip_get_option(ctx*, str, ptr)
+int  fora_hip_index_sizes(ctx*, ptr, ptr, ptr)
+int  fora_hip_build_index(ctx*)
+int  fora_hip_get_index(ctx*, ptr, uint64, ptr, ptr)
+int  fora_hip_set_index(ctx*, ptr, uint64, ptr, ptr)
+int  fora_hip_clear_index(ctx*)
+int  fora_hip_query_batch(ctx*, ptr, int, int, ptr, query_stats*)
+int  fora_hip_query_batch_fix(ctx*, ptr, int, int, ptr, ptr, query_stats*)
+int  fora_hip_query_sparse_batch(ctx*, ptr, int, int, double, ptr, query_stats*, sparse_stats*)
+int  fora_hip_sparse_fetch(ctx*, ptr, ptr, ptr, uint64)
+int  fora_hip_sparse_clear(ctx*)
+int  fora_hip_sparse_propagate(ctx*, ptr, int, ptr, int, int, int64, int, ptr, ptr, int64, prop_stats*)
+int  fora_hip_sparse_propagate_t(ctx*, ptr, int, ptr, int, int, int64, int, ptr, ptr, int64, propt_stats*)
+int  fora_hip_sparse_propagate_vals(ctx*, ptr, int, ptr, int, int, int64, int, ptr, int, ptr, ptr, int64, prop_stats*)
+int  fora_hip_sparse_propagate_t_vals(ctx*, ptr, int, ptr, int, int, int64, int, ptr, int, ptr, ptr, int64, propt_stats*)
+int  fora_hip_sparse_sddmm(ctx*, ptr, int, ptr, int, int64, ptr, int, int64, int, ptr, ptr, uint64, sddmm_stats*)
+int  fora_hip_sparse_softmax(ctx*, ptr, int, ptr, int, double, ptr, ptr, uint64, softmax_stats*)
+int  fora_hip_sparse_softmax_bwd(ctx*, ptr, int, ptr, int, ptr, int, double, ptr, ptr, uint64, softmax_stats*)
+int  fora_hip_sparse_attention(ctx*, ptr, int, ptr, int, int64, ptr, int, int64, ptr, int, int64, int, int, int, double, ptr, ptr, int64, ptr, ptr, uint64, attn_stats*)
+int  fora_hip_sparse_attention_bwd(ctx*, ptr, int, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, uint64, int, int, int, double, attn_grads*, attn_bwd_stats*)
+int  fora_hip_sparse_transpose_fetch(ctx*, ptr, int, ptr, ptr, ptr, ptr, uint64)
+int  fora_hip_store_put(ctx*, ptr, int, int, store_stats*)
+int  fora_hip_store_load(ctx*, ptr, int64, ptr, ptr, int, store_stats*)
+int  fora_hip_store_take(ctx*, ptr, int, ptr, store_stats*)
+int  fora_hip_store_info(ctx*, ptr, ptr, ptr)
+int  fora_hip_store_clear(ctx*)
+int  fora_hip_sparse_compact(ctx*, ptr, int, ptr, cols_stats*)
+int  fora_hip_sparse_cols_fetch(ctx*, ptr, uint64)
+int  fora_hip_sweep_batch(ctx*, ptr, int, int, double, int64, ptr, sweep_row*, query_stats*, sweep_stats*)
+int  fora_hip_sweep_fetch(ctx*, ptr, ptr, ptr, uint64)
+int  fora_hip_sweep_clear(ctx*)
+int  fora_hip_query_seeds_batch(ctx*, ptr, ptr, ptr, int, int, ptr, ptr, int, ptr, ptr, ptr, seeds_stats*)
+int  fora_hip_seeds_sparse_batch(ctx*, ptr, ptr, ptr, int, int, double, ptr, ptr, seeds_stats*, sparse_stats*)
+int  fora_hip_query_sparse_topk_batch(ctx*, ptr, int, int, double, int64, ptr, query_stats*, sparse_stats*, topk_stats*)
+int  fora_hip_seeds_sparse_topk_batch(ctx*, ptr, ptr, ptr, int, int, double, int64, ptr, ptr, seeds_stats*, sparse_stats*, topk_stats*)
+int  fora_hip_seeds_sweep_batch(ctx*, ptr, ptr, ptr, int, int, double, int64, ptr, sweep_row*, seeds_stats*, sweep_stats*)
+int  fora_hip_topk_batch(ctx*, ptr, int, int, double, double, int, ptr, ptr, ptr)
+int  fora_hip_topk_bound_batch(ctx*, ptr, int, int, double, double, double, int, ptr, ptr, ptr)
+int  fora_hip_power_iteration_batch(ctx*, ptr, int, int, ptr, ptr, int, ptr, ptr)
+int  fora_hip_montecarlo_batch(ctx*, ptr, int, double, ptr, ptr, int, ptr, ptr, query_stats*)
+int  fora_hip_fwdpush_batch(ctx*, ptr, int, double, double, ptr, ptr, ptr, int, ptr, ptr, query_stats*)
+int  fora_hip_bippr_batch(ctx*, ptr, int, double, double, ptr, ptr, int, ptr, ptr, query_stats*, bwd_stats*)
+int  fora_hip_bippr_targets_batch(ctx*, ptr, int, ptr, int, double, double, ptr, ptr, query_stats*, bwd_stats*)
+int  fora_hip_push_batch(ctx*, ptr, int, ptr, ptr, query_stats*)
+int  fora_hip_bwdpush_batch(ctx*, ptr, int, double, ptr, ptr, bwd_stats*)
+int  fora_hip_walk_counts(ctx*, ptr, double, ptr, ptr)
+int  fora_hip_walks(ctx*, uint32, uint32, int, ptr, ptr, int64, ptr)
+int  fora_hip_reset_timing(ctx*)
+int  fora_hip_get_timing(ctx*, timing*)
+int  fora_hip_get_stamps(ctx*, ptr)
+test int fora_hip_test_sweep_rows(ctx*, ptr, int, double, int64, ptr, sweep_row*, sweep_stats*)
+test int fora_hip_test_sparse_rows(ctx*, ptr, int, double, ptr, sparse_stats*)
+test int fora_hip_test_sparse_topk_rows(ctx*, ptr, int, double, int64, ptr, sparse_stats*, topk_stats*)
+test int fora_hip_test_sweep_scan(ctx*, ptr, ptr, int64, uint64, ptr)
+test int fora_hip_test_exp(ctx*, ptr, int64, ptr)
+"""
+
+
+def _rows(text):
+    """{name: (test_only, restype, argtypes)} of the rows of _ABI"""
+    out = {}
+    for row in text.strip().splitlines():
+        *mark, ret, sig = row.split(None, 2) if row.startswith("test ") else row.split(None, 1)
+        name, args = sig.rstrip(")").split("(")
+        out[name] = (bool(mark), _TYPES[ret], [_TYPES[a] for a in args.split(", ") if a])
+    return out
+
+
+ABI = _rows(_ABI)
+SYMBOLS = [name for name, row in ABI.items() if not row[0]]
+TEST_SYMBOLS = [name for name, row in ABI.items() if row[0]]  # TEST_LIB only
 
 
 PROP_SEG = 256  # FORA_PROP_SEG
@@ -209,34 +241,29 @@ def lib_path():
     return os.environ.get("FORA_HIP_LIB") or os.path.join(_HERE, "libfora_hip.so")
 
 
-_OTHER = {}
+TEST_LIB = os.path.join(_HERE, "libfora_hip_test.so")  # -DFORA_TEST_PATHS=1: threshold rounds / bounded deferral compiled in
+_LIBS = {}
+
+
+def _bind(lib):
+    """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
+    product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
+    for name, (_, restype, argtypes) in ABI.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 def load(path=None):
     """Loads the in-tree HIP library (path: another build of it -- libfora_hip_test.so, the build with the schedule
     experiments compiled in, for their twin-equivalence tests).  Fails loudly when it has not been built."""
-    global _LIB
-    if path is not None:
-        if path not in _OTHER:
-            if not os.path.exists(path):
-                raise ImportError(f"{path} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-            lib = C.CDLL(path)
-            lib.fora_hip_last_error.restype = C.c_char_p
-            lib.fora_hip_destroy.restype = None
-            _OTHER[path] = lib
-        return _OTHER[path]
-    if _LIB is None:
-        p = lib_path()
-        if not os.path.exists(p):
-            raise ImportError(f"{p} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _LIB = C.CDLL(p)
-        _LIB.fora_hip_last_error.restype = C.c_char_p
-        _LIB.fora_hip_destroy.restype = None
-    return _LIB
-
-
-TEST_LIB = os.path.join(_HERE, "libfora_hip_test.so")  # -DFORA_TEST_PATHS=1: threshold rounds / bounded deferral compiled in
-TEST_SYMBOLS = ["fora_hip_test_sweep_rows", "fora_hip_test_sweep_scan"]  # the TEST ENTRY POINTS of include/fora_hip.h: TEST_LIB only
+    path = path or lib_path()
+    if path not in _LIBS:
+        if not os.path.exists(path):
+            raise ImportError(f"{path} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        _LIBS[path] = _bind(C.CDLL(path))
+    return _LIBS[path]
 
 
 def _p(a):
@@ -249,7 +276,7 @@ class Engine:
     def __init__(self, device=0, lib=None):
         self._lib = load(lib)
         self._ctx = C.c_void_p()
-        rc = self._lib.fora_hip_create(C.c_int(device), C.byref(self._ctx))
+        rc = self._lib.fora_hip_create(device, C.byref(self._ctx))
         if rc:
             raise ForaError(rc, "fora_hip_create failed (no gfx950 GPU visible?)")
         self.n = 0
@@ -273,22 +300,20 @@ class Engine:
     def device_info(self):
         arch = C.create_string_buffer(64)
         cus, hbm = C.c_int(0), C.c_uint64(0)
-        self._chk(self._lib.fora_hip_device_info(self._ctx, arch, C.c_int(64), C.byref(cus), C.byref(hbm)))
+        self._chk(self._lib.fora_hip_device_info(self._ctx, arch, 64, C.byref(cus), C.byref(hbm)))
         return arch.value.decode(), cus.value, hbm.value
 
     def set_graph(self, n, m_attr, row_ptr, col):
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
         col = np.ascontiguousarray(col, dtype=np.int32)
-        self._chk(self._lib.fora_hip_set_graph(self._ctx, C.c_int32(n), C.c_int64(m_attr), _p(row_ptr), _p(col)))
+        self._chk(self._lib.fora_hip_set_graph(self._ctx, n, m_attr, _p(row_ptr), _p(col)))
         self.n = int(n)
 
     def set_params(self, alpha=0.2, epsilon=0.5, rmax_scale=1.0, opt=False, seed=0):
-        self._chk(self._lib.fora_hip_set_params(self._ctx, C.c_double(alpha), C.c_double(epsilon),
-                                                C.c_double(rmax_scale), C.c_int(int(opt)), C.c_uint64(seed)))
+        self._chk(self._lib.fora_hip_set_params(self._ctx, alpha, epsilon, rmax_scale, int(opt), seed))
 
     def set_params_raw(self, alpha, rmax, omega, opt=False, seed=0):
-        self._chk(self._lib.fora_hip_set_params_raw(self._ctx, C.c_double(alpha), C.c_double(rmax),
-                                                    C.c_double(omega), C.c_int(int(opt)), C.c_uint64(seed)))
+        self._chk(self._lib.fora_hip_set_params_raw(self._ctx, alpha, rmax, omega, int(opt), seed))
 
     def get_params(self):
         rmax, omega = C.c_double(0), C.c_double(0)
@@ -296,7 +321,7 @@ class Engine:
         return rmax.value, omega.value
 
     def set_batch(self, batch):
-        self._chk(self._lib.fora_hip_set_batch(self._ctx, C.c_int(batch)))
+        self._chk(self._lib.fora_hip_set_batch(self._ctx, batch))
 
     def get_batch(self):
         return self._lib.fora_hip_get_batch(self._ctx)
@@ -317,14 +342,14 @@ class Engine:
         rw = np.zeros(max(1, total), dtype=np.int32)
         off = np.zeros(self.n, dtype=np.uint64)
         cnt = np.zeros(self.n, dtype=np.uint64)
-        self._chk(self._lib.fora_hip_get_index(self._ctx, _p(rw), C.c_uint64(total), _p(off), _p(cnt)))
+        self._chk(self._lib.fora_hip_get_index(self._ctx, _p(rw), total, _p(off), _p(cnt)))
         return rw[:total], off, cnt
 
     def set_index(self, rw_idx, off, cnt):
         rw_idx = np.ascontiguousarray(rw_idx, dtype=np.int32)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         cnt = np.ascontiguousarray(cnt, dtype=np.uint64)
-        self._chk(self._lib.fora_hip_set_index(self._ctx, _p(rw_idx), C.c_uint64(rw_idx.size), _p(off), _p(cnt)))
+        self._chk(self._lib.fora_hip_set_index(self._ctx, _p(rw_idx), rw_idx.size, _p(off), _p(cnt)))
 
     def clear_index(self):
         self._chk(self._lib.fora_hip_clear_index(self._ctx))
@@ -341,8 +366,7 @@ class Engine:
         nq = src.size
         st = (QueryStats * max(1, nq))()
         out = np.zeros((nq, self.n), dtype=np.float64) if want_ppr else None
-        self._chk(self._lib.fora_hip_query_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)),
-                                                 _p(out), st))
+        self._chk(self._lib.fora_hip_query_batch(self._ctx, _p(src), nq, int(with_idx), _p(out), st))
         return out, self._stats(st, nq)
 
     def query_fix(self, sources, with_idx=False, want_residue=True):
@@ -351,8 +375,7 @@ class Engine:
         st = (QueryStats * max(1, nq))()
         ppr = np.zeros((nq, self.n), dtype=np.uint64)
         res = np.zeros((nq, self.n), dtype=np.uint64) if want_residue else None
-        self._chk(self._lib.fora_hip_query_batch_fix(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)),
-                                                     _p(ppr), _p(res), st))
+        self._chk(self._lib.fora_hip_query_batch_fix(self._ctx, _p(src), nq, int(with_idx), _p(ppr), _p(res), st))
         return ppr, res, self._stats(st, nq)
 
     def query_sparse(self, sources, with_idx=False, threshold=None, want_fix=False, device=False):
@@ -368,8 +391,7 @@ class Engine:
         sp = SparseStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
-                                                        _p(row_ptr), st, C.byref(sp)))
+        self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src), nq, int(with_idx), thr, _p(row_ptr), st, C.byref(sp)))
         row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(sp.entries), want_fix, device, "query_sparse")
         out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
         return out + (self._stats(st, nq), sp.as_dict())
@@ -384,38 +406,47 @@ class Engine:
         sp, tk = SparseStats(), TopkStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
-                                                             C.c_int64(int(k)), _p(row_ptr), st, C.byref(sp), C.byref(tk)))
+        self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src), nq, int(with_idx), thr, int(k), _p(row_ptr), st,
+                                                             C.byref(sp), C.byref(tk)))
         row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(sp.entries), want_fix, device, "query_sparse_topk")
         out = (row_ptr, ids, vals) + ((fix,) if want_fix else ())
         return out + (self._stats(st, nq), sp.as_dict(), tk.as_dict())
 
+    def _torch_device(self, who):
+        """the context's GPU as a torch device, for who(device=True)"""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{who}(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
+                               "HIP runtime: import torch before the first Engine is created")
+        return torch.device("cuda", self.device)
+
+    def _held_outputs(self, specs, device, who):
+        """The outputs of a held result, one per (length, numpy dtype, torch dtype name) of specs (None: not wanted): numpy
+        zeros, or with device torch tensors on the context's GPU, the device synchronised once they are made.  Returns
+        (arrays, pointers), None for an output that is not wanted."""
+        if not device:
+            arrs = [None if s is None else np.zeros(s[0], dtype=s[1]) for s in specs]
+            return arrs, [_p(a) for a in arrs]
+        import torch
+        dev = self._torch_device(who)
+        arrs = [None if s is None else torch.empty(s[0], dtype=getattr(torch, s[2]), device=dev) for s in specs]
+        torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
+        return arrs, [None if a is None else a.data_ptr() for a in arrs]
+
     def _sparse_result(self, row_ptr, e, want_fix, device, who):
         """The held sparse result of e entries through fora_hip_sparse_fetch: (row_ptr, ids, vals, fix or None) as numpy
         arrays, or with device as torch tensors on the context's GPU."""
+        specs = [(e, np.int32, "int32"), (e, np.float64, "float64"), (e, np.uint64, "int64") if want_fix else None]
+        (ids, vals, fix), ptrs = self._held_outputs(specs, device, who)
+        self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, *ptrs, e))
         if device:
             import torch
-            if not torch.cuda.is_available():
-                raise RuntimeError(f"{who}(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
-                                   "HIP runtime: import torch before the first Engine is created")
-            dev = torch.device("cuda", self.device)
-            ids = torch.empty(e, dtype=torch.int32, device=dev)
-            vals = torch.empty(e, dtype=torch.float64, device=dev)
-            fix = torch.empty(e, dtype=torch.int64, device=dev) if want_fix else None
-            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
-            self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()),
-                                                      C.c_void_p(fix.data_ptr()) if want_fix else None, C.c_uint64(e)))
-            row_ptr = torch.from_numpy(row_ptr).to(dev)
-        else:
-            ids = np.zeros(e, dtype=np.int32)
-            vals = np.zeros(e, dtype=np.float64)
-            fix = np.zeros(e, dtype=np.uint64) if want_fix else None
-            self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), C.c_uint64(e)))
+            row_ptr = torch.from_numpy(row_ptr).to(ids.device)
         return row_ptr, ids, vals, fix
 
     def sparse_fetch(self, ids=None, vals=None, fix=None, cap=0):
         """fora_hip_sparse_fetch into caller-made numpy arrays (any of them None): the held result, again."""
-        self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), C.c_uint64(int(cap))))
+        self._chk(self._lib.fora_hip_sparse_fetch(self._ctx, _p(ids), _p(vals), _p(fix), int(cap)))
 
     def sparse_clear(self):
         self._chk(self._lib.fora_hip_sparse_clear(self._ctx))
@@ -424,11 +455,9 @@ class Engine:
     def store_put(self, row_ptr, append=False):
         """The held sparse result into the store (fora_hip_store_put), replacing it or, with append, behind its rows.
         row_ptr: as the sparse call returned it.  Returns the stats dict."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        rp, nq, _ = self._row_ptr(row_ptr)
         st = StoreStats()
-        self._chk(self._lib.fora_hip_store_put(self._ctx, _p(rp), C.c_int(rp.size - 1), C.c_int(int(bool(append))), C.byref(st)))
+        self._chk(self._lib.fora_hip_store_put(self._ctx, _p(rp), nq, int(bool(append)), C.byref(st)))
         return st.as_dict()
 
     def _store_array(self, x, entries, np_dtype, name):
@@ -458,31 +487,27 @@ class Engine:
         words; int64 bits are taken as they are) with row_ptr[-1] entries each -- numpy arrays, or torch tensors on the
         context's GPU, which the device reads in place (a slice of a larger tensor is fine).  Every id is checked on the GPU:
         inside [0, n) and strictly ascending inside a row.  Returns the stats dict."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        rp, nrows, e = self._row_ptr(row_ptr)
         if rp.ndim != 1 or rp.size < 1:
             raise ValueError("row_ptr must hold nrows + 1 entries")
-        e = max(int(rp[-1]), 0)
+        e = max(e, 0)
         iptr, i_dev, _ki = self._store_array(ids, e, np.int32, "ids")
         fptr, f_dev, _kf = self._store_array(fix, e, np.uint64, "fix")
         if i_dev or f_dev:
             import torch
             torch.cuda.synchronize(torch.device("cuda", self.device))  # (the tensors may have been written on another stream)
         st = StoreStats()
-        self._chk(self._lib.fora_hip_store_load(self._ctx, _p(rp), C.c_int64(rp.size - 1), iptr, fptr, C.c_int(int(bool(append))), C.byref(st)))
+        self._chk(self._lib.fora_hip_store_load(self._ctx, _p(rp), nrows, iptr, fptr, int(bool(append)), C.byref(st)))
         return st.as_dict()
 
     def store_take(self, rows):
         """Rows `rows` of the store, in that order, become the held sparse result (fora_hip_store_take): one copy on the GPU,
         no query.  Returns (row_ptr, stats): the row_ptr every call on the held rows takes (sparse_propagate, sparse_attention,
         torch_ops ...); sparse_fetch copies the rows out."""
-        if self._is_torch(rows):
-            rows = rows.cpu().numpy()
-        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        r = self._row_ptr(rows)[0].reshape(-1)
         row_ptr = np.zeros(r.size + 1, dtype=np.int64)
         st = StoreStats()
-        self._chk(self._lib.fora_hip_store_take(self._ctx, _p(r), C.c_int(r.size), _p(row_ptr), C.byref(st)))
+        self._chk(self._lib.fora_hip_store_take(self._ctx, _p(r), r.size, _p(row_ptr), C.byref(st)))
         return row_ptr, st.as_dict()
 
     def store_info(self):
@@ -508,25 +533,13 @@ class Engine:
         outputs of that many rows -- the n_id of a sampled mini-batch.  row_ptr: as the sparse call or store_take returned
         it.  Returns (cols, stats dict): cols a numpy int32 array, or with device=True a torch int32 tensor on the context's
         GPU.  Ends with the held result; a second compaction of the same result is refused."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        rp, nq, _ = self._row_ptr(row_ptr)
         nc, st = C.c_int64(0), ColsStats()
         if device:
-            import torch
-            if not torch.cuda.is_available():
-                raise RuntimeError("sparse_compact(device=True): torch sees no GPU here.  torch and libfora_hip.so must "
-                                   "share one HIP runtime: import torch before the first Engine is created")
-        self._chk(self._lib.fora_hip_sparse_compact(self._ctx, _p(rp), C.c_int(rp.size - 1), C.byref(nc), C.byref(st)))
-        if device:
-            dev = torch.device("cuda", self.device)
-            cols = torch.empty(nc.value, dtype=torch.int32, device=dev)
-            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
-            ptr = C.c_void_p(cols.data_ptr()) if nc.value else None
-        else:
-            cols = np.zeros(nc.value, dtype=np.int32)
-            ptr = _p(cols) if nc.value else None
-        self._chk(self._lib.fora_hip_sparse_cols_fetch(self._ctx, ptr, C.c_uint64(nc.value)))
+            self._torch_device("sparse_compact")  # (refused before anything is compacted)
+        self._chk(self._lib.fora_hip_sparse_compact(self._ctx, _p(rp), nq, C.byref(nc), C.byref(st)))
+        (cols,), (ptr,) = self._held_outputs([(nc.value, np.int32, "int32")], device, "sparse_compact")
+        self._chk(self._lib.fora_hip_sparse_cols_fetch(self._ctx, ptr if nc.value else None, nc.value))
         return cols, st.as_dict()
 
     def store_take_compact(self, rows, device=False):
@@ -540,6 +553,14 @@ class Engine:
     @staticmethod
     def _is_torch(x):
         return type(x).__module__.split(".")[0] == "torch"
+
+    def _row_ptr(self, row_ptr):
+        """(rp, nq, entries) of the row_ptr argument of the calls on the held rows: a host int64 array of nq + 1 offsets, from
+        a numpy array or a torch tensor"""
+        if self._is_torch(row_ptr):
+            row_ptr = row_ptr.cpu().numpy()
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        return rp, rp.size - 1, int(rp.reshape(-1)[-1]) if rp.size else 0
 
     def _prop_feat(self, feat, bf16, rows=None, name="feat", shape=None):
         """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate ([n, d]; n: the held
@@ -589,32 +610,6 @@ class Engine:
             raise ValueError(f"{name} must be [nq, d] of the output's type with a column stride of one element")
         return ptr, int(ldo)
 
-    def _prop_values(self, values, entries, on_dev):
-        """(pointer, val_type, keep-alive) of the values argument of sparse_propagate / sparse_propagate_t: one float32 or
-        float64 per held entry, a numpy array or a torch tensor on the context's GPU (with torch operands only: the call
-        synchronises the device once, for all of them)"""
-        if self._is_torch(values):
-            import torch
-            if not on_dev:
-                raise ValueError("torch values go with a torch feat / grad")
-            if not values.is_cuda or values.device.index != self.device:
-                raise ValueError("torch values must live on the context's GPU")
-            if values.dtype not in (torch.float32, torch.float64):
-                raise ValueError("values must be float32 or float64")
-            if values.dim() != 1 or values.shape[0] != entries:
-                raise ValueError("values must hold one element per held entry")
-            v = values.detach()
-            if entries > 1 and v.stride(0) != 1:
-                v = v.contiguous()
-            return C.c_void_p(v.data_ptr()), (PROP_F64 if v.dtype == torch.float64 else PROP_F32), v
-        a = np.asarray(values)
-        if a.dtype not in (np.float32, np.float64):
-            raise ValueError("values must be float32 or float64")
-        if a.ndim != 1 or a.shape[0] != entries:
-            raise ValueError("values must hold one element per held entry")
-        a = np.ascontiguousarray(a)
-        return _p(a), (PROP_F64 if a.dtype == np.float64 else PROP_F32), a
-
     def sparse_propagate(self, row_ptr, feat, normalize=False, want32=True, want64=False, bf16=False, out32=None, out64=None, values=None):
         """out = (held sparse rows) x feat (fora_hip_sparse_propagate, the PROPAGATE contract of include/fora_hip.h), on the held
         result of query_sparse / query_seeds_sparse: out[i, c] = sum over the entries of row i of val * feat[id, c] in the
@@ -627,22 +622,15 @@ class Engine:
         past d are left alone), both with the same row stride.  values (fora_hip_sparse_propagate_vals, PROPAGATE WITH
         VALUES): one float32 or float64 per held entry, in held order, used as the weights in place of the held values --
         numpy, or a torch tensor on the GPU beside a torch feat; not together with normalize."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq = rp.size - 1
+        rp, nq, e = self._row_ptr(row_ptr)
         fptr, ftype, d, ldf, on_dev, _keep = self._prop_feat(feat, bf16)
+        fn, vals = self._lib.fora_hip_sparse_propagate, ()
         if values is not None:
-            vptr, vtype, _vkeep = self._prop_values(values, int(rp[-1]), on_dev)
+            vptr, vtype, _, _vkeep = self._entry_operand(values, e, "values", beside=on_dev)
+            fn, vals = self._lib.fora_hip_sparse_propagate_vals, (vptr, vtype)
         out32, out64, p32, p64, ldo = self._prop_outputs(nq, d, on_dev, want32, want64, out32, out64)
         ps = PropStats()
-        if values is not None:
-            self._chk(self._lib.fora_hip_sparse_propagate_vals(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
-                                                               C.c_int(PROP_NORMALIZE if normalize else 0), vptr, C.c_int(vtype), p32, p64,
-                                                               C.c_int64(ldo), C.byref(ps)))
-            return out32, out64, ps.as_dict()
-        self._chk(self._lib.fora_hip_sparse_propagate(self._ctx, _p(rp), C.c_int(nq), fptr, C.c_int(ftype), C.c_int(d), C.c_int64(ldf),
-                                                      C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
+        self._chk(fn(self._ctx, _p(rp), nq, fptr, ftype, d, ldf, PROP_NORMALIZE if normalize else 0, *vals, p32, p64, ldo, C.byref(ps)))
         return out32, out64, ps.as_dict()
 
     def _prop_outputs(self, rows, d, on_dev, want32, want64, out32, out64):
@@ -684,22 +672,15 @@ class Engine:
         tensors on the device with a torch grad, numpy arrays otherwise.  The first call on a held result builds its
         transposition (stats["built"] == 1), later calls reuse it.  values (fora_hip_sparse_propagate_t_vals): as for
         sparse_propagate, one element per held entry in HELD order."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq = rp.size - 1
+        rp, nq, e = self._row_ptr(row_ptr)
         gptr, gtype, d, ldg, on_dev, _keep = self._prop_feat(grad, bf16, rows=nq, name="grad")
+        fn, vals = self._lib.fora_hip_sparse_propagate_t, ()
         if values is not None:
-            vptr, vtype, _vkeep = self._prop_values(values, int(rp[-1]), on_dev)
+            vptr, vtype, _, _vkeep = self._entry_operand(values, e, "values", beside=on_dev)
+            fn, vals = self._lib.fora_hip_sparse_propagate_t_vals, (vptr, vtype)
         out32, out64, p32, p64, ldo = self._prop_outputs(self.held_cols, d, on_dev, want32, want64, out32, out64)
         ps = PropTStats()
-        if values is not None:
-            self._chk(self._lib.fora_hip_sparse_propagate_t_vals(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
-                                                                 C.c_int(PROP_NORMALIZE if normalize else 0), vptr, C.c_int(vtype), p32, p64,
-                                                                 C.c_int64(ldo), C.byref(ps)))
-            return out32, out64, ps.as_dict()
-        self._chk(self._lib.fora_hip_sparse_propagate_t(self._ctx, _p(rp), C.c_int(nq), gptr, C.c_int(gtype), C.c_int(d), C.c_int64(ldg),
-                                                        C.c_int(PROP_NORMALIZE if normalize else 0), p32, p64, C.c_int64(ldo), C.byref(ps)))
+        self._chk(fn(self._ctx, _p(rp), nq, gptr, gtype, d, ldg, PROP_NORMALIZE if normalize else 0, *vals, p32, p64, ldo, C.byref(ps)))
         return out32, out64, ps.as_dict()
 
     def sparse_sddmm(self, row_ptr, a, b, want32=True, want64=False, out32=None, out64=None, a_bf16=False, b_bf16=False):
@@ -710,18 +691,14 @@ class Engine:
         (out32 or None, out64 or None, stats dict): float32 / float64 [entries], torch tensors on the device when a or b is
         a torch tensor, numpy arrays otherwise; out32 / out64: caller-made contiguous outputs of at least `entries`
         elements to fill instead, each a numpy array or a torch tensor on the GPU."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
+        rp, nq, e = self._row_ptr(row_ptr)
         aptr, atype, d, lda, a_dev, _ka = self._prop_feat(a, a_bf16, rows=nq, name="a")
         bptr, btype, db, ldb, b_dev, _kb = self._prop_feat(b, b_bf16, name="b")
         if db != d:
             raise ValueError("a and b must have the same number of columns")
         out32, out64, p32, p64, cap = self._entry_outputs(e, a_dev or b_dev, want32, want64, out32, out64)
         st = SddmmStats()
-        self._chk(self._lib.fora_hip_sparse_sddmm(self._ctx, _p(rp), C.c_int(nq), aptr, C.c_int(atype), C.c_int64(lda), bptr, C.c_int(btype),
-                                                  C.c_int64(ldb), C.c_int(d), p32, p64, C.c_uint64(cap), C.byref(st)))
+        self._chk(self._lib.fora_hip_sparse_sddmm(self._ctx, _p(rp), nq, aptr, atype, lda, bptr, btype, ldb, d, p32, p64, cap, C.byref(st)))
         return out32, out64, st.as_dict()
 
     def _entry_outputs(self, e, on_dev, want32, want64, out32, out64):
@@ -759,13 +736,17 @@ class Engine:
             torch.cuda.synchronize(dev)  # (the operands may have been written, and the allocator may hand out memory, on another stream)
         return out32, out64, ptrs[0], ptrs[1], cap or 0
 
-    def _entry_operand(self, x, entries, name):
-        """(pointer, element type, on_device, keep-alive) of a per-entry input of sparse_softmax / sparse_softmax_bwd: one
-        float32 or float64 per held entry, a numpy array or a torch tensor on the context's GPU"""
+    def _entry_operand(self, x, entries, name, beside=None):
+        """(pointer, element type, on_device, keep-alive) of a per-entry input -- the scores / y / grad of sparse_softmax and
+        sparse_softmax_bwd, the values of sparse_propagate and sparse_propagate_t: one float32 or float64 per held entry, a
+        numpy array or a torch tensor on the context's GPU.  beside (the values only): whether the feat / grad beside them is
+        a torch tensor -- torch values need one: the call synchronises the device once, for all its operands."""
         if self._is_torch(x):
             import torch
+            if beside is False:
+                raise ValueError(f"torch {name} go with a torch feat / grad")
             if not x.is_cuda or x.device.index != self.device:
-                raise ValueError(f"a torch {name} must live on the context's GPU")
+                raise ValueError(f"{'torch' if beside else 'a torch'} {name} must live on the context's GPU")
             if x.dtype not in (torch.float32, torch.float64):
                 raise ValueError(f"{name} must be float32 or float64")
             if x.dim() != 1 or x.shape[0] != entries:
@@ -789,15 +770,11 @@ class Engine:
         tensor on the context's GPU.  A row with a NaN, with +inf, or of -inf only becomes NaN (stats["nan_rows"]).  Returns
         (out32 or None, out64 or None, stats dict): [entries], torch tensors on the device when scores is one, numpy arrays
         otherwise; out32 / out64: caller-made contiguous outputs of at least `entries` elements, as for sparse_sddmm."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
+        rp, nq, e = self._row_ptr(row_ptr)
         sptr, stype, on_dev, _keep = self._entry_operand(scores, e, "scores")
         out32, out64, p32, p64, cap = self._entry_outputs(e, on_dev, want32, want64, out32, out64)
         st = SoftmaxStats()
-        self._chk(self._lib.fora_hip_sparse_softmax(self._ctx, _p(rp), C.c_int(nq), sptr, C.c_int(stype), C.c_double(float(scale)), p32, p64,
-                                                    C.c_uint64(cap), C.byref(st)))
+        self._chk(self._lib.fora_hip_sparse_softmax(self._ctx, _p(rp), nq, sptr, stype, float(scale), p32, p64, cap, C.byref(st)))
         return out32, out64, st.as_dict()
 
     def sparse_softmax_bwd(self, row_ptr, y, grad, scale=1.0, want32=True, want64=False, out32=None, out64=None):
@@ -805,16 +782,13 @@ class Engine:
         (fora_hip_sparse_softmax_bwd): the gradient of sparse_softmax with respect to scores, y its output and scale its
         scale.  y and grad: float32 or float64 each, numpy or torch on the GPU; outputs as for sparse_softmax (torch when
         either input is)."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
+        rp, nq, e = self._row_ptr(row_ptr)
         yptr, ytype, y_dev, _ky = self._entry_operand(y, e, "y")
         gptr, gtype, g_dev, _kg = self._entry_operand(grad, e, "grad")
         out32, out64, p32, p64, cap = self._entry_outputs(e, y_dev or g_dev, want32, want64, out32, out64)
         st = SoftmaxStats()
-        self._chk(self._lib.fora_hip_sparse_softmax_bwd(self._ctx, _p(rp), C.c_int(nq), yptr, C.c_int(ytype), gptr, C.c_int(gtype), C.c_double(float(scale)),
-                                                        p32, p64, C.c_uint64(cap), C.byref(st)))
+        self._chk(self._lib.fora_hip_sparse_softmax_bwd(self._ctx, _p(rp), nq, yptr, ytype, gptr, gtype, float(scale),
+                                                        p32, p64, cap, C.byref(st)))
         return out32, out64, st.as_dict()
 
     def sparse_attention(self, row_ptr, Q, K, V, heads=1, scale=None, want32=True, want64=False, want_y32=False, want_y64=False,
@@ -828,10 +802,7 @@ class Engine:
         [nq, heads * dv], y (the probabilities, with want_y32 / want_y64) [heads, entries]; torch tensors on the device when
         an operand is a torch tensor, numpy arrays otherwise.  out32 / out64: caller-made outputs as for sparse_propagate.
         A (row, head) with a NaN score, a +inf, or -inf only is written as NaN (stats["nan_rows"])."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
+        rp, nq, e = self._row_ptr(row_ptr)
         heads = int(heads)
         qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nq, name="Q")
         kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, name="K")
@@ -848,9 +819,8 @@ class Engine:
         out32, out64, p32, p64, ldo = self._prop_outputs(nq, wv, on_dev, want32, want64, out32, out64)
         st = AttnStats()
         sc = float(d) ** -0.5 if scale is None else float(scale)
-        self._chk(self._lib.fora_hip_sparse_attention(self._ctx, _p(rp), C.c_int(nq), qptr, C.c_int(qtype), C.c_int64(ldq), kptr, C.c_int(ktype),
-                                                      C.c_int64(ldk), vptr, C.c_int(vtype), C.c_int64(ldv), C.c_int(d), C.c_int(dv), C.c_int(heads),
-                                                      C.c_double(sc), p32, p64, C.c_int64(ldo), py32, py64, C.c_uint64(ycap), C.byref(st)))
+        self._chk(self._lib.fora_hip_sparse_attention(self._ctx, _p(rp), nq, qptr, qtype, ldq, kptr, ktype, ldk, vptr, vtype, ldv, d, dv, heads, sc,
+                                                      p32, p64, ldo, py32, py64, ycap, C.byref(st)))
         if y32 is not None:
             y32 = y32.reshape(heads, e)
         if y64 is not None:
@@ -871,10 +841,7 @@ class Engine:
         (the two of one gradient with the same row stride; a caller-made output makes its gradient wanted).  The first call on
         a held result builds its transposition (stats["built"] == 1) and plans the columns; later calls reuse both
         (stats["plan_cached"] == 1)."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
+        rp, nq, e = self._row_ptr(row_ptr)
         heads = int(heads)
         qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nq, name="Q")
         kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, name="K")
@@ -903,10 +870,8 @@ class Engine:
             outs += [o32, o64]
         st = AttnBwdStats()
         sc = float(d) ** -0.5 if scale is None else float(scale)
-        self._chk(self._lib.fora_hip_sparse_attention_bwd(self._ctx, _p(rp), C.c_int(nq), qptr, C.c_int(qtype), C.c_int64(ldq), kptr, C.c_int(ktype),
-                                                          C.c_int64(ldk), vptr, C.c_int(vtype), C.c_int64(ldv), gptr, C.c_int(gtype), C.c_int64(ldg),
-                                                          yptr, C.c_int(ytype), C.c_uint64(heads * e), C.c_int(d), C.c_int(dv), C.c_int(heads),
-                                                          C.c_double(sc), C.byref(gr), C.byref(st)))
+        self._chk(self._lib.fora_hip_sparse_attention_bwd(self._ctx, _p(rp), nq, qptr, qtype, ldq, kptr, ktype, ldk, vptr, vtype, ldv, gptr, gtype, ldg,
+                                                          yptr, ytype, heads * e, d, dv, heads, sc, C.byref(gr), C.byref(st)))
         return (*outs, st.as_dict())
 
     def sparse_transpose_fetch(self, row_ptr, want_fix=False, device=False):
@@ -914,30 +879,11 @@ class Engine:
         (col_ptr, rows, vals, fix) -- a CSR over the n nodes, column v listing the rows that keep v in ascending order.
         device=False: numpy arrays (int64, int32, float64, uint64); device=True: torch tensors on the context's GPU (fix as
         int64 bits), as for query_sparse."""
-        if self._is_torch(row_ptr):
-            row_ptr = row_ptr.cpu().numpy()
-        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
-        nq, e = rp.size - 1, int(rp[-1])
-        if device:
-            import torch
-            if not torch.cuda.is_available():
-                raise RuntimeError("sparse_transpose_fetch(device=True): torch sees no GPU here.  torch and libfora_hip.so must "
-                                   "share one HIP runtime: import torch before the first Engine is created")
-            dev = torch.device("cuda", self.device)
-            col_ptr = torch.empty(self.held_cols + 1, dtype=torch.int64, device=dev)
-            rows = torch.empty(e, dtype=torch.int32, device=dev)
-            vals = torch.empty(e, dtype=torch.float64, device=dev)
-            fix = torch.empty(e, dtype=torch.int64, device=dev) if want_fix else None
-            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            col_ptr = np.zeros(self.held_cols + 1, dtype=np.int64)
-            rows = np.zeros(e, dtype=np.int32)
-            vals = np.zeros(e, dtype=np.float64)
-            fix = np.zeros(e, dtype=np.uint64) if want_fix else None
-            ptr = _p
-        self._chk(self._lib.fora_hip_sparse_transpose_fetch(self._ctx, _p(rp), C.c_int(nq), ptr(col_ptr), ptr(rows), ptr(fix), ptr(vals),
-                                                            C.c_uint64(e)))
+        rp, nq, e = self._row_ptr(row_ptr)
+        specs = [(self.held_cols + 1, np.int64, "int64"), (e, np.int32, "int32"), (e, np.uint64, "int64") if want_fix else None,
+                 (e, np.float64, "float64")]
+        (col_ptr, rows, fix, vals), ptrs = self._held_outputs(specs, device, "sparse_transpose_fetch")
+        self._chk(self._lib.fora_hip_sparse_transpose_fetch(self._ctx, _p(rp), nq, *ptrs, e))
         return (col_ptr, rows, vals) + ((fix,) if want_fix else ())
 
     def _propagate_chunks(self, total, chunk, feat, bf16, want32, want64, normalize, run):
@@ -978,11 +924,10 @@ class Engine:
             rp = np.zeros(i1 - i0 + 1, dtype=np.int64)
             part = (QueryStats * (i1 - i0)).from_buffer(st, i0 * C.sizeof(QueryStats))
             if topk is None:
-                self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)), C.c_double(thr),
-                                                                _p(rp), part, None))
+                self._chk(self._lib.fora_hip_query_sparse_batch(self._ctx, _p(src[i0:i1]), i1 - i0, int(with_idx), thr, _p(rp), part, None))
             else:
-                self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src[i0:i1]), C.c_int(i1 - i0), C.c_int(int(with_idx)),
-                                                                     C.c_double(thr), C.c_int64(int(topk)), _p(rp), part, None, None))
+                self._chk(self._lib.fora_hip_query_sparse_topk_batch(self._ctx, _p(src[i0:i1]), i1 - i0, int(with_idx), thr, int(topk),
+                                                                     _p(rp), part, None, None))
             return rp
         out32, out64, props = self._propagate_chunks(nq, chunk, feat, bf16, want32, want64, normalize, run)
         return {"out32": out32, "out64": out64, "stats": self._stats(st, nq), "prop": props}
@@ -1003,11 +948,11 @@ class Engine:
             sd_ = np.ascontiguousarray(seeds[lo:hi])
             w_ = None if w is None else np.ascontiguousarray(w[lo:hi])
             if topk is None:
-                self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
-                                                                C.c_double(thr), _p(rp), None, None, None))
+                self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), i1 - i0, int(with_idx),
+                                                                thr, _p(rp), None, None, None))
             else:
-                self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), C.c_int(i1 - i0), C.c_int(int(with_idx)),
-                                                                     C.c_double(thr), C.c_int64(int(topk)), _p(rp), None, None, None, None))
+                self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(sp_), _p(sd_), _p(w_), i1 - i0, int(with_idx),
+                                                                     thr, int(topk), _p(rp), None, None, None, None))
             return rp
         out32, out64, props = self._propagate_chunks(ns, chunk, feat, bf16, want32, want64, normalize, run)
         return {"out32": out32, "out64": out64, "prop": props}
@@ -1028,8 +973,8 @@ class Engine:
         sw = SweepStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_sweep_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(int(with_idx)), C.c_double(thr),
-                                                 C.c_int64(int(max_size)), _p(row_ptr), rows, st, C.byref(sw)))
+        self._chk(self._lib.fora_hip_sweep_batch(self._ctx, _p(src), nq, int(with_idx), thr, int(max_size), _p(row_ptr), rows, st,
+                                                 C.byref(sw)))
         out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=nq).copy(),
                "stats": self._stats(st, nq), "sweep": sw.as_dict()}
         if want_profile:
@@ -1039,23 +984,9 @@ class Engine:
     def sweep_fetch(self, entries, device=False):
         """The held profile, again (fora_hip_sweep_fetch): (ids, cut, vol) of `entries` entries each."""
         e = int(entries)
-        if device:
-            import torch
-            if not torch.cuda.is_available():
-                raise RuntimeError("sweep_fetch(device=True): torch sees no GPU here.  torch and libfora_hip.so must share one "
-                                   "HIP runtime: import torch before the first Engine is created")
-            dev = torch.device("cuda", self.device)
-            ids = torch.empty(e, dtype=torch.int32, device=dev)
-            cut = torch.empty(e, dtype=torch.int64, device=dev)
-            vol = torch.empty(e, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize(dev)  # (the allocator may hand out memory another stream still uses)
-            self._chk(self._lib.fora_hip_sweep_fetch(self._ctx, C.c_void_p(ids.data_ptr()), C.c_void_p(cut.data_ptr()),
-                                                     C.c_void_p(vol.data_ptr()), C.c_uint64(e)))
-        else:
-            ids = np.zeros(e, dtype=np.int32)
-            cut = np.zeros(e, dtype=np.uint64)
-            vol = np.zeros(e, dtype=np.uint64)
-            self._chk(self._lib.fora_hip_sweep_fetch(self._ctx, _p(ids), _p(cut), _p(vol), C.c_uint64(e)))
+        specs = [(e, np.int32, "int32"), (e, np.uint64, "int64"), (e, np.uint64, "int64")]
+        (ids, cut, vol), ptrs = self._held_outputs(specs, device, "sweep_fetch")
+        self._chk(self._lib.fora_hip_sweep_fetch(self._ctx, *ptrs, e))
         return ids, cut, vol
 
     def sweep_clear(self):
@@ -1078,8 +1009,7 @@ class Engine:
         sw = SweepStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._test_entry("fora_hip_test_sweep_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(thr), C.c_int64(int(max_size)),
-                                                               _p(row_ptr), rows, C.byref(sw)))
+        self._chk(self._test_entry("fora_hip_test_sweep_rows")(self._ctx, _p(fix), nq, thr, int(max_size), _p(row_ptr), rows, C.byref(sw)))
         out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=nq).copy(), "sweep": sw.as_dict()}
         if want_profile:
             out["ids"], out["cut"], out["vol"] = self.sweep_fetch(int(row_ptr[-1]))
@@ -1094,8 +1024,7 @@ class Engine:
         nq = fix.shape[0]
         sp = SparseStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
-        self._chk(self._test_entry("fora_hip_test_sparse_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(float(threshold)), _p(row_ptr),
-                                                                C.byref(sp)))
+        self._chk(self._test_entry("fora_hip_test_sparse_rows")(self._ctx, _p(fix), nq, float(threshold), _p(row_ptr), C.byref(sp)))
         return row_ptr, sp.as_dict()
 
     def test_sparse_topk_rows(self, rows_fix, k, threshold=0.0):
@@ -1107,8 +1036,8 @@ class Engine:
         nq = fix.shape[0]
         sp, tk = SparseStats(), TopkStats()
         row_ptr = np.zeros(nq + 1, dtype=np.int64)
-        self._chk(self._test_entry("fora_hip_test_sparse_topk_rows")(self._ctx, _p(fix), C.c_int(nq), C.c_double(float(threshold)),
-                                                                     C.c_int64(int(k)), _p(row_ptr), C.byref(sp), C.byref(tk)))
+        self._chk(self._test_entry("fora_hip_test_sparse_topk_rows")(self._ctx, _p(fix), nq, float(threshold), int(k), _p(row_ptr),
+                                                                     C.byref(sp), C.byref(tk)))
         return row_ptr, sp.as_dict(), tk.as_dict()
 
     def test_sweep_scan(self, diff, vol, nnz):
@@ -1119,7 +1048,7 @@ class Engine:
         if cut.ndim != 1 or cut.shape != v.shape:
             raise ValueError("diff and vol must be one-dimensional and of one length")
         out = np.zeros(6, dtype=np.uint64)
-        self._chk(self._test_entry("fora_hip_test_sweep_scan")(self._ctx, _p(cut), _p(v), C.c_int64(cut.size), C.c_uint64(int(nnz)), _p(out)))
+        self._chk(self._test_entry("fora_hip_test_sweep_scan")(self._ctx, _p(cut), _p(v), cut.size, int(nnz), _p(out)))
         return cut.view(np.uint64), v, dict(zip(("len", "best", "cut", "vol", "den", "edges"), (int(x) for x in out)))
 
     def test_exp(self, t):
@@ -1127,7 +1056,7 @@ class Engine:
         Returns a float64 array of the same shape."""
         a = np.ascontiguousarray(t, dtype=np.float64)
         out = np.zeros(a.shape, dtype=np.float64)
-        self._chk(self._test_entry("fora_hip_test_exp")(self._ctx, _p(a), C.c_int64(a.size), _p(out)))
+        self._chk(self._test_entry("fora_hip_test_exp")(self._ctx, _p(a), a.size, _p(out)))
         return out
 
     def local_cluster(self, sources, with_idx=False, threshold=None, max_size=0):
@@ -1144,7 +1073,7 @@ class Engine:
         st = (QueryStats * max(1, nq))()
         rsv = np.zeros((nq, self.n), dtype=np.uint64) if want else None
         res = np.zeros((nq, self.n), dtype=np.uint64) if want else None
-        self._chk(self._lib.fora_hip_push_batch(self._ctx, _p(src), C.c_int(nq), _p(rsv), _p(res), st))
+        self._chk(self._lib.fora_hip_push_batch(self._ctx, _p(src), nq, _p(rsv), _p(res), st))
         if not want:
             return self._stats(st, nq)
         return rsv, res, self._stats(st, nq)
@@ -1155,15 +1084,12 @@ class Engine:
         ids = np.zeros((nq, k), dtype=np.int32)
         sc = np.zeros((nq, k), dtype=np.float64)
         rounds = np.zeros(max(1, nq), dtype=np.int32)
-        self._chk(self._lib.fora_hip_topk_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(k), C.c_double(epsilon),
-                                                C.c_double(rmax_scale), C.c_int(int(with_idx)), _p(ids), _p(sc),
-                                                _p(rounds)))
+        self._chk(self._lib.fora_hip_topk_batch(self._ctx, _p(src), nq, k, epsilon, rmax_scale, int(with_idx), _p(ids), _p(sc), _p(rounds)))
         return ids, sc, rounds[:nq]
 
     def set_balanced(self, on=True, start_scale=0.0, c_pop=0.0, c_edge=0.0, t_walk=0.0, t_idx=0.0):
         """--balanced (query.h:848-884); costs <= 0 select the MI355X defaults, start_scale <= 0 the reference's 8."""
-        self._chk(self._lib.fora_hip_set_balanced(self._ctx, C.c_int(int(on)), C.c_double(start_scale), C.c_double(c_pop),
-                                                  C.c_double(c_edge), C.c_double(t_walk), C.c_double(t_idx)))
+        self._chk(self._lib.fora_hip_set_balanced(self._ctx, int(on), start_scale, c_pop, c_edge, t_walk, t_idx))
 
     def topk_bound(self, sources, k, epsilon=0.5, rmax_scale=1.0, ppr_decay_alpha=0.77, with_idx=False):
         """get_topk without --opt (top-k with bounds, query.h:909-969)."""
@@ -1172,9 +1098,8 @@ class Engine:
         ids = np.zeros((nq, k), dtype=np.int32)
         sc = np.zeros((nq, k), dtype=np.float64)
         rounds = np.zeros(max(1, nq), dtype=np.int32)
-        self._chk(self._lib.fora_hip_topk_bound_batch(self._ctx, _p(src), C.c_int(nq), C.c_int(k), C.c_double(epsilon),
-                                                      C.c_double(rmax_scale), C.c_double(ppr_decay_alpha),
-                                                      C.c_int(int(with_idx)), _p(ids), _p(sc), _p(rounds)))
+        self._chk(self._lib.fora_hip_topk_bound_batch(self._ctx, _p(src), nq, k, epsilon, rmax_scale, ppr_decay_alpha, int(with_idx),
+                                                      _p(ids), _p(sc), _p(rounds)))
         return ids, sc, rounds[:nq]
 
     def power_iteration(self, sources, max_iter=100, k=0, want_ppr=True, want_fix=False):
@@ -1187,8 +1112,8 @@ class Engine:
         ids = np.zeros((nq, k), dtype=np.int32) if k else None
         sc = np.zeros((nq, k), dtype=np.float64) if k else None
         self._chk(self._lib.fora_hip_power_iteration_batch(
-            self._ctx, _p(src), C.c_int(nq), C.c_int(max_iter), _p(ppr) if want_ppr else None,
-            _p(fix) if want_fix else None, C.c_int(k), _p(ids) if k else None, _p(sc) if k else None))
+            self._ctx, _p(src), nq, max_iter, _p(ppr) if want_ppr else None,
+            _p(fix) if want_fix else None, k, _p(ids) if k else None, _p(sc) if k else None))
         return ppr, fix, ids, sc
 
     # ---- baselines (--algo montecarlo / fwdpush)
@@ -1202,8 +1127,7 @@ class Engine:
         fix = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
         ids = np.zeros((nq, k), dtype=np.int32) if k else None
         sc = np.zeros((nq, k), dtype=np.float64) if k else None
-        self._chk(self._lib.fora_hip_montecarlo_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), _p(ppr), _p(fix),
-                                                      C.c_int(k), _p(ids), _p(sc), st))
+        self._chk(self._lib.fora_hip_montecarlo_batch(self._ctx, _p(src), nq, epsilon, _p(ppr), _p(fix), k, _p(ids), _p(sc), st))
         return ppr, fix, ids, sc, self._stats(st, nq)
 
     def fwdpush(self, sources, epsilon=0.5, rmax_scale=1.0, k=0, want_ppr=False, want_fix=True):
@@ -1217,8 +1141,8 @@ class Engine:
         res = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
         ids = np.zeros((nq, k), dtype=np.int32) if k else None
         sc = np.zeros((nq, k), dtype=np.float64) if k else None
-        self._chk(self._lib.fora_hip_fwdpush_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), C.c_double(rmax_scale),
-                                                   _p(ppr), _p(rsv), _p(res), C.c_int(k), _p(ids), _p(sc), st))
+        self._chk(self._lib.fora_hip_fwdpush_batch(self._ctx, _p(src), nq, epsilon, rmax_scale,
+                                                   _p(ppr), _p(rsv), _p(res), k, _p(ids), _p(sc), st))
         return ppr, rsv, res, ids, sc, self._stats(st, nq)
 
     def bippr(self, sources, epsilon=0.5, rmax_scale=1.0, k=0, want_ppr=False, want_fix=True):
@@ -1232,8 +1156,8 @@ class Engine:
         fix = np.zeros((nq, self.n), dtype=np.uint64) if want_fix else None
         ids = np.zeros((nq, k), dtype=np.int32) if k else None
         sc = np.zeros((nq, k), dtype=np.float64) if k else None
-        self._chk(self._lib.fora_hip_bippr_batch(self._ctx, _p(src), C.c_int(nq), C.c_double(epsilon), C.c_double(rmax_scale),
-                                                 _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), st, C.byref(bwd)))
+        self._chk(self._lib.fora_hip_bippr_batch(self._ctx, _p(src), nq, epsilon, rmax_scale,
+                                                 _p(ppr), _p(fix), k, _p(ids), _p(sc), st, C.byref(bwd)))
         return ppr, fix, ids, sc, self._stats(st, nq), bwd.as_dict()
 
     def bippr_targets(self, sources, targets, epsilon=0.5, rmax_scale=1.0, want_est=False, want_fix=True):
@@ -1247,8 +1171,8 @@ class Engine:
         bwd = BwdStats()
         est = np.zeros((nq, nt), dtype=np.float64) if want_est else None
         fix = np.zeros((nq, nt), dtype=np.uint64) if want_fix else None
-        self._chk(self._lib.fora_hip_bippr_targets_batch(self._ctx, _p(src), C.c_int(nq), _p(tg), C.c_int(nt), C.c_double(epsilon),
-                                                         C.c_double(rmax_scale), _p(est), _p(fix), st, C.byref(bwd)))
+        self._chk(self._lib.fora_hip_bippr_targets_batch(self._ctx, _p(src), nq, _p(tg), nt, epsilon,
+                                                         rmax_scale, _p(est), _p(fix), st, C.byref(bwd)))
         return est, fix, self._stats(st, nq), bwd.as_dict()
 
     @staticmethod
@@ -1286,8 +1210,8 @@ class Engine:
         ids = np.zeros((ns, k), dtype=np.int32) if k > 0 else None
         sc = np.zeros((ns, k), dtype=np.float64) if k > 0 else None
         sums = np.zeros(ns, dtype=np.uint64)
-        self._chk(self._lib.fora_hip_query_seeds_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
-                                                       _p(ppr), _p(fix), C.c_int(k), _p(ids), _p(sc), _p(sums), C.byref(st)))
+        self._chk(self._lib.fora_hip_query_seeds_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), ns, int(with_idx),
+                                                       _p(ppr), _p(fix), k, _p(ids), _p(sc), _p(sums), C.byref(st)))
         return {"fix": fix, "ppr": ppr, "ids": ids, "scores": sc, "row_sum_fix": sums, "stats": st.as_dict()}
 
     def query_seeds_sparse(self, sets, weights=None, with_idx=False, threshold=None, want_fix=False, device=False):
@@ -1304,8 +1228,8 @@ class Engine:
         row_ptr = np.zeros(ns + 1, dtype=np.int64)
         sums = np.zeros(ns, dtype=np.uint64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
-                                                        C.c_double(thr), _p(row_ptr), _p(sums), C.byref(st), C.byref(sp)))
+        self._chk(self._lib.fora_hip_seeds_sparse_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), ns, int(with_idx),
+                                                        thr, _p(row_ptr), _p(sums), C.byref(st), C.byref(sp)))
         row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(row_ptr[-1]), want_fix, device, "query_seeds_sparse")
         return {"row_ptr": row_ptr, "ids": ids, "vals": vals, "fix": fix, "row_sum_fix": sums, "stats": st.as_dict(),
                 "sparse": sp.as_dict()}
@@ -1320,9 +1244,8 @@ class Engine:
         row_ptr = np.zeros(ns + 1, dtype=np.int64)
         sums = np.zeros(ns, dtype=np.uint64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
-                                                             C.c_double(thr), C.c_int64(int(k)), _p(row_ptr), _p(sums), C.byref(st),
-                                                             C.byref(sp), C.byref(tk)))
+        self._chk(self._lib.fora_hip_seeds_sparse_topk_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), ns, int(with_idx),
+                                                             thr, int(k), _p(row_ptr), _p(sums), C.byref(st), C.byref(sp), C.byref(tk)))
         row_ptr, ids, vals, fix = self._sparse_result(row_ptr, int(row_ptr[-1]), want_fix, device, "query_seeds_sparse_topk")
         return {"row_ptr": row_ptr, "ids": ids, "vals": vals, "fix": fix, "row_sum_fix": sums, "stats": st.as_dict(),
                 "sparse": sp.as_dict(), "topk": tk.as_dict()}
@@ -1337,9 +1260,8 @@ class Engine:
         sw = SweepStats()
         row_ptr = np.zeros(ns + 1, dtype=np.int64)
         thr = 1.0 / self.n if threshold is None else float(threshold)
-        self._chk(self._lib.fora_hip_seeds_sweep_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), C.c_int(ns), C.c_int(int(with_idx)),
-                                                       C.c_double(thr), C.c_int64(int(max_size)), _p(row_ptr), rows, C.byref(st),
-                                                       C.byref(sw)))
+        self._chk(self._lib.fora_hip_seeds_sweep_batch(self._ctx, _p(set_ptr), _p(seeds), _p(w), ns, int(with_idx),
+                                                       thr, int(max_size), _p(row_ptr), rows, C.byref(st), C.byref(sw)))
         out = {"row_ptr": row_ptr, "rows": np.frombuffer(rows, dtype=_SWEEP_ROW_DTYPE, count=ns).copy(),
                "stats": st.as_dict(), "sweep": sw.as_dict()}
         if want_profile:
@@ -1362,28 +1284,26 @@ class Engine:
         rsv = np.zeros((nt, self.n), dtype=np.uint64)
         res = np.zeros((nt, self.n), dtype=np.uint64)
         bwd = BwdStats()
-        self._chk(self._lib.fora_hip_bwdpush_batch(self._ctx, _p(tg), C.c_int(nt), C.c_double(rmax), _p(rsv), _p(res),
-                                                   C.byref(bwd)))
+        self._chk(self._lib.fora_hip_bwdpush_batch(self._ctx, _p(tg), nt, rmax, _p(rsv), _p(res), C.byref(bwd)))
         return rsv, res, bwd.as_dict()
 
     def walk_counts(self, residue, rsum):
         residue = np.ascontiguousarray(residue, dtype=np.float64)
         out = np.zeros(self.n, dtype=np.uint64)
         N = C.c_uint64(0)
-        self._chk(self._lib.fora_hip_walk_counts(self._ctx, _p(residue), C.c_double(rsum), _p(out), C.byref(N)))
+        self._chk(self._lib.fora_hip_walk_counts(self._ctx, _p(residue), rsum, _p(out), C.byref(N)))
         return N.value, out
 
     def walks(self, stream, rnd, starts, js, no_zero_hop=False):
         starts = np.ascontiguousarray(starts, dtype=np.int32)
         js = np.ascontiguousarray(js, dtype=np.uint64)
         out = np.zeros(starts.size, dtype=np.int32)
-        self._chk(self._lib.fora_hip_walks(self._ctx, C.c_uint32(stream), C.c_uint32(rnd), C.c_int(int(no_zero_hop)),
-                                           _p(starts), _p(js), C.c_int64(starts.size), _p(out)))
+        self._chk(self._lib.fora_hip_walks(self._ctx, stream, rnd, int(no_zero_hop), _p(starts), _p(js), starts.size, _p(out)))
         return out
 
     # ---- measurement
     def set_option(self, name, value):
-        self._chk(self._lib.fora_hip_set_option(self._ctx, name.encode(), C.c_int64(int(value))))
+        self._chk(self._lib.fora_hip_set_option(self._ctx, name.encode(), int(value)))
 
     def get_option(self, name):
         v = C.c_int64(0)
@@ -1391,7 +1311,7 @@ class Engine:
         return int(v.value)
 
     def reset_options(self):
-        self._chk(self._lib.fora_hip_set_option(self._ctx, b"reset", C.c_int64(0)))
+        self._chk(self._lib.fora_hip_set_option(self._ctx, b"reset", 0))
 
     def reset_timing(self):
         self._chk(self._lib.fora_hip_reset_timing(self._ctx))

@@ -199,28 +199,19 @@ def test_the_split_of_the_columns_against_brute_force(attn_bwd_plan_check):
 
 
 def test_abi_surface():
-    import ctypes
     import inspect
-    import re
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     assert hdr.index(" * ATTENTION (fora_hip_sparse_attention)") < hdr.index(" * ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd)") < hdr.index(" * PROPAGATE WITH VALUES (")
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"typedef struct \{([^}]*)\} fora_attn_bwd_stats;", plain)
-    fields = [f.strip() for decl in m.group(1).split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert [f for f, _ in capi.AttnBwdStats._fields_] == fields and ctypes.sizeof(capi.AttnBwdStats) == 120
-    m = re.search(r"typedef struct \{([^}]*)\} fora_attn_grads;", plain)
-    fields = [decl.split()[-1].lstrip("*") for decl in m.group(1).split(";") if decl.strip()]
-    assert [f for f, _ in capi.AttnGrads._fields_] == fields and ctypes.sizeof(capi.AttnGrads) == 72
-    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    # (the fields and sizes of the two structs against the header: tests/test_capi_cpu.py)
+    assert capi.STRUCTS["fora_attn_bwd_stats"] is capi.AttnBwdStats and capi.STRUCTS["fora_attn_grads"] is capi.AttnGrads
+    product, test = capi.load(), capi.load(capi.TEST_LIB)
     name = "fora_hip_sparse_attention_bwd"
     assert hasattr(product, name) and hasattr(test, name) and name in capi.SYMBOLS
     # NULL ctx: answered without touching the GPU
-    vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     fn = product.fora_hip_sparse_attention_bwd
-    fn.argtypes = [vp, vp, i, vp, i, i64, vp, i, i64, vp, i, i64, vp, i, i64, vp, i, ctypes.c_uint64, i, i, i, ctypes.c_double, vp, vp]
     assert fn(None, None, 0, None, 0, 1, None, 0, 1, None, 0, 1, None, 0, 1, None, 0, 0, 1, 1, 1, 1.0, None, None) == -1
     assert callable(capi.Engine.sparse_attention_bwd)
     sig = inspect.signature(capi.Engine.sparse_attention_bwd)

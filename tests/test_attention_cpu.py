@@ -176,22 +176,16 @@ def test_the_split_of_the_rows_against_brute_force(attn_plan_check):
 
 
 def test_abi_surface():
-    import ctypes
-    import re
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     assert " * ATTENTION (fora_hip_sparse_attention)" in hdr and hdr.index("ROW SOFTMAX (") < hdr.index("ATTENTION (") < hdr.index("PROPAGATE WITH VALUES (")
-    m = re.search(r"typedef struct \{([^}]*)\} fora_attn_stats;", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
-    fields = [f.strip() for decl in m.group(1).split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert [f for f, _ in capi.AttnStats._fields_] == fields and ctypes.sizeof(capi.AttnStats) == 72
-    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    assert capi.STRUCTS["fora_attn_stats"] is capi.AttnStats  # (its fields and size against the header: tests/test_capi_cpu.py)
+    product, test = capi.load(), capi.load(capi.TEST_LIB)
     name = "fora_hip_sparse_attention"
     assert hasattr(product, name) and hasattr(test, name) and name in capi.SYMBOLS
     # NULL ctx: answered without touching the GPU
-    vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    product.fora_hip_sparse_attention.argtypes = [vp, vp, i, vp, i, i64, vp, i, i64, vp, i, i64, i, i, i, ctypes.c_double, vp, vp, i64, vp, vp, ctypes.c_uint64, vp]
     assert product.fora_hip_sparse_attention(None, None, 0, None, 0, 1, None, 0, 1, None, 0, 1, 1, 1, 1, 1.0, None, None, 1, None, None, 0, None) == -1
     assert callable(capi.Engine.sparse_attention)
     from fora_amd import torch_ops

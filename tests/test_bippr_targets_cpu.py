@@ -1,6 +1,5 @@
 """Targeted BiPPR on CPU: the header declares fora_hip_bippr_targets_batch with the signature of its contract, the library
 exports it, fora_amd.capi binds it and the Engine has bippr_targets.  The GPU runs are in test_bippr_targets_gpu.py."""
-import ctypes
 import inspect
 import os
 import re
@@ -39,8 +38,5 @@ def test_library_exports_it_and_a_null_ctx_is_an_argument_error():
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
-    lib = ctypes.CDLL(capi.lib_path())
-    fn = getattr(lib, NAME)
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
-                   ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    fn = getattr(capi.load(), NAME)
     assert fn(None, None, 0, None, 0, 0.5, 1.0, None, None, None, None) == -1  # FORA_E_ARG, answered without a GPU

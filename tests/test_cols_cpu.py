@@ -87,18 +87,15 @@ def test_header_library_and_binding_name_the_columns():
     from fora_amd import capi
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fora_hip.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(fora_hip_\w+)\s*\(", text))
-    lib = ctypes.CDLL(capi.lib_path())
+    lib = capi.load()
     for name in NAMES:
         assert name in declared and hasattr(lib, name) and name in capi.SYMBOLS, name
-    assert "fora_cols_stats" in text and ctypes.sizeof(capi.ColsStats) == 32
+    assert "fora_cols_stats" in text and capi.STRUCTS["fora_cols_stats"] is capi.ColsStats  # (fields, size: tests/test_capi_cpu.py)
     for m in ("sparse_compact", "store_take_compact"):
         assert callable(getattr(capi.Engine, m))
     assert isinstance(capi.Engine.held_cols, property)
     # a NULL ctx is answered without touching the GPU (there is none here)
-    vp, i, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
     one = (ctypes.c_int64 * 2)()
-    lib.fora_hip_sparse_compact.argtypes = [vp, vp, i, vp, vp]
-    lib.fora_hip_sparse_cols_fetch.argtypes = [vp, vp, u64]
     assert lib.fora_hip_sparse_compact(None, one, 0, one, None) == -1
     assert lib.fora_hip_sparse_cols_fetch(None, None, 0) == -1
     assert "cols_block" in open(os.path.join(ROOT, "INTEGRATION.md")).read()

@@ -312,8 +312,9 @@ def test_lifetime_and_errors(engine, tiny_dangling):
     assert _raw_cols_fetch(engine, again, nc) == 0
     _eq(again, cols, "cols")
     # the store holds node ids: a put of the compacted result is refused, the store is what it was
-    st = (C.c_uint64 * 8)()
-    assert lib.fora_hip_store_put(engine._ctx, _p(row_ptr), C.c_int(nq), C.c_int(0), st) == E_ARG
+    from fora_amd import capi
+    st = capi.StoreStats()
+    assert lib.fora_hip_store_put(engine._ctx, _p(row_ptr), C.c_int(nq), C.c_int(0), C.byref(st)) == E_ARG
     assert lib.fora_hip_store_put(engine._ctx, _p(row_ptr), C.c_int(nq), C.c_int(1), None) == E_ARG
     assert engine.store_info() == info
     # a feat over all n nodes is refused by the binding; the local one gives the bits of before

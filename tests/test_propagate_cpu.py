@@ -2,7 +2,6 @@
 yardstick, the test inputs' power to tell one order of additions from another, the host-only segment plan
 (fora_amd/csrc/fora_prop_plan.h) against brute force under the address and undefined-behaviour sanitizers -- a stand-alone
 program and nothing else is sanitized -- and the library's symbol."""
-import ctypes
 import math
 import os
 import subprocess
@@ -156,20 +155,17 @@ def test_symbol_and_null_ctx():
     __graft_entry__.build()
     from fora_amd import capi
     assert "fora_hip_sparse_propagate" in capi.SYMBOLS
-    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    product, test = capi.load(), capi.load(capi.TEST_LIB)
     for lib in (product, test):
         fn = lib.fora_hip_sparse_propagate
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         rp = np.zeros(2, dtype=np.int64)
         out = np.full(4, 7.0, dtype=np.float32)
         assert fn(None, rp.ctypes.data, 1, None, 0, 4, 4, 0, out.ctypes.data, None, 4, None) == -1
         assert (out == 7.0).all()
     assert hasattr(test, "fora_hip_test_sparse_rows") and not hasattr(product, "fora_hip_test_sparse_rows")
-    test.fora_hip_test_sparse_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
     assert test.fora_hip_test_sparse_rows(None, None, 0, 0.0, None, None) == -1
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     assert "fora_hip_test_sparse_rows" in hdr and "fora_hip_test_sparse_rows" not in __import__("re").sub(r"/\*.*?\*/", "", hdr, flags=__import__("re").S)
     for meth in ("sparse_propagate", "propagate", "propagate_seeds", "test_sparse_rows"):
         assert callable(getattr(capi.Engine, meth))
-    assert ctypes.sizeof(capi.PropStats) == 56
+    assert capi.STRUCTS["fora_prop_stats"] is capi.PropStats  # (its fields and size against the header: tests/test_capi_cpu.py)

@@ -2,7 +2,6 @@
 independent yardstick, the injected input's power to tell one order of a column's entries from another, the host-only tier
 split and sorting network (fora_amd/csrc/fora_propt_plan.h) against brute force under the address and undefined-behaviour
 sanitizers -- a stand-alone program and nothing else is sanitized -- and the library's symbols."""
-import ctypes
 import math
 import os
 import subprocess
@@ -145,23 +144,17 @@ def test_symbols_and_null_ctx():
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     assert "PROPAGATE, TRANSPOSED" in hdr
-    m = re.search(r"typedef struct \{([^}]*)\} fora_propt_stats;", code)
-    assert m
-    fields = [f.strip() for decl in m.group(1).split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert [f for f, _ in capi.PropTStats._fields_] == fields and ctypes.sizeof(capi.PropTStats) == 88
+    assert capi.STRUCTS["fora_propt_stats"] is capi.PropTStats  # (its fields and size against the header: tests/test_capi_cpu.py)
     names = ("fora_hip_sparse_propagate_t", "fora_hip_sparse_transpose_fetch")
-    for lib in (ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)):
+    for lib in (capi.load(), capi.load(capi.TEST_LIB)):
         for name in names:
             assert hasattr(lib, name) and name in capi.SYMBOLS and re.search(r"\bint\s+" + name + r"\s*\(", code), name
         fn = lib.fora_hip_sparse_propagate_t
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
         rp = np.zeros(2, dtype=np.int64)
         out = np.full(4, 7.0, dtype=np.float32)
         assert fn(None, rp.ctypes.data, 1, None, 0, 4, 4, 0, out.ctypes.data, None, 4, None) == -1
         assert (out == 7.0).all()
         fetch = lib.fora_hip_sparse_transpose_fetch
-        fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_uint64]
         assert fetch(None, rp.ctypes.data, 1, None, None, None, None, 0) == -1
     for meth in ("sparse_propagate_t", "sparse_transpose_fetch"):
         assert callable(getattr(capi.Engine, meth))

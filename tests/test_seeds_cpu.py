@@ -1,7 +1,6 @@
 """Seed sets on CPU: the weight rules and the combine of tests/seeds_ref.py as the SEED SETS contract states them; the header
 declares fora_hip_query_seeds_batch, the library exports it and fora_amd.capi binds it.  The GPU runs are in
 test_seeds_gpu.py."""
-import ctypes
 import inspect
 import os
 import re
@@ -85,17 +84,12 @@ def test_capi_binds_it_and_the_engine_has_query_seeds():
     assert list(sig.parameters) == ["self", "sets", "weights", "with_idx", "k", "want_ppr", "want_fix"]
     d = {k: p.default for k, p in sig.parameters.items()}
     assert (d["weights"], d["with_idx"], d["k"], d["want_ppr"], d["want_fix"]) == (None, False, 0, False, True)
-    assert [f for f, _ in capi.SeedsStats._fields_] == ["seeds", "distinct", "queries", "dangling", "batches", "reserved_",
-                                                        "combine_ms"]
-    assert ctypes.sizeof(capi.SeedsStats) == 48
+    assert capi.STRUCTS["fora_seeds_stats"] is capi.SeedsStats  # (its fields and size against the header: tests/test_capi_cpu.py)
 
 
 def test_library_exports_it_and_a_null_ctx_is_an_argument_error():
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
-    lib = ctypes.CDLL(capi.lib_path())
-    fn = getattr(lib, NAME)
-    fn.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + \
-                  [ctypes.c_void_p] * 4
+    fn = getattr(capi.load(), NAME)
     assert fn(None, None, None, None, 0, 0, None, None, 0, None, None, None, None) == -1  # FORA_E_ARG, answered without a GPU

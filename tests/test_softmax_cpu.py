@@ -233,28 +233,19 @@ def test_the_work_lists_against_brute_force(plan_check):
 
 
 def test_abi_surface():
-    import ctypes
-    import re
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     assert "ROW SOFTMAX" in hdr and "fora_hip_test_exp" in hdr
-    m = re.search(r"typedef struct \{([^}]*)\} fora_softmax_stats;", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
-    fields = [f.strip() for decl in m.group(1).split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert [f for f, _ in capi.SoftmaxStats._fields_] == fields and ctypes.sizeof(capi.SoftmaxStats) == 64
-    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    assert capi.STRUCTS["fora_softmax_stats"] is capi.SoftmaxStats  # (its fields and size against the header: tests/test_capi_cpu.py)
+    product, test = capi.load(), capi.load(capi.TEST_LIB)
     for name in ("fora_hip_sparse_softmax", "fora_hip_sparse_softmax_bwd"):
         assert hasattr(product, name) and hasattr(test, name) and name in capi.SYMBOLS
     assert hasattr(test, "fora_hip_test_exp") and not hasattr(product, "fora_hip_test_exp")
     # NULL ctx: answered without touching the GPU
-    product.fora_hip_sparse_softmax.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     assert product.fora_hip_sparse_softmax(None, None, 0, None, 0, 1.0, None, None, 0, None) == -1
-    product.fora_hip_sparse_softmax_bwd.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                                    ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     assert product.fora_hip_sparse_softmax_bwd(None, None, 0, None, 0, None, 0, 1.0, None, None, 0, None) == -1
-    test.fora_hip_test_exp.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     assert test.fora_hip_test_exp(None, None, 0, None) == -1
     for meth in ("sparse_softmax", "sparse_softmax_bwd", "test_exp"):
         assert callable(getattr(capi.Engine, meth))

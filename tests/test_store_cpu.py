@@ -114,20 +114,14 @@ def test_header_library_and_binding_name_the_store():
     from fora_amd import capi
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fora_hip.h")).read(), flags=re.S)
     declared = set(re.findall(r"\b(fora_hip_\w+)\s*\(", text))
-    lib = ctypes.CDLL(capi.lib_path())
+    lib = capi.load()
     for name in NAMES:
         assert name in declared and hasattr(lib, name) and name in capi.SYMBOLS, name
-    assert "fora_store_stats" in text and ctypes.sizeof(capi.StoreStats) == 56
+    assert "fora_store_stats" in text and capi.STRUCTS["fora_store_stats"] is capi.StoreStats  # (fields, size: tests/test_capi_cpu.py)
     for m in ("store_put", "store_load", "store_take", "store_info", "store_clear"):
         assert callable(getattr(capi.Engine, m))
     # a NULL ctx is answered without touching the GPU (there is none here)
-    vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     one = (ctypes.c_int64 * 2)()
-    lib.fora_hip_store_put.argtypes = [vp, vp, i, i, vp]
-    lib.fora_hip_store_load.argtypes = [vp, vp, i64, vp, vp, i, vp]
-    lib.fora_hip_store_take.argtypes = [vp, vp, i, vp, vp]
-    lib.fora_hip_store_info.argtypes = [vp, vp, vp, vp]
-    lib.fora_hip_store_clear.argtypes = [vp]
     assert lib.fora_hip_store_put(None, one, 0, 0, None) == -1
     assert lib.fora_hip_store_load(None, one, 0, None, None, 0, None) == -1
     assert lib.fora_hip_store_take(None, one, 0, one, None) == -1

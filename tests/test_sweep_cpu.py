@@ -4,7 +4,6 @@ rows of the oracle's twin; the C ABI's new symbols and structs; and the generato
 (tie-heavy and hubs-first rows, rings, pairs, inputs of k_sweep_scan), each against the brute force and for the property the
 GPU test relies on.  The two test-only entry points must be in libfora_hip_test.so and nowhere else.  Last, the host-side plan
 of a sweep batch (fora_amd/csrc/fora_sweep_plan.h) against tests/sweep_plan_check.cpp's brute force, under the sanitizers."""
-import ctypes
 import os
 import re
 import subprocess
@@ -246,27 +245,19 @@ def test_c_abi_declares_exports_and_binds_the_sweep():
     for name in ("fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear"):
         assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
     assert "SWEEP CUT" in hdr
-    assert re.search(r"typedef struct \{ int64_t len, best; uint64_t cut, vol, den; double conductance; \} fora_sweep_row;", code)
-    m = re.search(r"typedef struct \{([^}]*)\} fora_sweep_stats;", code)
-    assert m
-    fields = [f.strip() for decl in m.group(1).split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
-    lib = ctypes.CDLL(capi.lib_path())
+    lib = capi.load()
     for name in ("fora_hip_sweep_batch", "fora_hip_sweep_fetch", "fora_hip_sweep_clear"):
         assert hasattr(lib, name) and name in capi.SYMBOLS
-    assert ctypes.sizeof(capi.SweepRow) == 48 and [f for f, _ in capi.SweepRow._fields_] == ["len", "best", "cut", "vol", "den", "conductance"]
-    assert ctypes.sizeof(capi.SweepStats) == 64 and [f for f, _ in capi.SweepStats._fields_] == fields
+    # (fora_sweep_row and fora_sweep_stats against the header and the compiler: tests/test_capi_cpu.py)
+    assert capi.STRUCTS["fora_sweep_row"] is capi.SweepRow and capi.STRUCTS["fora_sweep_stats"] is capi.SweepStats
     for meth in ("sweep", "sweep_fetch", "sweep_clear", "local_cluster"):
         assert callable(getattr(capi.Engine, meth))
     # NULL ctx: answered without touching the GPU
-    lib.fora_hip_sweep_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int64,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     assert lib.fora_hip_sweep_batch(None, None, 0, 0, 0.0, 0, None, None, None, None) == -1
-    lib.fora_hip_sweep_fetch.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint64]
     assert lib.fora_hip_sweep_fetch(None, None, None, None, 0) == -1
-    lib.fora_hip_sweep_clear.argtypes = [ctypes.c_void_p]
     assert lib.fora_hip_sweep_clear(None) == -1
 
 
@@ -276,8 +267,8 @@ def test_test_entry_points_are_in_the_test_library_only():
     import __graft_entry__
     __graft_entry__.build()
     from fora_amd import capi
-    assert capi.TEST_SYMBOLS == ["fora_hip_test_sweep_rows", "fora_hip_test_sweep_scan"]
-    product, test = ctypes.CDLL(capi.lib_path()), ctypes.CDLL(capi.TEST_LIB)
+    assert {"fora_hip_test_sweep_rows", "fora_hip_test_sweep_scan"} <= set(capi.TEST_SYMBOLS) and len(capi.TEST_SYMBOLS) == 5
+    product, test = capi.load(), capi.load(capi.TEST_LIB)
     hdr = open(os.path.join(ROOT, "include", "fora_hip.h")).read()
     assert "TEST ENTRY POINTS" in hdr
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -287,9 +278,7 @@ def test_test_entry_points_are_in_the_test_library_only():
     for name in capi.SYMBOLS:
         assert hasattr(test, name), name
     # NULL ctx: answered without touching the GPU
-    test.fora_hip_test_sweep_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int64] + [ctypes.c_void_p] * 3
     assert test.fora_hip_test_sweep_rows(None, None, 0, 0.0, 0, None, None, None) == -1
-    test.fora_hip_test_sweep_scan.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p]
     assert test.fora_hip_test_sweep_scan(None, None, None, 0, 0, None) == -1
     for meth in ("test_sweep_rows", "test_sweep_scan"):
         assert callable(getattr(capi.Engine, meth))
