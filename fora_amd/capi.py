@@ -226,6 +226,7 @@ TEST_SYMBOLS = [name for name, row in ABI.items() if row[0]]  # TEST_LIB only
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
+PROP_F16, PROP_E4M3, PROP_E5M2 = 4, 5, 6  # (NARROW OPERANDS of include/fora_hip.h: legal where PROP_BF16 is; 3 is no type)
 PROP_NORMALIZE = 1
 
 
@@ -565,23 +566,38 @@ class Engine:
     def _prop_feat(self, feat, bf16, rows=None, name="feat", shape=None):
         """(pointer, feat_type, d, ldf, on_device, keep-alive) of the feat argument of sparse_propagate ([n, d]; n: the held
         columns, held_cols), or with rows / name of the grad argument of sparse_propagate_t ([nq, d]; shape: how the
-        message names another shape)"""
+        message names another shape).  The element type comes from a torch tensor's dtype (float32, bfloat16, float16,
+        float8_e4m3fn, float8_e5m2) and from a numpy array's (float32, float16); the codes of bf16 and FP8 have no numpy dtype
+        and come as uint16 with the operand's keyword (bf16=, a_bf16=, q_bf16= ...) True or "bf16", as uint8 with "e4m3" or
+        "e5m2" -- the calls' docstrings say "bf16=True" for short.  Every other dtype is a ValueError."""
         shape = shape or ("[n, d] (n: the held columns)" if rows is None else "[nq, d]")
         rows = self.held_cols if rows is None else rows
         if self._is_torch(feat):
             import torch
             if not feat.is_cuda or feat.device.index != self.device:
                 raise ValueError(f"a torch {name} must live on the context's GPU")
-            if feat.dtype not in (torch.float32, torch.bfloat16):
-                raise ValueError(f"a torch {name} must be float32 or bfloat16")
+            types = {torch.float32: PROP_F32, torch.bfloat16: PROP_BF16, torch.float16: PROP_F16, torch.float8_e4m3fn: PROP_E4M3,
+                     torch.float8_e5m2: PROP_E5M2}
+            if feat.dtype not in types:
+                raise ValueError(f"a torch {name} must be float32, bfloat16, float16, float8_e4m3fn or float8_e5m2")
             if feat.dim() != 2 or feat.shape[0] != rows or (feat.shape[1] > 1 and feat.stride(1) != 1):
                 raise ValueError(f"{name} must be {shape} with a column stride of one element")
             ldf = feat.stride(0) if feat.shape[0] > 1 else feat.shape[1]
-            return C.c_void_p(feat.data_ptr()), (PROP_BF16 if feat.dtype == torch.bfloat16 else PROP_F32), int(feat.shape[1]), int(ldf), True, feat
+            return C.c_void_p(feat.data_ptr()), types[feat.dtype], int(feat.shape[1]), int(ldf), True, feat
         a = np.asarray(feat)
-        want = np.uint16 if bf16 else np.float32
+        # the keyword says what the codes of an integer array are: True or "bf16" for uint16, "e4m3" or "e5m2" for uint8
+        if isinstance(bf16, str):
+            if bf16 not in ("bf16", "e4m3", "e5m2"):
+                raise ValueError(f'{name}: the element type "{bf16}" is not "bf16", "e4m3" or "e5m2"')
+            ftype, want = {"bf16": (PROP_BF16, np.uint16), "e4m3": (PROP_E4M3, np.uint8), "e5m2": (PROP_E5M2, np.uint8)}[bf16]
+        elif bf16:
+            ftype, want = PROP_BF16, np.uint16
+        elif a.dtype == np.float16:
+            ftype, want = PROP_F16, np.float16
+        else:
+            ftype, want = PROP_F32, np.float32
         if a.dtype != want:
-            raise ValueError(f"a numpy {name} must be float32, or uint16 with bf16=True")
+            raise ValueError(f'a numpy {name} must be float32 or float16, or uint16 with bf16=True, or uint8 with "e4m3" or "e5m2" in its place')
         if a.ndim != 2 or a.shape[0] != rows:
             raise ValueError(f"{name} must be {shape}")
         it = a.itemsize
@@ -590,7 +606,7 @@ class Engine:
         elif (a.shape[1] > 1 and a.strides[1] != it) or (a.shape[0] > 1 and (a.strides[0] % it or a.strides[0] < a.shape[1] * it)):
             raise ValueError(f"{name}: a column stride other than one element (or rows that overlap) is not supported")
         ldf = a.strides[0] // it if a.shape[0] > 1 else a.shape[1]
-        return _p(a), (PROP_BF16 if bf16 else PROP_F32), int(a.shape[1]), int(ldf), False, a
+        return _p(a), ftype, int(a.shape[1]), int(ldf), False, a
 
     def _prop_out(self, out, nq, d, dtype, on_device, name):
         """(pointer, ldo, array) of a caller-made output ([nq, d], row stride = ldo) -- it must live where feat lives"""
@@ -616,7 +632,7 @@ class Engine:
         contract's fixed order, every bit defined.  row_ptr: as the sparse call returned it.  feat: a numpy float32 array
         [n, d] (the row stride becomes ldf; a column stride other than one element is rejected), a numpy uint16 array with
         bf16=True, or a torch tensor on the context's GPU (float32 or bfloat16, any row stride: a column slice of a wider
-        tensor is read in place).  normalize: every row divided by the sum of its kept values.  Returns
+        tensor is read in place).  The narrow types (float16, FP8 E4M3 / E5M2), here and in every call below: _prop_feat.  normalize: every row divided by the sum of its kept values.  Returns
         (out32 or None, out64 or None, stats dict): float32 / float64 [nq, d]; torch tensors on the device with a torch
         feat, numpy arrays otherwise.  out32 / out64: caller-made outputs to fill instead (their row stride is ldo; columns
         past d are left alone), both with the same row stride.  values (fora_hip_sparse_propagate_vals, PROPAGATE WITH

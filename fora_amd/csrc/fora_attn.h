@@ -31,7 +31,7 @@ __device__ __forceinline__ void attn_wave_sync() {
 }
 
 // the product of one (row, head): o32 / o64 point at the head's first output column of the row (either may be null)
-template <bool BF16, int V>
+template <int ET, int V>
 __device__ __forceinline__ void attn_product(const double *ysh, const int32_t *idsh, uint32_t len, const void *v, int64_t ldv, uint64_t vcol, uint32_t dv,
                                              uint32_t lane, float *o32, double *o64) {
 #pragma clang fp contract(off)
@@ -41,7 +41,7 @@ __device__ __forceinline__ void attn_product(const double *ysh, const int32_t *i
 #pragma unroll
         for (int i = 0; i < V; i++) acc[i] = 0.0;
         for (uint32_t k = 0; k < len; k += PROP_INFLIGHT) {
-            PropRaw<BF16, V> raw[PROP_INFLIGHT];
+            PropRaw<ET, V> raw[PROP_INFLIGHT];
             uint64_t off[PROP_INFLIGHT];
             double w[PROP_INFLIGHT];
 #pragma unroll
@@ -50,23 +50,23 @@ __device__ __forceinline__ void attn_product(const double *ysh, const int32_t *i
                 off[u] = (uint64_t)(uint32_t)idsh[from] * (uint64_t)ldv + vcol + c0;
                 w[u] = ysh[from];
 #pragma unroll
-                for (int j = 0; j < PropRaw<BF16, V>::W; j++) raw[u].w[j] = 0;
+                for (int j = 0; j < PropRaw<ET, V>::W; j++) raw[u].w[j] = 0;
             }
             if (ncol == (uint32_t)V) { // (as in prop_gather_body: the choice stands outside the loop over the rows)
 #pragma unroll
                 for (int u = 0; u < PROP_INFLIGHT; u++)
-                    if (k + (uint32_t)u < len) prop_load_full<BF16, V>(v, off[u], raw[u]);
+                    if (k + (uint32_t)u < len) prop_load_full<ET, V>(v, off[u], raw[u]);
             } else {
 #pragma unroll
                 for (int u = 0; u < PROP_INFLIGHT; u++)
-                    if (k + (uint32_t)u < len) prop_load_tail<BF16, V>(v, off[u], ncol, raw[u]);
+                    if (k + (uint32_t)u < len) prop_load_tail<ET, V>(v, off[u], ncol, raw[u]);
             }
 #pragma unroll
             for (int u = 0; u < PROP_INFLIGHT; u++) {
                 const bool valid = k + (uint32_t)u < len;
 #pragma unroll
                 for (int i = 0; i < V; i++) {
-                    const double term = w[u] * prop_widen<BF16, V>(raw[u], i);
+                    const double term = w[u] * prop_widen<ET, V>(raw[u], i);
                     const double sum = acc[i] + term;
                     acc[i] = valid ? sum : acc[i];
                 }
@@ -85,12 +85,13 @@ __device__ __forceinline__ void attn_product(const double *ysh, const int32_t *i
 // grid = ceil(nrow * heads / ATTN_ROWS) workgroups of BLOCK threads.  Wave u of the grid owns head u % heads of row u / heads
 // of the list (adjacent waves share a row of q).  q, k, v: the whole operands; head j reads the columns [j * d, (j + 1) * d) of
 // q and k and [j * dv, (j + 1) * dv) of v.  lg = log2 of the lane group of the scores.  out32 / out64: nq x heads * dv with
-// their own pitches, either may be null; y32 / y64: [heads][entries], both may be null.
-template <bool Q_BF16, bool K_BF16, bool V_BF16, int V>
+// their own pitches, either may be null; y32 / y64: [heads][entries], both may be null.  Q_ET, K_ET: the types of the two
+// one-element-per-lane operands as sddmm_load takes them (types: sddmm_types() of the two, for ELT_ANY); V_ET: v's own type.
+template <int Q_ET, int K_ET, int V_ET, int V>
 __global__ void __launch_bounds__(BLOCK) k_attn_short(const PropSeg *rows, uint64_t nrow, uint32_t heads, const int32_t *ids, const void *q, int64_t ldq,
                                                       const void *k, int64_t ldk, const void *v, int64_t ldv, uint32_t d, uint32_t dv, uint32_t lg,
                                                       double scale, uint64_t entries, float *out32, int64_t ld32, double *out64, int64_t ld64,
-                                                      float *y32, double *y64, uint32_t *nan_rows) {
+                                                      float *y32, double *y64, uint32_t *nan_rows, uint32_t types) {
 #pragma clang fp contract(off)
     __shared__ double sh_y[ATTN_ROWS][PROP_SEG];
     __shared__ int32_t sh_id[ATTN_ROWS][PROP_SEG];
@@ -115,7 +116,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_short(const PropSeg *rows, uint6
 #pragma unroll
     for (uint32_t j = 0; j < SMAX_PER_LANE; j++)
         if (lane + 64u * j < sg.len) idsh[lane + 64u * j] = ids[sg.first + lane + 64u * j];
-    sddmm_scores<Q_BF16, K_BF16>(ids + sg.first, sg.len, q, (uint64_t)(uint32_t)sg.row * (uint64_t)ldq + (uint64_t)head * d, k, ldk, (uint64_t)head * d, d, lg, lane,
+    sddmm_scores<Q_ET, K_ET>(ids + sg.first, sg.len, q, (uint64_t)(uint32_t)sg.row * (uint64_t)ldq + (uint64_t)head * d, k, ldk, (uint64_t)head * d, d, lg, lane, types,
                                  [=](uint32_t e, double s) { ysh[e] = s; });
     attn_wave_sync();
     // ---- softmax in registers
@@ -144,7 +145,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_short(const PropSeg *rows, uint6
     smax_store(rel, lane, x, nullptr, ysh);
     attn_wave_sync();
     // ---- the product
-    attn_product<V_BF16, V>(ysh, idsh, sg.len, v, ldv, (uint64_t)head * dv, dv, lane, o32, o64);
+    attn_product<V_ET, V>(ysh, idsh, sg.len, v, ldv, (uint64_t)head * dv, dv, lane, o32, o64);
 }
 
 // The longer rows go through the existing kernels, whose products define no NaN payload: this one rewrites the dv outputs of

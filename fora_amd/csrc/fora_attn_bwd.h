@@ -28,12 +28,13 @@ namespace fora {
 // of the list.  g: nq x heads * dv (the gradient of the output), v: n x heads * dv, k: n x heads * d -- the whole operands;
 // lgv = log2 of the lane group that scores dv columns.  y: [heads][entries], f64 when y_f64, else f32 widened exactly.
 // ds (null: no column side wants it): [heads][entries].  dq32 / dq64: nq x heads * d with their own pitches; both null: dq is
-// not wanted and the product is skipped.
-template <bool G_BF16, bool V_BF16, bool K_BF16, int V>
+// not wanted and the product is skipped.  G_ET, V_ET: the types of g and v as sddmm_load takes them (types: sddmm_types() of the
+// two, for ELT_ANY); K_ET: k's own type.
+template <int G_ET, int V_ET, int K_ET, int V>
 __global__ void __launch_bounds__(BLOCK) k_attn_bwd_short(const PropSeg *rows, uint64_t nrow, uint32_t heads, const int32_t *ids, const void *g, int64_t ldg,
                                                           const void *v, int64_t ldv, const void *k, int64_t ldk, uint32_t d, uint32_t dv, uint32_t lgv,
                                                           double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *dq32, int64_t ld32,
-                                                          double *dq64, int64_t ld64) {
+                                                          double *dq64, int64_t ld64, uint32_t types) {
 #pragma clang fp contract(off)
     __shared__ double sh_s[ATTN_ROWS][PROP_SEG];
     __shared__ int32_t sh_id[ATTN_ROWS][PROP_SEG];
@@ -58,7 +59,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_bwd_short(const PropSeg *rows, u
 #pragma unroll
     for (uint32_t j = 0; j < SMAX_PER_LANE; j++)
         if (lane + 64u * j < sg.len) idsh[lane + 64u * j] = ids[sg.first + lane + 64u * j];
-    sddmm_scores<G_BF16, V_BF16>(ids + sg.first, sg.len, g, (uint64_t)(uint32_t)sg.row * (uint64_t)ldg + (uint64_t)head * dv, v, ldv, (uint64_t)head * dv, dv, lgv, lane,
+    sddmm_scores<G_ET, V_ET>(ids + sg.first, sg.len, g, (uint64_t)(uint32_t)sg.row * (uint64_t)ldg + (uint64_t)head * dv, v, ldv, (uint64_t)head * dv, dv, lgv, lane, types,
                                  [=](uint32_t e, double s) { ssh[e] = s; });
     attn_wave_sync();
     // ---- D and ds in registers: y from the caller's array, dy from LDS
@@ -74,7 +75,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_bwd_short(const PropSeg *rows, u
     smax_store(rel, lane, yv, nullptr, ssh);
     attn_wave_sync();
     // ---- dq
-    attn_product<K_BF16, V>(ssh, idsh, sg.len, k, ldk, (uint64_t)head * d, d, lane, o32, o64);
+    attn_product<K_ET, V>(ssh, idsh, sg.len, k, ldk, (uint64_t)head * d, d, lane, o32, o64);
 }
 
 // grid = (ceil(ncol * heads / (units per workgroup)), column tiles), BLOCK threads; units per workgroup = (BLOCK / 64) * (64 / G).
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_bwd_short(const PropSeg *rows, u
 // time, one per lane, hands them round with a shuffle, and has the loads of PROP_INFLIGHT feat rows issued before the first is
 // widened and added.  The adds follow the entry order.  out32 / out64: n x heads * w with their own pitches, either may be
 // null.
-template <bool BF16, int V, bool VAL64>
+template <int ET, int V, bool VAL64>
 __global__ void __launch_bounds__(BLOCK) k_attn_cols(const PropSeg *cols, uint64_t ncol, uint32_t heads, const int32_t *rows, const int64_t *pos, const void *values,
                                                      uint64_t entries, const void *feat, int64_t ldf, uint32_t w, uint32_t G, float *out32, int64_t ld32,
                                                      double *out64, int64_t ld64) {
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(BLOCK) k_attn_cols(const PropSeg *cols, uint64
         }
         const uint32_t cnt = min(G, len - base);
         for (uint32_t k = 0; k < cnt; k += PROP_INFLIGHT) {
-            PropRaw<BF16, V> raw[PROP_INFLIGHT];
+            PropRaw<ET, V> raw[PROP_INFLIGHT];
             uint64_t off[PROP_INFLIGHT];
             double wt[PROP_INFLIGHT];
 #pragma unroll
@@ -129,23 +130,23 @@ __global__ void __launch_bounds__(BLOCK) k_attn_cols(const PropSeg *cols, uint64
                 off[t] = (uint64_t)(uint32_t)__shfl(id_l, from, (int)G) * (uint64_t)ldf + fcol;
                 wt[t] = __shfl(w_l, from, (int)G);
 #pragma unroll
-                for (int j = 0; j < PropRaw<BF16, V>::W; j++) raw[t].w[j] = 0;
+                for (int j = 0; j < PropRaw<ET, V>::W; j++) raw[t].w[j] = 0;
             }
             if (ncl == (uint32_t)V) { // (as in prop_gather_body: the choice stands outside the loop over the rows)
 #pragma unroll
                 for (int t = 0; t < PROP_INFLIGHT; t++)
-                    if (k + (uint32_t)t < cnt) prop_load_full<BF16, V>(feat, off[t], raw[t]);
+                    if (k + (uint32_t)t < cnt) prop_load_full<ET, V>(feat, off[t], raw[t]);
             } else if (ncl) {
 #pragma unroll
                 for (int t = 0; t < PROP_INFLIGHT; t++)
-                    if (k + (uint32_t)t < cnt) prop_load_tail<BF16, V>(feat, off[t], ncl, raw[t]);
+                    if (k + (uint32_t)t < cnt) prop_load_tail<ET, V>(feat, off[t], ncl, raw[t]);
             }
 #pragma unroll
             for (int t = 0; t < PROP_INFLIGHT; t++) {
                 const bool valid = k + (uint32_t)t < cnt;
 #pragma unroll
                 for (int i = 0; i < V; i++) {
-                    const double term = wt[t] * prop_widen<BF16, V>(raw[t], i);
+                    const double term = wt[t] * prop_widen<ET, V>(raw[t], i);
                     const double sum = acc[i] + term;
                     acc[i] = valid ? sum : acc[i];
                 }

@@ -2519,19 +2519,45 @@ template <typename T> struct HeldOut {
         return FORA_OK;
     }
 };
-// f(std::bool_constant<bf16>, std::integral_constant<int, V>): the instantiation for an element type and the vector width that
-// prop_geom / attn_vec_width took from prop_widths(bf16)
-template <typename F> void with_vec(bool bf16, uint32_t V, F &&f) {
-    using std::integral_constant;
-    if (!bf16) switch (V) {
-        case 4: f(std::false_type{}, integral_constant<int, 4>{}); break;
-        case 2: f(std::false_type{}, integral_constant<int, 2>{}); break;
-        default: f(std::false_type{}, integral_constant<int, 1>{}); break;
-    } else switch (V) {
-        case 8: f(std::true_type{}, integral_constant<int, 8>{}); break;
-        case 4: f(std::true_type{}, integral_constant<int, 4>{}); break;
-        default: f(std::true_type{}, integral_constant<int, 1>{}); break;
+// The element types of the dense operands are those of fora_narrow.h, which also says how many bytes each takes (elt_bytes)
+static_assert(ELT_F32 == FORA_PROP_F32 && ELT_BF16 == FORA_PROP_BF16 && ELT_F16 == FORA_PROP_F16 && ELT_E4M3 == FORA_PROP_E4M3 && ELT_E5M2 == FORA_PROP_E5M2,
+              "fora_narrow.h and include/fora_hip.h name one set of element types");
+template <int N> using int_c = std::integral_constant<int, N>;
+// f(int_c<ET>, int_c<V>): the instantiation for an element type and one of the three vector widths that prop_geom /
+// attn_vec_width took from prop_widths_bytes(elt_bytes(et)) -- a load site of V elements a lane, whose layout hangs on the type
+template <int ET, typename F> void with_vec_of(uint32_t V, F &&f) {
+    constexpr int wide = 16 / (int)elt_bytes(ET), mid = elt_bytes(ET) == 4 ? 2 : 4;
+    if (V == (uint32_t)wide) f(int_c<ET>{}, int_c<wide>{});
+    else if (V == (uint32_t)mid) f(int_c<ET>{}, int_c<mid>{});
+    else f(int_c<ET>{}, int_c<1>{});
+}
+template <typename F> void with_vec(int et, uint32_t V, F &&f) {
+    switch (et) {
+        case ELT_F32: with_vec_of<ELT_F32>(V, f); break;
+        case ELT_BF16: with_vec_of<ELT_BF16>(V, f); break;
+        case ELT_F16: with_vec_of<ELT_F16>(V, f); break;
+        case ELT_E4M3: with_vec_of<ELT_E4M3>(V, f); break;
+        default: with_vec_of<ELT_E5M2>(V, f); break;
     }
+}
+// f(int_c<A>, int_c<B>) for the two operands of a one-element-per-lane load site (sddmm_load): the four compiled-in pairs of
+// f32 and bf16, and one class, ELT_ANY for both, that reads the types at run time when either is a narrow one
+template <typename F> void with_elt_pair(int a, int b, F &&f) {
+    const bool a_old = a == ELT_F32 || a == ELT_BF16, b_old = b == ELT_F32 || b == ELT_BF16;
+    if (!a_old || !b_old) f(int_c<ELT_ANY>{}, int_c<ELT_ANY>{});
+    else if (a == ELT_BF16) { if (b == ELT_BF16) f(int_c<ELT_BF16>{}, int_c<ELT_BF16>{}); else f(int_c<ELT_BF16>{}, int_c<ELT_F32>{}); }
+    else { if (b == ELT_BF16) f(int_c<ELT_F32>{}, int_c<ELT_BF16>{}); else f(int_c<ELT_F32>{}, int_c<ELT_F32>{}); }
+}
+// f(int_c<A>, int_c<B>, int_c<ET>, int_c<V>) for a fused kernel with a pair of one-element-per-lane operands and a vector one:
+// the 24 instantiations of old while all three types are f32 or bf16; with a narrow type anywhere, ELT_ANY for the pair and
+// the vector operand's own type -- 15 more, not 5 * 5 * 15
+template <typename F> void with_fused_types(int a, int b, int vt, uint32_t V, F &&f) {
+    const auto old = [](int t) { return t == ELT_F32 || t == ELT_BF16; };
+    if (!old(a) || !old(b) || !old(vt)) with_vec(vt, V, [&](auto E, auto W) { f(int_c<ELT_ANY>{}, int_c<ELT_ANY>{}, E, W); });
+    else with_elt_pair(a, b, [&](auto A, auto B) {
+        if (vt == ELT_BF16) with_vec_of<ELT_BF16>(V, [&](auto E, auto W) { f(A, B, E, W); });
+        else with_vec_of<ELT_F32>(V, [&](auto E, auto W) { f(A, B, E, W); });
+    });
 }
 // f(std::bool_constant<a>, std::bool_constant<b>)
 template <typename F> void with_bools(bool a, bool b, F &&f) {
@@ -2568,20 +2594,20 @@ struct PropSide {
 };
 struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
 
-template <bool BF16, int V>
+template <int ET, int V>
 void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
     const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
     const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
     if (sd.values) with_bools(sd.pos != nullptr, sd.val64, [&](auto POS, auto V64) {
-        hipLaunchKernelGGL((k_prop_gather_vals<BF16, V, POS.value, V64.value>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
+        hipLaunchKernelGGL((k_prop_gather_vals<ET, V, POS.value, V64.value>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
     });
-    else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
-    else hipLaunchKernelGGL((k_prop_gather<BF16, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
+    else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
+    else hipLaunchKernelGGL((k_prop_gather<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
 }
 // the two kernels chunk by chunk over a plan whose segments and records lie at d_segs and d_recs: the partial sums of one chunk
 // live at a time in the ctx's buffers, which the caller has ensured.  timed: an event pair per launch (PROPAGATE's own stats);
 // a caller with a span of its own around the whole passes false.
-void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, bool bf16, const PropGeom &g,
+void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, int et, const PropGeom &g,
                         const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed) {
     PropBufs &b = c->pr;
     for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
@@ -2590,7 +2616,7 @@ void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs
             EvSpan ev(c);
             if (timed) ev.begin(EV_PROP_GATHER);
             const PropSeg *segs = d_segs + ch.seg0;
-            with_vec(bf16, g.V, [&](auto B, auto V) { prop_launch_gather<B.value, V.value>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); });
+            with_vec(et, g.V, [&](auto E, auto V) { prop_launch_gather<E.value, V.value>(c, g, segs, ch.nseg, sd, feat, ldf, d, b.d_part.get(), segsum); });
         }
         if (ch.nrec) {
             EvSpan ev(c);
@@ -2618,7 +2644,7 @@ template <typename... O> int held_fetch(fora_ctx *c, const O &...o) { // the sta
 }
 // the product of one side with feat (resolved, as values and the outputs are): plan, buffers, the two kernels chunk by chunk, the
 // staged outputs; the stream is idle and the event times are collected when it returns FORA_OK
-int prop_run(fora_ctx *c, const PropSide &side, HeldIn feat, HeldIn values, bool bf16, int d, int64_t ldf, HeldOut<float> o32, HeldOut<double> o64, PropRunStats &rs) {
+int prop_run(fora_ctx *c, const PropSide &side, HeldIn feat, HeldIn values, int et, int d, int64_t ldf, HeldOut<float> o32, HeldOut<double> o64, PropRunStats &rs) {
     PropSide sd = side;
     const int nq = sd.rows;
     PropBufs &b = c->pr;
@@ -2642,10 +2668,10 @@ int prop_run(fora_ctx *c, const PropSide &side, HeldIn feat, HeldIn values, bool
     if (int rc = o64.reserve(c, b.d_out64)) return rc;
     if (!plan.segs.empty()) HIPCHK(c, hipMemcpy(b.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(b.d_recs.get(), plan.recs.data(), plan.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
-    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat.ptr(), ldf, d, bf16 ? 2 : 4, prop_widths(bf16), PROP_NWIDTHS);
+    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat.ptr(), ldf, d, elt_bytes(et), prop_widths_bytes(elt_bytes(et)), PROP_NWIDTHS);
     uint64_t *const segsum = sd.divide ? b.d_segsum.get() : nullptr;
     c->tm.prop_gather_ms = c->tm.prop_combine_ms = 0;
-    prop_launch_chunks(c, plan, b.d_segs.get(), b.d_recs.get(), sd, bf16, g, feat.ptr(), ldf, d, segsum, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), true);
+    prop_launch_chunks(c, plan, b.d_segs.get(), b.d_recs.get(), sd, et, g, feat.ptr(), ldf, d, segsum, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), true);
     if (int rc = held_fetch(c, o32, o64)) return rc;
     if (int rc = held_call_end(c, "sparse propagate")) return rc;
     rs.segments = total; rs.max_row = plan.max_row; rs.chunks = (int32_t)plan.chunks.size(); rs.feat_on_device = feat.on_device();
@@ -2653,22 +2679,21 @@ int prop_run(fora_ctx *c, const PropSide &side, HeldIn feat, HeldIn values, bool
 }
 // the operands and outputs of the two products: feat of feat_rows rows, values per entry, out of out_rows rows
 struct PropIO { HeldIn feat, values; HeldOut<float> o32; HeldOut<double> o64; };
-PropIO prop_io(fora_ctx *c, const void *feat, bool bf16, uint64_t feat_rows, int64_t ldf, int d, const void *values, int val_type, float *out32, double *out64,
+PropIO prop_io(fora_ctx *c, const void *feat, int et, uint64_t feat_rows, int64_t ldf, int d, const void *values, int val_type, float *out32, double *out64,
                uint64_t out_rows, int64_t ldo) {
-    return PropIO{HeldIn::matrix(feat, feat_rows, ldf, (uint64_t)d, bf16 ? 2 : 4), HeldIn::vector(values, c->sp.entries, val_type == FORA_PROP_F64 ? 8 : 4),
+    return PropIO{HeldIn::matrix(feat, feat_rows, ldf, (uint64_t)d, elt_bytes(et)), HeldIn::vector(values, c->sp.entries, val_type == FORA_PROP_F64 ? 8 : 4),
                   HeldOut<float>{out32, ldo, out_rows, (uint64_t)d}, HeldOut<double>{out64, ldo, out_rows, (uint64_t)d}};
 }
 int prop_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, const void *values, int val_type,
               float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
-    const bool bf16 = feat_type == FORA_PROP_BF16;
-    PropIO io = prop_io(c, feat, bf16, held_cols(c), ldf, d, values, val_type, out32, out64, (uint64_t)nq, ldo);
+    PropIO io = prop_io(c, feat, feat_type, held_cols(c), ldf, d, values, val_type, out32, out64, (uint64_t)nq, ldo);
     if (int rc = held_resolve(c, io.values, io.feat, io.o32, io.o64)) return rc;
     const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), c->sp.d_fix.get(), nullptr, (flags & FORA_PROP_NORMALIZE) != 0, values, val_type == FORA_PROP_F64, nullptr};
     PropRunStats rs;
-    if (int rc = prop_run(c, sd, io.feat, io.values, bf16, d, ldf, io.o32, io.o64, rs)) return rc;
+    if (int rc = prop_run(c, sd, io.feat, io.values, feat_type, d, ldf, io.o32, io.o64, rs)) return rc;
     if (ps) {
         ps->entries = c->sp.entries; ps->segments = rs.segments; ps->max_row = rs.max_row;
-        ps->feat_bytes = c->sp.entries * (uint64_t)d * (bf16 ? 2 : 4);
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * elt_bytes(feat_type);
         ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device;
         ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
     }
@@ -2772,8 +2797,7 @@ int propt_ensure_pos(fora_ctx *c, const int64_t *row_ptr, int nq) {
 }
 int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, const void *values, int val_type,
                float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
-    const bool bf16 = grad_type == FORA_PROP_BF16;
-    PropIO io = prop_io(c, grad, bf16, (uint64_t)nq, ldg, d, values, val_type, out32, out64, held_cols(c), ldo);
+    PropIO io = prop_io(c, grad, grad_type, (uint64_t)nq, ldg, d, values, val_type, out32, out64, held_cols(c), ldo);
     if (int rc = held_resolve(c, io.feat, io.values, io.o32, io.o64)) return rc; // (before the transposition is built)
     bool built_now = false;
     if (int rc = propt_ensure(c, row_ptr, nq, built_now)) return rc;
@@ -2783,11 +2807,11 @@ int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, in
     const PropSide sd{t.h_col_ptr.data(), (int)held_cols(c), t.d_rows.get(), t.d_fix.get(), (flags & FORA_PROP_NORMALIZE) ? t.d_rsum.get() : nullptr, false,
                       values, val_type == FORA_PROP_F64, values ? t.d_pos.get() : nullptr};
     PropRunStats rs;
-    if (int rc = prop_run(c, sd, io.feat, io.values, bf16, d, ldg, io.o32, io.o64, rs)) return rc;
+    if (int rc = prop_run(c, sd, io.feat, io.values, grad_type, d, ldg, io.o32, io.o64, rs)) return rc;
     if (built_now) transpose_ms = c->tm.propt_transpose_ms; // (with values: the places too)
     if (ps) {
         ps->entries = c->sp.entries; ps->columns = t.columns; ps->segments = rs.segments; ps->max_col = t.max_col;
-        ps->feat_bytes = c->sp.entries * (uint64_t)d * (bf16 ? 2 : 4);
+        ps->feat_bytes = c->sp.entries * (uint64_t)d * elt_bytes(grad_type);
         ps->chunks = rs.chunks; ps->feat_on_device = rs.feat_on_device; ps->built = built_now ? 1 : 0;
         if (built_now) { ps->short_cols = (int32_t)t.short_cols; ps->lds_cols = (int32_t)t.lds_cols; ps->global_cols = (int32_t)t.global_cols; }
         ps->transpose_ms = transpose_ms; ps->gather_ms = c->tm.prop_gather_ms; ps->combine_ms = c->tm.prop_combine_ms;
@@ -2796,22 +2820,22 @@ int propt_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, in
 }
 
 // ---- SCORES (SDDMM)
-template <bool A_BF16, bool B_BF16>
-void sddmm_launch(fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg, float *o32, double *o64) {
+template <int A_ET, int B_ET>
+void sddmm_launch(fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg, float *o32, double *o64,
+                  uint32_t types) {
     const uint64_t units = nseg * SDDMM_UNITS, per_wg = BLOCK / 64;
-    hipLaunchKernelGGL((k_prop_sddmm<A_BF16, B_BF16>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, nseg,
-                       (const int32_t *)c->sp.d_ids.get(), a, lda, b, ldb, (uint32_t)d, lg, o32, o64);
+    hipLaunchKernelGGL((k_prop_sddmm<A_ET, B_ET>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, nseg,
+                       (const int32_t *)c->sp.d_ids.get(), a, lda, b, ldb, (uint32_t)d, lg, o32, o64, types);
 }
 // sddmm_launch for the element types of a and b
-void sddmm_launch_for(bool a_bf16, bool b_bf16, fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg,
+void sddmm_launch_for(int a_type, int b_type, fora_ctx *c, const PropSeg *segs, uint64_t nseg, const void *a, int64_t lda, const void *b, int64_t ldb, int d, uint32_t lg,
                       float *o32, double *o64) {
-    with_bools(a_bf16, b_bf16, [&](auto AB, auto BB) { sddmm_launch<AB.value, BB.value>(c, segs, nseg, a, lda, b, ldb, d, lg, o32, o64); });
+    with_elt_pair(a_type, b_type, [&](auto A, auto B) { sddmm_launch<A.value, B.value>(c, segs, nseg, a, lda, b, ldb, d, lg, o32, o64, sddmm_types(a_type, b_type)); });
 }
 int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a_, int a_type, int64_t lda, const void *b_, int b_type, int64_t ldb, int d,
                float *out32, double *out64, fora_sddmm_stats *st) {
     const uint64_t entries = c->sp.entries;
-    const bool a_bf16 = a_type == FORA_PROP_BF16, b_bf16 = b_type == FORA_PROP_BF16;
-    const uint32_t a_elt = a_bf16 ? 2 : 4, b_elt = b_bf16 ? 2 : 4;
+    const uint32_t a_elt = elt_bytes(a_type), b_elt = elt_bytes(b_type);
     HeldIn a = HeldIn::matrix(a_, (uint64_t)nq, lda, (uint64_t)d, a_elt), b = HeldIn::matrix(b_, held_cols(c), ldb, (uint64_t)d, b_elt);
     HeldOut<float> o32 = HeldOut<float>::vector(out32, entries);
     HeldOut<double> o64 = HeldOut<double>::vector(out64, entries);
@@ -2829,7 +2853,7 @@ int sddmm_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a_, int 
     if (!plan.segs.empty()) {
         HIPCHK(c, hipMemcpy(pb.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
         EvSpan ev(c, EV_SDDMM);
-        sddmm_launch_for(a_bf16, b_bf16, c, pb.d_segs.get(), plan.segs.size(), a.ptr(), lda, b.ptr(), ldb, d, prop_group_lg((uint32_t)d), o32.ptr(), o64.ptr());
+        sddmm_launch_for(a_type, b_type, c, pb.d_segs.get(), plan.segs.size(), a.ptr(), lda, b.ptr(), ldb, d, prop_group_lg((uint32_t)d), o32.ptr(), o64.ptr());
     }
     if (int rc = held_fetch(c, o32, o64)) return rc;
     if (int rc = held_call_end(c, "sparse sddmm")) return rc;
@@ -2932,12 +2956,12 @@ int softmax_entry(fora_ctx *c, const char *who, const int64_t *row_ptr, int nq, 
 }
 
 // ---- ATTENTION
-template <bool QB, bool KB, bool VB, int V>
+template <int QE, int KE, int VE, int V>
 void attn_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *q, int64_t ldq, const void *k, int64_t ldk, const void *v, int64_t ldv,
-                 int d, int dv, uint32_t lg, double scale, uint64_t entries, float *o32, int64_t ld32, double *o64, int64_t ld64, float *y32, double *y64, uint32_t *nan_rows) {
+                 int d, int dv, uint32_t lg, double scale, uint64_t entries, float *o32, int64_t ld32, double *o64, int64_t ld64, float *y32, double *y64, uint32_t *nan_rows, uint32_t types) {
     const uint64_t units = nrow * (uint64_t)heads;
-    hipLaunchKernelGGL((k_attn_short<QB, KB, VB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
-                       (const int32_t *)c->sp.d_ids.get(), q, ldq, k, ldk, v, ldv, (uint32_t)d, (uint32_t)dv, lg, scale, entries, o32, ld32, o64, ld64, y32, y64, nan_rows);
+    hipLaunchKernelGGL((k_attn_short<QE, KE, VE, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), q, ldq, k, ldk, v, ldv, (uint32_t)d, (uint32_t)dv, lg, scale, entries, o32, ld32, o64, ld64, y32, y64, nan_rows, types);
 }
 inline const void *attn_cols(const void *m, uint64_t col, uint32_t elt) { return (const unsigned char *)m + col * elt; }
 
@@ -2945,8 +2969,7 @@ int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, 
                    const void *v_, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
                    float *y32_, double *y64_, fora_attn_stats *st) {
     const uint64_t entries = c->sp.entries, n = held_cols(c);
-    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16;
-    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4;
+    const uint32_t q_elt = elt_bytes(q_type), k_elt = elt_bytes(k_type), v_elt = elt_bytes(v_type);
     const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
     HeldIn q = HeldIn::matrix(q_, (uint64_t)nq, ldq, wq, q_elt), k = HeldIn::matrix(k_, n, ldk, wq, k_elt), v = HeldIn::matrix(v_, n, ldv, wv, v_elt);
     HeldOut<float> o32{out32, ldo, (uint64_t)nq, wv}, y32 = HeldOut<float>::vector(y32_, (uint64_t)heads * entries);
@@ -2993,33 +3016,31 @@ int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, 
         HIPCHK(c, hipMemcpy(pb.d_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
     }
     const uint32_t lg = prop_group_lg((uint32_t)d);
-    const uint32_t *const widths = prop_widths(v_bf16);
+    const uint32_t *const widths = prop_widths_bytes(v_elt);
     c->tm.attn_ms = 0;
     uint32_t nan_rows = 0;
     HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
     {
         EvSpan ev(c, EV_ATTN);
-        if (!plan.shrt.empty()) with_bools(q_bf16, k_bf16, [&](auto QB, auto KB) {
-            constexpr bool qb = decltype(QB)::value, kb = decltype(KB)::value;
-            with_vec(v_bf16, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto VB, auto V) {
-                attn_launch<qb, kb, VB.value, V.value>(c, ds + at_short, plan.shrt.size(), heads, q.ptr(), ldq, k.ptr(), ldk, v.ptr(), ldv, d, dv, lg, scale, entries,
-                                                       o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get());
+        if (!plan.shrt.empty())
+            with_fused_types(q_type, k_type, v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto QE, auto KE, auto VE, auto V) {
+                attn_launch<QE.value, KE.value, VE.value, V.value>(c, ds + at_short, plan.shrt.size(), heads, q.ptr(), ldq, k.ptr(), ldk, v.ptr(), ldv, d, dv, lg, scale, entries,
+                                                                   o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get(), sddmm_types(q_type, k_type));
             });
-        });
         for (int h = 0; lng && h < heads; h++) { // the longer rows, one head at a time through the two per-entry buffers
             const void *qh = attn_cols(q.ptr(), (uint64_t)h * d, q_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
             double *const s64 = pb.d_attn_s.get();
             double *const yh64 = y64.ptr() ? y64.ptr((uint64_t)h * entries) : pb.d_attn_y.get();
             float *const yh32 = y32.ptr((uint64_t)h * entries);
             const PropSeg *segs = ds + at_lsegs;
-            sddmm_launch_for(q_bf16, k_bf16, c, segs, plan.lng.segs.size(), qh, ldq, kh, ldk, d, lg, nullptr, s64);
+            sddmm_launch_for(q_type, k_type, c, segs, plan.lng.segs.size(), qh, ldq, kh, ldk, d, lg, nullptr, s64);
             const SoftmaxWork w{ds + at_sm, ds + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, pb.d_smax_nan.get()};
             softmax_launch<double>(c, w, s64, scale, yh32, yh64);
             const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), nullptr, nullptr, false, yh64, true, nullptr};
             const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, PROP_NWIDTHS);
             float *const oh32 = o32.ptr((uint64_t)h * dv);
             double *const oh64 = o64.ptr((uint64_t)h * dv);
-            prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, v_bf16, g, vh, ldv, dv, nullptr, oh32, o32.ld(), oh64, o64.ld(), false);
+            prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, v_type, g, vh, ldv, dv, nullptr, oh32, o32.ld(), oh64, o64.ld(), false);
             const dim3 grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(plan.lrows.size(), 65535));
             hipLaunchKernelGGL(k_attn_nan_rows, grid, dim3(BLOCK), 0, c->stream, (const PropSeg *)(ds + at_lrows), (uint64_t)plan.lrows.size(), (const double *)yh64,
                                (uint32_t)dv, oh32, o32.ld(), oh64, o64.ld());
@@ -3038,22 +3059,23 @@ int attention_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *q_, 
 }
 
 // ---- ATTENTION, BACKWARD
-template <bool GB, bool VB, bool KB, int V>
+template <int GE, int VE, int KE, int V>
 void attn_bwd_launch(fora_ctx *c, const PropSeg *rows, uint64_t nrow, int heads, const void *g, int64_t ldg, const void *v, int64_t ldv, const void *k, int64_t ldk,
-                     int d, int dv, uint32_t lgv, double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *o32, int64_t ld32, double *o64, int64_t ld64) {
+                     int d, int dv, uint32_t lgv, double scale, uint64_t entries, const void *y, bool y_f64, double *ds, float *o32, int64_t ld32, double *o64, int64_t ld64,
+                     uint32_t types) {
     const uint64_t units = nrow * (uint64_t)heads;
-    hipLaunchKernelGGL((k_attn_bwd_short<GB, VB, KB, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
-                       (const int32_t *)c->sp.d_ids.get(), g, ldg, v, ldv, k, ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, entries, y, y_f64, ds, o32, ld32, o64, ld64);
+    hipLaunchKernelGGL((k_attn_bwd_short<GE, VE, KE, V>), dim3((unsigned)((units + ATTN_ROWS - 1) / ATTN_ROWS)), dim3(BLOCK), 0, c->stream, rows, nrow, (uint32_t)heads,
+                       (const int32_t *)c->sp.d_ids.get(), g, ldg, v, ldv, k, ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, entries, y, y_f64, ds, o32, ld32, o64, ld64, types);
 }
-template <bool BF16, int V>
+template <int ET, int V>
 void attn_cols_launch(fora_ctx *c, const PropGeom &g, const PropSeg *cols, uint64_t ncol, int heads, const void *values, bool val64, uint64_t entries,
                       const void *feat, int64_t ldf, int w, float *o32, int64_t ld32, double *o64, int64_t ld64) {
     const uint64_t units = ncol * (uint64_t)heads, per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
     const dim3 grid((unsigned)((units + per_wg - 1) / per_wg), g.tiles);
     const int32_t *rows = c->pt.d_rows.get();
     const int64_t *pos = c->pt.d_pos.get();
-    if (val64) hipLaunchKernelGGL((k_attn_cols<BF16, V, true>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
-    else hipLaunchKernelGGL((k_attn_cols<BF16, V, false>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+    if (val64) hipLaunchKernelGGL((k_attn_cols<ET, V, true>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
+    else hipLaunchKernelGGL((k_attn_cols<ET, V, false>), grid, dim3(BLOCK), 0, c->stream, cols, ncol, (uint32_t)heads, rows, pos, values, entries, feat, ldf, (uint32_t)w, g.G, o32, ld32, o64, ld64);
 }
 // +0.0 to an n x width output: one clear where the rows lie back to back, a clear per row band otherwise (a pitch wider than
 // the output: what lies between the rows is the caller's)
@@ -3065,19 +3087,19 @@ template <typename T> hipError_t attn_zero(fora_ctx *c, T *out, int64_t ld, uint
 // one gradient of the column side: out[v][h * w + c] = the sum over column v's entries p of values[h * entries + pos[p]] *
 // feat[rows[p]][h * w + c].  The outputs zeroed (the empty columns), the short columns of all heads in one launch, the longer
 // ones head by head through PROPAGATE's kernels over the cached plan.
-int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, bool val64, const void *feat, bool bf16, int64_t ldf, int w,
+int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, bool val64, const void *feat, int et, int64_t ldf, int w,
                   float *o32, int64_t ld32, double *o64, int64_t ld64) {
     const PropTBufs &t = c->pt;
     const AttnColPlan &cp = t.cols.plan;
     const uint64_t n = held_cols(c);
-    const uint32_t elt = bf16 ? 2 : 4;
-    const uint32_t *const widths = prop_widths(bf16);
+    const uint32_t elt = elt_bytes(et);
+    const uint32_t *const widths = prop_widths_bytes(elt);
     HIPCHK(c, attn_zero(c, o32, ld32, n, (uint64_t)heads * (uint64_t)w));
     HIPCHK(c, attn_zero(c, o64, ld64, n, (uint64_t)heads * (uint64_t)w));
     if (!cp.shrt.empty()) {
         const PropGeom g = attn_cols_geom(attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, widths, PROP_NWIDTHS), w);
-        with_vec(bf16, g.V, [&](auto B, auto V) {
-            attn_cols_launch<B.value, V.value>(c, g, t.cols.d_short.get(), cp.shrt.size(), heads, values, val64, entries, feat, ldf, w, o32, ld32, o64, ld64);
+        with_vec(et, g.V, [&](auto E, auto V) {
+            attn_cols_launch<E.value, V.value>(c, g, t.cols.d_short.get(), cp.shrt.size(), heads, values, val64, entries, feat, ldf, w, o32, ld32, o64, ld64);
         });
     }
     for (int h = 0; cp.long_cols && h < heads; h++) {
@@ -3085,7 +3107,7 @@ int attn_bwd_cols(fora_ctx *c, int heads, uint64_t entries, const void *values, 
         const void *vh = (const unsigned char *)values + (uint64_t)h * entries * (val64 ? 8 : 4);
         const PropSide sd{t.h_col_ptr.data(), (int)n, t.d_rows.get(), nullptr, nullptr, false, vh, val64, t.d_pos.get()};
         const PropGeom g = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, widths, PROP_NWIDTHS);
-        prop_launch_chunks(c, cp.lng, t.cols.d_lsegs.get(), t.cols.d_lrecs.get(), sd, bf16, g, fh, ldf, w, nullptr, o32 ? o32 + (uint64_t)h * w : nullptr, ld32,
+        prop_launch_chunks(c, cp.lng, t.cols.d_lsegs.get(), t.cols.d_lrecs.get(), sd, et, g, fh, ldf, w, nullptr, o32 ? o32 + (uint64_t)h * w : nullptr, ld32,
                            o64 ? o64 + (uint64_t)h * w : nullptr, ld64, false);
     }
     return FORA_OK;
@@ -3095,9 +3117,8 @@ int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *
                        const void *v_, int v_type, int64_t ldv, const void *g_, int g_type, int64_t ldg, const void *y_, int y_type,
                        int d, int dv, int heads, double scale, const fora_attn_grads &gr, fora_attn_bwd_stats *st) {
     const uint64_t entries = c->sp.entries, n = held_cols(c);
-    const bool q_bf16 = q_type == FORA_PROP_BF16, k_bf16 = k_type == FORA_PROP_BF16, v_bf16 = v_type == FORA_PROP_BF16, g_bf16 = g_type == FORA_PROP_BF16;
     const bool y_f64 = y_type == FORA_PROP_F64;
-    const uint32_t q_elt = q_bf16 ? 2 : 4, k_elt = k_bf16 ? 2 : 4, v_elt = v_bf16 ? 2 : 4, g_elt = g_bf16 ? 2 : 4, y_elt = y_f64 ? 8 : 4;
+    const uint32_t q_elt = elt_bytes(q_type), k_elt = elt_bytes(k_type), v_elt = elt_bytes(v_type), g_elt = elt_bytes(g_type), y_elt = y_f64 ? 8 : 4;
     const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q, k, dq and dk; of v, g and dv
     const bool want_dq = gr.dq32 || gr.dq64, want_dk = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64;
     const bool want_rows = want_dq || want_dk, want_cols = want_dk || want_dv; // dy and ds; the transposition
@@ -3179,34 +3200,32 @@ int attention_bwd_impl(fora_ctx *c, const int64_t *row_ptr, int nq, const void *
     }
     double *const ds = want_dk || lng_rows ? pb.d_attn_ds.get() : nullptr;
     const uint32_t lgv = prop_group_lg((uint32_t)dv); // (the dv columns of dy)
-    const uint32_t *const widths_k = prop_widths(k_bf16);
+    const uint32_t *const widths_k = prop_widths_bytes(k_elt);
     c->tm.attn_ms = 0;
     {
         EvSpan ev(c, EV_ATTN);
-        if (want_rows && !plan.shrt.empty()) with_bools(g_bf16, v_bf16, [&](auto GB, auto VB) { // dy, ds and dq of the short rows, all heads
-            constexpr bool gb = decltype(GB)::value, vb = decltype(VB)::value;
-            with_vec(k_bf16, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto KB, auto V) {
-                attn_bwd_launch<gb, vb, KB.value, V.value>(c, dsg + at_short, plan.shrt.size(), heads, g.ptr(), ldg, v.ptr(), ldv, k.ptr(), ldk, d, dv, lgv, scale, entries,
-                                                           y.ptr(), y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld());
+        if (want_rows && !plan.shrt.empty()) // dy, ds and dq of the short rows, all heads
+            with_fused_types(g_type, v_type, k_type, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto GE, auto VE, auto KE, auto V) {
+                attn_bwd_launch<GE.value, VE.value, KE.value, V.value>(c, dsg + at_short, plan.shrt.size(), heads, g.ptr(), ldg, v.ptr(), ldv, k.ptr(), ldk, d, dv, lgv, scale, entries,
+                                                                       y.ptr(), y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld(), sddmm_types(g_type, v_type));
             });
-        });
         for (int h = 0; lng_rows && h < heads; h++) { // the longer rows, one head at a time: dy, ds into the head's slice, dq
             const void *gh = attn_cols(g.ptr(), (uint64_t)h * dv, g_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt);
             const void *yh = (const unsigned char *)y.ptr() + (uint64_t)h * entries * y_elt;
             double *const dy64 = pb.d_attn_s.get(), *const dsh = ds + (uint64_t)h * entries;
             const PropSeg *segs = dsg + at_lsegs;
-            sddmm_launch_for(g_bf16, v_bf16, c, segs, plan.lng.segs.size(), gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
+            sddmm_launch_for(g_type, v_type, c, segs, plan.lng.segs.size(), gh, ldg, vh, ldv, dv, lgv, nullptr, dy64);
             const SoftmaxWork w{dsg + at_sm, dsg + at_sm + sm.n_short, sm.n_short, sm.n_long, pb.d_smax.get(), pb.d_smax.get() + sm.n_long, nullptr};
             if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, scale, nullptr, dsh);
             else softmax_bwd_launch<float, double>(c, w, yh, dy64, scale, nullptr, dsh);
             if (want_dq) {
                 const PropSide sd{row_ptr, nq, c->sp.d_ids.get(), nullptr, nullptr, false, dsh, true, nullptr};
                 const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, PROP_NWIDTHS);
-                prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, k_bf16, gm, kh, ldk, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
+                prop_launch_chunks(c, plan.lng, segs, pb.d_recs.get(), sd, k_type, gm, kh, ldk, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
             }
         }
-        if (want_dk) if (int rc = attn_bwd_cols(c, heads, entries, ds, true, q.ptr(), q_bf16, ldq, d, dk32.ptr(), dk32.ld(), dk64.ptr(), dk64.ld())) return rc;
-        if (want_dv) if (int rc = attn_bwd_cols(c, heads, entries, y.ptr(), y_f64, g.ptr(), g_bf16, ldg, dv, dv32.ptr(), dv32.ld(), dv64.ptr(), dv64.ld())) return rc;
+        if (want_dk) if (int rc = attn_bwd_cols(c, heads, entries, ds, true, q.ptr(), q_type, ldq, d, dk32.ptr(), dk32.ld(), dk64.ptr(), dk64.ld())) return rc;
+        if (want_dv) if (int rc = attn_bwd_cols(c, heads, entries, y.ptr(), y_f64, g.ptr(), g_type, ldg, dv, dv32.ptr(), dv32.ld(), dv64.ptr(), dv64.ld())) return rc;
     }
     if (int rc = held_fetch(c, dq32, dq64, dk32, dk64, dv32, dv64)) return rc;
     if (int rc = held_call_end(c, "sparse attention_bwd")) return rc;
@@ -3642,7 +3661,7 @@ static_assert(PROP_SEG == FORA_PROP_SEG, "fora_prop_plan.h and include/fora_hip.
 static int prop_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *feat, int feat_type, int d, int64_t ldf, int flags, bool with_values,
                       const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_prop_stats *ps) {
     if (int rc = held_call_begin(c, "sparse propagate", row_ptr, nq)) return rc;
-    if (feat_type != FORA_PROP_F32 && feat_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate: unknown feat_type");
+    if (!elt_known(feat_type)) return fail(c, FORA_E_ARG, "sparse propagate: unknown feat_type");
     if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate: unknown flag");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate: d outside 1 .. 65536");
     if (ldf < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate: a leading dimension smaller than d");
@@ -3672,7 +3691,7 @@ int fora_hip_sparse_propagate_vals(fora_ctx *c, const int64_t *row_ptr, int nq, 
 static int propt_entry(fora_ctx *c, const int64_t *row_ptr, int nq, const void *grad, int grad_type, int d, int64_t ldg, int flags, bool with_values,
                        const void *values, int val_type, float *out32, double *out64, int64_t ldo, fora_propt_stats *ps) {
     if (int rc = held_call_begin(c, "sparse propagate_t", row_ptr, nq)) return rc;
-    if (grad_type != FORA_PROP_F32 && grad_type != FORA_PROP_BF16) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown grad_type");
+    if (!elt_known(grad_type)) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown grad_type");
     if (flags & ~FORA_PROP_NORMALIZE) return fail(c, FORA_E_ARG, "sparse propagate_t: unknown flag");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse propagate_t: d outside 1 .. 65536");
     if (ldg < d || ldo < d) return fail(c, FORA_E_ARG, "sparse propagate_t: a leading dimension smaller than d");
@@ -3701,7 +3720,7 @@ int fora_hip_sparse_propagate_t_vals(fora_ctx *c, const int64_t *row_ptr, int nq
 int fora_hip_sparse_sddmm(fora_ctx *c, const int64_t *row_ptr, int nq, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d,
                           float *out32, double *out64, uint64_t cap, fora_sddmm_stats *st) {
     if (int rc = held_call_begin(c, "sparse sddmm", row_ptr, nq)) return rc;
-    if ((a_type != FORA_PROP_F32 && a_type != FORA_PROP_BF16) || (b_type != FORA_PROP_F32 && b_type != FORA_PROP_BF16))
+    if (!elt_known(a_type) || !elt_known(b_type))
         return fail(c, FORA_E_ARG, "sparse sddmm: unknown a_type or b_type");
     if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, "sparse sddmm: d outside 1 .. 65536");
     if (lda < d || ldb < d) return fail(c, FORA_E_ARG, "sparse sddmm: a leading dimension smaller than d");
@@ -3732,8 +3751,7 @@ int fora_hip_sparse_attention(fora_ctx *c, const int64_t *row_ptr, int nq, const
                               const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double scale, float *out32, double *out64, int64_t ldo,
                               float *y32, double *y64, uint64_t ycap, fora_attn_stats *st) {
     if (int rc = held_call_begin(c, "sparse attention", row_ptr, nq)) return rc;
-    const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
-    if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type)) return fail(c, FORA_E_ARG, "sparse attention: unknown q_type, k_type or v_type");
+    if (!elt_known(q_type) || !elt_known(k_type) || !elt_known(v_type)) return fail(c, FORA_E_ARG, "sparse attention: unknown q_type, k_type or v_type");
     if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: d or dv outside 1 .. 65536");
     if (heads < 1 || (int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, "sparse attention: heads < 1, or heads * d or heads * dv over 65536");
     if (ldq < (int64_t)heads * d || ldk < (int64_t)heads * d) return fail(c, FORA_E_ARG, "sparse attention: ldq or ldk smaller than heads * d");
@@ -3756,9 +3774,8 @@ int fora_hip_sparse_attention_bwd(fora_ctx *c, const int64_t *row_ptr, int nq, c
                                   const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap,
                                   int d, int dv, int heads, double scale, const fora_attn_grads *grads, fora_attn_bwd_stats *st) {
     if (int rc = held_call_begin(c, "sparse attention_bwd", row_ptr, nq)) return rc;
-    const auto type_ok = [](int t) { return t == FORA_PROP_F32 || t == FORA_PROP_BF16; };
     const char *who = "sparse attention_bwd: ";
-    if (!type_ok(q_type) || !type_ok(k_type) || !type_ok(v_type) || !type_ok(g_type)) return fail(c, FORA_E_ARG, std::string(who) + "unknown q_type, k_type, v_type or g_type");
+    if (!elt_known(q_type) || !elt_known(k_type) || !elt_known(v_type) || !elt_known(g_type)) return fail(c, FORA_E_ARG, std::string(who) + "unknown q_type, k_type, v_type or g_type");
     if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, std::string(who) + "y_type is neither f32 nor f64");
     if (d < 1 || d > 65536 || dv < 1 || dv > 65536) return fail(c, FORA_E_ARG, std::string(who) + "d or dv outside 1 .. 65536");
     if (heads < 1 || (int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, std::string(who) + "heads < 1, or heads * d or heads * dv over 65536");

@@ -13,53 +13,69 @@
 // is no explicit fma.  The kernels take pointers and sizes, not Dev; BLOCK and fix2d come from fora_kernels.h.
 #pragma once
 #include "fora_kernels.h" // BLOCK, fix2d
+#include "fora_narrow.h" // the element types, narrow_widen
 #include "fora_prop_plan.h"
 
 namespace fora {
 
 constexpr int PROP_INFLIGHT = 4; // feature rows a lane group has in flight
 
-// V adjacent columns of one feature row as they lie in memory: f32 one word per column, bf16 two columns per word (one
-// column in the low half when V == 1).  Loading and widening are apart on purpose: the kernel issues the loads of
-// PROP_INFLIGHT rows first and widens to f64 only where it adds, so that no load waits for the one before it.
-template <bool BF16, int V> struct PropRaw {
-    static constexpr int W = BF16 ? (V > 1 ? V / 2 : 1) : V;
+// V adjacent columns of one feature row as they lie in memory: f32 one word per column, bf16 and f16 two columns per word,
+// FP8 four (one column in the low end of the word when V == 1).  Loading and widening are apart on purpose: the kernel
+// issues the loads of PROP_INFLIGHT rows first and widens to f64 only where it adds, so that no load waits for the one
+// before it.  ET: the element type (fora_narrow.h), known where the kernel is compiled, since the layout hangs on it.
+template <int ET, int V> struct PropRaw {
+    static constexpr int PER = 4 / (int)elt_bytes(ET); // columns to a word
+    static constexpr int W = V > PER ? V / PER : 1;
     uint32_t w[W];
 };
 // all V columns exist: one load of V elements -- the host chose V so that it is aligned (prop_geom)
-template <bool BF16, int V>
-__device__ __forceinline__ void prop_load_full(const void *feat, uint64_t off, PropRaw<BF16, V> &r) {
-    if constexpr (!BF16) {
+template <int ET, int V>
+__device__ __forceinline__ void prop_load_full(const void *feat, uint64_t off, PropRaw<ET, V> &r) {
+    if constexpr (elt_bytes(ET) == 4) {
         const float *p = (const float *)feat + off;
         if constexpr (V == 4) { const uint4 x = *(const uint4 *)p; r.w[0] = x.x; r.w[1] = x.y; r.w[2] = x.z; r.w[3] = x.w; }
         else if constexpr (V == 2) { const uint2 x = *(const uint2 *)p; r.w[0] = x.x; r.w[1] = x.y; }
         else r.w[0] = __float_as_uint(p[0]);
-    } else {
+    } else if constexpr (elt_bytes(ET) == 2) {
         const uint16_t *p = (const uint16_t *)feat + off;
         if constexpr (V == 8) { const uint4 x = *(const uint4 *)p; r.w[0] = x.x; r.w[1] = x.y; r.w[2] = x.z; r.w[3] = x.w; }
         else if constexpr (V == 4) { const uint2 x = *(const uint2 *)p; r.w[0] = x.x; r.w[1] = x.y; }
         else r.w[0] = p[0];
+    } else {
+        const uint8_t *p = (const uint8_t *)feat + off;
+        if constexpr (V == 16) { const uint4 x = *(const uint4 *)p; r.w[0] = x.x; r.w[1] = x.y; r.w[2] = x.z; r.w[3] = x.w; }
+        else if constexpr (V == 4) r.w[0] = *(const uint32_t *)p;
+        else r.w[0] = p[0];
     }
 }
 // a tile's last lane: ncol < V columns exist, read one by one; the others stay 0 and are never stored
-template <bool BF16, int V>
-__device__ __forceinline__ void prop_load_tail(const void *feat, uint64_t off, uint32_t ncol, PropRaw<BF16, V> &r) {
-    if constexpr (!BF16) {
+template <int ET, int V>
+__device__ __forceinline__ void prop_load_tail(const void *feat, uint64_t off, uint32_t ncol, PropRaw<ET, V> &r) {
+    if constexpr (elt_bytes(ET) == 4) {
         const float *p = (const float *)feat + off;
 #pragma unroll
         for (int v = 0; v < V; v++) if ((uint32_t)v < ncol) r.w[v] = __float_as_uint(p[v]);
-    } else {
+    } else if constexpr (elt_bytes(ET) == 2) {
         const uint16_t *p = (const uint16_t *)feat + off;
 #pragma unroll
         for (int v = 0; v < V; v++) if ((uint32_t)v < ncol) r.w[v / 2] |= (uint32_t)p[v] << (16 * (v & 1));
+    } else {
+        const uint8_t *p = (const uint8_t *)feat + off;
+#pragma unroll
+        for (int v = 0; v < V; v++) if ((uint32_t)v < ncol) r.w[v / 4] |= (uint32_t)p[v] << (8 * (v & 3));
     }
 }
-// column v as a double: f32 widened, bf16 bits << 16 as f32 widened -- both exact
-template <bool BF16, int V>
-__device__ __forceinline__ double prop_widen(const PropRaw<BF16, V> &r, int v) {
-    if constexpr (!BF16) return (double)__uint_as_float(r.w[v]);
-    else if constexpr (V == 1) return (double)__uint_as_float(r.w[0] << 16);
-    else return (double)__uint_as_float((v & 1) ? (r.w[v / 2] & 0xFFFF0000u) : (r.w[v / 2] << 16));
+// column v as a double: f32 widened, bf16 bits << 16 as f32 widened, a narrow type's code widened as fora_narrow.h says --
+// all exact
+template <int ET, int V>
+__device__ __forceinline__ double prop_widen(const PropRaw<ET, V> &r, int v) {
+    if constexpr (ET == ELT_F32) return (double)__uint_as_float(r.w[v]);
+    else if constexpr (ET == ELT_BF16) {
+        if constexpr (V == 1) return (double)__uint_as_float(r.w[0] << 16);
+        else return (double)__uint_as_float((v & 1) ? (r.w[v / 2] & 0xFFFF0000u) : (r.w[v / 2] << 16));
+    } else if constexpr (ET == ELT_F16) return (double)narrow_widen<ET>((r.w[v / 2] >> (16 * (v & 1))) & 0xFFFFu);
+    else return (double)narrow_widen_byte<ET>(r.w[v / 4], v & 3);
 }
 
 // grid = (ceil(nseg / (segments per workgroup)), column tiles), BLOCK threads.  A wave holds 64 / G lane groups; group g of
@@ -77,7 +93,7 @@ __device__ __forceinline__ double prop_widen(const PropRaw<BF16, V> &r, int v) {
 // list (the forward product); PROP_W_POS: values[pos[p]], pos the held place of transposed entry p.  VAL64: values are f64,
 // else f32 widened exactly.  With values no word is read and no word sum is made.
 enum : int { PROP_W_FIX = 0, PROP_W_VALUES = 1, PROP_W_POS = 2 };
-template <bool BF16, int V, bool TNORM, int WSRC = PROP_W_FIX, bool VAL64 = false>
+template <int ET, int V, bool TNORM, int WSRC = PROP_W_FIX, bool VAL64 = false>
 __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
                                                  int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum, const uint64_t *rsum,
                                                  const void *values = nullptr, const int64_t *pos = nullptr) {
@@ -114,7 +130,7 @@ __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t n
         }
         const uint32_t cnt = min(G, len - base);
         for (uint32_t k = 0; k < cnt; k += PROP_INFLIGHT) {
-            PropRaw<BF16, V> raw[PROP_INFLIGHT];
+            PropRaw<ET, V> raw[PROP_INFLIGHT];
             uint64_t off[PROP_INFLIGHT];
             double w[PROP_INFLIGHT];
 #pragma unroll
@@ -123,23 +139,23 @@ __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t n
                 off[u] = (uint64_t)(uint32_t)__shfl(id_l, from, (int)G) * (uint64_t)ldf + c0;
                 w[u] = __shfl(w_l, from, (int)G);
 #pragma unroll
-                for (int j = 0; j < PropRaw<BF16, V>::W; j++) raw[u].w[j] = 0;
+                for (int j = 0; j < PropRaw<ET, V>::W; j++) raw[u].w[j] = 0;
             }
             if (ncol == (uint32_t)V) { // the full-lane / tail-lane choice stands outside the loop over the rows: the loads follow each other
 #pragma unroll
                 for (int u = 0; u < PROP_INFLIGHT; u++)
-                    if (k + (uint32_t)u < cnt) prop_load_full<BF16, V>(feat, off[u], raw[u]);
+                    if (k + (uint32_t)u < cnt) prop_load_full<ET, V>(feat, off[u], raw[u]);
             } else if (ncol) {
 #pragma unroll
                 for (int u = 0; u < PROP_INFLIGHT; u++)
-                    if (k + (uint32_t)u < cnt) prop_load_tail<BF16, V>(feat, off[u], ncol, raw[u]);
+                    if (k + (uint32_t)u < cnt) prop_load_tail<ET, V>(feat, off[u], ncol, raw[u]);
             }
 #pragma unroll
             for (int u = 0; u < PROP_INFLIGHT; u++) {
                 const bool valid = k + (uint32_t)u < cnt;
 #pragma unroll
                 for (int v = 0; v < V; v++) {
-                    const double term = w[u] * prop_widen<BF16, V>(raw[u], v);
+                    const double term = w[u] * prop_widen<ET, V>(raw[u], v);
                     const double sum = acc[v] + term;
                     acc[v] = valid ? sum : acc[v];
                 }
@@ -154,24 +170,24 @@ __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t n
             if ((uint32_t)v < ncol) part[(uint64_t)slot * d + c0 + (uint32_t)v] = acc[v];
     }
 }
-template <bool BF16, int V>
+template <int ET, int V>
 __global__ void __launch_bounds__(BLOCK) k_prop_gather(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
                                                        int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum) {
-    prop_gather_body<BF16, V, false>(segs, nseg, ids, fix, feat, ldf, d, G, part, segsum, nullptr);
+    prop_gather_body<ET, V, false>(segs, nseg, ids, fix, feat, ldf, d, G, part, segsum, nullptr);
 }
 // the same over the transposition (ids: the rows of a column's entries, feat: the gradient), every weight divided by its row's
 // word sum
-template <bool BF16, int V>
+template <int ET, int V>
 __global__ void __launch_bounds__(BLOCK) k_prop_gather_t(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
                                                          int64_t ldf, uint32_t d, uint32_t G, double *part, const uint64_t *rsum) {
-    prop_gather_body<BF16, V, true>(segs, nseg, ids, fix, feat, ldf, d, G, part, nullptr, rsum);
+    prop_gather_body<ET, V, true>(segs, nseg, ids, fix, feat, ldf, d, G, part, nullptr, rsum);
 }
 
 // PROPAGATE WITH VALUES: the same body with the caller's values as weights -- forward (pos null) and transposed
-template <bool BF16, int V, bool POS, bool VAL64>
+template <int ET, int V, bool POS, bool VAL64>
 __global__ void __launch_bounds__(BLOCK) k_prop_gather_vals(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const void *values, const int64_t *pos,
                                                             const void *feat, int64_t ldf, uint32_t d, uint32_t G, double *part) {
-    prop_gather_body<BF16, V, false, POS ? PROP_W_POS : PROP_W_VALUES, VAL64>(segs, nseg, ids, nullptr, feat, ldf, d, G, part, nullptr, nullptr, values, pos);
+    prop_gather_body<ET, V, false, POS ? PROP_W_POS : PROP_W_VALUES, VAL64>(segs, nseg, ids, nullptr, feat, ldf, d, G, part, nullptr, nullptr, values, pos);
 }
 
 // One lane per (row record, column) of a chunk.  grid = (column blocks, record groups): with d >= BLOCK a workgroup takes

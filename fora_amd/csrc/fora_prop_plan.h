@@ -120,6 +120,12 @@ inline const uint32_t *prop_widths(bool bf16) {
     static const uint32_t f32[PROP_NWIDTHS] = {4, 2, 1}, b16[PROP_NWIDTHS] = {8, 4, 1};
     return bf16 ? b16 : f32;
 }
+// the same by element size: the two tables above for 4 and 2 bytes (f16 lies as bf16 does), and for the one-byte types
+// (FP8) 16 columns -- four words, the widest load -- then one word, then one byte
+inline const uint32_t *prop_widths_bytes(uint32_t elt_bytes) {
+    static const uint32_t b8[PROP_NWIDTHS] = {16, 4, 1};
+    return elt_bytes == 1 ? b8 : prop_widths(elt_bytes == 2);
+}
 // the group exponent: the smallest lg <= 6 with 2^lg >= d -- the lanes that share a d-column dot product, at most a wave
 inline uint32_t prop_group_lg(uint32_t d) {
     uint32_t lg = 0;

@@ -12,6 +12,7 @@
 // Nothing is fused: the file is compiled with -ffp-contract=off and the kernel says so again itself.
 #pragma once
 #include "fora_kernels.h" // BLOCK
+#include "fora_narrow.h" // the element types, narrow_widen
 #include "fora_prop_plan.h"
 
 namespace fora {
@@ -21,10 +22,26 @@ constexpr uint32_t SDDMM_UNITS = PROP_SEG / SDDMM_SUB; // waves per segment
 constexpr int SDDMM_INFLIGHT = 4;      // entries a lane group has in flight
 static_assert(SDDMM_INFLIGHT == 4, "k_prop_sddmm merges the trees of exactly four entries");
 
-template <bool BF16> __device__ __forceinline__ uint32_t sddmm_load(const void *m, uint64_t at) {
-    if constexpr (BF16) return (uint32_t)((const uint16_t *)m)[at] << 16;
-    else return __float_as_uint(((const float *)m)[at]);
+// One element as the bits of its f32 widening.  ET: the element type where the kernel was compiled for it -- f32 and bf16, the
+// two that the instantiations of old take -- or ELT_ANY: the type is rt, the same for the whole wave, and the load switches on
+// it (one element per lane: nothing about the lanes' layout hangs on the type, and a class of its own for every pair of
+// five types would be 25 kernels where there are 5).
+template <int ET> __device__ __forceinline__ uint32_t sddmm_load(const void *m, uint64_t at, int rt) {
+    static_assert(ET == ELT_F32 || ET == ELT_BF16 || ET == ELT_ANY, "a compiled-in type is f32 or bf16");
+    if constexpr (ET == ELT_BF16) return (uint32_t)((const uint16_t *)m)[at] << 16;
+    else if constexpr (ET == ELT_F32) return __float_as_uint(((const float *)m)[at]);
+    else {
+        switch (rt) {
+        case ELT_F32: return __float_as_uint(((const float *)m)[at]);
+        case ELT_BF16: return (uint32_t)((const uint16_t *)m)[at] << 16;
+        case ELT_F16: return __float_as_uint(narrow_widen<ELT_F16>(((const uint16_t *)m)[at]));
+        case ELT_E4M3: return __float_as_uint(narrow_widen<ELT_E4M3>(((const uint8_t *)m)[at]));
+        default: return __float_as_uint(narrow_widen<ELT_E5M2>(((const uint8_t *)m)[at]));
+        }
+    }
 }
+// the run-time types of a and b in one kernel argument (read only by the ELT_ANY instantiations)
+constexpr uint32_t sddmm_types(int a_type, int b_type) { return (uint32_t)a_type | (uint32_t)b_type << 8; }
 
 // The scores of `cnt` entries with the ids ids[0 .. cnt) against one row of a (arow: its first element), by one whole wave;
 // lg = log2(G).  Group g of the wave's 64 / G groups takes the entries g, g + 64 / G, ..., SDDMM_INFLIGHT of them per round.
@@ -32,10 +49,12 @@ template <bool BF16> __device__ __forceinline__ uint32_t sddmm_load(const void *
 // and is never handed on.  bcol: the first column of b that counts (a column slice: a head), added to every row's place.
 // sink(k, s): called once per entry k < cnt, on the lane that ends up with its score s -- the one thing in which the callers
 // differ (k_prop_sddmm stores it, k_attn_short of fora_attn.h keeps it in LDS).
-template <bool A_BF16, bool B_BF16, typename Sink>
+// A_ET, B_ET: the element types of a and b as sddmm_load takes them; types: sddmm_types() of the two, for ELT_ANY.
+template <int A_ET, int B_ET, typename Sink>
 __device__ __forceinline__ void sddmm_scores(const int32_t *ids, uint32_t cnt, const void *a, uint64_t arow, const void *b, int64_t ldb, uint64_t bcol,
-                                             uint32_t d, uint32_t lg, uint32_t lane, Sink &&sink) {
+                                             uint32_t d, uint32_t lg, uint32_t lane, uint32_t types, Sink &&sink) {
 #pragma clang fp contract(off)
+    const int a_rt = (int)(types & 0xFFu), b_rt = (int)(types >> 8);
     const uint32_t G = 1u << lg;
     const uint32_t gl = lane & (G - 1u), grp = lane >> lg, ngrp = 64u >> lg;
     for (uint32_t j0 = 0; j0 < cnt; j0 += ngrp * SDDMM_INFLIGHT) {
@@ -50,10 +69,10 @@ __device__ __forceinline__ void sddmm_scores(const int32_t *ids, uint32_t cnt, c
             q[u] = 0.0;
         }
         for (uint32_t c = gl; c < d; c += 64u) {
-            const double av = (double)__uint_as_float(sddmm_load<A_BF16>(a, arow + c));
+            const double av = (double)__uint_as_float(sddmm_load<A_ET>(a, arow + c, a_rt));
             uint32_t raw[SDDMM_INFLIGHT];
 #pragma unroll
-            for (int u = 0; u < SDDMM_INFLIGHT; u++) raw[u] = valid[u] ? sddmm_load<B_BF16>(b, brow[u] + c) : 0u;
+            for (int u = 0; u < SDDMM_INFLIGHT; u++) raw[u] = valid[u] ? sddmm_load<B_ET>(b, brow[u] + c, b_rt) : 0u;
 #pragma unroll
             for (int u = 0; u < SDDMM_INFLIGHT; u++) {
                 const double t = av * (double)__uint_as_float(raw[u]);
@@ -96,9 +115,9 @@ __device__ __forceinline__ void sddmm_scores(const int32_t *ids, uint32_t cnt, c
 
 // grid = ceil(nseg * SDDMM_UNITS / (BLOCK / 64)) workgroups of BLOCK threads; lg = log2(G).  Wave u of the grid owns the
 // entries [sub * SDDMM_SUB, ...) of segment u / SDDMM_UNITS, sub = u % SDDMM_UNITS, and scores them with sddmm_scores.
-template <bool A_BF16, bool B_BF16>
+template <int A_ET, int B_ET>
 __global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const void *a, int64_t lda, const void *b,
-                                                      int64_t ldb, uint32_t d, uint32_t lg, float *out32, double *out64) {
+                                                      int64_t ldb, uint32_t d, uint32_t lg, float *out32, double *out64, uint32_t types) {
 #pragma clang fp contract(off)
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t unit = (uint64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
@@ -110,7 +129,7 @@ __global__ void __launch_bounds__(BLOCK) k_prop_sddmm(const PropSeg *segs, uint6
     const uint32_t cnt = min(SDDMM_SUB, sg.len - lo);
     const int64_t e0 = sg.first + lo;
     const uint64_t arow = (uint64_t)(uint32_t)sg.row * (uint64_t)lda;
-    sddmm_scores<A_BF16, B_BF16>(ids + e0, cnt, a, arow, b, ldb, 0ull, d, lg, lane, [=](uint32_t k, double sc) {
+    sddmm_scores<A_ET, B_ET>(ids + e0, cnt, a, arow, b, ldb, 0ull, d, lg, lane, types, [=](uint32_t k, double sc) {
         if (out64) out64[e0 + k] = sc;
         if (out32) out32[e0 + k] = (float)sc;
     });

@@ -25,10 +25,7 @@ class _PprPropagate(torch.autograd.Function):
         if engine.get_option("sparse_generation") != ctx.generation:
             raise RuntimeError("ppr_propagate: the engine's held sparse result was replaced or cleared after the forward pass; "
                                "the backward pass needs the rows the forward pass used")
-        if G.dtype not in (torch.float32, torch.bfloat16):
-            G = G.to(torch.float32)
-        if G.dim() != 2 or (G.shape[1] > 1 and G.stride(1) != 1) or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
-            G = G.contiguous()  # (an expanded or transposed gradient; a row-strided one is read in place)
+        G = _dense_operand(G)  # (an expanded or transposed gradient is copied; a row-strided one is read in place)
         out32, _, _ = engine.sparse_propagate_t(ctx.row_ptr, G, normalize=ctx.normalize, want32=True, want64=False)
         return (out32 if ctx.dtype == torch.float32 else out32.to(ctx.dtype)), None, None, None
 
@@ -39,13 +36,25 @@ def _held_guard(ctx_gen, engine, who):
                            "the backward pass needs the rows the forward pass used")
 
 
+_FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+
+
 def _dense_operand(X):
-    """a gradient as the library reads it: float32 or bfloat16, [rows, d], column stride one element"""
-    if X.dtype not in (torch.float32, torch.bfloat16):
+    """a gradient as the library reads it: float32, bfloat16 or float16, [rows, d], column stride one element"""
+    if X.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         X = X.to(torch.float32)
     if X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1) or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
         X = X.contiguous()
     return X
+
+
+def _refuse_fp8_grad(who, **operands):
+    """an FP8 tensor is a constant operand (the library reads it as it lies): one that asks for a gradient is refused before
+    anything runs -- the gradient would have to be rounded to 8 bits, which is the caller's decision and scaling"""
+    for name, X in operands.items():
+        if torch.is_tensor(X) and X.dtype in _FP8 and X.requires_grad:
+            raise ValueError(f"{who}: {name} is an FP8 tensor that requires grad; an FP8 operand is a constant -- keep the "
+                             "parameter in a wider dtype and pass its FP8 copy detached")
 
 
 def _entry_values(g):
@@ -111,14 +120,15 @@ class _PprSddmm(torch.autograd.Function):
 
 def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
     """Z = (held sparse rows of `engine`) x H as a differentiable torch operation.  row_ptr: as query_sparse /
-    query_seeds_sparse returned it (a numpy array or a tensor).  H: [n, d] (n = engine.held_cols) float32 or bfloat16 on the
-    engine's GPU, column stride one element.  Returns Z [nq, d] float32 on the device; Z.backward(G) leaves H.grad = (held rows)^T x G in H's
+    query_seeds_sparse returned it (a numpy array or a tensor).  H: [n, d] (n = engine.held_cols) float32, bfloat16 or float16 on the
+    engine's GPU (or FP8 -- float8_e4m3fn, float8_e5m2 -- as a constant: one that requires grad is a ValueError), column stride one element.  Returns Z [nq, d] float32 on the device; Z.backward(G) leaves H.grad = (held rows)^T x G in H's
     dtype.  The rows must still be held when the backward pass runs: a query_sparse, query_seeds_sparse, store_take,
     sparse_compact, sparse_clear or set_graph in between makes it raise.
     values: a float32 or float64 tensor of `entries` elements on the device, one per held entry in held order, used as the
     weights in place of the PPR values (Engine.sparse_propagate(values=)); the result is then differentiable in both H and
     values -- H.grad by the transposed product with the same values, values.grad = ppr_sddmm(G, H).  Not together with
     normalize.  values=None is the code path this function always had."""
+    _refuse_fp8_grad("ppr_propagate", H=H)
     if values is None:
         return _PprPropagate.apply(H, engine, row_ptr, bool(normalize))
     if normalize:
@@ -128,9 +138,10 @@ def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
 
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
-    the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32 or bfloat16 tensors on the engine's GPU with a column
+    the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32, bfloat16 or float16 tensors (or constant FP8 ones) on the engine's GPU with a column
     stride of one element: A.grad = P(g) x B and B.grad = P(g)^T x A, the two products with the scores' gradient g as values.
     The rows must still be held when the backward pass runs."""
+    _refuse_fp8_grad("ppr_sddmm", A=A, B=B)
     return _PprSddmm.apply(A, B, engine, row_ptr)
 
 
@@ -246,7 +257,7 @@ def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1, backward=
     """ppr_attention with all three steps in ONE library call (Engine.sparse_attention, the ATTENTION contract): the rows of at
     most 256 entries are scored, normalised and multiplied by one wave each without anything written in between, and nothing
     is rounded to float32 between the steps.  Q: [nq, heads * d], K: [n, heads * d], V: [n, heads * dv] (n =
-    engine.held_cols: over a compacted result K and V are the rows `cols` of the full matrices), float32 or bfloat16 on the
+    engine.held_cols: over a compacted result K and V are the rows `cols` of the full matrices), float32, bfloat16 or float16 (or constant FP8 tensors) on the
     engine's GPU; head j attends with the columns [j * d, (j + 1) * d) of Q and K and writes the columns
     [j * dv, (j + 1) * dv) of the result, [nq, heads * dv] float32.  scale defaults to d ** -0.5 and is a number, not a
     differentiable operand.  Differentiable in Q, K and V: the backward pass runs head by head with the calls ppr_attention
@@ -259,6 +270,7 @@ def ppr_attention_fused(engine, row_ptr, Q, K, V, scale=None, heads=1, backward=
         raise ValueError("ppr_attention_fused: heads must be at least 1 and divide the columns of Q and of V")
     if backward not in ("calls", "fused"):
         raise ValueError('ppr_attention_fused: backward is "calls" or "fused"')
+    _refuse_fp8_grad("ppr_attention_fused", Q=Q, K=K, V=V)
     if scale is None:
         scale = float(Q.shape[1] // heads) ** -0.5
     fn = _PprAttentionFused if backward == "calls" else _PprAttentionFusedBwd

@@ -488,6 +488,23 @@
  *     and give the bits they always gave, before and after a call with values.
  *   - with values equal to the f64 vals of fora_hip_sparse_fetch both calls give the bits of the plain calls without
  *     FORA_PROP_NORMALIZE.
+ * NARROW OPERANDS (FORA_PROP_F16, FORA_PROP_E4M3, FORA_PROP_E5M2): three more element types for the dense operands, legal in
+ * every argument where FORA_PROP_BF16 is -- feat_type and grad_type of PROPAGATE, of PROPAGATE, TRANSPOSED and of their forms
+ * WITH VALUES; a_type and b_type of SCORES (SDDMM); q_type, k_type and v_type of ATTENTION and of ATTENTION, BACKWARD, and its
+ * g_type -- each chosen independently of the others.  They stay FORA_E_ARG wherever FORA_PROP_BF16 is: as val_type, as the
+ * score, y or grad type of ROW SOFTMAX, as y_type.  The value 3 is no type and FORA_E_ARG everywhere.
+ *   - FORA_PROP_F16 is IEEE binary16 with s, e (5 bits), m (10 bits): e = 0 is (-1)^s * m * 2^-24; 1 <= e <= 30 is
+ *     (-1)^s * (1024 + m) * 2^(e - 25); e = 31 with m = 0 is +-inf, with m != 0 NaN.
+ *   - FORA_PROP_E5M2 is the binary16 whose bits are byte << 8 (torch.float8_e5m2).
+ *   - FORA_PROP_E4M3 is the OCP "fn" form (torch.float8_e4m3fn) with s, e (4 bits), m (3 bits): e = 0 is (-1)^s * m * 2^-9,
+ *     otherwise (-1)^s * (8 + m) * 2^(e - 10); 0x7F and 0xFF are NaN, there are no infinities, the largest value is 448.
+ *   - every value is exactly an f32; -0 stays -0; a NaN code widens to some quiet NaN, and no payload is defined.
+ *   - with an operand of a narrow type every call gives, bit for bit and in every output (out32, out64, y32, y64, dq, dk, dv),
+ *     what it gives with that operand widened to FORA_PROP_F32 by this rule; where a NaN is involved, NaN-ness is what agrees.
+ *     "t_c is exact" of SCORES (SDDMM) keeps holding: the significands only get shorter.
+ *   - an operand needs only element alignment -- any byte offset for FP8, any pitch, a column slice of a wider tensor; a host
+ *     operand is uploaded by its element size; feat_bytes (fora_prop_stats, fora_propt_stats) and bytes (fora_sddmm_stats)
+ *     count 1 or 2 bytes per element.  No option and no launch shape changes a bit.
  * ROW STORE (fora_hip_store_put, fora_hip_store_load, fora_hip_store_take, fora_hip_store_info, fora_hip_store_clear): a library
  * of sparse rows kept on the device, any list of which becomes the held sparse result with one copy on the GPU and no query --
  * the rows of the training nodes are computed once and every mini-batch takes its own.
@@ -761,6 +778,7 @@ int fora_hip_sparse_clear(fora_ctx *ctx);
  * order of operations.  feat: n x d elements of feat_type, row-major with pitch ldf; out32 / out64: nq x d with pitch ldo. */
 #define FORA_PROP_SEG 256
 enum { FORA_PROP_F32 = 0, FORA_PROP_BF16 = 1 };
+enum { FORA_PROP_F16 = 4, FORA_PROP_E4M3 = 5, FORA_PROP_E5M2 = 6 }; /* NARROW OPERANDS above: legal where FORA_PROP_BF16 is; 3 is no type */
 enum { FORA_PROP_NORMALIZE = 1 };
 typedef struct { uint64_t entries, segments, max_row, feat_bytes; /* entries * d * element size */
                  int32_t chunks, feat_on_device; double gather_ms, combine_ms; } fora_prop_stats;
