@@ -5,7 +5,9 @@ The C ABI is stated once here: the struct mirrors, and _ABI, one row per functio
 argtypes) on whatever the library exports -- so a call passes plain Python values and ctypes converts, or refuses,
 each of them.  A new entry point takes three steps: its prototype in include/fora_hip.h, its row in _ABI (a struct of
 its own: a mirror in STRUCTS), one Engine method.  tests/test_capi_cpu.py derives every row and every mirror from the
-header again and fails until they match."""
+header again and fails until they match.  Entry points declared in the extension header include/fora_hip_ext.h have
+their rows in a second table, _ABI_EXT, of the same syntax, bound by the same load() (tests/test_subgraph_cpu.py holds
+it to that header); they report statistics through out-pointers and add no struct."""
 import ctypes as C
 import os
 
@@ -223,6 +225,15 @@ ABI = _rows(_ABI)
 SYMBOLS = [name for name, row in ABI.items() if not row[0]]
 TEST_SYMBOLS = [name for name, row in ABI.items() if row[0]]  # TEST_LIB only
 
+# the entry points of include/fora_hip_ext.h, the extension header: the same rows, a table of their own (the census of
+# include/fora_hip.h is pinned); tests/test_subgraph_cpu.py derives them from that header again
+_ABI_EXT = """
+int  fora_hip_sparse_subgraph(ctx*, ptr, int, ptr, ptr, ptr)
+int  fora_hip_sparse_subgraph_fetch(ctx*, ptr, ptr, ptr, uint64)
+"""
+ABI_EXT = _rows(_ABI_EXT)
+EXT_SYMBOLS = list(ABI_EXT)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -237,6 +248,17 @@ def to_torch_csr(row_ptr, ids, vals, n):
     return torch.sparse_csr_tensor(row_ptr, ids.to(torch.int64), vals, size=(row_ptr.numel() - 1, int(n)))
 
 
+def subgraph_edge_index(sub_ptr, sub_col):
+    """The [2, edges] COO pair (source, target; int64, local ids) of a CSR of Engine.sparse_subgraph: numpy arrays give a
+    numpy array, torch tensors a tensor on their device."""
+    if type(sub_ptr).__module__.split(".")[0] == "torch":
+        import torch
+        rows = torch.arange(sub_ptr.numel() - 1, dtype=torch.int64, device=sub_ptr.device)
+        return torch.stack([torch.repeat_interleave(rows, sub_ptr[1:] - sub_ptr[:-1]), sub_col.to(torch.int64)])
+    sub_ptr = np.asarray(sub_ptr, dtype=np.int64)
+    return np.stack([np.repeat(np.arange(sub_ptr.size - 1, dtype=np.int64), np.diff(sub_ptr)), np.asarray(sub_col, dtype=np.int64)])
+
+
 def lib_path():
     # FORA_HIP_LIB: experiment tooling only (tools/pushbench.py times several builds of the library)
     return os.environ.get("FORA_HIP_LIB") or os.path.join(_HERE, "libfora_hip.so")
@@ -249,7 +271,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in ABI.items():
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -549,6 +571,35 @@ class Engine:
         row_ptr, _ = self.store_take(rows)
         cols, st = self.sparse_compact(row_ptr, device=device)
         return row_ptr, cols, st
+
+    # ---- the induced subgraph of the compacted held result (the SUBGRAPH contract of include/fora_hip_ext.h)
+    def sparse_subgraph(self, row_ptr, want_eid=False, device=False):
+        """The subgraph the graph induces on cols, the columns of the compacted held result (fora_hip_sparse_subgraph): a CSR
+        over len(cols) rows in local ids -- row j holds the out-edges of node cols[j] whose target is in cols, in the graph's
+        own order, multi-edges and self-loops as they stand.  row_ptr: as the sparse call or store_take returned it (the
+        result must have been compacted: sparse_compact, store_take_compact).  Returns (sub_ptr, sub_col, sub_eid, stats
+        dict): sub_ptr int64 [len(cols) + 1], sub_col int32 the targets' ranks in cols, sub_eid int64 the edges' places in
+        the graph's col array (None unless want_eid) -- numpy arrays, or with device=True torch tensors on the context's GPU;
+        stats: edges, scanned (the out-degrees of cols, added up: the edges read), sub_ms (device time of the kernels).
+        subgraph_edge_index makes the COO pair of it.  Ends with the held result."""
+        rp, nq, _ = self._row_ptr(row_ptr)
+        edges, scanned, ms = C.c_int64(0), C.c_uint64(0), C.c_double(0)
+        if device:
+            self._torch_device("sparse_subgraph")  # (refused before anything is built)
+        self._chk(self._lib.fora_hip_sparse_subgraph(self._ctx, _p(rp), nq, C.byref(edges), C.byref(scanned), C.byref(ms)))
+        e, nc = edges.value, self.held_cols
+        specs = [(nc + 1, np.int64, "int64"), (e, np.int32, "int32"), (e, np.int64, "int64") if want_eid else None]
+        (sub_ptr, sub_col, sub_eid), ptrs = self._held_outputs(specs, device, "sparse_subgraph")
+        self._chk(self._lib.fora_hip_sparse_subgraph_fetch(self._ctx, *ptrs, e))
+        return sub_ptr, sub_col, sub_eid, {"edges": e, "scanned": scanned.value, "sub_ms": ms.value}
+
+    def store_take_subgraph(self, rows, want_eid=False, device=False):
+        """store_take, sparse_compact, sparse_subgraph: rows `rows` of the store become the held result over their own
+        columns, with the graph's edges among those columns.  Returns (row_ptr, cols, sub_ptr, sub_col, sub_eid or None,
+        stats dict of the subgraph)."""
+        row_ptr, cols, _ = self.store_take_compact(rows, device=device)
+        sub_ptr, sub_col, sub_eid, st = self.sparse_subgraph(row_ptr, want_eid=want_eid, device=device)
+        return row_ptr, cols, sub_ptr, sub_col, sub_eid, st
 
     # ---- feature propagation (the PROPAGATE contract of include/fora_hip.h)
     @staticmethod

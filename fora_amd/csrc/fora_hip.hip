@@ -20,7 +20,8 @@
 #include "fora_attn_bwd.h"
 #include "fora_store.h"
 #include "fora_cols.h"
-#include "../../include/fora_hip.h"
+#include "fora_subgraph.h"
+#include "../../include/fora_hip_ext.h"
 
 #include <algorithm>
 #include <cassert>
@@ -42,7 +43,7 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -113,6 +114,7 @@ struct Tunables {
     int64_t attn_short = ATTN_SHORT_MAX; // ATTENTION (fora_hip_sparse_attention): a non-empty row of at most this many entries (clamped to 0 .. 256, fora_attn_plan.h) is one wave's per head in the fused kernel k_attn_short; a longer one goes through the kernels of SCORES, ROW SOFTMAX and PROPAGATE WITH VALUES inside the same call; 0: every row does.  Same bits for every value.  ATTENTION, BACKWARD (fora_hip_sparse_attention_bwd) reads it for rows (k_attn_bwd_short) and columns (k_attn_cols, fora_attn_bwd_plan.h) alike
     int64_t take_span = STORE_SPAN_DEFAULT; // ROW STORE (fora_hip_store_take; the check of fora_hip_store_load): output entries one workgroup copies, a multiple of 64 and at least 64 (store_span, fora_store_plan.h).  Same bits for every value.  DESIGN.md 5.20 has the runs behind the default
     int64_t cols_block = COLS_BLOCK_DEFAULT; // COLUMNS (fora_hip_sparse_compact): words of the bitmap one workgroup of k_cols_totals / k_cols_list counts, a power of two from 1 to 4096 (cols_block, fora_cols_plan.h).  Same bits for every value.  DESIGN.md 5.21 has the runs behind the default
+    int64_t sub_span = SUB_SPAN_DEFAULT; // SUBGRAPH (fora_hip_sparse_subgraph): scanned edges one workgroup of k_sub_count / k_sub_write takes, a power of two from 256 to 8192 (sub_span, fora_subgraph_plan.h).  Same bits for every value.  The default is provisional and unmeasured
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -129,7 +131,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"prop_segs", &Tunables::prop_segs, false}, {"propt_lds_cap", &Tunables::propt_lds_cap, false},
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
     {"softmax_short", &Tunables::softmax_short, false}, {"attn_short", &Tunables::attn_short, false},
-    {"take_span", &Tunables::take_span, false}, {"cols_block", &Tunables::cols_block, false},
+    {"take_span", &Tunables::take_span, false}, {"cols_block", &Tunables::cols_block, false}, {"sub_span", &Tunables::sub_span, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -404,9 +406,21 @@ struct RowStore {
 
 // COLUMNS (fora_hip_sparse_compact, fora_hip_sparse_cols_fetch): the bitmap over the n nodes, the rank of every word's first set
 // bit, the blocks' totals and offsets, nc, and U itself.  d_cols is U while the held result is compacted (SparseResult::cols
-// entries of it); the rest is scratch of the call in progress.  Grow-only, freed by set_graph and destroy (free_cols).
+// entries of it), and d_bitmap and d_wrank describe U for as long: cols_compact_impl is their only writer, and a compacted result
+// is not compacted again -- SUBGRAPH reads them.  The totals, offsets and nc are scratch of the call in progress.  Grow-only,
+// freed by set_graph and destroy (free_cols).
 struct ColsBufs {
     DevBuf<unsigned long long> d_bitmap, d_nc; DevBuf<uint32_t> d_wrank, d_btot; DevBuf<int32_t> d_cols;
+};
+
+// SUBGRAPH (fora_hip_sparse_subgraph, fora_hip_sparse_subgraph_fetch): the CSR the graph induces on the columns of the compacted
+// held result -- d_ptr [nc + 1], d_col and d_eid [edges] while `valid` -- and the scratch of the call in progress: scan_ptr
+// [nc + 1] and base [nc] of the rows, the row blocks' totals | offsets, the spans' kept counts and offsets, S | edges.  valid
+// ends with the held result (sparse_unheld).  Grow-only, freed by set_graph and destroy (free_sub).
+struct SubBufs {
+    bool valid = false; uint64_t edges = 0;
+    DevBuf<int64_t> d_ptr, d_eid, d_scan, d_base; DevBuf<int32_t> d_col;
+    DevBuf<uint64_t> d_rtot, d_off; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_tot;
 };
 
 // The loose words of the context, grouped by role.
@@ -441,7 +455,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -451,7 +465,7 @@ struct fora_ctx {
     std::string err;
     Tunables opt_;
     int grid_blocks = 2048; // (option `grid`)
-    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt; RowStore st; ColsBufs cl;
+    Graph g; Index ix; Workspace ws; BwdBufs bw; SparseResult sp; SeedBufs sd; SweepResult swp; PropBufs pr; PropTBufs pt; RowStore st; ColsBufs cl; SubBufs sb;
     bool topk_lds_ready = false; // k_topk_rows<true> may take the whole of a CU's LDS (topk_lds_limit)
     uint64_t sparse_gen = 0;   // fora_hip_get_option "sparse_generation": counts the times a sparse result became held or stopped being held
     int batch_req = 0;        // the caller's request (fora_hip_set_batch), not part of a plan
@@ -483,6 +497,7 @@ void sparse_unheld(fora_ctx *c) {
     if (c->sp.valid) c->sparse_gen++;
     c->sp.valid = false; c->sp.entries = 0;
     c->sp.compacted = false; c->sp.cols = 0;
+    c->sb.valid = false; c->sb.edges = 0; // (the subgraph over its columns)
     if (c->pt.built) { (void)hipSetDevice(c->device); c->pt = PropTBufs{}; }
 }
 void free_sparse(fora_ctx *c) { sparse_unheld(c); c->sp = SparseResult{}; }
@@ -490,6 +505,7 @@ void free_sweep(fora_ctx *c) { c->swp = SweepResult{}; }
 void free_prop(fora_ctx *c) { c->pr = PropBufs{}; }
 void free_store(fora_ctx *c) { c->st = RowStore{}; }
 void free_cols(fora_ctx *c) { c->cl = ColsBufs{}; }
+void free_sub(fora_ctx *c) { c->sb = SubBufs{}; }
 // the columns of the held sparse result: the n nodes, or its own nc once fora_hip_sparse_compact has relabelled it.  Every call
 // on the held rows sizes and plans its column side by this
 inline uint64_t held_cols(const fora_ctx *c) { return c->sp.compacted ? c->sp.cols : (uint64_t)c->g.n; }
@@ -1010,6 +1026,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SOFTMAX: t.softmax_ms += ms; break;           // the k_softmax_* kernels of a call: fora_softmax_stats only
         case EV_ATTN: t.attn_ms += ms; break;                 // every launch of an ATTENTION call: fora_attn_stats only
         case EV_COLS: t.cols_ms += ms; break;                 // the bitmap's clear and the five k_cols_* kernels: fora_cols_stats only
+        case EV_SUB: t.sub_ms += ms; break;                   // the k_sub_* kernels of a call: ms_out of fora_hip_sparse_subgraph only
         case EV_STORE: t.store_ms += ms; break;               // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -3298,6 +3315,7 @@ void fora_hip_destroy(fora_ctx *c) {
     free_prop(c);
     free_store(c);
     free_cols(c);
+    free_sub(c);
     c->bw = BwdBufs{};
     c->d_stamps.reset();
     for (auto &p : c->tm.ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -3334,6 +3352,7 @@ int fora_hip_set_graph(fora_ctx *c, int32_t n, int64_t m_attr, const int64_t *ro
     free_prop(c); // (the upload of another graph's features)
     free_store(c); // (rows over another graph's nodes)
     free_cols(c); // (a bitmap over another graph's nodes)
+    free_sub(c); // (edges of another graph)
     c->sd = SeedBufs{}; // (a block sized for another n; until here it holds ns * n * 8 bytes that later calls cannot plan slots in)
     c->retry.scale = 1; c->retry.scale_topk = 1;
     const int rc = [&]() -> int {
@@ -4053,6 +4072,108 @@ int fora_hip_sparse_cols_fetch(fora_ctx *c, int32_t *cols, uint64_t cap) {
     if (cols) if (int rc = sparse_dest(c, cols, on_device)) return rc;
     if (c->sp.cols) HIPCHK(c, hipMemcpyAsync(cols, c->cl.d_cols.get(), c->sp.cols * 4, hipMemcpyDefault, c->stream));
     return held_call_end(c, "sparse cols fetch", false);
+}
+
+// ---- SUBGRAPH (the contract of include/fora_hip_ext.h; kernels in fora_subgraph.h, the arithmetic in fora_subgraph_plan.h)
+namespace {
+// a word of the device on the host, the stream idle behind it; a failure leaves no subgraph held (the call only reads the held result)
+int sub_read(fora_ctx *c, const unsigned long long *d, unsigned long long &v) {
+    int rc = FORA_OK;
+    if (const hipError_t e = hipMemcpyAsync(&v, d, sizeof(v), hipMemcpyDeviceToHost, c->stream); e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        rc = fail(c, FORA_E_HIP, std::string("sparse subgraph: ") + hipGetErrorString(e));
+    } else rc = held_call_end(c, "sparse subgraph", false);
+    if (rc) c->sb.valid = false;
+    return rc;
+}
+int subgraph_impl(fora_ctx *c, int64_t *edges_out, uint64_t *scanned_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    const ColsBufs &cl = c->cl;
+    const uint64_t nc = c->sp.cols, nnz = (uint64_t)c->g.nnz;
+    const uint32_t n = (uint32_t)c->g.n, span = sub_span(c->opt_.sub_span);
+    unsigned long long S = 0, edges = 0;
+    c->tm.sub_ms = 0;
+    if (nc) {
+        // ---- every buffer whose size is known before the first launch: a call that finds no room has changed nothing
+        const char *what = "the subgraph";
+        const uint64_t rblocks = (nc + BLOCK - 1) / BLOCK;
+        if (int rc = prop_ensure(c, b.d_scan, (size_t)nc + 1, what)) return rc;
+        if (int rc = prop_ensure(c, b.d_base, (size_t)nc, what)) return rc;
+        if (int rc = prop_ensure(c, b.d_rtot, 2 * (size_t)rblocks, what)) return rc; // totals | offsets
+        if (int rc = prop_ensure(c, b.d_tot, 2, what)) return rc;                    // S | edges
+        if (int rc = prop_ensure(c, b.d_ptr, (size_t)nc + 1, what)) return rc;
+        const auto grid = [](uint64_t units) { return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(units, 1), 1u << 16)); }; // (the kernels stride over their work)
+        const int32_t *U = cl.d_cols.get();
+        const int64_t *row_ptr = c->g.d_row_ptr.get();
+        const unsigned long long *bitmap = cl.d_bitmap.get();
+        uint64_t *const rtot = b.d_rtot.get(), *const roff = rtot + rblocks;
+        { // rows: the out-degrees of U, scanned
+            EvSpan ev(c, EV_SUB);
+            hipLaunchKernelGGL(k_sub_row_totals, grid(rblocks), dim3(BLOCK), 0, c->stream, U, nc, row_ptr, n, rblocks, rtot);
+            hipLaunchKernelGGL(k_sub_scan<uint64_t>, dim3(1), dim3(BLOCK), 0, c->stream, (const uint64_t *)rtot, rblocks, roff, b.d_tot.get());
+            hipLaunchKernelGGL(k_sub_row_list, grid(rblocks), dim3(BLOCK), 0, c->stream, U, nc, row_ptr, n, rblocks, (const uint64_t *)roff, b.d_scan.get(), b.d_base.get());
+        }
+        if (int rc = sub_read(c, b.d_tot.get(), S)) return rc; // (the first of the call's two synchronisations: S sizes the spans)
+        if (S > nnz) { b.valid = false; return fail(c, FORA_E_HIP, "sparse subgraph: more scanned edges than the graph has"); }
+        const uint64_t spans = sub_spans(S, span);
+        if (spans) {
+            if (int rc = prop_ensure(c, b.d_cnt, (size_t)spans, what)) return rc;
+            if (int rc = prop_ensure(c, b.d_off, (size_t)spans, what)) return rc;
+            {
+                EvSpan ev(c, EV_SUB);
+                hipLaunchKernelGGL(k_sub_count, grid(spans), dim3(BLOCK), 0, c->stream, (const int64_t *)b.d_scan.get(), (const int64_t *)b.d_base.get(), nc, (uint64_t)S, span, spans,
+                                   (const int32_t *)c->g.d_col.get(), nnz, bitmap, n, b.d_cnt.get());
+                hipLaunchKernelGGL(k_sub_scan<uint32_t>, dim3(1), dim3(BLOCK), 0, c->stream, (const uint32_t *)b.d_cnt.get(), spans, b.d_off.get(), b.d_tot.get() + 1);
+            }
+            if (int rc = sub_read(c, b.d_tot.get() + 1, edges)) return rc; // (the second: the edges size sub_col and sub_eid)
+            if (edges > S) { b.valid = false; return fail(c, FORA_E_HIP, "sparse subgraph: more kept edges than scanned ones"); }
+            if (int rc = prop_ensure(c, b.d_col, (size_t)edges, what)) return rc;
+            if (int rc = prop_ensure(c, b.d_eid, (size_t)edges, what)) return rc;
+            b.valid = false; // (sub_ptr, sub_col and sub_eid are written from here on)
+            EvSpan ev(c, EV_SUB);
+            hipLaunchKernelGGL(k_sub_write, grid(spans), dim3(BLOCK), ((size_t)span + 1) * sizeof(uint32_t), c->stream, (const int64_t *)b.d_scan.get(), (const int64_t *)b.d_base.get(), nc,
+                               (uint64_t)S, span, spans, (const int32_t *)c->g.d_col.get(), nnz, bitmap, (const uint32_t *)cl.d_wrank.get(), n, (const uint64_t *)b.d_off.get(),
+                               b.d_ptr.get(), b.d_col.get(), b.d_eid.get(), (uint64_t)edges);
+        } else { // no node of U has an out-edge: nc + 1 offsets of 0
+            b.valid = false;
+            if (const hipError_t e = hipMemsetAsync(b.d_ptr.get(), 0, ((size_t)nc + 1) * 8, c->stream); e != hipSuccess) return fail(c, FORA_E_HIP, std::string("sparse subgraph: ") + hipGetErrorString(e));
+        }
+    }
+    if (int rc = held_call_end(c, "sparse subgraph")) { b.valid = false; return rc; }
+    b.valid = true; b.edges = edges;
+    *edges_out = (int64_t)edges;
+    if (scanned_out) *scanned_out = S;
+    if (ms_out) *ms_out = c->tm.sub_ms;
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_sparse_subgraph(fora_ctx *c, const int64_t *row_ptr, int nq, int64_t *edges_out, uint64_t *scanned_out, double *ms_out) {
+    if (int rc = held_call_begin(c, "sparse subgraph", row_ptr, nq)) return rc;
+    if (!edges_out) return fail(c, FORA_E_ARG, "sparse subgraph: edges_out is required");
+    if (!c->sp.compacted) return fail(c, FORA_E_ARG, "sparse subgraph: the held result is not compacted (fora_hip_sparse_compact first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_impl(c, edges_out, scanned_out, ms_out));
+}
+
+int fora_hip_sparse_subgraph_fetch(fora_ctx *c, int64_t *sub_ptr, int32_t *sub_col, int64_t *sub_eid, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, "sparse subgraph fetch: no subgraph is held");
+    if (cap < c->sb.edges) return fail(c, FORA_E_ARG, "sparse subgraph fetch: cap is smaller than the held edges");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool ptr_on_device = false, col_on_device = false, eid_on_device = false;
+    if (sub_ptr) if (int rc = sparse_dest(c, sub_ptr, ptr_on_device)) return rc;
+    if (sub_col) if (int rc = sparse_dest(c, sub_col, col_on_device)) return rc;
+    if (sub_eid) if (int rc = sparse_dest(c, sub_eid, eid_on_device)) return rc;
+    const uint64_t nc = c->sp.cols, edges = c->sb.edges;
+    if (sub_ptr) {
+        if (nc) HIPCHK(c, hipMemcpyAsync(sub_ptr, c->sb.d_ptr.get(), ((size_t)nc + 1) * 8, hipMemcpyDefault, c->stream));
+        else if (ptr_on_device) HIPCHK(c, hipMemsetAsync(sub_ptr, 0, 8, c->stream)); // (nothing was launched: the one offset)
+        else sub_ptr[0] = 0;
+    }
+    if (sub_col && edges) HIPCHK(c, hipMemcpyAsync(sub_col, c->sb.d_col.get(), (size_t)edges * 4, hipMemcpyDefault, c->stream));
+    if (sub_eid && edges) HIPCHK(c, hipMemcpyAsync(sub_eid, c->sb.d_eid.get(), (size_t)edges * 8, hipMemcpyDefault, c->stream));
+    return held_call_end(c, "sparse subgraph fetch", false);
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

@@ -474,6 +474,22 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w, u
     total = a0 + a1 + a2 + a3;
     return x + (w > 0 ? a0 : 0) + (w > 1 ? a1 : 0) + (w > 2 ? a2 : 0);
 }
+// the same in 64 bits (sums of out-degrees, of kept edges); s_w: 4-entry LDS scratch
+__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t *s_w, uint64_t &total) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long x = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[w] = x;
+    __syncthreads();
+    const uint64_t a0 = s_w[0], a1 = s_w[1], a2 = s_w[2], a3 = s_w[3];
+    total = a0 + a1 + a2 + a3;
+    return x - v + (w > 0 ? a0 : 0) + (w > 1 ? a1 : 0) + (w > 2 ? a2 : 0);
+}
 
 // Entry search.  A tile's NT entries (frontier nodes, walk items) hold cnt[i] units each (edges, quads, walks), concatenated:
 // s_pref[0 .. NT] are the exclusive prefix sums in LDS, s_pref[NT] the total.  Unit x < total belongs to the largest entry lo
