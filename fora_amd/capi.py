@@ -7,7 +7,9 @@ each of them.  A new entry point takes three steps: its prototype in include/for
 its own: a mirror in STRUCTS), one Engine method.  tests/test_capi_cpu.py derives every row and every mirror from the
 header again and fails until they match.  Entry points declared in the extension header include/fora_hip_ext.h have
 their rows in a second table, _ABI_EXT, of the same syntax, bound by the same load() (tests/test_subgraph_cpu.py holds
-it to that header); they report statistics through out-pointers and add no struct."""
+it to that header); they report statistics through out-pointers and add no struct.  The entry points of
+include/fora_hip_gnn.h (message passing on the held subgraph) have a third table of the same kind, _ABI_GNN
+(tests/test_subgraph_prop_cpu.py)."""
 import ctypes as C
 import os
 
@@ -234,6 +236,17 @@ int  fora_hip_sparse_subgraph_fetch(ctx*, ptr, ptr, ptr, uint64)
 ABI_EXT = _rows(_ABI_EXT)
 EXT_SYMBOLS = list(ABI_EXT)
 
+# the entry points of include/fora_hip_gnn.h, message passing on the held subgraph: a third table of the same syntax (the
+# censuses of the two headers above are pinned); tests/test_subgraph_prop_cpu.py derives them from that header again
+_ABI_GNN = """
+int  fora_hip_subgraph_propagate(ctx*, ptr, int, int, int64, int, ptr, int, ptr, ptr, int64, ptr, ptr)
+int  fora_hip_subgraph_propagate_t(ctx*, ptr, int, int, int64, int, ptr, int, ptr, ptr, int64, ptr, ptr)
+int  fora_hip_subgraph_transpose_fetch(ctx*, ptr, ptr, ptr, uint64)
+"""
+ABI_GNN = _rows(_ABI_GNN)
+GNN_SYMBOLS = list(ABI_GNN)
+SUB_MEAN = 1  # FORA_SUB_MEAN
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -271,7 +284,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -600,6 +613,72 @@ class Engine:
         row_ptr, cols, _ = self.store_take_compact(rows, device=device)
         sub_ptr, sub_col, sub_eid, st = self.sparse_subgraph(row_ptr, want_eid=want_eid, device=device)
         return row_ptr, cols, sub_ptr, sub_col, sub_eid, st
+
+    # ---- message passing on the held subgraph (the SUBGRAPH PRODUCTS contract of include/fora_hip_gnn.h)
+    def _subgraph_product(self, fn, who, X, values, mean, want32, want64, out32, out64, bf16):
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, f"{who}: no subgraph is held (sparse_subgraph first)")
+        if mean and values is not None:
+            raise ForaError(-1, f"{who}: mean and values exclude each other (pass 1 / count as values)")
+        xptr, xtype, d, ldx, on_dev, _keep = self._prop_feat(X, bf16, rows=nc, name="X", shape="[nc, d] (nc: the held columns)")
+        vptr, vtype, _vkeep = None, PROP_F32, None
+        if values is not None:
+            vptr, vtype, _, _vkeep = self._entry_operand(values, edges, "values", beside=on_dev)
+            if edges == 0:
+                vptr = None
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, d, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
+        flags = SUB_MEAN if mean else 0
+        self._chk(fn(self._ctx, xptr, xtype, d, ldx, flags, vptr, vtype, p32, p64, ldo, info, ms))
+        return out32, out64, {"edges": edges, "built": int(info[0]), "long_rows": int(info[1]), "chunks": int(info[2]), "x_on_device": int(info[3]),
+                              "transpose_ms": ms[0], "short_ms": ms[1], "long_ms": ms[2]}
+
+    def subgraph_propagate(self, X, values=None, mean=False, want32=True, want64=False, out32=None, out64=None, bf16=False):
+        """out = A_S x X over the held subgraph (fora_hip_subgraph_propagate, the SUBGRAPH PRODUCTS contract of
+        include/fora_hip_gnn.h): out[j] = sum over the edges e of row j of sparse_subgraph's CSR, in the order of sub_col, of
+        w_e * X[sub_col[e]] -- the aggregation over the out-neighbours of cols[j] inside the batch, multi-edges as often as
+        they stand, every bit defined.  X: [nc, d] (nc = held_cols), with the conventions of sparse_propagate's feat: a numpy
+        float32 / float16 array, uint16 or uint8 codes with bf16=True / "bf16" / "e4m3" / "e5m2", or a torch tensor on the
+        context's GPU (a column slice is read in place).  values: one float32 or float64 per edge of the subgraph in the
+        order of sub_col (None: every weight 1.0) -- numpy, or a torch tensor beside a torch X.  mean: every output row
+        divided by the number of its edges (a row without edges is 0); not together with values.  Returns (out32 or None,
+        out64 or None, stats dict): [nc, d], torch tensors with a torch X, numpy arrays otherwise; out32 / out64:
+        caller-made outputs as for sparse_propagate.  stats: edges, built (this call built the transposition), long_rows
+        (output rows longer than the option "sub_short"), chunks of their path, x_on_device, and the device times
+        transpose_ms, short_ms, long_ms."""
+        return self._subgraph_product(self._lib.fora_hip_subgraph_propagate, "subgraph_propagate", X, values, mean, want32, want64, out32, out64, bf16)
+
+    def subgraph_propagate_t(self, G, values=None, mean=False, want32=True, want64=False, out32=None, out64=None, bf16=False):
+        """out = A_S^T x G over the held subgraph (fora_hip_subgraph_propagate_t): out[v] = sum over the edges e with
+        sub_col[e] == v, in ascending e, of w_e * G[row of e] -- the aggregation over in-neighbours, and the gradient of
+        subgraph_propagate with respect to X when G is the gradient with respect to its output.  values is still indexed by
+        the edge's place in sub_col; mean divides by a column's number of edges.  Operands, outputs and stats as for
+        subgraph_propagate; the first transposed call on a held subgraph builds its transposition (stats["built"] == 1)."""
+        return self._subgraph_product(self._lib.fora_hip_subgraph_propagate_t, "subgraph_propagate_t", G, values, mean, want32, want64, out32, out64, bf16)
+
+    def subgraph_degrees(self, transposed=False, device=False):
+        """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition
+        if it is not there): int64 [nc], numpy or with device=True a torch tensor -- the counts FORA_SUB_MEAN divides by."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_degrees: no subgraph is held (sparse_subgraph first)")
+        (ptr,), (p,) = self._held_outputs([(nc + 1, np.int64, "int64")], device, "subgraph_degrees")
+        fetch = self._lib.fora_hip_subgraph_transpose_fetch if transposed else self._lib.fora_hip_sparse_subgraph_fetch
+        self._chk(fetch(self._ctx, p, None, None, edges))
+        return ptr[1:] - ptr[:-1]
+
+    def subgraph_transpose_fetch(self, device=False):
+        """The transposition of the held subgraph (fora_hip_subgraph_transpose_fetch), built if it is not there: (in_ptr int64
+        [nc + 1], in_row int32, in_pos int64 [edges]) -- column by column the local row every entry came from and the edge's
+        place in sub_col, ascending inside a column.  numpy arrays, or with device=True torch tensors on the context's GPU."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_transpose_fetch: no subgraph is held (sparse_subgraph first)")
+        specs = [(nc + 1, np.int64, "int64"), (edges, np.int32, "int32"), (edges, np.int64, "int64")]
+        (in_ptr, in_row, in_pos), ptrs = self._held_outputs(specs, device, "subgraph_transpose_fetch")
+        self._chk(self._lib.fora_hip_subgraph_transpose_fetch(self._ctx, *ptrs, edges))
+        return in_ptr, in_row, in_pos
 
     # ---- feature propagation (the PROPAGATE contract of include/fora_hip.h)
     @staticmethod

@@ -21,7 +21,8 @@
 #include "fora_store.h"
 #include "fora_cols.h"
 #include "fora_subgraph.h"
-#include "../../include/fora_hip_ext.h"
+#include "fora_subgraph_prop.h"
+#include "../../include/fora_hip_gnn.h"
 
 #include <algorithm>
 #include <cassert>
@@ -43,7 +44,8 @@ namespace {
 // launches count under which kind.
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
-              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB };
+              EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
+              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -115,6 +117,7 @@ struct Tunables {
     int64_t take_span = STORE_SPAN_DEFAULT; // ROW STORE (fora_hip_store_take; the check of fora_hip_store_load): output entries one workgroup copies, a multiple of 64 and at least 64 (store_span, fora_store_plan.h).  Same bits for every value.  DESIGN.md 5.20 has the runs behind the default
     int64_t cols_block = COLS_BLOCK_DEFAULT; // COLUMNS (fora_hip_sparse_compact): words of the bitmap one workgroup of k_cols_totals / k_cols_list counts, a power of two from 1 to 4096 (cols_block, fora_cols_plan.h).  Same bits for every value.  DESIGN.md 5.21 has the runs behind the default
     int64_t sub_span = SUB_SPAN_DEFAULT; // SUBGRAPH (fora_hip_sparse_subgraph): scanned edges one workgroup of k_sub_count / k_sub_write takes, a power of two from 256 to 8192 (sub_span, fora_subgraph_plan.h).  Same bits for every value.  The default is provisional and unmeasured
+    int64_t sub_short = SUB_SHORT_DEFAULT; // SUBGRAPH PRODUCTS (fora_hip_subgraph_propagate, fora_hip_subgraph_propagate_t): an output row of at most this many entries (clamped to 0 .. 256, fora_subgraph_prop_plan.h) is summed and written by the one-pass kernel k_sub_agg; a longer one goes through the kernels of PROPAGATE inside the same call; 0: every non-empty row does.  Same bits for every value
     int64_t seeds_rows = 256;    // seed sets, sparse rows and sweeps (fora_hip_seeds_sparse_batch, fora_hip_seeds_sweep_batch): rows of the accumulator block compacted / sorted at a time (at least 1; seeds_chunk); bounds the count, total, descriptor and sort buffers.  Same bits for every value
 };
 static const struct { const char *name; int64_t Tunables::*field; bool layout; } OPTIONS[] = {
@@ -132,6 +135,7 @@ static const struct { const char *name; int64_t Tunables::*field; bool layout; }
     {"topk_lds_cap", &Tunables::topk_lds_cap, false}, {"topk_cand", &Tunables::topk_cand, false},
     {"softmax_short", &Tunables::softmax_short, false}, {"attn_short", &Tunables::attn_short, false},
     {"take_span", &Tunables::take_span, false}, {"cols_block", &Tunables::cols_block, false}, {"sub_span", &Tunables::sub_span, false},
+    {"sub_short", &Tunables::sub_short, false},
 };
 // knobs that choose another push SCHEDULE (other, equally valid result bits): never taken from the environment -- a stray
 // variable must not change what a query returns; fora_hip_set_option sets them (tests, experiments)
@@ -417,10 +421,25 @@ struct ColsBufs {
 // held result -- d_ptr [nc + 1], d_col and d_eid [edges] while `valid` -- and the scratch of the call in progress: scan_ptr
 // [nc + 1] and base [nc] of the rows, the row blocks' totals | offsets, the spans' kept counts and offsets, S | edges.  valid
 // ends with the held result (sparse_unheld).  Grow-only, freed by set_graph and destroy (free_sub).
+// SUBGRAPH PRODUCTS (include/fora_hip_gnn.h) keep what they derive from the held subgraph in `prop`: its transposition, built by
+// the first transposed call or fora_hip_subgraph_transpose_fetch, and per side the host copy of the offsets with the plan of
+// the long rows and its device tables, made by the first call that needs them under a value of "sub_short" and a chunk size.
+// All of it ends when the subgraph ends or is built again (sub_prop_drop) and is freed by free_sub.
+struct SubProp {
+    struct Side {
+        bool have_ptr = false; std::vector<int64_t> h_ptr;  // the offsets on the host: sub_ptr / in_ptr
+        bool planned = false; uint32_t cap = 0; uint64_t per = 0; // the key of the plan
+        SubSplit split; PropPlan plan;                      // (host: the chunks sequence the launches)
+        DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;
+    } fwd, tr;
+    bool t_built = false;
+    DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row; // [nc + 1], [edges], [edges]: the entries column by column
+};
 struct SubBufs {
     bool valid = false; uint64_t edges = 0;
     DevBuf<int64_t> d_ptr, d_eid, d_scan, d_base; DevBuf<int32_t> d_col;
     DevBuf<uint64_t> d_rtot, d_off; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_tot;
+    SubProp prop; bool prop_used = false; // (prop_used: prop holds something)
 };
 
 // The loose words of the context, grouped by role.
@@ -455,7 +474,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -492,12 +511,19 @@ int fail(fora_ctx *c, int code, const std::string &msg) {
 
 // every buffer of the group freed, every field of it back at its initialiser
 void free_graph(fora_ctx *c) { c->g = Graph{}; }
+// what SUBGRAPH PRODUCTS derived from the held subgraph goes: the subgraph ends or is built again
+void sub_prop_drop(fora_ctx *c) {
+    if (!c->sb.prop_used) return;
+    (void)hipSetDevice(c->device);
+    c->sb.prop = SubProp{}; c->sb.prop_used = false;
+}
 // the held sparse result stops being held (its arrays stay): the generation moves, the transposition built from it goes
 void sparse_unheld(fora_ctx *c) {
     if (c->sp.valid) c->sparse_gen++;
     c->sp.valid = false; c->sp.entries = 0;
     c->sp.compacted = false; c->sp.cols = 0;
     c->sb.valid = false; c->sb.edges = 0; // (the subgraph over its columns)
+    sub_prop_drop(c);
     if (c->pt.built) { (void)hipSetDevice(c->device); c->pt = PropTBufs{}; }
 }
 void free_sparse(fora_ctx *c) { sparse_unheld(c); c->sp = SparseResult{}; }
@@ -1027,7 +1053,10 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_ATTN: t.attn_ms += ms; break;                 // every launch of an ATTENTION call: fora_attn_stats only
         case EV_COLS: t.cols_ms += ms; break;                 // the bitmap's clear and the five k_cols_* kernels: fora_cols_stats only
         case EV_SUB: t.sub_ms += ms; break;                   // the k_sub_* kernels of a call: ms_out of fora_hip_sparse_subgraph only
-        case EV_STORE: t.store_ms += ms; break;               // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
+        case EV_SUBP_T: t.subp_t_ms += ms; break;             // the transposition of the held subgraph: ms_out[0] of the SUBGRAPH PRODUCTS calls only
+        case EV_SUBP_SHORT: t.subp_short_ms += ms; break;     // k_sub_agg: ms_out[1] of those calls only
+        case EV_SUBP_LONG: t.subp_long_ms += ms; break;       // the gather and combine launches of their long rows: ms_out[2] only
+        case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
     }
@@ -2608,6 +2637,7 @@ struct PropSide {
     bool divide;                             // forward and normalised: a row's sum divided by its word sum in the combine
     const void *values = nullptr; bool val64 = false; // PROPAGATE WITH VALUES: the weights (device; null: the words), f64 or f32
     const int64_t *pos = nullptr;            // (device) with values, transposed: the held place of every entry; forward: null
+    bool unit = false;                       // SUBGRAPH PRODUCTS without values: every weight 1.0, fix is not read
 };
 struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
 
@@ -2618,6 +2648,7 @@ void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uin
     if (sd.values) with_bools(sd.pos != nullptr, sd.val64, [&](auto POS, auto V64) {
         hipLaunchKernelGGL((k_prop_gather_vals<ET, V, POS.value, V64.value>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
     });
+    else if (sd.unit) hipLaunchKernelGGL((k_sub_gather_one<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, feat, ldf, (uint32_t)d, g.G, part);
     else if (sd.rsum) hipLaunchKernelGGL((k_prop_gather_t<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, sd.rsum);
     else hipLaunchKernelGGL((k_prop_gather<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.fix, feat, ldf, (uint32_t)d, g.G, part, segsum);
 }
@@ -2625,7 +2656,8 @@ void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uin
 // live at a time in the ctx's buffers, which the caller has ensured.  timed: an event pair per launch (PROPAGATE's own stats);
 // a caller with a span of its own around the whole passes false.
 void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs, const PropRowRec *d_recs, const PropSide &sd, int et, const PropGeom &g,
-                        const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed) {
+                        const void *feat, int64_t ldf, int d, uint64_t *segsum, float *w32, int64_t ld32, double *w64, int64_t ld64, bool timed,
+                        const int64_t *mean_ptr = nullptr) { // (mean_ptr, device: FORA_SUB_MEAN -- a finished row divided by its number of entries)
     PropBufs &b = c->pr;
     for (size_t ci = 0; ci < plan.chunks.size(); ci++) {
         const PropChunk &ch = plan.chunks[ci];
@@ -2640,9 +2672,12 @@ void prop_launch_chunks(fora_ctx *c, const PropPlan &plan, const PropSeg *d_segs
             if (timed) ev.begin(EV_PROP_COMBINE);
             const uint32_t rpb = d < BLOCK ? (uint32_t)(BLOCK / d) : 1u; // whole records per workgroup when a record is narrower than one
             const dim3 grid((unsigned)((d + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>((ch.nrec + rpb - 1) / rpb, 65535));
-            hipLaunchKernelGGL(k_prop_combine, grid, dim3(BLOCK), 0, c->stream, d_recs + ch.rec0, ch.nrec,
-                               (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
-                               (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, ld32, w64, ld64);
+            const auto combine = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, c->stream, d_recs + ch.rec0, ch.nrec,
+                                   (uint32_t)d, rpb, (const double *)b.d_part.get(), (const uint64_t *)segsum, (const double *)b.d_carry.part(ci & 1, (size_t)d), b.d_carry.part(~ci & 1, (size_t)d),
+                                   (const uint64_t *)b.d_scarry.part(ci & 1, 1), b.d_scarry.part(~ci & 1, 1), w32, ld32, w64, ld64, mean_ptr);
+            };
+            if (mean_ptr) combine(k_prop_combine<true>); else combine(k_prop_combine<false>);
         }
     }
 }
@@ -3455,6 +3490,7 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "team_suspended")) { *value = c->team_run.suspend; return FORA_OK; }             // calls left that do not try the team push
     if (!strcmp(name, "sparse_generation")) { *value = (int64_t)c->sparse_gen; return FORA_OK; }    // moves whenever a sparse result becomes held or stops being held
     if (!strcmp(name, "sparse_cols")) { *value = (int64_t)held_cols(c); return FORA_OK; }           // the columns of the calls on the held rows: n, or nc while a compacted result is held (COLUMNS)
+    if (!strcmp(name, "sub_edges")) { *value = c->sp.valid && c->sp.compacted && c->sb.valid ? (int64_t)c->sb.edges : -1; return FORA_OK; } // the edges of the held subgraph (SUBGRAPH); -1: none is held
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
     if (!strcmp(name, "walk_dg_wgs_per_cu")) { // k_walk_dg's resident workgroups per CU at this graph's tables (0: the graph has no degree-grouped copy)
         const WalkDG &g = c->g.walk.dg;
@@ -4093,6 +4129,7 @@ int subgraph_impl(fora_ctx *c, int64_t *edges_out, uint64_t *scanned_out, double
     const uint32_t n = (uint32_t)c->g.n, span = sub_span(c->opt_.sub_span);
     unsigned long long S = 0, edges = 0;
     c->tm.sub_ms = 0;
+    sub_prop_drop(c); // (the transposition and the plans of SUBGRAPH PRODUCTS were made from the arrays this call writes again)
     if (nc) {
         // ---- every buffer whose size is known before the first launch: a call that finds no room has changed nothing
         const char *what = "the subgraph";
@@ -4174,6 +4211,220 @@ int fora_hip_sparse_subgraph_fetch(fora_ctx *c, int64_t *sub_ptr, int32_t *sub_c
     if (sub_col && edges) HIPCHK(c, hipMemcpyAsync(sub_col, c->sb.d_col.get(), (size_t)edges * 4, hipMemcpyDefault, c->stream));
     if (sub_eid && edges) HIPCHK(c, hipMemcpyAsync(sub_eid, c->sb.d_eid.get(), (size_t)edges * 8, hipMemcpyDefault, c->stream));
     return held_call_end(c, "sparse subgraph fetch", false);
+}
+
+// ---- SUBGRAPH PRODUCTS (the contract of include/fora_hip_gnn.h; kernels in fora_subgraph_prop.h, the split in fora_subgraph_prop_plan.h)
+static_assert(SUB_SHORT_MAX == FORA_PROP_SEG, "a short row of SUBGRAPH PRODUCTS is one segment of the contract");
+namespace {
+// the transposition of the held subgraph: counts, the host's prefix sum, places, every column's keys sorted on the tiers of
+// PROPAGATE, TRANSPOSED (a key is sub_key(row, place in the row), so a multi-edge's two entries keep the order of their places),
+// then in_row and in_pos.  Complete or absent: built in locals, moved into SubBufs::prop after the last step.
+int subt_build(fora_ctx *c) {
+    SubBufs &b = c->sb;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row;
+    DevBuf<uint32_t> d_cnt; PinBuf<uint32_t> h_cnt; // counts per column, then the cursors of the place pass; their pinned landing area
+    DevBuf<uint64_t> d_key; DevBuf<PropTRun> d_runs;
+    std::vector<int64_t> h_in_ptr((size_t)nc + 1, 0);
+    // ---- every buffer before the first launch
+    const char *what = "the subgraph's transposition";
+    if (int rc = prop_ensure(c, d_in_ptr, (size_t)nc + 1, what)) return rc;
+    if (int rc = prop_ensure(c, d_in_row, (size_t)edges, what)) return rc;
+    if (int rc = prop_ensure(c, d_in_pos, (size_t)edges, what)) return rc;
+    if (int rc = prop_ensure(c, d_cnt, (size_t)nc, what)) return rc;
+    if (int rc = prop_ensure(c, d_key, (size_t)edges, what)) return rc;
+    if (int rc = prop_ensure(c, d_runs, (size_t)propt_max_runs(nc, edges), what)) return rc;
+    if (h_cnt.alloc((size_t)std::max<uint64_t>(nc, 1)) != hipSuccess) { (void)hipGetLastError(); return fail(c, FORA_E_NOMEM, "no pinned memory for the subgraph's transposition"); }
+    if (edges) {
+        const uint32_t wgs = (uint32_t)std::min<uint64_t>(nc, 65535);
+        const int64_t *sub_ptr = b.d_ptr.get();
+        const int32_t *sub_col = b.d_col.get();
+        EvSpan ev(c, EV_SUBP_T);
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)nc));
+        hipLaunchKernelGGL(k_subt_count, dim3(wgs), dim3(BLOCK), 0, c->stream, sub_ptr, (uint32_t)nc, sub_col, d_cnt.get());
+        HIPCHK(c, hipMemcpyAsync(h_cnt.get(), d_cnt.get(), (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the counts are back)
+        if (propt_scan(h_cnt.get(), (int64_t)nc, h_in_ptr.data()) != edges) return fail(c, FORA_E_HIP, "subgraph transpose: the counts do not add up to the held edges");
+        const PropTTiers tiers = propt_tiers(h_in_ptr.data(), (int64_t)nc, c->opt_.propt_lds_cap);
+        if (tiers.runs.size() > d_runs.size()) return fail(c, FORA_E_HIP, "subgraph transpose: more runs than the table holds");
+        HIPCHK(c, hipMemcpyAsync(d_in_ptr.get(), h_in_ptr.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (!tiers.runs.empty()) HIPCHK(c, hipMemcpyAsync(d_runs.get(), tiers.runs.data(), tiers.runs.size() * sizeof(PropTRun), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, d_cnt.zero(c->stream, (size_t)nc));
+        hipLaunchKernelGGL(k_propt_place, dim3(wgs), dim3(BLOCK), 0, c->stream, sub_ptr, (uint32_t)nc, sub_col, (uint32_t)nc, (const int64_t *)d_in_ptr.get(), d_cnt.get(),
+                           d_key.get(), edges);
+        const PropTRun *r_short = d_runs.get(), *r_lds = r_short + tiers.n_short, *r_global = r_lds + tiers.n_lds;
+        if (tiers.n_short) hipLaunchKernelGGL(k_propt_sort_short, dim3((tiers.n_short + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, r_short, tiers.n_short, d_key.get());
+        if (tiers.n_lds) hipLaunchKernelGGL(k_propt_sort_lds, dim3(tiers.n_lds), dim3(BLOCK), 0, c->stream, r_lds, d_key.get());
+        if (tiers.n_global) {
+            const uint32_t P = propt_pow2(tiers.max_global);
+            const unsigned gx = (unsigned)std::min<uint32_t>(std::max<uint32_t>(1, P / 2 / BLOCK), 1024);
+            for (uint32_t r0 = 0; r0 < tiers.n_global; r0 += 65535) { // (a grid's y extent)
+                const dim3 grid(gx, std::min<uint32_t>(65535, tiers.n_global - r0));
+                for (uint32_t k = 2; k <= P; k <<= 1) {
+                    hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, 0u);
+                    for (uint32_t j = k >> 2; j; j >>= 1) hipLaunchKernelGGL(k_propt_sort_step, grid, dim3(BLOCK), 0, c->stream, r_global + r0, d_key.get(), k, j);
+                }
+            }
+        }
+        hipLaunchKernelGGL(k_subt_fill, dim3((unsigned)std::min<uint64_t>((edges + BLOCK - 1) / BLOCK, 8192)), dim3(BLOCK), 0, c->stream, (const uint64_t *)d_key.get(), edges,
+                           sub_ptr, (uint32_t)nc, d_in_row.get(), d_in_pos.get());
+        ev.end();
+    } else HIPCHK(c, d_in_ptr.zero(c->stream, (size_t)nc + 1));
+    if (int rc = held_call_end(c, "subgraph transpose")) return rc; // (idle: the tables go out of use)
+    SubProp &p = b.prop;
+    p.d_in_ptr = std::move(d_in_ptr); p.d_in_row = std::move(d_in_row); p.d_in_pos = std::move(d_in_pos);
+    p.tr = SubProp::Side{};
+    p.tr.h_ptr = std::move(h_in_ptr); p.tr.have_ptr = true;
+    p.t_built = true; b.prop_used = true;
+    return FORA_OK;
+}
+int subt_ensure(fora_ctx *c, bool &built_now) {
+    built_now = false;
+    if (c->sb.prop.t_built) return FORA_OK;
+    if (int rc = subt_build(c)) return rc;
+    built_now = true;
+    return FORA_OK;
+}
+// the offsets of a side on the host: in_ptr came with the transposition, sub_ptr is copied once per held subgraph
+int sub_side_ptr(fora_ctx *c, SubProp::Side &s) {
+    if (s.have_ptr) return FORA_OK;
+    const uint64_t nc = c->sp.cols;
+    s.h_ptr.assign((size_t)nc + 1, 0);
+    HIPCHK(c, hipMemcpy(s.h_ptr.data(), c->sb.d_ptr.get(), ((size_t)nc + 1) * 8, hipMemcpyDeviceToHost));
+    s.have_ptr = true; c->sb.prop_used = true;
+    return FORA_OK;
+}
+// the plan of a side's long rows under (cap, per), with its tables on the device: made when the key moves, kept otherwise
+int sub_side_plan(fora_ctx *c, SubProp::Side &s, uint32_t cap, uint64_t per) {
+    if (s.planned && s.cap == cap && s.per == per) return FORA_OK;
+    s.planned = false;
+    PropPlan plan = sub_long_plan(s.h_ptr.data(), (int)c->sp.cols, cap, per);
+    if (int rc = prop_ensure(c, s.d_segs, plan.segs.size(), "the long rows' segment table")) return rc;
+    if (int rc = prop_ensure(c, s.d_recs, plan.recs.size(), "the long rows' segment table")) return rc;
+    if (!plan.segs.empty()) HIPCHK(c, hipMemcpy(s.d_segs.get(), plan.segs.data(), plan.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (!plan.recs.empty()) HIPCHK(c, hipMemcpy(s.d_recs.get(), plan.recs.data(), plan.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    s.plan = std::move(plan); s.cap = cap; s.per = per; s.planned = true;
+    return FORA_OK;
+}
+// one product over the held subgraph (forward: its rows; transposed: its columns).  nc > 0; the arguments have passed sub_prop_entry
+int subgraph_prop_impl(fora_ctx *c, bool transposed, const void *x, int x_type, int d, int64_t ldx, int flags, const void *values, int val_type,
+                       float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    const char *who = transposed ? "subgraph propagate_t" : "subgraph propagate";
+    const uint32_t elt = elt_bytes(x_type);
+    HeldIn feat = HeldIn::matrix(x, nc, ldx, (uint64_t)d, elt), vals = HeldIn::vector(values, edges, val_type == FORA_PROP_F64 ? 8 : 4);
+    HeldOut<float> o32{out32, ldo, nc, (uint64_t)d};
+    HeldOut<double> o64{out64, ldo, nc, (uint64_t)d};
+    if (int rc = held_resolve(c, feat, vals, o32, o64)) return rc; // (before anything is built)
+    c->tm.subp_t_ms = c->tm.subp_short_ms = c->tm.subp_long_ms = 0;
+    bool built_now = false;
+    if (transposed) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &side = transposed ? sp.tr : sp.fwd;
+    // ---- the split and, for the long rows, the plan: from the host copy of the offsets, kept with the subgraph
+    const uint32_t cap = sub_short_cap(c->opt_.sub_short);
+    if (int rc = sub_side_ptr(c, side)) return rc;
+    if (!side.planned || side.cap != cap) { side.split = sub_split(side.h_ptr.data(), (int)nc, cap); side.planned = false; side.cap = cap; }
+    const SubSplit split = side.split;
+    const bool lng = split.long_rows != 0;
+    uint64_t per = 1;
+    if (lng) {
+        size_t fr = 0, tot = 0;
+        if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+        per = prop_chunk_segs(c->opt_.prop_segs, split.long_segs, (uint64_t)fr, d);
+    }
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = sub_side_plan(c, side, cap, per)) return rc;
+    if (int rc = feat.stage(c, pb.d_feat, "the feature upload")) return rc;
+    if (int rc = vals.stage(c, pb.d_vals, "the values upload")) return rc;
+    if (lng) {
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)d), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)d, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat.ptr(), ldx, d, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+    const int64_t *ptr = transposed ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *ids = transposed ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *pos = transposed && vals.ptr() ? sp.d_in_pos.get() : nullptr;
+    const bool val64 = val_type == FORA_PROP_F64, mean = (flags & FORA_SUB_MEAN) != 0;
+    if (split.short_rows) {
+        EvSpan ev(c, EV_SUBP_SHORT);
+        const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+        const dim3 grid((unsigned)((nc + per_wg - 1) / per_wg), g.tiles);
+        const uint32_t wmode = vals.ptr() ? (val64 ? 2u : 1u) : 0u;
+        with_vec(x_type, g.V, [&](auto E, auto V) {
+            hipLaunchKernelGGL((k_sub_agg<E.value, V.value>), grid, dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids, pos, vals.ptr(), wmode, feat.ptr(), ldx, (uint32_t)d, g.G,
+                               mean ? 1u : 0u, o32.ptr(), o32.ld(), o64.ptr(), o64.ld());
+        });
+    }
+    if (lng) {
+        EvSpan ev(c, EV_SUBP_LONG);
+        const PropSide sd{side.h_ptr.data(), (int)nc, ids, nullptr, nullptr, false, vals.ptr(), val64, pos, vals.ptr() == nullptr};
+        prop_launch_chunks(c, side.plan, side.d_segs.get(), side.d_recs.get(), sd, x_type, g, feat.ptr(), ldx, d, nullptr, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), false,
+                           mean ? ptr : nullptr);
+    }
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, who)) return rc;
+    if (info_out) { info_out[0] = built_now ? 1 : 0; info_out[1] = (int64_t)split.long_rows; info_out[2] = lng ? (int64_t)side.plan.chunks.size() : 0; info_out[3] = feat.on_device(); }
+    if (ms_out) { ms_out[0] = c->tm.subp_t_ms; ms_out[1] = c->tm.subp_short_ms; ms_out[2] = c->tm.subp_long_ms; }
+    return FORA_OK;
+}
+int sub_prop_entry(fora_ctx *c, bool transposed, const void *x, int x_type, int d, int64_t ldx, int flags, const void *values, int val_type,
+                   float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = transposed ? "subgraph propagate_t" : "subgraph propagate";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + ": no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(x_type)) return fail(c, FORA_E_ARG, who + ": unknown element type");
+    if (flags & ~FORA_SUB_MEAN) return fail(c, FORA_E_ARG, who + ": unknown flag");
+    if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, who + ": d outside 1 .. 65536");
+    if (ldx < d || ldo < d) return fail(c, FORA_E_ARG, who + ": a leading dimension smaller than d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + ": no output");
+    if (c->sp.cols && !x) return fail(c, FORA_E_ARG, who + ": null operand");
+    if (values) {
+        if (flags & FORA_SUB_MEAN) return fail(c, FORA_E_ARG, who + ": FORA_SUB_MEAN with values");
+        if (val_type != FORA_PROP_F32 && val_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + ": val_type is neither f32 nor f64");
+    }
+    if (info_out) memset(info_out, 0, 4 * sizeof(int64_t));
+    if (ms_out) memset(ms_out, 0, 3 * sizeof(double));
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_prop_impl(c, transposed, x, x_type, d, ldx, flags, c->sb.edges ? values : nullptr, val_type, out32, out64, ldo, info_out, ms_out));
+}
+} // namespace
+
+int fora_hip_subgraph_propagate(fora_ctx *c, const void *x, int x_type, int d, int64_t ldx, int flags, const void *values, int val_type,
+                                float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    return sub_prop_entry(c, false, x, x_type, d, ldx, flags, values, val_type, out32, out64, ldo, info_out, ms_out);
+}
+int fora_hip_subgraph_propagate_t(fora_ctx *c, const void *g, int g_type, int d, int64_t ldg, int flags, const void *values, int val_type,
+                                  float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    return sub_prop_entry(c, true, g, g_type, d, ldg, flags, values, val_type, out32, out64, ldo, info_out, ms_out);
+}
+int fora_hip_subgraph_transpose_fetch(fora_ctx *c, int64_t *in_ptr, int32_t *in_row, int64_t *in_pos, uint64_t cap) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, "subgraph transpose fetch: no subgraph is held");
+    if (cap < c->sb.edges) return fail(c, FORA_E_ARG, "subgraph transpose fetch: cap is smaller than the held edges");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool ptr_on_device = false, row_on_device = false, pos_on_device = false;
+    if (in_ptr) if (int rc = sparse_dest(c, in_ptr, ptr_on_device)) return rc;
+    if (in_row) if (int rc = sparse_dest(c, in_row, row_on_device)) return rc;
+    if (in_pos) if (int rc = sparse_dest(c, in_pos, pos_on_device)) return rc;
+    const uint64_t nc = c->sp.cols, edges = c->sb.edges;
+    if (!nc) { // (nothing is built or launched: the one offset)
+        if (in_ptr) { if (ptr_on_device) HIPCHK(c, hipMemsetAsync(in_ptr, 0, 8, c->stream)); else in_ptr[0] = 0; }
+        return held_call_end(c, "subgraph transpose fetch", false);
+    }
+    bool built_now = false;
+    if (int rc = drop_pairs_unless_ok(c, subt_ensure(c, built_now))) return rc;
+    const SubProp &p = c->sb.prop;
+    if (in_ptr) HIPCHK(c, hipMemcpyAsync(in_ptr, p.d_in_ptr.get(), ((size_t)nc + 1) * 8, hipMemcpyDefault, c->stream));
+    if (in_row && edges) HIPCHK(c, hipMemcpyAsync(in_row, p.d_in_row.get(), (size_t)edges * 4, hipMemcpyDefault, c->stream));
+    if (in_pos && edges) HIPCHK(c, hipMemcpyAsync(in_pos, p.d_in_pos.get(), (size_t)edges * 8, hipMemcpyDefault, c->stream));
+    return held_call_end(c, "subgraph transpose fetch", false);
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

@@ -91,8 +91,9 @@ __device__ __forceinline__ double prop_widen(const PropRaw<ET, V> &r, int v) {
 // WSRC (PROPAGATE WITH VALUES): where an entry's weight comes from -- PROP_W_FIX: its held word (the two kernels above, which
 // compile to what they were before the parameter existed); PROP_W_VALUES: the caller's values[e], e the entry's place in the
 // list (the forward product); PROP_W_POS: values[pos[p]], pos the held place of transposed entry p.  VAL64: values are f64,
-// else f32 widened exactly.  With values no word is read and no word sum is made.
-enum : int { PROP_W_FIX = 0, PROP_W_VALUES = 1, PROP_W_POS = 2 };
+// else f32 widened exactly.  With values no word is read and no word sum is made.  PROP_W_ONE: every weight is exactly 1.0 and
+// nothing is read for it (SUBGRAPH PRODUCTS without values, fora_subgraph_prop.h).
+enum : int { PROP_W_FIX = 0, PROP_W_VALUES = 1, PROP_W_POS = 2, PROP_W_ONE = 3 };
 template <int ET, int V, bool TNORM, int WSRC = PROP_W_FIX, bool VAL64 = false>
 __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t nseg, const int32_t *ids, const uint64_t *fix, const void *feat,
                                                  int64_t ldf, uint32_t d, uint32_t G, double *part, uint64_t *segsum, const uint64_t *rsum,
@@ -120,6 +121,9 @@ __device__ __forceinline__ void prop_gather_body(const PropSeg *segs, uint64_t n
                 ssum += f;
                 w_l = fix2d(f);
                 if constexpr (TNORM) w_l = w_l / fix2d(rsum[id_l]);
+            } else if constexpr (WSRC == PROP_W_ONE) {
+                id_l = ids[first + base + gl];
+                w_l = 1.0;
             } else {
                 id_l = ids[first + base + gl];
                 int64_t at = first + base + gl;
@@ -196,9 +200,12 @@ __global__ void __launch_bounds__(BLOCK) k_prop_gather_vals(const PropSeg *segs,
 // sum) of the row that the chunk before cut / that this chunk cuts -- two buffers that swap from chunk to chunk, since the
 // row that reads one and the row that writes one are different lanes.  segsum null: no normalisation.  out32 / out64:
 // either may be null; each has its own pitch (a staged output is dense, the caller's device memory has the caller's ldo).
+// MEAN (SUBGRAPH PRODUCTS, FORA_SUB_MEAN): the finished sum of row r divided once by its number of terms,
+// mean_ptr[r + 1] - mean_ptr[r] (the records of such a plan have entries); without it mean_ptr is not read.
+template <bool MEAN = false>
 __global__ void __launch_bounds__(BLOCK) k_prop_combine(const PropRowRec *recs, uint64_t nrec, uint32_t d, uint32_t rpb, const double *part, const uint64_t *segsum,
                                                         const double *carry_in, double *carry_out, const uint64_t *scarry_in, uint64_t *scarry_out,
-                                                        float *out32, int64_t ld32, double *out64, int64_t ld64) {
+                                                        float *out32, int64_t ld32, double *out64, int64_t ld64, const int64_t *mean_ptr) {
 #pragma clang fp contract(off)
     const uint32_t rl = rpb > 1 ? threadIdx.x / d : 0u;
     const uint32_t c = rpb > 1 ? threadIdx.x - rl * d : blockIdx.x * BLOCK + threadIdx.x;
@@ -220,6 +227,10 @@ __global__ void __launch_bounds__(BLOCK) k_prop_combine(const PropRowRec *recs, 
             continue;
         }
         if (segsum && S) acc = acc / fix2d(S);
+        if constexpr (MEAN) {
+            const int64_t terms = mean_ptr[r.row + 1] - mean_ptr[r.row];
+            if (terms > 0) acc = acc / (double)terms;
+        }
         if (out64) out64[(int64_t)r.row * ld64 + c] = acc;
         if (out32) out32[(int64_t)r.row * ld32 + c] = (float)acc;
     }

@@ -7,7 +7,9 @@ the library and torch share one HIP runtime.  fora_amd/__init__.py does not impo
 Wherever an operand or a gradient below has n rows, n is the engine's held column count (Engine.held_cols): the nodes of the
 graph, or, after Engine.sparse_compact / store_take_compact, the nc nodes `cols` that the held rows touch -- pass X[cols] and
 autograd carries the gradient back through that index.  A compaction between a forward and its backward pass makes the
-backward pass raise, like any other change of the held rows."""
+backward pass raise, like any other change of the held rows.
+subgraph_propagate is message passing over the graph's own edges among those nc nodes (Engine.sparse_subgraph): A_S x X and
+A_S^T x X, each the other's gradient."""
 import torch
 
 
@@ -134,6 +136,60 @@ def ppr_propagate(engine, row_ptr, H, normalize=False, values=None):
     if normalize:
         raise ValueError("ppr_propagate: normalize and values exclude each other (a division is the caller's: see row_softmax)")
     return _PprPropagateValues.apply(H, values, engine, row_ptr)
+
+
+class _SubgraphPropagate(torch.autograd.Function):
+    """Y = A_S x X (transposed: A_S^T x X) over the held subgraph; dX = the opposite product of G, after G's rows were divided
+    by the forward counts when the forward call took the mean"""
+
+    @staticmethod
+    def forward(ctx, X, engine, values, mean, transposed):
+        fwd = engine.subgraph_propagate_t if transposed else engine.subgraph_propagate
+        out32, _, _ = fwd(X.detach(), values=values, mean=mean, want32=True, want64=False)
+        ctx.engine, ctx.values, ctx.mean, ctx.transposed, ctx.dtype = engine, values, mean, transposed, X.dtype
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "subgraph_propagate")
+        G = _dense_operand(G)
+        if ctx.mean:
+            cnt = engine.subgraph_degrees(transposed=ctx.transposed, device=True).clamp(min=1)
+            G = (G.to(torch.float64) / cnt.to(torch.float64)[:, None]).to(torch.float32)
+        bwd = engine.subgraph_propagate if ctx.transposed else engine.subgraph_propagate_t
+        out32, _, _ = bwd(G, values=ctx.values, want32=True, want64=False)
+        return (out32 if ctx.dtype == torch.float32 else out32.to(ctx.dtype)), None, None, None, None
+
+
+def subgraph_propagate(engine, X, values=None, norm=None, direction="out"):
+    """One message-passing step over the subgraph `engine` holds (Engine.sparse_subgraph) as a differentiable torch operation.
+    X: [nc, d] (nc = engine.held_cols) float32, bfloat16 or float16 on the engine's GPU (or FP8 as a constant: one that requires
+    grad is a ValueError), column stride one element.  direction "out": Y = A_S x X, every node sums its out-neighbours inside
+    the batch (Engine.subgraph_propagate); "in": Y = A_S^T x X, its in-neighbours (Engine.subgraph_propagate_t).  Returns Y
+    [nc, d] float32 on the device; the backward pass is the opposite call on the gradient G, so X.grad has defined bits too.
+    values: one float32 or float64 per edge of the subgraph in the order of sub_col (a tensor on the device or a numpy array),
+    used as the weights in both passes; it is a constant here -- a values tensor that requires grad is a ValueError (its
+    gradient is an SDDMM over the subgraph's edges, which the library does not have yet).
+    norm="mean" (not together with values): every output row is divided by the number of its terms.  The backward pass is
+    then DEFINED as this composition: count_j = the number of terms of forward row j (at least 1), G'[j] =
+    float32(float64(G[j]) / float64(count_j)) in torch, X.grad = the plain (unit-weight, no mean) opposite product of G'.
+    The subgraph must still be held when the backward pass runs: a call that replaces or clears the held rows in between
+    makes it raise."""
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_propagate: direction is "out" or "in"')
+    if norm not in (None, "mean"):
+        raise ValueError('subgraph_propagate: norm is None or "mean"')
+    _refuse_fp8_grad("subgraph_propagate", X=X)
+    if torch.is_tensor(values):
+        if values.requires_grad:
+            raise ValueError("subgraph_propagate: values is a constant here; a values tensor that requires grad is not supported "
+                             "(its gradient is an SDDMM over the subgraph's edges)")
+        values = _entry_values(values.detach())
+    if norm == "mean" and values is not None:
+        raise ValueError("subgraph_propagate: norm and values exclude each other (pass the normalisation as values)")
+    return _SubgraphPropagate.apply(X, engine, values, norm == "mean", direction == "in")
 
 
 def ppr_sddmm(engine, row_ptr, A, B):
