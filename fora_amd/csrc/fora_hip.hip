@@ -3492,6 +3492,8 @@ int fora_hip_get_option(fora_ctx *c, const char *name, int64_t *value) {
     if (!strcmp(name, "sparse_cols")) { *value = (int64_t)held_cols(c); return FORA_OK; }           // the columns of the calls on the held rows: n, or nc while a compacted result is held (COLUMNS)
     if (!strcmp(name, "sub_edges")) { *value = c->sp.valid && c->sp.compacted && c->sb.valid ? (int64_t)c->sb.edges : -1; return FORA_OK; } // the edges of the held subgraph (SUBGRAPH); -1: none is held
     if (!strcmp(name, "team_members")) { *value = c->g.team.T; return FORA_OK; }                      // 0: this graph / workspace has no team push
+    if (!strcmp(name, "team_local_ids")) { *value = c->g.team.T ? c->g.team.R : 0; return FORA_OK; }   // R of the built team tables: local ids per member (0: no team push)
+    if (!strcmp(name, "team_hub_sums")) { *value = c->g.team.T ? c->g.team.H : 0; return FORA_OK; }    // their H: hub sums per member, after the cut to the free LDS (0: none, or no team push)
     if (!strcmp(name, "walk_dg_wgs_per_cu")) { // k_walk_dg's resident workgroups per CU at this graph's tables (0: the graph has no degree-grouped copy)
         const WalkDG &g = c->g.walk.dg;
         int wgs = 0;

@@ -280,7 +280,7 @@ static void check_team(const Csr &g, uint32_t force, uint32_t max_members, uint3
         R = std::max(64u, (*std::max_element(share.begin(), share.end()) + 63) / 64 * 64);
         if (R <= TEAM_R_CAP) break;
     }
-    std::printf("team_T=%u ", t.T);
+    std::printf("team_T=%u team_R_cap=%u ", t.T, TEAM_R_CAP);
     if (!T) { CHECK(t.T == 0 && t.colt.empty() && t.off.empty(), "team: no tables when no member count within max_members fits"); return; }
     CHECK(t.T == T && t.R == R, "team: T is the smallest power of two >= force whose largest share, rounded to 64, is <= TEAM_R_CAP");
     CHECK(T <= (uint32_t)TEAM_MAX && R <= (1u << TEAM_LBITS) && n <= (1u << 19), "team: owner, local id and node fit their fields");
