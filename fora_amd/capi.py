@@ -247,6 +247,14 @@ ABI_GNN = _rows(_ABI_GNN)
 GNN_SYMBOLS = list(ABI_GNN)
 SUB_MEAN = 1  # FORA_SUB_MEAN
 
+# the entry point of include/fora_hip_edge.h, scores per edge of the held subgraph: a fourth table of the same syntax (the
+# censuses of the three headers above are pinned); tests/test_subgraph_sddmm_cpu.py derives it from that header again
+_ABI_EDGE = """
+int  fora_hip_subgraph_sddmm(ctx*, ptr, int, int64, ptr, int, int64, int, int, ptr, ptr, uint64, ptr, ptr)
+"""
+ABI_EDGE = _rows(_ABI_EDGE)
+EDGE_SYMBOLS = list(ABI_EDGE)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -284,7 +292,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -656,6 +664,40 @@ class Engine:
         the edge's place in sub_col; mean divides by a column's number of edges.  Operands, outputs and stats as for
         subgraph_propagate; the first transposed call on a held subgraph builds its transposition (stats["built"] == 1)."""
         return self._subgraph_product(self._lib.fora_hip_subgraph_propagate_t, "subgraph_propagate_t", G, values, mean, want32, want64, out32, out64, bf16)
+
+    # ---- scores per edge of the held subgraph (the EDGE SCORES contract of include/fora_hip_edge.h)
+    def subgraph_sddmm(self, a, b, heads=1, want32=True, want64=False, out32=None, out64=None, a_bf16=False, b_bf16=False):
+        """score[h, e] = <a[row of e], b[sub_col[e]]> over the columns [h * d, (h + 1) * d) for every edge e of the held
+        subgraph and every head h (fora_hip_subgraph_sddmm, the EDGE SCORES contract of include/fora_hip_edge.h): the order of
+        additions of sparse_sddmm inside the head's slice, every bit defined, all heads in one launch.  a, b: [nc, heads * d]
+        (nc = held_cols), each a numpy array or a torch tensor on the context's GPU with the conventions of sparse_sddmm's
+        operands (a_bf16 / b_bf16: True, "bf16", "e4m3", "e5m2" for numpy codes); the two may differ in type and in where
+        they live.  Returns (out32 or None, out64 or None, stats dict): float32 / float64 [heads, edges] -- row h is the
+        contiguous per-edge array that values= of subgraph_propagate takes -- torch tensors on the device when a or b is a
+        torch tensor, numpy arrays otherwise; out32 / out64: caller-made contiguous outputs of heads * edges elements to
+        fill instead (any shape), each a numpy array or a torch tensor on the GPU.  The weight gradient of
+        subgraph_propagate(X, values=w) is subgraph_sddmm(G, X); of subgraph_propagate_t it is subgraph_sddmm(X, G).
+        stats: edges, workgroups, a_on_device, b_on_device, sddmm_ms."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_sddmm: no subgraph is held (sparse_subgraph first)")
+        heads = int(heads)
+        shape = "[nc, heads * d] (nc: the held columns)"
+        aptr, atype, wa, lda, a_dev, _ka = self._prop_feat(a, a_bf16, rows=nc, name="a", shape=shape)
+        bptr, btype, wb, ldb, b_dev, _kb = self._prop_feat(b, b_bf16, rows=nc, name="b", shape=shape)
+        if wb != wa or heads < 1 or wa % heads:
+            raise ValueError("a and b must have the same number of columns, and heads (at least 1) must divide it")
+        for o in (out32, out64):
+            if o is not None and not (o.is_contiguous() if self._is_torch(o) else o.flags.c_contiguous):
+                raise ValueError("out32 / out64 must be contiguous")
+        flat32 = out32.reshape(-1) if out32 is not None else None          # (views: the call fills the caller's memory)
+        flat64 = out64.reshape(-1) if out64 is not None else None
+        flat32, flat64, p32, p64, cap = self._entry_outputs(heads * edges, a_dev or b_dev, want32, want64, flat32, flat64)
+        info, ms = (C.c_int64 * 4)(), C.c_double(0)
+        self._chk(self._lib.fora_hip_subgraph_sddmm(self._ctx, aptr, atype, lda, bptr, btype, ldb, wa // heads, heads, p32, p64, cap, info, C.byref(ms)))
+        shaped = lambda o: o if o is None else o[:heads * edges].reshape(heads, edges)
+        return shaped(flat32), shaped(flat64), {"edges": int(info[0]), "workgroups": int(info[1]), "a_on_device": int(info[2]),
+                                                "b_on_device": int(info[3]), "sddmm_ms": ms.value}
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -22,7 +22,8 @@
 #include "fora_cols.h"
 #include "fora_subgraph.h"
 #include "fora_subgraph_prop.h"
-#include "../../include/fora_hip_gnn.h"
+#include "fora_subgraph_sddmm.h"
+#include "../../include/fora_hip_edge.h"
 
 #include <algorithm>
 #include <cassert>
@@ -45,7 +46,7 @@ namespace {
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
               EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
-              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG };
+              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -474,7 +475,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -1056,6 +1057,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SUBP_T: t.subp_t_ms += ms; break;             // the transposition of the held subgraph: ms_out[0] of the SUBGRAPH PRODUCTS calls only
         case EV_SUBP_SHORT: t.subp_short_ms += ms; break;     // k_sub_agg: ms_out[1] of those calls only
         case EV_SUBP_LONG: t.subp_long_ms += ms; break;       // the gather and combine launches of their long rows: ms_out[2] only
+        case EV_SUB_SDDMM: t.sub_sddmm_ms += ms; break;       // k_sub_sddmm: ms_out of fora_hip_subgraph_sddmm only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -4427,6 +4429,62 @@ int fora_hip_subgraph_transpose_fetch(fora_ctx *c, int64_t *in_ptr, int32_t *in_
     if (in_row && edges) HIPCHK(c, hipMemcpyAsync(in_row, p.d_in_row.get(), (size_t)edges * 4, hipMemcpyDefault, c->stream));
     if (in_pos && edges) HIPCHK(c, hipMemcpyAsync(in_pos, p.d_in_pos.get(), (size_t)edges * 8, hipMemcpyDefault, c->stream));
     return held_call_end(c, "subgraph transpose fetch", false);
+}
+
+// ---- EDGE SCORES (the contract of include/fora_hip_edge.h; the kernel in fora_subgraph_sddmm.h).  No plan, no table, nothing kept:
+// the kernel finds the rows of its edges in sub_ptr itself.
+namespace {
+// nc > 0 and edges > 0; the arguments have passed fora_hip_subgraph_sddmm
+int subgraph_sddmm_impl(fora_ctx *c, const void *a_, int a_type, int64_t lda, const void *b_, int b_type, int64_t ldb, int d, int heads,
+                        float *out32, double *out64, int64_t *info_out, double *ms_out) {
+    const SubBufs &sb = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = sb.edges, width = (uint64_t)heads * (uint64_t)d;
+    HeldIn a = HeldIn::matrix(a_, nc, lda, width, elt_bytes(a_type)), b = HeldIn::matrix(b_, nc, ldb, width, elt_bytes(b_type));
+    HeldOut<float> o32 = HeldOut<float>::vector(out32, (uint64_t)heads * edges);
+    HeldOut<double> o64 = HeldOut<double>::vector(out64, (uint64_t)heads * edges);
+    if (int rc = held_resolve(c, a, b, o32, o64)) return rc;
+    // ---- every buffer of the call before the launch: a call that finds no room has written nothing
+    if (int rc = a.stage(c, pb.d_a, "the upload of a")) return rc;
+    if (int rc = b.stage(c, pb.d_feat, "the upload of b")) return rc;
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    c->tm.sub_sddmm_ms = 0;
+    const uint64_t spans = (edges + SUBS_SPAN - 1) / SUBS_SPAN;
+    const uint64_t wgs = (spans + SUBS_WAVES - 1) / SUBS_WAVES;
+    if (wgs > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph sddmm: more edges than one launch takes"); // (2^39 edges: no memory holds their sub_col)
+    const unsigned grid = (unsigned)wgs;
+    {
+        EvSpan ev(c, EV_SUB_SDDMM);
+        with_elt_pair(a_type, b_type, [&](auto A, auto B) {
+            hipLaunchKernelGGL((k_sub_sddmm<A.value, B.value>), dim3(grid), dim3(BLOCK), 0, c->stream, (const int64_t *)sb.d_ptr.get(), (uint32_t)nc,
+                               (const int32_t *)sb.d_col.get(), edges, a.ptr(), lda, b.ptr(), ldb, (uint32_t)d, (uint32_t)heads, prop_group_lg((uint32_t)d),
+                               o32.ptr(), o64.ptr(), sddmm_types(a_type, b_type));
+        });
+    }
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, "subgraph sddmm")) return rc;
+    if (info_out) { info_out[0] = (int64_t)edges; info_out[1] = (int64_t)grid; info_out[2] = a.on_device(); info_out[3] = b.on_device(); }
+    if (ms_out) ms_out[0] = c->tm.sub_sddmm_ms;
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_sddmm(fora_ctx *c, const void *a, int a_type, int64_t lda, const void *b, int b_type, int64_t ldb, int d, int heads,
+                            float *out32, double *out64, uint64_t ocap, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, "subgraph sddmm: no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(a_type) || !elt_known(b_type)) return fail(c, FORA_E_ARG, "subgraph sddmm: unknown a_type or b_type");
+    if (d < 1 || heads < 1 || (int64_t)d * (int64_t)heads > 65536) return fail(c, FORA_E_ARG, "subgraph sddmm: d or heads below 1, or heads * d above 65536");
+    if (lda < (int64_t)d * heads || ldb < (int64_t)d * heads) return fail(c, FORA_E_ARG, "subgraph sddmm: a leading dimension smaller than heads * d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, "subgraph sddmm: no output");
+    if (ocap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, "subgraph sddmm: ocap is smaller than heads * edges");
+    if (info_out) { memset(info_out, 0, 4 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = 0;
+    if (!c->sp.cols || !c->sb.edges) return FORA_OK; // (no edge: nothing launched or written)
+    if (!a || !b) return fail(c, FORA_E_ARG, "subgraph sddmm: null a or b");
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_sddmm_impl(c, a, a_type, lda, b, b_type, ldb, d, heads, out32, out64, info_out, ms_out));
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

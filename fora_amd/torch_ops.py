@@ -9,7 +9,9 @@ graph, or, after Engine.sparse_compact / store_take_compact, the nc nodes `cols`
 autograd carries the gradient back through that index.  A compaction between a forward and its backward pass makes the
 backward pass raise, like any other change of the held rows.
 subgraph_propagate is message passing over the graph's own edges among those nc nodes (Engine.sparse_subgraph): A_S x X and
-A_S^T x X, each the other's gradient."""
+A_S^T x X, each the other's gradient.  subgraph_sddmm scores every edge of that subgraph, all heads in one call, and
+subgraph_propagate_values is the product with learnable edge weights: the scores and the two products are each other's
+gradients, as ppr_sddmm and ppr_propagate(values=) are on the held rows."""
 import torch
 
 
@@ -171,7 +173,7 @@ def subgraph_propagate(engine, X, values=None, norm=None, direction="out"):
     [nc, d] float32 on the device; the backward pass is the opposite call on the gradient G, so X.grad has defined bits too.
     values: one float32 or float64 per edge of the subgraph in the order of sub_col (a tensor on the device or a numpy array),
     used as the weights in both passes; it is a constant here -- a values tensor that requires grad is a ValueError (its
-    gradient is an SDDMM over the subgraph's edges, which the library does not have yet).
+    gradient is an SDDMM over the subgraph's edges: subgraph_propagate_values is the product with learnable weights).
     norm="mean" (not together with values): every output row is divided by the number of its terms.  The backward pass is
     then DEFINED as this composition: count_j = the number of terms of forward row j (at least 1), G'[j] =
     float32(float64(G[j]) / float64(count_j)) in torch, X.grad = the plain (unit-weight, no mean) opposite product of G'.
@@ -185,11 +187,107 @@ def subgraph_propagate(engine, X, values=None, norm=None, direction="out"):
     if torch.is_tensor(values):
         if values.requires_grad:
             raise ValueError("subgraph_propagate: values is a constant here; a values tensor that requires grad is not supported "
-                             "(its gradient is an SDDMM over the subgraph's edges)")
+                             "(its gradient is an SDDMM over the subgraph's edges: call subgraph_propagate_values)")
         values = _entry_values(values.detach())
     if norm == "mean" and values is not None:
         raise ValueError("subgraph_propagate: norm and values exclude each other (pass the normalisation as values)")
     return _SubgraphPropagate.apply(X, engine, values, norm == "mean", direction == "in")
+
+
+def _as_leaf_dtype(g, X):
+    return g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+
+
+class _SubgraphSddmm(torch.autograd.Function):
+    """scores[h] = sddmm over the subgraph's edges of the head's column slices of A and B; per head, with g_h the gradient of
+    its scores as values: dA[:, slice] = A_S(g_h) x B[:, slice], dB[:, slice] = A_S(g_h)^T x A[:, slice], written in place"""
+
+    @staticmethod
+    def forward(ctx, A, B, engine, heads):
+        out32, _, _ = engine.subgraph_sddmm(A.detach(), B.detach(), heads=heads, want32=True, want64=False)
+        ctx.save_for_backward(A, B)
+        ctx.engine, ctx.heads = engine, heads
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, g):
+        A, B = ctx.saved_tensors
+        engine, heads = ctx.engine, ctx.heads
+        _held_guard(ctx.generation, engine, "subgraph_sddmm")
+        g = _entry_values(g)
+        d = A.shape[1] // heads
+        Ad, Bd = A.detach(), B.detach()
+        dA = torch.empty(A.shape, dtype=torch.float32, device=A.device) if ctx.needs_input_grad[0] else None
+        dB = torch.empty(B.shape, dtype=torch.float32, device=B.device) if ctx.needs_input_grad[1] else None
+        for h in range(heads):
+            cs = slice(h * d, (h + 1) * d)
+            if dA is not None:
+                engine.subgraph_propagate(Bd[:, cs], values=g[h], want64=False, out32=dA[:, cs])
+            if dB is not None:
+                engine.subgraph_propagate_t(Ad[:, cs], values=g[h], want64=False, out32=dB[:, cs])
+        return _as_leaf_dtype(dA, A), _as_leaf_dtype(dB, B), None, None
+
+
+def subgraph_sddmm(engine, A, B, heads=1):
+    """scores[h, e] = <A[row of e], B[sub_col[e]]> over the columns [h * d, (h + 1) * d) for every edge e of the subgraph
+    `engine` holds (Engine.subgraph_sddmm, the EDGE SCORES contract), float32 [heads, edges] on the device: edge gates, link
+    scores, the scores of an attention layer over the sampled graph.  A, B: [nc, heads * d] (nc = engine.held_cols) float32,
+    bfloat16 or float16 tensors on the engine's GPU (or FP8 as constants: one that requires grad is a ValueError), column
+    stride one element.  Differentiable in A and B: with g_h the gradient of head h's scores, A.grad[:, slice] =
+    A_S(g_h) x B[:, slice] and B.grad[:, slice] = A_S(g_h)^T x A[:, slice] -- the two subgraph products with values = g_h on
+    the head's column slice, written in place -- in the leaf's dtype.  The subgraph must still be held when the backward pass
+    runs."""
+    heads = int(heads)
+    if heads < 1 or A.dim() != 2 or A.shape[1] % heads:
+        raise ValueError("subgraph_sddmm: heads must be at least 1 and divide the columns of A and B")
+    _refuse_fp8_grad("subgraph_sddmm", A=A, B=B)
+    return _SubgraphSddmm.apply(A, B, engine, heads)
+
+
+class _SubgraphPropagateValues(torch.autograd.Function):
+    """Y = A_S(values) x X (transposed: A_S(values)^T x X); dX = the opposite product of G with the same values; dvalues =
+    subgraph_sddmm(G, X) (transposed: subgraph_sddmm(X, G)) -- the operand read at the edge's row comes first"""
+
+    @staticmethod
+    def forward(ctx, X, values, engine, transposed):
+        fwd = engine.subgraph_propagate_t if transposed else engine.subgraph_propagate
+        out32, _, _ = fwd(X.detach(), values=values.detach(), want32=True, want64=False)
+        ctx.save_for_backward(X, values)
+        ctx.engine, ctx.transposed = engine, transposed
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        X, values = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "subgraph_propagate_values")
+        G = _dense_operand(G)
+        dX = dv = None
+        if ctx.needs_input_grad[0]:
+            bwd = engine.subgraph_propagate if ctx.transposed else engine.subgraph_propagate_t
+            dX, _, _ = bwd(G, values=values.detach(), want32=True, want64=False)
+        if ctx.needs_input_grad[1]:
+            a, b = (X.detach(), G) if ctx.transposed else (G, X.detach())
+            dv, _, _ = engine.subgraph_sddmm(a, b, heads=1, want32=True, want64=False)
+            dv = dv[0]
+        return _as_leaf_dtype(dX, X), dv, None, None
+
+
+def subgraph_propagate_values(engine, X, values, direction="out"):
+    """subgraph_propagate with LEARNABLE edge weights: Y = A_S(values) x X (direction "out") or A_S(values)^T x X ("in") over
+    the subgraph `engine` holds, float32 [nc, d] on the device, differentiable in X and in values.  X: as for
+    subgraph_propagate.  values: a float32 tensor of one element per edge of the subgraph in the order of sub_col, on the
+    engine's GPU.  X.grad is the opposite product of the gradient G with the same values; values.grad[e] =
+    <G[row of e], X[sub_col[e]]> for "out" and <X[row of e], G[sub_col[e]]> for "in" (Engine.subgraph_sddmm with the operands
+    in that order), float32, every bit defined.  The subgraph must still be held when the backward pass runs."""
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_propagate_values: direction is "out" or "in"')
+    if not torch.is_tensor(values) or values.dtype != torch.float32 or values.dim() != 1:
+        raise ValueError("subgraph_propagate_values: values is a float32 tensor of one element per edge")
+    _refuse_fp8_grad("subgraph_propagate_values", X=X)
+    return _SubgraphPropagateValues.apply(X, values, engine, direction == "in")
 
 
 def ppr_sddmm(engine, row_ptr, A, B):
