@@ -255,6 +255,16 @@ int  fora_hip_subgraph_sddmm(ctx*, ptr, int, int64, ptr, int, int64, int, int, p
 ABI_EDGE = _rows(_ABI_EDGE)
 EDGE_SYMBOLS = list(ABI_EDGE)
 
+# the entry points of include/fora_hip_edge_softmax.h, the softmax over each node's edges of the held subgraph: a fifth table
+# (the censuses of the four headers above are pinned); tests/test_subgraph_softmax_cpu.py derives it from that header again
+_ABI_EDGE_SOFTMAX = """
+int  fora_hip_subgraph_softmax(ctx*, ptr, int, int, double, int, ptr, ptr, uint64, ptr, ptr)
+int  fora_hip_subgraph_softmax_bwd(ctx*, ptr, int, ptr, int, int, double, int, ptr, ptr, uint64, ptr, ptr)
+"""
+ABI_EDGE_SOFTMAX = _rows(_ABI_EDGE_SOFTMAX)
+EDGE_SOFTMAX_SYMBOLS = list(ABI_EDGE_SOFTMAX)
+SUB_BY_COL = 2  # FORA_SUB_BY_COL
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -292,7 +302,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -698,6 +708,60 @@ class Engine:
         shaped = lambda o: o if o is None else o[:heads * edges].reshape(heads, edges)
         return shaped(flat32), shaped(flat64), {"edges": int(info[0]), "workgroups": int(info[1]), "a_on_device": int(info[2]),
                                                 "b_on_device": int(info[3]), "sddmm_ms": ms.value}
+
+    # ---- softmax over each node's edges of the held subgraph (the EDGE SOFTMAX contract of include/fora_hip_edge_softmax.h)
+    def _edge_operand(self, x, edges, name):
+        """(pointer, element type, on_device, heads, keep-alive) of a [heads, edges] operand of the EDGE SOFTMAX calls: float32
+        or float64, a numpy array or a torch tensor on the context's GPU, read in place when it is contiguous"""
+        if getattr(x, "ndim", 0) != 2 or x.shape[0] < 1 or x.shape[1] != edges:
+            raise ValueError(f"{name} must be [heads, edges] with at least one head")
+        flat = (x.detach().contiguous() if self._is_torch(x) else np.ascontiguousarray(x)).reshape(-1)
+        ptr, et, on_dev, keep = self._entry_operand(flat, flat.shape[0], name)
+        return ptr, et, on_dev, int(x.shape[0]), keep
+
+    def _subgraph_softmax(self, who, operands, scale, by, want32, want64, out32, out64):
+        edges = self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, f"{who}: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError(f'{who}: by is "row" or "col"')
+        ops = [self._edge_operand(x, edges, name) for name, x in operands]
+        heads = ops[0][3]
+        if any(o[3] != heads for o in ops):
+            raise ValueError(f"{who}: y and g must have the same number of heads")
+        for o in (out32, out64):
+            if o is not None and not (o.is_contiguous() if self._is_torch(o) else o.flags.c_contiguous):
+                raise ValueError("out32 / out64 must be contiguous")
+        flat32 = out32.reshape(-1) if out32 is not None else None          # (views: the call fills the caller's memory)
+        flat64 = out64.reshape(-1) if out64 is not None else None
+        flat32, flat64, p32, p64, cap = self._entry_outputs(heads * edges, any(o[2] for o in ops), want32, want64, flat32, flat64)
+        info, ms = (C.c_int64 * 4)(), (C.c_double * 2)()
+        args = [a for o in ops for a in o[:2]]
+        fn = getattr(self._lib, "fora_hip_" + who)
+        self._chk(fn(self._ctx, *args, heads, float(scale), SUB_BY_COL if by == "col" else 0, p32, p64, cap, info, ms))
+        shaped = lambda o: o if o is None else o[:heads * edges].reshape(heads, edges)
+        return shaped(flat32), shaped(flat64), {"edges": int(info[0]), "long_groups": int(info[1]), "nan_groups": int(info[2]), "built": int(info[3]),
+                                                "short_ms": ms[0], "long_ms": ms[1]}
+
+    def subgraph_softmax(self, scores, scale=1.0, by="row", want32=True, want64=False, out32=None, out64=None):
+        """y[h, e] = the softmax of scores[h, e] * scale inside the group of edge e of the held subgraph, head by head
+        (fora_hip_subgraph_softmax, the EDGE SOFTMAX contract of include/fora_hip_edge_softmax.h): by="row" a group is the edges
+        of a row (a node's out-edges, what subgraph_propagate sums over), by="col" the edges of a column (its in-edges, what
+        subgraph_propagate_t sums over; the first such call builds the transposition, stats["built"] == 1).  Per head and
+        group the bits are sparse_softmax's.  scores: [heads, edges] float32 or float64 in the order of sub_col -- what
+        subgraph_sddmm returns -- a numpy array or a torch tensor on the context's GPU.  Returns (out32 or None, out64 or None,
+        stats dict): [heads, edges], row h what values= of the subgraph products takes; torch tensors on the device when scores
+        is one; out32 / out64: caller-made contiguous outputs of heads * edges elements to fill instead.  A (group, head) with a
+        NaN, with +inf, or of -inf only becomes NaN (stats["nan_groups"]).  stats: edges, long_groups, nan_groups, built,
+        short_ms, long_ms."""
+        return self._subgraph_softmax("subgraph_softmax", [("scores", scores)], scale, by, want32, want64, out32, out64)
+
+    def subgraph_softmax_bwd(self, y, g, scale=1.0, by="row", want32=True, want64=False, out32=None, out64=None):
+        """dx[h, e] = ((g[h, e] - D) * y[h, e]) * scale with D = the group's sum of y * g in the contract's order
+        (fora_hip_subgraph_softmax_bwd): the gradient of subgraph_softmax with respect to scores, y its output, scale and by
+        its arguments.  y and g: [heads, edges], float32 or float64 each, numpy or torch on the GPU; outputs as for
+        subgraph_softmax (torch when either input is)."""
+        return self._subgraph_softmax("subgraph_softmax_bwd", [("y", y), ("g", g)], scale, by, want32, want64, out32, out64)
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -23,7 +23,8 @@
 #include "fora_subgraph.h"
 #include "fora_subgraph_prop.h"
 #include "fora_subgraph_sddmm.h"
-#include "../../include/fora_hip_edge.h"
+#include "fora_subgraph_softmax.h"
+#include "../../include/fora_hip_edge_softmax.h"
 
 #include <algorithm>
 #include <cassert>
@@ -46,7 +47,7 @@ namespace {
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
               EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
-              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM };
+              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -432,6 +433,9 @@ struct SubProp {
         bool planned = false; uint32_t cap = 0; uint64_t per = 0; // the key of the plan
         SubSplit split; PropPlan plan;                      // (host: the chunks sequence the launches)
         DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;
+        // EDGE SOFTMAX: the segments of the groups longer than sm_cap (the long list of softmax_lists), made under a value of "softmax_short"
+        bool sm_listed = false; uint32_t sm_cap = 0; uint64_t sm_short = 0, sm_long = 0, sm_nseg = 0; // (sm_short: the non-empty groups of at most sm_cap entries)
+        DevBuf<PropSeg> d_sm_segs;
     } fwd, tr;
     bool t_built = false;
     DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row; // [nc + 1], [edges], [edges]: the entries column by column
@@ -475,7 +479,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -1058,6 +1062,8 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SUBP_SHORT: t.subp_short_ms += ms; break;     // k_sub_agg: ms_out[1] of those calls only
         case EV_SUBP_LONG: t.subp_long_ms += ms; break;       // the gather and combine launches of their long rows: ms_out[2] only
         case EV_SUB_SDDMM: t.sub_sddmm_ms += ms; break;       // k_sub_sddmm: ms_out of fora_hip_subgraph_sddmm only
+        case EV_SUB_SMAX_SHORT: t.sub_smax_short_ms += ms; break; // k_sub_softmax / _bwd: ms_out[0] of the EDGE SOFTMAX calls only
+        case EV_SUB_SMAX_LONG: t.sub_smax_long_ms += ms; break;   // the k_sub_softmax_seg_* / _div launches of their longer groups: ms_out[1] only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -4485,6 +4491,147 @@ int fora_hip_subgraph_sddmm(fora_ctx *c, const void *a, int a_type, int64_t lda,
     if (!a || !b) return fail(c, FORA_E_ARG, "subgraph sddmm: null a or b");
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, subgraph_sddmm_impl(c, a, a_type, lda, b, b_type, ldb, d, heads, out32, out64, info_out, ms_out));
+}
+
+// ---- EDGE SOFTMAX (the contract of include/fora_hip_edge_softmax.h; the kernels in fora_subgraph_softmax.h).  The short path plans
+// nothing; the segment list of the longer groups is made from the side's host offsets once per held subgraph, side and cap.
+static_assert((FORA_SUB_BY_COL & FORA_SUB_MEAN) == 0, "FORA_SUB_BY_COL is a bit FORA_SUB_MEAN does not use");
+namespace {
+// the long list of a side under cap, on the device with the side: made when the key moves, kept otherwise
+int sub_side_softmax_list(fora_ctx *c, SubProp::Side &s, uint32_t cap) {
+    if (s.sm_listed && s.sm_cap == cap) return FORA_OK;
+    s.sm_listed = false;
+    const int nc = (int)c->sp.cols;
+    const int64_t *ptr = s.h_ptr.data();
+    const PropPlan plan = prop_plan_if(ptr, nc, 1ull << 62, [cap](int, uint64_t len) { return len > cap; }); // (one chunk: a slot is the place in the list)
+    const SoftmaxLists l = softmax_lists(plan.segs, ptr, cap); // (every segment is a longer group's: the long list alone)
+    uint64_t shrt = 0;
+    for (int i = 0; i < nc; i++) {
+        const uint64_t len = (uint64_t)(ptr[i + 1] - ptr[i]);
+        if (len && len <= cap) shrt++;
+    }
+    if (int rc = prop_ensure(c, s.d_sm_segs, l.segs.size(), "the longer groups' segment list")) return rc;
+    if (!l.segs.empty()) HIPCHK(c, hipMemcpy(s.d_sm_segs.get(), l.segs.data(), l.segs.size() * sizeof(PropSeg), hipMemcpyHostToDevice));
+    s.sm_cap = cap; s.sm_short = shrt; s.sm_long = l.long_rows; s.sm_nseg = l.n_long; s.sm_listed = true;
+    c->sb.prop_used = true;
+    return FORA_OK;
+}
+// what the launches of one call share.  ptr / pos: sub_ptr and null by row, in_ptr and in_pos by column
+struct SubSoftmaxWork {
+    const int64_t *ptr, *pos; uint32_t nc, cap; bool shrt; const PropSeg *segs; uint64_t nseg, edges; uint32_t heads; double scale;
+    double *seg_max, *part; uint32_t *nan_groups; float *o32; double *o64;
+    dim3 short_grid() const { return dim3((unsigned)(((uint64_t)nc + SSM_WAVES - 1) / SSM_WAVES)); }
+    dim3 long_grid() const { return dim3((unsigned)((nseg + SSM_WAVES - 1) / SSM_WAVES), std::min<uint32_t>(heads, 65535u)); }
+};
+extern "C++" { // (templates: this part of the file lies among the entry points)
+template <typename TS, bool BYCOL>
+void sub_softmax_launch(fora_ctx *c, const SubSoftmaxWork &w, const void *scores) {
+    const TS *x = (const TS *)scores;
+    if (w.shrt) {
+        EvSpan ev(c, EV_SUB_SMAX_SHORT);
+        hipLaunchKernelGGL((k_sub_softmax<TS, BYCOL>), w.short_grid(), dim3(BLOCK), 0, c->stream, w.ptr, w.nc, w.cap, w.pos, x, w.edges, w.heads, w.scale, w.o32, w.o64, w.nan_groups);
+    }
+    if (w.nseg) {
+        EvSpan ev(c, EV_SUB_SMAX_LONG);
+        hipLaunchKernelGGL((k_sub_softmax_seg_max<TS, BYCOL>), w.long_grid(), dim3(BLOCK), 0, c->stream, w.segs, w.nseg, w.pos, x, w.edges, w.heads, w.scale, w.seg_max);
+        hipLaunchKernelGGL((k_sub_softmax_seg_sum<TS, BYCOL>), w.long_grid(), dim3(BLOCK), 0, c->stream, w.segs, w.nseg, w.pos, x, w.edges, w.heads, w.scale,
+                           (const double *)w.seg_max, w.part);
+        hipLaunchKernelGGL((k_sub_softmax_div<TS, BYCOL>), w.long_grid(), dim3(BLOCK), 0, c->stream, w.segs, w.nseg, w.pos, x, w.edges, w.heads, w.scale,
+                           (const double *)w.seg_max, (const double *)w.part, w.o32, w.o64, w.nan_groups);
+    }
+}
+template <typename TY, typename TG, bool BYCOL>
+void sub_softmax_bwd_launch(fora_ctx *c, const SubSoftmaxWork &w, const void *y, const void *g) {
+    const TY *yy = (const TY *)y;
+    const TG *gg = (const TG *)g;
+    if (w.shrt) {
+        EvSpan ev(c, EV_SUB_SMAX_SHORT);
+        hipLaunchKernelGGL((k_sub_softmax_bwd<TY, TG, BYCOL>), w.short_grid(), dim3(BLOCK), 0, c->stream, w.ptr, w.nc, w.cap, w.pos, yy, gg, w.edges, w.heads, w.scale, w.o32, w.o64);
+    }
+    if (w.nseg) {
+        EvSpan ev(c, EV_SUB_SMAX_LONG);
+        hipLaunchKernelGGL((k_sub_softmax_bwd_seg_sum<TY, TG, BYCOL>), w.long_grid(), dim3(BLOCK), 0, c->stream, w.segs, w.nseg, w.pos, yy, gg, w.edges, w.heads, w.part);
+        hipLaunchKernelGGL((k_sub_softmax_bwd_div<TY, TG, BYCOL>), w.long_grid(), dim3(BLOCK), 0, c->stream, w.segs, w.nseg, w.pos, yy, gg, w.edges, w.heads, w.scale,
+                           (const double *)w.part, w.o32, w.o64);
+    }
+}
+} // extern "C++"
+// both calls: in = scores (forward) or y (backward), grad = g (backward).  nc > 0 and edges > 0; the arguments have passed sub_softmax_entry
+int subgraph_softmax_impl(fora_ctx *c, bool bwd, const void *in_, int in_type, const void *grad_, int g_type, int heads, double scale, bool by_col,
+                          float *out32, double *out64, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges, total = (uint64_t)heads * edges;
+    const bool in64 = in_type == FORA_PROP_F64, g64 = g_type == FORA_PROP_F64;
+    HeldIn in = HeldIn::vector(in_, total, in64 ? 8 : 4), grad = HeldIn::vector(grad_, total, g64 ? 8 : 4);
+    HeldOut<float> o32 = HeldOut<float>::vector(out32, total);
+    HeldOut<double> o64 = HeldOut<double>::vector(out64, total);
+    if (int rc = held_resolve(c, in, grad, o32, o64)) return rc; // (before anything is built)
+    c->tm.sub_smax_short_ms = c->tm.sub_smax_long_ms = 0;
+    bool built_now = false;
+    if (by_col) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &side = by_col ? sp.tr : sp.fwd;
+    const uint32_t cap = softmax_short_cap(c->opt_.softmax_short);
+    if (int rc = sub_side_ptr(c, side)) return rc;
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = sub_side_softmax_list(c, side, cap)) return rc;
+    const uint64_t nseg = side.sm_nseg;
+    if (nc + SSM_WAVES > 0x7FFFFFFFull || nseg + SSM_WAVES > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph softmax: more groups or segments than one launch takes");
+    if (int rc = in.stage(c, pb.d_vals, bwd ? "the upload of y" : "the upload of the scores")) return rc;
+    if (int rc = grad.stage(c, pb.d_a, "the upload of g")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)heads * (size_t)nseg, "the segment maxima and sums")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    const SubSoftmaxWork w{by_col ? sp.d_in_ptr.get() : b.d_ptr.get(), by_col ? sp.d_in_pos.get() : nullptr, (uint32_t)nc, cap, side.sm_short != 0,
+                           side.d_sm_segs.get(), nseg, edges, (uint32_t)heads, scale, pb.d_smax.get(), pb.d_smax.get() + (size_t)heads * (size_t)nseg,
+                           pb.d_smax_nan.get(), o32.ptr(), o64.ptr()};
+    uint32_t nan_groups = 0;
+    if (!bwd) HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+    with_bools(in64, by_col, [&](auto IN64, auto BYCOL) {
+        using TI = std::conditional_t<IN64.value, double, float>;
+        if (!bwd) sub_softmax_launch<TI, BYCOL.value>(c, w, in.ptr());
+        else if (g64) sub_softmax_bwd_launch<TI, double, BYCOL.value>(c, w, in.ptr(), grad.ptr());
+        else sub_softmax_bwd_launch<TI, float, BYCOL.value>(c, w, in.ptr(), grad.ptr());
+    });
+    if (!bwd) HIPCHK(c, hipMemcpyAsync(&nan_groups, pb.d_smax_nan.get(), sizeof(nan_groups), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = held_fetch(c, o32, o64)) return rc;
+    if (int rc = held_call_end(c, bwd ? "subgraph softmax_bwd" : "subgraph softmax")) return rc;
+    if (info_out) { info_out[0] = (int64_t)edges; info_out[1] = (int64_t)side.sm_long; info_out[2] = (int64_t)nan_groups; info_out[3] = built_now ? 1 : 0; }
+    if (ms_out) { ms_out[0] = c->tm.sub_smax_short_ms; ms_out[1] = c->tm.sub_smax_long_ms; }
+    return FORA_OK;
+}
+// the frame of the two calls (grad / g_type: the backward call's)
+int sub_softmax_entry(fora_ctx *c, bool bwd, const void *in, int in_type, const void *grad, int g_type, int heads, double scale, int flags,
+                      float *out32, double *out64, uint64_t ocap, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = bwd ? "subgraph softmax_bwd: " : "subgraph softmax: ";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (in_type != FORA_PROP_F32 && in_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + "an element type that is neither f32 nor f64");
+    if (bwd && g_type != FORA_PROP_F32 && g_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + "an element type that is neither f32 nor f64");
+    if (heads < 1) return fail(c, FORA_E_ARG, who + "heads below 1");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, who + "scale is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + "no output");
+    if (ocap / (uint64_t)heads < c->sb.edges || ocap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ocap is smaller than heads * edges");
+    if (info_out) { memset(info_out, 0, 4 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols || !c->sb.edges) return FORA_OK; // (no edge: nothing launched or written)
+    if (!in || (bwd && !grad)) return fail(c, FORA_E_ARG, who + "null operand");
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_softmax_impl(c, bwd, in, in_type, bwd ? grad : nullptr, g_type, heads, scale, (flags & FORA_SUB_BY_COL) != 0,
+                                                         out32, out64, info_out, ms_out));
+}
+} // namespace
+
+int fora_hip_subgraph_softmax(fora_ctx *c, const void *scores, int s_type, int heads, double scale, int flags, float *out32, double *out64, uint64_t ocap,
+                              int64_t *info_out, double *ms_out) {
+    return sub_softmax_entry(c, false, scores, s_type, nullptr, FORA_PROP_F32, heads, scale, flags, out32, out64, ocap, info_out, ms_out);
+}
+int fora_hip_subgraph_softmax_bwd(fora_ctx *c, const void *y, int y_type, const void *g, int g_type, int heads, double scale, int flags,
+                                  float *out32, double *out64, uint64_t ocap, int64_t *info_out, double *ms_out) {
+    return sub_softmax_entry(c, true, y, y_type, g, g_type, heads, scale, flags, out32, out64, ocap, info_out, ms_out);
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

@@ -11,7 +11,8 @@ backward pass raise, like any other change of the held rows.
 subgraph_propagate is message passing over the graph's own edges among those nc nodes (Engine.sparse_subgraph): A_S x X and
 A_S^T x X, each the other's gradient.  subgraph_sddmm scores every edge of that subgraph, all heads in one call, and
 subgraph_propagate_values is the product with learnable edge weights: the scores and the two products are each other's
-gradients, as ppr_sddmm and ppr_propagate(values=) are on the held rows."""
+gradients, as ppr_sddmm and ppr_propagate(values=) are on the held rows.  subgraph_edge_softmax is the softmax over each
+node's out- or in-edges between the two, and subgraph_attention composes the three."""
 import torch
 
 
@@ -288,6 +289,67 @@ def subgraph_propagate_values(engine, X, values, direction="out"):
         raise ValueError("subgraph_propagate_values: values is a float32 tensor of one element per edge")
     _refuse_fp8_grad("subgraph_propagate_values", X=X)
     return _SubgraphPropagateValues.apply(X, values, engine, direction == "in")
+
+
+class _SubgraphEdgeSoftmax(torch.autograd.Function):
+    """y = the softmax of scores * scale inside every group of the subgraph's edges (Engine.subgraph_softmax), y32 saved;
+    dscores = ((g - sum_group(y g)) y) scale (Engine.subgraph_softmax_bwd)"""
+
+    @staticmethod
+    def forward(ctx, scores, engine, scale, by):
+        s = scores.detach()
+        if s.dtype not in (torch.float32, torch.float64):
+            s = s.to(torch.float32)
+        y32, _, _ = engine.subgraph_softmax(s, scale=scale, by=by, want32=True, want64=False)
+        ctx.save_for_backward(y32)
+        ctx.engine, ctx.scale, ctx.by, ctx.dtype = engine, scale, by, scores.dtype
+        ctx.generation = engine.get_option("sparse_generation")
+        return y32
+
+    @staticmethod
+    def backward(ctx, g):
+        (y32,) = ctx.saved_tensors
+        _held_guard(ctx.generation, ctx.engine, "subgraph_edge_softmax")
+        dx, _, _ = ctx.engine.subgraph_softmax_bwd(y32, _entry_values(g), scale=ctx.scale, by=ctx.by, want32=True, want64=False)
+        return (dx if ctx.dtype == torch.float32 else dx.to(ctx.dtype)), None, None, None
+
+
+def subgraph_edge_softmax(engine, scores, scale=1.0, by="row"):
+    """softmax of scores * scale over each node's edges of the subgraph `engine` holds, head by head (Engine.subgraph_softmax,
+    the EDGE SOFTMAX contract: the defined exp and fixed order of ppr_row_softmax, every bit defined), float32 [heads, edges]
+    on the device.  scores: [heads, edges] in the order of sub_col -- what subgraph_sddmm returns -- a float32 or float64
+    tensor on the engine's GPU; the gradient comes back in its dtype.  by="row": over the out-edges of a node, the groups
+    subgraph_propagate_values(direction="out") sums over; by="col": over its in-edges, the groups of direction="in".  The
+    backward pass is Engine.subgraph_softmax_bwd on the saved float32 output.  scale is a number, not a differentiable
+    operand.  The subgraph must still be held when the backward pass runs."""
+    if by not in ("row", "col"):
+        raise ValueError('subgraph_edge_softmax: by is "row" or "col"')
+    if not torch.is_tensor(scores) or scores.dim() != 2:
+        raise ValueError("subgraph_edge_softmax: scores is a [heads, edges] tensor")
+    return _SubgraphEdgeSoftmax.apply(scores, engine, float(scale), by)
+
+
+def subgraph_attention(engine, Q, K, V, heads=1, scale=None, direction="out"):
+    """Attention over the sampled graph, every step a call of the library with defined bits: the composition of
+    subgraph_sddmm, subgraph_edge_softmax and, per head, subgraph_propagate_values -- no backward code of its own.
+    direction="out": node j attends over its out-edges, out[j] = sum over the edges e of row j of y[e] * V[sub_col[e]] with
+    y = softmax over the row of scale * <Q[j], K[sub_col[e]]>.  direction="in": node v attends over its in-edges, out[v] =
+    sum over the edges e with sub_col[e] == v of y[e] * V[row of e] with y = softmax over the column of scale *
+    <Q[v], K[row of e]> (the scores are subgraph_sddmm(K, Q): a is read at the edge's row).  Q, K: [nc, heads * d], V:
+    [nc, heads * dv], float32, bfloat16 or float16 tensors on the engine's GPU (FP8 as constants); scale: d ** -0.5 when
+    None.  Returns float32 [nc, heads * dv], differentiable in Q, K and V."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_attention: direction is "out" or "in"')
+    if heads < 1 or Q.dim() != 2 or V.dim() != 2 or Q.shape[1] % heads or V.shape[1] % heads:
+        raise ValueError("subgraph_attention: heads must be at least 1 and divide the columns of Q, K and V")
+    _refuse_fp8_grad("subgraph_attention", Q=Q, K=K, V=V)
+    d, dv = Q.shape[1] // heads, V.shape[1] // heads
+    scale = float(d) ** -0.5 if scale is None else float(scale)
+    out = direction == "out"
+    scores = subgraph_sddmm(engine, Q, K, heads=heads) if out else subgraph_sddmm(engine, K, Q, heads=heads)
+    y = subgraph_edge_softmax(engine, scores, scale=scale, by="row" if out else "col")
+    return torch.cat([subgraph_propagate_values(engine, V[:, h * dv:(h + 1) * dv], y[h], direction=direction) for h in range(heads)], dim=1)
 
 
 def ppr_sddmm(engine, row_ptr, A, B):
