@@ -265,6 +265,14 @@ ABI_EDGE_SOFTMAX = _rows(_ABI_EDGE_SOFTMAX)
 EDGE_SOFTMAX_SYMBOLS = list(ABI_EDGE_SOFTMAX)
 SUB_BY_COL = 2  # FORA_SUB_BY_COL
 
+# the entry point of include/fora_hip_edge_attention.h, attention over each node's edges of the held subgraph in one call: a sixth
+# table (the censuses of the five headers above are pinned); tests/test_subgraph_attention_cpu.py derives it from that header again
+_ABI_EDGE_ATTENTION = """
+int  fora_hip_subgraph_attention(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, int, int, int, double, int, ptr, ptr, int64, ptr, ptr, uint64, ptr, ptr)
+"""
+ABI_EDGE_ATTENTION = _rows(_ABI_EDGE_ATTENTION)
+EDGE_ATTENTION_SYMBOLS = list(ABI_EDGE_ATTENTION)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -302,7 +310,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -762,6 +770,50 @@ class Engine:
         its arguments.  y and g: [heads, edges], float32 or float64 each, numpy or torch on the GPU; outputs as for
         subgraph_softmax (torch when either input is)."""
         return self._subgraph_softmax("subgraph_softmax_bwd", [("y", y), ("g", g)], scale, by, want32, want64, out32, out64)
+
+    # ---- attention over each node's edges of the held subgraph in one call (the EDGE ATTENTION contract of include/fora_hip_edge_attention.h)
+    def subgraph_attention(self, Q, K, V, heads=1, scale=None, by="row", want32=True, want64=False, want_y32=False, want_y64=False,
+                           out32=None, out64=None, q_bf16=False, k_bf16=False, v_bf16=False):
+        """out = softmax over each node's edges of (scale * score) times V, head by head, in ONE call (fora_hip_subgraph_attention,
+        the EDGE ATTENTION contract of include/fora_hip_edge_attention.h): bit for bit subgraph_sddmm (float64), subgraph_softmax and
+        subgraph_propagate / subgraph_propagate_t (values=the float64 probabilities) on the column slices of the heads.  by="row":
+        node j attends over its out-edges, score = <Q[j], K[sub_col[e]]>, out[j] sums V[sub_col[e]]; by="col": node u over its
+        in-edges, score = <K[row of e], Q[u]>, out[u] sums V[row of e] (the first such call builds the transposition,
+        stats["built"] == 1).  Q, K: [nc, heads * d], V: [nc, heads * dv] (nc = held_cols), all numpy arrays or all torch tensors
+        on the context's GPU, with the conventions of subgraph_sddmm's operands (q_bf16 / k_bf16 / v_bf16: True, "bf16", "e4m3",
+        "e5m2" for numpy codes); a column slice is read in place.  scale: d ** -0.5 when None.  Returns (out32 or None, out64 or
+        None, y32 or None, y64 or None, stats dict): out [nc, heads * dv], y (the probabilities, with want_y32 / want_y64)
+        [heads, edges] in the order of sub_col; out32 / out64: caller-made outputs as for subgraph_propagate.  A (group, head)
+        with a NaN score, a +inf, or -inf only is written as NaN (stats["nan_pairs"]); a node without edges gets zeros.  stats:
+        edges, short_groups (non-empty, at most the option "attn_short" edges: the fused kernel's), long_groups, nan_pairs, built,
+        short_ms, long_ms."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_attention: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError('subgraph_attention: by is "row" or "col"')
+        heads = int(heads)
+        shape = "[nc, heads * d] (nc: the held columns)"
+        qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nc, name="Q", shape=shape)
+        kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, rows=nc, name="K", shape=shape)
+        vptr, vtype, wv, ldv, v_dev, _kv = self._prop_feat(V, v_bf16, rows=nc, name="V", shape="[nc, heads * dv] (nc: the held columns)")
+        if heads < 1 or wq % heads or wv % heads:
+            raise ValueError("heads must be at least 1 and divide the columns of Q and of V")
+        if wk != wq:
+            raise ValueError("Q and K must have the same number of columns")
+        d, dv = wq // heads, wv // heads
+        on_dev = q_dev or k_dev or v_dev
+        if on_dev and not (q_dev and k_dev and v_dev):
+            raise ValueError("Q, K and V: all torch tensors on the GPU, or all numpy arrays")
+        y32, y64, py32, py64, ycap = self._entry_outputs(heads * edges, on_dev, want_y32, want_y64, None, None)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, wv, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 5)(), (C.c_double * 2)()
+        sc = float(d) ** -0.5 if scale is None else float(scale)
+        self._chk(self._lib.fora_hip_subgraph_attention(self._ctx, qptr, qtype, ldq, kptr, ktype, ldk, vptr, vtype, ldv, d, dv, heads, sc,
+                                                        SUB_BY_COL if by == "col" else 0, p32, p64, ldo, py32, py64, ycap, info, ms))
+        shaped = lambda y: y if y is None else y.reshape(heads, edges)
+        return out32, out64, shaped(y32), shaped(y64), {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]),
+                                                         "nan_pairs": int(info[3]), "built": int(info[4]), "short_ms": ms[0], "long_ms": ms[1]}
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -24,7 +24,8 @@
 #include "fora_subgraph_prop.h"
 #include "fora_subgraph_sddmm.h"
 #include "fora_subgraph_softmax.h"
-#include "../../include/fora_hip_edge_softmax.h"
+#include "fora_subgraph_attn.h"
+#include "../../include/fora_hip_edge_attention.h"
 
 #include <algorithm>
 #include <cassert>
@@ -47,7 +48,7 @@ namespace {
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
               EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
-              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG };
+              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG, EV_SUB_ATTN_SHORT, EV_SUB_ATTN_LONG };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -436,6 +437,11 @@ struct SubProp {
         // EDGE SOFTMAX: the segments of the groups longer than sm_cap (the long list of softmax_lists), made under a value of "softmax_short"
         bool sm_listed = false; uint32_t sm_cap = 0; uint64_t sm_short = 0, sm_long = 0, sm_nseg = 0; // (sm_short: the non-empty groups of at most sm_cap entries)
         DevBuf<PropSeg> d_sm_segs;
+        // EDGE ATTENTION: the groups longer than at_cap -- their plan under at_per segments a chunk, and on the device its segments,
+        // then the two lists of softmax_lists under at_sm_cap, then one PropSeg per long group (AttnPlan::lrows); made when the key moves
+        bool at_planned = false; uint32_t at_cap = 0, at_sm_cap = 0; uint64_t at_per = 0, at_short = 0; // (at_short: the non-empty groups of at most at_cap edges)
+        PropPlan at_plan; uint64_t at_sm_short = 0, at_sm_long = 0, at_lrows = 0, at_longest = 0;
+        DevBuf<PropSeg> d_at_segs; DevBuf<PropRowRec> d_at_recs;
     } fwd, tr;
     bool t_built = false;
     DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row; // [nc + 1], [edges], [edges]: the entries column by column
@@ -479,7 +485,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0, sub_attn_short_ms = 0, sub_attn_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -1064,6 +1070,8 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SUB_SDDMM: t.sub_sddmm_ms += ms; break;       // k_sub_sddmm: ms_out of fora_hip_subgraph_sddmm only
         case EV_SUB_SMAX_SHORT: t.sub_smax_short_ms += ms; break; // k_sub_softmax / _bwd: ms_out[0] of the EDGE SOFTMAX calls only
         case EV_SUB_SMAX_LONG: t.sub_smax_long_ms += ms; break;   // the k_sub_softmax_seg_* / _div launches of their longer groups: ms_out[1] only
+        case EV_SUB_ATTN_SHORT: t.sub_attn_short_ms += ms; break; // k_sub_attn: ms_out[0] of fora_hip_subgraph_attention only
+        case EV_SUB_ATTN_LONG: t.sub_attn_long_ms += ms; break;   // the three steps' kernels over its longer groups, head by head: ms_out[1] only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -4632,6 +4640,161 @@ int fora_hip_subgraph_softmax(fora_ctx *c, const void *scores, int s_type, int h
 int fora_hip_subgraph_softmax_bwd(fora_ctx *c, const void *y, int y_type, const void *g, int g_type, int heads, double scale, int flags,
                                   float *out32, double *out64, uint64_t ocap, int64_t *info_out, double *ms_out) {
     return sub_softmax_entry(c, true, y, y_type, g, g_type, heads, scale, flags, out32, out64, ocap, info_out, ms_out);
+}
+
+// ---- EDGE ATTENTION (the contract of include/fora_hip_edge_attention.h; the fused kernel in fora_subgraph_attn.h).  The groups of at
+// most "attn_short" edges, the empty ones included, are k_sub_attn's; the longer ones go head by head through the kernels of the
+// three steps in the group's own order -- by row over (sub_ptr, sub_col), by column over (in_ptr, in_row), so that their scores and
+// y live in position order in the ctx's scratch -- as attention_impl runs the longer held rows.
+namespace {
+// the long groups of a side under (cap, per, sm_cap): plan, softmax lists and row list, on the device with the side
+int sub_side_attn_plan(fora_ctx *c, SubProp::Side &s, uint32_t cap, uint64_t per, uint32_t sm_cap) {
+    if (s.at_planned && s.at_cap == cap && s.at_per == per && s.at_sm_cap == sm_cap) return FORA_OK;
+    s.at_planned = false;
+    const AttnPlan plan = attn_plan(s.h_ptr.data(), (int)c->sp.cols, cap, per);
+    const SoftmaxLists sm = softmax_lists(plan.lng.segs, s.h_ptr.data(), sm_cap);
+    const size_t n_l = plan.lng.segs.size(), n_sm = sm.segs.size(), n_r = plan.lrows.size();
+    if (int rc = prop_ensure(c, s.d_at_segs, n_l + n_sm + n_r, "the longer groups' segment table")) return rc;
+    if (int rc = prop_ensure(c, s.d_at_recs, plan.lng.recs.size(), "the longer groups' segment table")) return rc;
+    PropSeg *const ds = s.d_at_segs.get();
+    if (n_l) HIPCHK(c, hipMemcpy(ds, plan.lng.segs.data(), n_l * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (n_sm) HIPCHK(c, hipMemcpy(ds + n_l, sm.segs.data(), n_sm * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (n_r) HIPCHK(c, hipMemcpy(ds + n_l + n_sm, plan.lrows.data(), n_r * sizeof(PropSeg), hipMemcpyHostToDevice));
+    if (!plan.lng.recs.empty()) HIPCHK(c, hipMemcpy(s.d_at_recs.get(), plan.lng.recs.data(), plan.lng.recs.size() * sizeof(PropRowRec), hipMemcpyHostToDevice));
+    s.at_longest = 0;
+    for (const PropSeg &r : plan.lrows) s.at_longest = std::max<uint64_t>(s.at_longest, r.len);
+    s.at_short = plan.short_rows; s.at_lrows = n_r; s.at_sm_short = sm.n_short; s.at_sm_long = sm.n_long;
+    s.at_plan = plan.lng; s.at_cap = cap; s.at_per = per; s.at_sm_cap = sm_cap; s.at_planned = true;
+    c->sb.prop_used = true;
+    return FORA_OK;
+}
+// nc > 0; the arguments have passed fora_hip_subgraph_attention
+int subgraph_attention_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk, const void *v_, int v_type, int64_t ldv,
+                            int d, int dv, int heads, double scale, bool by_col, float *out32, double *out64, int64_t ldo, float *y32_, double *y64_,
+                            int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    const uint32_t q_elt = elt_bytes(q_type), k_elt = elt_bytes(k_type), v_elt = elt_bytes(v_type);
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q and k; of v and out
+    HeldIn q = HeldIn::matrix(q_, nc, ldq, wq, q_elt), k = HeldIn::matrix(k_, nc, ldk, wq, k_elt), v = HeldIn::matrix(v_, nc, ldv, wv, v_elt);
+    HeldOut<float> o32{out32, ldo, nc, wv}, y32 = HeldOut<float>::vector(y32_, (uint64_t)heads * edges);
+    HeldOut<double> o64{out64, ldo, nc, wv}, y64 = HeldOut<double>::vector(y64_, (uint64_t)heads * edges);
+    if (int rc = held_resolve(c, q, k, v, o32, o64, y32, y64)) return rc; // (before anything is built)
+    c->tm.sub_attn_short_ms = c->tm.sub_attn_long_ms = 0;
+    by_col = by_col && edges; // (without an edge every group of either side is empty: nothing is transposed)
+    bool built_now = false;
+    if (by_col) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &side = by_col ? sp.tr : sp.fwd;
+    if (int rc = sub_side_ptr(c, side)) return rc;
+    // ---- the split, and for the longer groups the chunks of prop_segs segments (0: a quarter of the free memory in partial sums at most)
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    const uint64_t long_segs = prop_long_segments(side.h_ptr.data(), (int)nc, cap);
+    size_t fr = 0, tot = 0;
+    if (long_segs && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, long_segs, (uint64_t)fr, dv);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = sub_side_attn_plan(c, side, cap, per, softmax_short_cap(c->opt_.softmax_short))) return rc;
+    const bool lng = side.at_lrows != 0;
+    const uint32_t chunks = ((uint32_t)heads + (uint32_t)SGA_HEADS - 1) / (uint32_t)SGA_HEADS;
+    const uint64_t wgs = (nc * chunks + SGA_WAVES - 1) / SGA_WAVES;
+    if (wgs > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph attention: more groups than one launch takes");
+    if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
+    if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
+    if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    const bool y_scratch = by_col || !y64_; // the long groups' y of one head: in place in y64 only where that is their own order
+    if (lng) {
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)dv), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)side.at_sm_long, "the segment maxima and sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)edges, "the scores of the longer groups")) return rc;
+        if (y_scratch) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)edges, "the y of the longer groups")) return rc;
+    }
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = y32.reserve(c, pb.d_y32)) return rc;
+    if (int rc = y64.reserve(c, pb.d_y64)) return rc;
+    const int64_t *ptr = by_col ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *ids = by_col ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *pos = by_col ? sp.d_in_pos.get() : nullptr;
+    const uint32_t lg = prop_group_lg((uint32_t)d), types = sddmm_types(q_type, k_type);
+    const uint32_t *const widths = prop_widths_bytes(v_elt);
+    uint32_t nan_pairs = 0;
+    HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+    {
+        EvSpan ev(c, EV_SUB_ATTN_SHORT);
+        with_fused_types(q_type, k_type, v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto QE, auto KE, auto VE, auto V) {
+            const auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids, pos, (uint32_t)heads, chunks, q.ptr(), ldq, k.ptr(), ldk,
+                                   v.ptr(), ldv, (uint32_t)d, (uint32_t)dv, lg, scale, edges, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get(), types);
+            };
+            if (by_col) launch(k_sub_attn<QE.value, KE.value, VE.value, V.value, true>);
+            else launch(k_sub_attn<QE.value, KE.value, VE.value, V.value, false>);
+        });
+    }
+    if (lng) {
+        EvSpan ev(c, EV_SUB_ATTN_LONG);
+        const PropPlan &plan = side.at_plan;
+        const size_t n_l = plan.segs.size();
+        const PropSeg *const segs = side.d_at_segs.get(), *const sm_segs = segs + n_l, *const lrows = sm_segs + side.at_sm_short + side.at_sm_long;
+        const SoftmaxWork w{sm_segs, sm_segs + side.at_sm_short, side.at_sm_short, side.at_sm_long, pb.d_smax.get(), pb.d_smax.get() + side.at_sm_long, pb.d_smax_nan.get()};
+        const dim3 nan_grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(side.at_lrows, 65535));
+        const dim3 y_grid((unsigned)std::min<uint64_t>((side.at_longest + BLOCK - 1) / BLOCK, 1024), (unsigned)std::min<uint64_t>(side.at_lrows, 65535));
+        for (int h = 0; h < heads; h++) { // one head at a time through the two per-edge buffers
+            const void *qh = attn_cols(q.ptr(), (uint64_t)h * d, q_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
+            double *const s64 = pb.d_attn_s.get();
+            double *const yh64 = y_scratch ? pb.d_attn_y.get() : y64.ptr((uint64_t)h * edges);
+            with_elt_pair(q_type, k_type, [&](auto A, auto B) { // (the group's row of q against the k rows of its ids; the products commute: by column the same bits as <k, q>)
+                const uint64_t units = (uint64_t)n_l * SDDMM_UNITS, per_wg = BLOCK / 64;
+                hipLaunchKernelGGL((k_prop_sddmm<A.value, B.value>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_l, ids, qh, ldq, kh, ldk,
+                                   (uint32_t)d, lg, (float *)nullptr, s64, types);
+            });
+            softmax_launch<double>(c, w, s64, scale, by_col ? nullptr : y32.ptr((uint64_t)h * edges), yh64);
+            const PropSide sd{side.h_ptr.data(), (int)nc, ids, nullptr, nullptr, false, yh64, true, nullptr};
+            const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, PROP_NWIDTHS);
+            float *const oh32 = o32.ptr((uint64_t)h * dv);
+            double *const oh64 = o64.ptr((uint64_t)h * dv);
+            prop_launch_chunks(c, plan, segs, side.d_at_recs.get(), sd, v_type, g, vh, ldv, dv, nullptr, oh32, o32.ld(), oh64, o64.ld(), false);
+            hipLaunchKernelGGL(k_attn_nan_rows, nan_grid, dim3(BLOCK), 0, c->stream, lrows, side.at_lrows, (const double *)yh64, (uint32_t)dv, oh32, o32.ld(), oh64, o64.ld());
+            if (by_col && (y32.ptr() || y64.ptr()))
+                hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, side.at_lrows, pos, (const double *)yh64, y32.ptr((uint64_t)h * edges),
+                                   y64.ptr((uint64_t)h * edges));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(&nan_pairs, pb.d_smax_nan.get(), sizeof(nan_pairs), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = held_fetch(c, o32, o64, y32, y64)) return rc;
+    if (int rc = held_call_end(c, "subgraph attention")) return rc;
+    if (info_out) { info_out[0] = (int64_t)edges; info_out[1] = (int64_t)side.at_short; info_out[2] = (int64_t)side.at_lrows; info_out[3] = (int64_t)nan_pairs; info_out[4] = built_now ? 1 : 0; }
+    if (ms_out) { ms_out[0] = c->tm.sub_attn_short_ms; ms_out[1] = c->tm.sub_attn_long_ms; }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_attention(fora_ctx *c, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk, const void *v, int v_type, int64_t ldv,
+                                int d, int dv, int heads, double scale, int flags, float *out32, double *out64, int64_t ldo, float *y32, double *y64, uint64_t ycap,
+                                int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph attention: ";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(q_type) || !elt_known(k_type) || !elt_known(v_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (d < 1 || dv < 1 || heads < 1) return fail(c, FORA_E_ARG, who + "d, dv or heads below 1");
+    if ((int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, who + "heads * d or heads * dv above 65536");
+    if (ldq < (int64_t)heads * d || ldk < (int64_t)heads * d || ldv < (int64_t)heads * dv || ldo < (int64_t)heads * dv)
+        return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, who + "scale is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + "no output");
+    if ((y32 || y64) && ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    if (c->sp.cols && c->sb.edges && (!q || !k || !v)) return fail(c, FORA_E_ARG, who + "null operand");
+    if (info_out) { memset(info_out, 0, 5 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_attention_impl(c, q, q_type, ldq, k, k_type, ldk, v, v_type, ldv, d, dv, heads, scale, (flags & FORA_SUB_BY_COL) != 0,
+                                                           out32, out64, ldo, y32, y64, info_out, ms_out));
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

@@ -337,7 +337,8 @@ def subgraph_attention(engine, Q, K, V, heads=1, scale=None, direction="out"):
     sum over the edges e with sub_col[e] == v of y[e] * V[row of e] with y = softmax over the column of scale *
     <Q[v], K[row of e]> (the scores are subgraph_sddmm(K, Q): a is read at the edge's row).  Q, K: [nc, heads * d], V:
     [nc, heads * dv], float32, bfloat16 or float16 tensors on the engine's GPU (FP8 as constants); scale: d ** -0.5 when
-    None.  Returns float32 [nc, heads * dv], differentiable in Q, K and V."""
+    None.  Returns float32 [nc, heads * dv], differentiable in Q, K and V.  subgraph_attention_fused is the same layer with
+    the forward pass in one library call."""
     heads = int(heads)
     if direction not in ("out", "in"):
         raise ValueError('subgraph_attention: direction is "out" or "in"')
@@ -350,6 +351,68 @@ def subgraph_attention(engine, Q, K, V, heads=1, scale=None, direction="out"):
     scores = subgraph_sddmm(engine, Q, K, heads=heads) if out else subgraph_sddmm(engine, K, Q, heads=heads)
     y = subgraph_edge_softmax(engine, scores, scale=scale, by="row" if out else "col")
     return torch.cat([subgraph_propagate_values(engine, V[:, h * dv:(h + 1) * dv], y[h], direction=direction) for h in range(heads)], dim=1)
+
+
+class _SubgraphAttentionFused(torch.autograd.Function):
+    """out = attention over the held subgraph in one call (Engine.subgraph_attention), y32 saved; the backward pass with the
+    existing calls on it: dV = the opposite product with y[h] as values, dy = subgraph_sddmm of (G, V) -- (V, G) inwards -- and
+    ds = subgraph_softmax_bwd for all heads at once, dQ and dK the two products with ds[h] as values"""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, engine, scale, heads, inwards):
+        out32, _, y32, _, _ = engine.subgraph_attention(Q.detach(), K.detach(), V.detach(), heads=heads, scale=scale, by="col" if inwards else "row",
+                                                        want32=True, want64=False, want_y32=True)
+        ctx.save_for_backward(Q, K, V, y32)
+        ctx.engine, ctx.scale, ctx.heads, ctx.inwards = engine, scale, heads, inwards
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        Q, K, V, y32 = ctx.saved_tensors
+        engine, heads, inwards = ctx.engine, ctx.heads, ctx.inwards
+        _held_guard(ctx.generation, engine, "subgraph_attention_fused")
+        G = _dense_operand(G)
+        d, dv = Q.shape[1] // heads, V.shape[1] // heads
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        Qd, Kd, Vd = Q.detach(), K.detach(), V.detach()
+        # along: the product that sums over the forward pass's groups; across: its transpose
+        along, across = (engine.subgraph_propagate_t, engine.subgraph_propagate) if inwards else (engine.subgraph_propagate, engine.subgraph_propagate_t)
+        new = lambda X: torch.empty(X.shape, dtype=torch.float32, device=X.device)
+        dQ, dK, dV = new(Q) if need_q else None, new(K) if need_k else None, new(V) if need_v else None
+        if need_v:
+            for h in range(heads):
+                vs = slice(h * dv, (h + 1) * dv)
+                across(G[:, vs], values=y32[h], want64=False, out32=dV[:, vs])
+        if need_q or need_k:
+            dy, _, _ = engine.subgraph_sddmm(Vd, G, heads=heads) if inwards else engine.subgraph_sddmm(G, Vd, heads=heads)
+            ds, _, _ = engine.subgraph_softmax_bwd(y32, dy, scale=ctx.scale, by="col" if inwards else "row")
+            for h in range(heads):
+                qs = slice(h * d, (h + 1) * d)
+                if need_q:
+                    along(Kd[:, qs], values=ds[h], want64=False, out32=dQ[:, qs])
+                if need_k:
+                    across(Qd[:, qs], values=ds[h], want64=False, out32=dK[:, qs])
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dQ, Q), cast(dK, K), cast(dV, V), None, None, None, None
+
+
+def subgraph_attention_fused(engine, Q, K, V, heads=1, scale=None, direction="out"):
+    """subgraph_attention with the forward pass in ONE library call (Engine.subgraph_attention, the EDGE ATTENTION contract): a
+    node's edges are scored, normalised and multiplied by one wave for up to four heads at a time, nothing is written between
+    the steps and nothing is rounded to float32 between them.  Operands, direction, scale and the result as for
+    subgraph_attention: Q, K [nc, heads * d], V [nc, heads * dv], float32, bfloat16 or float16 tensors on the engine's GPU (FP8
+    as constants); float32 [nc, heads * dv], differentiable in Q, K and V.  The backward pass runs the existing calls on the
+    float32 probabilities the forward call saved: the scores' and the softmax's gradients for all heads in one call each, the
+    products head by head.  The subgraph must still be held when it runs."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_attention_fused: direction is "out" or "in"')
+    if heads < 1 or Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[1] % heads or V.shape[1] % heads or K.shape[1] != Q.shape[1]:
+        raise ValueError("subgraph_attention_fused: heads must be at least 1 and divide the columns of Q, K and V, and Q and K be as wide")
+    _refuse_fp8_grad("subgraph_attention_fused", Q=Q, K=K, V=V)
+    scale = float(Q.shape[1] // heads) ** -0.5 if scale is None else float(scale)
+    return _SubgraphAttentionFused.apply(Q, K, V, engine, scale, heads, direction == "in")
 
 
 def ppr_sddmm(engine, row_ptr, A, B):
