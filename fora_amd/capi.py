@@ -273,6 +273,14 @@ int  fora_hip_subgraph_attention(ctx*, ptr, int, int64, ptr, int, int64, ptr, in
 ABI_EDGE_ATTENTION = _rows(_ABI_EDGE_ATTENTION)
 EDGE_ATTENTION_SYMBOLS = list(ABI_EDGE_ATTENTION)
 
+# the entry point of include/fora_hip_edge_attention_bwd.h, the gradients of that call in one call: a seventh table (the censuses of
+# the six headers above are pinned); tests/test_subgraph_attention_bwd_cpu.py derives it from that header again
+_ABI_EDGE_ATTENTION_BWD = """
+int  fora_hip_subgraph_attention_bwd(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, uint64, int, int, int, double, int, attn_grads*, ptr, ptr)
+"""
+ABI_EDGE_ATTENTION_BWD = _rows(_ABI_EDGE_ATTENTION_BWD)
+EDGE_ATTENTION_BWD_SYMBOLS = list(ABI_EDGE_ATTENTION_BWD)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -310,7 +318,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -814,6 +822,58 @@ class Engine:
         shaped = lambda y: y if y is None else y.reshape(heads, edges)
         return out32, out64, shaped(y32), shaped(y64), {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]),
                                                          "nan_pairs": int(info[3]), "built": int(info[4]), "short_ms": ms[0], "long_ms": ms[1]}
+
+    def subgraph_attention_bwd(self, Q, K, V, G, y, heads=1, scale=None, by="row", want_dq=True, want_dk=True, want_dv=True, want32=True, want64=False,
+                               q_bf16=False, k_bf16=False, v_bf16=False, g_bf16=False, dq32=None, dq64=None, dk32=None, dk64=None, dv32=None, dv64=None):
+        """The gradients of subgraph_attention with respect to Q, K and V for all heads in ONE call
+        (fora_hip_subgraph_attention_bwd, the EDGE ATTENTION, BACKWARD contract of include/fora_hip_edge_attention_bwd.h): bit for
+        bit subgraph_sddmm(G, V) -- (V, G) by="col" -- in float64, subgraph_softmax_bwd(y, .), the product along the forward
+        call's grouping of K with ds as values and the product across it of Q with ds and of G with y, on the column slices of
+        the heads, nothing rounded to float32 in between.  Q, K, V, heads, scale, by: the forward call's; G: [nc, heads * dv],
+        the gradient of its output (g_bf16 as q_bf16); y: [heads, edges] float32 or float64, the probabilities it returned.
+        All operands torch tensors on the context's GPU, or all numpy arrays.  want_dq / want_dk / want_dv: a gradient that is
+        not wanted is not computed.  Returns (dq32, dq64, dk32, dk64, dv32, dv64, stats dict): dq and dk [nc, heads * d], dv
+        [nc, heads * dv], None where not wanted; dq32 .. dv64: caller-made outputs to fill instead, as for subgraph_propagate
+        (the two of one gradient with the same row stride; a caller-made output makes its gradient wanted).  stats: edges,
+        short_groups and long_groups (the forward call's grouping), across_short and across_long (the opposite one; 0 when
+        neither dk nor dv is wanted), built, short_ms, long_ms."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_attention_bwd: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError('subgraph_attention_bwd: by is "row" or "col"')
+        heads = int(heads)
+        shape = "[nc, heads * d] (nc: the held columns)"
+        qptr, qtype, wq, ldq, q_dev, _kq = self._prop_feat(Q, q_bf16, rows=nc, name="Q", shape=shape)
+        kptr, ktype, wk, ldk, k_dev, _kk = self._prop_feat(K, k_bf16, rows=nc, name="K", shape=shape)
+        vptr, vtype, wv, ldv, v_dev, _kv = self._prop_feat(V, v_bf16, rows=nc, name="V", shape="[nc, heads * dv] (nc: the held columns)")
+        gptr, gtype, wg, ldg, g_dev, _kg = self._prop_feat(G, g_bf16, rows=nc, name="G", shape="[nc, heads * dv] (nc: the held columns)")
+        if heads < 1 or wq % heads or wv % heads:
+            raise ValueError("heads must be at least 1 and divide the columns of Q and of V")
+        if wk != wq or wg != wv:
+            raise ValueError("Q and K, and V and G, must have the same number of columns")
+        d, dv = wq // heads, wv // heads
+        on_dev = q_dev or k_dev or v_dev or g_dev or self._is_torch(y)
+        if on_dev and not (q_dev and k_dev and v_dev and g_dev and self._is_torch(y)):
+            raise ValueError("Q, K, V, G and y: all torch tensors on the GPU, or all numpy arrays")
+        yptr, ytype, _, _, _ky = self._edge_operand(y, edges, "y")
+        if y.shape[0] != heads:
+            raise ValueError("y must be [heads, edges]")
+        gr = AttnGrads()
+        outs = []
+        for name, w, want, o32, o64 in (("dq", wq, want_dq, dq32, dq64), ("dk", wq, want_dk, dk32, dk64), ("dv", wv, want_dv, dv32, dv64)):
+            want = want or o32 is not None or o64 is not None
+            o32, o64, p32, p64, ld = self._prop_outputs(nc, w, on_dev, want and want32, want and want64, o32, o64) if want else (None, None, None, None, w)
+            setattr(gr, name + "32", p32.value if p32 is not None else None)
+            setattr(gr, name + "64", p64.value if p64 is not None else None)
+            setattr(gr, "ld" + name, ld)
+            outs += [o32, o64]
+        info, ms = (C.c_int64 * 6)(), (C.c_double * 2)()
+        sc = float(d) ** -0.5 if scale is None else float(scale)
+        self._chk(self._lib.fora_hip_subgraph_attention_bwd(self._ctx, qptr, qtype, ldq, kptr, ktype, ldk, vptr, vtype, ldv, gptr, gtype, ldg, yptr, ytype, heads * edges,
+                                                            d, dv, heads, sc, SUB_BY_COL if by == "col" else 0, C.byref(gr), info, ms))
+        return (*outs, {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]), "across_short": int(info[3]),
+                        "across_long": int(info[4]), "built": int(info[5]), "short_ms": ms[0], "long_ms": ms[1]})
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -25,7 +25,8 @@
 #include "fora_subgraph_sddmm.h"
 #include "fora_subgraph_softmax.h"
 #include "fora_subgraph_attn.h"
-#include "../../include/fora_hip_edge_attention.h"
+#include "fora_subgraph_attn_bwd.h"
+#include "../../include/fora_hip_edge_attention_bwd.h"
 
 #include <algorithm>
 #include <cassert>
@@ -1070,7 +1071,7 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SUB_SDDMM: t.sub_sddmm_ms += ms; break;       // k_sub_sddmm: ms_out of fora_hip_subgraph_sddmm only
         case EV_SUB_SMAX_SHORT: t.sub_smax_short_ms += ms; break; // k_sub_softmax / _bwd: ms_out[0] of the EDGE SOFTMAX calls only
         case EV_SUB_SMAX_LONG: t.sub_smax_long_ms += ms; break;   // the k_sub_softmax_seg_* / _div launches of their longer groups: ms_out[1] only
-        case EV_SUB_ATTN_SHORT: t.sub_attn_short_ms += ms; break; // k_sub_attn: ms_out[0] of fora_hip_subgraph_attention only
+        case EV_SUB_ATTN_SHORT: t.sub_attn_short_ms += ms; break; // k_sub_attn; k_sub_attn_bwd and k_sub_attn_across: ms_out[0] of fora_hip_subgraph_attention and of its _bwd only
         case EV_SUB_ATTN_LONG: t.sub_attn_long_ms += ms; break;   // the three steps' kernels over its longer groups, head by head: ms_out[1] only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
@@ -4795,6 +4796,205 @@ int fora_hip_subgraph_attention(fora_ctx *c, const void *q, int q_type, int64_t 
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, subgraph_attention_impl(c, q, q_type, ldq, k, k_type, ldk, v, v_type, ldv, d, dv, heads, scale, (flags & FORA_SUB_BY_COL) != 0,
                                                            out32, out64, ldo, y32, y64, info_out, ms_out));
+}
+
+// ---- EDGE ATTENTION, BACKWARD (the contract of include/fora_hip_edge_attention_bwd.h; the fused kernels in fora_subgraph_attn_bwd.h).
+// The ALONG side is the forward call's grouping -- dy, ds and dq -- the ACROSS side the opposite one -- dk and dv; each has the plan
+// the forward call would make for it (sub_side_attn_plan), kept with the subgraph.  On either side the groups of at most
+// "attn_short" edges, the empty ones included, are the fused kernels'; the longer ones go head by head through the kernels of the
+// steps, as attention_bwd_impl runs the longer held rows.  Their dy and ds live in position order of the along side: by row that
+// is the order of sub_col, and ds is written straight into the head's slice of the ds buffer; by column y is gathered into
+// position order first, ds takes the place of dy and k_sub_attn_y_places copies it to the buffer's edge order.
+namespace {
+// nc > 0; the arguments have passed fora_hip_subgraph_attention_bwd
+int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk, const void *v_, int v_type, int64_t ldv,
+                                const void *g_, int g_type, int64_t ldg, const void *y_, int y_type, int d, int dv, int heads, double scale, bool by_col,
+                                const fora_attn_grads &gr, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    const bool y_f64 = y_type == FORA_PROP_F64;
+    const uint32_t q_elt = elt_bytes(q_type), k_elt = elt_bytes(k_type), v_elt = elt_bytes(v_type), g_elt = elt_bytes(g_type), y_elt = y_f64 ? 8 : 4;
+    const uint64_t wq = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of q, k, dq and dk; of v, g and dv
+    const bool want_dq = gr.dq32 || gr.dq64, want_dk = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64;
+    const bool want_along = want_dq || want_dk, want_across = want_dk || want_dv; // dy and ds; the opposite grouping
+    HeldIn q = HeldIn::matrix(q_, nc, ldq, wq, q_elt), k = HeldIn::matrix(k_, nc, ldk, wq, k_elt), v = HeldIn::matrix(v_, nc, ldv, wv, v_elt);
+    HeldIn g = HeldIn::matrix(g_, nc, ldg, wv, g_elt), y = HeldIn::vector(y_, (uint64_t)heads * edges, y_elt);
+    HeldOut<float> dq32{gr.dq32, gr.lddq, nc, wq}, dk32{gr.dk32, gr.lddk, nc, wq}, dv32{gr.dv32, gr.lddv, nc, wv};
+    HeldOut<double> dq64{gr.dq64, gr.lddq, nc, wq}, dk64{gr.dk64, gr.lddk, nc, wq}, dv64{gr.dv64, gr.lddv, nc, wv};
+    if (int rc = held_resolve(c, q, k, v, g, y, dq32, dq64, dk32, dk64, dv32, dv64)) return rc; // (before anything is built)
+    c->tm.sub_attn_short_ms = c->tm.sub_attn_long_ms = 0;
+    // ---- the two sides.  Without an edge every group of either side is empty: both are the rows, nothing is transposed
+    const bool a_col = by_col && edges, x_col = !by_col && edges;
+    bool built_now = false;
+    if (a_col || (x_col && want_across)) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &along = a_col ? sp.tr : sp.fwd, &across = x_col ? sp.tr : sp.fwd;
+    if (int rc = sub_side_ptr(c, along)) return rc;
+    if (want_across) if (int rc = sub_side_ptr(c, across)) return rc;
+    // ---- the split, and for the longer groups the chunks of prop_segs segments (0: a quarter of the free memory in partial sums at most)
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short), sm_cap = softmax_short_cap(c->opt_.softmax_short);
+    const int wmax = std::max(d, dv);
+    const uint64_t a_segs = prop_long_segments(along.h_ptr.data(), (int)nc, cap), x_segs = want_across ? prop_long_segments(across.h_ptr.data(), (int)nc, cap) : 0;
+    size_t fr = 0, tot = 0;
+    if ((a_segs || x_segs) && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t a_per = prop_chunk_segs(c->opt_.prop_segs, a_segs, (uint64_t)fr, wmax), x_per = prop_chunk_segs(c->opt_.prop_segs, x_segs, (uint64_t)fr, wmax);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing.  An operand that no
+    // wanted gradient reads is not uploaded
+    if (int rc = sub_side_attn_plan(c, along, cap, a_per, sm_cap)) return rc;
+    if (want_across) if (int rc = sub_side_attn_plan(c, across, cap, x_per, sm_cap)) return rc;
+    const bool a_lng = want_along && along.at_lrows != 0, x_lng = want_across && across.at_lrows != 0;
+    const uint32_t chunks = ((uint32_t)heads + (uint32_t)SGA_HEADS - 1) / (uint32_t)SGA_HEADS;
+    const uint64_t wgs = (nc * chunks + SGA_WAVES - 1) / SGA_WAVES;
+    if (wgs > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph attention_bwd: more groups than one launch takes");
+    if (want_dk) if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
+    if (want_dq) if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
+    if (want_along) if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    if (int rc = g.stage(c, pb.d_g, "the upload of g")) return rc;
+    if (int rc = y.stage(c, pb.d_vals, "the upload of y")) return rc;
+    if (a_lng) {
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)along.at_sm_long, "the segment sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)edges, "the dy of the longer groups")) return rc;
+        if (a_col) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)edges, "the y of the longer groups")) return rc;
+    }
+    if (a_lng || x_lng) {
+        const uint64_t part = std::max(a_lng && want_dq ? a_per * (uint64_t)d : 0, x_lng ? x_per * (uint64_t)wmax : 0);
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)part, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)wmax, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    const bool ds_buf = want_dk || (a_lng && !a_col);
+    if (ds_buf) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)edges, "ds")) return rc;
+    if (int rc = dq32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = dq64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = dk32.reserve(c, pb.d_dk32)) return rc;
+    if (int rc = dk64.reserve(c, pb.d_dk64)) return rc;
+    if (int rc = dv32.reserve(c, pb.d_dv32)) return rc;
+    if (int rc = dv64.reserve(c, pb.d_dv64)) return rc;
+    const int64_t *a_ptr = a_col ? sp.d_in_ptr.get() : b.d_ptr.get(), *x_ptr = x_col ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *a_ids = a_col ? sp.d_in_row.get() : b.d_col.get(), *x_ids = x_col ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *a_pos = a_col ? sp.d_in_pos.get() : nullptr, *x_pos = x_col ? sp.d_in_pos.get() : nullptr;
+    double *const ds = ds_buf ? pb.d_attn_ds.get() : nullptr;
+    const uint32_t lgv = prop_group_lg((uint32_t)dv), types = sddmm_types(g_type, v_type); // (the dv columns of dy)
+    const uint32_t *const widths_k = prop_widths_bytes(k_elt);
+    // one gradient of the across side: the groups of at most cap edges of all heads in one launch; then the longer ones head by head
+    const auto across_short = [&](const void *values, bool val64, const void *feat, int et, uint32_t elt, int64_t ldf, int w, const HeldOut<float> &o32, const HeldOut<double> &o64) {
+        const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+        with_vec(et, V, [&](auto E, auto W) {
+            with_bools(val64, x_col, [&](auto V64, auto BYCOL) {
+                hipLaunchKernelGGL((k_sub_attn_across<decltype(E)::value, decltype(W)::value, decltype(V64)::value, decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0,
+                                   c->stream, x_ptr, (uint32_t)nc, cap, x_ids, x_pos, (uint32_t)heads, chunks, values, edges, feat, ldf, (uint32_t)w, o32.ptr(), o32.ld(),
+                                   o64.ptr(), o64.ld());
+            });
+        });
+    };
+    const auto across_long = [&](const void *values, bool val64, const void *feat, int et, uint32_t elt, int64_t ldf, int w, const HeldOut<float> &o32, const HeldOut<double> &o64) {
+        for (int h = 0; h < heads; h++) {
+            const void *fh = attn_cols(feat, (uint64_t)h * w, elt);
+            const void *vh = (const unsigned char *)values + (uint64_t)h * edges * (val64 ? 8 : 4);
+            const PropSide sd{across.h_ptr.data(), (int)nc, x_ids, nullptr, nullptr, false, vh, val64, x_pos};
+            const PropGeom gm = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+            prop_launch_chunks(c, across.at_plan, across.d_at_segs.get(), across.d_at_recs.get(), sd, et, gm, fh, ldf, w, nullptr, o32.ptr((uint64_t)h * w), o32.ld(),
+                               o64.ptr((uint64_t)h * w), o64.ld(), false);
+        }
+    };
+    if (want_along) { // dy, ds and dq of the groups of at most cap edges, all heads
+        EvSpan ev(c, EV_SUB_ATTN_SHORT);
+        with_fused_types(g_type, v_type, k_type, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto GE, auto VE, auto KE, auto V) {
+            const auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, a_ptr, (uint32_t)nc, cap, a_ids, a_pos, (uint32_t)heads, chunks, g.ptr(), ldg, v.ptr(), ldv,
+                                   k.ptr(), ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, edges, y.ptr(), y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld(), types);
+            };
+            if (a_col) launch(k_sub_attn_bwd<GE.value, VE.value, KE.value, V.value, true>);
+            else launch(k_sub_attn_bwd<GE.value, VE.value, KE.value, V.value, false>);
+        });
+    }
+    if (a_lng) { // the longer groups, one head at a time: dy, ds, dq
+        EvSpan ev(c, EV_SUB_ATTN_LONG);
+        const PropPlan &plan = along.at_plan;
+        const size_t n_l = plan.segs.size();
+        const PropSeg *const segs = along.d_at_segs.get(), *const sm_segs = segs + n_l, *const lrows = sm_segs + along.at_sm_short + along.at_sm_long;
+        const SoftmaxWork w{sm_segs, sm_segs + along.at_sm_short, along.at_sm_short, along.at_sm_long, pb.d_smax.get(), pb.d_smax.get() + along.at_sm_long, nullptr};
+        const dim3 y_grid((unsigned)std::min<uint64_t>((along.at_longest + BLOCK - 1) / BLOCK, 1024), (unsigned)std::min<uint64_t>(along.at_lrows, 65535));
+        for (int h = 0; h < heads; h++) {
+            const void *gh = attn_cols(g.ptr(), (uint64_t)h * dv, g_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
+            const void *yh = (const unsigned char *)y.ptr() + (uint64_t)h * edges * y_elt;
+            double *const dy64 = pb.d_attn_s.get(), *const dsh = ds ? ds + (uint64_t)h * edges : nullptr;
+            with_elt_pair(g_type, v_type, [&](auto A, auto B) { // (the group's row of g against the v rows of its ids; the products commute: by column the same bits as <v, g>)
+                const uint64_t units = (uint64_t)n_l * SDDMM_UNITS, per_wg = BLOCK / 64;
+                hipLaunchKernelGGL((k_prop_sddmm<A.value, B.value>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_l, a_ids, gh, ldg, vh, ldv,
+                                   (uint32_t)dv, lgv, (float *)nullptr, dy64, types);
+            });
+            const double *dsp; // ds of the head's longer groups in position order
+            if (!a_col) {
+                if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, scale, nullptr, dsh);
+                else softmax_bwd_launch<float, double>(c, w, yh, dy64, scale, nullptr, dsh);
+                dsp = dsh;
+            } else {
+                double *const yp = pb.d_attn_y.get();
+                if (y_f64) hipLaunchKernelGGL(k_sub_attn_y_gather<double>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)yh, yp);
+                else hipLaunchKernelGGL(k_sub_attn_y_gather<float>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const float *)yh, yp);
+                softmax_bwd_launch<double, double>(c, w, yp, dy64, scale, nullptr, dy64); // (in place: a lane writes the places it has read, after the sums' launch)
+                if (want_dk) hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)dy64, (float *)nullptr, dsh);
+                dsp = dy64;
+            }
+            if (want_dq) {
+                const void *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt);
+                const PropSide sd{along.h_ptr.data(), (int)nc, a_ids, nullptr, nullptr, false, dsp, true, nullptr};
+                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, PROP_NWIDTHS);
+                prop_launch_chunks(c, plan, segs, along.d_at_recs.get(), sd, k_type, gm, kh, ldk, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
+            }
+        }
+    }
+    if (want_across) {
+        EvSpan ev(c, EV_SUB_ATTN_SHORT);
+        if (want_dk) across_short(ds, true, q.ptr(), q_type, q_elt, ldq, d, dk32, dk64);
+        if (want_dv) across_short(y.ptr(), y_f64, g.ptr(), g_type, g_elt, ldg, dv, dv32, dv64);
+    }
+    if (x_lng) {
+        EvSpan ev(c, EV_SUB_ATTN_LONG);
+        if (want_dk) across_long(ds, true, q.ptr(), q_type, q_elt, ldq, d, dk32, dk64);
+        if (want_dv) across_long(y.ptr(), y_f64, g.ptr(), g_type, g_elt, ldg, dv, dv32, dv64);
+    }
+    if (int rc = held_fetch(c, dq32, dq64, dk32, dk64, dv32, dv64)) return rc;
+    if (int rc = held_call_end(c, "subgraph attention_bwd")) return rc;
+    if (info_out) {
+        info_out[0] = (int64_t)edges; info_out[1] = (int64_t)along.at_short; info_out[2] = (int64_t)along.at_lrows;
+        info_out[3] = want_across ? (int64_t)across.at_short : 0; info_out[4] = want_across ? (int64_t)across.at_lrows : 0; info_out[5] = built_now ? 1 : 0;
+    }
+    if (ms_out) { ms_out[0] = c->tm.sub_attn_short_ms; ms_out[1] = c->tm.sub_attn_long_ms; }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_attention_bwd(fora_ctx *c, const void *q, int q_type, int64_t ldq, const void *k, int k_type, int64_t ldk, const void *v, int v_type, int64_t ldv,
+                                    const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap, int d, int dv, int heads, double scale, int flags,
+                                    const fora_attn_grads *grads, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph attention_bwd: ";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(q_type) || !elt_known(k_type) || !elt_known(v_type) || !elt_known(g_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + "y_type is neither f32 nor f64");
+    if (d < 1 || dv < 1 || heads < 1) return fail(c, FORA_E_ARG, who + "d, dv or heads below 1");
+    if ((int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, who + "heads * d or heads * dv above 65536");
+    if (ldq < (int64_t)heads * d || ldk < (int64_t)heads * d || ldv < (int64_t)heads * dv || ldg < (int64_t)heads * dv)
+        return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(scale)) return fail(c, FORA_E_ARG, who + "scale is not finite");
+    if (!grads) return fail(c, FORA_E_ARG, who + "no output");
+    const bool want_dq = grads->dq32 || grads->dq64, want_dk = grads->dk32 || grads->dk64, want_dv = grads->dv32 || grads->dv64;
+    if (!want_dq && !want_dk && !want_dv) return fail(c, FORA_E_ARG, who + "no output");
+    if ((want_dq && grads->lddq < (int64_t)heads * d) || (want_dk && grads->lddk < (int64_t)heads * d) || (want_dv && grads->lddv < (int64_t)heads * dv))
+        return fail(c, FORA_E_ARG, who + "lddq or lddk smaller than heads * d, or lddv smaller than heads * dv");
+    if (ycap / (uint64_t)heads < c->sb.edges || ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    const bool e = c->sp.cols && c->sb.edges;
+    if (e && (!q || !k || !v || !g || !y)) return fail(c, FORA_E_ARG, who + "null q, k, v, g or y");
+    if (info_out) { memset(info_out, 0, 6 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_attention_bwd_impl(c, e ? q : nullptr, q_type, ldq, e ? k : nullptr, k_type, ldk, e ? v : nullptr, v_type, ldv, e ? g : nullptr, g_type,
+                                                               ldg, e ? y : nullptr, y_type, d, dv, heads, scale, (flags & FORA_SUB_BY_COL) != 0, *grads, info_out, ms_out));
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

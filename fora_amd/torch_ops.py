@@ -415,6 +415,42 @@ def subgraph_attention_fused(engine, Q, K, V, heads=1, scale=None, direction="ou
     return _SubgraphAttentionFused.apply(Q, K, V, engine, scale, heads, direction == "in")
 
 
+class _SubgraphAttentionTrained(_SubgraphAttentionFused):
+    """the same forward pass; the backward pass is ONE call for all heads (Engine.subgraph_attention_bwd) on the saved y32, with
+    nothing rounded to float32 between its steps"""
+
+    @staticmethod
+    def backward(ctx, G):
+        Q, K, V, y32 = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "subgraph_attention_trained")
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None, None, None
+        dQ, _, dK, _, dV, _, stats = engine.subgraph_attention_bwd(Q.detach(), K.detach(), V.detach(), _dense_operand(G), y32, heads=ctx.heads, scale=ctx.scale,
+                                                                   by="col" if ctx.inwards else "row", want_dq=need_q, want_dk=need_k, want_dv=need_v,
+                                                                   want32=True, want64=False)
+        engine.last_subgraph_attention_bwd = stats
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dQ, Q), cast(dK, K), cast(dV, V), None, None, None, None
+
+
+def subgraph_attention_trained(engine, Q, K, V, heads=1, scale=None, direction="out"):
+    """subgraph_attention_fused with the backward pass in ONE library call as well (Engine.subgraph_attention_bwd, the EDGE
+    ATTENTION, BACKWARD contract): the same forward call and result, the float32 probabilities saved; the backward pass computes
+    only the gradients autograd asks for, for all heads at once, and rounds nothing to float32 between its steps -- a layer's
+    training step is two library calls.  Operands, heads, scale and direction as for subgraph_attention_fused.  The subgraph
+    must still be held when the backward pass runs; its stats are left in engine.last_subgraph_attention_bwd."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_attention_trained: direction is "out" or "in"')
+    if heads < 1 or Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or Q.shape[1] % heads or V.shape[1] % heads or K.shape[1] != Q.shape[1]:
+        raise ValueError("subgraph_attention_trained: heads must be at least 1 and divide the columns of Q, K and V, and Q and K be as wide")
+    _refuse_fp8_grad("subgraph_attention_trained", Q=Q, K=K, V=V)
+    scale = float(Q.shape[1] // heads) ** -0.5 if scale is None else float(scale)
+    return _SubgraphAttentionTrained.apply(Q, K, V, engine, scale, heads, direction == "in")
+
+
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
     the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32, bfloat16 or float16 tensors (or constant FP8 ones) on the engine's GPU with a column
