@@ -281,6 +281,15 @@ int  fora_hip_subgraph_attention_bwd(ctx*, ptr, int, int64, ptr, int, int64, ptr
 ABI_EDGE_ATTENTION_BWD = _rows(_ABI_EDGE_ATTENTION_BWD)
 EDGE_ATTENTION_BWD_SYMBOLS = list(ABI_EDGE_ATTENTION_BWD)
 
+# the entry points of include/fora_hip_edge_gat.h, graph attention (additive scores) over the held subgraph, forward and backward:
+# an eighth table (the censuses of the seven headers above are pinned); tests/test_subgraph_gat_cpu.py derives it from that header again
+_ABI_EDGE_GAT = """
+int  fora_hip_subgraph_gat(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, int, int, double, int, ptr, ptr, int64, ptr, ptr, uint64, ptr, ptr)
+int  fora_hip_subgraph_gat_bwd(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, uint64, int, int, double, int, attn_grads*, ptr, ptr)
+"""
+ABI_EDGE_GAT = _rows(_ABI_EDGE_GAT)
+EDGE_GAT_SYMBOLS = list(ABI_EDGE_GAT)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -318,7 +327,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -872,6 +881,80 @@ class Engine:
         sc = float(d) ** -0.5 if scale is None else float(scale)
         self._chk(self._lib.fora_hip_subgraph_attention_bwd(self._ctx, qptr, qtype, ldq, kptr, ktype, ldk, vptr, vtype, ldv, gptr, gtype, ldg, yptr, ytype, heads * edges,
                                                             d, dv, heads, sc, SUB_BY_COL if by == "col" else 0, C.byref(gr), info, ms))
+        return (*outs, {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]), "across_short": int(info[3]),
+                        "across_long": int(info[4]), "built": int(info[5]), "short_ms": ms[0], "long_ms": ms[1]})
+
+    # ---- graph attention (additive scores) over the held subgraph (the EDGE GAT contracts of include/fora_hip_edge_gat.h)
+    def _gat_operands(self, who, by, heads, named):
+        """the checks and the (pointer, type, pitch) triples of el, er, V (and G): ([triples], dv, on_dev, keep-alives)"""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, f"{who}: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError(f'{who}: by is "row" or "col"')
+        ops = [self._prop_feat(x, kind, rows=nc, name=name, shape="[nc, heads] (el, er) or [nc, heads * dv] (nc: the held columns)") for name, x, kind in named]
+        widths = [o[2] for o in ops]
+        if heads < 1 or widths[0] != heads or widths[1] != heads or widths[2] % heads or any(w != widths[2] for w in widths[3:]):
+            raise ValueError(f"{who}: el and er must be [nc, heads], heads (at least 1) must divide the columns of V, and G be as wide as V")
+        return ops, widths[2] // heads, [o[4] for o in ops], nc, edges
+
+    def subgraph_gat(self, el, er, V, heads=1, slope=0.2, by="row", want32=True, want64=False, want_y32=False, want_y64=False, out32=None, out64=None,
+                     el_bf16=False, er_bf16=False, v_bf16=False):
+        """out = softmax over each node's edges of LeakyReLU(el[row of e] + er[sub_col[e]]) times V, head by head, in ONE call
+        (fora_hip_subgraph_gat, the EDGE GAT contract of include/fora_hip_edge_gat.h): a graph attention network's layer.  Bit
+        for bit the float64 sum and LeakyReLU, subgraph_softmax and subgraph_propagate / subgraph_propagate_t (values=the float64
+        probabilities) on the heads' column slices.  by="row": node j attends over its out-edges and out[j] sums V[sub_col[e]];
+        by="col": node u over its in-edges and out[u] sums V[row of e] (the first such call builds the transposition); el is
+        read at the edge's row and er at its column either way.  el, er: [nc, heads], V: [nc, heads * dv] (nc = held_cols), all
+        numpy arrays or all torch tensors on the context's GPU, with the conventions of subgraph_attention's operands (el_bf16 /
+        er_bf16 / v_bf16: True, "bf16", "e4m3", "e5m2" for numpy codes); a column slice is read in place.  Returns (out32 or
+        None, out64 or None, y32 or None, y64 or None, stats dict) as subgraph_attention does, with its stats."""
+        heads = int(heads)
+        (e_l, e_r, v), dv, devs, nc, edges = self._gat_operands("subgraph_gat", by, heads, (("el", el, el_bf16), ("er", er, er_bf16), ("V", V, v_bf16)))
+        on_dev = any(devs)
+        if on_dev and not all(devs):
+            raise ValueError("el, er and V: all torch tensors on the GPU, or all numpy arrays")
+        y32, y64, py32, py64, ycap = self._entry_outputs(heads * edges, on_dev, want_y32, want_y64, None, None)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, heads * dv, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 5)(), (C.c_double * 2)()
+        self._chk(self._lib.fora_hip_subgraph_gat(self._ctx, e_l[0], e_l[1], e_l[3], e_r[0], e_r[1], e_r[3], v[0], v[1], v[3], dv, heads, float(slope),
+                                                  SUB_BY_COL if by == "col" else 0, p32, p64, ldo, py32, py64, ycap, info, ms))
+        shaped = lambda y: y if y is None else y.reshape(heads, edges)
+        return out32, out64, shaped(y32), shaped(y64), {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]),
+                                                         "nan_pairs": int(info[3]), "built": int(info[4]), "short_ms": ms[0], "long_ms": ms[1]}
+
+    def subgraph_gat_bwd(self, el, er, V, G, y, heads=1, slope=0.2, by="row", want_del=True, want_der=True, want_dv=True, want32=True, want64=False,
+                         el_bf16=False, er_bf16=False, v_bf16=False, g_bf16=False, del32=None, del64=None, der32=None, der64=None, dv32=None, dv64=None):
+        """The gradients of subgraph_gat with respect to el, er and V for all heads in ONE call (fora_hip_subgraph_gat_bwd, the
+        EDGE GAT, BACKWARD contract of include/fora_hip_edge_gat.h): bit for bit subgraph_sddmm(G, V) -- (V, G) by="col" -- in
+        float64, subgraph_softmax_bwd(y, .), dz = ds or ds * slope by the sign of el + er, the ordered sums of dz along the
+        forward call's grouping (d el by row, d er by column) and across it, and the product across it of G with y.  el, er, V,
+        heads, slope, by: the forward call's; G: [nc, heads * dv]; y: [heads, edges] float32 or float64, the probabilities it
+        returned.  All operands torch tensors on the context's GPU, or all numpy arrays.  A gradient that is not wanted is not
+        computed.  Returns (del32, del64, der32, der64, dv32, dv64, stats dict): d el and d er [nc, heads], dv [nc, heads * dv],
+        None where not wanted; del32 .. dv64: caller-made outputs to fill instead, as for subgraph_attention_bwd, whose stats
+        these are."""
+        heads = int(heads)
+        ops, dv, devs, nc, edges = self._gat_operands("subgraph_gat_bwd", by, heads, (("el", el, el_bf16), ("er", er, er_bf16), ("V", V, v_bf16), ("G", G, g_bf16)))
+        on_dev = any(devs) or self._is_torch(y)
+        if on_dev and not (all(devs) and self._is_torch(y)):
+            raise ValueError("el, er, V, G and y: all torch tensors on the GPU, or all numpy arrays")
+        yptr, ytype, _, _, _ky = self._edge_operand(y, edges, "y")
+        if y.shape[0] != heads:
+            raise ValueError("y must be [heads, edges]")
+        gr = AttnGrads()
+        outs = []
+        for name, w, want, o32, o64 in (("dq", heads, want_del, del32, del64), ("dk", heads, want_der, der32, der64), ("dv", heads * dv, want_dv, dv32, dv64)):
+            want = want or o32 is not None or o64 is not None
+            o32, o64, p32, p64, ld = self._prop_outputs(nc, w, on_dev, want and want32, want and want64, o32, o64) if want else (None, None, None, None, w)
+            setattr(gr, name + "32", p32.value if p32 is not None else None)
+            setattr(gr, name + "64", p64.value if p64 is not None else None)
+            setattr(gr, "ld" + name, ld)
+            outs += [o32, o64]
+        info, ms = (C.c_int64 * 6)(), (C.c_double * 2)()
+        args = [a for o in ops for a in (o[0], o[1], o[3])]
+        self._chk(self._lib.fora_hip_subgraph_gat_bwd(self._ctx, *args, yptr, ytype, heads * edges, dv, heads, float(slope), SUB_BY_COL if by == "col" else 0,
+                                                      C.byref(gr), info, ms))
         return (*outs, {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]), "across_short": int(info[3]),
                         "across_long": int(info[4]), "built": int(info[5]), "short_ms": ms[0], "long_ms": ms[1]})
 

@@ -26,7 +26,8 @@
 #include "fora_subgraph_softmax.h"
 #include "fora_subgraph_attn.h"
 #include "fora_subgraph_attn_bwd.h"
-#include "../../include/fora_hip_edge_attention_bwd.h"
+#include "fora_subgraph_gat.h"
+#include "../../include/fora_hip_edge_gat.h"
 
 #include <algorithm>
 #include <cassert>
@@ -446,6 +447,7 @@ struct SubProp {
     } fwd, tr;
     bool t_built = false;
     DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row; // [nc + 1], [edges], [edges]: the entries column by column
+    bool have_ones = false; DevBuf<float> d_ones;                 // EDGE GAT, BACKWARD: [nc] of 1.0f, the column the longer groups' sums of dz multiply
 };
 struct SubBufs {
     bool valid = false; uint64_t edges = 0;
@@ -4648,6 +4650,7 @@ int fora_hip_subgraph_softmax_bwd(fora_ctx *c, const void *y, int y_type, const 
 // three steps in the group's own order -- by row over (sub_ptr, sub_col), by column over (in_ptr, in_row), so that their scores and
 // y live in position order in the ctx's scratch -- as attention_impl runs the longer held rows.
 namespace {
+inline unsigned gat_seg_grid(size_t nseg) { return (unsigned)std::min<size_t>(std::max<size_t>(nseg, 1), 0x7FFFFFFFu); } // k_gat_seg: a workgroup per segment
 // the long groups of a side under (cap, per, sm_cap): plan, softmax lists and row list, on the device with the side
 int sub_side_attn_plan(fora_ctx *c, SubProp::Side &s, uint32_t cap, uint64_t per, uint32_t sm_cap) {
     if (s.at_planned && s.at_cap == cap && s.at_per == per && s.at_sm_cap == sm_cap) return FORA_OK;
@@ -4669,10 +4672,12 @@ int sub_side_attn_plan(fora_ctx *c, SubProp::Side &s, uint32_t cap, uint64_t per
     c->sb.prop_used = true;
     return FORA_OK;
 }
-// nc > 0; the arguments have passed fora_hip_subgraph_attention
+// nc > 0; the arguments have passed fora_hip_subgraph_attention -- or fora_hip_subgraph_gat, EDGE GAT (include/fora_hip_edge_gat.h; the
+// kernels in fora_subgraph_gat.h), which is this call with another score: gat_slope is then the LeakyReLU's slope, q the operand
+// read at the GROUP's node (el by row, er by column) and k the one read at the other end, d = 1 and scale = 1.0
 int subgraph_attention_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk, const void *v_, int v_type, int64_t ldv,
                             int d, int dv, int heads, double scale, bool by_col, float *out32, double *out64, int64_t ldo, float *y32_, double *y64_,
-                            int64_t *info_out, double *ms_out) {
+                            int64_t *info_out, double *ms_out, const double *gat_slope = nullptr) {
     SubBufs &b = c->sb;
     PropBufs &pb = c->pr;
     const uint64_t nc = c->sp.cols, edges = b.edges;
@@ -4727,7 +4732,14 @@ int subgraph_attention_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq
     HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
     {
         EvSpan ev(c, EV_SUB_ATTN_SHORT);
-        with_fused_types(q_type, k_type, v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto QE, auto KE, auto VE, auto V) {
+        if (gat_slope) with_vec(v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto VE, auto V) {
+            with_bools(by_col, false, [&](auto BYCOL, auto) {
+                hipLaunchKernelGGL((k_sub_gat<decltype(VE)::value, decltype(V)::value, decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids,
+                                   pos, (uint32_t)heads, chunks, q.ptr(), ldq, k.ptr(), ldk, v.ptr(), ldv, (uint32_t)dv, *gat_slope, edges, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(),
+                                   y32.ptr(), y64.ptr(), pb.d_smax_nan.get(), types);
+            });
+        });
+        else with_fused_types(q_type, k_type, v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto QE, auto KE, auto VE, auto V) {
             const auto launch = [&](auto kernel) {
                 hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids, pos, (uint32_t)heads, chunks, q.ptr(), ldq, k.ptr(), ldk,
                                    v.ptr(), ldv, (uint32_t)d, (uint32_t)dv, lg, scale, edges, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get(), types);
@@ -4748,7 +4760,8 @@ int subgraph_attention_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq
             const void *qh = attn_cols(q.ptr(), (uint64_t)h * d, q_elt), *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
             double *const s64 = pb.d_attn_s.get();
             double *const yh64 = y_scratch ? pb.d_attn_y.get() : y64.ptr((uint64_t)h * edges);
-            with_elt_pair(q_type, k_type, [&](auto A, auto B) { // (the group's row of q against the k rows of its ids; the products commute: by column the same bits as <k, q>)
+            if (gat_slope) hipLaunchKernelGGL(k_gat_seg<false>, dim3(gat_seg_grid(n_l)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_l, ids, qh, ldq, kh, ldk, types, *gat_slope, s64);
+            else with_elt_pair(q_type, k_type, [&](auto A, auto B) { // (the group's row of q against the k rows of its ids; the products commute: by column the same bits as <k, q>)
                 const uint64_t units = (uint64_t)n_l * SDDMM_UNITS, per_wg = BLOCK / 64;
                 hipLaunchKernelGGL((k_prop_sddmm<A.value, B.value>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_l, ids, qh, ldq, kh, ldk,
                                    (uint32_t)d, lg, (float *)nullptr, s64, types);
@@ -4806,10 +4819,42 @@ int fora_hip_subgraph_attention(fora_ctx *c, const void *q, int q_type, int64_t 
 // is the order of sub_col, and ds is written straight into the head's slice of the ds buffer; by column y is gathered into
 // position order first, ds takes the place of dy and k_sub_attn_y_places copies it to the buffer's edge order.
 namespace {
-// nc > 0; the arguments have passed fora_hip_subgraph_attention_bwd
+// The ACROSS side of a backward call -- the grouping opposite to the forward call's -- and one gradient of it: the product of
+// the head's w columns of feat with values, [heads][edges] in the order of sub_col.  sub_across_short: the groups of at most cap
+// edges of all heads in one launch; sub_across_long: the longer ones head by head, on the plan kept with the side
+struct SubAcross { const SubProp::Side &side; const int64_t *ptr; const int32_t *ids; const int64_t *pos; bool col; uint64_t nc, edges; uint32_t cap; int heads; };
+inline uint32_t sga_chunks(int heads) { return ((uint32_t)heads + (uint32_t)SGA_HEADS - 1) / (uint32_t)SGA_HEADS; }
+inline uint64_t sga_wgs(uint64_t nc, int heads) { return (nc * sga_chunks(heads) + SGA_WAVES - 1) / SGA_WAVES; }
+void sub_across_short(fora_ctx *c, const SubAcross &x, const void *values, bool val64, const void *feat, int et, int64_t ldf, int w, const HeldOut<float> &o32,
+                      const HeldOut<double> &o64) {
+    const uint32_t elt = elt_bytes(et), V = attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, x.heads, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+    with_vec(et, V, [&](auto E, auto W) {
+        with_bools(val64, x.col, [&](auto V64, auto BYCOL) {
+            hipLaunchKernelGGL((k_sub_attn_across<decltype(E)::value, decltype(W)::value, decltype(V64)::value, decltype(BYCOL)::value>), dim3((unsigned)sga_wgs(x.nc, x.heads)),
+                               dim3(BLOCK), 0, c->stream, x.ptr, (uint32_t)x.nc, x.cap, x.ids, x.pos, (uint32_t)x.heads, sga_chunks(x.heads), values, x.edges, feat, ldf, (uint32_t)w,
+                               o32.ptr(), o32.ld(), o64.ptr(), o64.ld());
+        });
+    });
+}
+void sub_across_long(fora_ctx *c, const SubAcross &x, const void *values, bool val64, const void *feat, int et, int64_t ldf, int w, const HeldOut<float> &o32,
+                     const HeldOut<double> &o64, bool per_head = true) { // (per_head false: one feat column for every head -- EDGE GAT's ones)
+    const uint32_t elt = elt_bytes(et);
+    for (int h = 0; h < x.heads; h++) {
+        const void *fh = per_head ? attn_cols(feat, (uint64_t)h * w, elt) : feat;
+        const void *vh = (const unsigned char *)values + (uint64_t)h * x.edges * (val64 ? 8 : 4);
+        const PropSide sd{x.side.h_ptr.data(), (int)x.nc, x.ids, nullptr, nullptr, false, vh, val64, x.pos};
+        const PropGeom gm = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+        prop_launch_chunks(c, x.side.at_plan, x.side.d_at_segs.get(), x.side.d_at_recs.get(), sd, et, gm, fh, ldf, w, nullptr, o32.ptr((uint64_t)h * w), o32.ld(),
+                           o64.ptr((uint64_t)h * w), o64.ld(), false);
+    }
+}
+// nc > 0; the arguments have passed fora_hip_subgraph_attention_bwd -- or fora_hip_subgraph_gat_bwd, EDGE GAT, BACKWARD, which is this
+// call with another score: gat_slope is then the LeakyReLU's slope, q the operand read at the GROUP's node and k the one at the other
+// end, as in subgraph_attention_impl, d = 1 and scale = 1.0; ds becomes dz on its way, dq and dk are the along and the across sum of
+// dz -- the products of a ones column with it -- and q and k are read for z whenever dy is computed
 int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t ldq, const void *k_, int k_type, int64_t ldk, const void *v_, int v_type, int64_t ldv,
                                 const void *g_, int g_type, int64_t ldg, const void *y_, int y_type, int d, int dv, int heads, double scale, bool by_col,
-                                const fora_attn_grads &gr, int64_t *info_out, double *ms_out) {
+                                const fora_attn_grads &gr, int64_t *info_out, double *ms_out, const double *gat_slope = nullptr) {
     SubBufs &b = c->sb;
     PropBufs &pb = c->pr;
     const uint64_t nc = c->sp.cols, edges = b.edges;
@@ -4847,8 +4892,8 @@ int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t
     const uint32_t chunks = ((uint32_t)heads + (uint32_t)SGA_HEADS - 1) / (uint32_t)SGA_HEADS;
     const uint64_t wgs = (nc * chunks + SGA_WAVES - 1) / SGA_WAVES;
     if (wgs > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph attention_bwd: more groups than one launch takes");
-    if (want_dk) if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
-    if (want_dq) if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
+    if (gat_slope ? want_along : want_dk) if (int rc = q.stage(c, pb.d_a, "the upload of q")) return rc;
+    if (gat_slope ? want_along : want_dq) if (int rc = k.stage(c, pb.d_feat, "the upload of k")) return rc;
     if (want_along) if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
     if (int rc = g.stage(c, pb.d_g, "the upload of g")) return rc;
     if (int rc = y.stage(c, pb.d_vals, "the upload of y")) return rc;
@@ -4865,6 +4910,8 @@ int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t
     }
     const bool ds_buf = want_dk || (a_lng && !a_col);
     if (ds_buf) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)edges, "ds")) return rc;
+    const bool ones_col = gat_slope && ((a_lng && want_dq) || (x_lng && want_dk)); // (kept with the subgraph: nc of them, written once)
+    if (ones_col && !sp.have_ones) if (int rc = prop_ensure(c, sp.d_ones, (size_t)nc, "the ones column")) return rc;
     if (int rc = dq32.reserve(c, pb.d_out32)) return rc;
     if (int rc = dq64.reserve(c, pb.d_out64)) return rc;
     if (int rc = dk32.reserve(c, pb.d_dk32)) return rc;
@@ -4877,30 +4924,23 @@ int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t
     double *const ds = ds_buf ? pb.d_attn_ds.get() : nullptr;
     const uint32_t lgv = prop_group_lg((uint32_t)dv), types = sddmm_types(g_type, v_type); // (the dv columns of dy)
     const uint32_t *const widths_k = prop_widths_bytes(k_elt);
-    // one gradient of the across side: the groups of at most cap edges of all heads in one launch; then the longer ones head by head
-    const auto across_short = [&](const void *values, bool val64, const void *feat, int et, uint32_t elt, int64_t ldf, int w, const HeldOut<float> &o32, const HeldOut<double> &o64) {
-        const uint32_t V = attn_vec_width((uint64_t)(uintptr_t)feat, ldf, w, heads, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
-        with_vec(et, V, [&](auto E, auto W) {
-            with_bools(val64, x_col, [&](auto V64, auto BYCOL) {
-                hipLaunchKernelGGL((k_sub_attn_across<decltype(E)::value, decltype(W)::value, decltype(V64)::value, decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0,
-                                   c->stream, x_ptr, (uint32_t)nc, cap, x_ids, x_pos, (uint32_t)heads, chunks, values, edges, feat, ldf, (uint32_t)w, o32.ptr(), o32.ld(),
-                                   o64.ptr(), o64.ld());
-            });
-        });
-    };
-    const auto across_long = [&](const void *values, bool val64, const void *feat, int et, uint32_t elt, int64_t ldf, int w, const HeldOut<float> &o32, const HeldOut<double> &o64) {
-        for (int h = 0; h < heads; h++) {
-            const void *fh = attn_cols(feat, (uint64_t)h * w, elt);
-            const void *vh = (const unsigned char *)values + (uint64_t)h * edges * (val64 ? 8 : 4);
-            const PropSide sd{across.h_ptr.data(), (int)nc, x_ids, nullptr, nullptr, false, vh, val64, x_pos};
-            const PropGeom gm = prop_geom((uint64_t)(uintptr_t)fh, ldf, w, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
-            prop_launch_chunks(c, across.at_plan, across.d_at_segs.get(), across.d_at_recs.get(), sd, et, gm, fh, ldf, w, nullptr, o32.ptr((uint64_t)h * w), o32.ld(),
-                               o64.ptr((uint64_t)h * w), o64.ld(), false);
-        }
-    };
+    const uint32_t qk_types = sddmm_types(q_type, k_type);
+    if (ones_col && !sp.have_ones) {
+        hipLaunchKernelGGL(k_gat_ones, dim3((unsigned)std::min<uint64_t>((nc + BLOCK - 1) / BLOCK, 65535)), dim3(BLOCK), 0, c->stream, sp.d_ones.get(), nc);
+        sp.have_ones = true; c->sb.prop_used = true;
+    }
+    const float *const ones = sp.d_ones.get();
+    const SubAcross xs{across, x_ptr, x_ids, x_pos, x_col, nc, edges, cap, heads};
     if (want_along) { // dy, ds and dq of the groups of at most cap edges, all heads
         EvSpan ev(c, EV_SUB_ATTN_SHORT);
-        with_fused_types(g_type, v_type, k_type, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto GE, auto VE, auto KE, auto V) {
+        if (gat_slope) with_elt_pair(g_type, v_type, [&](auto GE, auto VE) {
+            with_bools(a_col, false, [&](auto BYCOL, auto) {
+                hipLaunchKernelGGL((k_sub_gat_bwd<decltype(GE)::value, decltype(VE)::value, decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, a_ptr, (uint32_t)nc,
+                                   cap, a_ids, a_pos, (uint32_t)heads, chunks, q.ptr(), ldq, k.ptr(), ldk, g.ptr(), ldg, v.ptr(), ldv, (uint32_t)dv, lgv, *gat_slope, edges, y.ptr(),
+                                   y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld(), qk_types, types);
+            });
+        });
+        else with_fused_types(g_type, v_type, k_type, attn_vec_width((uint64_t)(uintptr_t)k.ptr(), ldk, d, heads, k_elt, widths_k, PROP_NWIDTHS), [&](auto GE, auto VE, auto KE, auto V) {
             const auto launch = [&](auto kernel) {
                 hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, a_ptr, (uint32_t)nc, cap, a_ids, a_pos, (uint32_t)heads, chunks, g.ptr(), ldg, v.ptr(), ldv,
                                    k.ptr(), ldk, (uint32_t)d, (uint32_t)dv, lgv, scale, edges, y.ptr(), y_f64, want_dk ? ds : nullptr, dq32.ptr(), dq32.ld(), dq64.ptr(), dq64.ld(), types);
@@ -4935,26 +4975,36 @@ int subgraph_attention_bwd_impl(fora_ctx *c, const void *q_, int q_type, int64_t
                 if (y_f64) hipLaunchKernelGGL(k_sub_attn_y_gather<double>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)yh, yp);
                 else hipLaunchKernelGGL(k_sub_attn_y_gather<float>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const float *)yh, yp);
                 softmax_bwd_launch<double, double>(c, w, yp, dy64, scale, nullptr, dy64); // (in place: a lane writes the places it has read, after the sums' launch)
-                if (want_dk) hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)dy64, (float *)nullptr, dsh);
                 dsp = dy64;
             }
-            if (want_dq) {
-                const void *kh = attn_cols(k.ptr(), (uint64_t)h * d, k_elt);
+            if (gat_slope) // dz in place of ds, z from the head's column of q and k
+                hipLaunchKernelGGL(k_gat_seg<true>, dim3(gat_seg_grid(n_l)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_l, a_ids, attn_cols(q.ptr(), (uint64_t)h, q_elt), ldq,
+                                   attn_cols(k.ptr(), (uint64_t)h, k_elt), ldk, qk_types, *gat_slope, const_cast<double *>(dsp));
+            if (a_col && want_dk) hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, dsp, (float *)nullptr, dsh);
+            if (want_dq) { // (EDGE GAT: the ones column in k's place, for every head)
+                const void *kh = gat_slope ? (const void *)ones : attn_cols(k.ptr(), (uint64_t)h * d, k_elt);
+                const int kt = gat_slope ? (int)ELT_F32 : k_type;
+                const int64_t ldkh = gat_slope ? 1 : ldk;
                 const PropSide sd{along.h_ptr.data(), (int)nc, a_ids, nullptr, nullptr, false, dsp, true, nullptr};
-                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldk, d, k_elt, widths_k, PROP_NWIDTHS);
-                prop_launch_chunks(c, plan, segs, along.d_at_recs.get(), sd, k_type, gm, kh, ldk, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
+                const PropGeom gm = prop_geom((uint64_t)(uintptr_t)kh, ldkh, d, elt_bytes(kt), prop_widths_bytes(elt_bytes(kt)), PROP_NWIDTHS);
+                prop_launch_chunks(c, plan, segs, along.d_at_recs.get(), sd, kt, gm, kh, ldkh, d, nullptr, dq32.ptr((uint64_t)h * d), dq32.ld(), dq64.ptr((uint64_t)h * d), dq64.ld(), false);
             }
         }
     }
     if (want_across) {
         EvSpan ev(c, EV_SUB_ATTN_SHORT);
-        if (want_dk) across_short(ds, true, q.ptr(), q_type, q_elt, ldq, d, dk32, dk64);
-        if (want_dv) across_short(y.ptr(), y_f64, g.ptr(), g_type, g_elt, ldg, dv, dv32, dv64);
+        if (want_dk && gat_slope) with_bools(x_col, false, [&](auto BYCOL, auto) {
+            hipLaunchKernelGGL((k_sub_gat_across<decltype(BYCOL)::value>), dim3((unsigned)((nc + SGA_WAVES - 1) / SGA_WAVES)), dim3(BLOCK), 0, c->stream, x_ptr, (uint32_t)nc, cap, x_pos,
+                               (uint32_t)heads, (const double *)ds, edges, dk32.ptr(), dk32.ld(), dk64.ptr(), dk64.ld());
+        });
+        else if (want_dk) sub_across_short(c, xs, ds, true, q.ptr(), q_type, ldq, d, dk32, dk64);
+        if (want_dv) sub_across_short(c, xs, y.ptr(), y_f64, g.ptr(), g_type, ldg, dv, dv32, dv64);
     }
     if (x_lng) {
         EvSpan ev(c, EV_SUB_ATTN_LONG);
-        if (want_dk) across_long(ds, true, q.ptr(), q_type, q_elt, ldq, d, dk32, dk64);
-        if (want_dv) across_long(y.ptr(), y_f64, g.ptr(), g_type, g_elt, ldg, dv, dv32, dv64);
+        if (want_dk && gat_slope) sub_across_long(c, xs, ds, true, ones, ELT_F32, 1, 1, dk32, dk64, false);
+        else if (want_dk) sub_across_long(c, xs, ds, true, q.ptr(), q_type, ldq, d, dk32, dk64);
+        if (want_dv) sub_across_long(c, xs, y.ptr(), y_f64, g.ptr(), g_type, ldg, dv, dv32, dv64);
     }
     if (int rc = held_fetch(c, dq32, dq64, dk32, dk64, dv32, dv64)) return rc;
     if (int rc = held_call_end(c, "subgraph attention_bwd")) return rc;
@@ -4995,6 +5045,72 @@ int fora_hip_subgraph_attention_bwd(fora_ctx *c, const void *q, int q_type, int6
     HIPCHK(c, hipSetDevice(c->device));
     return drop_pairs_unless_ok(c, subgraph_attention_bwd_impl(c, e ? q : nullptr, q_type, ldq, e ? k : nullptr, k_type, ldk, e ? v : nullptr, v_type, ldv, e ? g : nullptr, g_type,
                                                                ldg, e ? y : nullptr, y_type, d, dv, heads, scale, (flags & FORA_SUB_BY_COL) != 0, *grads, info_out, ms_out));
+}
+
+// ---- EDGE GAT and EDGE GAT, BACKWARD (the contracts of include/fora_hip_edge_gat.h; the kernels in fora_subgraph_gat.h): the two
+// attention calls above with the additive score.  What is stated here is the checks of the entry points and which of el and er is
+// read at the group's node: el by row, er by column -- and so which of d el and d er is the along sum of dz.
+namespace {
+int sub_gat_checks(fora_ctx *c, const std::string &who, int el_type, int64_t ldel, int er_type, int64_t lder, int v_type, int64_t ldv, int dv, int heads, double slope, int flags) {
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(el_type) || !elt_known(er_type) || !elt_known(v_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (dv < 1 || heads < 1) return fail(c, FORA_E_ARG, who + "dv or heads below 1");
+    if ((int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, who + "heads * dv above 65536");
+    if (ldel < heads || lder < heads || ldv < (int64_t)heads * dv) return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(slope)) return fail(c, FORA_E_ARG, who + "slope is not finite");
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_gat(fora_ctx *c, const void *el, int el_type, int64_t ldel, const void *er, int er_type, int64_t lder, const void *v, int v_type, int64_t ldv,
+                          int dv, int heads, double slope, int flags, float *out32, double *out64, int64_t ldo, float *y32, double *y64, uint64_t ycap,
+                          int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph gat: ";
+    if (int rc = sub_gat_checks(c, who, el_type, ldel, er_type, lder, v_type, ldv, dv, heads, slope, flags)) return rc;
+    if (ldo < (int64_t)heads * dv) return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + "no output");
+    if ((y32 || y64) && ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    if (c->sp.cols && c->sb.edges && (!el || !er || !v)) return fail(c, FORA_E_ARG, who + "null operand");
+    if (info_out) { memset(info_out, 0, 5 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool by_col = (flags & FORA_SUB_BY_COL) != 0;
+    const int rc = by_col ? subgraph_attention_impl(c, er, er_type, lder, el, el_type, ldel, v, v_type, ldv, 1, dv, heads, 1.0, true, out32, out64, ldo, y32, y64, info_out, ms_out, &slope)
+                          : subgraph_attention_impl(c, el, el_type, ldel, er, er_type, lder, v, v_type, ldv, 1, dv, heads, 1.0, false, out32, out64, ldo, y32, y64, info_out, ms_out, &slope);
+    return drop_pairs_unless_ok(c, rc);
+}
+
+int fora_hip_subgraph_gat_bwd(fora_ctx *c, const void *el, int el_type, int64_t ldel, const void *er, int er_type, int64_t lder, const void *v, int v_type, int64_t ldv,
+                              const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap, int dv, int heads, double slope, int flags,
+                              const fora_attn_grads *grads, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph gat_bwd: ";
+    if (int rc = sub_gat_checks(c, who, el_type, ldel, er_type, lder, v_type, ldv, dv, heads, slope, flags)) return rc;
+    if (!elt_known(g_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + "y_type is neither f32 nor f64");
+    if (ldg < (int64_t)heads * dv) return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (!grads) return fail(c, FORA_E_ARG, who + "no output");
+    const bool want_el = grads->dq32 || grads->dq64, want_er = grads->dk32 || grads->dk64, want_dv = grads->dv32 || grads->dv64;
+    if (!want_el && !want_er && !want_dv) return fail(c, FORA_E_ARG, who + "no output");
+    if ((want_el && grads->lddq < heads) || (want_er && grads->lddk < heads) || (want_dv && grads->lddv < (int64_t)heads * dv))
+        return fail(c, FORA_E_ARG, who + "lddq or lddk smaller than heads, or lddv smaller than heads * dv");
+    if (ycap / (uint64_t)heads < c->sb.edges || ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    const bool e = c->sp.cols && c->sb.edges;
+    if (e && (!el || !er || !v || !g || !y)) return fail(c, FORA_E_ARG, who + "null el, er, v, g or y");
+    if (info_out) { memset(info_out, 0, 6 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!e) el = er = v = g = y = nullptr;
+    const bool by_col = (flags & FORA_SUB_BY_COL) != 0;
+    fora_attn_grads gr = *grads; // by column the group's operand is er: d er is the along sum, d el the across one
+    if (by_col) { std::swap(gr.dq32, gr.dk32); std::swap(gr.dq64, gr.dk64); std::swap(gr.lddq, gr.lddk); }
+    const int rc = by_col ? subgraph_attention_bwd_impl(c, er, er_type, lder, el, el_type, ldel, v, v_type, ldv, g, g_type, ldg, y, y_type, 1, dv, heads, 1.0, true, gr, info_out, ms_out, &slope)
+                          : subgraph_attention_bwd_impl(c, el, el_type, ldel, er, er_type, lder, v, v_type, ldv, g, g_type, ldg, y, y_type, 1, dv, heads, 1.0, false, gr, info_out, ms_out, &slope);
+    return drop_pairs_unless_ok(c, rc);
 }
 
 // ---- ROW STORE (the contract of include/fora_hip.h; kernels in fora_store.h, the plan in fora_store_plan.h)

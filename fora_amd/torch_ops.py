@@ -451,6 +451,54 @@ def subgraph_attention_trained(engine, Q, K, V, heads=1, scale=None, direction="
     return _SubgraphAttentionTrained.apply(Q, K, V, engine, scale, heads, direction == "in")
 
 
+class _SubgraphGat(torch.autograd.Function):
+    """out = graph attention over the held subgraph in one call (Engine.subgraph_gat), y32 saved; the backward pass is ONE call
+    for all heads (Engine.subgraph_gat_bwd) on it, for the gradients autograd asks for"""
+
+    @staticmethod
+    def forward(ctx, el, er, V, engine, slope, heads, inwards):
+        out32, _, y32, _, _ = engine.subgraph_gat(el.detach(), er.detach(), V.detach(), heads=heads, slope=slope, by="col" if inwards else "row",
+                                                  want32=True, want64=False, want_y32=True)
+        ctx.save_for_backward(el, er, V, y32)
+        ctx.engine, ctx.slope, ctx.heads, ctx.inwards = engine, slope, heads, inwards
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        el, er, V, y32 = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "subgraph_gat")
+        need_l, need_r, need_v = ctx.needs_input_grad[:3]
+        if not (need_l or need_r or need_v):
+            return None, None, None, None, None, None, None
+        dl, _, dr, _, dV, _, stats = engine.subgraph_gat_bwd(el.detach(), er.detach(), V.detach(), _dense_operand(G), y32, heads=ctx.heads, slope=ctx.slope,
+                                                             by="col" if ctx.inwards else "row", want_del=need_l, want_der=need_r, want_dv=need_v,
+                                                             want32=True, want64=False)
+        engine.last_subgraph_gat_bwd = stats
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dl, el), cast(dr, er), cast(dV, V), None, None, None, None
+
+
+def subgraph_gat(engine, el, er, V, heads=1, slope=0.2, direction="out"):
+    """A graph attention network's layer over the sampled graph in two library calls (Engine.subgraph_gat and, backward,
+    Engine.subgraph_gat_bwd; the EDGE GAT contracts): the score of edge e is LeakyReLU(el[row of e] + er[sub_col[e]]) with the
+    negative slope `slope`, per head -- el = (feat * attn_l).sum(-1) and er = (feat * attn_r).sum(-1) of a GATConv layer.
+    direction="out": node j attends over its out-edges, out[j] = sum over the edges e of row j of y[e] * V[sub_col[e]];
+    direction="in": node v over its in-edges, out[v] = sum over the edges e with sub_col[e] == v of y[e] * V[row of e]; y the
+    softmax of the scores over the node's edges.  el, er: [nc, heads], V: [nc, heads * dv], float32, bfloat16 or float16
+    tensors on the engine's GPU (FP8 as constants).  Returns float32 [nc, heads * dv], differentiable in el, er and V; nothing
+    is rounded to float32 between the steps of either pass.  The subgraph must still be held when the backward pass runs; its
+    stats are left in engine.last_subgraph_gat_bwd."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_gat: direction is "out" or "in"')
+    if heads < 1 or el.dim() != 2 or er.dim() != 2 or V.dim() != 2 or el.shape[1] != heads or er.shape[1] != heads or V.shape[1] % heads:
+        raise ValueError("subgraph_gat: el and er must be [nc, heads] and heads (at least 1) divide the columns of V")
+    _refuse_fp8_grad("subgraph_gat", el=el, er=er, V=V)
+    return _SubgraphGat.apply(el, er, V, engine, float(slope), heads, direction == "in")
+
+
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
     the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32, bfloat16 or float16 tensors (or constant FP8 ones) on the engine's GPU with a column
