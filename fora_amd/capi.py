@@ -290,6 +290,16 @@ int  fora_hip_subgraph_gat_bwd(ctx*, ptr, int, int64, ptr, int, int64, ptr, int,
 ABI_EDGE_GAT = _rows(_ABI_EDGE_GAT)
 EDGE_GAT_SYMBOLS = list(ABI_EDGE_GAT)
 
+# the entry points of include/fora_hip_pool.h, max / min pooling over the neighbours in the held subgraph, forward and backward: a
+# ninth table (the censuses of the eight headers above are pinned); tests/test_subgraph_pool_cpu.py derives it from that header again
+_ABI_POOL = """
+int  fora_hip_subgraph_pool(ctx*, ptr, int, int, int64, int, ptr, ptr, int64, ptr, int64, ptr, ptr)
+int  fora_hip_subgraph_pool_bwd(ctx*, ptr, int, int, int64, int, ptr, int64, ptr, ptr, int64, ptr, ptr)
+"""
+ABI_POOL = _rows(_ABI_POOL)
+POOL_SYMBOLS = list(ABI_POOL)
+POOL_MIN = 4  # FORA_POOL_MIN
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -327,7 +337,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()) + list(ABI_POOL.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -699,6 +709,76 @@ class Engine:
         the edge's place in sub_col; mean divides by a column's number of edges.  Operands, outputs and stats as for
         subgraph_propagate; the first transposed call on a held subgraph builds its transposition (stats["built"] == 1)."""
         return self._subgraph_product(self._lib.fora_hip_subgraph_propagate_t, "subgraph_propagate_t", G, values, mean, want32, want64, out32, out64, bf16)
+
+    # ---- max / min pooling over the neighbours in the held subgraph (the SUBGRAPH POOL contract of include/fora_hip_pool.h)
+    def _pool_arg(self, arg, nc, d, on_dev, make):
+        """(arg, pointer, lda) of the [nc, d] int32 arg of subgraph_pool / subgraph_pool_bwd: the caller's, or with make one made
+        where the operand lives; it must live there"""
+        if arg is None and not make:
+            return None, None, d
+        if arg is None:
+            if on_dev:
+                import torch
+                arg = torch.empty((nc, d), dtype=torch.int32, device=torch.device("cuda", self.device))
+            else:
+                arg = np.zeros((nc, d), dtype=np.int32)
+        if on_dev:
+            import torch
+            ptr, lda = self._prop_out(arg, nc, d, torch.int32, True, "arg")
+        else:
+            ptr, lda = self._prop_out(arg, nc, d, np.int32, False, "arg")
+        return arg, ptr, lda
+
+    def _pool_flags(self, who, op, by):
+        if op not in ("max", "min") or by not in ("row", "col"):
+            raise ValueError(f'{who}: op is "max" or "min", by is "row" or "col"')
+        return (POOL_MIN if op == "min" else 0) | (SUB_BY_COL if by == "col" else 0)
+
+    @staticmethod
+    def _pool_stats(edges, info, ms):
+        return {"edges": edges, "built": int(info[0]), "long_rows": int(info[1]), "chunks": int(info[2]), "x_on_device": int(info[3]),
+                "transpose_ms": ms[0], "short_ms": ms[1], "long_ms": ms[2]}
+
+    def subgraph_pool(self, X, op="max", by="row", want32=True, want64=False, want_arg=True, out32=None, out64=None, arg=None, bf16=False):
+        """out[j, c] = the maximum (op="min": the minimum) of X[src(e), c] over the group of node j in the held subgraph, and
+        arg[j, c] = the edge e that gave it (fora_hip_subgraph_pool, the SUBGRAPH POOL contract of include/fora_hip_pool.h).
+        by="row": the group is the edges of row j of sparse_subgraph's CSR, src = sub_col[e] -- the out-neighbours; by="col": the
+        edges whose target is j in ascending e, src their row -- the in-neighbours.  An edge is named by its place in sub_col
+        under both.  The winner is the first entry under a total order -- a NaN before every number, then the larger (smaller)
+        value, -0.0 and +0.0 equal, every tie to the smaller e -- so every bit is defined; a NaN winner is written as the
+        quiet NaN, an empty group as +0.0 with arg -1.  X: [nc, d] with the conventions of subgraph_propagate.  Returns
+        (out32 or None, out64 or None, arg or None, stats dict): torch tensors with a torch X, numpy arrays otherwise; arg is
+        int32 [nc, d]; out32 / out64 / arg: caller-made outputs (a column slice is written in place).  stats as for
+        subgraph_propagate (chunks: 1 where groups longer than "sub_short" exist -- they take one launch)."""
+        flags = self._pool_flags("subgraph_pool", op, by)
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_pool: no subgraph is held (sparse_subgraph first)")
+        xptr, xtype, d, ldx, on_dev, _keep = self._prop_feat(X, bf16, rows=nc, name="X", shape="[nc, d] (nc: the held columns)")
+        arg, aptr, lda = self._pool_arg(arg, nc, d, on_dev, want_arg)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, d, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
+        self._chk(self._lib.fora_hip_subgraph_pool(self._ctx, xptr, xtype, d, ldx, flags, p32, p64, ldo, aptr, lda, info, ms))
+        return out32, out64, arg, self._pool_stats(edges, info, ms)
+
+    def subgraph_pool_bwd(self, G, arg, by="row", want32=True, want64=False, out32=None, out64=None, bf16=False):
+        """The gradient of subgraph_pool with respect to X (fora_hip_subgraph_pool_bwd): out[u, c] = the sum, over the edges e
+        that have u as their source in the forward call's grouping `by`, in ascending e, of G[j(e), c] where arg[j(e), c] == e
+        and of +0.0 elsewhere -- the whole gradient of an output element goes to the one edge arg names; the sum is ordered as
+        every product on the held subgraph is.  G: [nc, d] as X; arg: the forward call's, int32 [nc, d] where G lives.  An arg
+        entry that names no edge of its group adds nothing.  Returns (out32 or None, out64 or None, stats dict)."""
+        flags = self._pool_flags("subgraph_pool_bwd", "max", by)
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_pool_bwd: no subgraph is held (sparse_subgraph first)")
+        gptr, gtype, d, ldg, on_dev, _keep = self._prop_feat(G, bf16, rows=nc, name="G", shape="[nc, d] (nc: the held columns)")
+        if arg is None:
+            raise ValueError("subgraph_pool_bwd: arg is the forward call's, not None")
+        arg, aptr, lda = self._pool_arg(arg, nc, d, on_dev, False)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, d, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 4)(), (C.c_double * 3)()
+        self._chk(self._lib.fora_hip_subgraph_pool_bwd(self._ctx, gptr, gtype, d, ldg, flags, aptr, lda, p32, p64, ldo, info, ms))
+        return out32, out64, self._pool_stats(edges, info, ms)
 
     # ---- scores per edge of the held subgraph (the EDGE SCORES contract of include/fora_hip_edge.h)
     def subgraph_sddmm(self, a, b, heads=1, want32=True, want64=False, out32=None, out64=None, a_bf16=False, b_bf16=False):

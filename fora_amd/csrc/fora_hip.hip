@@ -27,7 +27,9 @@
 #include "fora_subgraph_attn.h"
 #include "fora_subgraph_attn_bwd.h"
 #include "fora_subgraph_gat.h"
+#include "fora_subgraph_pool.h"
 #include "../../include/fora_hip_edge_gat.h"
+#include "../../include/fora_hip_pool.h"
 
 #include <algorithm>
 #include <cassert>
@@ -50,7 +52,8 @@ namespace {
 enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_BATCH, EV_PUSH_ACCUM, EV_WALK_ACCUM, EV_ROUND_SWEEP,
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
               EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
-              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG, EV_SUB_ATTN_SHORT, EV_SUB_ATTN_LONG };
+              EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG, EV_SUB_ATTN_SHORT, EV_SUB_ATTN_LONG,
+              EV_POOL_T, EV_POOL_SHORT, EV_POOL_LONG };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -369,6 +372,7 @@ struct PropBufs {
     DevBuf<unsigned char> d_feat, d_a, d_vals, d_v, d_g;
     // outputs on their way to host arrays (HeldOut::reserve): the nq-row or per-entry output of every call (dq too); y; dk; dv
     DevBuf<float> d_out32, d_y32, d_dk32, d_dv32; DevBuf<double> d_out64, d_y64, d_dk64, d_dv64;
+    DevBuf<int32_t> d_arg;                               // SUBGRAPH POOL: arg on its way to a host array
     // scratch of the launches
     DevBuf<PropSeg> d_segs; DevBuf<PropRowRec> d_recs;   // the call's plan (fora_prop_plan.h)
     DevBuf<double> d_part; DevBuf<uint64_t> d_segsum;    // partial sums [prop_segs][d] and word sums [prop_segs] of the chunk in progress
@@ -444,6 +448,9 @@ struct SubProp {
         bool at_planned = false; uint32_t at_cap = 0, at_sm_cap = 0; uint64_t at_per = 0, at_short = 0; // (at_short: the non-empty groups of at most at_cap edges)
         PropPlan at_plan; uint64_t at_sm_short = 0, at_sm_long = 0, at_lrows = 0, at_longest = 0;
         DevBuf<PropSeg> d_at_segs; DevBuf<PropRowRec> d_at_recs;
+        // SUBGRAPH POOL: the groups longer than pool_cap, one workgroup each (k_sub_pool_long), made under a value of "sub_short"
+        bool pool_listed = false; uint32_t pool_cap = 0; uint64_t pool_long = 0;
+        DevBuf<int32_t> d_pool_list;
     } fwd, tr;
     bool t_built = false;
     DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row; // [nc + 1], [edges], [edges]: the entries column by column
@@ -488,7 +495,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0, sub_attn_short_ms = 0, sub_attn_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0, sub_attn_short_ms = 0, sub_attn_long_ms = 0, pool_t_ms = 0, pool_short_ms = 0, pool_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -1075,6 +1082,9 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_SUB_SMAX_LONG: t.sub_smax_long_ms += ms; break;   // the k_sub_softmax_seg_* / _div launches of their longer groups: ms_out[1] only
         case EV_SUB_ATTN_SHORT: t.sub_attn_short_ms += ms; break; // k_sub_attn; k_sub_attn_bwd and k_sub_attn_across: ms_out[0] of fora_hip_subgraph_attention and of its _bwd only
         case EV_SUB_ATTN_LONG: t.sub_attn_long_ms += ms; break;   // the three steps' kernels over its longer groups, head by head: ms_out[1] only
+        case EV_POOL_T: t.pool_t_ms += ms; break;             // the transposition where a SUBGRAPH POOL call builds it: ms_out[0] of those calls only
+        case EV_POOL_SHORT: t.pool_short_ms += ms; break;     // k_sub_pool / k_sub_pool_bwd: ms_out[1] only
+        case EV_POOL_LONG: t.pool_long_ms += ms; break;       // k_sub_pool_long; k_sub_pool_bwd_seg and the combines behind it: ms_out[2] only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -2657,6 +2667,8 @@ struct PropSide {
     const void *values = nullptr; bool val64 = false; // PROPAGATE WITH VALUES: the weights (device; null: the words), f64 or f32
     const int64_t *pos = nullptr;            // (device) with values, transposed: the held place of every entry; forward: null
     bool unit = false;                       // SUBGRAPH PRODUCTS without values: every weight 1.0, fix is not read
+    const int32_t *pool_arg = nullptr; int64_t pool_lda = 0; bool pool_wide = false; // SUBGRAPH POOL, BACKWARD: the gather is the select-add of
+                                             // k_sub_pool_bwd_seg over arg (device; pos: the edge of every entry, null: its own place)
 };
 struct PropRunStats { uint64_t segments = 0, max_row = 0; int32_t chunks = 0, feat_on_device = 0; };
 
@@ -2664,7 +2676,9 @@ template <int ET, int V>
 void prop_launch_gather(fora_ctx *c, const PropGeom &g, const PropSeg *segs, uint64_t nseg, const PropSide &sd, const void *feat, int64_t ldf, int d, double *part, uint64_t *segsum) {
     const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
     const dim3 grid((unsigned)((nseg + per_wg - 1) / per_wg), g.tiles);
-    if (sd.values) with_bools(sd.pos != nullptr, sd.val64, [&](auto POS, auto V64) {
+    if (sd.pool_arg) hipLaunchKernelGGL((k_sub_pool_bwd_seg<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.pos, feat, ldf, (uint32_t)d, g.G, sd.pool_arg, sd.pool_lda,
+                                        sd.pool_wide ? 1u : 0u, part);
+    else if (sd.values) with_bools(sd.pos != nullptr, sd.val64, [&](auto POS, auto V64) {
         hipLaunchKernelGGL((k_prop_gather_vals<ET, V, POS.value, V64.value>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, sd.values, sd.pos, feat, ldf, (uint32_t)d, g.G, part);
     });
     else if (sd.unit) hipLaunchKernelGGL((k_sub_gather_one<ET, V>), grid, dim3(BLOCK), 0, c->stream, segs, nseg, sd.ids, feat, ldf, (uint32_t)d, g.G, part);
@@ -4240,7 +4254,7 @@ namespace {
 // the transposition of the held subgraph: counts, the host's prefix sum, places, every column's keys sorted on the tiers of
 // PROPAGATE, TRANSPOSED (a key is sub_key(row, place in the row), so a multi-edge's two entries keep the order of their places),
 // then in_row and in_pos.  Complete or absent: built in locals, moved into SubBufs::prop after the last step.
-int subt_build(fora_ctx *c) {
+int subt_build(fora_ctx *c, EvKind kind) {
     SubBufs &b = c->sb;
     const uint64_t nc = c->sp.cols, edges = b.edges;
     DevBuf<int64_t> d_in_ptr, d_in_pos; DevBuf<int32_t> d_in_row;
@@ -4260,7 +4274,7 @@ int subt_build(fora_ctx *c) {
         const uint32_t wgs = (uint32_t)std::min<uint64_t>(nc, 65535);
         const int64_t *sub_ptr = b.d_ptr.get();
         const int32_t *sub_col = b.d_col.get();
-        EvSpan ev(c, EV_SUBP_T);
+        EvSpan ev(c, kind);
         HIPCHK(c, d_cnt.zero(c->stream, (size_t)nc));
         hipLaunchKernelGGL(k_subt_count, dim3(wgs), dim3(BLOCK), 0, c->stream, sub_ptr, (uint32_t)nc, sub_col, d_cnt.get());
         HIPCHK(c, hipMemcpyAsync(h_cnt.get(), d_cnt.get(), (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
@@ -4299,10 +4313,10 @@ int subt_build(fora_ctx *c) {
     p.t_built = true; b.prop_used = true;
     return FORA_OK;
 }
-int subt_ensure(fora_ctx *c, bool &built_now) {
+int subt_ensure(fora_ctx *c, bool &built_now, EvKind kind = EV_SUBP_T) { // (kind: whose ms_out the build is timed under)
     built_now = false;
     if (c->sb.prop.t_built) return FORA_OK;
-    if (int rc = subt_build(c)) return rc;
+    if (int rc = subt_build(c, kind)) return rc;
     built_now = true;
     return FORA_OK;
 }
@@ -4446,6 +4460,144 @@ int fora_hip_subgraph_transpose_fetch(fora_ctx *c, int64_t *in_ptr, int32_t *in_
     if (in_row && edges) HIPCHK(c, hipMemcpyAsync(in_row, p.d_in_row.get(), (size_t)edges * 4, hipMemcpyDefault, c->stream));
     if (in_pos && edges) HIPCHK(c, hipMemcpyAsync(in_pos, p.d_in_pos.get(), (size_t)edges * 8, hipMemcpyDefault, c->stream));
     return held_call_end(c, "subgraph transpose fetch", false);
+}
+
+// ---- SUBGRAPH POOL (the contract of include/fora_hip_pool.h; the kernels in fora_subgraph_pool.h): the frame of SUBGRAPH PRODUCTS
+// with another reduction.  Forward a group is short (k_sub_pool) or has a workgroup of its own (k_sub_pool_long, over a list
+// kept with the side); backward the across side is split and planned exactly as a product's, and k_prop_combine adds up what
+// k_sub_pool_bwd_seg leaves.
+static_assert((FORA_POOL_MIN & (FORA_SUB_MEAN | FORA_SUB_BY_COL)) == 0, "the flags of SUBGRAPH POOL are bits of their own");
+namespace {
+// the side's groups longer than cap, as a list on the device: made when the cap moves, kept otherwise
+int pool_side_list(fora_ctx *c, SubProp::Side &s, uint32_t cap) {
+    if (s.pool_listed && s.pool_cap == cap) return FORA_OK;
+    s.pool_listed = false;
+    std::vector<int32_t> list;
+    for (uint64_t i = 0; i < c->sp.cols; i++)
+        if (!sub_row_short((uint64_t)(s.h_ptr[i + 1] - s.h_ptr[i]), cap)) list.push_back((int32_t)i);
+    if (int rc = prop_ensure(c, s.d_pool_list, list.size(), "the long groups' list")) return rc;
+    if (!list.empty()) HIPCHK(c, hipMemcpy(s.d_pool_list.get(), list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    s.pool_cap = cap; s.pool_long = list.size(); s.pool_listed = true; c->sb.prop_used = true;
+    return FORA_OK;
+}
+// nc > 0; the arguments have passed pool_entry.  Forward: arg_out may be null; backward: arg_in is not.
+int subgraph_pool_impl(fora_ctx *c, bool bwd, const void *x, int x_type, int d, int64_t ldx, int flags, const int32_t *arg_in, int32_t *arg_out, int64_t lda,
+                       float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols;
+    const char *who = bwd ? "subgraph pool_bwd" : "subgraph pool";
+    const uint32_t elt = elt_bytes(x_type);
+    const bool by_col = (flags & FORA_SUB_BY_COL) != 0;
+    const bool transposed = by_col != bwd; // the side whose groups are summed or searched: the columns forward by column and backward by row
+    HeldIn feat = HeldIn::matrix(x, nc, ldx, (uint64_t)d, elt), ain = HeldIn::matrix(arg_in, nc, lda, (uint64_t)d, 4);
+    HeldOut<float> o32{out32, ldo, nc, (uint64_t)d};
+    HeldOut<double> o64{out64, ldo, nc, (uint64_t)d};
+    HeldOut<int32_t> oarg{arg_out, lda, nc, (uint64_t)d};
+    if (int rc = held_resolve(c, feat, ain, o32, o64, oarg)) return rc; // (before anything is built)
+    c->tm.pool_t_ms = c->tm.pool_short_ms = c->tm.pool_long_ms = 0;
+    bool built_now = false;
+    if (transposed) if (int rc = subt_ensure(c, built_now, EV_POOL_T)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &side = transposed ? sp.tr : sp.fwd;
+    const uint32_t cap = sub_short_cap(c->opt_.sub_short);
+    if (int rc = sub_side_ptr(c, side)) return rc;
+    // ---- the split; backward also the plan of the long groups, as a product makes it
+    uint64_t long_rows = 0, per = 1, chunks = 0;
+    if (bwd) {
+        if (!side.planned || side.cap != cap) { side.split = sub_split(side.h_ptr.data(), (int)nc, cap); side.planned = false; side.cap = cap; }
+        long_rows = side.split.long_rows;
+        if (long_rows) {
+            size_t fr = 0, tot = 0;
+            if (c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+            per = prop_chunk_segs(c->opt_.prop_segs, side.split.long_segs, (uint64_t)fr, d);
+        }
+        if (int rc = sub_side_plan(c, side, cap, per)) return rc;
+        chunks = long_rows ? side.plan.chunks.size() : 0;
+    } else {
+        if (int rc = pool_side_list(c, side, cap)) return rc;
+        long_rows = side.pool_long;
+        chunks = long_rows ? 1 : 0;
+    }
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = feat.stage(c, pb.d_feat, "the operand's upload")) return rc;
+    if (int rc = ain.stage(c, pb.d_a, "the upload of arg")) return rc;
+    if (bwd && long_rows) {
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)d), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)d, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = oarg.reserve(c, pb.d_arg)) return rc;
+    const PropGeom g = prop_geom((uint64_t)(uintptr_t)feat.ptr(), ldx, d, elt, prop_widths_bytes(elt), PROP_NWIDTHS);
+    const int64_t *ptr = transposed ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *ids = transposed ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *pos = transposed ? sp.d_in_pos.get() : nullptr; // the edge of an entry of the transposition; forward it is the entry's own place
+    const int32_t *arg = (const int32_t *)ain.ptr();
+    const uint32_t aw = std::min<uint32_t>(g.V, 4); // the words of one load of arg: base and pitch aligned to them, or one word at a time
+    const bool wide = bwd && (uint64_t)(uintptr_t)arg % (4ull * aw) == 0 && lda % (int64_t)aw == 0;
+    const uint32_t neg = (flags & FORA_POOL_MIN) ? 1u : 0u;
+    if (nc > long_rows) {
+        EvSpan ev(c, EV_POOL_SHORT);
+        const uint64_t per_wg = (uint64_t)g.segs_per_wave * (BLOCK / 64);
+        const dim3 grid((unsigned)((nc + per_wg - 1) / per_wg), g.tiles);
+        with_vec(x_type, g.V, [&](auto E, auto V) {
+            if (bwd) hipLaunchKernelGGL((k_sub_pool_bwd<E.value, V.value>), grid, dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids, pos, feat.ptr(), ldx, (uint32_t)d, g.G, arg, lda,
+                                        wide ? 1u : 0u, o32.ptr(), o32.ld(), o64.ptr(), o64.ld());
+            else hipLaunchKernelGGL((k_sub_pool<E.value, V.value>), grid, dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap, ids, pos, feat.ptr(), ldx, (uint32_t)d, g.G, neg, o32.ptr(),
+                                    o32.ld(), o64.ptr(), o64.ld(), oarg.ptr(), oarg.ld());
+        });
+    }
+    if (long_rows) {
+        EvSpan ev(c, EV_POOL_LONG);
+        if (bwd) {
+            PropSide sd{side.h_ptr.data(), (int)nc, ids, nullptr, nullptr, false, nullptr, false, pos, false};
+            sd.pool_arg = arg; sd.pool_lda = lda; sd.pool_wide = wide;
+            prop_launch_chunks(c, side.plan, side.d_segs.get(), side.d_recs.get(), sd, x_type, g, feat.ptr(), ldx, d, nullptr, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), false);
+        } else {
+            const dim3 grid((unsigned)long_rows, g.tiles);
+            const size_t lds = (size_t)(BLOCK / 64 - 1) * g.G * g.V * 12;
+            with_vec(x_type, g.V, [&](auto E, auto V) {
+                hipLaunchKernelGGL((k_sub_pool_long<E.value, V.value>), grid, dim3(BLOCK), lds, c->stream, ptr, (const int32_t *)side.d_pool_list.get(), ids, pos, feat.ptr(), ldx, (uint32_t)d,
+                                   g.G, neg, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), oarg.ptr(), oarg.ld());
+            });
+        }
+    }
+    if (int rc = held_fetch(c, o32, o64, oarg)) return rc;
+    if (int rc = held_call_end(c, who)) return rc;
+    if (info_out) { info_out[0] = built_now ? 1 : 0; info_out[1] = (int64_t)long_rows; info_out[2] = (int64_t)chunks; info_out[3] = feat.on_device(); }
+    if (ms_out) { ms_out[0] = c->tm.pool_t_ms; ms_out[1] = c->tm.pool_short_ms; ms_out[2] = c->tm.pool_long_ms; }
+    return FORA_OK;
+}
+int pool_entry(fora_ctx *c, bool bwd, const void *x, int x_type, int d, int64_t ldx, int flags, const int32_t *arg_in, int32_t *arg_out, int64_t lda,
+               float *out32, double *out64, int64_t ldo, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = bwd ? "subgraph pool_bwd" : "subgraph pool";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + ": no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(x_type)) return fail(c, FORA_E_ARG, who + ": unknown element type");
+    if (flags & ~(FORA_SUB_BY_COL | FORA_POOL_MIN)) return fail(c, FORA_E_ARG, who + ": unknown flag");
+    if (d < 1 || d > 65536) return fail(c, FORA_E_ARG, who + ": d outside 1 .. 65536");
+    if (ldx < d || ldo < d || ((arg_in || arg_out) && lda < d)) return fail(c, FORA_E_ARG, who + ": a leading dimension smaller than d");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + ": no output");
+    if (bwd && !arg_in) return fail(c, FORA_E_ARG, who + ": null arg");
+    if (c->sp.cols && !x) return fail(c, FORA_E_ARG, who + ": null operand");
+    if ((arg_in || arg_out) && c->sb.edges >= (1ull << 31)) return fail(c, FORA_E_ARG, who + ": arg names an edge in 31 bits; the held subgraph has more");
+    if (info_out) memset(info_out, 0, 4 * sizeof(int64_t));
+    if (ms_out) memset(ms_out, 0, 3 * sizeof(double));
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    return drop_pairs_unless_ok(c, subgraph_pool_impl(c, bwd, x, x_type, d, ldx, flags, arg_in, arg_out, lda, out32, out64, ldo, info_out, ms_out));
+}
+} // namespace
+
+int fora_hip_subgraph_pool(fora_ctx *c, const void *x, int x_type, int d, int64_t ldx, int flags, float *out32, double *out64, int64_t ldo, int32_t *arg, int64_t lda,
+                           int64_t *info_out, double *ms_out) {
+    return pool_entry(c, false, x, x_type, d, ldx, flags, nullptr, arg, lda, out32, out64, ldo, info_out, ms_out);
+}
+int fora_hip_subgraph_pool_bwd(fora_ctx *c, const void *g, int g_type, int d, int64_t ldg, int flags, const int32_t *arg, int64_t lda, float *out32, double *out64, int64_t ldo,
+                               int64_t *info_out, double *ms_out) {
+    return pool_entry(c, true, g, g_type, d, ldg, flags, arg, nullptr, lda, out32, out64, ldo, info_out, ms_out);
 }
 
 // ---- EDGE SCORES (the contract of include/fora_hip_edge.h; the kernel in fora_subgraph_sddmm.h).  No plan, no table, nothing kept:

@@ -199,6 +199,44 @@ def _as_leaf_dtype(g, X):
     return g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
 
 
+class _SubgraphPool(torch.autograd.Function):
+    """Y = max / min of X over each node's group of the held subgraph; dX = the one backward call over the arg the forward kept"""
+
+    @staticmethod
+    def forward(ctx, X, engine, op, by):
+        out32, _, arg, _ = engine.subgraph_pool(X.detach(), op=op, by=by, want32=True, want64=False, want_arg=True)
+        ctx.engine, ctx.by, ctx.arg, ctx.leaf = engine, by, arg, X.new_empty(0)   # (arg: int32 [nc, d] on the device; leaf: X's dtype)
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        _held_guard(ctx.generation, ctx.engine, "subgraph_pool")
+        out32, _, _ = ctx.engine.subgraph_pool_bwd(_dense_operand(G), ctx.arg, by=ctx.by, want32=True, want64=False)
+        return _as_leaf_dtype(out32, ctx.leaf), None, None, None
+
+
+def subgraph_pool(engine, X, op="max", direction="out"):
+    """Max or min pooling over the subgraph `engine` holds (Engine.sparse_subgraph) as a differentiable torch operation: Y[j, c] =
+    the maximum (op="min": the minimum) of X[v, c] over the out-neighbours v of node j inside the batch (direction "out":
+    Engine.subgraph_pool by row) or over its in-neighbours ("in": by column); a node without neighbours gets 0.  X: [nc, d]
+    (nc = engine.held_cols) float32, bfloat16 or float16 on the engine's GPU (or FP8 as a constant: one that requires grad is a
+    ValueError), column stride one element.  Returns Y [nc, d] float32 on the device.
+    The tie rule: the winner of (j, c) is the FIRST edge of the group -- by its place in sub_col -- among those that hold the
+    extreme value, -0.0 and +0.0 counting as equal; a NaN beats every number, the first NaN wins.  The backward pass gives the
+    WHOLE gradient G[j, c] to that first extremal edge's source node and nothing to the others that tie with it.  This differs
+    from torch.scatter_reduce(..., "amax" / "amin"), whose backward pass splits the gradient evenly over the tied entries;
+    here X.grad is an ordered float64 sum per element, rounded once, so every bit of it is defined.  The forward pass keeps
+    the winners as an int32 tensor on the device, and the backward pass is one call over it.  The subgraph must still be held
+    when the backward pass runs: a call that replaces or clears the held rows in between makes it raise."""
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_pool: direction is "out" or "in"')
+    if op not in ("max", "min"):
+        raise ValueError('subgraph_pool: op is "max" or "min"')
+    _refuse_fp8_grad("subgraph_pool", X=X)
+    return _SubgraphPool.apply(X, engine, op, "row" if direction == "out" else "col")
+
+
 class _SubgraphSddmm(torch.autograd.Function):
     """scores[h] = sddmm over the subgraph's edges of the head's column slices of A and B; per head, with g_h the gradient of
     its scores as values: dA[:, slice] = A_S(g_h) x B[:, slice], dB[:, slice] = A_S(g_h)^T x A[:, slice], written in place"""
