@@ -300,6 +300,14 @@ ABI_POOL = _rows(_ABI_POOL)
 POOL_SYMBOLS = list(ABI_POOL)
 POOL_MIN = 4  # FORA_POOL_MIN
 
+# the entry point of include/fora_hip_edge_gatv2.h, GATv2 attention over the held subgraph, forward: a tenth table (the censuses
+# of the nine headers above are pinned); tests/test_subgraph_gatv2_cpu.py derives it from that header again
+_ABI_EDGE_GATV2 = """
+int  fora_hip_subgraph_gatv2(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, int, int, int, double, int, ptr, ptr, int64, ptr, ptr, uint64, ptr, ptr)
+"""
+ABI_EDGE_GATV2 = _rows(_ABI_EDGE_GATV2)
+EDGE_GATV2_SYMBOLS = list(ABI_EDGE_GATV2)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -337,7 +345,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()) + list(ABI_POOL.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()) + list(ABI_POOL.items()) + list(ABI_EDGE_GATV2.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -1037,6 +1045,46 @@ class Engine:
                                                       C.byref(gr), info, ms))
         return (*outs, {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]), "across_short": int(info[3]),
                         "across_long": int(info[4]), "built": int(info[5]), "short_ms": ms[0], "long_ms": ms[1]})
+
+    # ---- GATv2 attention over the held subgraph (the EDGE GATV2 contract of include/fora_hip_edge_gatv2.h)
+    def subgraph_gatv2(self, xl, xr, att, V, heads=1, slope=0.2, by="row", want32=True, want64=False, want_y32=False, want_y64=False, out32=None, out64=None,
+                       xl_kind=False, xr_kind=False, att_kind=False, v_kind=False):
+        """out = softmax over each node's edges of sum_c att[h, c] * LeakyReLU(xl[row of e, h d + c] + xr[sub_col[e], h d + c])
+        times V, head by head, in ONE call (fora_hip_subgraph_gatv2, the EDGE GATV2 contract of include/fora_hip_edge_gatv2.h): a
+        GATv2 layer.  Bit for bit the float64 addition, LeakyReLU, multiplication and the ordered sum of subgraph_sddmm, then
+        subgraph_softmax and subgraph_propagate / subgraph_propagate_t (values=the float64 probabilities) on the heads' column
+        slices.  by="row": node j attends over its out-edges and out[j] sums V[sub_col[e]]; by="col": node u over its in-edges and
+        out[u] sums V[row of e] (the first such call builds the transposition); xl is read at the edge's row and xr at its column
+        either way, and they may be one array.  xl, xr: [nc, heads * d], att: [heads, d], V: [nc, heads * dv] (nc = held_cols), all
+        numpy arrays or all torch tensors on the context's GPU, with the conventions of subgraph_attention's operands (xl_kind /
+        xr_kind / att_kind / v_kind: True, "bf16", "e4m3", "e5m2" for numpy codes); a column slice is read in place.  Returns what
+        subgraph_gat returns: (out32 or None, out64 or None, y32 or None, y64 or None, stats dict)."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_gatv2: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError('subgraph_gatv2: by is "row" or "col"')
+        heads = int(heads)
+        wide = "[nc, heads * d] (xl, xr) or [nc, heads * dv] (nc: the held columns)"
+        x_l, x_r, v = (self._prop_feat(x, kind, rows=nc, name=name, shape=wide) for name, x, kind in (("xl", xl, xl_kind), ("xr", xr, xr_kind), ("V", V, v_kind)))
+        if heads < 1 or x_l[2] % heads or x_r[2] != x_l[2] or v[2] % heads:
+            raise ValueError("subgraph_gatv2: xl and xr must be as wide, and heads (at least 1) divide their columns and those of V")
+        d, dv = x_l[2] // heads, v[2] // heads
+        a = self._prop_feat(att, att_kind, rows=heads, name="att", shape="[heads, d]")
+        if a[2] != d:
+            raise ValueError("subgraph_gatv2: att must be [heads, d]")
+        devs = [o[4] for o in (x_l, x_r, a, v)]
+        on_dev = any(devs)
+        if on_dev and not all(devs):
+            raise ValueError("xl, xr, att and V: all torch tensors on the GPU, or all numpy arrays")
+        y32, y64, py32, py64, ycap = self._entry_outputs(heads * edges, on_dev, want_y32, want_y64, None, None)
+        out32, out64, p32, p64, ldo = self._prop_outputs(nc, heads * dv, on_dev, want32, want64, out32, out64)
+        info, ms = (C.c_int64 * 5)(), (C.c_double * 2)()
+        self._chk(self._lib.fora_hip_subgraph_gatv2(self._ctx, x_l[0], x_l[1], x_l[3], x_r[0], x_r[1], x_r[3], a[0], a[1], a[3], v[0], v[1], v[3], d, dv, heads,
+                                                    float(slope), SUB_BY_COL if by == "col" else 0, p32, p64, ldo, py32, py64, ycap, info, ms))
+        shaped = lambda y: y if y is None else y.reshape(heads, edges)
+        return out32, out64, shaped(y32), shaped(y64), {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]),
+                                                         "nan_pairs": int(info[3]), "built": int(info[4]), "short_ms": ms[0], "long_ms": ms[1]}
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -27,8 +27,10 @@
 #include "fora_subgraph_attn.h"
 #include "fora_subgraph_attn_bwd.h"
 #include "fora_subgraph_gat.h"
+#include "fora_subgraph_gatv2.h"
 #include "fora_subgraph_pool.h"
 #include "../../include/fora_hip_edge_gat.h"
+#include "../../include/fora_hip_edge_gatv2.h"
 #include "../../include/fora_hip_pool.h"
 
 #include <algorithm>
@@ -53,7 +55,7 @@ enum EvKind { EV_PUSH_POP, EV_PUSH_EXPAND, EV_WALK_ALLOC, EV_WALK, EV_OTHER, EV_
               EV_PUSH_TAIL, EV_PUSH_TEAM, EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE,
               EV_SW_COMPACT, EV_SW_SORT, EV_SW_CUT, EV_PROP_GATHER, EV_PROP_COMBINE, EV_PROPT_TRANSPOSE, EV_TK_SELECT, EV_SDDMM, EV_SOFTMAX, EV_ATTN, EV_STORE, EV_COLS, EV_SUB,
               EV_SUBP_T, EV_SUBP_SHORT, EV_SUBP_LONG, EV_SUB_SDDMM, EV_SUB_SMAX_SHORT, EV_SUB_SMAX_LONG, EV_SUB_ATTN_SHORT, EV_SUB_ATTN_LONG,
-              EV_POOL_T, EV_POOL_SHORT, EV_POOL_LONG };
+              EV_POOL_T, EV_POOL_SHORT, EV_POOL_LONG, EV_SUB_GATV2_SHORT, EV_SUB_GATV2_LONG };
 struct EvPair { hipEvent_t a, b; EvKind kind; };
 
 } // namespace
@@ -495,7 +497,7 @@ struct Timing { // event pairs of the launches (EvSpan, ev_collect) and what the
     bool profiling = true;
     std::vector<EvPair> ev_pool; size_t ev_used = 0;
     fora_timing total{};
-    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0, sub_attn_short_ms = 0, sub_attn_long_ms = 0, pool_t_ms = 0, pool_short_ms = 0, pool_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
+    double bwd_ms = 0, combine_ms = 0, sp_compact_ms = 0, seed_combine_ms = 0, sw_compact_ms = 0, sw_sort_ms = 0, sw_cut_ms = 0, prop_gather_ms = 0, prop_combine_ms = 0, propt_transpose_ms = 0, tk_select_ms = 0, sddmm_ms = 0, softmax_ms = 0, attn_ms = 0, store_ms = 0, cols_ms = 0, sub_ms = 0, subp_t_ms = 0, subp_short_ms = 0, subp_long_ms = 0, sub_sddmm_ms = 0, sub_smax_short_ms = 0, sub_smax_long_ms = 0, sub_attn_short_ms = 0, sub_attn_long_ms = 0, pool_t_ms = 0, pool_short_ms = 0, pool_long_ms = 0, sub_gatv2_short_ms = 0, sub_gatv2_long_ms = 0; // of the call in progress (EV_BWD, EV_COMBINE, EV_SP_COMPACT, EV_SEED_COMBINE)
 };
 
 struct fora_ctx {
@@ -1085,6 +1087,8 @@ void ev_collect(fora_ctx *c) { // call after the stream is idle
         case EV_POOL_T: t.pool_t_ms += ms; break;             // the transposition where a SUBGRAPH POOL call builds it: ms_out[0] of those calls only
         case EV_POOL_SHORT: t.pool_short_ms += ms; break;     // k_sub_pool / k_sub_pool_bwd: ms_out[1] only
         case EV_POOL_LONG: t.pool_long_ms += ms; break;       // k_sub_pool_long; k_sub_pool_bwd_seg and the combines behind it: ms_out[2] only
+        case EV_SUB_GATV2_SHORT: t.sub_gatv2_short_ms += ms; break; // k_sub_gatv2: ms_out[0] of fora_hip_subgraph_gatv2 only
+        case EV_SUB_GATV2_LONG: t.sub_gatv2_long_ms += ms; break;   // k_gatv2_seg and the two steps' kernels over its longer groups, head by head: ms_out[1] only
         case EV_STORE: t.store_ms += ms; break;              // k_store_take; k_store_check and the copies of a put / load: fora_store_stats only
         case EV_PROPT_TRANSPOSE: t.propt_transpose_ms += ms; break; // the k_propt_* kernels and the host's prefix sum between them: fora_propt_stats only
         }
@@ -5262,6 +5266,140 @@ int fora_hip_subgraph_gat_bwd(fora_ctx *c, const void *el, int el_type, int64_t 
     if (by_col) { std::swap(gr.dq32, gr.dk32); std::swap(gr.dq64, gr.dk64); std::swap(gr.lddq, gr.lddk); }
     const int rc = by_col ? subgraph_attention_bwd_impl(c, er, er_type, lder, el, el_type, ldel, v, v_type, ldv, g, g_type, ldg, y, y_type, 1, dv, heads, 1.0, true, gr, info_out, ms_out, &slope)
                           : subgraph_attention_bwd_impl(c, el, el_type, ldel, er, er_type, lder, v, v_type, ldv, g, g_type, ldg, y, y_type, 1, dv, heads, 1.0, false, gr, info_out, ms_out, &slope);
+    return drop_pairs_unless_ok(c, rc);
+}
+
+// ---- EDGE GATV2 (the contract of include/fora_hip_edge_gatv2.h; the kernels in fora_subgraph_gatv2.h): the frame of
+// subgraph_attention_impl with the score of GATv2.  gs is the operand read at the GROUP's node (xl by row, xr by column) and os the
+// one gathered at the other end; the groups of at most "attn_short" edges are k_sub_gatv2's, the longer ones go head by head
+// through k_gatv2_seg and the kernels of EDGE SOFTMAX and the SUBGRAPH PRODUCT on the along side's plan.
+namespace {
+// nc > 0; the arguments have passed fora_hip_subgraph_gatv2
+int subgraph_gatv2_impl(fora_ctx *c, const void *gs_, int gs_type, int64_t ldgs, const void *os_, int os_type, int64_t ldos, const void *att_, int att_type, int64_t ldatt,
+                        const void *v_, int v_type, int64_t ldv, int d, int dv, int heads, double slope, bool by_col, float *out32, double *out64, int64_t ldo,
+                        float *y32_, double *y64_, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    const uint32_t gs_elt = elt_bytes(gs_type), os_elt = elt_bytes(os_type), att_elt = elt_bytes(att_type), v_elt = elt_bytes(v_type);
+    const uint64_t wx = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of xl and xr; of v and out
+    HeldIn gs = HeldIn::matrix(gs_, nc, ldgs, wx, gs_elt), os = HeldIn::matrix(os_, nc, ldos, wx, os_elt), att = HeldIn::matrix(att_, (uint64_t)heads, ldatt, (uint64_t)d, att_elt),
+           v = HeldIn::matrix(v_, nc, ldv, wv, v_elt);
+    HeldOut<float> o32{out32, ldo, nc, wv}, y32 = HeldOut<float>::vector(y32_, (uint64_t)heads * edges);
+    HeldOut<double> o64{out64, ldo, nc, wv}, y64 = HeldOut<double>::vector(y64_, (uint64_t)heads * edges);
+    if (int rc = held_resolve(c, gs, os, att, v, o32, o64, y32, y64)) return rc; // (before anything is built)
+    c->tm.sub_gatv2_short_ms = c->tm.sub_gatv2_long_ms = 0;
+    by_col = by_col && edges; // (without an edge every group of either side is empty: nothing is transposed)
+    bool built_now = false;
+    if (by_col) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &side = by_col ? sp.tr : sp.fwd;
+    if (int rc = sub_side_ptr(c, side)) return rc;
+    // ---- the split, and for the longer groups the chunks of prop_segs segments, as subgraph_attention_impl makes them
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short);
+    const uint64_t long_segs = prop_long_segments(side.h_ptr.data(), (int)nc, cap);
+    size_t fr = 0, tot = 0;
+    if (long_segs && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t per = prop_chunk_segs(c->opt_.prop_segs, long_segs, (uint64_t)fr, dv);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing
+    if (int rc = sub_side_attn_plan(c, side, cap, per, softmax_short_cap(c->opt_.softmax_short))) return rc;
+    const bool lng = side.at_lrows != 0;
+    const uint32_t chunks = sga_chunks(heads);
+    const uint64_t wgs = sga_wgs(nc, heads), n_l = side.at_plan.segs.size(), seg_wgs = (n_l * SDDMM_UNITS + BLOCK / 64 - 1) / (BLOCK / 64);
+    if (wgs > 0x7FFFFFFFull || seg_wgs > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph gatv2: more groups or segments than one launch takes");
+    // (xl and xr may be one host array: each is staged in a buffer of its own all the same, the operands are independent)
+    if (int rc = gs.stage(c, pb.d_a, "the upload of the group's operand")) return rc;
+    if (int rc = os.stage(c, pb.d_feat, "the upload of the gathered operand")) return rc;
+    if (int rc = att.stage(c, pb.d_g, "the upload of att")) return rc;
+    if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    if (int rc = prop_ensure(c, pb.d_smax_nan, 1, "the segment maxima and sums")) return rc;
+    const bool y_scratch = by_col || !y64_; // the long groups' y of one head: in place in y64 only where that is their own order
+    if (lng) {
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(per * (uint64_t)dv), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)side.at_sm_long, "the segment maxima and sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)edges, "the scores of the longer groups")) return rc;
+        if (y_scratch) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)edges, "the y of the longer groups")) return rc;
+    }
+    if (int rc = o32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = o64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = y32.reserve(c, pb.d_y32)) return rc;
+    if (int rc = y64.reserve(c, pb.d_y64)) return rc;
+    const int64_t *ptr = by_col ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *ids = by_col ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *pos = by_col ? sp.d_in_pos.get() : nullptr;
+    const uint32_t lg = prop_group_lg((uint32_t)d), types = gatv2_types(gs_type, os_type, att_type);
+    const uint32_t *const widths = prop_widths_bytes(v_elt);
+    uint32_t nan_pairs = 0;
+    HIPCHK(c, pb.d_smax_nan.zero(c->stream, 1));
+    {
+        EvSpan ev(c, EV_SUB_GATV2_SHORT);
+        with_vec(v_type, attn_vec_width((uint64_t)(uintptr_t)v.ptr(), ldv, dv, heads, v_elt, widths, PROP_NWIDTHS), [&](auto VE, auto V) {
+            with_bools(by_col, false, [&](auto BYCOL, auto) {
+                hipLaunchKernelGGL((k_sub_gatv2<decltype(VE)::value, decltype(V)::value, decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, ptr, (uint32_t)nc, cap,
+                                   ids, pos, (uint32_t)heads, chunks, gs.ptr(), ldgs, os.ptr(), ldos, att.ptr(), ldatt, v.ptr(), ldv, (uint32_t)d, (uint32_t)dv, lg, slope, edges,
+                                   o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), y32.ptr(), y64.ptr(), pb.d_smax_nan.get(), types);
+            });
+        });
+    }
+    if (lng) {
+        EvSpan ev(c, EV_SUB_GATV2_LONG);
+        const PropPlan &plan = side.at_plan;
+        const PropSeg *const segs = side.d_at_segs.get(), *const sm_segs = segs + n_l, *const lrows = sm_segs + side.at_sm_short + side.at_sm_long;
+        const SoftmaxWork w{sm_segs, sm_segs + side.at_sm_short, side.at_sm_short, side.at_sm_long, pb.d_smax.get(), pb.d_smax.get() + side.at_sm_long, pb.d_smax_nan.get()};
+        const dim3 nan_grid((unsigned)((dv + BLOCK - 1) / BLOCK), (unsigned)std::min<uint64_t>(side.at_lrows, 65535));
+        const dim3 y_grid((unsigned)std::min<uint64_t>((side.at_longest + BLOCK - 1) / BLOCK, 1024), (unsigned)std::min<uint64_t>(side.at_lrows, 65535));
+        for (int h = 0; h < heads; h++) { // one head at a time through the two per-edge buffers
+            const void *gh = attn_cols(gs.ptr(), (uint64_t)h * d, gs_elt), *oh = attn_cols(os.ptr(), (uint64_t)h * d, os_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
+            const void *ah = attn_cols(att.ptr(), (uint64_t)h * (uint64_t)ldatt, att_elt); // (row h of att)
+            double *const s64 = pb.d_attn_s.get();
+            double *const yh64 = y_scratch ? pb.d_attn_y.get() : y64.ptr((uint64_t)h * edges);
+            hipLaunchKernelGGL(k_gatv2_seg, dim3((unsigned)seg_wgs), dim3(BLOCK), 0, c->stream, segs, n_l, ids, gh, ldgs, oh, ldos, ah, (uint32_t)d, lg, types, slope, s64);
+            softmax_launch<double>(c, w, s64, 1.0, by_col ? nullptr : y32.ptr((uint64_t)h * edges), yh64);
+            const PropSide sd{side.h_ptr.data(), (int)nc, ids, nullptr, nullptr, false, yh64, true, nullptr};
+            const PropGeom g = prop_geom((uint64_t)(uintptr_t)vh, ldv, dv, v_elt, widths, PROP_NWIDTHS);
+            float *const oh32 = o32.ptr((uint64_t)h * dv);
+            double *const oh64 = o64.ptr((uint64_t)h * dv);
+            prop_launch_chunks(c, plan, segs, side.d_at_recs.get(), sd, v_type, g, vh, ldv, dv, nullptr, oh32, o32.ld(), oh64, o64.ld(), false);
+            hipLaunchKernelGGL(k_attn_nan_rows, nan_grid, dim3(BLOCK), 0, c->stream, lrows, side.at_lrows, (const double *)yh64, (uint32_t)dv, oh32, o32.ld(), oh64, o64.ld());
+            if (by_col && (y32.ptr() || y64.ptr()))
+                hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, side.at_lrows, pos, (const double *)yh64, y32.ptr((uint64_t)h * edges),
+                                   y64.ptr((uint64_t)h * edges));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(&nan_pairs, pb.d_smax_nan.get(), sizeof(nan_pairs), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = held_fetch(c, o32, o64, y32, y64)) return rc;
+    if (int rc = held_call_end(c, "subgraph gatv2")) return rc;
+    if (info_out) { info_out[0] = (int64_t)edges; info_out[1] = (int64_t)side.at_short; info_out[2] = (int64_t)side.at_lrows; info_out[3] = (int64_t)nan_pairs; info_out[4] = built_now ? 1 : 0; }
+    if (ms_out) { ms_out[0] = c->tm.sub_gatv2_short_ms; ms_out[1] = c->tm.sub_gatv2_long_ms; }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_gatv2(fora_ctx *c, const void *xl, int xl_type, int64_t ldxl, const void *xr, int xr_type, int64_t ldxr, const void *att, int att_type, int64_t ldatt,
+                            const void *v, int v_type, int64_t ldv, int d, int dv, int heads, double slope, int flags, float *out32, double *out64, int64_t ldo,
+                            float *y32, double *y64, uint64_t ycap, int64_t *info_out, double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph gatv2: ";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(xl_type) || !elt_known(xr_type) || !elt_known(att_type) || !elt_known(v_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (d < 1 || dv < 1 || heads < 1) return fail(c, FORA_E_ARG, who + "d, dv or heads below 1");
+    if ((int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, who + "heads * d or heads * dv above 65536");
+    if (ldxl < (int64_t)heads * d || ldxr < (int64_t)heads * d || ldatt < d || ldv < (int64_t)heads * dv || ldo < (int64_t)heads * dv)
+        return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(slope)) return fail(c, FORA_E_ARG, who + "slope is not finite");
+    if (!out32 && !out64) return fail(c, FORA_E_ARG, who + "no output");
+    if ((y32 || y64) && ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    if (c->sp.cols && c->sb.edges && (!xl || !xr || !att || !v)) return fail(c, FORA_E_ARG, who + "null operand");
+    if (info_out) { memset(info_out, 0, 5 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool by_col = (flags & FORA_SUB_BY_COL) != 0; // by column the group's operand is xr and the gathered one xl
+    const int rc = by_col ? subgraph_gatv2_impl(c, xr, xr_type, ldxr, xl, xl_type, ldxl, att, att_type, ldatt, v, v_type, ldv, d, dv, heads, slope, true, out32, out64, ldo, y32, y64, info_out, ms_out)
+                          : subgraph_gatv2_impl(c, xl, xl_type, ldxl, xr, xr_type, ldxr, att, att_type, ldatt, v, v_type, ldv, d, dv, heads, slope, false, out32, out64, ldo, y32, y64, info_out, ms_out);
     return drop_pairs_unless_ok(c, rc);
 }
 

@@ -537,6 +537,86 @@ def subgraph_gat(engine, el, er, V, heads=1, slope=0.2, direction="out"):
     return _SubgraphGat.apply(el, er, V, engine, float(slope), heads, direction == "in")
 
 
+class _SubgraphGatv2(torch.autograd.Function):
+    """out = GATv2 attention over the held subgraph in one call (Engine.subgraph_gatv2), y32 saved; the backward pass with the
+    existing calls on it -- dV = the opposite product with y[h] as values, dy = subgraph_sddmm of (G, V) -- (V, G) inwards -- and
+    ds = subgraph_softmax_bwd for all heads at once -- and from ds in plain torch on the edge index, head by head, so that the
+    intermediate stays [edges, d]"""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, V, engine, slope, heads, inwards):
+        out32, _, y32, _, _ = engine.subgraph_gatv2(xl.detach(), xr.detach(), att.detach(), V.detach(), heads=heads, slope=slope, by="col" if inwards else "row",
+                                                    want32=True, want64=False, want_y32=True)
+        ctx.save_for_backward(xl, xr, att, V, y32)
+        ctx.engine, ctx.slope, ctx.heads, ctx.inwards = engine, slope, heads, inwards
+        ctx.generation = engine.get_option("sparse_generation")
+        return out32
+
+    @staticmethod
+    def backward(ctx, G):
+        xl, xr, att, V, y32 = ctx.saved_tensors
+        engine, heads, slope, inwards = ctx.engine, ctx.heads, ctx.slope, ctx.inwards
+        _held_guard(ctx.generation, engine, "subgraph_gatv2")
+        need_l, need_r, need_a, need_v = ctx.needs_input_grad[:4]
+        G = _dense_operand(G)
+        d, dv = xl.shape[1] // heads, V.shape[1] // heads
+        f32 = lambda X: X.detach().to(torch.float32)
+        dxl, dxr, datt, dV = (torch.zeros(X.shape, dtype=torch.float32, device=X.device) if need else None
+                              for X, need in ((xl, need_l), (xr, need_r), (att, need_a), (V, need_v)))
+        if need_v:
+            across = engine.subgraph_propagate if inwards else engine.subgraph_propagate_t
+            for h in range(heads):
+                vs = slice(h * dv, (h + 1) * dv)
+                across(G[:, vs], values=y32[h], want64=False, out32=dV[:, vs])
+        if need_l or need_r or need_a:
+            Vd = V.detach()
+            dy, _, _ = engine.subgraph_sddmm(Vd, G, heads=heads) if inwards else engine.subgraph_sddmm(G, Vd, heads=heads)
+            ds, _, _ = engine.subgraph_softmax_bwd(y32, dy, scale=1.0, by="col" if inwards else "row")
+            # the edge index in the order of sub_col, from the transposition: entry p of column u is edge in_pos[p] of row in_row[p]
+            in_ptr, in_row, in_pos = engine.subgraph_transpose_fetch(device=True)
+            rows, cols = torch.empty_like(in_pos), torch.empty_like(in_pos)
+            rows[in_pos] = in_row.to(torch.int64)
+            cols[in_pos] = torch.repeat_interleave(torch.arange(in_ptr.numel() - 1, device=in_ptr.device), in_ptr[1:] - in_ptr[:-1])
+            xl32, xr32, att32 = f32(xl), f32(xr), f32(att)
+            for h in range(heads):
+                hs = slice(h * d, (h + 1) * d)
+                u = xl32[rows, hs] + xr32[cols, hs]
+                dsh = ds[h].unsqueeze(1)
+                if need_a:
+                    datt[h] = (dsh * torch.nn.functional.leaky_relu(u, slope)).sum(0)
+                if need_l or need_r:
+                    du = dsh * att32[h] * torch.where(u >= 0, 1.0, slope)
+                    if need_l:
+                        dxl[:, hs].index_add_(0, rows, du)
+                    if need_r:
+                        dxr[:, hs].index_add_(0, cols, du)
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dxl, xl), cast(dxr, xr), cast(datt, att), cast(dV, V), None, None, None, None
+
+
+def subgraph_gatv2(engine, xl, xr, att, V, heads=1, slope=0.2, direction="out"):
+    """A GATv2 layer over the sampled graph with the forward pass in ONE library call (Engine.subgraph_gatv2, the EDGE GATV2
+    contract): the score of edge e is sum_c att[h, c] * LeakyReLU(xl[row of e, h d + c] + xr[sub_col[e], h d + c]) with the
+    negative slope `slope`, per head -- xl = lin_l(x) and xr = lin_r(x) of a GATv2Conv layer; they may be one tensor.
+    direction="out": node j attends over its out-edges, out[j] = sum over the edges e of row j of y[e] * V[sub_col[e]];
+    direction="in": node v over its in-edges, out[v] = sum over the edges e with sub_col[e] == v of y[e] * V[row of e]; y the
+    softmax of the scores over the node's edges.  xl, xr: [nc, heads * d], att: [heads, d], V: [nc, heads * dv], float32,
+    bfloat16 or float16 tensors on the engine's GPU (FP8 as constants).  Returns float32 [nc, heads * dv], differentiable in xl,
+    xr, att and V.  The forward pass has the contract's bits.  The backward pass is composed: the gradients of V, of the
+    probabilities and of the scores come from the existing calls on the float32 probabilities the forward call saved, and the
+    gradients of xl, xr and att from them in plain torch (index_add over the edge index, float32) -- this half defines no bits.
+    The subgraph must still be held when it runs."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_gatv2: direction is "out" or "in"')
+    if heads < 1 or xl.dim() != 2 or xr.dim() != 2 or V.dim() != 2 or xl.shape[1] % heads or V.shape[1] % heads or xr.shape[1] != xl.shape[1]:
+        raise ValueError("subgraph_gatv2: heads must be at least 1 and divide the columns of xl, xr and V, and xl and xr be as wide")
+    if att.dim() != 2 or tuple(att.shape) != (heads, xl.shape[1] // heads):
+        raise ValueError("subgraph_gatv2: att must be [heads, d]")
+    _refuse_fp8_grad("subgraph_gatv2", xl=xl, xr=xr, att=att, V=V)
+    return _SubgraphGatv2.apply(xl, xr, att, V, engine, float(slope), heads, direction == "in")
+
+
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
     the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32, bfloat16 or float16 tensors (or constant FP8 ones) on the engine's GPU with a column
