@@ -308,6 +308,14 @@ int  fora_hip_subgraph_gatv2(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, i
 ABI_EDGE_GATV2 = _rows(_ABI_EDGE_GATV2)
 EDGE_GATV2_SYMBOLS = list(ABI_EDGE_GATV2)
 
+# the entry point of include/fora_hip_edge_gatv2_bwd.h, the backward pass of GATv2 attention over the held subgraph: an eleventh
+# table (the censuses of the ten headers above are pinned); tests/test_subgraph_gatv2_bwd_cpu.py derives it from that header again
+_ABI_EDGE_GATV2_BWD = """
+int  fora_hip_subgraph_gatv2_bwd(ctx*, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, int64, ptr, int, uint64, int, int, int, double, int, attn_grads*, ptr, ptr, int64, ptr, ptr)
+"""
+ABI_EDGE_GATV2_BWD = _rows(_ABI_EDGE_GATV2_BWD)
+EDGE_GATV2_BWD_SYMBOLS = list(ABI_EDGE_GATV2_BWD)
+
 
 PROP_SEG = 256  # FORA_PROP_SEG
 PROP_F32, PROP_BF16, PROP_F64 = 0, 1, 2  # (PROP_F64: the values of the *_vals calls only)
@@ -345,7 +353,7 @@ _LIBS = {}
 def _bind(lib):
     """restype and argtypes of every row of the ABI the library exports; a symbol it lacks (a test entry point in the
     product library, a newer call in an older build under FORA_HIP_LIB) stays unbound and raises AttributeError on use"""
-    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()) + list(ABI_POOL.items()) + list(ABI_EDGE_GATV2.items()):
+    for name, (_, restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_GNN.items()) + list(ABI_EDGE.items()) + list(ABI_EDGE_SOFTMAX.items()) + list(ABI_EDGE_ATTENTION.items()) + list(ABI_EDGE_ATTENTION_BWD.items()) + list(ABI_EDGE_GAT.items()) + list(ABI_POOL.items()) + list(ABI_EDGE_GATV2.items()) + list(ABI_EDGE_GATV2_BWD.items()):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -1085,6 +1093,57 @@ class Engine:
         shaped = lambda y: y if y is None else y.reshape(heads, edges)
         return out32, out64, shaped(y32), shaped(y64), {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]),
                                                          "nan_pairs": int(info[3]), "built": int(info[4]), "short_ms": ms[0], "long_ms": ms[1]}
+
+    def subgraph_gatv2_bwd(self, xl, xr, att, V, G, y, heads=1, slope=0.2, by="row", want_dxl=True, want_dxr=True, want_datt=True, want_dv=True, want32=True,
+                           want64=False, xl_kind=False, xr_kind=False, att_kind=False, v_kind=False, g_kind=False):
+        """The gradients of subgraph_gatv2 with respect to xl, xr, att and V for all heads in ONE call (fora_hip_subgraph_gatv2_bwd,
+        the EDGE GATV2, BACKWARD contract of include/fora_hip_edge_gatv2_bwd.h): dy, ds and dV as subgraph_gat_bwd has them, then
+        through the score in float64 -- u = xl[row] + xr[col] again, du = ds * (att or att * slope by the sign of u) summed over
+        each node's edges on either side in the order of subgraph_propagate / subgraph_propagate_t, ds * LeakyReLU(u) summed over
+        all edges in tiles of 256 groups -- every bit defined, no atomics.  xl, xr, att, V, heads, slope, by: the forward call's;
+        G: [nc, heads * dv]; y: [heads, edges] float32 or float64, the probabilities it returned.  All operands torch tensors on
+        the context's GPU, or all numpy arrays.  A gradient that is not wanted is not computed.  Returns (dxl32, dxl64, dxr32,
+        dxr64, datt32, datt64, dv32, dv64, stats dict): dxl and dxr [nc, heads * d], datt [heads, d], dv [nc, heads * dv], None
+        where not wanted; the stats are subgraph_gat_bwd's."""
+        nc, edges = self.held_cols, self.get_option("sub_edges")
+        if edges < 0:
+            raise ForaError(-1, "subgraph_gatv2_bwd: no subgraph is held (sparse_subgraph first)")
+        if by not in ("row", "col"):
+            raise ValueError('subgraph_gatv2_bwd: by is "row" or "col"')
+        heads = int(heads)
+        wide = "[nc, heads * d] (xl, xr) or [nc, heads * dv] (nc: the held columns)"
+        x_l, x_r, v, g = (self._prop_feat(x, kind, rows=nc, name=name, shape=wide)
+                          for name, x, kind in (("xl", xl, xl_kind), ("xr", xr, xr_kind), ("V", V, v_kind), ("G", G, g_kind)))
+        if heads < 1 or x_l[2] % heads or x_r[2] != x_l[2] or v[2] % heads or g[2] != v[2]:
+            raise ValueError("subgraph_gatv2_bwd: xl and xr must be as wide, heads (at least 1) divide their columns and those of V, and G be as wide as V")
+        d, dv = x_l[2] // heads, v[2] // heads
+        a = self._prop_feat(att, att_kind, rows=heads, name="att", shape="[heads, d]")
+        if a[2] != d:
+            raise ValueError("subgraph_gatv2_bwd: att must be [heads, d]")
+        ops = (x_l, x_r, a, v, g)
+        devs = [o[4] for o in ops] + [self._is_torch(y)]
+        on_dev = any(devs)
+        if on_dev and not all(devs):
+            raise ValueError("xl, xr, att, V, G and y: all torch tensors on the GPU, or all numpy arrays")
+        yptr, ytype, _, _, _ky = self._edge_operand(y, edges, "y")
+        if y.shape[0] != heads:
+            raise ValueError("y must be [heads, edges]")
+        gr, outs, ptrs = AttnGrads(), [], {}
+        for name, rows, w, want in (("dq", nc, heads * d, want_dxl), ("dk", nc, heads * d, want_dxr), ("datt", heads, d, want_datt), ("dv", nc, heads * dv, want_dv)):
+            o32, o64, p32, p64, ld = self._prop_outputs(rows, w, on_dev, want32, want64, None, None) if want else (None, None, None, None, w)
+            ptrs[name] = (p32, p64, ld)
+            outs += [o32, o64]
+        for name in ("dq", "dk", "dv"):
+            p32, p64, ld = ptrs[name]
+            setattr(gr, name + "32", p32.value if p32 is not None else None)
+            setattr(gr, name + "64", p64.value if p64 is not None else None)
+            setattr(gr, "ld" + name, ld)
+        info, ms = (C.c_int64 * 6)(), (C.c_double * 2)()
+        args = [x for o in ops for x in (o[0], o[1], o[3])]
+        self._chk(self._lib.fora_hip_subgraph_gatv2_bwd(self._ctx, *args, yptr, ytype, heads * edges, d, dv, heads, float(slope), SUB_BY_COL if by == "col" else 0,
+                                                        C.byref(gr), *ptrs["datt"], info, ms))
+        return (*outs, {"edges": int(info[0]), "short_groups": int(info[1]), "long_groups": int(info[2]), "across_short": int(info[3]),
+                        "across_long": int(info[4]), "built": int(info[5]), "short_ms": ms[0], "long_ms": ms[1]})
 
     def subgraph_degrees(self, transposed=False, device=False):
         """The number of edges of every row of the held subgraph (transposed: of every column; this builds the transposition

@@ -28,9 +28,11 @@
 #include "fora_subgraph_attn_bwd.h"
 #include "fora_subgraph_gat.h"
 #include "fora_subgraph_gatv2.h"
+#include "fora_subgraph_gatv2_bwd.h"
 #include "fora_subgraph_pool.h"
 #include "../../include/fora_hip_edge_gat.h"
 #include "../../include/fora_hip_edge_gatv2.h"
+#include "../../include/fora_hip_edge_gatv2_bwd.h"
 #include "../../include/fora_hip_pool.h"
 
 #include <algorithm>
@@ -382,6 +384,8 @@ struct PropBufs {
     DevBuf<double> d_smax; DevBuf<uint32_t> d_smax_nan;  // ROW SOFTMAX: [2][long segments] segment maxima and sums; [1] the rows written as NaN
     DevBuf<double> d_attn_s, d_attn_y;                   // ATTENTION: [entries] the scores (BACKWARD: dy) and the y of the longer rows, one head at a time
     DevBuf<double> d_attn_ds;                            // ATTENTION, BACKWARD: [heads][entries] ds, written by the row side and read by the column side
+    DevBuf<unsigned char> d_att;                         // EDGE GATV2, BACKWARD: the upload of att (d_g holds g there)
+    DevBuf<double> d_gv2_p, d_gv2_part;                  // EDGE GATV2, BACKWARD: P [nc][heads * d] and its tile sums; the longer groups' partial rows [segments][heads * d]
 };
 // PROPAGATE, TRANSPOSED (fora_hip_sparse_propagate_t, fora_hip_sparse_transpose_fetch): the transposition of the held sparse
 // result, built by the first of the two calls after a result becomes held and kept with it -- it ends wherever the held
@@ -5400,6 +5404,218 @@ int fora_hip_subgraph_gatv2(fora_ctx *c, const void *xl, int xl_type, int64_t ld
     const bool by_col = (flags & FORA_SUB_BY_COL) != 0; // by column the group's operand is xr and the gathered one xl
     const int rc = by_col ? subgraph_gatv2_impl(c, xr, xr_type, ldxr, xl, xl_type, ldxl, att, att_type, ldatt, v, v_type, ldv, d, dv, heads, slope, true, out32, out64, ldo, y32, y64, info_out, ms_out)
                           : subgraph_gatv2_impl(c, xl, xl_type, ldxl, xr, xr_type, ldxr, att, att_type, ldatt, v, v_type, ldv, d, dv, heads, slope, false, out32, out64, ldo, y32, y64, info_out, ms_out);
+    return drop_pairs_unless_ok(c, rc);
+}
+
+// ---- EDGE GATV2, BACKWARD (the contract of include/fora_hip_edge_gatv2_bwd.h; the kernels in fora_subgraph_gatv2_bwd.h): the frame
+// of subgraph_attention_bwd_impl.  gs is the operand read at the ALONG group's node (xl by row, xr by column) and os the one at
+// the other end, so gr.dq* carry d gs, the along sum of du, and gr.dk* d os, the across one.  The groups of at most "attn_short"
+// edges of either side are one wave's (k_sub_gatv2_bwd, k_sub_gatv2_across, k_sub_attn_across for dv); the longer ones get dy and
+// ds head by head through the steps' own kernels, then k_gatv2_bwd_seg and k_gatv2_bwd_join on that side's plan.
+static_assert(GV2_TILE == FORA_GATV2_DATT_TILE, "fora_subgraph_gatv2_bwd.h and include/fora_hip_edge_gatv2_bwd.h name one tile length");
+namespace {
+// nc > 0; the arguments have passed fora_hip_subgraph_gatv2_bwd
+int subgraph_gatv2_bwd_impl(fora_ctx *c, const void *gs_, int gs_type, int64_t ldgs, const void *os_, int os_type, int64_t ldos, const void *att_, int att_type, int64_t ldatt,
+                            const void *v_, int v_type, int64_t ldv, const void *g_, int g_type, int64_t ldg, const void *y_, int y_type, int d, int dv, int heads,
+                            double slope, bool by_col, const fora_attn_grads &gr, float *datt32, double *datt64, int64_t lddatt, int64_t *info_out, double *ms_out) {
+    SubBufs &b = c->sb;
+    PropBufs &pb = c->pr;
+    const uint64_t nc = c->sp.cols, edges = b.edges;
+    const bool y_f64 = y_type == FORA_PROP_F64;
+    const uint32_t gs_elt = elt_bytes(gs_type), os_elt = elt_bytes(os_type), att_elt = elt_bytes(att_type), v_elt = elt_bytes(v_type), g_elt = elt_bytes(g_type), y_elt = y_f64 ? 8 : 4;
+    const uint64_t wx = (uint64_t)heads * (uint64_t)d, wv = (uint64_t)heads * (uint64_t)dv; // columns of xl, xr and their gradients; of v, g and dv
+    const bool want_dg = gr.dq32 || gr.dq64, want_do = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64, want_da = datt32 || datt64;
+    const bool want_x = want_dg || want_do || want_da, want_acc = want_dg || want_da, want_across = want_do || want_dv; // dy and ds; the along sums; the opposite grouping
+    HeldIn gs = HeldIn::matrix(gs_, nc, ldgs, wx, gs_elt), os = HeldIn::matrix(os_, nc, ldos, wx, os_elt), att = HeldIn::matrix(att_, (uint64_t)heads, ldatt, (uint64_t)d, att_elt);
+    HeldIn v = HeldIn::matrix(v_, nc, ldv, wv, v_elt), g = HeldIn::matrix(g_, nc, ldg, wv, g_elt), y = HeldIn::vector(y_, (uint64_t)heads * edges, y_elt);
+    HeldOut<float> dg32{gr.dq32, gr.lddq, nc, wx}, do32{gr.dk32, gr.lddk, nc, wx}, dv32{gr.dv32, gr.lddv, nc, wv}, da32{datt32, lddatt, (uint64_t)heads, (uint64_t)d};
+    HeldOut<double> dg64{gr.dq64, gr.lddq, nc, wx}, do64{gr.dk64, gr.lddk, nc, wx}, dv64{gr.dv64, gr.lddv, nc, wv}, da64{datt64, lddatt, (uint64_t)heads, (uint64_t)d};
+    if (int rc = held_resolve(c, gs, os, att, v, g, y, dg32, dg64, do32, do64, dv32, dv64, da32, da64)) return rc; // (before anything is built)
+    c->tm.sub_gatv2_short_ms = c->tm.sub_gatv2_long_ms = 0;
+    // ---- the two sides.  Without an edge every group of either side is empty: both are the rows, nothing is transposed
+    const bool a_col = by_col && edges, x_col = !by_col && edges;
+    bool built_now = false;
+    if (a_col || (x_col && want_across)) if (int rc = subt_ensure(c, built_now)) return rc;
+    SubProp &sp = b.prop;
+    SubProp::Side &along = a_col ? sp.tr : sp.fwd, &across = x_col ? sp.tr : sp.fwd;
+    if (int rc = sub_side_ptr(c, along)) return rc;
+    if (want_across) if (int rc = sub_side_ptr(c, across)) return rc;
+    // ---- the split, and for dv of the longer across groups the chunks of prop_segs segments, as subgraph_attention_bwd_impl makes them
+    const uint32_t cap = attn_short_cap(c->opt_.attn_short), sm_cap = softmax_short_cap(c->opt_.softmax_short);
+    const uint64_t a_segs = prop_long_segments(along.h_ptr.data(), (int)nc, cap), x_segs = want_across ? prop_long_segments(across.h_ptr.data(), (int)nc, cap) : 0;
+    size_t fr = 0, tot = 0;
+    if ((a_segs || x_segs) && c->opt_.prop_segs <= 0) HIPCHK(c, hipMemGetInfo(&fr, &tot));
+    const uint64_t a_per = prop_chunk_segs(c->opt_.prop_segs, a_segs, (uint64_t)fr, dv), x_per = prop_chunk_segs(c->opt_.prop_segs, x_segs, (uint64_t)fr, dv);
+    // ---- every buffer of the call before the first launch: a call that finds no room has written nothing.  An operand that no
+    // wanted gradient reads is not uploaded
+    if (int rc = sub_side_attn_plan(c, along, cap, a_per, sm_cap)) return rc;
+    if (want_across) if (int rc = sub_side_attn_plan(c, across, cap, x_per, sm_cap)) return rc;
+    const bool a_lng = want_x && along.at_lrows != 0, x_lng = want_across && across.at_lrows != 0;
+    const uint32_t chunks = sga_chunks(heads);
+    const uint64_t wgs = sga_wgs(nc, heads), n_la = along.at_plan.segs.size(), n_lx = want_across ? across.at_plan.segs.size() : 0;
+    const uint64_t tiles = (nc + GV2_TILE - 1) / GV2_TILE, col_wgs = (wx + BLOCK - 1) / BLOCK;
+    const auto seg_wgs = [&](uint64_t n) { return (n * chunks + SGA_WAVES - 1) / SGA_WAVES; };
+    if (wgs > 0x7FFFFFFFull || seg_wgs(std::max(n_la, n_lx)) > 0x7FFFFFFFull) return fail(c, FORA_E_ARG, "subgraph gatv2_bwd: more groups or segments than one launch takes");
+    if (want_x) {
+        if (int rc = gs.stage(c, pb.d_a, "the upload of the group's operand")) return rc;
+        if (int rc = os.stage(c, pb.d_feat, "the upload of the gathered operand")) return rc;
+        if (int rc = att.stage(c, pb.d_att, "the upload of att")) return rc;
+        if (int rc = v.stage(c, pb.d_v, "the upload of v")) return rc;
+    }
+    if (int rc = g.stage(c, pb.d_g, "the upload of g")) return rc;
+    if (int rc = y.stage(c, pb.d_vals, "the upload of y")) return rc;
+    if (a_lng) {
+        if (int rc = prop_ensure(c, pb.d_smax, 2 * (size_t)along.at_sm_long, "the segment sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_attn_s, (size_t)edges, "the dy of the longer groups")) return rc;
+        if (a_col) if (int rc = prop_ensure(c, pb.d_attn_y, (size_t)edges, "the y of the longer groups")) return rc;
+    }
+    if (x_lng && want_dv) {
+        if (int rc = prop_ensure(c, pb.d_part, (size_t)(x_per * (uint64_t)dv), "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_carry, 2 * (size_t)dv, "the partial sums")) return rc;
+        if (int rc = prop_ensure(c, pb.d_scarry, 2, "the partial sums")) return rc;
+    }
+    const bool ds_buf = want_do || a_lng; // (the segments of the longer groups read ds in place)
+    if (ds_buf) if (int rc = prop_ensure(c, pb.d_attn_ds, (size_t)heads * (size_t)edges, "ds")) return rc;
+    if (want_da) if (int rc = prop_ensure(c, pb.d_gv2_p, (size_t)((nc + tiles) * wx), "P and its tile sums")) return rc;
+    const uint64_t a_part = a_lng && want_acc ? n_la * wx * (want_da ? 2 : 1) : 0, x_part = x_lng && want_do ? n_lx * wx : 0; // (one after the other on the stream)
+    if (a_part || x_part) if (int rc = prop_ensure(c, pb.d_gv2_part, (size_t)std::max(a_part, x_part), "the segments' partial rows")) return rc;
+    if (int rc = dg32.reserve(c, pb.d_out32)) return rc;
+    if (int rc = dg64.reserve(c, pb.d_out64)) return rc;
+    if (int rc = do32.reserve(c, pb.d_dk32)) return rc;
+    if (int rc = do64.reserve(c, pb.d_dk64)) return rc;
+    if (int rc = dv32.reserve(c, pb.d_dv32)) return rc;
+    if (int rc = dv64.reserve(c, pb.d_dv64)) return rc;
+    if (int rc = da32.reserve(c, pb.d_y32)) return rc;
+    if (int rc = da64.reserve(c, pb.d_y64)) return rc;
+    const int64_t *a_ptr = a_col ? sp.d_in_ptr.get() : b.d_ptr.get(), *x_ptr = x_col ? sp.d_in_ptr.get() : b.d_ptr.get();
+    const int32_t *a_ids = a_col ? sp.d_in_row.get() : b.d_col.get(), *x_ids = x_col ? sp.d_in_row.get() : b.d_col.get();
+    const int64_t *a_pos = a_col ? sp.d_in_pos.get() : nullptr, *x_pos = x_col ? sp.d_in_pos.get() : nullptr;
+    double *const ds = ds_buf ? pb.d_attn_ds.get() : nullptr, *const pg = want_da ? pb.d_gv2_p.get() : nullptr, *const part = pb.d_gv2_part.get();
+    const uint32_t lgv = prop_group_lg((uint32_t)dv), gv_types = sddmm_types(g_type, v_type); // (the dv columns of dy)
+    const uint32_t a_types = gatv2_types(gs_type, os_type, att_type), x_types = gatv2_types(os_type, gs_type, att_type);
+    const SubAcross xs{across, x_ptr, x_ids, x_pos, x_col, nc, edges, cap, heads};
+    const auto join = [&](const PropSeg *segs, uint64_t n, const int64_t *ptr, const double *part_p, const HeldOut<float> &o32, const HeldOut<double> &o64, double *p) {
+        hipLaunchKernelGGL(k_gatv2_bwd_join, dim3((unsigned)col_wgs, (unsigned)std::min<uint64_t>(n, 65535)), dim3(BLOCK), 0, c->stream, segs, n, ptr, (uint32_t)wx, (const double *)part,
+                           part_p, o32.ptr(), o32.ld(), o64.ptr(), o64.ld(), p);
+    };
+    if (want_x) { // dy and ds of the groups of at most cap edges, all heads; d gs and P of those groups
+        EvSpan ev(c, EV_SUB_GATV2_SHORT);
+        with_elt_pair(g_type, v_type, [&](auto GE, auto VE) {
+            with_bools(a_col, want_da, [&](auto BYCOL, auto WP) {
+                hipLaunchKernelGGL((k_sub_gatv2_bwd<decltype(GE)::value, decltype(VE)::value, decltype(BYCOL)::value, decltype(WP)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream,
+                                   a_ptr, (uint32_t)nc, cap, a_ids, a_pos, (uint32_t)heads, chunks, gs.ptr(), ldgs, os.ptr(), ldos, att.ptr(), ldatt, g.ptr(), ldg, v.ptr(), ldv,
+                                   (uint32_t)d, (uint32_t)dv, lgv, slope, edges, y.ptr(), y_f64, want_do ? ds : nullptr, dg32.ptr(), dg32.ld(), dg64.ptr(), dg64.ld(), pg, a_types,
+                                   gv_types);
+            });
+        });
+    }
+    if (a_lng) { // the longer groups: dy and ds one head at a time, into the ds buffer; then their segments, all heads
+        EvSpan ev(c, EV_SUB_GATV2_LONG);
+        const PropSeg *const segs = along.d_at_segs.get(), *const sm_segs = segs + n_la, *const lrows = sm_segs + along.at_sm_short + along.at_sm_long;
+        const SoftmaxWork w{sm_segs, sm_segs + along.at_sm_short, along.at_sm_short, along.at_sm_long, pb.d_smax.get(), pb.d_smax.get() + along.at_sm_long, nullptr};
+        const dim3 y_grid((unsigned)std::min<uint64_t>((along.at_longest + BLOCK - 1) / BLOCK, 1024), (unsigned)std::min<uint64_t>(along.at_lrows, 65535));
+        for (int h = 0; h < heads; h++) {
+            const void *gh = attn_cols(g.ptr(), (uint64_t)h * dv, g_elt), *vh = attn_cols(v.ptr(), (uint64_t)h * dv, v_elt);
+            const void *yh = (const unsigned char *)y.ptr() + (uint64_t)h * edges * y_elt;
+            double *const dy64 = pb.d_attn_s.get(), *const dsh = ds + (uint64_t)h * edges;
+            with_elt_pair(g_type, v_type, [&](auto A, auto B) { // (the group's row of g against the v rows of its ids, as subgraph_attention_bwd_impl)
+                const uint64_t units = (uint64_t)n_la * SDDMM_UNITS, per_wg = BLOCK / 64;
+                hipLaunchKernelGGL((k_prop_sddmm<A.value, B.value>), dim3((unsigned)((units + per_wg - 1) / per_wg)), dim3(BLOCK), 0, c->stream, segs, (uint64_t)n_la, a_ids, gh, ldg, vh, ldv,
+                                   (uint32_t)dv, lgv, (float *)nullptr, dy64, gv_types);
+            });
+            if (!a_col) {
+                if (y_f64) softmax_bwd_launch<double, double>(c, w, yh, dy64, 1.0, nullptr, dsh);
+                else softmax_bwd_launch<float, double>(c, w, yh, dy64, 1.0, nullptr, dsh);
+            } else {
+                double *const yp = pb.d_attn_y.get();
+                if (y_f64) hipLaunchKernelGGL(k_sub_attn_y_gather<double>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)yh, yp);
+                else hipLaunchKernelGGL(k_sub_attn_y_gather<float>, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const float *)yh, yp);
+                softmax_bwd_launch<double, double>(c, w, yp, dy64, 1.0, nullptr, dy64); // (in place: a lane writes the places it has read, after the sums' launch)
+                hipLaunchKernelGGL(k_sub_attn_y_places, y_grid, dim3(BLOCK), 0, c->stream, lrows, along.at_lrows, a_pos, (const double *)dy64, (float *)nullptr, dsh);
+            }
+        }
+        if (want_acc) {
+            double *const part_p = want_da ? part + n_la * wx : nullptr;
+            with_bools(want_da, false, [&](auto WP, auto) {
+                hipLaunchKernelGGL((k_gatv2_bwd_seg<decltype(WP)::value>), dim3((unsigned)seg_wgs(n_la)), dim3(BLOCK), 0, c->stream, segs, n_la, a_ids, a_pos, (uint32_t)heads, chunks,
+                                   gs.ptr(), ldgs, os.ptr(), ldos, att.ptr(), ldatt, (uint32_t)d, slope, edges, (const double *)ds, part, part_p, a_types);
+            });
+            join(segs, n_la, a_ptr, part_p, dg32, dg64, pg);
+        }
+    }
+    if (want_across) {
+        EvSpan ev(c, EV_SUB_GATV2_SHORT);
+        if (want_do) with_bools(x_col, false, [&](auto BYCOL, auto) { // this side's groups sit at the nodes where os is read
+            hipLaunchKernelGGL((k_sub_gatv2_across<decltype(BYCOL)::value>), dim3((unsigned)wgs), dim3(BLOCK), 0, c->stream, x_ptr, (uint32_t)nc, cap, x_ids, x_pos, (uint32_t)heads,
+                               chunks, os.ptr(), ldos, gs.ptr(), ldgs, att.ptr(), ldatt, (uint32_t)d, slope, edges, (const double *)ds, do32.ptr(), do32.ld(), do64.ptr(), do64.ld(),
+                               x_types);
+        });
+        if (want_dv) sub_across_short(c, xs, y.ptr(), y_f64, g.ptr(), g_type, ldg, dv, dv32, dv64);
+    }
+    if (x_lng) {
+        EvSpan ev(c, EV_SUB_GATV2_LONG);
+        if (want_do) {
+            const PropSeg *const segs = across.d_at_segs.get();
+            hipLaunchKernelGGL(k_gatv2_bwd_seg<false>, dim3((unsigned)seg_wgs(n_lx)), dim3(BLOCK), 0, c->stream, segs, n_lx, x_ids, x_pos, (uint32_t)heads, chunks, os.ptr(), ldos, gs.ptr(),
+                               ldgs, att.ptr(), ldatt, (uint32_t)d, slope, edges, (const double *)ds, part, (double *)nullptr, x_types);
+            join(segs, n_lx, x_ptr, nullptr, do32, do64, nullptr);
+        }
+        if (want_dv) sub_across_long(c, xs, y.ptr(), y_f64, g.ptr(), g_type, ldg, dv, dv32, dv64);
+    }
+    if (want_da) { // the tiles of GV2_TILE groups in parallel, then one pass over the tile sums
+        EvSpan ev(c, EV_SUB_GATV2_SHORT);
+        double *const tsum = pg + nc * wx;
+        hipLaunchKernelGGL(k_gatv2_datt, dim3((unsigned)col_wgs, (unsigned)std::min<uint64_t>(tiles, 65535)), dim3(BLOCK), 0, c->stream, (const double *)pg, nc, (uint64_t)GV2_TILE,
+                           (uint32_t)wx, (uint32_t)wx, wx, (float *)nullptr, (int64_t)wx, tsum, (int64_t)wx);
+        hipLaunchKernelGGL(k_gatv2_datt, dim3((unsigned)col_wgs, 1), dim3(BLOCK), 0, c->stream, (const double *)tsum, tiles, tiles, (uint32_t)wx, (uint32_t)d, (uint64_t)0, da32.ptr(),
+                           da32.ld(), da64.ptr(), da64.ld());
+    }
+    if (int rc = held_fetch(c, dg32, dg64, do32, do64, dv32, dv64, da32, da64)) return rc;
+    if (int rc = held_call_end(c, "subgraph gatv2_bwd")) return rc;
+    if (info_out) {
+        info_out[0] = (int64_t)edges; info_out[1] = (int64_t)along.at_short; info_out[2] = (int64_t)along.at_lrows;
+        info_out[3] = want_across ? (int64_t)across.at_short : 0; info_out[4] = want_across ? (int64_t)across.at_lrows : 0; info_out[5] = built_now ? 1 : 0;
+    }
+    if (ms_out) { ms_out[0] = c->tm.sub_gatv2_short_ms; ms_out[1] = c->tm.sub_gatv2_long_ms; }
+    return FORA_OK;
+}
+} // namespace
+
+int fora_hip_subgraph_gatv2_bwd(fora_ctx *c, const void *xl, int xl_type, int64_t ldxl, const void *xr, int xr_type, int64_t ldxr, const void *att, int att_type, int64_t ldatt,
+                                const void *v, int v_type, int64_t ldv, const void *g, int g_type, int64_t ldg, const void *y, int y_type, uint64_t ycap, int d, int dv,
+                                int heads, double slope, int flags, const fora_attn_grads *grads, float *datt32, double *datt64, int64_t lddatt, int64_t *info_out,
+                                double *ms_out) {
+    if (!c) return FORA_E_ARG;
+    const std::string who = "subgraph gatv2_bwd: ";
+    if (!c->sp.valid || !c->sp.compacted || !c->sb.valid) return fail(c, FORA_E_ARG, who + "no subgraph is held (fora_hip_sparse_subgraph first)");
+    if (!elt_known(xl_type) || !elt_known(xr_type) || !elt_known(att_type) || !elt_known(v_type) || !elt_known(g_type)) return fail(c, FORA_E_ARG, who + "unknown element type");
+    if (y_type != FORA_PROP_F32 && y_type != FORA_PROP_F64) return fail(c, FORA_E_ARG, who + "y_type is neither f32 nor f64");
+    if (d < 1 || dv < 1 || heads < 1) return fail(c, FORA_E_ARG, who + "d, dv or heads below 1");
+    if ((int64_t)heads * d > 65536 || (int64_t)heads * dv > 65536) return fail(c, FORA_E_ARG, who + "heads * d or heads * dv above 65536");
+    if (ldxl < (int64_t)heads * d || ldxr < (int64_t)heads * d || ldatt < d || ldv < (int64_t)heads * dv || ldg < (int64_t)heads * dv)
+        return fail(c, FORA_E_ARG, who + "a leading dimension smaller than its matrix is wide");
+    if (flags & ~FORA_SUB_BY_COL) return fail(c, FORA_E_ARG, who + "unknown flag");
+    if (!std::isfinite(slope)) return fail(c, FORA_E_ARG, who + "slope is not finite");
+    fora_attn_grads gr = grads ? *grads : fora_attn_grads{};
+    const bool want_dl = gr.dq32 || gr.dq64, want_dr = gr.dk32 || gr.dk64, want_dv = gr.dv32 || gr.dv64, want_da = datt32 || datt64;
+    if (!want_dl && !want_dr && !want_dv && !want_da) return fail(c, FORA_E_ARG, who + "no output");
+    if ((want_dl && gr.lddq < (int64_t)heads * d) || (want_dr && gr.lddk < (int64_t)heads * d) || (want_dv && gr.lddv < (int64_t)heads * dv) || (want_da && lddatt < d))
+        return fail(c, FORA_E_ARG, who + "lddq or lddk smaller than heads * d, lddv smaller than heads * dv, or lddatt smaller than d");
+    if (ycap / (uint64_t)heads < c->sb.edges || ycap < (uint64_t)heads * c->sb.edges) return fail(c, FORA_E_ARG, who + "ycap is smaller than heads * edges");
+    const bool e = c->sp.cols && c->sb.edges;
+    if (e && (!xl || !xr || !att || !v || !g || !y)) return fail(c, FORA_E_ARG, who + "null xl, xr, att, v, g or y");
+    if (info_out) { memset(info_out, 0, 6 * sizeof(int64_t)); info_out[0] = (int64_t)c->sb.edges; }
+    if (ms_out) ms_out[0] = ms_out[1] = 0;
+    if (!c->sp.cols) return FORA_OK; // (no output rows: nothing launched)
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!e) xl = xr = att = v = g = y = nullptr;
+    const bool by_col = (flags & FORA_SUB_BY_COL) != 0;
+    // by column the group's operand is xr: d xr is the along sum, d xl the across one
+    if (by_col) { std::swap(gr.dq32, gr.dk32); std::swap(gr.dq64, gr.dk64); std::swap(gr.lddq, gr.lddk); }
+    const int rc = by_col ? subgraph_gatv2_bwd_impl(c, xr, xr_type, ldxr, xl, xl_type, ldxl, att, att_type, ldatt, v, v_type, ldv, g, g_type, ldg, y, y_type, d, dv, heads, slope, true, gr,
+                                                    datt32, datt64, lddatt, info_out, ms_out)
+                          : subgraph_gatv2_bwd_impl(c, xl, xl_type, ldxl, xr, xr_type, ldxr, att, att_type, ldatt, v, v_type, ldv, g, g_type, ldg, y, y_type, d, dv, heads, slope, false, gr,
+                                                    datt32, datt64, lddatt, info_out, ms_out);
     return drop_pairs_unless_ok(c, rc);
 }
 

@@ -617,6 +617,44 @@ def subgraph_gatv2(engine, xl, xr, att, V, heads=1, slope=0.2, direction="out"):
     return _SubgraphGatv2.apply(xl, xr, att, V, engine, float(slope), heads, direction == "in")
 
 
+class _SubgraphGatv2Trained(_SubgraphGatv2):
+    """the same forward pass; the backward pass is ONE call for all heads (Engine.subgraph_gatv2_bwd) on the saved y32, for the
+    gradients autograd asks for: float64 throughout, no atomics, the same bits on every run"""
+
+    @staticmethod
+    def backward(ctx, G):
+        xl, xr, att, V, y32 = ctx.saved_tensors
+        engine = ctx.engine
+        _held_guard(ctx.generation, engine, "subgraph_gatv2_trained")
+        need_l, need_r, need_a, need_v = ctx.needs_input_grad[:4]
+        if not (need_l or need_r or need_a or need_v):
+            return None, None, None, None, None, None, None, None
+        dxl, _, dxr, _, datt, _, dV, _, stats = engine.subgraph_gatv2_bwd(xl.detach(), xr.detach(), att.detach(), V.detach(), _dense_operand(G), y32, heads=ctx.heads,
+                                                                          slope=ctx.slope, by="col" if ctx.inwards else "row", want_dxl=need_l, want_dxr=need_r,
+                                                                          want_datt=need_a, want_dv=need_v, want32=True, want64=False)
+        engine.last_subgraph_gatv2_bwd = stats
+        cast = lambda g, X: g if g is None or X.dtype == torch.float32 else g.to(X.dtype)
+        return cast(dxl, xl), cast(dxr, xr), cast(datt, att), cast(dV, V), None, None, None, None
+
+
+def subgraph_gatv2_trained(engine, xl, xr, att, V, heads=1, slope=0.2, direction="out"):
+    """subgraph_gatv2 with the backward pass in ONE library call as well (Engine.subgraph_gatv2_bwd, the EDGE GATV2, BACKWARD
+    contract): the same forward call and result, the float32 probabilities saved; the backward pass computes only the gradients
+    autograd asks for, for all heads at once, chains them through float64 and adds every sum in a fixed order -- two runs give the
+    same bits, which the composed pass of subgraph_gatv2 cannot promise.  Operands, heads, slope and direction as for
+    subgraph_gatv2.  The subgraph must still be held when the backward pass runs; its stats are left in
+    engine.last_subgraph_gatv2_bwd."""
+    heads = int(heads)
+    if direction not in ("out", "in"):
+        raise ValueError('subgraph_gatv2_trained: direction is "out" or "in"')
+    if heads < 1 or xl.dim() != 2 or xr.dim() != 2 or V.dim() != 2 or xl.shape[1] % heads or V.shape[1] % heads or xr.shape[1] != xl.shape[1]:
+        raise ValueError("subgraph_gatv2_trained: heads must be at least 1 and divide the columns of xl, xr and V, and xl and xr be as wide")
+    if att.dim() != 2 or tuple(att.shape) != (heads, xl.shape[1] // heads):
+        raise ValueError("subgraph_gatv2_trained: att must be [heads, d]")
+    _refuse_fp8_grad("subgraph_gatv2_trained", xl=xl, xr=xr, att=att, V=V)
+    return _SubgraphGatv2Trained.apply(xl, xr, att, V, engine, float(slope), heads, direction == "in")
+
+
 def ppr_sddmm(engine, row_ptr, A, B):
     """scores[e] = <A[row of e], B[id of e]> for every held entry e of `engine` (Engine.sparse_sddmm), float32 [entries] on
     the device, differentiable in A ([nq, d]) and B ([n, d], n = engine.held_cols), float32, bfloat16 or float16 tensors (or constant FP8 ones) on the engine's GPU with a column
